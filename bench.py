@@ -14,13 +14,18 @@ N GPUs (weak scaling), one process per GPU:
       channel-sharded; per step ONE all-reduce of the noise clip's channel sum (stationary.py:61-64).
   --workload config3: configs[2] (non-stationary), time-sharded like config2 (seam all-gather only).
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel of the step (HIP events around
-every launch, on the launch stream, inside the timed region); `cpu_baseline` times the numpy oracle (a
-port of the reference's CPU path) on the host cores: 1 core and a process pool over chunks (the
-reference's n_jobs semantics, base.py:206-216).  Extra keys (outside the timed region, N = 1 only):
-`other_configs` (configs[2], configs[4] forward / forward+backward, the PCIe-inclusive numpy->numpy
-rate), `parity` (the engine's result of this run against the oracle on one chunk), and at N > 1
-`distributed` (world size, backend, per-step collective time, per-rank oracle spot check, halo check).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the headline
+(`value`, `ms_per_step`, ...); at N > 1 the line also carries `distributed` (world size, backend, per-step
+collective time, per-rank oracle spot check, halo check).  `--dump-outputs DIR` writes the last timed
+step's output (a fixed, seeded sample of it) to DIR as float32 .npy files.
+
+`--full` adds everything else, all of it outside the timed steps except the roofline's events:
+`roofline` for the dominant kernel of the step (untimed per-stage survey passes, then HIP events around
+that kernel on every E-th timed step), the per-kernel table, GPU clock / power state, and at N = 1
+`cpu_baseline` (the reference -- or the numpy port of its CPU path -- on the host cores: 1 core and a
+process pool over chunks, the reference's n_jobs semantics, base.py:206-216), `other_configs` (configs[2],
+configs[4] forward / forward+backward, other geometries and dtypes, the PCIe-inclusive numpy->numpy rate)
+and `parity` (the engine's result of this run against the oracle on one chunk).
 """
 import argparse
 import json
@@ -62,6 +67,8 @@ VALU_PEAK_TFLOPS = 157.3            # MI355X_MICROARCH.md: float32 vector peak (
 ALGO_FLOPS_PER_SAMPLE = 450         # two 1024-point real transforms per 256-sample hop, smoothing, log / compare / window / overlap-add
 TRAFFIC_DETAIL = "profiles/r06_v7_traffic_detail.json"   # rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes (tools/gpu_traffic.sh), committed
 C4_CHANNELS, C4_SAMPLES = 8, SR * 1800   # configs[3]: one GPU's share
+DUMP_MAX_VALUES = 8 * 1024 * 1024       # --dump-outputs: 32 MB of float32 over all ranks
+DUMP_SEED = 20240601
 
 
 class GpuState:
@@ -169,6 +176,20 @@ def per_stage_ms(gate, fn, reps=4, ev_oh=0.0):
     gate.profile_enable(False)
     gate.profile_select(None)
     return out
+
+
+def dump_output(out, directory, world, rank):
+    """--dump-outputs: the step's output as DIR/output.npy (DIR/output_rank<r>.npy at N > 1), float32, flattened in row-major
+    order.  An output larger than this rank's share of DUMP_MAX_VALUES is sampled at positions drawn from a fixed seed
+    (sorted, repeats possible), so that two builds given the same arguments write the same positions."""
+    flat = out.reshape(-1)
+    cap = DUMP_MAX_VALUES // world
+    if flat.numel() > cap:
+        idx = np.sort(np.random.default_rng(DUMP_SEED + rank).integers(0, flat.numel(), size=cap))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    os.makedirs(directory, exist_ok=True)
+    name = "output.npy" if world == 1 else "output_rank%d.npy" % rank
+    np.save(os.path.join(directory, name), flat.float().cpu().numpy())
 
 
 def synth_on_device(n, seed, device, tone_hz=1000.0, offset=0):
@@ -402,12 +423,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline leg")
     ap.add_argument("--event-every", type=int, default=4,
-                    help="HIP events around the dominant kernel (and a step-boundary event) on every E-th step of the timed "
-                         "region: each event pair is ~6 us of queue time around a 0.25 ms kernel, 4 %% of a step when every "
+                    help="a step-boundary event (and, with --full, HIP events around the dominant kernel) on every E-th step of "
+                         "the timed region: each event pair is ~6 us of queue time around a 0.25 ms kernel, 4 %% of a step when every "
                          "step carries them (1 = every step)")
-    ap.add_argument("--no-extras", action="store_true", help="skip other_configs / parity legs")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the other_configs / parity legs")
     ap.add_argument("--workload", choices=["config2", "config3", "config4"], default="config2")
     ap.add_argument("--nonstationary", action="store_true", help="alias of --workload config3")
     ap.add_argument("--dry-nccl", action="store_true",
@@ -415,7 +436,17 @@ def main():
                          "all_gather_into_tensor + barrier over RCCL; prints one JSON line and exits (no workload)")
     ap.add_argument("--streams", type=int, default=1,
                     help="independent calls in flight on separate HIP streams (serving mode; default 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, per-kernel table, GPU state, cpu_baseline, parity and other_configs legs "
+                         "(a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's output to DIR as float32 .npy (a fixed, seeded "
+                         "sample of at most %d values in all)" % DUMP_MAX_VALUES)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
     if args.nonstationary:
         args.workload = "config3"
 
@@ -450,7 +481,8 @@ def main():
             dist.init_process_group(pg_backend)
 
     global GPU_STATE
-    GPU_STATE = GpuState(dev_index)
+    if args.full or args.dry_nccl:
+        GPU_STATE = GpuState(dev_index)
     if args.dry_nccl:
         return dry_nccl(world, rank, device, pg_backend)
     import __graft_entry__
@@ -564,12 +596,13 @@ def main():
     _gc.freeze()
     GC_PAUSES.clear()
     gate = engine_gate()
-    ev_oh = event_pair_overhead_ms()
-    # untimed survey passes: one stage bracketed by HIP events at a time -> per-kernel table + dominant kernel
-    # (serving mode: steps rotate over the S handles; one survey call = S steps, of which exactly one runs on the profiled handle)
-    survey_fn = step if n_streams == 1 else (lambda: [step() for _ in range(n_streams)])
-    survey = per_stage_ms(gate, survey_fn, reps=4, ev_oh=ev_oh)
-    dom = max(survey, key=lambda k: survey[k][0])
+    if args.full:
+        ev_oh = event_pair_overhead_ms()
+        # untimed survey passes: one stage bracketed by HIP events at a time -> per-kernel table + dominant kernel
+        # (serving mode: steps rotate over the S handles; one survey call = S steps, of which exactly one runs on the profiled handle)
+        survey_fn = step if n_streams == 1 else (lambda: [step() for _ in range(n_streams)])
+        survey = per_stage_ms(gate, survey_fn, reps=4, ev_oh=ev_oh)
+        dom = max(survey, key=lambda k: survey[k][0])
     # untimed settle loop on top of the W warm-up steps, DIRECTLY before the timed region: ~0.1 s of back-to-back steps
     # so that clock / power-state transitions of a GPU that was idle a moment ago happen BEFORE the timed steps.  (Up to
     # round 4 the survey pass and a gc.collect() sat between this loop and the timed region: the queue ran dry for
@@ -609,10 +642,11 @@ def main():
         settle_steps = 20 if wl == "config4" else 200
         for _ in range(settle_steps):
             step()
-    # timed region: HIP events (on the launch stream) only around the dominant kernel, plus one event per
-    # step boundary (median of the per-step times next to the mean)
-    gate.profile_select([dom])
-    gate.profile_enable(False)
+    # timed region: one event per step boundary on every E-th step (median of the per-step times next to the mean);
+    # --full: HIP events (on the launch stream) around the dominant kernel on those steps too
+    if args.full:
+        gate.profile_select([dom])
+        gate.profile_enable(False)
     # (events on every E-th step only: the kernel's average duration over those launches is the roofline's; the steps
     # between run as a caller's would, without instrumentation in the queue)
     E = max(1, args.event_every) * n_streams
@@ -633,7 +667,8 @@ def main():
         on = i % E == 0
         if on and marks:
             marks[i].record()
-        gate.profile_enable(on)          # a host flag of the handle: no queue traffic
+        if args.full:
+            gate.profile_enable(on)      # a host flag of the handle: no queue traffic
         th0 = time.perf_counter()
         out = step()
         host_ms.append((time.perf_counter() - th0) * 1e3)
@@ -645,9 +680,12 @@ def main():
     elapsed_local = elapsed
     for o in ts_objs + ([tsn] if tsn is not None else []):
         o.finish()          # the deferred verdict on the last step's shard layout (outside the timed region)
-    profs = [gate.profile_read(reset=True)]
-    gate.profile_enable(False)
-    gate.profile_select(None)
+    if args.dump_outputs:
+        dump_output(out, args.dump_outputs, world, rank)
+    if args.full:
+        profs = [gate.profile_read(reset=True)]
+        gate.profile_enable(False)
+        gate.profile_select(None)
     # per-step times between consecutive step-boundary events (E steps apart: their mean)
     per_step = None
     if marks:
@@ -761,29 +799,6 @@ def main():
     if rank == 0:
         total = float(samples_per_gpu) * world * args.steps
         value = total / elapsed / 1e6
-        # dominant kernel over the timed region
-        agg = {}
-        for p in profs:
-            for k, (ms, cnt) in p.items():
-                a = agg.setdefault(k, [0.0, 0])
-                a[0] += ms
-                a[1] += cnt
-        avg_ms = agg[dom][0] / agg[dom][1]
-        # the event pairs live in the handle of stream 0: it ran every n_streams-th step
-        steps_profiled = len(sampled)
-        launches_per_step = agg[dom][1] / steps_profiled
-        algo_bytes = ALGO_BYTES_PER_SAMPLE * samples_per_gpu / launches_per_step
-        achieved = algo_bytes / (avg_ms * 1e-3) / 1e9
-        traffic = None
-        tp = os.path.join(ROOT, "profiles", "traffic.json")
-        traffic_src = None
-        if wl == "config2" and os.path.exists(tp):
-            try:
-                traffic = json.load(open(tp)).get(dom)
-                traffic_src = ("profiles/traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
-                               "workload (FETCH_SIZE x2 corrected), committed -- NOT measured in this run")
-            except Exception:
-                traffic = None
         desc = {"config2": "configs[1]: synthetic 48 kHz mono 10 min per GPU, stationary reduce_noise",
                 "config3": "configs[2]: synthetic 48 kHz mono 10 min per GPU, non-stationary reduce_noise",
                 "config4": "configs[3]: synthetic 48 kHz, 8 channels x 30 min per GPU (64 channels on 8 GPUs), "
@@ -803,53 +818,79 @@ def main():
                        "calls_in_flight": n_streams,
                        **({"gate_form": "one ticket-drawn tile per workgroup (SG_OPT_TILE_ORDER 2: serving mode)"}
                           if n_streams > 1 and wl == "config2" else {})},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
-                         "traffic_source": traffic_src,
-                         "avg_launch_ms": round(avg_ms, 4), "algorithmic_bytes_per_launch": int(algo_bytes),
-                         "events": "HIP events around this kernel on every %d-th step of the timed region (%d launches)"
-                                   % (E, agg[dom][1]),
-                         "whole_step_frac": round(value * 1e6 / world * ALGO_BYTES_PER_SAMPLE / 1e9
-                                                  / HBM_PEAK_GBS, 5),
-                         # the binding resource of this kernel is the float32 vector pipe, not HBM:
-                         "valu": {"achieved": round(ALGO_FLOPS_PER_SAMPLE * samples_per_gpu / launches_per_step / (avg_ms * 1e-3) / 1e12, 2),
-                                  "peak": VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
-                                  "frac": round(ALGO_FLOPS_PER_SAMPLE * samples_per_gpu / launches_per_step / (avg_ms * 1e-3) / 1e12
-                                                / VALU_PEAK_TFLOPS, 4),
-                                  "basis": "algorithmic flops (%d per sample, SURVEY.md 8(d)) / dominant-kernel time"
-                                           % ALGO_FLOPS_PER_SAMPLE}},
-            # per-kernel table of the untimed SURVEY passes (per_stage_ms: one stage bracketed at a time, 4 steps each).
-            # `raw` is what the events say; an empty event pair already measures `event_pair_overhead_ms`, which
-            # `kernel_ms_per_step` has subtracted per launch -- so the kernels of a step add up to no more than the step
-            "kernel_ms_per_step": {k: round(v[0], 4) for k, v in sorted(survey.items(), key=lambda kv: -kv[1][0])},
-            "kernel_ms_per_step_raw": {k: round(v[2], 4) for k, v in sorted(survey.items(), key=lambda kv: -kv[1][0])},
-            "kernel_launches_per_step": {k: v[1] for k, v in sorted(survey.items(), key=lambda kv: -kv[1][0])},
-            "event_pair_overhead_ms": round(ev_oh, 5),
         }
-        line["kernel_ms_sum"] = round(sum(line["kernel_ms_per_step"].values()), 4)
-        line["kernel_ms_sum_le_step"] = bool(line["kernel_ms_sum"] <= line["ms_per_step"])
-        line["kernel_ms_note"] = ("event-bracketed kernel times (one stage at a time, empty-pair time subtracted) still include the "
-                                  "launch / drain bubble a kernel has when events fence it (~3-5 % of a 0.25 ms kernel: the gate reads "
-                                  "0.262-0.265 ms here, 0.252 ms in rocprofv3's kernel trace, profiles/); back to back in a step the bubbles "
-                                  "overlap, so the sum may exceed ms_per_step by a few percent.  The roofline uses the dominant kernel's "
-                                  "time from the TIMED region; rocprofv3 averages are committed under profiles/")
-        line["roofline"]["avg_launch_ms_corrected"] = round(max(0.0, avg_ms - ev_oh), 4)
-        if wl == "config3":
-            # four kernels of comparable weight share this call's work (k_mag_fast, k_iir_chain_par, k_iir_mask, k_apply_fast):
-            # whole-call algorithmic bytes over ONE of them would flatter it 3-4 x.  `frac` / `achieved`
-            # are the WHOLE CALL's; the dominant kernel's own launch time stays in avg_launch_ms
-            rl = line["roofline"]
-            rl["dominant_kernel_only"] = {"achieved": rl["achieved"], "frac": rl["frac"],
-                                          "note": "whole-call bytes / this one kernel's time: NOT a roofline fraction of the call"}
-            whole = value * 1e6 / world * ALGO_BYTES_PER_SAMPLE / 1e9
-            rl["achieved"], rl["frac"] = round(whole, 2), round(whole / HBM_PEAK_GBS, 5)
-            rl["basis"] = "whole call: algorithmic bytes of a step / ms_per_step (several kernels of comparable weight per call)"
-            rl["valu"]["frac"] = round(ALGO_FLOPS_PER_SAMPLE * value * 1e6 / world / 1e12 / VALU_PEAK_TFLOPS, 4)
-            rl["valu"]["achieved"] = round(ALGO_FLOPS_PER_SAMPLE * value * 1e6 / world / 1e12, 2)
-            rl["valu"]["basis"] = "algorithmic flops (%d per sample) / whole step" % ALGO_FLOPS_PER_SAMPLE
-        line["gpu_state"] = {"before_settle": state_before_settle, "before_timed": state_before, "after_timed": state_after,
-                             "source": "librocm_smi64 in-process (sclk / mclk of the current DPM level, socket power, cap, "
-                                       "junction temperature); read outside the timed region's events, microseconds each"}
+        if args.full:
+            # dominant kernel over the timed region
+            agg = {}
+            for p in profs:
+                for k, (ms, cnt) in p.items():
+                    a = agg.setdefault(k, [0.0, 0])
+                    a[0] += ms
+                    a[1] += cnt
+            avg_ms = agg[dom][0] / agg[dom][1]
+            # the event pairs live in the handle of stream 0: it ran every n_streams-th step
+            steps_profiled = len(sampled)
+            launches_per_step = agg[dom][1] / steps_profiled
+            algo_bytes = ALGO_BYTES_PER_SAMPLE * samples_per_gpu / launches_per_step
+            achieved = algo_bytes / (avg_ms * 1e-3) / 1e9
+            traffic = None
+            tp = os.path.join(ROOT, "profiles", "traffic.json")
+            traffic_src = None
+            if wl == "config2" and os.path.exists(tp):
+                try:
+                    traffic = json.load(open(tp)).get(dom)
+                    traffic_src = ("profiles/traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
+                                   "workload (FETCH_SIZE x2 corrected), committed -- NOT measured in this run")
+                except Exception:
+                    traffic = None
+            line.update({
+                "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
+                             "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
+                             "traffic_source": traffic_src,
+                             "avg_launch_ms": round(avg_ms, 4), "algorithmic_bytes_per_launch": int(algo_bytes),
+                             "events": "HIP events around this kernel on every %d-th step of the timed region (%d launches)"
+                                       % (E, agg[dom][1]),
+                             "whole_step_frac": round(value * 1e6 / world * ALGO_BYTES_PER_SAMPLE / 1e9
+                                                      / HBM_PEAK_GBS, 5),
+                             # the binding resource of this kernel is the float32 vector pipe, not HBM:
+                             "valu": {"achieved": round(ALGO_FLOPS_PER_SAMPLE * samples_per_gpu / launches_per_step / (avg_ms * 1e-3) / 1e12, 2),
+                                      "peak": VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                      "frac": round(ALGO_FLOPS_PER_SAMPLE * samples_per_gpu / launches_per_step / (avg_ms * 1e-3) / 1e12
+                                                    / VALU_PEAK_TFLOPS, 4),
+                                      "basis": "algorithmic flops (%d per sample, SURVEY.md 8(d)) / dominant-kernel time"
+                                               % ALGO_FLOPS_PER_SAMPLE}},
+                # per-kernel table of the untimed SURVEY passes (per_stage_ms: one stage bracketed at a time, 4 steps each).
+                # `raw` is what the events say; an empty event pair already measures `event_pair_overhead_ms`, which
+                # `kernel_ms_per_step` has subtracted per launch -- so the kernels of a step add up to no more than the step
+                "kernel_ms_per_step": {k: round(v[0], 4) for k, v in sorted(survey.items(), key=lambda kv: -kv[1][0])},
+                "kernel_ms_per_step_raw": {k: round(v[2], 4) for k, v in sorted(survey.items(), key=lambda kv: -kv[1][0])},
+                "kernel_launches_per_step": {k: v[1] for k, v in sorted(survey.items(), key=lambda kv: -kv[1][0])},
+                "event_pair_overhead_ms": round(ev_oh, 5),
+            })
+            line["kernel_ms_sum"] = round(sum(line["kernel_ms_per_step"].values()), 4)
+            line["kernel_ms_sum_le_step"] = bool(line["kernel_ms_sum"] <= line["ms_per_step"])
+            line["kernel_ms_note"] = ("event-bracketed kernel times (one stage at a time, empty-pair time subtracted) still include the "
+                                      "launch / drain bubble a kernel has when events fence it (~3-5 % of a 0.25 ms kernel: the gate reads "
+                                      "0.262-0.265 ms here, 0.252 ms in rocprofv3's kernel trace, profiles/); back to back in a step the bubbles "
+                                      "overlap, so the sum may exceed ms_per_step by a few percent.  The roofline uses the dominant kernel's "
+                                      "time from the TIMED region; rocprofv3 averages are committed under profiles/")
+            line["roofline"]["avg_launch_ms_corrected"] = round(max(0.0, avg_ms - ev_oh), 4)
+            if wl == "config3":
+                # four kernels of comparable weight share this call's work (k_mag_fast, k_iir_chain_par, k_iir_mask, k_apply_fast):
+                # whole-call algorithmic bytes over ONE of them would flatter it 3-4 x.  `frac` / `achieved`
+                # are the WHOLE CALL's; the dominant kernel's own launch time stays in avg_launch_ms
+                rl = line["roofline"]
+                rl["dominant_kernel_only"] = {"achieved": rl["achieved"], "frac": rl["frac"],
+                                              "note": "whole-call bytes / this one kernel's time: NOT a roofline fraction of the call"}
+                whole = value * 1e6 / world * ALGO_BYTES_PER_SAMPLE / 1e9
+                rl["achieved"], rl["frac"] = round(whole, 2), round(whole / HBM_PEAK_GBS, 5)
+                rl["basis"] = "whole call: algorithmic bytes of a step / ms_per_step (several kernels of comparable weight per call)"
+                rl["valu"]["frac"] = round(ALGO_FLOPS_PER_SAMPLE * value * 1e6 / world / 1e12 / VALU_PEAK_TFLOPS, 4)
+                rl["valu"]["achieved"] = round(ALGO_FLOPS_PER_SAMPLE * value * 1e6 / world / 1e12, 2)
+                rl["valu"]["basis"] = "algorithmic flops (%d per sample) / whole step" % ALGO_FLOPS_PER_SAMPLE
+            line["gpu_state"] = {"before_settle": state_before_settle, "before_timed": state_before, "after_timed": state_after,
+                                 "source": "librocm_smi64 in-process (sclk / mclk of the current DPM level, socket power, cap, "
+                                           "junction temperature); read outside the timed region's events, microseconds each"}
         line["settle"] = {"steps": settle_steps, "ms_per_step_blocks": settle_blocks,
                           "rule": "N = 1: blocks of ~60 ms of steps until two consecutive blocks agree within 0.5 % (cap 1.2 s), then 50 "
                                   "steps to refill the queue; N > 1: fixed count (every rank must run the same collectives)"}
@@ -864,13 +905,13 @@ def main():
             line["host_enqueue_ms_per_step"] = [round(t, 4) for t in host_ms]
         if distributed:
             line["distributed"] = distributed
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             line.update(extras(device, wl, out, y2d, gate, O))
         line["settle_steps_untimed"] = settle_steps
         line["host_gc"] = {"pauses_over_1ms": [(g_, round(ms_, 2)) for g_, ms_ in GC_PAUSES if ms_ > 1.0],
                            "note": "CPython collector pauses on the enqueueing thread since the warm-up (generation, ms); "
                                    "objects alive after the warm-up are frozen (gc.freeze)"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line))
     if world > 1:

@@ -60,6 +60,37 @@ def test_full_size_config3_nonstationary(nr):
         assert O.rel_err(o1[ich * 600000:(ich + 1) * 600000], ref) < TOL, ich
 
 
+def test_bench_plain_run_dumps_the_timed_output(nr, tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: one JSON line with the headline fields and no --full legs,
+    K timed steps, and DIR/output.npy = the seeded sample of the last step's output -- the same samples reduce_noise gives
+    for the same recording in this process."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--dump-outputs", str(tmp_path)]
+    pr = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
+    assert pr.returncode == 0, pr.stderr[-2000:]
+    lines = [ln for ln in pr.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, pr.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1
+    assert d["unit"] == "Msamples/s" and d["higher_is_better"] is True and d["dtype"] == "f32" and d["ms_per_step"] > 0
+    assert abs(d["value"] - bench.N_PER_GPU / (d["ms_per_step"] * 1e-3) / 1e6) <= 0.01 * d["value"]
+    assert not {"roofline", "kernel_ms_per_step", "cpu_baseline", "other_configs", "parity", "gpu_state"} & set(d)
+    assert sorted(os.listdir(tmp_path)) == ["output.npy"]
+    got = np.load(tmp_path / "output.npy")
+    assert got.dtype == np.float32 and got.shape == (bench.DUMP_MAX_VALUES,) and got.nbytes <= 64 << 20
+    y = bench.synth_on_device(bench.N_PER_GPU, 1234, torch.device("cuda", 0))
+    out = nr.reduce_noise(y=y, sr=48000, stationary=True).cpu().numpy()
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, out.size, size=bench.DUMP_MAX_VALUES))
+    assert O.rel_err(got, out[idx]) < 1e-6
+
+
 def test_config4_one_gpu_share(nr):
     """One GPU's share of BASELINE.json configs[3]: 8 channels x 30 min @ 48 kHz, stationary (the
     64-channel recording is channel-sharded 8 per GPU).  1152 (channel, chunk) units; the oracle on

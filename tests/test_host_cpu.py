@@ -134,7 +134,7 @@ def test_header_is_plain_c_and_c_example_links(tmp_path):
 
 
 def test_committed_bench_line_has_the_contract_fields():
-    """The bench line committed under profiles/ (produced by `python bench.py` on an MI355X) carries every
+    """The bench line committed under profiles/ (produced by `python bench.py --full` on an MI355X) carries every
     field of the driver's contract, incl. the roofline and cpu_baseline objects."""
     import glob
     import json

@@ -174,7 +174,7 @@ def test_bench_two_ranks_end_to_end_over_gloo(workload):
     env.pop("RANK", None)
     steps = "2"
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", steps, "--warmup", "1",
-           "--no-cpu-baseline", "--workload", workload]
+           "--full", "--no-cpu-baseline", "--workload", workload]
     pr = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert pr.returncode == 0, pr.stderr[-2000:]
     lines = [ln for ln in pr.stdout.splitlines() if ln.startswith("{")]

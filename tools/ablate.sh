@@ -1,7 +1,7 @@
 #!/bin/bash
 # Build k_apply_fast ablation variants (SG_ABLATE bit mask, fastpath.hpp) into noisereduce_amd/_ab/
 # usage: tools/ablate.sh "0 1 2 4 8 16"   (here, cross-compiling);  then on the GPU box:
-#        for f in noisereduce_amd/_ab/*.so; do SG_LIB_PATH=$PWD/$f python bench.py --steps 30 --no-cpu-baseline; done
+#        for f in noisereduce_amd/_ab/*.so; do SG_LIB_PATH=$PWD/$f python bench.py --full --steps 30 --no-cpu-baseline; done
 set -e
 cd "$(dirname "$0")/.."
 mkdir -p noisereduce_amd/_ab

@@ -2,7 +2,7 @@
 # On the GPU box: time every build under noisereduce_amd/_ab/ with bench.py, print the kernel table.
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 for f in noisereduce_amd/_ab/*.so; do
-  SG_LIB_PATH=$PWD/$f python bench.py --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | python3 -c "
+  SG_LIB_PATH=$PWD/$f python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=d['kernel_ms_per_step']

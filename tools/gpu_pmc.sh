@@ -8,7 +8,7 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/pmc_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-CMD=${PMC_CMD:-"python $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline $*"}
+CMD=${PMC_CMD:-"python $REPO/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline $*"}
 rocprofv3 --kernel-trace --pmc $CTRS -d "$OUT" -o "$TAG" --output-format csv -- $CMD > "$OUT/bench.json" 2> "$OUT/bench.err"
 F=$(find "$OUT" -name '*counter_collection.csv' | head -1)
 if [ -n "$F" ]; then

@@ -8,7 +8,7 @@ OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats -d "$OUT" -o "$TAG" --output-format csv -- \
-  python "$REPO/bench.py" --steps 5 --warmup 2 --no-cpu-baseline "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
+  python "$REPO/bench.py" --full --steps 5 --warmup 2 --no-cpu-baseline "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
 find "$OUT" -name '*kernel_stats.csv' | head -3
 F=$(find "$OUT" -name '*kernel_stats.csv' | head -1)
 [ -n "$F" ] && head -30 "$F"

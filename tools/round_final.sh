@@ -10,9 +10,9 @@ mkdir -p "$OUT"
 cd "$REPO"
 python -c "import __graft_entry__ as g; g.build()" > "$OUT/build.log" 2>&1
 (python -m pytest tests -m gpu -q 2>&1 | tail -5) > "$OUT/pytest_gpu.txt"
-python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
-python bench.py --workload config3 --no-cpu-baseline > "$OUT/bench_config3.json" 2>> "$OUT/bench.err"
-python bench.py --workload config4 --no-cpu-baseline --steps 10 --warmup 3 > "$OUT/bench_config4.json" 2>> "$OUT/bench.err"
+python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
+python bench.py --full --workload config3 --no-cpu-baseline > "$OUT/bench_config3.json" 2>> "$OUT/bench.err"
+python bench.py --full --workload config4 --no-cpu-baseline --steps 10 --warmup 3 > "$OUT/bench_config4.json" 2>> "$OUT/bench.err"
 tools/gpu_profile.sh ${TAG}k --no-extras > "$OUT/prof.log" 2>&1
 tools/gpu_profile.sh ${TAG}k3 --no-extras --workload config3 > "$OUT/prof3.log" 2>&1
 tools/gpu_traffic.sh > "$OUT/traffic.log" 2>&1
