@@ -151,6 +151,46 @@ SG_API int sg_filter_padded(sg_handle* h, const void* chunk_dev, int in_dtype, v
                      int out_dtype, int64_t C, int64_t Lp, int64_t in_stride,
                      int64_t out_stride, void* stream);
 
+/* ---- variant S: ragged batches of recordings --------------------------------------------- */
+/* Many recordings of different lengths and channel counts in one call, each gated exactly as reduce_noise gates it
+ * alone (noisereduce.py:13-185 -> base.py:167-226 per recording).  x_dev holds every recording's channels (sample type
+ * in_dtype); out_dev receives every recording's output (out_dtype). */
+typedef struct sg_clip {   /* one recording of the batch */
+  int64_t x_offset;        /* element offset of channel 0 in x_dev; channel c at x_offset + c * x_stride */
+  int64_t n;               /* samples per channel */
+  int64_t x_stride;        /* elements between channels */
+  int32_t channels;
+  int32_t noise;           /* stationary gate: index into the noise table (ignored by the non-stationary gate) */
+  int64_t out_offset;      /* element offset of channel 0 in out_dev */
+  int64_t out_stride;      /* elements between output channels */
+} sg_clip;
+typedef struct sg_noise_src {   /* one noise clip (stationary.py:47-64: the caller applies clip_noise_stationary to n) */
+  int64_t offset;          /* element offset of channel 0 */
+  int64_t n;               /* samples per channel, >= win_length */
+  int64_t stride;          /* elements between channels */
+  int32_t channels;        /* the statistics read the channel mean (stationary.py:61) */
+  int32_t in_x;            /* 1: the samples live in x_dev (sample type in_dtype), 0: in noise_dev (noise_dtype) */
+} sg_noise_src;
+/* Bytes of HBM workspace sg_process_clips needs to process all clips in ONE sub-batch (tables and fields, for the
+ * handle's chunk_size / padding and the noise sources the clips use; host arithmetic only).  It is the figure
+ * sg_process_clips compares with its budget: max_workspace_bytes >= the result runs the clips as one sub-batch, a smaller
+ * budget splits them (clips in order, each sub-batch as large as fits; a clip that alone exceeds the budget is a sub-batch
+ * of its own).  The handle keeps the largest workspace it has used until sg_destroy; a stationary call also keeps
+ * n_noise * round_up(n_fft / 2 + 1, 16) doubles of thresholds (sg_debug_clip_thresholds). */
+SG_API int sg_clips_workspace_bytes(const sg_handle* h, const sg_noise_src* noise, int32_t n_noise, const sg_clip* clips,
+                                    int64_t n_clips, int64_t* bytes);
+/* Replaces a loop of SpectralGate.get_traces calls (base.py:167-226) over n_clips recordings.  Every recording is cut into
+ * the reference's units -- one unit [-padding, n + padding) when n <= chunk_size (or chunk_size == 0, meaning None:
+ * base.py:222), else ceil(n / chunk_size) windows of chunk_size + 2 padding samples (base.py:152-156,175-216) -- and every
+ * unit is gated on its own frame count: stationary gate with the threshold of its clip's noise source (stationary.py:47-127,
+ * thresholds computed here from the noise table), non-stationary gate with the recurrence over the unit's frames
+ * (nonstationary.py:47-115).  Kept samples are written to out_dev; nothing else is.  Clips are independent: a recording's
+ * output does not depend on the other clips, their order or the sub-batch split.  max_workspace_bytes: sub-batch budget
+ * (0: 4 GiB).  chunk_size / padding / window / smoothing come from the handle (variant S only).  Enqueues only. */
+SG_API int sg_process_clips(sg_handle* h, const void* x_dev, int in_dtype, const void* noise_dev, int noise_dtype,
+                            const sg_noise_src* noise, int32_t n_noise, const sg_clip* clips, int64_t n_clips,
+                            void* out_dev, int out_dtype, int64_t max_workspace_bytes, void* stream);
+
 /* ---- variant T -------------------------------------------------------------------- */
 
 /* Replaces TorchGate.forward(x, xn) (torchgate.py:200-264): x (B, L) -> out

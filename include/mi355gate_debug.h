@@ -34,6 +34,12 @@ SG_API int sg_debug_range(const sg_handle* h, int64_t range[2]);
 SG_API int sg_debug_counter(sg_handle* h, int32_t which, int64_t* value, void* stream);
 SG_API int sg_debug_fetch(sg_handle* h, int32_t what, void* host, int64_t bytes, void* stream);
 
+/* Per-noise-source thresholds in dB of the last sg_process_clips call, [n_noise][n_bins] float64 (stationary gate;
+ * stationary.py:79-81 for each source).  Synchronises. */
+SG_API int sg_debug_clip_thresholds(sg_handle* h, double* host, int32_t n_noise, int32_t n_bins, void* stream);
+/* Sub-batches the last sg_process_clips call was split into. */
+SG_API int sg_debug_clip_batches(const sg_handle* h, int64_t* value);
+
 /* ---- development options (sg_set_option / sg_get_option of mi355gate.h) ----------------- */
 #define SG_OPT_FORCE_UNFUSED 1 /* value != 0: use the materialised (v1) kernels everywhere */
 #define SG_OPT_FORCE_F64_DECIDE 3 /* value != 0: decide every mask cell from a float64 STFT */
@@ -93,7 +99,15 @@ SG_API int sg_debug_fetch(sg_handle* h, int32_t what, void* host, int64_t bytes,
 #define SG_STAGE_ROW_GATE 17   /* k_row_gate: TorchGate.forward of a whole row (<= 64 frames) in one kernel */
 #define SG_STAGE_IIR_CHAIN 18 /* non-stationary gate: carries of the time tiles (k_iir_chain_par; serial form k_iir_part / k_iir_comb + k_iir_chain) */
 #define SG_STAGE_IIR_MASK 19  /* non-stationary gate: k_iir_mask<nt> -- recurrence, sigmoid and both smoothing passes in one kernel */
-#define SG_N_STAGES 20
+/* ragged batches (sg_process_clips, ragged.hip): one launch of each per sub-batch */
+#define SG_STAGE_RG_NOISE_POWER 20 /* stationary: float64 transform of every noise frame */
+#define SG_STAGE_RG_NOISE_FINAL 21 /* stationary: per-source band maxima, moments, thresholds, compare constants */
+#define SG_STAGE_RG_DECIDE 22      /* float64 transform of every data frame: decision bits + band maxima (stationary) / magnitudes */
+#define SG_STAGE_RG_IIR 23         /* non-stationary: one-pole filtfilt over each unit's frames + sigmoid */
+#define SG_STAGE_RG_FSMOOTH 24     /* mask smoothing along frequency (with the -top_db floor override, stationary) */
+#define SG_STAGE_RG_APPLY 25       /* smoothing along time + masked multiply + inverse transform of every live frame */
+#define SG_STAGE_RG_OLA 26         /* overlap-add of the kept samples */
+#define SG_N_STAGES 27
 /* When enabled, every kernel launch is bracketed by a hipEvent pair recorded on the launch
  * stream.  sg_profile_read synchronises those events and returns accumulated milliseconds
  * and launch counts per stage (arrays of SG_N_STAGES); reset != 0 clears the accumulators. */

@@ -23,7 +23,7 @@ LIB_PATH = os.path.join(_HERE, "libmi355gate.so")
 SG_F32, SG_F64, SG_I16, SG_I32 = 0, 1, 2, 3
 SG_VARIANT_S, SG_VARIANT_T = 0, 1
 SG_E_INVALID, SG_E_UNSUPPORTED, SG_E_HIP, SG_E_NOMEM, SG_E_STATE, SG_E_HANDOFF = -1, -2, -3, -4, -5, -6
-SG_N_STAGES = 20
+SG_N_STAGES = 27
 SG_OPT_FORCE_F64_DECIDE = 3
 SG_OPT_FORCE_NOSEAM = 4
 SG_OPT_FORCE_NOLEAN = 5
@@ -62,6 +62,17 @@ class SgParams(Structure):
     ]
 
 
+class SgClip(Structure):
+    """struct sg_clip (include/mi355gate.h)."""
+    _fields_ = [("x_offset", c_int64), ("n", c_int64), ("x_stride", c_int64), ("channels", c_int32),
+                ("noise", c_int32), ("out_offset", c_int64), ("out_stride", c_int64)]
+
+
+class SgNoiseSrc(Structure):
+    """struct sg_noise_src (include/mi355gate.h)."""
+    _fields_ = [("offset", c_int64), ("n", c_int64), ("stride", c_int64), ("channels", c_int32), ("in_x", c_int32)]
+
+
 # every symbol include/mi355gate.h and include/mi355gate_debug.h declare: name -> (restype, argtypes)
 _PROTOTYPES = {
     "sg_version": (c_int, []),
@@ -87,6 +98,11 @@ _PROTOTYPES = {
     "sg_process_batch_backward": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64,
                                           c_void_p, c_void_p, c_int64, c_void_p]),
     "sg_stft": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
+    "sg_clips_workspace_bytes": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, POINTER(c_int64)]),
+    "sg_process_clips": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int32, c_void_p, c_int64,
+                                 c_void_p, c_int, c_int64, c_void_p]),
+    "sg_debug_clip_thresholds": (c_int, [c_void_p, POINTER(c_double), c_int32, c_int32, c_void_p]),
+    "sg_debug_clip_batches": (c_int, [c_void_p, POINTER(c_int64)]),
     "sg_set_option": (c_int, [c_void_p, c_int32, c_int64]),
     "sg_get_option": (c_int, [c_void_p, c_int32, POINTER(c_int64)]),
     "sg_check_errors": (c_int, [c_void_p, c_void_p]),
@@ -396,6 +412,45 @@ class Gate:
                 self._h, grad_out.data_ptr(), _sg_dtype(grad_out), B, L, gs, mask.data_ptr(),
                 gx.data_ptr(), L, self._stream()))
         return gx
+
+    # -- ragged batches (sg_process_clips) ---------------------------------------------------------
+    def process_clips(self, x, clips, out, noise=None, noise_srcs=(), max_workspace_bytes=0):
+        """x, out: 1-D device tensors holding every clip (offsets / strides in `clips`, a sequence of SgClip);
+        noise: 1-D device tensor or None; noise_srcs: sequence of SgNoiseSrc."""
+        self._on_device(x)
+        self._on_device(out)
+        n_clips = len(clips)
+        carr = (SgClip * max(1, n_clips))(*clips)
+        narr = (SgNoiseSrc * max(1, len(noise_srcs)))(*noise_srcs)
+        if noise is not None:
+            self._on_device(noise)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.sg_process_clips(
+                self._h, x.data_ptr(), _sg_dtype(x), None if noise is None else noise.data_ptr(),
+                SG_F64 if noise is None else _sg_dtype(noise), narr, len(noise_srcs), carr, n_clips, out.data_ptr(),
+                _sg_dtype(out), int(max_workspace_bytes), self._stream()))
+        return out
+
+    def clips_workspace_bytes(self, clips, noise_srcs=()):
+        """Workspace bytes process_clips needs for `clips` in one sub-batch (what max_workspace_bytes is compared with)."""
+        carr = (SgClip * max(1, len(clips)))(*clips)
+        narr = (SgNoiseSrc * max(1, len(noise_srcs)))(*noise_srcs)
+        out = c_int64()
+        self._check(self.lib.sg_clips_workspace_bytes(self._h, narr, len(noise_srcs), carr, len(clips), byref(out)))
+        return out.value
+
+    def clip_thresholds(self, n_noise):
+        """(n_noise, F) float64 thresholds of the last process_clips call (synchronises)."""
+        out = np.empty((int(n_noise), self.n_bins), dtype=np.float64)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.sg_debug_clip_thresholds(self._h, out.ctypes.data_as(POINTER(c_double)), int(n_noise),
+                                                          self.n_bins, self._stream()))
+        return out
+
+    def clip_batches(self):
+        v = c_int64()
+        self._check(self.lib.sg_debug_clip_batches(self._h, byref(v)))
+        return int(v.value)
 
     def set_option(self, option, value):
         self._check(self.lib.sg_set_option(self._h, int(option), int(value)))

@@ -39,6 +39,7 @@
 #include "big.hpp"
 #include "exact.hpp"
 #include "apply64.hpp"
+#include "ragged.hpp"
 
 // complex transform length from which a whole 256-thread workgroup (instead of one wavefront) works on ONE frame in
 // the general LDS kernels: at N = 2048 (n_fft = 4096) a wavefront holds 4 radix-8 butterflies = 64 complex values per
@@ -199,6 +200,7 @@ struct sg_handle {
   std::vector<hipEvent_t> prof_pool;
   double prof_ms[SG_N_STAGES] = {0};
   int64_t prof_cnt[SG_N_STAGES] = {0};
+  sg::RgState* rg = nullptr;        // ragged batches (sg_process_clips, ragged.hip): workspace and threshold tap
   std::string err;
 };
 
@@ -1312,6 +1314,7 @@ extern "C" int sg_destroy(sg_handle* h) {
                     &h->czt_bh64, &h->czt_tw32, &h->czt_ch32, &h->czt_bh32, &h->logtab, &h->big_twM, &h->big_tw2,
                     &h->big_ch, &h->big_bh, &h->big_W, &h->big_W2, &h->xP, &h->xraw, &h->xM, &h->xtmp, &h->xseg, &h->invn5, &h->invn25, &h->invn20, &h->rg_count, &h->alim, &h->nss, &h->mr_pt32, &h->mr_pt64, &h->o5tab, &h->o25tab, &h->o20tab})
     free_buf(*b);
+  sg::rg_free(h->rg);
   delete h;
   return SG_OK;
 }
@@ -3800,7 +3803,14 @@ extern "C" const char* sg_stage_name(int32_t stage) {
                                            "k_gate_onepass (fft+decide+smooth+mask+ifft+ola)",
                                            "k_row_gate (fft+row stats+decide+smooth+mask+ifft+ola)",
                                            "k_iir_chain_par (tile carries; serial: k_iir_part / k_iir_comb + k_iir_chain)",
-                                           "k_iir_mask<nt> (recurrence+sigmoid+smoothing)"};
+                                           "k_iir_mask<nt> (recurrence+sigmoid+smoothing)",
+                                           "k_rg_noise_power (clips: noise transform)",
+                                           "k_rg_noise_final (clips: thresholds)",
+                                           "k_rg_decide (clips: transform + bits / magnitudes)",
+                                           "k_rg_iir (clips: recurrence + sigmoid)",
+                                           "k_rg_fsmooth (clips: frequency smoothing)",
+                                           "k_rg_apply (clips: time smoothing + mask + inverse transform)",
+                                           "k_rg_ola (clips: overlap-add)"};
   return (stage >= 0 && stage < SG_N_STAGES) ? names[stage] : "?";
 }
 
@@ -3950,5 +3960,59 @@ extern "C" int sg_debug_fetch(sg_handle* h, int32_t what, void* host, int64_t by
     return SG_OK;
   }
   HIPCHK(h, hipMemcpy(host, src, need, hipMemcpyDeviceToHost));
+  return SG_OK;
+}
+
+// ---- ragged batches: thin wrappers over ragged.hip ------------------------------------------------------------------
+static void* rg_prof_begin(void* ctx, int stage, hipStream_t st) { return new ProfScope((sg_handle*)ctx, stage, st); }
+static void rg_prof_end(void* tok) { delete (ProfScope*)tok; }
+
+static sg::RgCtx rg_ctx(sg_handle* h) {
+  sg::RgCtx c{};
+  c.n = h->n; c.N = h->N; c.W = h->W; c.H = h->H; c.F = h->F; c.FS = h->FS; c.padL = h->padL;
+  c.mag_scale = h->mag_scale; c.tw64 = h->tw64.p; c.wfull64 = (const double*)h->wfull64.p;
+  c.stationary = h->p.stationary; c.cs = h->p.chunk_size; c.pad = h->p.padding;
+  c.nf = h->p.smooth_mask ? h->p.n_grad_freq : 0;
+  c.nt = h->p.smooth_mask ? h->p.n_grad_time : 0;
+  c.prop = h->p.prop_decrease; c.top_db = h->p.top_db; c.n_std = h->p.n_std_thresh; c.iir_b = h->p.iir_b;
+  c.nthresh = h->p.nonstat_thresh; c.slope = h->p.nonstat_slope; c.ddof = h->p.ddof;
+  c.hook_ctx = h; c.prof_begin = rg_prof_begin; c.prof_end = rg_prof_end;
+  return c;
+}
+
+static bool rg_variant_ok(sg_handle* h) {
+  if (h->p.variant != SG_VARIANT_S) { h->err = "sg_process_clips is a variant-S entry point"; return false; }
+  return true;
+}
+
+extern "C" int sg_clips_workspace_bytes(const sg_handle* h, const sg_noise_src* noise, int32_t n_noise, const sg_clip* clips,
+                                        int64_t n_clips, int64_t* bytes) {
+  if (!h || !bytes || n_clips < 0 || (n_clips > 0 && !clips) || n_noise < 0 || (n_noise > 0 && !noise)) return SG_E_INVALID;
+  sg_handle* hm = const_cast<sg_handle*>(h);
+  if (!rg_variant_ok(hm)) return SG_E_INVALID;
+  return sg::rg_workspace_bytes(rg_ctx(hm), noise, n_noise, clips, n_clips, bytes, &hm->err);
+}
+
+extern "C" int sg_process_clips(sg_handle* h, const void* x_dev, int in_dtype, const void* noise_dev, int noise_dtype,
+                                const sg_noise_src* noise, int32_t n_noise, const sg_clip* clips, int64_t n_clips,
+                                void* out_dev, int out_dtype, int64_t max_workspace_bytes, void* stream) {
+  if (!h) return SG_E_INVALID;
+  if (!rg_variant_ok(h)) return SG_E_INVALID;
+  if (n_clips < 0 || (n_clips > 0 && (!clips || !x_dev || !out_dev)) || !dtype_ok(in_dtype) || !dtype_ok(out_dtype) ||
+      n_noise < 0 || (n_noise > 0 && !noise) || (h->p.stationary && n_noise > 0 && !dtype_ok(noise_dtype) && noise_dev))
+    FAIL(h, SG_E_INVALID, "sg_process_clips: bad argument");
+  if (n_clips == 0) return SG_OK;
+  return sg::rg_process(&h->rg, rg_ctx(h), x_dev, in_dtype, noise_dev, noise_dtype, noise, n_noise, clips, n_clips, out_dev,
+                        out_dtype, max_workspace_bytes, (hipStream_t)stream, &h->err);
+}
+
+extern "C" int sg_debug_clip_thresholds(sg_handle* h, double* host, int32_t n_noise, int32_t n_bins, void* stream) {
+  if (!h || !host || n_bins != h->F) return SG_E_INVALID;
+  return sg::rg_thresholds(h->rg, host, n_noise, n_bins, (hipStream_t)stream, &h->err);
+}
+
+extern "C" int sg_debug_clip_batches(const sg_handle* h, int64_t* value) {
+  if (!h || !value) return SG_E_INVALID;
+  *value = sg::rg_last_batches(h->rg);
   return SG_OK;
 }
