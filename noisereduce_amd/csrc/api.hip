@@ -101,6 +101,7 @@ std::string fmt(const char* f, ...) {
 }
 }  // namespace
 
+struct RegGeom;
 struct sg_handle {
   sg_params p{};
   int n = 0, N = 0, W = 0, H = 0, F = 0, FS = 0, padL = 0;
@@ -119,7 +120,7 @@ struct sg_handle {
   bool t2_ready = false;             // T2 / alim hold the compare constants of the CURRENT threshold (any writer of thresh clears it)
   DevBuf logtab;                     // db_fast (kernels.hpp): {rd(1 / c_i), -log2 of it} for 128 mantissa centres
   DevBuf part;                       // partial reductions of the column statistics
-  DevBuf tw512, invn;                // fast path tables (n_fft = 1024, hop = 256)
+  DevBuf tw512, invn;                // fast path tables (n_fft = 1024, hop = 256; 512 / 256 / 2048, hop = n_fft / 4): invn = 1 / window envelope per hop phase
   DevBuf seam;                       // partial seam hops of abutting apply tiles
   DevBuf ftab;                       // k_smooth_bits2 phase-1 lookup tables (nf <= 5)
   int sm2_tt = 64;                   // k_smooth_bits2 tile height (frames)
@@ -165,17 +166,12 @@ struct sg_handle {
   bool mr_ok = false;                // n_fft even, n_fft / 2 <= 2048 with prime factors <= 13, not a power of two: the float32 and
   MrPlan mr{};                       // float64 STFT / decision / apply kernels of mixed.hpp (run-time radix schedule) instead of chirp-z
   DevBuf mr_pt32, mr_pt64;           // the plan's per-pass twiddle tables (mr_pass_tables)
-  DevBuf o5tab, o25tab, o20tab;      // k_gate_onepass512 / 256 / 2048: MFMA operands + byte expansion (onepass512.hpp, onepass256.hpp, onepass2048.hpp)
+  DevBuf regtab;                     // k_gate_onepass512 / 256 / 2048: MFMA operands + byte expansion (onepass512.hpp, onepass256.hpp, onepass2048.hpp)
   DevBuf czt_tw64, czt_ch64, czt_bh64, czt_tw32, czt_ch32, czt_bh32;
   bool force_noseam = false;
   bool force_nolean = false;         // SG_OPT_FORCE_NOLEAN: full-size slices + stored frames (2 waves/SIMD)
   bool fast_ok = false;              // default geometry: fused apply kernel available
-  bool fast5_ok = false;             // n_fft = win = 512, hop = 128: register-transform kernels of fast512.hpp
-  DevBuf invn5;                      // 1 / window envelope per hop phase (128) of that geometry
-  bool fast25_ok = false;            // n_fft = win = 256, hop = 64: register-transform kernels of fast256.hpp (round 5)
-  DevBuf invn25;                     // 1 / window envelope per hop phase (64)
-  bool fast20_ok = false;            // n_fft = win = 2048, hop = 512: register-transform kernels of fast2048.hpp
-  DevBuf invn20;                     // 1 / window envelope per hop phase (512)
+  const RegGeom* reg = nullptr;      // n_fft = win = 512 / 256 / 2048, hop = n_fft / 4: register-transform kernels (reg_geom)
   bool force_nofast = false;
   bool force_f64_decide = false;     // SG_OPT_FORCE_F64_DECIDE: float64 STFT for every mask decision
   int64_t ktot = 1;                  // (nf+1)^2 (nt+1)^2: integer weight total of the smoothing filter
@@ -203,6 +199,68 @@ struct sg_handle {
   sg::RgState* rg = nullptr;        // ragged batches (sg_process_clips, ragged.hip): workspace and threshold tap
   std::string err;
 };
+
+// Register geometries: n_fft = win = 512 / 256 / 2048, hop = n_fft / 4 (fast512.hpp, fast256.hpp, fast2048.hpp and the
+// one-pass gates of onepass512.hpp, onepass256.hpp, onepass2048.hpp).  One descriptor per geometry holds its constants and
+// its kernels; sg_create stores the handle's (sg_handle::reg) and every stage of these geometries reads it.
+
+// geometry constants of the one-pass gate of a register geometry
+struct OnePassSmall {
+  int hop, NF, NH, tile_words, xw, max_nf, max_nt, F;
+  size_t lds;
+  int extra = 0;   // abutting tiles (NH == NF): the last tile must reach 3 hops past the range (its leading partials)
+};
+
+struct RegGeom {
+  int n_fft, hop;
+  int frames;                 // frames per decide / magnitude tile and per abutting apply tile
+  int hops;                   // complete hops per overlapping apply tile (frames - 3)
+  size_t lds;                 // dynamic LDS of the decide / magnitude / apply kernels
+  DevBuf sg_handle::*tw;      // twiddle table (RegArgs::tw): tw512, or tw32 at n_fft = 2048
+  OnePassSmall op, op_seam;   // one-pass gate on overlapping tiles (SG_OPT_FORCE_NOSEAM) / abutting tiles + k_ola_seam
+  bool abut;                  // the one-pass gate needs abutting tiles (2048: op_seam only)
+  int tab_kb;                 // k-blocks of time weights in the gate's MFMA table (sg_create; 2048 lays its table out apart)
+  void (*decide[2])(fast::RegArgs);        // <4, false>, <4, true>: REDO (the units whose floor test fired)
+  void (*mag)(fast::RegArgs);
+  void (*apply[2])(fast::RegArgs);         // <4, false>: float mask, <4, true>: uint16 weight sums in K
+  void (*gate[2])(fast::OnePassRegArgs);   // <4, false>, <4, true>: REDO
+  void (*seam)(fast::SeamArgs);            // k_ola_seam<hop, frames>
+};
+
+constexpr size_t FAST5_LDS = (size_t)(fast::FN + 4 * fast::WAVE_CX_H) * sizeof(fast::cf) + (512 + 264) * sizeof(float);
+constexpr size_t FAST25_LDS = (size_t)(fast::FN + 4 * fast::WAVE_CX_H) * sizeof(fast::cf) + (256 + fast::F25_T2) * sizeof(float);
+constexpr size_t FAST20_LDS = (size_t)(1024 + 4 * fast::WAVE_CX_H) * sizeof(fast::cf) + 1028 * sizeof(float);
+
+// n_fft = 512: the 512-point complex transform of the default geometry carries two real frames
+static const RegGeom REG512{
+    512, 128, 32, 29, FAST5_LDS, &sg_handle::tw512,
+    {128, fast::O5_NF, fast::O5_NH, fast::O5_TILE_WORDS, fast::O5_XW, fast::O5_MAX_NF, fast::O5_MAX_NT, 257, FAST5_LDS + 16 + 2048},
+    {128, fast::O5_NF, fast::O5_NF, fast::O5_TILE_WORDS, fast::O5_XW, fast::O5_MAX_NF, fast::O5_MAX_NT, 257, FAST5_LDS + 16 + 2048, 3},
+    false, 2,
+    {fast::k_decide_fast512<4, false>, fast::k_decide_fast512<4, true>}, fast::k_mag_fast512<4>,
+    {fast::k_apply_fast512<4, false>, fast::k_apply_fast512<4, true>},
+    {fast::k_gate_onepass512<4, false>, fast::k_gate_onepass512<4, true>}, fast::k_ola_seam<128, 32>};
+// n_fft = 256 (round 5): the same transform carries four real frames
+static const RegGeom REG256{
+    256, 64, 64, 61, FAST25_LDS, &sg_handle::tw512,
+    {64, fast::O25_NF, fast::O25_NH, fast::O25_TILE_WORDS, fast::O25_XW, fast::O25_MAX_NF, fast::O25_MAX_NT, 129, FAST25_LDS + 16 + 2048},
+    {64, fast::O25_NF, fast::O25_NF, fast::O25_TILE_WORDS, fast::O25_XW, fast::O25_MAX_NF, fast::O25_MAX_NT, 129, FAST25_LDS + 16 + 2048, 3},
+    false, 3,
+    {fast::k_decide_fast256<4, false>, fast::k_decide_fast256<4, true>}, fast::k_mag_fast256<4>,
+    {fast::k_apply_fast256<4, false>, fast::k_apply_fast256<4, true>},
+    {fast::k_gate_onepass256<4, false>, fast::k_gate_onepass256<4, true>}, fast::k_ola_seam<64, 64>};
+// n_fft = 2048: one real frame per 32 lanes (1024-point transform); the one-pass gate's tiles always abut
+static const RegGeom REG2048{
+    2048, 512, 8, 5, FAST20_LDS, &sg_handle::tw32,
+    {512, fast::O20_NF, fast::O20_NF, fast::O20_TILE_WORDS, fast::O20_XW, fast::O20_MAX_NF, fast::O20_MAX_NT, 1025, FAST20_LDS + 16 + 2048, 3},
+    {512, fast::O20_NF, fast::O20_NF, fast::O20_TILE_WORDS, fast::O20_XW, fast::O20_MAX_NF, fast::O20_MAX_NT, 1025, FAST20_LDS + 16 + 2048, 3},
+    true, 1,
+    {fast::k_decide_fast2048<4, false>, fast::k_decide_fast2048<4, true>}, fast::k_mag_fast2048<4>,
+    {fast::k_apply_fast2048<4, false>, fast::k_apply_fast2048<4, true>},
+    {fast::k_gate_onepass2048<4, false>, fast::k_gate_onepass2048<4, true>}, fast::k_ola_seam<512, 8>};
+
+// the handle's register geometry, or nullptr (another geometry, or SG_OPT_FORCE_NOFAST)
+static const RegGeom* reg_geom(const sg_handle* h) { return h->force_nofast ? nullptr : h->reg; }
 
 namespace {
 // Optional roctx ranges around every stage's enqueue (SG_ROCTX=1 in the environment at sg_create): the stages show
@@ -1101,73 +1159,43 @@ extern "C" int sg_create(const sg_params* p, const double* window_host, sg_handl
     if (!rc) rc = upload(h, h->kf, kf.data(), kf.size() * sizeof(float));
     if (!rc) rc = upload(h, h->kt, kt.data(), kt.size() * sizeof(float));
   }
-  if (!rc && n == 1024 && W == 1024 && h->H == 256) {
+  // 1 / window envelope per hop phase of the geometries with hop = n_fft / 4 (sum over the 4 frames that overlap a hop)
+  auto upload_invn = [&](int hop) {
+    std::vector<float> invn(hop);
+    for (int s2 = 0; s2 < hop; ++s2) {
+      double acc = 0.0;
+      for (int q = 0; q < 4; ++q) acc += wfull[hop * q + s2] * wfull[hop * q + s2];
+      invn[s2] = (float)(acc > 1e-10 ? 1.0 / acc : 1.0);
+    }
+    return upload(h, h->invn, invn.data(), invn.size() * sizeof(float));
+  };
+  // w_512^j: the 512-point register transform of n_fft = 1024 / 512 / 256 (fastpath.hpp)
+  auto upload_tw512 = [&]() {
     std::vector<cx<float>> t512(512);
     for (int j = 0; j < 512; ++j) {
       long double a = -2.0L * 3.14159265358979323846264338327950288L * (long double)j / 512.0L;
       t512[j] = {(float)cosl(a), (float)sinl(a)};
     }
-    std::vector<float> invn(256);
-    for (int s2 = 0; s2 < 256; ++s2) {
-      double acc = 0.0;
-      for (int q = 0; q < 4; ++q) acc += wfull[256 * q + s2] * wfull[256 * q + s2];
-      invn[s2] = (float)(acc > 1e-10 ? 1.0 / acc : 1.0);
-    }
+    return upload(h, h->tw512, t512.data(), t512.size() * sizeof(cx<float>));
+  };
+  if (!rc && n == 1024 && W == 1024 && h->H == 256) {
     std::vector<double> norm64(256);
     for (int s2 = 0; s2 < 256; ++s2) {
       double acc = 0.0;
       for (int q = 0; q < 4; ++q) acc += wfull[256 * q + s2] * wfull[256 * q + s2];   // frames t-3 .. t in scipy's order
       norm64[s2] = acc;
     }
-    rc = upload(h, h->tw512, t512.data(), t512.size() * sizeof(cx<float>));
-    if (!rc) rc = upload(h, h->invn, invn.data(), invn.size() * sizeof(float));
+    rc = upload_tw512();
+    if (!rc) rc = upload_invn(256);
     if (!rc) rc = upload(h, h->norm64, norm64.data(), norm64.size() * sizeof(double));
     h->fast_ok = true;
   }
-  if (!rc && n == 512 && W == 512 && h->H == 128) {
-    // fast512.hpp: the 512-point complex transform of the default geometry carries two real frames of 512 samples
-    std::vector<cx<float>> t512(512);
-    for (int j = 0; j < 512; ++j) {
-      long double a = -2.0L * 3.14159265358979323846264338327950288L * (long double)j / 512.0L;
-      t512[j] = {(float)cosl(a), (float)sinl(a)};
+  for (const RegGeom* r : {&REG512, &REG256, &REG2048})
+    if (!rc && n == r->n_fft && W == r->n_fft && h->H == r->hop) {
+      if (r->tw == &sg_handle::tw512) rc = upload_tw512();   // (2048 reads tw32)
+      if (!rc) rc = upload_invn(r->hop);
+      h->reg = r;
     }
-    std::vector<float> invn(128);
-    for (int s2 = 0; s2 < 128; ++s2) {
-      double acc = 0.0;
-      for (int q = 0; q < 4; ++q) acc += wfull[128 * q + s2] * wfull[128 * q + s2];
-      invn[s2] = (float)(acc > 1e-10 ? 1.0 / acc : 1.0);
-    }
-    rc = upload(h, h->tw512, t512.data(), t512.size() * sizeof(cx<float>));
-    if (!rc) rc = upload(h, h->invn5, invn.data(), invn.size() * sizeof(float));
-    h->fast5_ok = true;
-  }
-  if (!rc && n == 256 && W == 256 && h->H == 64) {
-    // fast256.hpp: the same 512-point register transform carries FOUR real frames of 256 samples
-    std::vector<cx<float>> t512(512);
-    for (int j = 0; j < 512; ++j) {
-      long double a = -2.0L * 3.14159265358979323846264338327950288L * (long double)j / 512.0L;
-      t512[j] = {(float)cosl(a), (float)sinl(a)};
-    }
-    std::vector<float> invn(64);
-    for (int s2 = 0; s2 < 64; ++s2) {
-      double acc = 0.0;
-      for (int q = 0; q < 4; ++q) acc += wfull[64 * q + s2] * wfull[64 * q + s2];
-      invn[s2] = (float)(acc > 1e-10 ? 1.0 / acc : 1.0);
-    }
-    rc = upload(h, h->tw512, t512.data(), t512.size() * sizeof(cx<float>));
-    if (!rc) rc = upload(h, h->invn25, invn.data(), invn.size() * sizeof(float));
-    h->fast25_ok = true;
-  }
-  if (!rc && n == 2048 && W == 2048 && h->H == 512) {
-    std::vector<float> invn(512);
-    for (int s2 = 0; s2 < 512; ++s2) {
-      double acc = 0.0;
-      for (int q = 0; q < 4; ++q) acc += wfull[512 * q + s2] * wfull[512 * q + s2];
-      invn[s2] = (float)(acc > 1e-10 ? 1.0 / acc : 1.0);
-    }
-    rc = upload(h, h->invn20, invn.data(), invn.size() * sizeof(float));
-    h->fast20_ok = true;
-  }
   if (!rc && p->smooth_mask && 8 + 2 * p->n_grad_freq <= 18) {
     // counts of 8 adjacent bins f..f+7 from the 18-bit window b[f-nf .. f-nf+17]: two 9-bit tables
     const int nf = p->n_grad_freq;
@@ -1229,67 +1257,37 @@ extern "C" int sg_create(const sg_params* p, const double* window_host, sg_handl
       }
     }
   }
-  if (!rc && h->fast5_ok && p->smooth_mask && p->n_grad_freq <= fast::O5_MAX_NF && p->n_grad_time <= fast::O5_MAX_NT) {
-    // operands of k_gate_onepass512's MFMA smoothing (onepass512.hpp), v_mfma_i32_16x16x32_i8 layout: lane l = (q = l / 16,
-    // j = l % 16) supplies bytes e = 0..7 = k slots 8 q + e of row / column j
+  const RegGeom* rg = h->reg;
+  if (!rc && rg && p->smooth_mask && p->n_grad_freq <= rg->op.max_nf && p->n_grad_time <= rg->op.max_nt) {
+    // operands of the one-pass gate's MFMA smoothing (onepass512.hpp, onepass256.hpp, onepass2048.hpp), v_mfma_i32_16x16x32_i8
+    // layout: lane l = (q = l / 16, j = l % 16) supplies bytes e = 0..7 = k slots 8 q + e of row / column j
     const int nf = p->n_grad_freq, nt = p->n_grad_time;
-    std::vector<unsigned long long> tb(448, 0ull);
-    auto wt = [&](int d) { const int ad = d < 0 ? -d : d; return ad <= nt ? nt + 1 - ad : 0; };
-    for (int l = 0; l < 64; ++l) {
-      const int q = l / 16, j = l % 16;
-      for (int e = 0; e < 8; ++e) {
-        const int a = 8 * q + e - 8 - j, aa = a < 0 ? -a : a;
-        tb[l] |= (unsigned long long)(aa <= nf ? nf + 1 - aa : 0) << (8 * e);
-        // k slot 8 q + e: row 4 q + e of the first block (e < 4) / 16 + 4 q + (e - 4) of the second; output frame j at row nt + j
-        const int r1 = e < 4 ? 4 * q + e : 16 + 4 * q + (e - 4);
-        tb[64 + l] |= (unsigned long long)wt(r1 - nt - j) << (8 * e);
-        tb[128 + l] |= (unsigned long long)wt(32 + r1 - nt - j) << (8 * e);
-      }
-    }
-    for (int v = 0; v < 256; ++v)
-      for (int e = 0; e < 8; ++e) tb[192 + v] |= (unsigned long long)((v >> e) & 1) << (8 * e);
-    rc = upload(h, h->o5tab, tb.data(), tb.size() * 8);
-  }
-  if (!rc && h->fast25_ok && p->smooth_mask && p->n_grad_freq <= fast::O25_MAX_NF && p->n_grad_time <= fast::O25_MAX_NT) {
-    // k_gate_onepass256 (onepass256.hpp): the same operands with THREE k-blocks of time weights
-    const int nf = p->n_grad_freq, nt = p->n_grad_time;
-    std::vector<unsigned long long> tb(512, 0ull);
-    auto wt = [&](int d) { const int ad = d < 0 ? -d : d; return ad <= nt ? nt + 1 - ad : 0; };
-    for (int l = 0; l < 64; ++l) {
-      const int q = l / 16, j = l % 16;
-      for (int e = 0; e < 8; ++e) {
-        const int a = 8 * q + e - 8 - j, aa = a < 0 ? -a : a;
-        tb[l] |= (unsigned long long)(aa <= nf ? nf + 1 - aa : 0) << (8 * e);
-        const int r1 = e < 4 ? 4 * q + e : 16 + 4 * q + (e - 4);
-        tb[64 + l] |= (unsigned long long)wt(r1 - nt - j) << (8 * e);
-        tb[128 + l] |= (unsigned long long)wt(32 + r1 - nt - j) << (8 * e);
-        tb[192 + l] |= (unsigned long long)wt(64 + r1 - nt - j) << (8 * e);
-      }
-    }
-    for (int v = 0; v < 256; ++v)
-      for (int e = 0; e < 8; ++e) tb[256 + v] |= (unsigned long long)((v >> e) & 1) << (8 * e);
-    rc = upload(h, h->o25tab, tb.data(), tb.size() * 8);
-  }
-  if (!rc && h->fast20_ok && p->smooth_mask && p->n_grad_freq <= fast::O20_MAX_NF && p->n_grad_time <= fast::O20_MAX_NT) {
-    // k_gate_onepass2048 (onepass2048.hpp): TWO band matrices (bins 16 b - 24 + k and 16 b + 8 + k against output bin 16 b + j), one
-    // k-block of time weights
-    const int nf = p->n_grad_freq, nt = p->n_grad_time;
-    std::vector<unsigned long long> tb(448, 0ull);
     auto wt = [&](int d) { const int ad = d < 0 ? -d : d; return ad <= nt ? nt + 1 - ad : 0; };
     auto wf = [&](int d) { const int ad = d < 0 ? -d : d; return ad <= nf ? nf + 1 - ad : 0; };
+    const bool two = rg == &REG2048;
+    const int ex = 64 * (two ? 3 : 1 + rg->tab_kb);   // the byte expansion follows the operands
+    std::vector<unsigned long long> tb(ex + 256, 0ull);
     for (int l = 0; l < 64; ++l) {
       const int q = l / 16, j = l % 16;
       for (int e = 0; e < 8; ++e) {
         const int k = 8 * q + e;
-        tb[l] |= (unsigned long long)wf(k - 24 - j) << (8 * e);
-        tb[64 + l] |= (unsigned long long)wf(k + 8 - j) << (8 * e);
+        // k slot 8 q + e: row 4 q + e of the first block (e < 4) / 16 + 4 q + (e - 4) of the second; output frame j at row nt + j
         const int r1 = e < 4 ? 4 * q + e : 16 + 4 * q + (e - 4);
-        tb[128 + l] |= (unsigned long long)wt(r1 - nt - j) << (8 * e);
+        if (two) {
+          // 2048: TWO band matrices (bins 16 b - 24 + k and 16 b + 8 + k against output bin 16 b + j), one k-block of time weights
+          tb[l] |= (unsigned long long)wf(k - 24 - j) << (8 * e);
+          tb[64 + l] |= (unsigned long long)wf(k + 8 - j) << (8 * e);
+          tb[128 + l] |= (unsigned long long)wt(r1 - nt - j) << (8 * e);
+        } else {
+          // 512 / 256: one band matrix, tab_kb k-blocks of time weights
+          tb[l] |= (unsigned long long)wf(k - 8 - j) << (8 * e);
+          for (int b = 0; b < rg->tab_kb; ++b) tb[64 * (1 + b) + l] |= (unsigned long long)wt(32 * b + r1 - nt - j) << (8 * e);
+        }
       }
     }
     for (int v = 0; v < 256; ++v)
-      for (int e = 0; e < 8; ++e) tb[192 + v] |= (unsigned long long)((v >> e) & 1) << (8 * e);
-    rc = upload(h, h->o20tab, tb.data(), tb.size() * 8);
+      for (int e = 0; e < 8; ++e) tb[ex + v] |= (unsigned long long)((v >> e) & 1) << (8 * e);
+    rc = upload(h, h->regtab, tb.data(), tb.size() * 8);
   }
   if (!rc) rc = ensure(h, h->thresh, (size_t)h->FS * sizeof(double));
   if (rc) {
@@ -1312,7 +1310,7 @@ extern "C" int sg_destroy(sg_handle* h) {
                     &h->need, &h->T2, &h->part, &h->tw512, &h->invn, &h->seam, &h->ftab, &h->xbits, &h->xpart,
                     &h->xticket, &h->xtick2, &h->ftab3, &h->xexp, &h->optab, &h->nsp, &h->nsc, &h->xin, &h->czt_tw64, &h->czt_ch64,
                     &h->czt_bh64, &h->czt_tw32, &h->czt_ch32, &h->czt_bh32, &h->logtab, &h->big_twM, &h->big_tw2,
-                    &h->big_ch, &h->big_bh, &h->big_W, &h->big_W2, &h->xP, &h->xraw, &h->xM, &h->xtmp, &h->xseg, &h->invn5, &h->invn25, &h->invn20, &h->rg_count, &h->alim, &h->nss, &h->mr_pt32, &h->mr_pt64, &h->o5tab, &h->o25tab, &h->o20tab})
+                    &h->big_ch, &h->big_bh, &h->big_W, &h->big_W2, &h->xP, &h->xraw, &h->xM, &h->xtmp, &h->xseg, &h->rg_count, &h->alim, &h->nss, &h->mr_pt32, &h->mr_pt64, &h->regtab})
     free_buf(*b);
   sg::rg_free(h->rg);
   delete h;
@@ -1486,106 +1484,8 @@ static int stage_decide(sg_handle* h, const Geom& g, int64_t ub, const double* t
 }
 
 // ------------------------------------------------------------------------------------------
-// n_fft = 512 / hop 128 on the register transform (fast512.hpp)
+// stages of the register geometries (n_fft = 512 / 256 / 2048): each reads the handle's RegGeom
 // ------------------------------------------------------------------------------------------
-static fast::Fast5Args fast5_args(const sg_handle* h, const View& v, const Geom& g) {
-  fast::Fast5Args A{};
-  A.view = v; A.g = g;
-  A.win = (const float*)h->wa32.p;
-  A.win64 = (const double*)h->wfull64.p;
-  A.tw512 = (const fast::cf*)h->tw512.p;
-  A.tw64 = (const cx<double>*)h->tw64.p;
-  A.mag_scale = h->mag_scale; A.top_db = h->p.top_db;
-  A.wsq = (const float*)h->wsq32.p;
-  A.invn = (const float*)h->invn5.p;
-  return A;
-}
-constexpr size_t FAST5_LDS = (size_t)(fast::FN + 4 * fast::WAVE_CX_H) * sizeof(fast::cf) + (512 + 264) * sizeof(float);
-
-static int stage_decide512(sg_handle* h, const View& v, const Geom& g, int64_t ub, const ThreshConsts& tc,
-                           unsigned long long* bits, hipStream_t st, const FloorLazy& fl = FloorLazy{}, bool redo = false) {
-  ProfScope ps(h, redo ? SG_STAGE_STFT_MAX : SG_STAGE_DECIDE_FAST, st);   // (the early-exit second launch is booked with the pre-pass)
-  fast::Fast5Args A = fast5_args(h, v, g);
-  A.tc = tc;
-  A.bits = bits;
-  A.fl = fl;
-  auto go = [&](auto kern) -> hipError_t {
-    hipError_t e = set_lds(reinterpret_cast<const void*>(kern), FAST5_LDS);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((g.T + 31) / 32), (unsigned)ub), dim3(256), FAST5_LDS, st, A);
-    return hipGetLastError();
-  };
-  if (redo) HIPCHK(h, go(fast::k_decide_fast512<4, true>));
-  else HIPCHK(h, go(fast::k_decide_fast512<4, false>));
-  return SG_OK;
-}
-
-static int stage_mag512(sg_handle* h, const View& v, const Geom& g, int64_t ub, float* mag, hipStream_t st, double iir_b = 0.0,
-                        double* sub = nullptr /* per-tile recurrence partials (mag_sub_partials) */) {
-  ProfScope ps(h, SG_STAGE_STFT_MAG, st);
-  fast::Fast5Args A = fast5_args(h, v, g);
-  A.mag = mag;
-  A.iir_b = iir_b;
-  A.sub = sub;
-  auto kern = fast::k_mag_fast512<4>;
-  HIPCHK(h, set_lds(reinterpret_cast<const void*>(kern), FAST5_LDS));
-  hipLaunchKernelGGL(kern, dim3((unsigned)((g.T + 31) / 32), (unsigned)ub), dim3(256), FAST5_LDS, st, A);
-  HIPCHK(h, hipGetLastError());
-  return SG_OK;
-}
-
-// seam hops of abutting apply / one-pass tiles at n_fft = 512 / 256 (fastpath.hpp: k_ola_seam); ARGS = Fast5Args / Fast25Args
-template <int HOP, int NF, typename ARGS>
-static int launch_seam_small(sg_handle* h, const ARGS& A, int64_t ub, hipStream_t st) {
-  if (A.n_tiles < 2) return SG_OK;
-  fast::SeamArgs S{};
-  S.view = A.view; S.g = A.g; S.om = A.om; S.h_begin = A.h_begin; S.h_end = A.h_end; S.normalize = A.normalize;
-  S.invn = A.invn; S.wsq = A.wsq; S.part = A.part; S.n_tiles = A.n_tiles;
-  hipLaunchKernelGGL((fast::k_ola_seam<HOP, NF>), dim3((unsigned)(A.n_tiles - 1), (unsigned)ub), dim3(HOP), 0, st, S);
-  HIPCHK(h, hipGetLastError());
-  return SG_OK;
-}
-
-static int stage_apply512(sg_handle* h, const View& v, const Geom& g, int64_t ub, const OutMap& om,
-                          const float* mask_f /* nullptr: uint16 weight sums in h->K16 (natural bin order) */,
-                          int normalize, hipStream_t st) {
-  ProfScope ps(h, SG_STAGE_APPLY_FAST, st);
-  fast::Fast5Args A = fast5_args(h, v, g);
-  A.Mf = mask_f;
-  A.K = (const unsigned short*)h->K16.p;
-  A.inv_ktot = (float)(1.0 / (double)h->ktot);
-  A.om = om;
-  A.normalize = normalize;
-  A.h_begin = (om.p0 + g.padL) / 128;
-  A.h_end = (om.p1 - 1 + g.padL) / 128 + 1;
-  const int64_t nh = A.h_end - A.h_begin;
-  if (nh <= 0) return SG_OK;
-  // (round 6) abutting tiles of 32 frames; the 3 hops that straddle two tiles as partial sums + k_ola_seam (fastpath.hpp)
-  const int64_t tiles = (nh + 3 + 31) / 32;
-  const bool seam = tiles >= 2 && !h->force_noseam;
-  A.part = nullptr;
-  A.n_tiles = (int)tiles;
-  if (seam) {
-    int rc = ensure(h, h->seam, (size_t)ub * tiles * 6 * 128 * sizeof(float));
-    if (rc) return rc;
-    A.part = (float*)h->seam.p;
-  }
-  const dim3 grid((unsigned)(seam ? tiles : (nh + 28) / 29), (unsigned)ub);
-  if (mask_f) {
-    auto kern = fast::k_apply_fast512<4, false>;
-    HIPCHK(h, set_lds(reinterpret_cast<const void*>(kern), FAST5_LDS));
-    hipLaunchKernelGGL(kern, grid, dim3(256), FAST5_LDS, st, A);
-  } else {
-    auto kern = fast::k_apply_fast512<4, true>;
-    HIPCHK(h, set_lds(reinterpret_cast<const void*>(kern), FAST5_LDS));
-    hipLaunchKernelGGL(kern, grid, dim3(256), FAST5_LDS, st, A);
-  }
-  HIPCHK(h, hipGetLastError());
-  if (seam) return launch_seam_small<128, 32>(h, A, ub, st);
-  return SG_OK;
-}
-
-// (round 6) one-pass gate for n_fft = 512 (onepass512.hpp): decide + smooth + apply in one kernel, tiles exchange their bits
 static int handoff_prepare(sg_handle* h, hipStream_t st);
 static int handoff_next_epoch(sg_handle* h, hipStream_t st);
 static int stage_prep_floor(sg_handle* h, const View& v, const Geom& g, int64_t ub, ThreshConsts* tc_out, hipStream_t st,
@@ -1593,12 +1493,151 @@ static int stage_prep_floor(sg_handle* h, const View& v, const Geom& g, int64_t 
 template <int MODE>
 static hipError_t launch_bits_any(const sg_handle* h, const View& v, const Geom& g, int64_t units, const ThreshConsts& tc,
                                   unsigned long long* pmax_bits, unsigned long long* bits, int wpr, hipStream_t st);
-// geometry constants of a small one-pass gate (onepass512.hpp / onepass256.hpp)
-struct OnePassSmall {
-  int hop, NF, NH, tile_words, xw, max_nf, max_nt, F;
-  size_t lds;
-  int extra = 0;   // abutting tiles (NH == NF, n_fft = 2048): the last tile must reach 3 hops past the range (its leading partials)
+
+static fast::RegArgs reg_args(const sg_handle* h, const RegGeom* r, const View& v, const Geom& g) {
+  fast::RegArgs A{};
+  A.view = v; A.g = g;
+  A.win = (const float*)h->wa32.p;
+  A.win64 = (const double*)h->wfull64.p;
+  A.tw = (const fast::cf*)(h->*r->tw).p;
+  A.tw64 = (const cx<double>*)h->tw64.p;
+  A.mag_scale = h->mag_scale; A.top_db = h->p.top_db;
+  A.wsq = (const float*)h->wsq32.p;
+  A.invn = (const float*)h->invn.p;
+  return A;
+}
+
+// one launch of a register-transform kernel: 256 threads, `lds` bytes of dynamic LDS
+template <typename ARGS>
+static hipError_t reg_launch(void (*kern)(ARGS), dim3 grid, size_t lds, hipStream_t st, const ARGS& A) {
+  hipError_t e = set_lds(reinterpret_cast<const void*>(kern), lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, A);
+  return hipGetLastError();
+}
+
+static int stage_decide_reg(sg_handle* h, const RegGeom* r, const View& v, const Geom& g, int64_t ub, const ThreshConsts& tc,
+                            unsigned long long* bits, hipStream_t st, const FloorLazy& fl = FloorLazy{}, bool redo = false) {
+  ProfScope ps(h, redo ? SG_STAGE_STFT_MAX : SG_STAGE_DECIDE_FAST, st);   // (the early-exit second launch is booked with the pre-pass)
+  fast::RegArgs A = reg_args(h, r, v, g);
+  A.tc = tc;
+  A.bits = bits;
+  A.fl = fl;
+  HIPCHK(h, reg_launch(r->decide[redo], dim3((unsigned)((g.T + r->frames - 1) / r->frames), (unsigned)ub), r->lds, st, A));
+  return SG_OK;
+}
+
+static int stage_mag_reg(sg_handle* h, const RegGeom* r, const View& v, const Geom& g, int64_t ub, float* mag, hipStream_t st,
+                         double iir_b, double* sub /* per-tile recurrence partials (mag_sub_partials) */) {
+  ProfScope ps(h, SG_STAGE_STFT_MAG, st);
+  fast::RegArgs A = reg_args(h, r, v, g);
+  A.mag = mag;
+  A.iir_b = iir_b;
+  A.sub = sub;
+  HIPCHK(h, reg_launch(r->mag, dim3((unsigned)((g.T + r->frames - 1) / r->frames), (unsigned)ub), r->lds, st, A));
+  return SG_OK;
+}
+
+// seam hops of abutting apply / one-pass tiles (fastpath.hpp: k_ola_seam)
+static int launch_seam(sg_handle* h, const RegGeom* r, const fast::RegArgs& A, int64_t ub, hipStream_t st) {
+  if (A.n_tiles < 2) return SG_OK;
+  fast::SeamArgs S{};
+  S.view = A.view; S.g = A.g; S.om = A.om; S.h_begin = A.h_begin; S.h_end = A.h_end; S.normalize = A.normalize;
+  S.invn = A.invn; S.wsq = A.wsq; S.part = A.part; S.n_tiles = A.n_tiles;
+  hipLaunchKernelGGL(r->seam, dim3((unsigned)(A.n_tiles - 1), (unsigned)ub), dim3(r->hop), 0, st, S);
+  HIPCHK(h, hipGetLastError());
+  return SG_OK;
+}
+
+// abutting tiles over the hops [hb, he) + their seam partials in h->seam
+static int reg_seam_tiles(sg_handle* h, const RegGeom* r, int64_t hb, int64_t he, int64_t ub, fast::RegArgs* A) {
+  const int64_t tiles = (he - hb + 3 + r->frames - 1) / r->frames;
+  int rc = ensure(h, h->seam, (size_t)ub * tiles * 6 * r->hop * sizeof(float));
+  if (rc) return rc;
+  A->part = (float*)h->seam.p;
+  A->n_tiles = (int)tiles;
+  return SG_OK;
+}
+
+static int stage_apply_reg(sg_handle* h, const RegGeom* r, const View& v, const Geom& g, int64_t ub, const OutMap& om,
+                           const float* mask_f /* nullptr: uint16 weight sums in h->K16 (natural bin order) */,
+                           int normalize, hipStream_t st) {
+  ProfScope ps(h, SG_STAGE_APPLY_FAST, st);
+  fast::RegArgs A = reg_args(h, r, v, g);
+  A.Mf = mask_f;
+  A.K = (const unsigned short*)h->K16.p;
+  A.inv_ktot = (float)(1.0 / (double)h->ktot);
+  A.om = om;
+  A.normalize = normalize;
+  A.h_begin = (om.p0 + g.padL) / r->hop;
+  A.h_end = (om.p1 - 1 + g.padL) / r->hop + 1;
+  const int64_t nh = A.h_end - A.h_begin;
+  if (nh <= 0) return SG_OK;
+  // (round 6) abutting tiles; the 3 hops that straddle two tiles as partial sums + k_ola_seam (fastpath.hpp)
+  const int64_t tiles = (nh + 3 + r->frames - 1) / r->frames;
+  const bool seam = tiles >= 2 && !h->force_noseam;
+  A.n_tiles = (int)tiles;
+  int rc;
+  if (seam && (rc = reg_seam_tiles(h, r, A.h_begin, A.h_end, ub, &A))) return rc;
+  const dim3 grid((unsigned)(seam ? tiles : (nh + r->hops - 1) / r->hops), (unsigned)ub);
+  HIPCHK(h, reg_launch(r->apply[mask_f == nullptr], grid, r->lds, st, A));
+  if (seam) return launch_seam(h, r, A, ub, st);
+  return SG_OK;
+}
+
+// Floor test of a gate call (is some band's -top_db floor possibly live?): a priori -- k_unit_absmax reads the recording once
+// more (stage_prep_floor: 26 us of a 345 us call at 10 minutes of 48 kHz) -- or in the gate / decision kernels on the samples
+// they stage (onepass.hpp "floor test"), which costs nothing unless a unit reports; then that unit is gated twice.  Both are
+// exact; the choice is a prediction from the host-mapped stamp "a unit of launch <epoch> reported / had its flag set", read
+// WITHOUT synchronising (it may lag by the calls still queued): recent -> a priori.  Opens the call's hand-off epoch first
+// (the floor test stamps err_host[1] with it).  lazy: tc / fl hold the in-kernel test's constants (k_prep_thresh_lazy writes
+// `nb` bounds when the threshold did not come from sg_noise_stats); otherwise the caller runs stage_prep_floor.
+struct FloorSetup {
+  bool lazy = false;
+  ThreshConsts tc{};
+  FloorLazy fl{};
 };
+static int floor_setup(sg_handle* h, const Geom& g, int64_t ub, int nb, hipStream_t st, FloorSetup* out) {
+  int rc;
+  if ((rc = handoff_prepare(h, st))) return rc;
+  const unsigned live_stamp = h->err_host[1];
+  // the flags the tiles raise are tagged with this launch's epoch (30 bits; 0 = untagged): nothing to clear per call
+  const unsigned need_tag = h->epoch & 0x3fffffffu;
+  // Once per 2^30 launches the tag wraps: flags of the previous era carry LARGER tags, which atomicMax would keep.  Not
+  // every epoch reaches this function (a lazy call takes two, stage_apply_fast takes its own), so the crossing is
+  // detected by the era (epoch >> 30) changing between two calls here, not by need_tag == 0.
+  const unsigned era = h->epoch >> 30;
+  if (era != h->need_era || need_tag == 0u) {
+    if (h->need.p) HIPCHK(h, hipMemsetAsync(h->need.p, 0, h->need.bytes, st));
+    if (h->alim.p) HIPCHK(h, hipMemsetAsync((char*)h->alim.p + 4, 0, 4, st));
+    h->need_era = era;
+  }
+  FloorSetup f;
+  f.lazy = need_tag != 0u &&
+           (h->floor_test == 2 || (h->floor_test == 0 && !(live_stamp != 0u && h->epoch - live_stamp <= 16u)));
+  if (f.lazy) {
+    const int wpr = (g.F + 63) / 64;
+    if ((rc = ensure(h, h->bits, (size_t)ub * g.T * wpr * 8))) return rc;
+    if ((rc = ensure_zeroed(h, h->need, (size_t)ub * 4, st))) return rc;
+    if ((rc = ensure(h, h->T2, (size_t)g.FS * 8))) return rc;
+    if ((rc = ensure_zeroed(h, h->alim, 256, st))) return rc;
+    if (!h->t2_ready) {
+      // the threshold did not come from sg_noise_stats (whose last kernel derives T2 / alim itself): one small launch
+      ProfScope ps(h, SG_STAGE_PREP, st);
+      hipLaunchKernelGGL(k_prep_thresh_lazy, dim3(1), dim3(256), 0, st, (const double*)h->thresh.p, g.F, h->mag_scale,
+                         h->sum_abs_w, h->p.top_db, (double*)h->T2.p, (unsigned*)h->alim.p, nb);
+      HIPCHK(h, hipGetLastError());
+      h->t2_ready = true;
+    }
+    f.tc = ThreshConsts{(const double*)h->T2.p, (const double*)h->thresh.p, (const double*)h->pmax.p, (const int*)h->need.p,
+                        need_tag};
+    f.fl = FloorLazy{(unsigned*)h->alim.p, nb, h->err_dev + 1, h->epoch};
+  }
+  *out = f;
+  return SG_OK;
+}
+
+// (round 6) one-pass gate of a register geometry: decide + smooth + apply in one kernel, tiles exchange their bits
 static bool onepass_small_ok(const sg_handle* h, const Geom& g, const OutMap& om, const OnePassSmall& S, const DevBuf& tab) {
   if (h->force_nofast || h->force_split || h->force_f64_decide || h->force_unfused || !h->fused_ok) return false;
   if (h->p.variant != SG_VARIANT_S || !h->p.stationary || !h->p.smooth_mask) return false;
@@ -1607,46 +1646,20 @@ static bool onepass_small_ok(const sg_handle* h, const Geom& g, const OutMap& om
   const int64_t hb = (om.p0 + g.padL) / S.hop, he = (om.p1 - 1 + g.padL) / S.hop + 1;
   return he > hb;
 }
-// PARGS: the kernel's argument struct (its member A already filled with the geometry's tables); launch(P, redo) enqueues it
-template <typename PARGS, typename LAUNCH>
+// P: the kernel's argument struct (its member A already filled with the geometry's tables); launch(P, redo) enqueues it
+template <typename LAUNCH>
 static int stage_onepass_small(sg_handle* h, const View& v, const View& vx, const Geom& g, int64_t ub, const OutMap& om,
-                               hipStream_t st, const OnePassSmall& S, PARGS P, const DevBuf& tab, LAUNCH launch) {
+                               hipStream_t st, const OnePassSmall& S, fast::OnePassRegArgs P, const DevBuf& tab, LAUNCH launch) {
   int rc;
-  if ((rc = handoff_prepare(h, st))) return rc;
-  const unsigned live_stamp = h->err_host[1];
-  const unsigned need_tag = h->epoch & 0x3fffffffu;
-  const unsigned era = h->epoch >> 30;
-  if (era != h->need_era || need_tag == 0u) {
-    if (h->need.p) HIPCHK(h, hipMemsetAsync(h->need.p, 0, h->need.bytes, st));
-    if (h->alim.p) HIPCHK(h, hipMemsetAsync((char*)h->alim.p + 4, 0, 4, st));
-    h->need_era = era;
-  }
-  const bool lazy = need_tag != 0u &&
-                    (h->floor_test == 2 || (h->floor_test == 0 && !(live_stamp != 0u && h->epoch - live_stamp <= 16u)));
+  FloorSetup fs;
+  if ((rc = floor_setup(h, g, ub, (g.FS + 63) / 64, st, &fs))) return rc;
+  const bool lazy = fs.lazy;
   ++(lazy ? h->n_floor_lazy : h->n_floor_apriori);
   const int wpr = (g.F + 63) / 64;
-  ThreshConsts tc{};
-  FloorLazy fl{};
-  if (!lazy) {
-    if ((rc = stage_prep_floor(h, v, g, ub, &tc, st, &vx, h->err_dev + 1, h->epoch))) return rc;
-  } else {
-    const int nb = (g.FS + 63) / 64;
-    if ((rc = ensure(h, h->bits, (size_t)ub * g.T * wpr * 8))) return rc;
-    if ((rc = ensure_zeroed(h, h->need, (size_t)ub * 4, st))) return rc;
-    if ((rc = ensure(h, h->T2, (size_t)g.FS * 8))) return rc;
-    if ((rc = ensure_zeroed(h, h->alim, 256, st))) return rc;
-    if (!h->t2_ready) {
-      ProfScope ps(h, SG_STAGE_PREP, st);
-      hipLaunchKernelGGL(k_prep_thresh_lazy, dim3(1), dim3(256), 0, st, (const double*)h->thresh.p, g.F, h->mag_scale,
-                         h->sum_abs_w, h->p.top_db, (double*)h->T2.p, (unsigned*)h->alim.p, nb);
-      HIPCHK(h, hipGetLastError());
-      h->t2_ready = true;
-    }
-    tc = ThreshConsts{(const double*)h->T2.p, (const double*)h->thresh.p, (const double*)h->pmax.p, (const int*)h->need.p, need_tag};
-    fl = FloorLazy{(unsigned*)h->alim.p, nb, h->err_dev + 1, h->epoch};
-  }
+  if (!lazy && (rc = stage_prep_floor(h, v, g, ub, &fs.tc, st, &vx, h->err_dev + 1, h->epoch))) return rc;
+  const ThreshConsts& tc = fs.tc;
   P.A.tc = tc;
-  P.A.fl = fl;
+  P.A.fl = fs.fl;
   P.A.inv_ktot = (float)(1.0 / (double)h->ktot);
   P.A.om = om;
   P.A.normalize = 1;
@@ -1702,302 +1715,33 @@ static int stage_onepass_small(sg_handle* h, const View& v, const View& vx, cons
   return SG_OK;
 }
 
-static const OnePassSmall O5_GEOM{128, fast::O5_NF, fast::O5_NH, fast::O5_TILE_WORDS, fast::O5_XW, fast::O5_MAX_NF, fast::O5_MAX_NT, 257,
-                                  FAST5_LDS + 16 + 2048};
-// (abutting tiles + k_ola_seam: the default; SG_OPT_FORCE_NOSEAM keeps the overlapping tiles above)
-static const OnePassSmall O5_GEOM_SEAM{128, fast::O5_NF, fast::O5_NF, fast::O5_TILE_WORDS, fast::O5_XW, fast::O5_MAX_NF, fast::O5_MAX_NT, 257,
-                                       FAST5_LDS + 16 + 2048, 3};
-static bool onepass512_ok(const sg_handle* h, const Geom& g, const OutMap& om) {
-  return h->fast5_ok && onepass_small_ok(h, g, om, O5_GEOM, h->o5tab);
+static bool onepass_reg_ok(const sg_handle* h, const RegGeom* r, const Geom& g, const OutMap& om) {
+  return !(r->abut && h->force_noseam) && onepass_small_ok(h, g, om, r->op, h->regtab);
 }
-static int stage_onepass512(sg_handle* h, const View& v, const View& vx, const Geom& g, int64_t ub, const OutMap& om,
-                            hipStream_t st) {
-  fast::OnePass5Args P{};
-  P.A = fast5_args(h, v, g);
-  const bool seam = !h->force_noseam;
-  if (seam) {
-    const int64_t hb = (om.p0 + g.padL) / 128, he = (om.p1 - 1 + g.padL) / 128 + 1;
-    const int64_t tiles = (he - hb + 3 + 31) / 32;
-    int rc = ensure(h, h->seam, (size_t)ub * tiles * 6 * 128 * sizeof(float));
-    if (rc) return rc;
-    P.A.part = (float*)h->seam.p;
-    P.A.n_tiles = (int)tiles;
-  }
-  fast::Fast5Args last{};
-  auto launch = [&](const fast::OnePass5Args& Q, bool redo, dim3 grid) -> hipError_t {
+static int stage_onepass_reg(sg_handle* h, const RegGeom* r, const View& v, const View& vx, const Geom& g, int64_t ub,
+                             const OutMap& om, hipStream_t st) {
+  fast::OnePassRegArgs P{};
+  P.A = reg_args(h, r, v, g);
+  // (abutting tiles + k_ola_seam: the default; SG_OPT_FORCE_NOSEAM keeps overlapping tiles where the geometry has them)
+  const bool seam = r->abut || !h->force_noseam;
+  int rc;
+  if (seam && (rc = reg_seam_tiles(h, r, (om.p0 + g.padL) / r->hop, (om.p1 - 1 + g.padL) / r->hop + 1, ub, &P.A))) return rc;
+  const OnePassSmall& S = seam ? r->op_seam : r->op;
+  fast::RegArgs last{};
+  auto launch = [&](const fast::OnePassRegArgs& Q, bool redo, dim3 grid) -> hipError_t {
     last = Q.A;
-    auto go = [&](auto kern) -> hipError_t {
-      hipError_t e = set_lds(reinterpret_cast<const void*>(kern), O5_GEOM.lds);
-      if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(kern, grid, dim3(256), O5_GEOM.lds, st, Q);
-      return hipGetLastError();
-    };
-    return redo ? go(fast::k_gate_onepass512<4, true>) : go(fast::k_gate_onepass512<4, false>);
+    return reg_launch(r->gate[redo], grid, S.lds, st, Q);
   };
-  int rc = stage_onepass_small(h, v, vx, g, ub, om, st, seam ? O5_GEOM_SEAM : O5_GEOM, P, h->o5tab, launch);
-  if (rc || !seam) return rc;
+  if ((rc = stage_onepass_small(h, v, vx, g, ub, om, st, S, P, h->regtab, launch)) || !seam) return rc;
+  if (r->abut && P.A.n_tiles < 2) return SG_OK;   // (2048 books no seam stage for a single tile)
   ProfScope ps(h, SG_STAGE_APPLY_FAST, st);   // (after the second launch, if any: a redone unit rewrote its partials)
-  return launch_seam_small<128, 32>(h, last, ub, st);
-}
-
-// ------------------------------------------------------------------------------------------
-// n_fft = 256 / hop 64 on the register transform (fast256.hpp, round 5): four frames per lane group
-// ------------------------------------------------------------------------------------------
-static fast::Fast25Args fast25_args(const sg_handle* h, const View& v, const Geom& g) {
-  fast::Fast25Args A{};
-  A.view = v; A.g = g;
-  A.win = (const float*)h->wa32.p;
-  A.win64 = (const double*)h->wfull64.p;
-  A.tw512 = (const fast::cf*)h->tw512.p;
-  A.tw64 = (const cx<double>*)h->tw64.p;
-  A.mag_scale = h->mag_scale; A.top_db = h->p.top_db;
-  A.wsq = (const float*)h->wsq32.p;
-  A.invn = (const float*)h->invn25.p;
-  return A;
-}
-constexpr size_t FAST25_LDS = (size_t)(fast::FN + 4 * fast::WAVE_CX_H) * sizeof(fast::cf) + (256 + fast::F25_T2) * sizeof(float);
-
-static int stage_decide256(sg_handle* h, const View& v, const Geom& g, int64_t ub, const ThreshConsts& tc,
-                           unsigned long long* bits, hipStream_t st, const FloorLazy& fl = FloorLazy{}, bool redo = false) {
-  ProfScope ps(h, redo ? SG_STAGE_STFT_MAX : SG_STAGE_DECIDE_FAST, st);
-  fast::Fast25Args A = fast25_args(h, v, g);
-  A.tc = tc;
-  A.bits = bits;
-  A.fl = fl;
-  auto go = [&](auto kern) -> hipError_t {
-    hipError_t e = set_lds(reinterpret_cast<const void*>(kern), FAST25_LDS);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((g.T + 63) / 64), (unsigned)ub), dim3(256), FAST25_LDS, st, A);
-    return hipGetLastError();
-  };
-  if (redo) HIPCHK(h, go(fast::k_decide_fast256<4, true>));
-  else HIPCHK(h, go(fast::k_decide_fast256<4, false>));
-  return SG_OK;
-}
-
-static int stage_mag256(sg_handle* h, const View& v, const Geom& g, int64_t ub, float* mag, hipStream_t st, double iir_b = 0.0,
-                        double* sub = nullptr /* per-tile recurrence partials (mag_sub_partials) */) {
-  ProfScope ps(h, SG_STAGE_STFT_MAG, st);
-  fast::Fast25Args A = fast25_args(h, v, g);
-  A.mag = mag;
-  A.iir_b = iir_b;
-  A.sub = sub;
-  auto kern = fast::k_mag_fast256<4>;
-  HIPCHK(h, set_lds(reinterpret_cast<const void*>(kern), FAST25_LDS));
-  hipLaunchKernelGGL(kern, dim3((unsigned)((g.T + 63) / 64), (unsigned)ub), dim3(256), FAST25_LDS, st, A);
-  HIPCHK(h, hipGetLastError());
-  return SG_OK;
-}
-
-static int stage_apply256(sg_handle* h, const View& v, const Geom& g, int64_t ub, const OutMap& om,
-                          const float* mask_f /* nullptr: uint16 weight sums in h->K16 (natural bin order) */,
-                          int normalize, hipStream_t st) {
-  ProfScope ps(h, SG_STAGE_APPLY_FAST, st);
-  fast::Fast25Args A = fast25_args(h, v, g);
-  A.Mf = mask_f;
-  A.K = (const unsigned short*)h->K16.p;
-  A.inv_ktot = (float)(1.0 / (double)h->ktot);
-  A.om = om;
-  A.normalize = normalize;
-  A.h_begin = (om.p0 + g.padL) / 64;
-  A.h_end = (om.p1 - 1 + g.padL) / 64 + 1;
-  const int64_t nh = A.h_end - A.h_begin;
-  if (nh <= 0) return SG_OK;
-  // (round 6) abutting tiles of 64 frames + k_ola_seam (see stage_apply512)
-  const int64_t tiles = (nh + 3 + 63) / 64;
-  const bool seam = tiles >= 2 && !h->force_noseam;
-  A.part = nullptr;
-  A.n_tiles = (int)tiles;
-  if (seam) {
-    int rc = ensure(h, h->seam, (size_t)ub * tiles * 6 * 64 * sizeof(float));
-    if (rc) return rc;
-    A.part = (float*)h->seam.p;
-  }
-  const dim3 grid((unsigned)(seam ? tiles : (nh + 60) / 61), (unsigned)ub);
-  if (mask_f) {
-    auto kern = fast::k_apply_fast256<4, false>;
-    HIPCHK(h, set_lds(reinterpret_cast<const void*>(kern), FAST25_LDS));
-    hipLaunchKernelGGL(kern, grid, dim3(256), FAST25_LDS, st, A);
-  } else {
-    auto kern = fast::k_apply_fast256<4, true>;
-    HIPCHK(h, set_lds(reinterpret_cast<const void*>(kern), FAST25_LDS));
-    hipLaunchKernelGGL(kern, grid, dim3(256), FAST25_LDS, st, A);
-  }
-  HIPCHK(h, hipGetLastError());
-  if (seam) return launch_seam_small<64, 64>(h, A, ub, st);
-  return SG_OK;
-}
-
-// (round 6) one-pass gate for n_fft = 256 (onepass256.hpp)
-static const OnePassSmall O25_GEOM{64, fast::O25_NF, fast::O25_NH, fast::O25_TILE_WORDS, fast::O25_XW, fast::O25_MAX_NF, fast::O25_MAX_NT,
-                                   129, FAST25_LDS + 16 + 2048};
-static const OnePassSmall O25_GEOM_SEAM{64, fast::O25_NF, fast::O25_NF, fast::O25_TILE_WORDS, fast::O25_XW, fast::O25_MAX_NF, fast::O25_MAX_NT,
-                                        129, FAST25_LDS + 16 + 2048, 3};
-static bool onepass256_ok(const sg_handle* h, const Geom& g, const OutMap& om) {
-  return h->fast25_ok && onepass_small_ok(h, g, om, O25_GEOM, h->o25tab);
-}
-static int stage_onepass256(sg_handle* h, const View& v, const View& vx, const Geom& g, int64_t ub, const OutMap& om,
-                            hipStream_t st) {
-  fast::OnePass25Args P{};
-  P.A = fast25_args(h, v, g);
-  const bool seam = !h->force_noseam;
-  if (seam) {
-    const int64_t hb = (om.p0 + g.padL) / 64, he = (om.p1 - 1 + g.padL) / 64 + 1;
-    const int64_t tiles = (he - hb + 3 + 63) / 64;
-    int rc = ensure(h, h->seam, (size_t)ub * tiles * 6 * 64 * sizeof(float));
-    if (rc) return rc;
-    P.A.part = (float*)h->seam.p;
-    P.A.n_tiles = (int)tiles;
-  }
-  fast::Fast25Args last{};
-  auto launch = [&](const fast::OnePass25Args& Q, bool redo, dim3 grid) -> hipError_t {
-    last = Q.A;
-    auto go = [&](auto kern) -> hipError_t {
-      hipError_t e = set_lds(reinterpret_cast<const void*>(kern), O25_GEOM.lds);
-      if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(kern, grid, dim3(256), O25_GEOM.lds, st, Q);
-      return hipGetLastError();
-    };
-    return redo ? go(fast::k_gate_onepass256<4, true>) : go(fast::k_gate_onepass256<4, false>);
-  };
-  int rc = stage_onepass_small(h, v, vx, g, ub, om, st, seam ? O25_GEOM_SEAM : O25_GEOM, P, h->o25tab, launch);
-  if (rc || !seam) return rc;
-  ProfScope ps(h, SG_STAGE_APPLY_FAST, st);
-  return launch_seam_small<64, 64>(h, last, ub, st);
-}
-
-// ------------------------------------------------------------------------------------------
-// n_fft = 2048 / hop 512 on the register transform (fast2048.hpp)
-// ------------------------------------------------------------------------------------------
-static fast::Fast20Args fast20_args(const sg_handle* h, const View& v, const Geom& g) {
-  fast::Fast20Args A{};
-  A.view = v; A.g = g;
-  A.win = (const float*)h->wa32.p;
-  A.win64 = (const double*)h->wfull64.p;
-  A.tw2048 = (const fast::cf*)h->tw32.p;
-  A.tw64 = (const cx<double>*)h->tw64.p;
-  A.mag_scale = h->mag_scale; A.top_db = h->p.top_db;
-  A.wsq = (const float*)h->wsq32.p;
-  A.invn = (const float*)h->invn20.p;
-  return A;
-}
-constexpr size_t FAST20_LDS = (size_t)(1024 + 4 * fast::WAVE_CX_H) * sizeof(fast::cf) + 1028 * sizeof(float);
-
-static int stage_decide2048(sg_handle* h, const View& v, const Geom& g, int64_t ub, const ThreshConsts& tc,
-                            unsigned long long* bits, hipStream_t st, const FloorLazy& fl = FloorLazy{}, bool redo = false) {
-  ProfScope ps(h, redo ? SG_STAGE_STFT_MAX : SG_STAGE_DECIDE_FAST, st);
-  fast::Fast20Args A = fast20_args(h, v, g);
-  A.tc = tc;
-  A.bits = bits;
-  A.fl = fl;
-  auto go = [&](auto kern) -> hipError_t {
-    hipError_t e = set_lds(reinterpret_cast<const void*>(kern), FAST20_LDS);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((g.T + 7) / 8), (unsigned)ub), dim3(256), FAST20_LDS, st, A);
-    return hipGetLastError();
-  };
-  if (redo) HIPCHK(h, go(fast::k_decide_fast2048<4, true>));
-  else HIPCHK(h, go(fast::k_decide_fast2048<4, false>));
-  return SG_OK;
-}
-
-static int stage_mag2048(sg_handle* h, const View& v, const Geom& g, int64_t ub, float* mag, hipStream_t st, double iir_b = 0.0,
-                        double* sub = nullptr /* per-tile recurrence partials (mag_sub_partials) */) {
-  ProfScope ps(h, SG_STAGE_STFT_MAG, st);
-  fast::Fast20Args A = fast20_args(h, v, g);
-  A.mag = mag;
-  A.iir_b = iir_b;
-  A.sub = sub;
-  auto kern = fast::k_mag_fast2048<4>;
-  HIPCHK(h, set_lds(reinterpret_cast<const void*>(kern), FAST20_LDS));
-  hipLaunchKernelGGL(kern, dim3((unsigned)((g.T + 7) / 8), (unsigned)ub), dim3(256), FAST20_LDS, st, A);
-  HIPCHK(h, hipGetLastError());
-  return SG_OK;
-}
-
-static int stage_apply2048(sg_handle* h, const View& v, const Geom& g, int64_t ub, const OutMap& om,
-                           const float* mask_f /* nullptr: uint16 weight sums in h->K16 */, int normalize, hipStream_t st) {
-  ProfScope ps(h, SG_STAGE_APPLY_FAST, st);
-  fast::Fast20Args A = fast20_args(h, v, g);
-  A.Mf = mask_f;
-  A.K = (const unsigned short*)h->K16.p;
-  A.inv_ktot = (float)(1.0 / (double)h->ktot);
-  A.om = om;
-  A.normalize = normalize;
-  A.h_begin = (om.p0 + g.padL) / 512;
-  A.h_end = (om.p1 - 1 + g.padL) / 512 + 1;
-  const int64_t nh = A.h_end - A.h_begin;
-  if (nh <= 0) return SG_OK;
-  // abutting tiles of 8 frames; the 3 hops that straddle two tiles as partial sums + k_ola_seam2048
-  const int64_t tiles = (nh + 3 + 7) / 8;
-  const bool seam = tiles >= 2 && !h->force_noseam;
-  A.part = nullptr;
-  A.n_tiles = (int)tiles;
-  if (seam) {
-    int rc = ensure(h, h->seam, (size_t)ub * tiles * 6 * 512 * sizeof(float));
-    if (rc) return rc;
-    A.part = (float*)h->seam.p;
-  }
-  const dim3 grid((unsigned)(seam ? tiles : (nh + 4) / 5), (unsigned)ub);
-  if (mask_f) {
-    auto kern = fast::k_apply_fast2048<4, false>;
-    HIPCHK(h, set_lds(reinterpret_cast<const void*>(kern), FAST20_LDS));
-    hipLaunchKernelGGL(kern, grid, dim3(256), FAST20_LDS, st, A);
-  } else {
-    auto kern = fast::k_apply_fast2048<4, true>;
-    HIPCHK(h, set_lds(reinterpret_cast<const void*>(kern), FAST20_LDS));
-    hipLaunchKernelGGL(kern, grid, dim3(256), FAST20_LDS, st, A);
-  }
-  HIPCHK(h, hipGetLastError());
-  if (seam) {
-    hipLaunchKernelGGL(fast::k_ola_seam2048<8>, dim3((unsigned)(tiles - 1), (unsigned)ub), dim3(512), 0, st, A);
-    HIPCHK(h, hipGetLastError());
-  }
-  return SG_OK;
-}
-
-// (round 6) one-pass gate for n_fft = 2048 (onepass2048.hpp): abutting tiles of 8 frames + k_ola_seam2048
-static const OnePassSmall O20_GEOM{512, fast::O20_NF, fast::O20_NF, fast::O20_TILE_WORDS, fast::O20_XW, fast::O20_MAX_NF, fast::O20_MAX_NT,
-                                   1025, FAST20_LDS + 16 + 2048, 3};
-static bool onepass2048_ok(const sg_handle* h, const Geom& g, const OutMap& om) {
-  return h->fast20_ok && !h->force_noseam && onepass_small_ok(h, g, om, O20_GEOM, h->o20tab);
-}
-static int stage_onepass2048(sg_handle* h, const View& v, const View& vx, const Geom& g, int64_t ub, const OutMap& om,
-                             hipStream_t st) {
-  fast::OnePass20Args P{};
-  P.A = fast20_args(h, v, g);
-  const int64_t hb = (om.p0 + g.padL) / 512, he = (om.p1 - 1 + g.padL) / 512 + 1;
-  const int64_t tiles = (he - hb + 3 + 7) / 8;
-  int rc = ensure(h, h->seam, (size_t)ub * tiles * 6 * 512 * sizeof(float));
-  if (rc) return rc;
-  P.A.part = (float*)h->seam.p;
-  P.A.n_tiles = (int)tiles;
-  fast::Fast20Args last{};
-  auto launch = [&](const fast::OnePass20Args& Q, bool redo, dim3 grid) -> hipError_t {
-    last = Q.A;
-    auto go = [&](auto kern) -> hipError_t {
-      hipError_t e = set_lds(reinterpret_cast<const void*>(kern), O20_GEOM.lds);
-      if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(kern, grid, dim3(256), O20_GEOM.lds, st, Q);
-      return hipGetLastError();
-    };
-    return redo ? go(fast::k_gate_onepass2048<4, true>) : go(fast::k_gate_onepass2048<4, false>);
-  };
-  if ((rc = stage_onepass_small(h, v, vx, g, ub, om, st, O20_GEOM, P, h->o20tab, launch))) return rc;
-  if (tiles >= 2) {   // the hops that straddle two tiles (after the second launch, if any: a redone unit rewrote its partials)
-    ProfScope ps(h, SG_STAGE_APPLY_FAST, st);
-    hipLaunchKernelGGL(fast::k_ola_seam2048<8>, dim3((unsigned)(tiles - 1), (unsigned)ub), dim3(512), 0, st, last);
-    HIPCHK(h, hipGetLastError());
-  }
-  return SG_OK;
+  return launch_seam(h, r, last, ub, st);
 }
 
 static int stage_mag(sg_handle* h, const View& v, const Geom& g, int64_t ub, hipStream_t st, double iir_b = 0.0,
                      double* sub = nullptr /* register geometries: recurrence partials per magnitude tile (16 / 32 / 64 / 8 frames) */) {
   float* mag = (float*)h->P.p;
-  if (h->fast5_ok && !h->force_nofast) return stage_mag512(h, v, g, ub, mag, st, iir_b, sub);
-  if (h->fast25_ok && !h->force_nofast) return stage_mag256(h, v, g, ub, mag, st, iir_b, sub);
-  if (h->fast20_ok && !h->force_nofast) return stage_mag2048(h, v, g, ub, mag, st, iir_b, sub);
+  if (const RegGeom* r = reg_geom(h)) return stage_mag_reg(h, r, v, g, ub, mag, st, iir_b, sub);
   if (h->fast_ok && !h->force_nofast) {
     ProfScope ps(h, SG_STAGE_STFT_MAG, st);
     constexpr int WAVES = 4;
@@ -2044,11 +1788,12 @@ static bool nonstat2_ok(const sg_handle* h, const Geom& g) {
 static int stage_nonstat_mask2(sg_handle* h, const View& v, const Geom& g, int64_t ub, bool smooth, hipStream_t st) {
   // register geometries: the magnitude kernel also leaves the recurrence partials of its tiles -- 16 frames at n_fft = 1024,
   // (round 6) 32 / 64 / 8 at 512 / 256 / 2048 -- no second pass over |X| (k_iir_part); PER pieces per 64-frame tile of the chain
-  const int plen = h->fast5_ok ? 32 : h->fast25_ok ? 64 : h->fast20_ok ? 8 : 16, per = NS_TT / plen;
+  const RegGeom* r = reg_geom(h);
+  const int plen = r ? r->frames : 16, per = NS_TT / plen;
   const int64_t nsub = (g.T + plen - 1) / plen;
-  const bool sub_small = (h->fast5_ok || h->fast25_ok || h->fast20_ok) && !h->force_nofast && SG_CHAIN_PAR && !h->force_split &&
-                         ub <= 65535 && nsp_ok((g.T + NS_TT - 1) / NS_TT, per);   // (the serial chain kernels know 16-frame pieces only)
-  const bool sub_ok = (h->fast_ok && !h->force_nofast && !(h->fast5_ok || h->fast20_ok || h->fast25_ok)) || sub_small;
+  const bool sub_ok = r ? SG_CHAIN_PAR && !h->force_split && ub <= 65535 &&
+                              nsp_ok((g.T + NS_TT - 1) / NS_TT, per)   // (the serial chain kernels know 16-frame pieces only)
+                        : h->fast_ok && !h->force_nofast;
   int rc;
   if (sub_ok && (rc = ensure(h, h->nss, (size_t)ub * nsub * 2 * g.FS * sizeof(double)))) return rc;
   rc = stage_mag(h, v, g, ub, st, h->p.iir_b, sub_ok ? (double*)h->nss.p : nullptr);
@@ -2331,45 +2076,17 @@ static int stage_fused_mask(sg_handle* h, const View& v, const Geom& g, int64_t 
   const int wpr = (g.F + 63) / 64;
   int rc;
   if ((rc = ensure(h, h->K16, (size_t)ub * g.T * g.FS * 2))) return rc;
-  ThreshConsts tc{};
   // (round 6) The register-transform decision kernels of n_fft = 512 / 256 / 2048 stage every sample of a unit's window: they
   // run the floor test themselves (thresh.hpp: FloorLazy -- the one-pass gate's protocol) instead of k_unit_absmax +
-  // k_prep_thresh reading the recording once more before the gate.  Same prediction as stage_onepass: a priori when a recent
-  // call on the handle reported (SG_OPT_FLOOR_TEST forces either); both end in exact band maxima.
-  const bool reg_path = !fast && !h->force_f64_decide && !h->force_nofast && (h->fast20_ok || h->fast25_ok || h->fast5_ok);
-  bool lazy = false;
-  FloorLazy fl{};
-  if (reg_path && h->floor_test != 1) {
-    if ((rc = handoff_prepare(h, st))) return rc;     // (a fresh epoch = the tag of this call's flags; the host-mapped stamp)
-    const unsigned live_stamp = h->err_host[1];
-    const unsigned need_tag = h->epoch & 0x3fffffffu;
-    const unsigned era = h->epoch >> 30;
-    if (era != h->need_era || need_tag == 0u) {   // (tags wrapped: flags of the previous era carry larger ones)
-      if (h->need.p) HIPCHK(h, hipMemsetAsync(h->need.p, 0, h->need.bytes, st));
-      if (h->alim.p) HIPCHK(h, hipMemsetAsync((char*)h->alim.p + 4, 0, 4, st));
-      h->need_era = era;
-    }
-    lazy = need_tag != 0u && (h->floor_test == 2 || !(live_stamp != 0u && h->epoch - live_stamp <= 16u));
-    if (lazy) {
-      const int nb = (g.FS + 63) / 64;
-      if ((rc = ensure(h, h->bits, (size_t)ub * g.T * wpr * 8))) return rc;
-      if ((rc = ensure_zeroed(h, h->need, (size_t)ub * 4, st))) return rc;
-      if ((rc = ensure(h, h->T2, (size_t)g.FS * 8))) return rc;
-      if ((rc = ensure_zeroed(h, h->alim, 256, st))) return rc;
-      if (!h->t2_ready) {   // the threshold did not come from sg_noise_stats (whose last kernel derives T2 / alim itself)
-        ProfScope ps(h, SG_STAGE_PREP, st);
-        hipLaunchKernelGGL(k_prep_thresh_lazy, dim3(1), dim3(256), 0, st, (const double*)h->thresh.p, g.F, h->mag_scale,
-                           h->sum_abs_w, h->p.top_db, (double*)h->T2.p, (unsigned*)h->alim.p, nb);
-        HIPCHK(h, hipGetLastError());
-        h->t2_ready = true;
-      }
-      tc = ThreshConsts{(const double*)h->T2.p, (const double*)h->thresh.p, (const double*)h->pmax.p, (const int*)h->need.p,
-                        need_tag};
-      fl = FloorLazy{(unsigned*)h->alim.p, nb, h->err_dev + 1, h->epoch};
-    }
-  }
-  if (reg_path) ++(lazy ? h->n_floor_lazy : h->n_floor_apriori);
-  if (!lazy && (rc = stage_prep_floor(h, v, g, ub, &tc, st, nullptr, reg_path && h->err_dev ? h->err_dev + 1 : nullptr, h->epoch)))
+  // k_prep_thresh reading the recording once more before the gate.  Same prediction as the one-pass gates (floor_setup);
+  // both end in exact band maxima.
+  const RegGeom* r = !fast && !h->force_f64_decide ? reg_geom(h) : nullptr;
+  FloorSetup fs;
+  if (r && h->floor_test != 1 && (rc = floor_setup(h, g, ub, (g.FS + 63) / 64, st, &fs))) return rc;
+  const bool lazy = fs.lazy;
+  const ThreshConsts& tc = fs.tc;
+  if (r) ++(lazy ? h->n_floor_lazy : h->n_floor_apriori);
+  if (!lazy && (rc = stage_prep_floor(h, v, g, ub, &fs.tc, st, nullptr, r && h->err_dev ? h->err_dev + 1 : nullptr, h->epoch)))
     return rc;
   if (fast && !h->force_f64_decide) {
     ProfScope ps(h, SG_STAGE_DECIDE_FAST, st);
@@ -2395,17 +2112,8 @@ static int stage_fused_mask(sg_handle* h, const View& v, const Geom& g, int64_t 
     dim3 grid((unsigned)((quads + per_block - 1) / per_block), (unsigned)ub);
     hipLaunchKernelGGL(kern, grid, dim3(WAVES * 64), lds, st, D);
     HIPCHK(h, hipGetLastError());
-  } else if (!h->force_f64_decide && h->fast20_ok && !h->force_nofast) {
-    int rc20 = stage_decide2048(h, v, g, ub, tc, (unsigned long long*)h->bits.p, st, fl);
-    if (rc20) return rc20;
-  } else if (!h->force_f64_decide && h->fast25_ok && !h->force_nofast) {
-    // n_fft = 256: register transform, four frames per lane group
-    int rc25 = stage_decide256(h, v, g, ub, tc, (unsigned long long*)h->bits.p, st, fl);
-    if (rc25) return rc25;
-  } else if (!h->force_f64_decide && h->fast5_ok && !h->force_nofast) {
-    // n_fft = 512: register transform, two frames per lane group
-    int rc5 = stage_decide512(h, v, g, ub, tc, (unsigned long long*)h->bits.p, st, fl);
-    if (rc5) return rc5;
+  } else if (r) {
+    if ((rc = stage_decide_reg(h, r, v, g, ub, tc, (unsigned long long*)h->bits.p, st, fs.fl))) return rc;
   } else if (!h->force_f64_decide) {
     // other power-of-two frame lengths: float32 LDS transform + exact refinement
     ProfScope ps(h, SG_STAGE_STFT_BITS, st);
@@ -2422,16 +2130,13 @@ static int stage_fused_mask(sg_handle* h, const View& v, const Geom& g, int64_t 
       ProfScope ps(h, SG_STAGE_STFT_MAX, st);
       HIPCHK(h, launch_bits_any<0>(h, v, g, ub, tc, (unsigned long long*)h->pmax.p, (unsigned long long*)h->bits.p, wpr, st));
     }
-    int rcr = h->fast20_ok ? stage_decide2048(h, v, g, ub, tc, (unsigned long long*)h->bits.p, st, fl, true)
-              : h->fast25_ok ? stage_decide256(h, v, g, ub, tc, (unsigned long long*)h->bits.p, st, fl, true)
-                             : stage_decide512(h, v, g, ub, tc, (unsigned long long*)h->bits.p, st, fl, true);
-    if (rcr) return rcr;
+    if ((rc = stage_decide_reg(h, r, v, g, ub, tc, (unsigned long long*)h->bits.p, st, fs.fl, true))) return rc;
   }
   { int rc2 = stage_smooth_bits(h, g, ub, fast, tb, te, st); if (rc2) return rc2; }
   const int nf = h->p.n_grad_freq, nt = h->p.n_grad_time;
   int64_t cells = ub * g.T * g.FS;
   if (fast) return SG_OK;  // the fused apply kernel reads K directly
-  if ((h->fast5_ok || h->fast20_ok || h->fast25_ok) && !h->force_nofast && h->p.prop_decrease == 1.0) return SG_OK;   // so do k_apply_fast512 / 2048 / 256<K>
+  if (reg_geom(h) && h->p.prop_decrease == 1.0) return SG_OK;   // so do k_apply_fast512 / 256 / 2048<K>
   // (round 5) ... and k_apply_istft (power-of-two frames on the LDS transform): the float mask field is only written when
   // somebody asks for it (sg_debug_fetch field 1 expands the K counts of the last batch then)
   h->dbg_k16_only = k16_apply_geom(h) && h->p.prop_decrease == 1.0;
@@ -2604,48 +2309,12 @@ static int stage_onepass(sg_handle* h, const View& v, const View& vx, const Geom
                          hipStream_t st) {
   constexpr int WAVES = 4, NF = 16;
   int rc;
-  // (first: the floor test stamps err_host[1] with this launch's epoch)
-  if ((rc = handoff_prepare(h, st))) return rc;
-  // Floor test (is some band's -top_db floor possibly live?): a priori -- k_unit_absmax reads the recording once more, 26 us
-  // of a 345 us call at 10 minutes of 48 kHz -- or by the gate kernel on the samples it stages (onepass.hpp "floor test"),
-  // which costs nothing unless a unit reports; then that unit is gated twice.  Both are exact; the choice is a
-  // prediction from the host-mapped stamp "a unit of launch <epoch> reported / had its flag set", read WITHOUT
-  // synchronising (it may lag by the calls still queued): recent -> a priori.
-  const unsigned live_stamp = h->err_host[1];
-  // the flags the tiles raise are tagged with this launch's epoch (30 bits; 0 = untagged): nothing to clear per call
-  const unsigned need_tag = h->epoch & 0x3fffffffu;
-  // Once per 2^30 launches the tag wraps: flags of the previous era carry LARGER tags, which atomicMax would keep.  Not
-  // every epoch reaches this function (a lazy call takes two, stage_apply_fast takes its own), so the crossing is
-  // detected by the era (epoch >> 30) changing between two calls here, not by need_tag == 0.
-  const unsigned era = h->epoch >> 30;
-  if (era != h->need_era || need_tag == 0u) {
-    if (h->need.p) HIPCHK(h, hipMemsetAsync(h->need.p, 0, h->need.bytes, st));
-    if (h->alim.p) HIPCHK(h, hipMemsetAsync((char*)h->alim.p + 4, 0, 4, st));
-    h->need_era = era;
-  }
-  const bool lazy = need_tag != 0u &&
-                    (h->floor_test == 2 || (h->floor_test == 0 && !(live_stamp != 0u && h->epoch - live_stamp <= 16u)));
-  ThreshConsts tc{};
+  FloorSetup fs;
+  if ((rc = floor_setup(h, g, ub, OP_ALIM_BLOCKS, st, &fs))) return rc;
+  const bool lazy = fs.lazy;
+  const ThreshConsts& tc = fs.tc;
   ++(lazy ? h->n_floor_lazy : h->n_floor_apriori);
-  if (!lazy) {
-    if ((rc = stage_prep_floor(h, v, g, ub, &tc, st, &vx, h->err_dev + 1, h->epoch))) return rc;
-  } else {
-    const int wpr = (g.F + 63) / 64;
-    if ((rc = ensure(h, h->bits, (size_t)ub * g.T * wpr * 8))) return rc;
-    if ((rc = ensure_zeroed(h, h->need, (size_t)ub * 4, st))) return rc;
-    if ((rc = ensure(h, h->T2, (size_t)g.FS * 8))) return rc;
-    if ((rc = ensure_zeroed(h, h->alim, 256, st))) return rc;
-    if (!h->t2_ready) {
-      // the threshold did not come from sg_noise_stats (whose last kernel derives T2 / alim itself): one small launch
-      ProfScope ps(h, SG_STAGE_PREP, st);
-      hipLaunchKernelGGL(k_prep_thresh_lazy, dim3(1), dim3(256), 0, st, (const double*)h->thresh.p, g.F, h->mag_scale,
-                         h->sum_abs_w, h->p.top_db, (double*)h->T2.p, (unsigned*)h->alim.p);
-      HIPCHK(h, hipGetLastError());
-      h->t2_ready = true;
-    }
-    tc = ThreshConsts{(const double*)h->T2.p, (const double*)h->thresh.p, (const double*)h->pmax.p, (const int*)h->need.p,
-                      need_tag};
-  }
+  if (!lazy && (rc = stage_prep_floor(h, v, g, ub, &fs.tc, st, &vx, h->err_dev + 1, h->epoch))) return rc;
   fast::OnePassArgs P;
   P.x_exact = vx.x; P.stride_exact = vx.stride; P.dtype_exact = vx.dtype;
   fast::ApplyArgs& A = P.A;
@@ -3076,11 +2745,10 @@ static int run_S(sg_handle* h, View v, int64_t total_units, const OutMap& om, hi
   // one-pass gate (any prop_decrease) or, with prop_decrease == 1, the three-kernel bit-mask path: only bit /
   // count fields in the workspace
   const bool onepass = h->fused_ok && !h->force_unfused && h->fast_ok && !h->force_nofast && onepass_ok(h, g, om);
-  const bool onepass5 = !onepass && onepass512_ok(h, g, om);
-  const bool onepass25 = !onepass && !onepass5 && onepass256_ok(h, g, om);
-  const bool onepass20 = !onepass && !onepass5 && !onepass25 && onepass2048_ok(h, g, om);
-  const bool lean = onepass || onepass5 || onepass25 || onepass20 || (h->fused_ok && !h->force_unfused && h->fast_ok && !h->force_nofast &&
-                                            h->p.prop_decrease == 1.0);
+  const RegGeom* r = reg_geom(h);
+  const bool onepass_r = r && onepass_reg_ok(h, r, g, om);   // (the one-pass gate of a register geometry)
+  const bool lean = onepass || onepass_r || (h->fused_ok && !h->force_unfused && h->fast_ok && !h->force_nofast &&
+                                             h->p.prop_decrease == 1.0);
   int64_t ub = units_per_batch(h, g, total_units, lean);
   int rc = ensure_ws(h, g, ub, lean);
   if (rc) return rc;
@@ -3088,7 +2756,7 @@ static int run_S(sg_handle* h, View v, int64_t total_units, const OutMap& om, hi
   // frame (in every kernel).  Convert the readable part of the rows ONCE -- (float)sample is what those kernels
   // compute anyway -- and keep the original view for the float64 work (exact refinement, floor pre-pass).
   const View vx = v;
-  if (v.dtype != SG_F32 && ((h->fast_ok && !h->force_nofast && (onepass || (!h->p.stationary && nonstat2_ok(h, g)))) || onepass5 || onepass25 || onepass20)) {
+  if (v.dtype != SG_F32 && ((h->fast_ok && !h->force_nofast && (onepass || (!h->p.stationary && nonstat2_ok(h, g)))) || onepass_r)) {
     const int64_t rows = total_units / std::max<int64_t>(1, v.n_chunks), len = v.hi - v.lo;
     const size_t bytes = (size_t)rows * len * sizeof(float);
     if (len > 0 && bytes <= ((size_t)16 << 30)) {
@@ -3115,24 +2783,10 @@ static int run_S(sg_handle* h, View v, int64_t total_units, const OutMap& om, hi
       h->dbg_units = nb; h->dbg_T = g.T; h->dbg_has_P = false; h->dbg_fused = true; h->dbg_fast = true;
       continue;
     }
-    if (onepass5) {
+    if (onepass_r) {
       View vxb = vx;
       vxb.unit0 = u0;
-      if ((rc = stage_onepass512(h, v, vxb, g, nb, om, st))) return rc;
-      h->dbg_units = nb; h->dbg_T = g.T; h->dbg_has_P = false; h->dbg_fused = true; h->dbg_fast = true; h->dbg_k16_only = false;
-      continue;
-    }
-    if (onepass25) {
-      View vxb = vx;
-      vxb.unit0 = u0;
-      if ((rc = stage_onepass256(h, v, vxb, g, nb, om, st))) return rc;
-      h->dbg_units = nb; h->dbg_T = g.T; h->dbg_has_P = false; h->dbg_fused = true; h->dbg_fast = true; h->dbg_k16_only = false;
-      continue;
-    }
-    if (onepass20) {
-      View vxb = vx;
-      vxb.unit0 = u0;
-      if ((rc = stage_onepass2048(h, v, vxb, g, nb, om, st))) return rc;
+      if ((rc = stage_onepass_reg(h, r, v, vxb, g, nb, om, st))) return rc;
       h->dbg_units = nb; h->dbg_T = g.T; h->dbg_has_P = false; h->dbg_fused = true; h->dbg_fast = true; h->dbg_k16_only = false;
       continue;
     }
@@ -3146,7 +2800,7 @@ static int run_S(sg_handle* h, View v, int64_t total_units, const OutMap& om, hi
       continue;
     }
     // float mask field (natural bin order for the general apply kernels, lane order for the fused one)
-    h->dbg_fast = geom_fast || (fused && (h->fast5_ok || h->fast20_ok || h->fast25_ok) && !h->force_nofast && h->p.prop_decrease == 1.0);
+    h->dbg_fast = geom_fast || (fused && r && h->p.prop_decrease == 1.0);
     if (fused) {
       if ((rc = stage_fused_mask(h, v, g, nb, false, 0, g.T, st))) return rc;
     } else {
@@ -3165,15 +2819,9 @@ static int run_S(sg_handle* h, View v, int64_t total_units, const OutMap& om, hi
     }
     if (geom_fast) {
       if ((rc = stage_apply_fast(h, v, g, nb, om, (const float*)h->M.p, 1, st))) return rc;
-    } else if (h->fast25_ok && !h->force_nofast) {
+    } else if (r) {
       const bool kmask = fused && h->p.prop_decrease == 1.0;   // the bit-mask stages left uint16 sums, no float mask
-      if ((rc = stage_apply256(h, v, g, nb, om, kmask ? nullptr : (const float*)h->M.p, 1, st))) return rc;
-    } else if (h->fast5_ok && !h->force_nofast) {
-      const bool kmask = fused && h->p.prop_decrease == 1.0;   // the bit-mask stages left uint16 sums, no float mask
-      if ((rc = stage_apply512(h, v, g, nb, om, kmask ? nullptr : (const float*)h->M.p, 1, st))) return rc;
-    } else if (h->fast20_ok && !h->force_nofast) {
-      const bool kmask = fused && h->p.prop_decrease == 1.0;
-      if ((rc = stage_apply2048(h, v, g, nb, om, kmask ? nullptr : (const float*)h->M.p, 1, st))) return rc;
+      if ((rc = stage_apply_reg(h, r, v, g, nb, om, kmask ? nullptr : (const float*)h->M.p, 1, st))) return rc;
     } else if (fused && h->dbg_k16_only) {
       if ((rc = stage_apply_ola(h, v, g, nb, nullptr, om, 1, st, (const unsigned short*)h->K16.p, 1.0f / (float)h->ktot))) return rc;
     } else {
@@ -3358,7 +3006,7 @@ extern "C" int sg_noise_stats(sg_handle* h, const void* noise_dev, int dtype, in
   Geom g = make_geom(h, n);
   if ((rc = ensure_ws(h, g, 1))) return rc;
   h->t2_ready = false;
-  if ((rc = stage_stats(h, v, g, 1, (double*)h->thresh.p, st, /*gate_consts=*/h->fast_ok || h->fast5_ok || h->fast25_ok || h->fast20_ok))) return rc;
+  if ((rc = stage_stats(h, v, g, 1, (double*)h->thresh.p, st, /*gate_consts=*/h->fast_ok || h->reg))) return rc;
   h->has_thresh = true;
   return SG_OK;
 }
@@ -3587,12 +3235,8 @@ extern "C" int sg_process_batch(sg_handle* h, const void* x_dev, int dtype, int6
                                hipMemcpyDeviceToDevice, st));
     if (geom_fast) {
       if ((rc = stage_apply_fast(h, v, g, nb, om, (const float*)h->M.p, 1, st))) return rc;
-    } else if (h->fast25_ok && !h->force_nofast) {
-      if ((rc = stage_apply256(h, v, g, nb, om, (const float*)h->M.p, 1, st))) return rc;
-    } else if (h->fast5_ok && !h->force_nofast) {
-      if ((rc = stage_apply512(h, v, g, nb, om, (const float*)h->M.p, 1, st))) return rc;
-    } else if (h->fast20_ok && !h->force_nofast) {
-      if ((rc = stage_apply2048(h, v, g, nb, om, (const float*)h->M.p, 1, st))) return rc;
+    } else if (const RegGeom* r = reg_geom(h)) {
+      if ((rc = stage_apply_reg(h, r, v, g, nb, om, (const float*)h->M.p, 1, st))) return rc;
     } else {
       if ((rc = stage_apply_ola(h, v, g, nb, (const float*)h->M.p, om, 1, st))) return rc;
     }
@@ -3674,12 +3318,8 @@ extern "C" int sg_process_batch_backward(sg_handle* h, const void* grad_out_dev,
     const float* mk = mask_dev + (size_t)u0 * g.T * g.FS;
     if (h->fast_ok && !h->force_nofast) {
       if ((rc = stage_apply_fast(h, v, gb, nb, om, mk, 0, st))) return rc;
-    } else if (h->fast25_ok && !h->force_nofast) {
-      if ((rc = stage_apply256(h, v, gb, nb, om, mk, 0, st))) return rc;
-    } else if (h->fast5_ok && !h->force_nofast) {
-      if ((rc = stage_apply512(h, v, gb, nb, om, mk, 0, st))) return rc;
-    } else if (h->fast20_ok && !h->force_nofast) {
-      if ((rc = stage_apply2048(h, v, gb, nb, om, mk, 0, st))) return rc;
+    } else if (const RegGeom* r = reg_geom(h)) {
+      if ((rc = stage_apply_reg(h, r, v, gb, nb, om, mk, 0, st))) return rc;
     } else {
       if ((rc = stage_apply_ola(h, v, gb, nb, mk, om, 0, st))) return rc;
     }

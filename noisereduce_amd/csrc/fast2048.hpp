@@ -12,7 +12,7 @@
 // and hands the partner's half of the result back through a second shuffle -- the partner does the same for registers
 // 16..31.  Lane 0 (rows 0: bins 32 k2) pairs its own registers i <-> 32 - i; DC / Nyquist and bin 512 are explicit.
 // Tile = 4 waves = 8 frames, hop = 512 samples.  Tiles abut: the 3 hops that straddle two tiles are written as partial
-// sums and combined by k_ola_seam2048 (overlapping tiles would redo 3 of every 8 transforms).
+// sums and combined by k_ola_seam<512, 8> (fastpath.hpp; overlapping tiles would redo 3 of every 8 transforms).
 //
 //   k_decide_fast2048   float32 decisions + exact float64 refinement -> bits [unit][frame][17 words]
 //   k_mag_fast2048      |X| float32, natural bin order
@@ -30,32 +30,6 @@ constexpr int F20_FSL = 512 + 16;     // complex slots per frame slice (32 rows 
 constexpr int F20_XP = 512 + 32;      // floats between the 512-sample rows of the staged span
 static_assert(2 * F20_FSL <= WAVE_CX_H, "two frame slices must fit a wave's region");
 
-struct Fast20Args {
-  View view;
-  Geom g;
-  const float* win;          // window float32 (2048)
-  const double* win64;       // window float64 (2048)
-  const cf* tw2048;          // w_2048^k, k < 1024 (float32)
-  const cx<double>* tw64;    // w_2048^k, k < 1024 (float64)
-  ThreshConsts tc;
-  double mag_scale, top_db;
-  unsigned long long* bits;  // [units][T][17]
-  float* mag;                // [units][T][FS]
-  const float* Mf;           // float mask [units][T][FS]
-  const unsigned short* K;   // apply<KMASK>: integer weight sums of the smoothed bit mask [units][T][FS], natural order
-  float inv_ktot;
-  const float* wsq;          // window squared (2048)
-  const float* invn;         // 1 / sum_q wsq[512 q + s], s < 512
-  OutMap om;
-  int64_t h_begin, h_end;
-  int normalize;
-  float* part;               // seam mode: [units][tiles][6][512] un-normalised partial hops (3 leading, 3 trailing), else nullptr
-  int n_tiles;
-  FloorLazy fl;              // decide: in-kernel floor test (thresh.hpp), alim == nullptr: flags computed a priori
-  double iir_b;              // magnitude: the recurrence's b (non-stationary gate) ...
-  double* sub;               // ... and its per-tile partials [units][tiles][2][FS] (fastpath.hpp: mag_sub_partials), or nullptr
-};
-
 // w_1024^e from the w_2048 table
 __device__ __forceinline__ cf f20_w1024(const cf* tw2048, int e) {
   e &= 1023;
@@ -67,7 +41,7 @@ __device__ __forceinline__ cf f20_w1024(const cf* tw2048, int e) {
 // Stage the twiddle table T[k1][c] = w_1024^(k1 c) and the tile's sample span; gather v[r] = (x[2m], x[2m+1]) * w,
 // m = c + 32 r, of frame tf0 + 2 wave + g.
 template <int WAVES, bool MX = false>
-__device__ __forceinline__ unsigned f20_gather(const Fast20Args& A, cf* tw, cf* regions, int64_t row, int64_t chunk,
+__device__ __forceinline__ unsigned f20_gather(const RegArgs& A, cf* tw, cf* regions, int64_t row, int64_t chunk,
                                            int64_t tf0, cf* v, bool& valid) {   // returns (MX) the largest |sample| this thread staged, as a bit pattern
   unsigned mx_ = 0u;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 5, c = lane & 31;
@@ -80,7 +54,7 @@ __device__ __forceinline__ unsigned f20_gather(const Fast20Args& A, cf* tw, cf* 
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       const int i = min(tid + k * WAVES * 64, 1023);
-      t[k] = f20_w1024(A.tw2048, (i >> 5) * (i & 31));
+      t[k] = f20_w1024(A.tw, (i >> 5) * (i & 31));
     }
 #pragma unroll
     for (int k = 0; k < K; ++k) {
@@ -188,7 +162,7 @@ __device__ __forceinline__ cf f20_wk(cf wl, int k2) {
   return {wl.x * cs - wl.y * sn, wl.x * sn + wl.y * cs};
 }
 
-__device__ __forceinline__ double f20_exact_power(const Fast20Args& A, int64_t row, int64_t chunk, int64_t t, int f, int lane) {
+__device__ __forceinline__ double f20_exact_power(const RegArgs& A, int64_t row, int64_t chunk, int64_t t, int f, int lane) {
   const int64_t s0 = t * F20_H - A.g.padL;
   double re = 0.0, im = 0.0;
 #pragma unroll 4
@@ -211,7 +185,7 @@ __device__ __forceinline__ double f20_exact_power(const Fast20Args& A, int64_t r
 // ---------------------------------------------------------------------------------------------------------------
 // REDO: the second launch of a call with the in-kernel floor test (thresh.hpp: FloorLazy): only the units whose test fired.
 template <int WAVES, bool REDO = false>
-__global__ __launch_bounds__(WAVES * 64, 3) void k_decide_fast2048(Fast20Args A) {
+__global__ __launch_bounds__(WAVES * 64, 3) void k_decide_fast2048(RegArgs A) {
   if (REDO && A.fl.alim[1] != A.tc.need_tag) return;   // no unit of this call reported (the common case)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   cf* tw = reinterpret_cast<cf*>(smem);                 // [32][32] w_1024^(k1 c)
@@ -257,7 +231,7 @@ __global__ __launch_bounds__(WAVES * 64, 3) void k_decide_fast2048(Fast20Args A)
     fft1k_fwd(v, fb, tw + z0, c);
   }
   const float d2 = nrm2 > 0.f ? 8.0f * 2.3283064e-10f * nrm2 : -1.0f;
-  const cf wl = A.tw2048[c];
+  const cf wl = A.tw[c];
   unsigned pred = 0, amb = 0;
   bool predN = false, ambN = false;     // bin 1024 (lane 0)
   {
@@ -306,7 +280,7 @@ __global__ __launch_bounds__(WAVES * 64, 3) void k_decide_fast2048(Fast20Args A)
     const int q = amb_s ? (__ffs((int)amb_s) - 1) : 32;
     const int cs = src & 31, gs = src >> 5;
     const int f = q < 32 ? cs + 32 * q : 1024;
-    const Fast20Args& L = *late_args<Fast20Args>();     // (cold path: arguments re-read here, not kept live from the entry)
+    const RegArgs& L = *late_args<RegArgs>();     // (cold path: arguments re-read here, not kept live from the entry)
     const double P = f20_exact_power(L, row, chunk, tq + gs, f, lane);
     double t2 = L.tc.T2[f];
     if (floor_live) {
@@ -344,7 +318,7 @@ __global__ __launch_bounds__(WAVES * 64, 3) void k_decide_fast2048(Fast20Args A)
 
 // ---------------------------------------------------------------------------------------------------------------
 template <int WAVES>
-__global__ __launch_bounds__(WAVES * 64, 3) void k_mag_fast2048(Fast20Args A) {
+__global__ __launch_bounds__(WAVES * 64, 3) void k_mag_fast2048(RegArgs A) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   cf* tw = reinterpret_cast<cf*>(smem);
   cf* regions = tw + 1024;
@@ -365,7 +339,7 @@ __global__ __launch_bounds__(WAVES * 64, 3) void k_mag_fast2048(Fast20Args A) {
   if (tq < G.T) {   // (wave-uniform)
     cf* fb = regions + wave * WAVE_CX_H + g * F20_FSL;
     fft1k_fwd(v, fb, tw, c);
-    const cf wl = A.tw2048[c];
+    const cf wl = A.tw[c];
     float* mrow = A.mag + (u * G.T + (valid ? tq + g : 0)) * (int64_t)G.FS;
     float* trow = reinterpret_cast<float*>(regions + wave * WAVE_CX_H) + g * TP;
     const int src = (lane & 32) | ((32 - c) & 31);
@@ -404,7 +378,7 @@ __global__ __launch_bounds__(WAVES * 64, 3) void k_mag_fast2048(Fast20Args A) {
 
 // ---------------------------------------------------------------------------------------------------------------
 template <int WAVES, bool KMASK>
-__global__ __launch_bounds__(WAVES * 64, 3) void k_apply_fast2048(Fast20Args A) {
+__global__ __launch_bounds__(WAVES * 64, 3) void k_apply_fast2048(RegArgs A) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   cf* tw = reinterpret_cast<cf*>(smem);
   cf* regions = tw + 1024;
@@ -414,7 +388,7 @@ __global__ __launch_bounds__(WAVES * 64, 3) void k_apply_fast2048(Fast20Args A) 
   const int64_t row = (A.view.unit0 + u) / A.view.n_chunks;
   const int64_t chunk = A.view.c0 + (A.view.unit0 + u) % A.view.n_chunks;
   constexpr int NF = 2 * WAVES, NH = NF - 3;
-  const bool seam = A.part != nullptr;        // abutting tiles + k_ola_seam2048, else overlapping tiles
+  const bool seam = A.part != nullptr;        // abutting tiles + k_ola_seam (fastpath.hpp), else overlapping tiles
   const int64_t tf0 = A.h_begin - 3 + (int64_t)blockIdx.x * (seam ? NF : NH);
   cf v[32];
   bool valid;
@@ -429,7 +403,7 @@ __global__ __launch_bounds__(WAVES * 64, 3) void k_apply_fast2048(Fast20Args A) 
       asm volatile("" : "+v"(z0));
       fft1k_fwd(v, fb, tw + z0, c);
     }
-    const cf wl = A.tw2048[c];
+    const cf wl = A.tw[c];
     const int64_t moff = (u * G.T + (valid ? t : 0)) * (int64_t)G.FS;
     // pair_mask leaves out four 1/2 factors; the inverse transform a factor 1024; K / ktot for the integer sums
     const float ks = (KMASK ? A.inv_ktot : 1.0f) * (0.25f / 1024.0f);
@@ -558,49 +532,6 @@ __global__ __launch_bounds__(WAVES * 64, 3) void k_apply_fast2048(Fast20Args A) 
       if (gi < A.om.g_lo || gi >= A.om.g_hi) continue;
       store_sample(A.om.out, A.om.dtype, row * A.om.stride + gi - A.om.g0, p < G.Lout ? vals[e] : 0.f);
     }
-  }
-}
-
-// Seam hops of abutting tiles: hop tf0(b + 1) + k (k = 0..2) = trailing partial k of tile b + leading partial k of tile
-// b + 1 (fixed order), normalised and stored.
-template <int NF>
-__global__ __launch_bounds__(512) void k_ola_seam2048(Fast20Args A) {
-  const Geom& G = A.g;
-  const int64_t u = blockIdx.y, b = blockIdx.x;
-  const int64_t row = (A.view.unit0 + u) / A.view.n_chunks;
-  const int64_t chunk = A.view.c0 + (A.view.unit0 + u) % A.view.n_chunks;
-  const int s = threadIdx.x;
-  const float* pa = A.part + ((u * A.n_tiles + b) * 6 + 3) * 512;
-  const float* pb = A.part + ((u * A.n_tiles + b + 1) * 6 + 0) * 512;
-  // (round 6) all six partials and the envelope in flight before the first use: the three hops were three dependent round
-  // trips (8.3 us for a kernel that moves 1.8 MB)
-  float va[3], vb[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) { va[k] = pa[k * 512 + s]; vb[k] = pb[k * 512 + s]; }
-  const float inv = A.invn[s];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const int64_t h = A.h_begin - 3 + (int64_t)NF * (b + 1) + k;
-    if (h < A.h_begin || h >= A.h_end) continue;
-    float val = va[k] + vb[k];
-    if (A.normalize) {
-      if (h - 3 >= 0 && h < G.T) {
-        val *= inv;
-      } else {
-        float nrm = 0.f;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int64_t ti = h - q;
-          if (ti >= 0 && ti < G.T) nrm += A.wsq[F20_H * q + s];
-        }
-        val /= (nrm > 1e-10f ? nrm : 1.f);
-      }
-    }
-    const int64_t p = h * F20_H + s - G.padL;
-    if (p < A.om.p0 || p >= A.om.p1) continue;
-    const int64_t gi = chunk * A.om.g_step + (p - A.om.p0);
-    if (gi < A.om.g_lo || gi >= A.om.g_hi) continue;
-    store_sample(A.om.out, A.om.dtype, row * A.om.stride + gi - A.om.g0, p < G.Lout ? val : 0.f);
   }
 }
 

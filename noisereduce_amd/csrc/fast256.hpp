@@ -38,32 +38,6 @@ __host__ __device__ inline int bin6(int c, int e) {   // real bin of pair slot e
   return e < 4 ? 32 * e : 16 + 32 * (e - 4);
 }
 
-struct Fast25Args {
-  View view;
-  Geom g;
-  const float* win;        // window, float32 (256)
-  const double* win64;     // window, float64 (256): exact refinement
-  const cf* tw512;         // w_512^j (512)
-  const cx<double>* tw64;  // w_256^j float64 (128 entries; w^(j+128) = -w^j)
-  ThreshConsts tc;
-  double mag_scale, top_db;
-  unsigned long long* bits;  // decide: [units][T][3]
-  float* mag;                // magnitude: [units][T][FS]
-  const float* Mf;           // apply: float mask [units][T][FS], natural bin order
-  const unsigned short* K;   // apply<KMASK>: integer weight sums of the smoothed bit mask [units][T][FS] (mask = K / ktot)
-  float inv_ktot;
-  const float* wsq;          // apply: window squared (256)
-  const float* invn;         // apply: 1 / sum_q wsq[64 q + s], s < 64
-  OutMap om;
-  int64_t h_begin, h_end;    // apply: ext hops (64-sample blocks, ext = unit sample + padL) to produce
-  int normalize;
-  FloorLazy fl;              // decide: in-kernel floor test (thresh.hpp), alim == nullptr: flags computed a priori
-  float* part;               // apply / one-pass gate, seam mode: [units][tiles][6][hop] un-normalised partial hops (3 leading, 3 trailing: k_ola_seam), else nullptr
-  int n_tiles;
-  double iir_b;              // magnitude: the recurrence's b (non-stationary gate) ...
-  double* sub;               // ... and its per-tile partials [units][tiles][2][FS] (fastpath.hpp: mag_sub_partials), or nullptr
-};
-
 // second stage: two DFT8 per row (even columns = sequence 1, odd columns = sequence 2)
 template <bool INV>
 __device__ __forceinline__ void f25_stage2(cf* v) {
@@ -128,13 +102,13 @@ __device__ __forceinline__ void f25_inv_half(cf* v, cf* fb, const cf* tw512, int
 // stage tables + the tile's sample span, gather the lane's 32 complex points: v[r] = (x[m], y[m]) * w[m], m = cp + 8 r, of the
 // lane's frame pair X = tf0 + 16 wave + 4 g + 2 (c & 1), Y = X + 1.  Returns with the span consumed.
 template <int WAVES, bool MX = false>
-__device__ __forceinline__ unsigned f25_gather(const Fast25Args& A, cf* tw512, cf* regions, float* swin, int64_t row,
+__device__ __forceinline__ unsigned f25_gather(const RegArgs& A, cf* tw512, cf* regions, float* swin, int64_t row,
                                            int64_t chunk, int64_t tf0, cf* v, bool& validX, bool& validY) {   // returns (MX) the largest |sample| this thread staged, as a bit pattern
   unsigned mx_ = 0u;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15, cp = c >> 1;
   constexpr int NF = F25_FPW * WAVES, ROWS = NF - 1 + 4, SPAN = ROWS * F25_H;
   static_assert(ROWS * F25_XP * 4 <= WAVES * WAVE_CX_H * 8, "span must fit the exchange slices");
-  stage_tables<WAVES * 64, 64>(tw512, A.tw512, swin, A.win, tid);
+  stage_tables<WAVES * 64, 64>(tw512, A.tw, swin, A.win, tid);
   const Geom& G = A.g;
   const int64_t s0b = tf0 * F25_H - G.padL;
   const int64_t gb = chunk * A.view.cs - A.view.pad + s0b;
@@ -187,7 +161,7 @@ __device__ __forceinline__ void f25_pair(const cf* v, int off, int e, bool l0, c
   else b = sel(pb[11 - e], pb[7 - e]);
 }
 
-__device__ __forceinline__ double f25_exact_power(const Fast25Args& A, int64_t row, int64_t chunk, int64_t t, int f, int lane) {
+__device__ __forceinline__ double f25_exact_power(const RegArgs& A, int64_t row, int64_t chunk, int64_t t, int f, int lane) {
   const int64_t s0 = t * F25_H - A.g.padL;
   double re = 0.0, im = 0.0;
 #pragma unroll
@@ -235,7 +209,7 @@ __device__ __forceinline__ void f25_powers(const cf* v, bool l0, float (&P)[4][8
 // ---------------------------------------------------------------------------------------------------------------
 // REDO: the second launch of a call with the in-kernel floor test (thresh.hpp: FloorLazy): only the units whose test fired.
 template <int WAVES, bool REDO = false>
-__global__ __launch_bounds__(WAVES * 64, 3) void k_decide_fast256(Fast25Args A) {
+__global__ __launch_bounds__(WAVES * 64, 3) void k_decide_fast256(RegArgs A) {
   if (REDO && A.fl.alim[1] != A.tc.need_tag) return;   // no unit of this call reported (the common case)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   cf* tw512 = reinterpret_cast<cf*>(smem);
@@ -330,7 +304,7 @@ __global__ __launch_bounds__(WAVES * 64, 3) void k_decide_fast256(Fast25Args A) 
     if (sam) { q = __ffs((int)sam) - 1; fr = q >> 3; f = bin6(cs, q & 7); }
     else { q = -1; fr = __ffs((int)s128) - 1; f = 128; }
     const int64_t t = tq + 4 * gs + fr;
-    const Fast25Args& L = *late_args<Fast25Args>();     // (cold path: arguments re-read here, not kept live from the entry)
+    const RegArgs& L = *late_args<RegArgs>();     // (cold path: arguments re-read here, not kept live from the entry)
     const double Pe = f25_exact_power(L, row, chunk, t, f, lane);
     double t2 = L.tc.T2[f];
     if (floor_live) {
@@ -376,7 +350,7 @@ __global__ __launch_bounds__(WAVES * 64, 3) void k_decide_fast256(Fast25Args A) 
 
 // ---------------------------------------------------------------------------------------------------------------
 template <int WAVES>
-__global__ __launch_bounds__(WAVES * 64, 3) void k_mag_fast256(Fast25Args A) {
+__global__ __launch_bounds__(WAVES * 64, 3) void k_mag_fast256(RegArgs A) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   cf* tw512 = reinterpret_cast<cf*>(smem);
   cf* regions = tw512 + FN;
@@ -431,7 +405,7 @@ __global__ __launch_bounds__(WAVES * 64, 3) void k_mag_fast256(Fast25Args A) {
 // Apply: FFT -> x mask -> IFFT -> window -> overlap-add -> samples.  Tiles overlap by 3 frames: a tile of NF frames
 // completes NF - 3 hops on its own.
 template <int WAVES, bool KMASK>
-__global__ __launch_bounds__(WAVES * 64, 3) void k_apply_fast256(Fast25Args A) {
+__global__ __launch_bounds__(WAVES * 64, 3) void k_apply_fast256(RegArgs A) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   cf* tw512 = reinterpret_cast<cf*>(smem);
   cf* regions = tw512 + FN;

@@ -30,43 +30,17 @@ __host__ __device__ inline int bin5(int c, int sl) {   // bin of pair slot sl (0
   return sl < 8 ? 32 * sl : 16 + 32 * (sl - 8);        // (lane 0, slot 0 = bin 0; bin 256 rides separately)
 }
 
-struct Fast5Args {
-  View view;
-  Geom g;
-  const float* win;        // window, float32 (512)
-  const double* win64;     // window, float64 (512): exact refinement
-  const cf* tw512;         // w_512^j (512)
-  const cx<double>* tw64;  // w_512^j float64 (256 entries: j < 256; w^(j+256) = -w^j)
-  ThreshConsts tc;
-  double mag_scale, top_db;
-  unsigned long long* bits;  // decide: [units][T][5]
-  float* mag;                // magnitude: [units][T][FS]
-  const float* Mf;           // apply: float mask [units][T][FS], natural bin order
-  const unsigned short* K;   // apply<KMASK>: integer weight sums of the smoothed bit mask [units][T][FS] (mask = K / ktot)
-  float inv_ktot;
-  const float* wsq;          // apply: window squared (512)
-  const float* invn;         // apply: 1 / sum_q wsq[128 q + s], s < 128
-  OutMap om;
-  int64_t h_begin, h_end;    // apply: ext hops (128-sample blocks, ext = unit sample + padL) to produce
-  int normalize;
-  FloorLazy fl;              // decide: in-kernel floor test (thresh.hpp), alim == nullptr: flags computed a priori
-  float* part;               // apply / one-pass gate, seam mode: [units][tiles][6][hop] un-normalised partial hops (3 leading, 3 trailing: k_ola_seam), else nullptr
-  int n_tiles;
-  double iir_b;              // magnitude: the recurrence's b (non-stationary gate) ...
-  double* sub;               // ... and its per-tile partials [units][tiles][2][FS] (fastpath.hpp: mag_sub_partials), or nullptr
-};
-
 // stage tables + the tile's sample span, gather the lane's 32 complex points of its frame pair:
 // v[r] = (a[m], b[m]) * w[m], m = c + 16 r; frame A = tq + 2 g, frame B = A + 1.  `tf0`: first frame of the tile.
 // Returns with the span consumed (the exchange slices may be overwritten).
 template <int WAVES, bool MX = false>
-__device__ __forceinline__ unsigned f5_gather(const Fast5Args& A, cf* tw512, cf* regions, float* swin, int64_t row,
+__device__ __forceinline__ unsigned f5_gather(const RegArgs& A, cf* tw512, cf* regions, float* swin, int64_t row,
                                           int64_t chunk, int64_t tf0, int64_t t_lim, cf* v, bool& validA, bool& validB) {   // returns (MX) the largest |sample| this thread staged, as a bit pattern
   unsigned mx_ = 0u;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15;
   constexpr int NF = F5_FPW * WAVES, ROWS = NF - 1 + 4, SPAN = ROWS * F5_H;
   static_assert(ROWS * F5_XP * 4 <= WAVES * WAVE_CX_H * 8, "span must fit the exchange slices");
-  stage_tables<WAVES * 64, 128>(tw512, A.tw512, swin, A.win, tid);
+  stage_tables<WAVES * 64, 128>(tw512, A.tw, swin, A.win, tid);
   const Geom& G = A.g;
   const int64_t s0b = tf0 * F5_H - G.padL;
   const int64_t gb = chunk * A.view.cs - A.view.pad + s0b;
@@ -119,7 +93,7 @@ __device__ __forceinline__ void f5_pair(const cf* v, int sl, bool l0, cf& a, cf&
   b = sl < 8 ? sel(v[16 - sl], v[31 - sl]) : sel(v[39 - sl], v[31 - sl]);
 }
 
-__device__ __forceinline__ double f5_exact_power(const Fast5Args& A, int64_t row, int64_t chunk, int64_t t, int f, int lane) {
+__device__ __forceinline__ double f5_exact_power(const RegArgs& A, int64_t row, int64_t chunk, int64_t t, int f, int lane) {
   const int64_t s0 = t * F5_H - A.g.padL;
   double re = 0.0, im = 0.0;
 #pragma unroll 4
@@ -142,7 +116,7 @@ __device__ __forceinline__ double f5_exact_power(const Fast5Args& A, int64_t row
 // ---------------------------------------------------------------------------------------------------------------
 // REDO: the second launch of a call with the in-kernel floor test (thresh.hpp: FloorLazy): only the units whose test fired.
 template <int WAVES, bool REDO = false>
-__global__ __launch_bounds__(WAVES * 64, 3) void k_decide_fast512(Fast5Args A) {
+__global__ __launch_bounds__(WAVES * 64, 3) void k_decide_fast512(RegArgs A) {
   if (REDO && A.fl.alim[1] != A.tc.need_tag) return;   // no unit of this call reported (the common case)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   cf* tw512 = reinterpret_cast<cf*>(smem);
@@ -243,7 +217,7 @@ __global__ __launch_bounds__(WAVES * 64, 3) void k_decide_fast512(Fast5Args A) {
     else if (s256A) { which = 2; f = 256; }
     else { which = 3; f = 256; }
     const int64_t t = tq + 2 * gs + (which & 1);
-    const Fast5Args& L = *late_args<Fast5Args>();       // (cold path: arguments re-read here, not kept live from the entry)
+    const RegArgs& L = *late_args<RegArgs>();       // (cold path: arguments re-read here, not kept live from the entry)
     const double P = f5_exact_power(L, row, chunk, t, f, lane);
     double t2 = L.tc.T2[f];
     if (floor_live) {
@@ -304,7 +278,7 @@ __global__ __launch_bounds__(WAVES * 64, 3) void k_decide_fast512(Fast5Args A) {
 
 // ---------------------------------------------------------------------------------------------------------------
 template <int WAVES>
-__global__ __launch_bounds__(WAVES * 64, 3) void k_mag_fast512(Fast5Args A) {
+__global__ __launch_bounds__(WAVES * 64, 3) void k_mag_fast512(RegArgs A) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   cf* tw512 = reinterpret_cast<cf*>(smem);
   cf* regions = tw512 + FN;
@@ -365,7 +339,7 @@ __global__ __launch_bounds__(WAVES * 64, 3) void k_mag_fast512(Fast5Args A) {
 // Apply: FFT -> x mask -> IFFT -> window -> overlap-add -> samples.  Tiles overlap by 3 frames: a tile of NF frames
 // completes NF - 3 hops on its own.
 template <int WAVES, bool KMASK>
-__global__ __launch_bounds__(WAVES * 64, 3) void k_apply_fast512(Fast5Args A) {
+__global__ __launch_bounds__(WAVES * 64, 3) void k_apply_fast512(RegArgs A) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   cf* tw512 = reinterpret_cast<cf*>(smem);
   cf* regions = tw512 + FN;

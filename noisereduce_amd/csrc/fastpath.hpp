@@ -476,7 +476,7 @@ __device__ __forceinline__ void fft512_inv(cf* v, cf* fb, const cf* tw512, int c
 constexpr int FPITCH_H = 256 + 16;
 constexpr int WAVE_CX_H = 4 * FPITCH_H;
 
-// (round 6) Abutting tiles for the packed-transform geometries (n_fft = 512 / 256) as at n_fft = 2048 (fast2048.hpp): a tile of NF frames
+// (round 6) Abutting tiles for the register-transform geometries (n_fft = 512 / 256 / 2048): a tile of NF frames
 // completes NF - 3 hops; the 3 hops that straddle two tiles leave as partial sums -- part[unit][tile][6][HOP]: slots 0..2 the tile's
 // leading hops, 3..5 its trailing ones -- and k_ola_seam combines them: hop tf0(b + 1) + k = trailing k of tile b + leading k of tile
 // b + 1 (fixed order), normalised and stored.  Overlapping tiles redo 3 of every 32 / 64 transforms AND make 10 % more tiles: on two
@@ -492,6 +492,50 @@ struct SeamArgs {
   const float* part;
   int n_tiles;
 };
+// Arguments of the register-transform kernels of n_fft = 512 / 256 / 2048, hop = n_fft / 4 (fast512.hpp, fast256.hpp,
+// fast2048.hpp): decide, magnitude and apply.  Fields an entry point does not use stay zero.
+struct RegArgs {
+  View view;
+  Geom g;
+  const float* win;          // window, float32 (n_fft)
+  const double* win64;       // window, float64 (n_fft): exact refinement
+  const cf* tw;              // 512 / 256: w_512^j (512); 2048: w_2048^k, k < 1024
+  const cx<double>* tw64;    // w_n^j float64, j < n / 2 (w^(j + n/2) = -w^j)
+  ThreshConsts tc;
+  double mag_scale, top_db;
+  unsigned long long* bits;  // decide: [units][T][(F + 63) / 64]
+  float* mag;                // magnitude: [units][T][FS]
+  const float* Mf;           // apply: float mask [units][T][FS], natural bin order
+  const unsigned short* K;   // apply<KMASK>: integer weight sums of the smoothed bit mask [units][T][FS] (mask = K / ktot)
+  float inv_ktot;
+  const float* wsq;          // apply: window squared (n_fft)
+  const float* invn;         // apply: 1 / sum_q wsq[hop q + s], s < hop
+  OutMap om;
+  int64_t h_begin, h_end;    // apply: ext hops (hop-sample blocks, ext = unit sample + padL) to produce
+  int normalize;
+  FloorLazy fl;              // decide: in-kernel floor test (thresh.hpp), alim == nullptr: flags computed a priori
+  float* part;               // apply / one-pass gate, seam mode: [units][tiles][6][hop] un-normalised partial hops (3 leading, 3 trailing: k_ola_seam), else nullptr
+  int n_tiles;
+  double iir_b;              // magnitude: the recurrence's b (non-stationary gate) ...
+  double* sub;               // ... and its per-tile partials [units][tiles][2][FS] (fastpath.hpp: mag_sub_partials), or nullptr
+};
+
+// Arguments of the one-pass gates of the same geometries (onepass512.hpp, onepass256.hpp, onepass2048.hpp)
+struct OnePassRegArgs {
+  RegArgs A;                   // view, geometry, tables, compare constants, output map, hop range, floor test (FIRST: late_args)
+  unsigned long long* xbits;   // [units][n_tiles + 2][NF][XW][2] published mask bits: granules {32 bits, epoch}
+  unsigned* ticket;            // work counter: never reset, a launch takes exactly units * (n_tiles + 2) tickets
+  unsigned ticket_base;
+  unsigned epoch;
+  unsigned poll_epoch;         // = epoch; tests (SG_OPT_INJECT_HANDOFF_FAULT bits 3..4): a tag no producer writes, with spin_max = 0
+  int spin_max;                // polls per hand-off before the tile gives up (OP_SPIN_MAX)
+  unsigned* err;               // host-mapped word: bit 0 = a bit hand-off timed out
+  int nf, nt, n_tiles;
+  int scan_q;                  // in-kernel floor test: samples of the unit window's unstaged part that each tile scans
+  float prop;                  // prop_decrease: mask = prop K / ktot + (1 - prop)   (stationary.py:116-119: after the smoothing)
+  const unsigned long long* tab;   // MFMA operands + byte expansion (layout: the geometry's onepass*.hpp)
+};
+
 template <int HOP, int NF>
 __global__ __launch_bounds__(HOP) void k_ola_seam(SeamArgs A) {
   const Geom& G = A.g;

@@ -1,10 +1,10 @@
 // One-pass stationary gate for n_fft = win = 2048, hop = 512 (round 6): k_gate_onepass512 (onepass512.hpp) on the transforms of
 // fast2048.hpp -- one real frame per 32 lanes, a tile of 8 frames (4 wavefronts x 2), 1025 bins = 17 bit words per frame.
 //
-//   k_decide_fast2048 + k_smooth_bits2 + k_apply_fast2048<K> + k_ola_seam2048   ->   k_gate_onepass2048 + k_ola_seam2048
+//   k_decide_fast2048 + k_smooth_bits2 + k_apply_fast2048<K> + k_ola_seam<512, 8>   ->   k_gate_onepass2048 + k_ola_seam<512, 8>
 //
 // Tiles ABUT, as k_apply_fast2048's (overlapping by 3 frames would redo 3 of every 8 transforms): the 3 hops that straddle two
-// tiles leave as partial sums and k_ola_seam2048 combines them -- the bits are the only exchange inside the launch.
+// tiles leave as partial sums and k_ola_seam (fastpath.hpp) combines them -- the bits are the only exchange inside the launch.
 // Integer smoothing on the matrix cores, with two differences from the 512 / 256 kernels:
 //   * the frequency half-width is 10 bins at 48 kHz, 23 at 22.05 kHz (base.py:100: 500 Hz / (sr / 1024)): a 16-bin output block
 //     reads 16 + 2 nf <= 64 bins = TWO 32-bin k-blocks (band matrices Bf_lo: bins 16 b - 24 .., Bf_hi: bins 16 b + 8 ..), nf <= 24;
@@ -35,23 +35,8 @@ constexpr int O20_MAX_NF = 24;
 #ifndef O20_OCC
 #define O20_OCC 3
 #endif
-struct OnePass20Args {
-  Fast20Args A;                // FIRST (late_args); part / n_tiles: the seam partials
-  unsigned long long* xbits;   // [units][n_tiles + 2][8][17][2] published mask bits: granules {32 bits, epoch}
-  unsigned* ticket;
-  unsigned ticket_base;
-  unsigned epoch;
-  unsigned poll_epoch;         // = epoch; tests (SG_OPT_INJECT_HANDOFF_FAULT bits 3..4): a tag no producer writes, with spin_max = 0
-  int spin_max;                // polls per hand-off before the tile gives up (OP_SPIN_MAX)
-  unsigned* err;
-  int nf, nt, n_tiles;
-  int scan_q;
-  float prop;                  // prop_decrease (onepass512.hpp)
-  const unsigned long long* tab;
-};
-
 template <int WAVES, bool REDO = false>
-__global__ __launch_bounds__(WAVES * 64, O20_OCC) void k_gate_onepass2048(OnePass20Args P) {
+__global__ __launch_bounds__(WAVES * 64, O20_OCC) void k_gate_onepass2048(OnePassRegArgs P) {
   static_assert(WAVES == 4, "tile = 8 frames");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   cf* tw = reinterpret_cast<cf*>(smem);                 // [32][32] w_1024^(k1 c)
@@ -59,7 +44,7 @@ __global__ __launch_bounds__(WAVES * 64, O20_OCC) void k_gate_onepass2048(OnePas
   float* s_t2 = reinterpret_cast<float*>(regions + WAVES * WAVE_CX_H);   // [1025] compare constants x4
   unsigned* s_misc = reinterpret_cast<unsigned*>(s_t2 + 1028);           // [0] ticket, [1] lost hand-off
   unsigned long long* s_exp = reinterpret_cast<unsigned long long*>(s_misc + 4);   // [256] byte -> eight 0 / 1 bytes
-  const Fast20Args& A = P.A;
+  const RegArgs& A = P.A;
   if (REDO && A.fl.alim[1] != A.tc.need_tag) return;   // no unit of this call reported (the common case)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 5, c = lane & 31;
   const Geom& G = A.g;
@@ -124,7 +109,7 @@ __global__ __launch_bounds__(WAVES * 64, O20_OCC) void k_gate_onepass2048(OnePas
     asm volatile("" : "+v"(z0));
     fft1k_fwd(v, fb, tw + z0, c);
   }
-  const cf wl = A.tw2048[c];
+  const cf wl = A.tw[c];
   const int src = (lane & 32) | ((32 - c) & 31);
   const bool l0 = c == 0;
   unsigned long long myword = 0ull;   // lane c < 17 of group g: word c of frame tq + g
@@ -182,7 +167,7 @@ __global__ __launch_bounds__(WAVES * 64, O20_OCC) void k_gate_onepass2048(OnePas
         const int q = amb_s ? (__ffs((int)amb_s) - 1) : 32;
         const int cs = sl & 31, gs = sl >> 5;
         const int f = q < 32 ? cs + 32 * q : 1024;
-        const Fast20Args& L = *late_args<Fast20Args>();     // (cold path: arguments re-read here; A is the FIRST member)
+        const RegArgs& L = *late_args<RegArgs>();     // (cold path: arguments re-read here; A is the FIRST member)
         const double Pe = f20_exact_power(L, row, chunk, tq + gs, f, lane);
         double t2 = L.tc.T2[f];
         if (floor_live) {

@@ -29,23 +29,8 @@ constexpr int O25_MAX_NF = 8;
 #ifndef O25_OCC
 #define O25_OCC 3
 #endif
-struct OnePass25Args {
-  Fast25Args A;                // FIRST (late_args)
-  unsigned long long* xbits;   // [units][n_tiles + 2][64][3][2] published mask bits: granules {32 bits, epoch}
-  unsigned* ticket;
-  unsigned ticket_base;
-  unsigned epoch;
-  unsigned poll_epoch;         // = epoch; tests (SG_OPT_INJECT_HANDOFF_FAULT bits 3..4): a tag no producer writes, with spin_max = 0
-  int spin_max;                // polls per hand-off before the tile gives up (OP_SPIN_MAX)
-  unsigned* err;
-  int nf, nt, n_tiles;
-  int scan_q;
-  float prop;                  // prop_decrease (onepass512.hpp)
-  const unsigned long long* tab;
-};
-
 template <int WAVES, bool REDO = false>
-__global__ __launch_bounds__(WAVES * 64, O25_OCC) void k_gate_onepass256(OnePass25Args P) {
+__global__ __launch_bounds__(WAVES * 64, O25_OCC) void k_gate_onepass256(OnePassRegArgs P) {
   static_assert(WAVES == 4, "tile = 64 frames");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   cf* tw512 = reinterpret_cast<cf*>(smem);
@@ -54,7 +39,7 @@ __global__ __launch_bounds__(WAVES * 64, O25_OCC) void k_gate_onepass256(OnePass
   float* s_t2 = swin + F25_N;                // [129] float32 compare constants x4
   unsigned* s_misc = reinterpret_cast<unsigned*>(s_t2 + F25_T2);   // [0] ticket, [1] lost hand-off
   unsigned long long* s_exp = reinterpret_cast<unsigned long long*>(s_misc + 4);   // [256] byte -> eight 0 / 1 bytes
-  const Fast25Args& A = P.A;
+  const RegArgs& A = P.A;
   if (REDO && A.fl.alim[1] != A.tc.need_tag) return;   // no unit of this call reported (the common case)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15, cp = c >> 1;
   const Geom& G = A.g;
@@ -179,7 +164,7 @@ __global__ __launch_bounds__(WAVES * 64, O25_OCC) void k_gate_onepass256(OnePass
         if (sam) { q = __ffs((int)sam) - 1; fr = q >> 3; f = bin6(cs, q & 7); }
         else { q = -1; fr = __ffs((int)s128) - 1; f = 128; }
         const int64_t t = tq + 4 * gs + fr;
-        const Fast25Args& L = *late_args<Fast25Args>();     // (A is the FIRST member of the kernel's argument)
+        const RegArgs& L = *late_args<RegArgs>();     // (A is the FIRST member of the kernel's argument)
         const double Pe = f25_exact_power(L, row, chunk, t, f, lane);
         double t2 = L.tc.T2[f];
         if (floor_live) {

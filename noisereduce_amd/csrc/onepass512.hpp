@@ -43,23 +43,8 @@ constexpr int O5_MAX_NF = 8;                       // the 32 x 16 band matrix of
 #ifndef O5_OCC
 #define O5_OCC 3   // workgroups per CU the register budget is set for
 #endif
-struct OnePass5Args {
-  Fast5Args A;                 // view, geometry, tables, compare constants, output map, hop range, floor test (FIRST: late_args)
-  unsigned long long* xbits;   // [units][n_tiles + 2][32][5][2] published mask bits: granules {32 bits, epoch}
-  unsigned* ticket;            // work counter: never reset, a launch takes exactly units * (n_tiles + 2) tickets
-  unsigned ticket_base;
-  unsigned epoch;
-  unsigned poll_epoch;         // = epoch; tests (SG_OPT_INJECT_HANDOFF_FAULT bits 3..4): a tag no producer writes, with spin_max = 0
-  int spin_max;                // polls per hand-off before the tile gives up (OP_SPIN_MAX)
-  unsigned* err;               // host-mapped word: bit 0 = a bit hand-off timed out
-  int nf, nt, n_tiles;
-  int scan_q;                  // in-kernel floor test: samples of the unit window's unstaged part that each tile scans
-  float prop;                  // prop_decrease: mask = prop K / ktot + (1 - prop)   (stationary.py:116-119: after the smoothing)
-  const unsigned long long* tab;   // MFMA operands + byte expansion (see above)
-};
-
 template <int WAVES, bool REDO = false>
-__global__ __launch_bounds__(WAVES * 64, O5_OCC) void k_gate_onepass512(OnePass5Args P) {
+__global__ __launch_bounds__(WAVES * 64, O5_OCC) void k_gate_onepass512(OnePassRegArgs P) {
   static_assert(WAVES == 4, "tile = 32 frames");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   cf* tw512 = reinterpret_cast<cf*>(smem);
@@ -68,7 +53,7 @@ __global__ __launch_bounds__(WAVES * 64, O5_OCC) void k_gate_onepass512(OnePass5
   float* s_t2 = swin + F5_N;                 // [257] float32 compare constants x4 (the split works on 2 X)
   unsigned* s_misc = reinterpret_cast<unsigned*>(s_t2 + 264);   // [0] ticket, [1] lost hand-off
   unsigned long long* s_exp = reinterpret_cast<unsigned long long*>(s_misc + 4);   // [256] byte -> eight 0 / 1 bytes
-  const Fast5Args& A = P.A;
+  const RegArgs& A = P.A;
   if (REDO && A.fl.alim[1] != A.tc.need_tag) return;   // no unit of this call reported (the common case)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15;
   const Geom& G = A.g;
@@ -203,7 +188,7 @@ __global__ __launch_bounds__(WAVES * 64, O5_OCC) void k_gate_onepass512(OnePass5
         else if (s256A) { which = 2; f = 256; }
         else { which = 3; f = 256; }
         const int64_t t = tq + 2 * gs + (which & 1);
-        const Fast5Args& L = *late_args<Fast5Args>();       // (cold path: arguments re-read here; A is the FIRST member)
+        const RegArgs& L = *late_args<RegArgs>();       // (cold path: arguments re-read here; A is the FIRST member)
         const double Pe = f5_exact_power(L, row, chunk, t, f, lane);
         double t2 = L.tc.T2[f];
         if (floor_live) {

@@ -289,7 +289,7 @@ def test_nfft2048_decisions_equal_the_float64_decisions(nr):
     assert bits_fast.shape == bits_64.shape and d1 - d0 > 300
     assert np.array_equal(bits_fast[:, d0:d1], bits_64[:, d0:d1])
     assert torch.equal(out_fast, out_64)
-    # ... and the four-kernel path (k_decide_fast2048 + k_smooth_bits2 + k_apply_fast2048 + k_ola_seam2048): same bits, same samples
+    # ... and the four-kernel path (k_decide_fast2048 + k_smooth_bits2 + k_apply_fast2048 + k_ola_seam<512, 8>): same bits, same samples
     sg._gate.set_option(_ffi.SG_OPT_FORCE_SPLIT, 1)
     try:
         out_3k = sg.get_traces().clone()

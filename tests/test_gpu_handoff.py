@@ -255,7 +255,7 @@ def test_lost_handoff_poisons_the_output(nr, stationary, bits, what):
 @pytest.mark.parametrize("n_fft", [256, 512, 2048])
 def test_lost_handoff_poisons_the_small_onepass_gates(nr, n_fft):
     """The same for k_gate_onepass256 / 512 / 2048 (round 6): a tile whose neighbours' bits never arrive poisons every hop it
-    touches (2048: complete hops AND the partial sums k_ola_seam2048 combines), sets the error word itself, and the next
+    touches (2048: complete hops AND the partial sums k_ola_seam<512, 8> combines), sets the error word itself, and the next
     call on the handle is clean."""
     from noisereduce_amd import _ffi
     from noisereduce_amd.spectralgate.stationary import SpectralGateStationary
