@@ -212,6 +212,28 @@ SG_API int sg_process_batch_backward(sg_handle* h, const void* grad_out_dev, int
                               int64_t L, int64_t go_stride, const float* mask_dev,
                               void* grad_x_dev, int64_t gx_stride, void* stream);
 
+/* sg_process_batch for a PADDED batch: row i of x (B, L) holds lengths[i] samples of audio, 2 * win_length <= lengths[i] <= L,
+ * and padding after them (host array of B entries; NULL: every row is full).  With T_i = 1 + lengths[i] / hop and
+ * Lout_i = hop * (lengths[i] / hop): out[i][0 .. Lout_i) is what sg_process_batch returns for the row alone at length
+ * lengths[i] (statistics, moving mean, mask smoothing and window envelope over the row's own T_i frames), and
+ * out[i][Lout_i .. sg_output_length(L)) is 0.  Samples at or beyond lengths[i] are never read.  xn_lengths: the same for the
+ * rows of xn (Bn entries, each in [2 * win_length, Ln]; NULL: full).  A row's result does not depend on the other rows,
+ * their order or L.  mask_out_dev as in sg_process_batch (frames >= T_i of row i are 0; natural bin order), for
+ * sg_process_rows_backward.  Power-of-two n_fft from 256 to 4096 (SG_E_UNSUPPORTED otherwise); float32 / float64 rows.
+ * Rows are packed into sub-batches under the handle's max_workspace_bytes (0: 4 GiB); a fixed number of launches per
+ * sub-batch.  Enqueues only. */
+SG_API int sg_process_rows(sg_handle* h, const void* x_dev, int dtype, int64_t B, int64_t L, int64_t x_stride,
+                           const int64_t* lengths, const void* xn_dev, int64_t Bn, int64_t Ln, int64_t xn_stride,
+                           const int64_t* xn_lengths, void* out_dev, int out_dtype, int64_t out_stride,
+                           float* mask_out_dev, void* stream);
+
+/* Adjoint of sg_process_rows with the mask held fixed: grad_out (B, sg_output_length(L)) -> grad_x (B, L).
+ * grad_x[i][0 .. lengths[i]) is the gradient of the row alone, grad_x[i][lengths[i] .. L) is 0, and
+ * grad_out[i][Lout_i ..) is never read. */
+SG_API int sg_process_rows_backward(sg_handle* h, const void* grad_out_dev, int dtype, int64_t B, int64_t L,
+                                    int64_t go_stride, const int64_t* lengths, const float* mask_dev, void* grad_x_dev,
+                                    int64_t gx_stride, void* stream);
+
 /* ---- stage taps (used by the parity tests; also plain STFT/ISTFT operators) ------ */
 
 /* Forward STFT of (B, L) rows -> complex float64 Z[B][T][F] (interleaved re,im), same

@@ -39,6 +39,8 @@ SG_API int sg_debug_fetch(sg_handle* h, int32_t what, void* host, int64_t bytes,
 SG_API int sg_debug_clip_thresholds(sg_handle* h, double* host, int32_t n_noise, int32_t n_bins, void* stream);
 /* Sub-batches the last sg_process_clips call was split into. */
 SG_API int sg_debug_clip_batches(const sg_handle* h, int64_t* value);
+/* Sub-batches the last sg_process_rows / sg_process_rows_backward call was split into. */
+SG_API int sg_debug_rows_batches(const sg_handle* h, int64_t* value);
 
 /* ---- development options (sg_set_option / sg_get_option of mi355gate.h) ----------------- */
 #define SG_OPT_FORCE_UNFUSED 1 /* value != 0: use the materialised (v1) kernels everywhere */
@@ -99,7 +101,8 @@ SG_API int sg_debug_clip_batches(const sg_handle* h, int64_t* value);
 #define SG_STAGE_ROW_GATE 17   /* k_row_gate: TorchGate.forward of a whole row (<= 64 frames) in one kernel */
 #define SG_STAGE_IIR_CHAIN 18 /* non-stationary gate: carries of the time tiles (k_iir_chain_par; serial form k_iir_part / k_iir_comb + k_iir_chain) */
 #define SG_STAGE_IIR_MASK 19  /* non-stationary gate: k_iir_mask<nt> -- recurrence, sigmoid and both smoothing passes in one kernel */
-/* ragged batches (sg_process_clips, ragged.hip): one launch of each per sub-batch */
+/* ragged batches (sg_process_clips, ragged.hip): one launch of each per sub-batch.  sg_process_rows (rows.hip) books its
+ * launches under the same seven stages (its moving mean under SG_STAGE_RG_IIR). */
 #define SG_STAGE_RG_NOISE_POWER 20 /* stationary: float64 transform of every noise frame */
 #define SG_STAGE_RG_NOISE_FINAL 21 /* stationary: per-source band maxima, moments, thresholds, compare constants */
 #define SG_STAGE_RG_DECIDE 22      /* float64 transform of every data frame: decision bits + band maxima (stationary) / magnitudes */

@@ -97,6 +97,11 @@ _PROTOTYPES = {
                                  c_void_p]),
     "sg_process_batch_backward": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64,
                                           c_void_p, c_void_p, c_int64, c_void_p]),
+    "sg_process_rows": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64,
+                                c_int64, c_int64, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p]),
+    "sg_process_rows_backward": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                                         c_void_p, c_int64, c_void_p]),
+    "sg_debug_rows_batches": (c_int, [c_void_p, POINTER(c_int64)]),
     "sg_stft": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
     "sg_clips_workspace_bytes": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, POINTER(c_int64)]),
     "sg_process_clips": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int32, c_void_p, c_int64,
@@ -412,6 +417,65 @@ class Gate:
                 self._h, grad_out.data_ptr(), _sg_dtype(grad_out), B, L, gs, mask.data_ptr(),
                 gx.data_ptr(), L, self._stream()))
         return gx
+
+    # -- variant T: padded batches of different-length rows (sg_process_rows) ------------------------
+    @staticmethod
+    def _lengths(lengths, count):
+        """Host int64 array for the C ABI (None stays None: every row full)."""
+        if lengths is None:
+            return None, None
+        a = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1))
+        if a.shape[0] != count:
+            raise ValueError(f"expected {count} lengths, got {a.shape[0]}")
+        return a, a.ctypes.data_as(c_void_p)
+
+    def process_rows(self, x, lengths, xn=None, xn_lengths=None, out_dtype=None, save_mask=False):
+        """TorchGate.forward on a padded batch: row i holds lengths[i] samples (host integers) and padding after
+        them.  Returns (B, output_length(L)); row i is the gate of x[i, :lengths[i]] alone, zeros beyond
+        hop * (lengths[i] // hop).  With save_mask=True also the (B, T, FS) float32 mask (natural bin order, frames
+        beyond the row's own zero) for process_rows_backward."""
+        self._on_device(x)
+        x, xs = _rows(x)
+        B, L = x.shape
+        Lout = self.output_length(L)
+        out = torch.empty((B, Lout), dtype=out_dtype or x.dtype, device=self.device)
+        mask = None
+        if save_mask:
+            FS = (self.n_bins + 15) // 16 * 16
+            mask = torch.empty((B, self.n_frames(L), FS), dtype=torch.float32, device=self.device)
+        if xn is not None:
+            self._on_device(xn)
+            if xn.dtype != x.dtype:
+                xn = xn.to(x.dtype)
+            xn, xns = _rows(xn)
+            xn_ptr, Bn, Ln = xn.data_ptr(), xn.shape[0], xn.shape[1]
+        else:
+            xn_ptr, Bn, Ln, xns = None, 0, 0, 0
+        la, lp = self._lengths(lengths, B)
+        na, np_ = self._lengths(xn_lengths if xn is not None else None, Bn)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.sg_process_rows(
+                self._h, x.data_ptr(), _sg_dtype(x), B, L, xs, lp, xn_ptr, Bn, Ln, xns, np_, out.data_ptr(),
+                _sg_dtype(out), Lout, None if mask is None else mask.data_ptr(), self._stream()))
+        return (out, mask) if save_mask else out
+
+    def process_rows_backward(self, grad_out, mask, L, lengths):
+        """Adjoint of process_rows with the mask fixed: (B, Lout) -> (B, L), zero at and beyond lengths[i]."""
+        self._on_device(grad_out)
+        grad_out, gs = _rows(grad_out)
+        B = grad_out.shape[0]
+        gx = torch.empty((B, L), dtype=grad_out.dtype, device=self.device)
+        la, lp = self._lengths(lengths, B)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.sg_process_rows_backward(
+                self._h, grad_out.data_ptr(), _sg_dtype(grad_out), B, L, gs, lp, mask.data_ptr(),
+                gx.data_ptr(), L, self._stream()))
+        return gx
+
+    def rows_batches(self):
+        v = c_int64()
+        self._check(self.lib.sg_debug_rows_batches(self._h, byref(v)))
+        return int(v.value)
 
     # -- ragged batches (sg_process_clips) ---------------------------------------------------------
     def process_clips(self, x, clips, out, noise=None, noise_srcs=(), max_workspace_bytes=0):

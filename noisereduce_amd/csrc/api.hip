@@ -40,6 +40,7 @@
 #include "exact.hpp"
 #include "apply64.hpp"
 #include "ragged.hpp"
+#include "rows.hpp"
 
 // complex transform length from which a whole 256-thread workgroup (instead of one wavefront) works on ONE frame in
 // the general LDS kernels: at N = 2048 (n_fft = 4096) a wavefront holds 4 radix-8 butterflies = 64 complex values per
@@ -197,6 +198,7 @@ struct sg_handle {
   double prof_ms[SG_N_STAGES] = {0};
   int64_t prof_cnt[SG_N_STAGES] = {0};
   sg::RgState* rg = nullptr;        // ragged batches (sg_process_clips, ragged.hip): workspace and threshold tap
+  sg::RwState* rw = nullptr;        // padded batches of different-length rows (sg_process_rows, rows.hip): workspace
   std::string err;
 };
 
@@ -1313,6 +1315,7 @@ extern "C" int sg_destroy(sg_handle* h) {
                     &h->big_ch, &h->big_bh, &h->big_W, &h->big_W2, &h->xP, &h->xraw, &h->xM, &h->xtmp, &h->xseg, &h->rg_count, &h->alim, &h->nss, &h->mr_pt32, &h->mr_pt64, &h->regtab})
     free_buf(*b);
   sg::rg_free(h->rg);
+  sg::rw_free(h->rw);
   delete h;
   return SG_OK;
 }
@@ -3654,5 +3657,44 @@ extern "C" int sg_debug_clip_thresholds(sg_handle* h, double* host, int32_t n_no
 extern "C" int sg_debug_clip_batches(const sg_handle* h, int64_t* value) {
   if (!h || !value) return SG_E_INVALID;
   *value = sg::rg_last_batches(h->rg);
+  return SG_OK;
+}
+
+// ---- padded batches of different-length rows: thin wrappers over rows.hip ---------------------------------------------
+static int64_t rw_budget(const sg_handle* h) { return h->p.max_workspace_bytes > 0 ? h->p.max_workspace_bytes : 0; }
+
+extern "C" int sg_process_rows(sg_handle* h, const void* x_dev, int dtype, int64_t B, int64_t L, int64_t x_stride,
+                               const int64_t* lengths, const void* xn_dev, int64_t Bn, int64_t Ln, int64_t xn_stride,
+                               const int64_t* xn_lengths, void* out_dev, int out_dtype, int64_t out_stride,
+                               float* mask_out_dev, void* stream) {
+  if (!h) return SG_E_INVALID;
+  if (h->p.variant != SG_VARIANT_T) FAIL(h, SG_E_INVALID, "sg_process_rows is a variant-T entry point");
+  if (!x_dev || !out_dev || (dtype != SG_F32 && dtype != SG_F64) || (out_dtype != SG_F32 && out_dtype != SG_F64) || B < 1 ||
+      x_stride < L || out_stride < 0)
+    FAIL(h, SG_E_INVALID, "sg_process_rows: bad argument");
+  if (L < 2 * (int64_t)h->W) FAIL(h, SG_E_INVALID, "x must be bigger than %d", 2 * h->W);  // torchgate.py:215-216
+  if (xn_dev) {
+    if (Ln < 2 * (int64_t)h->W) FAIL(h, SG_E_INVALID, "xn must be bigger than %d", 2 * h->W);  // :219-220
+    if (Bn != 1 && Bn != B) FAIL(h, SG_E_INVALID, "xn rows (%lld) must be 1 or the batch size", (long long)Bn);
+  }
+  return sg::rw_process(&h->rw, rg_ctx(h), h->p.n_movemean, x_dev, dtype, B, L, x_stride, lengths, xn_dev, Bn, Ln, xn_stride,
+                        xn_lengths, out_dev, out_dtype, out_stride, mask_out_dev, rw_budget(h), (hipStream_t)stream, &h->err);
+}
+
+extern "C" int sg_process_rows_backward(sg_handle* h, const void* grad_out_dev, int dtype, int64_t B, int64_t L,
+                                        int64_t go_stride, const int64_t* lengths, const float* mask_dev, void* grad_x_dev,
+                                        int64_t gx_stride, void* stream) {
+  if (!h) return SG_E_INVALID;
+  if (h->p.variant != SG_VARIANT_T) FAIL(h, SG_E_INVALID, "sg_process_rows_backward is a variant-T entry point");
+  if (!grad_out_dev || !grad_x_dev || !mask_dev || B < 1 || (dtype != SG_F32 && dtype != SG_F64) || gx_stride < L ||
+      L < 2 * (int64_t)h->W)
+    FAIL(h, SG_E_INVALID, "sg_process_rows_backward: bad argument");
+  return sg::rw_backward(&h->rw, rg_ctx(h), grad_out_dev, dtype, B, L, go_stride, lengths, mask_dev, grad_x_dev, gx_stride,
+                         rw_budget(h), (hipStream_t)stream, &h->err);
+}
+
+extern "C" int sg_debug_rows_batches(const sg_handle* h, int64_t* value) {
+  if (!h || !value) return SG_E_INVALID;
+  *value = sg::rw_last_batches(h->rw);
   return SG_OK;
 }

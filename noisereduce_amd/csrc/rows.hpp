@@ -1,0 +1,37 @@
+// Padded batches of different-length rows (sg_process_rows / sg_process_rows_backward, mi355gate.h): TorchGate.forward
+// on a (B, L) tensor whose row i holds lengths[i] samples of audio and padding after them.
+//
+// sg_process_batch takes one Geom per launch -- one length and one frame count for every row.  Here every row has its
+// own length, frame count T_i = 1 + len_i / hop and output length hop * (len_i / hop), and every kernel finds its work
+// through a TILE TABLE (workgroup -> row or noise row, first / last frame, band or sample), as ragged.hip's do: the
+// number of launches per sub-batch is fixed, whatever the batch size and the lengths.
+//
+// This header is shared by api.hip (thin C wrappers, sg_handle) and rows.hip (tables, kernels); it holds no kernels.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <string>
+
+#include "ragged.hpp"
+
+namespace sg {
+
+struct RwState;   // per-handle workspace of the rows path (rows.hip)
+void rw_free(RwState* s);
+
+// c: the handle's geometry and gate parameters (RgCtx; cs / pad / iir_b unused); kbox: moving-mean length of the
+// non-stationary gate.  lengths / xn_lengths: host arrays or nullptr (every row full).  mask_out: nullptr or
+// float[B][1 + L / H][FS].  max_ws: sub-batch budget in bytes (<= 0: 4 GiB).
+int rw_process(RwState** sp, const RgCtx& c, int kbox, const void* x_dev, int dtype, int64_t B, int64_t L, int64_t x_stride,
+               const int64_t* lengths, const void* xn_dev, int64_t Bn, int64_t Ln, int64_t xn_stride,
+               const int64_t* xn_lengths, void* out_dev, int out_dtype, int64_t out_stride, float* mask_out,
+               int64_t max_ws, hipStream_t st, std::string* err);
+// adjoint with the mask fixed: grad_out (B, H * (L / H)) -> grad_x (B, L); mask: what rw_process wrote
+int rw_backward(RwState** sp, const RgCtx& c, const void* go_dev, int dtype, int64_t B, int64_t L, int64_t go_stride,
+                const int64_t* lengths, const float* mask, void* gx_dev, int64_t gx_stride, int64_t max_ws,
+                hipStream_t st, std::string* err);
+// sub-batches the last call was split into
+int64_t rw_last_batches(const RwState* s);
+
+}  // namespace sg

@@ -10,6 +10,7 @@ from typing import Optional, Union
 import torch
 
 from noisereduce_amd import _ffi
+from noisereduce_amd.torchgate import rows as _rows
 from noisereduce_amd.torchgate.utils import linspace
 
 
@@ -31,6 +32,30 @@ class _GateFunction(torch.autograd.Function):
         (mask,) = ctx.saved_tensors
         gx = ctx.gate.process_batch_backward(grad_out.contiguous(), mask, ctx.L)
         return gx, None, None
+
+
+class _RowsFunction(torch.autograd.Function):
+    """forward(x, lengths=...): the table-driven kernels of csrc/rows.hip.  ``lengths`` / ``xn_lengths`` are host int64
+    arrays (or None); the backward gets the same lengths."""
+
+    @staticmethod
+    def forward(ctx, x, xn, module, lengths, xn_lengths):
+        gate = module._gate_for(x.device)
+        if ctx.needs_input_grad[0]:
+            y, mask = gate.process_rows(x.detach(), lengths, xn, xn_lengths, save_mask=True)
+            ctx.gate = gate
+            ctx.L = x.shape[-1]
+            ctx.lengths = lengths
+            ctx.save_for_backward(mask)
+        else:
+            y = gate.process_rows(x, lengths, xn, xn_lengths)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (mask,) = ctx.saved_tensors
+        gx = ctx.gate.process_rows_backward(grad_out.contiguous(), mask, ctx.L, ctx.lengths)
+        return gx, None, None, None, None
 
 
 class TorchGate(torch.nn.Module):
@@ -108,11 +133,25 @@ class TorchGate(torch.nn.Module):
             self._gates[key] = g
         return g
 
-    def forward(self, x: torch.Tensor, xn: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, xn: Optional[torch.Tensor] = None, lengths=None,
+                xn_lengths=None) -> torch.Tensor:
         """x: (batch, signal_length); xn: optional noise signal(s) for the stationary
         statistics.  Returns (batch, hop*(signal_length//hop)) in x.dtype
-        (torchgate.py:200-264)."""
+        (torchgate.py:200-264).
+
+        lengths: None, or one integer per row (sequence, numpy array, CPU or device tensor -- a device tensor is
+        copied to the host, which synchronises) for a zero-padded batch: row i holds ``lengths[i]`` samples,
+        ``2 * win_length <= lengths[i] <= signal_length``.  ``y[i, :hop * (lengths[i] // hop)]`` is then what
+        ``forward(x[i:i+1, :lengths[i]], xn_i)`` returns -- band statistics, moving mean, mask smoothing and window
+        envelope over the row's own frames -- and the rest of the row is 0.  ``x[i, lengths[i]:]`` is never read, a
+        row does not depend on the other rows, and the gradient is 0 beyond ``lengths[i]``.  xn_lengths: the same
+        for the rows of ``xn`` (1 or batch integers).  When every length equals the padded length the call takes
+        the full-length path and is bitwise ``forward(x, xn)``.  Power-of-two n_fft from 256 to 4096 gate the whole
+        batch in a fixed number of launches (csrc/rows.hip); any other n_fft loops over the rows through the
+        full-length path (correct, one call per row)."""
         assert x.ndim == 2
+        if lengths is not None or xn_lengths is not None:
+            return self._forward_rows(x, xn, lengths, xn_lengths)
         if x.shape[-1] < self.win_length * 2:
             raise Exception(f"x must be bigger than {self.win_length * 2}")
         assert xn is None or xn.ndim == 1 or xn.ndim == 2
@@ -133,6 +172,55 @@ class TorchGate(torch.nn.Module):
             if self.nonstationary:
                 xn = None  # unused by the non-stationary mask (torchgate.py:235-236)
         y = _GateFunction.apply(x, xn, self)
+        return y.to(dtype=dtype)
+
+    def _forward_rows(self, x, xn, lengths, xn_lengths):
+        """forward with per-row lengths: validation, then the full-length path (every row full), the table-driven
+        kernels, or -- for an n_fft they are not built for -- one full-length call per row."""
+        assert xn is None or xn.ndim == 1 or xn.ndim == 2
+        B, L = x.shape
+        if L < self.win_length * 2:
+            raise Exception(f"x must be bigger than {self.win_length * 2}")
+        if xn is not None and xn.shape[-1] < self.win_length * 2:
+            raise Exception(f"xn must be bigger than {self.win_length * 2}")
+        if lengths is not None:
+            lengths = _rows.as_lengths(lengths, B)
+            _rows.plan(lengths, L, self.win_length, self.hop_length)
+        if xn_lengths is not None:
+            if xn is None:
+                raise ValueError("xn_lengths given without xn")
+            Bn = 1 if xn.ndim == 1 else xn.shape[0]
+            if Bn != 1 and Bn != B:
+                raise ValueError(f"xn rows ({Bn}) must be 1 or the batch size")
+            xn_lengths = _rows.as_lengths(xn_lengths, Bn, "xn_lengths")
+            _rows.plan(xn_lengths, xn.shape[-1], self.win_length, self.hop_length, "xn_lengths")
+        if x.device.type != "cuda":
+            raise RuntimeError("noisereduce_amd.TorchGate runs on the GPU only (no CPU fallback): "
+                               "move the input with x.to('cuda')")
+        if _rows.all_full(lengths, L) and (xn is None or _rows.all_full(xn_lengths, xn.shape[-1])):
+            return self.forward(x, xn)
+        if not _rows.native(self.n_fft):
+            H = self.hop_length
+            y = x.new_zeros((B, H * (L // H)))
+            for i in range(B):
+                n = L if lengths is None else int(lengths[i])
+                xi = None
+                if xn is not None:
+                    xi = xn if xn.ndim == 1 else xn[(i if xn.shape[0] > 1 else 0)][None]
+                    if xn_lengths is not None:
+                        xi = xi[..., :int(xn_lengths[i if len(xn_lengths) > 1 else 0])]
+                y[i, :H * (n // H)] = self.forward(x[i:i + 1, :n], xi)[0]
+            return y
+        dtype = x.dtype
+        if dtype not in (torch.float32, torch.float64):
+            x = x.float()
+        if xn is not None:
+            xn = xn.detach().to(device=x.device, dtype=x.dtype)
+            if xn.ndim == 1:
+                xn = xn.unsqueeze(0)
+            if self.nonstationary:
+                xn, xn_lengths = None, None  # unused by the non-stationary mask (torchgate.py:235-236)
+        y = _RowsFunction.apply(x, xn, self, lengths, xn_lengths)
         return y.to(dtype=dtype)
 
     def __getstate__(self):
