@@ -62,6 +62,7 @@ def test_float64_transform_against_rfft(n_fft):
     (352, 16000, 30000, dict(chunk_size=12000, padding=1500)),
     (416, 16000, 30000, dict(chunk_size=12000, padding=1500)),
     (3600, 48000, 130000, dict(chunk_size=60000, padding=9000, time_mask_smooth_ms=200)),
+    (4000, 48000, 140000, dict(chunk_size=60000, padding=9000, time_mask_smooth_ms=200)),   # N = 2000: ~152 KB of LDS, one workgroup per CU
 ])
 def test_reduce_noise_matches_the_oracle(nr, n_fft, sr, n, extra, stationary):
     y = O.synth_signal(n, sr=sr, seed=n_fft + 1, tone_hz=sr / 31.0).astype(np.float32)

@@ -1,0 +1,340 @@
+"""Every gate path against the float64 oracle stage by stage and hop block by hop block (tests/parity_budget.py).
+
+One matrix (parity_budget.CELLS: kernel family x column settings), three checks per cell:
+
+a. decision bits (stationary): the kernel's bits inside ``debug_range()`` equal the oracle's ``raw`` of the same unit --
+   every unit, every channel, all F bands; no differing cell outside the 1e-8 dB ambiguity margin, at most 1e-5 of a
+   unit's cells inside it;
+b. the smoothed mask, whole field incl. bands 0 and F - 1 and the first / last column, wherever a float mask exists
+   (``debug_field(1)``; the non-stationary raw sigmoid through ``debug_field(0)``); which fields a route must keep
+   follows from the kernels it launched, and each route must launch the kernels its cell is labelled with;
+c. the output of every unit, per hop block of the kept range, within FACTOR x the float32 emulation's error there
+   (``precision="float64"`` cells: 1e-12 of the block's own peak) -- for the default route and every forced route.
+
+Then (a) / (c) for TorchGate.forward: row gate, four-kernel path, ``lengths=`` rows (those: the final mask the call
+hands back, against the oracle's).
+
+The largest local_error / budget per family and route goes to the file named by PARITY_BUDGET_OUT, if set
+(profiles/parity_budget.json is that file from an MI355X run)."""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import spectralgate_oracle as O
+from tests import parity_budget as PB
+
+pytestmark = pytest.mark.gpu
+
+_RATIOS = {}
+
+
+def _note(family, route, ratio):
+    key = "%s/%s" % (family, route)
+    _RATIOS[key] = max(_RATIOS.get(key, 0.0), float(ratio))
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _dump_ratios():
+    yield
+    path = os.environ.get("PARITY_BUDGET_OUT")
+    if path:
+        with open(path, "w") as f:
+            json.dump({"factor_allowed": PB.FACTOR, "largest_local_error_over_budget": dict(sorted(_RATIOS.items()))},
+                      f, indent=1)
+
+
+def _make_sg(case):
+    from noisereduce_amd.spectralgate.nonstationary import SpectralGateNonStationary
+    from noisereduce_amd.spectralgate.stationary import SpectralGateStationary
+    kw = case["kw"]
+    y = case["y"].astype(case["dtype"])
+    base = dict(y=y, sr=PB.SR, prop_decrease=kw["prop_decrease"], chunk_size=kw["chunk_size"], padding=kw["padding"],
+                n_fft=kw["n_fft"], win_length=kw.get("win_length"), hop_length=kw.get("hop_length"), time_constant_s=2.0,
+                freq_mask_smooth_hz=kw.get("freq_mask_smooth_hz", 500), time_mask_smooth_ms=kw.get("time_mask_smooth_ms", 50),
+                tmp_folder=None, use_tqdm=False, n_jobs=1, precision=case["precision"])
+    if kw["stationary"]:
+        yn = None if case["y_noise"] is None else case["y_noise"].astype(case["dtype"])
+        return SpectralGateStationary(y_noise=yn, n_std_thresh_stationary=1.5, clip_noise_stationary=True, **base)
+    return SpectralGateNonStationary(thresh_n_mult_nonstationary=2, sigmoid_slope_nonstationary=10, **base)
+
+
+def _routes(cell, case):
+    from noisereduce_amd import _ffi
+    routes = [("default", [])]
+    if case["precision"] == "float64":
+        return routes
+    if cell["family"] == "register":
+        routes.append(("force_split", [(_ffi.SG_OPT_FORCE_SPLIT, 1)]))
+    routes.append(("force_nofast", [(_ffi.SG_OPT_FORCE_NOFAST, 1)]))
+    routes.append(("force_unfused", [(_ffi.SG_OPT_FORCE_UNFUSED, 1)]))
+    return routes
+
+
+# sg_debug_fetch refuses a field the last call's kernels did not keep with one of these messages (api.hip); any other
+# error -- a size mismatch, a lost hand-off -- is an error
+_NO_SUCH_FIELD = ("fetch field 3", "bit field only exists on the fused path", "lane order",
+                  "does not materialise the raw mask")
+
+
+def _fetch(gate, what):
+    """A debug field of the last call as (units, F, T), or None where the kernels that ran keep no such field."""
+    try:
+        return np.swapaxes(gate.debug_field(what), 1, 2)
+    except RuntimeError as e:
+        if any(m in str(e) for m in _NO_SUCH_FIELD):
+            return None
+        raise
+
+
+def _stages(gate):
+    """Kernels the last call launched (first word of each profiled stage name); resets the accumulators."""
+    return {k.split(" ")[0] for k in gate.profile_read(reset=True)}
+
+
+def _assert_route(cell, case, route, stages):
+    """A cell must run the kernels its label claims (a shape that quietly routes elsewhere fails here)."""
+    fam, stat = PB.kernel_family(cell), case["kw"]["stationary"]
+    tag = "%s [%s]: launched %s" % (PB.cell_id(cell), route, sorted(stages))
+    if case["precision"] == "float64":
+        return
+    register_only = {"k_gate_onepass", "k_decide_fast", "k_apply_fast"}
+    if fam != "register":
+        assert not (stages & register_only) and "k_apply_istft" in stages, tag
+    if route == "force_unfused":
+        assert ("k_decide" in stages and "k_stft<double>" in stages) if stat else "k_box_mask" in stages, tag
+        return
+    if not stat:
+        assert "k_iir_mask<nt>" in stages, tag
+        if fam == "register":
+            assert ("k_apply_istft" if route == "force_nofast" else "k_apply_fast") in stages, tag
+        return
+    if fam == "register":
+        if route == "default":
+            assert "k_gate_onepass" in stages, tag
+        elif route == "force_split":
+            assert "k_decide_fast" in stages and "k_apply_fast" in stages and "k_gate_onepass" not in stages, tag
+        else:
+            assert "k_stft_bits<decide>" in stages and "k_apply_istft" in stages, tag
+    elif fam == "mixed_radix":   # the fused bit-mask route exists for mixed radix, not for chirp-z
+        assert ("k_stft_bits<decide>" in stages) == (route != "no_mixed_radix"), tag
+    elif fam in ("chirp_z", "four_step"):
+        assert "k_decide" in stages and "k_stft<double>" in stages, tag
+
+
+def _check_output(tag, cell, case, got, out, units, emus, route):
+    """c: every unit, every hop block of its kept range."""
+    peak = np.max(np.abs(out))
+    got = np.atleast_2d(got)
+    assert got.shape == np.atleast_2d(out).shape
+    f64 = case["precision"] == "float64"
+    worst = 0.0
+    for ui, u in enumerate(units):
+        s0, e0 = u["dst"]
+        if f64:
+            bad, ratio = PB.local_check(got[u["ch"], s0:e0], u, precision="float64", global_peak=peak)
+        else:
+            bad, ratio = PB.local_check(got[u["ch"], s0:e0], u, bud=PB.budget(u, emus[ui][0]))
+        worst = max(worst, ratio)
+        if len(bad):
+            err = PB.local_error(got[u["ch"], s0:e0], u["want"], u["cfg"]["H"])
+            raise AssertionError("%s unit %d (channel %d, chunk %d): hop blocks %s of %d over their bound: error %s, largest "
+                                 "error / budget in the unit %.2f" % (tag, ui, u["ch"], u["chunk"], bad[:10].tolist(), len(err),
+                                                                      err[bad[:10]], ratio))
+    print("%s: largest local_error / budget %.2f" % (tag, worst))
+    _note(PB.kernel_family(cell) + ("_f64" if f64 else ""), route, worst)
+
+
+def _check_bits(tag, gate, units, materialised):
+    """a: decision bits of every unit against the oracle's raw.  The bit-mask stages keep bits (field 3) for the frames
+    of debug_range(); the materialised kernels keep the raw mask as floats (field 0) for every frame."""
+    if materialised:
+        raw = _fetch(gate, 0)
+        assert raw is not None, "%s: the materialised kernels keep the raw mask" % tag
+        bits, (d0, d1) = raw > 0.5, (0, raw.shape[2])
+    else:
+        bits = _fetch(gate, 3)
+        assert bits is not None, "%s: the bit-mask stages keep the decision bits" % tag
+        d0, d1 = gate.debug_range()
+    assert bits.shape[0] == len(units), "%s: %d units in the last batch, %d in the call" % (tag, bits.shape[0], len(units))
+    assert 0 <= d0 < d1 <= bits.shape[2], (tag, d0, d1)
+    for ui, u in enumerate(units):
+        cells, left = PB.bit_diff(bits[ui], u, frames=(d0, d1))
+        assert left <= PB.LEFT_OUT_CAP
+        assert len(cells) == 0, "%s unit %d: %d decision bits differ from the oracle, first (band, frame) %s of frames " \
+                                "[%d, %d)" % (tag, ui, len(cells), cells[:6].tolist(), d0, d1)
+
+
+def _check_stationary_mask(tag, gate, units, materialised, must_exist):
+    """b, stationary: the smoothed float mask where one exists.  Returns whether it did."""
+    M = _fetch(gate, 1)
+    if M is None:
+        assert not must_exist, "%s: the general apply kernels read a float mask field" % tag
+        return False
+    assert M.shape[0] == len(units)
+    d0, d1 = (0, M.shape[2]) if materialised else gate.debug_range()
+    assert 0 <= d0 < d1 <= M.shape[2], (tag, d0, d1)
+    for ui, u in enumerate(units):
+        # (the materialised kernels smooth a float field with float taps: parity_budget.mask_bound)
+        bound = PB.mask_bound(u["cfg"], integer_taps=not materialised)
+        cells, w = PB.mask_diff(M[ui], u, frames=(d0, d1), bound=bound)
+        assert len(cells) == 0, "%s unit %d: smoothed mask off by up to %.3g (bound %.3g) at %d cells, first (band, frame) " \
+                                "%s" % (tag, ui, w, bound, len(cells), cells[:6].tolist())
+    return True
+
+
+def _field_rule(M, want, emu, what):
+    """Non-stationary float fields (<= 1): max |M - want| over the unit's field within FACTOR x the float32 emulation's
+    largest error over the same field + 4 eps32.  The budget is pooled over the WHOLE field, not over five columns as
+    for the output: a cell's error is the transform's error (~eps32 of the frame's peak bin, whatever |X| is) times
+    slope x m (1 - m) / S, which spans orders of magnitude from cell to cell -- the field's maximum sits in the few
+    cells that are both mid-slope and far below the frame's peak, and which frames hold such a cell differs between
+    two correct float32 transforms.  (Per column over t - 2 .. t + 2 this rule measured 9.7 x in one column of
+    mixed_radix-400-c5, all of it one such cell: band 192, frame 18, |X| = 2.6e-3 of the peak bin, kernel 0.5 eps32
+    of that peak off.)"""
+    err = np.abs(M.astype(np.float64) - want)
+    bud = float(np.max(np.abs(emu.astype(np.float64) - want)))
+    f, t = np.unravel_index(np.argmax(err), err.shape)
+    assert err[f, t] <= PB.FACTOR * bud + 4 * PB.EPS32, "%s: off by %.3g at (band %d, frame %d); the emulation's largest " \
+                                                        "error over the field is %.3g" % (what, err[f, t], f, t, bud)
+    return err[f, t] / bud if bud > 0 else 0.0
+
+
+def _check_nonstationary_fields(tag, gate, units, emus, raw_must_exist):
+    """b, non-stationary: final mask (field 1, every route) and raw sigmoid (field 0, materialised kernels)."""
+    M = _fetch(gate, 1)
+    assert M is not None and M.shape[0] == len(units), "%s: the non-stationary gates keep their final mask" % tag
+    raw = _fetch(gate, 0)
+    assert (raw is not None) == raw_must_exist, "%s: raw sigmoid field %s" % (tag, "missing" if raw is None else "unexpected")
+    for ui, (u, e) in enumerate(zip(units, emus)):
+        _field_rule(M[ui], u["mask"], e[2], "%s unit %d final mask" % (tag, ui))
+        if raw is not None:
+            _field_rule(raw[ui], u["raw"], e[1], "%s unit %d raw sigmoid" % (tag, ui))
+
+
+def _run_cell(cell, case, out, units, sg, routes):
+    """Every route of a cell: the route itself, then checks c, a, b."""
+    gate = sg._gate
+    f64 = case["precision"] == "float64"
+    emus = None if f64 else [PB.emulate_stages_f32(u) for u in units]
+    stationary = case["kw"]["stationary"]
+    gate.profile_enable(True)
+    try:
+        for name, opts in routes:
+            tag = "%s [%s]" % (PB.cell_id(cell), name)
+            with gate.lock, gate.with_options(opts):
+                gate.profile_read(reset=True)
+                got = sg.get_traces()
+                stages = _stages(gate)
+                assert got.dtype == np.dtype(case["dtype"])
+                _assert_route(cell, case, name, stages)
+                _check_output(tag, cell, case, got, out, units, emus, name)
+                if f64:
+                    continue                               # the float64 pipeline keeps no debug fields
+                materialised = "k_decide" in stages        # float64 transform + float raw / smoothed fields
+                if stationary:
+                    _check_bits(tag, gate, units, materialised)
+                    _check_stationary_mask(tag, gate, units, materialised,
+                                           must_exist=materialised or "k_apply_istft" in stages)
+                else:
+                    _check_nonstationary_fields(tag, gate, units, emus, raw_must_exist="k_box_mask" in stages)
+    finally:
+        gate.profile_enable(False)
+
+
+@pytest.mark.parametrize("cell", PB.CELLS, ids=PB.cell_id)
+def test_cell(cell):
+    case = PB.cell_case(cell)
+    out, units = PB.cell_oracle(cell)
+    _run_cell(cell, case, out, units, _make_sg(case), _routes(cell, case))
+
+
+@pytest.mark.parametrize("cell", [c for c in PB.CELLS if c["family"] == "mixed_radix" and c.get("precision") != "float64"],
+                         ids=PB.cell_id)
+def test_cell_on_the_chirp_z_route(cell, monkeypatch):
+    """The mixed-radix sizes once more with SG_NO_MIXED_RADIX=1 at handle creation (chirp-z kernels)."""
+    from noisereduce_amd import _ffi
+    case = PB.cell_case(cell)
+    out, units = PB.cell_oracle(cell)
+    monkeypatch.setenv("SG_NO_MIXED_RADIX", "1")
+    _ffi.clear_gate_cache()
+    try:
+        sg = _make_sg(case)
+        _run_cell(cell, case, out, units, sg, [("no_mixed_radix", [])])
+        del sg
+    finally:
+        monkeypatch.delenv("SG_NO_MIXED_RADIX")
+        _ffi.clear_gate_cache()
+
+
+# ---- TorchGate.forward ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("i", range(len(PB.T_CELLS)), ids=[PB.t_cell_id(c) for c in PB.T_CELLS])
+def test_torchgate_cell(i):
+    from noisereduce_amd import _ffi
+    from noisereduce_amd.torchgate import TorchGate
+    case = PB.t_case(i)
+    cell, kw = case["cell"], case["kw"]
+    n_fft = kw["n_fft"]
+    H = n_fft // 4
+    window = torch.hann_window(n_fft).double().numpy()
+    tg = TorchGate(sr=PB.T_SR, **kw).cuda()
+    x = torch.from_numpy(case["x"]).cuda()
+    xn = None if case["xn"] is None else torch.from_numpy(case["xn"]).cuda()
+    xn64 = None if case["xn"] is None else case["xn"].astype(np.float64)
+    lengths = case["lengths"]
+    B, L = case["x"].shape
+    gate = tg._gate_for(x.device)
+    mask = None
+    if lengths is None:
+        got = tg(x, xn).cpu().numpy()
+        _, units = PB.torchgate_units(case["x"].astype(np.float64), PB.T_SR, xn=xn64, window=window, **kw)
+    else:
+        got = tg(x, xn, lengths=lengths).cpu().numpy()
+        if n_fft & (n_fft - 1) == 0:      # the table-driven kernels hand back their final mask (other sizes: one call per row)
+            with gate.lock:
+                got2, mask = gate.process_rows(x, lengths, xn, None, save_mask=True)
+            assert np.array_equal(got2.cpu().numpy(), got)
+            mask = mask.cpu().numpy()
+        units = []
+        for b in range(B):
+            _, ub = PB.torchgate_units(case["x"][b:b + 1, :int(lengths[b])].astype(np.float64), PB.T_SR, xn=xn64,
+                                       window=window, **kw)
+            units.append(ub[0])
+    tag = PB.t_cell_id(cell)
+    worst = 0.0
+    for b, u in enumerate(units):
+        n = len(u["want"])
+        bad, ratio = PB.local_check(got[b, :n], u)
+        worst = max(worst, ratio)
+        assert len(bad) == 0, "%s row %d: hop blocks %s over their bound (largest error / budget %.2f)" % (tag, b, bad[:10].tolist(), ratio)
+        assert np.all(got[b, n:] == 0)
+        if mask is not None and u["cfg"]["stationary"]:
+            T = u["mask"].shape[1]
+            cells, w = PB.mask_diff(mask[b, :T, :n_fft // 2 + 1].T, u)
+            assert len(cells) == 0, "%s row %d: final mask off by up to %.3g at %d cells, first %s" % (tag, b, w, len(cells), cells[:6].tolist())
+            assert np.all(mask[b, T:, :n_fft // 2 + 1] == 0)
+    print("%s: largest local_error / budget %.2f" % (tag, worst))
+    _note("torchgate_%d" % n_fft, cell["path"], worst)
+    if lengths is not None and mask is None and not kw["nonstationary"]:
+        # one full-length call per row: the fields of the last call are the last row's
+        raw = _fetch(gate, 0)
+        assert raw is not None and raw.shape[0] == 1 and raw.shape[2] == units[-1]["raw"].shape[1], tag
+        cells, left = PB.bit_diff(raw[0] > 0.5, units[-1])
+        assert left <= PB.LEFT_OUT_CAP and len(cells) == 0, "%s last row: decision bits differ at %s" % (tag, cells[:6].tolist())
+        M = _fetch(gate, 1)
+        cells, w = PB.mask_diff(M[0], units[-1], bound=PB.mask_bound(units[-1]["cfg"], integer_taps=False))
+        assert len(cells) == 0, "%s last row: final mask off by up to %.3g" % (tag, w)
+    if lengths is None and not kw["nonstationary"]:
+        bits = _fetch(gate, 3)
+        if bits is None:
+            raw = _fetch(gate, 0)
+            assert raw is not None, "%s: neither the bit field nor the raw mask can be fetched" % tag
+            bits = raw > 0.5
+        assert bits.shape[0] == B
+        for b, u in enumerate(units):
+            cells, left = PB.bit_diff(bits[b], u)
+            assert left <= PB.LEFT_OUT_CAP
+            assert len(cells) == 0, "%s row %d: %d decision bits differ from the oracle, first (band, frame) %s" % (
+                tag, b, len(cells), cells[:6].tolist())
