@@ -191,6 +191,49 @@ SG_API int sg_process_clips(sg_handle* h, const void* x_dev, int in_dtype, const
                             const sg_noise_src* noise, int32_t n_noise, const sg_clip* clips, int64_t n_clips,
                             void* out_dev, int out_dtype, int64_t max_workspace_bytes, void* stream);
 
+/* ---- variant S: banks of live streams ------------------------------------------------------ */
+/* The stationary gate with a fixed noise threshold, advanced block by block (no counterpart in the reference, which needs
+ * the whole recording: base.py:130-226).  A bank holds n_slots independent streams of `channels` channels; a step pushes
+ * a block of any length (0 included) to any subset of them and runs a fixed number of launches.  With h = win_length / 2,
+ * nt = the time half width of the mask smoothing (0 without smoothing) and n samples received, a stream has emitted
+ * E(n) = max(0, (floor((n + h - win_length) / hop) - nt + 1) * hop - h) samples (sg_stream_emitted: host arithmetic), so
+ * the delay stays below win_length + (nt + 1) * hop samples.  The concatenated output is the offline gate of the whole
+ * signal for padding = 0 (frames, mask smoothing and overlap-add of sg_process_clips' single window), except for the
+ * -top_db floor, which is causal: a band's floor at frame t is its maximum over frames 0..t minus top_db.  A NaN / Inf
+ * sample gates every band from its first frame on until the slot is flushed or reset.  The output does not depend on the
+ * block split, the slot, or the other streams of a step.  Stationary handles with a power-of-two n_fft from 256 to 4096
+ * (SG_E_UNSUPPORTED / SG_E_INVALID otherwise).  The handle must outlive the bank; errors are reported through it
+ * (sg_last_error(h)). */
+typedef struct sg_stream_bank sg_stream_bank;
+typedef struct sg_stream_rec {   /* one stream's part of a step */
+  int32_t slot;
+  int32_t flush;           /* != 0: the stream ends with this block: every remaining sample is emitted, the slot is empty after */
+  int64_t n_samples;       /* block length per channel, 0 .. max_block */
+  int64_t in_offset;       /* element offset of channel 0 of the block in in_dev; channel c at in_offset + c * in_stride */
+  int64_t in_stride;
+  int64_t out_offset;      /* element offset of channel 0 of the emitted samples in out_dev */
+  int64_t out_stride;
+} sg_stream_rec;
+SG_API int sg_stream_create(sg_handle* h, int32_t n_slots, int32_t channels, int64_t max_block, sg_stream_bank** out);
+SG_API int sg_stream_destroy(sg_stream_bank* b);
+/* Threshold (dB, n_fft / 2 + 1 values) of the listed slots: thresh_host, or -- thresh_host == NULL -- the handle's current
+ * threshold on the device (sg_noise_stats / sg_set_noise_threshold*), copied: later changes of the handle's do not reach
+ * the bank.  Enqueues only. */
+SG_API int sg_stream_set_threshold(sg_stream_bank* b, const int32_t* slots, int32_t n_slots, const double* thresh_host,
+                                   int32_t n_bins, void* stream);
+/* One step.  Record i appends n_samples samples per channel to its stream and writes the E(n + n_samples) - E(n) newly
+ * final samples per channel (flush: all n + n_samples - E(n) remaining ones, the inverse transform's zero tail included;
+ * fewer than win_length samples in the whole stream: SG_E_INVALID) to out_dev.  A slot appears at most once per step.
+ * Samples beyond n_samples are never read, nothing beyond the emitted samples is written.  SG_F32 / SG_F64 buffers.
+ * Every argument is checked before any device work; enqueues only. */
+SG_API int sg_stream_push(sg_stream_bank* b, const void* in_dev, int in_dtype, void* out_dev, int out_dtype,
+                          const sg_stream_rec* recs, int32_t n_recs, void* stream);
+/* Empties the listed slots (their thresholds stay). */
+SG_API int sg_stream_reset(sg_stream_bank* b, const int32_t* slots, int32_t n_slots, void* stream);
+/* E(n) for the handle's geometry; samples received / emitted so far on a slot.  Host arithmetic only. */
+SG_API int sg_stream_emitted(const sg_handle* h, int64_t n, int64_t* emitted);
+SG_API int sg_stream_counters(const sg_stream_bank* b, int32_t slot, int64_t* n, int64_t* emitted);
+
 /* ---- variant T -------------------------------------------------------------------- */
 
 /* Replaces TorchGate.forward(x, xn) (torchgate.py:200-264): x (B, L) -> out

@@ -73,6 +73,12 @@ class SgNoiseSrc(Structure):
     _fields_ = [("offset", c_int64), ("n", c_int64), ("stride", c_int64), ("channels", c_int32), ("in_x", c_int32)]
 
 
+class SgStreamRec(Structure):
+    """struct sg_stream_rec (include/mi355gate.h)."""
+    _fields_ = [("slot", c_int32), ("flush", c_int32), ("n_samples", c_int64), ("in_offset", c_int64),
+                ("in_stride", c_int64), ("out_offset", c_int64), ("out_stride", c_int64)]
+
+
 # every symbol include/mi355gate.h and include/mi355gate_debug.h declare: name -> (restype, argtypes)
 _PROTOTYPES = {
     "sg_version": (c_int, []),
@@ -108,6 +114,13 @@ _PROTOTYPES = {
                                  c_void_p, c_int, c_int64, c_void_p]),
     "sg_debug_clip_thresholds": (c_int, [c_void_p, POINTER(c_double), c_int32, c_int32, c_void_p]),
     "sg_debug_clip_batches": (c_int, [c_void_p, POINTER(c_int64)]),
+    "sg_stream_create": (c_int, [c_void_p, c_int32, c_int32, c_int64, POINTER(c_void_p)]),
+    "sg_stream_destroy": (c_int, [c_void_p]),
+    "sg_stream_set_threshold": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p]),
+    "sg_stream_push": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int32, c_void_p]),
+    "sg_stream_reset": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
+    "sg_stream_emitted": (c_int, [c_void_p, c_int64, POINTER(c_int64)]),
+    "sg_stream_counters": (c_int, [c_void_p, c_int32, POINTER(c_int64), POINTER(c_int64)]),
     "sg_set_option": (c_int, [c_void_p, c_int32, c_int64]),
     "sg_get_option": (c_int, [c_void_p, c_int32, POINTER(c_int64)]),
     "sg_check_errors": (c_int, [c_void_p, c_void_p]),
@@ -515,6 +528,55 @@ class Gate:
         v = c_int64()
         self._check(self.lib.sg_debug_clip_batches(self._h, byref(v)))
         return int(v.value)
+
+    # -- banks of live streams (sg_stream_*) --------------------------------------------------------
+    def stream_create(self, n_slots, channels, max_block):
+        b = c_void_p()
+        with torch.cuda.device(self.device):
+            self._check(self.lib.sg_stream_create(self._h, int(n_slots), int(channels), int(max_block), byref(b)))
+        return b
+
+    def stream_destroy(self, bank):
+        if bank is not None and bank.value and self._h.value:
+            with torch.cuda.device(self.device):
+                self.lib.sg_stream_destroy(bank)
+
+    def stream_set_threshold(self, bank, slots, thresh=None):
+        """thresh: n_bins dB values (host), or None for the handle's current threshold on the device."""
+        sl = np.ascontiguousarray(np.asarray(slots, dtype=np.int32).reshape(-1))
+        tp, t = None, None
+        if thresh is not None:
+            t = np.ascontiguousarray(np.asarray(thresh, dtype=np.float64).reshape(-1))
+            if t.shape[0] != self.n_bins:
+                raise ValueError(f"thresholds_db must hold n_fft // 2 + 1 = {self.n_bins} values")
+            tp = t.ctypes.data_as(c_void_p)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.sg_stream_set_threshold(bank, sl.ctypes.data_as(c_void_p), int(sl.shape[0]), tp,
+                                                         self.n_bins, self._stream()))
+
+    def stream_push(self, bank, x, out, recs):
+        """x, out: 1-D float32 / float64 device tensors; recs: sequence of SgStreamRec.  Enqueues only."""
+        self._on_device(x)
+        self._on_device(out)
+        arr = (SgStreamRec * max(1, len(recs)))(*recs)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.sg_stream_push(bank, x.data_ptr(), _sg_dtype(x), out.data_ptr(), _sg_dtype(out), arr,
+                                                len(recs), self._stream()))
+
+    def stream_reset(self, bank, slots):
+        sl = np.ascontiguousarray(np.asarray(slots, dtype=np.int32).reshape(-1))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.sg_stream_reset(bank, sl.ctypes.data_as(c_void_p), int(sl.shape[0]), self._stream()))
+
+    def stream_emitted(self, n):
+        v = c_int64()
+        self._check(self.lib.sg_stream_emitted(self._h, int(n), byref(v)))
+        return int(v.value)
+
+    def stream_counters(self, bank, slot):
+        n, e = c_int64(), c_int64()
+        self._check(self.lib.sg_stream_counters(bank, int(slot), byref(n), byref(e)))
+        return int(n.value), int(e.value)
 
     def set_option(self, option, value):
         self._check(self.lib.sg_set_option(self._h, int(option), int(value)))

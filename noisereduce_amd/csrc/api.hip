@@ -41,6 +41,7 @@
 #include "apply64.hpp"
 #include "ragged.hpp"
 #include "rows.hpp"
+#include "stream.hpp"
 
 // complex transform length from which a whole 256-thread workgroup (instead of one wavefront) works on ONE frame in
 // the general LDS kernels: at N = 2048 (n_fft = 4096) a wavefront holds 4 radix-8 butterflies = 64 complex values per
@@ -3697,4 +3698,63 @@ extern "C" int sg_debug_rows_batches(const sg_handle* h, int64_t* value) {
   if (!h || !value) return SG_E_INVALID;
   *value = sg::rw_last_batches(h->rw);
   return SG_OK;
+}
+
+// ---- banks of live streams: thin wrappers over stream.hip --------------------------------------------------------------
+struct sg_stream_bank {
+  sg_handle* h;
+  sg::StBank* b;
+};
+
+extern "C" int sg_stream_create(sg_handle* h, int32_t n_slots, int32_t channels, int64_t max_block, sg_stream_bank** out) {
+  if (!h || !out) return SG_E_INVALID;
+  if (h->p.variant != SG_VARIANT_S) FAIL(h, SG_E_INVALID, "sg_stream_create is a variant-S entry point");
+  sg::StBank* b = nullptr;
+  int rc = sg::st_create(&b, rg_ctx(h), n_slots, channels, max_block, &h->err);
+  if (rc) return rc;
+  *out = new sg_stream_bank{h, b};
+  return SG_OK;
+}
+
+extern "C" int sg_stream_destroy(sg_stream_bank* b) {
+  if (!b) return SG_OK;
+  sg::st_destroy(b->b);
+  delete b;
+  return SG_OK;
+}
+
+extern "C" int sg_stream_set_threshold(sg_stream_bank* b, const int32_t* slots, int32_t n_slots, const double* thresh_host,
+                                       int32_t n_bins, void* stream) {
+  if (!b) return SG_E_INVALID;
+  sg_handle* h = b->h;
+  if (n_bins != h->F) FAIL(h, SG_E_INVALID, "sg_stream_set_threshold: n_bins must be %d", h->F);
+  if (!thresh_host && !h->has_thresh) FAIL(h, SG_E_STATE, "no noise threshold set");
+  return sg::st_set_threshold(b->b, slots, n_slots, thresh_host ? nullptr : (const double*)h->thresh.p, thresh_host,
+                              (hipStream_t)stream, &h->err);
+}
+
+extern "C" int sg_stream_push(sg_stream_bank* b, const void* in_dev, int in_dtype, void* out_dev, int out_dtype,
+                              const sg_stream_rec* recs, int32_t n_recs, void* stream) {
+  if (!b) return SG_E_INVALID;
+  sg_handle* h = b->h;
+  if (n_recs < 0 || (n_recs > 0 && !recs) || (in_dtype != SG_F32 && in_dtype != SG_F64) ||
+      (out_dtype != SG_F32 && out_dtype != SG_F64))
+    FAIL(h, SG_E_INVALID, "sg_stream_push: bad argument (float32 / float64 buffers)");
+  return sg::st_push(b->b, in_dev, in_dtype, out_dev, out_dtype, recs, n_recs, (hipStream_t)stream, &h->err);
+}
+
+extern "C" int sg_stream_reset(sg_stream_bank* b, const int32_t* slots, int32_t n_slots, void* stream) {
+  if (!b) return SG_E_INVALID;
+  return sg::st_reset(b->b, slots, n_slots, (hipStream_t)stream, &b->h->err);
+}
+
+extern "C" int sg_stream_emitted(const sg_handle* h, int64_t n, int64_t* emitted) {
+  if (!h || !emitted || n < 0) return SG_E_INVALID;
+  *emitted = sg::st_emitted(h->W, h->H, h->p.smooth_mask ? h->p.n_grad_time : 0, n);
+  return SG_OK;
+}
+
+extern "C" int sg_stream_counters(const sg_stream_bank* b, int32_t slot, int64_t* n, int64_t* emitted) {
+  if (!b || !n || !emitted) return SG_E_INVALID;
+  return sg::st_counters(b->b, slot, n, emitted, &b->h->err);
 }

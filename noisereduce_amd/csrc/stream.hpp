@@ -1,0 +1,40 @@
+// Banks of live streams (sg_stream_*, mi355gate.h): the stationary gate advanced block by block.
+//
+// A bank holds n_slots independent streams of `channels` channels each.  Every step (sg_stream_push) takes whatever block
+// each pushed stream received and runs a FIXED number of launches, whatever the number of streams and the block lengths;
+// the state that survives between steps lives in HBM and belongs to the bank:
+//   ring   [unit][RC]          float64 samples not yet covered by an applied frame (RC = W + (nt + 1) H)
+//   bits   [unit][RB][wpr]     final raw-mask bits of the last decided frames (causal -top_db floor already applied)
+//   rmax   [unit][FS]          running band maximum of the power, float64, NaN-sticky
+//   carry  [unit][2][W]        partial overlap-add sums of the samples not yet emitted (double buffered per step)
+//   thr/T2 [slot][FS]          threshold in dB and its compare constant on the raw power
+// (unit = slot * channels + channel).  The counters n, t_dec, t_applied, E are host arithmetic, mirrored in the bank.
+//
+// This header is shared by api.hip (thin C wrappers) and stream.hip (tables, kernels); it holds no kernels.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <string>
+
+#include "../../include/mi355gate.h"
+#include "ragged.hpp"
+
+namespace sg {
+
+struct StBank;
+
+// samples emitted after n received: max(0, (t_dec(n) - nt + 1) H - h), t_dec(n) = floor((n + h - W) / H)
+int64_t st_emitted(int W, int H, int nt, int64_t n);
+
+int st_create(StBank** out, const RgCtx& c, int32_t n_slots, int32_t channels, int64_t max_block, std::string* err);
+void st_destroy(StBank* b);
+// thresh_dev: F dB values on the device (the handle's); thresh_host: F dB values on the host; exactly one is non-null
+int st_set_threshold(StBank* b, const int32_t* slots, int32_t n, const double* thresh_dev, const double* thresh_host,
+                     hipStream_t st, std::string* err);
+int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_dtype, const sg_stream_rec* recs,
+            int32_t n_recs, hipStream_t st, std::string* err);
+int st_reset(StBank* b, const int32_t* slots, int32_t n, hipStream_t st, std::string* err);
+int st_counters(const StBank* b, int32_t slot, int64_t* n, int64_t* emitted, std::string* err);
+
+}  // namespace sg

@@ -1,0 +1,313 @@
+"""``StreamBank`` / ``StreamGate`` -- the stationary gate for live audio: streams gated block by block on the GPU.
+
+Everything else in the package needs the last sample of a recording before the first one comes out.  A ``StreamBank``
+holds many independent streams with a fixed noise profile; each step takes whatever block every stream received (0
+samples, 1 sample, a second -- different streams different lengths) and returns the samples that became final, in a fixed
+number of kernel launches per step (sg_stream_push, include/mi355gate.h).
+
+With ``W`` = win_length, ``H`` = hop_length, ``h = W // 2``, ``nt`` = the time half width of the mask smoothing (0 with
+smoothing off) and ``n`` samples received, a stream has emitted ``emitted(n, W, H, nt) = max(0, (t_dec(n) - nt + 1) * H - h)``
+samples, ``t_dec(n) = floor((n + h - W) / H)``: every sample whose frames all have their final mask.  The delay is below
+``latency_samples = W + (nt + 1) * H`` samples (3 584 at the 48 kHz defaults: 75 ms).  ``flush`` ends a stream: the
+remaining frames see zeros after the last sample and the remaining samples come out.
+
+The concatenated output of a stream equals ``reduce_noise(y, sr, y_noise=..., stationary=True, chunk_size=None,
+padding=0)`` of the whole signal, whatever the block split, with one designed difference: the -top_db floor is causal.
+Offline a band's floor is its maximum over the whole recording minus 80 dB; here it is the maximum over the frames up
+to and including the current one.  The two agree wherever no band's maximum exceeds its threshold by more than 80 dB.
+A NaN / Inf sample gates every band from its first frame on until the slot is flushed or reset; the NaN itself survives.
+A stream's output does not depend, bitwise, on how it was cut into blocks, on its slot, or on the other streams of a step.
+
+Out of scope: the non-stationary gate (its smoothing runs backward over the whole chunk), ``TorchGate``, integer
+blocks, several GPUs, and ``n_fft`` other than a power of two from 256 to 4096 (``ValueError``).
+"""
+import numpy as np
+import torch
+
+from noisereduce_amd import _ffi
+
+_NONE_CHUNK = 1 << 62
+_N_FFTS = (256, 512, 1024, 2048, 4096)
+_FLOATS = (np.dtype(np.float32), np.dtype(np.float64))
+
+
+def t_decided(n, W, H):
+    """Last frame that lies inside the first ``n`` samples (-1: none)."""
+    a = n + W // 2 - W
+    return -1 if a < 0 else a // H
+
+
+def emitted(n, W, H, nt):
+    """Samples a stream has emitted after receiving ``n`` (host arithmetic; no GPU)."""
+    return max(0, (t_decided(n, W, H) - nt + 1) * H - W // 2)
+
+
+def _widths(sr, n_fft, H, freq_mask_smooth_hz, time_mask_smooth_ms):
+    """(n_grad_freq, n_grad_time, smooth) with the reference's errors (SpectralGate._generate_mask_smoothing_filter)."""
+    if freq_mask_smooth_hz is None and time_mask_smooth_ms is None:
+        return 1, 1, False
+    nf = nt = 1
+    if freq_mask_smooth_hz is not None:
+        nf = int(freq_mask_smooth_hz / (sr / (n_fft / 2)))
+        if nf < 1:
+            raise ValueError("freq_mask_smooth_hz needs to be at least {}Hz".format(int((sr / (n_fft / 2)))))
+    if time_mask_smooth_ms is not None:
+        nt = int(time_mask_smooth_ms / ((H / sr) * 1000))
+        if nt < 1:
+            raise ValueError("time_mask_smooth_ms needs to be at least {}ms".format(int((H / sr) * 1000)))
+    return nf, nt, not (nf == 1 and nt == 1)
+
+
+class StreamBank:
+    """``n_streams`` live streams of ``channels`` channels each, gated with the stationary gate (module docstring).
+
+    The noise profile is fixed per stream: ``y_noise`` (a noise clip, ``(n,)`` or ``(C, n)``; channel mean, whole clip,
+    the float64 statistics ``reduce_noise`` uses) or ``thresholds_db`` (``n_fft // 2 + 1`` dB values) sets it for every
+    slot; ``set_noise(slots, ...)`` overrides it per stream.  ``max_block`` is the longest block a step may push to one
+    stream (default: one second).
+
+    ``push({slot: block})`` -> ``{slot: out}``: blocks are ``(n,)`` or ``(C, n)`` float32 / float64 numpy arrays or
+    device tensors; device tensors in give device tensors out with no host synchronisation (output lengths are host
+    arithmetic); numpy in gives numpy out.  ``flush(slots)`` -> ``{slot: tail}`` ends streams (fewer than ``win_length``
+    samples in all: ``ValueError``) and leaves the slots empty; ``reset(slots)`` drops their state."""
+
+    def __init__(self, sr, n_streams, channels=1, y_noise=None, thresholds_db=None, prop_decrease=1.0,
+                 n_std_thresh_stationary=1.5, freq_mask_smooth_hz=500, time_mask_smooth_ms=50, n_fft=1024,
+                 win_length=None, hop_length=None, max_block=None, device="cuda", stationary=True):
+        if not stationary:
+            raise ValueError("StreamBank: only the stationary gate streams (the non-stationary gate smooths backward "
+                             "over the whole chunk)")
+        n_fft = int(n_fft)
+        if n_fft not in _N_FFTS:
+            raise ValueError("StreamBank: n_fft must be a power of two from 256 to 4096")
+        W = n_fft if win_length is None else int(win_length)
+        H = W // 4 if hop_length is None else int(hop_length)
+        if W > n_fft or W < 2 or H < 1:
+            raise ValueError("StreamBank: needs 2 <= win_length <= n_fft and hop_length >= 1")
+        if int(n_streams) < 1 or int(channels) < 1:
+            raise ValueError("StreamBank: n_streams and channels must be at least 1")
+        if y_noise is not None and thresholds_db is not None:
+            raise ValueError("StreamBank: give y_noise or thresholds_db, not both")
+        nf, nt, smooth = _widths(sr, n_fft, H, freq_mask_smooth_hz, time_mask_smooth_ms)
+        self.sr, self.n_fft, self.win_length, self.hop_length = sr, n_fft, W, H
+        self.n_streams, self.channels = int(n_streams), int(channels)
+        self.nt = nt if smooth else 0
+        self.max_block = int(sr) if max_block is None else int(max_block)
+        if self.max_block < 1:
+            raise ValueError("StreamBank: max_block must be at least 1")
+        self.latency_samples = W + (self.nt + 1) * H
+        self._n = [0] * self.n_streams        # samples received / emitted per slot (mirrors of the library's counters)
+        self._e = [0] * self.n_streams
+        self._has_noise = [False] * self.n_streams
+        self._kind = [(False, np.dtype(np.float32), True)] * self.n_streams   # (tensor I/O, dtype, flat) of the last block
+        self._bank = self._gate = None
+        self._pending = []                    # noise profiles set before the first device call
+        self._device_arg = device
+        self._gate_kw = dict(variant=_ffi.SG_VARIANT_S, stationary=True, n_fft=n_fft, win_length=W, hop_length=H,
+                             n_grad_freq=nf if smooth else 1, n_grad_time=nt if smooth else 1, smooth_mask=smooth,
+                             chunk_size=_NONE_CHUNK, padding=0, prop_decrease=prop_decrease,
+                             n_std_thresh=n_std_thresh_stationary, top_db=80.0, ddof=0)
+        if y_noise is not None or thresholds_db is not None:
+            self.set_noise(range(self.n_streams), y_noise=y_noise, thresholds_db=thresholds_db)
+
+    def _ensure(self):
+        """The engine handle and the bank's device state, created at the first call that needs the GPU (arguments are
+        checked before that); then the noise profiles set so far."""
+        if self._bank is None:
+            self._gate = _ffi.Gate(self._device_arg, **self._gate_kw)
+            self.device = self._gate.device
+            self._bank = self._gate.stream_create(self.n_streams, self.channels, self.max_block)
+        pending, self._pending = self._pending, []
+        for slots, kind, val in pending:
+            if kind == "db":
+                self._gate.stream_set_threshold(self._bank, slots, val)
+            else:
+                with torch.cuda.device(self.device):
+                    self._gate.noise_stats(val.to(self.device, torch.float64))
+                    self._gate.stream_set_threshold(self._bank, slots, None)
+
+    # -- plumbing ----------------------------------------------------------------------------------------------
+    def close(self):
+        if getattr(self, "_bank", None) is not None:
+            self._gate.stream_destroy(self._bank)
+            self._bank = None
+            self._gate.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _slots(self, slots):
+        out = [slots] if isinstance(slots, (int, np.integer)) else list(slots)
+        for s in out:
+            if not isinstance(s, (int, np.integer)) or s < 0 or s >= self.n_streams:
+                raise ValueError(f"StreamBank: unknown slot {s!r} (the bank has {self.n_streams})")
+        return [int(s) for s in out]
+
+    @property
+    def gate(self):
+        """The engine handle (per-kernel timing: ``gate.profile_enable()`` / ``profile_read()``)."""
+        self._ensure()
+        return self._gate
+
+    def received(self, slot):
+        return self._n[self._slots(slot)[0]]
+
+    def thresholds(self):
+        """The dB threshold the handle computed last (``set_noise(..., y_noise=)``), as a numpy array (synchronises)."""
+        return self.gate.get_noise_threshold()
+
+    # -- noise profile -----------------------------------------------------------------------------------------
+    def set_noise(self, slots, y_noise=None, thresholds_db=None):
+        slots = self._slots(slots)
+        if (y_noise is None) == (thresholds_db is None):
+            raise ValueError("set_noise: give y_noise or thresholds_db")
+        if thresholds_db is not None:
+            t = np.asarray(thresholds_db, dtype=np.float64).reshape(-1)
+            if t.shape[0] != self.n_fft // 2 + 1:
+                raise ValueError(f"thresholds_db must hold n_fft // 2 + 1 = {self.n_fft // 2 + 1} values")
+            self._pending.append((slots, "db", t))
+        else:
+            a = y_noise.detach() if isinstance(y_noise, torch.Tensor) else np.asarray(y_noise)
+            if a.ndim == 1:
+                a = a[None, :]
+            if a.ndim != 2:
+                raise ValueError("noise waveform must be in shape (# frames, # channels)")
+            if a.shape[1] < self.win_length:
+                raise ValueError(f"noise clip of {a.shape[1]} samples is shorter than win_length={self.win_length}")
+            if not isinstance(a, torch.Tensor):
+                a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))
+            self._pending.append((slots, "clip", a))
+        for s in slots:
+            self._has_noise[s] = True
+        if self._bank is not None:
+            self._ensure()
+
+    # -- steps -------------------------------------------------------------------------------------------------
+    def _step(self, blocks, flush):
+        """blocks: {slot: block or None}; every argument is checked before any device work."""
+        C, W = self.channels, self.win_length
+        items, tensor_io = [], None
+        for s, blk in blocks.items():
+            s = self._slots(s)[0]
+            if not self._has_noise[s]:
+                raise ValueError(f"StreamBank: slot {s} has no noise profile (y_noise / thresholds_db / set_noise)")
+            if blk is None:
+                items.append((s, None, 0, self._kind[s][2]))
+                continue
+            is_t = isinstance(blk, torch.Tensor)
+            a = blk.detach() if is_t else np.asarray(blk)
+            if tensor_io is None:
+                tensor_io = is_t
+            elif tensor_io != is_t:
+                raise ValueError("StreamBank: the blocks of a step must be all numpy arrays or all device tensors")
+            dt = np.dtype(str(a.dtype).replace("torch.", ""))
+            if dt not in _FLOATS:
+                raise ValueError(f"StreamBank: blocks are float32 or float64 (got {dt}; integer blocks are out of scope)")
+            if is_t and a.device.type != "cuda":
+                raise ValueError("StreamBank: block tensors must live on the GPU")
+            flat = a.ndim == 1
+            if a.ndim not in (1, 2) or (flat and C != 1) or (not flat and a.shape[0] != C):
+                raise ValueError(f"StreamBank: slot {s}: a block is (n,) or ({C}, n), got {tuple(a.shape)}")
+            n = int(a.shape[-1])
+            if n > self.max_block:
+                raise ValueError(f"StreamBank: slot {s}: block of {n} samples is longer than max_block={self.max_block}")
+            items.append((s, a, n, flat))
+        if len({it[0] for it in items}) != len(items):
+            raise ValueError("StreamBank: a slot appears twice in one step")
+        if flush:
+            for s, a, n, flat in items:
+                if self._n[s] + n < W:
+                    raise ValueError(f"StreamBank: slot {s}: a stream of {self._n[s] + n} samples is shorter than "
+                                     f"win_length={W}")
+        if tensor_io is None:      # a flush without a last block: what the streams were fed with
+            tensor_io = bool(items) and all(self._kind[s][0] for s, _, _, _ in items)
+        self._ensure()
+        wide = any(a is not None and str(a.dtype).endswith("float64") for _, a, _, _ in items)
+        tdt = torch.float64 if wide else torch.float32
+        recs, outs, in_off, out_off = [], [], 0, 0
+        for s, a, n, flat in items:
+            n1 = self._n[s] + n
+            k = (n1 if flush else emitted(n1, W, self.hop_length, self.nt)) - self._e[s]
+            recs.append(_ffi.SgStreamRec(slot=s, flush=int(flush), n_samples=n, in_offset=in_off, in_stride=n,
+                                         out_offset=out_off, out_stride=k))
+            outs.append((s, a, k, flat, out_off))
+            in_off += C * n
+            out_off += C * k
+        with torch.cuda.device(self.device):
+            parts = [a.reshape(-1) for _, a, n, _ in items if a is not None and n > 0]
+            if tensor_io:
+                x = torch.cat([p.to(tdt) for p in parts]) if parts else torch.empty(0, dtype=tdt, device=self.device)
+            else:
+                xh = torch.empty(max(in_off, 1), dtype=tdt, pin_memory=True)
+                if parts:
+                    xh.numpy()[:in_off] = np.concatenate(parts)
+                x = xh.to(self.device, non_blocking=True)
+            if x.numel() == 0:
+                x = torch.empty(1, dtype=tdt, device=self.device)
+            out = torch.empty(max(out_off, 1), dtype=tdt, device=self.device)
+            self._gate.stream_push(self._bank, x, out, recs)
+            for (s, a, n, flat), (_, _, k, _, _) in zip(items, outs):
+                if flush:
+                    self._n[s] = self._e[s] = 0
+                else:
+                    self._n[s] += n
+                    self._e[s] += k
+            res = {}
+            host = None if tensor_io else out.cpu().numpy()
+            for s, a, k, flat, off in outs:
+                o = (out if tensor_io else host)[off:off + C * k].reshape(C, k)
+                if a is not None:
+                    dt = a.dtype
+                    self._kind[s] = (tensor_io, np.dtype(str(dt).replace("torch.", "")), flat)
+                else:
+                    dt = self._kind[s][1]
+                    if tensor_io:
+                        dt = torch.float64 if dt == np.float64 else torch.float32
+                if flat and C == 1:
+                    o = o[0]
+                res[s] = o.to(dt) if tensor_io else o.astype(dt, copy=True)
+            return res
+
+    def push(self, blocks):
+        """``{slot: block}`` -> ``{slot: newly final samples}`` (possibly empty).  No host synchronisation for device
+        tensors.  Device-tensor results are views into one output buffer of the step."""
+        return self._step(dict(blocks), flush=False)
+
+    def flush(self, slots, blocks=None):
+        """End the streams in ``slots``: ``{slot: remaining samples}``, of the kind and type the streams were last fed with;
+        ``blocks`` may give a last block per slot.  The slots are empty and reusable afterwards."""
+        slots = self._slots(slots)
+        d = {s: None for s in slots}
+        if blocks:
+            d.update(blocks)
+        return self._step(d, flush=True)
+
+    def reset(self, slots):
+        slots = self._slots(slots)
+        if self._bank is not None:
+            self._gate.stream_reset(self._bank, slots)
+        for s in slots:
+            self._n[s] = self._e[s] = 0
+
+
+class StreamGate:
+    """One stream: ``push(block) -> out``, ``flush() -> tail`` (a ``StreamBank`` of one slot; same arguments)."""
+
+    def __init__(self, sr, y_noise=None, **kw):
+        self.bank = StreamBank(sr, 1, y_noise=y_noise, **kw)
+        self.latency_samples = self.bank.latency_samples
+
+    def push(self, block):
+        return self.bank.push({0: block})[0]
+
+    def flush(self):
+        return self.bank.flush([0])[0]
+
+    def reset(self):
+        self.bank.reset([0])
+
+    def close(self):
+        self.bank.close()
