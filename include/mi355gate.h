@@ -202,7 +202,8 @@ SG_API int sg_process_clips(sg_handle* h, const void* x_dev, int in_dtype, const
  * -top_db floor, which is causal: a band's floor at frame t is its maximum over frames 0..t minus top_db.  A NaN / Inf
  * sample gates every band from its first frame on until the slot is flushed or reset.  The output does not depend on the
  * block split, the slot, or the other streams of a step.  Stationary handles with a power-of-two n_fft from 256 to 4096
- * (SG_E_UNSUPPORTED / SG_E_INVALID otherwise).  The handle must outlive the bank; errors are reported through it
+ * (SG_E_UNSUPPORTED / SG_E_INVALID otherwise; non-stationary handles: sg_stream_create_nonstationary
+ * below).  The handle must outlive the bank; errors are reported through it
  * (sg_last_error(h)). */
 typedef struct sg_stream_bank sg_stream_bank;
 typedef struct sg_stream_rec {   /* one stream's part of a step */
@@ -233,6 +234,26 @@ SG_API int sg_stream_reset(sg_stream_bank* b, const int32_t* slots, int32_t n_sl
 /* E(n) for the handle's geometry; samples received / emitted so far on a slot.  Host arithmetic only. */
 SG_API int sg_stream_emitted(const sg_handle* h, int64_t n, int64_t* emitted);
 SG_API int sg_stream_counters(const sg_stream_bank* b, int32_t slot, int64_t* n, int64_t* emitted);
+/* The non-stationary gate as a stream (the handle is non-stationary; iir_b, nonstat_thresh, nonstat_slope are its own).
+ * No noise profile: sg_stream_set_threshold fails on such a bank; push / reset / destroy / counters serve it as they serve a
+ * stationary one.  The forward one-pole pass fwd[f, t] = b A[f, t] + (1 - b) fwd[f, t - 1], fwd[f, -1] = A[f, 0], A = |X|,
+ * is carried per band; the smoothed level of frame t is the reference's forward-backward smoother of the signal as known
+ * lookahead_frames = L frames later: with e = min(t + L, last frame of the stream), s = fwd[f, e], then
+ * s = b fwd[f, k] + (1 - b) s for k = e, e - 1, ..., t.  The mask is sigmoid(((A - s) / s - nonstat_thresh) * nonstat_slope),
+ * smoothed and scaled by prop_decrease as sg_process_clips does.  A frame is decided once frames up to t + L lie inside the
+ * audio (or at the flush), so E(n) is sg_stream_emitted's with nt + L in place of nt (sg_stream_bank_emitted) and the delay
+ * stays below win_length + (nt + L + 1) * hop samples.  With L >= the stream's frame count - 1 the output is the offline
+ * gate of the whole signal for padding = 0; a small L with a long time constant gates more causally, by design.  Digital
+ * silence gives 0 / 0 = NaN as offline; a NaN / Inf sample keeps the forward state NaN until the slot is flushed or reset.
+ * lookahead_frames is 0 .. SG_STREAM_MAX_LOOKAHEAD (SG_E_INVALID beyond: the backward pass of a frame is
+ * lookahead_frames + 1 dependent steps per band).  sg_stream_state_bytes: the device memory a bank of the handle's kind
+ * would hold (host arithmetic; lookahead_frames is ignored for a stationary handle). */
+#define SG_STREAM_MAX_LOOKAHEAD 4096
+SG_API int sg_stream_create_nonstationary(sg_handle* h, int32_t n_slots, int32_t channels, int64_t max_block,
+                                          int32_t lookahead_frames, sg_stream_bank** out);
+SG_API int sg_stream_state_bytes(const sg_handle* h, int32_t n_slots, int32_t channels, int64_t max_block,
+                                 int32_t lookahead_frames, int64_t* bytes);
+SG_API int sg_stream_bank_emitted(const sg_stream_bank* b, int64_t n, int64_t* emitted);
 
 /* ---- variant T -------------------------------------------------------------------- */
 

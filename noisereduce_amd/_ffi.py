@@ -121,6 +121,9 @@ _PROTOTYPES = {
     "sg_stream_reset": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
     "sg_stream_emitted": (c_int, [c_void_p, c_int64, POINTER(c_int64)]),
     "sg_stream_counters": (c_int, [c_void_p, c_int32, POINTER(c_int64), POINTER(c_int64)]),
+    "sg_stream_create_nonstationary": (c_int, [c_void_p, c_int32, c_int32, c_int64, c_int32, POINTER(c_void_p)]),
+    "sg_stream_state_bytes": (c_int, [c_void_p, c_int32, c_int32, c_int64, c_int32, POINTER(c_int64)]),
+    "sg_stream_bank_emitted": (c_int, [c_void_p, c_int64, POINTER(c_int64)]),
     "sg_set_option": (c_int, [c_void_p, c_int32, c_int64]),
     "sg_get_option": (c_int, [c_void_p, c_int32, POINTER(c_int64)]),
     "sg_check_errors": (c_int, [c_void_p, c_void_p]),
@@ -535,6 +538,24 @@ class Gate:
         with torch.cuda.device(self.device):
             self._check(self.lib.sg_stream_create(self._h, int(n_slots), int(channels), int(max_block), byref(b)))
         return b
+
+    def stream_create_nonstationary(self, n_slots, channels, max_block, lookahead_frames):
+        b = c_void_p()
+        with torch.cuda.device(self.device):
+            self._check(self.lib.sg_stream_create_nonstationary(self._h, int(n_slots), int(channels), int(max_block),
+                                                                int(lookahead_frames), byref(b)))
+        return b
+
+    def stream_state_bytes(self, n_slots, channels, max_block, lookahead_frames=0):
+        v = c_int64()
+        self._check(self.lib.sg_stream_state_bytes(self._h, int(n_slots), int(channels), int(max_block),
+                                                   int(lookahead_frames), byref(v)))
+        return int(v.value)
+
+    def stream_bank_emitted(self, bank, n):
+        v = c_int64()
+        self._check(self.lib.sg_stream_bank_emitted(bank, int(n), byref(v)))
+        return int(v.value)
 
     def stream_destroy(self, bank):
         if bank is not None and bank.value and self._h.value:

@@ -3710,9 +3710,34 @@ extern "C" int sg_stream_create(sg_handle* h, int32_t n_slots, int32_t channels,
   if (!h || !out) return SG_E_INVALID;
   if (h->p.variant != SG_VARIANT_S) FAIL(h, SG_E_INVALID, "sg_stream_create is a variant-S entry point");
   sg::StBank* b = nullptr;
-  int rc = sg::st_create(&b, rg_ctx(h), n_slots, channels, max_block, &h->err);
+  int rc = sg::st_create(&b, rg_ctx(h), n_slots, channels, max_block, false, 0, &h->err);
   if (rc) return rc;
   *out = new sg_stream_bank{h, b};
+  return SG_OK;
+}
+
+extern "C" int sg_stream_create_nonstationary(sg_handle* h, int32_t n_slots, int32_t channels, int64_t max_block,
+                                              int32_t lookahead_frames, sg_stream_bank** out) {
+  if (!h || !out) return SG_E_INVALID;
+  if (h->p.variant != SG_VARIANT_S) FAIL(h, SG_E_INVALID, "sg_stream_create_nonstationary is a variant-S entry point");
+  sg::StBank* b = nullptr;
+  int rc = sg::st_create(&b, rg_ctx(h), n_slots, channels, max_block, true, lookahead_frames, &h->err);
+  if (rc) return rc;
+  *out = new sg_stream_bank{h, b};
+  return SG_OK;
+}
+
+extern "C" int sg_stream_state_bytes(const sg_handle* h, int32_t n_slots, int32_t channels, int64_t max_block,
+                                     int32_t lookahead_frames, int64_t* bytes) {
+  if (!h || !bytes || n_slots < 1 || channels < 1 || max_block < 1 || lookahead_frames < 0) return SG_E_INVALID;
+  sg_handle* hm = const_cast<sg_handle*>(h);
+  *bytes = sg::st_state_bytes(rg_ctx(hm), !h->p.stationary, n_slots, channels, max_block, h->p.stationary ? 0 : lookahead_frames);
+  return SG_OK;
+}
+
+extern "C" int sg_stream_bank_emitted(const sg_stream_bank* b, int64_t n, int64_t* emitted) {
+  if (!b || !emitted || n < 0) return SG_E_INVALID;
+  *emitted = sg::st_bank_emitted(b->b, n);
   return SG_OK;
 }
 

@@ -8,6 +8,10 @@
 //                 the ring / the caller's block, as k_rg_apply does)
 //   k_st_finish   overlap-add of the newly final samples into the caller's output + partial sums of the samples still
 //                 open (carry), then the state update: block -> ring, band maxima of flushed streams cleared
+// A non-stationary bank (sg_stream_create_nonstationary) runs the same four launches with k_sn_decide in the first place:
+// float64 transform, A = |X|, the forward one-pole pass carried per band, the A / fwd rows of the last L + 1 frames kept,
+// and for every frame that has L frames after it (or the stream's end, at a flush) the backward pass over those L + 1
+// rows and the sigmoid into a ring of float mask rows, which k_st_fsmooth<true> / k_st_apply<N, true> read instead of bits.
 // Nothing waits on another workgroup.  No workgroup reads state that another workgroup of the same launch writes: the
 // ring is only written by k_st_finish (which does not read it), the carry is double buffered, the bit rows of a unit are
 // written by its one decide workgroup.  One fixed evaluation order per frame and per output sample: a stream's output
@@ -32,7 +36,8 @@ namespace sg {
 struct StUnit {
   int64_t in_off, out_off;   // element of in holding the block's first sample / of out receiving sample E0
   int64_t n0, n1;            // samples received before / after this step
-  int64_t td0, td1;          // last decided frame before / after (-1: none)
+  int64_t td0, td1;          // last decided (transformed) frame before / after (-1: none)
+  int64_t ts0, ts1;          // non-stationary: last frame with a raw mask row before / after (td - lookahead; td at a flush)
   int64_t ta0, ta1;          // last applied frame before / after
   int64_t Tend;              // frames of the whole stream when flushing, else "unbounded"
   int64_t Lout;              // flush: valid samples of the inverse transform (zero tail beyond)
@@ -69,6 +74,13 @@ struct StArgs {
   float* seg;
   int n, W, H, F, FS, padL, wpr, RC, RB, nf, nt;
   double mag_scale, top_db, prop, ktot;
+  // non-stationary banks
+  double* fst;     // [unit][FS] forward state fwd[f, td]
+  double* fa;      // [unit][RF][2][FS] A and fwd rows of the last transformed frames, frame t at t % RF
+  float* mk;       // [unit][RB][FS] raw (sigmoid) mask rows, frame t at t % RB
+  int RF, L;
+  double iir_b;
+  float nthresh, slope;
 };
 
 __device__ __forceinline__ double st_nan_if_nonfinite(double P) { return (P <= 1.79769313486231570e308) ? P : (double)NAN; }
@@ -198,21 +210,90 @@ __global__ __launch_bounds__(st_nt<N>()) void k_st_decide(StArgs A) {
   }
 }
 
+// ---- non-stationary decide: forward pass over the unit's new frames, backward pass + sigmoid of the decidable ones ------
+// Band k belongs to one thread for the whole launch: the A / fwd rows it reads in the second loop are its own stores of
+// the first loop or of an earlier step, so no barrier separates the two.  S_L[f, t] = the reference's forward-backward
+// smoother of frames 0 .. e, e = min(t + L, last frame): seeded with fwd[e], then k = e .. t in that order whatever the
+// block split.  The sigmoid is the offline kernels' (ragged.hip rg_sigmoid_ratio): S = 0 gives 0 / 0 = NaN as there.
+template <int N>
+__global__ __launch_bounds__(st_nt<N>()) void k_sn_decide(StArgs A) {
+  constexpr int NT = st_nt<N>(), SY = st_sy<N>();
+  if ((int64_t)blockIdx.x >= A.n_dec) return;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  cx<double>* tw = reinterpret_cast<cx<double>*>(smem);
+  cx<double>* buf = tw + N;
+  const int lane = threadIdx.x;
+  const StTile tl = A.tiles[A.t_dec + blockIdx.x];
+  const StUnit U = A.units[tl.idx];
+  stage_twiddles<NT, N>(tw, A.tw, lane);
+  __syncthreads();
+  constexpr int M = N / NT + 1;
+  const double b = A.iir_b, c = 1.0 - A.iir_b;
+  double* fst = A.fst + (int64_t)U.state * A.FS;
+  double* fa = A.fa + (int64_t)U.state * A.RF * 2 * A.FS;
+  double fw[M];
+#pragma unroll
+  for (int m = 0; m < M; ++m) {
+    const int k = lane + NT * m;
+    fw[m] = (k <= N && U.td0 >= 0) ? fst[k] : 0.0;
+  }
+  for (int64_t t = U.td0 + 1; t <= U.td1; ++t) {
+    st_frame_fft<N>(A, U, t, buf, tw, lane);
+    double* row = fa + (t % A.RF) * 2 * A.FS;
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+      const int k = lane + NT * m;
+      if (k <= N) {
+        const cx<double> X = st_bin<N>(buf, tw, k);
+        const double a = sqrt(st_nan_if_nonfinite(X.x * X.x + X.y * X.y));
+        if (t == 0) fw[m] = a;   // fwd[f, -1] = A[f, 0]
+        fw[m] = b * a + c * fw[m];
+        row[k] = a;
+        row[A.FS + k] = fw[m];
+      }
+    }
+    team_sync<SY>();
+  }
+#pragma unroll
+  for (int m = 0; m < M; ++m) {
+    const int k = lane + NT * m;
+    if (k <= N && U.td1 > U.td0) fst[k] = fw[m];
+  }
+  for (int64_t t = U.ts0 + 1; t <= U.ts1; ++t) {
+    const int64_t e = t + A.L < U.td1 ? t + A.L : U.td1;
+    float* mrow = A.mk + ((int64_t)U.state * A.RB + t % A.RB) * A.FS;
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+      const int k = lane + NT * m;
+      if (k <= N) {
+        double s = fa[((e % A.RF) * 2 + 1) * A.FS + k];
+        for (int64_t q = e; q >= t; --q) s = b * fa[((q % A.RF) * 2 + 1) * A.FS + k] + c * s;
+        const double av = fa[(t % A.RF) * 2 * A.FS + k];
+        const float ratio = (float)(av - s) / (float)s;
+        mrow[k] = 1.0f / (1.0f + __expf(-(ratio - A.nthresh) * A.slope));
+      }
+    }
+  }
+}
+
 // ---- mask smoothing along frequency: R[row][f] = sum_df (nf + 1 - |df|) raw[row][f + df] ----------------------------
+// NS: the raw mask is a row of floats (the sigmoid) instead of a row of bits
+template <bool NS>
 __global__ __launch_bounds__(256) void k_st_fsmooth(StArgs A) {
   if ((int64_t)blockIdx.x >= A.n_fs) return;
   const StTile tl = A.tiles[A.t_fs + blockIdx.x];
   const StUnit U = A.units[tl.idx];
   const int nf = A.nf;
   for (int64_t r = tl.a; r < tl.b; ++r) {
-    const unsigned long long* brow = A.bits + ((int64_t)U.state * A.RB + r % A.RB) * A.wpr;
+    const unsigned long long* brow = NS ? nullptr : A.bits + ((int64_t)U.state * A.RB + r % A.RB) * A.wpr;
+    const float* frow = NS ? A.mk + ((int64_t)U.state * A.RB + r % A.RB) * A.FS : nullptr;
     float* out = A.R + (U.mrow + r - U.r0) * A.FS;
     for (int f = threadIdx.x; f < A.F; f += blockDim.x) {
       float acc = 0.f;
       for (int df = -nf; df <= nf; ++df) {
         const int g = f + df;
         if (g < 0 || g >= A.F) continue;
-        acc += (float)(nf + 1 - (df < 0 ? -df : df)) * (float)((brow[g >> 6] >> (g & 63)) & 1ull);
+        acc += (float)(nf + 1 - (df < 0 ? -df : df)) * (NS ? frow[g] : (float)((brow[g >> 6] >> (g & 63)) & 1ull));
       }
       out[f] = acc;
     }
@@ -220,7 +301,7 @@ __global__ __launch_bounds__(256) void k_st_fsmooth(StArgs A) {
 }
 
 // ---- applied frames: time smoothing, masked multiply, inverse transform (k_rg_apply) ---------------------------------
-template <int N>
+template <int N, bool NS>
 __global__ __launch_bounds__(st_nt<N>()) void k_st_apply(StArgs A) {
   constexpr int NT = st_nt<N>(), SY = st_sy<N>();
   if ((int64_t)blockIdx.x >= A.n_ap) return;
@@ -243,6 +324,7 @@ __global__ __launch_bounds__(st_nt<N>()) void k_st_apply(StArgs A) {
         const int64_t d = q - t;
         K += (double)(nt + 1 - (d < 0 ? -d : d)) * (double)A.R[(U.mrow + q - U.r0) * A.FS + k];
       }
+      if (NS) return (K / A.ktot) * A.prop + (1.0 - A.prop);   // smoothed first, prop_decrease after (k_rg_apply)
       return (A.prop * K + (1.0 - A.prop) * Et * (double)tri_valid(A.nf, k, A.F)) / A.ktot;
     };
     for (int k = lane; k <= N / 2; k += NT) {
@@ -325,7 +407,7 @@ __global__ __launch_bounds__(256) void k_st_finish(StArgs A) {
 
 // ---- host side ---------------------------------------------------------------------------------------------------
 struct StSlot {
-  int64_t n = 0, td = -1, ta = -1, E = 0;
+  int64_t n = 0, td = -1, ts = -1, ta = -1, E = 0;
   int par = 0;
   bool has_thr = false;
 };
@@ -333,8 +415,11 @@ struct StSlot {
 struct StBank {
   RgCtx c{};
   int n_slots = 0, C = 0, RC = 0, RB = 0, wpr = 0;
+  int ns = 0, L = 0, RF = 0;   // non-stationary bank, its lookahead in frames, depth of the A / fwd ring
   int64_t max_block = 0;
   double *ring = nullptr, *rmax = nullptr, *carry = nullptr, *thr = nullptr, *T2 = nullptr, *stage = nullptr;
+  double *fst = nullptr, *fa = nullptr;
+  float* mk = nullptr;
   unsigned long long* bits = nullptr;
   int32_t* slot_list = nullptr;
   void* tabs = nullptr;
@@ -361,7 +446,7 @@ int64_t st_emitted(int W, int H, int nt, int64_t n) {
 void st_destroy(StBank* b) {
   if (!b) return;
   for (void* p : {(void*)b->ring, (void*)b->rmax, (void*)b->carry, (void*)b->thr, (void*)b->T2, (void*)b->stage, (void*)b->bits,
-                  (void*)b->slot_list, b->tabs, b->ws})
+                  (void*)b->fst, (void*)b->fa, (void*)b->mk, (void*)b->slot_list, b->tabs, b->ws})
     if (p) (void)hipFree(p);
   delete b;
 }
@@ -397,17 +482,23 @@ struct Prof {
   ~Prof() { if (c.prof_end) c.prof_end(tok); }
 };
 
+// which: 0 = k_st_decide, 1 = k_st_apply<N, false>, 2 = k_sn_decide, 3 = k_st_apply<N, true>
 template <int N>
 hipError_t launch_fft_kernel(const StArgs& A, int which, unsigned grid, hipStream_t st) {
   const size_t lds = (size_t)(N + lpn<double>(N)) * sizeof(cx<double>);
-  const void* k = which == 0 ? reinterpret_cast<const void*>(k_st_decide<N>) : reinterpret_cast<const void*>(k_st_apply<N>);
+  const void* k = which == 0   ? reinterpret_cast<const void*>(k_st_decide<N>)
+                  : which == 1 ? reinterpret_cast<const void*>(k_st_apply<N, false>)
+                  : which == 2 ? reinterpret_cast<const void*>(k_sn_decide<N>)
+                               : reinterpret_cast<const void*>(k_st_apply<N, true>);
   if (lds > 65536) {
     hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
   }
   const dim3 blk(st_nt<N>());
   if (which == 0) hipLaunchKernelGGL(k_st_decide<N>, dim3(grid), blk, lds, st, A);
-  else hipLaunchKernelGGL(k_st_apply<N>, dim3(grid), blk, lds, st, A);
+  else if (which == 1) hipLaunchKernelGGL((k_st_apply<N, false>), dim3(grid), blk, lds, st, A);
+  else if (which == 2) hipLaunchKernelGGL(k_sn_decide<N>, dim3(grid), blk, lds, st, A);
+  else hipLaunchKernelGGL((k_st_apply<N, true>), dim3(grid), blk, lds, st, A);
   return hipGetLastError();
 }
 
@@ -436,9 +527,30 @@ int check_slots(const StBank* b, const int32_t* slots, int32_t n, const char* wh
 }
 }  // namespace
 
-int st_create(StBank** out, const RgCtx& c, int32_t n_slots, int32_t channels, int64_t max_block, std::string* err) {
+int64_t st_state_bytes(const RgCtx& c, bool ns, int64_t n_slots, int64_t channels, int64_t max_block, int64_t L) {
+  const int64_t nu = n_slots * channels, mf = max_frames(c, max_block);
+  const int64_t RC = c.W + (c.nt + L + 1) * c.H, RB = 2 * (int64_t)c.nt + 1 + L + mf;
+  int64_t per = RC * 8 + 2 * (int64_t)c.W * 8;
+  if (ns) per += (int64_t)c.FS * 8 + (L + 1 + mf) * 2 * c.FS * 8 + RB * c.FS * 4;
+  else per += (int64_t)c.FS * 8 + RB * ((c.F + 63) / 64) * 8;
+  return nu * per;
+}
+
+int st_create(StBank** out, const RgCtx& c, int32_t n_slots, int32_t channels, int64_t max_block, bool ns, int32_t lookahead,
+              std::string* err) {
   if (!geom_ok(c)) { *err = "sg_stream_create: n_fft must be a power of two from 256 to 4096"; return SG_E_UNSUPPORTED; }
-  if (!c.stationary) { *err = "sg_stream_create: only the stationary gate streams"; return SG_E_INVALID; }
+  if (!ns && !c.stationary) {
+    *err = "sg_stream_create: a non-stationary handle streams through sg_stream_create_nonstationary";
+    return SG_E_INVALID;
+  }
+  if (ns && c.stationary) { *err = "sg_stream_create_nonstationary: the handle is stationary"; return SG_E_INVALID; }
+  // (one thread per band walks the L + 1 forward rows of every decided frame: the cap bounds a step's serial work)
+  if (ns && (lookahead < 0 || lookahead > SG_STREAM_MAX_LOOKAHEAD)) {
+    char m[120];
+    snprintf(m, sizeof m, "sg_stream_create_nonstationary: lookahead_frames must be 0 .. %d", SG_STREAM_MAX_LOOKAHEAD);
+    *err = m;
+    return SG_E_INVALID;
+  }
   if (n_slots < 1 || channels < 1 || max_block < 1 || (int64_t)n_slots * channels > (1 << 24)) {
     *err = "sg_stream_create: n_slots, channels and max_block must be at least 1";
     return SG_E_INVALID;
@@ -448,10 +560,26 @@ int st_create(StBank** out, const RgCtx& c, int32_t n_slots, int32_t channels, i
   b->n_slots = n_slots;
   b->C = channels;
   b->max_block = max_block;
-  b->RC = c.W + (c.nt + 1) * c.H;
-  b->RB = (int)std::min<int64_t>(INT32_MAX, 2 * (int64_t)c.nt + 1 + max_frames(c, max_block));
+  b->ns = ns ? 1 : 0;
+  b->L = ns ? lookahead : 0;
+  // (a flush decides the L frames a push holds back on top of the block's own: the mask rows are L deeper for it)
+  const int64_t RC = c.W + ((int64_t)c.nt + b->L + 1) * c.H, RB = 2 * (int64_t)c.nt + 1 + b->L + max_frames(c, max_block);
+  const int64_t RF = (int64_t)b->L + 1 + max_frames(c, max_block);
+  if (ns && (RC > INT32_MAX || RF > INT32_MAX || RB > INT32_MAX)) {
+    char m[200];
+    snprintf(m, sizeof m, "sg_stream_create_nonstationary: max_block = %lld with lookahead_frames = %d needs rings deeper than 2^31",
+             (long long)max_block, b->L);
+    *err = m;
+    delete b;
+    return SG_E_INVALID;
+  }
+  b->RC = (int)RC;
+  b->RB = (int)std::min<int64_t>(INT32_MAX, RB);
+  b->RF = (int)RF;
   b->wpr = (c.F + 63) / 64;
   b->slots.assign(n_slots, StSlot());
+  if (ns)
+    for (auto& sl : b->slots) sl.has_thr = true;   // a non-stationary stream needs no noise profile
   const size_t nu = (size_t)n_slots * channels;
   bool ok = true;
   auto take = [&](void** p, size_t bytes, bool zero) {
@@ -460,12 +588,18 @@ int st_create(StBank** out, const RgCtx& c, int32_t n_slots, int32_t channels, i
     if (zero && hipMemset(*p, 0, bytes) != hipSuccess) ok = false;
   };
   take((void**)&b->ring, nu * b->RC * 8, false);
-  take((void**)&b->rmax, nu * c.FS * 8, true);
   take((void**)&b->carry, nu * 2 * c.W * 8, false);
-  take((void**)&b->bits, nu * (size_t)b->RB * b->wpr * 8, false);
-  take((void**)&b->thr, (size_t)n_slots * c.FS * 8, true);
-  take((void**)&b->T2, (size_t)n_slots * c.FS * 8, true);
-  take((void**)&b->stage, (size_t)c.FS * 8, true);
+  if (ns) {
+    take((void**)&b->fst, nu * c.FS * 8, true);
+    take((void**)&b->fa, nu * (size_t)b->RF * 2 * c.FS * 8, false);
+    take((void**)&b->mk, nu * (size_t)b->RB * c.FS * 4, false);
+  } else {
+    take((void**)&b->rmax, nu * c.FS * 8, true);
+    take((void**)&b->bits, nu * (size_t)b->RB * b->wpr * 8, false);
+    take((void**)&b->thr, (size_t)n_slots * c.FS * 8, true);
+    take((void**)&b->T2, (size_t)n_slots * c.FS * 8, true);
+    take((void**)&b->stage, (size_t)c.FS * 8, true);
+  }
   take((void**)&b->slot_list, (size_t)n_slots * 4, true);
   // tables and scratch of a typical step up front (a larger step grows them, which synchronises once)
   const int64_t mf = max_frames(c, max_block);
@@ -475,8 +609,11 @@ int st_create(StBank** out, const RgCtx& c, int32_t n_slots, int32_t channels, i
   b->ws_bytes = std::min<size_t>(WS_PREALLOC, nu * per_unit);
   take(&b->ws, b->ws_bytes, false);
   if (!ok) {
+    char m[200];
+    snprintf(m, sizeof m, "sg_stream_create: device allocation failed (the bank's state is %lld bytes)",
+             (long long)st_state_bytes(c, ns, n_slots, channels, max_block, b->L));
     st_destroy(b);
-    *err = "sg_stream_create: device allocation failed";
+    *err = m;
     return SG_E_NOMEM;
   }
   *out = b;
@@ -487,6 +624,7 @@ int st_set_threshold(StBank* b, const int32_t* slots, int32_t n, const double* t
                      hipStream_t st, std::string* err) {
   int rc = check_slots(b, slots, n, "sg_stream_set_threshold", err);
   if (rc) return rc;
+  if (b->ns) { *err = "sg_stream_set_threshold: a non-stationary bank takes no noise threshold"; return SG_E_INVALID; }
   if (n > b->n_slots) { *err = "sg_stream_set_threshold: more slots listed than the bank has"; return SG_E_INVALID; }
   if (n == 0) return SG_OK;
   const double* src = thresh_dev;
@@ -513,7 +651,9 @@ int st_reset(StBank* b, const int32_t* slots, int32_t n, hipStream_t st, std::st
   if (rc) return rc;
   for (int32_t i = 0; i < n; ++i) {
     // (the ring, the bit rows and the carry need no clearing: a fresh stream reads none of them before it writes them)
-    if (hipMemsetAsync(b->rmax + (size_t)slots[i] * b->C * b->c.FS, 0, (size_t)b->C * b->c.FS * 8, st) != hipSuccess) {
+    // (nor does the forward state of a non-stationary unit: frame 0 seeds it)
+    if (!b->ns &&
+        hipMemsetAsync(b->rmax + (size_t)slots[i] * b->C * b->c.FS, 0, (size_t)b->C * b->c.FS * 8, st) != hipSuccess) {
       *err = "sg_stream_reset: hipMemsetAsync failed";
       return SG_E_HIP;
     }
@@ -523,6 +663,8 @@ int st_reset(StBank* b, const int32_t* slots, int32_t n, hipStream_t st, std::st
   }
   return SG_OK;
 }
+
+int64_t st_bank_emitted(const StBank* b, int64_t n) { return st_emitted(b->c.W, b->c.H, b->c.nt + b->L, n); }
 
 int st_counters(const StBank* b, int32_t slot, int64_t* n, int64_t* emitted, std::string* err) {
   if (slot < 0 || slot >= b->n_slots) { *err = "sg_stream_counters: unknown slot"; return SG_E_INVALID; }
@@ -586,6 +728,7 @@ int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_
     U.n0 = S.n;
     U.n1 = S.n + r.n_samples;
     U.td0 = S.td;
+    U.ts0 = S.ts;
     U.ta0 = S.ta;
     U.E0 = S.E;
     U.flush = r.flush ? 1 : 0;
@@ -594,13 +737,15 @@ int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_
       U.Tend = T;
       U.Lout = (T - 1) * c.H + c.W - 2 * (int64_t)h;
       U.td1 = T - 1;
+      U.ts1 = T - 1;
       U.ta1 = T - 1;
       U.E1 = U.n1;
     } else {
       U.Tend = UNBOUNDED;
       U.Lout = UNBOUNDED;
       U.td1 = std::max(U.td0, st_tdec(c.W, c.H, U.n1));
-      U.ta1 = std::max(U.ta0, U.td1 - c.nt);
+      U.ts1 = std::max(U.ts0, U.td1 - b->L);
+      U.ta1 = std::max(U.ta0, U.ts1 - c.nt);
       U.E1 = std::max<int64_t>(0, (U.ta1 + 1) * c.H - h);
     }
     U.cov0 = U.ta0 >= 0 ? U.ta0 * c.H - h + c.W : 0;
@@ -622,7 +767,7 @@ int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_
     StSlot& N = after[i];
     N.has_thr = true;
     if (!r.flush) {
-      N.n = U.n1; N.td = U.td1; N.ta = U.ta1; N.E = U.E1;
+      N.n = U.n1; N.td = U.td1; N.ts = U.ts1; N.ta = U.ta1; N.E = U.E1;
       N.par = U.ta1 > U.ta0 ? (S.par ^ 1) : S.par;
     }
   }
@@ -631,7 +776,7 @@ int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_
   StArgs A{};
   A.t_dec = 0;
   for (size_t u = 0; u < units.size(); ++u)
-    if (units[u].td1 > units[u].td0) push(u, 0, units[u].td0 + 1, units[u].td1 + 1);
+    if (units[u].td1 > units[u].td0 || units[u].ts1 > units[u].ts0) push(u, 0, units[u].td0 + 1, units[u].td1 + 1);
   A.n_dec = (int64_t)tiles.size();
   A.t_fs = (int64_t)tiles.size();
   for (size_t u = 0; u < units.size(); ++u)
@@ -652,7 +797,7 @@ int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_
     }
     if (!U.flush)
       for (int64_t p = std::max(U.n0, U.n1 - b->RC); p < U.n1; p += 256) push(u, ST_APPEND, p, std::min(U.n1, p + 256));
-    else
+    else if (!b->ns)
       push(u, ST_CLEAR, 0, 0);
   }
   A.n_fin = (int64_t)tiles.size() - A.t_fin;
@@ -682,12 +827,20 @@ int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_
   A.nf = c.nf; A.nt = c.nt;
   A.mag_scale = c.mag_scale; A.top_db = c.top_db; A.prop = c.prop;
   A.ktot = (double)((int64_t)(c.nf + 1) * (c.nf + 1) * (int64_t)(c.nt + 1) * (c.nt + 1));
+  A.fst = b->fst; A.fa = b->fa; A.mk = b->mk; A.RF = b->RF; A.L = b->L;
+  A.iir_b = c.iir_b; A.nthresh = (float)c.nthresh; A.slope = (float)c.slope;
+  const bool ns = b->ns != 0;
   // ---- the step: the same four launches whatever was pushed
   auto grid = [](int64_t n) { return dim3((unsigned)std::max<int64_t>(1, n)); };
   hipError_t e = hipSuccess;
-  { Prof pr(c, SG_STAGE_RG_DECIDE, st); e = launch_fft(c.N, A, 0, A.n_dec, st); }
-  if (e == hipSuccess) { Prof pr(c, SG_STAGE_RG_FSMOOTH, st); hipLaunchKernelGGL(k_st_fsmooth, grid(A.n_fs), dim3(256), 0, st, A); e = hipGetLastError(); }
-  if (e == hipSuccess) { Prof pr(c, SG_STAGE_RG_APPLY, st); e = launch_fft(c.N, A, 1, A.n_ap, st); }
+  { Prof pr(c, SG_STAGE_RG_DECIDE, st); e = launch_fft(c.N, A, ns ? 2 : 0, A.n_dec, st); }
+  if (e == hipSuccess) {
+    Prof pr(c, SG_STAGE_RG_FSMOOTH, st);
+    if (ns) hipLaunchKernelGGL(k_st_fsmooth<true>, grid(A.n_fs), dim3(256), 0, st, A);
+    else hipLaunchKernelGGL(k_st_fsmooth<false>, grid(A.n_fs), dim3(256), 0, st, A);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) { Prof pr(c, SG_STAGE_RG_APPLY, st); e = launch_fft(c.N, A, ns ? 3 : 1, A.n_ap, st); }
   if (e == hipSuccess) { Prof pr(c, SG_STAGE_RG_OLA, st); hipLaunchKernelGGL(k_st_finish, grid(A.n_fin), dim3(256), 0, st, A); e = hipGetLastError(); }
   if (e != hipSuccess) {
     *err = std::string("sg_stream_push: launch failed: ") + hipGetErrorString(e);

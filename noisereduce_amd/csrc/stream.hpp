@@ -1,4 +1,5 @@
-// Banks of live streams (sg_stream_*, mi355gate.h): the stationary gate advanced block by block.
+// Banks of live streams (sg_stream_*, mi355gate.h): the stationary gate, or the non-stationary gate with a bounded
+// lookahead, advanced block by block.
 //
 // A bank holds n_slots independent streams of `channels` channels each.  Every step (sg_stream_push) takes whatever block
 // each pushed stream received and runs a FIXED number of launches, whatever the number of streams and the block lengths;
@@ -8,6 +9,11 @@
 //   rmax   [unit][FS]          running band maximum of the power, float64, NaN-sticky
 //   carry  [unit][2][W]        partial overlap-add sums of the samples not yet emitted (double buffered per step)
 //   thr/T2 [slot][FS]          threshold in dB and its compare constant on the raw power
+// A non-stationary bank (lookahead L frames; no thresholds) holds instead of bits / rmax / thr / T2:
+//   fst    [unit][FS]          forward one-pole state fwd[f, last transformed frame], float64
+//   fa     [unit][RF][2][FS]   A = |X| and fwd of the last transformed frames, float64 (RF = L + 1 + frames of max_block)
+//   mk     [unit][RB][FS]      raw sigmoid mask rows, float32 (RB = 2 nt + 1 + L + frames of max_block)
+// and its ring is RC = W + (nt + L + 1) H samples.
 // (unit = slot * channels + channel).  The counters n, t_dec, t_applied, E are host arithmetic, mirrored in the bank.
 //
 // This header is shared by api.hip (thin C wrappers) and stream.hip (tables, kernels); it holds no kernels.
@@ -27,7 +33,13 @@ struct StBank;
 // samples emitted after n received: max(0, (t_dec(n) - nt + 1) H - h), t_dec(n) = floor((n + h - W) / H)
 int64_t st_emitted(int W, int H, int nt, int64_t n);
 
-int st_create(StBank** out, const RgCtx& c, int32_t n_slots, int32_t channels, int64_t max_block, std::string* err);
+// ns: a non-stationary bank with `lookahead` frames (the handle must be non-stationary); else lookahead is ignored
+int st_create(StBank** out, const RgCtx& c, int32_t n_slots, int32_t channels, int64_t max_block, bool ns, int32_t lookahead,
+              std::string* err);
+// bytes of device state st_create allocates for such a bank (host arithmetic)
+int64_t st_state_bytes(const RgCtx& c, bool ns, int64_t n_slots, int64_t channels, int64_t max_block, int64_t L);
+// samples a stream of this bank has emitted after n received: st_emitted with nt + lookahead
+int64_t st_bank_emitted(const StBank* b, int64_t n);
 void st_destroy(StBank* b);
 // thresh_dev: F dB values on the device (the handle's); thresh_host: F dB values on the host; exactly one is non-null
 int st_set_threshold(StBank* b, const int32_t* slots, int32_t n, const double* thresh_dev, const double* thresh_host,

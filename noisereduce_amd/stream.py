@@ -1,4 +1,5 @@
-"""``StreamBank`` / ``StreamGate`` -- the stationary gate for live audio: streams gated block by block on the GPU.
+"""``StreamBank`` / ``StreamGate`` -- the gate for live audio: streams gated block by block on the GPU, with the
+stationary gate (a fixed noise profile) or the non-stationary one (no profile, a bounded lookahead).
 
 Everything else in the package needs the last sample of a recording before the first one comes out.  A ``StreamBank``
 holds many independent streams with a fixed noise profile; each step takes whatever block every stream received (0
@@ -18,8 +19,22 @@ to and including the current one.  The two agree wherever no band's maximum exce
 A NaN / Inf sample gates every band from its first frame on until the slot is flushed or reset; the NaN itself survives.
 A stream's output does not depend, bitwise, on how it was cut into blocks, on its slot, or on the other streams of a step.
 
-Out of scope: the non-stationary gate (its smoothing runs backward over the whole chunk), ``TorchGate``, integer
-blocks, several GPUs, and ``n_fft`` other than a power of two from 256 to 4096 (``ValueError``).
+``stationary=False`` streams the non-stationary gate (``reduce_noise``'s default) and takes no noise profile.  Offline its
+smoother runs forward and then backward over the whole recording; here the forward pass ``fwd[f, t] = b A[f, t] + (1 - b)
+fwd[f, t - 1]`` (``fwd[f, -1] = A[f, 0]``, ``A = |X|``, ``b`` from ``time_constant_s``) is carried per band, and the level of
+frame ``t`` is the same forward-backward smoother of the signal as known ``L = lookahead_frames`` frames later: with ``e =
+min(t + L, T - 1)``, ``s = fwd[f, e]``, then ``s = b fwd[f, k] + (1 - b) s`` for ``k = e, ..., t``.  The mask is the offline
+one from there on.  ``L = int(lookahead_ms / (H / sr * 1000))`` adds to ``nt`` everywhere above: ``emitted(n, W, H, nt +
+L)``, ``latency_samples = W + (nt + L + 1) * H``.  With ``L >= T - 1`` the output is ``reduce_noise(y, sr, stationary=False,
+chunk_size=None, padding=0)`` of the whole signal; the distance shrinks with ``L`` (16 kHz, n_fft 512 / 400 / 160,
+``time_constant_s=0.1``: 0.45 of the offline output's peak at ``L = 0``, 2.7e-3 at 32, 2.9e-7 at 128).  With a long time
+constant and a small ``L`` -- the default ``time_constant_s=2`` at ``L`` up to 64 -- the level lags the signal as any
+causal smoother does and the output differs from the offline one by more than its peak: by design, as the causal floor is.
+Digital silence gives ``0 / 0`` = NaN as offline; a NaN / Inf sample keeps the band levels NaN until the slot is flushed or
+reset.
+
+Out of scope: ``TorchGate``, integer blocks, several GPUs, and ``n_fft`` other than a power of two from 256 to 4096
+(``ValueError``).
 """
 import numpy as np
 import torch
@@ -29,6 +44,8 @@ from noisereduce_amd import _ffi
 _NONE_CHUNK = 1 << 62
 _N_FFTS = (256, 512, 1024, 2048, 4096)
 _FLOATS = (np.dtype(np.float32), np.dtype(np.float64))
+MAX_STATE_BYTES = 32 << 30      # default bound on a bank's device state (``max_state_bytes=``)
+MAX_LOOKAHEAD_FRAMES = 4096     # SG_STREAM_MAX_LOOKAHEAD (include/mi355gate.h)
 
 
 def t_decided(n, W, H):
@@ -40,6 +57,26 @@ def t_decided(n, W, H):
 def emitted(n, W, H, nt):
     """Samples a stream has emitted after receiving ``n`` (host arithmetic; no GPU)."""
     return max(0, (t_decided(n, W, H) - nt + 1) * H - W // 2)
+
+
+def iir_coefficient(time_constant_s, sr, H):
+    """One-pole coefficient of the reference's get_time_smoothed_representation."""
+    t_frames = time_constant_s * sr / float(H)
+    return (np.sqrt(1 + 4 * t_frames ** 2) - 1) / (2 * t_frames ** 2)
+
+
+def state_bytes(n_units, n_fft, W, H, nt, L, max_block, stationary):
+    """Device memory a bank holds between steps (sg_stream_state_bytes' arithmetic; DESIGN section 13's state table)."""
+    F = n_fft // 2 + 1
+    FS = (F + 15) // 16 * 16
+    mf = (max_block + W // 2) // H + 3
+    per = (W + (nt + L + 1) * H) * 8 + 2 * W * 8 + FS * 8
+    RB = 2 * nt + 1 + L + mf
+    if stationary:
+        per += RB * ((F + 63) // 64) * 8
+    else:
+        per += (L + 1 + mf) * 2 * FS * 8 + RB * FS * 4
+    return n_units * per
 
 
 def _widths(sr, n_fft, H, freq_mask_smooth_hz, time_mask_smooth_ms):
@@ -59,7 +96,9 @@ def _widths(sr, n_fft, H, freq_mask_smooth_hz, time_mask_smooth_ms):
 
 
 class StreamBank:
-    """``n_streams`` live streams of ``channels`` channels each, gated with the stationary gate (module docstring).
+    """``n_streams`` live streams of ``channels`` channels each, gated with the stationary gate or, ``stationary=False``,
+    the non-stationary one with ``lookahead_ms`` of lookahead (module docstring; no noise profile then, and
+    ``time_constant_s``, ``thresh_n_mult_nonstationary``, ``sigmoid_slope_nonstationary`` as ``reduce_noise``).
 
     The noise profile is fixed per stream: ``y_noise`` (a noise clip, ``(n,)`` or ``(C, n)``; channel mean, whole clip,
     the float64 statistics ``reduce_noise`` uses) or ``thresholds_db`` (``n_fft // 2 + 1`` dB values) sets it for every
@@ -73,10 +112,18 @@ class StreamBank:
 
     def __init__(self, sr, n_streams, channels=1, y_noise=None, thresholds_db=None, prop_decrease=1.0,
                  n_std_thresh_stationary=1.5, freq_mask_smooth_hz=500, time_mask_smooth_ms=50, n_fft=1024,
-                 win_length=None, hop_length=None, max_block=None, device="cuda", stationary=True):
-        if not stationary:
-            raise ValueError("StreamBank: only the stationary gate streams (the non-stationary gate smooths backward "
-                             "over the whole chunk)")
+                 win_length=None, hop_length=None, max_block=None, device="cuda", stationary=True, lookahead_ms=0.0,
+                 time_constant_s=2.0, thresh_n_mult_nonstationary=2, sigmoid_slope_nonstationary=10,
+                 max_state_bytes=MAX_STATE_BYTES):
+        stationary = bool(stationary)
+        if not stationary and (y_noise is not None or thresholds_db is not None):
+            raise ValueError("StreamBank: the non-stationary gate takes no noise profile (y_noise / thresholds_db)")
+        if stationary and lookahead_ms:
+            raise ValueError("StreamBank: lookahead_ms belongs to the non-stationary gate (stationary=False)")
+        if not (lookahead_ms >= 0 and np.isfinite(lookahead_ms)):
+            raise ValueError("StreamBank: lookahead_ms must be finite and at least 0")
+        if not stationary and not time_constant_s > 0:
+            raise ValueError("StreamBank: time_constant_s must be positive")
         n_fft = int(n_fft)
         if n_fft not in _N_FFTS:
             raise ValueError("StreamBank: n_fft must be a power of two from 256 to 4096")
@@ -95,18 +142,33 @@ class StreamBank:
         self.max_block = int(sr) if max_block is None else int(max_block)
         if self.max_block < 1:
             raise ValueError("StreamBank: max_block must be at least 1")
-        self.latency_samples = W + (self.nt + 1) * H
+        self.stationary = stationary
+        self.lookahead_frames = 0 if stationary else int(lookahead_ms / ((H / sr) * 1000))
+        self._lag = self.nt + self.lookahead_frames      # frames between the last one inside the audio and the last applied
+        self.latency_samples = W + (self._lag + 1) * H
+        self.state_bytes = state_bytes(self.n_streams * self.channels, n_fft, W, H, self.nt, self.lookahead_frames,
+                                       self.max_block, stationary)
+        if not stationary and self.state_bytes > max_state_bytes:
+            raise ValueError(f"StreamBank: {self.n_streams} x {self.channels} streams with lookahead_frames="
+                             f"{self.lookahead_frames} and max_block={self.max_block} need {self.state_bytes} bytes of "
+                             f"device state (max_state_bytes={max_state_bytes})")
+        if self.lookahead_frames > MAX_LOOKAHEAD_FRAMES:
+            raise ValueError(f"StreamBank: lookahead_ms={lookahead_ms} is {self.lookahead_frames} frames; at most "
+                             f"{MAX_LOOKAHEAD_FRAMES} (the backward pass of a frame is that many dependent steps per band)")
         self._n = [0] * self.n_streams        # samples received / emitted per slot (mirrors of the library's counters)
         self._e = [0] * self.n_streams
-        self._has_noise = [False] * self.n_streams
+        self._has_noise = [not stationary] * self.n_streams
         self._kind = [(False, np.dtype(np.float32), True)] * self.n_streams   # (tensor I/O, dtype, flat) of the last block
         self._bank = self._gate = None
         self._pending = []                    # noise profiles set before the first device call
         self._device_arg = device
-        self._gate_kw = dict(variant=_ffi.SG_VARIANT_S, stationary=True, n_fft=n_fft, win_length=W, hop_length=H,
+        self._gate_kw = dict(variant=_ffi.SG_VARIANT_S, stationary=stationary, n_fft=n_fft, win_length=W, hop_length=H,
                              n_grad_freq=nf if smooth else 1, n_grad_time=nt if smooth else 1, smooth_mask=smooth,
                              chunk_size=_NONE_CHUNK, padding=0, prop_decrease=prop_decrease,
                              n_std_thresh=n_std_thresh_stationary, top_db=80.0, ddof=0)
+        if not stationary:
+            self._gate_kw.update(iir_b=float(iir_coefficient(time_constant_s, sr, H)),
+                                 nonstat_thresh=thresh_n_mult_nonstationary, nonstat_slope=sigmoid_slope_nonstationary)
         if y_noise is not None or thresholds_db is not None:
             self.set_noise(range(self.n_streams), y_noise=y_noise, thresholds_db=thresholds_db)
 
@@ -116,7 +178,11 @@ class StreamBank:
         if self._bank is None:
             self._gate = _ffi.Gate(self._device_arg, **self._gate_kw)
             self.device = self._gate.device
-            self._bank = self._gate.stream_create(self.n_streams, self.channels, self.max_block)
+            if self.stationary:
+                self._bank = self._gate.stream_create(self.n_streams, self.channels, self.max_block)
+            else:
+                self._bank = self._gate.stream_create_nonstationary(self.n_streams, self.channels, self.max_block,
+                                                                    self.lookahead_frames)
         pending, self._pending = self._pending, []
         for slots, kind, val in pending:
             if kind == "db":
@@ -157,10 +223,14 @@ class StreamBank:
 
     def thresholds(self):
         """The dB threshold the handle computed last (``set_noise(..., y_noise=)``), as a numpy array (synchronises)."""
+        if not self.stationary:
+            raise ValueError("StreamBank: the non-stationary gate has no thresholds")
         return self.gate.get_noise_threshold()
 
     # -- noise profile -----------------------------------------------------------------------------------------
     def set_noise(self, slots, y_noise=None, thresholds_db=None):
+        if not self.stationary:
+            raise ValueError("set_noise: the non-stationary gate takes no noise profile")
         slots = self._slots(slots)
         if (y_noise is None) == (thresholds_db is None):
             raise ValueError("set_noise: give y_noise or thresholds_db")
@@ -230,7 +300,7 @@ class StreamBank:
         recs, outs, in_off, out_off = [], [], 0, 0
         for s, a, n, flat in items:
             n1 = self._n[s] + n
-            k = (n1 if flush else emitted(n1, W, self.hop_length, self.nt)) - self._e[s]
+            k = (n1 if flush else emitted(n1, W, self.hop_length, self._lag)) - self._e[s]
             recs.append(_ffi.SgStreamRec(slot=s, flush=int(flush), n_samples=n, in_offset=in_off, in_stride=n,
                                          out_offset=out_off, out_stride=k))
             outs.append((s, a, k, flat, out_off))
@@ -294,7 +364,8 @@ class StreamBank:
 
 
 class StreamGate:
-    """One stream: ``push(block) -> out``, ``flush() -> tail`` (a ``StreamBank`` of one slot; same arguments)."""
+    """One stream: ``push(block) -> out``, ``flush() -> tail`` (a ``StreamBank`` of one slot; same arguments,
+    ``stationary=False`` included)."""
 
     def __init__(self, sr, y_noise=None, **kw):
         self.bank = StreamBank(sr, 1, y_noise=y_noise, **kw)
