@@ -78,4 +78,12 @@ __device__ __forceinline__ double cell_db(double P, double mag_scale) {
   return 20.0 * log10(sqrt(P) * mag_scale + 2.220446049250313e-16);
 }
 
+// sigmoid(((A - S) / S - thresh) * slope) of the non-stationary raw masks (nonstationary.py:70-76): the difference in
+// float64 (cancellation), the smooth remainder (division, exp) in float32 -- the mask is a float32 field and no decision
+// hangs on it.  S = 0 gives 0 / 0 = NaN, as the reference.  The one definition for kernels.hpp and the table-driven paths.
+__device__ __forceinline__ float sigmoid_ratio(double av, double s, float nthresh, float slope) {
+  const float ratio = (float)(av - s) / (float)s;
+  return 1.0f / (1.0f + __expf(-(ratio - nthresh) * slope));
+}
+
 }  // namespace sg

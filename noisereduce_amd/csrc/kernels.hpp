@@ -845,13 +845,7 @@ __global__ void k_decide_bits_t2(const double* __restrict__ P, Geom g, const dou
 // (nonstationary.py:106-115), then sigmoid((A-S)/S - thresh) * slope) (nonstationary.py:70-76).
 // One thread per (unit, bin); lanes = bins (coalesced row walk).  raw is used as scratch for
 // the forward pass.
-// sigmoid(((A - S) / S - thresh) * slope): the difference in float64 (cancellation), the smooth
-// remainder (division, exp) in float32 -- the mask is a float32 field and no decision hangs on it.
-__device__ __forceinline__ float sigmoid_ratio(double av, double s, float nthresh, float slope) {
-  const float ratio = (float)(av - s) / (float)s;
-  return 1.0f / (1.0f + __expf(-(ratio - nthresh) * slope));
-}
-
+// The sigmoid is geom.hpp's sigmoid_ratio.
 __global__ void k_iir_sigmoid(const float* __restrict__ A, Geom g, double b, double nthresh, double slope,
                               float* __restrict__ raw) {
   const int f = blockIdx.x * blockDim.x + threadIdx.x;

@@ -7,6 +7,7 @@
 // or the lengths of the clips.
 //
 // This header is shared by api.hip (thin C wrappers, sg_handle) and ragged.hip (tables, kernels); it holds no kernels.
+// RgCtx is also what rows.hip and stream.hip take of a handle, and what tile_core.hpp's fill_consts reads.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -17,7 +18,7 @@
 
 namespace sg {
 
-// what ragged.hip needs of a handle (filled by api.hip: sg_handle stays private to that translation unit)
+// what the table-driven paths (ragged.hip, rows.hip, stream.hip) need of a handle (filled by api.hip: sg_handle stays private to that translation unit)
 struct RgCtx {
   int n, N, W, H, F, FS, padL;       // n_fft, n_fft / 2, win_length, hop, bins, padded bins, zero extension W / 2
   double mag_scale;                  // 1 / sum(w)

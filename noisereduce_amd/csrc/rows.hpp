@@ -3,8 +3,8 @@
 //
 // sg_process_batch takes one Geom per launch -- one length and one frame count for every row.  Here every row has its
 // own length, frame count T_i = 1 + len_i / hop and output length hop * (len_i / hop), and every kernel finds its work
-// through a TILE TABLE (workgroup -> row or noise row, first / last frame, band or sample), as ragged.hip's do: the
-// number of launches per sub-batch is fixed, whatever the batch size and the lengths.
+// through a TILE TABLE (workgroup -> row or noise row, first / last frame, band or sample): the number of launches per
+// sub-batch is fixed, whatever the batch size and the lengths.  The frame work is tile_core.hpp's.
 //
 // This header is shared by api.hip (thin C wrappers, sg_handle) and rows.hip (tables, kernels); it holds no kernels.
 #pragma once
@@ -13,7 +13,7 @@
 
 #include <string>
 
-#include "ragged.hpp"
+#include "ragged.hpp"   // RgCtx
 
 namespace sg {
 

@@ -16,6 +16,7 @@
 // and its ring is RC = W + (nt + L + 1) H samples.
 // (unit = slot * channels + channel).  The counters n, t_dec, t_applied, E are host arithmetic, mirrored in the bank.
 //
+// The frame work of the kernels is tile_core.hpp's, shared with the clips and the rows.
 // This header is shared by api.hip (thin C wrappers) and stream.hip (tables, kernels); it holds no kernels.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -24,7 +25,7 @@
 #include <string>
 
 #include "../../include/mi355gate.h"
-#include "ragged.hpp"
+#include "ragged.hpp"   // RgCtx
 
 namespace sg {
 
