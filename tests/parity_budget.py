@@ -13,7 +13,8 @@ helpers here hold a kernel to the float64 oracle per stage and per hop block ins
                        float64 oracle is the error a correct float32 implementation is entitled to;
 * ``local_error`` / ``budget`` / ``local_check``   per hop block: max |got - want| against FACTOR x the emulation's;
 * ``bit_diff``         decision bits against the oracle's ``raw``, leaving out cells within ``DELTA_DB`` of the threshold;
-* ``mask_bound``       what a float32 smoothed mask may differ from the oracle's by.
+* ``mask_bound``       what a float32 smoothed mask may differ from the oracle's by;
+* ``TILE_CELLS``       the matrix of the three table-driven paths (clips, rows, streams), at the end of the module.
 
 Where the numbers come from (none is taken from the code under test):
 
@@ -614,3 +615,260 @@ def _t_case(i):
 
 def t_case(i):
     return _t_case(i)
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# non-stationary float fields (tests/test_gpu_stagewise.py, tests/test_gpu_tile_parity.py)
+# ----------------------------------------------------------------------------------------------------------------
+def _field_rule(M, want, emu, what):
+    """Non-stationary float fields (<= 1): max |M - want| over the unit's field within FACTOR x the float32 emulation's
+    largest error over the same field + 4 eps32.  The budget is pooled over the WHOLE field, not over five columns as
+    for the output: a cell's error is the transform's error (~eps32 of the frame's peak bin, whatever |X| is) times
+    slope x m (1 - m) / S, which spans orders of magnitude from cell to cell -- the field's maximum sits in the few
+    cells that are both mid-slope and far below the frame's peak, and which frames hold such a cell differs between
+    two correct float32 transforms.  (Per column over t - 2 .. t + 2 this rule measured 9.7 x in one column of
+    mixed_radix-400-c5, all of it one such cell: band 192, frame 18, |X| = 2.6e-3 of the peak bin, kernel 0.5 eps32
+    of that peak off.)"""
+    err = np.abs(M.astype(np.float64) - want)
+    bud = float(np.max(np.abs(emu.astype(np.float64) - want)))
+    f, t = np.unravel_index(np.argmax(err), err.shape)
+    assert err[f, t] <= FACTOR * bud + 4 * EPS32, "%s: off by %.3g at (band %d, frame %d); the emulation's largest " \
+                                                        "error over the field is %.3g" % (what, err[f, t], f, t, bud)
+    return err[f, t] / bud if bud > 0 else 0.0
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# the tile matrix: the three table-driven paths (clips: csrc/ragged.hip, rows: csrc/rows.hip, stream: csrc/stream.hip),
+# shared by tests/test_tile_parity_host.py (conditions on the oracle) and tests/test_gpu_tile_parity.py
+# ----------------------------------------------------------------------------------------------------------------
+# Shapes are in units of the hop and the smallest that still cross every seam of csrc/tile_core.hpp: 8 frames per
+# transform tile (2 in the stream), 16 rows per smoothing tile, 256 positions per overlap-add tile, the 64-band words of
+# a bit row (F = n_fft / 2 + 1 leaves the Nyquist bit alone in the last word).
+#
+# Two inputs of column T0 differ from "two_level over a sigma = 1e-4 profile", because the oracle itself says that input
+# checks nothing there (tests/test_tile_parity_host.py holds both conditions):
+# * rows-S: TorchGate floors a band at its maximum - 40 dB.  two_level's quiet half lies 60 dB down, so every cell of it
+#   sits on the floor, 20 dB above a 1e-4 profile's threshold: the mask is all-pass.  The rows take two_level with the
+#   quiet half 30 dB down (inside the 40 dB) and the profile at that half's level, sigma = 0.1 x 10^(-30/20).
+# * stream-S: the offline oracle is the stream's truth only where no band's maximum - 80 dB exceeds its threshold (the
+#   causal floor, tests/stream_model.py: ``live is False``).  two_level's 0.5 tone stands ~100 dB over a 1e-4 profile's
+#   threshold in its band at n_fft = 4096.  The streams take the profile at sigma = 2e-3: the loud half passes, the
+#   quiet half's noise is gated, its tone passes.
+TILE_NFFT = (256, 512, 1024, 2048, 4096)
+TILE_PATHS = ("clips-S", "clips-NS", "rows-S", "rows-NS", "stream-S", "stream-NS")
+TILE_COLUMNS = [
+    dict(name="T0", signal="two_level", prop=1.0, smooth="3x2", noise="quiet"),
+    dict(name="T1", signal="dc_nyquist", prop=0.7, smooth="3x2", short_window=True),
+    dict(name="T2", signal="bin_centred", prop=1.0, smooth="off", dtype="float64"),
+    dict(name="T3", signal="burst_at_seam", prop=0.7, smooth="t9"),
+]
+# level of the noise clip a stationary cell is given where the path cannot take the statistics from the signal itself
+_TILE_SIGMA = {"two_level": 1e-4, "dc_nyquist": 0.1, "bin_centred": 0.05, "burst_at_seam": 0.003}
+_ROWS_QUIET = 10.0 ** (-30.0 / 20.0)
+_STREAM_QUIET_SIGMA = 2e-3
+# (path, n_fft, col) -> seed offset: a seed that lands a stationary decision within 1e-6 dB of its threshold, or leaves a
+# non-stationary unit without a cell below 0.1 / above 0.9, is changed (tests/test_tile_parity_host.py checks)
+_TILE_RESEED = {("rows-S", 256, 3): 7}
+
+
+def _tile_cells():
+    cells = []
+    for p, path in enumerate(TILE_PATHS):
+        for i, n_fft in enumerate(TILE_NFFT):
+            for col in (0, 1 + (p + i) % 3):      # T0 plus one of T1..T3 by rotation
+                cells.append(dict(TILE_COLUMNS[col], path=path, n_fft=n_fft, col=col, stationary=path.endswith("-S")))
+    return cells
+
+
+TILE_CELLS = _tile_cells()
+
+
+def tile_cell_id(c):
+    return "%s-%d-%s" % (c["path"], c["n_fft"], c["name"])
+
+
+def _tile_geometry(n_fft, col):
+    """(W, H, keyword arguments of the window and the smoothing) of a column."""
+    c = TILE_COLUMNS[col]
+    if c.get("short_window"):
+        W = (3 * n_fft) // 4
+        H = (W // 4) | 1
+        kw = dict(n_fft=n_fft, win_length=W, hop_length=H)
+    else:
+        W, H = n_fft, n_fft // 4
+        kw = dict(n_fft=n_fft)
+    ms = 1000.0 * H / SR
+    kw.update({"3x2": dict(freq_mask_smooth_hz=3.02 * SR / (n_fft / 2), time_mask_smooth_ms=2.02 * ms),
+               "off": dict(freq_mask_smooth_hz=None, time_mask_smooth_ms=None),
+               "t9": dict(freq_mask_smooth_hz=None, time_mask_smooth_ms=9.02 * ms)}[c["smooth"]])
+    kw["prop_decrease"] = c["prop"]
+    return W, H, kw
+
+
+def _tile_signal(kind, n, seed, n_fft, cs, pad, quiet=1e-3):
+    if kind == "two_level":
+        y = signals._base(n, SR, seed)
+        y[n // 2:] *= quiet
+        return y.astype(F32)
+    if kind == "dc_nyquist":
+        return signals.dc_nyquist(n, SR, seed)
+    if kind == "bin_centred":
+        return signals.bin_centred(n, n_fft, seed)
+    return signals.burst_at_seam(n, cs, pad, SR, seed)
+
+
+def _tile_noise(sigma, n, seed):
+    return (sigma * np.random.default_rng(seed).standard_normal(n)).astype(F32)
+
+
+def _primes_near(x):
+    """The prime closest to x from above."""
+    p = max(2, int(x))
+    while any(p % d == 0 for d in range(2, int(p ** 0.5) + 1)):
+        p += 1
+    return p
+
+
+def stream_cuts(kind, N, W, H, rng):
+    """Block plans of a stream of N samples (``whole`` / ``edge`` / ``random``: tests/test_gpu_stream.py's ``_cuts``)."""
+    if kind == "whole":
+        return []
+    if kind == "edge":       # 1-sample blocks around the sample that completes a frame, and a few 0-sample blocks
+        e = 3 * H - W // 2 + W
+        return sorted(min(c, N) for c in (e - 3, e - 2, e - 1, e, e, e, e + 1, e + 2, N // 2, N // 2))
+    if kind == "prime":      # blocks of a prime number of samples near 1.3 hops
+        p = _primes_near(1.3 * H)
+        return list(range(p, N, p))
+    if kind == "random":
+        return sorted(int(c) for c in rng.integers(0, N + 1, 7))
+    raise KeyError(kind)
+
+
+STREAM_PLANS = ("whole", "edge", "prime", "random")
+
+
+def tile_window(W):
+    """The (W,) table TorchGate hands the engine: torch's float32 Hann window, as float64 (torch is imported here only:
+    a numpy float32 Hann may differ from torch's in the last bit, which is the size of the budget)."""
+    import torch
+    return torch.hann_window(W).double().numpy()
+
+
+@functools.lru_cache(maxsize=None)
+def _tile_case(path, n_fft, col):
+    c = dict(TILE_COLUMNS[col], path=path, n_fft=n_fft, col=col, stationary=path.endswith("-S"))
+    stationary = c["stationary"]
+    W, H, kw = _tile_geometry(n_fft, col)
+    dtype = c.get("dtype", "float32")
+    kind = c["signal"]
+    seed = 7000 * TILE_PATHS.index(path) + 100 * col + n_fft % 997 + _TILE_RESEED.get((path, n_fft, col), 0)
+    nlen = max(24 * H, 2 * W)
+    sigma = _TILE_SIGMA[kind]
+    case = dict(cell=c, W=W, H=H, kw=kw, dtype=dtype, seed=seed)
+    if path.startswith("clips"):
+        cs, pad = 24 * H + 5, 4 * H + 3
+        lens = [2 * cs + cs // 3, cs, cs + 1, W - 3, 8 * H * 3 - 1]
+        chans = [1, 2, 1, 1, 2]
+        ys = []
+        for i, (n, C) in enumerate(zip(lens, chans)):
+            ch = [_tile_signal(kind, n, seed + 31 * i + 7 * k, n_fft, cs, pad) for k in range(C)]
+            if i == 2:        # time-reversed: the one kept sample of its second chunk (and that chunk's frames) is loud
+                ch = [v[::-1].copy() for v in ch]
+            ys.append(np.stack(ch) if C > 1 else ch[0])
+        y_noise = None
+        if stationary and col == 0:
+            y_noise = _tile_noise(sigma, nlen, seed + 5)                      # one shared noise clip
+        elif stationary:                                                      # per clip; clip 1 (2 channels) is its own
+            y_noise = [None if i == 1 else _tile_noise(sigma * (1.0, 0.0, 0.5, 1.0, 0.7)[i], nlen, seed + 5 + i)
+                       for i in range(len(ys))]                                # (profiles of different levels)
+        case.update(ys=ys, y_noise=y_noise, kw=dict(kw, chunk_size=cs, padding=pad, stationary=stationary))
+    elif path.startswith("rows"):
+        L = 40 * H + 13
+        lens = [L, 2 * W, 2 * W + 1, 15 * H + 3, 16 * H, 23 * H + H - 1, 24 * H + 1]      # T = 1 + n // H: .., 16, 17, 24, 25
+        x = np.full((len(lens), L), np.nan, dtype=F32)
+        for b, n in enumerate(lens):
+            # (bursts at a quarter and inside the second half of the row: two 2 x H bursts in a 2 W row leave the row's own
+            # statistics without a passing cell when they sit in the middle)
+            x[b, :n] = _tile_signal(kind, n, seed + 31 * b, n_fft, n // 4, 2 * H, quiet=_ROWS_QUIET)
+        xn = _tile_noise(0.1 * _ROWS_QUIET, nlen, seed + 5)[None, :] if (stationary and col == 0) else None
+        case.update(x=x, lengths=np.array(lens, dtype=np.int64), xn=xn, kw=dict(kw, nonstationary=not stationary))
+    else:
+        C = 2 if col == 0 else 1
+        N = W + 40 * H + 13
+        ch = [_tile_signal(kind, N, seed + 7 * k, n_fft, N // 3, 4 * H) for k in range(C)]
+        y = np.stack(ch) if C > 1 else ch[0]
+        rng = np.random.default_rng(seed + 3)
+        plans = {k: stream_cuts(k, N, W, H, rng) for k in STREAM_PLANS}
+        noise = _tile_noise(_STREAM_QUIET_SIGMA if col == 0 else sigma, nlen, seed + 5) if stationary else None
+        T = (N + 2 * (W // 2) - W) // H + 1
+        case.update(y=y, C=C, plans=plans, y_noise=noise, frames=T, lookahead_ms=(T + 2) * H / SR * 1000.0,
+                    kw=dict(kw, stationary=stationary, chunk_size=None, padding=0))
+    return case
+
+
+def tile_case(c):
+    """Inputs of a tile cell (float32-valued arrays; ``dtype`` is what the call is given).  clips: ``ys``, ``y_noise``
+    (None, one array, or a per-clip list), ``kw`` for reduce_noise_batch / ``oracle_units``.  rows: ``x`` (B, L) with
+    NaN beyond ``lengths``, ``xn``, ``kw`` for TorchGate / ``torchgate_units``.  stream: ``y``, ``C``, ``plans`` {name:
+    cuts}, ``y_noise``, ``lookahead_ms`` (covers the stream), ``kw`` for ``oracle_units``."""
+    return _tile_case(c["path"], c["n_fft"], c["col"])
+
+
+@functools.lru_cache(maxsize=6)
+def _tile_oracle(path, n_fft, col):
+    case = _tile_case(path, n_fft, col)
+    f64 = lambda a: None if a is None else np.asarray(a, dtype=np.float64)   # noqa: E731
+    if path.startswith("clips"):
+        yn = case["y_noise"]
+        return [oracle_units(f64(y), SR, y_noise=f64(yn[i]) if isinstance(yn, list) else f64(yn), **case["kw"])[1]
+                for i, y in enumerate(case["ys"])]
+    if path.startswith("rows"):
+        window = tile_window(case["W"])
+        return [torchgate_units(f64(case["x"][b:b + 1, :int(n)]), SR, xn=f64(case["xn"]), window=window, **case["kw"])[1]
+                for b, n in enumerate(case["lengths"])]
+    return [oracle_units(f64(case["y"]), SR, y_noise=f64(case["y_noise"]), **case["kw"])[1]]
+
+
+def tile_oracle(c):
+    """The oracle's units of a tile cell: one list per clip / row / stream (channel-major, then chunks)."""
+    return _tile_oracle(c["path"], c["n_fft"], c["col"])
+
+
+def live_frames(unit):
+    """First and last frame of a variant-S unit whose window reaches a kept sample."""
+    c = unit["cfg"]
+    k0, k1 = unit["keep"]
+    T = unit["raw"].shape[1]
+    h = c["W"] // 2
+    lo = max(0, -(-(k0 + h - c["W"] + 1) // c["H"]))
+    hi = min(T - 1, (k1 - 1 + h) // c["H"])
+    return lo, hi
+
+
+@functools.lru_cache(maxsize=None)
+def causal_floor_case(n_fft):
+    """The input of test_causal_floor_is_the_models_and_not_the_offline_one (tests/test_gpu_stream.py) at another n_fft:
+    1e-5 noise, a 0.5 tone from the middle on, a 1e-5 noise profile -- the running band maximum lifts the floor above
+    the threshold from the middle on, so the truth is the causal model (tests/stream_model.py), not the offline oracle.
+    Returns ``dict(y, noise, kw, unit)``: ``unit`` is the offline oracle's with ``raw`` / ``mask`` / ``y`` / ``want`` redone
+    under the causal floor (same keys; local_check / emulate_f32 apply as they stand)."""
+    H = n_fft // 4
+    rng = np.random.default_rng(11 + n_fft)
+    N = n_fft + 40 * H + 13
+    y = 1e-5 * rng.standard_normal(N)
+    y[N // 2:] += 0.5 * np.sin(2 * np.pi * 1000.0 * np.arange(N - N // 2) / SR)
+    y = y.astype(F32)
+    noise = (1e-5 * rng.standard_normal(max(24 * H, 2 * n_fft))).astype(F32)
+    kw = dict(n_fft=n_fft, stationary=True, chunk_size=None, padding=0, freq_mask_smooth_hz=3.02 * SR / (n_fft / 2),
+              time_mask_smooth_ms=2.02 * 1000.0 * H / SR)
+    _, units = oracle_units(y.astype(np.float64), SR, y_noise=noise.astype(np.float64), **kw)
+    u = dict(units[0])
+    with np.errstate(divide="ignore"):
+        db = 20.0 * np.log10(np.abs(u["Z"]) + O.EPS64)
+    u["db"] = np.maximum(db, np.maximum.accumulate(db, axis=1) - 80.0)
+    u["raw"] = u["db"] > u["thresh"][:, None]
+    u["mask"] = smooth_mask(u["raw"], u["cfg"])
+    u["y"] = regate(u, mask=u["mask"])
+    k0, k1 = u["keep"]
+    u["want"] = u["y"][k0:k1]
+    return dict(y=y, noise=noise, kw=kw, unit=u, offline=units[0])

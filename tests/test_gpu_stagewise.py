@@ -25,6 +25,7 @@ import torch
 
 from oracle import spectralgate_oracle as O
 from tests import parity_budget as PB
+from tests.parity_budget import _field_rule
 
 pytestmark = pytest.mark.gpu
 
@@ -183,23 +184,6 @@ def _check_stationary_mask(tag, gate, units, materialised, must_exist):
         assert len(cells) == 0, "%s unit %d: smoothed mask off by up to %.3g (bound %.3g) at %d cells, first (band, frame) " \
                                 "%s" % (tag, ui, w, bound, len(cells), cells[:6].tolist())
     return True
-
-
-def _field_rule(M, want, emu, what):
-    """Non-stationary float fields (<= 1): max |M - want| over the unit's field within FACTOR x the float32 emulation's
-    largest error over the same field + 4 eps32.  The budget is pooled over the WHOLE field, not over five columns as
-    for the output: a cell's error is the transform's error (~eps32 of the frame's peak bin, whatever |X| is) times
-    slope x m (1 - m) / S, which spans orders of magnitude from cell to cell -- the field's maximum sits in the few
-    cells that are both mid-slope and far below the frame's peak, and which frames hold such a cell differs between
-    two correct float32 transforms.  (Per column over t - 2 .. t + 2 this rule measured 9.7 x in one column of
-    mixed_radix-400-c5, all of it one such cell: band 192, frame 18, |X| = 2.6e-3 of the peak bin, kernel 0.5 eps32
-    of that peak off.)"""
-    err = np.abs(M.astype(np.float64) - want)
-    bud = float(np.max(np.abs(emu.astype(np.float64) - want)))
-    f, t = np.unravel_index(np.argmax(err), err.shape)
-    assert err[f, t] <= PB.FACTOR * bud + 4 * PB.EPS32, "%s: off by %.3g at (band %d, frame %d); the emulation's largest " \
-                                                        "error over the field is %.3g" % (what, err[f, t], f, t, bud)
-    return err[f, t] / bud if bud > 0 else 0.0
 
 
 def _check_nonstationary_fields(tag, gate, units, emus, raw_must_exist):
