@@ -254,6 +254,33 @@ SG_API int sg_stream_create_nonstationary(sg_handle* h, int32_t n_slots, int32_t
 SG_API int sg_stream_state_bytes(const sg_handle* h, int32_t n_slots, int32_t channels, int64_t max_block,
                                  int32_t lookahead_frames, int64_t* bytes);
 SG_API int sg_stream_bank_emitted(const sg_stream_bank* b, int64_t n, int64_t* emitted);
+/* The stationary gate with the noise profile learnt from the stream itself (the handle is stationary; n_std_thresh and
+ * top_db are its own).  Offline, without a noise clip, the reference takes a band's threshold from the mean and the standard
+ * deviation of the band's floored dB values over the whole recording; here they are a running estimate, carried per
+ * (stream, channel) and band and evaluated inside the decide launch.  For frames t = 0, 1, ... in order, the recurrence being
+ * the definition:
+ *   db = 20 log10(|X[f, t]| + eps)    rmax = max(rmax, db)    x = max(db, rmax - top_db)          (NaN-sticky)
+ *   if learn_frames < 0 or t < learn_frames:  Wn = forget * Wn + 1,  d = x - mu,  mu += d / Wn,  M2 = forget * M2 + d * (x - mu)
+ *   thr = mu + n_std_thresh * sqrt(M2 / Wn)    the cell passes when x > thr
+ * from Wn = mu = M2 = 0.  forget = 1 gives the cumulative mean and standard deviation (ddof = 0) of frames 0 .. t; forget =
+ * exp(-hop / (sr * memory_s)) in (0, 1) forgets exponentially; after learn_frames frames the profile is held.  Frame t is part
+ * of its own threshold, so frame 0 is gated whole (thr = x); a band whose dB value is exactly constant stays exactly gated; a
+ * NaN / Inf sample gates every band until the slot is flushed or reset; forget <= 1 - 1 / (1 + n_std_thresh^2) (0.69 for 1.5)
+ * gates everything, since a cell lies at most sqrt(Wn - 1) deviations above a mean it is part of and Wn < 1 / (1 - forget).
+ * Every channel has its own statistics (the reference
+ * takes the threshold from the channel mean; no difference for one channel).  With forget = 1, learn_frames < 0 and no band
+ * ranging over more than top_db, the threshold after the last frame of a stream is the reference's threshold of that signal as
+ * its own noise clip.  Frames, E(n), the delay, flush and the launches per step are a stationary bank's.  forget outside
+ * (0, 1] or learn_frames == 0: SG_E_INVALID.  sg_stream_set_threshold fails on such a bank; a flush and sg_stream_reset clear
+ * the statistics.
+ * sg_stream_noise_profile: the threshold (dB) after the last decided frame of every channel of `slot`, channels x (n_fft / 2 +
+ * 1) values to thresh_host, NaN for a channel without a decided frame.  SYNCHRONISES `stream` (the only call here that
+ * does).  sg_stream_state_bytes_adaptive: sg_stream_state_bytes for such a bank. */
+SG_API int sg_stream_create_adaptive(sg_handle* h, int32_t n_slots, int32_t channels, int64_t max_block, double forget,
+                                     int64_t learn_frames, sg_stream_bank** out);
+SG_API int sg_stream_noise_profile(sg_stream_bank* b, int32_t slot, double* thresh_host, int32_t n_bins, void* stream);
+SG_API int sg_stream_state_bytes_adaptive(const sg_handle* h, int32_t n_slots, int32_t channels, int64_t max_block,
+                                          int64_t* bytes);
 
 /* ---- variant T -------------------------------------------------------------------- */
 

@@ -124,6 +124,9 @@ _PROTOTYPES = {
     "sg_stream_create_nonstationary": (c_int, [c_void_p, c_int32, c_int32, c_int64, c_int32, POINTER(c_void_p)]),
     "sg_stream_state_bytes": (c_int, [c_void_p, c_int32, c_int32, c_int64, c_int32, POINTER(c_int64)]),
     "sg_stream_bank_emitted": (c_int, [c_void_p, c_int64, POINTER(c_int64)]),
+    "sg_stream_create_adaptive": (c_int, [c_void_p, c_int32, c_int32, c_int64, c_double, c_int64, POINTER(c_void_p)]),
+    "sg_stream_noise_profile": (c_int, [c_void_p, c_int32, POINTER(c_double), c_int32, c_void_p]),
+    "sg_stream_state_bytes_adaptive": (c_int, [c_void_p, c_int32, c_int32, c_int64, POINTER(c_int64)]),
     "sg_set_option": (c_int, [c_void_p, c_int32, c_int64]),
     "sg_get_option": (c_int, [c_void_p, c_int32, POINTER(c_int64)]),
     "sg_check_errors": (c_int, [c_void_p, c_void_p]),
@@ -546,8 +549,28 @@ class Gate:
                                                                 int(lookahead_frames), byref(b)))
         return b
 
-    def stream_state_bytes(self, n_slots, channels, max_block, lookahead_frames=0):
+    def stream_create_adaptive(self, n_slots, channels, max_block, forget, learn_frames):
+        """forget: per-frame factor in (0, 1]; learn_frames: >= 1, or negative for unlimited."""
+        b = c_void_p()
+        with torch.cuda.device(self.device):
+            self._check(self.lib.sg_stream_create_adaptive(self._h, int(n_slots), int(channels), int(max_block),
+                                                           float(forget), int(learn_frames), byref(b)))
+        return b
+
+    def stream_noise_profile(self, bank, slot, channels):
+        """(channels, n_bins) float64 dB thresholds of an adaptive bank's slot (synchronises the current stream)."""
+        out = np.empty((int(channels), self.n_bins), dtype=np.float64)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.sg_stream_noise_profile(bank, int(slot), out.ctypes.data_as(POINTER(c_double)),
+                                                         self.n_bins, self._stream()))
+        return out
+
+    def stream_state_bytes(self, n_slots, channels, max_block, lookahead_frames=0, adaptive=False):
         v = c_int64()
+        if adaptive:
+            self._check(self.lib.sg_stream_state_bytes_adaptive(self._h, int(n_slots), int(channels), int(max_block),
+                                                                byref(v)))
+            return int(v.value)
         self._check(self.lib.sg_stream_state_bytes(self._h, int(n_slots), int(channels), int(max_block),
                                                    int(lookahead_frames), byref(v)))
         return int(v.value)

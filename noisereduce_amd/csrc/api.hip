@@ -3710,7 +3710,7 @@ extern "C" int sg_stream_create(sg_handle* h, int32_t n_slots, int32_t channels,
   if (!h || !out) return SG_E_INVALID;
   if (h->p.variant != SG_VARIANT_S) FAIL(h, SG_E_INVALID, "sg_stream_create is a variant-S entry point");
   sg::StBank* b = nullptr;
-  int rc = sg::st_create(&b, rg_ctx(h), n_slots, channels, max_block, false, 0, &h->err);
+  int rc = sg::st_create(&b, rg_ctx(h), n_slots, channels, max_block, false, 0, nullptr, &h->err);
   if (rc) return rc;
   *out = new sg_stream_bank{h, b};
   return SG_OK;
@@ -3721,7 +3721,7 @@ extern "C" int sg_stream_create_nonstationary(sg_handle* h, int32_t n_slots, int
   if (!h || !out) return SG_E_INVALID;
   if (h->p.variant != SG_VARIANT_S) FAIL(h, SG_E_INVALID, "sg_stream_create_nonstationary is a variant-S entry point");
   sg::StBank* b = nullptr;
-  int rc = sg::st_create(&b, rg_ctx(h), n_slots, channels, max_block, true, lookahead_frames, &h->err);
+  int rc = sg::st_create(&b, rg_ctx(h), n_slots, channels, max_block, true, lookahead_frames, nullptr, &h->err);
   if (rc) return rc;
   *out = new sg_stream_bank{h, b};
   return SG_OK;
@@ -3733,6 +3733,34 @@ extern "C" int sg_stream_state_bytes(const sg_handle* h, int32_t n_slots, int32_
   sg_handle* hm = const_cast<sg_handle*>(h);
   *bytes = sg::st_state_bytes(rg_ctx(hm), !h->p.stationary, n_slots, channels, max_block, h->p.stationary ? 0 : lookahead_frames);
   return SG_OK;
+}
+
+extern "C" int sg_stream_create_adaptive(sg_handle* h, int32_t n_slots, int32_t channels, int64_t max_block, double forget,
+                                         int64_t learn_frames, sg_stream_bank** out) {
+  if (!h || !out) return SG_E_INVALID;
+  if (h->p.variant != SG_VARIANT_S) FAIL(h, SG_E_INVALID, "sg_stream_create_adaptive is a variant-S entry point");
+  sg::StBank* b = nullptr;
+  const sg::StAdaptive ad{forget, learn_frames};
+  int rc = sg::st_create(&b, rg_ctx(h), n_slots, channels, max_block, false, 0, &ad, &h->err);
+  if (rc) return rc;
+  *out = new sg_stream_bank{h, b};
+  return SG_OK;
+}
+
+extern "C" int sg_stream_state_bytes_adaptive(const sg_handle* h, int32_t n_slots, int32_t channels, int64_t max_block,
+                                              int64_t* bytes) {
+  if (!h || !bytes || n_slots < 1 || channels < 1 || max_block < 1 || !h->p.stationary) return SG_E_INVALID;
+  sg_handle* hm = const_cast<sg_handle*>(h);
+  *bytes = sg::st_state_bytes(rg_ctx(hm), false, n_slots, channels, max_block, 0, true);
+  return SG_OK;
+}
+
+extern "C" int sg_stream_noise_profile(sg_stream_bank* b, int32_t slot, double* thresh_host, int32_t n_bins, void* stream) {
+  if (!b) return SG_E_INVALID;
+  sg_handle* h = b->h;
+  if (!thresh_host) FAIL(h, SG_E_INVALID, "sg_stream_noise_profile: thresh_host is null");
+  if (n_bins != h->F) FAIL(h, SG_E_INVALID, "sg_stream_noise_profile: n_bins must be %d", h->F);
+  return sg::st_noise_profile(b->b, slot, thresh_host, (hipStream_t)stream, &h->err);
 }
 
 extern "C" int sg_stream_bank_emitted(const sg_stream_bank* b, int64_t n, int64_t* emitted) {

@@ -12,6 +12,10 @@
 // float64 transform, A = |X|, the forward one-pole pass carried per band, the A / fwd rows of the last L + 1 frames kept,
 // and for every frame that has L frames after it (or the stream's end, at a flush) the backward pass over those L + 1
 // rows and the sigmoid into a ring of float mask rows, which k_st_fsmooth<true> / k_st_apply<N, true> read instead of bits.
+// An adaptive bank (sg_stream_create_adaptive) is a stationary bank without a noise profile: k_sa_decide takes the first
+// place and learns the threshold of every band from the stream itself, a running weighted mean and deviation of the
+// floored dB values carried per band (nst), evaluated frame by frame before the compare.  The other three launches are the
+// stationary ones.
 // What a frame goes through is tile_core.hpp's, shared with ragged.hip and rows.hip; this file holds what only a stream
 // has: the ring / block loader, the decisions against a RUNNING band maximum, the carried recurrence, the carry of the
 // overlap-add and the state update.
@@ -73,6 +77,10 @@ struct StArgs {
   double* fa;      // [unit][RF][2][FS] A and fwd rows of the last transformed frames, frame t at t % RF
   float* mk;       // [unit][RB][FS] raw (sigmoid) mask rows, frame t at t % RB
   int RF, L;
+  // adaptive banks
+  double* nst;     // [unit][3][FS] weight sum Wn, mean mu and weighted squared deviations M2 of the floored dB values
+  double lam;      // forgetting factor per frame, (0, 1]
+  int64_t learn;   // frames that update the statistics (negative: all of them)
   TileConsts c;
 };
 
@@ -155,6 +163,89 @@ __global__ __launch_bounds__(tile_nt<N>()) void k_st_decide(StArgs A) {
   for (int m = 0; m < M; ++m) {
     const int k = lane + NT * m;
     if (k <= N) rmax[k] = rm[m];
+  }
+}
+
+// ---- adaptive decide: the threshold of a band is learnt from the stream's own frames -----------------------------------
+// Per band, frames in order (the recurrence IS the definition; West's weighted incremental moments):
+//   rmax = max(rmax, dB)   x = max(dB, rmax - top_db)
+//   while learning:  Wn = lam Wn + 1,  d = x - mu,  mu += d / Wn,  M2 = lam M2 + d (x - mu)
+//   thr = mu + n_std sqrt(M2 / Wn)   pass = x > thr
+// Frame t is part of its own threshold.  The compare is in dB: the threshold moves with every frame, so there is no compare
+// constant on the raw power and no band mode.  The running maximum lives in registers as its dB value; the state keeps the
+// power that gave it (what k_st_decide keeps), written when the maximum moves and turned into dB again at the next entry:
+// cell_db of the same double, so the same bits whatever the block split.  (A fourth register array for the power costs
+// n_fft = 1024 its registers: the one-wavefront team then spills.)  A constant band has d = 0 exactly: mu and M2 stay exact
+// and the compare is exactly false, which S2 / n - mean^2 would leave to rounding.  Wn depends on the frame only; it is
+// stored per band so that a unit's state is self-contained.  The moments are evaluated without contraction: one rounding
+// per operation of the recurrence as written.
+template <int N>
+__global__ __launch_bounds__(tile_nt<N>()) void k_sa_decide(StArgs A) {
+  constexpr int NT = tile_nt<N>(), SY = tile_sy<N>();
+  if ((int64_t)blockIdx.x >= A.n_dec) return;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  cx<double>* tw = reinterpret_cast<cx<double>*>(smem);
+  cx<double>* buf = tw + N;
+  const int lane = threadIdx.x;
+  const Tile tl = A.tiles[A.t_dec + blockIdx.x];
+  const StUnit U = A.units[tl.idx];
+  stage_tile_twiddles<N>(tw, A.c.tw);
+  constexpr int M = tile_bins<N>();
+  const int FS = A.c.FS;
+  double* rmax = A.rmax + (int64_t)U.state * FS;
+  double* nst = A.nst + (int64_t)U.state * 3 * FS;
+  double rd[M], mu[M], m2[M];
+  double wn = nst[lane];   // (lane < NT <= N: a band of the unit)
+#pragma unroll
+  for (int m = 0; m < M; ++m) {
+    const int k = lane + NT * m;
+    rd[m] = mu[m] = m2[m] = 0.0;
+    if (k <= N) {
+      rd[m] = cell_db(rmax[k], A.c.mag_scale);
+      mu[m] = nst[FS + k];
+      m2[m] = nst[2 * FS + k];
+    }
+  }
+  for (int64_t t = tl.a; t < tl.b; ++t) {
+    st_frame_fft<N>(A, U, t, buf, tw, lane);
+    unsigned long long* row = A.bits + ((int64_t)U.state * A.RB + t % A.RB) * A.c.wpr;
+    const bool learn = A.learn < 0 || t < A.learn;
+    if (learn) wn = A.lam * wn + 1.0;
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+      const int k = lane + NT * m;
+      bool pass = false;
+      if (k <= N) {
+        const double P = bin_power<N>(buf, tw, k);
+        const double db = cell_db(P, A.c.mag_scale);
+        if (db != db || db > rd[m]) {   // the maximum moves (NaN-sticky): its power goes to the state at once
+          rd[m] = nanmax(rd[m], db);
+          rmax[k] = (rd[m] != rd[m]) ? (double)NAN : P;
+        }
+        {
+#pragma clang fp contract(off)
+          const double x = nanmax(db, rd[m] - A.c.top_db);
+          if (learn) {
+            const double d = x - mu[m];
+            mu[m] = mu[m] + d / wn;
+            m2[m] = A.lam * m2[m] + d * (x - mu[m]);
+          }
+          const double thr = mu[m] + A.c.n_std * sqrt(m2[m] / wn);
+          pass = x > thr;
+        }
+      }
+      store_ballot(row, A.c.wpr, lane, k, pass);
+    }
+    team_sync<SY>();
+  }
+#pragma unroll
+  for (int m = 0; m < M; ++m) {
+    const int k = lane + NT * m;
+    if (k <= N) {
+      nst[k] = wn;
+      nst[FS + k] = mu[m];
+      nst[2 * FS + k] = m2[m];
+    }
   }
 }
 
@@ -269,6 +360,8 @@ __global__ __launch_bounds__(256) void k_st_finish(StArgs A) {
   const int W = A.c.W, H = A.c.H;
   if (tl.kind == ST_CLEAR) {
     for (int f = threadIdx.x; f < A.c.FS; f += blockDim.x) A.rmax[(int64_t)U.state * A.c.FS + f] = 0.0;
+    if (A.nst)
+      for (int f = threadIdx.x; f < 3 * A.c.FS; f += blockDim.x) A.nst[(int64_t)U.state * 3 * A.c.FS + f] = 0.0;
     return;
   }
   const int64_t p = tl.a + threadIdx.x;
@@ -309,9 +402,12 @@ struct StBank {
   RgCtx c{};
   int n_slots = 0, C = 0, RC = 0, RB = 0, wpr = 0;
   int ns = 0, L = 0, RF = 0;   // non-stationary bank, its lookahead in frames, depth of the A / fwd ring
+  int ad = 0;                  // adaptive bank: the noise statistics are learnt from the stream (nst)
+  double lam = 1.0;
+  int64_t learn = -1;
   int64_t max_block = 0;
   double *ring = nullptr, *rmax = nullptr, *carry = nullptr, *thr = nullptr, *T2 = nullptr, *stage = nullptr;
-  double *fst = nullptr, *fa = nullptr;
+  double *fst = nullptr, *fa = nullptr, *nst = nullptr;
   float* mk = nullptr;
   unsigned long long* bits = nullptr;
   int32_t* slot_list = nullptr;
@@ -335,7 +431,7 @@ int64_t st_emitted(int W, int H, int nt, int64_t n) {
 void st_destroy(StBank* b) {
   if (!b) return;
   for (void* p : {(void*)b->ring, (void*)b->rmax, (void*)b->carry, (void*)b->thr, (void*)b->T2, (void*)b->stage, (void*)b->bits,
-                  (void*)b->fst, (void*)b->fa, (void*)b->mk, (void*)b->slot_list, b->tabs, b->ws})
+                  (void*)b->fst, (void*)b->fa, (void*)b->nst, (void*)b->mk, (void*)b->slot_list, b->tabs, b->ws})
     if (p) (void)hipFree(p);
   delete b;
 }
@@ -361,17 +457,29 @@ int check_slots(const StBank* b, const int32_t* slots, int32_t n, const char* wh
 }
 }  // namespace
 
-int64_t st_state_bytes(const RgCtx& c, bool ns, int64_t n_slots, int64_t channels, int64_t max_block, int64_t L) {
+int64_t st_state_bytes(const RgCtx& c, bool ns, int64_t n_slots, int64_t channels, int64_t max_block, int64_t L, bool adaptive) {
   const int64_t nu = n_slots * channels, mf = max_frames(c, max_block);
   const int64_t RC = c.W + (c.nt + L + 1) * c.H, RB = 2 * (int64_t)c.nt + 1 + L + mf;
   int64_t per = RC * 8 + 2 * (int64_t)c.W * 8;
   if (ns) per += (int64_t)c.FS * 8 + (L + 1 + mf) * 2 * c.FS * 8 + RB * c.FS * 4;
   else per += (int64_t)c.FS * 8 + RB * ((c.F + 63) / 64) * 8;
+  if (adaptive) per += 3 * (int64_t)c.FS * 8;
   return nu * per;
 }
 
 int st_create(StBank** out, const RgCtx& c, int32_t n_slots, int32_t channels, int64_t max_block, bool ns, int32_t lookahead,
-              std::string* err) {
+              const StAdaptive* ad, std::string* err) {
+  if (ad && !c.stationary) { *err = "sg_stream_create_adaptive: the handle is not stationary"; return SG_E_INVALID; }
+  if (ad && !(ad->forget > 0.0 && ad->forget <= 1.0)) {
+    char m[120];
+    snprintf(m, sizeof m, "sg_stream_create_adaptive: forget must lie in (0, 1], got %g", ad->forget);
+    *err = m;
+    return SG_E_INVALID;
+  }
+  if (ad && ad->learn_frames == 0) {
+    *err = "sg_stream_create_adaptive: learn_frames must be at least 1 (or negative: unlimited), got 0";
+    return SG_E_INVALID;
+  }
   if (!tile_geom_ok(c.N)) { *err = "sg_stream_create: n_fft must be a power of two from 256 to 4096"; return SG_E_UNSUPPORTED; }
   if (!ns && !c.stationary) {
     *err = "sg_stream_create: a non-stationary handle streams through sg_stream_create_nonstationary";
@@ -396,6 +504,11 @@ int st_create(StBank** out, const RgCtx& c, int32_t n_slots, int32_t channels, i
   b->max_block = max_block;
   b->ns = ns ? 1 : 0;
   b->L = ns ? lookahead : 0;
+  if (ad) {
+    b->ad = 1;
+    b->lam = ad->forget;
+    b->learn = ad->learn_frames < 0 ? -1 : ad->learn_frames;
+  }
   // (a flush decides the L frames a push holds back on top of the block's own: the mask rows are L deeper for it)
   const int64_t RC = c.W + ((int64_t)c.nt + b->L + 1) * c.H, RB = 2 * (int64_t)c.nt + 1 + b->L + max_frames(c, max_block);
   const int64_t RF = (int64_t)b->L + 1 + max_frames(c, max_block);
@@ -412,8 +525,8 @@ int st_create(StBank** out, const RgCtx& c, int32_t n_slots, int32_t channels, i
   b->RF = (int)RF;
   b->wpr = (c.F + 63) / 64;
   b->slots.assign(n_slots, StSlot());
-  if (ns)
-    for (auto& sl : b->slots) sl.has_thr = true;   // a non-stationary stream needs no noise profile
+  if (ns || ad)
+    for (auto& sl : b->slots) sl.has_thr = true;   // a non-stationary or adaptive stream needs no noise profile
   const size_t nu = (size_t)n_slots * channels;
   bool ok = true;
   auto take = [&](void** p, size_t bytes, bool zero) {
@@ -430,9 +543,13 @@ int st_create(StBank** out, const RgCtx& c, int32_t n_slots, int32_t channels, i
   } else {
     take((void**)&b->rmax, nu * c.FS * 8, true);
     take((void**)&b->bits, nu * (size_t)b->RB * b->wpr * 8, false);
-    take((void**)&b->thr, (size_t)n_slots * c.FS * 8, true);
-    take((void**)&b->T2, (size_t)n_slots * c.FS * 8, true);
-    take((void**)&b->stage, (size_t)c.FS * 8, true);
+    if (ad) {
+      take((void**)&b->nst, nu * 3 * c.FS * 8, true);
+    } else {
+      take((void**)&b->thr, (size_t)n_slots * c.FS * 8, true);
+      take((void**)&b->T2, (size_t)n_slots * c.FS * 8, true);
+      take((void**)&b->stage, (size_t)c.FS * 8, true);
+    }
   }
   take((void**)&b->slot_list, (size_t)n_slots * 4, true);
   // tables and scratch of a typical step up front (a larger step grows them, which synchronises once)
@@ -445,7 +562,7 @@ int st_create(StBank** out, const RgCtx& c, int32_t n_slots, int32_t channels, i
   if (!ok) {
     char m[200];
     snprintf(m, sizeof m, "sg_stream_create: device allocation failed (the bank's state is %lld bytes)",
-             (long long)st_state_bytes(c, ns, n_slots, channels, max_block, b->L));
+             (long long)st_state_bytes(c, ns, n_slots, channels, max_block, b->L, ad != nullptr));
     st_destroy(b);
     *err = m;
     return SG_E_NOMEM;
@@ -459,6 +576,7 @@ int st_set_threshold(StBank* b, const int32_t* slots, int32_t n, const double* t
   int rc = check_slots(b, slots, n, "sg_stream_set_threshold", err);
   if (rc) return rc;
   if (b->ns) { *err = "sg_stream_set_threshold: a non-stationary bank takes no noise threshold"; return SG_E_INVALID; }
+  if (b->ad) { *err = "sg_stream_set_threshold: an adaptive bank learns its threshold from the stream"; return SG_E_INVALID; }
   if (n > b->n_slots) { *err = "sg_stream_set_threshold: more slots listed than the bank has"; return SG_E_INVALID; }
   if (n == 0) return SG_OK;
   const double* src = thresh_dev;
@@ -491,9 +609,37 @@ int st_reset(StBank* b, const int32_t* slots, int32_t n, hipStream_t st, std::st
       *err = "sg_stream_reset: hipMemsetAsync failed";
       return SG_E_HIP;
     }
+    if (b->ad &&
+        hipMemsetAsync(b->nst + (size_t)slots[i] * b->C * 3 * b->c.FS, 0, (size_t)b->C * 3 * b->c.FS * 8, st) != hipSuccess) {
+      *err = "sg_stream_reset: hipMemsetAsync failed";
+      return SG_E_HIP;
+    }
     const bool thr = b->slots[slots[i]].has_thr;
     b->slots[slots[i]] = StSlot();
     b->slots[slots[i]].has_thr = thr;
+  }
+  return SG_OK;
+}
+
+int st_noise_profile(StBank* b, int32_t slot, double* thresh_host, hipStream_t st, std::string* err) {
+  if (!b->ad) { *err = "sg_stream_noise_profile: the bank is not adaptive (its profile is the one it was given)"; return SG_E_INVALID; }
+  if (slot < 0 || slot >= b->n_slots) {
+    char m[120];
+    snprintf(m, sizeof m, "sg_stream_noise_profile: unknown slot %d (the bank has %d)", slot, b->n_slots);
+    *err = m;
+    return SG_E_INVALID;
+  }
+  const int FS = b->c.FS, F = b->c.F;
+  std::vector<double> host((size_t)b->C * 3 * FS);
+  if (hipMemcpyAsync(host.data(), b->nst + (size_t)slot * b->C * 3 * FS, host.size() * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess) {
+    *err = "sg_stream_noise_profile: copy of the statistics failed";
+    return SG_E_HIP;
+  }
+  // k_sa_decide's threshold after the unit's last decided frame; Wn = 0 (no frame yet): 0 / 0 = NaN
+  for (int ch = 0; ch < b->C; ++ch) {
+    const double* s = host.data() + (size_t)ch * 3 * FS;
+    for (int f = 0; f < F; ++f) thresh_host[(size_t)ch * F + f] = s[FS + f] + b->c.n_std * std::sqrt(s[2 * FS + f] / s[f]);
   }
   return SG_OK;
 }
@@ -646,6 +792,7 @@ int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_
   A.R = (float*)b->ws; A.seg = (float*)((char*)b->ws + Rb);
   A.RC = b->RC; A.RB = b->RB;
   A.fst = b->fst; A.fa = b->fa; A.mk = b->mk; A.RF = b->RF; A.L = b->L;
+  A.nst = b->nst; A.lam = b->lam; A.learn = b->learn;
   A.c = fill_consts(c);
   const bool ns = b->ns != 0;
   // ---- the step: the same four launches whatever was pushed
@@ -653,6 +800,7 @@ int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_
   {
     Prof pr(c, SG_STAGE_RG_DECIDE, st);
     e = dispatch_N(c.N, [&](auto n) {
+      if (b->ad) return launch_tile_kernel<n()>(k_sa_decide<n()>, A.n_dec, st, A);
       return ns ? launch_tile_kernel<n()>(k_sn_decide<n()>, A.n_dec, st, A) : launch_tile_kernel<n()>(k_st_decide<n()>, A.n_dec, st, A);
     });
   }

@@ -14,6 +14,8 @@
 //   fa     [unit][RF][2][FS]   A = |X| and fwd of the last transformed frames, float64 (RF = L + 1 + frames of max_block)
 //   mk     [unit][RB][FS]      raw sigmoid mask rows, float32 (RB = 2 nt + 1 + L + frames of max_block)
 // and its ring is RC = W + (nt + L + 1) H samples.
+// An adaptive bank (the stationary gate with the noise profile learnt from the stream itself) holds no thr / T2 but
+//   nst    [unit][3][FS]       Wn, mu, M2: weight sum, mean and weighted squared deviations of the floored dB values, float64
 // (unit = slot * channels + channel).  The counters n, t_dec, t_applied, E are host arithmetic, mirrored in the bank.
 //
 // The frame work of the kernels is tile_core.hpp's, shared with the clips and the rows.
@@ -34,11 +36,22 @@ struct StBank;
 // samples emitted after n received: max(0, (t_dec(n) - nt + 1) H - h), t_dec(n) = floor((n + h - W) / H)
 int64_t st_emitted(int W, int H, int nt, int64_t n);
 
-// ns: a non-stationary bank with `lookahead` frames (the handle must be non-stationary); else lookahead is ignored
+// an adaptive bank's estimate: forgetting factor per frame in (0, 1], frames that update it (>= 1; negative: all)
+struct StAdaptive {
+  double forget;
+  int64_t learn_frames;
+};
+
+// ns: a non-stationary bank with `lookahead` frames (the handle must be non-stationary); else lookahead is ignored.
+// ad: non-null for an adaptive bank (the handle must be stationary)
 int st_create(StBank** out, const RgCtx& c, int32_t n_slots, int32_t channels, int64_t max_block, bool ns, int32_t lookahead,
-              std::string* err);
+              const StAdaptive* ad, std::string* err);
 // bytes of device state st_create allocates for such a bank (host arithmetic)
-int64_t st_state_bytes(const RgCtx& c, bool ns, int64_t n_slots, int64_t channels, int64_t max_block, int64_t L);
+int64_t st_state_bytes(const RgCtx& c, bool ns, int64_t n_slots, int64_t channels, int64_t max_block, int64_t L,
+                       bool adaptive = false);
+// adaptive banks: the threshold (dB) after the last decided frame of every channel of `slot`, channels x F values, NaN
+// where no frame was decided yet.  Synchronises the stream.
+int st_noise_profile(StBank* b, int32_t slot, double* thresh_host, hipStream_t st, std::string* err);
 // samples a stream of this bank has emitted after n received: st_emitted with nt + lookahead
 int64_t st_bank_emitted(const StBank* b, int64_t n);
 void st_destroy(StBank* b);

@@ -1,5 +1,6 @@
 """``StreamBank`` / ``StreamGate`` -- the gate for live audio: streams gated block by block on the GPU, with the
-stationary gate (a fixed noise profile) or the non-stationary one (no profile, a bounded lookahead).
+stationary gate (a fixed noise profile, or one learnt from the stream itself) or the non-stationary one (no profile, a
+bounded lookahead).
 
 Everything else in the package needs the last sample of a recording before the first one comes out.  A ``StreamBank``
 holds many independent streams with a fixed noise profile; each step takes whatever block every stream received (0
@@ -33,6 +34,31 @@ causal smoother does and the output differs from the offline one by more than it
 Digital silence gives ``0 / 0`` = NaN as offline; a NaN / Inf sample keeps the band levels NaN until the slot is flushed or
 reset.
 
+``noise_from_stream=True`` is the stationary gate without a noise clip, as ``reduce_noise(y, sr, stationary=True)`` is
+offline: there a band's threshold is the mean plus ``n_std_thresh_stationary`` standard deviations of the band's floored dB
+values over the whole recording; here the two are a running estimate per (stream, channel) and band.  The recurrence is the
+definition.  For frames ``t = 0, 1, ...`` in order::
+
+    db = 20 log10(|X[f, t]| + eps);  rmax = max(rmax, db);  x = max(db, rmax - top_db)     (the causal floor; NaN-sticky)
+    if t < learn_frames (or learning is unlimited):
+        Wn = lam * Wn + 1;  d = x - mu;  mu = mu + d / Wn;  M2 = lam * M2 + d * (x - mu)
+    thr = mu + n_std_thresh_stationary * sqrt(M2 / Wn);  the cell passes when x > thr
+
+from ``Wn = mu = M2 = 0``.  ``noise_memory_s=None`` is ``lam = 1``: the cumulative mean and standard deviation (``ddof = 0``,
+as the reference's ``np.std``) of frames ``0 .. t``; otherwise ``lam = exp(-H / (sr * noise_memory_s))`` forgets
+exponentially.  ``noise_learn_s`` holds the profile after ``learn_frames = int(noise_learn_s * sr / H)`` frames (``None``:
+it keeps learning).  Frame ``t`` is part of its own threshold, as every frame of a recording is offline.  What follows from
+the definition: frame 0 has ``M2 = 0`` and ``thr = x``, so it is gated whole; a band whose dB value is exactly constant
+(leading digital silence) has ``d = 0`` exactly and stays exactly gated; a NaN / Inf sample gates every band until the slot
+is flushed or reset, forgetting or not; a memory of less than about three hops gates EVERYTHING -- frame ``t`` has the
+share ``1 / Wn`` of its own statistics, a cell can lie at most ``sqrt(Wn - 1)`` deviations above its own mean, and ``Wn``
+stays below ``1 / (1 - lam)``: with ``n_std_thresh_stationary = 1.5`` nothing passes for ``lam <= 0.69``
+(``noise_memory_s <= 2.7 H / sr``; in general ``lam <= 1 - 1 / (1 + n_std^2)``).  Every channel of a multichannel stream has its own statistics -- the reference
+takes one threshold from the channel mean; the two are the same thing for one channel.  With ``lam = 1``, unlimited learning
+and no band ranging over more than ``top_db``, ``noise_profile`` just before the flush is the reference's threshold of the
+whole signal.  Everything else -- frames, ``emitted``, ``latency_samples``, flush, launches per step, bitwise independence
+of the block split, the slot and the other streams -- is the fixed-profile bank's.
+
 Out of scope: ``TorchGate``, integer blocks, several GPUs, and ``n_fft`` other than a power of two from 256 to 4096
 (``ValueError``).
 """
@@ -65,8 +91,9 @@ def iir_coefficient(time_constant_s, sr, H):
     return (np.sqrt(1 + 4 * t_frames ** 2) - 1) / (2 * t_frames ** 2)
 
 
-def state_bytes(n_units, n_fft, W, H, nt, L, max_block, stationary):
-    """Device memory a bank holds between steps (sg_stream_state_bytes' arithmetic; DESIGN section 13's state table)."""
+def state_bytes(n_units, n_fft, W, H, nt, L, max_block, stationary, noise_from_stream=False):
+    """Device memory a bank holds between steps (sg_stream_state_bytes' arithmetic; DESIGN section 13's state table).
+    ``noise_from_stream``: the three float64 rows of noise statistics per unit of an adaptive bank."""
     F = n_fft // 2 + 1
     FS = (F + 15) // 16 * 16
     mf = (max_block + W // 2) // H + 3
@@ -76,6 +103,8 @@ def state_bytes(n_units, n_fft, W, H, nt, L, max_block, stationary):
         per += RB * ((F + 63) // 64) * 8
     else:
         per += (L + 1 + mf) * 2 * FS * 8 + RB * FS * 4
+    if noise_from_stream:
+        per += 3 * FS * 8
     return n_units * per
 
 
@@ -108,14 +137,32 @@ class StreamBank:
     ``push({slot: block})`` -> ``{slot: out}``: blocks are ``(n,)`` or ``(C, n)`` float32 / float64 numpy arrays or
     device tensors; device tensors in give device tensors out with no host synchronisation (output lengths are host
     arithmetic); numpy in gives numpy out.  ``flush(slots)`` -> ``{slot: tail}`` ends streams (fewer than ``win_length``
-    samples in all: ``ValueError``) and leaves the slots empty; ``reset(slots)`` drops their state."""
+    samples in all: ``ValueError``) and leaves the slots empty; ``reset(slots)`` drops their state.
+
+    ``noise_from_stream=True`` takes no profile: every (stream, channel) learns its own from the frames it has seen, a
+    running mean and standard deviation of the floored dB values per band (the recurrence in the module docstring),
+    cumulative or, ``noise_memory_s``, forgetting exponentially with that time constant, and held after ``noise_learn_s``
+    seconds if given (a ``noise_memory_s`` of less than about three hops gates everything: module docstring).  The
+    statistics are per channel (the reference thresholds on the channel mean; the same for
+    ``channels=1``).  ``noise_profile(slot)`` reads the current threshold; ``set_noise`` and ``thresholds`` raise."""
 
     def __init__(self, sr, n_streams, channels=1, y_noise=None, thresholds_db=None, prop_decrease=1.0,
                  n_std_thresh_stationary=1.5, freq_mask_smooth_hz=500, time_mask_smooth_ms=50, n_fft=1024,
                  win_length=None, hop_length=None, max_block=None, device="cuda", stationary=True, lookahead_ms=0.0,
                  time_constant_s=2.0, thresh_n_mult_nonstationary=2, sigmoid_slope_nonstationary=10,
-                 max_state_bytes=MAX_STATE_BYTES):
+                 max_state_bytes=MAX_STATE_BYTES, noise_from_stream=False, noise_memory_s=None, noise_learn_s=None):
         stationary = bool(stationary)
+        noise_from_stream = bool(noise_from_stream)
+        if noise_from_stream and (y_noise is not None or thresholds_db is not None):
+            raise ValueError("StreamBank: noise_from_stream learns the profile; give no y_noise / thresholds_db with it")
+        if noise_from_stream and not stationary:
+            raise ValueError("StreamBank: noise_from_stream belongs to the stationary gate (stationary=True)")
+        if not noise_from_stream and (noise_memory_s is not None or noise_learn_s is not None):
+            raise ValueError("StreamBank: noise_memory_s / noise_learn_s need noise_from_stream=True")
+        if noise_memory_s is not None and not (np.isfinite(noise_memory_s) and noise_memory_s > 0):
+            raise ValueError(f"StreamBank: noise_memory_s must be finite and positive (got {noise_memory_s!r})")
+        if noise_learn_s is not None and not (np.isfinite(noise_learn_s) and noise_learn_s > 0):
+            raise ValueError(f"StreamBank: noise_learn_s must be finite and positive (got {noise_learn_s!r})")
         if not stationary and (y_noise is not None or thresholds_db is not None):
             raise ValueError("StreamBank: the non-stationary gate takes no noise profile (y_noise / thresholds_db)")
         if stationary and lookahead_ms:
@@ -143,11 +190,22 @@ class StreamBank:
         if self.max_block < 1:
             raise ValueError("StreamBank: max_block must be at least 1")
         self.stationary = stationary
+        self.noise_from_stream = noise_from_stream
+        self.noise_forget, self.noise_learn_frames = 1.0, -1      # lam per frame; frames that learn (-1: all)
+        if noise_memory_s is not None:
+            self.noise_forget = float(np.exp(-H / (sr * float(noise_memory_s))))
+            if not self.noise_forget > 0.0:
+                raise ValueError(f"StreamBank: noise_memory_s={noise_memory_s!r} is too short against one hop "
+                                 f"({H / sr:g} s): the forgetting factor underflows")
+        if noise_learn_s is not None:
+            self.noise_learn_frames = int(noise_learn_s * sr / H)
+            if self.noise_learn_frames < 1:
+                raise ValueError(f"StreamBank: noise_learn_s={noise_learn_s!r} is shorter than one hop ({H / sr:g} s)")
         self.lookahead_frames = 0 if stationary else int(lookahead_ms / ((H / sr) * 1000))
         self._lag = self.nt + self.lookahead_frames      # frames between the last one inside the audio and the last applied
         self.latency_samples = W + (self._lag + 1) * H
         self.state_bytes = state_bytes(self.n_streams * self.channels, n_fft, W, H, self.nt, self.lookahead_frames,
-                                       self.max_block, stationary)
+                                       self.max_block, stationary, noise_from_stream)
         if not stationary and self.state_bytes > max_state_bytes:
             raise ValueError(f"StreamBank: {self.n_streams} x {self.channels} streams with lookahead_frames="
                              f"{self.lookahead_frames} and max_block={self.max_block} need {self.state_bytes} bytes of "
@@ -157,7 +215,7 @@ class StreamBank:
                              f"{MAX_LOOKAHEAD_FRAMES} (the backward pass of a frame is that many dependent steps per band)")
         self._n = [0] * self.n_streams        # samples received / emitted per slot (mirrors of the library's counters)
         self._e = [0] * self.n_streams
-        self._has_noise = [not stationary] * self.n_streams
+        self._has_noise = [not stationary or noise_from_stream] * self.n_streams
         self._kind = [(False, np.dtype(np.float32), True)] * self.n_streams   # (tensor I/O, dtype, flat) of the last block
         self._bank = self._gate = None
         self._pending = []                    # noise profiles set before the first device call
@@ -178,7 +236,10 @@ class StreamBank:
         if self._bank is None:
             self._gate = _ffi.Gate(self._device_arg, **self._gate_kw)
             self.device = self._gate.device
-            if self.stationary:
+            if self.noise_from_stream:
+                self._bank = self._gate.stream_create_adaptive(self.n_streams, self.channels, self.max_block,
+                                                               self.noise_forget, self.noise_learn_frames)
+            elif self.stationary:
                 self._bank = self._gate.stream_create(self.n_streams, self.channels, self.max_block)
             else:
                 self._bank = self._gate.stream_create_nonstationary(self.n_streams, self.channels, self.max_block,
@@ -225,12 +286,26 @@ class StreamBank:
         """The dB threshold the handle computed last (``set_noise(..., y_noise=)``), as a numpy array (synchronises)."""
         if not self.stationary:
             raise ValueError("StreamBank: the non-stationary gate has no thresholds")
+        if self.noise_from_stream:
+            raise ValueError("StreamBank: a noise_from_stream bank computes no threshold on the handle; "
+                             "noise_profile(slot) reads the one a stream has learnt")
         return self.gate.get_noise_threshold()
+
+    def noise_profile(self, slot):
+        """``noise_from_stream`` banks: the dB threshold of every band after the last frame decided on ``slot``, a
+        ``(channels, n_fft // 2 + 1)`` float64 numpy array; NaN before the first frame.  Synchronises."""
+        if not self.noise_from_stream:
+            raise ValueError("StreamBank: noise_profile belongs to noise_from_stream=True (thresholds() otherwise)")
+        s = self._slots(slot)[0]
+        self._ensure()
+        return self._gate.stream_noise_profile(self._bank, s, self.channels)
 
     # -- noise profile -----------------------------------------------------------------------------------------
     def set_noise(self, slots, y_noise=None, thresholds_db=None):
         if not self.stationary:
             raise ValueError("set_noise: the non-stationary gate takes no noise profile")
+        if self.noise_from_stream:
+            raise ValueError("set_noise: a noise_from_stream bank learns its profile from the stream")
         slots = self._slots(slots)
         if (y_noise is None) == (thresholds_db is None):
             raise ValueError("set_noise: give y_noise or thresholds_db")
@@ -365,7 +440,7 @@ class StreamBank:
 
 class StreamGate:
     """One stream: ``push(block) -> out``, ``flush() -> tail`` (a ``StreamBank`` of one slot; same arguments,
-    ``stationary=False`` included)."""
+    ``stationary=False`` and ``noise_from_stream=True`` included)."""
 
     def __init__(self, sr, y_noise=None, **kw):
         self.bank = StreamBank(sr, 1, y_noise=y_noise, **kw)
@@ -379,6 +454,9 @@ class StreamGate:
 
     def reset(self):
         self.bank.reset([0])
+
+    def noise_profile(self):
+        return self.bank.noise_profile(0)
 
     def close(self):
         self.bank.close()
