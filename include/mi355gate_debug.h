@@ -41,6 +41,14 @@ SG_API int sg_debug_clip_thresholds(sg_handle* h, double* host, int32_t n_noise,
 SG_API int sg_debug_clip_batches(const sg_handle* h, int64_t* value);
 /* Sub-batches the last sg_process_rows / sg_process_rows_backward call was split into. */
 SG_API int sg_debug_rows_batches(const sg_handle* h, int64_t* value);
+/* Which kernels the last sg_process_batch_backward / sg_process_rows_backward call on this handle launched (0: none yet).
+ * Host bookkeeping only: no kernel reads or writes it. */
+#define SG_BWD_ROW 1  /* k_row_backward: a row of at most 64 frames in one workgroup (n_fft = 1024) */
+#define SG_BWD_FAST 2 /* k_env_scale + the tiled k_apply_fast (n_fft = 1024) */
+#define SG_BWD_REG 3  /* k_env_scale + the register apply kernels (n_fft = 512 / 256 / 2048) */
+#define SG_BWD_OLA 4  /* k_env_scale + k_apply_istft + k_ola (every other geometry, or SG_OPT_FORCE_NOFAST) */
+#define SG_BWD_ROWS 5 /* rw_backward (sg_process_rows_backward) */
+SG_API int sg_debug_backward_route(const sg_handle* h, int64_t* value);
 
 /* ---- development options (sg_set_option / sg_get_option of mi355gate.h) ----------------- */
 #define SG_OPT_FORCE_UNFUSED 1 /* value != 0: use the materialised (v1) kernels everywhere */

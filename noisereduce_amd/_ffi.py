@@ -39,6 +39,7 @@ SG_OPT_TILE_ORDER = 15
 SG_OPT_EXACT_MATERIALISED = 16
 SG_OPT_FORCE_UNFUSED = 1
 SG_OPT_FORCE_NOFAST = 2
+SG_BWD_ROW, SG_BWD_FAST, SG_BWD_REG, SG_BWD_OLA, SG_BWD_ROWS = 1, 2, 3, 4, 5
 
 _TORCH_DTYPES = {torch.float32: SG_F32, torch.float64: SG_F64, torch.int16: SG_I16,
                  torch.int32: SG_I32}
@@ -108,6 +109,7 @@ _PROTOTYPES = {
     "sg_process_rows_backward": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p,
                                          c_void_p, c_int64, c_void_p]),
     "sg_debug_rows_batches": (c_int, [c_void_p, POINTER(c_int64)]),
+    "sg_debug_backward_route": (c_int, [c_void_p, POINTER(c_int64)]),
     "sg_stft": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
     "sg_clips_workspace_bytes": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, POINTER(c_int64)]),
     "sg_process_clips": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int32, c_void_p, c_int64,
@@ -494,6 +496,13 @@ class Gate:
     def rows_batches(self):
         v = c_int64()
         self._check(self.lib.sg_debug_rows_batches(self._h, byref(v)))
+        return int(v.value)
+
+    def backward_route(self):
+        """SG_BWD_* (include/mi355gate_debug.h) of the last backward call on this handle: 1 k_row_backward, 2 tiled
+        k_apply_fast, 3 register apply kernels, 4 k_apply_istft + k_ola, 5 rw_backward; 0 before any."""
+        v = c_int64()
+        self._check(self.lib.sg_debug_backward_route(self._h, byref(v)))
         return int(v.value)
 
     # -- ragged batches (sg_process_clips) ---------------------------------------------------------

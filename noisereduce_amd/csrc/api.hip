@@ -155,6 +155,7 @@ struct sg_handle {
   int rg_shape = 16;                 // SG_OPT_ROWGATE_SHAPE: waves per workgroup of the row gate (16 x 1 quad, or 8 x 2 quads)
   bool rg_tap = false;               // SG_OPT_ROWGATE_TAP: keep the row gate's float32 power tile (stage tap 4)
   bool dbg_rg = false;               // the last batch ran on the row gate
+  int dbg_bwd_route = 0;             // sg_debug_backward_route: SG_BWD_* of the last backward call (0: none yet)
   DevBuf rg_count;                   // k_row_gate: number of (row, band) pairs that took the exact path (one counter, never reset)
   bool dbg_xbits = false;            // the last batch's mask bits live in xbits (tile-blocked)
   int dbg_trows = 16, dbg_tstep = 16, dbg_twords = 0, dbg_txw = 9;   // ... in tiles of trows frames every tstep frames, twords granule halves, txw words per row
@@ -3272,6 +3273,7 @@ extern "C" int sg_process_batch_backward(sg_handle* h, const void* grad_out_dev,
   if (h->fast_ok && !h->force_nofast && h->rowgate_mode != 1 && g.F == 513 && g.T >= 1 && g.T <= fast::RG_FRAMES) {
     // rows of at most 64 frames: the whole backward of a row in one workgroup (rowbwd.hpp) -- no grad_out / envelope copy,
     // no tiles, no hand-offs
+    h->dbg_bwd_route = SG_BWD_ROW;
     ProfScope ps(h, SG_STAGE_APPLY_FAST, st);
     fast::RowBwdArgs A;
     View v{};
@@ -3321,10 +3323,13 @@ extern "C" int sg_process_batch_backward(sg_handle* h, const void* grad_out_dev,
     om.p0 = 0; om.p1 = L; om.g_step = 0; om.g0 = 0; om.g_lo = 0; om.g_hi = L;
     const float* mk = mask_dev + (size_t)u0 * g.T * g.FS;
     if (h->fast_ok && !h->force_nofast) {
+      h->dbg_bwd_route = SG_BWD_FAST;
       if ((rc = stage_apply_fast(h, v, gb, nb, om, mk, 0, st))) return rc;
     } else if (const RegGeom* r = reg_geom(h)) {
+      h->dbg_bwd_route = SG_BWD_REG;
       if ((rc = stage_apply_reg(h, r, v, gb, nb, om, mk, 0, st))) return rc;
     } else {
+      h->dbg_bwd_route = SG_BWD_OLA;
       if ((rc = stage_apply_ola(h, v, gb, nb, mk, om, 0, st))) return rc;
     }
   }
@@ -3690,6 +3695,7 @@ extern "C" int sg_process_rows_backward(sg_handle* h, const void* grad_out_dev, 
   if (!grad_out_dev || !grad_x_dev || !mask_dev || B < 1 || (dtype != SG_F32 && dtype != SG_F64) || gx_stride < L ||
       L < 2 * (int64_t)h->W)
     FAIL(h, SG_E_INVALID, "sg_process_rows_backward: bad argument");
+  h->dbg_bwd_route = SG_BWD_ROWS;
   return sg::rw_backward(&h->rw, rg_ctx(h), grad_out_dev, dtype, B, L, go_stride, lengths, mask_dev, grad_x_dev, gx_stride,
                          rw_budget(h), (hipStream_t)stream, &h->err);
 }
@@ -3697,6 +3703,12 @@ extern "C" int sg_process_rows_backward(sg_handle* h, const void* grad_out_dev, 
 extern "C" int sg_debug_rows_batches(const sg_handle* h, int64_t* value) {
   if (!h || !value) return SG_E_INVALID;
   *value = sg::rw_last_batches(h->rw);
+  return SG_OK;
+}
+
+extern "C" int sg_debug_backward_route(const sg_handle* h, int64_t* value) {
+  if (!h || !value) return SG_E_INVALID;
+  *value = h->dbg_bwd_route;
   return SG_OK;
 }
 

@@ -14,7 +14,10 @@ helpers here hold a kernel to the float64 oracle per stage and per hop block ins
 * ``local_error`` / ``budget`` / ``local_check``   per hop block: max |got - want| against FACTOR x the emulation's;
 * ``bit_diff``         decision bits against the oracle's ``raw``, leaving out cells within ``DELTA_DB`` of the threshold;
 * ``mask_bound``       what a float32 smoothed mask may differ from the oracle's by;
-* ``TILE_CELLS``       the matrix of the three table-driven paths (clips, rows, streams), at the end of the module.
+* ``TILE_CELLS``       the matrix of the three table-driven paths (clips, rows, streams);
+* ``adjoint_f64`` / ``emulate_adjoint_f32`` / ``adjoint_unit`` / ``B_CELLS``   TorchGate's backward: the float64 adjoint of
+                       the fixed-mask gate, the same in the kernels' arithmetic, and the matrix of the backward routes,
+                       at the end of the module.
 
 Where the numbers come from (none is taken from the code under test):
 
@@ -872,3 +875,245 @@ def causal_floor_case(n_fft):
     k0, k1 = u["keep"]
     u["want"] = u["y"][k0:k1]
     return dict(y=y, noise=noise, kw=kw, unit=u, offline=units[0])
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# TorchGate's backward (tests/test_backward_parity_host.py)
+# ----------------------------------------------------------------------------------------------------------------
+# y = D^-1 trim( OLA( Ws irfft( M rfft( Wa frames( pad(x) ) ) ) ) ) with the mask M fixed (O.stft_torch, O.istft_torch) is
+# linear in x.  irfft(M rfft(.)) with a real M is a circular convolution with a real even kernel, hence its own adjoint;
+# Wa = Ws = the window padded to n_fft.  So
+#   g_x = trim_L( frames^T( Wa irfft( M rfft( Ws frames( pad( g_y / env ) ) ) ) ) )
+# where frames^T is an UN-normalised overlap-add onto the padded input (L + 2 (n_fft // 2) samples) and trim_L drops
+# the centre padding: all L input samples get a gradient, the tail [Lq, L) the forward never writes included.
+def adjoint_geometry(cfg, L):
+    """``(p, T, Lq)``: centre padding, frames, output samples of a row of L input samples (torch.stft / torch.istft)."""
+    n_fft, H = cfg["n_fft"], cfg["H"]
+    p = n_fft // 2
+    T = 1 + (L + 2 * p - n_fft) // H
+    return p, T, n_fft + (T - 1) * H - 2 * p
+
+
+def adjoint_envelope(cfg, L):
+    """torch.istft's window envelope after the n_fft // 2 trim, (Lq,) float64."""
+    p, T, Lq = adjoint_geometry(cfg, L)
+    w2 = O._centered_window(cfg["n_fft"], cfg["W"], cfg["window"]) ** 2
+    env = np.zeros(cfg["n_fft"] + (T - 1) * cfg["H"])
+    for t in range(T):
+        env[t * cfg["H"]:t * cfg["H"] + cfg["n_fft"]] += w2
+    return env[p:p + Lq]
+
+
+def adjoint_frames_f64(gy, mask, cfg, L, env=None):
+    """The per-frame terms of the adjoint before the scatter, (T, n_fft) float64: Wa irfft(M rfft(Ws frames(g_y / env))).
+    ``env``: another envelope than ``adjoint_envelope`` (planted defects)."""
+    n_fft, H = cfg["n_fft"], cfg["H"]
+    p, T, Lq = adjoint_geometry(cfg, L)
+    gy = np.asarray(gy, dtype=np.float64)
+    mask = np.asarray(mask, dtype=np.float64)
+    assert gy.shape == (Lq,) and mask.shape == (n_fft // 2 + 1, T), (gy.shape, mask.shape, Lq, T)
+    wf = O._centered_window(n_fft, cfg["W"], cfg["window"])
+    buf = np.zeros(n_fft + (T - 1) * H)
+    buf[p:p + Lq] = gy / (adjoint_envelope(cfg, L) if env is None else env)
+    idx = np.arange(n_fft)[None, :] + H * np.arange(T)[:, None]
+    Z = np.fft.rfft(buf[idx] * wf[None, :], axis=-1) * mask.T
+    return np.fft.irfft(Z, n=n_fft, axis=-1) * wf[None, :]
+
+
+def adjoint_scatter(fr, cfg, L):
+    """frames^T and the trim: (T, n_fft) per-frame terms -> (L,) gradient."""
+    n_fft, H = cfg["n_fft"], cfg["H"]
+    p, T, _ = adjoint_geometry(cfg, L)
+    assert fr.shape == (T, n_fft)
+    ext = np.zeros(L + 2 * p, dtype=fr.dtype)
+    for t in range(T):
+        ext[t * H:t * H + n_fft] += fr[t]
+    return ext[p:p + L]
+
+
+def adjoint_f64(gy, mask, cfg, L):
+    """The gradient of ``O.istft_torch(O.stft_torch(x) * M)`` w.r.t. one row x of L samples, M fixed, in float64 numpy.
+    gy: (Lq,);  mask: (F, T) float64;  cfg: the dict ``torchgate_units`` builds (n_fft, W, H, window).  Returns (L,)."""
+    return adjoint_scatter(adjoint_frames_f64(gy, mask, cfg, L), cfg, L)
+
+
+def emulate_adjoint_f32(gy, mask, cfg, L, window=None):
+    """``adjoint_f64`` in the kernels' arithmetic: float32 envelope sums and g_y / env, float32 window, scipy.fft's
+    rfft / irfft on float32, float32 mask multiply, float32 overlap-add.  ``window``: another (n_fft,) float32 table
+    than the rounded ``cfg['window']`` (the false-positive control).  Returns (L,) float32."""
+    n_fft, H = cfg["n_fft"], cfg["H"]
+    p, T, Lq = adjoint_geometry(cfg, L)
+    wf = O._centered_window(n_fft, cfg["W"], cfg["window"]).astype(F32) if window is None else np.asarray(window, dtype=F32)
+    w2 = wf * wf
+    env = np.zeros(n_fft + (T - 1) * H, dtype=F32)
+    for t in range(T):
+        env[t * H:t * H + n_fft] += w2
+    buf = np.zeros(n_fft + (T - 1) * H, dtype=F32)
+    buf[p:p + Lq] = np.asarray(gy, dtype=F32) / env[p:p + Lq]
+    idx = np.arange(n_fft)[None, :] + H * np.arange(T)[:, None]
+    Z = scipy.fft.rfft(buf[idx] * wf[None, :], n=n_fft, axis=-1)
+    assert Z.dtype == np.complex64, "scipy.fft left float32"
+    fr = scipy.fft.irfft(Z * np.asarray(mask, dtype=np.float64).astype(F32).T, n=n_fft, axis=-1) * wf[None, :]
+    assert fr.dtype == F32
+    return adjoint_scatter(fr, cfg, L)
+
+
+def adjoint_unit(gy, mask, cfg, L):
+    """A unit for ``local_error`` / ``budget`` / ``local_check`` as they stand: ``want`` the float64 gradient over
+    ``keep = (0, L)``, ``emu`` the float32 emulation, ``bud`` its pooled per-hop-block error -- hand it on,
+    ``local_check(got, u, bud=u['bud'])``: ``emulate_f32`` is the forward's.  ``mask`` is what the reference is GIVEN --
+    on the GPU the float32 mask the engine saved for the forward."""
+    u = dict(gy=np.asarray(gy, dtype=np.float64), mask=np.asarray(mask, dtype=np.float64), cfg=cfg, L=L, keep=(0, L))
+    u["want"] = adjoint_f64(u["gy"], u["mask"], cfg, L)
+    u["emu"] = emulate_adjoint_f32(u["gy"], u["mask"], cfg, L)
+    u["bud"] = budget(u, emu=u["emu"])
+    return u
+
+
+# The backward matrix: one cell per route of sg_process_batch_backward / sg_process_rows_backward and per transform
+# family behind stage_apply_ola.  ``route``: the kernels the cell's shape and options reach (row = k_row_backward, fast = k_apply_fast, reg = the
+# register apply kernels, ola = stage_apply_ola, rows = rw_backward).  ``opts``: development options by
+# name (SG_OPT_<name>); ``env``: set while the handle is created.  L in hops (+ a remainder that is no multiple of H, so
+# the tail [Lq, L) exists); the rows cells hold five rows of their own lengths, NaN beyond them.  The four-step sizes
+# (n_fft = 16384) are left out: one cell of them costs more than the rest of the matrix, and their backward is the same
+# stage_apply_ola call as 4096's with another transform behind it, which the forward matrix (CELLS) holds.
+def _b(name, route, n_fft, hops, rem, **kw):
+    return dict(kw, name=name, route=route, n_fft=n_fft, hops=hops, rem=rem)
+
+
+B_CELLS = [
+    _b("row-T64", "row", 1024, 63, 13),
+    _b("row-T9", "row", 1024, 8, 0),
+    _b("fast-T65", "fast", 1024, 64, 13),
+    _b("fast-norowgate", "fast", 1024, 63, 13, opts=(("FORCE_NOROWGATE", 1),), like="row-T64"),     # the same input
+    _b("fast-ns", "fast", 1024, 70, 5, nonstationary=True, prop=0.7),
+    _b("reg-512", "reg", 512, 70, 13),
+    _b("reg-256", "reg", 256, 70, 13),
+    _b("reg-2048", "reg", 2048, 70, 13),
+    _b("reg-512-f64", "reg", 512, 70, 13, dtype="float64"),
+    _b("lds-128", "ola", 128, 40, 7),
+    _b("lds-4096", "ola", 4096, 40, 7),
+    _b("lds-512-w400-h101", "ola", 512, 40, 7, W=400, H=101),
+    _b("lds-1024-nofast", "ola", 1024, 64, 13, opts=(("FORCE_NOFAST", 1),)),
+    _b("mixed-400", "ola", 400, 40, 7),
+    _b("mixed-1000", "ola", 1000, 40, 7),
+    _b("czt-601", "ola", 601, 40, 7),
+    _b("czt-400", "ola", 400, 40, 7, env=(("SG_NO_MIXED_RADIX", "1"),)),
+    _b("rows-256", "rows", 256, 60, 13, lengths=True),
+    _b("rows-1024", "rows", 1024, 60, 13, lengths=True),
+    _b("rows-4096", "rows", 4096, 60, 13, lengths=True),
+    _b("rows-1024-ns", "rows", 1024, 60, 13, lengths=True, nonstationary=True),
+]
+B_ROWS_K = 37          # the rows cells' fourth and fifth row hold H k and H k + H - 1 samples
+
+
+def b_cell_id(c):
+    return c["name"]
+
+
+def grad_field(Lq, H, seed, impulses=True):
+    """The first grad_out of a row: tone + noise of amplitude ~1, the second half 60 dB down, impulses of amplitude 1
+    on both sides of the first hop seam, at the last hop and the last sample, and one in the middle of the quiet half
+    (``impulses=False``: without them -- tests/test_backward_parity_host.py)."""
+    rng = np.random.default_rng(seed)
+    g = 0.3 * rng.standard_normal(Lq) + 0.7 * np.sin(2 * np.pi * 1234.5 * np.arange(Lq) / T_SR)
+    g[Lq // 2:] *= 1e-3
+    for s in (0, 1, H - 1, H, Lq - H, Lq - 1, (3 * Lq) // 4) if impulses else ():
+        g[s] += 1.0
+    return g.astype(F32)
+
+
+def grad_impulses(Lq):
+    """The second grad_out: the two ends alone."""
+    g = np.zeros(Lq, dtype=F32)
+    g[0] = g[Lq - 1] = 1.0
+    return g
+
+
+B_LOUD = ((0.0, 0.08), (0.70, 0.78), (0.91, 1.0))
+
+
+def b_signal(kind, n, seed, only=None):
+    """A row of x: ``signals.two_level``'s content (kind 0: tone + noise) or ``signals.dc_nyquist``'s (kind 1) in two
+    levels 30 dB apart, loud over ``B_LOUD`` (shares of the row) only.  TorchGate's stationary gate takes its threshold
+    from the row itself, mean + 1.5 std of each band's dB over the frames: with a share f of the frames A dB above the
+    rest that is A (f + 1.5 sqrt(f (1 - f))) above the quiet level, which the loud frames only exceed for f < 0.31.
+    ``two_level`` as it stands (f = 0.5, its quiet half on the -40 dB floor) and ``dc_nyquist`` (one level) leave masks
+    that pass next to nothing anywhere, and a gradient that is next to zero with them.  Here f = 0.25: the mask passes
+    at the start of a row, inside the quiet half of the ``grad_field`` and at the row's end (so the tail [Lq, L) gets a
+    gradient), and gates between.  ``only``: one of the three loud stretches alone -- a row of a few frames (2 W samples:
+    9 frames, each 4 hops wide) is loud in every frame with all three."""
+    y = signals._base(n, T_SR, seed) if kind == 0 else signals.dc_nyquist(n, T_SR, seed).astype(np.float64)
+    env = np.full(n, _ROWS_QUIET)
+    for a, b in (B_LOUD if only is None else B_LOUD[only:only + 1]):
+        env[int(a * n):int(np.ceil(b * n))] = 1.0
+    return (y * env).astype(F32)
+
+
+@functools.lru_cache(maxsize=None)
+def _b_case(i):
+    c = B_CELLS[i]
+    i = [d["name"] for d in B_CELLS].index(c.get("like", c["name"]))      # (seeds)
+    n_fft = c["n_fft"]
+    W = c.get("W", n_fft)
+    H = c.get("H", W // 4)
+    L = c["hops"] * H + c["rem"]
+    kw = dict(n_fft=n_fft, nonstationary=bool(c.get("nonstationary", False)), prop_decrease=c.get("prop", 1.0))
+    if "W" in c:
+        kw.update(win_length=W, hop_length=H)
+    if n_fft not in (1024, 512):
+        kw.update(freq_mask_smooth_hz=3.02 * T_SR / (n_fft / 2), time_mask_smooth_ms=2.02 * H / T_SR * 1000)
+    if c.get("lengths"):
+        lens = [L, 2 * W, 2 * W + 1, H * B_ROWS_K, H * B_ROWS_K + H - 1]
+    else:
+        lens = [L] * 3
+    x = np.full((len(lens), L), np.nan, dtype=F32)
+    for b, n in enumerate(lens):
+        x[b, :n] = b_signal(b % 2, n, 70 * i + b, only=b % 3 if n // H < 16 else None)
+    cfg = dict(n_fft=n_fft, W=W, H=H, window=tile_window(W))
+    gy1, gy2 = [], []
+    for b, n in enumerate(lens):
+        Lq = adjoint_geometry(cfg, n)[2]
+        gy1.append(grad_field(Lq, H, 7000 + 70 * i + b))
+        gy2.append(grad_impulses(Lq))
+    return dict(cell=c, x=x, lens=lens, lengths=np.array(lens, dtype=np.int64) if c.get("lengths") else None, kw=kw,
+                W=W, H=H, L=L, cfg=cfg, gy=(gy1, gy2), dtype=c.get("dtype", "float32"))
+
+
+def b_case(i):
+    """Inputs of a backward cell: ``x`` (B, L) float32-valued (NaN beyond a row's own samples), ``lens`` per row,
+    ``lengths`` (rows cells; else None), ``kw`` for TorchGate / ``torchgate_units``, ``cfg`` for ``adjoint_f64``,
+    ``gy = (first, second)``: per row a (Lq_row,) float32 grad_out (``grad_field``, ``grad_impulses``)."""
+    return _b_case(i)
+
+
+@functools.lru_cache(maxsize=4)
+def _b_oracle(i):
+    case = _b_case(i)
+    return [torchgate_units(case["x"][b:b + 1, :n].astype(np.float64), T_SR, window=case["cfg"]["window"], **case["kw"])[1][0]
+            for b, n in enumerate(case["lens"])]
+
+
+def b_oracle(i):
+    """The forward oracle's unit of every row of a backward cell (the row gated alone)."""
+    return _b_oracle(i)
+
+
+def adjoint_check_rows(tag, gx, gy, mask, cfg, lens):
+    """A gradient (B, L) against ``adjoint_f64`` row by row: row b holds ``lens[b]`` samples, its grad_out is
+    ``gy[b][:Lq_b]``, its mask ``mask[b, :T_b, :F]`` ((B, T, FS) as the engine saves it, natural bin order).  No hop
+    block of ``[0, lens[b])`` may be over its float32 bound (``local_check``); returns the largest local_error / budget."""
+    gx, mask = np.asarray(gx), np.asarray(mask)
+    F = cfg["n_fft"] // 2 + 1
+    worst = 0.0
+    for b, n in enumerate(lens):
+        p, T, Lq = adjoint_geometry(cfg, n)
+        u = adjoint_unit(np.asarray(gy[b])[:Lq], mask[b, :T, :F].T, cfg, n)
+        bad, ratio = local_check(gx[b, :n], u, bud=u["bud"])
+        worst = max(worst, ratio)
+        if len(bad):
+            err = local_error(gx[b, :n], u["want"], cfg["H"])
+            raise AssertionError("%s row %d: hop blocks %s of %d over their bound: error %s, budget %s, largest error / budget "
+                                 "in the row %.2f" % (tag, b, bad[:10].tolist(), len(err), err[bad[:10]], u["bud"][bad[:10]],
+                                                      ratio))
+    return worst

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from oracle import spectralgate_oracle as O
+from tests import parity_budget as PB
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -129,5 +130,12 @@ def test_torchgate(kw):
     y = tg(xg)
     want = O.torchgate_T(x.numpy().astype(np.float64), sr, **kw)
     assert O.rel_err(y.detach().cpu().numpy(), want) < TOL
+    mask = y.grad_fn.saved_tensors[0].detach().cpu().numpy()      # (B, T, FS) float32, natural bin order
     y.sum().backward()
     assert torch.isfinite(xg.grad).all() and xg.grad.shape == x.shape
+    # the gradient against the float64 adjoint with the mask of this forward, per hop block (tests/parity_budget.py)
+    W = kw.get("win_length", kw["n_fft"])
+    cfg = dict(n_fft=kw["n_fft"], W=W, H=kw.get("hop_length", W // 4), window=PB.tile_window(W))
+    gy = np.ones((B, y.shape[1]), dtype=np.float32)
+    ratio = PB.adjoint_check_rows("torchgate %r" % (kw,), xg.grad.cpu().numpy(), gy, mask, cfg, [L] * B)
+    print("torchgate %r backward: largest local_error / budget %.3f" % (kw, ratio))
