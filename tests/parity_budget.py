@@ -275,11 +275,12 @@ def _sigmoid_f32(r, shift, mult):
         return (F32(1.0) / (F32(1.0) + np.exp(-(r + F32(shift)) * F32(mult)))).astype(F32)
 
 
-def emulate_stages_f32(unit):
-    """``(y32, raw32, mask32)`` of a unit evaluated in float32 (see ``emulate_f32``)."""
+def _spectrum_f32(unit):
+    """The unit's transform in float32: ``(Z (F, T) complex64, wf, wsum, p, n_frame, T)``."""
     c = unit["cfg"]
     n_fft, W, H = c["n_fft"], c["W"], c["H"]
     x = np.asarray(unit["x"], dtype=F32)
+    wsum = None
     if c["variant"] == "S":
         w = O.hann_periodic(W).astype(F32)
         wsum = F32(np.sum(w.astype(np.float64)))
@@ -296,7 +297,19 @@ def emulate_stages_f32(unit):
     assert Z.dtype == np.complex64, "scipy.fft left float32"
     if c["variant"] == "S":
         Z = Z * (F32(1.0) / wsum)
-    Z = Z.T                                                   # (F, T) complex64
+    return Z.T, wf, wsum, p, n_frame, T                       # (F, T) complex64
+
+
+def spectrum_f32(unit):
+    """(F, T) complex64: the unit's float32 transform (float32 frames, window, pocketfft) alone."""
+    return _spectrum_f32(unit)[0]
+
+
+def emulate_stages_f32(unit):
+    """``(y32, raw32, mask32)`` of a unit evaluated in float32 (see ``emulate_f32``)."""
+    c = unit["cfg"]
+    n_fft, W, H = c["n_fft"], c["W"], c["H"]
+    Z, wf, wsum, p, n_frame, T = _spectrum_f32(unit)
     # ---- mask ----
     raw32 = None
     if c["stationary"]:
@@ -1117,3 +1130,357 @@ def adjoint_check_rows(tag, gx, gy, mask, cfg, lens):
                                  "in the row %.2f" % (tag, b, bad[:10].tolist(), len(err), err[bad[:10]], u["bud"][bad[:10]],
                                                       ratio))
     return worst
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# near-threshold cells: the exact re-evaluation of ambiguous decisions (tests/test_ambiguous_cells_host.py: conditions on
+# the oracle and planted defects; tests/test_gpu_ambiguous_cells.py: the kernels)
+# ----------------------------------------------------------------------------------------------------------------
+# Every bulk decision kernel runs a float32 transform, flags a cell AMBIGUOUS when ||X| - T| <= delta with
+# delta = 2^-16 ||x w||_2 (|X|, T in the unscaled transform's units), and has the whole wave re-evaluate each flagged cell
+# as one float64 DFT sum of that bin.  On random input about one cell in 1e5 is flagged, at bands and frames nobody
+# chose.  The inputs here are BUILT so that chosen cells sit inside delta / 2 of their thresholds, on both sides:
+#
+# * the threshold comes from a separate noise clip, so it stays put while the recording is moved (the row gate's cell:
+#   from the row itself, re-derived in every iteration);
+# * every band of every unit (channel, chunk) holds a target, every frame of a unit holds one -- frame 0 and the last
+#   frame, which read zero padding or the neighbouring chunk's samples, included -- except the three frames on each
+#   side of the unit's CROWDED frame; so every frame position modulo a decision kernel's frames per workgroup is hit
+#   whatever that count is, as long as a unit holds three workgroups of the largest one a route of the cell launches
+#   (tests/test_ambiguous_cells_host.py reads the counts from the kernels' headers and launches).  Where a size has more
+#   frames than bands (n_fft = 64, 256) a frame whose neighbours leave no band free stays empty;
+# * the crowded frame holds a target on every 4th band (every 8th where 4 n_fft / W > 4), bands 0, n_fft / 4 and
+#   n_fft / 2 among them: one wave retires many cells, several per lane, the Nyquist flag with the rest;
+# * two targets whose frames share a sample (within a unit or across a chunk seam) lie >= 4 n_fft / W bins apart, the
+#   width of the Hann main lobe, so moving one barely moves the other;
+# * goals: | |X| / T - 1 | log-uniform in [5e-8, 2e-6], random sign.  T ~ 2 ||x w|| on noise, so 2e-6 is ~0.25 delta;
+#   the lower end is ~5 x the float32 rounding of the samples (2^-25 ||x w|| x 0.6 in |X|, ~1e-8 T) and 50 x 1e-7 dB.
+#
+# The solve is a Jacobi iteration in float64: every target's complex deficit X (want / |X| - 1) is cancelled by adding the
+# windowed cosine and sine of its bin over the samples the frame really reads (a 2 x 2 real system per target: at a
+# unit's edge the frame is cut short); all targets at once, until every | |X| / T - 1 - goal | <= 1e-12.  Then the samples
+# are rounded to the cell's dtype, and what counts is the oracle's view of the ROUNDED samples.
+#
+# Chirp-z, four-step and the tile core (clips, rows, streams) decide in float64 and have no ambiguity path: no cell.
+# Two cells run float64 decisions all the same and hold them to the same bits: n_fft = 8192 (no float32 decision kernel
+# at that size) and TorchGate with xn= (four-kernel path).  k_row_gate, which re-evaluates whole bands, only runs on rows
+# that take their threshold from themselves: its cell (rowgate-1024-own) re-derives the threshold from the row in every
+# iteration.  That fixed point contracts only while a band holds few targets (each drags the six overlapping frames of
+# its band along), so there bands 0, n_fft / 4 and n_fft / 2 are targeted in the crowded frame alone.
+A_SEP = 4              # targets in sample-overlapping frames: >= A_SEP n_fft / W bins apart
+A_GOAL = (5e-8, 2e-6)
+A_TOL = 1e-12
+_A_REG = ("default", "force_split", "force_nofast")
+
+
+def _a(name, family, n_fft, frames, routes=("default",), **kw):
+    return dict(kw, name=name, family=family, n_fft=n_fft, frames=frames, routes=routes)
+
+
+# frames: hops per chunk (a unit holds 3 more frames); >= 3 workgroups of the size's decision kernels
+A_CELLS = [
+    _a("register-1024", "register", 1024, 48, _A_REG),
+    _a("register-512", "register", 512, 96, _A_REG),
+    _a("register-256", "register", 256, 192, _A_REG),
+    _a("register-2048", "register", 2048, 48, _A_REG),
+    _a("lds-64", "lds_pow2", 64, 192),
+    _a("lds-4096", "lds_pow2", 4096, 32),
+    _a("lds-8192", "lds_pow2", 8192, 32),
+    _a("lds-1024-w600-h151", "lds_pow2", 1024, 48, W=600, H=151),
+    _a("mixed-400", "mixed_radix", 400, 48),
+    _a("mixed-4000", "mixed_radix", 4000, 32),
+    _a("register-1024-f64", "register", 1024, 48, dtype="float64"),
+    _a("register-1024-i16", "register", 1024, 48, dtype="int16"),
+    _a("torchgate-1024-xn", "torchgate", 1024, 62, xn=True),
+    _a("rowgate-1024-own", "torchgate", 1024, 62),
+]
+_A_RESEED = {}         # name -> seed offset (tests/test_ambiguous_cells_host.py holds the conditions a seed must meet)
+
+
+def a_cell_id(c):
+    return c["name"]
+
+
+def a_cell(name):
+    return next(c for c in A_CELLS if c["name"] == name)
+
+
+def _a_window(cell, W):
+    """The float64 analysis window over the frame a transform reads, and that frame's length."""
+    if cell["family"] == "torchgate":
+        return O._centered_window(cell["n_fft"], W, tile_window(W)), cell["n_fft"]
+    return O.hann_periodic(W), W
+
+
+def _a_frames(row, g0, v0, v1, T, n_frame, H):
+    """(T, n_frame): frame t holds row[g0 + t H + m] where v0 <= index < v1, zeros elsewhere."""
+    buf = np.zeros(n_frame + (T - 1) * H)
+    a, b = max(v0, g0), min(v1, g0 + len(buf))
+    buf[a - g0:b - g0] = row[a:b]
+    return buf[np.arange(n_frame)[None, :] + H * np.arange(T)[:, None]]
+
+
+def _a_stride(A, ov, sep):
+    """A stride s so that bands less than sep apart land >= ov places apart in a list of A frames."""
+    for s in range(ov + 1, A):
+        if all(min((s * d) % A, A - (s * d) % A) >= ov for d in range(1, sep)):
+            return s
+    raise ValueError("no stride for %d frames" % A)
+
+
+def _a_place(geo, F, n_fft, n_frame, H, sep, rng, extras=True):
+    """Targets of every unit: ``[(bands, frames)]`` and the crowded frame of each unit."""
+    ov = -(-n_frame // H)
+    step = 4 * -(-sep // 4)
+    placed = {}            # channel -> (first sample of the frame, band) of every target so far
+    lists = [([], []) for _ in geo]
+    crowded = [g["T"] // 2 for g in geo]
+
+    def free(g, f, t):
+        at = placed.setdefault(g["ch"], [[], []])
+        s = np.asarray(at[0]) - (g["g0"] + t * H)
+        near = (np.abs(s) < n_frame) & (np.abs(np.asarray(at[1]) - f) < sep)
+        return not near.any()
+
+    def put(ui, f, t):
+        g = geo[ui]
+        at = placed.setdefault(g["ch"], [[], []])
+        lists[ui][0].append(f)
+        lists[ui][1].append(t)
+        at[0].append(g["g0"] + t * H)
+        at[1].append(f)
+
+    def fill(ui, t):
+        f0 = int(rng.integers(1, F - 1))
+        for f in ((f0 + k) % F for k in range(F)):
+            if f % step and free(geo[ui], f, t):
+                put(ui, f, t)
+                return True
+        return False
+
+    # first, in every unit: the crowded frame; frame 0 and the last frame (they read padding or the neighbour chunk,
+    # and across a seam they share samples with the neighbour's frames); bands 0, n_fft / 4 and n_fft / 2 once more in
+    # every twelfth frame, so that the bins every kernel treats apart get enough targets for a share of them to mean
+    # something
+    for ui, g in enumerate(geo):
+        for f in range(0, F, step):
+            put(ui, f, crowded[ui])
+    for ui, g in enumerate(geo):
+        for t in (0, g["T"] - 1):
+            if not fill(ui, t):
+                raise ValueError("no band left for frame %d of unit %d" % (t, ui))
+    for ui, g in enumerate(geo):
+        T, tc = g["T"], crowded[ui]
+        allowed = [t for t in range(T) if abs(t - tc) >= ov]
+        for t in allowed[2::12] if extras else ():
+            for f in (0, n_fft // 4, n_fft // 2):
+                if free(g, f, t):
+                    put(ui, f, t)
+        s = _a_stride(len(allowed), ov, sep)
+        n = 0
+        for f in range(F):
+            if f % step == 0:
+                continue
+            i0 = (s * n) % len(allowed)      # (a count, not f: f skips the crowded bands, and s f would skip frames)
+            n += 1
+            for k in range(len(allowed)):
+                t = allowed[(i0 + k) % len(allowed)]
+                if free(g, f, t):
+                    put(ui, f, t)
+                    break
+            else:
+                raise ValueError("no frame left for band %d" % f)
+        # frames the bands left out (more frames than bands); a frame whose neighbours leave no band free stays empty
+        # (tests/test_ambiguous_cells_host.py holds what must be hit)
+        hit = set(lists[ui][1])
+        for t in allowed:
+            if t not in hit and fill(ui, t):
+                hit.add(t)
+    return [(np.array(tf), np.array(tt)) for tf, tt in lists], crowded
+
+
+def _a_solve(y2, geo, targets, goals, wf, n_fft, n_frame, H, tlin, max_iter=400, relax=1.0):
+    """The Jacobi iteration.  y2: (rows, N) float64, changed in place; ``tlin(Xs)``: per unit the (F,) threshold in the
+    unscaled transform's units (given every unit's spectrum: the row gate's own-statistics cell re-derives it).
+    Returns (iterations, largest | |X| / T - 1 - goal |)."""
+    w2 = wf * wf
+    pre = []
+    for g, (tf, tt) in zip(geo, targets):
+        valid = _a_frames(np.ones(y2.shape[1]), g["g0"], g["v0"], g["v1"], g["T"], n_frame, H)
+        Q = np.fft.fft(valid * w2[None, :], n=n_fft, axis=-1)
+        q = Q[tt, (2 * tf) % n_fft]
+        E = Q[tt, 0].real
+        pre.append(dict(valid=valid, Scc=0.5 * (E + q.real), Sss=0.5 * (E - q.real), Scs=-0.5 * q.imag,
+                        edge=(tf == 0) | (2 * tf == n_fft)))
+    err = np.inf
+    for it in range(max_iter):
+        Xs = [np.fft.rfft(_a_frames(y2[g["ch"]], g["g0"], g["v0"], g["v1"], g["T"], n_frame, H) * wf[None, :], n=n_fft, axis=-1)
+              for g in geo]                                                          # (T, F) each
+        tl = tlin(Xs)
+        err, ups = 0.0, []
+        for g, (tf, tt), goal, p, X, t_lin in zip(geo, targets, goals, pre, Xs, tl):
+            x = X[tt, tf]
+            want = t_lin[tf] * (1.0 + goal)
+            err = max(err, float(np.max(np.abs(np.abs(x) / t_lin[tf] - 1.0 - goal))))
+            d = relax * x * (want / np.abs(x) - 1.0)
+            det = p["Scs"] ** 2 - p["Scc"] * p["Sss"]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                a = np.where(p["edge"], d.real / p["Scc"], (-p["Sss"] * d.real - p["Scs"] * d.imag) / det)
+                b = np.where(p["edge"], 0.0, (p["Scs"] * d.real + p["Scc"] * d.imag) / det)
+            spec = np.zeros(X.shape, dtype=np.complex128)
+            spec[tt, tf] = np.where(p["edge"], n_fft * a, 0.5 * n_fft * (a - 1j * b))
+            ups.append(np.fft.irfft(spec, n=n_fft, axis=-1)[:, :n_frame] * wf[None, :] * p["valid"])
+        if err <= A_TOL:
+            return it, err
+        for g, up in zip(geo, ups):
+            row = y2[g["ch"]]
+            for t in range(g["T"]):
+                a0 = g["g0"] + t * H
+                lo, hi = max(a0, 0), min(a0 + n_frame, len(row))
+                row[lo:hi] += up[t, lo - a0:hi - a0]
+    return max_iter, err
+
+
+def unit_delta(unit):
+    """(T,) float64: delta = 2^-16 ||x w||_2 of every frame, from the stored samples and the float64 window, in the
+    unscaled transform's units."""
+    c = unit["cfg"]
+    if c["variant"] == "S":
+        wf, n_frame = O.hann_periodic(c["W"]), c["W"]
+    else:
+        wf, n_frame = O._centered_window(c["n_fft"], c["W"], c["window"]), c["n_fft"]
+    T = unit["raw"].shape[1]
+    x = np.asarray(unit["x"], dtype=np.float64)
+    fr = _a_frames(x, -(n_frame // 2), 0, len(x), T, n_frame, c["H"]) * wf[None, :]
+    return 2.0 ** -16 * np.sqrt(np.sum(fr * fr, axis=1))
+
+
+def unit_margin(unit):
+    """(F, T) float64: (|X| - T) / delta of every cell (positive: the cell passes)."""
+    c = unit["cfg"]
+    s = float(np.sum(O.hann_periodic(c["W"]))) if c["variant"] == "S" else 1.0
+    t_lin = (10.0 ** (unit["thresh"] / 20.0) - O.EPS64) * s
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return (np.abs(unit["Z"]) * s - t_lin[:, None]) / unit_delta(unit)[None, :]
+
+
+@functools.lru_cache(maxsize=None)
+def _near_threshold_case(name):
+    c = a_cell(name)
+    n_fft = c["n_fft"]
+    W = c.get("W", n_fft)
+    H = c.get("H", W // 4)
+    F = n_fft // 2 + 1
+    dtype = c.get("dtype", "float32")
+    rows = c["family"] == "torchgate"
+    seed = 4100 + 37 * [d["name"] for d in A_CELLS].index(name) + _A_RESEED.get(name, 0)
+    rng = np.random.default_rng(seed)
+    wf, n_frame = _a_window(c, W)
+    sep = -(-A_SEP * n_fft // W)
+    level = 8000.0 if dtype == "int16" else 0.1
+    if rows:
+        sr, Cn, N = T_SR, 3, c["frames"] * H + 128
+        kw = dict(n_fft=n_fft)
+        geo = [dict(ch=b, chunk=0, g0=-(n_fft // 2), v0=0, v1=N, T=1 + N // H) for b in range(Cn)]
+        noise = (level * rng.standard_normal((1, 30 * H))).astype(F32) if c.get("xn") else None
+    else:
+        sr, Cn = SR, 2
+        cs, pad = c["frames"] * H + 5, H + 3
+        N = 2 * cs - 7
+        kw = dict(stationary=True, n_fft=n_fft, chunk_size=cs, padding=pad, prop_decrease=1.0)
+        if "W" in c:
+            kw.update(win_length=W, hop_length=H)
+        if n_fft not in (1024, 512, 256, 2048) or "W" in c:
+            kw.update(freq_mask_smooth_hz=3.02 * SR / (n_fft / 2), time_mask_smooth_ms=2.02 * H / SR * 1000)
+        geo = [dict(ch=ci, chunk=k, g0=k * cs - pad - W // 2, v0=max(0, k * cs - pad), v1=min(N, (k + 1) * cs + pad),
+                    T=(cs + 2 * pad + 2 * (W // 2) - W) // H + 1) for ci in range(Cn) for k in range(2)]
+        noise = level * rng.standard_normal(max(24 * H, 2 * W))
+        noise = np.clip(np.rint(noise), -32768, 32767).astype(np.int16) if dtype == "int16" else noise.astype(F32)
+    y2 = level * rng.standard_normal((Cn, N))
+    # (own statistics: a band's threshold moves with every cell of the band, and each target drags the six frames that
+    # overlap it along; six more targets in one band make that map expanding, so bands 0, n_fft / 4 and n_fft / 2 keep to
+    # the crowded frame there)
+    targets, crowded = _a_place(geo, F, n_fft, n_frame, H, sep, rng, extras=not (rows and noise is None))
+    goals = [rng.choice([-1.0, 1.0], len(tf)) * np.exp(rng.uniform(np.log(A_GOAL[0]), np.log(A_GOAL[1]), len(tf)))
+             for tf, _ in targets]
+    def cap_goals(t_lins):
+        # a frame cut short at a unit's edge holds little of the window: delta shrinks with ||x w||, T does not, so the
+        # goal there is capped at 0.4 delta (delta of the recording as drawn; the solve only adds to it)
+        for g, (tf, tt), goal, t_lin in zip(geo, targets, goals, t_lins):
+            fr = _a_frames(y2[g["ch"]], g["g0"], g["v0"], g["v1"], g["T"], n_frame, H) * wf[None, :]
+            cap = 0.4 * 2.0 ** -16 * np.sqrt(np.sum(fr * fr, axis=1))[tt] / t_lin[tf]
+            goal[:] = np.sign(goal) * np.minimum(np.abs(goal), np.maximum(cap, A_GOAL[0]))
+
+    if rows and noise is None:
+        def tlin(Xs):                           # the row's own mean + 1.5 std (ddof = 1) of its floored dB field
+            out = []
+            for X in Xs:
+                db = O.amp_to_db(X.T, 40.0)
+                out.append(10.0 ** ((np.mean(db, axis=-1) + 1.5 * np.std(db, axis=-1, ddof=1)) / 20.0) - O.EPS64)
+            return out
+    elif rows:
+        db = O.amp_to_db(O.stft_torch(noise.astype(np.float64), n_fft, W, H, tile_window(W))[0], 40.0)
+        fixed = 10.0 ** ((np.mean(db, axis=-1) + 1.5 * np.std(db, axis=-1, ddof=1)) / 20.0) - O.EPS64
+        tlin = lambda Xs: [fixed] * len(Xs)     # noqa: E731
+    else:
+        th, _, _ = O.noise_threshold_S(noise.astype(np.float64)[None, :], n_fft, W, H, 1.5, kw["chunk_size"], True)
+        fixed = (10.0 ** (th / 20.0) - O.EPS64) * float(np.sum(wf))
+        tlin = lambda Xs: [fixed] * len(Xs)     # noqa: E731
+    cap_goals(tlin([np.fft.rfft(_a_frames(y2[g["ch"]], g["g0"], g["v0"], g["v1"], g["T"], n_frame, H) * wf[None, :], n=n_fft,
+                                axis=-1) for g in geo]))
+
+    def stored(v):
+        return np.clip(np.rint(v), -32768, 32767).astype(np.int16) if dtype == "int16" else v.astype(dtype)
+
+    # (the own-statistics threshold moves with the row: quarter steps keep the fixed point from overshooting)
+    relax = 0.25 if rows and noise is None else 1.0
+    its, err = _a_solve(y2, geo, targets, goals, wf, n_fft, n_frame, H, tlin, relax=relax, max_iter=int(400 / relax))
+    # rounding the samples moves |X| by ~1e-8 T (int16: by several delta), and now and then a target lands within
+    # bit_diff's reach of its threshold: such a target's goal is moved outwards by half and the solve taken up again
+    for _ in range(12):
+        y = stored(y2)
+        y64 = y.astype(np.float64)
+        Xs = [np.fft.rfft(_a_frames(y64[g["ch"]], g["g0"], g["v0"], g["v1"], g["T"], n_frame, H) * wf[None, :], n=n_fft,
+                          axis=-1) for g in geo]
+        again = False
+        for (tf, tt), goal, X, t_lin in zip(targets, goals, Xs, tlin(Xs)):
+            close = np.abs(20.0 * np.log10(np.abs(X[tt, tf]) / t_lin[tf])) < 4e-7
+            if dtype == "int16":
+                close &= np.abs(goal) < 1.0      # (once: the cell then leaves delta / 2 and is no target)
+                goal[close] = np.where(goal[close] > 0, 2.0, -0.5)
+            else:
+                goal[close] *= 1.5
+            again |= bool(close.any())
+        if not again:
+            break
+        its += _a_solve(y2, geo, targets, goals, wf, n_fft, n_frame, H, tlin, relax=relax)[0]
+    # the oracle's view of the stored samples
+    if rows:
+        out, units = torchgate_units(y.astype(np.float64), sr, xn=None if noise is None else noise.astype(np.float64),
+                                     window=tile_window(W), **kw)
+    else:
+        out, units = oracle_units(y.astype(np.float64), sr, y_noise=noise.astype(np.float64), **kw)
+    assert [(u["ch"], u["chunk"]) for u in units] == [(g["ch"], g["chunk"]) for g in geo]
+    margins = []
+    for ui, u in enumerate(units):
+        assert u["raw"].shape == (F, geo[ui]["T"]), (u["raw"].shape, F, geo[ui]["T"])
+        tf, tt = targets[ui]
+        m = unit_margin(u)[tf, tt]
+        if dtype == "int16":     # rounding to integers moves |X| by several delta: the targets are those that stayed
+            keep = np.abs(m) <= 0.5
+            targets[ui], goals[ui], m = (tf[keep], tt[keep]), goals[ui][keep], m[keep]
+        margins.append(m)
+    return dict(cell=c, y=y, y_noise=noise, xn=noise if rows else None, kw=kw, dtype=dtype, precision=None, sr=sr, W=W, H=H,
+                targets=targets, goals=goals, margins=margins, crowded=crowded, step=4 * -(-sep // 4), sep=sep,
+                iterations=its, residual=err, out=out, units=units, geo=geo)
+
+
+def near_threshold_case(cell):
+    """A near-threshold cell: ``y`` (2, N) in the cell's dtype (row gate: ``y`` is x (3, L) float32), ``y_noise`` the
+    noise clip the threshold comes from (``xn`` for the row gate; None: the row's own statistics), ``kw`` for
+    reduce_noise / ``oracle_units`` (TorchGate / ``torchgate_units``), and the oracle's view of the STORED samples:
+    ``out``, ``units``; per unit ``targets[ui] = (bands, frames)``, ``goals[ui]`` (|X| / T - 1 before rounding),
+    ``margins[ui]`` ((|X| - T) / delta after rounding), ``crowded[ui]`` the crowded frame, ``geo[ui]['g0']`` the sample of the
+    recording frame 0 starts at; ``iterations`` / ``residual``
+    of the solve."""
+    return _near_threshold_case(cell["name"])
