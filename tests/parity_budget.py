@@ -17,7 +17,10 @@ helpers here hold a kernel to the float64 oracle per stage and per hop block ins
 * ``TILE_CELLS``       the matrix of the three table-driven paths (clips, rows, streams);
 * ``adjoint_f64`` / ``emulate_adjoint_f32`` / ``adjoint_unit`` / ``B_CELLS``   TorchGate's backward: the float64 adjoint of
                        the fixed-mask gate, the same in the kernels' arithmetic, and the matrix of the backward routes,
-                       at the end of the module.
+                       further down;
+* ``F_CELLS`` / ``floor_gate_case`` / ``S_CLIPS`` / ``floor_stats_case``   the -80 dB floor band by band: gate inputs with
+                       a few lifted bands per unit and one band +g / -g dB from its switch, and noise clips that reach
+                       every branch of the single-pass statistics, at the end of the module.
 
 Where the numbers come from (none is taken from the code under test):
 
@@ -1484,3 +1487,328 @@ def near_threshold_case(cell):
     recording frame 0 starts at; ``iterations`` / ``residual``
     of the solve."""
     return _near_threshold_case(cell["name"])
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# the -80 dB floor, band by band (tests/test_floor_host.py: conditions on the oracle and planted defects;
+# tests/test_gpu_floor.py: the kernels)
+# ----------------------------------------------------------------------------------------------------------------
+# _amp_to_db floors a band's dB at (its maximum over the padded chunk) - 80.  In the gate a band whose maximum exceeds
+# thresh[f] + 80 dB passes whole (a LIFTED band); in the noise statistics cells more than 80 dB under their band's maximum
+# enter mean and std at the floor.  The inputs here engage both band by band, near the switch:
+#
+# gate (``floor_gate_case``): five units of 56 frames (chunk_size 37 H + 11, padding 9 H + 5, N = 4 chunk_size + 300) of
+# white noise 10 dB under a white noise clip (all amplitudes below are set from the clip's thresholds, so every n_fft
+# and window meets the same margins), plus
+#   * a tone on bin n_fft / 8 over 6 hops in the middle of chunk 1 (no other unit's window holds it);
+#   * an alternating-sign burst (band F - 1) in the LAST W samples of unit 0's padded window: unit 0's only lifting
+#     frames lie wholly in its right padding; unit 1 holds the burst in its body;
+#   * a constant level (band 0) over the FIRST W samples of unit 3's padded window -- a whole frame -- so unit 3's
+#     only lifting frames lie wholly in its left padding; unit 2 holds it in its body;
+#   * a tone on bin 63.5 in the middle of chunk 2 (bands 63 | 64, both sides of the 64-band seam; F > 66 only) and, where
+#     the last 64-band block holds more than four bands, a tone in the middle of that block;
+#   * unit 4 lifts nothing.  (``switch="dc"``: a second constant level early in chunk 2, see ``_f_build``.)
+# The SWITCH band -- band n_fft / 8 + 3 of unit 1, or band 0 of unit 3 (``switch="dc"``) -- is placed at +g and at -g dB
+# from its switch by bisecting its content's amplitude in float64 (g log-uniform in [1e-5, 1e-3]; int16: [3e-4, 1e-3],
+# whole sample values move |X| by ~3e-5 dB); then the samples are rounded to the cell's dtype and the margins re-read.
+#
+# statistics (``floor_stats_case``): noise clips of 150 - 300 frames with zero runs of W + (m - 1) H samples aligned to
+# the frames (exactly m zero-power frames in every band), a steady tone over the middle third above noise 80 dB down
+# (floored cells in the tone's main-lobe bands only), and a plain clip.
+F_GAIN = (1e-5, 1e-3)
+F_GAIN_I16 = (3e-4, 1e-3)
+F_OVER_DB = dict(tone=14.0, nyq=8.0, dc=8.0, seam=10.0, last=10.0)     # a content's peak band over its switch
+_F_REG = ("default", "force_split", "force_nofast", "force_unfused", "floor_test_1", "floor_test_2")
+
+
+def _f(name, family, n_fft, routes=("default",), **kw):
+    return dict(kw, name=name, family=family, n_fft=n_fft, routes=routes)
+
+
+F_CELLS = [
+    _f("register-1024", "register", 1024, _F_REG, switch="dc"),
+    _f("register-512", "register", 512, _F_REG),
+    _f("register-256", "register", 256, _F_REG),
+    _f("register-2048", "register", 2048, _F_REG),
+    _f("lds-64", "lds_pow2", 64),
+    _f("lds-4096", "lds_pow2", 4096),
+    _f("lds-1024-w600-h151", "lds_pow2", 1024, W=600, H=151),
+    _f("lds-8192", "lds_pow2", 8192),
+    _f("mixed-400", "mixed_radix", 400),
+    _f("czt-777", "chirp_z", 777),
+    _f("register-1024-f64", "register", 1024, dtype="float64", precision="float64"),
+    _f("register-1024-i16", "register", 1024, dtype="int16", sw_off=2),
+    _f("register-1024-p07", "register", 1024, ("default", "force_split"), prop=0.7),
+    _f("batch-1024", "clips", 1024, batch=True),
+]
+_F_RESEED = {"register-1024": 1}         # name -> seed offset (tests/test_floor_host.py holds the conditions a seed must meet)
+
+
+def f_cell_id(c):
+    return c["name"]
+
+
+def f_cell(name):
+    return next(c for c in F_CELLS if c["name"] == name)
+
+
+def switch_margin(unit):
+    """(F,) float64: m[f] = max_t dB - 80 - thresh[f] of a stationary unit (positive: the band is lifted)."""
+    with np.errstate(divide="ignore"):
+        db = 20.0 * np.log10(np.abs(unit["Z"]) + O.EPS64)
+    return db.max(axis=1) - 80.0 - unit["thresh"]
+
+
+def _f_store(v, dtype):
+    return np.clip(np.rint(v), -32768, 32767).astype(np.int16) if dtype == "int16" else np.asarray(v).astype(dtype)
+
+
+def _f_geometry(c):
+    n_fft = c["n_fft"]
+    W = c.get("W", n_fft)
+    H = c.get("H", W // 4)
+    cs, pad = 37 * H + 11, 9 * H + 5
+    return n_fft, W, H, cs, pad, 4 * cs + 300
+
+
+def _f_kw(c):
+    n_fft, W, H, cs, pad, N = _f_geometry(c)
+    kw = dict(stationary=True, n_fft=n_fft, chunk_size=cs, padding=pad, prop_decrease=c.get("prop", 1.0))
+    if "W" in c:
+        kw.update(win_length=W, hop_length=H)
+    if n_fft not in (1024, 512, 256, 2048) or "W" in c:
+        kw.update(freq_mask_smooth_hz=3.02 * SR / (n_fft / 2), time_mask_smooth_ms=2.02 * H / SR * 1000)
+    return kw
+
+
+def _f_unit_window(y64, k, cs, pad):
+    return O.read_chunk(y64[None, :], k * cs - pad, (k + 1) * cs + pad)[0]
+
+
+def _f_build(c, sign):
+    """One build of a gate cell: the switch band at sign x g."""
+    n_fft, W, H, cs, pad, N = _f_geometry(c)
+    F = n_fft // 2 + 1
+    dtype = c.get("dtype", "float32")
+    i16 = dtype == "int16"
+    seed = 5200 + 41 * [d["name"] for d in F_CELLS].index(c["name"]) + _F_RESEED.get(c["name"], 0)
+    rng = np.random.default_rng(seed)
+    # the clip's level follows sqrt(W), so the thresholds -- and with them every amplitude below -- are those of W = 1024
+    # at every size; int16: the base noise is 1 LSB RMS, the clip 3
+    level = (1e5 if i16 else 1.0) * np.sqrt(W / 1024.0)
+    base = level * 1e-5 * rng.standard_normal(N)
+    noise = level * 3e-5 * rng.standard_normal(40 * H)
+    sw_kind = c.get("switch", "tone")
+    if sw_kind == "dc":
+        # band 0 must hold the MINIMUM threshold: the clip loses its running mean over W / 4 samples
+        noise = noise - np.convolve(noise, np.ones(W // 4) / (W // 4), mode="same")
+    noise = _f_store(noise, dtype)
+    kw = _f_kw(c)
+    thresh, _, _ = O.noise_threshold_S(noise.astype(np.float64)[None, :], n_fft, W, H, 1.5, cs, True)
+    sw_lin = 10.0 ** ((thresh + 80.0) / 20.0)         # |X| (oracle's scale) at which a band's floor reaches its threshold
+    lo, hi = F_GAIN_I16 if i16 else F_GAIN
+    g = float(np.exp(rng.uniform(np.log(lo), np.log(hi))))
+    i = np.arange(N, dtype=np.float64)
+    over = {k: 10.0 ** (v / 20.0) for k, v in F_OVER_DB.items()}
+    kt = n_fft // 8
+    parts = {}
+
+    def span(a, b):
+        e = np.zeros(N)
+        e[a:b] = 1.0
+        return e
+    mid1 = cs + 15 * H
+    parts["tone"] = (2.0 * sw_lin[kt] * over["tone"], span(mid1, mid1 + 6 * H) * np.sin(2 * np.pi * kt * (i - mid1) / n_fft))
+    parts["nyq"] = (sw_lin[F - 1] * over["nyq"], span(cs + pad - W, cs + pad) * (1.0 - 2.0 * (i % 2)))
+    parts["dc"] = (sw_lin[0] * over["dc"], span(3 * cs - pad, 3 * cs - pad + W))
+    mid2 = 2 * cs + 14 * H
+    if sw_kind == "dc":
+        # unit 2 holds the switch burst in its body, 11 samples off unit 3's frame grid: its band 0 would sit next to the
+        # switch too.  A second level early in chunk 2 (unit 1 sees it in its right padding, unit 3 not at all) lifts it
+        parts["dc2"] = (sw_lin[0] * over["dc"], span(2 * cs + 2 * H, 2 * cs + 2 * H + W))
+    if F > 66:
+        parts["seam"] = (2.0 * sw_lin[63] * over["seam"], span(mid2, mid2 + 8 * H) * np.sin(2 * np.pi * 63.5 * (i - mid2) / n_fft))
+    rem = (F - 1) % 64
+    if rem >= 4:
+        kl = F - 1 - rem // 2
+        parts["last"] = (2.0 * sw_lin[kl] * over["last"],
+                         span(mid2 + H, mid2 + 7 * H) * np.sin(2 * np.pi * kl * (i - mid2) / n_fft + 0.4))
+    sw_part, sw_unit, sw_band = ("dc", 3, 0) if sw_kind == "dc" else ("tone", 1, kt + c.get("sw_off", 3))
+    rest = base + sum(a * s for k, (a, s) in parts.items() if k != sw_part)
+    shape = parts[sw_part][1]
+    w = O.hann_periodic(W)
+
+    def margin(A, stored=False):
+        y = rest + A * shape
+        if stored:
+            y = _f_store(y, dtype).astype(np.float64)
+        x = _f_unit_window(y, sw_unit, cs, pad)
+        ext = np.concatenate([np.zeros(W // 2), x, np.zeros(W // 2)])
+        T = (len(ext) - W) // H + 1
+        fr = ext[np.arange(W)[None, :] + H * np.arange(T)[:, None]] * w[None, :]
+        if sw_band == 0:
+            mag = np.abs(fr.sum(axis=1))
+        else:
+            mag = np.abs(fr @ np.exp(-2j * np.pi * sw_band * np.arange(W) / n_fft))
+        return 20.0 * np.log10(mag.max() / w.sum() + O.EPS64) - 80.0 - thresh[sw_band]
+
+    goal = sign * g
+    a_lo, a_hi = 0.0, (32000.0 if i16 else 0.95)
+    assert margin(a_lo) < goal < margin(a_hi), (c["name"], margin(a_lo), margin(a_hi))
+    for _ in range(200):
+        a_mid = 0.5 * (a_lo + a_hi)
+        if margin(a_mid) < goal:
+            a_lo = a_mid
+        else:
+            a_hi = a_mid
+        if a_hi - a_lo <= 1e-15 * a_hi:
+            break
+    A = 0.5 * (a_lo + a_hi)
+    y = _f_store(rest + A * shape, dtype)
+    return dict(y=y, y_plain=_f_store(base, dtype), y_noise=noise, kw=kw, dtype=dtype, precision=c.get("precision"), g=g, goal=goal, amplitude=A,
+                switch=(sw_unit, sw_band), placed=margin(A), stored=margin(A, stored=True), seed=seed)
+
+
+@functools.lru_cache(maxsize=None)
+def _floor_gate_case(name, sign):
+    c = f_cell(name)
+    case = _f_build(c, sign)
+    out, units = oracle_units(case["y"].astype(np.float64), SR, y_noise=case["y_noise"].astype(np.float64), **case["kw"])
+    case.update(cell=c, out=out, units=units, margins=[switch_margin(u) for u in units])
+    return case
+
+
+def floor_gate_case(cell, sign=+1):
+    """A floor cell's gate input, the switch band at ``sign`` x g: ``y`` (N,) and ``y_noise`` in the cell's dtype, ``kw``
+    for reduce_noise / ``oracle_units``, the oracle's view of the STORED samples (``out``, ``units``) and per unit the
+    switch margin ``margins[ui][f] = max_t dB - 80 - thresh[f]``; ``switch = (unit, band)``, ``g``, ``amplitude``,
+    ``placed`` / ``stored``: the switch band's margin before / after rounding to the dtype; ``y_plain``: the same
+    recording without the added content (no band lifts: ``floor_plain_oracle``)."""
+    return _floor_gate_case(cell["name"], int(sign))
+
+
+@functools.lru_cache(maxsize=4)
+def _floor_plain_oracle(name):
+    case = _floor_gate_case(name, 1)
+    return oracle_units(case["y_plain"].astype(np.float64), SR, y_noise=case["y_noise"].astype(np.float64), **case["kw"])
+
+
+def floor_plain_oracle(cell):
+    """``(out, units)`` of the cell's recording without the added content."""
+    return _floor_plain_oracle(cell["name"])
+
+
+def floor_batch_case(cell):
+    """``reduce_noise_batch``: three clips of different length over one shared noise clip -- the +g build (lifts bands),
+    the start of its first chunk alone (cut before the burst: lifts nothing) and a stretch of the -g build from inside
+    chunk 1 on (its chunk grid is another one: the tone and both bursts lie elsewhere in its units)."""
+    a, b = floor_gate_case(cell, +1), floor_gate_case(cell, -1)
+    n_fft, W, H, cs, pad, N = _f_geometry(cell)
+    ys = [a["y"], a["y"][:cs - 2 * n_fft].copy(), b["y"][cs + 7:3 * cs - 2 * H].copy()]
+    return dict(ys=ys, y_noise=a["y_noise"], kw=a["kw"], dtype=a["dtype"])
+
+
+@functools.lru_cache(maxsize=2)
+def _floor_batch_oracle(name):
+    case = floor_batch_case(f_cell(name))
+    yn = case["y_noise"].astype(np.float64)
+    return [oracle_units(y.astype(np.float64), SR, y_noise=yn, **case["kw"])[1] for y in case["ys"]]
+
+
+def floor_batch_oracle(cell):
+    return _floor_batch_oracle(cell["name"])
+
+
+# ---- statistics ----
+S_CLIPS = [
+    dict(name="runs-1024", n_fft=1024, frames=221, kind="runs"),
+    dict(name="runs-256", n_fft=256, frames=263, kind="runs"),
+    dict(name="tone-mid-1024", n_fft=1024, frames=190, kind="tone", bin=32.0),
+    dict(name="tone-seam-1024", n_fft=1024, frames=190, kind="tone", bin=63.5),
+    dict(name="tone-seam-256", n_fft=256, frames=290, kind="tone", bin=63.5),
+    dict(name="plain-1024", n_fft=1024, frames=160, kind="plain"),
+]
+
+
+def s_clip_id(c):
+    return c["name"]
+
+
+def stats_slices(T, F, frames_per_slice, slices_max, maxs, tg):
+    """The slice count of the single-pass statistics of one unit of T frames (api.hip: stat_slices and stage_stats),
+    and the slice boundaries (kernels.hpp: k_colstats1)."""
+    blocks = (F + 63) // 64
+    nts = max(1, min(-(-2048 // blocks), slices_max, max(1, T // 16)))
+    nts = max(1, min(nts, tg * maxs, T // frames_per_slice))
+    return nts, [T * s // nts for s in range(nts + 1)]
+
+
+@functools.lru_cache(maxsize=None)
+def _floor_stats_case(name, nts):
+    c = next(d for d in S_CLIPS if d["name"] == name)
+    n_fft, T = c["n_fft"], c["frames"]
+    W, H = n_fft, n_fft // 4
+    N = (T - 1) * H + 3
+    rng = np.random.default_rng(6100 + [d["name"] for d in S_CLIPS].index(name))
+    y = 0.1 * rng.standard_normal(N)
+    runs = []
+    if c["kind"] == "runs":
+        b = [T * s // nts for s in range(nts + 1)]
+        assert nts >= 5, nts
+        # (first frame, m): frame 0 alone (the pivot; slice 0 holds one floored frame), two inside slice 1, three inside
+        # slice 2, a pair straddling the boundary of slices 3 | 4, five up to the last frame
+        runs = [(0, 1), (b[1] + 9, 2), (b[2] + 11, 3), (b[4] - 1, 2), (T - 5, 5)]
+        for t0, m in runs:
+            y[max(0, t0 * H - W // 2):(t0 + m - 1) * H + W // 2] = 0.0
+    elif c["kind"] == "tone":
+        i = np.arange(N, dtype=np.float64)
+        a, e = N // 3, (2 * N) // 3
+        # noise 80 dB under the tone in the tone's band: |X| of white noise is ~1.1 sigma sqrt(0.375 W) / (0.5 W)
+        y = 0.25e-4 * np.sqrt(W) / 1.3 * rng.standard_normal(N)
+        # (switched on and off over 4 W samples each: a hard edge spreads the tone over every band of the edge frames)
+        ramp = np.clip(np.minimum(i - a, e - i) / (4.0 * W), 0.0, 1.0)
+        y += 0.5 * np.sin(0.5 * np.pi * ramp) ** 2 * np.sin(2 * np.pi * c["bin"] * i / n_fft)
+    y = y.astype(F32)
+    kw = dict(stationary=True, n_fft=n_fft, chunk_size=N + 1, padding=0, prop_decrease=1.0)
+    return dict(clip=c, y_noise=y, runs=runs, kw=kw, T=T, W=W, H=H, nts=nts)
+
+
+def floor_stats_case(clip, nts):
+    """A statistics clip: ``y_noise`` (float32), ``runs`` [(first zero-power frame, m)], ``T`` frames; ``nts``: the slice
+    count the engine uses for it (the zero runs are placed against its slice boundaries)."""
+    return _floor_stats_case(clip["name"], int(nts))
+
+
+def engine_stats_constants():
+    """``(frames_per_slice, slices_max, maxs, tg)`` of the single-pass noise statistics, read from the sources
+    (csrc/api.hip: SG_STAT_FRAMES_PER_SLICE, SG_STAT_SLICES_MAX and the expressions ``stats_slices`` restates;
+    csrc/kernels.hpp: STAT1_MAXS, STAT_TG and k_colstats1's slice boundaries)."""
+    import os
+    import re
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "noisereduce_amd", "csrc")
+    with open(os.path.join(csrc, "api.hip")) as f:
+        api = f.read()
+    with open(os.path.join(csrc, "kernels.hpp")) as f:
+        ker = f.read()
+
+    def num(text, pattern):
+        m = re.search(pattern, text)
+        assert m, pattern
+        return int(m.group(1))
+    # the expressions restated in stats_slices
+    assert "int64_t nts = (2048 + blocks - 1) / blocks;" in api
+    assert "std::min<int64_t>(SG_STAT_SLICES_MAX, std::max<int64_t>(1, g.T / 16))" in api
+    assert "std::min(stat_slices(g, ub), STAT_TG * STAT1_MAXS), g.T / SG_STAT_FRAMES_PER_SLICE)" in api
+    assert "const int64_t tb = g.T * ts / nts, te = g.T * (ts + 1) / nts;" in ker
+    return (num(api, r"#define SG_STAT_FRAMES_PER_SLICE (\d+)"), num(api, r"#define SG_STAT_SLICES_MAX (\d+)"),
+            num(ker, r"constexpr int STAT1_MAXS = (\d+);"), num(ker, r"constexpr int STAT_TG = (\d+);"))
+
+
+def stats_clip_slices(clip):
+    """``(nts, boundaries)`` the engine uses for a statistics clip."""
+    return stats_slices(clip["frames"], clip["n_fft"] // 2 + 1, *engine_stats_constants())
+
+
+def amp_db_bits(unit, thresh):
+    """The decision bits of a stationary unit under another threshold (F,)."""
+    return O.amp_to_db(unit["Z"], 80.0) > np.asarray(thresh)[:, None]
