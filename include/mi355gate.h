@@ -225,7 +225,8 @@ SG_API int sg_stream_set_threshold(sg_stream_bank* b, const int32_t* slots, int3
 /* One step.  Record i appends n_samples samples per channel to its stream and writes the E(n + n_samples) - E(n) newly
  * final samples per channel (flush: all n + n_samples - E(n) remaining ones, the inverse transform's zero tail included;
  * fewer than win_length samples in the whole stream: SG_E_INVALID) to out_dev.  A slot appears at most once per step.
- * Samples beyond n_samples are never read, nothing beyond the emitted samples is written.  SG_F32 / SG_F64 buffers.
+ * Samples beyond n_samples are never read, nothing beyond the emitted samples is written.  SG_F32 / SG_F64 buffers
+ * (an exact bank, sg_stream_create_ex below: SG_I16 / SG_I32 too).
  * Every argument is checked before any device work; enqueues only. */
 SG_API int sg_stream_push(sg_stream_bank* b, const void* in_dev, int in_dtype, void* out_dev, int out_dtype,
                           const sg_stream_rec* recs, int32_t n_recs, void* stream);
@@ -281,6 +282,37 @@ SG_API int sg_stream_create_adaptive(sg_handle* h, int32_t n_slots, int32_t chan
 SG_API int sg_stream_noise_profile(sg_stream_bank* b, int32_t slot, double* thresh_host, int32_t n_bins, void* stream);
 SG_API int sg_stream_state_bytes_adaptive(const sg_handle* h, int32_t n_slots, int32_t channels, int64_t max_block,
                                           int64_t* bytes);
+/* Exact banks.  A bank made by the three create calls above stores a frame's segment as float32 and rounds every sample to
+ * float32 before it is written: float32-accurate whatever the buffers' type.  sg_stream_create_ex with exact != 0 makes
+ * the same bank -- same frames, E(n), delay, flush, launches per step, independence of the block split, the slot and the
+ * other streams -- whose segments (and, non-stationary, sigmoid mask rows and smoothed rows) are float64, and whose
+ * sg_stream_push takes SG_I16 / SG_I32 as well as SG_F32 / SG_F64 for in_dtype and out_dtype, independently of each
+ * other.  An output sample is the float64 result of the streaming gate's definition at the buffer's type: SG_F64 as is,
+ * SG_F32 rounded once, SG_I16 / SG_I32 truncated toward zero as ndarray.astype does (the offline integer contract of
+ * sg_process_chunks), NaN -> 0 (a non-stationary bank gives 0 / 0 = NaN on digital silence; what astype makes of NaN
+ * differs from platform to platform, 0 is the stated choice); a value outside the integer type's range is as unspecified
+ * as astype's.  A float64 value within rounding noise of an integer may truncate to either neighbour, as offline.  On any
+ * other bank the integer codes are SG_E_INVALID as before, and nothing changes state.
+ * kind selects the create call (SG_STREAM_FIXED: sg_stream_create; SG_STREAM_NONSTATIONARY: lookahead_frames is read;
+ * SG_STREAM_ADAPTIVE: forget and learn_frames are read; fields a kind does not read are ignored).  With exact == 0 the
+ * bank is the one the matching create call makes.  sg_stream_state_bytes_ex: the device memory such a bank would hold --
+ * an exact non-stationary bank keeps its mask rows at 8 bytes, nothing else differs (host arithmetic; SG_E_INVALID when
+ * kind does not fit the handle). */
+#define SG_STREAM_FIXED 0
+#define SG_STREAM_NONSTATIONARY 1
+#define SG_STREAM_ADAPTIVE 2
+typedef struct sg_stream_desc {
+  int32_t n_slots;
+  int32_t channels;
+  int64_t max_block;
+  int32_t kind;              /* SG_STREAM_FIXED / SG_STREAM_NONSTATIONARY / SG_STREAM_ADAPTIVE */
+  int32_t lookahead_frames;  /* non-stationary: 0 .. SG_STREAM_MAX_LOOKAHEAD */
+  double forget;             /* adaptive: forgetting factor per frame, (0, 1] */
+  int64_t learn_frames;      /* adaptive: frames that update the statistics (negative: all) */
+  int32_t exact;             /* != 0: float64 segments, every sample type in and out */
+} sg_stream_desc;
+SG_API int sg_stream_create_ex(sg_handle* h, const sg_stream_desc* desc, sg_stream_bank** out);
+SG_API int sg_stream_state_bytes_ex(const sg_handle* h, const sg_stream_desc* desc, int64_t* bytes);
 
 /* ---- variant T -------------------------------------------------------------------- */
 

@@ -80,6 +80,15 @@ class SgStreamRec(Structure):
                 ("in_stride", c_int64), ("out_offset", c_int64), ("out_stride", c_int64)]
 
 
+SG_STREAM_FIXED, SG_STREAM_NONSTATIONARY, SG_STREAM_ADAPTIVE = 0, 1, 2
+
+
+class SgStreamDesc(Structure):
+    """struct sg_stream_desc (include/mi355gate.h)."""
+    _fields_ = [("n_slots", c_int32), ("channels", c_int32), ("max_block", c_int64), ("kind", c_int32),
+                ("lookahead_frames", c_int32), ("forget", c_double), ("learn_frames", c_int64), ("exact", c_int32)]
+
+
 # every symbol include/mi355gate.h and include/mi355gate_debug.h declare: name -> (restype, argtypes)
 _PROTOTYPES = {
     "sg_version": (c_int, []),
@@ -129,6 +138,8 @@ _PROTOTYPES = {
     "sg_stream_create_adaptive": (c_int, [c_void_p, c_int32, c_int32, c_int64, c_double, c_int64, POINTER(c_void_p)]),
     "sg_stream_noise_profile": (c_int, [c_void_p, c_int32, POINTER(c_double), c_int32, c_void_p]),
     "sg_stream_state_bytes_adaptive": (c_int, [c_void_p, c_int32, c_int32, c_int64, POINTER(c_int64)]),
+    "sg_stream_create_ex": (c_int, [c_void_p, POINTER(SgStreamDesc), POINTER(c_void_p)]),
+    "sg_stream_state_bytes_ex": (c_int, [c_void_p, POINTER(SgStreamDesc), POINTER(c_int64)]),
     "sg_set_option": (c_int, [c_void_p, c_int32, c_int64]),
     "sg_get_option": (c_int, [c_void_p, c_int32, POINTER(c_int64)]),
     "sg_check_errors": (c_int, [c_void_p, c_void_p]),
@@ -566,6 +577,25 @@ class Gate:
                                                            float(forget), int(learn_frames), byref(b)))
         return b
 
+    @staticmethod
+    def stream_desc(n_slots, channels, max_block, kind=SG_STREAM_FIXED, lookahead_frames=0, forget=1.0, learn_frames=-1,
+                    exact=False):
+        return SgStreamDesc(n_slots=int(n_slots), channels=int(channels), max_block=int(max_block), kind=int(kind),
+                            lookahead_frames=int(lookahead_frames), forget=float(forget), learn_frames=int(learn_frames),
+                            exact=int(bool(exact)))
+
+    def stream_create_ex(self, desc):
+        """desc: SgStreamDesc (stream_desc(...)).  exact=True: a bank that takes and returns every sample type exactly."""
+        b = c_void_p()
+        with torch.cuda.device(self.device):
+            self._check(self.lib.sg_stream_create_ex(self._h, byref(desc), byref(b)))
+        return b
+
+    def stream_state_bytes_ex(self, desc):
+        v = c_int64()
+        self._check(self.lib.sg_stream_state_bytes_ex(self._h, byref(desc), byref(v)))
+        return int(v.value)
+
     def stream_noise_profile(self, bank, slot, channels):
         """(channels, n_bins) float64 dB thresholds of an adaptive bank's slot (synchronises the current stream)."""
         out = np.empty((int(channels), self.n_bins), dtype=np.float64)
@@ -608,7 +638,8 @@ class Gate:
                                                          self.n_bins, self._stream()))
 
     def stream_push(self, bank, x, out, recs):
-        """x, out: 1-D float32 / float64 device tensors; recs: sequence of SgStreamRec.  Enqueues only."""
+        """x, out: 1-D float32 / float64 device tensors (an exact bank: int16 / int32 too); recs: sequence of SgStreamRec.
+        Enqueues only."""
         self._on_device(x)
         self._on_device(out)
         arr = (SgStreamRec * max(1, len(recs)))(*recs)

@@ -3718,11 +3718,42 @@ struct sg_stream_bank {
   sg::StBank* b;
 };
 
+// the one create call behind the four entry points; `who` names the caller in the variant message
+static int stream_create(sg_handle* h, const sg_stream_desc& d, const char* who, sg_stream_bank** out) {
+  if (h->p.variant != SG_VARIANT_S) FAIL(h, SG_E_INVALID, "%s is a variant-S entry point", who);
+  sg::StBank* b = nullptr;
+  const sg::StAdaptive ad{d.forget, d.learn_frames};
+  const bool ns = d.kind == SG_STREAM_NONSTATIONARY;
+  int rc = sg::st_create(&b, rg_ctx(h), d.n_slots, d.channels, d.max_block, ns, ns ? d.lookahead_frames : 0,
+                         d.kind == SG_STREAM_ADAPTIVE ? &ad : nullptr, d.exact != 0, &h->err);
+  if (rc) return rc;
+  *out = new sg_stream_bank{h, b};
+  return SG_OK;
+}
+
+extern "C" int sg_stream_create_ex(sg_handle* h, const sg_stream_desc* desc, sg_stream_bank** out) {
+  if (!h || !out) return SG_E_INVALID;
+  if (!desc) FAIL(h, SG_E_INVALID, "sg_stream_create_ex: desc is null");
+  if (desc->kind != SG_STREAM_FIXED && desc->kind != SG_STREAM_NONSTATIONARY && desc->kind != SG_STREAM_ADAPTIVE)
+    FAIL(h, SG_E_INVALID, "sg_stream_create_ex: unknown kind %d", desc->kind);
+  return stream_create(h, *desc, "sg_stream_create_ex", out);
+}
+
+extern "C" int sg_stream_state_bytes_ex(const sg_handle* h, const sg_stream_desc* d, int64_t* bytes) {
+  if (!h || !d || !bytes || d->n_slots < 1 || d->channels < 1 || d->max_block < 1) return SG_E_INVALID;
+  const bool ns = d->kind == SG_STREAM_NONSTATIONARY, ad = d->kind == SG_STREAM_ADAPTIVE;
+  if ((!ns && !ad && d->kind != SG_STREAM_FIXED) || (ns && d->lookahead_frames < 0) || ns == (h->p.stationary != 0))
+    return SG_E_INVALID;
+  sg_handle* hm = const_cast<sg_handle*>(h);
+  *bytes = sg::st_state_bytes(rg_ctx(hm), ns, d->n_slots, d->channels, d->max_block, ns ? d->lookahead_frames : 0, ad, d->exact != 0);
+  return SG_OK;
+}
+
 extern "C" int sg_stream_create(sg_handle* h, int32_t n_slots, int32_t channels, int64_t max_block, sg_stream_bank** out) {
   if (!h || !out) return SG_E_INVALID;
   if (h->p.variant != SG_VARIANT_S) FAIL(h, SG_E_INVALID, "sg_stream_create is a variant-S entry point");
   sg::StBank* b = nullptr;
-  int rc = sg::st_create(&b, rg_ctx(h), n_slots, channels, max_block, false, 0, nullptr, &h->err);
+  int rc = sg::st_create(&b, rg_ctx(h), n_slots, channels, max_block, false, 0, nullptr, false, &h->err);
   if (rc) return rc;
   *out = new sg_stream_bank{h, b};
   return SG_OK;
@@ -3733,7 +3764,7 @@ extern "C" int sg_stream_create_nonstationary(sg_handle* h, int32_t n_slots, int
   if (!h || !out) return SG_E_INVALID;
   if (h->p.variant != SG_VARIANT_S) FAIL(h, SG_E_INVALID, "sg_stream_create_nonstationary is a variant-S entry point");
   sg::StBank* b = nullptr;
-  int rc = sg::st_create(&b, rg_ctx(h), n_slots, channels, max_block, true, lookahead_frames, nullptr, &h->err);
+  int rc = sg::st_create(&b, rg_ctx(h), n_slots, channels, max_block, true, lookahead_frames, nullptr, false, &h->err);
   if (rc) return rc;
   *out = new sg_stream_bank{h, b};
   return SG_OK;
@@ -3753,7 +3784,7 @@ extern "C" int sg_stream_create_adaptive(sg_handle* h, int32_t n_slots, int32_t 
   if (h->p.variant != SG_VARIANT_S) FAIL(h, SG_E_INVALID, "sg_stream_create_adaptive is a variant-S entry point");
   sg::StBank* b = nullptr;
   const sg::StAdaptive ad{forget, learn_frames};
-  int rc = sg::st_create(&b, rg_ctx(h), n_slots, channels, max_block, false, 0, &ad, &h->err);
+  int rc = sg::st_create(&b, rg_ctx(h), n_slots, channels, max_block, false, 0, &ad, false, &h->err);
   if (rc) return rc;
   *out = new sg_stream_bank{h, b};
   return SG_OK;
@@ -3802,8 +3833,8 @@ extern "C" int sg_stream_push(sg_stream_bank* b, const void* in_dev, int in_dtyp
                               const sg_stream_rec* recs, int32_t n_recs, void* stream) {
   if (!b) return SG_E_INVALID;
   sg_handle* h = b->h;
-  if (n_recs < 0 || (n_recs > 0 && !recs) || (in_dtype != SG_F32 && in_dtype != SG_F64) ||
-      (out_dtype != SG_F32 && out_dtype != SG_F64))
+  // (the sample codes an exact bank takes beyond float32 / float64 are st_push's to check: it knows the bank)
+  if (n_recs < 0 || (n_recs > 0 && !recs) || !dtype_ok(in_dtype) || !dtype_ok(out_dtype))
     FAIL(h, SG_E_INVALID, "sg_stream_push: bad argument (float32 / float64 buffers)");
   return sg::st_push(b->b, in_dev, in_dtype, out_dev, out_dtype, recs, n_recs, (hipStream_t)stream, &h->err);
 }

@@ -72,6 +72,17 @@ __device__ __forceinline__ void store_sample(void* p, int dtype, int64_t idx, fl
   }
 }
 
+// The float64 value itself (the exact stream banks): float64 as is, float32 rounded once, integers truncated toward zero
+// as ndarray.astype does.  NaN becomes integer 0: astype of NaN differs from platform to platform, 0 is the stated choice.
+__device__ __forceinline__ void store_sample(void* p, int dtype, int64_t idx, double val) {
+  switch (dtype) {
+    case 0: ((float*)p)[idx] = (float)val; break;
+    case 1: ((double*)p)[idx] = val; break;
+    case 2: ((int16_t*)p)[idx] = (val != val) ? (int16_t)0 : (int16_t)val; break;
+    default: ((int32_t*)p)[idx] = (val != val) ? (int32_t)0 : (int32_t)val; break;
+  }
+}
+
 // dB of one cell exactly as the reference writes it: 20*log10(|Z| + eps)
 // (spectralgate/utils.py:15; torchgate/utils.py:22), |Z| = sqrt(P) * mag_scale.
 __device__ __forceinline__ double cell_db(double P, double mag_scale) {

@@ -19,6 +19,12 @@
 // What a frame goes through is tile_core.hpp's, shared with ragged.hip and rows.hip; this file holds what only a stream
 // has: the ring / block loader, the decisions against a RUNNING band maximum, the carried recurrence, the carry of the
 // overlap-add and the state update.
+// An exact bank (sg_stream_create_ex, exact != 0) runs the same four launches in their exact instantiations: the segment
+// rows are float64 (k_st_apply<N, NS, true>: double2 stores, the float form's lane-to-sample mapping), k_st_finish<true>
+// sums them and stores the float64 value through geom.hpp's store_sample(double) -- float64 as is, float32 rounded once,
+// int16 / int32 truncated toward zero, NaN -> 0.  A non-stationary exact bank also keeps the sigmoid ring mk and the
+// smoothed rows R in float64 (k_sn_decide<N, true>: the sigmoid in float64; k_st_fsmooth<true, true>); a stationary or
+// adaptive one keeps float R, which holds small integers there and is exact already.
 // Nothing waits on another workgroup.  No workgroup reads state that another workgroup of the same launch writes: the
 // ring is only written by k_st_finish (which does not read it), the carry is double buffered, the bit rows of a unit are
 // written by its one decide workgroup.  One fixed evaluation order per frame and per output sample: a stream's output
@@ -69,13 +75,13 @@ struct StArgs {
   double* carry;
   const double* thr;
   const double* T2;
-  float* R;
-  float* seg;
+  void* R;         // smoothed rows: float, double in a non-stationary exact bank
+  void* seg;       // segment rows: float, double in an exact bank
   int RC, RB;
   // non-stationary banks
   double* fst;     // [unit][FS] forward state fwd[f, td]
   double* fa;      // [unit][RF][2][FS] A and fwd rows of the last transformed frames, frame t at t % RF
-  float* mk;       // [unit][RB][FS] raw (sigmoid) mask rows, frame t at t % RB
+  void* mk;        // [unit][RB][FS] raw (sigmoid) mask rows, frame t at t % RB: float, double in an exact bank
   int RF, L;
   // adaptive banks
   double* nst;     // [unit][3][FS] weight sum Wn, mean mu and weighted squared deviations M2 of the floored dB values
@@ -254,8 +260,10 @@ __global__ __launch_bounds__(tile_nt<N>()) void k_sa_decide(StArgs A) {
 // the first loop or of an earlier step, so no barrier separates the two.  S_L[f, t] = the reference's forward-backward
 // smoother of frames 0 .. e, e = min(t + L, last frame): seeded with fwd[e], then k = e .. t in that order whatever the
 // block split.  The sigmoid is the offline kernels' (geom.hpp sigmoid_ratio): S = 0 gives 0 / 0 = NaN as there.
-template <int N>
+// EX: the rows of an exact bank, float64, the sigmoid evaluated in float64 as the reference does (exact.hpp's form).
+template <int N, bool EX>
 __global__ __launch_bounds__(tile_nt<N>()) void k_sn_decide(StArgs A) {
+  using MT = typename std::conditional<EX, double, float>::type;
   constexpr int NT = tile_nt<N>(), SY = tile_sy<N>();
   if ((int64_t)blockIdx.x >= A.n_dec) return;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -300,37 +308,44 @@ __global__ __launch_bounds__(tile_nt<N>()) void k_sn_decide(StArgs A) {
   }
   for (int64_t t = U.ts0 + 1; t <= U.ts1; ++t) {
     const int64_t e = t + A.L < U.td1 ? t + A.L : U.td1;
-    float* mrow = A.mk + ((int64_t)U.state * A.RB + t % A.RB) * FS;
+    MT* mrow = (MT*)A.mk + ((int64_t)U.state * A.RB + t % A.RB) * FS;
 #pragma unroll
     for (int m = 0; m < M; ++m) {
       const int k = lane + NT * m;
       if (k <= N) {
         double s = fa[((e % A.RF) * 2 + 1) * FS + k];
         for (int64_t q = e; q >= t; --q) s = b * fa[((q % A.RF) * 2 + 1) * FS + k] + c * s;
-        mrow[k] = sigmoid_ratio(fa[(t % A.RF) * 2 * FS + k], s, nthresh, slope);
+        const double a = fa[(t % A.RF) * 2 * FS + k];
+        if constexpr (EX) mrow[k] = 1.0 / (1.0 + exp(-((a - s) / s - A.c.nthresh) * A.c.slope));
+        else mrow[k] = sigmoid_ratio(a, s, nthresh, slope);
       }
     }
   }
 }
 
 // ---- mask smoothing along frequency (fsmooth_row) -------------------------------------------------------------------
-// NS: the raw mask is a row of floats (the sigmoid) instead of a row of final bits
-template <bool NS>
+// NS: the raw mask is a row of floats (the sigmoid) instead of a row of final bits; EX (with NS): a row of doubles,
+// summed in double in the same ascending df order
+template <bool NS, bool EX>
 __global__ __launch_bounds__(256) void k_st_fsmooth(StArgs A) {
+  using RT = typename std::conditional<EX, double, float>::type;
   if ((int64_t)blockIdx.x >= A.n_fs) return;
   const Tile tl = A.tiles[A.t_fs + blockIdx.x];
   const StUnit U = A.units[tl.idx];
   for (int64_t r = tl.a; r < tl.b; ++r) {
     const unsigned long long* brow = NS ? nullptr : A.bits + ((int64_t)U.state * A.RB + r % A.RB) * A.c.wpr;
-    const float* frow = NS ? A.mk + ((int64_t)U.state * A.RB + r % A.RB) * A.c.FS : nullptr;
-    fsmooth_row(A.R + (U.mrow + r - U.r0) * A.c.FS, A.c.F, A.c.nf,
-                [&](int g) -> float { return NS ? frow[g] : bit_at(brow, g); });
+    const RT* frow = NS ? (const RT*)A.mk + ((int64_t)U.state * A.RB + r % A.RB) * A.c.FS : nullptr;
+    fsmooth_row((RT*)A.R + (U.mrow + r - U.r0) * A.c.FS, A.c.F, A.c.nf,
+                [&](int g) -> RT { return NS ? frow[g] : (RT)bit_at(brow, g); });
   }
 }
 
 // ---- applied frames: time smoothing, masked multiply, inverse transform ------------------------------------------------
-template <int N, bool NS>
+// EX: float64 segment rows; float64 smoothed rows too where the raw mask is the sigmoid (NS)
+template <int N, bool NS, bool EX>
 __global__ __launch_bounds__(tile_nt<N>()) void k_st_apply(StArgs A) {
+  using ST = typename std::conditional<EX, double, float>::type;
+  using RT = typename std::conditional<EX && NS, double, float>::type;
   if ((int64_t)blockIdx.x >= A.n_ap) return;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   cx<double>* tw = reinterpret_cast<cx<double>*>(smem);
@@ -343,17 +358,20 @@ __global__ __launch_bounds__(tile_nt<N>()) void k_st_apply(StArgs A) {
     st_frame_fft<N>(A, U, t, buf, tw, lane);
     const TimeTaps tp = time_taps(t, A.c.nt, U.Tend);
     auto mask_at = [&](int k) -> double {
-      const double K = time_smooth(A.R, A.c.FS, [&](int64_t q) { return U.mrow + q - U.r0; }, tp, t, A.c.nt, k);
+      const double K = time_smooth((const RT*)A.R, A.c.FS, [&](int64_t q) { return U.mrow + q - U.r0; }, tp, t, A.c.nt, k);
       return NS ? mask_nonstationary(A.c, K) : mask_stationary(A.c, K, tp.Et, k);
     };
-    mask_and_invert<N>(buf, tw, lane, mask_at, A.c.wfull, A.seg + (U.srow + t - (U.ta0 + 1)) * (int64_t)A.c.n);
+    mask_and_invert<N>(buf, tw, lane, mask_at, A.c.wfull, (ST*)A.seg + (U.srow + t - (U.ta0 + 1)) * (int64_t)A.c.n);
   }
 }
 
 // ---- overlap-add of the newly final samples, partial sums of the open ones, state update ----------------------------
 // Sample p sums its frames in frame order, continuing the partial sum an earlier step left in the carry: the additions
 // are the same whatever the block split.  out = sum seg / sum w^2; positions >= Lout are the zero tail.
+// EX: float64 segments, and the float64 value goes to the caller's sample type without a detour through float32.
+template <bool EX>
 __global__ __launch_bounds__(256) void k_st_finish(StArgs A) {
+  using ST = typename std::conditional<EX, double, float>::type;
   if ((int64_t)blockIdx.x >= A.n_fin) return;
   const Tile tl = A.tiles[A.t_fin + blockIdx.x];
   const StUnit U = A.units[tl.idx];
@@ -378,7 +396,7 @@ __global__ __launch_bounds__(256) void k_st_finish(StArgs A) {
   double acc = p < U.cov0 ? cold[p % W] : 0.0;
   const int64_t ta = t_lo > U.ta0 + 1 ? t_lo : U.ta0 + 1, tb = t_hi < U.ta1 ? t_hi : U.ta1;
   for (int64_t t = ta; t <= tb; ++t)
-    acc += (double)A.seg[(U.srow + t - (U.ta0 + 1)) * (int64_t)A.c.n + (int)(e - t * H)];
+    acc += (double)((const ST*)A.seg)[(U.srow + t - (U.ta0 + 1)) * (int64_t)A.c.n + (int)(e - t * H)];
   if (p >= U.E1) {
     cnew[p % W] = acc;
     return;
@@ -388,7 +406,8 @@ __global__ __launch_bounds__(256) void k_st_finish(StArgs A) {
     const double norm = ola_envelope(A.c.wfull, e, H, t_lo, t_hi);
     val = norm > 1e-10 ? acc / norm : acc;
   }
-  store_sample(A.out, A.out_dtype, U.out_off + (p - U.E0), (float)val);
+  if constexpr (EX) store_sample(A.out, A.out_dtype, U.out_off + (p - U.E0), val);
+  else store_sample(A.out, A.out_dtype, U.out_off + (p - U.E0), (float)val);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
@@ -403,12 +422,13 @@ struct StBank {
   int n_slots = 0, C = 0, RC = 0, RB = 0, wpr = 0;
   int ns = 0, L = 0, RF = 0;   // non-stationary bank, its lookahead in frames, depth of the A / fwd ring
   int ad = 0;                  // adaptive bank: the noise statistics are learnt from the stream (nst)
+  int exact = 0;               // exact bank: float64 segments (and sigmoid rows), any sample type in and out
   double lam = 1.0;
   int64_t learn = -1;
   int64_t max_block = 0;
   double *ring = nullptr, *rmax = nullptr, *carry = nullptr, *thr = nullptr, *T2 = nullptr, *stage = nullptr;
   double *fst = nullptr, *fa = nullptr, *nst = nullptr;
-  float* mk = nullptr;
+  void* mk = nullptr;
   unsigned long long* bits = nullptr;
   int32_t* slot_list = nullptr;
   void* tabs = nullptr;
@@ -457,18 +477,19 @@ int check_slots(const StBank* b, const int32_t* slots, int32_t n, const char* wh
 }
 }  // namespace
 
-int64_t st_state_bytes(const RgCtx& c, bool ns, int64_t n_slots, int64_t channels, int64_t max_block, int64_t L, bool adaptive) {
+int64_t st_state_bytes(const RgCtx& c, bool ns, int64_t n_slots, int64_t channels, int64_t max_block, int64_t L, bool adaptive,
+                       bool exact) {
   const int64_t nu = n_slots * channels, mf = max_frames(c, max_block);
   const int64_t RC = c.W + (c.nt + L + 1) * c.H, RB = 2 * (int64_t)c.nt + 1 + L + mf;
   int64_t per = RC * 8 + 2 * (int64_t)c.W * 8;
-  if (ns) per += (int64_t)c.FS * 8 + (L + 1 + mf) * 2 * c.FS * 8 + RB * c.FS * 4;
+  if (ns) per += (int64_t)c.FS * 8 + (L + 1 + mf) * 2 * c.FS * 8 + RB * c.FS * (exact ? 8 : 4);
   else per += (int64_t)c.FS * 8 + RB * ((c.F + 63) / 64) * 8;
   if (adaptive) per += 3 * (int64_t)c.FS * 8;
   return nu * per;
 }
 
 int st_create(StBank** out, const RgCtx& c, int32_t n_slots, int32_t channels, int64_t max_block, bool ns, int32_t lookahead,
-              const StAdaptive* ad, std::string* err) {
+              const StAdaptive* ad, bool exact, std::string* err) {
   if (ad && !c.stationary) { *err = "sg_stream_create_adaptive: the handle is not stationary"; return SG_E_INVALID; }
   if (ad && !(ad->forget > 0.0 && ad->forget <= 1.0)) {
     char m[120];
@@ -504,6 +525,7 @@ int st_create(StBank** out, const RgCtx& c, int32_t n_slots, int32_t channels, i
   b->max_block = max_block;
   b->ns = ns ? 1 : 0;
   b->L = ns ? lookahead : 0;
+  b->exact = exact ? 1 : 0;
   if (ad) {
     b->ad = 1;
     b->lam = ad->forget;
@@ -539,7 +561,7 @@ int st_create(StBank** out, const RgCtx& c, int32_t n_slots, int32_t channels, i
   if (ns) {
     take((void**)&b->fst, nu * c.FS * 8, true);
     take((void**)&b->fa, nu * (size_t)b->RF * 2 * c.FS * 8, false);
-    take((void**)&b->mk, nu * (size_t)b->RB * c.FS * 4, false);
+    take(&b->mk, nu * (size_t)b->RB * c.FS * (exact ? 8 : 4), false);
   } else {
     take((void**)&b->rmax, nu * c.FS * 8, true);
     take((void**)&b->bits, nu * (size_t)b->RB * b->wpr * 8, false);
@@ -556,13 +578,13 @@ int st_create(StBank** out, const RgCtx& c, int32_t n_slots, int32_t channels, i
   const int64_t mf = max_frames(c, max_block);
   b->tabs_bytes = align256(nu * sizeof(StUnit)) + align256(nu * 16 * sizeof(Tile));
   take(&b->tabs, b->tabs_bytes, false);
-  const size_t per_unit = align256((size_t)(mf + 2 * c.nt) * c.FS * 4) + align256((size_t)mf * c.n * 4);
+  const size_t per_unit = align256((size_t)(mf + 2 * c.nt) * c.FS * (exact && ns ? 8 : 4)) + align256((size_t)mf * c.n * (exact ? 8 : 4));
   b->ws_bytes = std::min<size_t>(WS_PREALLOC, nu * per_unit);
   take(&b->ws, b->ws_bytes, false);
   if (!ok) {
     char m[200];
     snprintf(m, sizeof m, "sg_stream_create: device allocation failed (the bank's state is %lld bytes)",
-             (long long)st_state_bytes(c, ns, n_slots, channels, max_block, b->L, ad != nullptr));
+             (long long)st_state_bytes(c, ns, n_slots, channels, max_block, b->L, ad != nullptr, exact));
     st_destroy(b);
     *err = m;
     return SG_E_NOMEM;
@@ -659,6 +681,11 @@ int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_
   const int h = c.W / 2;
   char msg[200];
   // ---- every argument is checked before any device work or state change
+  auto dtype_ok = [&](int d) { return d == SG_F32 || d == SG_F64 || (b->exact && (d == SG_I16 || d == SG_I32)); };
+  if (!dtype_ok(in_dtype) || !dtype_ok(out_dtype)) {
+    *err = "sg_stream_push: bad argument (float32 / float64 buffers)";
+    return SG_E_INVALID;
+  }
   std::vector<char> seen(b->n_slots, 0);
   for (int32_t i = 0; i < n_recs; ++i) {
     const sg_stream_rec& r = recs[i];
@@ -778,7 +805,8 @@ int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_
   const size_t ub = align256(units.size() * sizeof(StUnit)), tb = align256(tl.tiles.size() * sizeof(Tile));
   int rc = grow_device_buffer(&b->tabs, &b->tabs_bytes, ub + tb, st, "sg_stream_push", "table", err);
   if (rc) return rc;
-  const size_t Rb = align256((size_t)mrows * c.FS * 4), Sb = align256((size_t)sframes * c.n * 4);
+  const bool ex = b->exact != 0;
+  const size_t Rb = align256((size_t)mrows * c.FS * (ex && b->ns ? 8 : 4)), Sb = align256((size_t)sframes * c.n * (ex ? 8 : 4));
   if ((rc = grow_device_buffer(&b->ws, &b->ws_bytes, Rb + Sb, st, "sg_stream_push", "workspace", err))) return rc;
   if (upload_tables(b->tabs, st, {{units.data(), units.size() * sizeof(StUnit), ub},
                                   {tl.tiles.data(), tl.tiles.size() * sizeof(Tile), tb}}) != hipSuccess) {
@@ -789,7 +817,7 @@ int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_
   A.units = (const StUnit*)b->tabs;
   A.tiles = (const Tile*)((char*)b->tabs + ub);
   A.ring = b->ring; A.bits = b->bits; A.rmax = b->rmax; A.carry = b->carry; A.thr = b->thr; A.T2 = b->T2;
-  A.R = (float*)b->ws; A.seg = (float*)((char*)b->ws + Rb);
+  A.R = b->ws; A.seg = (char*)b->ws + Rb;
   A.RC = b->RC; A.RB = b->RB;
   A.fst = b->fst; A.fa = b->fa; A.mk = b->mk; A.RF = b->RF; A.L = b->L;
   A.nst = b->nst; A.lam = b->lam; A.learn = b->learn;
@@ -801,20 +829,22 @@ int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_
     Prof pr(c, SG_STAGE_RG_DECIDE, st);
     e = dispatch_N(c.N, [&](auto n) {
       if (b->ad) return launch_tile_kernel<n()>(k_sa_decide<n()>, A.n_dec, st, A);
-      return ns ? launch_tile_kernel<n()>(k_sn_decide<n()>, A.n_dec, st, A) : launch_tile_kernel<n()>(k_st_decide<n()>, A.n_dec, st, A);
+      if (ns) return ex ? launch_tile_kernel<n()>(k_sn_decide<n(), true>, A.n_dec, st, A) : launch_tile_kernel<n()>(k_sn_decide<n(), false>, A.n_dec, st, A);
+      return launch_tile_kernel<n()>(k_st_decide<n()>, A.n_dec, st, A);
     });
   }
   if (e == hipSuccess) {
     Prof pr(c, SG_STAGE_RG_FSMOOTH, st);
-    e = launch_flat_kernel(ns ? k_st_fsmooth<true> : k_st_fsmooth<false>, A.n_fs, 256, st, A);
+    e = launch_flat_kernel(ns ? (ex ? k_st_fsmooth<true, true> : k_st_fsmooth<true, false>) : k_st_fsmooth<false, false>, A.n_fs, 256, st, A);
   }
   if (e == hipSuccess) {
     Prof pr(c, SG_STAGE_RG_APPLY, st);
     e = dispatch_N(c.N, [&](auto n) {
-      return ns ? launch_tile_kernel<n()>(k_st_apply<n(), true>, A.n_ap, st, A) : launch_tile_kernel<n()>(k_st_apply<n(), false>, A.n_ap, st, A);
+      if (ex) return ns ? launch_tile_kernel<n()>(k_st_apply<n(), true, true>, A.n_ap, st, A) : launch_tile_kernel<n()>(k_st_apply<n(), false, true>, A.n_ap, st, A);
+      return ns ? launch_tile_kernel<n()>(k_st_apply<n(), true, false>, A.n_ap, st, A) : launch_tile_kernel<n()>(k_st_apply<n(), false, false>, A.n_ap, st, A);
     });
   }
-  if (e == hipSuccess) { Prof pr(c, SG_STAGE_RG_OLA, st); e = launch_flat_kernel(k_st_finish, A.n_fin, 256, st, A); }
+  if (e == hipSuccess) { Prof pr(c, SG_STAGE_RG_OLA, st); e = launch_flat_kernel(ex ? k_st_finish<true> : k_st_finish<false>, A.n_fin, 256, st, A); }
   if (e != hipSuccess) {
     *err = std::string("sg_stream_push: launch failed: ") + hipGetErrorString(e);
     return SG_E_HIP;

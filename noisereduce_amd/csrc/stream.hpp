@@ -12,7 +12,8 @@
 // A non-stationary bank (lookahead L frames; no thresholds) holds instead of bits / rmax / thr / T2:
 //   fst    [unit][FS]          forward one-pole state fwd[f, last transformed frame], float64
 //   fa     [unit][RF][2][FS]   A = |X| and fwd of the last transformed frames, float64 (RF = L + 1 + frames of max_block)
-//   mk     [unit][RB][FS]      raw sigmoid mask rows, float32 (RB = 2 nt + 1 + L + frames of max_block)
+//   mk     [unit][RB][FS]      raw sigmoid mask rows, float32 -- float64 in an exact bank -- (RB = 2 nt + 1 + L + frames of
+//                              max_block)
 // and its ring is RC = W + (nt + L + 1) H samples.
 // An adaptive bank (the stationary gate with the noise profile learnt from the stream itself) holds no thr / T2 but
 //   nst    [unit][3][FS]       Wn, mu, M2: weight sum, mean and weighted squared deviations of the floored dB values, float64
@@ -44,11 +45,13 @@ struct StAdaptive {
 
 // ns: a non-stationary bank with `lookahead` frames (the handle must be non-stationary); else lookahead is ignored.
 // ad: non-null for an adaptive bank (the handle must be stationary)
+// exact: float64 segments (and, non-stationary, float64 mk rows): the bank takes and returns every sample type, each
+// exactly (sg_stream_create_ex)
 int st_create(StBank** out, const RgCtx& c, int32_t n_slots, int32_t channels, int64_t max_block, bool ns, int32_t lookahead,
-              const StAdaptive* ad, std::string* err);
+              const StAdaptive* ad, bool exact, std::string* err);
 // bytes of device state st_create allocates for such a bank (host arithmetic)
 int64_t st_state_bytes(const RgCtx& c, bool ns, int64_t n_slots, int64_t channels, int64_t max_block, int64_t L,
-                       bool adaptive = false);
+                       bool adaptive = false, bool exact = false);
 // adaptive banks: the threshold (dB) after the last decided frame of every channel of `slot`, channels x F values, NaN
 // where no frame was decided yet.  Synchronises the stream.
 int st_noise_profile(StBank* b, int32_t slot, double* thresh_host, hipStream_t st, std::string* err);

@@ -168,16 +168,17 @@ __device__ __forceinline__ int band_mode(double pmax, double th, double t2, doub
 
 __device__ __forceinline__ float bit_at(const unsigned long long* row, int g) { return (float)((row[g >> 6] >> (g & 63)) & 1ull); }
 
-// mask smoothing along frequency, one row by the whole workgroup: out[f] = sum_df (nf + 1 - |df|) raw(f + df), float32,
-// df ascending, bands outside [0, F) skipped
-template <class Raw>
-__device__ __forceinline__ void fsmooth_row(float* out, int F, int nf, Raw&& raw) {
+// mask smoothing along frequency, one row by the whole workgroup: out[f] = sum_df (nf + 1 - |df|) raw(f + df), in the
+// row's element type RT (float32; float64 for the sigmoid rows of an exact stream bank), df ascending, bands outside
+// [0, F) skipped
+template <class RT = float, class Raw>
+__device__ __forceinline__ void fsmooth_row(RT* out, int F, int nf, Raw&& raw) {
   for (int f = threadIdx.x; f < F; f += blockDim.x) {
-    float acc = 0.f;
+    RT acc = (RT)0;
     for (int df = -nf; df <= nf; ++df) {
       const int g = f + df;
       if (g < 0 || g >= F) continue;
-      acc += (float)(nf + 1 - (df < 0 ? -df : df)) * raw(g);
+      acc += (RT)(nf + 1 - (df < 0 ? -df : df)) * raw(g);
     }
     out[f] = acc;
   }
@@ -192,8 +193,8 @@ struct TimeTaps {
 __device__ __forceinline__ TimeTaps time_taps(int64_t t, int nt, int64_t T) {
   return {t - nt < 0 ? 0 : t - nt, t + nt >= T ? T - 1 : t + nt, (double)tri_valid(nt, t, T)};
 }
-template <class RowOf>
-__device__ __forceinline__ double time_smooth(const float* R, int FS, RowOf&& row_of, const TimeTaps& tp, int64_t t, int nt, int k) {
+template <class RT = float, class RowOf>
+__device__ __forceinline__ double time_smooth(const RT* R, int FS, RowOf&& row_of, const TimeTaps& tp, int64_t t, int nt, int k) {
   double K = 0.0;
   for (int64_t q = tp.ta; q <= tp.tb; ++q) {
     const int64_t d = q - t;
@@ -211,10 +212,11 @@ __device__ __forceinline__ double mask_nonstationary(const TileConsts& C, double
 }
 
 // the packed transform of a real frame in buf times mask_at(k), k = 0 .. N (split / mask / merge; mask_at is called
-// once per band), inverse transform, synthesis window, the frame's n samples to seg_row
-template <int N, class MaskAt>
+// once per band), inverse transform, synthesis window, the frame's n samples to seg_row in its element type ST (float32
+// rounds them once; float64 -- an exact stream bank -- keeps them: same lane-to-sample mapping, double2 stores)
+template <int N, class ST = float, class MaskAt>
 __device__ __forceinline__ void mask_and_invert(cx<double>* buf, const cx<double>* tw, int lane, MaskAt&& mask_at,
-                                                const double* wfull, float* seg_row) {
+                                                const double* wfull, ST* seg_row) {
   constexpr int NT = tile_nt<N>(), SY = tile_sy<N>();
   for (int k = lane; k <= N / 2; k += NT) {
     if (k == 0) {
@@ -241,11 +243,13 @@ __device__ __forceinline__ void mask_and_invert(cx<double>* buf, const cx<double
   }
   team_sync<SY>();
   wave_fft<double, N, true, NT, SY>(buf, tw, lane);
-  float2* srow = reinterpret_cast<float2*>(seg_row);
   const double inv = 1.0 / (double)N;
   for (int j = lane; j < N; j += NT) {
     const cx<double> z = buf[lp<double>(j)];
-    srow[j] = make_float2((float)(z.x * wfull[2 * j] * inv), (float)(z.y * wfull[2 * j + 1] * inv));
+    if constexpr (std::is_same<ST, double>::value)
+      reinterpret_cast<double2*>(seg_row)[j] = make_double2(z.x * wfull[2 * j] * inv, z.y * wfull[2 * j + 1] * inv);
+    else
+      reinterpret_cast<float2*>(seg_row)[j] = make_float2((float)(z.x * wfull[2 * j] * inv), (float)(z.y * wfull[2 * j + 1] * inv));
   }
   team_sync<SY>();
 }
@@ -267,8 +271,8 @@ __device__ __forceinline__ double ola_envelope(const double* wfull, int64_t e, i
 }
 // overlap-add of the offline paths at extended position e: sum of the frames' segments (frame t's at seg_row_of(t) * n)
 // and the envelope, in one walk over the frames
-template <class SegRowOf>
-__device__ __forceinline__ void ola_sum(const TileConsts& C, const float* seg, SegRowOf&& seg_row_of, int64_t e, int64_t T,
+template <class ST = float, class SegRowOf>
+__device__ __forceinline__ void ola_sum(const TileConsts& C, const ST* seg, SegRowOf&& seg_row_of, int64_t e, int64_t T,
                                         double* acc, double* norm) {
   int64_t t_lo, t_hi;
   ola_span(e, C.n, C.H, T, &t_lo, &t_hi);

@@ -59,8 +59,30 @@ and no band ranging over more than ``top_db``, ``noise_profile`` just before the
 whole signal.  Everything else -- frames, ``emitted``, ``latency_samples``, flush, launches per step, bitwise independence
 of the block split, the slot and the other streams -- is the fixed-profile bank's.
 
-Out of scope: ``TorchGate``, integer blocks, several GPUs, and ``n_fft`` other than a power of two from 256 to 4096
-(``ValueError``).
+``precision="float64"`` makes the bank exact: its streams are the gate above at the block's own sample type.  The default
+bank stores every frame's segment as float32 and rounds every sample to float32 before it leaves the device (a
+non-stationary one also keeps its sigmoid and smoothed mask rows as float32), so a float64 block comes back float32-accurate
+in a float64 array and integer blocks are refused.  The exact bank keeps all of that in float64 -- the transforms, the ring
+and the overlap-add carry are float64 in both -- and takes float32, float64, int16 and int32 blocks, every slot getting its
+own block's type back:
+
+* float64 blocks come back float64-accurate (1e-12 of peak against the float64 model instead of 1e-7);
+* float32 blocks are that float64 result rounded once;
+* int16 / int32 blocks are ``trunc(float64 result)``, as ``ndarray.astype`` truncates and as ``reduce_noise`` returns integer
+  recordings offline: where the causal floor is not live, ``reduce_noise(y_int, sr, ..., chunk_size=None, padding=0)`` of the
+  whole recording.  The caveat is the offline one: a float64 value within rounding noise of an integer may truncate to either
+  neighbour.  NaN (digital silence in a non-stationary bank is ``0 / 0``) becomes integer 0 -- what ``astype`` makes of NaN
+  differs from platform to platform, so 0 is the stated choice.  Values outside the integer range are as unspecified as
+  ``astype``'s.
+
+A step whose blocks all share one sample type travels in that type both ways (an int16 step uploads and downloads 2 bytes
+per sample); a step of mixed types travels as float64, which holds all four types exactly, and every slot's result is
+converted on arrival with the same rounding / truncation / NaN rule.  Either way a slot's samples are bitwise those of the
+same stream pushed alone.  Everything else -- frames, ``emitted``, ``latency_samples``, flush, four launches per step,
+bitwise independence of the block split, the slot and the other streams -- is unchanged; the cost is a scratch twice as wide
+and, non-stationary, mask rows of 8 bytes (``state_bytes(..., exact=True)``).
+
+Out of scope: ``TorchGate``, several GPUs, and ``n_fft`` other than a power of two from 256 to 4096 (``ValueError``).
 """
 import numpy as np
 import torch
@@ -70,6 +92,9 @@ from noisereduce_amd import _ffi
 _NONE_CHUNK = 1 << 62
 _N_FFTS = (256, 512, 1024, 2048, 4096)
 _FLOATS = (np.dtype(np.float32), np.dtype(np.float64))
+_EXACT_TYPES = _FLOATS + (np.dtype(np.int16), np.dtype(np.int32))      # what a precision="float64" bank takes
+_TORCH = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64, np.dtype(np.int16): torch.int16,
+          np.dtype(np.int32): torch.int32}
 MAX_STATE_BYTES = 32 << 30      # default bound on a bank's device state (``max_state_bytes=``)
 MAX_LOOKAHEAD_FRAMES = 4096     # SG_STREAM_MAX_LOOKAHEAD (include/mi355gate.h)
 
@@ -91,9 +116,10 @@ def iir_coefficient(time_constant_s, sr, H):
     return (np.sqrt(1 + 4 * t_frames ** 2) - 1) / (2 * t_frames ** 2)
 
 
-def state_bytes(n_units, n_fft, W, H, nt, L, max_block, stationary, noise_from_stream=False):
-    """Device memory a bank holds between steps (sg_stream_state_bytes' arithmetic; DESIGN section 13's state table).
-    ``noise_from_stream``: the three float64 rows of noise statistics per unit of an adaptive bank."""
+def state_bytes(n_units, n_fft, W, H, nt, L, max_block, stationary, noise_from_stream=False, exact=False):
+    """Device memory a bank holds between steps (sg_stream_state_bytes_ex's arithmetic; DESIGN section 13's state table).
+    ``noise_from_stream``: the three float64 rows of noise statistics per unit of an adaptive bank.  ``exact``: the
+    sigmoid rows of a non-stationary bank at 8 bytes (nothing else of the state differs)."""
     F = n_fft // 2 + 1
     FS = (F + 15) // 16 * 16
     mf = (max_block + W // 2) // H + 3
@@ -102,7 +128,7 @@ def state_bytes(n_units, n_fft, W, H, nt, L, max_block, stationary, noise_from_s
     if stationary:
         per += RB * ((F + 63) // 64) * 8
     else:
-        per += (L + 1 + mf) * 2 * FS * 8 + RB * FS * 4
+        per += (L + 1 + mf) * 2 * FS * 8 + RB * FS * (8 if exact else 4)
     if noise_from_stream:
         per += 3 * FS * 8
     return n_units * per
@@ -135,7 +161,8 @@ class StreamBank:
     stream (default: one second).
 
     ``push({slot: block})`` -> ``{slot: out}``: blocks are ``(n,)`` or ``(C, n)`` float32 / float64 numpy arrays or
-    device tensors; device tensors in give device tensors out with no host synchronisation (output lengths are host
+    device tensors (``precision="float64"``: int16 / int32 too, every slot gets its block's type back, each sample the
+    float64 result at that type -- module docstring); device tensors in give device tensors out with no host synchronisation (output lengths are host
     arithmetic); numpy in gives numpy out.  ``flush(slots)`` -> ``{slot: tail}`` ends streams (fewer than ``win_length``
     samples in all: ``ValueError``) and leaves the slots empty; ``reset(slots)`` drops their state.
 
@@ -150,7 +177,11 @@ class StreamBank:
                  n_std_thresh_stationary=1.5, freq_mask_smooth_hz=500, time_mask_smooth_ms=50, n_fft=1024,
                  win_length=None, hop_length=None, max_block=None, device="cuda", stationary=True, lookahead_ms=0.0,
                  time_constant_s=2.0, thresh_n_mult_nonstationary=2, sigmoid_slope_nonstationary=10,
-                 max_state_bytes=MAX_STATE_BYTES, noise_from_stream=False, noise_memory_s=None, noise_learn_s=None):
+                 max_state_bytes=MAX_STATE_BYTES, noise_from_stream=False, noise_memory_s=None, noise_learn_s=None,
+                 precision=None):
+        if precision not in (None, "float32", "float64"):
+            raise ValueError(f"StreamBank: precision must be None, 'float32' or 'float64' (got {precision!r})")
+        self.exact = precision == "float64"
         stationary = bool(stationary)
         noise_from_stream = bool(noise_from_stream)
         if noise_from_stream and (y_noise is not None or thresholds_db is not None):
@@ -205,7 +236,7 @@ class StreamBank:
         self._lag = self.nt + self.lookahead_frames      # frames between the last one inside the audio and the last applied
         self.latency_samples = W + (self._lag + 1) * H
         self.state_bytes = state_bytes(self.n_streams * self.channels, n_fft, W, H, self.nt, self.lookahead_frames,
-                                       self.max_block, stationary, noise_from_stream)
+                                       self.max_block, stationary, noise_from_stream, self.exact)
         if not stationary and self.state_bytes > max_state_bytes:
             raise ValueError(f"StreamBank: {self.n_streams} x {self.channels} streams with lookahead_frames="
                              f"{self.lookahead_frames} and max_block={self.max_block} need {self.state_bytes} bytes of "
@@ -236,7 +267,13 @@ class StreamBank:
         if self._bank is None:
             self._gate = _ffi.Gate(self._device_arg, **self._gate_kw)
             self.device = self._gate.device
-            if self.noise_from_stream:
+            if self.exact:
+                kind = (_ffi.SG_STREAM_ADAPTIVE if self.noise_from_stream else
+                        _ffi.SG_STREAM_FIXED if self.stationary else _ffi.SG_STREAM_NONSTATIONARY)
+                self._bank = self._gate.stream_create_ex(_ffi.Gate.stream_desc(
+                    self.n_streams, self.channels, self.max_block, kind, self.lookahead_frames, self.noise_forget,
+                    self.noise_learn_frames, exact=True))
+            elif self.noise_from_stream:
                 self._bank = self._gate.stream_create_adaptive(self.n_streams, self.channels, self.max_block,
                                                                self.noise_forget, self.noise_learn_frames)
             elif self.stationary:
@@ -349,8 +386,11 @@ class StreamBank:
             elif tensor_io != is_t:
                 raise ValueError("StreamBank: the blocks of a step must be all numpy arrays or all device tensors")
             dt = np.dtype(str(a.dtype).replace("torch.", ""))
-            if dt not in _FLOATS:
-                raise ValueError(f"StreamBank: blocks are float32 or float64 (got {dt}; integer blocks are out of scope)")
+            if self.exact and dt not in _EXACT_TYPES:
+                raise ValueError(f"StreamBank: blocks are float32, float64, int16 or int32 (got {dt})")
+            if not self.exact and dt not in _FLOATS:
+                raise ValueError(f"StreamBank: blocks are float32 or float64 (got {dt}; precision=\"float64\" takes "
+                                 f"int16 / int32 blocks too)")
             if is_t and a.device.type != "cuda":
                 raise ValueError("StreamBank: block tensors must live on the GPU")
             flat = a.ndim == 1
@@ -370,8 +410,14 @@ class StreamBank:
         if tensor_io is None:      # a flush without a last block: what the streams were fed with
             tensor_io = bool(items) and all(self._kind[s][0] for s, _, _, _ in items)
         self._ensure()
-        wide = any(a is not None and str(a.dtype).endswith("float64") for _, a, _, _ in items)
-        tdt = torch.float64 if wide else torch.float32
+        if self.exact:      # one sample type: the step travels in it; several: in float64, which holds every one exactly
+            kinds = {np.dtype(str(a.dtype).replace("torch.", "")) if a is not None else self._kind[s][1]
+                     for s, a, _, _ in items}
+            travel = kinds.pop() if len(kinds) == 1 else np.dtype(np.float64)
+        else:
+            wide = any(a is not None and str(a.dtype).endswith("float64") for _, a, _, _ in items)
+            travel = np.dtype(np.float64 if wide else np.float32)
+        tdt = _TORCH[travel]
         recs, outs, in_off, out_off = [], [], 0, 0
         for s, a, n, flat in items:
             n1 = self._n[s] + n
@@ -388,7 +434,7 @@ class StreamBank:
             else:
                 xh = torch.empty(max(in_off, 1), dtype=tdt, pin_memory=True)
                 if parts:
-                    xh.numpy()[:in_off] = np.concatenate(parts)
+                    xh.numpy()[:in_off] = np.concatenate([p.astype(travel, copy=False) for p in parts])
                 x = xh.to(self.device, non_blocking=True)
             if x.numel() == 0:
                 x = torch.empty(1, dtype=tdt, device=self.device)
@@ -410,9 +456,13 @@ class StreamBank:
                 else:
                     dt = self._kind[s][1]
                     if tensor_io:
-                        dt = torch.float64 if dt == np.float64 else torch.float32
+                        dt = _TORCH[dt]
                 if flat and C == 1:
                     o = o[0]
+                if self.exact and not (dt.is_floating_point if tensor_io else dt.kind == "f"):
+                    # (a mixed step arrives as float64: the kernel's integer store -- NaN -> 0, then truncation)
+                    if o.dtype != dt:
+                        o = torch.where(o != o, torch.zeros_like(o), o) if tensor_io else np.where(o != o, 0.0, o)
                 res[s] = o.to(dt) if tensor_io else o.astype(dt, copy=True)
             return res
 
@@ -440,7 +490,7 @@ class StreamBank:
 
 class StreamGate:
     """One stream: ``push(block) -> out``, ``flush() -> tail`` (a ``StreamBank`` of one slot; same arguments,
-    ``stationary=False`` and ``noise_from_stream=True`` included)."""
+    ``stationary=False``, ``noise_from_stream=True`` and ``precision="float64"`` included)."""
 
     def __init__(self, sr, y_noise=None, **kw):
         self.bank = StreamBank(sr, 1, y_noise=y_noise, **kw)
