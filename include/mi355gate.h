@@ -313,6 +313,70 @@ typedef struct sg_stream_desc {
 } sg_stream_desc;
 SG_API int sg_stream_create_ex(sg_handle* h, const sg_stream_desc* desc, sg_stream_bank** out);
 SG_API int sg_stream_state_bytes_ex(const sg_handle* h, const sg_stream_desc* desc, int64_t* bytes);
+/* State transfer.  sg_stream_export copies what the listed slots' streams need to go on -- and nothing else -- out of the
+ * bank into blob_dev; sg_stream_import writes such payloads into slots of a COMPATIBLE bank (this one, or one of another
+ * n_slots, max_block, device or process), after which sg_stream_counters and the next sg_stream_push continue each stream
+ * bit for bit as if it had always lived there.  Compatible: every signature field of sg_stream_head equal (SG_E_INVALID
+ * names the first that differs).  One launch per call, however many slots; enqueues only.  Export does not disturb the
+ * streams; import drops whatever the target slots held, their thresholds included (has_thr is the source's).
+ *   slot i's payload lies at blob_dev + offsets[i]: offsets are multiples of 256 bytes, blob_dev is 256-byte aligned; the
+ *   payloads of an export must not overlap, those of an import may (two slots fed from one payload: a fork);
+ *   heads[i] is written by export (host memory) and read by import; payload_bytes = sg_stream_export_bytes (host
+ *   arithmetic from the slot's counters, a multiple of 8); `client` is opaque to the library and travels unchanged.
+ * The payload is canonical: samples and frame rows in index order from the first live one, not at their ring positions,
+ * so it does not depend on max_block.  Per slot: a fixed bank's thr and T2 rows; then per channel the ring samples
+ * [max(0, n - RC), n), the live overlap-add carry [E, ta * hop - h + win_length), and -- stationary / adaptive -- the band
+ * maxima and the bit rows of frames [max(0, ta + 1 - nt), td], -- adaptive -- the three rows of noise statistics, -- non-
+ * stationary -- the forward state, the A / fwd rows of frames (ts, td] and the sigmoid rows of frames [max(0, ta + 1 -
+ * nt), ts].  Every argument is checked before any device work: an unknown slot, a slot listed twice,
+ * a bad offset, a head whose magic, version, signature, counters (td, ts, ta, E follow from n) or payload_bytes do not
+ * fit are SG_E_INVALID and change nothing.  Import commits the host counters at enqueue, as sg_stream_push does. */
+#define SG_STREAM_HEAD_MAGIC 0x54534753 /* "SGST" */
+#define SG_STREAM_HEAD_VERSION 1
+typedef struct sg_stream_head {
+  int32_t magic;
+  int32_t version;
+  /* signature: what has to be equal between the two banks */
+  int32_t n_fft;
+  int32_t win_length;
+  int32_t hop_length;
+  int32_t channels;
+  int32_t kind;              /* SG_STREAM_FIXED / SG_STREAM_NONSTATIONARY / SG_STREAM_ADAPTIVE */
+  int32_t n_grad_freq;
+  int32_t n_grad_time;
+  int32_t smooth_mask;
+  int32_t lookahead_frames;
+  int32_t exact;
+  double prop_decrease;
+  double n_std_thresh;
+  double top_db;
+  double iir_b;
+  double nonstat_thresh;
+  double nonstat_slope;
+  double noise_forget;
+  int64_t noise_learn_frames;
+  /* counters of the stream */
+  int64_t n;                 /* samples received */
+  int64_t td;                /* last transformed frame (-1: none) */
+  int64_t ts;                /* last frame with a raw mask row */
+  int64_t ta;                /* last applied frame */
+  int64_t E;                 /* samples emitted */
+  int32_t par;               /* the live carry buffer */
+  int32_t has_thr;           /* the slot has its noise profile */
+  int64_t payload_bytes;
+  int32_t client0;           /* opaque to the library (the Python layer: kind of the last block) */
+  int32_t client1;
+  int32_t client2;
+  int32_t client3;
+} sg_stream_head;
+SG_API int sg_stream_export_bytes(const sg_stream_bank* b, int32_t slot, int64_t* bytes);
+/* The payload size that a header's signature and n give: host arithmetic without a bank, a handle or a device (what a
+ * receiver checks a header against before it allocates anything).  SG_E_INVALID for a signature no bank can have. */
+SG_API int sg_stream_head_bytes(const sg_stream_head* head, int64_t* bytes);
+SG_API int sg_stream_export(sg_stream_bank* b, const int32_t* slots, int32_t n_slots, void* blob_dev, const int64_t* offsets,
+                            sg_stream_head* heads_out, void* stream);
+SG_API int sg_stream_import(sg_stream_bank* b, const int32_t* slots, int32_t n_slots, const void* blob_dev,
+                            const int64_t* offsets, const sg_stream_head* heads_in, void* stream);
 
 /* ---- variant T -------------------------------------------------------------------- */
 

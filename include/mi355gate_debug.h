@@ -119,9 +119,14 @@ SG_API int sg_debug_backward_route(const sg_handle* h, int64_t* value);
 #define SG_STAGE_RG_APPLY 25       /* smoothing along time + masked multiply + inverse transform of every live frame */
 #define SG_STAGE_RG_OLA 26         /* overlap-add of the kept samples */
 #define SG_N_STAGES 27
+/* stages beyond the 27 every reader of sg_profile_read(..., SG_N_STAGES, ...) knows: state transfer of stream banks */
+#define SG_STAGE_ST_EXPORT 27      /* k_st_export (sg_stream_export): one launch per call */
+#define SG_STAGE_ST_IMPORT 28      /* k_st_import (sg_stream_import): one launch per call */
+#define SG_N_STAGES_ALL 29
 /* When enabled, every kernel launch is bracketed by a hipEvent pair recorded on the launch
  * stream.  sg_profile_read synchronises those events and returns accumulated milliseconds
- * and launch counts per stage (arrays of SG_N_STAGES); reset != 0 clears the accumulators. */
+ * and launch counts per stage (arrays of n_stages = SG_N_STAGES, or SG_N_STAGES_ALL with the
+ * stages above); reset != 0 clears the accumulators of every stage. */
 SG_API int sg_profile_enable(sg_handle* h, int32_t on);
 /* Restrict the event pairs to the stages whose bit (1 << SG_STAGE_*) is set; 0 = all stages.  Timing
  * one kernel costs two event records per step instead of ~30. */

@@ -5,6 +5,6 @@ kernels behind the C ABI in include/mi355gate.h).  Mirrors
 /root/reference/noisereduce/__init__.py:1."""
 from noisereduce_amd.noisereduce import reduce_noise  # noqa: F401
 from noisereduce_amd.batch import reduce_noise_batch  # noqa: F401
-from noisereduce_amd.stream import StreamBank, StreamGate  # noqa: F401
+from noisereduce_amd.stream import StreamBank, StreamGate, StreamState  # noqa: F401
 
-__all__ = ["reduce_noise", "reduce_noise_batch", "StreamBank", "StreamGate"]
+__all__ = ["reduce_noise", "reduce_noise_batch", "StreamBank", "StreamGate", "StreamState"]

@@ -24,6 +24,7 @@ SG_F32, SG_F64, SG_I16, SG_I32 = 0, 1, 2, 3
 SG_VARIANT_S, SG_VARIANT_T = 0, 1
 SG_E_INVALID, SG_E_UNSUPPORTED, SG_E_HIP, SG_E_NOMEM, SG_E_STATE, SG_E_HANDOFF = -1, -2, -3, -4, -5, -6
 SG_N_STAGES = 27
+SG_N_STAGES_ALL = 29      # with the state-transfer stages of stream banks (SG_STAGE_ST_EXPORT / SG_STAGE_ST_IMPORT)
 SG_OPT_FORCE_F64_DECIDE = 3
 SG_OPT_FORCE_NOSEAM = 4
 SG_OPT_FORCE_NOLEAN = 5
@@ -89,6 +90,26 @@ class SgStreamDesc(Structure):
                 ("lookahead_frames", c_int32), ("forget", c_double), ("learn_frames", c_int64), ("exact", c_int32)]
 
 
+SG_STREAM_HEAD_MAGIC, SG_STREAM_HEAD_VERSION = 0x54534753, 1
+
+
+class SgStreamHead(Structure):
+    """struct sg_stream_head (include/mi355gate.h): signature, counters and payload size of one stream's state."""
+    _fields_ = [("magic", c_int32), ("version", c_int32), ("n_fft", c_int32), ("win_length", c_int32),
+                ("hop_length", c_int32), ("channels", c_int32), ("kind", c_int32), ("n_grad_freq", c_int32),
+                ("n_grad_time", c_int32), ("smooth_mask", c_int32), ("lookahead_frames", c_int32), ("exact", c_int32),
+                ("prop_decrease", c_double), ("n_std_thresh", c_double), ("top_db", c_double), ("iir_b", c_double),
+                ("nonstat_thresh", c_double), ("nonstat_slope", c_double), ("noise_forget", c_double),
+                ("noise_learn_frames", c_int64), ("n", c_int64), ("td", c_int64), ("ts", c_int64), ("ta", c_int64),
+                ("E", c_int64), ("par", c_int32), ("has_thr", c_int32), ("payload_bytes", c_int64),
+                ("client0", c_int32), ("client1", c_int32), ("client2", c_int32), ("client3", c_int32)]
+
+
+# the fields two banks must share for a state to move between them, in the order they are compared
+STREAM_SIGNATURE = ("n_fft", "win_length", "hop_length", "channels", "kind", "n_grad_freq", "n_grad_time", "smooth_mask",
+                    "lookahead_frames", "exact", "prop_decrease", "n_std_thresh", "top_db", "iir_b", "nonstat_thresh",
+                    "nonstat_slope", "noise_forget", "noise_learn_frames")
+
 # every symbol include/mi355gate.h and include/mi355gate_debug.h declare: name -> (restype, argtypes)
 _PROTOTYPES = {
     "sg_version": (c_int, []),
@@ -140,6 +161,10 @@ _PROTOTYPES = {
     "sg_stream_state_bytes_adaptive": (c_int, [c_void_p, c_int32, c_int32, c_int64, POINTER(c_int64)]),
     "sg_stream_create_ex": (c_int, [c_void_p, POINTER(SgStreamDesc), POINTER(c_void_p)]),
     "sg_stream_state_bytes_ex": (c_int, [c_void_p, POINTER(SgStreamDesc), POINTER(c_int64)]),
+    "sg_stream_export_bytes": (c_int, [c_void_p, c_int32, POINTER(c_int64)]),
+    "sg_stream_head_bytes": (c_int, [POINTER(SgStreamHead), POINTER(c_int64)]),
+    "sg_stream_export": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, POINTER(SgStreamHead), c_void_p]),
+    "sg_stream_import": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, POINTER(SgStreamHead), c_void_p]),
     "sg_set_option": (c_int, [c_void_p, c_int32, c_int64]),
     "sg_get_option": (c_int, [c_void_p, c_int32, POINTER(c_int64)]),
     "sg_check_errors": (c_int, [c_void_p, c_void_p]),
@@ -662,6 +687,34 @@ class Gate:
         self._check(self.lib.sg_stream_counters(bank, int(slot), byref(n), byref(e)))
         return int(n.value), int(e.value)
 
+    def stream_export_bytes(self, bank, slot):
+        """Bytes of the slot's state payload right now (host arithmetic from its counters)."""
+        v = c_int64()
+        self._check(self.lib.sg_stream_export_bytes(bank, int(slot), byref(v)))
+        return int(v.value)
+
+    def stream_export(self, bank, slots, blob, offsets):
+        """blob: 1-D uint8 device tensor; slot i's payload goes to byte offsets[i] (multiples of 256).  Returns the
+        SgStreamHead of every slot.  One launch; enqueues only."""
+        self._on_device(blob)
+        sl = np.ascontiguousarray(np.asarray(slots, dtype=np.int32).reshape(-1))
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
+        heads = (SgStreamHead * max(1, sl.shape[0]))()
+        with torch.cuda.device(self.device):
+            self._check(self.lib.sg_stream_export(bank, sl.ctypes.data_as(c_void_p), int(sl.shape[0]), blob.data_ptr(),
+                                                  off.ctypes.data_as(c_void_p), heads, self._stream()))
+        return [heads[i] for i in range(sl.shape[0])]
+
+    def stream_import(self, bank, slots, blob, offsets, heads):
+        """The reverse of stream_export into `slots` of a compatible bank.  One launch; enqueues only."""
+        self._on_device(blob)
+        sl = np.ascontiguousarray(np.asarray(slots, dtype=np.int32).reshape(-1))
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
+        arr = (SgStreamHead * max(1, len(heads)))(*heads)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.sg_stream_import(bank, sl.ctypes.data_as(c_void_p), int(sl.shape[0]), blob.data_ptr(),
+                                                  off.ctypes.data_as(c_void_p), arr, self._stream()))
+
     def set_option(self, option, value):
         self._check(self.lib.sg_set_option(self._h, int(option), int(value)))
 
@@ -723,18 +776,18 @@ class Gate:
         """Time only the named stages (names as returned by profile_read); None = all."""
         mask = 0
         if stage_names:
-            names = [self.lib.sg_stage_name(i).decode() for i in range(SG_N_STAGES)]
+            names = [self.lib.sg_stage_name(i).decode() for i in range(SG_N_STAGES_ALL)]
             for n in stage_names:
                 mask |= 1 << names.index(n)
         self._check(self.lib.sg_profile_select(self._h, mask))
 
     def profile_read(self, reset=True):
         """{stage name: (total ms, launches)} accumulated since the last reset (synchronises)."""
-        ms = (c_double * SG_N_STAGES)()
-        cnt = (c_int64 * SG_N_STAGES)()
+        ms = (c_double * SG_N_STAGES_ALL)()
+        cnt = (c_int64 * SG_N_STAGES_ALL)()
         with torch.cuda.device(self.device):
-            self._check(self.lib.sg_profile_read(self._h, ms, cnt, SG_N_STAGES, int(bool(reset))))
-        return {self.lib.sg_stage_name(i).decode(): (ms[i], cnt[i]) for i in range(SG_N_STAGES)
+            self._check(self.lib.sg_profile_read(self._h, ms, cnt, SG_N_STAGES_ALL, int(bool(reset))))
+        return {self.lib.sg_stage_name(i).decode(): (ms[i], cnt[i]) for i in range(SG_N_STAGES_ALL)
                 if cnt[i]}
 
     # -- stage taps ------------------------------------------------------------------

@@ -197,8 +197,8 @@ struct sg_handle {
   struct ProfRec { int stage; hipEvent_t a, b; };
   std::vector<ProfRec> prof_live;
   std::vector<hipEvent_t> prof_pool;
-  double prof_ms[SG_N_STAGES] = {0};
-  int64_t prof_cnt[SG_N_STAGES] = {0};
+  double prof_ms[SG_N_STAGES_ALL] = {0};
+  int64_t prof_cnt[SG_N_STAGES_ALL] = {0};
   sg::RgState* rg = nullptr;        // ragged batches (sg_process_clips, ragged.hip): workspace and threshold tap
   sg::RwState* rw = nullptr;        // padded batches of different-length rows (sg_process_rows, rows.hip): workspace
   std::string err;
@@ -3420,7 +3420,8 @@ extern "C" int sg_profile_select(sg_handle* h, int64_t stage_mask) {
 
 extern "C" int sg_profile_read(sg_handle* h, double* ms, int64_t* counts, int32_t n_stages, int32_t reset) {
   if (!h) return SG_E_INVALID;
-  if (n_stages != SG_N_STAGES) FAIL(h, SG_E_INVALID, "sg_profile_read: n_stages must be %d", SG_N_STAGES);
+  if (n_stages != SG_N_STAGES && n_stages != SG_N_STAGES_ALL)
+    FAIL(h, SG_E_INVALID, "sg_profile_read: n_stages must be %d (or %d)", SG_N_STAGES, SG_N_STAGES_ALL);
   for (auto& r : h->prof_live) {
     HIPCHK(h, hipEventSynchronize(r.b));
     float t = 0.f;
@@ -3431,16 +3432,16 @@ extern "C" int sg_profile_read(sg_handle* h, double* ms, int64_t* counts, int32_
     h->prof_pool.push_back(r.b);
   }
   h->prof_live.clear();
-  for (int i = 0; i < SG_N_STAGES; ++i) {
-    if (ms) ms[i] = h->prof_ms[i];
-    if (counts) counts[i] = h->prof_cnt[i];
+  for (int i = 0; i < SG_N_STAGES_ALL; ++i) {
+    if (ms && i < n_stages) ms[i] = h->prof_ms[i];
+    if (counts && i < n_stages) counts[i] = h->prof_cnt[i];
     if (reset) { h->prof_ms[i] = 0; h->prof_cnt[i] = 0; }
   }
   return SG_OK;
 }
 
 extern "C" const char* sg_stage_name(int32_t stage) {
-  static const char* names[SG_N_STAGES] = {"k_channel_mean", "k_stft<double> (power)", "k_colmax", "k_colstats",
+  static const char* names[SG_N_STAGES_ALL] = {"k_channel_mean", "k_stft<double> (power)", "k_colmax", "k_colstats",
                                            "k_decide", "k_mag_fast* / k_stft<float> (magnitude)",
                                            "k_box_mask / k_iir_sigmoid / k_boxcar_sigmoid (non-stationary mask, other paths)",
                                            "mask smoothing (k_smooth_bits2 / k_smooth_tiled / k_smooth_f+k_smooth_t)",
@@ -3459,8 +3460,10 @@ extern "C" const char* sg_stage_name(int32_t stage) {
                                            "k_rg_iir (clips: recurrence + sigmoid)",
                                            "k_rg_fsmooth (clips: frequency smoothing)",
                                            "k_rg_apply (clips: time smoothing + mask + inverse transform)",
-                                           "k_rg_ola (clips: overlap-add)"};
-  return (stage >= 0 && stage < SG_N_STAGES) ? names[stage] : "?";
+                                           "k_rg_ola (clips: overlap-add)",
+                                           "k_st_export (stream state -> payload)",
+                                           "k_st_import (payload -> stream state)"};
+  return (stage >= 0 && stage < SG_N_STAGES_ALL) ? names[stage] : "?";
 }
 
 extern "C" int sg_debug_dims(const sg_handle* h, int64_t dims[3]) {
@@ -3853,4 +3856,36 @@ extern "C" int sg_stream_emitted(const sg_handle* h, int64_t n, int64_t* emitted
 extern "C" int sg_stream_counters(const sg_stream_bank* b, int32_t slot, int64_t* n, int64_t* emitted) {
   if (!b || !n || !emitted) return SG_E_INVALID;
   return sg::st_counters(b->b, slot, n, emitted, &b->h->err);
+}
+
+// the handle's part of a stream state's signature (the bank's part is stream.hip's)
+static sg_stream_head stream_signature(const sg_handle* h) {
+  sg_stream_head s{};
+  s.n_fft = h->p.n_fft; s.win_length = h->W; s.hop_length = h->H;
+  s.n_grad_freq = h->p.n_grad_freq; s.n_grad_time = h->p.n_grad_time; s.smooth_mask = h->p.smooth_mask ? 1 : 0;
+  s.prop_decrease = h->p.prop_decrease; s.n_std_thresh = h->p.n_std_thresh; s.top_db = h->p.top_db;
+  s.iir_b = h->p.iir_b; s.nonstat_thresh = h->p.nonstat_thresh; s.nonstat_slope = h->p.nonstat_slope;
+  return s;
+}
+
+extern "C" int sg_stream_export_bytes(const sg_stream_bank* b, int32_t slot, int64_t* bytes) {
+  if (!b || !bytes) return SG_E_INVALID;
+  return sg::st_export_bytes(b->b, slot, bytes, &b->h->err);
+}
+
+extern "C" int sg_stream_head_bytes(const sg_stream_head* head, int64_t* bytes) {
+  if (!head || !bytes) return SG_E_INVALID;
+  return sg::st_head_bytes(*head, bytes);
+}
+
+extern "C" int sg_stream_export(sg_stream_bank* b, const int32_t* slots, int32_t n_slots, void* blob_dev, const int64_t* offsets,
+                                sg_stream_head* heads_out, void* stream) {
+  if (!b) return SG_E_INVALID;
+  return sg::st_export(b->b, slots, n_slots, blob_dev, offsets, stream_signature(b->h), heads_out, (hipStream_t)stream, &b->h->err);
+}
+
+extern "C" int sg_stream_import(sg_stream_bank* b, const int32_t* slots, int32_t n_slots, const void* blob_dev,
+                                const int64_t* offsets, const sg_stream_head* heads_in, void* stream) {
+  if (!b) return SG_E_INVALID;
+  return sg::st_import(b->b, slots, n_slots, blob_dev, offsets, stream_signature(b->h), heads_in, (hipStream_t)stream, &b->h->err);
 }

@@ -25,6 +25,8 @@
 // int16 / int32 truncated toward zero, NaN -> 0.  A non-stationary exact bank also keeps the sigmoid ring mk and the
 // smoothed rows R in float64 (k_sn_decide<N, true>: the sigmoid in float64; k_st_fsmooth<true, true>); a stationary or
 // adaptive one keeps float R, which holds small integers there and is exact already.
+// State transfer (sg_stream_export / sg_stream_import) is two more kernels, k_st_export and k_st_import, outside the step: one
+// launch per call copies the live part of the listed slots' state to / from a canonical payload.
 // Nothing waits on another workgroup.  No workgroup reads state that another workgroup of the same launch writes: the
 // ring is only written by k_st_finish (which does not read it), the carry is double buffered, the bit rows of a unit are
 // written by its one decide workgroup.  One fixed evaluation order per frame and per output sample: a stream's output
@@ -35,6 +37,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 #include "tile_core.hpp"
@@ -409,6 +412,59 @@ __global__ __launch_bounds__(256) void k_st_finish(StArgs A) {
   if constexpr (EX) store_sample(A.out, A.out_dtype, U.out_off + (p - U.E0), val);
   else store_sample(A.out, A.out_dtype, U.out_off + (p - U.E0), (float)val);
 }
+
+// ---- state transfer: a slot's live state <-> a canonical payload (sg_stream_export / sg_stream_import) ------------------
+// Everything a stream keeps is 8-byte words (a float mask row is FS / 2 of them, FS being a multiple of 16), so both
+// directions are one copy kernel over a table of fields.  A field is `rows` rows of rw words that live in a ring of R rows
+// on the device, row first + i at position (first + i) % R, and lie in index order in the payload: the payload does not
+// know RB or RF, which depend on max_block.  A tile is up to XW words of one field.  Export only reads state, import only
+// writes it, and a slot appears once per call: no workgroup reads what another one of the launch writes.
+struct StXField {
+  unsigned long long* dev;   // row 0 of the ring on the device
+  int64_t blob;              // word of the payload buffer holding word 0 of the field
+  uint32_t first, R, rw, pad;   // first live row's ring position (< R), rows of the ring, words per row
+};
+struct StXArgs {
+  unsigned long long* blob;
+  const StXField* fields;
+  const Tile* tiles;
+  int64_t n_tiles;
+};
+constexpr int XW = 2048;   // words per tile: 8 per thread, all loads in flight before the first store
+
+template <bool IMPORT>
+__device__ __forceinline__ void st_copy_tile(const StXArgs& A) {
+  if ((int64_t)blockIdx.x >= A.n_tiles) return;
+  const Tile tl = A.tiles[blockIdx.x];
+  const StXField f = A.fields[tl.idx];
+  const uint32_t w0 = (uint32_t)tl.a + threadIdx.x, w1 = (uint32_t)tl.b;
+  unsigned long long* blob = A.blob + f.blob;
+  unsigned long long v[XW / 256];
+  int64_t at[XW / 256];
+#pragma unroll
+  for (int q = 0; q < XW / 256; ++q) {
+    const uint32_t w = w0 + 256u * q;
+    v[q] = 0;
+    at[q] = 0;
+    if (w < w1) {
+      const uint32_t i = w / f.rw, j = w - i * f.rw;
+      uint32_t row = f.first + i;   // (i < R: a field never holds more rows than its ring)
+      if (row >= f.R) row -= f.R;
+      at[q] = (int64_t)row * f.rw + j;
+      v[q] = IMPORT ? blob[w] : f.dev[at[q]];
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < XW / 256; ++q) {
+    const uint32_t w = w0 + 256u * q;
+    if (w < w1) {
+      if (IMPORT) f.dev[at[q]] = v[q];
+      else blob[w] = v[q];
+    }
+  }
+}
+__global__ __launch_bounds__(256) void k_st_export(StXArgs A) { st_copy_tile<false>(A); }
+__global__ __launch_bounds__(256) void k_st_import(StXArgs A) { st_copy_tile<true>(A); }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
 struct StSlot {
@@ -850,6 +906,267 @@ int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_
     return SG_E_HIP;
   }
   for (int32_t i = 0; i < n_recs; ++i) b->slots[recs[i].slot] = after[i];
+  return SG_OK;
+}
+
+// ---- state transfer ------------------------------------------------------------------------------------------------
+namespace {
+// what of a stream that has received n samples a later step can still read (every counter follows from n)
+struct StLive {
+  int64_t td, ts, ta, E;
+  int64_t ring_lo, ring_n;   // samples [ring_lo, n)
+  int64_t car_n;             // carry positions [E, E + car_n)
+  int64_t row_lo, bit_rows;  // bit rows [row_lo, td] (stationary / adaptive)
+  int64_t mk_rows;           // sigmoid rows [row_lo, ts] (non-stationary)
+  int64_t fa_rows;           // A / fwd rows (ts, td] (non-stationary)
+};
+// what the arithmetic needs of a bank -- or of a header alone (sg_stream_head_bytes)
+struct StGeo {
+  int64_t W, H, nt, L, RC, FS, wpr, C;
+  bool ns, ad, fixed, exact;
+};
+StGeo st_geo(const StBank* b) {
+  return StGeo{b->c.W, b->c.H, b->c.nt, b->L, b->RC, b->c.FS, b->wpr, b->C, b->ns != 0, b->ad != 0, b->thr != nullptr, b->exact != 0};
+}
+StGeo st_geo(const sg_stream_head& hd) {
+  StGeo g{};
+  const int64_t F = hd.n_fft / 2 + 1;
+  g.W = hd.win_length; g.H = hd.hop_length; g.C = hd.channels;
+  g.nt = hd.smooth_mask ? hd.n_grad_time : 0;
+  g.ns = hd.kind == SG_STREAM_NONSTATIONARY; g.ad = hd.kind == SG_STREAM_ADAPTIVE; g.fixed = hd.kind == SG_STREAM_FIXED;
+  g.exact = hd.exact != 0;
+  g.L = g.ns ? hd.lookahead_frames : 0;
+  g.RC = g.W + (g.nt + g.L + 1) * g.H;
+  g.FS = (F + 15) / 16 * 16;
+  g.wpr = (F + 63) / 64;
+  return g;
+}
+StLive st_live(const StGeo& g, int64_t n) {
+  const int64_t h = g.W / 2;
+  StLive v{};
+  v.td = st_tdec((int)g.W, (int)g.H, n);
+  v.ts = std::max<int64_t>(-1, v.td - g.L);
+  v.ta = std::max<int64_t>(-1, v.ts - g.nt);
+  v.E = std::max<int64_t>(0, (v.ta + 1) * g.H - h);
+  v.ring_lo = std::max<int64_t>(0, n - g.RC);
+  v.ring_n = n - v.ring_lo;
+  v.car_n = v.ta >= 0 ? std::max<int64_t>(0, v.ta * g.H - h + g.W - v.E) : 0;
+  v.row_lo = std::max<int64_t>(0, v.ta + 1 - g.nt);
+  v.bit_rows = g.ns ? 0 : v.td - v.row_lo + 1;
+  v.mk_rows = g.ns ? v.ts - v.row_lo + 1 : 0;
+  v.fa_rows = g.ns ? v.td - v.ts : 0;
+  return v;
+}
+StLive st_live(const StBank* b, int64_t n) { return st_live(st_geo(b), n); }
+// words of a float mask row / a double one
+int64_t mk_words(const StGeo& g) { return g.exact ? g.FS : g.FS / 2; }
+int64_t mk_words(const StBank* b) { return mk_words(st_geo(b)); }
+
+int64_t st_payload_words(const StGeo& g, int64_t n) {
+  const StLive v = st_live(g, n);
+  int64_t per = v.ring_n + v.car_n;
+  if (g.ns) per += g.FS + v.fa_rows * 2 * g.FS + v.mk_rows * mk_words(g);
+  else per += g.FS + v.bit_rows * g.wpr;
+  if (g.ad) per += 3 * g.FS;
+  return (g.fixed ? 2 * g.FS : 0) + g.C * per;
+}
+int64_t st_payload_words(const StBank* b, int64_t n) { return st_payload_words(st_geo(b), n); }
+
+// the fields of one slot in payload order, word 0 of the payload at `blob`; the tiles of each
+void st_fields(const StBank* b, int32_t slot, int64_t n, int par, int64_t blob, std::vector<StXField>* fields, TileList* tl) {
+  const StLive v = st_live(b, n);
+  const RgCtx& c = b->c;
+  const int64_t FS = c.FS;
+  auto field = [&](void* dev, int64_t first, int64_t R, int64_t rw, int64_t rows) {
+    if (rows > 0) {
+      fields->push_back(StXField{(unsigned long long*)dev, blob, (uint32_t)(first % R), (uint32_t)R, (uint32_t)rw, 0u});
+      tl->push_ranges((int64_t)fields->size() - 1, 0, rows * rw, XW);
+    }
+    blob += rows * rw;
+  };
+  if (b->thr) {
+    field(b->thr + (int64_t)slot * FS, 0, 1, FS, 1);
+    field(b->T2 + (int64_t)slot * FS, 0, 1, FS, 1);
+  }
+  for (int ch = 0; ch < b->C; ++ch) {
+    const int64_t u = (int64_t)slot * b->C + ch;
+    field(b->ring + u * b->RC, v.ring_lo, b->RC, 1, v.ring_n);
+    field(b->carry + (u * 2 + par) * c.W, v.E, c.W, 1, v.car_n);
+    if (b->ns) {
+      field(b->fst + u * FS, 0, 1, FS, 1);
+      field(b->fa + u * b->RF * 2 * FS, v.ts + 1, b->RF, 2 * FS, v.fa_rows);
+      field((unsigned long long*)b->mk + u * b->RB * mk_words(b), v.row_lo, b->RB, mk_words(b), v.mk_rows);
+    } else {
+      field(b->rmax + u * FS, 0, 1, FS, 1);
+      field(b->bits + u * b->RB * b->wpr, v.row_lo, b->RB, b->wpr, v.bit_rows);
+    }
+    if (b->ad) field(b->nst + u * 3 * FS, 0, 1, 3 * FS, 1);
+  }
+}
+
+void st_sign(const StBank* b, sg_stream_head* hd) {
+  hd->magic = SG_STREAM_HEAD_MAGIC;
+  hd->version = SG_STREAM_HEAD_VERSION;
+  hd->channels = b->C;
+  hd->kind = b->ad ? SG_STREAM_ADAPTIVE : b->ns ? SG_STREAM_NONSTATIONARY : SG_STREAM_FIXED;
+  hd->lookahead_frames = b->L;
+  hd->exact = b->exact;
+  hd->noise_forget = b->lam;
+  hd->noise_learn_frames = b->learn;
+}
+
+// the first signature field of `hd` that differs from the bank's (`own`), or null
+const char* st_sig_diff(const sg_stream_head& hd, const sg_stream_head& own) {
+#define SG_SIG(f) if (!(hd.f == own.f)) return #f;
+  SG_SIG(n_fft) SG_SIG(win_length) SG_SIG(hop_length) SG_SIG(channels) SG_SIG(kind) SG_SIG(n_grad_freq) SG_SIG(n_grad_time)
+  SG_SIG(smooth_mask) SG_SIG(lookahead_frames) SG_SIG(exact) SG_SIG(prop_decrease) SG_SIG(n_std_thresh) SG_SIG(top_db)
+  SG_SIG(iir_b) SG_SIG(nonstat_thresh) SG_SIG(nonstat_slope) SG_SIG(noise_forget) SG_SIG(noise_learn_frames)
+#undef SG_SIG
+  return nullptr;
+}
+
+int st_check_transfer(const StBank* b, const int32_t* slots, int32_t n, const void* blob_dev, const int64_t* offsets,
+                      const void* heads, const char* who, std::string* err) {
+  int rc = check_slots(b, slots, n, who, err);
+  if (rc) return rc;
+  char m[200];
+  if (n > 0 && (!blob_dev || !offsets || !heads || ((uintptr_t)blob_dev & 255))) {
+    *err = std::string(who) + ": blob_dev (256-byte aligned), offsets and heads are needed";
+    return SG_E_INVALID;
+  }
+  std::vector<char> seen(b->n_slots, 0);
+  for (int32_t i = 0; i < n; ++i) {
+    if (seen[slots[i]]) {
+      snprintf(m, sizeof m, "%s: slot %d appears twice in one call", who, slots[i]);
+      *err = m;
+      return SG_E_INVALID;
+    }
+    seen[slots[i]] = 1;
+    if (offsets[i] < 0 || (offsets[i] & 255)) {
+      snprintf(m, sizeof m, "%s: slot %d: payload offset %lld is not a multiple of 256", who, slots[i], (long long)offsets[i]);
+      *err = m;
+      return SG_E_INVALID;
+    }
+  }
+  return SG_OK;
+}
+
+// fields + tiles to the table buffer, then the one launch
+template <class K>
+int st_transfer(StBank* b, K kernel, int stage, void* blob_dev, const std::vector<StXField>& fields, const TileList& tl,
+                hipStream_t st, const char* who, std::string* err) {
+  const size_t fb = align256(fields.size() * sizeof(StXField)), tb = align256(tl.tiles.size() * sizeof(Tile));
+  int rc = grow_device_buffer(&b->tabs, &b->tabs_bytes, fb + tb, st, who, "table", err);
+  if (rc) return rc;
+  if (upload_tables(b->tabs, st, {{fields.data(), fields.size() * sizeof(StXField), fb},
+                                  {tl.tiles.data(), tl.tiles.size() * sizeof(Tile), tb}}) != hipSuccess) {
+    *err = std::string(who) + ": table upload failed";
+    return SG_E_HIP;
+  }
+  StXArgs A{};
+  A.blob = (unsigned long long*)blob_dev;
+  A.fields = (const StXField*)b->tabs;
+  A.tiles = (const Tile*)((char*)b->tabs + fb);
+  A.n_tiles = tl.size();
+  hipError_t e;
+  { Prof pr(b->c, stage, st); e = launch_flat_kernel(kernel, A.n_tiles, 256, st, A); }
+  if (e != hipSuccess) {
+    *err = std::string(who) + ": launch failed: " + hipGetErrorString(e);
+    return SG_E_HIP;
+  }
+  return SG_OK;
+}
+}  // namespace
+
+int st_head_bytes(const sg_stream_head& hd, int64_t* bytes) {
+  const bool ns = hd.kind == SG_STREAM_NONSTATIONARY;
+  if (hd.n < 0 || !tile_geom_ok(hd.n_fft / 2) || (hd.n_fft & 1) || hd.win_length < 2 || hd.win_length > hd.n_fft ||
+      hd.hop_length < 1 || hd.channels < 1 || hd.n_grad_time < 0 ||
+      (hd.kind != SG_STREAM_FIXED && !ns && hd.kind != SG_STREAM_ADAPTIVE) ||
+      (ns && (hd.lookahead_frames < 0 || hd.lookahead_frames > SG_STREAM_MAX_LOOKAHEAD)))
+    return SG_E_INVALID;
+  *bytes = 8 * st_payload_words(st_geo(hd), hd.n);
+  return SG_OK;
+}
+
+int st_export_bytes(const StBank* b, int32_t slot, int64_t* bytes, std::string* err) {
+  if (slot < 0 || slot >= b->n_slots) { *err = "sg_stream_export_bytes: unknown slot"; return SG_E_INVALID; }
+  *bytes = 8 * st_payload_words(b, b->slots[slot].n);
+  return SG_OK;
+}
+
+int st_export(StBank* b, const int32_t* slots, int32_t n, void* blob_dev, const int64_t* offsets, const sg_stream_head& sig,
+              sg_stream_head* heads, hipStream_t st, std::string* err) {
+  const char* who = "sg_stream_export";
+  int rc = st_check_transfer(b, slots, n, blob_dev, offsets, heads, who, err);
+  if (rc) return rc;
+  if (n == 0) return SG_OK;
+  // (payloads that overlap would make two workgroups write the same words)
+  std::vector<std::pair<int64_t, int64_t>> spans;
+  for (int32_t i = 0; i < n; ++i) spans.push_back({offsets[i], offsets[i] + 8 * st_payload_words(b, b->slots[slots[i]].n)});
+  std::sort(spans.begin(), spans.end());
+  for (size_t i = 1; i < spans.size(); ++i)
+    if (spans[i].first < spans[i - 1].second) { *err = "sg_stream_export: payloads overlap"; return SG_E_INVALID; }
+  std::vector<StXField> fields;
+  TileList tl;
+  for (int32_t i = 0; i < n; ++i) {
+    const StSlot& S = b->slots[slots[i]];
+    sg_stream_head hd = sig;
+    st_sign(b, &hd);
+    hd.n = S.n; hd.td = S.td; hd.ts = S.ts; hd.ta = S.ta; hd.E = S.E;
+    hd.par = S.par;
+    hd.has_thr = S.has_thr ? 1 : 0;
+    hd.payload_bytes = 8 * st_payload_words(b, S.n);
+    hd.client0 = hd.client1 = hd.client2 = hd.client3 = 0;
+    heads[i] = hd;
+    st_fields(b, slots[i], S.n, S.par, offsets[i] / 8, &fields, &tl);
+  }
+  return st_transfer(b, k_st_export, SG_STAGE_ST_EXPORT, blob_dev, fields, tl, st, who, err);
+}
+
+int st_import(StBank* b, const int32_t* slots, int32_t n, const void* blob_dev, const int64_t* offsets, const sg_stream_head& sig,
+              const sg_stream_head* heads, hipStream_t st, std::string* err) {
+  const char* who = "sg_stream_import";
+  int rc = st_check_transfer(b, slots, n, blob_dev, offsets, heads, who, err);
+  if (rc) return rc;
+  if (n == 0) return SG_OK;
+  char m[200];
+  sg_stream_head own = sig;
+  st_sign(b, &own);
+  for (int32_t i = 0; i < n; ++i) {
+    const sg_stream_head& hd = heads[i];
+    if (hd.magic != SG_STREAM_HEAD_MAGIC || hd.version != SG_STREAM_HEAD_VERSION) {
+      snprintf(m, sizeof m, "sg_stream_import: slot %d: not a stream state of this version (magic %#x, version %d)", slots[i],
+               (unsigned)hd.magic, hd.version);
+      *err = m;
+      return SG_E_INVALID;
+    }
+    if (const char* f = st_sig_diff(hd, own)) {
+      snprintf(m, sizeof m, "sg_stream_import: slot %d: the state comes from a different kind of bank: %s differs", slots[i], f);
+      *err = m;
+      return SG_E_INVALID;
+    }
+    // (the sizes of every write below follow from n alone; the other counters have to be the ones n gives)
+    const StLive v = hd.n >= 0 ? st_live(b, hd.n) : StLive{};
+    if (hd.n < 0 || hd.td != v.td || hd.ts != v.ts || hd.ta != v.ta || hd.E != v.E || (hd.par != 0 && hd.par != 1) ||
+        hd.payload_bytes != 8 * st_payload_words(b, hd.n)) {
+      snprintf(m, sizeof m, "sg_stream_import: slot %d: the state's counters or payload size do not fit together", slots[i]);
+      *err = m;
+      return SG_E_INVALID;
+    }
+  }
+  std::vector<StXField> fields;
+  TileList tl;
+  for (int32_t i = 0; i < n; ++i) st_fields(b, slots[i], heads[i].n, heads[i].par, offsets[i] / 8, &fields, &tl);
+  rc = st_transfer(b, k_st_import, SG_STAGE_ST_IMPORT, const_cast<void*>(blob_dev), fields, tl, st, who, err);
+  if (rc) return rc;
+  for (int32_t i = 0; i < n; ++i) {
+    const sg_stream_head& hd = heads[i];
+    StSlot& S = b->slots[slots[i]];
+    S.n = hd.n; S.td = hd.td; S.ts = hd.ts; S.ta = hd.ta; S.E = hd.E;
+    S.par = hd.par;
+    S.has_thr = b->thr ? hd.has_thr != 0 : true;
+  }
   return SG_OK;
 }
 }  // namespace sg

@@ -18,6 +18,7 @@
 // An adaptive bank (the stationary gate with the noise profile learnt from the stream itself) holds no thr / T2 but
 //   nst    [unit][3][FS]       Wn, mu, M2: weight sum, mean and weighted squared deviations of the floored dB values, float64
 // (unit = slot * channels + channel).  The counters n, t_dec, t_applied, E are host arithmetic, mirrored in the bank.
+// st_export / st_import move the live part of all this between banks of the same gate.
 //
 // The frame work of the kernels is tile_core.hpp's, shared with the clips and the rows.
 // This header is shared by api.hip (thin C wrappers) and stream.hip (tables, kernels); it holds no kernels.
@@ -65,5 +66,14 @@ int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_
             int32_t n_recs, hipStream_t st, std::string* err);
 int st_reset(StBank* b, const int32_t* slots, int32_t n, hipStream_t st, std::string* err);
 int st_counters(const StBank* b, int32_t slot, int64_t* n, int64_t* emitted, std::string* err);
+// state transfer (sg_stream_export_bytes / _export / _import): `sig` carries the handle's part of the signature (the gate's
+// parameters); the bank's part, the counters and the payload size are filled in / checked here.  One launch each.
+int st_export_bytes(const StBank* b, int32_t slot, int64_t* bytes, std::string* err);
+// the payload size a header's signature and n give: no bank, no device
+int st_head_bytes(const sg_stream_head& hd, int64_t* bytes);
+int st_export(StBank* b, const int32_t* slots, int32_t n, void* blob_dev, const int64_t* offsets, const sg_stream_head& sig,
+              sg_stream_head* heads, hipStream_t st, std::string* err);
+int st_import(StBank* b, const int32_t* slots, int32_t n, const void* blob_dev, const int64_t* offsets, const sg_stream_head& sig,
+              const sg_stream_head* heads, hipStream_t st, std::string* err);
 
 }  // namespace sg

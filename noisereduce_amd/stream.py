@@ -82,8 +82,19 @@ same stream pushed alone.  Everything else -- frames, ``emitted``, ``latency_sam
 bitwise independence of the block split, the slot and the other streams -- is unchanged; the cost is a scratch twice as wide
 and, non-stationary, mask rows of 8 bytes (``state_bytes(..., exact=True)``).
 
-Out of scope: ``TorchGate``, several GPUs, and ``n_fft`` other than a power of two from 256 to 4096 (``ValueError``).
+A stream is not tied to the bank it started in.  ``snapshot(slots)`` reads out what a stream needs to go on -- the samples
+no applied frame has covered yet, the open overlap-add sums, the mask rows later frames smooth over, the running band maxima,
+the learnt noise statistics or the forward level and the rows still ahead of the lookahead, the slot's threshold -- as a
+``StreamState``, and ``restore({slot: state})`` writes it into any slot of any bank of the same gate (same geometry, kind,
+smoothing, lookahead, precision and gate parameters; another ``n_streams``, ``max_block``, device or, through
+``to_bytes`` / ``from_bytes``, process).  The stream goes on there bit for bit as it would have without the move; restoring
+one state twice forks a stream.  One launch per call, no host synchronisation for device states.
+
+Out of scope: ``TorchGate``, collectives between GPUs (a state's bytes are the transport), and ``n_fft`` other than a power
+of two from 256 to 4096 (``ValueError``).
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -132,6 +143,69 @@ def state_bytes(n_units, n_fft, W, H, nt, L, max_block, stationary, noise_from_s
     if noise_from_stream:
         per += 3 * FS * 8
     return n_units * per
+
+
+def state_payload_bytes(n, n_fft, W, H, nt, L, channels, kind, exact=False):
+    """Bytes of one slot's ``StreamState`` payload after ``n`` samples (sg_stream_export_bytes' arithmetic; DESIGN section
+    13d's layout table).  ``kind``: "fixed", "nonstationary" or "adaptive"; ``nt``: 0 with the smoothing off.  Does not
+    depend on ``max_block``: the payload holds the live rows in index order, not the bank's rings."""
+    F = n_fft // 2 + 1
+    FS = (F + 15) // 16 * 16
+    wpr = (F + 63) // 64
+    L = L if kind == "nonstationary" else 0
+    RC = W + (nt + L + 1) * H
+    td = t_decided(n, W, H)
+    ts = max(-1, td - L)
+    ta = max(-1, ts - nt)
+    E = max(0, (ta + 1) * H - W // 2)
+    words = min(n, RC)                                                  # ring: samples [max(0, n - RC), n)
+    words += max(0, ta * H - W // 2 + W - E) if ta >= 0 else 0          # the live carry: [E, ta H - h + W)
+    row_lo = max(0, ta + 1 - nt)
+    if kind == "nonstationary":
+        words += FS                                                     # fst
+        words += (td - ts) * 2 * FS                                     # fa: frames (ts, td]
+        words += (ts - row_lo + 1) * (FS if exact else FS // 2)         # mk: frames [row_lo, ts]
+    else:
+        words += FS + (td - row_lo + 1) * wpr                           # rmax; bits: frames [row_lo, td]
+    if kind == "adaptive":
+        words += 3 * FS                                                 # nst
+    return 8 * ((2 * FS if kind == "fixed" else 0) + channels * words)  # thr, T2 once per slot
+
+
+_KINDS = ("fixed", "nonstationary", "adaptive")      # SG_STREAM_FIXED / _NONSTATIONARY / _ADAPTIVE
+_DTYPE_CODES = (np.dtype(np.float32), np.dtype(np.float64), np.dtype(np.int16), np.dtype(np.int32))   # SG_F32 ...
+_HEAD_BYTES = ctypes.sizeof(_ffi.SgStreamHead)
+
+
+class StreamState:
+    """One stream's state as ``StreamBank.snapshot`` took it: a header (``head``, an ``_ffi.SgStreamHead``: format version,
+    the signature a bank must share to take it, the stream's counters, what kind of block it was last fed with) and the
+    payload (``payload``, a uint8 tensor: a view into the snapshot's one device buffer, or host memory for a state built
+    ``from_bytes``).  ``received`` / ``emitted``: the stream's samples in and out so far."""
+
+    def __init__(self, head, payload):
+        self.head, self.payload = head, payload
+        self.received, self.emitted = int(head.n), int(head.E)
+
+    def to_bytes(self):
+        """Header + payload as self-contained bytes (synchronises and copies to the host)."""
+        return bytes(self.head) + self.payload.detach().cpu().numpy().tobytes()
+
+    @classmethod
+    def from_bytes(cls, blob):
+        blob = bytes(blob)
+        if len(blob) < _HEAD_BYTES:
+            raise ValueError(f"StreamState: {len(blob)} bytes are fewer than a header ({_HEAD_BYTES})")
+        head = _ffi.SgStreamHead.from_buffer_copy(blob[:_HEAD_BYTES])
+        if head.magic != _ffi.SG_STREAM_HEAD_MAGIC:
+            raise ValueError(f"StreamState: not a stream state (magic {head.magic & 0xffffffff:#x})")
+        if head.version != _ffi.SG_STREAM_HEAD_VERSION:
+            raise ValueError(f"StreamState: format version {head.version} (this library reads "
+                             f"{_ffi.SG_STREAM_HEAD_VERSION})")
+        if head.payload_bytes < 0 or len(blob) != _HEAD_BYTES + head.payload_bytes:
+            raise ValueError(f"StreamState: {len(blob)} bytes, the header announces {_HEAD_BYTES} + {head.payload_bytes}")
+        payload = torch.from_numpy(np.frombuffer(blob, dtype=np.uint8, offset=_HEAD_BYTES).copy())
+        return cls(head, payload)
 
 
 def _widths(sr, n_fft, H, freq_mask_smooth_hz, time_mask_smooth_ms):
@@ -487,6 +561,118 @@ class StreamBank:
         for s in slots:
             self._n[s] = self._e[s] = 0
 
+    # -- state transfer ----------------------------------------------------------------------------------------
+    def _signature(self):
+        """The fields of ``_ffi.STREAM_SIGNATURE`` as this bank has them (what sg_stream_export writes into a header)."""
+        kw = self._gate_kw
+        kind = 2 if self.noise_from_stream else 0 if self.stationary else 1
+        return dict(n_fft=self.n_fft, win_length=self.win_length, hop_length=self.hop_length, channels=self.channels,
+                    kind=kind, n_grad_freq=int(kw["n_grad_freq"]), n_grad_time=int(kw["n_grad_time"]),
+                    smooth_mask=int(bool(kw["smooth_mask"])), lookahead_frames=self.lookahead_frames, exact=int(self.exact),
+                    prop_decrease=float(kw["prop_decrease"]), n_std_thresh=float(kw["n_std_thresh"]),
+                    top_db=float(kw["top_db"]), iir_b=float(kw.get("iir_b", 0.0)),
+                    nonstat_thresh=float(kw.get("nonstat_thresh", 2.0)), nonstat_slope=float(kw.get("nonstat_slope", 10.0)),
+                    noise_forget=float(self.noise_forget), noise_learn_frames=int(self.noise_learn_frames))
+
+    def state_bytes_of(self, slot):
+        """Bytes of ``slot``'s state payload right now (host arithmetic from ``received(slot)``)."""
+        return state_payload_bytes(self._n[self._slots(slot)[0]], self.n_fft, self.win_length, self.hop_length, self.nt,
+                                   self.lookahead_frames, self.channels, _KINDS[self._signature()["kind"]], self.exact)
+
+    def snapshot(self, slots):
+        """``{slot: StreamState}`` of the listed slots, without disturbing them: one launch on the current stream, no host
+        synchronisation; the payloads are views into one uint8 device buffer.  A slot that has received nothing is valid
+        (restoring it is ``reset``, plus the slot's noise profile if it had one)."""
+        slots = self._slots(slots)
+        if len(set(slots)) != len(slots):
+            raise ValueError("StreamBank: a slot appears twice in one snapshot")
+        self._ensure()
+        sizes = [self._gate.stream_export_bytes(self._bank, s) for s in slots]
+        offsets, total = [], 0
+        for b in sizes:
+            offsets.append(total)
+            total += (b + 255) // 256 * 256
+        with torch.cuda.device(self.device):
+            blob = torch.empty(max(total, 256), dtype=torch.uint8, device=self.device)
+            heads = self._gate.stream_export(self._bank, slots, blob, offsets)
+        out = {}
+        for s, hd, off, b in zip(slots, heads, offsets, sizes):
+            tensor_io, dt, flat = self._kind[s]
+            hd.client0, hd.client1, hd.client2 = int(tensor_io), _DTYPE_CODES.index(dt), int(flat)
+            out[s] = StreamState(hd, blob[off:off + b])
+        return out
+
+    def restore(self, states):
+        """``{slot: StreamState}`` (or ``(slot, state)`` pairs): every listed slot continues the state's stream (whatever it held is dropped; its noise
+        profile is the source's).  The states may come from this bank or any bank with the same signature, whatever its
+        ``n_streams``, ``max_block``, device or slot, or from ``StreamState.from_bytes`` (uploaded here).  Every argument is
+        checked before any device work; one launch on the current stream, no host synchronisation for device states."""
+        items = []
+        for s, state in (states.items() if hasattr(states, "items") else states):      # a mapping, or (slot, state) pairs
+            s = self._slots(s)[0]
+            if not isinstance(state, StreamState):
+                raise ValueError(f"StreamBank: slot {s}: restore takes StreamState objects (got {type(state).__name__})")
+            items.append((s, state))
+        if len({s for s, _ in items}) != len(items):
+            raise ValueError("StreamBank: a slot appears twice in one restore")
+        own = self._signature()
+        for s, state in items:
+            hd = state.head
+            if hd.magic != _ffi.SG_STREAM_HEAD_MAGIC or hd.version != _ffi.SG_STREAM_HEAD_VERSION:
+                raise ValueError(f"StreamBank: slot {s}: not a stream state of format version {_ffi.SG_STREAM_HEAD_VERSION}")
+            for f in _ffi.STREAM_SIGNATURE:
+                if getattr(hd, f) != own[f]:
+                    raise ValueError(f"StreamBank: slot {s}: the state comes from a different kind of bank: {f} is "
+                                     f"{getattr(hd, f)!r} there and {own[f]!r} here")
+            td = t_decided(hd.n, self.win_length, self.hop_length)
+            ts = max(-1, td - self.lookahead_frames)
+            ta = max(-1, ts - self.nt)
+            if hd.n < 0 or (hd.td, hd.ts, hd.ta) != (td, ts, ta) or hd.par not in (0, 1) or \
+                    hd.E != emitted(hd.n, self.win_length, self.hop_length, self._lag):
+                raise ValueError(f"StreamBank: slot {s}: the state's counters do not fit together (n = {hd.n})")
+            want = state_payload_bytes(hd.n, self.n_fft, self.win_length, self.hop_length, self.nt, self.lookahead_frames,
+                                       self.channels, _KINDS[own["kind"]], self.exact)
+            if hd.payload_bytes != want or state.payload.numel() != want or state.payload.dtype != torch.uint8:
+                raise ValueError(f"StreamBank: slot {s}: the state's payload is {state.payload.numel()} bytes, its counters "
+                                 f"need {want}")
+            if not (0 <= hd.client1 < len(_DTYPE_CODES)):
+                raise ValueError(f"StreamBank: slot {s}: unknown sample type code {hd.client1} in the state")
+        if not items:
+            return
+        self._ensure()
+        with torch.cuda.device(self.device):
+            blob, offsets = self._gather([st.payload for _, st in items])
+            self._gate.stream_import(self._bank, [s for s, _ in items], blob, offsets, [st.head for _, st in items])
+        for s, state in items:
+            hd = state.head
+            self._n[s], self._e[s] = int(hd.n), int(hd.E)
+            self._has_noise[s] = bool(hd.has_thr) or not self.stationary or self.noise_from_stream
+            self._kind[s] = (bool(hd.client0), _DTYPE_CODES[hd.client1], bool(hd.client2))
+
+    def _gather(self, payloads):
+        """(a uint8 tensor on the bank's device, byte offset of every payload from its first byte).  Contiguous payloads on
+        this device at 256-byte aligned addresses (a snapshot's views) are read where they lie, offsets counted from the
+        lowest one; anything else -- host states, other devices -- is packed into a new buffer, host states through one
+        pinned upload."""
+        if all(p.device == self.device and p.is_contiguous() and p.data_ptr() % 256 == 0 for p in payloads):
+            first = min(payloads, key=lambda p: p.data_ptr())
+            return first, [p.data_ptr() - first.data_ptr() for p in payloads]
+        offsets, total = [], 0
+        for p in payloads:
+            offsets.append(total)
+            total += (p.numel() + 255) // 256 * 256
+        blob = torch.empty(max(total, 256), dtype=torch.uint8, device=self.device)
+        host = [(o, p) for o, p in zip(offsets, payloads) if p.device.type == "cpu"]
+        if len(host) == len(payloads):
+            stage = torch.empty(max(total, 256), dtype=torch.uint8, pin_memory=True)
+            for o, p in host:
+                stage[o:o + p.numel()] = p
+            blob.copy_(stage, non_blocking=True)
+            return blob, offsets
+        for o, p in zip(offsets, payloads):
+            blob[o:o + p.numel()].copy_(p, non_blocking=True)
+        return blob, offsets
+
 
 class StreamGate:
     """One stream: ``push(block) -> out``, ``flush() -> tail`` (a ``StreamBank`` of one slot; same arguments,
@@ -507,6 +693,14 @@ class StreamGate:
 
     def noise_profile(self):
         return self.bank.noise_profile(0)
+
+    def snapshot(self):
+        """The stream's ``StreamState`` (``StreamBank.snapshot``)."""
+        return self.bank.snapshot([0])[0]
+
+    def restore(self, state):
+        """Continue ``state``'s stream here (``StreamBank.restore``)."""
+        self.bank.restore({0: state})
 
     def close(self):
         self.bank.close()
