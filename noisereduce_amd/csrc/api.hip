@@ -126,6 +126,7 @@ struct sg_handle {
   DevBuf seam;                       // partial seam hops of abutting apply tiles
   DevBuf ftab;                       // k_smooth_bits2 phase-1 lookup tables (nf <= 5)
   int sm2_tt = 64;                   // k_smooth_bits2 tile height (frames)
+  bool t_sm2_ok = true;              // variant T: the smoothing filter's tile of k_smooth_bits2 fits the LDS (sg_process_batch's bit-mask route)
   // one-pass gate (onepass.hpp): published mask bits per tile, publication flags, work counter, tables
   DevBuf xbits, xpart, xticket, xtick2, ftab3, xexp, optab;
   DevBuf xin;                        // float32 copy of a recording held in another sample dtype
@@ -331,6 +332,7 @@ struct ProfScope {
     hipError_t e_ = (call);                                                                  \
     if (e_ != hipSuccess) {                                                                  \
       (h)->err = fmt("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
+      (void)hipGetLastError(); /* reported here: not once more by the next launch check of any handle */ \
       return SG_E_HIP;                                                                       \
     }                                                                                        \
   } while (0)
@@ -1088,18 +1090,28 @@ extern "C" int sg_create(const sg_params* p, const double* window_host, sg_handl
     h->mr_ok = !pow2 && !bigf && n % 2 == 0 && n >= 8 && mr_make_plan(n / 2, &h->mr) && getenv("SG_NO_MIXED_RADIX") == nullptr;
     h->fused_ok = p->variant == SG_VARIANT_S && p->stationary && h->ktot <= 65535 && (pow2 || h->mr_ok) && n <= 4096 &&
                   (!p->smooth_mask || p->n_grad_time <= 96);
-    if (h->fused_ok && p->smooth_mask) {
-      // the integer smoothing kernel holds (tt + 2 nt) rows of all F bins in LDS: 64-frame tiles, lower ones for long rows
+    // the integer smoothing kernel holds (tt + 2 nt) rows of all F bins in LDS: 64-frame tiles, lower ones for long rows
+    // and wide time smoothing; returns the bytes of the tile it settled on
+    auto fit_sm2_tile = [&](int tt_max) {
       const int wpr = (h->F + 63) / 64;
       const bool small = (p->n_grad_freq + 1) * (p->n_grad_freq + 1) <= 255;
       size_t lds = 0;
-      for (h->sm2_tt = smooth2_tt_max(h->F); h->sm2_tt >= 16; h->sm2_tt >>= 1) {
+      for (h->sm2_tt = tt_max; h->sm2_tt >= 16; h->sm2_tt >>= 1) {
         const int rows = h->sm2_tt + 2 * p->n_grad_time;
         lds = smooth2_cf_bytes(rows + 2, h->F, small ? 1 : 2) + (size_t)rows * (wpr + 2) * 8 + 8192;
         if (lds <= 150 * 1024) break;
       }
-      if (lds > 150 * 1024 || p->n_grad_freq > 30) h->fused_ok = false;
+      return lds;
+    };
+    if (h->fused_ok && p->smooth_mask) {
+      if (fit_sm2_tile(smooth2_tt_max(h->F)) > 150 * 1024 || p->n_grad_freq > 30) h->fused_ok = false;
     }
+    // variant T's bit-mask route (sg_process_batch) smooths with the same kernel and used to launch it with 64-frame tiles
+    // whatever the filter: from n_grad_time = 82 on (n_fft = 1024) the tile exceeds the LDS and the call failed.  The same
+    // search, from the 64 frames it always ran with; a filter no tile fits keeps the float smoothing kernels.
+    if (p->variant == SG_VARIANT_T && p->stationary && p->smooth_mask && p->n_grad_freq <= 30 && h->ktot <= 65535 &&
+        p->n_grad_time <= 96)
+      h->t_sm2_ok = fit_sm2_tile(SM2_TT) <= 150 * 1024;
   }
   // window embedded in an n_fft frame: scipy zero-pads the windowed frame at the END
   // (scipy/_spectral_py.py:2202) and extends the signal by W//2; torch centres the window
@@ -3177,7 +3189,7 @@ extern "C" int sg_process_batch(sg_handle* h, const void* x_dev, int dtype, int6
       // default geometry, full reduction: decisions as bits -> exact integer smoothing -> uint16 sums
       // read by the fused apply kernel (same stages as the variant-S fused path)
       const bool bits_path = h->fast_ok && !h->force_nofast && !h->force_unfused && h->p.prop_decrease == 1.0 &&
-                             h->ktot <= 65535 && (!h->p.smooth_mask || h->p.n_grad_time <= 96);
+                             h->ktot <= 65535 && (!h->p.smooth_mask || (h->p.n_grad_time <= 96 && h->t_sm2_ok));
       // short rows: statistics + constants + decisions of a (row, 64 bands) tile in one kernel
       const size_t tile_bytes = (size_t)g.T * 64 * sizeof(double);
       const bool row_fused = bits_path && tile_bytes <= 64 * 1024;

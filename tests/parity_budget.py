@@ -20,7 +20,10 @@ helpers here hold a kernel to the float64 oracle per stage and per hop block ins
                        further down;
 * ``F_CELLS`` / ``floor_gate_case`` / ``S_CLIPS`` / ``floor_stats_case``   the -80 dB floor band by band: gate inputs with
                        a few lifted bands per unit and one band +g / -g dB from its switch, and noise clips that reach
-                       every branch of the single-pass statistics, at the end of the module.
+                       every branch of the single-pass statistics;
+* ``R_CELLS`` / ``r_case`` / ``r_oracle`` / ``r_budget``   the routes of TorchGate.forward without lengths= (rows per unit batch,
+                       frames per row, noise rows, unit batches) on rows that all differ from each other, at the end of the
+                       module.
 
 Where the numbers come from (none is taken from the code under test):
 
@@ -1812,3 +1815,239 @@ def stats_clip_slices(clip):
 def amp_db_bits(unit, thresh):
     """The decision bits of a stationary unit under another threshold (F,)."""
     return O.amp_to_db(unit["Z"], 80.0) > np.asarray(thresh)[:, None]
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# the route matrix of TorchGate.forward without lengths= (csrc/api.hip: sg_process_batch), shared by
+# tests/test_torchgate_routes_host.py (conditions on the oracle, planted defects) and tests/test_gpu_torchgate_routes.py
+# ----------------------------------------------------------------------------------------------------------------
+# sg_process_batch picks its kernels from the rows of a unit batch (below 16 / from 16 on), the frames of a row (up to
+# 64 with 160 rows: the row gate; up to 128: k_row_decide; beyond: k_t2_rows + k_decide_bits_t2), where the thresholds
+# come from (the rows, one noise row, one noise row per row) and the number of unit batches the workspace budget allows.
+# T_CELLS above never varies any of them.  Every row of an R cell differs from every other row in level, colour, tone and
+# (some) in floor and DC / Nyquist content, so that a threshold, band maximum or mask taken from another row or another
+# batch changes hundreds of decisions (tests/test_torchgate_routes_host.py holds that).
+#
+# ``batches``: the rows per unit batch the cell means to run in; a cell with more than one gets a workspace budget
+# (``r_budget``) and the GPU test asserts the split from what the handle reports, not from the budget.
+# ``route``: what decides -- row_gate (k_row_gate), row_decide (k_row_decide: statistics + constants + bits of a tile),
+# t2 (k_t2_rows + k_decide_bits_t2), float (k_decide, float raw mask + float smoothing), box (k_box_mask), ns_raw
+# (k_boxcar_sigmoid + the general smoothing kernels).  ``apply``: fast (k_apply_fast), reg (a register geometry's apply
+# kernel), ola (k_apply_istft + k_ola).  ``xn``: None, "one" (one noise row: ustride = 0), "rows" (a noise row per row:
+# ustride = FS, vn.unit0 = u0 per batch), ``xnT`` its frames.
+# (nt96 / wide-nt: 241 frames, not 240 -- 4 rows of 240 frames get 15 statistics slices, and 240 is a multiple of 15.
+# nt96 is wide-nt's other side: the widest time smoothing that stays on the bit-mask path.  Both switch the frequency
+# smoothing off: with the default 500 Hz, (nf + 1)^2 (nt + 1)^2 exceeds 65535 and the path is left through ktot instead.)
+R_SR = 16000
+_NT97_MS = 97.02 * 256 / R_SR * 1000       # time_mask_smooth_ms of n_grad_time = 97 at hop 256
+_NT96_MS = 96.02 * 256 / R_SR * 1000
+
+
+def _r(name, n_fft, B, T, route, apply="fast", xn=None, xnT=None, batches=None, kw=None, **more):
+    return dict(name=name, n_fft=n_fft, B=B, T=T, route=route, apply=apply, xn=xn, xnT=xnT,
+                batches=list(batches) if batches else [B], kw=dict(kw or {}), **more)
+
+
+R_CELLS = [
+    _r("t128", 1024, 5, 128, "row_decide"),
+    _r("t129", 1024, 5, 129, "t2"),
+    _r("b15", 1024, 15, 150, "t2"),
+    _r("b16", 1024, 16, 150, "t2"),
+    _r("b16-nofast", 1024, 16, 150, "float", apply="ola", nofast=True),
+    _r("xnB-15", 1024, 15, 100, "row_decide", xn="rows", xnT=41),
+    _r("xnB-16", 1024, 16, 100, "row_decide", xn="rows", xnT=41),
+    _r("xnB-long", 1024, 17, 200, "t2", xn="rows", xnT=260),
+    _r("xn1-long", 1024, 6, 200, "t2", xn="one", xnT=260),
+    _r("split", 1024, 37, 129, "t2", batches=(16, 16, 5)),
+    _r("split-xnB", 1024, 37, 100, "row_decide", xn="rows", xnT=41, batches=(16, 16, 5)),
+    _r("split-rowgate", 1024, 200, 64, "row_gate", batches=(80, 80, 40)),
+    _r("rg-64", 1024, 160, 64, "row_gate"),
+    _r("rg-65", 1024, 160, 65, "row_decide"),
+    _r("rg-159", 1024, 159, 64, "row_decide"),
+    _r("prop07", 1024, 16, 150, "float", kw=dict(prop_decrease=0.7)),
+    _r("nt96", 1024, 4, 241, "t2", kw=dict(freq_mask_smooth_hz=None, time_mask_smooth_ms=_NT96_MS)),
+    _r("wide-nt", 1024, 4, 241, "float", kw=dict(freq_mask_smooth_hz=None, time_mask_smooth_ms=_NT97_MS)),
+    _r("n512", 512, 16, 150, "float", apply="reg"),
+    _r("n2048", 2048, 16, 150, "float", apply="reg",
+       kw=dict(freq_mask_smooth_hz=3.02 * R_SR / 1024, time_mask_smooth_ms=2.02 * 512 / R_SR * 1000)),
+    _r("n512-win", 512, 5, 150, "float", apply="ola", xn="one", xnT=77, kw=dict(win_length=400, hop_length=101)),
+    _r("n400", 400, 17, 140, "float", apply="ola", xn="rows", xnT=61,
+       kw=dict(freq_mask_smooth_hz=3.02 * R_SR / 200, time_mask_smooth_ms=2.02 * 100 / R_SR * 1000)),
+    _r("f64", 1024, 16, 129, "t2", dtype="float64"),
+    _r("ns-box", 1024, 20, 150, "box", batches=(8, 8, 4), kw=dict(nonstationary=True)),
+    _r("ns-raw", 1024, 20, 150, "ns_raw", batches=(8, 8, 4),
+       kw=dict(nonstationary=True, n_movemean_nonstationary=7)),
+]
+R_FLOOR_EVERY = 4            # rows b with b % 4 == 3: second half 60 dB down, plus a steady hum that keeps its bands unlifted
+R_DCNY_ROWS = (1, 2)         # rows with DC + Nyquist content (signals.dc_nyquist's)
+_R_RESEED = {}               # name -> seed offset (tests/test_torchgate_routes_host.py holds the conditions a seed must meet)
+
+
+def r_cell_id(c):
+    return c["name"]
+
+
+def r_cell(name):
+    return next(c for c in R_CELLS if c["name"] == name)
+
+
+def r_geometry(c):
+    """(n_fft, W, H) of a route cell."""
+    return O.resolve_stft_params(c["n_fft"], c["kw"].get("win_length"), c["kw"].get("hop_length"))
+
+
+def _one_pole(rng, n, pole):
+    """Unit-variance noise through y[i] = pole y[i - 1] + w[i]."""
+    import scipy.signal
+    w = rng.standard_normal(n + 64)
+    return scipy.signal.lfilter([1.0], [1.0, -pole], w)[64:] * np.sqrt(1.0 - pole * pole)
+
+
+def r_row_pole(b):
+    """Row b's colour: low-pass and high-pass alternate, the pole's size walks over 17 values."""
+    return (1.0 if b % 2 == 0 else -1.0) * (0.1 + 0.8 * ((5 * b) % 17) / 17.0)
+
+
+def r_row_level(b):
+    """Row b's level: 3 dB steps over 24 dB."""
+    return 10.0 ** (-3.0 * (b % 9) / 20.0)
+
+
+def route_rows(B, L, seed, sr=R_SR):
+    """(B, L) float32: row b = 0.1 x level_b x one-pole noise (pole_b) + a 0.5 x level_b tone of its own frequency that is
+    on for 30 % of the row from a row-dependent sample on.  Rows b % 4 == 3: everything after L / 2 scaled by 1e-3, plus a
+    steady 0.05 x level_b hum at a quarter of the sampling rate (its bands stay within 40 dB of their maximum, every other
+    band of the row is lifted by the floor).  Rows 1 and 2: + 0.01 DC + 0.02 (-1)^n, scaled by the row's level."""
+    i = np.arange(L, dtype=np.float64)
+    x = np.empty((B, L), dtype=F32)
+    for b in range(B):
+        rng = np.random.default_rng(seed + 101 * b)
+        lev = r_row_level(b)
+        hz = sr * (0.05 + 0.4 * ((7 * b + 3) % 31) / 31.0) + 3.7 * b
+        on = int(L * (0.15 + 0.5 * ((3 * b) % 11) / 11.0))
+        y = 0.1 * _one_pole(rng, L, r_row_pole(b))
+        y[on:on + (3 * L) // 10] += 0.5 * np.sin(2 * np.pi * hz * i[on:on + (3 * L) // 10] / sr)
+        y *= lev
+        if b % R_FLOOR_EVERY == R_FLOOR_EVERY - 1:
+            y[L // 2:] *= 1e-3
+            y += 0.05 * lev * np.sin(2 * np.pi * (0.25 * sr + 7.3) * i / sr)
+        if b in R_DCNY_ROWS:
+            y += lev * (0.01 + 0.02 * (1.0 - 2.0 * (np.arange(L) % 2)))
+        x[b] = y.astype(F32)
+    return x
+
+
+def route_noise(Bn, Ln, seed):
+    """(Bn, Ln) float32 noise rows, no tone.  Bn > 1: row b coloured and levelled like row b of ``route_rows``, 6 dB under
+    its noise.  Bn == 1: nearly white (pole 0.1) at -14 dB of row 0's noise, the middle of the rows' 24 dB of levels, so
+    that the loudest row is not all-pass and the quietest not all-gated."""
+    xn = np.empty((Bn, Ln), dtype=F32)
+    for b in range(Bn):
+        rng = np.random.default_rng(seed + 7919 + 101 * b)
+        if Bn == 1:
+            xn[b] = (0.1 * 10.0 ** (-14.0 / 20.0) * _one_pole(rng, Ln, 0.1)).astype(F32)
+        else:
+            xn[b] = (0.05 * r_row_level(b) * _one_pole(rng, Ln, r_row_pole(b))).astype(F32)
+    return xn
+
+
+@functools.lru_cache(maxsize=None)
+def _r_case(name):
+    c = r_cell(name)
+    n_fft, W, H = r_geometry(c)
+    L = (c["T"] - 1) * H + 13
+    seed = 4000 + 37 * [d["name"] for d in R_CELLS].index(name) + _R_RESEED.get(name, 0)
+    x = route_rows(c["B"], L, seed)
+    xn = None
+    if c["xn"]:
+        xn = route_noise(c["B"] if c["xn"] == "rows" else 1, (c["xnT"] - 1) * H + 13, seed)
+    kw = dict(c["kw"], n_fft=n_fft)
+    return dict(cell=c, x=x, xn=xn, kw=kw, L=L, W=W, H=H, dtype=c.get("dtype", "float32"),
+                stationary=not kw.get("nonstationary", False))
+
+
+def r_case(c):
+    """Inputs of a route cell: ``x`` (B, L) and ``xn`` (None, (1, Ln) or (B, Ln)), float32-valued; ``kw`` for TorchGate /
+    ``torchgate_units`` (sr = R_SR); ``dtype`` what the call is given."""
+    return _r_case(c["name"])
+
+
+@functools.lru_cache(maxsize=3)
+def _r_oracle(name):
+    case = _r_case(name)
+    xn = None if case["xn"] is None else case["xn"].astype(np.float64)
+    return torchgate_units(case["x"].astype(np.float64), R_SR, xn=xn, window=tile_window(case["W"]), **case["kw"])[1]
+
+
+def r_oracle(c):
+    """The oracle's units of a route cell, one per row."""
+    return _r_oracle(c["name"])
+
+
+def r_unit_bytes(n_fft, T):
+    """Workspace bytes of one unit of T frames as csrc/api.hip's ``unit_bytes`` (not lean) has them; the expressions are
+    checked against the source."""
+    import os
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "noisereduce_amd", "csrc")
+    with open(os.path.join(csrc, "api.hip")) as f:
+        api = f.read()
+    with open(os.path.join(csrc, "nonstat_mask.hpp")) as f:
+        ns = f.read()
+    assert "return cells * (8 + 4 + 4 + 2) + (size_t)g.T * g.n * 4 + (size_t)g.FS * 16 +" in api
+    assert "(size_t)(g.T / NS_TT + 1) * 2 * g.FS * 8 * 2 +" in api
+    assert "(size_t)(g.T / 8 + 1) * 2 * g.FS * 8;" in api
+    assert "int64_t ub = ws_budget(h) / (int64_t)unit_bytes(h, g, lean);" in api
+    assert "constexpr int NS_TT = 64;" in ns
+    FS = (n_fft // 2 + 1 + 15) // 16 * 16
+    cells = T * FS
+    return cells * 18 + T * n_fft * 4 + FS * 16 + (T // 64 + 1) * 2 * FS * 8 * 2 + (T // 8 + 1) * 2 * FS * 8
+
+
+def r_budget(c):
+    """``max_workspace_bytes`` for the cell's split (0: the default budget, one batch): room for batches[0] units of the
+    larger of the two geometries (rows, noise rows) and half a unit more."""
+    if len(c["batches"]) == 1:
+        return 0
+    per = r_unit_bytes(c["n_fft"], max(c["T"], c["xnT"] or 0))
+    return per * c["batches"][0] + per // 2
+
+
+def r_stat_slices(c, T, nb, single_pass):
+    """Slice count of the column statistics over a batch of nb units of T frames (api.hip: stat_slices; stage_stats for
+    the single-pass kernels), re-derived from the sources as ``engine_stats_constants`` does."""
+    fps, smax, maxs, tg = engine_stats_constants()
+    blocks = ((c["n_fft"] // 2 + 1 + 63) // 64) * nb
+    nts = max(1, min(-(-2048 // blocks), smax, max(1, T // 16)))
+    if single_pass:
+        nts = max(1, min(nts, tg * maxs, T // fps))
+    return nts
+
+
+def r_stats_launches(c):
+    """[(what, T, nb, single_pass)] of a stationary cell: every launch of the column statistics / column maxima that slices
+    the frames (sg_process_batch: stage_stats on the noise, stage_power's k_colmax below 16 rows and stage_colstats on
+    the rows where k_row_decide and k_row_gate do not take them)."""
+    out = []
+    if c["xn"] == "one":
+        out.append(("noise", c["xnT"], 1, True))
+    for nb in c["batches"]:
+        if c["xn"] == "rows":
+            out.append(("noise", c["xnT"], nb, nb < 16))
+        if c["route"] in ("t2", "float"):
+            out.append(("rows", c["T"], nb, False))
+    return out
+
+
+def torchgate_gate_kwargs(tg, **extra):
+    """Keyword arguments of ``_ffi.Gate`` for the handle a TorchGate module creates (torchgate.py: _gate_for), for tests
+    that need a handle of their own (a workspace budget)."""
+    import torch
+    from noisereduce_amd import _ffi
+    nf, nt = tg._n_grad
+    kw = dict(variant=_ffi.SG_VARIANT_T, stationary=not tg.nonstationary, n_fft=tg.n_fft, win_length=tg.win_length,
+              hop_length=tg.hop_length, n_grad_freq=nf, n_grad_time=nt, smooth_mask=tg.smoothing_filter is not None,
+              prop_decrease=tg.prop_decrease, n_std_thresh=tg.n_std_thresh_stationary, top_db=40.0, ddof=1,
+              n_movemean=tg.n_movemean_nonstationary, nonstat_thresh=tg.n_thresh_nonstationary,
+              nonstat_slope=1.0 / tg.temp_coeff_nonstationary, window=torch.hann_window(tg.win_length).double().numpy())
+    kw.update(extra)
+    return kw

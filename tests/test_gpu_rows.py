@@ -15,6 +15,7 @@ if ROOT not in sys.path:
 
 from oracle import spectralgate_oracle as O  # noqa: E402
 from oracle.torchgate_torch_port import torchgate_cpu  # noqa: E402
+from tests.parity_budget import torchgate_gate_kwargs as _gate_kwargs  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 SR = 16000
@@ -232,18 +233,6 @@ def test_rows_are_independent(kw):
     keep = [i for i in range(len(lens)) if i != 2]
     assert torch.equal(yb[keep], y[keep])
     assert bool(torch.isnan(yb[2]).any())
-
-
-def _gate_kwargs(tg, **extra):
-    from noisereduce_amd import _ffi
-    nf, nt = tg._n_grad
-    kw = dict(variant=_ffi.SG_VARIANT_T, stationary=not tg.nonstationary, n_fft=tg.n_fft, win_length=tg.win_length,
-              hop_length=tg.hop_length, n_grad_freq=nf, n_grad_time=nt, smooth_mask=tg.smoothing_filter is not None,
-              prop_decrease=tg.prop_decrease, n_std_thresh=tg.n_std_thresh_stationary, top_db=40.0, ddof=1,
-              n_movemean=tg.n_movemean_nonstationary, nonstat_thresh=tg.n_thresh_nonstationary,
-              nonstat_slope=1.0 / tg.temp_coeff_nonstationary, window=torch.hann_window(tg.win_length).double().numpy())
-    kw.update(extra)
-    return kw
 
 
 @pytest.mark.parametrize("kw", [dict(), dict(nonstationary=True), dict(n_fft=512)])

@@ -1,6 +1,7 @@
 """TorchGate rows of 10 minutes (2 x 28.8 M samples, 112 k frames per row: k_colmax / k_colstats statistics instead of the
 one-kernel row statistics, 1758 time tiles of k_box_mask) and a 16-channel reduce_noise of 5-minute channels on the
-float64 pipeline for int16 samples, against the oracle.  usage: python tests/tools/long_rows_check.py"""
+float64 pipeline for int16 samples, against the oracle.  usage: python tests/tools/long_rows_check.py
+(The suite holds this route at small size: R_CELLS t129, b15, b16, split and ns-box of tests/test_gpu_torchgate_routes.py.)"""
 import os, sys, time, numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import noisereduce_amd as nr
