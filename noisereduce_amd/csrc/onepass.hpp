@@ -178,6 +178,14 @@ __device__ __forceinline__ double op_exact_power(const OnePassArgs& P, int64_t r
   return re * re + im * im;
 }
 
+// the quiet NaN of a lost hand-off, made where it is needed (cold): as a plain constant it is hoisted out of the persistent
+// tile loop into a register of its own, which then lives in scratch
+__device__ __forceinline__ unsigned op_nan_bits() {
+  unsigned v = 0x7fc00000u;
+  asm volatile("" : "+v"(v));
+  return v;
+}
+
 // OP_ABLATE (development only, default 0; results are wrong): 1 no decision stage, 2 no wait for the
 // neighbours' flags, 8 no exact refinement, 16 no wait for the previous tile's trailing hops
 #ifndef OP_ABLATE
@@ -227,6 +235,18 @@ __device__ __forceinline__ double op_exact_power(const OnePassArgs& P, int64_t r
 // Deadlock freedom as before (tickets; publish before wait); a launch needs two resident workgroups, and draws
 // total_tiles + gridDim.x tickets (every workgroup ends on one ticket >= total_tiles).
 // Not for REDO / LOSE / a-priori floor flags (compare constants depend on the unit there) / SG_OPT_TILE_ORDER 1.
+// DEFERRED SEAM (OP_DEFER_SEAM, PERSIST only).  An interior (tile_fast) tile j used to end by polling for tile j - 1's three
+// trailing partial hops.  Tile j - 1 runs in near lockstep and publishes them in its own last phase, so tile j always paid a
+// write-through plus a read round trip with nothing left to hide it behind (phase 13 of the trace).  Now tile j publishes its
+// trailing partials as before but leaves its three LEADING hops open: waves 0 - 2 write their un-normalised partial sums where
+// the finished samples will go (one float4 per lane; the same lane reads them back -- four loop-carried registers were 19
+// spilled ones in a kernel that sits at its 168) and thread 0 notes the tile's ticket and poison bit in s_misc[0].  One tile
+// later the workgroup loads them and tile j - 1's granules before the overlap-add's closing barrier -- published a whole
+// tile ago -- and finishes the hops in that iteration's epilogue: previous trailing + own leading, poison, normalise, store, the same sums
+// in the same order.  A tag that is still not current falls back to the bounded poll (OP_SPIN_MAX, NaN, error word).  An
+// open seam is closed on the spot before the workgroup leaves, in a halo tile's early exit, and in the epilogue of a tile
+// that is not tile_fast (those keep the immediate protocol for their own hops).  Deadlock freedom: a seam waits for a tile
+// with a LOWER ticket than any this workgroup has held since, and publishing never waits.
 #ifndef OP_LATE_P
 #define OP_LATE_P 1   // 1: every instantiation reads its arguments through late_args() (0 SGPR spills; 0: the by-value struct outside PERSIST)
 #endif
@@ -234,6 +254,10 @@ __device__ __forceinline__ double op_exact_power(const OnePassArgs& P, int64_t r
 #define OP_OCC 3   // workgroups per CU the register budget is set for (development builds: 2 shows the unconstrained pressure)
 #endif
 #define OP_DONE { if (PERSIST) continue; return; }
+#ifndef OP_DEFER_SEAM
+#define OP_DEFER_SEAM 1   // 1: PERSIST instantiations finish a tile_fast tile's leading hops one tile late (0: the immediate poll, A/B builds)
+#endif
+constexpr unsigned OP_SEAM_NONE = 0xffffffffu;   // s_misc[0] (PERSIST): ticket | poison << 31 of the tile whose leading hops are open
 template <int WAVES, bool PROP, bool LOSE = false, bool REDO = false, bool PERSIST = false>
 __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs Pk) {
   static_assert(WAVES == 4, "tile = 16 frames");
@@ -289,6 +313,7 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
       // (ticket_base == 0xffffffff: SG_OPT_TILE_ORDER 1, the block index instead of a ticket)
       s_misc[PERSIST ? 4 : 0] = Pk.ticket_base == 0xffffffffu ? blockIdx.x : atomicAdd(Pk.ticket, 1u) - Pk.ticket_base;
       s_misc[1] = 0u;   // set when a hand-off of this tile is lost: its output hops are POISONED (NaN), never plausible garbage
+      if (PERSIST) s_misc[0] = OP_SEAM_NONE;
     }
     tw512[tid] = tw_a;
     tw512[tid + 256] = tw_b;
@@ -365,6 +390,85 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
   float q[NQ];
   float sc[SCAN_REG];
   bool pf = false;
+  constexpr bool DEFER = PERSIST && OP_DEFER_SEAM;
+  // where the open seam of tile `pend` lives: the previous tile's trailing granules of hop `wv`, the output samples
+  auto seam_where = [](unsigned pend, const unsigned long long*& src, float*& dst) {
+    typedef const __attribute__((address_space(4))) char* kq_t;
+    kq_t kq = (kq_t)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(kq));
+#define OP_QARG(type, member) (*(const __attribute__((address_space(4))) type*)(kq + __builtin_offsetof(OnePassArgs, member)))
+    const unsigned tk = pend & 0x7fffffffu;
+    const unsigned ntl = (unsigned)OP_QARG(int, A.n_tiles), nttq = ntl + 2u;
+    const unsigned uq = tk / nttq;
+    const int jq = (int)(tk % nttq) - 1;
+    const unsigned guq = (unsigned)(OP_QARG(int64_t, A.view.unit0) + uq), nchq = (unsigned)OP_QARG(int32_t, A.view.n_chunks);
+    const int64_t rowq = guq / nchq, chunkq = OP_QARG(int64_t, A.view.c0) + guq % nchq;
+    const int64_t tfq = OP_QARG(int64_t, A.h_begin) - 3 + (int64_t)jq * NF;
+    const int64_t pb0 = tfq * 256 - OP_QARG(int32_t, A.g.padL);
+    const int64_t gi00 = chunkq * OP_QARG(int64_t, A.om.g_step) + (pb0 - OP_QARG(int64_t, A.om.p0));
+    // (the tile's part is wave-uniform: two scalar registers each, the lane's offset is added where it is used)
+    auto uni = [](const void* p_) -> char* {
+      const unsigned long long v_ = (unsigned long long)(uintptr_t)p_;
+      return (char*)(uintptr_t)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(v_ >> 32)) << 32) |
+                                (unsigned)__builtin_amdgcn_readfirstlane((int)v_));
+    };
+    dst = (float*)uni((float*)(uintptr_t)OP_QARG(unsigned long long, A.om.out) +
+                      (rowq * OP_QARG(int64_t, A.om.stride) + gi00 - OP_QARG(int64_t, A.om.g0)));
+    src = (const unsigned long long*)uni((const unsigned long long*)(uintptr_t)OP_QARG(unsigned long long, part2) +
+                                         ((size_t)uq * ntl + jq - 1) * 3 * 256);
+  };
+  auto seam_off = [](int wv, int s4_) -> int { return wv * 256 + s4_; };   // a lane's four samples of hop `wv`
+  // previous trailing + own leading, poison, normalise, store: the tail of the tile_fast epilogue.  g4 = the four granules
+  // as loaded (a tag that is not current yet: the bounded poll)
+  auto seam_finish = [&](unsigned pend, int wv, int s4_, unsigned long long g0_, unsigned long long g1_, unsigned long long g2_,
+                        unsigned long long g3_, float* dst, float4 ld, float4 nrm) {
+    op_v4u ga = {(unsigned)g0_, (unsigned)(g0_ >> 32), (unsigned)g1_, (unsigned)(g1_ >> 32)};
+    op_v4u gb = {(unsigned)g2_, (unsigned)(g2_ >> 32), (unsigned)g3_, (unsigned)(g3_ >> 32)};
+    typedef const __attribute__((address_space(4))) char* kq_t;
+    kq_t kq = (kq_t)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(kq));
+    const unsigned e = OP_QARG(unsigned, epoch);
+    if (!(ga[1] == e && ga[3] == e && gb[1] == e && gb[3] == e)) {   // (cold)
+      const unsigned long long* src;
+      float* d2_;
+      seam_where(pend, src, d2_);
+      src += seam_off(wv, s4_);
+      for (int spin = 0;; ++spin) {
+        asm volatile("global_load_dwordx4 %0, %2, off sc1\n\tglobal_load_dwordx4 %1, %2, off offset:16 sc1\n\ts_waitcnt vmcnt(0)"
+                     : "=&v"(ga), "=&v"(gb) : "v"(src) : "memory");
+        if (ga[1] == e && ga[3] == e && gb[1] == e && gb[3] == e) break;
+        if (spin >= OP_SPIN_MAX) {
+          atomicOr_system((unsigned*)(uintptr_t)OP_QARG(unsigned long long, err), 2u);
+          ga[0] = ga[2] = gb[0] = gb[2] = op_nan_bits();   // the previous tile's share is unknown: NaN, not a partial sum
+          break;
+        }
+        OP_POLL_SLEEP(spin);
+      }
+    }
+    const float psn = __uint_as_float((pend >> 31) * 0x7fc00000u);   // NaN or 0 (scalar arithmetic: as a select the constant was hoisted out of the tile loop and spilled)
+    float4 a;
+    a.x = __uint_as_float(ga[0]) + ld.x;
+    a.y = __uint_as_float(ga[2]) + ld.y;
+    a.z = __uint_as_float(gb[0]) + ld.z;
+    a.w = __uint_as_float(gb[2]) + ld.w;
+    a.x = (a.x + psn) * nrm.x; a.y = (a.y + psn) * nrm.y; a.z = (a.z + psn) * nrm.z; a.w = (a.w + psn) * nrm.w;
+    *reinterpret_cast<float4*>(dst + seam_off(wv, s4_)) = a;
+  };
+  // an open seam closed on the spot (cold: the workgroup leaves, a halo tile): waves 0 - 2
+  auto seam_close = [&](unsigned pend, int tid_) {
+    const int wv = tid_ >> 6, s4_ = (tid_ & 63) * 4;
+    if (pend == OP_SEAM_NONE || wv >= 3) return;
+    typedef const __attribute__((address_space(4))) char* kq_t;
+    kq_t kq = (kq_t)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(kq));
+    const float4 nrm = *reinterpret_cast<const float4*>(
+        &reinterpret_cast<const float*>((const char*)(uintptr_t)OP_QARG(unsigned long long, tab) + OP_TAB_INVN)[s4_]);
+    const unsigned long long* src;
+    float* dst;
+    seam_where(pend, src, dst);
+    const float4 ld = *reinterpret_cast<const float4*>(dst + seam_off(wv, s4_));   // the leading partial this lane left there
+    seam_finish(pend, wv, s4_, 0ull, 0ull, 0ull, 0ull, dst, ld, nrm);   // (tag 0 is never current: the epoch starts at 1 -- straight to the poll)
+  };
 
 #if OP_EXP_STALL_NS
   const unsigned long long op_exp_t0_ = wall_clock64();
@@ -434,7 +538,10 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
 #if OP_WHO
   if (PERSIST && threadIdx.x == 0 && ticket < 4096u) P.who[ticket * 4 + 2] = (blockIdx.x + 1u) | (iter << 16);   // who started the tile
 #endif
-  if (PERSIST && ticket >= P.total_tiles) return;   // (workgroup-uniform)
+  if (PERSIST && ticket >= P.total_tiles) {   // (workgroup-uniform)
+    if constexpr (DEFER) seam_close((unsigned)__builtin_amdgcn_readfirstlane((int)s_misc[0]), tid);
+    return;
+  }
 #if OP_TILECOUNT == 1
   if (PERSIST && threadIdx.x == 0) { atomicAdd_system(P.err + 4, 1u); atomicAdd_system(P.err + 5, ticket); }   // (diagnosis) every ticket taken up
 #endif
@@ -854,8 +961,16 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
     const op_v4u gr = {(unsigned)myword, m_epoch, (unsigned)(myword >> 32), m_epoch};
     op_st16_sc1(&xb_mine[((4 * wave + g) * OP_XW + c) * 2], gr);
   }
+  [[maybe_unused]] unsigned pend_halo = OP_SEAM_NONE;
+  if constexpr (DEFER) {
+    if (halo_tile) pend_halo = (unsigned)__builtin_amdgcn_readfirstlane((int)s_misc[0]);   // (read before, cleared after the barrier)
+  }
   __syncthreads();   // every wave is past its forward exchange: the slices are idle from here
   if (halo_tile) {
+    if constexpr (DEFER) {
+      seam_close(pend_halo, tid);
+      if (tid == 0) s_misc[0] = OP_SEAM_NONE;
+    }
     if constexpr (PERSIST) {
       // a halo tile ends here: its next ticket is drawn on the spot (two tiles in 149 at the default chunking)
 #if OP_MAX_ITERS == 1 || OP_DRAW_TOP
@@ -1151,6 +1266,30 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
 #ifndef OP_TK_LATE
 #define OP_TK_LATE 0  // 1: the next ticket reaches the other waves through a polled LDS word after the mask stage, not under the smoothing stage's barrier
 #endif
+#ifndef OP_SEAM_AT
+#define OP_SEAM_AT 4   // where the open seam's loads are issued: after that many quarters of the overlap-add (4: behind it)
+#endif
+  // DEFERRED SEAM: the open seam's granules (the tile before it published them a whole tile ago) are loaded during the
+  // overlap-add (after OP_SEAM_AT quarters of it) and used at the end of the epilogue
+  [[maybe_unused]] unsigned sm_pend = OP_SEAM_NONE;
+  [[maybe_unused]] unsigned long long sm_g0 = 0ull, sm_g1 = 0ull, sm_g2 = 0ull, sm_g3 = 0ull;
+  [[maybe_unused]] float* sm_dst = nullptr;
+  [[maybe_unused]] float4 sm_lead = make_float4(0.f, 0.f, 0.f, 0.f);
+  auto seam_issue = [&]() {
+    sm_pend = (unsigned)__builtin_amdgcn_readfirstlane((int)s_misc[0]);   // (every wave reads it before the barrier; thread 0 rewrites it after)
+    if (sm_pend != OP_SEAM_NONE && wave < 3) {
+      const unsigned long long* sm_src;
+      seam_where(sm_pend, sm_src, sm_dst);
+      sm_src += seam_off(wave, (tid & 63) * 4);
+      sm_g0 = __hip_atomic_load((const __attribute__((address_space(1))) unsigned long long*)(sm_src), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      sm_g1 = __hip_atomic_load((const __attribute__((address_space(1))) unsigned long long*)(sm_src + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      sm_g2 = __hip_atomic_load((const __attribute__((address_space(1))) unsigned long long*)(sm_src + 2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      sm_g3 = __hip_atomic_load((const __attribute__((address_space(1))) unsigned long long*)(sm_src + 3), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      typedef float op_v4f __attribute__((ext_vector_type(4)));
+      const op_v4f l4 = *(const __attribute__((address_space(1))) op_v4f*)(sm_dst + seam_off(wave, (tid & 63) * 4));
+      sm_lead = make_float4(l4[0], l4[1], l4[2], l4[3]);
+    }
+  };
   if constexpr (PERSIST && OP_PF_AT == 0) prefetch_next();
   float* acc = reinterpret_cast<float*>(regions + wave * WAVE_CX_H);
   {
@@ -1173,6 +1312,7 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
       }
       wave_lds_sync();
       if constexpr (PERSIST) { if (j + 1 == OP_PF_AT) prefetch_next(); }
+      if constexpr (DEFER) { if (j + 1 == OP_SEAM_AT) seam_issue(); }
     }
   }
   if constexpr (!PERSIST) load_n4();
@@ -1223,13 +1363,17 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
 #else
   const int64_t e_u = u, e_row = row, e_chunk = chunk, e_tf = tf_tile;
   const int e_jt = jt;
+  [[maybe_unused]] const unsigned e_ticket = ticket;
 #endif
   const float* fr = reinterpret_cast<const float*>(regions);
   const int s4 = (tid & 63) * 4;
   // A lost hand-off must not look like audio: a tile whose neighbour bits never arrived writes NaN to every hop it
   // finalises and publishes NaN partials (the next tile's straddling hops inherit them); a tile whose predecessor's
   // partial hops never arrived writes NaN to those three hops.  The error word still reports it (sg_check_errors).
-  const float poison = s_misc[1] != 0u ? __uint_as_float(0x7fc00000u) : 0.f;
+  // (a scalar select: as a vector one its NaN constant is hoisted out of the tile loop into a register of its own)
+  unsigned poison_u = __builtin_amdgcn_readfirstlane((int)s_misc[1]) != 0 ? 0x7fc00000u : 0u;
+  asm volatile("" : "+s"(poison_u));
+  const float poison = __uint_as_float(poison_u);
   // Hops that straddle two tiles: tile j publishes its three TRAILING partial hops (un-normalised sums) the
   // same way as the mask bits (write-through stores, drained, epoch flag per hop); tile j+1 adds its LEADING
   // partials and finalises them.  Per wave: trailing hop first (published early), interior hops, leading hop
@@ -1274,7 +1418,12 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
         a4.x += f4.x; a4.y += f4.y; a4.z += f4.z; a4.w += f4.w;
         fin(a4, wave + 4 * it);
       }
-      {
+      if constexpr (DEFER) {
+        // the seam left open one tile ago is finished, this tile's stays open
+        if (sm_pend != OP_SEAM_NONE) seam_finish(sm_pend, wave, s4, sm_g0, sm_g1, sm_g2, sm_g3, sm_dst, sm_lead, n4);
+        *reinterpret_cast<float4*>(dst0 + wave * 256) = ld4(wave * HPITCH);
+        if (tid == 0) s_misc[0] = e_ticket | (s_misc[1] != 0u ? 0x80000000u : 0u);
+      } else {
         float4 a4 = ld4(wave * HPITCH);
         const unsigned long long* src = e_part2 + (((size_t)e_u * e_ntiles + e_jt - 1) * 3 + wave) * 256 + s4;
         op_v4u ga, gb;
@@ -1288,7 +1437,7 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
 #if OP_WHO
             if (atomicAdd_system(e_err + 15, 1u) == 0u) { e_err[12] = e_ticket; e_err[13] = ga[1]; }
 #endif
-            ga[0] = ga[2] = gb[0] = gb[2] = 0x7fc00000u;   // the previous tile's share is unknown: NaN, not a partial sum
+            ga[0] = ga[2] = gb[0] = gb[2] = op_nan_bits();   // the previous tile's share is unknown: NaN, not a partial sum
             break;
           }
           OP_POLL_SLEEP(spin);
@@ -1303,6 +1452,11 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
       if constexpr (PERSIST && OP_PF_AT == 5) prefetch_next();
       OP_DONE;
     }
+  }
+  if constexpr (DEFER) {
+    // not a tile_fast tile (a unit's edge, an unaligned row): it keeps the immediate protocol, an open seam is closed first
+    if (sm_pend != OP_SEAM_NONE && wave < 3) seam_finish(sm_pend, wave, s4, sm_g0, sm_g1, sm_g2, sm_g3, sm_dst, sm_lead, n4);
+    if (tid == 0) s_misc[0] = OP_SEAM_NONE;
   }
   for (int it = 0; it < 5; ++it) {
     const int jj = wave < 3 ? (it == 0 ? NF + wave : (it == 4 ? wave : wave + 4 * it)) : (it < 4 ? 3 + 4 * it : -1);
@@ -1347,7 +1501,7 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
         if ((OP_ABLATE & 16) || (!LOSE && ga[1] == e && ga[3] == e && gb[1] == e && gb[3] == e)) break;
         if (LOSE || spin >= OP_SPIN_MAX) {
           atomicOr_system(e_err, 2u);
-          ga[0] = ga[2] = gb[0] = gb[2] = 0x7fc00000u;
+          ga[0] = ga[2] = gb[0] = gb[2] = op_nan_bits();
           break;
         }
         OP_POLL_SLEEP(spin);
