@@ -16,6 +16,7 @@
 #pragma once
 #include "kernels.hpp"
 #include "thresh.hpp"
+#include "exact1024.hpp"
 
 namespace sg {
 
@@ -1338,22 +1339,10 @@ struct DecideArgs {
 __device__ __forceinline__ double exact_power(const DecideArgs& A, int64_t row, int64_t chunk, int64_t t, int f,
                                               int lane) {
   const int64_t s0 = t * A.g.H - A.g.padL;
-  double re = 0.0, im = 0.0;
-#pragma unroll 4
-  for (int i = 0; i < 16; ++i) {
-    const int m = lane + 64 * i;
-    const double xv = view_sample(A.view, row, chunk, s0 + m) * A.win64[m];
-    const int j = (f * m) & 1023;
-    cx<double> w = A.tw64[j & 511];
-    if (j >= 512) { w.x = -w.x; w.y = -w.y; }
-    re += xv * w.x;
-    im += xv * w.y;
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    re += __shfl_xor(re, off);
-    im += __shfl_xor(im, off);
-  }
-  return re * re + im * im;
+  const int64_t e = chunk * A.view.cs - A.view.pad + s0;   // the frame's first sample in its row
+  int a, b;
+  exact1024_terms(s0, e, A.view.Lp, A.view.lo, A.view.hi, a, b);
+  return exact1024_power(A.view.x, A.view.dtype, row * A.view.stride + e, a, b, A.win64, A.tw64, f, lane);
 }
 
 template <int WAVES>

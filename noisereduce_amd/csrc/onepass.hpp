@@ -153,29 +153,12 @@ __device__ __forceinline__ double op_exact_power(const OnePassArgs& P, int64_t r
   const void* const x_exact = (const void*)(uintptr_t)OP_XARG(unsigned long long, x_exact);
   const int x_dtype = OP_XARG(int, dtype_exact);
   const char* const tab = (const char*)(uintptr_t)OP_XARG(unsigned long long, tab);
-  double re = 0.0, im = 0.0;
-#pragma unroll 4
-  for (int i = 0; i < 16; ++i) {
-    const int m = lane + 64 * i;
-    // the ORIGINAL samples: view_sample on A.view's geometry with the caller's pointer / dtype / stride
-    double xs = 0.0;
-    {
-      const int64_t sp = s0 + m;
-      const int64_t gi = chunk * v_cs - v_pad + sp;
-      if (sp >= 0 && sp < v_Lp && gi >= v_lo && gi < v_hi) xs = load_sample(x_exact, x_dtype, row * x_stride + gi);
-    }
-    const double xv = xs * reinterpret_cast<const double*>(tab + OP_TAB_WIN64)[m];
-    const int j = (f * m) & 1023;
-    cx<double> w = reinterpret_cast<const cx<double>*>(tab + OP_TAB_TW64)[j & 511];
-    if (j >= 512) { w.x = -w.x; w.y = -w.y; }
-    re += xv * w.x;
-    im += xv * w.y;
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    re += __shfl_xor(re, off);
-    im += __shfl_xor(im, off);
-  }
-  return re * re + im * im;
+  // the ORIGINAL samples: view_sample on A.view's geometry with the caller's pointer / dtype / stride
+  const int64_t e = chunk * v_cs - v_pad + s0;   // the frame's first sample in its row
+  int a, b;
+  exact1024_terms(s0, e, v_Lp, v_lo, v_hi, a, b);
+  return exact1024_power(x_exact, x_dtype, row * x_stride + e, a, b, reinterpret_cast<const double*>(tab + OP_TAB_WIN64),
+                         reinterpret_cast<const cx<double>*>(tab + OP_TAB_TW64), f, lane);
 }
 
 // the quiet NaN of a lost hand-off, made where it is needed (cold): as a plain constant it is hoisted out of the persistent
