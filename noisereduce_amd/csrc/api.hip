@@ -2421,12 +2421,19 @@ static int stage_onepass(sg_handle* h, const View& v, const View& vx, const Geom
           std::vector<unsigned> hst(*trn * 16);
           if (hipMemcpy(hst.data(), *trp, hst.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return;
           double sum[14] = {0}, w = 0, mx = 0;
+          double wsum[4][14] = {{0}}, ww[4] = {0};   // the same per wave index (slot = ticket * 4 + wave)
           for (size_t i = 0; i < *trn; ++i) {
             if (hst[i * 16 + 15] != 1u) continue;
             w += 1;
+            ww[i & 3] += 1;
             double tot = 0;
-            for (int k = 0; k < 14; ++k) { sum[k] += hst[i * 16 + k]; tot += hst[i * 16 + k]; }
+            for (int k = 0; k < 14; ++k) { sum[k] += hst[i * 16 + k]; wsum[i & 3][k] += hst[i * 16 + k]; tot += hst[i * 16 + k]; }
             mx = std::max(mx, tot);
+          }
+          for (int wv = 0; wv < 4; ++wv) {   // (tools/trace_onepass.py --table reads these lines)
+            fprintf(stderr, "[OP_TRACE] wave %d (%.0f completed):", wv, ww[wv]);
+            for (int k = 0; k < 14; ++k) fprintf(stderr, " %d:%.0f", k, wsum[wv][k] / (ww[wv] > 0 ? ww[wv] : 1));
+            fprintf(stderr, "\n");
           }
           fprintf(stderr, "[OP_TRACE] completed waves %.0f; average shader cycles per wave and phase:", w);
           double tot = 0;
@@ -2443,7 +2450,7 @@ static int stage_onepass(sg_handle* h, const View& v, const View& vx, const Geom
   {
     ProfScope ps(h, SG_STAGE_ONEPASS, st);
     const size_t lds = (size_t)(fast::FN + WAVES * fast::WAVE_CX_H) * sizeof(fast::cf) + (1024 + T2_FLOATS) * sizeof(float) +
-                       256 * 8 + 514 * 8 + 32 + (prop ? 528 : 0);
+                       256 * 8 + 514 * 8 + 192 * 8 + 32 + (prop ? 528 : 0);
     auto go = [&](auto kern) -> hipError_t {
       hipError_t e = set_lds(reinterpret_cast<const void*>(kern), lds);
       if (e != hipSuccess) return e;
@@ -2468,7 +2475,7 @@ static int stage_onepass(sg_handle* h, const View& v, const View& vx, const Geom
     P.ticket = (unsigned*)h->xticket.p + 8;   // its own counter (zeroed by the first launch's ticket-0 workgroup): it takes tickets only if a unit reported
     P.ticket_base = 0;
     const size_t lds = (size_t)(fast::FN + WAVES * fast::WAVE_CX_H) * sizeof(fast::cf) + (1024 + T2_FLOATS) * sizeof(float) +
-                       256 * 8 + 514 * 8 + 32 + (prop ? 528 : 0);
+                       256 * 8 + 514 * 8 + 192 * 8 + 32 + (prop ? 528 : 0);
     auto redo = [&](auto kern) -> hipError_t {
       hipError_t e = set_lds(reinterpret_cast<const void*>(kern), lds);
       if (e != hipSuccess) return e;

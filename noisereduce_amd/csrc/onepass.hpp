@@ -16,7 +16,7 @@
 //      uint16 weight sums K of its own 16 frames;
 // then x mask -> inverse transform -> window -> overlap-add -> store exactly as k_apply_fast<LEAN>.
 // The smoothing buffers live in the exchange slices, which are idle between the two transforms: the
-// kernel needs no more LDS than k_apply_fast (3 workgroups per CU).
+// kernel needs no more LDS than k_apply_fast plus its own small tables (3 workgroups per CU).
 //
 // Inter-workgroup protocol (MI355X_MICROARCH.md, "Workgroup dispatch, XCD placement & inter-workgroup
 // visibility"): payload and flag are 8/4-byte agent-scope relaxed atomics on both sides (sc1 stores and
@@ -67,14 +67,6 @@ constexpr int OP_TAB_WIN = 0, OP_TAB_WSQ = 4096, OP_TAB_INVN = 8192, OP_TAB_TW51
 #endif
 #ifndef OP_WHO
 #define OP_WHO 0   // (diagnosis) 1: a poll that gives up leaves its tile's ticket, what it waited for and the tag it saw in the error words 8..13
-#endif
-#ifndef OP_GLOBAL_DRAW
-#define OP_GLOBAL_DRAW 0   // (diagnosis) 1: the mid-tile ticket draws as GLOBAL atomics (the pointer re-read from the kernel-argument segment is a generic one: flat_atomic_add)
-#endif
-#if OP_GLOBAL_DRAW
-#define OP_DRAW_TICKET(p64) __hip_atomic_fetch_add((__attribute__((address_space(1))) unsigned*)(p64), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#else
-#define OP_DRAW_TICKET(p64) atomicAdd((unsigned*)(uintptr_t)(p64), 1u)
 #endif
 #ifndef OP_DRAW_TOP
 #define OP_DRAW_TOP 0   // (diagnosis, with -DOP_PF_AT=6) 1: the persistent loop draws its next ticket at the loop top -- no ticket is held while the previous tile is finished
@@ -169,6 +161,59 @@ __device__ __forceinline__ unsigned op_nan_bits() {
   return v;
 }
 
+// GLOBAL accesses where the pointer was rebuilt from a 64-bit kernel argument (late arguments): such a pointer is a generic one to
+// the compiler, its accesses are FLAT, and while a FLAT access is pending every wait the compiler emits is vmcnt(0) / lgkmcnt(0)
+// -- never a partial vmcnt(N) -- which also waits for whatever the wave issued AFTER the value it needs (the next tile's
+// prefetched samples, the open seam's loads) and for the write-through acknowledgements of the inline-asm sc1 stores.
+#ifndef OP_WAIT_SITES
+#define OP_WAIT_SITES 7   // (A/B builds) bit 0: the mid-tile ticket draw is a global atomic, bit 1: the epilogue's 1 / envelope load and output
+                          // stores are global accesses, bit 2: the smoothing stage's MFMA operands come from LDS (0: the parent's forms)
+#endif
+typedef float op_v4f __attribute__((ext_vector_type(4)));
+#if OP_WAIT_SITES & 2
+#define OP_G4 __attribute__((address_space(1)))
+#else
+#define OP_G4
+#endif
+__device__ __forceinline__ float4 op_ldg4(const float* p) {
+  const op_v4f v = *(const OP_G4 op_v4f*)p;
+  return make_float4(v[0], v[1], v[2], v[3]);
+}
+__device__ __forceinline__ void op_stg4(float* p, float4 a) {
+  const op_v4f v = {a.x, a.y, a.z, a.w};
+  *(OP_G4 op_v4f*)p = v;
+}
+// The mid-tile ticket draw (and a halo tile's, which consumes it at once): a GLOBAL returning atomic whose result the compiler waits for where it is consumed.  The address
+// passes through a vector register the compiler cannot see into: to a wave-uniform address the atomic optimizer applies its
+// wave reduction (v_mbcnt / s_bcnt1 / v_readfirstlane), and the readfirstlane waits for the atomic three instructions later.
+__device__ __forceinline__ unsigned op_draw_ticket_late(unsigned long long p64) {
+#if OP_WAIT_SITES & 1
+  asm volatile("" : "+v"(p64));
+  return __hip_atomic_fetch_add((__attribute__((address_space(1))) unsigned*)p64, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+  return atomicAdd((unsigned*)(uintptr_t)p64, 1u);
+#endif
+}
+
+// a lost hand-off's bit in the host-mapped error word (atomicOr_system on a GLOBAL pointer: cold, but its block lies inside
+// the smoothing stage and the epilogue, and a FLAT access there is one the compiler must assume pending at the next join)
+// (the word is host memory: the statement attribute of atomicOr_system keeps the compare-and-swap expansion -- an OR is not
+// among the atomics the bus carries)
+__device__ __forceinline__ void op_err_or(unsigned* p, unsigned bits) {
+  __HIP_ATOMIC_BACKWARD_COMPAT_MEMORY {
+    __hip_atomic_fetch_or((__attribute__((address_space(1))) unsigned*)p, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
+// lane ^ M (M < 32) by ds_swizzle: the pattern is an immediate.  __shfl_xor's ds_bpermute takes its lane index from a register,
+// and the indices of a wave's xor steps -- loop-invariant -- were hoisted out of the persistent tile loop: three registers
+// live through every phase of a kernel that sits at its 168, one of them in scratch in the PROP instantiation.
+template <int M>
+__device__ __forceinline__ int op_xor_lanes(int v) {
+  static_assert(M > 0 && M < 32, "within a half-wave");
+  return __builtin_amdgcn_ds_swizzle(v, (M << 10) | 0x1f);
+}
+
 // OP_ABLATE (development only, default 0; results are wrong): 1 no decision stage, 2 no wait for the
 // neighbours' flags, 8 no exact refinement, 16 no wait for the previous tile's trailing hops
 #ifndef OP_ABLATE
@@ -252,7 +297,10 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
   float* s_t2 = swin + 1024;
   unsigned long long* s_exp = reinterpret_cast<unsigned long long*>(s_t2 + T2_FLOATS);
   double* s_t2d = reinterpret_cast<double*>(s_exp + 256);   // exact compare constants (refinement), same order
-  unsigned* s_misc = reinterpret_cast<unsigned*>(s_t2d + 514);   // [0] ticket, [1] lost hand-off, [4], [5]: PERSIST ticket slots
+  // the smoothing stage's three MFMA operands (OP_TAB_MCONST, 192 x 8 B): from LDS their wait is an lgkmcnt one -- as loads from
+  // the table behind the bits' publish store the first MFMA waited for that store's write-through acknowledgement
+  unsigned long long* s_mc = reinterpret_cast<unsigned long long*>(s_t2d + 514);
+  unsigned* s_misc = reinterpret_cast<unsigned*>(s_mc + 192);   // [0] ticket, [1] lost hand-off, [4], [5]: PERSIST ticket slots
   unsigned char* s_ef = reinterpret_cast<unsigned char*>(s_misc + 8);  // PROP: integer weight (<= 81) of the valid taps along f, per bin
   constexpr int NF = 4 * WAVES;
   constexpr int SPAN = (NF - 1) * 256 + 1024, XPITCH = 288;
@@ -282,6 +330,7 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
     const cf tw_b = reinterpret_cast<const cf*>(Pk.tab + OP_TAB_TW512)[((tid + 256) >> 4) * (tid & 15)];
     const float4 w4 = reinterpret_cast<const float4*>(Pk.tab + OP_TAB_WIN)[tid];
     const unsigned long long e8 = reinterpret_cast<const unsigned long long*>(Pk.tab + OP_TAB_EXP8)[tid];
+    const unsigned long long mc8 = reinterpret_cast<const unsigned long long*>(Pk.tab + OP_TAB_MCONST)[min(tid, 191)];
     t2pre[0] = Pk.tc.T2[perm_inv(tid)];
     t2pre[1] = Pk.tc.T2[perm_inv(tid + 256)];
     t2pre[2] = Pk.tc.T2[perm_inv(512)];
@@ -302,6 +351,7 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
     tw512[tid + 256] = tw_b;
     reinterpret_cast<float4*>(swin)[tid] = w4;
     s_exp[tid] = e8;
+    if (tid < 192) s_mc[tid] = mc8;
     if constexpr (PROP) {
       for (int f = tid; f <= 512; f += WAVES * 64) {
         const int lo = max(-Pk.nf, -f), hi = min(Pk.nf, 512 - f);
@@ -421,7 +471,7 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
                      : "=&v"(ga), "=&v"(gb) : "v"(src) : "memory");
         if (ga[1] == e && ga[3] == e && gb[1] == e && gb[3] == e) break;
         if (spin >= OP_SPIN_MAX) {
-          atomicOr_system((unsigned*)(uintptr_t)OP_QARG(unsigned long long, err), 2u);
+          op_err_or((unsigned*)(uintptr_t)OP_QARG(unsigned long long, err), 2u);
           ga[0] = ga[2] = gb[0] = gb[2] = op_nan_bits();   // the previous tile's share is unknown: NaN, not a partial sum
           break;
         }
@@ -435,7 +485,7 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
     a.z = __uint_as_float(gb[0]) + ld.z;
     a.w = __uint_as_float(gb[2]) + ld.w;
     a.x = (a.x + psn) * nrm.x; a.y = (a.y + psn) * nrm.y; a.z = (a.z + psn) * nrm.z; a.w = (a.w + psn) * nrm.w;
-    *reinterpret_cast<float4*>(dst + seam_off(wv, s4_)) = a;
+    op_stg4(dst + seam_off(wv, s4_), a);
   };
   // an open seam closed on the spot (cold: the workgroup leaves, a halo tile): waves 0 - 2
   auto seam_close = [&](unsigned pend, int tid_) {
@@ -444,12 +494,11 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
     typedef const __attribute__((address_space(4))) char* kq_t;
     kq_t kq = (kq_t)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(kq));
-    const float4 nrm = *reinterpret_cast<const float4*>(
-        &reinterpret_cast<const float*>((const char*)(uintptr_t)OP_QARG(unsigned long long, tab) + OP_TAB_INVN)[s4_]);
+    const float4 nrm = op_ldg4(&reinterpret_cast<const float*>((const char*)(uintptr_t)OP_QARG(unsigned long long, tab) + OP_TAB_INVN)[s4_]);
     const unsigned long long* src;
     float* dst;
     seam_where(pend, src, dst);
-    const float4 ld = *reinterpret_cast<const float4*>(dst + seam_off(wv, s4_));   // the leading partial this lane left there
+    const float4 ld = op_ldg4(dst + seam_off(wv, s4_));   // the leading partial this lane left there
     seam_finish(pend, wv, s4_, 0ull, 0ull, 0ull, 0ull, dst, ld, nrm);   // (tag 0 is never current: the epoch starts at 1 -- straight to the poll)
   };
 
@@ -535,6 +584,7 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
     tw512[t_ + 256] = reinterpret_cast<const cf*>(P.tab + OP_TAB_TW512)[((t_ + 256) >> 4) * (t_ & 15)];
     reinterpret_cast<float4*>(swin)[t_] = reinterpret_cast<const float4*>(P.tab + OP_TAB_WIN)[t_];
     s_exp[t_] = reinterpret_cast<const unsigned long long*>(P.tab + OP_TAB_EXP8)[t_];
+    if (t_ < 192) s_mc[t_] = reinterpret_cast<const unsigned long long*>(P.tab + OP_TAB_MCONST)[t_];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       const int i = t_ + k * WAVES * 64;
@@ -702,10 +752,10 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
   {
 #pragma unroll
     for (int r = 0; r < 32; ++r) nrm2 += v[r].x * v[r].x + v[r].y * v[r].y;
-    nrm2 += __shfl_xor(nrm2, 1);
-    nrm2 += __shfl_xor(nrm2, 2);
-    nrm2 += __shfl_xor(nrm2, 4);
-    nrm2 += __shfl_xor(nrm2, 8);
+    nrm2 += __int_as_float(op_xor_lanes<1>(__float_as_int(nrm2)));
+    nrm2 += __int_as_float(op_xor_lanes<2>(__float_as_int(nrm2)));
+    nrm2 += __int_as_float(op_xor_lanes<4>(__float_as_int(nrm2)));
+    nrm2 += __int_as_float(op_xor_lanes<8>(__float_as_int(nrm2)));
   }
   {
     // an opaque ZERO OFFSET (not an opaque pointer: that would lose the LDS address space and turn every
@@ -887,16 +937,15 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
     // 0..15, high half = entry 16 + k.  (32 wave ballots + per-lane selects did the same in ~200 instructions.)
     unsigned tr = pred;
     // (`up` = lanes whose column index has bit `sft` set: a compile-time lane mask -> SGPR-pair selects, sel_s of fastpath.hpp)
-    auto tstep = [&](int sft, unsigned msk, unsigned long long up) {
-      const unsigned y = (unsigned)__shfl_xor((int)tr, sft);
+    auto tstep = [&](unsigned y, int sft, unsigned msk, unsigned long long up) {   // y = tr of lane ^ sft
       const unsigned ysh = sel_s(up, y >> sft, y << sft);
       const unsigned mk = sel_s(up, msk, ~msk);
       tr = (tr & ~mk) | (ysh & mk);
     };
-    tstep(8, 0x00ff00ffu, 0xff00ff00ff00ff00ull);
-    tstep(4, 0x0f0f0f0fu, 0xf0f0f0f0f0f0f0f0ull);
-    tstep(2, 0x33333333u, 0xccccccccccccccccull);
-    tstep(1, 0x55555555u, 0xaaaaaaaaaaaaaaaaull);
+    tstep((unsigned)op_xor_lanes<8>((int)tr), 8, 0x00ff00ffu, 0xff00ff00ff00ff00ull);
+    tstep((unsigned)op_xor_lanes<4>((int)tr), 4, 0x0f0f0f0fu, 0xf0f0f0f0f0f0f0f0ull);
+    tstep((unsigned)op_xor_lanes<2>((int)tr), 2, 0x33333333u, 0xccccccccccccccccull);
+    tstep((unsigned)op_xor_lanes<1>((int)tr), 1, 0x55555555u, 0xaaaaaaaaaaaaaaaaull);
     const unsigned long long b8 = __ballot(pred512);
     {
       const int sh = 16 * g;
@@ -959,7 +1008,7 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
 #if OP_MAX_ITERS == 1 || OP_DRAW_TOP
       if (tid == 0) s_misc[tk_slot ^ 1u] = 0xffffffffu;
 #else
-      if (tid == 0) s_misc[tk_slot ^ 1u] = OP_DRAW_TICKET(OP_MARG(unsigned long long, ticket)) - OP_MARG(unsigned, ticket_base);
+      if (tid == 0) s_misc[tk_slot ^ 1u] = op_draw_ticket_late(OP_MARG(unsigned long long, ticket)) - OP_MARG(unsigned, ticket_base);
 #endif
       pf = false;
       // (defined on this path too: left alone, the registers of the samples staged at the loop top would stay live up to here)
@@ -995,7 +1044,12 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
     wb[r * WP + WP - 1] = 0ull;
   }
   const int q4 = lane >> 4, j16 = lane & 15;
-  const long Bf = (long)reinterpret_cast<const unsigned long long*>(m_tab + OP_TAB_MCONST)[lane], At1 = (long)reinterpret_cast<const unsigned long long*>(m_tab + OP_TAB_MCONST)[64 + lane], At2 = (long)reinterpret_cast<const unsigned long long*>(m_tab + OP_TAB_MCONST)[128 + lane];
+#if OP_WAIT_SITES & 4
+  const long Bf = (long)s_mc[lane], At1 = (long)s_mc[64 + lane], At2 = (long)s_mc[128 + lane];
+#else
+  const unsigned long long* const mc_ = reinterpret_cast<const unsigned long long*>(m_tab + OP_TAB_MCONST);
+  const long Bf = (long)mc_[lane], At1 = (long)mc_[64 + lane], At2 = (long)mc_[128 + lane];
+#endif
   const bool three = 2 * m_nt > 16;      // a third row block (wave-uniform)
   // neighbour-list index m -> tile row: m < m_nt: row m (previous tile), else row m_nt + 16 + (m - m_nt) (next tile)
   const int m1 = j16, m2 = 16 + j16;
@@ -1030,7 +1084,7 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
     op_v4u gr = op_ld16_sc1(src);
     for (int spin = 0; !(OP_ABLATE & 2) && (LOSE || gr[1] != m_epoch || gr[3] != m_epoch); ++spin) {
       if (LOSE || spin >= OP_SPIN_MAX) {   // every spin is bounded: report instead of hanging the device
-        atomicOr_system(m_err, 1u);
+        op_err_or(m_err, 1u);
 #if OP_WHO
         if (atomicAdd_system(m_err + 14, 1u) == 0u) { m_err[8] = m_ticket; m_err[9] = (unsigned)i; m_err[10] = gr[1]; m_err[11] = m_epoch; }
 #endif
@@ -1045,13 +1099,14 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
   __syncthreads();
   OP_STAMP(8);   // neighbours' bits (poll) + barrier
   // PERSIST: the next ticket.  Drawn only now -- this tile no longer waits for a tile with a HIGHER ticket -- and consumed at
-  // the end of the smoothing stage: the atomic's round trip (~1.5 us) runs under the matrix-core work
+  // the end of the smoothing stage: the atomic's round trip (~1.5 us) runs under the matrix-core work (a GLOBAL atomic and no
+  // FLAT access pending: as flat_atomic_add wave 0's first MFMA of this stage waited vmcnt(0) for it -- op_draw_ticket_late)
   [[maybe_unused]] unsigned nx_raw = 0u;
   if constexpr (PERSIST) {
 #if OP_MAX_ITERS == 1 || OP_DRAW_TOP
     if (tid == 0) nx_raw = 0xffffffffu + OP_MARG(unsigned, ticket_base);   // "past the last tile": the workgroup leaves at the loop top
 #else
-    if (tid == 0) nx_raw = OP_DRAW_TICKET(OP_MARG(unsigned long long, ticket));
+    if (tid == 0) nx_raw = op_draw_ticket_late(OP_MARG(unsigned long long, ticket));
 #endif
   }
   {
@@ -1203,7 +1258,7 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
   }
   OP_STAMP(11);  // inverse transform
   float4 n4;   // 1 / window envelope of the lane's four samples of a hop
-  auto load_n4 = [&]() { n4 = *reinterpret_cast<const float4*>(&reinterpret_cast<const float*>(m_tab + OP_TAB_INVN)[(tid & 63) * 4]); };
+  auto load_n4 = [&]() { n4 = op_ldg4(&reinterpret_cast<const float*>(m_tab + OP_TAB_INVN)[(tid & 63) * 4]); };   // (a GLOBAL load: its wait is a partial vmcnt)
   if constexpr (PERSIST) load_n4();   // ahead of the prefetch: the epilogue's wait for it must not include the next tile's samples
   auto prefetch_next = [&]() {
     // ---- the NEXT tile's samples: loads issued here, consumed at the loop top (see PERSIST above) ----
@@ -1228,20 +1283,19 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
     const int n_jt = (int)(n_tk % n_ntt) - 1;
     const unsigned n_gu = (unsigned)(Pn.A.view.unit0 + n_u), n_nch = (unsigned)Pn.A.view.n_chunks;
     const TileSrc N = tile_src(Pn, (int64_t)(n_gu / n_nch), Pn.A.view.c0 + n_gu % n_nch, n_jt, true);
-    if (n_live && N.blk_vec) {
+    // NO BRANCH around the loads: at the join with a path that issued none the compiler has to assume the least number of loads
+    // behind n4, and the epilogue's wait for n4 is vmcnt(0) again -- for the whole span.  A next tile that stages sample by
+    // sample (a unit's edge, a halo tile: two in 149) or no tile at all never reads q / sc: its loads go to the constant
+    // tables (19 x 256 floats from their start: inside OP_TAB_BYTES).
+    static_assert(NQ * 256 * 4 <= OP_TAB_BYTES, "the stand-in loads stay inside the tables");
+    const bool n_vec = n_live && N.blk_vec, n_scan = n_live && N.sc_base != nullptr;
+    const float* const n_sp = n_vec ? N.sp : reinterpret_cast<const float*>(Pn.tab);
+    const float* const n_sc = n_scan ? N.sc_base : n_sp;
+    const int n_sc1 = n_scan ? N.sc_n1 : 0;
 #pragma unroll
-      for (int k = 0; k < NQ; ++k) q[k] = N.sp[tid + k * 256];
-    } else {
+    for (int k = 0; k < NQ; ++k) q[k] = n_sp[tid + k * 256];
 #pragma unroll
-      for (int k = 0; k < NQ; ++k) q[k] = 0.f;
-    }
-    if (n_live && N.sc_base != nullptr) {
-#pragma unroll
-      for (int k = 0; k < SCAN_REG; ++k) sc[k] = N.sc_base[min(tid + k * WAVES * 64, N.sc_n1)];
-    } else {
-#pragma unroll
-      for (int k = 0; k < SCAN_REG; ++k) sc[k] = 0.f;
-    }
+    for (int k = 0; k < SCAN_REG; ++k) sc[k] = n_sc[min(tid + k * WAVES * 64, n_sc1)];
   };
 #ifndef OP_PF_AT
 #define OP_PF_AT 2   // where the prefetch is issued: 0 before the overlap-add, 1 / 2 / 3 after that many quarters of it, 4 after it, 5 at the end of the epilogue
@@ -1268,9 +1322,7 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
       sm_g1 = __hip_atomic_load((const __attribute__((address_space(1))) unsigned long long*)(sm_src + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       sm_g2 = __hip_atomic_load((const __attribute__((address_space(1))) unsigned long long*)(sm_src + 2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       sm_g3 = __hip_atomic_load((const __attribute__((address_space(1))) unsigned long long*)(sm_src + 3), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      typedef float op_v4f __attribute__((ext_vector_type(4)));
-      const op_v4f l4 = *(const __attribute__((address_space(1))) op_v4f*)(sm_dst + seam_off(wave, (tid & 63) * 4));
-      sm_lead = make_float4(l4[0], l4[1], l4[2], l4[3]);
+      sm_lead = op_ldg4(sm_dst + seam_off(wave, (tid & 63) * 4));
     }
   };
   if constexpr (PERSIST && OP_PF_AT == 0) prefetch_next();
@@ -1377,7 +1429,7 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
       auto ld4 = [&](int off) { return *reinterpret_cast<const float4*>(&fr[off + s4]); };
       auto fin = [&](float4 a, int jj) {
         a.x = (a.x + poison) * n4.x; a.y = (a.y + poison) * n4.y; a.z = (a.z + poison) * n4.z; a.w = (a.w + poison) * n4.w;
-        *reinterpret_cast<float4*>(dst0 + jj * 256) = a;
+        op_stg4(dst0 + jj * 256, a);
       };
       if (wave == 3) {
 #pragma unroll
@@ -1404,7 +1456,7 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
       if constexpr (DEFER) {
         // the seam left open one tile ago is finished, this tile's stays open
         if (sm_pend != OP_SEAM_NONE) seam_finish(sm_pend, wave, s4, sm_g0, sm_g1, sm_g2, sm_g3, sm_dst, sm_lead, n4);
-        *reinterpret_cast<float4*>(dst0 + wave * 256) = ld4(wave * HPITCH);
+        op_stg4(dst0 + wave * 256, ld4(wave * HPITCH));
         if (tid == 0) s_misc[0] = e_ticket | (s_misc[1] != 0u ? 0x80000000u : 0u);
       } else {
         float4 a4 = ld4(wave * HPITCH);
@@ -1416,7 +1468,7 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
           const unsigned e = e_epoch;
           if ((OP_ABLATE & 16) || (!LOSE && ga[1] == e && ga[3] == e && gb[1] == e && gb[3] == e)) break;
           if (LOSE || spin >= OP_SPIN_MAX) {
-            atomicOr_system(e_err, 2u);
+            op_err_or(e_err, 2u);
 #if OP_WHO
             if (atomicAdd_system(e_err + 15, 1u) == 0u) { e_err[12] = e_ticket; e_err[13] = ga[1]; }
 #endif
@@ -1483,7 +1535,7 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
         const unsigned e = e_epoch;
         if ((OP_ABLATE & 16) || (!LOSE && ga[1] == e && ga[3] == e && gb[1] == e && gb[3] == e)) break;
         if (LOSE || spin >= OP_SPIN_MAX) {
-          atomicOr_system(e_err, 2u);
+          op_err_or(e_err, 2u);
           ga[0] = ga[2] = gb[0] = gb[2] = op_nan_bits();
           break;
         }
