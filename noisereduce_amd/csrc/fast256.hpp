@@ -535,57 +535,11 @@ __global__ __launch_bounds__(WAVES * 64, 3) void k_apply_fast256(RegArgs A) {
       const float4 f4 = *reinterpret_cast<const float4*>(&fr[wv * WAVE_CX_H * 2 + lh * F25_HP + s4]);
       a4.x += f4.x; a4.y += f4.y; a4.z += f4.z; a4.w += f4.w;
     }
-    if (seam && (jj < 3 || jj >= NF)) {   // straddling hop: partial sum only; slots 0..2 leading, 3..5 trailing
-      const int slot = jj < 3 ? jj : 3 + (jj - NF);
-      *reinterpret_cast<float4*>(A.part + ((((size_t)u * A.n_tiles + blockIdx.x) * 6 + slot) * F25_H + s4)) = a4;
+    if (seam && (jj < 3 || jj >= NF)) {   // straddling hop: partial sum only, k_ola_seam finishes it
+      store_partial_hop<F25_H>(A, u, blockIdx.x, jj, NF, s4, a4);
       continue;
     }
-    bool all_valid = true;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int64_t ti = h - q;
-      if (ti < 0 || ti >= G.T) all_valid = false;
-    }
-    if (!A.normalize) {
-    } else if (all_valid) {
-      const float4 n4 = *reinterpret_cast<const float4*>(&A.invn[s4]);
-      a4.x *= n4.x; a4.y *= n4.y; a4.z *= n4.z; a4.w *= n4.w;
-    } else {
-      float4 nrm = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int64_t ti = h - q;
-        if (ti >= 0 && ti < G.T) {
-          const float4 w4 = *reinterpret_cast<const float4*>(&A.wsq[F25_H * q + s4]);
-          nrm.x += w4.x; nrm.y += w4.y; nrm.z += w4.z; nrm.w += w4.w;
-        }
-      }
-      a4.x /= (nrm.x > 1e-10f ? nrm.x : 1.f);
-      a4.y /= (nrm.y > 1e-10f ? nrm.y : 1.f);
-      a4.z /= (nrm.z > 1e-10f ? nrm.z : 1.f);
-      a4.w /= (nrm.w > 1e-10f ? nrm.w : 1.f);
-    }
-    {
-      const int64_t pb = h * F25_H - G.padL;
-      const int64_t gi0 = chunk * A.om.g_step + (pb - A.om.p0);
-      if (A.om.dtype == 0 && pb >= A.om.p0 && pb + F25_H <= A.om.p1 && pb + F25_H <= G.Lout && gi0 >= A.om.g_lo &&
-          gi0 + F25_H <= A.om.g_hi) {
-        float* dst = (float*)A.om.out + (row * A.om.stride + gi0 - A.om.g0 + s4);
-        if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
-          *reinterpret_cast<float4*>(dst) = a4;
-          continue;
-        }
-      }
-    }
-    const float vals[4] = {a4.x, a4.y, a4.z, a4.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int64_t p = h * F25_H + s4 + e - G.padL;
-      if (p < A.om.p0 || p >= A.om.p1) continue;
-      const int64_t gi = chunk * A.om.g_step + (p - A.om.p0);
-      if (gi < A.om.g_lo || gi >= A.om.g_hi) continue;
-      store_sample(A.om.out, A.om.dtype, row * A.om.stride + gi - A.om.g0, p < G.Lout ? vals[e] : 0.f);
-    }
+    finish_hop<F25_H>(A, row, chunk, h, s4, a4);
   }
 }
 

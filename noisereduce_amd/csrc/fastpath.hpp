@@ -43,6 +43,22 @@ __device__ __forceinline__ void stage_t2_plain(float* s_t2, const double* __rest
   }
 }
 
+// The exact compare constant of band f of unit u: T2, "all pass" (-1) where the unit's -top_db floor lifts the band above its
+// threshold (floor_live = need == 1: pmax is valid), "no cell passes" in a unit with a non-finite sample (need == 2).
+// stage_t2_plain's `slow`, and the exact re-evaluation of an ambiguous cell (which passes the late_args() copy of the
+// arguments).  floor_live comes in as the caller's one scalar: compared again at the cold site, `need == 1` cost
+// k_gate_onepass512 a hundred more reloads of spilled SGPRs (324 against 219: profiles/onepass_reg_refactor.txt, B).
+__device__ __forceinline__ double t2_effective(const ThreshConsts& tc, int64_t u, int FS, int f, int need, bool floor_live,
+                                               double mag_scale, double top_db) {
+  double v = tc.T2[f];
+  if (floor_live) {
+    const double fl = cell_db(tc.pmax[u * FS + f], mag_scale) - top_db;
+    if (fl > tc.thresh[f]) v = -1.0;
+  }
+  if (need == 2) v = T2_NEVER;
+  return v;
+}
+
 // (round 5) The kernel's own argument struct re-read from the kernel-argument segment through an OPAQUE pointer, for the COLD
 // parts of a long kernel (the exact re-evaluation of an ambiguous cell needs the view's dozen fields, the float64 tables and
 // the threshold pointers).  Taken from the by-value argument they stay live in SGPRs from the kernel's entry through every
@@ -573,6 +589,69 @@ __global__ __launch_bounds__(HOP) void k_ola_seam(SeamArgs A) {
     const int64_t gi = chunk * A.om.g_step + (p - A.om.p0);
     if (gi < A.om.g_lo || gi >= A.om.g_hi) continue;
     store_sample(A.om.out, A.om.dtype, row * A.om.stride + gi - A.om.g0, p < G.Lout ? val : 0.f);
+  }
+}
+
+// The tail of the apply kernels and one-pass gates of the same geometries (k_apply_fast512 / 256 / 2048, k_gate_onepass512 /
+// 256 / 2048), per hop of HOP samples and thread (samples s4 .. s4 + 3, a4: their overlap-added sums).
+// A hop that straddles two abutting tiles leaves as a partial sum for k_ola_seam: hop jj of tile `tile` of NF frames, jj < 3
+// (slots 0..2, leading) or jj >= NF (slots 3..5, trailing).
+template <int HOP>
+__device__ __forceinline__ void store_partial_hop(const RegArgs& A, int64_t u, size_t tile, int jj, int NF, int s4, float4 a4) {
+  const int slot = jj < 3 ? jj : 3 + (jj - NF);
+  *reinterpret_cast<float4*>(A.part + ((((size_t)u * A.n_tiles + tile) * 6 + slot) * HOP + s4)) = a4;
+}
+// A complete hop h: envelope normalisation (1 / sum of the four frames' squared windows, or the sum over the frames inside [0, T)
+// at the recording's edges) and store -- one aligned float4 where the hop lies inside the output window and the destination
+// allows, else sample by sample through the output map.
+template <int HOP>
+__device__ __forceinline__ void finish_hop(const RegArgs& A, int64_t row, int64_t chunk, int64_t h, int s4, float4 a4) {
+  const Geom& G = A.g;
+  bool all_valid = true;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int64_t ti = h - q;
+    if (ti < 0 || ti >= G.T) all_valid = false;
+  }
+  if (!A.normalize) {
+  } else if (all_valid) {
+    const float4 n4 = *reinterpret_cast<const float4*>(&A.invn[s4]);
+    a4.x *= n4.x; a4.y *= n4.y; a4.z *= n4.z; a4.w *= n4.w;
+  } else {
+    float4 nrm = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int64_t ti = h - q;
+      if (ti >= 0 && ti < G.T) {
+        const float4 w4 = *reinterpret_cast<const float4*>(&A.wsq[HOP * q + s4]);
+        nrm.x += w4.x; nrm.y += w4.y; nrm.z += w4.z; nrm.w += w4.w;
+      }
+    }
+    a4.x /= (nrm.x > 1e-10f ? nrm.x : 1.f);
+    a4.y /= (nrm.y > 1e-10f ? nrm.y : 1.f);
+    a4.z /= (nrm.z > 1e-10f ? nrm.z : 1.f);
+    a4.w /= (nrm.w > 1e-10f ? nrm.w : 1.f);
+  }
+  {
+    const int64_t pb = h * HOP - G.padL;
+    const int64_t gi0 = chunk * A.om.g_step + (pb - A.om.p0);
+    if (A.om.dtype == 0 && pb >= A.om.p0 && pb + HOP <= A.om.p1 && pb + HOP <= G.Lout && gi0 >= A.om.g_lo &&
+        gi0 + HOP <= A.om.g_hi) {
+      float* dst = (float*)A.om.out + (row * A.om.stride + gi0 - A.om.g0 + s4);
+      if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+        *reinterpret_cast<float4*>(dst) = a4;
+        return;
+      }
+    }
+  }
+  const float vals[4] = {a4.x, a4.y, a4.z, a4.w};
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int64_t p = h * HOP + s4 + e - G.padL;
+    if (p < A.om.p0 || p >= A.om.p1) continue;
+    const int64_t gi = chunk * A.om.g_step + (p - A.om.p0);
+    if (gi < A.om.g_lo || gi >= A.om.g_hi) continue;
+    store_sample(A.om.out, A.om.dtype, row * A.om.stride + gi - A.om.g0, p < G.Lout ? vals[e] : 0.f);
   }
 }
 

@@ -1,22 +1,26 @@
-// One-pass stationary gate for n_fft = win = 2048, hop = 512 (round 6): k_gate_onepass512 (onepass512.hpp) on the transforms of
-// fast2048.hpp -- one real frame per 32 lanes, a tile of 8 frames (4 wavefronts x 2), 1025 bins = 17 bit words per frame.
+// One-pass stationary gate for n_fft = win = 2048, hop = 512 (round 6).
 //
 //   k_decide_fast2048 + k_smooth_bits2 + k_apply_fast2048<K> + k_ola_seam<512, 8>   ->   k_gate_onepass2048 + k_ola_seam<512, 8>
 //
-// Tiles ABUT, as k_apply_fast2048's (overlapping by 3 frames would redo 3 of every 8 transforms): the 3 hops that straddle two
-// tiles leave as partial sums and k_ola_seam (fastpath.hpp) combines them -- the bits are the only exchange inside the launch.
-// Integer smoothing on the matrix cores, with two differences from the 512 / 256 kernels:
-//   * the frequency half-width is 10 bins at 48 kHz, 23 at 22.05 kHz (base.py:100: 500 Hz / (sr / 1024)): a 16-bin output block
-//     reads 16 + 2 nf <= 64 bins = TWO 32-bin k-blocks (band matrices Bf_lo: bins 16 b - 24 .., Bf_hi: bins 16 b + 8 ..), nf <= 24;
-//   * H = bits x band reaches (nf + 1)^2 = 576 > 127 (the int8 range of the second product's operand): it enters the time
-//     product as two base-128 digits, K = At x (H & 127) + 128 At x (H >> 7)   (exact: integers).
-// 8 + 2 nt <= 32 bit rows (nt <= 8) = two 16-row blocks = ONE k-block of the time product.  Six MFMAs per bin block, 65 blocks.
-// The K tile (8 x 1025 uint16) and the bits live in the exchange slices, idle between the transforms; the pair stage reads its
-// mask entries straight from there (k_apply_fast2048<K> reads them from HBM), one barrier before the inverse exchange.
-// Everything else -- tickets, tagged granules, bounded polls / NaN-poisoned output, in-kernel floor test + REDO, spectra
-// parked during the exact re-evaluation -- as onepass512.hpp / onepass.hpp.
+// The tile scaffold is onepass_reg.hpp / fastpath.hpp (store_partial_hop, finish_hop), shared with onepass512.hpp and
+// onepass256.hpp.  This file's own:
+//   * the tile: 8 frames (4 wavefronts x 2), one real frame per 32 lanes on the transforms of fast2048.hpp, 1025 bins = 17 bit
+//     words per frame; decisions in the partner-lane form of k_decide_fast2048, packed with ballots.  Tiles always ABUT, as
+//     k_apply_fast2048's (overlapping by 3 frames would redo 3 of every 8 transforms): the 3 hops that straddle two tiles leave
+//     as partial sums and k_ola_seam (fastpath.hpp) combines them -- there is no overlapping form, the tile step is NF;
+//   * the integer smoothing on the matrix cores, with two differences from the 512 / 256 kernels:
+//       - the frequency half-width is 10 bins at 48 kHz, 23 at 22.05 kHz (base.py:100: 500 Hz / (sr / 1024)): a 16-bin output
+//         block reads 16 + 2 nf <= 64 bins = TWO 32-bin k-blocks (band matrices Bf_lo: bins 16 b - 24 .., Bf_hi: bins 16 b + 8 ..),
+//         nf <= 24;
+//       - H = bits x band reaches (nf + 1)^2 = 576 > 127 (the int8 range of the second product's operand): it enters the time
+//         product as two base-128 digits, K = At x (H & 127) + 128 At x (H >> 7)   (exact: integers).
+//     8 + 2 nt <= 32 bit rows (nt <= 8) = two 16-row blocks = ONE k-block of the time product.  Six MFMAs per bin block, 65 blocks.
+//   * the K tile (8 x 1025 uint16) and the bits live in the exchange slices, idle between the transforms; the pair stage reads its
+//     mask entries straight from there (k_apply_fast2048<K> reads them from HBM), one barrier before the inverse exchange; the
+//     overlap-add runs over the whole workgroup's hop buffer in four ordered rounds.
 #pragma once
 #include "fast2048.hpp"
+#include "onepass_reg.hpp"
 
 namespace sg {
 namespace fast {
@@ -48,53 +52,23 @@ __global__ __launch_bounds__(WAVES * 64, O20_OCC) void k_gate_onepass2048(OnePas
   if (REDO && A.fl.alim[1] != A.tc.need_tag) return;   // no unit of this call reported (the common case)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 5, c = lane & 31;
   const Geom& G = A.g;
-  if (tid == 0) {
-    s_misc[0] = atomicAdd(P.ticket, 1u) - P.ticket_base;
-    s_misc[1] = 0u;
-  }
+  reg_draw_ticket(P, s_misc, tid);
   s_exp[tid] = P.tab[192 + tid];
   const unsigned fl_bound = REDO ? 0xffffffffu : floor_lazy_bound(A.fl, lane);
   __syncthreads();
-  const int ntt = P.n_tiles + 2;                   // tiles per unit incl. one decide-only halo tile per side
-  const unsigned ticket = s_misc[0];
-  const int64_t u = ticket / (unsigned)ntt;
-  const int jt = (int)(ticket % (unsigned)ntt) - 1;
-  const bool halo_tile = jt < 0 || jt >= P.n_tiles;
-  const unsigned gu = (unsigned)(A.view.unit0 + u), nch = (unsigned)A.view.n_chunks;
-  const int64_t row = gu / nch;
-  const int64_t chunk = A.view.c0 + gu % nch;
-  const bool lazy = A.fl.alim != nullptr;
-  const int need = (lazy && !REDO) ? 0 : need_of(A.tc, u);
-  if (REDO && need == 0) return;   // whole workgroup
-  if (!REDO && lazy && ticket == 0u && tid == 0) P.ticket[8] = 0u;   // (the second launch's counter starts from zero)
-  const bool floor_live = need == 1;
-  auto t2eff = [&](int f) -> double {
-    double v = A.tc.T2[f];
-    if (floor_live) {
-      const double fl = cell_db(A.tc.pmax[u * G.FS + f], A.mag_scale) - A.top_db;
-      if (fl > A.tc.thresh[f]) v = -1.0;
-    }
-    if (need == 2) v = T2_NEVER;
-    return v;
-  };
-  stage_t2_plain<WAVES * 64, F20_F>(s_t2, A.tc.T2, need, 4.0, tid, t2eff);
+  const RegTile W = reg_tile_of<REDO>(P, s_misc[0], tid);   // (ticket 0 of a first launch: also zeroes the REDO launch's counter)
+  if (REDO && W.need == 0) return;   // whole workgroup
+  const int64_t u = W.u, row = W.row, chunk = W.chunk;
+  const int jt = W.jt, need = W.need;
+  const bool floor_live = W.floor_live;
+  stage_t2_plain<WAVES * 64, F20_F>(s_t2, A.tc.T2, need, 4.0, tid,
+                                 [&](int f) { return t2_effective(A.tc, u, G.FS, f, need, floor_live, A.mag_scale, A.top_db); });
   constexpr int NF = O20_NF;
   const int64_t tf0 = A.h_begin - 3 + (int64_t)jt * NF;   // first frame of the tile
   cf v[32];
   bool valid;
   unsigned fl_mx = f20_gather<WAVES, true>(A, tw, regions, row, chunk, tf0, v, valid);
-  if (!REDO && lazy) {   // the unit window's samples no tile stages: dealt to the unit's tiles in slices (onepass512.hpp)
-    constexpr int SPAN = (NF - 1 + 4) * F20_H;
-    const int64_t g0 = chunk * A.view.cs - A.view.pad;
-    const int64_t s_lo = max<int64_t>(0, A.view.lo - g0), s_hi = min<int64_t>(A.view.Lp, A.view.hi - g0);
-    const int64_t sp0 = (A.h_begin - 3 - NF) * F20_H - G.padL;
-    const int64_t sp1 = (A.h_begin - 3 + (int64_t)P.n_tiles * NF) * F20_H - G.padL + SPAN;
-    const int64_t first = min(s_hi, max(s_lo, sp0)), last = max(s_lo, min(s_hi, sp1));
-    const int64_t lenA = first - s_lo;
-    const int64_t c0 = (int64_t)(jt + 1) * P.scan_q, c1 = min(c0 + P.scan_q, lenA + (s_hi - last));
-    for (int64_t i = c0 + tid; i < c1; i += WAVES * 64)
-      fl_mx = max(fl_mx, __float_as_uint((float)view_sample(A.view, row, chunk, i < lenA ? s_lo + i : last + (i - lenA))) & 0x7fffffffu);
-  }
+  if (!REDO && W.lazy) floor_scan_padding<WAVES * 64, F20_H, NF>(A, P, row, chunk, jt, NF, tid, fl_mx);   // the padding no tile stages
   if (!REDO) floor_lazy_report(A.tc, A.fl, fl_bound, fl_mx, u, G.FS, lane);
   const int64_t tq = tf0 + 2 * wave;
   // ---- forward transform + decisions (k_decide_fast2048) ------------------------------------------------------
@@ -150,15 +124,10 @@ __global__ __launch_bounds__(WAVES * 64, O20_OCC) void k_gate_onepass2048(OnePas
     }
     if (need == 2 || !valid) { pred = 0; amb = 0; predN = false; ambN = false; }
     // exact re-evaluation of ambiguous cells, one at a time, whole wave cooperating; half of the spectra parked in the wave's
-    // idle exchange slice for the duration (onepass512.hpp)
+    // idle exchange slice for the duration (onepass_reg.hpp: park_upper_half)
     if (__ballot(amb != 0 || ambN) != 0ull) {
       float* park = reinterpret_cast<float*>(regions + wave * WAVE_CX_H) + lane;
-      static_assert(64 * 32 * 4 <= WAVE_CX_H * 8, "parked registers must fit the wave's slice");
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        park[(2 * i) * 64] = v[16 + i].x;
-        park[(2 * i + 1) * 64] = v[16 + i].y;
-      }
+      park_upper_half(v, park);
       while (true) {
         const unsigned long long pending = __ballot(amb != 0 || ambN);
         if (pending == 0) break;
@@ -169,13 +138,7 @@ __global__ __launch_bounds__(WAVES * 64, O20_OCC) void k_gate_onepass2048(OnePas
         const int f = q < 32 ? cs + 32 * q : 1024;
         const RegArgs& L = *late_args<RegArgs>();     // (cold path: arguments re-read here; A is the FIRST member)
         const double Pe = f20_exact_power(L, row, chunk, tq + gs, f, lane);
-        double t2 = L.tc.T2[f];
-        if (floor_live) {
-          const double fl = cell_db(L.tc.pmax[u * (int64_t)L.g.FS + f], L.mag_scale) - L.top_db;
-          if (fl > L.tc.thresh[f]) t2 = -1.0;
-        }
-        if (need == 2) t2 = T2_NEVER;
-        const bool pass = Pe > t2;
+        const bool pass = Pe > t2_effective(L.tc, u, L.g.FS, f, need, floor_live, L.mag_scale, L.top_db);
         if (lane == sl) {
           if (q < 32) {
             pred = (pred & ~(1u << q)) | ((pass ? 1u : 0u) << q);
@@ -187,11 +150,7 @@ __global__ __launch_bounds__(WAVES * 64, O20_OCC) void k_gate_onepass2048(OnePas
         }
       }
       wave_lds_sync();
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        v[16 + i].x = park[(2 * i) * 64];
-        v[16 + i].y = park[(2 * i + 1) * 64];
-      }
+      unpark_upper_half(v, park);
       wave_lds_sync();
     }
     // pack (k_decide_fast2048): the ballot of register k2 is, per frame, the 32 bins 32 k2 .. 32 k2 + 31 in natural order
@@ -209,13 +168,13 @@ __global__ __launch_bounds__(WAVES * 64, O20_OCC) void k_gate_onepass2048(OnePas
   }
   // ---- publish this tile's bits; the spectra stay in v[] --------------------------------------------------------
   const int fr = 2 * wave + g;      // tile row of this lane group's frame
-  unsigned long long* xb_mine = P.xbits + ((size_t)u * ntt + (jt + 1)) * O20_TILE_WORDS;
+  unsigned long long* xb_mine = P.xbits + ((size_t)u * W.ntt + (jt + 1)) * O20_TILE_WORDS;
   if (c < O20_XW) {
     const op_v4u ga = {(unsigned)myword, P.epoch, (unsigned)(myword >> 32), P.epoch};
     op_st16_sc1(&xb_mine[(fr * O20_XW + c) * 2], ga);
   }
   __syncthreads();   // every wave is past its forward exchange: the slices are idle from here
-  if (halo_tile) return;
+  if (W.halo_tile) return;
 
   // ---- integer smoothing on the matrix cores ---------------------------------------------------------------------
   const int nt = P.nt;
@@ -224,34 +183,8 @@ __global__ __launch_bounds__(WAVES * 64, O20_OCC) void k_gate_onepass2048(OnePas
   unsigned short* Ks = reinterpret_cast<unsigned short*>(arena + (size_t)O20_ROWS * O20_BW * 8);     // [8][O20_KP]
   static_assert(O20_ROWS * O20_BW * 8 + O20_NF * O20_KP * 2 <= WAVES * WAVE_CX_H * 8, "bits + K tile must fit the exchange slices");
   if (c < O20_XW) brow[(nt + fr) * O20_BW + 1 + c] = myword;
-  for (int r = tid; r < O20_ROWS; r += WAVES * 64) {
-    brow[r * O20_BW] = 0ull;
-    brow[r * O20_BW + O20_BW - 1] = 0ull;
-    if (r >= NF + 2 * nt) {       // rows past the neighbours': zero (the k-block reads them)
-#pragma unroll
-      for (int w = 1; w <= O20_XW; ++w) brow[r * O20_BW + w] = 0ull;
-    }
-  }
-  // neighbour rows: one 16-byte load per 64-bit word (2 nt x 17 words <= 272), polled until both tags are current
-  for (int i = tid; i < 2 * nt * O20_XW; i += WAVES * 64) {
-    const int side = i >= nt * O20_XW;
-    const int rem = i - side * nt * O20_XW;
-    const int rr = rem / O20_XW, w = rem - rr * O20_XW;
-    // tile j - 1 holds frames tf0 - 8 ..: frame tf0 - nt + rr is its row 8 - nt + rr; tile j + 1: frame tf0 + 8 + rr is its row rr
-    const unsigned long long* sp = side ? xb_mine + O20_TILE_WORDS + (rr * O20_XW + w) * 2
-                                        : xb_mine - O20_TILE_WORDS + ((NF - nt + rr) * O20_XW + w) * 2;
-    op_v4u gr = op_ld16_sc1(sp);
-    for (int spin = 0; gr[1] != P.poll_epoch || gr[3] != P.poll_epoch; ++spin) {
-      if (spin >= P.spin_max) {   // bounded: report instead of hanging the device
-        atomicOr_system(P.err, 1u);
-        s_misc[1] = 1u;            // the tile's mask is unknown: every hop it touches becomes NaN
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
-      gr = op_ld16_sc1(sp);
-    }
-    brow[(side ? nt + NF + rr : rr) * O20_BW + 1 + w] = (unsigned long long)gr[0] | ((unsigned long long)gr[2] << 32);
-  }
+  zero_bit_row_margins<NF, O20_XW, O20_ROWS, WAVES * 64>(brow, nt, tid);
+  poll_neighbour_rows<NF, O20_XW, O20_BW, WAVES * 64>(xb_mine, NF, nt, P, s_misc, brow, tid);
   const int q4 = lane >> 4, j16 = lane & 15;
   const long Bl = (long)P.tab[lane], Bh = (long)P.tab[64 + lane], At = (long)P.tab[128 + lane];
   __syncthreads();
@@ -260,8 +193,7 @@ __global__ __launch_bounds__(WAVES * 64, O20_OCC) void k_gate_onepass2048(OnePas
     // for the two row blocks (result: lane = bin column, 4 consecutive rows per lane group = the B layout of the time product);
     //   K[frame][bin] = sum_slot vt[row(slot) - nt - frame] H[row(slot)][bin],   k-slot 8 q + e = row 4 q + e of block 0 (e < 4) / 1
     // on the two base-128 digits of H.  Output frames 0..7 = lane groups q4 < 2.
-    typedef int o20_v4i __attribute__((ext_vector_type(4)));
-    const o20_v4i zero4 = {0, 0, 0, 0};
+    const reg_v4i zero4 = {0, 0, 0, 0};
     const unsigned char* wbb = reinterpret_cast<const unsigned char*>(brow);
     constexpr int WPB = O20_BW * 8;
     for (int b = wave; b < 65; b += WAVES) {
@@ -270,21 +202,18 @@ __global__ __launch_bounds__(WAVES * 64, O20_OCC) void k_gate_onepass2048(OnePas
       for (int m = 0; m < 2; ++m) {
         const unsigned char* rp = wbb + (16 * m + j16) * WPB + q4 + 2 * b;
         const long a0 = (long)s_exp[rp[5]], a1 = (long)s_exp[rp[9]];
-        o20_v4i hv = __builtin_amdgcn_mfma_i32_16x16x32_i8(a0, Bl, zero4, 0, 0, 0);
+        reg_v4i hv = __builtin_amdgcn_mfma_i32_16x16x32_i8(a0, Bl, zero4, 0, 0, 0);
         hv = __builtin_amdgcn_mfma_i32_16x16x32_i8(a1, Bh, hv, 0, 0, 0);
         lo[m] = ((unsigned)hv[0] & 127u) | (((unsigned)hv[1] & 127u) << 8) | (((unsigned)hv[2] & 127u) << 16) | (((unsigned)hv[3] & 127u) << 24);
         hi[m] = ((unsigned)hv[0] >> 7) | (((unsigned)hv[1] >> 7) << 8) | (((unsigned)hv[2] >> 7) << 16) | (((unsigned)hv[3] >> 7) << 24);
       }
       const long bt0 = (long)(((unsigned long long)lo[1] << 32) | (unsigned long long)lo[0]);
       const long bt1 = (long)(((unsigned long long)hi[1] << 32) | (unsigned long long)hi[0]);
-      const o20_v4i d0 = __builtin_amdgcn_mfma_i32_16x16x32_i8(At, bt0, zero4, 0, 0, 0);
-      const o20_v4i d1 = __builtin_amdgcn_mfma_i32_16x16x32_i8(At, bt1, zero4, 0, 0, 0);
+      const reg_v4i d0 = __builtin_amdgcn_mfma_i32_16x16x32_i8(At, bt0, zero4, 0, 0, 0);
+      const reg_v4i d1 = __builtin_amdgcn_mfma_i32_16x16x32_i8(At, bt1, zero4, 0, 0, 0);
       if (q4 < 2) {
         unsigned short* kd = Ks + (4 * q4) * O20_KP + 16 * b + j16;
-        kd[0] = (unsigned short)(d0[0] + (d1[0] << 7));
-        kd[O20_KP] = (unsigned short)(d0[1] + (d1[1] << 7));
-        kd[2 * O20_KP] = (unsigned short)(d0[2] + (d1[2] << 7));
-        kd[3 * O20_KP] = (unsigned short)(d0[3] + (d1[3] << 7));
+        store_k4(kd, O20_KP, d0 + (d1 << 7));
       }
     }
   }
@@ -366,57 +295,11 @@ __global__ __launch_bounds__(WAVES * 64, O20_OCC) void k_gate_onepass2048(OnePas
     if (h < A.h_begin || h >= A.h_end) continue;
     float4 a4 = *reinterpret_cast<const float4*>(&hop[jj * F20_XP + s4]);
     a4.x += poison; a4.y += poison; a4.z += poison; a4.w += poison;
-    if (jj < 3 || jj >= NF) {   // straddling hop: partial sum only; slots 0..2 leading, 3..5 trailing
-      const int slot = jj < 3 ? jj : 3 + (jj - NF);
-      *reinterpret_cast<float4*>(A.part + ((((size_t)u * A.n_tiles + jt) * 6 + slot) * 512 + s4)) = a4;
+    if (jj < 3 || jj >= NF) {   // straddling hop: partial sum only (poisoned with the tile), k_ola_seam finishes it
+      store_partial_hop<F20_H>(A, u, jt, jj, NF, s4, a4);
       continue;
     }
-    bool all_valid = true;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int64_t ti = h - q;
-      if (ti < 0 || ti >= G.T) all_valid = false;
-    }
-    if (!A.normalize) {
-    } else if (all_valid) {
-      const float4 n4 = *reinterpret_cast<const float4*>(&A.invn[s4]);
-      a4.x *= n4.x; a4.y *= n4.y; a4.z *= n4.z; a4.w *= n4.w;
-    } else {
-      float4 nrm = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int64_t ti = h - q;
-        if (ti >= 0 && ti < G.T) {
-          const float4 w4 = *reinterpret_cast<const float4*>(&A.wsq[F20_H * q + s4]);
-          nrm.x += w4.x; nrm.y += w4.y; nrm.z += w4.z; nrm.w += w4.w;
-        }
-      }
-      a4.x /= (nrm.x > 1e-10f ? nrm.x : 1.f);
-      a4.y /= (nrm.y > 1e-10f ? nrm.y : 1.f);
-      a4.z /= (nrm.z > 1e-10f ? nrm.z : 1.f);
-      a4.w /= (nrm.w > 1e-10f ? nrm.w : 1.f);
-    }
-    {
-      const int64_t pb = h * F20_H - G.padL;
-      const int64_t gi0 = chunk * A.om.g_step + (pb - A.om.p0);
-      if (A.om.dtype == 0 && pb >= A.om.p0 && pb + F20_H <= A.om.p1 && pb + F20_H <= G.Lout && gi0 >= A.om.g_lo &&
-          gi0 + F20_H <= A.om.g_hi) {
-        float* dst = (float*)A.om.out + (row * A.om.stride + gi0 - A.om.g0 + s4);
-        if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
-          *reinterpret_cast<float4*>(dst) = a4;
-          continue;
-        }
-      }
-    }
-    const float vals[4] = {a4.x, a4.y, a4.z, a4.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int64_t p = h * F20_H + s4 + e - G.padL;
-      if (p < A.om.p0 || p >= A.om.p1) continue;
-      const int64_t gi = chunk * A.om.g_step + (p - A.om.p0);
-      if (gi < A.om.g_lo || gi >= A.om.g_hi) continue;
-      store_sample(A.om.out, A.om.dtype, row * A.om.stride + gi - A.om.g0, p < G.Lout ? vals[e] : 0.f);
-    }
+    finish_hop<F20_H>(A, row, chunk, h, s4, a4);
   }
 }
 

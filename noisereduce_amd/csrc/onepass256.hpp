@@ -1,16 +1,19 @@
-// One-pass stationary gate for n_fft = win = 256, hop = 64 (round 6): k_gate_onepass512 (onepass512.hpp) on the transforms of
-// fast256.hpp -- four real frames per 512-point register transform, a tile of 64 frames (abutting tiles + k_ola_seam by default,
-// 61 complete hops per tile with SG_OPT_FORCE_NOSEAM: onepass512.hpp), 129 bins = 3 bit words per frame.
+// One-pass stationary gate for n_fft = win = 256, hop = 64 (round 6).
 //
 //   k_decide_fast256 + k_smooth_bits2 + k_apply_fast256<K>   ->   k_gate_onepass256   (no bit field, no K field in HBM)
 //
-// Integer smoothing on the matrix cores: 9 blocks of 16 bit rows (64 + 2 nt <= 144) x 9 blocks of 16 bins; per bin block
-// H = bits x band matrix for the nine row blocks, then K = time weights x H for the four 16-frame blocks of the tile, each
-// reaching 16 + 2 nt <= 96 rows = three k-blocks of 32 (the third only when nt > 24: at 48 kHz the 50 ms window is 37 frames).
-// Everything else -- tickets, tagged granules, bounded polls / NaN-poisoned output, in-kernel floor test + REDO, spectra
-// parked during the exact re-evaluation -- as onepass512.hpp / onepass.hpp.
+// The tile scaffold is onepass_reg.hpp / fastpath.hpp (store_partial_hop, finish_hop), shared with onepass512.hpp and
+// onepass2048.hpp.  This file's own:
+//   * the tile: 64 frames, FOUR real frames per 512-point register transform of fast256.hpp, 129 bins = 3 bit words per frame
+//     (abutting tiles + k_ola_seam by default, 61 complete hops per tile with SG_OPT_FORCE_NOSEAM); decisions on the four-frame
+//     split (the bits of k_decide_fast256), packed with ballots;
+//   * the integer smoothing on the matrix cores: 9 blocks of 16 bit rows (64 + 2 nt <= 144) x 9 blocks of 16 bins; per bin block
+//     H = bits x band matrix for the nine row blocks, then K = time weights x H for the four 16-frame blocks of the tile, each
+//     reaching 16 + 2 nt <= 96 rows = three k-blocks of 32 (the third only when nt > 24: at 48 kHz the 50 ms window is 37 frames);
+//   * x mask, merge, inverse transform and the wave-private overlap-add of k_apply_fast256<K>.
 #pragma once
 #include "fast256.hpp"
+#include "onepass_reg.hpp"
 
 namespace sg {
 namespace fast {
@@ -43,36 +46,17 @@ __global__ __launch_bounds__(WAVES * 64, O25_OCC) void k_gate_onepass256(OnePass
   if (REDO && A.fl.alim[1] != A.tc.need_tag) return;   // no unit of this call reported (the common case)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15, cp = c >> 1;
   const Geom& G = A.g;
-  if (tid == 0) {
-    s_misc[0] = atomicAdd(P.ticket, 1u) - P.ticket_base;
-    s_misc[1] = 0u;
-  }
+  reg_draw_ticket(P, s_misc, tid);
   s_exp[tid] = P.tab[256 + tid];
   const unsigned fl_bound = REDO ? 0xffffffffu : floor_lazy_bound(A.fl, lane);
   __syncthreads();
-  const int ntt = P.n_tiles + 2;
-  const unsigned ticket = s_misc[0];
-  const int64_t u = ticket / (unsigned)ntt;
-  const int jt = (int)(ticket % (unsigned)ntt) - 1;
-  const bool halo_tile = jt < 0 || jt >= P.n_tiles;
-  const unsigned gu = (unsigned)(A.view.unit0 + u), nch = (unsigned)A.view.n_chunks;
-  const int64_t row = gu / nch;
-  const int64_t chunk = A.view.c0 + gu % nch;
-  const bool lazy = A.fl.alim != nullptr;
-  const int need = (lazy && !REDO) ? 0 : need_of(A.tc, u);
-  if (REDO && need == 0) return;   // whole workgroup
-  if (!REDO && lazy && ticket == 0u && tid == 0) P.ticket[8] = 0u;
-  const bool floor_live = need == 1;
-  auto t2eff = [&](int f) -> double {
-    double v = A.tc.T2[f];
-    if (floor_live) {
-      const double fl = cell_db(A.tc.pmax[u * G.FS + f], A.mag_scale) - A.top_db;
-      if (fl > A.tc.thresh[f]) v = -1.0;
-    }
-    if (need == 2) v = T2_NEVER;
-    return v;
-  };
-  stage_t2_plain<WAVES * 64, F25_F>(s_t2, A.tc.T2, need, 4.0, tid, t2eff);
+  const RegTile W = reg_tile_of<REDO>(P, s_misc[0], tid);   // (ticket 0 of a first launch: also zeroes the REDO launch's counter)
+  if (REDO && W.need == 0) return;   // whole workgroup
+  const int64_t u = W.u, row = W.row, chunk = W.chunk;
+  const int jt = W.jt, need = W.need;
+  const bool floor_live = W.floor_live;
+  stage_t2_plain<WAVES * 64, F25_F>(s_t2, A.tc.T2, need, 4.0, tid,
+                                 [&](int f) { return t2_effective(A.tc, u, G.FS, f, need, floor_live, A.mag_scale, A.top_db); });
   constexpr int NF = O25_NF, NH = O25_NH;
   const bool seam = A.part != nullptr;   // abutting tiles + k_ola_seam (fastpath.hpp); else tiles that overlap by 3 frames
   const int step = seam ? NF : NH;       // frames from one tile to the next
@@ -80,18 +64,7 @@ __global__ __launch_bounds__(WAVES * 64, O25_OCC) void k_gate_onepass256(OnePass
   cf v[32];
   bool validX, validY;
   unsigned fl_mx = f25_gather<WAVES, true>(A, tw512, regions, swin, row, chunk, tf0, v, validX, validY);
-  if (!REDO && lazy) {   // the unit window's samples no tile stages: dealt to the unit's tiles in slices (onepass512.hpp)
-    constexpr int SPAN = (NF - 1 + 4) * F25_H;
-    const int64_t g0 = chunk * A.view.cs - A.view.pad;
-    const int64_t s_lo = max<int64_t>(0, A.view.lo - g0), s_hi = min<int64_t>(A.view.Lp, A.view.hi - g0);
-    const int64_t sp0 = (A.h_begin - 3 - step) * F25_H - G.padL;
-    const int64_t sp1 = (A.h_begin - 3 + (int64_t)P.n_tiles * step) * F25_H - G.padL + SPAN;
-    const int64_t first = min(s_hi, max(s_lo, sp0)), last = max(s_lo, min(s_hi, sp1));
-    const int64_t lenA = first - s_lo;
-    const int64_t c0 = (int64_t)(jt + 1) * P.scan_q, c1 = min(c0 + P.scan_q, lenA + (s_hi - last));
-    for (int64_t i = c0 + tid; i < c1; i += WAVES * 64)
-      fl_mx = max(fl_mx, __float_as_uint((float)view_sample(A.view, row, chunk, i < lenA ? s_lo + i : last + (i - lenA))) & 0x7fffffffu);
-  }
+  if (!REDO && W.lazy) floor_scan_padding<WAVES * 64, F25_H, NF>(A, P, row, chunk, jt, step, tid, fl_mx);   // the padding no tile stages
   if (!REDO) floor_lazy_report(A.tc, A.fl, fl_bound, fl_mx, u, G.FS, lane);
   const int64_t tq = tf0 + F25_FPW * wave;
   // ---- forward transform + decisions (k_decide_fast256) -------------------------------------------------------
@@ -148,12 +121,7 @@ __global__ __launch_bounds__(WAVES * 64, O25_OCC) void k_gate_onepass256(OnePass
     // exact re-evaluation of ambiguous cells; half of the spectra parked in the wave's idle exchange slice meanwhile
     if (__ballot(am != 0 || a128 != 0) != 0ull) {
       float* park = reinterpret_cast<float*>(regions + wave * WAVE_CX_H) + lane;
-      static_assert(64 * 32 * 4 <= WAVE_CX_H * 8, "parked registers must fit the wave's slice");
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        park[(2 * i) * 64] = v[16 + i].x;
-        park[(2 * i + 1) * 64] = v[16 + i].y;
-      }
+      park_upper_half(v, park);
       while (true) {
         const unsigned long long pending = __ballot(am != 0 || a128 != 0);
         if (pending == 0) break;
@@ -166,24 +134,14 @@ __global__ __launch_bounds__(WAVES * 64, O25_OCC) void k_gate_onepass256(OnePass
         const int64_t t = tq + 4 * gs + fr;
         const RegArgs& L = *late_args<RegArgs>();     // (A is the FIRST member of the kernel's argument)
         const double Pe = f25_exact_power(L, row, chunk, t, f, lane);
-        double t2 = L.tc.T2[f];
-        if (floor_live) {
-          const double fl = cell_db(L.tc.pmax[u * (int64_t)L.g.FS + f], L.mag_scale) - L.top_db;
-          if (fl > L.tc.thresh[f]) t2 = -1.0;
-        }
-        if (need == 2) t2 = T2_NEVER;
-        const bool pass = Pe > t2;
+        const bool pass = Pe > t2_effective(L.tc, u, L.g.FS, f, need, floor_live, L.mag_scale, L.top_db);
         if (lane == src) {
           if (q >= 0) { pr = (pr & ~(1u << q)) | ((pass ? 1u : 0u) << q); am &= ~(1u << q); }
           else { p128 = (p128 & ~(1u << fr)) | ((pass ? 1u : 0u) << fr); a128 &= ~(1u << fr); }
         }
       }
       wave_lds_sync();
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        v[16 + i].x = park[(2 * i) * 64];
-        v[16 + i].y = park[(2 * i + 1) * 64];
-      }
+      unpark_upper_half(v, park);
       wave_lds_sync();
     }
     // pack (k_decide_fast256)
@@ -210,13 +168,13 @@ __global__ __launch_bounds__(WAVES * 64, O25_OCC) void k_gate_onepass256(OnePass
   // ---- publish this tile's bits; the spectra stay in v[] --------------------------------------------------------
   const int fq = F25_FPW * wave + 4 * g;     // tile row of the group's first frame
   const int my_row = fq + (c >> 2), my_w = c & 3;
-  unsigned long long* xb_mine = P.xbits + ((size_t)u * ntt + (jt + 1)) * O25_TILE_WORDS;
+  unsigned long long* xb_mine = P.xbits + ((size_t)u * W.ntt + (jt + 1)) * O25_TILE_WORDS;
   if (my_w < O25_XW) {
     const op_v4u gr = {(unsigned)mine, P.epoch, (unsigned)(mine >> 32), P.epoch};
     op_st16_sc1(&xb_mine[(my_row * O25_XW + my_w) * 2], gr);
   }
   __syncthreads();   // every wave is past its forward exchange: the slices are idle from here
-  if (halo_tile) return;
+  if (W.halo_tile) return;
 
   // ---- integer smoothing on the matrix cores --------------------------------------------------------------------
   const int nt = P.nt;
@@ -225,40 +183,14 @@ __global__ __launch_bounds__(WAVES * 64, O25_OCC) void k_gate_onepass256(OnePass
   unsigned short* Ks = reinterpret_cast<unsigned short*>(arena + (size_t)O25_ROWS * O25_BW * 8);     // [64][O25_KP]
   static_assert(O25_ROWS * O25_BW * 8 + O25_NF * O25_KP * 2 <= WAVES * WAVE_CX_H * 8, "bits + K tile must fit the exchange slices");
   if (my_w < O25_XW) brow[(nt + my_row) * O25_BW + 1 + my_w] = mine;
-  for (int r = tid; r < O25_ROWS; r += WAVES * 64) {
-    brow[r * O25_BW] = 0ull;
-    brow[r * O25_BW + O25_BW - 1] = 0ull;
-    if (r >= NF + 2 * nt) {
-#pragma unroll
-      for (int w = 1; w <= O25_XW; ++w) brow[r * O25_BW + w] = 0ull;
-    }
-  }
-  for (int i = tid; i < 2 * nt * O25_XW; i += WAVES * 64) {
-    const int side = i >= nt * O25_XW;
-    const int rem = i - side * nt * O25_XW;
-    const int rr = rem / O25_XW, w = rem - rr * O25_XW;
-    // tile j - 1 holds frames tf0 - step ..: frame tf0 - nt + rr is its row step - nt + rr; tile j + 1: frame tf0 + 64 + rr is its row 64 - step + rr
-    const unsigned long long* src = side ? xb_mine + O25_TILE_WORDS + ((NF - step + rr) * O25_XW + w) * 2
-                                         : xb_mine - O25_TILE_WORDS + ((step - nt + rr) * O25_XW + w) * 2;
-    op_v4u gr = op_ld16_sc1(src);
-    for (int spin = 0; gr[1] != P.poll_epoch || gr[3] != P.poll_epoch; ++spin) {
-      if (spin >= P.spin_max) {
-        atomicOr_system(P.err, 1u);
-        s_misc[1] = 1u;
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
-      gr = op_ld16_sc1(src);
-    }
-    brow[(side ? nt + NF + rr : rr) * O25_BW + 1 + w] = (unsigned long long)gr[0] | ((unsigned long long)gr[2] << 32);
-  }
+  zero_bit_row_margins<NF, O25_XW, O25_ROWS, WAVES * 64>(brow, nt, tid);
+  poll_neighbour_rows<NF, O25_XW, O25_BW, WAVES * 64>(xb_mine, step, nt, P, s_misc, brow, tid);
   const int q4 = lane >> 4, j16 = lane & 15;
   const long Bf = (long)P.tab[lane], At1 = (long)P.tab[64 + lane], At2 = (long)P.tab[128 + lane], At3 = (long)P.tab[192 + lane];
   const bool three = 2 * nt > 48;      // a third k-block of rows (wave-uniform)
   __syncthreads();
   {
-    typedef int o25_v4i __attribute__((ext_vector_type(4)));
-    const o25_v4i zero4 = {0, 0, 0, 0};
+    const reg_v4i zero4 = {0, 0, 0, 0};
     const unsigned char* wbb = reinterpret_cast<const unsigned char*>(brow);
     constexpr int WPB = O25_BW * 8;
     for (int b = wave; b < 9; b += WAVES) {
@@ -266,7 +198,7 @@ __global__ __launch_bounds__(WAVES * 64, O25_OCC) void k_gate_onepass256(OnePass
 #pragma unroll
       for (int m = 0; m < 9; ++m) {
         const long a = (long)s_exp[wbb[(16 * m + j16) * WPB + 7 + q4 + 2 * b]];
-        const o25_v4i hv = __builtin_amdgcn_mfma_i32_16x16x32_i8(a, Bf, zero4, 0, 0, 0);
+        const reg_v4i hv = __builtin_amdgcn_mfma_i32_16x16x32_i8(a, Bf, zero4, 0, 0, 0);
         hp[m] = (unsigned)hv[0] | ((unsigned)hv[1] << 8) | ((unsigned)hv[2] << 16) | ((unsigned)hv[3] << 24);
       }
       hp[9] = 0u;
@@ -274,17 +206,14 @@ __global__ __launch_bounds__(WAVES * 64, O25_OCC) void k_gate_onepass256(OnePass
       for (int o = 0; o < 4; ++o) {   // output frames 16 o + j at bit row nt + 16 o + j: row blocks o .. o + 5
         const long bt1 = (long)(((unsigned long long)hp[o + 1] << 32) | (unsigned long long)hp[o]);
         const long bt2 = (long)(((unsigned long long)hp[o + 3] << 32) | (unsigned long long)hp[o + 2]);
-        o25_v4i d = __builtin_amdgcn_mfma_i32_16x16x32_i8(At1, bt1, zero4, 0, 0, 0);
+        reg_v4i d = __builtin_amdgcn_mfma_i32_16x16x32_i8(At1, bt1, zero4, 0, 0, 0);
         d = __builtin_amdgcn_mfma_i32_16x16x32_i8(At2, bt2, d, 0, 0, 0);
         if (three) {
           const long bt3 = (long)(((unsigned long long)hp[o + 5 < 10 ? o + 5 : 9] << 32) | (unsigned long long)hp[o + 4]);
           d = __builtin_amdgcn_mfma_i32_16x16x32_i8(At3, bt3, d, 0, 0, 0);
         }
         unsigned short* kd = Ks + (16 * o + 4 * q4) * O25_KP + 16 * b + j16;
-        kd[0] = (unsigned short)d[0];
-        kd[O25_KP] = (unsigned short)d[1];
-        kd[2 * O25_KP] = (unsigned short)d[2];
-        kd[3 * O25_KP] = (unsigned short)d[3];
+        store_k4(kd, O25_KP, d);
       }
     }
   }
@@ -392,57 +321,11 @@ __global__ __launch_bounds__(WAVES * 64, O25_OCC) void k_gate_onepass256(OnePass
       a4.x += f4.x; a4.y += f4.y; a4.z += f4.z; a4.w += f4.w;
     }
     a4.x += poison; a4.y += poison; a4.z += poison; a4.w += poison;
-    if (seam && (jj < 3 || jj >= NF)) {   // straddling hop: partial sum only (poisoned with the tile); slots 0..2 leading, 3..5 trailing
-      const int slot = jj < 3 ? jj : 3 + (jj - NF);
-      *reinterpret_cast<float4*>(A.part + ((((size_t)u * A.n_tiles + jt) * 6 + slot) * F25_H + s4)) = a4;
+    if (seam && (jj < 3 || jj >= NF)) {   // straddling hop: partial sum only (poisoned with the tile), k_ola_seam finishes it
+      store_partial_hop<F25_H>(A, u, jt, jj, NF, s4, a4);
       continue;
     }
-    bool all_valid = true;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int64_t ti = h - q;
-      if (ti < 0 || ti >= G.T) all_valid = false;
-    }
-    if (!A.normalize) {
-    } else if (all_valid) {
-      const float4 n4 = *reinterpret_cast<const float4*>(&A.invn[s4]);
-      a4.x *= n4.x; a4.y *= n4.y; a4.z *= n4.z; a4.w *= n4.w;
-    } else {
-      float4 nrm = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int64_t ti = h - q;
-        if (ti >= 0 && ti < G.T) {
-          const float4 w4 = *reinterpret_cast<const float4*>(&A.wsq[F25_H * q + s4]);
-          nrm.x += w4.x; nrm.y += w4.y; nrm.z += w4.z; nrm.w += w4.w;
-        }
-      }
-      a4.x /= (nrm.x > 1e-10f ? nrm.x : 1.f);
-      a4.y /= (nrm.y > 1e-10f ? nrm.y : 1.f);
-      a4.z /= (nrm.z > 1e-10f ? nrm.z : 1.f);
-      a4.w /= (nrm.w > 1e-10f ? nrm.w : 1.f);
-    }
-    {
-      const int64_t pb = h * F25_H - G.padL;
-      const int64_t gi0 = chunk * A.om.g_step + (pb - A.om.p0);
-      if (A.om.dtype == 0 && pb >= A.om.p0 && pb + F25_H <= A.om.p1 && pb + F25_H <= G.Lout && gi0 >= A.om.g_lo &&
-          gi0 + F25_H <= A.om.g_hi) {
-        float* dst = (float*)A.om.out + (row * A.om.stride + gi0 - A.om.g0 + s4);
-        if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
-          *reinterpret_cast<float4*>(dst) = a4;
-          continue;
-        }
-      }
-    }
-    const float vals[4] = {a4.x, a4.y, a4.z, a4.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int64_t p = h * F25_H + s4 + e - G.padL;
-      if (p < A.om.p0 || p >= A.om.p1) continue;
-      const int64_t gi = chunk * A.om.g_step + (p - A.om.p0);
-      if (gi < A.om.g_lo || gi >= A.om.g_hi) continue;
-      store_sample(A.om.out, A.om.dtype, row * A.om.stride + gi - A.om.g0, p < G.Lout ? vals[e] : 0.f);
-    }
+    finish_hop<F25_H>(A, row, chunk, h, s4, a4);
   }
 }
 

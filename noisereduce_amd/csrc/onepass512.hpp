@@ -3,28 +3,26 @@
 //   k_decide_fast512 + k_smooth_bits2 + k_apply_fast512<K>      (3 transforms per frame pair, bit field and K field in HBM)
 //     ->  k_gate_onepass512                                      (2 transforms per frame pair, neither field)
 //
-// The structure of k_gate_onepass (onepass.hpp) on the transforms of fast512.hpp.  A workgroup takes a TICKET and owns one tile
-// of 32 consecutive frames of one unit (4 wavefronts x 4 lane groups x one frame PAIR per 512-point register transform).  After
-// the forward transform it decides its 32 x 257 cells (float32 + exact float64 refinement: the bits of k_decide_fast512), keeps
-// the spectra in registers and
-//   1. publishes the tile's bits (32 rows x 5 words) to its neighbours as data-tagged granules {32 bits, launch epoch};
-//   2. polls the nt adjacent rows of tiles j - 1 and j + 1 (nt <= 24: the time half-width of the smoothing filter);
-//   3. smooths the (32 + 2 nt) x 257 bit tile with the exact integer separable triangle filter ON THE MATRIX CORES
-//      (v_mfma_i32_16x16x32_i8, the formulation of onepass.hpp): per 16-bin block, H = bits x band matrix for the five 16-row
-//      blocks of the tile (nf <= 8), then K = time weights x H for the two 16-frame halves (two 32-row k-blocks each:
-//      16 + 2 nt <= 64 rows); H never leaves the registers, bits and the K tile (uint16) live in the exchange slices, which are
-//      idle between the two transforms: 3 workgroups per CU as k_apply_fast512.  (A first build ran both directions as
-//      sliding-window recurrences in LDS -- popcounts along f, two running boxcars along t: 203 us per two minutes where the three
-//      kernels it replaces take 103.)
-// then x mask -> inverse transform -> window -> overlap-add -> store exactly as k_apply_fast512<K>.  Tiles ABUT by default (A.part
-// set: the 3 hops that straddle two tiles leave as partial sums, k_ola_seam -- fastpath.hpp -- combines them after the launch: 1490
-// workgroups per two minutes instead of 1640, no redundant transforms) or, SG_OPT_FORCE_NOSEAM, overlap by 3 frames (29 complete
-// hops per tile); either way the bits are the only exchange INSIDE the launch.  Inter-workgroup protocol, deadlock freedom (tickets; publish before wait), bounded polls and NaN-poisoned
-// output of a tile that lost a hand-off: onepass.hpp.  The -top_db floor test runs on the staged samples (thresh.hpp:
-// FloorLazy); REDO = the second launch for the units whose test fired.  Any prop_decrease (a scale and an offset on the
-// mask entries).
+// The tile scaffold -- ticket and tile identity, floor test over the unstaged padding, parked spectra around the exact
+// re-evaluation, published bits and the poll of the neighbours' rows, K rows, partial-sum slots and the finished hops -- is
+// onepass_reg.hpp / fastpath.hpp (store_partial_hop, finish_hop), shared with onepass256.hpp and onepass2048.hpp.  This file's own:
+//   * the tile: 32 consecutive frames (4 wavefronts x 4 lane groups x one frame PAIR per 512-point register transform of
+//     fast512.hpp), 257 bins = 5 bit words per frame; decisions in float32 + exact float64 refinement on the pair split (the
+//     bits of k_decide_fast512), packed by a 16 x 16 bit transpose across the lane group;
+//   * the integer smoothing ON THE MATRIX CORES (v_mfma_i32_16x16x32_i8, the formulation of onepass.hpp): per 16-bin block,
+//     H = bits x band matrix for the five 16-row blocks of the tile (32 + 2 nt <= 80 rows, nf <= 8), then K = time weights x H
+//     for the two 16-frame halves (two 32-row k-blocks each: 16 + 2 nt <= 64 rows, nt <= 24); H never leaves the registers, bits
+//     and the K tile (uint16) live in the exchange slices: 3 workgroups per CU as k_apply_fast512.  (A first build ran both
+//     directions as sliding-window recurrences in LDS -- popcounts along f, two running boxcars along t: 203 us per two minutes
+//     where the three kernels it replaces take 103.)
+//   * x mask, merge, inverse transform and the wave-private overlap-add of k_apply_fast512<K>, any prop_decrease (a scale and
+//     an offset on the mask entries).
+// Tiles ABUT by default (A.part set: the 3 hops that straddle two tiles leave as partial sums, k_ola_seam -- fastpath.hpp --
+// combines them after the launch: 1490 workgroups per two minutes instead of 1640, no redundant transforms) or,
+// SG_OPT_FORCE_NOSEAM, overlap by 3 frames (29 complete hops per tile).
 #pragma once
 #include "fast512.hpp"
+#include "onepass_reg.hpp"
 
 namespace sg {
 namespace fast {
@@ -57,36 +55,17 @@ __global__ __launch_bounds__(WAVES * 64, O5_OCC) void k_gate_onepass512(OnePassR
   if (REDO && A.fl.alim[1] != A.tc.need_tag) return;   // no unit of this call reported (the common case)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15;
   const Geom& G = A.g;
-  if (tid == 0) {
-    s_misc[0] = atomicAdd(P.ticket, 1u) - P.ticket_base;
-    s_misc[1] = 0u;
-  }
+  reg_draw_ticket(P, s_misc, tid);
   s_exp[tid] = P.tab[192 + tid];
   const unsigned fl_bound = REDO ? 0xffffffffu : floor_lazy_bound(A.fl, lane);
   __syncthreads();
-  const int ntt = P.n_tiles + 2;                   // tiles per unit incl. one decide-only halo tile per side
-  const unsigned ticket = s_misc[0];
-  const int64_t u = ticket / (unsigned)ntt;
-  const int jt = (int)(ticket % (unsigned)ntt) - 1;
-  const bool halo_tile = jt < 0 || jt >= P.n_tiles;
-  const unsigned gu = (unsigned)(A.view.unit0 + u), nch = (unsigned)A.view.n_chunks;
-  const int64_t row = gu / nch;
-  const int64_t chunk = A.view.c0 + gu % nch;
-  const bool lazy = A.fl.alim != nullptr;
-  const int need = (lazy && !REDO) ? 0 : need_of(A.tc, u);
-  if (REDO && need == 0) return;   // whole workgroup
-  if (!REDO && lazy && ticket == 0u && tid == 0) P.ticket[8] = 0u;   // (the second launch's counter starts from zero)
-  const bool floor_live = need == 1;
-  auto t2eff = [&](int f) -> double {
-    double v = A.tc.T2[f];
-    if (floor_live) {
-      const double fl = cell_db(A.tc.pmax[u * G.FS + f], A.mag_scale) - A.top_db;
-      if (fl > A.tc.thresh[f]) v = -1.0;
-    }
-    if (need == 2) v = T2_NEVER;
-    return v;
-  };
-  stage_t2_plain<WAVES * 64, F5_F>(s_t2, A.tc.T2, need, 4.0, tid, t2eff);
+  const RegTile W = reg_tile_of<REDO>(P, s_misc[0], tid);   // (ticket 0 of a first launch: also zeroes the REDO launch's counter)
+  if (REDO && W.need == 0) return;   // whole workgroup
+  const int64_t u = W.u, row = W.row, chunk = W.chunk;
+  const int jt = W.jt, need = W.need;
+  const bool floor_live = W.floor_live;
+  stage_t2_plain<WAVES * 64, F5_F>(s_t2, A.tc.T2, need, 4.0, tid,
+                                 [&](int f) { return t2_effective(A.tc, u, G.FS, f, need, floor_live, A.mag_scale, A.top_db); });
   constexpr int NF = O5_NF, NH = O5_NH;
   const bool seam = A.part != nullptr;   // abutting tiles + k_ola_seam (fastpath.hpp); else tiles that overlap by 3 frames
   const int step = seam ? NF : NH;       // frames from one tile to the next
@@ -94,21 +73,7 @@ __global__ __launch_bounds__(WAVES * 64, O5_OCC) void k_gate_onepass512(OnePassR
   cf v[32];
   bool validA, validB;
   unsigned fl_mx = f5_gather<WAVES, true>(A, tw512, regions, swin, row, chunk, tf0, G.T, v, validA, validB);
-  if (!REDO && lazy) {
-    // The tiles of a unit stage the frames its kept hops need (+- nt), not the whole window: the rest -- the chunk's padding
-    // beyond them, A = [s_lo, first span) and B = [last span's end, s_hi) -- is dealt to the unit's tiles in slices of scan_q
-    // samples of A ++ B (onepass.hpp "floor test"; a few hundred samples per tile at the default chunking)
-    constexpr int SPAN = (NF - 1 + 4) * F5_H;
-    const int64_t g0 = chunk * A.view.cs - A.view.pad;
-    const int64_t s_lo = max<int64_t>(0, A.view.lo - g0), s_hi = min<int64_t>(A.view.Lp, A.view.hi - g0);
-    const int64_t sp0 = (A.h_begin - 3 - step) * F5_H - G.padL;
-    const int64_t sp1 = (A.h_begin - 3 + (int64_t)P.n_tiles * step) * F5_H - G.padL + SPAN;
-    const int64_t first = min(s_hi, max(s_lo, sp0)), last = max(s_lo, min(s_hi, sp1));
-    const int64_t lenA = first - s_lo;
-    const int64_t c0 = (int64_t)(jt + 1) * P.scan_q, c1 = min(c0 + P.scan_q, lenA + (s_hi - last));
-    for (int64_t i = c0 + tid; i < c1; i += WAVES * 64)
-      fl_mx = max(fl_mx, __float_as_uint((float)view_sample(A.view, row, chunk, i < lenA ? s_lo + i : last + (i - lenA))) & 0x7fffffffu);
-  }
+  if (!REDO && W.lazy) floor_scan_padding<WAVES * 64, F5_H, NF>(A, P, row, chunk, jt, step, tid, fl_mx);   // the padding no tile stages
   if (!REDO) floor_lazy_report(A.tc, A.fl, fl_bound, fl_mx, u, G.FS, lane);
   const int64_t tq = tf0 + F5_FPW * wave;
   // ---- forward transform + decisions (k_decide_fast512) -------------------------------------------------------
@@ -162,18 +127,11 @@ __global__ __launch_bounds__(WAVES * 64, O5_OCC) void k_gate_onepass512(OnePassR
     if (need == 2) { pA = pB = 0; aA = aB = 0; p256A = p256B = a256A = a256B = false; }
     if (!validA) { pA = 0; aA = 0; p256A = a256A = false; }
     if (!validB) { pB = 0; aB = 0; p256B = a256B = false; }
-    // exact re-evaluation of ambiguous cells, one at a time, whole wave cooperating.  Rare (about one wave in fifty has an
-    // ambiguous cell), but its float64 temporaries do not fit next to the 64 registers of the spectra at three waves per SIMD
-    // (the first build kept 29 of them in scratch through the hot path): the wave parks half of the spectra in its idle
-    // exchange slice for the duration (onepass.hpp does the same).
+    // exact re-evaluation of ambiguous cells, one at a time, whole wave cooperating; half of the spectra parked in the wave's
+    // idle exchange slice for the duration (onepass_reg.hpp: park_upper_half)
     if (__ballot(aA != 0 || aB != 0 || a256A || a256B) != 0ull) {
       float* park = reinterpret_cast<float*>(regions + wave * WAVE_CX_H) + lane;
-      static_assert(64 * 32 * 4 <= WAVE_CX_H * 8, "parked registers must fit the wave's slice");
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        park[(2 * i) * 64] = v[16 + i].x;
-        park[(2 * i + 1) * 64] = v[16 + i].y;
-      }
+      park_upper_half(v, park);
       while (true) {   // exact re-evaluation of ambiguous cells, one at a time, whole wave cooperating
         const unsigned long long pending = __ballot(aA != 0 || aB != 0 || a256A || a256B);
         if (pending == 0) break;
@@ -190,13 +148,7 @@ __global__ __launch_bounds__(WAVES * 64, O5_OCC) void k_gate_onepass512(OnePassR
         const int64_t t = tq + 2 * gs + (which & 1);
         const RegArgs& L = *late_args<RegArgs>();       // (cold path: arguments re-read here; A is the FIRST member)
         const double Pe = f5_exact_power(L, row, chunk, t, f, lane);
-        double t2 = L.tc.T2[f];
-        if (floor_live) {
-          const double fl = cell_db(L.tc.pmax[u * (int64_t)L.g.FS + f], L.mag_scale) - L.top_db;
-          if (fl > L.tc.thresh[f]) t2 = -1.0;
-        }
-        if (need == 2) t2 = T2_NEVER;
-        const bool pass = Pe > t2;
+        const bool pass = Pe > t2_effective(L.tc, u, L.g.FS, f, need, floor_live, L.mag_scale, L.top_db);
         if (lane == src) {
           if (which == 0) { pA = (pA & ~(1u << q)) | ((pass ? 1u : 0u) << q); aA &= ~(1u << q); }
           else if (which == 1) { pB = (pB & ~(1u << q)) | ((pass ? 1u : 0u) << q); aB &= ~(1u << q); }
@@ -205,11 +157,7 @@ __global__ __launch_bounds__(WAVES * 64, O5_OCC) void k_gate_onepass512(OnePassR
         }
       }
       wave_lds_sync();
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        v[16 + i].x = park[(2 * i) * 64];
-        v[16 + i].y = park[(2 * i + 1) * 64];
-      }
+      unpark_upper_half(v, park);
       wave_lds_sync();
     }
     // pack (k_decide_fast512): 16 x 16 bit transpose across the lane group, then lane c < 4 assembles word c, lane 4 bin 256
@@ -246,7 +194,7 @@ __global__ __launch_bounds__(WAVES * 64, O5_OCC) void k_gate_onepass512(OnePassR
   }
   // ---- publish this tile's bits; the spectra stay in v[] --------------------------------------------------------
   const int fa = F5_FPW * wave + 2 * g;      // tile row of frame A (B: fa + 1)
-  unsigned long long* xb_mine = P.xbits + ((size_t)u * ntt + (jt + 1)) * O5_TILE_WORDS;
+  unsigned long long* xb_mine = P.xbits + ((size_t)u * W.ntt + (jt + 1)) * O5_TILE_WORDS;
   if (c < O5_XW) {
     const op_v4u ga = {(unsigned)wA, P.epoch, (unsigned)(wA >> 32), P.epoch};
     const op_v4u gb = {(unsigned)wB, P.epoch, (unsigned)(wB >> 32), P.epoch};
@@ -254,7 +202,7 @@ __global__ __launch_bounds__(WAVES * 64, O5_OCC) void k_gate_onepass512(OnePassR
     op_st16_sc1(&xb_mine[((fa + 1) * O5_XW + c) * 2], gb);
   }
   __syncthreads();   // every wave is past its forward exchange: the slices are idle from here
-  if (halo_tile) return;
+  if (W.halo_tile) return;
 
   // ---- integer smoothing on the matrix cores (onepass.hpp) ----------------------------------------------------------
   const int nt = P.nt;
@@ -266,34 +214,8 @@ __global__ __launch_bounds__(WAVES * 64, O5_OCC) void k_gate_onepass512(OnePassR
     brow[(nt + fa) * O5_BW + 1 + c] = wA;
     brow[(nt + fa + 1) * O5_BW + 1 + c] = wB;
   }
-  for (int r = tid; r < O5_ROWS; r += WAVES * 64) {
-    brow[r * O5_BW] = 0ull;
-    brow[r * O5_BW + O5_BW - 1] = 0ull;
-    if (r >= NF + 2 * nt) {       // rows past the neighbours': zero (the last k-block reads them)
-#pragma unroll
-      for (int w = 1; w <= O5_XW; ++w) brow[r * O5_BW + w] = 0ull;
-    }
-  }
-  // neighbour rows: one 16-byte load per 64-bit word (2 nt x 5 words <= 240: one per thread), polled until both tags are current
-  for (int i = tid; i < 2 * nt * O5_XW; i += WAVES * 64) {
-    const int side = i >= nt * O5_XW;
-    const int rem = i - side * nt * O5_XW;
-    const int rr = rem / O5_XW, w = rem - rr * O5_XW;
-    // tile j - 1 holds frames tf0 - step ..: frame tf0 - nt + rr is its row step - nt + rr; tile j + 1: frame tf0 + 32 + rr is its row 32 - step + rr
-    const unsigned long long* src = side ? xb_mine + O5_TILE_WORDS + ((NF - step + rr) * O5_XW + w) * 2
-                                         : xb_mine - O5_TILE_WORDS + ((step - nt + rr) * O5_XW + w) * 2;
-    op_v4u gr = op_ld16_sc1(src);
-    for (int spin = 0; gr[1] != P.poll_epoch || gr[3] != P.poll_epoch; ++spin) {
-      if (spin >= P.spin_max) {   // bounded: report instead of hanging the device
-        atomicOr_system(P.err, 1u);
-        s_misc[1] = 1u;            // the tile's mask is unknown: every hop it finalises becomes NaN
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
-      gr = op_ld16_sc1(src);
-    }
-    brow[(side ? nt + NF + rr : rr) * O5_BW + 1 + w] = (unsigned long long)gr[0] | ((unsigned long long)gr[2] << 32);
-  }
+  zero_bit_row_margins<NF, O5_XW, O5_ROWS, WAVES * 64>(brow, nt, tid);
+  poll_neighbour_rows<NF, O5_XW, O5_BW, WAVES * 64>(xb_mine, step, nt, P, s_misc, brow, tid);
   const int q4 = lane >> 4, j16 = lane & 15;
   const long Bf = (long)P.tab[lane], At1 = (long)P.tab[64 + lane], At2 = (long)P.tab[128 + lane];
   __syncthreads();
@@ -304,8 +226,7 @@ __global__ __launch_bounds__(WAVES * 64, O5_OCC) void k_gate_onepass512(OnePassR
     // Output frames 16 hh + j (hh = 0, 1) sit at bit row nt + 16 hh + j and reach rows 16 hh + j .. 16 hh + j + 2 nt: row blocks
     // hh .. hh + 3; k-slot 8 q + e of the first product = row 4 q + e of block hh (e < 4) / block hh + 1 (e >= 4), of the second
     // = blocks hh + 2 / hh + 3 -- the same weights for both halves.
-    typedef int o5_v4i __attribute__((ext_vector_type(4)));
-    const o5_v4i zero4 = {0, 0, 0, 0};
+    const reg_v4i zero4 = {0, 0, 0, 0};
     const unsigned char* wbb = reinterpret_cast<const unsigned char*>(brow);
     constexpr int WPB = O5_BW * 8;
     for (int b = wave; b < 17; b += WAVES) {
@@ -313,20 +234,17 @@ __global__ __launch_bounds__(WAVES * 64, O5_OCC) void k_gate_onepass512(OnePassR
 #pragma unroll
       for (int m = 0; m < 5; ++m) {
         const long a = (long)s_exp[wbb[(16 * m + j16) * WPB + 7 + q4 + 2 * b]];
-        const o5_v4i hv = __builtin_amdgcn_mfma_i32_16x16x32_i8(a, Bf, zero4, 0, 0, 0);
+        const reg_v4i hv = __builtin_amdgcn_mfma_i32_16x16x32_i8(a, Bf, zero4, 0, 0, 0);
         hp[m] = (unsigned)hv[0] | ((unsigned)hv[1] << 8) | ((unsigned)hv[2] << 16) | ((unsigned)hv[3] << 24);
       }
 #pragma unroll
       for (int hh = 0; hh < 2; ++hh) {
         const long bt1 = (long)(((unsigned long long)hp[hh + 1] << 32) | (unsigned long long)hp[hh]);
         const long bt2 = (long)(((unsigned long long)hp[hh + 3] << 32) | (unsigned long long)hp[hh + 2]);
-        o5_v4i d = __builtin_amdgcn_mfma_i32_16x16x32_i8(At1, bt1, zero4, 0, 0, 0);
+        reg_v4i d = __builtin_amdgcn_mfma_i32_16x16x32_i8(At1, bt1, zero4, 0, 0, 0);
         d = __builtin_amdgcn_mfma_i32_16x16x32_i8(At2, bt2, d, 0, 0, 0);
         unsigned short* kd = Ks + (16 * hh + 4 * q4) * O5_KP + 16 * b + j16;   // lane group q4: output frames 4 q4 .. 4 q4 + 3
-        kd[0] = (unsigned short)d[0];
-        kd[O5_KP] = (unsigned short)d[1];
-        kd[2 * O5_KP] = (unsigned short)d[2];
-        kd[3 * O5_KP] = (unsigned short)d[3];
+        store_k4(kd, O5_KP, d);
       }
     }
   }
@@ -442,57 +360,11 @@ __global__ __launch_bounds__(WAVES * 64, O5_OCC) void k_gate_onepass512(OnePassR
       a4.x += f4.x; a4.y += f4.y; a4.z += f4.z; a4.w += f4.w;
     }
     a4.x += poison; a4.y += poison; a4.z += poison; a4.w += poison;
-    if (seam && (jj < 3 || jj >= NF)) {   // straddling hop: partial sum only (poisoned with the tile); slots 0..2 leading, 3..5 trailing
-      const int slot = jj < 3 ? jj : 3 + (jj - NF);
-      *reinterpret_cast<float4*>(A.part + ((((size_t)u * A.n_tiles + jt) * 6 + slot) * F5_H + s4)) = a4;
+    if (seam && (jj < 3 || jj >= NF)) {   // straddling hop: partial sum only (poisoned with the tile), k_ola_seam finishes it
+      store_partial_hop<F5_H>(A, u, jt, jj, NF, s4, a4);
       continue;
     }
-    bool all_valid = true;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int64_t ti = h - q;
-      if (ti < 0 || ti >= G.T) all_valid = false;
-    }
-    if (!A.normalize) {
-    } else if (all_valid) {
-      const float4 n4 = *reinterpret_cast<const float4*>(&A.invn[s4]);
-      a4.x *= n4.x; a4.y *= n4.y; a4.z *= n4.z; a4.w *= n4.w;
-    } else {
-      float4 nrm = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int64_t ti = h - q;
-        if (ti >= 0 && ti < G.T) {
-          const float4 w4 = *reinterpret_cast<const float4*>(&A.wsq[F5_H * q + s4]);
-          nrm.x += w4.x; nrm.y += w4.y; nrm.z += w4.z; nrm.w += w4.w;
-        }
-      }
-      a4.x /= (nrm.x > 1e-10f ? nrm.x : 1.f);
-      a4.y /= (nrm.y > 1e-10f ? nrm.y : 1.f);
-      a4.z /= (nrm.z > 1e-10f ? nrm.z : 1.f);
-      a4.w /= (nrm.w > 1e-10f ? nrm.w : 1.f);
-    }
-    {
-      const int64_t pb = h * F5_H - G.padL;
-      const int64_t gi0 = chunk * A.om.g_step + (pb - A.om.p0);
-      if (A.om.dtype == 0 && pb >= A.om.p0 && pb + F5_H <= A.om.p1 && pb + F5_H <= G.Lout && gi0 >= A.om.g_lo &&
-          gi0 + F5_H <= A.om.g_hi) {
-        float* dst = (float*)A.om.out + (row * A.om.stride + gi0 - A.om.g0 + s4);
-        if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
-          *reinterpret_cast<float4*>(dst) = a4;
-          continue;
-        }
-      }
-    }
-    const float vals[4] = {a4.x, a4.y, a4.z, a4.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int64_t p = h * F5_H + s4 + e - G.padL;
-      if (p < A.om.p0 || p >= A.om.p1) continue;
-      const int64_t gi = chunk * A.om.g_step + (p - A.om.p0);
-      if (gi < A.om.g_lo || gi >= A.om.g_hi) continue;
-      store_sample(A.om.out, A.om.dtype, row * A.om.stride + gi - A.om.g0, p < G.Lout ? vals[e] : 0.f);
-    }
+    finish_hop<F5_H>(A, row, chunk, h, s4, a4);
   }
 }
 
