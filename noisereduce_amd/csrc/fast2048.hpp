@@ -162,76 +162,32 @@ __device__ __forceinline__ cf f20_wk(cf wl, int k2) {
   return {wl.x * cs - wl.y * sn, wl.x * sn + wl.y * cs};
 }
 
-__device__ __forceinline__ double f20_exact_power(const RegArgs& A, int64_t row, int64_t chunk, int64_t t, int f, int lane) {
-  const int64_t s0 = t * F20_H - A.g.padL;
-  double re = 0.0, im = 0.0;
-#pragma unroll 4
-  for (int i = 0; i < 32; ++i) {
-    const int m = lane + 64 * i;
-    const double xv = view_sample(A.view, row, chunk, s0 + m) * A.win64[m];
-    const int j = (f * m) & 2047;
-    cx<double> w = A.tw64[j & 1023];
-    if (j >= 1024) { w.x = -w.x; w.y = -w.y; }
-    re += xv * w.x;
-    im += xv * w.y;
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    re += __shfl_xor(re, off);
-    im += __shfl_xor(im, off);
-  }
-  return re * re + im * im;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// REDO: the second launch of a call with the in-kernel floor test (thresh.hpp: FloorLazy): only the units whose test fired.
-template <int WAVES, bool REDO = false>
-__global__ __launch_bounds__(WAVES * 64, 3) void k_decide_fast2048(RegArgs A) {
-  if (REDO && A.fl.alim[1] != A.tc.need_tag) return;   // no unit of this call reported (the common case)
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  cf* tw = reinterpret_cast<cf*>(smem);                 // [32][32] w_1024^(k1 c)
-  cf* regions = tw + 1024;
-  float* s_t2 = reinterpret_cast<float*>(regions + WAVES * WAVE_CX_H);   // [1025] compare constants x4
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 5, c = lane & 31;
-  const Geom& G = A.g;
-  const int64_t u = blockIdx.y;
-  const int64_t row = (A.view.unit0 + u) / A.view.n_chunks;
-  const int64_t chunk = A.view.c0 + (A.view.unit0 + u) % A.view.n_chunks;
-  const bool lazy = A.fl.alim != nullptr;
-  const int need = (lazy && !REDO) ? 0 : need_of(A.tc, u);
-  if (REDO && need == 0) return;   // whole workgroup
-  const unsigned fl_bound = REDO ? 0xffffffffu : floor_lazy_bound(A.fl, lane);
-  const bool floor_live = need == 1;
-  auto t2eff = [&](int f) -> double {
-    double v = A.tc.T2[f];
-    if (floor_live) {
-      const double fl = cell_db(A.tc.pmax[u * G.FS + f], A.mag_scale) - A.top_db;
-      if (fl > A.tc.thresh[f]) v = -1.0;
-    }
-    if (need == 2) v = T2_NEVER;
-    return v;
-  };
-  stage_t2_plain<WAVES * 64, F20_F>(s_t2, A.tc.T2, need, 4.0, tid, t2eff);
-  constexpr int NF = 2 * WAVES;
-  const int64_t tf0 = (int64_t)blockIdx.x * NF;
-  cf v[32];
-  bool valid;
-  const unsigned fl_mx = f20_gather<WAVES, true>(A, tw, regions, row, chunk, tf0, v, valid);
-  if (!REDO) floor_lazy_report(A.tc, A.fl, fl_bound, fl_mx, u, G.FS, lane);
-  const int64_t tq = tf0 + 2 * wave;
-  if (tq >= G.T) return;   // wave-uniform
+// The frame's norm (delta^2 = 2^-32 ||x w||^2, see k_decide_fast), then its forward transform in place (pinned behind the norm).
+__device__ __forceinline__ float f20_norm_fwd(cf* v, cf* fb, const cf* tw, int c) {
   float nrm2 = 0.f;
 #pragma unroll
   for (int r = 0; r < 32; ++r) nrm2 += v[r].x * v[r].x + v[r].y * v[r].y;
 #pragma unroll
   for (int o = 1; o < 32; o <<= 1) nrm2 += __shfl_xor(nrm2, o);
-  cf* fb = regions + wave * WAVE_CX_H + g * F20_FSL;
   {
     int z0 = 0;
     asm volatile("" : "+v"(z0));
     fft1k_fwd(v, fb, tw + z0, c);
   }
+  return nrm2;
+}
+
+// Decide and pack, the one text of k_decide_fast2048 (PARK = false) and k_gate_onepass2048 (PARK = true: v[] lives on into the
+// apply stage).  In: the transformed v[32] of frame tq + g (g = lane >> 5), the float32 compare constants x4 in s_t2, the frame's
+// norm taken BEFORE the transform, whether the frame exists, the unit's need / floor_live (reg_unit_of) and identity for the exact
+// re-evaluation, wl = w_2048^c (A.tw[c]); wslice: the wave's exchange slice (PARK).  Returns, in lane c < 17 of the group, word c of
+// the frame's 1025 bits.
+template <bool PARK>
+__device__ __forceinline__ unsigned long long f20_decide_pack(cf* v, const float* s_t2, float nrm2, bool valid, int need,
+                                                              bool floor_live, int64_t u, int64_t row, int64_t chunk, int64_t tq,
+                                                              int lane, cf wl, cf* wslice) {
+  const int g = lane >> 5, c = lane & 31;
   const float d2 = nrm2 > 0.f ? 8.0f * 2.3283064e-10f * nrm2 : -1.0f;
-  const cf wl = A.tw[c];
   unsigned pred = 0, amb = 0;
   bool predN = false, ambN = false;     // bin 1024 (lane 0)
   {
@@ -270,33 +226,39 @@ __global__ __launch_bounds__(WAVES * 64, 3) void k_decide_fast2048(RegArgs A) {
       decide(l0 ? p0 : pu, s_t2[c + 32 * (31 - i)], 31 - i);
     }
   }
-  if (need == 2) { pred = 0; amb = 0; predN = false; ambN = false; }
-  if (!valid) { pred = 0; amb = 0; predN = false; ambN = false; }
-  while (true) {
-    const unsigned long long pending = __ballot(amb != 0 || ambN);
-    if (pending == 0) break;
-    const int src = __ffsll((long long)pending) - 1;
-    const unsigned amb_s = (unsigned)__shfl((int)amb, src);
-    const int q = amb_s ? (__ffs((int)amb_s) - 1) : 32;
-    const int cs = src & 31, gs = src >> 5;
-    const int f = q < 32 ? cs + 32 * q : 1024;
-    const RegArgs& L = *late_args<RegArgs>();     // (cold path: arguments re-read here, not kept live from the entry)
-    const double P = f20_exact_power(L, row, chunk, tq + gs, f, lane);
-    double t2 = L.tc.T2[f];
-    if (floor_live) {
-      const double fl = cell_db(L.tc.pmax[u * (int64_t)L.g.FS + f], L.mag_scale) - L.top_db;
-      if (fl > L.tc.thresh[f]) t2 = -1.0;
-    }
-    if (need == 2) t2 = T2_NEVER;
-    const bool pass = P > t2;
-    if (lane == src) {
-      if (q < 32) {
-        pred = (pred & ~(1u << q)) | ((pass ? 1u : 0u) << q);
-        amb &= ~(1u << q);
-      } else {
-        predN = pass;
-        ambN = false;
+  // NaN powers have no sign; a frame outside the unit decides nothing
+  if (need == 2 || !valid) { pred = 0; amb = 0; predN = false; ambN = false; }
+  // exact re-evaluation of ambiguous cells, one at a time, whole wave cooperating; PARK: half of the spectra wait in the wave's
+  // idle exchange slice for the duration (fastpath.hpp: park_upper_half)
+  if (!PARK || __ballot(amb != 0 || ambN) != 0ull) {
+    float* park = reinterpret_cast<float*>(wslice) + lane;
+    if constexpr (PARK) park_upper_half(v, park);
+    while (true) {
+      const unsigned long long pending = __ballot(amb != 0 || ambN);
+      if (pending == 0) break;
+      const int src = __ffsll((long long)pending) - 1;
+      const unsigned amb_s = (unsigned)__shfl((int)amb, src);
+      const int q = amb_s ? (__ffs((int)amb_s) - 1) : 32;
+      const int cs = src & 31, gs = src >> 5;
+      const int f = q < 32 ? cs + 32 * q : 1024;
+      // (cold path: arguments re-read here, not kept live from the entry; RegArgs is, or is the FIRST member of, the kernel's argument)
+      const RegArgs& L = *late_args<RegArgs>();
+      const double Pe = reg_exact_power<2 * F20_NC>(L, row, chunk, tq + gs, f, lane);
+      const bool pass = Pe > t2_effective(L.tc, u, L.g.FS, f, need, floor_live, L.mag_scale, L.top_db);
+      if (lane == src) {
+        if (q < 32) {
+          pred = (pred & ~(1u << q)) | ((pass ? 1u : 0u) << q);
+          amb &= ~(1u << q);
+        } else {
+          predN = pass;
+          ambN = false;
+        }
       }
+    }
+    if constexpr (PARK) {
+      wave_lds_sync();
+      unpark_upper_half(v, park);
+      wave_lds_sync();
     }
   }
   // pack: the ballot of register k2 is, per frame, the 32 bins 32 k2 .. 32 k2 + 31 in natural order
@@ -312,6 +274,41 @@ __global__ __launch_bounds__(WAVES * 64, 3) void k_decide_fast2048(RegArgs A) {
     const unsigned long long bN = __ballot(predN);
     if (c == 16) myword = (bN >> sh) & 1ull;
   }
+  return myword;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// REDO: the second launch of a call with the in-kernel floor test (thresh.hpp: FloorLazy): only the units whose test fired.
+template <int WAVES, bool REDO = false>
+__global__ __launch_bounds__(WAVES * 64, 3) void k_decide_fast2048(RegArgs A) {
+  if (REDO && A.fl.alim[1] != A.tc.need_tag) return;   // no unit of this call reported (the common case)
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  cf* tw = reinterpret_cast<cf*>(smem);                 // [32][32] w_1024^(k1 c)
+  cf* regions = tw + 1024;
+  float* s_t2 = reinterpret_cast<float*>(regions + WAVES * WAVE_CX_H);   // [1025] compare constants x4
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 5, c = lane & 31;
+  const Geom& G = A.g;
+  const int64_t u = blockIdx.y;
+  const RegUnit W = reg_unit_of<REDO>(A, u);
+  if (REDO && W.need == 0) return;   // whole workgroup
+  const int64_t row = W.row, chunk = W.chunk;
+  const int need = W.need;
+  const bool floor_live = W.floor_live;
+  const unsigned fl_bound = REDO ? 0xffffffffu : floor_lazy_bound(A.fl, lane);
+  stage_t2_plain<WAVES * 64, F20_F>(s_t2, A.tc.T2, need, 4.0, tid,
+                                  [&](int f) { return t2_effective(A.tc, u, G.FS, f, need, floor_live, A.mag_scale, A.top_db); });
+  constexpr int NF = 2 * WAVES;
+  const int64_t tf0 = (int64_t)blockIdx.x * NF;
+  cf v[32];
+  bool valid;
+  const unsigned fl_mx = f20_gather<WAVES, true>(A, tw, regions, row, chunk, tf0, v, valid);
+  if (!REDO) floor_lazy_report(A.tc, A.fl, fl_bound, fl_mx, u, G.FS, lane);
+  const int64_t tq = tf0 + 2 * wave;
+  if (tq >= G.T) return;   // wave-uniform
+  cf* fb = regions + wave * WAVE_CX_H + g * F20_FSL;
+  const float nrm2 = f20_norm_fwd(v, fb, tw, c);
+  const unsigned long long myword =
+      f20_decide_pack<false>(v, s_t2, nrm2, valid, need, floor_live, u, row, chunk, tq, lane, A.tw[c], regions + wave * WAVE_CX_H);
   const int64_t t = tq + g;
   if (valid && c < 17) A.bits[(u * G.T + t) * 17 + c] = myword;
 }
@@ -325,8 +322,8 @@ __global__ __launch_bounds__(WAVES * 64, 3) void k_mag_fast2048(RegArgs A) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 5, c = lane & 31;
   const Geom& G = A.g;
   const int64_t u = blockIdx.y;
-  const int64_t row = (A.view.unit0 + u) / A.view.n_chunks;
-  const int64_t chunk = A.view.c0 + (A.view.unit0 + u) % A.view.n_chunks;
+  const RegUnit W = reg_unit_of<false>(A, u);   // (row and chunk; the rest folds away)
+  const int64_t row = W.row, chunk = W.chunk;
   constexpr int NF = 2 * WAVES;
   const int64_t tf0 = (int64_t)blockIdx.x * NF;
   cf v[32];
@@ -385,8 +382,8 @@ __global__ __launch_bounds__(WAVES * 64, 3) void k_apply_fast2048(RegArgs A) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 5, c = lane & 31;
   const Geom& G = A.g;
   const int64_t u = blockIdx.y;
-  const int64_t row = (A.view.unit0 + u) / A.view.n_chunks;
-  const int64_t chunk = A.view.c0 + (A.view.unit0 + u) % A.view.n_chunks;
+  const RegUnit W = reg_unit_of<false>(A, u);   // (row and chunk; the rest folds away)
+  const int64_t row = W.row, chunk = W.chunk;
   constexpr int NF = 2 * WAVES, NH = NF - 3;
   const bool seam = A.part != nullptr;        // abutting tiles + k_ola_seam (fastpath.hpp), else overlapping tiles
   const int64_t tf0 = A.h_begin - 3 + (int64_t)blockIdx.x * (seam ? NF : NH);

@@ -161,26 +161,6 @@ __device__ __forceinline__ void f25_pair(const cf* v, int off, int e, bool l0, c
   else b = sel(pb[11 - e], pb[7 - e]);
 }
 
-__device__ __forceinline__ double f25_exact_power(const RegArgs& A, int64_t row, int64_t chunk, int64_t t, int f, int lane) {
-  const int64_t s0 = t * F25_H - A.g.padL;
-  double re = 0.0, im = 0.0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int m = lane + 64 * i;
-    const double xv = view_sample(A.view, row, chunk, s0 + m) * A.win64[m];
-    const int j = (f * m) & 255;
-    cx<double> w = A.tw64[j & 127];
-    if (j >= 128) { w.x = -w.x; w.y = -w.y; }
-    re += xv * w.x;
-    im += xv * w.y;
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    re += __shfl_xor(re, off);
-    im += __shfl_xor(im, off);
-  }
-  return re * re + im * im;
-}
-
 // 4 |X|^2 of the lane's 8 slots for the four frames: P[fr][e]; lane 0: slot 0 = DC, P128[fr] = bin 128
 __device__ __forceinline__ void f25_powers(const cf* v, bool l0, float (&P)[4][8], float (&P128)[4]) {
 #pragma unroll
@@ -206,44 +186,9 @@ __device__ __forceinline__ void f25_powers(const cf* v, bool l0, float (&P)[4][8
   }
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// REDO: the second launch of a call with the in-kernel floor test (thresh.hpp: FloorLazy): only the units whose test fired.
-template <int WAVES, bool REDO = false>
-__global__ __launch_bounds__(WAVES * 64, 3) void k_decide_fast256(RegArgs A) {
-  if (REDO && A.fl.alim[1] != A.tc.need_tag) return;   // no unit of this call reported (the common case)
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  cf* tw512 = reinterpret_cast<cf*>(smem);
-  cf* regions = tw512 + FN;
-  float* swin = reinterpret_cast<float*>(regions + WAVES * WAVE_CX_H);
-  float* s_t2 = swin + F25_N;                // [129] float32 compare constants x4 (the split works on 2 X)
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15;
-  const Geom& G = A.g;
-  const int64_t u = blockIdx.y;
-  const int64_t row = (A.view.unit0 + u) / A.view.n_chunks;
-  const int64_t chunk = A.view.c0 + (A.view.unit0 + u) % A.view.n_chunks;
-  const bool lazy = A.fl.alim != nullptr;
-  const int need = (lazy && !REDO) ? 0 : need_of(A.tc, u);
-  if (REDO && need == 0) return;   // whole workgroup
-  const unsigned fl_bound = REDO ? 0xffffffffu : floor_lazy_bound(A.fl, lane);
-  const bool floor_live = need == 1;
-  auto t2eff = [&](int f) -> double {
-    double v = A.tc.T2[f];
-    if (floor_live) {
-      const double fl = cell_db(A.tc.pmax[u * G.FS + f], A.mag_scale) - A.top_db;
-      if (fl > A.tc.thresh[f]) v = -1.0;
-    }
-    if (need == 2) v = T2_NEVER;
-    return v;
-  };
-  stage_t2_plain<WAVES * 64, F25_F>(s_t2, A.tc.T2, need, 4.0, tid, t2eff);
-  constexpr int NF = F25_FPW * WAVES;
-  const int64_t tf0 = (int64_t)blockIdx.x * NF;
-  cf v[32];
-  bool validX, validY;
-  const unsigned fl_mx = f25_gather<WAVES, true>(A, tw512, regions, swin, row, chunk, tf0, v, validX, validY);
-  if (!REDO) floor_lazy_report(A.tc, A.fl, fl_bound, fl_mx, u, G.FS, lane);
-  const int64_t tq = tf0 + F25_FPW * wave;
-  if (tq >= G.T) return;   // wave-uniform; no barrier below
+// The norms of the lane group's two sequences, then the forward transform in place (pinned behind the norms).
+__device__ __forceinline__ void f25_norms_fwd(cf* v, cf* fb, const cf* tw512, int lane, float& n1, float& n2) {
+  const int c = lane & 15;
   // delta^2 = 2^-32 ||x w||^2 (see k_decide_fast): one sequence carries two frames, the rounding error in either spectrum
   // scales with the norm of the PAIR; the two sequences of a lane group never mix.  Norm over the 8 lanes of equal parity.
   float nXY = 0.f;
@@ -251,13 +196,25 @@ __global__ __launch_bounds__(WAVES * 64, 3) void k_decide_fast256(RegArgs A) {
   for (int r = 0; r < 32; ++r) nXY += v[r].x * v[r].x + v[r].y * v[r].y;
 #pragma unroll
   for (int o = 2; o < 16; o <<= 1) nXY += __shfl_xor(nXY, o);
-  const float n1 = __shfl(nXY, lane & 48), n2 = __shfl(nXY, (lane & 48) | 1);   // sequence 1 (even lanes), sequence 2
-  cf* fb = regions + wave * WAVE_CX_H + frame_base_h(g);
+  n1 = __shfl(nXY, lane & 48);   // sequence 1 (even lanes)
+  n2 = __shfl(nXY, (lane & 48) | 1);   // sequence 2
   {
     int z0 = 0;
     asm volatile("" : "+v"(z0));
     f25_fwd_half(v, fb, tw512 + z0, c);
   }
+}
+
+// Decide and pack, the one text of k_decide_fast256 (PARK = false) and k_gate_onepass256 (PARK = true: v[] lives on into the apply
+// stage).  In: the transformed v[32] of the lane group's four frames tq + 4 g + fr (g = lane >> 4), the float32 compare constants x4
+// in s_t2, the norms n1, n2 of the group's two sequences taken BEFORE the transform, the unit's frame count T (frames outside
+// [0, T) decide nothing), its need / floor_live (reg_unit_of) and identity for the exact re-evaluation; wslice: the wave's exchange
+// slice (PARK).  Returns, in lane c = 4 fr + w (w < 3) of the group, word w of frame fr's 129 bits.
+template <bool PARK>
+__device__ __forceinline__ unsigned long long f25_decide_pack(cf* v, const float* s_t2, float n1, float n2, int64_t T, int need,
+                                                              bool floor_live, int64_t u, int64_t row, int64_t chunk, int64_t tq,
+                                                              int lane, cf* wslice) {
+  const int g = lane >> 4, c = lane & 15;
   const bool l0 = c == 0;
   float d2[2];
   d2[0] = n1 > 0.f ? 8.0f * 2.3283064e-10f * n1 : -1.0f;
@@ -290,32 +247,37 @@ __global__ __launch_bounds__(WAVES * 64, 3) void k_decide_fast256(RegArgs A) {
   if (need == 2) { pr = 0; am = 0; p128 = 0; a128 = 0; }   // NaN powers have no sign
 #pragma unroll
   for (int fr = 0; fr < 4; ++fr) {
-    const bool ok = tg + fr >= 0 && tg + fr < G.T;
+    const bool ok = tg + fr >= 0 && tg + fr < T;
     if (!ok) { pr &= ~(0xffu << (8 * fr)); am &= ~(0xffu << (8 * fr)); p128 &= ~(1u << fr); a128 &= ~(1u << fr); }
   }
-  // exact re-evaluation of ambiguous cells, one at a time, whole wave cooperating
-  while (true) {
-    const unsigned long long pending = __ballot(am != 0 || a128 != 0);
-    if (pending == 0) break;
-    const int src = __ffsll((long long)pending) - 1;
-    const unsigned sam = (unsigned)__shfl((int)am, src), s128 = (unsigned)__shfl((int)a128, src);
-    const int cs = src & 15, gs = src >> 4;
-    int fr, f, q;
-    if (sam) { q = __ffs((int)sam) - 1; fr = q >> 3; f = bin6(cs, q & 7); }
-    else { q = -1; fr = __ffs((int)s128) - 1; f = 128; }
-    const int64_t t = tq + 4 * gs + fr;
-    const RegArgs& L = *late_args<RegArgs>();     // (cold path: arguments re-read here, not kept live from the entry)
-    const double Pe = f25_exact_power(L, row, chunk, t, f, lane);
-    double t2 = L.tc.T2[f];
-    if (floor_live) {
-      const double fl = cell_db(L.tc.pmax[u * (int64_t)L.g.FS + f], L.mag_scale) - L.top_db;
-      if (fl > L.tc.thresh[f]) t2 = -1.0;
+  // exact re-evaluation of ambiguous cells, one at a time, whole wave cooperating; PARK: half of the spectra wait in the wave's
+  // idle exchange slice for the duration (fastpath.hpp: park_upper_half)
+  if (!PARK || __ballot(am != 0 || a128 != 0) != 0ull) {
+    float* park = reinterpret_cast<float*>(wslice) + lane;
+    if constexpr (PARK) park_upper_half(v, park);
+    while (true) {
+      const unsigned long long pending = __ballot(am != 0 || a128 != 0);
+      if (pending == 0) break;
+      const int src = __ffsll((long long)pending) - 1;
+      const unsigned sam = (unsigned)__shfl((int)am, src), s128 = (unsigned)__shfl((int)a128, src);
+      const int cs = src & 15, gs = src >> 4;
+      int fr, f, q;
+      if (sam) { q = __ffs((int)sam) - 1; fr = q >> 3; f = bin6(cs, q & 7); }
+      else { q = -1; fr = __ffs((int)s128) - 1; f = 128; }
+      const int64_t t = tq + 4 * gs + fr;
+      // (cold path: arguments re-read here, not kept live from the entry; RegArgs is, or is the FIRST member of, the kernel's argument)
+      const RegArgs& L = *late_args<RegArgs>();
+      const double Pe = reg_exact_power<F25_N>(L, row, chunk, t, f, lane);
+      const bool pass = Pe > t2_effective(L.tc, u, L.g.FS, f, need, floor_live, L.mag_scale, L.top_db);
+      if (lane == src) {
+        if (q >= 0) { pr = (pr & ~(1u << q)) | ((pass ? 1u : 0u) << q); am &= ~(1u << q); }
+        else { p128 = (p128 & ~(1u << fr)) | ((pass ? 1u : 0u) << fr); a128 &= ~(1u << fr); }
+      }
     }
-    if (need == 2) t2 = T2_NEVER;
-    const bool pass = Pe > t2;
-    if (lane == src) {
-      if (q >= 0) { pr = (pr & ~(1u << q)) | ((pass ? 1u : 0u) << q); am &= ~(1u << q); }
-      else { p128 = (p128 & ~(1u << fr)) | ((pass ? 1u : 0u) << fr); a128 &= ~(1u << fr); }
+    if constexpr (PARK) {
+      wave_lds_sync();
+      unpark_upper_half(v, park);
+      wave_lds_sync();
     }
   }
   // Pack.  Block j (bins 32 j .. 32 j + 31) of a frame: bits 0..15 = the ballot of slot j (lane c -> bin 32 j + c; lane 0's
@@ -341,6 +303,44 @@ __global__ __launch_bounds__(WAVES * 64, 3) void k_decide_fast256(RegArgs A) {
     const unsigned long long w2 = (bN >> sh) & 1ull;
     if ((c >> 2) == fr) mine = (c & 3) == 0 ? w0 : ((c & 3) == 1 ? w1 : w2);
   }
+  return mine;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// REDO: the second launch of a call with the in-kernel floor test (thresh.hpp: FloorLazy): only the units whose test fired.
+template <int WAVES, bool REDO = false>
+__global__ __launch_bounds__(WAVES * 64, 3) void k_decide_fast256(RegArgs A) {
+  if (REDO && A.fl.alim[1] != A.tc.need_tag) return;   // no unit of this call reported (the common case)
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  cf* tw512 = reinterpret_cast<cf*>(smem);
+  cf* regions = tw512 + FN;
+  float* swin = reinterpret_cast<float*>(regions + WAVES * WAVE_CX_H);
+  float* s_t2 = swin + F25_N;                // [129] float32 compare constants x4 (the split works on 2 X)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15;
+  const Geom& G = A.g;
+  const int64_t u = blockIdx.y;
+  const RegUnit W = reg_unit_of<REDO>(A, u);
+  if (REDO && W.need == 0) return;   // whole workgroup
+  const int64_t row = W.row, chunk = W.chunk;
+  const int need = W.need;
+  const bool floor_live = W.floor_live;
+  const unsigned fl_bound = REDO ? 0xffffffffu : floor_lazy_bound(A.fl, lane);
+  stage_t2_plain<WAVES * 64, F25_F>(s_t2, A.tc.T2, need, 4.0, tid,
+                                  [&](int f) { return t2_effective(A.tc, u, G.FS, f, need, floor_live, A.mag_scale, A.top_db); });
+  constexpr int NF = F25_FPW * WAVES;
+  const int64_t tf0 = (int64_t)blockIdx.x * NF;
+  cf v[32];
+  bool validX, validY;
+  const unsigned fl_mx = f25_gather<WAVES, true>(A, tw512, regions, swin, row, chunk, tf0, v, validX, validY);
+  if (!REDO) floor_lazy_report(A.tc, A.fl, fl_bound, fl_mx, u, G.FS, lane);
+  const int64_t tq = tf0 + F25_FPW * wave;
+  if (tq >= G.T) return;   // wave-uniform; no barrier below
+  cf* fb = regions + wave * WAVE_CX_H + frame_base_h(g);
+  float n1, n2;
+  f25_norms_fwd(v, fb, tw512, lane, n1, n2);
+  const int64_t tg = tq + 4 * g;
+  const unsigned long long mine =
+      f25_decide_pack<false>(v, s_t2, n1, n2, G.T, need, floor_live, u, row, chunk, tq, lane, regions + wave * WAVE_CX_H);
   {
     const int fr = c >> 2, w = c & 3;
     const int64_t t = tg + fr;
@@ -358,8 +358,8 @@ __global__ __launch_bounds__(WAVES * 64, 3) void k_mag_fast256(RegArgs A) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15;
   const Geom& G = A.g;
   const int64_t u = blockIdx.y;
-  const int64_t row = (A.view.unit0 + u) / A.view.n_chunks;
-  const int64_t chunk = A.view.c0 + (A.view.unit0 + u) % A.view.n_chunks;
+  const RegUnit W = reg_unit_of<false>(A, u);   // (row and chunk; the rest folds away)
+  const int64_t row = W.row, chunk = W.chunk;
   constexpr int NF = F25_FPW * WAVES;
   const int64_t tf0 = (int64_t)blockIdx.x * NF;
   cf v[32];
@@ -413,8 +413,8 @@ __global__ __launch_bounds__(WAVES * 64, 3) void k_apply_fast256(RegArgs A) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15, cp = c >> 1;
   const Geom& G = A.g;
   const int64_t u = blockIdx.y;
-  const int64_t row = (A.view.unit0 + u) / A.view.n_chunks;
-  const int64_t chunk = A.view.c0 + (A.view.unit0 + u) % A.view.n_chunks;
+  const RegUnit W = reg_unit_of<false>(A, u);   // (row and chunk; the rest folds away)
+  const int64_t row = W.row, chunk = W.chunk;
   constexpr int NF = F25_FPW * WAVES, NH = NF - 3;
   const bool seam = A.part != nullptr;        // abutting tiles + k_ola_seam (fastpath.hpp), else tiles that overlap by 3 frames
   const int64_t tf0 = A.h_begin - 3 + (int64_t)blockIdx.x * (seam ? NF : NH);   // first frame of the tile

@@ -93,77 +93,31 @@ __device__ __forceinline__ void f5_pair(const cf* v, int sl, bool l0, cf& a, cf&
   b = sl < 8 ? sel(v[16 - sl], v[31 - sl]) : sel(v[39 - sl], v[31 - sl]);
 }
 
-__device__ __forceinline__ double f5_exact_power(const RegArgs& A, int64_t row, int64_t chunk, int64_t t, int f, int lane) {
-  const int64_t s0 = t * F5_H - A.g.padL;
-  double re = 0.0, im = 0.0;
-#pragma unroll 4
-  for (int i = 0; i < 8; ++i) {
-    const int m = lane + 64 * i;
-    const double xv = view_sample(A.view, row, chunk, s0 + m) * A.win64[m];
-    const int j = (f * m) & 511;
-    cx<double> w = A.tw64[j & 255];
-    if (j >= 256) { w.x = -w.x; w.y = -w.y; }
-    re += xv * w.x;
-    im += xv * w.y;
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    re += __shfl_xor(re, off);
-    im += __shfl_xor(im, off);
-  }
-  return re * re + im * im;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// REDO: the second launch of a call with the in-kernel floor test (thresh.hpp: FloorLazy): only the units whose test fired.
-template <int WAVES, bool REDO = false>
-__global__ __launch_bounds__(WAVES * 64, 3) void k_decide_fast512(RegArgs A) {
-  if (REDO && A.fl.alim[1] != A.tc.need_tag) return;   // no unit of this call reported (the common case)
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  cf* tw512 = reinterpret_cast<cf*>(smem);
-  cf* regions = tw512 + FN;
-  float* swin = reinterpret_cast<float*>(regions + WAVES * WAVE_CX_H);
-  float* s_t2 = swin + F5_N;                 // [257] float32 compare constants x4 (the split works on 2 X)
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15;
-  const Geom& G = A.g;
-  const int64_t u = blockIdx.y;
-  const int64_t row = (A.view.unit0 + u) / A.view.n_chunks;
-  const int64_t chunk = A.view.c0 + (A.view.unit0 + u) % A.view.n_chunks;
-  // lazy (A.fl.alim set): the first launch assumes "no floor live" and tests the samples it stages; REDO serves the flagged units
-  const bool lazy = A.fl.alim != nullptr;
-  const int need = (lazy && !REDO) ? 0 : need_of(A.tc, u);
-  if (REDO && need == 0) return;   // whole workgroup
-  const unsigned fl_bound = REDO ? 0xffffffffu : floor_lazy_bound(A.fl, lane);
-  const bool floor_live = need == 1;
-  auto t2eff = [&](int f) -> double {
-    double v = A.tc.T2[f];
-    if (floor_live) {
-      const double fl = cell_db(A.tc.pmax[u * G.FS + f], A.mag_scale) - A.top_db;
-      if (fl > A.tc.thresh[f]) v = -1.0;
-    }
-    if (need == 2) v = T2_NEVER;
-    return v;
-  };
-  stage_t2_plain<WAVES * 64, F5_F>(s_t2, A.tc.T2, need, 4.0, tid, t2eff);
-  constexpr int NF = F5_FPW * WAVES;
-  const int64_t tf0 = (int64_t)blockIdx.x * NF;
-  cf v[32];
-  bool validA, validB;
-  const unsigned fl_mx = f5_gather<WAVES, true>(A, tw512, regions, swin, row, chunk, tf0, G.T, v, validA, validB);
-  if (!REDO) floor_lazy_report(A.tc, A.fl, fl_bound, fl_mx, u, G.FS, lane);
-  const int64_t tq = tf0 + F5_FPW * wave;
-  if (tq >= G.T) return;   // wave-uniform; no barrier below
+// The norms of the lane group's two frames, then their forward transform in place (the transform pinned behind the norms).
+__device__ __forceinline__ void f5_norms_fwd(cf* v, cf* fb, const cf* tw512, int c, float& nA, float& nB) {
   // delta^2 = 2^-32 ||x w||^2 per frame (see k_decide_fast): the two frames' norms from the real / imaginary parts
-  float nA = 0.f, nB = 0.f;
+  nA = 0.f; nB = 0.f;
 #pragma unroll
   for (int r = 0; r < 32; ++r) { nA += v[r].x * v[r].x; nB += v[r].y * v[r].y; }
 #pragma unroll
   for (int o = 1; o < 16; o <<= 1) { nA += __shfl_xor(nA, o); nB += __shfl_xor(nB, o); }
-  cf* fb = regions + wave * WAVE_CX_H + frame_base_h(g);
   {
     int z0 = 0;
     asm volatile("" : "+v"(z0));
     fft512_fwd_half(v, fb, tw512 + z0, c);
   }
+}
+
+// Decide and pack, the one text of k_decide_fast512 (PARK = false) and k_gate_onepass512 (PARK = true: v[] lives on into the apply
+// stage).  In: the transformed v[32] of the lane's frame pair A = tq + 2 g, B = A + 1 (g = lane >> 4), the float32 compare constants
+// x4 in s_t2, the two frames' norms nA, nB taken BEFORE the transform, which of the two frames exist, the unit's need / floor_live
+// (reg_unit_of) and identity for the exact re-evaluation; wslice: the wave's exchange slice (PARK).  Out: lane c < 5 of the group
+// holds word c of the two frames' 257 bits in wA, wB.
+template <bool PARK>
+__device__ __forceinline__ void f5_decide_pack(cf* v, const float* s_t2, float nA, float nB, bool validA, bool validB, int need,
+                                               bool floor_live, int64_t u, int64_t row, int64_t chunk, int64_t tq, int lane,
+                                               cf* wslice, unsigned long long& wA, unsigned long long& wB) {
+  const int g = lane >> 4, c = lane & 15;
   const bool l0 = c == 0;
   // (one transform carries both frames: the rounding error in either spectrum scales with the norm of the PAIR)
   const float nAB = nA + nB;
@@ -202,35 +156,40 @@ __global__ __launch_bounds__(WAVES * 64, 3) void k_decide_fast512(RegArgs A) {
   if (need == 2) { pA = pB = 0; aA = aB = 0; p256A = p256B = a256A = a256B = false; }   // NaN powers have no sign
   if (!validA) { pA = 0; aA = 0; p256A = a256A = false; }
   if (!validB) { pB = 0; aB = 0; p256B = a256B = false; }
-  // exact re-evaluation of ambiguous cells, one at a time, whole wave cooperating
-  while (true) {
-    const unsigned long long pending = __ballot(aA != 0 || aB != 0 || a256A || a256B);
-    if (pending == 0) break;
-    const int src = __ffsll((long long)pending) - 1;
-    const unsigned sA = (unsigned)__shfl((int)aA, src), sB = (unsigned)__shfl((int)aB, src);
-    const int s256A = __shfl((int)a256A, src);
-    const int cs = src & 15, gs = src >> 4;
-    int which, f;   // 0: A slot, 1: B slot, 2: A bin 256, 3: B bin 256
-    int q = 0;
-    if (sA) { which = 0; q = __ffs((int)sA) - 1; f = bin5(cs, q); }
-    else if (sB) { which = 1; q = __ffs((int)sB) - 1; f = bin5(cs, q); }
-    else if (s256A) { which = 2; f = 256; }
-    else { which = 3; f = 256; }
-    const int64_t t = tq + 2 * gs + (which & 1);
-    const RegArgs& L = *late_args<RegArgs>();       // (cold path: arguments re-read here, not kept live from the entry)
-    const double P = f5_exact_power(L, row, chunk, t, f, lane);
-    double t2 = L.tc.T2[f];
-    if (floor_live) {
-      const double fl = cell_db(L.tc.pmax[u * (int64_t)L.g.FS + f], L.mag_scale) - L.top_db;
-      if (fl > L.tc.thresh[f]) t2 = -1.0;
+  // exact re-evaluation of ambiguous cells, one at a time, whole wave cooperating; PARK: half of the spectra wait in the wave's
+  // idle exchange slice for the duration (fastpath.hpp: park_upper_half)
+  if (!PARK || __ballot(aA != 0 || aB != 0 || a256A || a256B) != 0ull) {
+    float* park = reinterpret_cast<float*>(wslice) + lane;
+    if constexpr (PARK) park_upper_half(v, park);
+    while (true) {
+      const unsigned long long pending = __ballot(aA != 0 || aB != 0 || a256A || a256B);
+      if (pending == 0) break;
+      const int src = __ffsll((long long)pending) - 1;
+      const unsigned sA = (unsigned)__shfl((int)aA, src), sB = (unsigned)__shfl((int)aB, src);
+      const int s256A = __shfl((int)a256A, src);
+      const int cs = src & 15, gs = src >> 4;
+      int which, f;   // 0: A slot, 1: B slot, 2: A bin 256, 3: B bin 256
+      int q = 0;
+      if (sA) { which = 0; q = __ffs((int)sA) - 1; f = bin5(cs, q); }
+      else if (sB) { which = 1; q = __ffs((int)sB) - 1; f = bin5(cs, q); }
+      else if (s256A) { which = 2; f = 256; }
+      else { which = 3; f = 256; }
+      const int64_t t = tq + 2 * gs + (which & 1);
+      // (cold path: arguments re-read here, not kept live from the entry; RegArgs is, or is the FIRST member of, the kernel's argument)
+      const RegArgs& L = *late_args<RegArgs>();
+      const double Pe = reg_exact_power<F5_N>(L, row, chunk, t, f, lane);
+      const bool pass = Pe > t2_effective(L.tc, u, L.g.FS, f, need, floor_live, L.mag_scale, L.top_db);
+      if (lane == src) {
+        if (which == 0) { pA = (pA & ~(1u << q)) | ((pass ? 1u : 0u) << q); aA &= ~(1u << q); }
+        else if (which == 1) { pB = (pB & ~(1u << q)) | ((pass ? 1u : 0u) << q); aB &= ~(1u << q); }
+        else if (which == 2) { p256A = pass; a256A = false; }
+        else { p256B = pass; a256B = false; }
+      }
     }
-    if (need == 2) t2 = T2_NEVER;
-    const bool pass = P > t2;
-    if (lane == src) {
-      if (which == 0) { pA = (pA & ~(1u << q)) | ((pass ? 1u : 0u) << q); aA &= ~(1u << q); }
-      else if (which == 1) { pB = (pB & ~(1u << q)) | ((pass ? 1u : 0u) << q); aB &= ~(1u << q); }
-      else if (which == 2) { p256A = pass; a256A = false; }
-      else { p256B = pass; a256B = false; }
+    if constexpr (PARK) {
+      wave_lds_sync();
+      unpark_upper_half(v, park);
+      wave_lds_sync();
     }
   }
   // Pack.  A 16 x 16 bit transpose across the lane group (k_gate_onepass: four xor-shuffle steps on both 16-bit halves
@@ -251,7 +210,7 @@ __global__ __launch_bounds__(WAVES * 64, 3) void k_decide_fast512(RegArgs A) {
   tstep(2, 0x33333333u);
   tstep(1, 0x55555555u);
   const int gl = lane & 48, w = c & 3;
-  unsigned long long wA = 0ull, wB = 0ull;
+  wA = 0ull; wB = 0ull;
 #pragma unroll
   for (int h2 = 0; h2 < 2; ++h2) {
     const int j = 2 * w + h2;                                            // 32-bin block
@@ -269,6 +228,43 @@ __global__ __launch_bounds__(WAVES * 64, 3) void k_decide_fast512(RegArgs A) {
     const unsigned long long bA = __ballot(p256A), bB = __ballot(p256B);   // lane 0 of every group
     if (c == 4) { wA = (bA >> sh) & 1ull; wB = (bB >> sh) & 1ull; }
   }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// REDO: the second launch of a call with the in-kernel floor test (thresh.hpp: FloorLazy): only the units whose test fired.
+template <int WAVES, bool REDO = false>
+__global__ __launch_bounds__(WAVES * 64, 3) void k_decide_fast512(RegArgs A) {
+  if (REDO && A.fl.alim[1] != A.tc.need_tag) return;   // no unit of this call reported (the common case)
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  cf* tw512 = reinterpret_cast<cf*>(smem);
+  cf* regions = tw512 + FN;
+  float* swin = reinterpret_cast<float*>(regions + WAVES * WAVE_CX_H);
+  float* s_t2 = swin + F5_N;                 // [257] float32 compare constants x4 (the split works on 2 X)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15;
+  const Geom& G = A.g;
+  const int64_t u = blockIdx.y;
+  const RegUnit W = reg_unit_of<REDO>(A, u);
+  if (REDO && W.need == 0) return;   // whole workgroup
+  const int64_t row = W.row, chunk = W.chunk;
+  const int need = W.need;
+  const bool floor_live = W.floor_live;
+  const unsigned fl_bound = REDO ? 0xffffffffu : floor_lazy_bound(A.fl, lane);
+  stage_t2_plain<WAVES * 64, F5_F>(s_t2, A.tc.T2, need, 4.0, tid,
+                                 [&](int f) { return t2_effective(A.tc, u, G.FS, f, need, floor_live, A.mag_scale, A.top_db); });
+  constexpr int NF = F5_FPW * WAVES;
+  const int64_t tf0 = (int64_t)blockIdx.x * NF;
+  cf v[32];
+  bool validA, validB;
+  const unsigned fl_mx = f5_gather<WAVES, true>(A, tw512, regions, swin, row, chunk, tf0, G.T, v, validA, validB);
+  if (!REDO) floor_lazy_report(A.tc, A.fl, fl_bound, fl_mx, u, G.FS, lane);
+  const int64_t tq = tf0 + F5_FPW * wave;
+  if (tq >= G.T) return;   // wave-uniform; no barrier below
+  cf* fb = regions + wave * WAVE_CX_H + frame_base_h(g);
+  float nA, nB;
+  f5_norms_fwd(v, fb, tw512, c, nA, nB);
+  unsigned long long wA, wB;
+  f5_decide_pack<false>(v, s_t2, nA, nB, validA, validB, need, floor_live, u, row, chunk, tq, lane, regions + wave * WAVE_CX_H, wA,
+                        wB);
   const int64_t tA = tq + 2 * g;
   if (c < 5) {
     if (validA) A.bits[(u * G.T + tA) * 5 + c] = wA;
@@ -286,8 +282,8 @@ __global__ __launch_bounds__(WAVES * 64, 3) void k_mag_fast512(RegArgs A) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15;
   const Geom& G = A.g;
   const int64_t u = blockIdx.y;
-  const int64_t row = (A.view.unit0 + u) / A.view.n_chunks;
-  const int64_t chunk = A.view.c0 + (A.view.unit0 + u) % A.view.n_chunks;
+  const RegUnit W = reg_unit_of<false>(A, u);   // (row and chunk; the rest folds away)
+  const int64_t row = W.row, chunk = W.chunk;
   constexpr int NF = F5_FPW * WAVES;
   const int64_t tf0 = (int64_t)blockIdx.x * NF;
   cf v[32];
@@ -347,8 +343,8 @@ __global__ __launch_bounds__(WAVES * 64, 3) void k_apply_fast512(RegArgs A) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15;
   const Geom& G = A.g;
   const int64_t u = blockIdx.y;
-  const int64_t row = (A.view.unit0 + u) / A.view.n_chunks;
-  const int64_t chunk = A.view.c0 + (A.view.unit0 + u) % A.view.n_chunks;
+  const RegUnit W = reg_unit_of<false>(A, u);   // (row and chunk; the rest folds away)
+  const int64_t row = W.row, chunk = W.chunk;
   constexpr int NF = F5_FPW * WAVES, NH = NF - 3;
   const bool seam = A.part != nullptr;        // abutting tiles + k_ola_seam (fastpath.hpp), else tiles that overlap by 3 frames
   const int64_t tf0 = A.h_begin - 3 + (int64_t)blockIdx.x * (seam ? NF : NH);   // first frame of the tile

@@ -553,6 +553,73 @@ struct OnePassRegArgs {
   const unsigned long long* tab;   // MFMA operands + byte expansion (layout: the geometry's onepass*.hpp)
 };
 
+// Which unit of the view a kernel of these geometries works on, and what its compare constants need: the grid kernels
+// (u = blockIdx.y) and the ticket kernels (onepass_reg.hpp: reg_tile_of) alike.  32-bit division: a call has fewer than 2^32 units.
+struct RegUnit {
+  int64_t row, chunk;
+  bool lazy;         // the floor test runs in this launch (REDO: ran in the first one)
+  int need;          // 0: no floor live, 1: the unit's floor may be live, 2: a non-finite sample (thresh.hpp); REDO && need == 0:
+                     // nothing to redo, the caller returns
+  bool floor_live;   // need == 1
+};
+template <bool REDO>
+__device__ __forceinline__ RegUnit reg_unit_of(const RegArgs& A, int64_t u) {
+  RegUnit W;
+  const unsigned gu = (unsigned)(A.view.unit0 + u), nch = (unsigned)A.view.n_chunks;
+  W.row = gu / nch;
+  W.chunk = A.view.c0 + gu % nch;
+  // lazy (A.fl.alim set): the first launch assumes "no floor live" and tests the samples it stages; REDO serves the flagged units
+  W.lazy = A.fl.alim != nullptr;
+  W.need = (W.lazy && !REDO) ? 0 : need_of(A.tc, u);
+  W.floor_live = W.need == 1;
+  return W;
+}
+
+// |X_t[f]|^2 of frame t in float64, whole wave cooperating (lane: 0..63): the exact re-evaluation of an ambiguous cell.  N =
+// n_fft, hop N / 4, tw64 holds w_N^j for j < N / 2.  The summation order (lane + 64 i in turn, then the xor tree from 32 down) is
+// what the decision bits rest on.
+template <int N>
+__device__ __forceinline__ double reg_exact_power(const RegArgs& A, int64_t row, int64_t chunk, int64_t t, int f, int lane) {
+  constexpr int TRIPS = N / 64, UNROLL = TRIPS <= 4 ? TRIPS : 4;
+  const int64_t s0 = t * (N / 4) - A.g.padL;
+  double re = 0.0, im = 0.0;
+#pragma unroll UNROLL
+  for (int i = 0; i < TRIPS; ++i) {
+    const int m = lane + 64 * i;
+    const double xv = view_sample(A.view, row, chunk, s0 + m) * A.win64[m];
+    const int j = (f * m) & (N - 1);
+    cx<double> w = A.tw64[j & (N / 2 - 1)];
+    if (j >= N / 2) { w.x = -w.x; w.y = -w.y; }
+    re += xv * w.x;
+    im += xv * w.y;
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    re += __shfl_xor(re, off);
+    im += __shfl_xor(im, off);
+  }
+  return re * re + im * im;
+}
+
+// The exact re-evaluation of an ambiguous cell is rare (about one wave in fifty has one), but its float64 temporaries do not fit
+// next to the 64 registers of the spectra at three waves per SIMD in the one-pass gates, which keep the spectra for the apply stage
+// (a first build kept 29 of them in scratch through the hot path): there the wave parks v[16..31] in its idle exchange slice for the
+// duration (onepass.hpp does the same; fN_decide_pack<PARK = true>).  park: the slice + lane.
+__device__ __forceinline__ void park_upper_half(const cf* v, float* park) {
+  static_assert(64 * 32 * 4 <= WAVE_CX_H * 8, "parked registers must fit the wave's slice");
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    park[(2 * i) * 64] = v[16 + i].x;
+    park[(2 * i + 1) * 64] = v[16 + i].y;
+  }
+}
+__device__ __forceinline__ void unpark_upper_half(cf* v, const float* park) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    v[16 + i].x = park[(2 * i) * 64];
+    v[16 + i].y = park[(2 * i + 1) * 64];
+  }
+}
+
 template <int HOP, int NF>
 __global__ __launch_bounds__(HOP) void k_ola_seam(SeamArgs A) {
   const Geom& G = A.g;

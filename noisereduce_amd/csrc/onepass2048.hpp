@@ -71,101 +71,15 @@ __global__ __launch_bounds__(WAVES * 64, O20_OCC) void k_gate_onepass2048(OnePas
   if (!REDO && W.lazy) floor_scan_padding<WAVES * 64, F20_H, NF>(A, P, row, chunk, jt, NF, tid, fl_mx);   // the padding no tile stages
   if (!REDO) floor_lazy_report(A.tc, A.fl, fl_bound, fl_mx, u, G.FS, lane);
   const int64_t tq = tf0 + 2 * wave;
-  // ---- forward transform + decisions (k_decide_fast2048) ------------------------------------------------------
-  float nrm2 = 0.f;
-#pragma unroll
-  for (int r = 0; r < 32; ++r) nrm2 += v[r].x * v[r].x + v[r].y * v[r].y;
-#pragma unroll
-  for (int o = 1; o < 32; o <<= 1) nrm2 += __shfl_xor(nrm2, o);
+  // ---- forward transform + decisions (fast2048.hpp: f20_decide_pack) ------------------------------------------------------
   cf* fb = regions + wave * WAVE_CX_H + g * F20_FSL;
-  {
-    int z0 = 0;
-    asm volatile("" : "+v"(z0));
-    fft1k_fwd(v, fb, tw + z0, c);
-  }
+  const float nrm2 = f20_norm_fwd(v, fb, tw, c);
   const cf wl = A.tw[c];
   const int src = (lane & 32) | ((32 - c) & 31);
   const bool l0 = c == 0;
-  unsigned long long myword = 0ull;   // lane c < 17 of group g: word c of frame tq + g
-  {
-    const float d2 = nrm2 > 0.f ? 8.0f * 2.3283064e-10f * nrm2 : -1.0f;
-    unsigned pred = 0, amb = 0;
-    bool predN = false, ambN = false;     // bin 1024 (lane 0)
-    {
-      auto decide = [&](float Pw, float T, int q) {
-        const float diff = Pw - T;
-        pred |= (diff > 0.f ? 1u : 0u) << q;
-        amb |= ((diff * diff <= d2 * (Pw + T)) ? 1u : 0u) << q;
-      };
-      float Pp[16];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const cf ob = v[31 - i], own = v[(32 - i) & 31];
-        cf ta;
-        ta.x = __shfl(ob.x, src); ta.y = __shfl(ob.y, src);
-        const cf ba = {l0 ? own.x : ta.x, l0 ? own.y : ta.y};
-        cf xa, xb;
-        split_pair(v[i], ba, f20_wk(wl, i), xa, xb);
-        decide(xa.x * xa.x + xa.y * xa.y, s_t2[c + 32 * i], i);
-        Pp[i] = xb.x * xb.x + xb.y * xb.y;
-      }
-      {   // lane 0, i = 0: the pair (Zc[0], Zc[0]) also yields bin 1024
-        const float PN = Pp[0], TN = s_t2[1024], dN = PN - TN;
-        predN = l0 && dN > 0.f;
-        ambN = l0 && dN * dN <= d2 * (PN + TN);
-      }
-      const float P512 = 4.f * (v[16].x * v[16].x + v[16].y * v[16].y);   // lane 0: Zc[512] is its own partner
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const float pu = __shfl(Pp[i], src);
-        const float p0 = i < 15 ? Pp[i + 1] : P512;
-        decide(l0 ? p0 : pu, s_t2[c + 32 * (31 - i)], 31 - i);
-      }
-    }
-    if (need == 2 || !valid) { pred = 0; amb = 0; predN = false; ambN = false; }
-    // exact re-evaluation of ambiguous cells, one at a time, whole wave cooperating; half of the spectra parked in the wave's
-    // idle exchange slice for the duration (onepass_reg.hpp: park_upper_half)
-    if (__ballot(amb != 0 || ambN) != 0ull) {
-      float* park = reinterpret_cast<float*>(regions + wave * WAVE_CX_H) + lane;
-      park_upper_half(v, park);
-      while (true) {
-        const unsigned long long pending = __ballot(amb != 0 || ambN);
-        if (pending == 0) break;
-        const int sl = __ffsll((long long)pending) - 1;
-        const unsigned amb_s = (unsigned)__shfl((int)amb, sl);
-        const int q = amb_s ? (__ffs((int)amb_s) - 1) : 32;
-        const int cs = sl & 31, gs = sl >> 5;
-        const int f = q < 32 ? cs + 32 * q : 1024;
-        const RegArgs& L = *late_args<RegArgs>();     // (cold path: arguments re-read here; A is the FIRST member)
-        const double Pe = f20_exact_power(L, row, chunk, tq + gs, f, lane);
-        const bool pass = Pe > t2_effective(L.tc, u, L.g.FS, f, need, floor_live, L.mag_scale, L.top_db);
-        if (lane == sl) {
-          if (q < 32) {
-            pred = (pred & ~(1u << q)) | ((pass ? 1u : 0u) << q);
-            amb &= ~(1u << q);
-          } else {
-            predN = pass;
-            ambN = false;
-          }
-        }
-      }
-      wave_lds_sync();
-      unpark_upper_half(v, park);
-      wave_lds_sync();
-    }
-    // pack (k_decide_fast2048): the ballot of register k2 is, per frame, the 32 bins 32 k2 .. 32 k2 + 31 in natural order
-    const int sh = 32 * g;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) {
-      const unsigned long long b0 = __ballot((pred >> (2 * w)) & 1u), b1 = __ballot((pred >> (2 * w + 1)) & 1u);
-      const unsigned long long word = ((b0 >> sh) & 0xffffffffull) | (((b1 >> sh) & 0xffffffffull) << 32);
-      if (c == w) myword = word;
-    }
-    {
-      const unsigned long long bN = __ballot(predN);
-      if (c == 16) myword = (bN >> sh) & 1ull;
-    }
-  }
+  // lane c < 17 of group g: word c of frame tq + g
+  const unsigned long long myword =
+      f20_decide_pack<true>(v, s_t2, nrm2, valid, need, floor_live, u, row, chunk, tq, lane, wl, regions + wave * WAVE_CX_H);
   // ---- publish this tile's bits; the spectra stay in v[] --------------------------------------------------------
   const int fr = 2 * wave + g;      // tile row of this lane group's frame
   unsigned long long* xb_mine = P.xbits + ((size_t)u * W.ntt + (jt + 1)) * O20_TILE_WORDS;

@@ -67,104 +67,14 @@ __global__ __launch_bounds__(WAVES * 64, O25_OCC) void k_gate_onepass256(OnePass
   if (!REDO && W.lazy) floor_scan_padding<WAVES * 64, F25_H, NF>(A, P, row, chunk, jt, step, tid, fl_mx);   // the padding no tile stages
   if (!REDO) floor_lazy_report(A.tc, A.fl, fl_bound, fl_mx, u, G.FS, lane);
   const int64_t tq = tf0 + F25_FPW * wave;
-  // ---- forward transform + decisions (k_decide_fast256) -------------------------------------------------------
-  float nXY = 0.f;
-#pragma unroll
-  for (int r = 0; r < 32; ++r) nXY += v[r].x * v[r].x + v[r].y * v[r].y;
-#pragma unroll
-  for (int o = 2; o < 16; o <<= 1) nXY += __shfl_xor(nXY, o);
-  const float n1 = __shfl(nXY, lane & 48), n2 = __shfl(nXY, (lane & 48) | 1);
+  // ---- forward transform + decisions (fast256.hpp: f25_decide_pack) -------------------------------------------------------
   cf* fb = regions + wave * WAVE_CX_H + frame_base_h(g);
-  {
-    int z0 = 0;
-    asm volatile("" : "+v"(z0));
-    f25_fwd_half(v, fb, tw512 + z0, c);
-  }
+  float n1, n2;
+  f25_norms_fwd(v, fb, tw512, lane, n1, n2);
   const bool l0 = c == 0;
-  const int64_t tg = tq + 4 * g;
-  unsigned long long mine = 0ull;   // lane c = 4 fr + w (w < 3) of a group: word w of frame tg + fr
-  {
-    float d2[2];
-    d2[0] = n1 > 0.f ? 8.0f * 2.3283064e-10f * n1 : -1.0f;
-    d2[1] = n2 > 0.f ? 8.0f * 2.3283064e-10f * n2 : -1.0f;
-    unsigned pr = 0, am = 0;
-    unsigned p128 = 0, a128 = 0;
-    {
-      float Pw[4][8], P128[4];
-      f25_powers(v, l0, Pw, P128);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float T = s_t2[bin6(c, e)];
-#pragma unroll
-        for (int fr = 0; fr < 4; ++fr) {
-          const float diff = Pw[fr][e] - T;
-          pr |= (diff > 0.f ? 1u : 0u) << (8 * fr + e);
-          am |= ((diff * diff <= d2[fr >> 1] * (Pw[fr][e] + T)) ? 1u : 0u) << (8 * fr + e);
-        }
-      }
-      {
-        const float T = s_t2[128];
-#pragma unroll
-        for (int fr = 0; fr < 4; ++fr) {
-          const float diff = P128[fr] - T;
-          p128 |= ((l0 && diff > 0.f) ? 1u : 0u) << fr;
-          a128 |= ((l0 && diff * diff <= d2[fr >> 1] * (P128[fr] + T)) ? 1u : 0u) << fr;
-        }
-      }
-    }
-    if (need == 2) { pr = 0; am = 0; p128 = 0; a128 = 0; }
-#pragma unroll
-    for (int fr = 0; fr < 4; ++fr) {
-      const bool ok = tg + fr >= 0 && tg + fr < G.T;
-      if (!ok) { pr &= ~(0xffu << (8 * fr)); am &= ~(0xffu << (8 * fr)); p128 &= ~(1u << fr); a128 &= ~(1u << fr); }
-    }
-    // exact re-evaluation of ambiguous cells; half of the spectra parked in the wave's idle exchange slice meanwhile
-    if (__ballot(am != 0 || a128 != 0) != 0ull) {
-      float* park = reinterpret_cast<float*>(regions + wave * WAVE_CX_H) + lane;
-      park_upper_half(v, park);
-      while (true) {
-        const unsigned long long pending = __ballot(am != 0 || a128 != 0);
-        if (pending == 0) break;
-        const int src = __ffsll((long long)pending) - 1;
-        const unsigned sam = (unsigned)__shfl((int)am, src), s128 = (unsigned)__shfl((int)a128, src);
-        const int cs = src & 15, gs = src >> 4;
-        int fr, f, q;
-        if (sam) { q = __ffs((int)sam) - 1; fr = q >> 3; f = bin6(cs, q & 7); }
-        else { q = -1; fr = __ffs((int)s128) - 1; f = 128; }
-        const int64_t t = tq + 4 * gs + fr;
-        const RegArgs& L = *late_args<RegArgs>();     // (A is the FIRST member of the kernel's argument)
-        const double Pe = f25_exact_power(L, row, chunk, t, f, lane);
-        const bool pass = Pe > t2_effective(L.tc, u, L.g.FS, f, need, floor_live, L.mag_scale, L.top_db);
-        if (lane == src) {
-          if (q >= 0) { pr = (pr & ~(1u << q)) | ((pass ? 1u : 0u) << q); am &= ~(1u << q); }
-          else { p128 = (p128 & ~(1u << fr)) | ((pass ? 1u : 0u) << fr); a128 &= ~(1u << fr); }
-        }
-      }
-      wave_lds_sync();
-      unpark_upper_half(v, park);
-      wave_lds_sync();
-    }
-    // pack (k_decide_fast256)
-    const int sh = 16 * g;
-#pragma unroll
-    for (int fr = 0; fr < 4; ++fr) {
-      unsigned blk[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const unsigned long long b1 = __ballot(((pr >> (8 * fr + j)) & 1u) != 0);
-        const unsigned sb = l0 ? (pr >> (8 * fr + 4 + j)) & 1u : (pr >> (8 * fr + 7 - j)) & 1u;
-        const unsigned long long b2 = __ballot(sb != 0);
-        const unsigned lo = (unsigned)(b1 >> sh) & 0xffffu, up = (unsigned)(b2 >> sh) & 0xffffu;
-        const unsigned hi = (((__brev(up & 0xfffeu) >> 16) << 1) & 0xffffu) | (up & 1u);
-        blk[j] = lo | (hi << 16);
-      }
-      const unsigned long long bN = __ballot(((p128 >> fr) & 1u) != 0);
-      const unsigned long long w0 = (unsigned long long)blk[0] | ((unsigned long long)blk[1] << 32);
-      const unsigned long long w1 = (unsigned long long)blk[2] | ((unsigned long long)blk[3] << 32);
-      const unsigned long long w2 = (bN >> sh) & 1ull;
-      if ((c >> 2) == fr) mine = (c & 3) == 0 ? w0 : ((c & 3) == 1 ? w1 : w2);
-    }
-  }
+  // lane c = 4 fr + w (w < 3) of a group: word w of frame tq + 4 g + fr
+  const unsigned long long mine =
+      f25_decide_pack<true>(v, s_t2, n1, n2, G.T, need, floor_live, u, row, chunk, tq, lane, regions + wave * WAVE_CX_H);
   // ---- publish this tile's bits; the spectra stay in v[] --------------------------------------------------------
   const int fq = F25_FPW * wave + 4 * g;     // tile row of the group's first frame
   const int my_row = fq + (c >> 2), my_w = c & 3;

@@ -76,122 +76,14 @@ __global__ __launch_bounds__(WAVES * 64, O5_OCC) void k_gate_onepass512(OnePassR
   if (!REDO && W.lazy) floor_scan_padding<WAVES * 64, F5_H, NF>(A, P, row, chunk, jt, step, tid, fl_mx);   // the padding no tile stages
   if (!REDO) floor_lazy_report(A.tc, A.fl, fl_bound, fl_mx, u, G.FS, lane);
   const int64_t tq = tf0 + F5_FPW * wave;
-  // ---- forward transform + decisions (k_decide_fast512) -------------------------------------------------------
-  float nA = 0.f, nB = 0.f;
-#pragma unroll
-  for (int r = 0; r < 32; ++r) { nA += v[r].x * v[r].x; nB += v[r].y * v[r].y; }
-#pragma unroll
-  for (int o = 1; o < 16; o <<= 1) { nA += __shfl_xor(nA, o); nB += __shfl_xor(nB, o); }
+  // ---- forward transform + decisions (fast512.hpp: f5_decide_pack) -------------------------------------------------------
   cf* fb = regions + wave * WAVE_CX_H + frame_base_h(g);
-  {
-    int z0 = 0;
-    asm volatile("" : "+v"(z0));
-    fft512_fwd_half(v, fb, tw512 + z0, c);
-  }
+  float nA, nB;
+  f5_norms_fwd(v, fb, tw512, c, nA, nB);
   const bool l0 = c == 0;
-  unsigned long long wA = 0ull, wB = 0ull;   // lane c < 5 of group g: word c of frames tq + 2 g, tq + 2 g + 1
-  {
-    const float nAB = nA + nB;
-    const float dA = nAB > 0.f ? 8.0f * 2.3283064e-10f * nAB : -1.0f;
-    const float dB = dA;
-    unsigned pA = 0, pB = 0, aA = 0, aB = 0;
-    bool p256A = false, p256B = false, a256A = false, a256B = false;
-    auto decide = [&](float Pw, float T, float d2, unsigned& pr, unsigned& am, int q) {
-      const float diff = Pw - T;
-      pr |= (diff > 0.f ? 1u : 0u) << q;
-      am |= ((diff * diff <= d2 * (Pw + T)) ? 1u : 0u) << q;
-    };
-#pragma unroll
-    for (int sl = 0; sl < 16; ++sl) {
-      cf a, b;
-      f5_pair(v, sl, l0, a, b);
-      const cf E = {a.x + b.x, a.y - b.y}, O = {a.y + b.y, b.x - a.x};   // 2 A[k], 2 B[k]
-      float PA = E.x * E.x + E.y * E.y, PB = O.x * O.x + O.y * O.y;
-      if (sl == 0) {
-        const float xa = 2.f * v[0].x, xb = 2.f * v[0].y;
-        PA = l0 ? xa * xa : PA;
-        PB = l0 ? xb * xb : PB;
-      }
-      const float T = s_t2[bin5(c, sl)];
-      decide(PA, T, dA, pA, aA, sl);
-      decide(PB, T, dB, pB, aB, sl);
-    }
-    {
-      const float xa = 2.f * v[8].x, xb = 2.f * v[8].y, T = s_t2[256];
-      const float da = xa * xa - T, db = xb * xb - T;
-      p256A = l0 && da > 0.f;
-      p256B = l0 && db > 0.f;
-      a256A = l0 && da * da <= dA * (xa * xa + T);
-      a256B = l0 && db * db <= dB * (xb * xb + T);
-    }
-    if (need == 2) { pA = pB = 0; aA = aB = 0; p256A = p256B = a256A = a256B = false; }
-    if (!validA) { pA = 0; aA = 0; p256A = a256A = false; }
-    if (!validB) { pB = 0; aB = 0; p256B = a256B = false; }
-    // exact re-evaluation of ambiguous cells, one at a time, whole wave cooperating; half of the spectra parked in the wave's
-    // idle exchange slice for the duration (onepass_reg.hpp: park_upper_half)
-    if (__ballot(aA != 0 || aB != 0 || a256A || a256B) != 0ull) {
-      float* park = reinterpret_cast<float*>(regions + wave * WAVE_CX_H) + lane;
-      park_upper_half(v, park);
-      while (true) {   // exact re-evaluation of ambiguous cells, one at a time, whole wave cooperating
-        const unsigned long long pending = __ballot(aA != 0 || aB != 0 || a256A || a256B);
-        if (pending == 0) break;
-        const int src = __ffsll((long long)pending) - 1;
-        const unsigned sA = (unsigned)__shfl((int)aA, src), sB = (unsigned)__shfl((int)aB, src);
-        const int s256A = __shfl((int)a256A, src);
-        const int cs = src & 15, gs = src >> 4;
-        int which, f;
-        int q = 0;
-        if (sA) { which = 0; q = __ffs((int)sA) - 1; f = bin5(cs, q); }
-        else if (sB) { which = 1; q = __ffs((int)sB) - 1; f = bin5(cs, q); }
-        else if (s256A) { which = 2; f = 256; }
-        else { which = 3; f = 256; }
-        const int64_t t = tq + 2 * gs + (which & 1);
-        const RegArgs& L = *late_args<RegArgs>();       // (cold path: arguments re-read here; A is the FIRST member)
-        const double Pe = f5_exact_power(L, row, chunk, t, f, lane);
-        const bool pass = Pe > t2_effective(L.tc, u, L.g.FS, f, need, floor_live, L.mag_scale, L.top_db);
-        if (lane == src) {
-          if (which == 0) { pA = (pA & ~(1u << q)) | ((pass ? 1u : 0u) << q); aA &= ~(1u << q); }
-          else if (which == 1) { pB = (pB & ~(1u << q)) | ((pass ? 1u : 0u) << q); aB &= ~(1u << q); }
-          else if (which == 2) { p256A = pass; a256A = false; }
-          else { p256B = pass; a256B = false; }
-        }
-      }
-      wave_lds_sync();
-      unpark_upper_half(v, park);
-      wave_lds_sync();
-    }
-    // pack (k_decide_fast512): 16 x 16 bit transpose across the lane group, then lane c < 4 assembles word c, lane 4 bin 256
-    unsigned tr = (pA & 0xffffu) | (pB << 16);
-    auto tstep = [&](int sft, unsigned msk) {
-      const unsigned y = (unsigned)__shfl_xor((int)tr, sft);
-      const bool up = (c & sft) != 0;
-      const unsigned ysh = up ? (y >> sft) : (y << sft);
-      const unsigned mk = up ? msk : ~msk;
-      tr = (tr & ~mk) | (ysh & mk);
-    };
-    tstep(8, 0x00ff00ffu);
-    tstep(4, 0x0f0f0f0fu);
-    tstep(2, 0x33333333u);
-    tstep(1, 0x55555555u);
-    const int gl = lane & 48, w = c & 3;
-#pragma unroll
-    for (int h2 = 0; h2 < 2; ++h2) {
-      const int j = 2 * w + h2;
-      const unsigned lo = (unsigned)__shfl((int)tr, gl | j);
-      const unsigned up = (unsigned)__shfl((int)tr, gl | (15 - j));
-      const unsigned z0 = (unsigned)__shfl((int)tr, gl | (8 + j));
-      const unsigned upA = up & 0xfffeu, upB = (up >> 16) & 0xfffeu;
-      const unsigned hiA = (((__brev(upA) >> 16) << 1) & 0xffffu) | (z0 & 1u);
-      const unsigned hiB = (((__brev(upB) >> 16) << 1) & 0xffffu) | ((z0 >> 16) & 1u);
-      wA |= (unsigned long long)((lo & 0xffffu) | (hiA << 16)) << (32 * h2);
-      wB |= (unsigned long long)((lo >> 16) | (hiB << 16)) << (32 * h2);
-    }
-    {
-      const int sh = 16 * g;
-      const unsigned long long bA = __ballot(p256A), bB = __ballot(p256B);
-      if (c == 4) { wA = (bA >> sh) & 1ull; wB = (bB >> sh) & 1ull; }
-    }
-  }
+  unsigned long long wA, wB;   // lane c < 5 of group g: word c of frames tq + 2 g, tq + 2 g + 1
+  f5_decide_pack<true>(v, s_t2, nA, nB, validA, validB, need, floor_live, u, row, chunk, tq, lane, regions + wave * WAVE_CX_H, wA,
+                       wB);
   // ---- publish this tile's bits; the spectra stay in v[] --------------------------------------------------------
   const int fa = F5_FPW * wave + 2 * g;      // tile row of frame A (B: fa + 1)
   unsigned long long* xb_mine = P.xbits + ((size_t)u * W.ntt + (jt + 1)) * O5_TILE_WORDS;

@@ -12,9 +12,11 @@
 // NaN-poisoned output of a tile that lost a hand-off: onepass.hpp.  The -top_db floor test runs on the staged samples
 // (thresh.hpp: FloorLazy); REDO = the second launch for the units whose test fired.
 //
-// Here: what is the same text at every geometry -- the tile's identity, the floor test over the padding no tile stages, parking
-// half of the spectra around the exact re-evaluation, the bit rows' margins and the neighbours' rows, the K rows of an MFMA result.
-// The stages that differ (decide and pack, the MFMA shapes, the merge, the wave-private overlap-add) are in the kernels.
+// Here: what is the same text at every geometry -- the tile's identity, the floor test over the padding no tile stages, the bit
+// rows' margins and the neighbours' rows, the K rows of an MFMA result.  Decide and pack differ from geometry to geometry but not
+// between a geometry's two-pass and one-pass kernels: fN_decide_pack in fast512.hpp / fast256.hpp / fast2048.hpp, one text for both
+// (here with PARK: half of the spectra wait in the wave's slice during the exact re-evaluation, fastpath.hpp).  The MFMA shapes, the
+// merge and the wave-private overlap-add are in the kernels.
 #pragma once
 #include "fastpath.hpp"
 
@@ -34,32 +36,20 @@ __device__ __forceinline__ void reg_draw_ticket(const OnePassRegArgs& P, unsigne
 // Which tile a ticket is: n_tiles + 2 tickets per unit, one decide-only halo tile on each side of the unit's own.
 // reg_tile_of ALSO STORES: the workgroup that drew ticket 0 of a first launch zeroes P.ticket[8], the counter the REDO launch
 // draws from (thread 0, global memory).
-struct RegTile {
+struct RegTile : RegUnit {   // + row, chunk, lazy, need, floor_live (fastpath.hpp: reg_unit_of)
   int ntt;           // tiles per unit incl. the two halo tiles
   int64_t u;         // unit of this launch
   int jt;            // tile of the unit, -1 and n_tiles: the halo tiles
   bool halo_tile;
-  int64_t row, chunk;
-  bool lazy;         // the floor test runs in this launch (REDO: ran in the first one)
-  int need;          // 0: no floor live, 1: the unit's floor may be live, 2: a non-finite sample (thresh.hpp); REDO && need == 0:
-                     // nothing to redo, the caller returns
-  bool floor_live;   // need == 1
 };
 template <bool REDO>
 __device__ __forceinline__ RegTile reg_tile_of(const OnePassRegArgs& P, unsigned ticket, int tid) {
-  const RegArgs& A = P.A;
-  RegTile W;
-  W.ntt = P.n_tiles + 2;
-  const int ntt = W.ntt;
-  W.u = ticket / (unsigned)ntt;
-  W.jt = (int)(ticket % (unsigned)ntt) - 1;
+  const unsigned ntt = (unsigned)(P.n_tiles + 2);
+  RegTile W{reg_unit_of<REDO>(P.A, ticket / ntt)};
+  W.ntt = (int)ntt;
+  W.u = ticket / ntt;
+  W.jt = (int)(ticket % ntt) - 1;
   W.halo_tile = W.jt < 0 || W.jt >= P.n_tiles;
-  const unsigned gu = (unsigned)(A.view.unit0 + W.u), nch = (unsigned)A.view.n_chunks;
-  W.row = gu / nch;
-  W.chunk = A.view.c0 + gu % nch;
-  W.lazy = A.fl.alim != nullptr;
-  W.need = (W.lazy && !REDO) ? 0 : need_of(A.tc, W.u);
-  W.floor_live = W.need == 1;
   if (!REDO && W.lazy && ticket == 0u && tid == 0) P.ticket[8] = 0u;   // (the second launch's counter starts from zero)
   return W;
 }
@@ -81,25 +71,6 @@ __device__ __forceinline__ void floor_scan_padding(const RegArgs& A, const OnePa
   const int64_t c0 = (int64_t)(jt + 1) * P.scan_q, c1 = min(c0 + P.scan_q, lenA + (s_hi - last));
   for (int64_t i = c0 + tid; i < c1; i += THREADS)
     fl_mx = max(fl_mx, __float_as_uint((float)view_sample(A.view, row, chunk, i < lenA ? s_lo + i : last + (i - lenA))) & 0x7fffffffu);
-}
-
-// The exact re-evaluation of an ambiguous cell is rare (about one wave in fifty has one), but its float64 temporaries do not fit
-// next to the 64 registers of the spectra at three waves per SIMD (a first build kept 29 of them in scratch through the hot
-// path): the wave parks v[16..31] in its idle exchange slice for the duration (onepass.hpp does the same).  park: the slice + lane.
-__device__ __forceinline__ void park_upper_half(const cf* v, float* park) {
-  static_assert(64 * 32 * 4 <= WAVE_CX_H * 8, "parked registers must fit the wave's slice");
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    park[(2 * i) * 64] = v[16 + i].x;
-    park[(2 * i + 1) * 64] = v[16 + i].y;
-  }
-}
-__device__ __forceinline__ void unpark_upper_half(cf* v, const float* park) {
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    v[16 + i].x = park[(2 * i) * 64];
-    v[16 + i].y = park[(2 * i + 1) * 64];
-  }
 }
 
 // Bit rows in LDS, brow[ROWS][XW + 2]: one zero word on each side of a row, and zero rows past the neighbours' (the last
