@@ -58,14 +58,61 @@
 #endif
 #ifndef SG_CHAIN_PAR
 #define SG_CHAIN_PAR 1    // the non-stationary gate's tile chain in 16 parallel runs per band (nonstat.hpp: k_iir_chain_par); 0: A/B
+#endif
+// Development builds of the n_fft = 1024 one-pass gate (-DOP_WHO=1, -DOP_TRACE=1): process-wide device buffers that
+// stage_onepass attaches to the first launch's arguments; sg_debug_counter 16 / 8 read them back.
 #if OP_WHO
-static unsigned* g_who_dev = nullptr;     // (development builds) per workgroup of the persistent gate: ticket started, iteration, ticket drawn next, stage
+static unsigned* g_who_dev = nullptr;     // per workgroup of the persistent gate: ticket started, iteration, ticket drawn next, stage
+static hipError_t op_who_attach(sg::fast::OnePassArgs& P, hipStream_t st) {
+  hipError_t e;
+  if (!g_who_dev && (e = hipMalloc((void**)&g_who_dev, 4096 * 16)) != hipSuccess) return e;
+  P.who = g_who_dev;
+  return hipMemsetAsync(g_who_dev, 0, 4096 * 16, st);
+}
 #endif
 #if OP_TRACE
-static unsigned* g_trace_dev = nullptr;   // (development builds) the one-pass gate's phase trace of the last first launch: sg_debug_counter 8
+static unsigned* g_trace_dev = nullptr;   // the one-pass gate's phase trace of the last first launch: sg_debug_counter 8
 static size_t g_trace_tiles = 0;
 static int g_trace_ntt = 1;
-#endif
+static size_t g_trace_slots = 0;
+// at exit: the average shader cycles per wave and phase of the last traced launch (tools/trace_onepass.py --table reads these lines)
+static void op_trace_report() {
+  std::vector<unsigned> hst(g_trace_slots * 16);
+  if (hipMemcpy(hst.data(), g_trace_dev, hst.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return;
+  double sum[14] = {0}, w = 0, mx = 0;
+  double wsum[4][14] = {{0}}, ww[4] = {0};   // the same per wave index (slot = ticket * 4 + wave)
+  for (size_t i = 0; i < g_trace_slots; ++i) {
+    if (hst[i * 16 + 15] != 1u) continue;
+    w += 1;
+    ww[i & 3] += 1;
+    double tot = 0;
+    for (int k = 0; k < 14; ++k) { sum[k] += hst[i * 16 + k]; wsum[i & 3][k] += hst[i * 16 + k]; tot += hst[i * 16 + k]; }
+    mx = std::max(mx, tot);
+  }
+  for (int wv = 0; wv < 4; ++wv) {
+    fprintf(stderr, "[OP_TRACE] wave %d (%.0f completed):", wv, ww[wv]);
+    for (int k = 0; k < 14; ++k) fprintf(stderr, " %d:%.0f", k, wsum[wv][k] / (ww[wv] > 0 ? ww[wv] : 1));
+    fprintf(stderr, "\n");
+  }
+  fprintf(stderr, "[OP_TRACE] completed waves %.0f; average shader cycles per wave and phase:", w);
+  double tot = 0;
+  for (int k = 0; k < 14; ++k) { fprintf(stderr, " %d:%.0f", k, sum[k] / (w > 0 ? w : 1)); tot += sum[k] / (w > 0 ? w : 1); }
+  fprintf(stderr, "  sum %.0f  longest wave %.0f\n", tot, mx);
+}
+// one device trace [workgroup][wave][16] of `tiles` tiles (`ntt` per unit), overwritten by every launch
+static hipError_t op_trace_attach(sg::fast::OnePassArgs& P, size_t tiles, int ntt, hipStream_t st) {
+  const size_t slots = tiles * 4;
+  if (!g_trace_dev || g_trace_slots < slots) {
+    hipError_t e = hipMalloc((void**)&g_trace_dev, slots * 64);   // (the smaller one stays allocated, as the trace of a launch that may still run)
+    if (e != hipSuccess) return e;
+    g_trace_slots = slots;
+    static const int registered = atexit(op_trace_report);
+    (void)registered;
+  }
+  P.trace = g_trace_dev;
+  g_trace_tiles = tiles; g_trace_ntt = ntt;
+  return hipMemsetAsync(g_trace_dev, 0, slots * 64, st);
+}
 #endif
 #ifndef SG_STATS_TEAM
 #define SG_STATS_TEAM 1   // float64 noise-clip transform of 1024 points (n_fft = 2048) by a whole workgroup (launch_stft_n); 0: A/B
@@ -209,11 +256,23 @@ struct sg_handle {
 // one-pass gates of onepass512.hpp, onepass256.hpp, onepass2048.hpp).  One descriptor per geometry holds its constants and
 // its kernels; sg_create stores the handle's (sg_handle::reg) and every stage of these geometries reads it.
 
-// geometry constants of the one-pass gate of a register geometry
-struct OnePassSmall {
+// The hops (hop-sample blocks of the extended signal, ext = unit sample + padL) that hold the output samples [om.p0, om.p1)
+struct HopRange {
+  int64_t h_begin, h_end;
+  int64_t count() const { return h_end - h_begin; }
+};
+static HopRange hop_range(const OutMap& om, const Geom& g, int hop) {
+  return {(om.p0 + g.padL) / hop, (om.p1 - 1 + g.padL) / hop + 1};
+}
+// abutting tiles of `frames` frames over nh hops: the last tile must reach 3 hops past the range (its leading partials)
+static int64_t abutting_tiles(int64_t nh, int frames) { return (nh + 3 + frames - 1) / frames; }
+
+// geometry constants of a one-pass gate: tiles of NF frames every NH frames
+struct OnePassGeom {
   int hop, NF, NH, tile_words, xw, max_nf, max_nt, F;
-  size_t lds;
-  int extra = 0;   // abutting tiles (NH == NF): the last tile must reach 3 hops past the range (its leading partials)
+  size_t lds;      // dynamic LDS (n_fft = 1024: + OP_PROP_LDS when prop_decrease != 1)
+  int extra = 0;   // 3 when the tiles abut (NH == NF, abutting_tiles), 0 when they overlap by 3 frames
+  int64_t tiles(int64_t nh) const { return (nh + extra + NH - 1) / NH; }
 };
 
 struct RegGeom {
@@ -222,7 +281,7 @@ struct RegGeom {
   int hops;                   // complete hops per overlapping apply tile (frames - 3)
   size_t lds;                 // dynamic LDS of the decide / magnitude / apply kernels
   DevBuf sg_handle::*tw;      // twiddle table (RegArgs::tw): tw512, or tw32 at n_fft = 2048
-  OnePassSmall op, op_seam;   // one-pass gate on overlapping tiles (SG_OPT_FORCE_NOSEAM) / abutting tiles + k_ola_seam
+  OnePassGeom op, op_seam;    // one-pass gate on overlapping tiles (SG_OPT_FORCE_NOSEAM) / abutting tiles + k_ola_seam
   bool abut;                  // the one-pass gate needs abutting tiles (2048: op_seam only)
   int tab_kb;                 // k-blocks of time weights in the gate's MFMA table (sg_create; 2048 lays its table out apart)
   void (*decide[2])(fast::RegArgs);        // <4, false>, <4, true>: REDO (the units whose floor test fired)
@@ -263,6 +322,13 @@ static const RegGeom REG2048{
     {fast::k_decide_fast2048<4, false>, fast::k_decide_fast2048<4, true>}, fast::k_mag_fast2048<4>,
     {fast::k_apply_fast2048<4, false>, fast::k_apply_fast2048<4, true>},
     {fast::k_gate_onepass2048<4, false>, fast::k_gate_onepass2048<4, true>}, fast::k_ola_seam<512, 8>};
+
+// n_fft = 1024, hop 256 (onepass.hpp): abutting tiles of 16 frames.  The PROP instantiations keep 528 bytes more.
+constexpr size_t OP_PROP_LDS = 528;
+static const OnePassGeom OP1024{
+    256, 16, 16, fast::OP_TILE_WORDS, fast::OP_XW, 8, fast::OP_MAX_NT, 513,
+    (size_t)(fast::FN + 4 * fast::WAVE_CX_H) * sizeof(fast::cf) + (1024 + T2_FLOATS) * sizeof(float) + 256 * 8 + 514 * 8 + 192 * 8 + 32,
+    3};
 
 // the handle's register geometry, or nullptr (another geometry, or SG_OPT_FORCE_NOFAST)
 static const RegGeom* reg_geom(const sg_handle* h) { return h->force_nofast ? nullptr : h->reg; }
@@ -356,6 +422,22 @@ static hipError_t set_lds(const void* kern, size_t bytes) {
   hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   if (e == hipSuccess) have = bytes;
   return e;
+}
+
+// One kernel launch with `lds` bytes of dynamic LDS.  `raise`: the size may exceed the 64 KiB a kernel gets without asking
+// (set_lds first); a caller that knows its size is below passes false and saves the mutex and the map lookup.
+template <typename... KA, typename... A>
+static hipError_t launch_lds_if(bool raise, void (*kern)(KA...), dim3 grid, dim3 block, size_t lds, hipStream_t st, const A&... a) {
+  if (raise) {
+    hipError_t e = set_lds(reinterpret_cast<const void*>(kern), lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kern, grid, block, lds, st, a...);
+  return hipGetLastError();
+}
+template <typename... KA, typename... A>
+static hipError_t launch_lds(void (*kern)(KA...), dim3 grid, dim3 block, size_t lds, hipStream_t st, const A&... a) {
+  return launch_lds_if(true, kern, grid, block, lds, st, a...);
 }
 
 static int ensure(sg_handle* h, DevBuf& b, size_t bytes) {
@@ -538,8 +620,12 @@ static hipError_t launch_decide_lds_n(const sg_handle* h, const View& v, const G
   return hipGetLastError();
 }
 
+// (mixed-radix frame lengths, mixed.hpp: see the section below)
 static hipError_t launch_decide_mr(const sg_handle* h, const View& v, const Geom& g, int64_t units, const ThreshConsts& tc,
-                                   unsigned long long* bits, int wpr, hipStream_t st);
+                                   unsigned long long* bits, int wpr, hipStream_t st) {
+  return mr_launch_decide(h->mr, v, g, units, (const cx<float>*)h->tw32.p, (const cx<float>*)h->mr_pt32.p, (const float*)h->wa32.p, (const cx<double>*)h->tw64.p,
+                          (const double*)h->wfull64.p, tc, h->mag_scale, h->p.top_db, bits, wpr, st);
+}
 static hipError_t launch_decide_lds(const sg_handle* h, const View& v, const Geom& g, int64_t units,
                                     const ThreshConsts& tc, unsigned long long* bits, int wpr, hipStream_t st) {
   if (h->mr_ok) return launch_decide_mr(h, v, g, units, tc, bits, wpr, st);
@@ -608,19 +694,10 @@ static hipError_t launch_bits_mr(const sg_handle* h, const View& v, const Geom& 
   return mr_launch_bits(MODE, h->mr, v, g, units, (const cx<double>*)h->tw64.p, (const cx<double>*)h->mr_pt64.p, (const double*)h->wfull64.p, tc, h->mag_scale,
                         h->p.top_db, pmax_bits, bits, wpr, st);
 }
-static hipError_t launch_decide_mr(const sg_handle* h, const View& v, const Geom& g, int64_t units, const ThreshConsts& tc,
-                                   unsigned long long* bits, int wpr, hipStream_t st) {
-  return mr_launch_decide(h->mr, v, g, units, (const cx<float>*)h->tw32.p, (const cx<float>*)h->mr_pt32.p, (const float*)h->wa32.p, (const cx<double>*)h->tw64.p,
-                          (const double*)h->wfull64.p, tc, h->mag_scale, h->p.top_db, bits, wpr, st);
-}
 static hipError_t launch_apply_mr(const sg_handle* h, const View& v, const Geom& g, int64_t units, const float* wa, const float* ws,
                                   const float* M, float* seg, hipStream_t st, const unsigned short* K16, float kscale) {
   return mr_launch_apply(h->mr, v, g, units, (const cx<float>*)h->tw32.p, (const cx<float>*)h->mr_pt32.p, wa, ws, M, seg, K16, kscale, st);
 }
-template <int MODE>
-static hipError_t launch_bits(int N, const View& v, const Geom& g, int64_t units, const void* tw, const void* wfull,
-                              const ThreshConsts& tc, double mag_scale, double top_db, unsigned long long* pmax_bits,
-                              unsigned long long* bits, int wpr, hipStream_t st);
 // (the decision kernels of the fused path, whatever transform the frame length runs on)
 template <int MODE>
 static hipError_t launch_bits_any(const sg_handle* h, const View& v, const Geom& g, int64_t units, const ThreshConsts& tc,
@@ -1500,17 +1577,79 @@ static int stage_decide(sg_handle* h, const Geom& g, int64_t ub, const double* t
   return SG_OK;
 }
 
+// Hand-offs between workgroups of one launch (tagged granules, bounded polls): the host-mapped error word, the
+// verdict on earlier launches, a fresh epoch.  Granule buffers are zero when (re)allocated and the epoch only grows:
+// a fresh granule never carries it.
+// A new tag for the granules of the next hand-off launch (a call that launches twice takes two).
+static int handoff_next_epoch(sg_handle* h, hipStream_t st) {
+  if (++h->epoch == 0) {  // wrapped: tags of 2^32 launches ago could alias
+    if (h->xbits.p) HIPCHK(h, hipMemsetAsync(h->xbits.p, 0, h->xbits.bytes, st));
+    if (h->xpart.p) HIPCHK(h, hipMemsetAsync(h->xpart.p, 0, h->xpart.bytes, st));
+    h->epoch = 1;
+    if (h->err_host) h->err_host[1] = 0u;   // the floor-test stamp is an epoch too
+  }
+  return SG_OK;
+}
+
+static int handoff_prepare(sg_handle* h, hipStream_t st) {
+  {
+    // The work counter is never reset: every launch takes exactly its grid size in tickets, the kernels subtract
+    // the running base.
+    bool fresh = false;
+    int rc = ensure_zeroed(h, h->xticket, 64, st, &fresh);
+    if (rc) return rc;
+    if (fresh) h->ticket_base = 0;
+  }
+  if (!h->err_host) {
+    HIPCHK(h, hipHostMalloc((void**)&h->err_host, 64, hipHostMallocMapped));
+    *h->err_host = 0u;
+    h->err_host[1] = 0u;   // floor-test stamp (onepass_run)
+    HIPCHK(h, hipHostGetDevicePointer((void**)&h->err_dev, h->err_host, 0));
+  }
+  if (*h->err_host != 0u) {
+    // only reached by callers that never synchronise through the library (sg_check_errors and every synchronising
+    // entry point report a lost hand-off for the call that suffered it)
+    const unsigned e = *h->err_host;
+    *h->err_host = 0u;
+    FAIL(h, SG_E_HANDOFF, "a tile hand-off of an EARLIER call on this handle timed out (code %u): that call's output "
+                          "is invalid (call sg_check_errors after a call to learn about it in time)", e);
+  }
+  h->lose_now = 0;
+  if (h->inject_fault) {  // test hook: this launch "loses" a hand-off
+    *h->err_host = h->inject_fault & 7u;          // bits 0..2: reported only (the output is fine)
+    h->lose_now = (h->inject_fault >> 3) & 7u;    // bits 3..5: lost INSIDE the kernel (the output is poisoned)
+    h->inject_fault = 0;
+  }
+  return handoff_next_epoch(h, st);
+}
+
+// After the stream has been synchronised: did a hand-off of the work just completed time out?
+static int handoff_verdict(sg_handle* h) {
+  if (h->err_host && *h->err_host != 0u) {
+    const unsigned e = *h->err_host;
+    *h->err_host = 0u;
+    FAIL(h, SG_E_HANDOFF, "a tile hand-off timed out (code %u: %s%s%s): the output of the call(s) enqueued since the "
+                          "last check is invalid; re-run them (SG_OPT_FORCE_SPLIT + SG_OPT_FORCE_NOLEAN select the "
+                          "kernels without in-launch hand-offs)",
+         e, (e & 1u) ? "mask bits " : "", (e & 2u) ? "partial hops (one-pass gate) " : "",
+         (e & 4u) ? "partial hops (fused apply)" : "");
+  }
+  return SG_OK;
+}
+
+extern "C" int sg_check_errors(sg_handle* h, void* stream) {
+  if (!h) return SG_E_INVALID;
+  HIPCHK(h, hipStreamSynchronize((hipStream_t)stream));
+  return handoff_verdict(h);
+}
+
+// (defined next to the decision kernels' other stages, below)
+static int stage_prep_floor(sg_handle* h, const View& v, const Geom& g, int64_t ub, ThreshConsts* tc_out, hipStream_t st,
+                            const View* v_exact, unsigned* live_host, unsigned stamp);
+
 // ------------------------------------------------------------------------------------------
 // stages of the register geometries (n_fft = 512 / 256 / 2048): each reads the handle's RegGeom
 // ------------------------------------------------------------------------------------------
-static int handoff_prepare(sg_handle* h, hipStream_t st);
-static int handoff_next_epoch(sg_handle* h, hipStream_t st);
-static int stage_prep_floor(sg_handle* h, const View& v, const Geom& g, int64_t ub, ThreshConsts* tc_out, hipStream_t st,
-                            const View* v_exact, unsigned* live_host, unsigned stamp);
-template <int MODE>
-static hipError_t launch_bits_any(const sg_handle* h, const View& v, const Geom& g, int64_t units, const ThreshConsts& tc,
-                                  unsigned long long* pmax_bits, unsigned long long* bits, int wpr, hipStream_t st);
-
 static fast::RegArgs reg_args(const sg_handle* h, const RegGeom* r, const View& v, const Geom& g) {
   fast::RegArgs A{};
   A.view = v; A.g = g;
@@ -1524,15 +1663,6 @@ static fast::RegArgs reg_args(const sg_handle* h, const RegGeom* r, const View& 
   return A;
 }
 
-// one launch of a register-transform kernel: 256 threads, `lds` bytes of dynamic LDS
-template <typename ARGS>
-static hipError_t reg_launch(void (*kern)(ARGS), dim3 grid, size_t lds, hipStream_t st, const ARGS& A) {
-  hipError_t e = set_lds(reinterpret_cast<const void*>(kern), lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, A);
-  return hipGetLastError();
-}
-
 static int stage_decide_reg(sg_handle* h, const RegGeom* r, const View& v, const Geom& g, int64_t ub, const ThreshConsts& tc,
                             unsigned long long* bits, hipStream_t st, const FloorLazy& fl = FloorLazy{}, bool redo = false) {
   ProfScope ps(h, redo ? SG_STAGE_STFT_MAX : SG_STAGE_DECIDE_FAST, st);   // (the early-exit second launch is booked with the pre-pass)
@@ -1540,7 +1670,7 @@ static int stage_decide_reg(sg_handle* h, const RegGeom* r, const View& v, const
   A.tc = tc;
   A.bits = bits;
   A.fl = fl;
-  HIPCHK(h, reg_launch(r->decide[redo], dim3((unsigned)((g.T + r->frames - 1) / r->frames), (unsigned)ub), r->lds, st, A));
+  HIPCHK(h, launch_lds(r->decide[redo], dim3((unsigned)((g.T + r->frames - 1) / r->frames), (unsigned)ub), dim3(256), r->lds, st, A));
   return SG_OK;
 }
 
@@ -1551,7 +1681,7 @@ static int stage_mag_reg(sg_handle* h, const RegGeom* r, const View& v, const Ge
   A.mag = mag;
   A.iir_b = iir_b;
   A.sub = sub;
-  HIPCHK(h, reg_launch(r->mag, dim3((unsigned)((g.T + r->frames - 1) / r->frames), (unsigned)ub), r->lds, st, A));
+  HIPCHK(h, launch_lds(r->mag, dim3((unsigned)((g.T + r->frames - 1) / r->frames), (unsigned)ub), dim3(256), r->lds, st, A));
   return SG_OK;
 }
 
@@ -1566,9 +1696,9 @@ static int launch_seam(sg_handle* h, const RegGeom* r, const fast::RegArgs& A, i
   return SG_OK;
 }
 
-// abutting tiles over the hops [hb, he) + their seam partials in h->seam
-static int reg_seam_tiles(sg_handle* h, const RegGeom* r, int64_t hb, int64_t he, int64_t ub, fast::RegArgs* A) {
-  const int64_t tiles = (he - hb + 3 + r->frames - 1) / r->frames;
+// abutting tiles over nh hops + their seam partials in h->seam
+static int reg_seam_tiles(sg_handle* h, const RegGeom* r, int64_t nh, int64_t ub, fast::RegArgs* A) {
+  const int64_t tiles = abutting_tiles(nh, r->frames);
   int rc = ensure(h, h->seam, (size_t)ub * tiles * 6 * r->hop * sizeof(float));
   if (rc) return rc;
   A->part = (float*)h->seam.p;
@@ -1586,18 +1716,19 @@ static int stage_apply_reg(sg_handle* h, const RegGeom* r, const View& v, const 
   A.inv_ktot = (float)(1.0 / (double)h->ktot);
   A.om = om;
   A.normalize = normalize;
-  A.h_begin = (om.p0 + g.padL) / r->hop;
-  A.h_end = (om.p1 - 1 + g.padL) / r->hop + 1;
-  const int64_t nh = A.h_end - A.h_begin;
+  const HopRange hr = hop_range(om, g, r->hop);
+  A.h_begin = hr.h_begin;
+  A.h_end = hr.h_end;
+  const int64_t nh = hr.count();
   if (nh <= 0) return SG_OK;
   // (round 6) abutting tiles; the 3 hops that straddle two tiles as partial sums + k_ola_seam (fastpath.hpp)
-  const int64_t tiles = (nh + 3 + r->frames - 1) / r->frames;
+  const int64_t tiles = abutting_tiles(nh, r->frames);
   const bool seam = tiles >= 2 && !h->force_noseam;
   A.n_tiles = (int)tiles;
   int rc;
-  if (seam && (rc = reg_seam_tiles(h, r, A.h_begin, A.h_end, ub, &A))) return rc;
+  if (seam && (rc = reg_seam_tiles(h, r, nh, ub, &A))) return rc;
   const dim3 grid((unsigned)(seam ? tiles : (nh + r->hops - 1) / r->hops), (unsigned)ub);
-  HIPCHK(h, reg_launch(r->apply[mask_f == nullptr], grid, r->lds, st, A));
+  HIPCHK(h, launch_lds(r->apply[mask_f == nullptr], grid, dim3(256), r->lds, st, A));
   if (seam) return launch_seam(h, r, A, ub, st);
   return SG_OK;
 }
@@ -1654,102 +1785,120 @@ static int floor_setup(sg_handle* h, const Geom& g, int64_t ub, int nb, hipStrea
   return SG_OK;
 }
 
-// (round 6) one-pass gate of a register geometry: decide + smooth + apply in one kernel, tiles exchange their bits
-static bool onepass_small_ok(const sg_handle* h, const Geom& g, const OutMap& om, const OnePassSmall& S, const DevBuf& tab) {
-  if (h->force_nofast || h->force_split || h->force_f64_decide || h->force_unfused || !h->fused_ok) return false;
-  if (h->p.variant != SG_VARIANT_S || !h->p.stationary || !h->p.smooth_mask) return false;
-  if (h->p.n_grad_freq > S.max_nf || h->p.n_grad_time > S.max_nt || g.F != S.F || !tab.p) return false;
-  if (h->tile_order == 1) return false;
-  const int64_t hb = (om.p0 + g.padL) / S.hop, he = (om.p1 - 1 + g.padL) / S.hop + 1;
-  return he > hb;
-}
-// P: the kernel's argument struct (its member A already filled with the geometry's tables); launch(P, redo) enqueues it
-template <typename LAUNCH>
-static int stage_onepass_small(sg_handle* h, const View& v, const View& vx, const Geom& g, int64_t ub, const OutMap& om,
-                               hipStream_t st, const OnePassSmall& S, fast::OnePassRegArgs P, const DevBuf& tab, LAUNCH launch) {
+// One-pass gate (all four geometries): decide + smooth + apply in one kernel, tiles exchange their bits.  onepass_run owns the
+// launch protocol -- floor test, tiles, exchange buffer, tickets, epochs, the REDO launch of a lazy call -- and the two
+// geometries' stages (stage_onepass_reg, stage_onepass) supply what is particular to them.
+//
+// What onepass_run has worked out when it hands the arguments to the geometry's `first` hook:
+struct OnePassCall {
+  FloorSetup fs;      // fs.lazy: the floor test runs in the first launch and a REDO launch follows
+  int64_t n_tiles;    // tiles per unit (the exchange buffer holds two halo tiles more)
+  unsigned total;     // units * (n_tiles + 2): the workgroups, and the tickets, of a launch with one tile per workgroup
+  unsigned grid;      // workgroups of the first launch (the hook may change it) ...
+  unsigned tickets;   // ... and the tickets it draws from the running counter
+};
+// ARGS: the kernel's argument struct (fast::OnePassArgs / fast::OnePassRegArgs) with the geometry's tables filled in.
+// first(P, C) completes it before the first launch (compare constants, what only that kernel has) and returns SG_OK or an
+// error; launch(P, redo, grid) enqueues the kernel.  nb: bounds of the in-kernel floor test (floor_setup).
+template <typename ARGS, typename FIRST, typename LAUNCH>
+static int onepass_run(sg_handle* h, const View& v, const View& vx, const Geom& g, int64_t ub, const OutMap& om, hipStream_t st,
+                       const OnePassGeom& S, int nb, ARGS P, FIRST first, LAUNCH launch) {
   int rc;
-  FloorSetup fs;
-  if ((rc = floor_setup(h, g, ub, (g.FS + 63) / 64, st, &fs))) return rc;
-  const bool lazy = fs.lazy;
+  OnePassCall C;
+  if ((rc = floor_setup(h, g, ub, nb, st, &C.fs))) return rc;
+  const bool lazy = C.fs.lazy;
   ++(lazy ? h->n_floor_lazy : h->n_floor_apriori);
-  const int wpr = (g.F + 63) / 64;
-  if (!lazy && (rc = stage_prep_floor(h, v, g, ub, &fs.tc, st, &vx, h->err_dev + 1, h->epoch))) return rc;
-  const ThreshConsts& tc = fs.tc;
-  P.A.tc = tc;
-  P.A.fl = fs.fl;
-  P.A.inv_ktot = (float)(1.0 / (double)h->ktot);
+  if (!lazy && (rc = stage_prep_floor(h, v, g, ub, &C.fs.tc, st, &vx, h->err_dev + 1, h->epoch))) return rc;
+  const HopRange hr = hop_range(om, g, S.hop);
   P.A.om = om;
   P.A.normalize = 1;
-  P.A.h_begin = (om.p0 + g.padL) / S.hop;
-  P.A.h_end = (om.p1 - 1 + g.padL) / S.hop + 1;
-  const int64_t nh = P.A.h_end - P.A.h_begin;
-  const int64_t n_tiles = (nh + S.extra + S.NH - 1) / S.NH, ntt = n_tiles + 2;
+  P.A.h_begin = hr.h_begin;
+  P.A.h_end = hr.h_end;
+  const int64_t n_tiles = S.tiles(hr.count()), ntt = n_tiles + 2;
+  // granule buffers are zero when (re)allocated and the epoch only grows: a fresh granule never carries it
   if ((rc = ensure_zeroed(h, h->xbits, (size_t)ub * ntt * S.tile_words * 8, st))) return rc;
   P.xbits = (unsigned long long*)h->xbits.p;
   P.ticket = (unsigned*)h->xticket.p;
   P.ticket_base = h->ticket_base;
-  h->ticket_base += (unsigned)(ub * ntt);
   P.epoch = h->epoch;
-  const bool lose = (h->lose_now & 3u) != 0;   // test hook: every poll of this launch gives up at once (the timeout path itself)
-  P.poll_epoch = lose ? ~h->epoch : h->epoch;
-  P.spin_max = lose ? 0 : fast::OP_SPIN_MAX;
   P.err = h->err_dev;
-  P.nf = h->p.n_grad_freq; P.nt = h->p.n_grad_time; P.n_tiles = (int)n_tiles;
-  P.tab = (const unsigned long long*)tab.p;
+  P.nf = h->p.n_grad_freq; P.nt = h->p.n_grad_time;
   P.prop = (float)h->p.prop_decrease;
   {
     // the part of a unit's window outside its tiles' spans, dealt evenly to the unit's tiles ("floor test" in the kernels)
     const int64_t SPAN = (int64_t)(S.NF - 1 + 4) * S.hop;
-    const int64_t sp0 = (P.A.h_begin - 3 - S.NH) * S.hop - g.padL, sp1 = (P.A.h_begin - 3 + n_tiles * S.NH) * S.hop - g.padL + SPAN;
+    const int64_t sp0 = (hr.h_begin - 3 - S.NH) * S.hop - g.padL, sp1 = (hr.h_begin - 3 + n_tiles * S.NH) * S.hop - g.padL + SPAN;
     const int64_t inside = std::max<int64_t>(0, std::min<int64_t>(v.Lp, sp1) - std::max<int64_t>(0, sp0));
     const int64_t q = (v.Lp - inside + ntt - 1) / ntt;
     if (q > 0x7fffffff) FAIL(h, SG_E_UNSUPPORTED, "one-pass gate: window of %lld samples", (long long)v.Lp);
     P.scan_q = (int)q;
   }
-  const dim3 grid((unsigned)(ub * ntt));
+  C.n_tiles = n_tiles;
+  C.total = C.grid = C.tickets = (unsigned)(ub * ntt);
+  if ((rc = first(P, C))) return rc;
+  h->ticket_base += C.tickets;
   {
     ProfScope ps(h, SG_STAGE_ONEPASS, st);
-    HIPCHK(h, launch(P, false, grid));
+    HIPCHK(h, launch(P, false, dim3(C.grid)));
   }
   if (lazy) {
-    // the units whose floor test fired: float64 band maxima, then the gate again with them (both return at once otherwise)
+    // the units whose floor test fired: float64 band maxima, then the gate again with them.  Both launches return at once
+    // when no unit reported (the common case)
     ProfScope ps(h, SG_STAGE_STFT_MAX, st);
-    HIPCHK(h, launch_bits_any<0>(h, vx, g, ub, tc, (unsigned long long*)h->pmax.p, (unsigned long long*)h->bits.p, wpr, st));
+    HIPCHK(h, launch_bits_any<0>(h, vx, g, ub, C.fs.tc, (unsigned long long*)h->pmax.p, (unsigned long long*)h->bits.p,
+                                 (g.F + 63) / 64, st));
     if ((rc = handoff_next_epoch(h, st))) return rc;
     P.epoch = h->epoch;
-    P.poll_epoch = h->epoch;
-    P.spin_max = fast::OP_SPIN_MAX;
-    P.ticket = (unsigned*)h->xticket.p + 8;   // its own counter (zeroed by the first launch's ticket-0 workgroup)
+    P.ticket = (unsigned*)h->xticket.p + 8;   // its own counter (zeroed by the first launch's ticket-0 workgroup): it takes tickets only if a unit reported
     P.ticket_base = 0;
-    HIPCHK(h, launch(P, true, grid));
+    HIPCHK(h, launch(P, true, dim3(C.total)));
   }
   h->dbg_xbits = true;
   h->dbg_trows = S.NF; h->dbg_tstep = S.NH; h->dbg_twords = S.tile_words; h->dbg_txw = S.xw;
-  h->dbg_tf0 = P.A.h_begin - 3;
+  h->dbg_tf0 = hr.h_begin - 3;
   h->dbg_ntt = (int)ntt;
-  h->dbg_db = std::max<int64_t>(0, P.A.h_begin - 3 - S.NH);
-  h->dbg_de = std::min<int64_t>(g.T, P.A.h_begin - 3 + (int64_t)S.NH * (n_tiles + 1) + (S.NF - S.NH));
+  h->dbg_db = std::max<int64_t>(0, hr.h_begin - 3 - S.NH);
+  h->dbg_de = std::min<int64_t>(g.T, hr.h_begin - 3 + (int64_t)S.NH * (n_tiles + 1) + (S.NF - S.NH));
   return SG_OK;
 }
 
+// (round 6) one-pass gate of a register geometry
+static bool onepass_geom_ok(const sg_handle* h, const Geom& g, const OutMap& om, const OnePassGeom& S, const DevBuf& tab) {
+  if (h->force_nofast || h->force_split || h->force_f64_decide || h->force_unfused || !h->fused_ok) return false;
+  if (h->p.variant != SG_VARIANT_S || !h->p.stationary || !h->p.smooth_mask) return false;
+  if (h->p.n_grad_freq > S.max_nf || h->p.n_grad_time > S.max_nt || g.F != S.F || !tab.p) return false;
+  if (h->tile_order == 1) return false;
+  return hop_range(om, g, S.hop).count() > 0;
+}
 static bool onepass_reg_ok(const sg_handle* h, const RegGeom* r, const Geom& g, const OutMap& om) {
-  return !(r->abut && h->force_noseam) && onepass_small_ok(h, g, om, r->op, h->regtab);
+  return !(r->abut && h->force_noseam) && onepass_geom_ok(h, g, om, r->op, h->regtab);
 }
 static int stage_onepass_reg(sg_handle* h, const RegGeom* r, const View& v, const View& vx, const Geom& g, int64_t ub,
                              const OutMap& om, hipStream_t st) {
   fast::OnePassRegArgs P{};
   P.A = reg_args(h, r, v, g);
+  P.A.inv_ktot = (float)(1.0 / (double)h->ktot);
+  P.tab = (const unsigned long long*)h->regtab.p;
   // (abutting tiles + k_ola_seam: the default; SG_OPT_FORCE_NOSEAM keeps overlapping tiles where the geometry has them)
   const bool seam = r->abut || !h->force_noseam;
   int rc;
-  if (seam && (rc = reg_seam_tiles(h, r, (om.p0 + g.padL) / r->hop, (om.p1 - 1 + g.padL) / r->hop + 1, ub, &P.A))) return rc;
-  const OnePassSmall& S = seam ? r->op_seam : r->op;
-  fast::RegArgs last{};
-  auto launch = [&](const fast::OnePassRegArgs& Q, bool redo, dim3 grid) -> hipError_t {
-    last = Q.A;
-    return reg_launch(r->gate[redo], grid, S.lds, st, Q);
+  if (seam && (rc = reg_seam_tiles(h, r, hop_range(om, g, r->hop).count(), ub, &P.A))) return rc;
+  const OnePassGeom& S = seam ? r->op_seam : r->op;
+  auto first = [&](fast::OnePassRegArgs& Q, const OnePassCall& C) -> int {
+    Q.A.tc = C.fs.tc;
+    Q.A.fl = C.fs.fl;
+    Q.n_tiles = (int)C.n_tiles;
+    return SG_OK;
   };
-  if ((rc = stage_onepass_small(h, v, vx, g, ub, om, st, S, P, h->regtab, launch)) || !seam) return rc;
+  fast::RegArgs last{};
+  auto launch = [&](fast::OnePassRegArgs& Q, bool redo, dim3 grid) {
+    const bool lose = !redo && (h->lose_now & 3u);   // test hook: every poll of the first launch gives up at once (the timeout path itself)
+    Q.poll_epoch = lose ? ~Q.epoch : Q.epoch;
+    Q.spin_max = lose ? 0 : fast::OP_SPIN_MAX;
+    last = Q.A;
+    return launch_lds(r->gate[redo], grid, dim3(256), S.lds, st, Q);
+  };
+  if ((rc = onepass_run(h, v, vx, g, ub, om, st, S, (g.FS + 63) / 64, P, first, launch)) || !seam) return rc;
   if (r->abut && P.A.n_tiles < 2) return SG_OK;   // (2048 books no seam stage for a single tile)
   ProfScope ps(h, SG_STAGE_APPLY_FAST, st);   // (after the second launch, if any: a redone unit rewrote its partials)
   return launch_seam(h, r, last, ub, st);
@@ -2004,42 +2153,27 @@ static int stage_smooth_bits(sg_handle* h, const Geom& g, int64_t ub, bool fast,
     const unsigned long long* ftab = (small && h->ftab.p) ? (const unsigned long long*)h->ftab.p : nullptr;
     size_t lds = smooth2_cf_bytes(rows + 2, g.F, small ? 1 : 2) + (size_t)rows * (wpr + 2) * 8 + (ftab ? 8192 : 0);
     dim3 grid((unsigned)((te - tb + tt - 1) / tt), (unsigned)ub);
-    if (small) {
-      auto kern = k_smooth_bits2<uint8_t>;
-      if (lds > 65536)
-        HIPCHK(h, set_lds(reinterpret_cast<const void*>(kern), lds));
-      hipLaunchKernelGGL(kern, grid, dim3(SM2_THREADS), lds, st, (const unsigned long long*)h->bits.p, g, wpr, nf,
-                         nt, (unsigned short*)h->K16.p, fast ? 1 : 0, tb, te, ftab, tt);
-    } else {
-      auto kern = k_smooth_bits2<uint16_t>;
-      if (lds > 65536)
-        HIPCHK(h, set_lds(reinterpret_cast<const void*>(kern), lds));
-      hipLaunchKernelGGL(kern, grid, dim3(SM2_THREADS), lds, st, (const unsigned long long*)h->bits.p, g, wpr, nf,
-                         nt, (unsigned short*)h->K16.p, fast ? 1 : 0, tb, te, (const unsigned long long*)nullptr, tt);
-    }
+    // (cell: uint8_t weight sums while (nf + 1)^2 fits a byte, else uint16_t; ftab is null then)
+    auto go = [&](auto cell) {
+      return launch_lds_if(lds > 65536, k_smooth_bits2<decltype(cell)>, grid, dim3(SM2_THREADS), lds, st,
+                           (const unsigned long long*)h->bits.p, g, wpr, nf, nt, (unsigned short*)h->K16.p, fast ? 1 : 0, tb, te, ftab, tt);
+    };
+    HIPCHK(h, small ? go(uint8_t{}) : go(uint16_t{}));
   } else if (h->p.smooth_mask) {
     const int rows = SM_TT + 2 * nt;
     const bool small = (nf + 1) * (nf + 1) <= 255;
     size_t lds = smooth_cf_bytes(rows, g.F, small ? 1 : 2) + (size_t)rows * wpr * 8;
     dim3 grid((unsigned)((g.T + SM_TT - 1) / SM_TT), (unsigned)ub);
-    if (small) {
-      auto kern = k_smooth_bits<uint8_t>;
-      if (lds > 65536)
-        HIPCHK(h, set_lds(reinterpret_cast<const void*>(kern), lds));
-      hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, (const unsigned long long*)h->bits.p, g, wpr, nf, nt,
-                         (unsigned short*)h->K16.p, fast ? 1 : 0);
-    } else {
-      auto kern = k_smooth_bits<uint16_t>;
-      if (lds > 65536)
-        HIPCHK(h, set_lds(reinterpret_cast<const void*>(kern), lds));
-      hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, (const unsigned long long*)h->bits.p, g, wpr, nf, nt,
-                         (unsigned short*)h->K16.p, fast ? 1 : 0);
-    }
+    auto go = [&](auto cell) {
+      return launch_lds_if(lds > 65536, k_smooth_bits<decltype(cell)>, grid, dim3(256), lds, st,
+                           (const unsigned long long*)h->bits.p, g, wpr, nf, nt, (unsigned short*)h->K16.p, fast ? 1 : 0);
+    };
+    HIPCHK(h, small ? go(uint8_t{}) : go(uint16_t{}));
   } else {
     hipLaunchKernelGGL(k_bits_to_k16, dim3(grid_1d(cells, 256)), dim3(256), 0, st,
                        (const unsigned long long*)h->bits.p, g, wpr, (unsigned short*)h->K16.p, ub, fast ? 1 : 0);
+    HIPCHK(h, hipGetLastError());
   }
-  HIPCHK(h, hipGetLastError());
   return SG_OK;
 }
 
@@ -2080,7 +2214,6 @@ static int stage_prep_floor(sg_handle* h, const View& v, const Geom& g, int64_t 
   return SG_OK;
 }
 
-static int handoff_prepare(sg_handle* h, hipStream_t st);
 // Fused stationary mask (variant S): STFT(f64) -> bits -> integer smoothing -> K16 -> float mask.
 static int stage_fused_mask(sg_handle* h, const View& v, const Geom& g, int64_t ub, bool fast, int64_t tb,
                             int64_t te, hipStream_t st) {
@@ -2166,72 +2299,6 @@ static int stage_fused_mask(sg_handle* h, const View& v, const Geom& g, int64_t 
   return SG_OK;
 }
 
-// Hand-offs between workgroups of one launch (tagged granules, bounded polls): the host-mapped error word, the
-// verdict on earlier launches, a fresh epoch.  Granule buffers are zero when (re)allocated and the epoch only grows:
-// a fresh granule never carries it.
-// A new tag for the granules of the next hand-off launch (a call that launches twice takes two).
-static int handoff_next_epoch(sg_handle* h, hipStream_t st) {
-  if (++h->epoch == 0) {  // wrapped: tags of 2^32 launches ago could alias
-    if (h->xbits.p) HIPCHK(h, hipMemsetAsync(h->xbits.p, 0, h->xbits.bytes, st));
-    if (h->xpart.p) HIPCHK(h, hipMemsetAsync(h->xpart.p, 0, h->xpart.bytes, st));
-    h->epoch = 1;
-    if (h->err_host) h->err_host[1] = 0u;   // the floor-test stamp is an epoch too
-  }
-  return SG_OK;
-}
-
-static int handoff_prepare(sg_handle* h, hipStream_t st) {
-  {
-    // The work counter is never reset: every launch takes exactly its grid size in tickets, the kernels subtract
-    // the running base.
-    bool fresh = false;
-    int rc = ensure_zeroed(h, h->xticket, 64, st, &fresh);
-    if (rc) return rc;
-    if (fresh) h->ticket_base = 0;
-  }
-  if (!h->err_host) {
-    HIPCHK(h, hipHostMalloc((void**)&h->err_host, 64, hipHostMallocMapped));
-    *h->err_host = 0u;
-    h->err_host[1] = 0u;   // floor-test stamp (stage_onepass)
-    HIPCHK(h, hipHostGetDevicePointer((void**)&h->err_dev, h->err_host, 0));
-  }
-  if (*h->err_host != 0u) {
-    // only reached by callers that never synchronise through the library (sg_check_errors and every synchronising
-    // entry point report a lost hand-off for the call that suffered it)
-    const unsigned e = *h->err_host;
-    *h->err_host = 0u;
-    FAIL(h, SG_E_HANDOFF, "a tile hand-off of an EARLIER call on this handle timed out (code %u): that call's output "
-                          "is invalid (call sg_check_errors after a call to learn about it in time)", e);
-  }
-  h->lose_now = 0;
-  if (h->inject_fault) {  // test hook: this launch "loses" a hand-off
-    *h->err_host = h->inject_fault & 7u;          // bits 0..2: reported only (the output is fine)
-    h->lose_now = (h->inject_fault >> 3) & 7u;    // bits 3..5: lost INSIDE the kernel (the output is poisoned)
-    h->inject_fault = 0;
-  }
-  return handoff_next_epoch(h, st);
-}
-
-// After the stream has been synchronised: did a hand-off of the work just completed time out?
-static int handoff_verdict(sg_handle* h) {
-  if (h->err_host && *h->err_host != 0u) {
-    const unsigned e = *h->err_host;
-    *h->err_host = 0u;
-    FAIL(h, SG_E_HANDOFF, "a tile hand-off timed out (code %u: %s%s%s): the output of the call(s) enqueued since the "
-                          "last check is invalid; re-run them (SG_OPT_FORCE_SPLIT + SG_OPT_FORCE_NOLEAN select the "
-                          "kernels without in-launch hand-offs)",
-         e, (e & 1u) ? "mask bits " : "", (e & 2u) ? "partial hops (one-pass gate) " : "",
-         (e & 4u) ? "partial hops (fused apply)" : "");
-  }
-  return SG_OK;
-}
-
-extern "C" int sg_check_errors(sg_handle* h, void* stream) {
-  if (!h) return SG_E_INVALID;
-  HIPCHK(h, hipStreamSynchronize((hipStream_t)stream));
-  return handoff_verdict(h);
-}
-
 // Fused apply (default geometry): FFT -> mask(K) -> IFFT -> overlap-add -> output, one kernel.
 static int stage_apply_fast(sg_handle* h, const View& v, const Geom& g, int64_t ub, const OutMap& om,
                             const float* mask_f /* nullptr: uint16 counts in h->K16 */, int normalize,
@@ -2249,14 +2316,15 @@ static int stage_apply_fast(sg_handle* h, const View& v, const Geom& g, int64_t 
   A.tw512 = (const fast::cf*)h->tw512.p;
   A.tw1024 = (const fast::cf*)h->tw32.p;
   A.kscale = mask_f ? (float)(1.0 / 512.0) : (float)(1.0 / ((double)h->ktot * 512.0));
-  A.h_begin = (om.p0 + g.padL) / 256;
-  A.h_end = (om.p1 - 1 + g.padL) / 256 + 1;
-  const int64_t nh = A.h_end - A.h_begin;
+  const HopRange hr = hop_range(om, g, 256);
+  A.h_begin = hr.h_begin;
+  A.h_end = hr.h_end;
+  const int64_t nh = hr.count();
   if (nh <= 0) return SG_OK;
   constexpr int NF = 4 * WAVES, NH = NF - 3;
   size_t lds = (size_t)(fast::FN + WAVES * fast::WAVE_CX) * sizeof(fast::cf);
   // seam mode: abutting tiles + k_ola_seam for the straddling hops (3/16 fewer transforms)
-  const int64_t tiles_seam = (nh + 3 + NF - 1) / NF;
+  const int64_t tiles_seam = abutting_tiles(nh, NF);
   const bool seam = !h->force_noseam && tiles_seam >= 2;
   const bool lean = !h->force_nolean;
   // lean kernel: the straddling hops are handed from tile to tile inside the launch; else partial sums + k_ola_seam
@@ -2285,12 +2353,7 @@ static int stage_apply_fast(sg_handle* h, const View& v, const Geom& g, int64_t 
     A.n_tiles = (int)tiles_seam;
   }
   dim3 grid((unsigned)(seam ? tiles_seam : (nh + NH - 1) / NH), (unsigned)ub);
-  auto go = [&](auto kern, size_t lds_bytes) -> hipError_t {
-    hipError_t e = set_lds(reinterpret_cast<const void*>(kern), lds_bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, grid, dim3(WAVES * 64), lds_bytes, st, A);
-    return hipGetLastError();
-  };
+  auto go = [&](void (*kern)(fast::ApplyArgs), size_t lds_bytes) { return launch_lds(kern, grid, dim3(WAVES * 64), lds_bytes, st, A); };
   const size_t lds_lean = (size_t)(fast::FN + WAVES * fast::WAVE_CX_H) * sizeof(fast::cf) + 1024 * sizeof(float) + 16;
   const bool lose = inkernel && (h->lose_now & 4u);   // test hook: the instantiation whose hand-off polls give up at once
   if (mask_f) {
@@ -2302,7 +2365,6 @@ static int stage_apply_fast(sg_handle* h, const View& v, const Geom& g, int64_t 
     else if (lean) HIPCHK(h, go(fast::k_apply_fast<WAVES, true, true>, lds_lean));
     else HIPCHK(h, go(fast::k_apply_fast<WAVES, true, false>, lds));
   }
-  HIPCHK(h, hipGetLastError());
   if (seam && !inkernel) {
     hipLaunchKernelGGL(fast::k_ola_seam<NF>, dim3((unsigned)(tiles_seam - 1), (unsigned)ub), dim3(256), 0, st, A);
     HIPCHK(h, hipGetLastError());
@@ -2315,29 +2377,21 @@ static int stage_apply_fast(sg_handle* h, const View& v, const Geom& g, int64_t 
 // seam kernel for the 3 hops that straddle two tiles).  Returns 1 when the shape is not eligible
 // (the caller then runs the three-kernel path).
 static bool onepass_ok(const sg_handle* h, const Geom& g, const OutMap& om) {
+  const OnePassGeom& S = OP1024;
   if (h->force_split || h->force_f64_decide || h->force_noseam || h->force_nolean) return false;
-  if (!h->p.smooth_mask || h->p.n_grad_freq > 8 || h->p.n_grad_time > fast::OP_MAX_NT || !h->ftab3.p || !h->optab.p) return false;
-  if (g.F != 513) return false;
-  const int64_t hb = (om.p0 + g.padL) / 256, he = (om.p1 - 1 + g.padL) / 256 + 1;
-  return (he - hb + 3 + 15) / 16 >= 2;  // at least two abutting tiles (seam mode)
+  if (!h->p.smooth_mask || h->p.n_grad_freq > S.max_nf || h->p.n_grad_time > S.max_nt || !h->ftab3.p || !h->optab.p) return false;
+  if (g.F != S.F) return false;
+  return S.tiles(hop_range(om, g, S.hop).count()) >= 2;  // at least two abutting tiles (seam mode)
 }
 
 static int stage_onepass(sg_handle* h, const View& v, const View& vx, const Geom& g, int64_t ub, const OutMap& om,
                          hipStream_t st) {
-  constexpr int WAVES = 4, NF = 16;
-  int rc;
-  FloorSetup fs;
-  if ((rc = floor_setup(h, g, ub, OP_ALIM_BLOCKS, st, &fs))) return rc;
-  const bool lazy = fs.lazy;
-  const ThreshConsts& tc = fs.tc;
-  ++(lazy ? h->n_floor_lazy : h->n_floor_apriori);
-  if (!lazy && (rc = stage_prep_floor(h, v, g, ub, &fs.tc, st, &vx, h->err_dev + 1, h->epoch))) return rc;
-  fast::OnePassArgs P;
+  constexpr int WAVES = 4;
+  const OnePassGeom& S = OP1024;
+  fast::OnePassArgs P{};
   P.x_exact = vx.x; P.stride_exact = vx.stride; P.dtype_exact = vx.dtype;
-  fast::ApplyArgs& A = P.A;
-  A.view = v; A.g = g; A.om = om;
-  A.K = nullptr; A.Mf = nullptr;
-  A.normalize = 1;
+  fast::ApplyArgs& A = P.A;   // (K / Mf, part / part2, epoch, err, ticket stay null: the one-pass kernel has its own hand-off arguments)
+  A.view = v; A.g = g;
   A.win = (const float*)h->wa32.p;
   A.wsq = (const float*)h->wsq32.p;
   A.invn = (const float*)h->invn.p;
@@ -2345,154 +2399,63 @@ static int stage_onepass(sg_handle* h, const View& v, const View& vx, const Geom
   A.tw1024 = (const fast::cf*)h->tw32.p;
   const bool prop = h->p.prop_decrease != 1.0;
   A.kscale = prop ? (float)(1.0 / 512.0) : (float)(1.0 / ((double)h->ktot * 512.0));
-  A.h_begin = (om.p0 + g.padL) / 256;
-  A.h_end = (om.p1 - 1 + g.padL) / 256 + 1;
-  const int64_t nh = A.h_end - A.h_begin;
-  const int64_t n_tiles = (nh + 3 + NF - 1) / NF;
-  const int64_t ntt = n_tiles + 2;
-  if ((rc = ensure_zeroed(h, h->xpart, (size_t)ub * n_tiles * 3 * 256 * 8, st))) return rc;
-  A.part = nullptr;
-  A.part2 = nullptr;   // (the one-pass kernel has its own hand-off arguments)
-  A.epoch = 0;
-  A.err = nullptr;
-  A.n_tiles = (int)n_tiles;
-  if ((rc = ensure_zeroed(h, h->xbits, (size_t)ub * ntt * fast::OP_TILE_WORDS * 8, st))) return rc;
-  // granule buffers are zero when (re)allocated and the epoch only grows: a fresh granule never carries it
-  P.alim = lazy ? (unsigned*)h->alim.p : nullptr;
-  {
-    // the part of a unit's window outside its tiles' spans, dealt evenly to the unit's tiles (onepass.hpp "floor test")
-    constexpr int64_t SPAN = (NF - 1) * 256 + 1024;
-    const int64_t sp0 = (A.h_begin - 3 - NF) * 256 - g.padL, sp1 = (A.h_begin - 3 + n_tiles * NF) * 256 - g.padL + SPAN;
-    const int64_t inside = std::max<int64_t>(0, std::min<int64_t>(v.Lp, sp1) - std::max<int64_t>(0, sp0));
-    const int64_t q = (v.Lp - inside + ntt - 1) / ntt;
-    if (q > 0x7fffffff) FAIL(h, SG_E_UNSUPPORTED, "one-pass gate: window of %lld samples", (long long)v.Lp);
-    P.scan_q = (int)q;
-  }
   P.tab = (const char*)h->optab.p;
-  P.tc = tc;
   P.mag_scale = h->mag_scale; P.top_db = h->p.top_db;
-  P.xbits = (unsigned long long*)h->xbits.p;
-  P.part2 = (unsigned long long*)h->xpart.p;
-  P.ticket = (unsigned*)h->xticket.p;
-  P.epoch = h->epoch;
-  P.err = h->err_dev;
-  P.ticket_base = h->ticket_base;
-  // persistent workgroups (onepass.hpp "PERSIST"): the lazy first launch only -- its compare constants do not depend on the unit
-  const bool persist = lazy && h->tile_order == 0 && !(h->lose_now & 3u) && ub * ntt >= 2;
-  if (persist && h->n_cu == 0) {
-    int dev = 0, cus = 0;
-    HIPCHK(h, hipGetDevice(&dev));
-    HIPCHK(h, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    h->n_cu = cus > 0 ? cus : 256;
-  }
-  // three workgroups per CU (LDS) is what is resident at once; every workgroup ends on one ticket past the last tile
-  static const int pg_per_cu = [] { const char* e = getenv("SG_ONEPASS_WG_PER_CU"); int v = e ? atoi(e) : 3; return v >= 1 && v <= 3 ? v : 3; }();   // (experiments: fewer resident workgroups)
-#if OP_MAX_ITERS == 1
-  const unsigned pgrid = persist ? (unsigned)(ub * ntt) : 0u;   // (diagnosis) one workgroup per tile, each draws its one ticket
-#else
-  const unsigned pgrid = persist ? (unsigned)std::min<int64_t>(ub * ntt, (int64_t)pg_per_cu * h->n_cu) : 0u;
-#endif
-  P.total_tiles = (unsigned)(ub * ntt);
-  if (h->tile_order == 1) P.ticket_base = 0xffffffffu;   // SG_OPT_TILE_ORDER 1: tile = block index (no ticket)
-  else h->ticket_base += (unsigned)(ub * ntt) + (OP_MAX_ITERS == 1 ? 0u : pgrid);
-  P.nf = h->p.n_grad_freq; P.nt = h->p.n_grad_time;
-  P.prop = (float)h->p.prop_decrease;
   P.inv_ktot = 1.0f / (float)h->ktot;
+  bool persist = false;
+  auto first = [&](fast::OnePassArgs& Q, OnePassCall& C) -> int {
+    int rc;
+    if ((rc = ensure_zeroed(h, h->xpart, (size_t)ub * C.n_tiles * 3 * 256 * 8, st))) return rc;
+    Q.part2 = (unsigned long long*)h->xpart.p;
+    Q.A.n_tiles = (int)C.n_tiles;
+    Q.tc = C.fs.tc;
+    Q.alim = C.fs.lazy ? (unsigned*)h->alim.p : nullptr;
+    Q.total_tiles = C.total;
+    // persistent workgroups (onepass.hpp "PERSIST"): the lazy first launch only -- its compare constants do not depend on the unit
+    persist = C.fs.lazy && h->tile_order == 0 && !(h->lose_now & 3u) && C.total >= 2;
+    if (persist && h->n_cu == 0) {
+      int dev = 0, cus = 0;
+      HIPCHK(h, hipGetDevice(&dev));
+      HIPCHK(h, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+      h->n_cu = cus > 0 ? cus : 256;
+    }
+    // three workgroups per CU (LDS) is what is resident at once; every workgroup ends on one ticket past the last tile
+    static const int pg_per_cu = [] { const char* e = getenv("SG_ONEPASS_WG_PER_CU"); int v = e ? atoi(e) : 3; return v >= 1 && v <= 3 ? v : 3; }();   // (experiments: fewer resident workgroups)
+#if OP_MAX_ITERS == 1
+    (void)pg_per_cu;   // (diagnosis) one workgroup per tile, each draws its one ticket
+#else
+    if (persist) {
+      C.grid = (unsigned)std::min<int64_t>(C.total, (int64_t)pg_per_cu * h->n_cu);
+      C.tickets = C.total + C.grid;
+    }
+#endif
+    if (h->tile_order == 1) {   // SG_OPT_TILE_ORDER 1: tile = block index (no ticket)
+      Q.ticket_base = 0xffffffffu;
+      C.tickets = 0;
+    }
 #if OP_WHO
-  if (!g_who_dev) HIPCHK(h, hipMalloc((void**)&g_who_dev, 4096 * 16));
-  HIPCHK(h, hipMemsetAsync(g_who_dev, 0, 4096 * 16, st));
-  P.who = g_who_dev;
+    HIPCHK(h, op_who_attach(Q, st));
 #endif
 #if OP_TRACE
-  {
-    // development builds: one process-wide device trace [workgroup][wave][16], overwritten by every launch, averaged at exit
-    static unsigned* tr = nullptr;
-    static size_t tr_slots = 0;
-    const size_t slots = (size_t)ub * ntt * 4;
-    if (!tr || tr_slots < slots) {
-      HIPCHK(h, hipMalloc((void**)&tr, slots * 64));
-      tr_slots = slots;
-      static unsigned** trp = &tr;
-      static size_t* trn = &tr_slots;
-      static bool reg = false;
-      if (!reg) {
-        reg = true;
-        atexit([] {
-          std::vector<unsigned> hst(*trn * 16);
-          if (hipMemcpy(hst.data(), *trp, hst.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return;
-          double sum[14] = {0}, w = 0, mx = 0;
-          double wsum[4][14] = {{0}}, ww[4] = {0};   // the same per wave index (slot = ticket * 4 + wave)
-          for (size_t i = 0; i < *trn; ++i) {
-            if (hst[i * 16 + 15] != 1u) continue;
-            w += 1;
-            ww[i & 3] += 1;
-            double tot = 0;
-            for (int k = 0; k < 14; ++k) { sum[k] += hst[i * 16 + k]; wsum[i & 3][k] += hst[i * 16 + k]; tot += hst[i * 16 + k]; }
-            mx = std::max(mx, tot);
-          }
-          for (int wv = 0; wv < 4; ++wv) {   // (tools/trace_onepass.py --table reads these lines)
-            fprintf(stderr, "[OP_TRACE] wave %d (%.0f completed):", wv, ww[wv]);
-            for (int k = 0; k < 14; ++k) fprintf(stderr, " %d:%.0f", k, wsum[wv][k] / (ww[wv] > 0 ? ww[wv] : 1));
-            fprintf(stderr, "\n");
-          }
-          fprintf(stderr, "[OP_TRACE] completed waves %.0f; average shader cycles per wave and phase:", w);
-          double tot = 0;
-          for (int k = 0; k < 14; ++k) { fprintf(stderr, " %d:%.0f", k, sum[k] / (w > 0 ? w : 1)); tot += sum[k] / (w > 0 ? w : 1); }
-          fprintf(stderr, "  sum %.0f  longest wave %.0f\n", tot, mx);
-        });
-      }
-    }
-    HIPCHK(h, hipMemsetAsync(tr, 0, slots * 64, st));
-    P.trace = tr;
-    g_trace_dev = tr; g_trace_tiles = (size_t)ub * ntt; g_trace_ntt = (int)ntt;
-  }
+    HIPCHK(h, op_trace_attach(Q, C.total, (int)C.n_tiles + 2, st));
 #endif
-  {
-    ProfScope ps(h, SG_STAGE_ONEPASS, st);
-    const size_t lds = (size_t)(fast::FN + WAVES * fast::WAVE_CX_H) * sizeof(fast::cf) + (1024 + T2_FLOATS) * sizeof(float) +
-                       256 * 8 + 514 * 8 + 192 * 8 + 32 + (prop ? 528 : 0);
-    auto go = [&](auto kern) -> hipError_t {
-      hipError_t e = set_lds(reinterpret_cast<const void*>(kern), lds);
-      if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(kern, dim3(persist ? pgrid : (unsigned)(ub * ntt)), dim3(WAVES * 64), lds, st, P);
-      return hipGetLastError();
-    };
-    if (persist && prop) HIPCHK(h, go(fast::k_gate_onepass<WAVES, true, false, false, true>));
-    else if (persist) HIPCHK(h, go(fast::k_gate_onepass<WAVES, false, false, false, true>));
-    else if (h->lose_now & 3u) HIPCHK(h, go(fast::k_gate_onepass<WAVES, false, true>));   // test hook (PROP-free shape only)
-    else if (prop) HIPCHK(h, go(fast::k_gate_onepass<WAVES, true>));
-    else HIPCHK(h, go(fast::k_gate_onepass<WAVES, false>));
-  }
-  if (lazy) {
-    // the units whose floor test fired: float64 band maxima, then the gate again with them.  Both launches exit at once
-    // when no unit reported (the common case)
-    ProfScope ps(h, SG_STAGE_STFT_MAX, st);
-    const int wpr = (g.F + 63) / 64;
-    HIPCHK(h, launch_bits_any<0>(h, vx, g, ub, tc,
-                             (unsigned long long*)h->pmax.p, (unsigned long long*)h->bits.p, wpr, st));
-    if ((rc = handoff_next_epoch(h, st))) return rc;
-    P.epoch = h->epoch;
-    P.ticket = (unsigned*)h->xticket.p + 8;   // its own counter (zeroed by the first launch's ticket-0 workgroup): it takes tickets only if a unit reported
-    P.ticket_base = 0;
-    const size_t lds = (size_t)(fast::FN + WAVES * fast::WAVE_CX_H) * sizeof(fast::cf) + (1024 + T2_FLOATS) * sizeof(float) +
-                       256 * 8 + 514 * 8 + 192 * 8 + 32 + (prop ? 528 : 0);
-    auto redo = [&](auto kern) -> hipError_t {
-      hipError_t e = set_lds(reinterpret_cast<const void*>(kern), lds);
-      if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(kern, dim3((unsigned)(ub * ntt)), dim3(WAVES * 64), lds, st, P);
-      return hipGetLastError();
-    };
-    if (prop) HIPCHK(h, redo(fast::k_gate_onepass<WAVES, true, false, true>));
-    else HIPCHK(h, redo(fast::k_gate_onepass<WAVES, false, false, true>));
-    HIPCHK(h, hipGetLastError());
-  }
-  h->dbg_xbits = true;
-  h->dbg_trows = 16; h->dbg_tstep = 16; h->dbg_twords = fast::OP_TILE_WORDS; h->dbg_txw = fast::OP_XW;
-  h->dbg_tf0 = A.h_begin - 3;
-  h->dbg_ntt = (int)ntt;
-  h->dbg_db = std::max<int64_t>(0, A.h_begin - 3 - NF);
-  h->dbg_de = std::min<int64_t>(g.T, A.h_begin - 3 + NF * (n_tiles + 1));
-  return SG_OK;
+    return SG_OK;
+  };
+  const size_t lds = S.lds + (prop ? OP_PROP_LDS : 0);
+  auto launch = [&](const fast::OnePassArgs& Q, bool redo, dim3 grid) {
+    // <WAVES, PROP, LOSE, REDO, PERSIST>.  (The order of these lines is the order of the kernels in the code object.)
+    void (*kern)(fast::OnePassArgs);
+    if (!redo && persist) {
+      if (prop) kern = fast::k_gate_onepass<WAVES, true, false, false, true>;
+      else kern = fast::k_gate_onepass<WAVES, false, false, false, true>;
+    } else if (!redo && (h->lose_now & 3u)) kern = fast::k_gate_onepass<WAVES, false, true>;   // test hook (PROP-free shape only)
+    else if (!redo && prop) kern = fast::k_gate_onepass<WAVES, true>;
+    else if (!redo) kern = fast::k_gate_onepass<WAVES, false>;
+    else if (prop) kern = fast::k_gate_onepass<WAVES, true, false, true>;
+    else kern = fast::k_gate_onepass<WAVES, false, false, true>;
+    return launch_lds(kern, grid, dim3(WAVES * 64), lds, st, Q);
+  };
+  return onepass_run(h, v, vx, g, ub, om, st, S, OP_ALIM_BLOCKS, P, first, launch);
 }
 
 // float64 fused apply (apply64.hpp): K counts of stage_fused_mask -> output samples, everything in double
@@ -2500,11 +2463,7 @@ template <int WAVES, bool KMASK>
 static hipError_t launch_apply_fast64(fast::Apply64Args& A, int64_t nh, int64_t ub, hipStream_t st) {
   constexpr int NH = 4 * WAVES - 3;
   const size_t lds = (size_t)(fast::FN + WAVES * 4 * fast::FSLOTS_D + 17) * sizeof(fast::cd);
-  auto kern = fast::k_apply_fast64<WAVES, KMASK>;
-  hipError_t e = set_lds(reinterpret_cast<const void*>(kern), lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3((unsigned)((nh + NH - 1) / NH), (unsigned)ub), dim3(WAVES * 64), lds, st, A);
-  return hipGetLastError();
+  return launch_lds(fast::k_apply_fast64<WAVES, KMASK>, dim3((unsigned)((nh + NH - 1) / NH), (unsigned)ub), dim3(WAVES * 64), lds, st, A);
 }
 
 // mask_f64 == nullptr: the uint16 counts in h->K16 (stationary gate); else a float64 mask field [units][T][FS]
@@ -2522,9 +2481,10 @@ static int stage_apply_fast64(sg_handle* h, const View& v, const Geom& g, int64_
   A.prop = h->p.prop_decrease;
   A.nf = h->p.smooth_mask ? h->p.n_grad_freq : 0;
   A.nt = h->p.smooth_mask ? h->p.n_grad_time : 0;
-  A.h_begin = (om.p0 + g.padL) / 256;
-  A.h_end = (om.p1 - 1 + g.padL) / 256 + 1;
-  const int64_t nh = A.h_end - A.h_begin;
+  const HopRange hr = hop_range(om, g, 256);
+  A.h_begin = hr.h_begin;
+  A.h_end = hr.h_end;
+  const int64_t nh = hr.count();
   if (nh <= 0) return SG_OK;
   // tiles overlap by three frames: 8 wavefronts (32 frames -> 29 hops, 10 % of the transforms redone) unless the rows are
   // short; either way two wavefronts per SIMD (256 VGPRs) and one (8) or two (4) workgroups per CU
@@ -2561,8 +2521,8 @@ static int run_S_exact_fused(sg_handle* h, View v, int64_t total_units, const Ou
   for (int64_t u0 = 0; u0 < total_units; u0 += ub) {
     const int64_t nb = std::min(ub, total_units - u0);
     v.unit0 = u0;
-    const int64_t hb = (om.p0 + g.padL) / 256, he = (om.p1 - 1 + g.padL) / 256 + 1;
-    const int64_t tb = std::max<int64_t>(0, hb - 3), te = std::min<int64_t>(g.T, he);
+    const HopRange hr = hop_range(om, g, 256);
+    const int64_t tb = std::max<int64_t>(0, hr.h_begin - 3), te = std::min<int64_t>(g.T, hr.h_end);
     if ((rc = stage_fused_mask(h, v, g, nb, true, tb, std::max(te, tb + 1), st))) return rc;
     if ((rc = stage_apply_fast64(h, v, g, nb, om, st))) return rc;
     h->dbg_units = nb; h->dbg_T = g.T; h->dbg_has_P = false; h->dbg_fused = true; h->dbg_fast = true;
@@ -2816,8 +2776,8 @@ static int run_S(sg_handle* h, View v, int64_t total_units, const OutMap& om, hi
     }
     if (fast) {
       // frames the fused apply kernel touches: hops [h_begin, h_end) need frames h-3 .. h
-      const int64_t hb = (om.p0 + g.padL) / 256, he = (om.p1 - 1 + g.padL) / 256 + 1;
-      const int64_t tb = std::max<int64_t>(0, hb - 3), te = std::min<int64_t>(g.T, he);
+      const HopRange hr = hop_range(om, g, 256);
+      const int64_t tb = std::max<int64_t>(0, hr.h_begin - 3), te = std::min<int64_t>(g.T, hr.h_end);
       if ((rc = stage_fused_mask(h, v, g, nb, true, tb, std::max(te, tb + 1), st))) return rc;
       if ((rc = stage_apply_fast(h, v, g, nb, om, nullptr, 1, st))) return rc;
       h->dbg_units = nb; h->dbg_T = g.T; h->dbg_has_P = false; h->dbg_fused = true; h->dbg_fast = true;
