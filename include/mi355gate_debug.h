@@ -30,7 +30,22 @@ SG_API int sg_debug_range(const sg_handle* h, int64_t range[2]);
  * last gate call in which some chunk's floor test fired (0: never; synchronises).  which = 4 .. 16: development builds of the
  * persistent one-pass gate only (-DOP_TILECOUNT / -DOP_WHO / -DOP_TRACE libraries, tools/experiments/persist_*.py: words of the
  * host-mapped error block; 8: unfinished tiles of the phase trace; 16: the per-ticket draw / start record around ticket *value,
- * on stderr) -- they return 0 or SG_E_INVALID in the product library. */
+ * on stderr) -- they return 0 or SG_E_INVALID in the product library.  which = 17: the mask smoothing of the last
+ * variant-S gate call or sg_process_batch call on the handle, 0 when that call launched none or failed before it (host
+ * bookkeeping, no synchronisation; sg_process_rows / sg_process_clips / streams do not route on the widths and leave it alone): bits 0..7 the SG_SMOOTH_* kernel below, bits 8..15 the bytes of the cell it sums in (1 / 2: integer counts,
+ * 4 / 8: float / double), bits 16.. the output frames of one of its tiles (0: no tile). */
+#define SG_SMOOTH_OFF 1         /* no filter: k_prop_only / k_bits_to_k16 / kx_prop_only, or k_iir_mask<0> before a general smoothing launch */
+#define SG_SMOOTH_TILED 2       /* k_smooth_tiled: both float passes in one LDS tile */
+#define SG_SMOOTH_SEPARATE 3    /* k_smooth_f + k_smooth_t: two direct passes through global memory */
+#define SG_SMOOTH_BITS2 4       /* k_smooth_bits2<uint8_t / uint16_t>: integer sums over decision bits, tile of sm2_tt frames */
+#define SG_SMOOTH_BITS 5        /* k_smooth_bits (first generation, n_grad_freq > 30) */
+#define SG_SMOOTH_ONEPASS 6     /* k_gate_onepass (n_fft = 1024): MFMA smoothing inside the one-pass gate */
+#define SG_SMOOTH_ONEPASS_REG 7 /* k_gate_onepass512 / 256 / 2048 */
+#define SG_SMOOTH_ROW_GATE 8    /* k_row_gate (TorchGate rows of <= 64 frames) */
+#define SG_SMOOTH_IIR_MASK 9    /* k_iir_mask<nt>, nt >= 1: recurrence, sigmoid and both passes in one kernel */
+#define SG_SMOOTH_BOX_MASK 10   /* k_box_mask<nt> (TorchGate, non-stationary, n_movemean = 20) */
+#define SG_SMOOTH_X_TILED 11    /* kx_smooth_tiled (float64 pipeline) */
+#define SG_SMOOTH_X_SEPARATE 12 /* kx_smooth_f + kx_smooth_t (float64 pipeline) */
 SG_API int sg_debug_counter(sg_handle* h, int32_t which, int64_t* value, void* stream);
 SG_API int sg_debug_fetch(sg_handle* h, int32_t what, void* host, int64_t bytes, void* stream);
 

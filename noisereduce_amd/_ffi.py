@@ -41,6 +41,10 @@ SG_OPT_EXACT_MATERIALISED = 16
 SG_OPT_FORCE_UNFUSED = 1
 SG_OPT_FORCE_NOFAST = 2
 SG_BWD_ROW, SG_BWD_FAST, SG_BWD_REG, SG_BWD_OLA, SG_BWD_ROWS = 1, 2, 3, 4, 5
+# sg_debug_counter(17): the smoothing kernel of the last gate call (include/mi355gate_debug.h)
+SG_SMOOTH_NAMES = {0: "none", 1: "off", 2: "k_smooth_tiled", 3: "k_smooth_f+k_smooth_t", 4: "k_smooth_bits2", 5: "k_smooth_bits",
+                   6: "k_gate_onepass", 7: "k_gate_onepass_reg", 8: "k_row_gate", 9: "k_iir_mask<nt>", 10: "k_box_mask",
+                   11: "kx_smooth_tiled", 12: "kx_smooth_f+kx_smooth_t"}
 
 _TORCH_DTYPES = {torch.float32: SG_F32, torch.float64: SG_F64, torch.int16: SG_I16,
                  torch.int32: SG_I32}
@@ -816,6 +820,12 @@ class Gate:
         with torch.cuda.device(self.device):
             self._check(self.lib.sg_debug_counter(self._h, int(which), ctypes.byref(v), self._stream()))
         return int(v.value)
+
+    def smooth_route(self):
+        """The mask smoothing of the last gate call on this handle: ``(kernel name, bytes of the cell it sums in, output
+        frames per tile)`` -- sg_debug_counter(17), host bookkeeping only."""
+        v = self.debug_counter(17)
+        return SG_SMOOTH_NAMES[v & 0xff], (v >> 8) & 0xff, v >> 16
 
     def debug_field(self, what):
         """0: raw mask, 1: final mask (float32); 2: power (float64) of the last unit batch,

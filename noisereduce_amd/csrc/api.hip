@@ -194,6 +194,7 @@ struct sg_handle {
   bool force_split = false;          // SG_OPT_FORCE_SPLIT: decide / smooth / apply as three kernels
   int rowgate_mode = 0;              // SG_OPT_FORCE_NOROWGATE: 0 = by batch size, 1 = never, 2 = whenever the shape is eligible
   int64_t n_floor_lazy = 0, n_floor_apriori = 0;   // sg_debug_counter 1 / 2
+  int64_t smooth_route = 0;   // sg_debug_counter 17: SG_SMOOTH_* of the last smoothing launch | cell bytes << 8 | tile frames << 16
   int tile_order = 0;                // SG_OPT_TILE_ORDER: 0 (default, round 6) = persistent workgroups looping over tickets (onepass.hpp PERSIST), 2 = one ticket-drawn tile per workgroup (the kernel of rounds 2-5), 1 = tile = block index
                                      // block index (no ticket), 0 = persistent workgroups looping over tickets (round 6: 1 % faster alone on the
                                      // GPU, NOT the default -- next to TorchGate's row gate on a second stream it mis-gates a tile now and then:
@@ -332,6 +333,10 @@ static const OnePassGeom OP1024{
 
 // the handle's register geometry, or nullptr (another geometry, or SG_OPT_FORCE_NOFAST)
 static const RegGeom* reg_geom(const sg_handle* h) { return h->force_nofast ? nullptr : h->reg; }
+// host bookkeeping behind sg_debug_counter 17 (no kernel reads or writes it)
+static void note_smooth(sg_handle* h, int id, int cell_bytes, int tile_frames) {
+  h->smooth_route = (int64_t)id | ((int64_t)cell_bytes << 8) | ((int64_t)tile_frames << 16);
+}
 
 namespace {
 // Optional roctx ranges around every stage's enqueue (SG_ROCTX=1 in the environment at sg_create): the stages show
@@ -1898,7 +1903,9 @@ static int stage_onepass_reg(sg_handle* h, const RegGeom* r, const View& v, cons
     last = Q.A;
     return launch_lds(r->gate[redo], grid, dim3(256), S.lds, st, Q);
   };
-  if ((rc = onepass_run(h, v, vx, g, ub, om, st, S, (g.FS + 63) / 64, P, first, launch)) || !seam) return rc;
+  if ((rc = onepass_run(h, v, vx, g, ub, om, st, S, (g.FS + 63) / 64, P, first, launch))) return rc;
+  note_smooth(h, SG_SMOOTH_ONEPASS_REG, 1, S.NF);
+  if (!seam) return SG_OK;
   if (r->abut && P.A.n_tiles < 2) return SG_OK;   // (2048 books no seam stage for a single tile)
   ProfScope ps(h, SG_STAGE_APPLY_FAST, st);   // (after the second launch, if any: a redone unit rewrote its partials)
   return launch_seam(h, r, last, ub, st);
@@ -2026,6 +2033,7 @@ static int stage_nonstat_mask2(sg_handle* h, const View& v, const Geom& g, int64
                                 (const double*)h->nsc.p, g, tl, h->p.iir_b, h->p.nonstat_thresh, h->p.nonstat_slope, nf,
                                 to_raw ? 1.0f : (float)h->p.prop_decrease, to_raw ? (float*)h->raw.p : (float*)h->M.p));
     }
+    note_smooth(h, smooth ? SG_SMOOTH_IIR_MASK : SG_SMOOTH_OFF, 4, smooth ? NS_TT : 0);   // (k_iir_mask<0>: the general smoothing follows, if any)
   }
   return SG_OK;
 }
@@ -2050,6 +2058,7 @@ static int stage_box_mask(sg_handle* h, const View& v, const Geom& g, int64_t ub
     HIPCHK(h, launch_box_mask(nt, h->p.n_movemean, dim3(gx, (unsigned)std::min<int64_t>(65535, (int64_t)nk - k0), (unsigned)ub), st,
                               (const float*)h->P.p, g, h->p.nonstat_thresh, h->p.nonstat_slope, nf, (float)h->p.prop_decrease,
                               (float*)h->M.p, k0));
+  note_smooth(h, SG_SMOOTH_BOX_MASK, 4, NS_TT);
   return SG_OK;
 }
 
@@ -2084,6 +2093,7 @@ static int stage_smooth(sg_handle* h, const Geom& g, int64_t ub, hipStream_t st)
     hipLaunchKernelGGL(k_prop_only, dim3(grid_1d(cells, 256)), dim3(256), 0, st, (const float*)h->raw.p, g, p,
                        (float*)h->M.p, ub);
     HIPCHK(h, hipGetLastError());
+    note_smooth(h, SG_SMOOTH_OFF, 4, 0);
     return SG_OK;
   }
   // prop_decrease is applied before smoothing by stationary.py:108-114 and torchgate.py:241-249,
@@ -2104,6 +2114,7 @@ static int stage_smooth(sg_handle* h, const Geom& g, int64_t ub, hipStream_t st)
       hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, (const float*)h->raw.p, g, (const float*)h->kf.p, nf,
                          (const float*)h->kt.p, nt, p, prop_before0, (float*)h->M.p);
       HIPCHK(h, hipGetLastError());
+      note_smooth(h, SG_SMOOTH_TILED, 4, SMF_TT);
       return SG_OK;
     }
   }
@@ -2118,6 +2129,7 @@ static int stage_smooth(sg_handle* h, const Geom& g, int64_t ub, hipStream_t st)
                      (const float*)h->kt.p, h->p.n_grad_time, (const float*)h->kf.p, h->p.n_grad_freq, p,
                      prop_before, (float*)h->M.p, ub);
   HIPCHK(h, hipGetLastError());
+  note_smooth(h, SG_SMOOTH_SEPARATE, 4, 0);
   return SG_OK;
 }
 
@@ -2159,6 +2171,7 @@ static int stage_smooth_bits(sg_handle* h, const Geom& g, int64_t ub, bool fast,
                            (const unsigned long long*)h->bits.p, g, wpr, nf, nt, (unsigned short*)h->K16.p, fast ? 1 : 0, tb, te, ftab, tt);
     };
     HIPCHK(h, small ? go(uint8_t{}) : go(uint16_t{}));
+    note_smooth(h, SG_SMOOTH_BITS2, small ? 1 : 2, tt);
   } else if (h->p.smooth_mask) {
     const int rows = SM_TT + 2 * nt;
     const bool small = (nf + 1) * (nf + 1) <= 255;
@@ -2169,10 +2182,12 @@ static int stage_smooth_bits(sg_handle* h, const Geom& g, int64_t ub, bool fast,
                            (const unsigned long long*)h->bits.p, g, wpr, nf, nt, (unsigned short*)h->K16.p, fast ? 1 : 0);
     };
     HIPCHK(h, small ? go(uint8_t{}) : go(uint16_t{}));
+    note_smooth(h, SG_SMOOTH_BITS, small ? 1 : 2, SM_TT);
   } else {
     hipLaunchKernelGGL(k_bits_to_k16, dim3(grid_1d(cells, 256)), dim3(256), 0, st,
                        (const unsigned long long*)h->bits.p, g, wpr, (unsigned short*)h->K16.p, ub, fast ? 1 : 0);
     HIPCHK(h, hipGetLastError());
+    note_smooth(h, SG_SMOOTH_OFF, 2, 0);
   }
   return SG_OK;
 }
@@ -2455,7 +2470,9 @@ static int stage_onepass(sg_handle* h, const View& v, const View& vx, const Geom
     else kern = fast::k_gate_onepass<WAVES, false, false, true>;
     return launch_lds(kern, grid, dim3(WAVES * 64), lds, st, Q);
   };
-  return onepass_run(h, v, vx, g, ub, om, st, S, OP_ALIM_BLOCKS, P, first, launch);
+  const int rc = onepass_run(h, v, vx, g, ub, om, st, S, OP_ALIM_BLOCKS, P, first, launch);
+  if (!rc) note_smooth(h, SG_SMOOTH_ONEPASS, 1, S.NF);
+  return rc;
 }
 
 // float64 fused apply (apply64.hpp): K counts of stage_fused_mask -> output samples, everything in double
@@ -2668,10 +2685,12 @@ static int run_S_exact(sg_handle* h, View v, int64_t total_units, const OutMap& 
           hipLaunchKernelGGL(exact::kx_prop_only<float>, gr, dim3(256), 0, st, (const float*)h->xraw.p, g, p, (double*)h->xM.p, nb);
         else
           hipLaunchKernelGGL(exact::kx_prop_only<double>, gr, dim3(256), 0, st, (const double*)h->xraw.p, g, p, (double*)h->xM.p, nb);
+        note_smooth(h, SG_SMOOTH_OFF, 8, 0);
       } else if (!h->exact_materialised && exact::xsm_lds_bytes(nf, nt) <= 150 * 1024 && 2 * nf < exact::XSM_KMAX && 2 * nt < exact::XSM_KMAX && nb <= 65535 &&
                  (g.T + exact::XSM_TT - 1) / exact::XSM_TT <= 65535) {
         // (round 5) both passes in one LDS-tiled kernel, taps computed once per block
         const size_t lds = exact::xsm_lds_bytes(nf, nt);
+        note_smooth(h, SG_SMOOTH_X_TILED, 8, exact::XSM_TT);
         const dim3 gt((unsigned)((g.F + exact::XSM_FB - 1) / exact::XSM_FB), (unsigned)((g.T + exact::XSM_TT - 1) / exact::XSM_TT), (unsigned)nb);
         if (h->p.stationary) {
           auto kern = exact::kx_smooth_tiled<float>;
@@ -2688,6 +2707,7 @@ static int run_S_exact(sg_handle* h, View v, int64_t total_units, const OutMap& 
         else
           hipLaunchKernelGGL(exact::kx_smooth_f<double>, gr, dim3(256), 0, st, (const double*)h->xraw.p, g, nf, (double*)h->xtmp.p, nb);
         HIPCHK(h, hipGetLastError());
+        note_smooth(h, SG_SMOOTH_X_SEPARATE, 8, 0);
         hipLaunchKernelGGL(exact::kx_smooth_t, gr, dim3(256), 0, st, (const double*)h->xtmp.p, g, nt, nf, p, prop_before,
                            (double*)h->xM.p, nb);
       }
@@ -2718,6 +2738,7 @@ static int run_S_exact(sg_handle* h, View v, int64_t total_units, const OutMap& 
 
 // Variant S over a set of units described by `v` (unit0 filled per batch).
 static int run_S(sg_handle* h, View v, int64_t total_units, const OutMap& om, hipStream_t st) {
+  h->smooth_route = 0;   // (sg_debug_counter 17 speaks of THIS call: a path that notes nothing reports "none", not the call before)
   Geom g = make_geom(h, v.Lp);
   if (v.Lp < h->W) FAIL(h, SG_E_INVALID, "signal window of %lld samples is shorter than win_length=%d",
                         (long long)v.Lp, h->W);
@@ -2909,6 +2930,7 @@ static int stage_row_gate(sg_handle* h, const View& v, const Geom& g, int64_t nb
     hipLaunchKernelGGL((fast::k_row_gate<16, 1>), dim3((unsigned)nb), dim3(1024), lds, st, A);
   }
   HIPCHK(h, hipGetLastError());
+  note_smooth(h, SG_SMOOTH_ROW_GATE, 1, fast::RG_FRAMES);
   return SG_OK;
 }
 
@@ -3104,6 +3126,7 @@ extern "C" int sg_process_batch(sg_handle* h, const void* x_dev, int dtype, int6
   }
   hipStream_t st = (hipStream_t)stream;
   h->dbg_rg = false;
+  h->smooth_route = 0;   // (as in run_S)
   View v{};
   v.x = x_dev; v.dtype = dtype; v.stride = x_stride; v.N = L; v.lo = 0; v.hi = L; v.cs = 0; v.pad = 0; v.Lp = L; v.n_chunks = 1;
   Geom g = make_geom(h, L);
@@ -3461,6 +3484,10 @@ extern "C" int sg_debug_counter(sg_handle* h, int32_t which, int64_t* value, voi
   if (!h || !value) return SG_E_INVALID;
   if (which == 1 || which == 2) {   // host counters: one-pass gate calls with the in-kernel (1) / a-priori (2) floor test
     *value = which == 1 ? h->n_floor_lazy : h->n_floor_apriori;
+    return SG_OK;
+  }
+  if (which == 17) {   // SG_SMOOTH_* of the last smoothing launch | cell bytes << 8 | tile frames << 16 (host bookkeeping)
+    *value = h->smooth_route;
     return SG_OK;
   }
   if (which == 3) {   // launch epoch of the last gate call in which a chunk's floor test fired / flag was set (0: never)

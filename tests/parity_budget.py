@@ -22,8 +22,10 @@ helpers here hold a kernel to the float64 oracle per stage and per hop block ins
                        a few lifted bands per unit and one band +g / -g dB from its switch, and noise clips that reach
                        every branch of the single-pass statistics;
 * ``R_CELLS`` / ``r_case`` / ``r_oracle`` / ``r_budget``   the routes of TorchGate.forward without lengths= (rows per unit batch,
-                       frames per row, noise rows, unit batches) on rows that all differ from each other, at the end of the
-                       module.
+                       frames per row, noise rows, unit batches) on rows that all differ from each other;
+* ``W_CELLS`` / ``TW_CELLS`` / ``M_CELLS`` / ``w_route`` / ``tw_route``   mask smoothing half-widths and moving-mean lengths on
+                       both sides of every edge the engine routes on, with the routing predicates restated, at the end of
+                       the module.
 
 Where the numbers come from (none is taken from the code under test):
 
@@ -106,6 +108,53 @@ class signals:
             y[2 * chunk_size - (3 * padding) // 4:2 * chunk_size - padding // 4] *= g
         return y.astype(F32)
 
+    @staticmethod
+    def dappled(n, n_fft, blocks, sigma, seed):
+        """Three kinds of block for the width matrix (``W_CELLS``); ``blocks``: (start, stop, kind) sample ranges.
+
+        ``loud``    every decision is 1, in every band and frame that lies inside the block, by construction and not by
+                    chance: one sinusoid on every bin centre k = 0 .. n_fft / 2 (DC and Nyquist included), equal
+                    amplitudes, phases pi k^2 / 4, rms 0.25.  Under a Hann window of n_fft samples bin k holds
+                    c_k - (c_{k-1} + c_{k+1}) / 2; a hop of n_fft / 4 turns neighbouring bins by pi / 2 against each other,
+                    and with these phases the neighbours always stand at an odd multiple of pi / 4 to c_k: no frame's bin
+                    falls more than 10.7 dB under the single tone.  DC and Nyquist carry twice the amplitude: a real bin
+                    holds c_0 - Re(c_1 e^(i theta)), which vanishes at some frame offsets theta with equal amplitudes.
+                    Over every frame offset and bin the windowed tone sum then stays within 3.0 dB of one tone alone
+                    (8.3 dB at the odd size 601; summed numerically), 30 dB over the noise clip's mean at ``sigma`` = -40 dB.
+        ``steady``  (non-stationary cells) tones on every fourth bin only, so that no two leak into the same bin and every
+                    |X| is the same in every frame inside the block, over noise at ``sigma``: the sigmoid saturates at
+                    the block's onset and decays with the recurrence, instead of hovering mid-slope on the 4-frame
+                    pattern of ``loud`` (where the float32 emulation's error, times the slope, is no fair yardstick).
+        ``sparse``  white noise 1 dB over the noise clip's own level ``sigma``: the threshold (mean + 1.5 std of the
+                    clip's dB) lies 5.85 dB over the clip's mean power for a complex Gaussian bin, which a bin at the clip's
+                    level passes with probability exp(-3.85) = 2.1 % -- on the edge of the density the host test wants; at
+                    + 1 dB it is exp(-3.05) = 4.7 %.
+        ``quiet``   white noise 20 dB under the clip: no decision is 1.
+        Samples outside every block are zero."""
+        rng = np.random.default_rng(seed)
+        F = n_fft // 2 + 1
+        k = np.arange(F, dtype=np.float64)
+        spec = (n_fft / 2.0) * np.exp(1j * np.pi * k * k / 4.0)
+        spec[0] = 4.0 * spec[0].real            # (a real bin holds the whole amplitude, a complex one half of it; x 2)
+        if n_fft % 2 == 0:
+            spec[-1] = 4.0 * spec[-1].real
+        period = np.fft.irfft(spec, n=n_fft)
+        period *= 0.25 / np.sqrt(np.mean(period ** 2))
+        steady = np.fft.irfft(np.where(np.arange(F) % 4 == 0, spec, 0.0), n=n_fft)
+        steady *= 0.25 / np.sqrt(np.mean(steady ** 2))
+        y = np.zeros(n)
+        for a, b, kind in blocks:
+            a, b = max(0, a), min(n, b)
+            if b <= a:
+                continue
+            if kind == "loud":
+                y[a:b] = period[np.arange(a, b) % n_fft]
+            elif kind == "steady":
+                y[a:b] = steady[np.arange(a, b) % n_fft] + sigma * rng.standard_normal(b - a)
+            else:
+                y[a:b] = sigma * {"sparse": 10.0 ** (1.0 / 20.0), "quiet": 0.1}[kind] * rng.standard_normal(b - a)
+        return y.astype(F32)
+
 
 # ----------------------------------------------------------------------------------------------------------------
 # the oracle, unit by unit
@@ -114,6 +163,8 @@ def _final_mask(raw, cfg):
     """raw bits / raw sigmoid -> final mask in float64 with the smoothing summed directly (O.conv2_same_direct)."""
     raw = np.asarray(raw, dtype=np.float64)
     conv = (lambda m: O.conv2_same_direct(m, cfg["filt"])) if cfg["filt"] is not None else (lambda m: m)
+    if cfg["filt"] is not None and cfg.get("separable"):
+        conv = lambda m: conv2_same_separable(m, cfg["nf"], cfg["nt"])   # noqa: E731
     if cfg["variant"] == "T":
         return conv(cfg["prop"] * (raw - 1.0) + 1.0)
     if cfg["stationary"]:
@@ -121,10 +172,36 @@ def _final_mask(raw, cfg):
     return conv(raw) * cfg["prop"] + (1.0 - cfg["prop"])
 
 
+def conv2_same_separable(m, nf, nt, drop_f=False, drop_t=False, replicate=False):
+    """``O.conv2_same_direct(m, O.smoothing_filter(nf, nt))`` summed axis by axis in float64 with the filter's INTEGER
+    taps [1 .. n + 1 .. 1] and one division by (nf + 1)^2 (nt + 1)^2 at the end (a field of 0 / 1 decisions is summed
+    exactly): 2 nf + 2 nt + 2 passes over the field instead of (2 nf + 1)(2 nt + 1).  tests/test_smoothing_widths_host.py
+    holds it against the direct sum.  The three switches plant defects: the taps at |df| = nf / |dt| = nt left out (the
+    divisor stays), frames beyond the field replicated from frame 0 / T - 1 instead of zero."""
+    m = np.asarray(m, dtype=np.float64)
+    F, T = m.shape
+    P = np.zeros((F + 2 * nf, T))
+    P[nf:nf + F] = m
+    a = np.zeros((F, T))
+    for d in range(-nf, nf + 1):
+        if not (drop_f and abs(d) == nf):
+            a += (nf + 1 - abs(d)) * P[nf + d:nf + d + F]
+    P = np.zeros((F, T + 2 * nt))
+    P[:, nt:nt + T] = a
+    if replicate:
+        P[:, :nt] = a[:, :1]
+        P[:, nt + T:] = a[:, -1:]
+    out = np.zeros((F, T))
+    for d in range(-nt, nt + 1):
+        if not (drop_t and abs(d) == nt):
+            out += (nt + 1 - abs(d)) * P[:, nt + d:nt + d + T]
+    return out / float((nf + 1) ** 2 * (nt + 1) ** 2)
+
+
 def oracle_units(y, sr, stationary=False, y_noise=None, prop_decrease=1.0, time_constant_s=2.0,
                  freq_mask_smooth_hz=500, time_mask_smooth_ms=50, thresh_n_mult_nonstationary=2,
                  sigmoid_slope_nonstationary=10, n_std_thresh_stationary=1.5, chunk_size=600000, padding=30000,
-                 n_fft=1024, win_length=None, hop_length=None, clip_noise_stationary=True):
+                 n_fft=1024, win_length=None, hop_length=None, clip_noise_stationary=True, separable=False):
     """``O.reduce_noise_S`` with its stages kept.  Returns ``(out, units)``: ``out`` the float64 (C, N) / (N,) result
     (not cast to the input's dtype), ``units`` one dict per (channel, chunk) in the engine's unit order (channel-major):
 
@@ -140,7 +217,8 @@ def oracle_units(y, sr, stationary=False, y_noise=None, prop_decrease=1.0, time_
     nf, nt, smooth = O.mask_smoothing_widths(sr, n_fft, H, freq_mask_smooth_hz, time_mask_smooth_ms)
     filt = O.smoothing_filter(nf, nt) if smooth else None
     cfg = dict(variant="S", stationary=bool(stationary), n_fft=n_fft, W=W, H=H, prop=float(prop_decrease), nf=nf, nt=nt,
-               filt=filt, iir_b=None, thresh_n_mult=thresh_n_mult_nonstationary, slope=sigmoid_slope_nonstationary)
+               filt=filt, iir_b=None, thresh_n_mult=thresh_n_mult_nonstationary, slope=sigmoid_slope_nonstationary,
+               separable=bool(separable))      # (the final mask summed axis by axis: conv2_same_separable)
     thresh = None
     if stationary:
         yn2 = y2 if y_noise is None else np.atleast_2d(np.asarray(y_noise, dtype=np.float64))
@@ -183,7 +261,7 @@ def oracle_units(y, sr, stationary=False, y_noise=None, prop_decrease=1.0, time_
     return (out[0] if flat else out), units
 
 
-def torchgate_units(x, sr, xn=None, window=None, **kw):
+def torchgate_units(x, sr, xn=None, window=None, separable=False, **kw):
     """``O.torchgate_T(return_stages=True)`` as one unit per batch row (same keys as ``oracle_units``; ``keep`` is the
     whole output row).  ``window``: the (W,) table the engine was given (TorchGate: float32 Hann)."""
     x = np.asarray(x, dtype=np.float64)
@@ -195,7 +273,7 @@ def torchgate_units(x, sr, xn=None, window=None, **kw):
     cfg = dict(variant="T", stationary=not nonstat, n_fft=n_fft, W=W, H=H, prop=float(kw.get("prop_decrease", 1.0)),
                nf=nf, nt=nt, filt=O.smoothing_filter(nf, nt) if smooth else None, window=window,
                n_movemean=kw.get("n_movemean_nonstationary", 20), n_thresh=kw.get("n_thresh_nonstationary", 1.3),
-               temp=kw.get("temp_coeff_nonstationary", 0.1))
+               temp=kw.get("temp_coeff_nonstationary", 0.1), separable=bool(separable))
     units = []
     y = np.array(y)
     for b in range(x.shape[0]):
@@ -2051,3 +2129,492 @@ def torchgate_gate_kwargs(tg, **extra):
               nonstat_slope=1.0 / tg.temp_coeff_nonstationary, window=torch.hann_window(tg.win_length).double().numpy())
     kw.update(extra)
     return kw
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# the width matrix: mask smoothing half-widths (n_grad_freq, n_grad_time) on both sides of every edge the engine routes
+# on, shared by tests/test_smoothing_widths_host.py (conditions on the oracle, the routing restated) and
+# tests/test_gpu_smoothing_widths.py
+# ----------------------------------------------------------------------------------------------------------------
+# A cell: gate ("S": stationary, "NS": non-stationary, both variant S), n_fft (window = n_fft, hop = n_fft / 4 --
+# resolve_stft_params), the half-widths, the routes it runs, and
+#   none=True          a half-width of 1 is spelled None (the reference's other spelling of it), else 1.02 bins / frames
+#   small=True         a single unpadded unit of 34 frames: the field is smaller than the filter on both axes
+#   tc=...             time_constant_s (non-stationary)
+#   precision="float64"
+# Shapes: a unit holds 2 nt + 70 frames -- two edge tiles and an interior 64-frame tile of every smoothing kernel, whose
+# tiles are at most 64 frames wherever the filter is wide -- in two chunks with under one hop of padding, so that the
+# first and the last frame of a unit reach kept samples; one channel.
+W_LDS_CAP = 150 * 1024                 # the dynamic LDS every smoothing launch may ask for (api.hip)
+_W_REG = ("default", "force_split", "force_nofast")
+_W_CORNER = _W_REG + ("force_unfused",)
+
+
+def _w(gate, n_fft, nf, nt, routes=("default",), **kw):
+    name = "%s-%d-f%d-t%d" % (gate, n_fft, nf, nt) + "".join("-%s" % k if v is True else "-%s%s" % (k, v)
+                                                            for k, v in sorted(kw.items()) if k != "precision")
+    if kw.get("precision") == "float64":
+        name += "-f64"
+    if routes == ("force_unfused",):
+        name += "-unfused"
+    return dict(name=name, gate=gate, n_fft=n_fft, nf=nf, nt=nt, routes=tuple(routes), **kw)
+
+
+# ---- byte counts, from the constants of the headers ----
+def sm2_pitch(F):
+    """fused.hpp smooth2_pitch: LDS row pitch of k_smooth_bits2's phase-1 counts."""
+    return ((F + 3) & ~3) + 4 * ((F + 31) // 32) + 4
+
+
+def sm2_tile(F, nf, nt, tt_max=None):
+    """api.hip fit_sm2_tile: the tile height (frames) k_smooth_bits2 settles on, or None when no tile of >= 16 frames fits:
+    (tt + 2 nt + 2) rows of counts (1 byte while (nf + 1)^2 <= 255, else 2) + (tt + 2 nt) bit rows of ceil(F / 64) + 2
+    words + the 8 KiB lookup table <= 150 KiB; tt from smooth2_tt_max(F) = 256 / 128 / 64 (F <= 160 / <= 320 / above) down
+    by halves."""
+    ct = 1 if (nf + 1) ** 2 <= 255 else 2
+    wpr = (F + 63) // 64
+    tt = (256 if F <= 160 else 128 if F <= 320 else 64) if tt_max is None else tt_max
+    while tt >= 16:
+        rows = tt + 2 * nt
+        cf = ((rows + 2) * sm2_pitch(F) * ct + 15) & ~15
+        if cf + rows * (wpr + 2) * 8 + 8192 <= W_LDS_CAP:
+            return tt
+        tt >>= 1
+    return None
+
+
+def smf_lds_bytes(nf, nt):
+    """api.hip stage_smooth: k_smooth_tiled's tile, SMF_TT = SMF_FB = 64, SMF_KT = 192."""
+    rows, cols = 64 + 2 * nt, 64 + 2 * nf
+    return ((rows + 3) * (cols | 1) + (rows + 3) * 65 + 8 + 64 + 192 + 64 + 64) * 4
+
+
+def smooth_tiled_ok(nf, nt):
+    return smf_lds_bytes(nf, nt) <= W_LDS_CAP and nf <= 30 and 2 * nt + 4 <= 192 and 64 + 2 * nf <= 192
+
+
+def xsm_lds_bytes(nf, nt):
+    """exact.hpp xsm_lds_bytes: kx_smooth_tiled's tile, XSM_TT = 32, XSM_FB = 64, XSM_KMAX = 192."""
+    rows, cols = 32 + 2 * nt + 3, 64 + 2 * nf + 3
+    return (rows * (cols | 1) + rows * 65 + 2 * 192 + 64 + 32) * 8
+
+
+def x_tiled_ok(nf, nt):
+    return xsm_lds_bytes(nf, nt) <= W_LDS_CAP and 2 * nf < 192 and 2 * nt < 192
+
+
+def _last_nt(ok):
+    """The largest nt >= 1 with ok(nt) (ok is monotone)."""
+    nt = 1
+    while ok(nt + 1):
+        nt += 1
+    return nt
+
+
+def _mixed_radix(n_fft):
+    m = n_fft // 2
+    for p in (2, 3, 5, 7, 11, 13):
+        while m % p == 0:
+            m //= p
+    return n_fft % 2 == 0 and n_fft >= 8 and m == 1
+
+
+# one-pass gates: (max nf, max nt, frames per tile) -- api.hip OP1024 / REG512 / REG256 / REG2048 (abutting tiles)
+W_ONEPASS = {1024: (8, 16, 16), 512: (8, 24, 32), 256: (8, 40, 64), 2048: (24, 8, 8)}
+NS_IIR_NT = tuple(range(1, 21)) + (25, 34, 37)          # nonstat_mask.hpp: instantiated k_iir_mask<nt>
+NS_MAX_NF = 24
+
+
+def w_geometry(c):
+    return O.resolve_stft_params(c["n_fft"], None, None)
+
+
+def w_smooth(c):
+    """Whether the reference smooths at all: (1, 1) switches the filter off (base.py:111)."""
+    return not (c["nf"] == 1 and c["nt"] == 1)
+
+
+def w_iir_b(c):
+    n_fft, W, H = w_geometry(c)
+    return float(O.iir_coefficient(c.get("tc", 2.0), SR, H))
+
+
+def w_route(c, route):
+    """The routing predicates of csrc/api.hip restated: ``(smoothing kernel, bytes of its cell, frames per tile)`` as
+    ``Gate.smooth_route()`` reports it after the cell ran ``route``."""
+    n_fft, W, H = w_geometry(c)
+    F = n_fft // 2 + 1
+    nf, nt, smooth = c["nf"], c["nt"], w_smooth(c)
+    general = ("off", 4, 0) if not smooth else ("k_smooth_tiled", 4, 64) if smooth_tiled_ok(nf, nt) else \
+        ("k_smooth_f+k_smooth_t", 4, 0)
+    if c.get("precision") == "float64":
+        # the n_fft = 1024 stationary gate keeps the bit-mask stages and applies in float64 (exact_fused_ok); everything
+        # else is run_S_exact
+        if not (c["gate"] == "S" and n_fft == 1024 and w_fused_ok(c)):
+            return ("off", 8, 0) if not smooth else ("kx_smooth_tiled", 8, 32) if x_tiled_ok(nf, nt) else \
+                ("kx_smooth_f+kx_smooth_t", 8, 0)
+        return ("k_smooth_bits2", 1 if (nf + 1) ** 2 <= 255 else 2, sm2_tile(F, nf, nt)) if smooth else ("off", 2, 0)
+    if c["gate"] == "NS":
+        b = w_iir_b(c)
+        chain = route != "force_unfused" and 0.0 < b < 1.0 and (1.0 - b) ** (64 + 2 * 20) >= 1e-3
+        one = chain and smooth and (nt <= 20 or (1.0 - b) ** (64 + 2 * nt) >= 1e-3) and nf <= NS_MAX_NF and nt in NS_IIR_NT
+        return ("k_iir_mask<nt>", 4, 64) if one else general
+    if route == "force_unfused" or not w_fused_ok(c):
+        return general
+    if route == "default" and smooth and n_fft in W_ONEPASS:
+        mf, mt, frames = W_ONEPASS[n_fft]
+        if nf <= mf and nt <= mt:
+            return ("k_gate_onepass" if n_fft == 1024 else "k_gate_onepass_reg", 1, frames)
+    if not smooth:
+        return ("off", 2, 0)
+    return ("k_smooth_bits2", 1 if (nf + 1) ** 2 <= 255 else 2, sm2_tile(F, nf, nt))
+
+
+def w_fused_ok(c):
+    """api.hip fused_ok: the bit-mask path of the stationary gate -- integer sums in uint16, a power of two or a
+    mixed-radix size up to 4096, nt <= 96, nf <= 30, and a tile of k_smooth_bits2 that fits."""
+    n_fft, W, H = w_geometry(c)
+    nf, nt, smooth = c["nf"], c["nt"], w_smooth(c)
+    ktot = (nf + 1) ** 2 * (nt + 1) ** 2 if smooth else 1
+    pow2 = n_fft & (n_fft - 1) == 0
+    if not (ktot <= 65535 and (pow2 or _mixed_radix(n_fft)) and n_fft <= 4096):
+        return False
+    return not smooth or (nt <= 96 and nf <= 30 and sm2_tile(n_fft // 2 + 1, nf, nt) is not None)
+
+
+def _w_cells():
+    S, NS = "S", "NS"
+    cells = []
+    # ---- stationary, register geometries ----
+    cells += [_w(S, 1024, 1, 1, _W_CORNER, none=True),                 # no smoothing at all
+              _w(S, 1024, 1, 1, _W_REG),                               # ... spelled as numbers
+              _w(S, 1024, 1, 2, _W_REG, none=True), _w(S, 1024, 2, 1, _W_REG),
+              _w(S, 1024, 8, 8, _W_REG), _w(S, 1024, 8, 9, _W_REG),   # 2 nt > 16: the third row block (onepass.hpp)
+              _w(S, 1024, 8, 16, _W_CORNER), _w(S, 1024, 8, 17, _W_REG), _w(S, 1024, 9, 16, _W_REG)]
+    cells += [_w(S, 512, 8, 24, _W_CORNER), _w(S, 512, 8, 25, _W_REG), _w(S, 512, 9, 24, _W_REG),
+              # the operand table holds the time weights wt(32 b + row - nt - j) of k-block b = 0, 1 for the 16 output
+              # frames j of a product: 16 + 2 nt = 32 rows fill block 0 exactly at nt = 8, nt = 9 is the first to have
+              # non-zero weights in block 1 (and nt = 24 the last whose 64 rows fit both)
+              _w(S, 512, 3, 8, _W_REG), _w(S, 512, 3, 9, _W_REG)]
+    cells += [_w(S, 256, 8, 24, _W_REG), _w(S, 256, 8, 25, _W_REG),   # 2 nt > 48: the third k-block (onepass256.hpp)
+              _w(S, 256, 8, 27, _W_REG), _w(S, 256, 8, 28, _W_REG),   # ktot 63504 | 68121
+              _w(S, 256, 5, 40, _W_CORNER), _w(S, 256, 5, 41, _W_REG),   # ktot 60516 | 63504, past the gate's 40
+              _w(S, 256, 6, 40, _W_REG)]                                 # ktot 82369
+    cells += [_w(S, 2048, 8, 8, _W_REG), _w(S, 2048, 16, 8, _W_REG), _w(S, 2048, 24, 8, _W_CORNER),
+              _w(S, 2048, 25, 8, _W_REG), _w(S, 2048, 24, 9, _W_REG)]
+    # ---- stationary, general bit-mask path ----
+    for n_fft in (128, 400, 4096):
+        cells += [_w(S, n_fft, 5, 2), _w(S, n_fft, 6, 2),             # the 18-bit lookup table: 8 + 2 nf <= 18
+                  _w(S, n_fft, 14, 3), _w(S, n_fft, 15, 3),           # (nf + 1)^2 <= 255: uint8 | uint16 cells
+                  _w(S, n_fft, 30, 6), _w(S, n_fft, 31, 6),           # nf <= 30
+                  _w(S, n_fft, 14, 16), _w(S, n_fft, 15, 15),         # ktot 65025 | 65536
+                  _w(S, n_fft, 1, 96, none=True), _w(S, n_fft, 1, 97)]
+    # n_fft = 4096 (F = 2049, tiles from 64 frames down): the last nt of every tile height sm2_tile settles on at nf = 2,
+    # and the first nt no tile fits
+    seen = set()
+    for nt in range(1, 97):
+        tt = sm2_tile(2049, 2, nt)
+        if tt not in seen and tt is not None:
+            seen.add(tt)
+            cells.append(_w(S, 4096, 2, _last_nt(lambda t, tt=tt: sm2_tile(2049, 2, t) == tt or
+                                                 (sm2_tile(2049, 2, t) or 0) > tt)))
+    cells.append(_w(S, 4096, 2, _last_nt(lambda t: sm2_tile(2049, 2, t) is not None) + 1))
+    cells.append(_w(S, 64, 30, 30, small=True))
+    # ---- materialised float kernels: the chirp-z size 601, and SG_OPT_FORCE_UNFUSED at 1024 ----
+    nt30 = _last_nt(lambda t: smooth_tiled_ok(30, t))       # smf_lds_bytes(30, nt) <= 150 KiB
+    for n_fft, routes in ((601, ("default",)), (1024, ("force_unfused",))):
+        cells += [_w(S, n_fft, 30, nt30, routes), _w(S, n_fft, 30, nt30 + 1, routes),
+                  _w(S, n_fft, 2, 94, routes), _w(S, n_fft, 2, 95, routes),       # 2 nt + 4 <= SMF_KT = 192
+                  _w(S, n_fft, 31, 4, routes)]
+    # ---- non-stationary ----
+    for n_fft in (1024, 400):
+        cells += [_w(NS, n_fft, 2, nt) for nt in (20, 21, 24, 25, 26, 34, 37, 38)]
+        cells += [_w(NS, n_fft, 24, 9), _w(NS, n_fft, 25, 9),
+                  # c = 1 - b at a time constant of 18 frames is 0.946: c^(64 + 40) = 3.1e-3 keeps the tile-parallel
+                  # recurrence, c^(64 + 74) = 4.7e-4 < 1e-3 refuses k_iir_mask<37>
+                  _w(NS, n_fft, 2, 37, tc=18.0 * (n_fft // 4) / SR)]
+    # ---- precision="float64": the float64 pipeline's own smoothing kernels (n_fft = 512: run_S_exact) ----
+    # (2 nt < XSM_KMAX = 192 never decides: xsm_lds_bytes passes 150 KiB first at every nf -- nf = 3: from nt = 53 on.
+    # (3, 95) | (3, 96) therefore both run the two separate passes; the edge that exists at nf = 3 is the byte count's)
+    xnt30 = _last_nt(lambda t: x_tiled_ok(30, t))           # xsm_lds_bytes(30, nt) <= 150 KiB
+    xnt3 = _last_nt(lambda t: x_tiled_ok(3, t))
+    for gate in (S, NS):
+        cells += [_w(gate, 512, 3, 95, precision="float64"), _w(gate, 512, 3, 96, precision="float64"),
+                  _w(gate, 512, 3, xnt3, precision="float64"), _w(gate, 512, 3, xnt3 + 1, precision="float64"),
+                  _w(gate, 512, 30, xnt30, precision="float64"), _w(gate, 512, 30, xnt30 + 1, precision="float64"),
+                  _w(gate, 64, 30, 30, small=True, precision="float64")]
+    names = [c["name"] for c in cells]
+    assert len(set(names)) == len(names), sorted(n for n in names if names.count(n) > 1)
+    return cells
+
+
+W_CELLS = _w_cells()
+W_SIGMA = 0.25 * 10.0 ** (-40.0 / 20.0)        # the noise clip: 40 dB under the loud block (signals.dappled)
+# name -> seed offset: a seed that lands a stationary decision within 1e-6 dB of its threshold, leaves the sparse block
+# outside [0.02, 0.3] ones, or a non-stationary unit without cells below 0.1 / above 0.9 is changed
+# (tests/test_smoothing_widths_host.py holds the conditions)
+_W_RESEED = {}
+
+
+def w_cell_id(c):
+    return c["name"]
+
+
+def w_cell(name):
+    return next(c for c in W_CELLS if c["name"] == name)
+
+
+def w_blocks(c):
+    """``(N, chunk_size, padding, blocks)``: the recording of a width cell.  Two chunks; the loud block straddles the seam
+    (the last frames of unit 0 and the first of unit 1 lie inside it, and each unit sees 2 nt + 2 hops of it plus the
+    padding: a full filter footprint of ones), a sparse block of 48 hops on either side, quiet ends.  ``small``: loud,
+    sparse, quiet, loud in 9 + 10 + 6 + 8 hops of one unpadded unit.  Non-stationary cells: every chunk starts quiet (the
+    recurrence starts from its first frame: a unit that starts loud keeps its floor at that level and its sigmoid at 0
+    throughout) and holds a steady block of 2 nt + 4 hops between two sparse ones; the recording ends in three hops of
+    ``steady``, so that the last unit's last frame holds a sigmoid near 1 (its floor is the slow forward pass's last value)
+    and zero padding beyond the field differs from replication there.  No input does that at a unit's FIRST frame: the
+    forward pass starts at A[0] and the backward pass adds b sum (1 - b)^k fwd[k] with fwd[k] >= (1 - b)^k A[0], so
+    S[0] >= A[0] / (2 - b), (A - S) / S <= 1 - b and the sigmoid stays under sigmoid(-10) = 4.5e-5 -- replication of
+    frame 0 IS zero padding to that order."""
+    n_fft, W, H = w_geometry(c)
+    nt = c["nt"]
+    # (small: 34 frames, not 20 -- with fewer than nt + 1 frames the taps at |dt| = nt only ever meet the zero padding, and
+    # an implementation without them is not wrong on such a field; 34 frames and 33 bins are still under the 61 taps)
+    if c.get("small") and c["gate"] == "NS":
+        N = 33 * H + 5
+        return N, N + 9, 0, [(0, 6 * H, "quiet"), (6 * H, 14 * H, "sparse"), (14 * H, 24 * H, "steady"), (24 * H, N, "sparse"),
+                             (N - 3 * H, N, "steady")]
+    if c.get("small"):
+        N = 33 * H + 5
+        return N, N + 9, 0, [(0, 9 * H, "loud"), (9 * H, 19 * H, "sparse"), (19 * H, 25 * H, "quiet"), (25 * H, N, "loud")]
+    cs = (2 * nt + 68) * H + 5
+    pad = H // 2 + 3
+    N = 2 * cs - 7
+    if c["gate"] == "NS":
+        blocks = []
+        for s0 in (0, cs):
+            a, b = s0 + 12 * H, s0 + 36 * H
+            blocks += [(s0, a, "quiet"), (a, b, "sparse"), (b, b + (2 * nt + 4) * H, "steady"),
+                       (b + (2 * nt + 4) * H, min(N, s0 + cs), "sparse")]
+        blocks.append((N - 3 * H, N, "steady"))       # (an onset in the last frames of the last unit: below)
+        return N, cs, pad, blocks
+    half = (2 * nt + 2) * H + W
+    q = 12 * H
+    return N, cs, pad, [(0, q, "quiet"), (q, cs - half, "sparse"), (cs - half, cs + half, "loud"),
+                        (cs + half, N - q, "sparse"), (N - q, N, "quiet")]
+
+
+def w_block_frames(c, unit, kind):
+    """Frames of ``unit`` whose whole window lies inside a block of ``kind``: a boolean (T,) array."""
+    n_fft, W, H = w_geometry(c)
+    N, cs, pad, blocks = w_blocks(c)
+    T = unit["raw"].shape[1]
+    in_unit = -(W // 2) + H * np.arange(T)                     # first sample of frame t in the unit; the unit's ends are
+    whole = (in_unit >= 0) & (in_unit + W <= len(unit["x"]))   # zero-extended by W / 2: those frames are in no block
+    start = unit["dst"][0] - unit["keep"][0] + in_unit         # ... and in the recording
+    inside = np.zeros(T, dtype=bool)
+    for a, b, k in blocks:
+        if k == kind:
+            inside |= whole & (start >= a) & (start + W <= b)
+    return inside
+
+
+@functools.lru_cache(maxsize=None)
+def _w_case(name):
+    c = w_cell(name)
+    n_fft, W, H = w_geometry(c)
+    nf, nt = c["nf"], c["nt"]
+    N, cs, pad, blocks = w_blocks(c)
+    seed = 31000 + 7 * n_fft % 1009 + 101 * nf + nt + _W_RESEED.get(name, 0)
+    spell = lambda m, unit: None if (m == 1 and c.get("none")) else (m + 0.02) * unit   # noqa: E731
+    stationary = c["gate"] == "S"
+    kw = dict(stationary=stationary, n_fft=n_fft, chunk_size=cs, padding=pad, prop_decrease=1.0,
+              freq_mask_smooth_hz=spell(nf, SR / (n_fft / 2)), time_mask_smooth_ms=spell(nt, 1000.0 * H / SR))
+    if "tc" in c:
+        kw["time_constant_s"] = c["tc"]
+    y = signals.dappled(N, n_fft, blocks, W_SIGMA, seed)
+    y_noise = None
+    if stationary:
+        y_noise = (W_SIGMA * np.random.default_rng(seed + 5).standard_normal(max(64 * H, 2 * W))).astype(F32)
+    f64 = c.get("precision") == "float64"
+    return dict(cell=c, y=y, y_noise=y_noise, kw=kw, dtype="float64" if f64 else "float32", precision=c.get("precision"))
+
+
+def w_case(c):
+    """Input and keyword arguments of a width cell, laid out like ``cell_case``'s."""
+    return _w_case(c["name"])
+
+
+@functools.lru_cache(maxsize=4)
+def _w_oracle(name):
+    case = _w_case(name)
+    out, units = oracle_units(case["y"].astype(np.float64), SR, separable=True,
+                              y_noise=None if case["y_noise"] is None else case["y_noise"].astype(np.float64), **case["kw"])
+    c = case["cell"]
+    for u in units:
+        assert (u["cfg"]["nf"], u["cfg"]["nt"], u["cfg"]["filt"] is not None) == (c["nf"], c["nt"], w_smooth(c)), name
+    return out, units
+
+
+def w_oracle(c):
+    return _w_oracle(c["name"])
+
+
+# ---- TorchGate.forward (n_fft = 1024, float32) at the widths sg_process_batch routes on ----
+# rowgate=True: SG_OPT_FORCE_NOROWGATE = 2 (the row gate whenever the shape is eligible), rows of 64 frames, thresholds
+# from the rows themselves (the row gate takes no noise row).  Own statistics bound the loud block: with a share p of loud
+# frames D dB over the rest, mean + 1.5 std of the row's dB lies D (1.5 sqrt(p (1 - p)) - (1 - p)) over the loud level,
+# which is negative only for p < 0.31 -- and D is at most the 40 dB of TorchGate's floor.  A footprint of 2 nt + 1 WHOLE
+# loud frames costs more than that many frames of the statistics: a frame is four hops long, so three more frames on each
+# open side are partly loud (at the row's start the two reflected frames instead).  nt = 16 / 17: 33 / 35 frames, out of
+# the question; nt = 7 / 8 (the nf = 30 pair): 15 / 17 whole + 5 .. 6 partial = 20 .. 23 of 64 frames, p = 0.31 .. 0.36 --
+# the threshold lies AT or over the loud level, whatever the rest of the row holds.  So no row-gate cell sums its full
+# ktot anywhere (a sum next to the uint16 edge is made in full by k_smooth_bits2 instead: 65025 at (14, 16), variant S); a
+# 64-frame row holds 13 loud-touched frames here, p = 0.2, where the threshold is only 8 dB under the loud level, less than ``loud``'s bins move from frame to
+# frame: the row-gate rows take ``steady`` blocks (every fourth bin, the same level in every frame).  Every other stationary cell takes its thresholds from a noise row at W_SIGMA
+# and holds rows of 2 nt + 70 frames with the full footprint of ones.
+def _tw(gate, nf, nt, **kw):
+    name = "%s-f%d-t%d" % (gate, nf, nt) + "".join("-%s" % k for k, v in sorted(kw.items()) if v is True)
+    return dict(name=name, gate=gate, n_fft=1024, nf=nf, nt=nt, T=64 if kw.get("rowgate") else 2 * nt + 70, **kw)
+
+
+_TW_NT64 = _last_nt(lambda t: sm2_tile(513, 2, t, tt_max=64) == 64)
+_TW_NT32 = _last_nt(lambda t: sm2_tile(513, 2, t, tt_max=64) >= 32)
+TW_CELLS = [
+    _tw("T", 14, 16, rowgate=True), _tw("T", 14, 17, rowgate=True),      # ktot 65025 | 72900 (and nt <= 16)
+    _tw("T", 13, 17, rowgate=True),                                      # ktot 63504: nt <= RG_NTMAX = 16 alone
+    _tw("T", 30, 7, rowgate=True), _tw("T", 30, 8, rowgate=True),        # ktot 61504 | 77841
+    _tw("T", 2, 81), _tw("T", 2, 82),                 # the tile search from 64 frames (the launch failed here once)
+    _tw("T", 2, _TW_NT64), _tw("T", 2, _TW_NT64 + 1),  # ... whose 64-frame tile is left here (sm2_tile: 74 | 75)
+    _tw("T", 1, _TW_NT32), _tw("T", 1, _TW_NT32 + 1),  # ... and whose 32-frame tile here (90 | 91; nf = 1: ktot <= 65535)
+    _tw("T", 1, 96, none=True), _tw("T", 1, 97),
+    _tw("T", 30, 6), _tw("T", 31, 6),
+    _tw("TNS", 2, 12), _tw("TNS", 2, 13),             # k_box_mask<nt> is instantiated for nt = 0 .. 12
+    _tw("TNS", 2, 19), _tw("TNS", 2, 20), _tw("TNS", 2, 21),
+    _tw("TNS", 24, 9), _tw("TNS", 25, 9),
+]
+
+
+def tw_cell_id(c):
+    return c["name"]
+
+
+def tw_route(c):
+    """sg_process_batch's routing on the widths (csrc/api.hip), as ``Gate.smooth_route()`` reports it."""
+    nf, nt, smooth = c["nf"], c["nt"], w_smooth(c)
+    ktot = (nf + 1) ** 2 * (nt + 1) ** 2 if smooth else 1
+    general = ("off", 4, 0) if not smooth else ("k_smooth_tiled", 4, 64) if smooth_tiled_ok(nf, nt) else \
+        ("k_smooth_f+k_smooth_t", 4, 0)
+    if c["gate"] == "TNS":
+        box = c.get("kbox", 20) == 20 and (not smooth or (nf <= NS_MAX_NF and 1 <= nt <= 12))
+        return ("k_box_mask", 4, 64) if box else general
+    if c.get("rowgate") and smooth and ktot <= 65535 and c["T"] <= 64 and 1 <= nf <= 30 and 1 <= nt <= 16:
+        return ("k_row_gate", 1, 64)
+    if not smooth:
+        return ("off", 2, 0)
+    if not (nt <= 96 and ktot <= 65535):
+        return general
+    ct = 1 if (nf + 1) ** 2 <= 255 else 2
+    if nf > 30:
+        # the tile search is only made for nf <= 30 (t_sm2_ok keeps its default), and stage_smooth_bits hands nf > 30 to
+        # the first-generation k_smooth_bits: 64-frame tiles, (64 + 2 nt) rows of F counts -- (nf + 1)^2 >= 1024, so
+        # ktot <= 65535 leaves (nt + 1)^2 <= 63, nt <= 6: 76 rows, 82 KiB at most.  This is the only way into that kernel (variant S leaves the bit-mask path at nf > 30).
+        return ("k_smooth_bits", ct, 64)
+    tt = sm2_tile(513, nf, nt, tt_max=64)
+    return ("k_smooth_bits2", ct, tt) if tt else general
+
+
+def _tw_rows(c, B, seed):
+    H, W, T = 256, 1024, c["T"]
+    L = (T - 1) * H + 7
+    if c["gate"] == "TNS":
+        # (two hops of steady at either end: the moving mean over 20 frames, zero beyond the row, leaves the first and the
+        # last frame a sigmoid near 1, so that zero padding of the smoothing differs from replication at both ends)
+        blocks = [(0, 2 * H, "steady"), (2 * H, 10 * H, "quiet"), (10 * H, 30 * H, "sparse"), (30 * H, (34 + 2 * c["nt"]) * H, "steady"),
+                  ((34 + 2 * c["nt"]) * H, L - 2 * H, "sparse"), (L - 2 * H, L, "steady")]
+    elif c.get("rowgate"):
+        blocks = [(0, 10 * H, "steady"), (10 * H, 40 * H, "sparse"), (40 * H, L - 2 * H, "quiet"), (L - 2 * H, L, "steady")]
+    else:
+        a = (2 * c["nt"] + 2) * H + W // 2
+        blocks = [(0, a, "loud"), (a, a + 44 * H, "sparse"), (a + 44 * H, L - 6 * H, "quiet"), (L - 6 * H, L, "loud")]
+    return np.stack([signals.dappled(L, 1024, blocks, W_SIGMA, seed + 13 * b) for b in range(B)]), blocks
+
+
+@functools.lru_cache(maxsize=None)
+def _tw_case(name):
+    c = next(c for c in TW_CELLS if c["name"] == name)
+    H = 256
+    seed = 47000 + 101 * c["nf"] + c["nt"] + _W_RESEED.get(name, 0)
+    x, blocks = _tw_rows(c, 3 if c.get("rowgate") else 2, seed)
+    spell = lambda m, unit: None if (m == 1 and c.get("none")) else (m + 0.02) * unit   # noqa: E731
+    kw = dict(n_fft=1024, nonstationary=c["gate"] == "TNS", freq_mask_smooth_hz=spell(c["nf"], SR / 512.0),
+              time_mask_smooth_ms=spell(c["nt"], 1000.0 * H / SR))
+    xn = None
+    if c["gate"] == "T" and not c.get("rowgate"):
+        xn = (W_SIGMA * np.random.default_rng(seed + 5).standard_normal((1, 64 * H))).astype(F32)
+    return dict(cell=c, x=x, xn=xn, kw=kw, blocks=blocks)
+
+
+def tw_case(c):
+    return _tw_case(c["name"])
+
+
+@functools.lru_cache(maxsize=4)
+def _tw_oracle(name):
+    case = _tw_case(name)
+    xn = None if case["xn"] is None else case["xn"].astype(np.float64)
+    return torchgate_units(case["x"].astype(np.float64), SR, xn=xn, window=tile_window(1024), separable=True, **case["kw"])[1]
+
+
+def tw_oracle(c):
+    return _tw_oracle(c["name"])
+
+
+# ---- the moving mean of TorchGate's non-stationary gate (n_movemean_nonstationary), n_fft = 1024 ----
+# forward: k_boxcar_sigmoid (32-frame blocks; k_box_mask only knows the default 20) on rows of M_T frames; lengths=: the
+# moving mean of csrc/rows.hip (left = (kbox - 1) / 2).  padding="same" puts (k - 1) // 2 zeros on the left and k / 2 on the
+# right: asymmetric for even k.
+M_T = 40
+M_CELLS = [dict(name="mm%d" % k, kbox=k, lengths=False) for k in (1, 2, 3, 19, 21, 32, 33, M_T - 1, M_T, M_T + 5, 2 * M_T + 1)] + \
+          [dict(name="mm%d-lengths" % k, kbox=k, lengths=True) for k in (1, 2, 21, 30)]      # (the shortest row: 24 frames)
+M_LENGTHS = (M_T, 24, 33)       # frames per row of the lengths= cells
+
+
+def m_cell_id(c):
+    return c["name"]
+
+
+@functools.lru_cache(maxsize=None)
+def _m_case(name):
+    c = next(c for c in M_CELLS if c["name"] == name)
+    H = 256
+    frames = M_LENGTHS if c["lengths"] else (M_T, M_T)
+    L = (M_T - 1) * H + 7
+    x = np.full((len(frames), L), np.nan, dtype=F32) if c["lengths"] else np.zeros((len(frames), L), dtype=F32)
+    lens = []
+    for b, T in enumerate(frames):
+        n = (T - 1) * H + 7
+        blocks = [(0, 5 * H, "quiet"), (5 * H, 14 * H, "sparse"), (14 * H, 22 * H, "steady"), (22 * H, n, "sparse")]
+        x[b, :n] = signals.dappled(n, 1024, blocks, W_SIGMA, 53000 + 17 * c["kbox"] + b)
+        lens.append(n)
+    kw = dict(n_fft=1024, nonstationary=True, n_movemean_nonstationary=c["kbox"],
+              freq_mask_smooth_hz=2.02 * SR / 512.0, time_mask_smooth_ms=2.02 * 1000.0 * H / SR)
+    return dict(cell=c, x=x, lengths=np.array(lens, dtype=np.int64) if c["lengths"] else None, kw=kw)
+
+
+def m_case(c):
+    return _m_case(c["name"])
+
+
+@functools.lru_cache(maxsize=4)
+def _m_oracle(name):
+    case = _m_case(name)
+    window = tile_window(1024)
+    if case["lengths"] is None:
+        return torchgate_units(case["x"].astype(np.float64), SR, window=window, **case["kw"])[1]
+    return [torchgate_units(case["x"][b:b + 1, :int(n)].astype(np.float64), SR, window=window, **case["kw"])[1][0]
+            for b, n in enumerate(case["lengths"])]
+
+
+def m_oracle(c):
+    return _m_oracle(c["name"])
