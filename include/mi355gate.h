@@ -399,6 +399,25 @@ SG_API int sg_process_batch_backward(sg_handle* h, const void* grad_out_dev, int
                               int64_t L, int64_t go_stride, const float* mask_dev,
                               void* grad_x_dev, int64_t gx_stride, void* stream);
 
+/* The gated spectrogram, TorchGate.gated_stft: what the reference multiplies on the line before its torch.istft
+ * (torchgate.py:252).  x (B, L) -> spec [B][T][F] complex (interleaved re, im) of sample type dtype (SG_F32 -> 2 x float,
+ * SG_F64 -> 2 x double), T = sg_n_frames(L), F = n_fft/2 + 1, bins contiguous, no padding -- the storage of torch.stft's
+ * result; = rfft(window * frame) * mask, unscaled (torch.stft, center=True, pad_mode="constant").  The mask is the one
+ * sg_process_batch computes for the same input (same statistics, decisions and smoothing); xn / Bn / Ln as there.
+ * mask_out_dev: NULL or float[B][T][FS], the final mask, natural bin order (the buffer sg_gate_spectrum_backward takes).
+ * Power-of-two n_fft from 256 to 4096 (SG_E_UNSUPPORTED otherwise); float32 transforms for both sample types.  Rows are
+ * processed in sub-batches under the handle's max_workspace_bytes, with the same bits as unsplit.  Enqueues only. */
+SG_API int sg_gate_spectrum(sg_handle* h, const void* x_dev, int dtype, int64_t B, int64_t L, int64_t x_stride,
+                            const void* xn_dev, int64_t Bn, int64_t Ln, int64_t xn_stride,
+                            void* spec_dev, float* mask_out_dev, void* stream);
+
+/* Adjoint of sg_gate_spectrum with the mask held fixed: grad_spec [B][T][F] complex of dtype (dL/dRe + i dL/dIm) ->
+ * grad_x (B, L) of dtype = frames^T( window * Re sum_{k=0}^{n_fft/2} mask[k] grad[k] e^{+2 pi i k j / n_fft} ): every bin
+ * with weight 1, the imaginary parts of bins 0 and n_fft/2 unused, un-normalised overlap-add cropped to [0, L) -- the
+ * adjoint of an STFT, no envelope division.  No atomics: the same bits on every run.  Enqueues only. */
+SG_API int sg_gate_spectrum_backward(sg_handle* h, const void* grad_spec_dev, int dtype, int64_t B, int64_t L,
+                                     const float* mask_dev, void* grad_x_dev, int64_t gx_stride, void* stream);
+
 /* sg_process_batch for a PADDED batch: row i of x (B, L) holds lengths[i] samples of audio, 2 * win_length <= lengths[i] <= L,
  * and padding after them (host array of B entries; NULL: every row is full).  With T_i = 1 + lengths[i] / hop and
  * Lout_i = hop * (lengths[i] / hop): out[i][0 .. Lout_i) is what sg_process_batch returns for the row alone at length

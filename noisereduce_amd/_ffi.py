@@ -138,6 +138,10 @@ _PROTOTYPES = {
                                  c_void_p]),
     "sg_process_batch_backward": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64,
                                           c_void_p, c_void_p, c_int64, c_void_p]),
+    "sg_gate_spectrum": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64,
+                                 c_int64, c_void_p, c_void_p, c_void_p]),
+    "sg_gate_spectrum_backward": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_int64,
+                                          c_void_p]),
     "sg_process_rows": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64,
                                 c_int64, c_int64, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p]),
     "sg_process_rows_backward": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p,
@@ -478,6 +482,55 @@ class Gate:
                 self._h, grad_out.data_ptr(), _sg_dtype(grad_out), B, L, gs, mask.data_ptr(),
                 gx.data_ptr(), L, self._stream()))
         return gx
+
+    # -- variant T: the gated spectrogram (sg_gate_spectrum) ---------------------------------------
+    def gate_spectrum(self, x, xn=None, save_mask=False, out=None, mask_out=None):
+        """TorchGate.gated_stft: x (B, L) float32 / float64 -> (B, T, F, 2) real pairs of x.dtype, torch.stft's storage
+        (``torch.view_as_complex(Y).transpose(1, 2)`` is the (B, F, T) spectrogram).  With save_mask=True also the final
+        mask (B, T, FS) float32, natural bin order.  out / mask_out: contiguous tensors of those shapes to write into."""
+        self._on_device(x)
+        x, xs = _rows(x)
+        B, L = x.shape
+        T = self.n_frames(L)
+        if out is None:
+            out = torch.empty((B, T, self.n_bins, 2), dtype=x.dtype, device=self.device)
+        elif out.shape != (B, T, self.n_bins, 2) or out.dtype != x.dtype or not out.is_contiguous():
+            raise ValueError("out must be a contiguous (B, T, F, 2) tensor of x.dtype")
+        mask = None
+        if save_mask or mask_out is not None:
+            FS = (self.n_bins + 15) // 16 * 16
+            mask = mask_out if mask_out is not None else torch.empty((B, T, FS), dtype=torch.float32, device=self.device)
+            if mask.shape != (B, T, FS) or mask.dtype != torch.float32 or not mask.is_contiguous():
+                raise ValueError("mask_out must be a contiguous (B, T, FS) float32 tensor")
+        if xn is not None:
+            self._on_device(xn)
+            if xn.dtype != x.dtype:
+                xn = xn.to(x.dtype)
+            xn, xns = _rows(xn)
+            xn_ptr, Bn, Ln = xn.data_ptr(), xn.shape[0], xn.shape[1]
+        else:
+            xn_ptr, Bn, Ln, xns = None, 0, 0, 0
+        with torch.cuda.device(self.device):
+            self._check(self.lib.sg_gate_spectrum(
+                self._h, x.data_ptr(), _sg_dtype(x), B, L, xs, xn_ptr, Bn, Ln, xns, out.data_ptr(),
+                None if mask is None else mask.data_ptr(), self._stream()))
+        return (out, mask) if mask is not None else out
+
+    def gate_spectrum_backward(self, grad, mask, L, out=None):
+        """Adjoint of gate_spectrum with the mask fixed: grad (B, T, F, 2) real pairs -> (B, L) of grad.dtype.
+        out: a (B, L) tensor (rows may be strided) to write into."""
+        self._on_device(grad)
+        grad = grad.contiguous()
+        B = grad.shape[0]
+        if out is None:
+            out = torch.empty((B, L), dtype=grad.dtype, device=self.device)
+        elif out.shape != (B, L) or out.dtype != grad.dtype or (L > 1 and out.stride(1) != 1):
+            raise ValueError("out must be a (B, L) tensor of grad.dtype with contiguous rows")
+        with torch.cuda.device(self.device):
+            self._check(self.lib.sg_gate_spectrum_backward(
+                self._h, grad.data_ptr(), _sg_dtype(grad), B, L, mask.data_ptr(), out.data_ptr(),
+                out.stride(0) if B > 1 else L, self._stream()))
+        return out
 
     # -- variant T: padded batches of different-length rows (sg_process_rows) ------------------------
     @staticmethod

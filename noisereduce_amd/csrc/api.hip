@@ -42,6 +42,7 @@
 #include "ragged.hpp"
 #include "rows.hpp"
 #include "stream.hpp"
+#include "spec.hpp"
 
 // complex transform length from which a whole 256-thread workgroup (instead of one wavefront) works on ONE frame in
 // the general LDS kernels: at N = 2048 (n_fft = 4096) a wavefront holds 4 radix-8 butterflies = 64 complex values per
@@ -2085,13 +2086,15 @@ static int stage_nonstat_raw(sg_handle* h, const View& v, const Geom& g, int64_t
   return SG_OK;
 }
 
-static int stage_smooth(sg_handle* h, const Geom& g, int64_t ub, hipStream_t st) {
+// M_out: where the mask goes (nullptr: the workspace field h->M)
+static int stage_smooth(sg_handle* h, const Geom& g, int64_t ub, hipStream_t st, float* M_out = nullptr) {
+  float* const Mdst = M_out ? M_out : (float*)h->M.p;
   ProfScope ps(h, SG_STAGE_SMOOTH, st);
   int64_t cells = ub * g.T * g.FS;
   float p = (float)h->p.prop_decrease;
   if (!h->p.smooth_mask) {
     hipLaunchKernelGGL(k_prop_only, dim3(grid_1d(cells, 256)), dim3(256), 0, st, (const float*)h->raw.p, g, p,
-                       (float*)h->M.p, ub);
+                       Mdst, ub);
     HIPCHK(h, hipGetLastError());
     note_smooth(h, SG_SMOOTH_OFF, 4, 0);
     return SG_OK;
@@ -2112,7 +2115,7 @@ static int stage_smooth(sg_handle* h, const Geom& g, int64_t ub, hipStream_t st)
         HIPCHK(h, set_lds(reinterpret_cast<const void*>(kern), lds));
       dim3 grid((g.F + SMF_FB - 1) / SMF_FB, (unsigned)((g.T + SMF_TT - 1) / SMF_TT), (unsigned)ub);
       hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, (const float*)h->raw.p, g, (const float*)h->kf.p, nf,
-                         (const float*)h->kt.p, nt, p, prop_before0, (float*)h->M.p);
+                         (const float*)h->kt.p, nt, p, prop_before0, Mdst);
       HIPCHK(h, hipGetLastError());
       note_smooth(h, SG_SMOOTH_TILED, 4, SMF_TT);
       return SG_OK;
@@ -2127,7 +2130,7 @@ static int stage_smooth(sg_handle* h, const Geom& g, int64_t ub, hipStream_t st)
   int prop_before = (h->p.variant == SG_VARIANT_T || h->p.stationary) ? 1 : 0;
   hipLaunchKernelGGL(k_smooth_t, dim3(grid_1d(cells, 256)), dim3(256), 0, st, (const float*)tmp, g,
                      (const float*)h->kt.p, h->p.n_grad_time, (const float*)h->kf.p, h->p.n_grad_freq, p,
-                     prop_before, (float*)h->M.p, ub);
+                     prop_before, Mdst, ub);
   HIPCHK(h, hipGetLastError());
   note_smooth(h, SG_SMOOTH_SEPARATE, 4, 0);
   return SG_OK;
@@ -3112,13 +3115,22 @@ extern "C" int sg_filter_padded(sg_handle* h, const void* chunk_dev, int in_dtyp
 // ------------------------------------------------------------------------------------------
 // variant T
 // ------------------------------------------------------------------------------------------
-extern "C" int sg_process_batch(sg_handle* h, const void* x_dev, int dtype, int64_t B, int64_t L, int64_t x_stride,
-                                const void* xn_dev, int64_t Bn, int64_t Ln, int64_t xn_stride, void* out_dev,
-                                int out_dtype, int64_t out_stride, float* mask_out_dev, void* stream) {
-  if (!h) return SG_E_INVALID;
-  if (h->p.variant != SG_VARIANT_T) FAIL(h, SG_E_INVALID, "sg_process_batch is a variant-T entry point");
-  if (!x_dev || !out_dev || !dtype_ok(dtype) || !dtype_ok(out_dtype) || B < 1)
-    FAIL(h, SG_E_INVALID, "sg_process_batch: bad argument");
+// The gated spectrogram of one sub-batch (spec.hpp): rfft(window * frame) * mask -> spec_dev[u0 ..][T][F], mask in natural bin order.
+static int stage_spectrum(sg_handle* h, const View& v, const Geom& g, int64_t u0, int64_t nb, const float* mask, void* spec_dev,
+                          int dtype, hipStream_t st) {
+  ProfScope ps(h, SG_STAGE_APPLY_ISTFT, st);
+  char* dst = (char*)spec_dev + (size_t)u0 * g.T * g.F * 2 * (dtype == SG_F64 ? 8 : 4);
+  HIPCHK(h, spec_forward(v, g, nb, h->tw32.p, (const float*)h->wa32.p, mask, dst, dtype, st));
+  return SG_OK;
+}
+
+// sg_process_batch and sg_gate_spectrum: the statistics, decisions and smoothing of a batch of rows, then either the
+// inverse transform (out_dev) or, with spec_dev set, the masked spectrogram itself.  With spec_dev the one-launch row gate is
+// not taken, and the bit-mask route hands its decisions to the float smoothing kernels instead of the integer ones: the
+// spectrogram's mask is then the float field of the general route (h->M) at every geometry.
+static int process_batch_impl(sg_handle* h, const void* x_dev, int dtype, int64_t B, int64_t L, int64_t x_stride,
+                              const void* xn_dev, int64_t Bn, int64_t Ln, int64_t xn_stride, void* out_dev,
+                              int out_dtype, int64_t out_stride, float* mask_out_dev, void* spec_dev, void* stream) {
   if (L < 2 * (int64_t)h->W) FAIL(h, SG_E_INVALID, "x must be bigger than %d", 2 * h->W);  // torchgate.py:215-216
   if (xn_dev) {
     if (Ln < 2 * (int64_t)h->W) FAIL(h, SG_E_INVALID, "xn must be bigger than %d", 2 * h->W);  // :219-220
@@ -3164,7 +3176,7 @@ extern "C" int sg_process_batch(sg_handle* h, const void* x_dev, int dtype, int6
       } else {
         th = nullptr; ustride = g.FS;
       }
-      if (!xn_dev && rowgate_ok(h, g, B)) {
+      if (!spec_dev && !xn_dev && rowgate_ok(h, g, B)) {
         // one kernel per call: a workgroup per row (rowgate.hpp)
         v.unit0 = 0;
         View vr = v;
@@ -3216,31 +3228,42 @@ extern "C" int sg_process_batch(sg_handle* h, const void* x_dev, int dtype, int6
                              nb);
           HIPCHK(h, hipGetLastError());
         }
-        if ((rc = stage_smooth_bits(h, g, nb, true, 0, g.T, st))) return rc;
-        if (mask_out_dev) {  // float mask (natural bin order) for the backward pass
-          hipLaunchKernelGGL(k_k16_to_mask_perm, dim3(grid_1d(nb * g.T * g.FS, 256)), dim3(256), 0, st,
-                             (const unsigned short*)h->K16.p, g, 1.0f / (float)h->ktot,
-                             mask_out_dev + (size_t)u0 * g.T * g.FS, nb);
-          HIPCHK(h, hipGetLastError());
+        if (!spec_dev) {
+          if ((rc = stage_smooth_bits(h, g, nb, true, 0, g.T, st))) return rc;
+          if (mask_out_dev) {  // float mask (natural bin order) for the backward pass
+            hipLaunchKernelGGL(k_k16_to_mask_perm, dim3(grid_1d(nb * g.T * g.FS, 256)), dim3(256), 0, st,
+                               (const unsigned short*)h->K16.p, g, 1.0f / (float)h->ktot,
+                               mask_out_dev + (size_t)u0 * g.T * g.FS, nb);
+            HIPCHK(h, hipGetLastError());
+          }
+          if ((rc = stage_apply_fast(h, v, g, nb, om, nullptr, 1, st))) return rc;
+          h->dbg_units = nb; h->dbg_T = g.T; h->dbg_has_P = true; h->dbg_fused = true; h->dbg_fast = true;
+          h->dbg_db = 0; h->dbg_de = g.T;
+          continue;
         }
-        if ((rc = stage_apply_fast(h, v, g, nb, om, nullptr, 1, st))) return rc;
-        h->dbg_units = nb; h->dbg_T = g.T; h->dbg_has_P = true; h->dbg_fused = true; h->dbg_fast = true;
-        h->dbg_db = 0; h->dbg_de = g.T;
-        continue;
+        // the spectrogram kernel reads a float mask in natural bin order: the decision bits as a 0 / 1 field, smoothed by
+        // the float kernels below -- bitwise the mask this function writes without the bit-mask route, at every geometry
+        ProfScope ps(h, SG_STAGE_DECIDE, st);
+        HIPCHK(h, spec_bits_to_raw((const unsigned long long*)h->bits.p, g, wpr, (float*)h->raw.p, nb, st));
       }
-      if ((rc = stage_decide(h, g, nb, th, ustride, st))) return rc;
+      if (!bits_path && (rc = stage_decide(h, g, nb, th, ustride, st))) return rc;
     } else if (box_mask_ok(h)) {
       if ((rc = stage_box_mask(h, v, g, nb, st))) return rc;
     } else {
       if ((rc = stage_nonstat_raw(h, v, g, nb, st))) return rc;
     }
     const bool geom_fast = h->fast_ok && !h->force_nofast;
+    // the spectrogram reads the mask wherever it lies: smoothed straight into the caller's buffer, without the copy below
+    float* const mask_direct = (spec_dev && mask_out_dev && (h->p.stationary || !box_mask_ok(h)))
+                                   ? mask_out_dev + (size_t)u0 * g.T * g.FS : nullptr;
     if (h->p.stationary || !box_mask_ok(h))
-      if ((rc = stage_smooth(h, g, nb, st))) return rc;
-    if (mask_out_dev)
+      if ((rc = stage_smooth(h, g, nb, st, mask_direct))) return rc;
+    if (mask_out_dev && !mask_direct)
       HIPCHK(h, hipMemcpyAsync(mask_out_dev + (size_t)u0 * g.T * g.FS, h->M.p, (size_t)nb * g.T * g.FS * 4,
                                hipMemcpyDeviceToDevice, st));
-    if (geom_fast) {
+    if (spec_dev) {
+      if ((rc = stage_spectrum(h, v, g, u0, nb, mask_direct ? mask_direct : (const float*)h->M.p, spec_dev, dtype, st))) return rc;
+    } else if (geom_fast) {
       if ((rc = stage_apply_fast(h, v, g, nb, om, (const float*)h->M.p, 1, st))) return rc;
     } else if (const RegGeom* r = reg_geom(h)) {
       if ((rc = stage_apply_reg(h, r, v, g, nb, om, (const float*)h->M.p, 1, st))) return rc;
@@ -3253,6 +3276,64 @@ extern "C" int sg_process_batch(sg_handle* h, const void* x_dev, int dtype, int6
     h->dbg_has_raw = h->p.stationary || !box_mask_ok(h);
     h->dbg_fused = false;
     h->dbg_fast = geom_fast;
+  }
+  return SG_OK;
+}
+
+extern "C" int sg_process_batch(sg_handle* h, const void* x_dev, int dtype, int64_t B, int64_t L, int64_t x_stride,
+                                const void* xn_dev, int64_t Bn, int64_t Ln, int64_t xn_stride, void* out_dev,
+                                int out_dtype, int64_t out_stride, float* mask_out_dev, void* stream) {
+  if (!h) return SG_E_INVALID;
+  if (h->p.variant != SG_VARIANT_T) FAIL(h, SG_E_INVALID, "sg_process_batch is a variant-T entry point");
+  if (!x_dev || !out_dev || !dtype_ok(dtype) || !dtype_ok(out_dtype) || B < 1)
+    FAIL(h, SG_E_INVALID, "sg_process_batch: bad argument");
+  return process_batch_impl(h, x_dev, dtype, B, L, x_stride, xn_dev, Bn, Ln, xn_stride, out_dev, out_dtype, out_stride,
+                            mask_out_dev, nullptr, stream);
+}
+
+// TorchGate.gated_stft: X * mask in torch.stft's layout (spec.hpp)
+static bool spectrum_geom_ok(const sg_handle* h) { return spec_native(h->n) && !h->czt_M && !h->big_M && !h->mr_ok; }
+
+extern "C" int sg_gate_spectrum(sg_handle* h, const void* x_dev, int dtype, int64_t B, int64_t L, int64_t x_stride,
+                                const void* xn_dev, int64_t Bn, int64_t Ln, int64_t xn_stride, void* spec_dev,
+                                float* mask_out_dev, void* stream) {
+  if (!h) return SG_E_INVALID;
+  if (h->p.variant != SG_VARIANT_T) FAIL(h, SG_E_INVALID, "sg_gate_spectrum is a variant-T entry point");
+  if (!x_dev || !spec_dev || (dtype != SG_F32 && dtype != SG_F64) || B < 1)
+    FAIL(h, SG_E_INVALID, "sg_gate_spectrum: bad argument");
+  if (!spectrum_geom_ok(h))
+    FAIL(h, SG_E_UNSUPPORTED, "sg_gate_spectrum: n_fft=%d (powers of two from 256 to 4096 only)", h->n);
+  return process_batch_impl(h, x_dev, dtype, B, L, x_stride, xn_dev, Bn, Ln, xn_stride, nullptr, dtype, 0, mask_out_dev,
+                            spec_dev, stream);
+}
+
+// Adjoint of Y = M .* rfft( Wa frames(x) ) with M fixed: g_x = frames^T( Wa Re sum_k M[k] g[k] e^{+2 pi i k j / n} ), every bin
+// with weight 1 and no envelope division (the adjoint of an STFT, not an ISTFT).  Windowed frames into h->seg, then one gather.
+extern "C" int sg_gate_spectrum_backward(sg_handle* h, const void* grad_spec_dev, int dtype, int64_t B, int64_t L,
+                                         const float* mask_dev, void* grad_x_dev, int64_t gx_stride, void* stream) {
+  if (!h) return SG_E_INVALID;
+  if (h->p.variant != SG_VARIANT_T) FAIL(h, SG_E_INVALID, "sg_gate_spectrum_backward is a variant-T entry point");
+  if (!grad_spec_dev || !grad_x_dev || !mask_dev || B < 1 || (dtype != SG_F32 && dtype != SG_F64))
+    FAIL(h, SG_E_INVALID, "sg_gate_spectrum_backward: bad argument");
+  if (L < 2 * (int64_t)h->W) FAIL(h, SG_E_INVALID, "x must be bigger than %d", 2 * h->W);
+  if (!spectrum_geom_ok(h))
+    FAIL(h, SG_E_UNSUPPORTED, "sg_gate_spectrum_backward: n_fft=%d (powers of two from 256 to 4096 only)", h->n);
+  hipStream_t st = (hipStream_t)stream;
+  const Geom g = make_geom(h, L);
+  const int64_t ub = units_per_batch(h, g, B);
+  int rc;
+  if ((rc = ensure(h, h->seg, (size_t)ub * g.T * g.n * 4))) return rc;
+  const size_t esz = dtype == SG_F64 ? 8 : 4;
+  for (int64_t u0 = 0; u0 < B; u0 += ub) {
+    const int64_t nb = std::min(ub, B - u0);
+    {
+      ProfScope ps(h, SG_STAGE_APPLY_ISTFT, st);
+      HIPCHK(h, spec_backward_frames(g, nb, h->tw32.p, (const float*)h->wa32.p, mask_dev + (size_t)u0 * g.T * g.FS,
+                                     (const char*)grad_spec_dev + (size_t)u0 * g.T * g.F * 2 * esz, dtype, (float*)h->seg.p, st));
+    }
+    ProfScope ps(h, SG_STAGE_OLA, st);
+    HIPCHK(h, spec_backward_ola(g, nb, L, (const float*)h->seg.p, (char*)grad_x_dev + (size_t)u0 * gx_stride * esz, dtype,
+                                gx_stride, st));
   }
   return SG_OK;
 }

@@ -58,6 +58,27 @@ class _RowsFunction(torch.autograd.Function):
         return gx, None, None, None, None
 
 
+class _SpectrumFunction(torch.autograd.Function):
+    """gated_stft on the native kernels (sg_gate_spectrum): returns the real pairs (B, T, F, 2) -- torch.view_as_complex is
+    applied outside, so the complex autograd convention stays torch's -- and the mask, which carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, xn, module):
+        gate = module._gate_for(x.device)
+        pairs, mask = gate.gate_spectrum(x.detach(), xn, save_mask=True)
+        ctx.gate = gate
+        ctx.L = x.shape[-1]
+        ctx.save_for_backward(mask)
+        ctx.mark_non_differentiable(mask)
+        return pairs, mask
+
+    @staticmethod
+    def backward(ctx, grad_pairs, _grad_mask):
+        (mask,) = ctx.saved_tensors
+        gx = ctx.gate.gate_spectrum_backward(grad_pairs.contiguous(), mask, ctx.L)
+        return gx, None, None
+
+
 class TorchGate(torch.nn.Module):
     """A PyTorch module that applies a spectral gate to an input signal (see the reference
     docstring, torchgate.py:8-29, for the arguments)."""
@@ -173,6 +194,54 @@ class TorchGate(torch.nn.Module):
                 xn = None  # unused by the non-stationary mask (torchgate.py:235-236)
         y = _GateFunction.apply(x, xn, self)
         return y.to(dtype=dtype)
+
+    def gated_stft(self, x: torch.Tensor, xn: Optional[torch.Tensor] = None, return_mask: bool = False):
+        """The gated spectrogram ``Y = X * sig_mask`` that the reference multiplies on the line before its ``torch.istft``
+        (torchgate.py:223-252) -- for log-mel features, spectral losses or an enhancement front end, without the inverse
+        transform of ``forward`` and a further STFT.
+
+        x: (batch, signal_length), xn: as in ``forward``.  Returns Y (batch, n_fft // 2 + 1, frames) complex, where
+        ``X = torch.stft(x, n_fft, hop_length, win_length, window=hann_window(win_length), center=True,
+        pad_mode="constant", return_complex=True)`` (unscaled) and ``torch.istft(Y, ...)`` with the same arguments is
+        ``forward(x, xn)``.  float32 input gives complex64, float64 complex128, other dtypes go through ``.float()``.
+        The memory layout is ``torch.stft``'s: storage (batch, frames, bins) with the bins contiguous, returned as the
+        ``.transpose(1, 2)`` view.  With ``return_mask=True`` also the final mask (smoothed, prop_decrease applied) as a
+        float32 (batch, bins, frames) view of the engine's buffer.  Differentiable w.r.t. ``x`` with the mask detached,
+        like ``forward``; the mask carries no gradient.
+
+        Power-of-two n_fft from 256 to 4096 run on the native kernels (sg_gate_spectrum, csrc/spec.hip).  Any other
+        n_fft takes the composed, slow route: ``torch.stft(x) * mask`` with the mask of the full-length path and torch
+        autograd for the backward."""
+        assert x.ndim == 2
+        if x.shape[-1] < self.win_length * 2:
+            raise Exception(f"x must be bigger than {self.win_length * 2}")
+        assert xn is None or xn.ndim == 1 or xn.ndim == 2
+        if xn is not None and xn.shape[-1] < self.win_length * 2:
+            raise Exception(f"xn must be bigger than {self.win_length * 2}")
+        if x.device.type != "cuda":
+            raise RuntimeError("noisereduce_amd.TorchGate runs on the GPU only (no CPU fallback): "
+                               "move the input with x.to('cuda')")
+        if x.dtype not in (torch.float32, torch.float64):
+            x = x.float()
+        if xn is not None:
+            xn = xn.detach().to(device=x.device, dtype=x.dtype)
+            if xn.ndim == 1:
+                xn = xn.unsqueeze(0)
+            if self.nonstationary:
+                xn = None  # unused by the non-stationary mask (torchgate.py:235-236)
+        F = self.n_fft // 2 + 1
+        if _rows.native(self.n_fft):
+            pairs, mask = _SpectrumFunction.apply(x, xn, self)
+            Yt = torch.view_as_complex(pairs)
+        else:
+            with torch.no_grad():
+                _, mask = self._gate_for(x.device).process_batch(x.detach(), xn, save_mask=True)
+            window = torch.hann_window(self.win_length, device=x.device).to(x.dtype)  # the float32 table, as _gate_for
+            X = torch.stft(x, n_fft=self.n_fft, hop_length=self.hop_length, win_length=self.win_length, window=window,
+                           center=True, pad_mode="constant", return_complex=True)
+            Yt = X.transpose(1, 2).contiguous() * mask[:, :, :F].to(x.dtype)
+        Y = Yt.transpose(1, 2)
+        return (Y, mask[:, :, :F].transpose(1, 2)) if return_mask else Y
 
     def _forward_rows(self, x, xn, lengths, xn_lengths):
         """forward with per-row lengths: validation, then the full-length path (every row full), the table-driven
