@@ -46,6 +46,16 @@ SG_API int sg_debug_range(const sg_handle* h, int64_t range[2]);
 #define SG_SMOOTH_BOX_MASK 10   /* k_box_mask<nt> (TorchGate, non-stationary, n_movemean = 20) */
 #define SG_SMOOTH_X_TILED 11    /* kx_smooth_tiled (float64 pipeline) */
 #define SG_SMOOTH_X_SEPARATE 12 /* kx_smooth_f + kx_smooth_t (float64 pipeline) */
+/* which = 18: the route of the last sg_gate_spectrum call on the handle, 0 when that call failed before its first spectrum
+ * launch (host bookkeeping, no synchronisation; no kernel reads or writes it): bits 0..7 the SG_SPEC_* branch that made the
+ * decisions of the last sub-batch, bit 8 SG_SPEC_BITS_TO_RAW, bit 9 SG_SPEC_MASK_DIRECT, bits 16.. the number of sub-batches. */
+#define SG_SPEC_ROW_DECIDE 1    /* k_row_decide: statistics, constants and decision bits of a (row, 64 bands) tile, rows of <= 128 frames */
+#define SG_SPEC_T2_BITS 2       /* k_t2_rows + k_decide_bits_t2: decision bits of longer rows */
+#define SG_SPEC_DECIDE 3        /* stage_decide: the general float decisions */
+#define SG_SPEC_BOX_MASK 4      /* stage_box_mask: k_box_mask<nt> (non-stationary, n_movemean = 20) */
+#define SG_SPEC_NONSTAT_RAW 5   /* stage_nonstat_raw: the raw sigmoid field, smoothed by the general kernels */
+#define SG_SPEC_BITS_TO_RAW 0x100 /* the decision bits went through k_spec_bits_to_raw into the float smoothing kernels */
+#define SG_SPEC_MASK_DIRECT 0x200 /* the smoothing wrote straight into the caller's mask buffer (no copy from the workspace) */
 SG_API int sg_debug_counter(sg_handle* h, int32_t which, int64_t* value, void* stream);
 SG_API int sg_debug_fetch(sg_handle* h, int32_t what, void* host, int64_t bytes, void* stream);
 

@@ -45,6 +45,9 @@ SG_BWD_ROW, SG_BWD_FAST, SG_BWD_REG, SG_BWD_OLA, SG_BWD_ROWS = 1, 2, 3, 4, 5
 SG_SMOOTH_NAMES = {0: "none", 1: "off", 2: "k_smooth_tiled", 3: "k_smooth_f+k_smooth_t", 4: "k_smooth_bits2", 5: "k_smooth_bits",
                    6: "k_gate_onepass", 7: "k_gate_onepass_reg", 8: "k_row_gate", 9: "k_iir_mask<nt>", 10: "k_box_mask",
                    11: "kx_smooth_tiled", 12: "kx_smooth_f+kx_smooth_t"}
+# sg_debug_counter(18): SG_SPEC_* of include/mi355gate_debug.h, the decide branch of the last sg_gate_spectrum call
+SG_SPEC_NAMES = {0: "none", 1: "k_row_decide", 2: "k_t2_rows+k_decide_bits_t2", 3: "stage_decide", 4: "stage_box_mask",
+                 5: "stage_nonstat_raw"}
 
 _TORCH_DTYPES = {torch.float32: SG_F32, torch.float64: SG_F64, torch.int16: SG_I16,
                  torch.int32: SG_I32}
@@ -879,6 +882,13 @@ class Gate:
         frames per tile)`` -- sg_debug_counter(17), host bookkeeping only."""
         v = self.debug_counter(17)
         return SG_SMOOTH_NAMES[v & 0xff], (v >> 8) & 0xff, v >> 16
+
+    def spectrum_route(self):
+        """The route of the last gate_spectrum call on this handle: ``(decide branch, through k_spec_bits_to_raw, smoothed
+        straight into the caller's mask, sub-batches)`` -- sg_debug_counter(18), host bookkeeping only.  ("none", False,
+        False, 0): the call failed before its first spectrum launch."""
+        v = self.debug_counter(18)
+        return SG_SPEC_NAMES[v & 0xff], bool(v & 0x100), bool(v & 0x200), v >> 16
 
     def debug_field(self, what):
         """0: raw mask, 1: final mask (float32); 2: power (float64) of the last unit batch,

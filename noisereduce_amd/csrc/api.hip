@@ -196,6 +196,7 @@ struct sg_handle {
   int rowgate_mode = 0;              // SG_OPT_FORCE_NOROWGATE: 0 = by batch size, 1 = never, 2 = whenever the shape is eligible
   int64_t n_floor_lazy = 0, n_floor_apriori = 0;   // sg_debug_counter 1 / 2
   int64_t smooth_route = 0;   // sg_debug_counter 17: SG_SMOOTH_* of the last smoothing launch | cell bytes << 8 | tile frames << 16
+  int64_t spec_route = 0;     // sg_debug_counter 18: SG_SPEC_* decide branch of the last sg_gate_spectrum call | flags | sub-batches << 16
   int tile_order = 0;                // SG_OPT_TILE_ORDER: 0 (default, round 6) = persistent workgroups looping over tickets (onepass.hpp PERSIST), 2 = one ticket-drawn tile per workgroup (the kernel of rounds 2-5), 1 = tile = block index
                                      // block index (no ticket), 0 = persistent workgroups looping over tickets (round 6: 1 % faster alone on the
                                      // GPU, NOT the default -- next to TorchGate's row gate on a second stream it mis-gates a tile now and then:
@@ -3161,8 +3162,10 @@ static int process_batch_impl(sg_handle* h, const void* x_dev, int dtype, int64_
     vn.unit0 = 0;
     if ((rc = stage_stats(h, vn, gn, 1, (double*)h->thresh.p, st))) return rc;
   }
+  int64_t n_sub = 0;
   for (int64_t u0 = 0; u0 < B; u0 += ub) {
     int64_t nb = std::min(ub, B - u0);
+    int64_t branch = 0;   // (host bookkeeping behind sg_debug_counter 18: which statement below decided this sub-batch)
     v.unit0 = u0;
     if (h->p.stationary) {
       const double* th;
@@ -3245,12 +3248,16 @@ static int process_batch_impl(sg_handle* h, const void* x_dev, int dtype, int64_
         // the float kernels below -- bitwise the mask this function writes without the bit-mask route, at every geometry
         ProfScope ps(h, SG_STAGE_DECIDE, st);
         HIPCHK(h, spec_bits_to_raw((const unsigned long long*)h->bits.p, g, wpr, (float*)h->raw.p, nb, st));
+        branch = (row_fused ? SG_SPEC_ROW_DECIDE : SG_SPEC_T2_BITS) | SG_SPEC_BITS_TO_RAW;
       }
       if (!bits_path && (rc = stage_decide(h, g, nb, th, ustride, st))) return rc;
+      if (!bits_path) branch = SG_SPEC_DECIDE;
     } else if (box_mask_ok(h)) {
       if ((rc = stage_box_mask(h, v, g, nb, st))) return rc;
+      branch = SG_SPEC_BOX_MASK;
     } else {
       if ((rc = stage_nonstat_raw(h, v, g, nb, st))) return rc;
+      branch = SG_SPEC_NONSTAT_RAW;
     }
     const bool geom_fast = h->fast_ok && !h->force_nofast;
     // the spectrogram reads the mask wherever it lies: smoothed straight into the caller's buffer, without the copy below
@@ -3263,6 +3270,7 @@ static int process_batch_impl(sg_handle* h, const void* x_dev, int dtype, int64_
                                hipMemcpyDeviceToDevice, st));
     if (spec_dev) {
       if ((rc = stage_spectrum(h, v, g, u0, nb, mask_direct ? mask_direct : (const float*)h->M.p, spec_dev, dtype, st))) return rc;
+      h->spec_route = branch | (mask_direct ? SG_SPEC_MASK_DIRECT : 0) | (++n_sub << 16);
     } else if (geom_fast) {
       if ((rc = stage_apply_fast(h, v, g, nb, om, (const float*)h->M.p, 1, st))) return rc;
     } else if (const RegGeom* r = reg_geom(h)) {
@@ -3298,6 +3306,7 @@ extern "C" int sg_gate_spectrum(sg_handle* h, const void* x_dev, int dtype, int6
                                 const void* xn_dev, int64_t Bn, int64_t Ln, int64_t xn_stride, void* spec_dev,
                                 float* mask_out_dev, void* stream) {
   if (!h) return SG_E_INVALID;
+  h->spec_route = 0;   // (sg_debug_counter 18 speaks of THIS call)
   if (h->p.variant != SG_VARIANT_T) FAIL(h, SG_E_INVALID, "sg_gate_spectrum is a variant-T entry point");
   if (!x_dev || !spec_dev || (dtype != SG_F32 && dtype != SG_F64) || B < 1)
     FAIL(h, SG_E_INVALID, "sg_gate_spectrum: bad argument");
@@ -3569,6 +3578,10 @@ extern "C" int sg_debug_counter(sg_handle* h, int32_t which, int64_t* value, voi
   }
   if (which == 17) {   // SG_SMOOTH_* of the last smoothing launch | cell bytes << 8 | tile frames << 16 (host bookkeeping)
     *value = h->smooth_route;
+    return SG_OK;
+  }
+  if (which == 18) {   // SG_SPEC_* of the last sg_gate_spectrum call | flags | sub-batches << 16 (host bookkeeping)
+    *value = h->spec_route;
     return SG_OK;
   }
   if (which == 3) {   // launch epoch of the last gate call in which a chunk's floor test fired / flag was set (0: never)
