@@ -440,6 +440,29 @@ SG_API int sg_process_rows_backward(sg_handle* h, const void* grad_out_dev, int 
                                     int64_t go_stride, const int64_t* lengths, const float* mask_dev, void* grad_x_dev,
                                     int64_t gx_stride, void* stream);
 
+/* sg_gate_spectrum for a PADDED batch (lengths / xn_lengths as in sg_process_rows): spec [B][T][F] complex of dtype,
+ * T = sg_n_frames(L).  With T_i = 1 + lengths[i] / hop: spec[i][0 .. T_i) is what sg_gate_spectrum returns for the row
+ * alone at length lengths[i] -- statistics, moving mean, mask smoothing (zero-padded at the row's own last frame) and
+ * the -top_db floor over the row's own T_i frames; a frame sees zeros, never the padding, at or beyond lengths[i] -- and
+ * spec[i][T_i .. T) is +0.0 + 0.0i.  Samples at or beyond lengths[i] / xn_lengths[j] are never read.  A row's result does
+ * not depend on the other rows, their order or L.  mask_out_dev: NULL or float[B][T][FS], bit for bit the mask
+ * sg_process_rows writes for the same input (frames >= T_i are 0), for sg_gate_spectrum_rows_backward; the bins are
+ * multiplied by this float32 mask.  Float64 transforms for both sample types: a float64 result is stored unrounded, a
+ * float32 result rounded once.  Power-of-two n_fft from 256 to 4096 (SG_E_UNSUPPORTED otherwise).  Rows are packed into
+ * sub-batches under the handle's max_workspace_bytes (0: 4 GiB) with the same bits as unsplit; a fixed number of
+ * launches per sub-batch.  Enqueues only. */
+SG_API int sg_gate_spectrum_rows(sg_handle* h, const void* x_dev, int dtype, int64_t B, int64_t L, int64_t x_stride,
+                                 const int64_t* lengths, const void* xn_dev, int64_t Bn, int64_t Ln, int64_t xn_stride,
+                                 const int64_t* xn_lengths, void* spec_dev, float* mask_out_dev, void* stream);
+
+/* Adjoint of sg_gate_spectrum_rows with the mask held fixed: grad_spec [B][T][F] complex of dtype -> grad_x (B, L) of
+ * dtype, as sg_gate_spectrum_backward on every row alone: grad_x[i][0 .. lengths[i]) is the gradient of the row alone,
+ * grad_x[i][lengths[i] .. L) is 0, and grad_spec[i][T_i .. T) is never read.  No envelope division, no atomics: the same
+ * bits on every run.  Sub-batches as above.  Enqueues only. */
+SG_API int sg_gate_spectrum_rows_backward(sg_handle* h, const void* grad_spec_dev, int dtype, int64_t B, int64_t L,
+                                          const int64_t* lengths, const float* mask_dev, void* grad_x_dev,
+                                          int64_t gx_stride, void* stream);
+
 /* ---- stage taps (used by the parity tests; also plain STFT/ISTFT operators) ------ */
 
 /* Forward STFT of (B, L) rows -> complex float64 Z[B][T][F] (interleaved re,im), same

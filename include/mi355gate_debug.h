@@ -64,7 +64,8 @@ SG_API int sg_debug_fetch(sg_handle* h, int32_t what, void* host, int64_t bytes,
 SG_API int sg_debug_clip_thresholds(sg_handle* h, double* host, int32_t n_noise, int32_t n_bins, void* stream);
 /* Sub-batches the last sg_process_clips call was split into. */
 SG_API int sg_debug_clip_batches(const sg_handle* h, int64_t* value);
-/* Sub-batches the last sg_process_rows / sg_process_rows_backward call was split into. */
+/* Sub-batches the last sg_process_rows / sg_process_rows_backward / sg_gate_spectrum_rows / sg_gate_spectrum_rows_backward
+ * call was split into. */
 SG_API int sg_debug_rows_batches(const sg_handle* h, int64_t* value);
 /* Which kernels the last sg_process_batch_backward / sg_process_rows_backward call on this handle launched (0: none yet).
  * Host bookkeeping only: no kernel reads or writes it. */
@@ -135,7 +136,8 @@ SG_API int sg_debug_backward_route(const sg_handle* h, int64_t* value);
 #define SG_STAGE_IIR_CHAIN 18 /* non-stationary gate: carries of the time tiles (k_iir_chain_par; serial form k_iir_part / k_iir_comb + k_iir_chain) */
 #define SG_STAGE_IIR_MASK 19  /* non-stationary gate: k_iir_mask<nt> -- recurrence, sigmoid and both smoothing passes in one kernel */
 /* ragged batches (sg_process_clips, ragged.hip): one launch of each per sub-batch.  sg_process_rows (rows.hip) books its
- * launches under the same seven stages (its moving mean under SG_STAGE_RG_IIR). */
+ * launches under the same seven stages (its moving mean under SG_STAGE_RG_IIR), and so does sg_gate_spectrum_rows: its
+ * spectrum store and its adjoint frames under SG_STAGE_RG_APPLY, the adjoint's overlap-add under SG_STAGE_RG_OLA. */
 #define SG_STAGE_RG_NOISE_POWER 20 /* stationary: float64 transform of every noise frame */
 #define SG_STAGE_RG_NOISE_FINAL 21 /* stationary: per-source band maxima, moments, thresholds, compare constants */
 #define SG_STAGE_RG_DECIDE 22      /* float64 transform of every data frame: decision bits + band maxima (stationary) / magnitudes */

@@ -149,6 +149,10 @@ _PROTOTYPES = {
                                 c_int64, c_int64, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p]),
     "sg_process_rows_backward": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p,
                                          c_void_p, c_int64, c_void_p]),
+    "sg_gate_spectrum_rows": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64,
+                                      c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sg_gate_spectrum_rows_backward": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p,
+                                               c_void_p, c_int64, c_void_p]),
     "sg_debug_rows_batches": (c_int, [c_void_p, POINTER(c_int64)]),
     "sg_debug_backward_route": (c_int, [c_void_p, POINTER(c_int64)]),
     "sg_stft": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
@@ -587,6 +591,51 @@ class Gate:
             self._check(self.lib.sg_process_rows_backward(
                 self._h, grad_out.data_ptr(), _sg_dtype(grad_out), B, L, gs, lp, mask.data_ptr(),
                 gx.data_ptr(), L, self._stream()))
+        return gx
+
+    def gate_spectrum_rows(self, x, lengths, xn=None, xn_lengths=None, save_mask=False):
+        """TorchGate.gated_stft on a padded batch (sg_gate_spectrum_rows): row i holds lengths[i] samples (host integers)
+        and padding after them.  Returns (B, T, F, 2) real pairs of x.dtype, torch.stft's storage; frames
+        [0, 1 + lengths[i] // hop) of row i are the gated spectrum of x[i, :lengths[i]] alone, the frames after them
+        zero.  With save_mask=True also the (B, T, FS) float32 mask process_rows returns (natural bin order, frames
+        beyond the row's own zero) for gate_spectrum_rows_backward."""
+        self._on_device(x)
+        x, xs = _rows(x)
+        B, L = x.shape
+        T = self.n_frames(L)
+        out = torch.empty((B, T, self.n_bins, 2), dtype=x.dtype, device=self.device)
+        mask = None
+        if save_mask:
+            FS = (self.n_bins + 15) // 16 * 16
+            mask = torch.empty((B, T, FS), dtype=torch.float32, device=self.device)
+        if xn is not None:
+            self._on_device(xn)
+            if xn.dtype != x.dtype:
+                xn = xn.to(x.dtype)
+            xn, xns = _rows(xn)
+            xn_ptr, Bn, Ln = xn.data_ptr(), xn.shape[0], xn.shape[1]
+        else:
+            xn_ptr, Bn, Ln, xns = None, 0, 0, 0
+        la, lp = self._lengths(lengths, B)
+        na, np_ = self._lengths(xn_lengths if xn is not None else None, Bn)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.sg_gate_spectrum_rows(
+                self._h, x.data_ptr(), _sg_dtype(x), B, L, xs, lp, xn_ptr, Bn, Ln, xns, np_, out.data_ptr(),
+                None if mask is None else mask.data_ptr(), self._stream()))
+        return (out, mask) if save_mask else out
+
+    def gate_spectrum_rows_backward(self, grad, mask, L, lengths):
+        """Adjoint of gate_spectrum_rows with the mask fixed: grad (B, T, F, 2) real pairs -> (B, L) of grad.dtype, zero
+        at and beyond lengths[i]; grad[i, 1 + lengths[i] // hop:] is never read."""
+        self._on_device(grad)
+        grad = grad.contiguous()
+        B = grad.shape[0]
+        gx = torch.empty((B, L), dtype=grad.dtype, device=self.device)
+        la, lp = self._lengths(lengths, B)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.sg_gate_spectrum_rows_backward(
+                self._h, grad.data_ptr(), _sg_dtype(grad), B, L, lp, mask.data_ptr(), gx.data_ptr(), L,
+                self._stream()))
         return gx
 
     def rows_batches(self):

@@ -3803,6 +3803,35 @@ extern "C" int sg_process_rows_backward(sg_handle* h, const void* grad_out_dev, 
                          rw_budget(h), (hipStream_t)stream, &h->err);
 }
 
+// TorchGate.gated_stft(lengths=): the rows pipeline with the masked spectrum stored instead of inverted (rows.hpp)
+extern "C" int sg_gate_spectrum_rows(sg_handle* h, const void* x_dev, int dtype, int64_t B, int64_t L, int64_t x_stride,
+                                     const int64_t* lengths, const void* xn_dev, int64_t Bn, int64_t Ln, int64_t xn_stride,
+                                     const int64_t* xn_lengths, void* spec_dev, float* mask_out_dev, void* stream) {
+  if (!h) return SG_E_INVALID;
+  if (h->p.variant != SG_VARIANT_T) FAIL(h, SG_E_INVALID, "sg_gate_spectrum_rows is a variant-T entry point");
+  if (!x_dev || !spec_dev || (dtype != SG_F32 && dtype != SG_F64) || B < 1 || x_stride < L)
+    FAIL(h, SG_E_INVALID, "sg_gate_spectrum_rows: bad argument");
+  if (L < 2 * (int64_t)h->W) FAIL(h, SG_E_INVALID, "x must be bigger than %d", 2 * h->W);  // torchgate.py:215-216
+  if (xn_dev) {
+    if (Ln < 2 * (int64_t)h->W) FAIL(h, SG_E_INVALID, "xn must be bigger than %d", 2 * h->W);  // :219-220
+    if (Bn != 1 && Bn != B) FAIL(h, SG_E_INVALID, "xn rows (%lld) must be 1 or the batch size", (long long)Bn);
+  }
+  return sg::rw_spectrum(&h->rw, rg_ctx(h), h->p.n_movemean, x_dev, dtype, B, L, x_stride, lengths, xn_dev, Bn, Ln, xn_stride,
+                         xn_lengths, spec_dev, mask_out_dev, rw_budget(h), (hipStream_t)stream, &h->err);
+}
+
+extern "C" int sg_gate_spectrum_rows_backward(sg_handle* h, const void* grad_spec_dev, int dtype, int64_t B, int64_t L,
+                                              const int64_t* lengths, const float* mask_dev, void* grad_x_dev,
+                                              int64_t gx_stride, void* stream) {
+  if (!h) return SG_E_INVALID;
+  if (h->p.variant != SG_VARIANT_T) FAIL(h, SG_E_INVALID, "sg_gate_spectrum_rows_backward is a variant-T entry point");
+  if (!grad_spec_dev || !grad_x_dev || !mask_dev || B < 1 || (dtype != SG_F32 && dtype != SG_F64) || gx_stride < L ||
+      L < 2 * (int64_t)h->W)
+    FAIL(h, SG_E_INVALID, "sg_gate_spectrum_rows_backward: bad argument");
+  return sg::rw_spectrum_backward(&h->rw, rg_ctx(h), grad_spec_dev, dtype, B, L, lengths, mask_dev, grad_x_dev, gx_stride,
+                                  rw_budget(h), (hipStream_t)stream, &h->err);
+}
+
 extern "C" int sg_debug_rows_batches(const sg_handle* h, int64_t* value) {
   if (!h || !value) return SG_E_INVALID;
   *value = sg::rw_last_batches(h->rw);

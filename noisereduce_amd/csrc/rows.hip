@@ -1,5 +1,5 @@
-// Padded batches of different-length rows (sg_process_rows): tables, kernels and the host side.  See rows.hpp and
-// DESIGN section 12.
+// Padded batches of different-length rows (sg_process_rows, sg_gate_spectrum_rows): tables, kernels and the host side.
+// See rows.hpp and DESIGN sections 12 and 14.
 //
 // Variant T throughout (torch.stft(center=True, pad_mode="constant"): frame t is centred on sample t H; the window is
 // embedded in an n_fft frame; torch.istft's trimming and envelope).  Row i owns T_i = 1 + len_i / H frames; samples at
@@ -26,12 +26,13 @@ namespace sg {
 
 // ---- tables ------------------------------------------------------------------------------------------------------
 struct RwRow {
-  int64_t x_off;       // element of the source (x; backward: grad_out) holding sample 0 of the row
+  int64_t x_off;       // element of the source (x; backward: grad_out; spectrum backward: complex element of grad_spec)
+                       // holding sample 0 (frame 0, bin 0) of the row
   int64_t len;         // readable samples (forward: lengths[i]; backward: H * (lengths[i] / H))
   int64_t T;           // frames: 1 + lengths[i] / H
   int64_t Lout;        // positions that receive a value (forward: H * (lengths[i] / H); backward: lengths[i])
-  int64_t full;        // positions written, [Lout, full) with zeros (forward: H * (L / H); backward: L)
-  int64_t out_off;     // element of out receiving position 0
+  int64_t full;        // positions written, [Lout, full) with zeros (forward: H * (L / H); backward: L; spectrum forward: 0)
+  int64_t out_off;     // element of out receiving position 0 (spectrum forward: complex element of frame 0, bin 0)
   int64_t frow;        // first row of this row's frames in the bits / magnitude / mask / segment fields
   int64_t mask_off;    // element of the caller's mask holding frame 0, band 0
   int32_t noise;       // local noise index (stationary)
@@ -242,8 +243,76 @@ __global__ __launch_bounds__(tile_nt<N>()) void k_rw_apply(RwArgs A) {
   }
 }
 
-// ---- overlap-add over the row's own frames.  Forward: out = sum seg / envelope on [0, Lout_i); backward: the plain
-// sum (the adjoint of the framing) on [0, len_i).  Positions up to `full` are the zero tail. ----------------------------
+// ---- the gated spectrogram of a padded batch (sg_gate_spectrum_rows): k_rw_apply's mask, the bins stored instead of
+// inverted.  The tiles cover [0, T) of every row: frames at or beyond T_i store zeros and load nothing (no memset of the
+// output).  out: [B][T][F] complex of out_dtype, row i's frame 0 at complex element out_off; consecutive lanes store
+// consecutive bins.  The bins are multiplied by the mask AS RETURNED (rounded to float32), as sg_gate_spectrum does:
+// k_rw_spec_bwd is then the adjoint of exactly this map, and a complex128 result is X * mask to float64 rounding.
+template <int N>
+__global__ __launch_bounds__(tile_nt<N>()) void k_rw_spec(RwArgs A) {
+  constexpr int NT = tile_nt<N>(), SY = tile_sy<N>();
+  if ((int64_t)blockIdx.x >= A.n_ap) return;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  cx<double>* tw = reinterpret_cast<cx<double>*>(smem);
+  cx<double>* buf = tw + N;
+  const int lane = threadIdx.x;
+  const Tile tl = A.tiles[A.t_ap + blockIdx.x];
+  const RwRow U = A.rows[tl.idx];
+  stage_tile_twiddles<N>(tw, A.c.tw);
+  for (int64_t t = tl.a; t < tl.b; ++t) {
+    const int64_t srow = U.out_off + t * A.c.F;
+    if (t >= U.T) {
+      for (int k = lane; k <= N; k += NT) {
+        if (A.out_dtype == 1) ((double2*)A.out)[srow + k] = make_double2(0.0, 0.0);
+        else ((float2*)A.out)[srow + k] = make_float2(0.f, 0.f);
+      }
+      continue;
+    }
+    rw_frame_fft<N>(A, A.x, A.in_dtype, U.x_off, U.len, U.T, t, buf, tw, lane);
+    const TimeTaps tp = time_taps(t, A.c.nt, U.T);
+    const int64_t mrow = U.mask_off + t * A.c.FS;
+    for (int k = lane; k <= N; k += NT) {
+      const double K = time_smooth(A.R, A.c.FS, [&](int64_t q) { return U.frow + q; }, tp, t, A.c.nt, k);
+      const float m = (float)mask_stationary(A.c, K, tp.Et, k);
+      if (A.mask_out) A.mask_out[mrow + k] = m;
+      const cx<double> X = packed_bin<N>(buf, tw, k);
+      if (A.out_dtype == 1) ((double2*)A.out)[srow + k] = make_double2(X.x * (double)m, X.y * (double)m);
+      else ((float2*)A.out)[srow + k] = make_float2((float)(X.x * (double)m), (float)(X.y * (double)m));
+    }
+    team_sync<SY>();
+  }
+}
+
+// ---- its adjoint with the mask fixed (sg_gate_spectrum_rows_backward): frame t < T_i of row i from grad [B][T][F]
+// complex of in_dtype (frame 0 at complex element x_off) and the forward's mask -> window * un-normalised inverse of the
+// merged mask .* grad into seg (mask_and_adjoint).  Frames at or beyond T_i are not in the tile list: never read.
+// k_rw_ola's plain sum follows.
+template <int N>
+__global__ __launch_bounds__(tile_nt<N>()) void k_rw_spec_bwd(RwArgs A) {
+  if ((int64_t)blockIdx.x >= A.n_ap) return;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  cx<double>* tw = reinterpret_cast<cx<double>*>(smem);
+  cx<double>* buf = tw + N;
+  const int lane = threadIdx.x;
+  const Tile tl = A.tiles[A.t_ap + blockIdx.x];
+  const RwRow U = A.rows[tl.idx];
+  stage_tile_twiddles<N>(tw, A.c.tw);
+  for (int64_t t = tl.a; t < tl.b; ++t) {
+    const int64_t grow = U.x_off + t * A.c.F;
+    const float* mrow = A.mask_in + U.mask_off + t * A.c.FS;
+    auto grad_at = [&](int k) -> cx<double> {
+      if (A.in_dtype == 1) { const double2 g = ((const double2*)A.x)[grow + k]; return {g.x, g.y}; }
+      const float2 g = ((const float2*)A.x)[grow + k];
+      return {(double)g.x, (double)g.y};
+    };
+    mask_and_adjoint<N>(buf, tw, lane, grad_at, [&](int k) -> double { return (double)mrow[k]; }, A.c.wfull,
+                        A.seg + (U.frow + t) * (int64_t)A.c.n);
+  }
+}
+
+// ---- overlap-add over the row's own frames.  Forward: out = sum seg / envelope on [0, Lout_i); backward (of the
+// waveform and of the spectrogram alike): the plain sum (the adjoint of the framing) on [0, len_i).  Positions up to
+// `full` are the zero tail. --------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_rw_ola(RwArgs A) {
   if ((int64_t)blockIdx.x >= A.n_ola) return;
   const Tile tl = A.tiles[A.t_ola + blockIdx.x];
@@ -290,14 +359,16 @@ struct Sizer {
     noise_rows += T;
     ntiles += tile_cdiv(T, FPT) + tile_cdiv(c.F, 64);
   }
-  // T frames, `full` written positions; backward: apply and overlap-add tiles only
-  void add_row(const RgCtx& c, int64_t T, int64_t full, bool bwd) {
+  // T frames, `full` written positions; backward: apply and overlap-add tiles only.  Tap: frames the apply stage's
+  // tiles cover (the spectrum forward stores every frame of the padded row, and has no overlap-add: full = 0)
+  void add_row(const RgCtx& c, int64_t T, int64_t full, bool bwd, int64_t Tap) {
     ++nu;
     frows += T;
-    ntiles += tile_cdiv(T, FPT) + tile_cdiv(full, 256);
+    ntiles += tile_cdiv(Tap, FPT) + tile_cdiv(full, 256);
     if (!bwd) ntiles += tile_cdiv(T, FPT) + tile_cdiv(T, RPT) + (c.stationary ? 0 : tile_cdiv(c.F, 64));
   }
-  Layout layout(const RgCtx& c, bool bwd) const {
+  // no_seg: the spectrum forward keeps no frame segments
+  Layout layout(const RgCtx& c, bool bwd, bool no_seg) const {
     Layout L{};
     const int wpr = (c.F + 63) / 64;
     const bool st = c.stationary && !bwd, ns = !c.stationary && !bwd;
@@ -312,7 +383,7 @@ struct Sizer {
     L.mag = take(ns ? (size_t)frows * c.FS * 4 : 0);
     L.sig = take(ns ? (size_t)frows * c.FS * 4 : 0);
     L.R = take(bwd ? 0 : (size_t)frows * c.FS * 4);
-    L.seg = take((size_t)frows * c.n * 4);
+    L.seg = take(no_seg ? 0 : (size_t)frows * c.n * 4);
     L.total = o;
     return L;
   }
@@ -340,9 +411,11 @@ int check_lengths(const RgCtx& c, const char* who, const char* what, const int64
   return SG_OK;
 }
 
-// one call of either direction: rows [0, B) packed greedily into sub-batches under the budget
+// one call of either direction: rows [0, B) packed greedily into sub-batches under the budget.  spec: the gated
+// spectrogram -- forward: out is [B][T][F] complex of out_dtype, out_stride = T * F; backward: x is the gradient in that
+// layout, x_stride = T * F
 struct Call {
-  bool bwd;
+  bool bwd, spec;
   const void* x; int dtype; int64_t B, L, x_stride; const int64_t* lengths;
   const void* xn; int64_t Bn, Ln, xn_stride; const int64_t* xn_lengths;
   void* out; int out_dtype; int64_t out_stride;
@@ -358,6 +431,7 @@ int run(RwState** sp, const RgCtx& c, int kbox, const Call& q, int64_t max_ws, h
   const int64_t H = c.H;
   const int64_t Tfull = 1 + q.L / H, Lq = H * (q.L / H);
   const bool stat = c.stationary && !q.bwd;
+  const bool spec_fwd = q.spec && !q.bwd;
   const int noise_mode = !stat ? 0 : (!q.xn ? 1 : (q.Bn == 1 ? 2 : 3));   // 1: the row itself, 2: one shared row, 3: per row
   auto len_of = [&](int64_t i) { return q.lengths ? q.lengths[i] : q.L; };
   auto nlen_of = [&](int64_t i) { return q.xn_lengths ? q.xn_lengths[i] : q.Ln; };
@@ -375,8 +449,8 @@ int run(RwState** sp, const RgCtx& c, int kbox, const Call& q, int64_t max_ws, h
       Sizer zn = z;
       if (noise_mode == 1) zn.add_noise(c, 1 + len_of(i1) / H);
       if (noise_mode == 3) zn.add_noise(c, 1 + nlen_of(i1) / H);
-      zn.add_row(c, 1 + len_of(i1) / H, q.bwd ? q.L : Lq, q.bwd);
-      if (i1 > i0 && (int64_t)zn.layout(c, q.bwd).total > max_ws) break;
+      zn.add_row(c, 1 + len_of(i1) / H, spec_fwd ? 0 : (q.bwd ? q.L : Lq), q.bwd, spec_fwd ? Tfull : 1 + len_of(i1) / H);
+      if (i1 > i0 && (int64_t)zn.layout(c, q.bwd, spec_fwd).total > max_ws) break;
       if (zn.nu > INT32_MAX - 1) break;
       z = zn;
       ++i1;
@@ -397,8 +471,8 @@ int run(RwState** sp, const RgCtx& c, int kbox, const Call& q, int64_t max_ws, h
       U.x_off = i * q.x_stride;
       U.T = 1 + len / H;
       U.len = q.bwd ? H * (len / H) : len;
-      U.Lout = q.bwd ? len : H * (len / H);
-      U.full = q.bwd ? q.L : Lq;
+      U.Lout = spec_fwd ? 0 : (q.bwd ? len : H * (len / H));
+      U.full = spec_fwd ? 0 : (q.bwd ? q.L : Lq);
       U.out_off = i * q.out_stride;
       U.frow = frows; frows += U.T;
       U.mask_off = i * Tfull * c.FS;
@@ -427,7 +501,7 @@ int run(RwState** sp, const RgCtx& c, int kbox, const Call& q, int64_t max_ws, h
     for (int64_t u = 0; u < nfwd; ++u) tl.push_ranges(u, 0, rows[u].T, RPT);
     A.n_fs = tl.count_since(A.t_fs);
     A.t_ap = tl.begin_stage();
-    for (int64_t u = 0; u < nu; ++u) tl.push_ranges(u, 0, rows[u].T, FPT);
+    for (int64_t u = 0; u < nu; ++u) tl.push_ranges(u, 0, spec_fwd ? Tfull : rows[u].T, FPT);
     A.n_ap = tl.count_since(A.t_ap);
     A.t_ola = tl.begin_stage();
     for (int64_t u = 0; u < nu; ++u) tl.push_ranges(u, 0, rows[u].full, 256);
@@ -437,7 +511,7 @@ int run(RwState** sp, const RgCtx& c, int kbox, const Call& q, int64_t max_ws, h
       *err = std::string(who) + ": internal error: sub-batch tables disagree with their size estimate";
       return SG_E_STATE;
     }
-    const Layout Ly = z.layout(c, q.bwd);
+    const Layout Ly = z.layout(c, q.bwd, spec_fwd);
     int rc = grow_device_buffer(&S->ws, &S->ws_bytes, Ly.total, st, who, "workspace", err);
     if (rc) return rc;
     char* w = (char*)S->ws;
@@ -473,8 +547,13 @@ int run(RwState** sp, const RgCtx& c, int kbox, const Call& q, int64_t max_ws, h
       if (e == hipSuccess && !c.stationary) { Prof pr(c, SG_STAGE_RG_IIR, st); e = launch_flat_kernel(k_rw_box, A.n_box, 64, st, A); }
       if (e == hipSuccess) { Prof pr(c, SG_STAGE_RG_FSMOOTH, st); e = launch_flat_kernel(k_rw_fsmooth, A.n_fs, 256, st, A); }
     }
-    if (e == hipSuccess) { Prof pr(c, SG_STAGE_RG_APPLY, st); e = dispatch_N(c.N, [&](auto n) { return launch_tile_kernel<n()>(k_rw_apply<n()>, A.n_ap, st, A); }); }
-    if (e == hipSuccess) { Prof pr(c, SG_STAGE_RG_OLA, st); e = launch_flat_kernel(k_rw_ola, A.n_ola, 256, st, A); }
+    if (e == hipSuccess) {
+      Prof pr(c, SG_STAGE_RG_APPLY, st);
+      if (spec_fwd) e = dispatch_N(c.N, [&](auto n) { return launch_tile_kernel<n()>(k_rw_spec<n()>, A.n_ap, st, A); });
+      else if (q.spec) e = dispatch_N(c.N, [&](auto n) { return launch_tile_kernel<n()>(k_rw_spec_bwd<n()>, A.n_ap, st, A); });
+      else e = dispatch_N(c.N, [&](auto n) { return launch_tile_kernel<n()>(k_rw_apply<n()>, A.n_ap, st, A); });
+    }
+    if (e == hipSuccess && !spec_fwd) { Prof pr(c, SG_STAGE_RG_OLA, st); e = launch_flat_kernel(k_rw_ola, A.n_ola, 256, st, A); }
     if (e != hipSuccess) {
       *err = std::string(who) + ": launch failed: " + hipGetErrorString(e);
       return SG_E_HIP;
@@ -498,7 +577,7 @@ int rw_process(RwState** sp, const RgCtx& c, int kbox, const void* x_dev, int dt
   if (use_xn && (rc = check_lengths(c, who, "xn_lengths", xn_lengths, Bn, Ln, err))) return rc;
   if (!c.stationary && kbox < 1) { *err = std::string(who) + ": n_movemean must be at least 1"; return SG_E_INVALID; }
   Call q{};
-  q.bwd = false;
+  q.bwd = false; q.spec = false;
   q.x = x_dev; q.dtype = dtype; q.B = B; q.L = L; q.x_stride = x_stride; q.lengths = lengths;
   q.xn = use_xn ? xn_dev : nullptr; q.Bn = Bn; q.Ln = Ln; q.xn_stride = xn_stride; q.xn_lengths = use_xn ? xn_lengths : nullptr;
   q.out = out_dev; q.out_dtype = out_dtype; q.out_stride = out_stride;
@@ -514,8 +593,43 @@ int rw_backward(RwState** sp, const RgCtx& c, const void* go_dev, int dtype, int
   int rc = check_lengths(c, who, "lengths", lengths, B, L, err);
   if (rc) return rc;
   Call q{};
-  q.bwd = true;
+  q.bwd = true; q.spec = false;
   q.x = go_dev; q.dtype = dtype; q.B = B; q.L = L; q.x_stride = go_stride; q.lengths = lengths;
+  q.out = gx_dev; q.out_dtype = dtype; q.out_stride = gx_stride;
+  q.mask_in = mask;
+  return run(sp, c, 0, q, max_ws, st, who, err);
+}
+
+int rw_spectrum(RwState** sp, const RgCtx& c, int kbox, const void* x_dev, int dtype, int64_t B, int64_t L, int64_t x_stride,
+                const int64_t* lengths, const void* xn_dev, int64_t Bn, int64_t Ln, int64_t xn_stride,
+                const int64_t* xn_lengths, void* spec_dev, float* mask_out, int64_t max_ws, hipStream_t st,
+                std::string* err) {
+  const char* who = "sg_gate_spectrum_rows";
+  if (!geom_ok(c, who, err)) return SG_E_UNSUPPORTED;
+  int rc = check_lengths(c, who, "lengths", lengths, B, L, err);
+  if (rc) return rc;
+  const bool use_xn = xn_dev && c.stationary;
+  if (use_xn && (rc = check_lengths(c, who, "xn_lengths", xn_lengths, Bn, Ln, err))) return rc;
+  if (!c.stationary && kbox < 1) { *err = std::string(who) + ": n_movemean must be at least 1"; return SG_E_INVALID; }
+  Call q{};
+  q.bwd = false; q.spec = true;
+  q.x = x_dev; q.dtype = dtype; q.B = B; q.L = L; q.x_stride = x_stride; q.lengths = lengths;
+  q.xn = use_xn ? xn_dev : nullptr; q.Bn = Bn; q.Ln = Ln; q.xn_stride = xn_stride; q.xn_lengths = use_xn ? xn_lengths : nullptr;
+  q.out = spec_dev; q.out_dtype = dtype; q.out_stride = (1 + L / c.H) * (int64_t)c.F;
+  q.mask_out = mask_out; q.mask_in = nullptr;
+  return run(sp, c, kbox, q, max_ws, st, who, err);
+}
+
+int rw_spectrum_backward(RwState** sp, const RgCtx& c, const void* gs_dev, int dtype, int64_t B, int64_t L,
+                         const int64_t* lengths, const float* mask, void* gx_dev, int64_t gx_stride, int64_t max_ws,
+                         hipStream_t st, std::string* err) {
+  const char* who = "sg_gate_spectrum_rows_backward";
+  if (!geom_ok(c, who, err)) return SG_E_UNSUPPORTED;
+  int rc = check_lengths(c, who, "lengths", lengths, B, L, err);
+  if (rc) return rc;
+  Call q{};
+  q.bwd = true; q.spec = true;
+  q.x = gs_dev; q.dtype = dtype; q.B = B; q.L = L; q.x_stride = (1 + L / c.H) * (int64_t)c.F; q.lengths = lengths;
   q.out = gx_dev; q.out_dtype = dtype; q.out_stride = gx_stride;
   q.mask_in = mask;
   return run(sp, c, 0, q, max_ws, st, who, err);

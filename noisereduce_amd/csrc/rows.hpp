@@ -1,5 +1,6 @@
-// Padded batches of different-length rows (sg_process_rows / sg_process_rows_backward, mi355gate.h): TorchGate.forward
-// on a (B, L) tensor whose row i holds lengths[i] samples of audio and padding after them.
+// Padded batches of different-length rows (sg_process_rows / sg_process_rows_backward, sg_gate_spectrum_rows /
+// sg_gate_spectrum_rows_backward, mi355gate.h): TorchGate.forward and TorchGate.gated_stft on a (B, L) tensor whose row
+// i holds lengths[i] samples of audio and padding after them.
 //
 // sg_process_batch takes one Geom per launch -- one length and one frame count for every row.  Here every row has its
 // own length, frame count T_i = 1 + len_i / hop and output length hop * (len_i / hop), and every kernel finds its work
@@ -31,6 +32,19 @@ int rw_process(RwState** sp, const RgCtx& c, int kbox, const void* x_dev, int dt
 int rw_backward(RwState** sp, const RgCtx& c, const void* go_dev, int dtype, int64_t B, int64_t L, int64_t go_stride,
                 const int64_t* lengths, const float* mask, void* gx_dev, int64_t gx_stride, int64_t max_ws,
                 hipStream_t st, std::string* err);
+// The gated spectrogram of the padded batch (sg_gate_spectrum_rows): rw_process up to and including the mask smoothing
+// along frequency -- the same launches with the same arguments, so mask_out holds the same bits -- then X * mask stored
+// as spec [B][1 + L / H][F] complex of `dtype` instead of the inverse transform and the overlap-add.  Frames at or beyond
+// T_i are stored as zeros; nothing is loaded for them.
+int rw_spectrum(RwState** sp, const RgCtx& c, int kbox, const void* x_dev, int dtype, int64_t B, int64_t L, int64_t x_stride,
+                const int64_t* lengths, const void* xn_dev, int64_t Bn, int64_t Ln, int64_t xn_stride,
+                const int64_t* xn_lengths, void* spec_dev, float* mask_out, int64_t max_ws, hipStream_t st,
+                std::string* err);
+// its adjoint with the mask fixed: grad_spec [B][1 + L / H][F] complex of dtype -> grad_x (B, L), zero at and beyond
+// lengths[i]; frames at or beyond T_i of grad_spec are never read.  No envelope division, no atomics.
+int rw_spectrum_backward(RwState** sp, const RgCtx& c, const void* gs_dev, int dtype, int64_t B, int64_t L,
+                         const int64_t* lengths, const float* mask, void* gx_dev, int64_t gx_stride, int64_t max_ws,
+                         hipStream_t st, std::string* err);
 // sub-batches the last call was split into
 int64_t rw_last_batches(const RwState* s);
 

@@ -211,19 +211,53 @@ __device__ __forceinline__ double mask_nonstationary(const TileConsts& C, double
   return (K / C.ktot) * C.prop + (1.0 - C.prop);
 }
 
+// ---- the merge half of a masked inverse: the Hermitian half Y[0 .. N] of a length-2N real frame's spectrum back into
+// the packed half-size spectrum in buf, inverse transform, synthesis window.  Shared by mask_and_invert (Y = X * mask)
+// and the adjoint of the gated spectrogram (Y = grad * mask, rows.hip's k_rw_spec_bwd).
+// bins 0 and N, both real, into packed element 0
+__device__ __forceinline__ void merge_dc_nyquist(cx<double>* buf, double y0, double yN) {
+  buf[lp<double>(0)] = {0.5 * (y0 + yN), 0.5 * (y0 - yN)};
+}
+// bins k and N - k (0 < k <= N / 2; w = w_2N^k) into packed elements k and N - k
+__device__ __forceinline__ void merge_bin_pair(cx<double>* buf, int k, int N, cx<double> Yk, cx<double> Yn, cx<double> w) {
+  cx<double> Ep = {(Yk.x + Yn.x) * 0.5, (Yk.y - Yn.y) * 0.5};
+  cx<double> D = {(Yk.x - Yn.x) * 0.5, (Yk.y + Yn.y) * 0.5};
+  cx<double> wc = {w.x, -w.y};
+  cx<double> Op = cmul(D, wc);
+  buf[lp<double>(k)] = {Ep.x - Op.y, Ep.y + Op.x};
+  if (k != N - k) buf[lp<double>(N - k)] = {Ep.x + Op.y, -Ep.y + Op.x};
+}
+// the merged spectrum in buf (every lane has written its elements) -> un-normalised inverse transform -> window * scale,
+// the frame's n samples to seg_row in its element type ST (float32 rounds them once; float64 -- an exact stream bank --
+// keeps them: same lane-to-sample mapping, double2 stores)
+template <int N, class ST = float>
+__device__ __forceinline__ void invert_and_window(cx<double>* buf, const cx<double>* tw, int lane, const double* wfull,
+                                                  const double inv, ST* seg_row) {
+  constexpr int NT = tile_nt<N>(), SY = tile_sy<N>();
+  team_sync<SY>();
+  wave_fft<double, N, true, NT, SY>(buf, tw, lane);
+  for (int j = lane; j < N; j += NT) {
+    const cx<double> z = buf[lp<double>(j)];
+    if constexpr (std::is_same<ST, double>::value)
+      reinterpret_cast<double2*>(seg_row)[j] = make_double2(z.x * wfull[2 * j] * inv, z.y * wfull[2 * j + 1] * inv);
+    else
+      reinterpret_cast<float2*>(seg_row)[j] = make_float2((float)(z.x * wfull[2 * j] * inv), (float)(z.y * wfull[2 * j + 1] * inv));
+  }
+  team_sync<SY>();
+}
+
 // the packed transform of a real frame in buf times mask_at(k), k = 0 .. N (split / mask / merge; mask_at is called
-// once per band), inverse transform, synthesis window, the frame's n samples to seg_row in its element type ST (float32
-// rounds them once; float64 -- an exact stream bank -- keeps them: same lane-to-sample mapping, double2 stores)
+// once per band), inverse transform (1 / N), synthesis window, the frame's n samples to seg_row
 template <int N, class ST = float, class MaskAt>
 __device__ __forceinline__ void mask_and_invert(cx<double>* buf, const cx<double>* tw, int lane, MaskAt&& mask_at,
                                                 const double* wfull, ST* seg_row) {
-  constexpr int NT = tile_nt<N>(), SY = tile_sy<N>();
+  constexpr int NT = tile_nt<N>();
   for (int k = lane; k <= N / 2; k += NT) {
     if (k == 0) {
       cx<double> a = buf[lp<double>(0)];
       const double y0 = (a.x + a.y) * mask_at(0);
       const double yN = (a.x - a.y) * mask_at(N);
-      buf[lp<double>(0)] = {0.5 * (y0 + yN), 0.5 * (y0 - yN)};
+      merge_dc_nyquist(buf, y0, yN);
     } else {
       cx<double> a = buf[lp<double>(k)], b = buf[lp<double>(N - k)];
       cx<double> w = tw[k];
@@ -233,25 +267,30 @@ __device__ __forceinline__ void mask_and_invert(cx<double>* buf, const cx<double
       const double mk = mask_at(k), mn = (k != N - k) ? mask_at(N - k) : mk;
       cx<double> Yk = {(E.x + wO.x) * mk, (E.y + wO.y) * mk};
       cx<double> Yn = {(E.x - wO.x) * mn, (-E.y + wO.y) * mn};
-      cx<double> Ep = {(Yk.x + Yn.x) * 0.5, (Yk.y - Yn.y) * 0.5};
-      cx<double> D = {(Yk.x - Yn.x) * 0.5, (Yk.y + Yn.y) * 0.5};
-      cx<double> wc = {w.x, -w.y};
-      cx<double> Op = cmul(D, wc);
-      buf[lp<double>(k)] = {Ep.x - Op.y, Ep.y + Op.x};
-      if (k != N - k) buf[lp<double>(N - k)] = {Ep.x + Op.y, -Ep.y + Op.x};
+      merge_bin_pair(buf, k, N, Yk, Yn, w);
     }
   }
-  team_sync<SY>();
-  wave_fft<double, N, true, NT, SY>(buf, tw, lane);
-  const double inv = 1.0 / (double)N;
-  for (int j = lane; j < N; j += NT) {
-    const cx<double> z = buf[lp<double>(j)];
-    if constexpr (std::is_same<ST, double>::value)
-      reinterpret_cast<double2*>(seg_row)[j] = make_double2(z.x * wfull[2 * j] * inv, z.y * wfull[2 * j + 1] * inv);
-    else
-      reinterpret_cast<float2*>(seg_row)[j] = make_float2((float)(z.x * wfull[2 * j] * inv), (float)(z.y * wfull[2 * j + 1] * inv));
+  invert_and_window<N, ST>(buf, tw, lane, wfull, 1.0 / (double)N, seg_row);
+}
+
+// the adjoint frame of Y = mask .* rfft(window * frame) with the mask fixed: Y[k] = m[k] g[k] for
+// 0 < k < N, Y[0] = 2 m[0] Re g[0], Y[N] = 2 m[N] Re g[N] read as a Hermitian half, merged, inverted WITHOUT the 1 / N
+// and windowed: seg_row[j] = window[j] Re sum_{k=0}^{N} m[k] g[k] e^{+2 pi i k j / 2N}, every bin with weight 1.
+// grad_at(k) -> cx<double>, mask_at(k) -> double; each is called once per band.  No envelope division.
+template <int N, class ST = float, class GradAt, class MaskAt>
+__device__ __forceinline__ void mask_and_adjoint(cx<double>* buf, const cx<double>* tw, int lane, GradAt&& grad_at,
+                                                 MaskAt&& mask_at, const double* wfull, ST* seg_row) {
+  constexpr int NT = tile_nt<N>();
+  for (int k = lane; k <= N / 2; k += NT) {
+    if (k == 0) {
+      merge_dc_nyquist(buf, 2.0 * grad_at(0).x * mask_at(0), 2.0 * grad_at(N).x * mask_at(N));
+    } else {
+      const cx<double> gk = grad_at(k), gn = (k != N - k) ? grad_at(N - k) : gk;
+      const double mk = mask_at(k), mn = (k != N - k) ? mask_at(N - k) : mk;
+      merge_bin_pair(buf, k, N, {gk.x * mk, gk.y * mk}, {gn.x * mn, gn.y * mn}, tw[k]);
+    }
   }
-  team_sync<SY>();
+  invert_and_window<N, ST>(buf, tw, lane, wfull, 1.0, seg_row);
 }
 
 // frames [t_lo, t_hi] of a T-frame signal whose `span` samples cover extended position e (= output position + padL)

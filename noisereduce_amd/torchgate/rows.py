@@ -1,4 +1,5 @@
-"""Host-side planning for ``TorchGate.forward(x, lengths=...)``: padded batches whose rows end at different samples.
+"""Host-side planning for ``TorchGate.forward(x, lengths=...)`` and ``TorchGate.gated_stft(x, lengths=...)``: padded
+batches whose rows end at different samples.
 
 Pure Python / numpy (no GPU, no library): what each row's own STFT geometry is, which lengths are acceptable, and
 whether a call is in fact a full-length batch that today's kernels already gate.
@@ -44,5 +45,6 @@ def all_full(lengths, L):
 
 
 def native(n_fft):
-    """True when csrc/rows.hip gates this n_fft in one table-driven call; otherwise forward loops over the rows."""
+    """True when csrc/rows.hip gates this n_fft in one table-driven call; otherwise forward / gated_stft loop over the
+    rows."""
     return int(n_fft) in NATIVE_N_FFT

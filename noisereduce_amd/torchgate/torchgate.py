@@ -79,6 +79,29 @@ class _SpectrumFunction(torch.autograd.Function):
         return gx, None, None
 
 
+class _SpectrumRowsFunction(torch.autograd.Function):
+    """gated_stft(x, lengths=...) on the table-driven kernels (sg_gate_spectrum_rows): real pairs (B, T, F, 2) and the
+    mask, as _SpectrumFunction; ``lengths`` / ``xn_lengths`` are host int64 arrays (or None) and the backward gets the
+    same lengths."""
+
+    @staticmethod
+    def forward(ctx, x, xn, module, lengths, xn_lengths):
+        gate = module._gate_for(x.device)
+        pairs, mask = gate.gate_spectrum_rows(x.detach(), lengths, xn, xn_lengths, save_mask=True)
+        ctx.gate = gate
+        ctx.L = x.shape[-1]
+        ctx.lengths = lengths
+        ctx.save_for_backward(mask)
+        ctx.mark_non_differentiable(mask)
+        return pairs, mask
+
+    @staticmethod
+    def backward(ctx, grad_pairs, _grad_mask):
+        (mask,) = ctx.saved_tensors
+        gx = ctx.gate.gate_spectrum_rows_backward(grad_pairs.contiguous(), mask, ctx.L, ctx.lengths)
+        return gx, None, None, None, None
+
+
 class TorchGate(torch.nn.Module):
     """A PyTorch module that applies a spectral gate to an input signal (see the reference
     docstring, torchgate.py:8-29, for the arguments)."""
@@ -195,7 +218,16 @@ class TorchGate(torch.nn.Module):
         y = _GateFunction.apply(x, xn, self)
         return y.to(dtype=dtype)
 
-    def gated_stft(self, x: torch.Tensor, xn: Optional[torch.Tensor] = None, return_mask: bool = False):
+    def stft_lengths(self, lengths):
+        """Frames each row of a padded batch owns, ``1 + lengths // hop_length`` (``torch.stft(center=True)`` on the row
+        alone): the frames of ``gated_stft(x, lengths=lengths)`` that carry the row, the rest being zero.  A tensor
+        gives an int64 tensor on its device; a sequence or numpy array gives an int64 numpy array."""
+        if isinstance(lengths, torch.Tensor):
+            return 1 + torch.div(lengths.to(torch.int64), self.hop_length, rounding_mode="floor")
+        return 1 + _rows.as_lengths(lengths, len(lengths)) // int(self.hop_length)
+
+    def gated_stft(self, x: torch.Tensor, xn: Optional[torch.Tensor] = None, return_mask: bool = False, lengths=None,
+                   xn_lengths=None):
         """The gated spectrogram ``Y = X * sig_mask`` that the reference multiplies on the line before its ``torch.istft``
         (torchgate.py:223-252) -- for log-mel features, spectral losses or an enhancement front end, without the inverse
         transform of ``forward`` and a further STFT.
@@ -211,8 +243,20 @@ class TorchGate(torch.nn.Module):
 
         Power-of-two n_fft from 256 to 4096 run on the native kernels (sg_gate_spectrum, csrc/spec.hip).  Any other
         n_fft takes the composed, slow route: ``torch.stft(x) * mask`` with the mask of the full-length path and torch
-        autograd for the backward."""
+        autograd for the backward.
+
+        lengths / xn_lengths: as in ``forward``, for a zero-padded batch.  With ``T_i = 1 + lengths[i] // hop_length``
+        (``stft_lengths``), ``Y[i, :, :T_i]`` is what ``gated_stft(x[i:i+1, :lengths[i]], xn_i)`` returns -- band
+        statistics, moving mean, mask smoothing and the -top_db floor over the row's own frames, a frame seeing zeros
+        at and beyond ``lengths[i]`` -- and ``Y[i, :, T_i:]`` (and the mask there) is 0.  The padding is never read, a
+        row does not depend on the other rows, the gradient is that of the row alone up to ``lengths[i]`` and 0 after
+        it, and the gradient of ``Y[i, :, T_i:]`` is ignored.  When every length equals the padded length the call is
+        bitwise ``gated_stft(x, xn)``.  Power-of-two n_fft from 256 to 4096 gate the whole batch in a fixed number of
+        launches (sg_gate_spectrum_rows, csrc/rows.hip: float64 transforms, so complex128 is stored unrounded and
+        complex64 rounded once); any other n_fft makes one ``gated_stft`` call per row (correct, slow)."""
         assert x.ndim == 2
+        if lengths is not None or xn_lengths is not None:
+            return self._gated_stft_rows(x, xn, return_mask, lengths, xn_lengths)
         if x.shape[-1] < self.win_length * 2:
             raise Exception(f"x must be bigger than {self.win_length * 2}")
         assert xn is None or xn.ndim == 1 or xn.ndim == 2
@@ -243,11 +287,14 @@ class TorchGate(torch.nn.Module):
         Y = Yt.transpose(1, 2)
         return (Y, mask[:, :, :F].transpose(1, 2)) if return_mask else Y
 
-    def _forward_rows(self, x, xn, lengths, xn_lengths):
-        """forward with per-row lengths: validation, then the full-length path (every row full), the table-driven
-        kernels, or -- for an n_fft they are not built for -- one full-length call per row."""
+    def _check_rows(self, x, xn, lengths, xn_lengths, xn_rows=False):
+        """Validation of a call with per-row lengths (forward and gated_stft alike), before any device work: the
+        lengths as host int64 arrays (or None).  xn_rows: refuse a noise batch of neither 1 nor B rows here, whether
+        or not xn_lengths came with it (forward leaves that case to the engine)."""
         assert xn is None or xn.ndim == 1 or xn.ndim == 2
         B, L = x.shape
+        if xn_rows and xn is not None and xn.ndim == 2 and xn.shape[0] not in (1, B):
+            raise ValueError(f"xn rows ({xn.shape[0]}) must be 1 or the batch size")
         if L < self.win_length * 2:
             raise Exception(f"x must be bigger than {self.win_length * 2}")
         if xn is not None and xn.shape[-1] < self.win_length * 2:
@@ -266,6 +313,55 @@ class TorchGate(torch.nn.Module):
         if x.device.type != "cuda":
             raise RuntimeError("noisereduce_amd.TorchGate runs on the GPU only (no CPU fallback): "
                                "move the input with x.to('cuda')")
+        return lengths, xn_lengths
+
+    @staticmethod
+    def _noise_of_row(xn, xn_lengths, i):
+        """Row i's noise for a per-row call: its row of xn (or the shared one) cut at its own length."""
+        if xn is None:
+            return None
+        xi = xn if xn.ndim == 1 else xn[(i if xn.shape[0] > 1 else 0)][None]
+        if xn_lengths is not None:
+            xi = xi[..., :int(xn_lengths[i if len(xn_lengths) > 1 else 0])]
+        return xi
+
+    def _gated_stft_rows(self, x, xn, return_mask, lengths, xn_lengths):
+        """gated_stft with per-row lengths, routed as _forward_rows: the full-length path (every row full), the
+        table-driven kernels, or -- for an n_fft they are not built for -- one gated_stft call per row."""
+        lengths, xn_lengths = self._check_rows(x, xn, lengths, xn_lengths, xn_rows=True)
+        B, L = x.shape
+        if _rows.all_full(lengths, L) and (xn is None or _rows.all_full(xn_lengths, xn.shape[-1])):
+            return self.gated_stft(x, xn, return_mask)
+        F = self.n_fft // 2 + 1
+        if x.dtype not in (torch.float32, torch.float64):
+            x = x.float()
+        if not _rows.native(self.n_fft):
+            T = 1 + L // self.hop_length
+            Yt = torch.zeros((B, T, F), dtype=torch.complex64 if x.dtype == torch.float32 else torch.complex128,
+                             device=x.device)
+            mask = torch.zeros((B, T, F), dtype=torch.float32, device=x.device)
+            for i in range(B):
+                n = L if lengths is None else int(lengths[i])
+                Yi, Mi = self.gated_stft(x[i:i + 1, :n], self._noise_of_row(xn, xn_lengths, i), return_mask=True)
+                Yt[i, :Yi.shape[-1]] = Yi[0].transpose(0, 1)
+                mask[i, :Mi.shape[-1]] = Mi[0].transpose(0, 1)
+        else:
+            if xn is not None:
+                xn = xn.detach().to(device=x.device, dtype=x.dtype)
+                if xn.ndim == 1:
+                    xn = xn.unsqueeze(0)
+                if self.nonstationary:
+                    xn, xn_lengths = None, None  # unused by the non-stationary mask (torchgate.py:235-236)
+            pairs, mask = _SpectrumRowsFunction.apply(x, xn, self, lengths, xn_lengths)
+            Yt = torch.view_as_complex(pairs)
+        Y = Yt.transpose(1, 2)
+        return (Y, mask[:, :, :F].transpose(1, 2)) if return_mask else Y
+
+    def _forward_rows(self, x, xn, lengths, xn_lengths):
+        """forward with per-row lengths: validation, then the full-length path (every row full), the table-driven
+        kernels, or -- for an n_fft they are not built for -- one full-length call per row."""
+        lengths, xn_lengths = self._check_rows(x, xn, lengths, xn_lengths)
+        B, L = x.shape
         if _rows.all_full(lengths, L) and (xn is None or _rows.all_full(xn_lengths, xn.shape[-1])):
             return self.forward(x, xn)
         if not _rows.native(self.n_fft):
@@ -273,12 +369,7 @@ class TorchGate(torch.nn.Module):
             y = x.new_zeros((B, H * (L // H)))
             for i in range(B):
                 n = L if lengths is None else int(lengths[i])
-                xi = None
-                if xn is not None:
-                    xi = xn if xn.ndim == 1 else xn[(i if xn.shape[0] > 1 else 0)][None]
-                    if xn_lengths is not None:
-                        xi = xi[..., :int(xn_lengths[i if len(xn_lengths) > 1 else 0])]
-                y[i, :H * (n // H)] = self.forward(x[i:i + 1, :n], xi)[0]
+                y[i, :H * (n // H)] = self.forward(x[i:i + 1, :n], self._noise_of_row(xn, xn_lengths, i))[0]
             return y
         dtype = x.dtype
         if dtype not in (torch.float32, torch.float64):
