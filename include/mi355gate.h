@@ -230,6 +230,40 @@ SG_API int sg_stream_set_threshold(sg_stream_bank* b, const int32_t* slots, int3
  * Every argument is checked before any device work; enqueues only. */
 SG_API int sg_stream_push(sg_stream_bank* b, const void* in_dev, int in_dtype, void* out_dev, int out_dtype,
                           const sg_stream_rec* recs, int32_t n_recs, void* stream);
+/* One step that also hands out the gated spectrogram: sg_stream_push -- same records, same checks, same four launches,
+ * bitwise the same audio in out_dev and the same state afterwards -- plus, for every frame the step applies, the frame's
+ * gated spectrum Y[t, k] = Z[t, k] * mask[t, k], k = 0 .. n_fft / 2: the very product the step inverts, stored on its way
+ * to the inverse transform.  With F = n_fft / 2 + 1, h = win_length / 2, nt and L as above (L = 0 on a stationary bank):
+ *   - after n samples a stream has applied A(n) = max(0, floor((n + h - win_length) / hop) - nt - L + 1) frames
+ *     (sg_stream_bank_frames: host arithmetic; E(n) = max(0, A(n) * hop - h)).  Record i reports the A(n + n_samples) -
+ *     A(n) newly applied ones; a flush reports all remaining ones up to T = (N + 2 h - win_length) / hop + 1, N the
+ *     stream's length.  After any sequence of steps the reported frames of a stream, concatenated, are frames 0 .. A(n) -
+ *     1 (0 .. T - 1 after the flush); frame t is the frame of samples [t * hop - h, t * hop - h + win_length), zeros
+ *     outside the stream.  Frames that pass in a plain sg_stream_push step are simply not reported: the two kinds of
+ *     step mix freely.
+ *   - Z is scipy.signal.stft's transform of the whole signal (window scaled by 1 / sum(window), padding = 0) and mask the
+ *     final mask the audio is gated with: each frame is the offline Z * mask, with the causal -top_db floor (and, on a
+ *     non-stationary bank, the bounded lookahead) exactly as for the audio.  The mask is evaluated once per band in
+ *     float64 and Y is the float64 product rounded once to spec_dtype; bins 0 and n_fft / 2 carry an imaginary part of
+ *     +0.0.  scipy.signal.istft of the concatenated frames is the concatenated audio.
+ *   - Y and mask do not depend, bitwise, on the block split, the slot, the other streams of the step, or on whether
+ *     earlier steps were sg_stream_push or sg_stream_push_spectrum; sg_stream_export / sg_stream_import between spectrum
+ *     steps continue them bit for bit (the payload does not change).
+ * spec_dev holds complex values of spec_dtype's real type (SG_F32: float pairs, SG_F64: double pairs; any bank kind);
+ * mask_dev, which may be NULL, reals of that type.  spec_recs[i] places record i's frames: frame j of channel c goes to
+ * elements spec_offset + c * stride + j * F + k of spec_dev (complex elements) and mask_offset + c * stride + j * F + k of
+ * mask_dev, rows of F bins one after the other; stride >= frames * F for a multichannel bank.  Nothing else is written.
+ * Every argument is checked before any device work; enqueues only; counters commit at enqueue. */
+typedef struct sg_stream_spec_rec {   /* where one stream's newly applied frames go */
+  int64_t spec_offset;     /* element (complex) of spec_dev holding bin 0 of channel 0's first new frame */
+  int64_t mask_offset;     /* element (real) of mask_dev holding the same cell's mask; ignored when mask_dev is NULL */
+  int64_t stride;          /* elements from a channel's first new frame to the next channel's, in both buffers */
+} sg_stream_spec_rec;
+SG_API int sg_stream_push_spectrum(sg_stream_bank* b, const void* in_dev, int in_dtype, void* out_dev, int out_dtype,
+                                   void* spec_dev, int spec_dtype, void* mask_dev, const sg_stream_rec* recs,
+                                   const sg_stream_spec_rec* spec_recs, int32_t n_recs, void* stream);
+/* A(n) of the bank (nt + L): the frames a stream has applied after n samples.  Host arithmetic only. */
+SG_API int sg_stream_bank_frames(const sg_stream_bank* b, int64_t n, int64_t* frames);
 /* Empties the listed slots (their thresholds stay). */
 SG_API int sg_stream_reset(sg_stream_bank* b, const int32_t* slots, int32_t n_slots, void* stream);
 /* E(n) for the handle's geometry; samples received / emitted so far on a slot.  Host arithmetic only. */

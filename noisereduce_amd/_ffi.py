@@ -88,6 +88,11 @@ class SgStreamRec(Structure):
                 ("in_stride", c_int64), ("out_offset", c_int64), ("out_stride", c_int64)]
 
 
+class SgStreamSpecRec(Structure):
+    """struct sg_stream_spec_rec (include/mi355gate.h): where one record's newly applied frames go."""
+    _fields_ = [("spec_offset", c_int64), ("mask_offset", c_int64), ("stride", c_int64)]
+
+
 SG_STREAM_FIXED, SG_STREAM_NONSTATIONARY, SG_STREAM_ADAPTIVE = 0, 1, 2
 
 
@@ -165,6 +170,9 @@ _PROTOTYPES = {
     "sg_stream_destroy": (c_int, [c_void_p]),
     "sg_stream_set_threshold": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p]),
     "sg_stream_push": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int32, c_void_p]),
+    "sg_stream_push_spectrum": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                        c_void_p, c_int32, c_void_p]),
+    "sg_stream_bank_frames": (c_int, [c_void_p, c_int64, POINTER(c_int64)]),
     "sg_stream_reset": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
     "sg_stream_emitted": (c_int, [c_void_p, c_int64, POINTER(c_int64)]),
     "sg_stream_counters": (c_int, [c_void_p, c_int32, POINTER(c_int64), POINTER(c_int64)]),
@@ -780,6 +788,31 @@ class Gate:
         with torch.cuda.device(self.device):
             self._check(self.lib.sg_stream_push(bank, x.data_ptr(), _sg_dtype(x), out.data_ptr(), _sg_dtype(out), arr,
                                                 len(recs), self._stream()))
+
+    def stream_push_spectrum(self, bank, x, out, spec, mask, recs, spec_recs):
+        """stream_push that also stores every newly applied frame's gated spectrum: spec a 1-D complex64 / complex128
+        device tensor, mask None or a 1-D real tensor of spec's real type, spec_recs a sequence of SgStreamSpecRec
+        parallel to recs.  Enqueues only."""
+        if spec.dtype not in (torch.complex64, torch.complex128):
+            raise TypeError(f"stream_push_spectrum: spec is complex64 or complex128 (got {spec.dtype})")
+        real = torch.float32 if spec.dtype == torch.complex64 else torch.float64
+        if mask is not None and mask.dtype != real:
+            raise TypeError(f"stream_push_spectrum: mask must be {real} next to a {spec.dtype} spec (got {mask.dtype})")
+        if len(spec_recs) != len(recs):
+            raise ValueError("stream_push_spectrum: recs and spec_recs must have the same length")
+        for t in (x, out, spec) + (() if mask is None else (mask,)):
+            self._on_device(t)
+        arr = (SgStreamRec * max(1, len(recs)))(*recs)
+        sarr = (SgStreamSpecRec * max(1, len(spec_recs)))(*spec_recs)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.sg_stream_push_spectrum(
+                bank, x.data_ptr(), _sg_dtype(x), out.data_ptr(), _sg_dtype(out), spec.data_ptr(),
+                _TORCH_DTYPES[real], None if mask is None else mask.data_ptr(), arr, sarr, len(recs), self._stream()))
+
+    def stream_bank_frames(self, bank, n):
+        v = c_int64(0)
+        self._check(self.lib.sg_stream_bank_frames(bank, int(n), byref(v)))
+        return v.value
 
     def stream_reset(self, bank, slots):
         sl = np.ascontiguousarray(np.asarray(slots, dtype=np.int32).reshape(-1))

@@ -3971,6 +3971,23 @@ extern "C" int sg_stream_push(sg_stream_bank* b, const void* in_dev, int in_dtyp
   return sg::st_push(b->b, in_dev, in_dtype, out_dev, out_dtype, recs, n_recs, (hipStream_t)stream, &h->err);
 }
 
+extern "C" int sg_stream_push_spectrum(sg_stream_bank* b, const void* in_dev, int in_dtype, void* out_dev, int out_dtype,
+                                       void* spec_dev, int spec_dtype, void* mask_dev, const sg_stream_rec* recs,
+                                       const sg_stream_spec_rec* spec_recs, int32_t n_recs, void* stream) {
+  if (!b) return SG_E_INVALID;
+  sg_handle* h = b->h;
+  if (n_recs < 0 || (n_recs > 0 && !recs) || !dtype_ok(in_dtype) || !dtype_ok(out_dtype))
+    FAIL(h, SG_E_INVALID, "sg_stream_push_spectrum: bad argument (float32 / float64 buffers)");
+  const sg::StSpecOut so{spec_dev, spec_dtype, mask_dev, spec_recs};
+  return sg::st_push(b->b, in_dev, in_dtype, out_dev, out_dtype, recs, n_recs, (hipStream_t)stream, &h->err, &so);
+}
+
+extern "C" int sg_stream_bank_frames(const sg_stream_bank* b, int64_t n, int64_t* frames) {
+  if (!b || !frames || n < 0) return SG_E_INVALID;
+  *frames = sg::st_bank_frames(b->b, n);
+  return SG_OK;
+}
+
 extern "C" int sg_stream_reset(sg_stream_bank* b, const int32_t* slots, int32_t n_slots, void* stream) {
   if (!b) return SG_E_INVALID;
   return sg::st_reset(b->b, slots, n_slots, (hipStream_t)stream, &b->h->err);

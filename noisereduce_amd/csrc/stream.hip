@@ -27,6 +27,9 @@
 // adaptive one keeps float R, which holds small integers there and is exact already.
 // State transfer (sg_stream_export / sg_stream_import) is two more kernels, k_st_export and k_st_import, outside the step: one
 // launch per call copies the live part of the listed slots' state to / from a canonical payload.
+// A spectrum step (sg_stream_push_spectrum) is the same four launches with k_st_apply<N, NS, EX, true> in the third place:
+// it also stores every applied frame's gated spectrum Y = Z * mask (and, on request, the mask row) to the caller's buffers
+// on its way to the inverse transform.  No state, workspace or stage of its own.
 // Nothing waits on another workgroup.  No workgroup reads state that another workgroup of the same launch writes: the
 // ring is only written by k_st_finish (which does not read it), the carry is double buffered, the bit rows of a unit are
 // written by its one decide workgroup.  One fixed evaluation order per frame and per output sample: a stream's output
@@ -65,6 +68,11 @@ struct StUnit {
   int32_t flush;
 };
 enum { ST_OLA = 0, ST_APPEND = 1, ST_CLEAR = 2 };   // Tile::kind of the finish stage
+// a unit's part of a spectrum step: the element of spec / smask holding bin 0 of its first newly applied frame (ta0 + 1);
+// the frames follow as consecutive rows of F bins
+struct StSpec {
+  int64_t spec_off, mask_off;
+};
 
 struct StArgs {
   const void* x; int in_dtype;
@@ -91,6 +99,11 @@ struct StArgs {
   double lam;      // forgetting factor per frame, (0, 1]
   int64_t learn;   // frames that update the statistics (negative: all of them)
   TileConsts c;
+  // spectrum steps (k_st_apply<.., true> alone reads these; they come last so that nothing above moves)
+  void* spec;        // gated spectra: float2, double2 for spec_dtype == SG_F64
+  void* smask;       // final mask rows in the real type of spec_dtype, or null
+  const StSpec* sp;  // [unit]
+  int spec_dtype;
 };
 
 // sample s of the stream: zeros before 0 and from n1 on, the ring below n0, the caller's block from n0 on
@@ -345,7 +358,12 @@ __global__ __launch_bounds__(256) void k_st_fsmooth(StArgs A) {
 
 // ---- applied frames: time smoothing, masked multiply, inverse transform ------------------------------------------------
 // EX: float64 segment rows; float64 smoothed rows too where the raw mask is the sigmoid (NS)
-template <int N, bool NS, bool EX>
+// SP: the frame's gated spectrum goes to the caller as well.  Y[t, k] = X[k] * mask * mag_scale is the product that is
+// merged and inverted, in scipy.signal.stft's scaling (1 / sum(window): the inverse folds that factor into its window,
+// the store applies it), rounded once to spec's type; the mask value is the float64 one of that product.  Bins 0 and
+// n_fft / 2 carry an imaginary part of +0.0.  A lane's bins are lane + NT i and N - (lane + NT i): consecutive lanes
+// store consecutive float2 / double2 of the row in both halves.
+template <int N, bool NS, bool EX, bool SP = false>
 __global__ __launch_bounds__(tile_nt<N>()) void k_st_apply(StArgs A) {
   using ST = typename std::conditional<EX, double, float>::type;
   using RT = typename std::conditional<EX && NS, double, float>::type;
@@ -364,7 +382,23 @@ __global__ __launch_bounds__(tile_nt<N>()) void k_st_apply(StArgs A) {
       const double K = time_smooth((const RT*)A.R, A.c.FS, [&](int64_t q) { return U.mrow + q - U.r0; }, tp, t, A.c.nt, k);
       return NS ? mask_nonstationary(A.c, K) : mask_stationary(A.c, K, tp.Et, k);
     };
-    mask_and_invert<N>(buf, tw, lane, mask_at, A.c.wfull, (ST*)A.seg + (U.srow + t - (U.ta0 + 1)) * (int64_t)A.c.n);
+    ST* seg_row = (ST*)A.seg + (U.srow + t - (U.ta0 + 1)) * (int64_t)A.c.n;
+    if constexpr (SP) {
+      const StSpec S = A.sp[tl.idx];
+      const int64_t row = (t - (U.ta0 + 1)) * (int64_t)A.c.F;
+      const bool wide = A.spec_dtype == SG_F64;
+      mask_and_invert<N>(buf, tw, lane, mask_at, A.c.wfull, seg_row, [&](int k, cx<double> Y, double m) {
+        const double re = Y.x * A.c.mag_scale, im = (k == 0 || k == N) ? 0.0 : Y.y * A.c.mag_scale;
+        if (wide) reinterpret_cast<double2*>(A.spec)[S.spec_off + row + k] = make_double2(re, im);
+        else reinterpret_cast<float2*>(A.spec)[S.spec_off + row + k] = make_float2((float)re, (float)im);
+        if (A.smask) {
+          if (wide) reinterpret_cast<double*>(A.smask)[S.mask_off + row + k] = m;
+          else reinterpret_cast<float*>(A.smask)[S.mask_off + row + k] = (float)m;
+        }
+      });
+    } else {
+      mask_and_invert<N>(buf, tw, lane, mask_at, A.c.wfull, seg_row);
+    }
   }
 }
 
@@ -632,7 +666,7 @@ int st_create(StBank** out, const RgCtx& c, int32_t n_slots, int32_t channels, i
   take((void**)&b->slot_list, (size_t)n_slots * 4, true);
   // tables and scratch of a typical step up front (a larger step grows them, which synchronises once)
   const int64_t mf = max_frames(c, max_block);
-  b->tabs_bytes = align256(nu * sizeof(StUnit)) + align256(nu * 16 * sizeof(Tile));
+  b->tabs_bytes = align256(nu * sizeof(StUnit)) + align256(nu * 16 * sizeof(Tile)) + align256(nu * sizeof(StSpec));
   take(&b->tabs, b->tabs_bytes, false);
   const size_t per_unit = align256((size_t)(mf + 2 * c.nt) * c.FS * (exact && ns ? 8 : 4)) + align256((size_t)mf * c.n * (exact ? 8 : 4));
   b->ws_bytes = std::min<size_t>(WS_PREALLOC, nu * per_unit);
@@ -724,6 +758,11 @@ int st_noise_profile(StBank* b, int32_t slot, double* thresh_host, hipStream_t s
 
 int64_t st_bank_emitted(const StBank* b, int64_t n) { return st_emitted(b->c.W, b->c.H, b->c.nt + b->L, n); }
 
+int64_t st_bank_frames(const StBank* b, int64_t n) {
+  const int64_t a = st_tdec(b->c.W, b->c.H, n) - b->c.nt - b->L + 1;
+  return a > 0 ? a : 0;
+}
+
 int st_counters(const StBank* b, int32_t slot, int64_t* n, int64_t* emitted, std::string* err) {
   if (slot < 0 || slot >= b->n_slots) { *err = "sg_stream_counters: unknown slot"; return SG_E_INVALID; }
   *n = b->slots[slot].n;
@@ -732,55 +771,73 @@ int st_counters(const StBank* b, int32_t slot, int64_t* n, int64_t* emitted, std
 }
 
 int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_dtype, const sg_stream_rec* recs,
-            int32_t n_recs, hipStream_t st, std::string* err) {
+            int32_t n_recs, hipStream_t st, std::string* err, const StSpecOut* so) {
   const RgCtx& c = b->c;
   const int h = c.W / 2;
+  const char* who = so ? "sg_stream_push_spectrum" : "sg_stream_push";
   char msg[200];
   // ---- every argument is checked before any device work or state change
   auto dtype_ok = [&](int d) { return d == SG_F32 || d == SG_F64 || (b->exact && (d == SG_I16 || d == SG_I32)); };
   if (!dtype_ok(in_dtype) || !dtype_ok(out_dtype)) {
-    *err = "sg_stream_push: bad argument (float32 / float64 buffers)";
+    *err = std::string(who) + ": bad argument (float32 / float64 buffers)";
+    return SG_E_INVALID;
+  }
+  if (so && ((so->dtype != SG_F32 && so->dtype != SG_F64) || (n_recs > 0 && (!so->spec || !so->recs)))) {
+    *err = std::string(who) + ": bad argument (spec_dev and spec_recs are needed; spec_dtype is SG_F32 or SG_F64)";
     return SG_E_INVALID;
   }
   std::vector<char> seen(b->n_slots, 0);
   for (int32_t i = 0; i < n_recs; ++i) {
     const sg_stream_rec& r = recs[i];
     if (r.slot < 0 || r.slot >= b->n_slots) {
-      snprintf(msg, sizeof msg, "sg_stream_push: record %d: unknown slot %d (the bank has %d)", i, r.slot, b->n_slots);
+      snprintf(msg, sizeof msg, "%s: record %d: unknown slot %d (the bank has %d)", who, i, r.slot, b->n_slots);
       *err = msg;
       return SG_E_INVALID;
     }
     if (seen[r.slot]) {
-      snprintf(msg, sizeof msg, "sg_stream_push: slot %d appears twice in one step", r.slot);
+      snprintf(msg, sizeof msg, "%s: slot %d appears twice in one step", who, r.slot);
       *err = msg;
       return SG_E_INVALID;
     }
     seen[r.slot] = 1;
     if (r.n_samples < 0 || r.n_samples > b->max_block) {
-      snprintf(msg, sizeof msg, "sg_stream_push: slot %d: block of %lld samples (max_block is %lld)", r.slot,
+      snprintf(msg, sizeof msg, "%s: slot %d: block of %lld samples (max_block is %lld)", who, r.slot,
                (long long)r.n_samples, (long long)b->max_block);
       *err = msg;
       return SG_E_INVALID;
     }
     if (r.in_offset < 0 || r.out_offset < 0 || (b->C > 1 && (r.in_stride < r.n_samples || r.out_stride < 0))) {
-      snprintf(msg, sizeof msg, "sg_stream_push: slot %d: bad offsets / strides", r.slot);
+      snprintf(msg, sizeof msg, "%s: slot %d: bad offsets / strides", who, r.slot);
       *err = msg;
       return SG_E_INVALID;
     }
     if (!b->slots[r.slot].has_thr) {
-      snprintf(msg, sizeof msg, "sg_stream_push: slot %d has no noise threshold yet", r.slot);
+      snprintf(msg, sizeof msg, "%s: slot %d has no noise threshold yet", who, r.slot);
       *err = msg;
       return SG_E_STATE;
     }
     if (r.flush && b->slots[r.slot].n + r.n_samples < c.W) {
-      snprintf(msg, sizeof msg, "sg_stream_push: slot %d: a stream of %lld samples is shorter than win_length=%d", r.slot,
+      snprintf(msg, sizeof msg, "%s: slot %d: a stream of %lld samples is shorter than win_length=%d", who, r.slot,
                (long long)(b->slots[r.slot].n + r.n_samples), c.W);
       *err = msg;
       return SG_E_INVALID;
     }
+    if (so) {
+      // (the frames the record reports: those the plan below applies -- the same arithmetic)
+      const StSlot& S = b->slots[r.slot];
+      const int64_t n1 = S.n + r.n_samples;
+      const int64_t ta1 = r.flush ? (n1 + 2 * (int64_t)h - c.W) / c.H : std::max(S.ta, st_bank_frames(b, n1) - 1);
+      const sg_stream_spec_rec& q = so->recs[i];
+      if (q.spec_offset < 0 || (so->mask && q.mask_offset < 0) || (b->C > 1 && q.stride < (ta1 - S.ta) * c.F)) {
+        snprintf(msg, sizeof msg, "%s: slot %d: bad spectrum offsets / stride", who, r.slot);
+        *err = msg;
+        return SG_E_INVALID;
+      }
+    }
   }
   // ---- plan
   std::vector<StUnit> units;
+  std::vector<StSpec> specs;
   std::vector<StSlot> after(n_recs);
   int64_t mrows = 0, sframes = 0;
   const int64_t UNBOUNDED = (int64_t)1 << 60;
@@ -826,6 +883,7 @@ int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_
       V.mrow = mrows; mrows += V.r1 - V.r0;
       V.srow = sframes; sframes += V.ta1 - V.ta0;
       units.push_back(V);
+      if (so) specs.push_back(StSpec{so->recs[i].spec_offset + ch * so->recs[i].stride, so->recs[i].mask_offset + ch * so->recs[i].stride});
     }
     StSlot& N = after[i];
     N.has_thr = true;
@@ -859,14 +917,16 @@ int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_
   A.n_fin = tl.count_since(A.t_fin);
   // ---- tables and scratch
   const size_t ub = align256(units.size() * sizeof(StUnit)), tb = align256(tl.tiles.size() * sizeof(Tile));
-  int rc = grow_device_buffer(&b->tabs, &b->tabs_bytes, ub + tb, st, "sg_stream_push", "table", err);
+  const size_t sb = align256(specs.size() * sizeof(StSpec));
+  int rc = grow_device_buffer(&b->tabs, &b->tabs_bytes, ub + tb + sb, st, who, "table", err);
   if (rc) return rc;
   const bool ex = b->exact != 0;
   const size_t Rb = align256((size_t)mrows * c.FS * (ex && b->ns ? 8 : 4)), Sb = align256((size_t)sframes * c.n * (ex ? 8 : 4));
-  if ((rc = grow_device_buffer(&b->ws, &b->ws_bytes, Rb + Sb, st, "sg_stream_push", "workspace", err))) return rc;
+  if ((rc = grow_device_buffer(&b->ws, &b->ws_bytes, Rb + Sb, st, who, "workspace", err))) return rc;
   if (upload_tables(b->tabs, st, {{units.data(), units.size() * sizeof(StUnit), ub},
-                                  {tl.tiles.data(), tl.tiles.size() * sizeof(Tile), tb}}) != hipSuccess) {
-    *err = "sg_stream_push: table upload failed";
+                                  {tl.tiles.data(), tl.tiles.size() * sizeof(Tile), tb},
+                                  {specs.data(), specs.size() * sizeof(StSpec), sb}}) != hipSuccess) {
+    *err = std::string(who) + ": table upload failed";
     return SG_E_HIP;
   }
   A.x = in_dev; A.in_dtype = in_dtype; A.out = out_dev; A.out_dtype = out_dtype;
@@ -878,6 +938,10 @@ int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_
   A.fst = b->fst; A.fa = b->fa; A.mk = b->mk; A.RF = b->RF; A.L = b->L;
   A.nst = b->nst; A.lam = b->lam; A.learn = b->learn;
   A.c = fill_consts(c);
+  if (so) {
+    A.spec = so->spec; A.smask = so->mask; A.spec_dtype = so->dtype;
+    A.sp = (const StSpec*)((char*)b->tabs + ub + tb);
+  }
   const bool ns = b->ns != 0;
   // ---- the step: the same four launches whatever was pushed
   hipError_t e = hipSuccess;
@@ -896,13 +960,17 @@ int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_
   if (e == hipSuccess) {
     Prof pr(c, SG_STAGE_RG_APPLY, st);
     e = dispatch_N(c.N, [&](auto n) {
+      if (so) {
+        if (ex) return ns ? launch_tile_kernel<n()>(k_st_apply<n(), true, true, true>, A.n_ap, st, A) : launch_tile_kernel<n()>(k_st_apply<n(), false, true, true>, A.n_ap, st, A);
+        return ns ? launch_tile_kernel<n()>(k_st_apply<n(), true, false, true>, A.n_ap, st, A) : launch_tile_kernel<n()>(k_st_apply<n(), false, false, true>, A.n_ap, st, A);
+      }
       if (ex) return ns ? launch_tile_kernel<n()>(k_st_apply<n(), true, true>, A.n_ap, st, A) : launch_tile_kernel<n()>(k_st_apply<n(), false, true>, A.n_ap, st, A);
       return ns ? launch_tile_kernel<n()>(k_st_apply<n(), true, false>, A.n_ap, st, A) : launch_tile_kernel<n()>(k_st_apply<n(), false, false>, A.n_ap, st, A);
     });
   }
   if (e == hipSuccess) { Prof pr(c, SG_STAGE_RG_OLA, st); e = launch_flat_kernel(ex ? k_st_finish<true> : k_st_finish<false>, A.n_fin, 256, st, A); }
   if (e != hipSuccess) {
-    *err = std::string("sg_stream_push: launch failed: ") + hipGetErrorString(e);
+    *err = std::string(who) + ": launch failed: " + hipGetErrorString(e);
     return SG_E_HIP;
   }
   for (int32_t i = 0; i < n_recs; ++i) b->slots[recs[i].slot] = after[i];

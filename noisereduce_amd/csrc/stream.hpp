@@ -58,12 +58,23 @@ int64_t st_state_bytes(const RgCtx& c, bool ns, int64_t n_slots, int64_t channel
 int st_noise_profile(StBank* b, int32_t slot, double* thresh_host, hipStream_t st, std::string* err);
 // samples a stream of this bank has emitted after n received: st_emitted with nt + lookahead
 int64_t st_bank_emitted(const StBank* b, int64_t n);
+// frames a stream of this bank has applied after n received: max(0, t_dec(n) - nt - lookahead + 1)
+int64_t st_bank_frames(const StBank* b, int64_t n);
 void st_destroy(StBank* b);
 // thresh_dev: F dB values on the device (the handle's); thresh_host: F dB values on the host; exactly one is non-null
 int st_set_threshold(StBank* b, const int32_t* slots, int32_t n, const double* thresh_dev, const double* thresh_host,
                      hipStream_t st, std::string* err);
+// what a spectrum step (sg_stream_push_spectrum) stores on top of a push: spec / mask buffers (mask may be null), the
+// element type of both (SG_F32: float2 / float, SG_F64: double2 / double), and the table parallel to the step's records
+struct StSpecOut {
+  void* spec;
+  int dtype;
+  void* mask;
+  const sg_stream_spec_rec* recs;
+};
+// so == nullptr: sg_stream_push.  Otherwise the same plan and launches, the apply launch in its spectrum-storing form
 int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_dtype, const sg_stream_rec* recs,
-            int32_t n_recs, hipStream_t st, std::string* err);
+            int32_t n_recs, hipStream_t st, std::string* err, const StSpecOut* so = nullptr);
 int st_reset(StBank* b, const int32_t* slots, int32_t n, hipStream_t st, std::string* err);
 int st_counters(const StBank* b, int32_t slot, int64_t* n, int64_t* emitted, std::string* err);
 // state transfer (sg_stream_export_bytes / _export / _import): `sig` carries the handle's part of the signature (the gate's

@@ -247,16 +247,28 @@ __device__ __forceinline__ void invert_and_window(cx<double>* buf, const cx<doub
 }
 
 // the packed transform of a real frame in buf times mask_at(k), k = 0 .. N (split / mask / merge; mask_at is called
-// once per band), inverse transform (1 / N), synthesis window, the frame's n samples to seg_row
-template <int N, class ST = float, class MaskAt>
+// once per band), inverse transform (1 / N), synthesis window, the frame's n samples to seg_row.  emit(k, Y, m) sees
+// every band's product Y[k] = X[k] * m -- the value that is merged and inverted, X unscaled -- and its mask value m
+// once: a lane's bands are k = lane + NT i ascending and N - k descending, so lanes hold consecutive bins either way
+// (the stream bank's spectrum store).  Bins 0 and N are real: their Y.y is +0.0.
+struct NoEmit {
+  __device__ __forceinline__ void operator()(int, cx<double>, double) const {}
+};
+template <int N, class ST = float, class MaskAt, class Emit = NoEmit>
 __device__ __forceinline__ void mask_and_invert(cx<double>* buf, const cx<double>* tw, int lane, MaskAt&& mask_at,
-                                                const double* wfull, ST* seg_row) {
+                                                const double* wfull, ST* seg_row, Emit&& emit = Emit()) {
   constexpr int NT = tile_nt<N>();
   for (int k = lane; k <= N / 2; k += NT) {
     if (k == 0) {
       cx<double> a = buf[lp<double>(0)];
-      const double y0 = (a.x + a.y) * mask_at(0);
-      const double yN = (a.x - a.y) * mask_at(N);
+      const double s0 = a.x + a.y;
+      const double m0 = mask_at(0);
+      const double y0 = s0 * m0;
+      const double sN = a.x - a.y;
+      const double mN = mask_at(N);
+      const double yN = sN * mN;
+      emit(0, cx<double>{y0, 0.0}, m0);
+      emit(N, cx<double>{yN, 0.0}, mN);
       merge_dc_nyquist(buf, y0, yN);
     } else {
       cx<double> a = buf[lp<double>(k)], b = buf[lp<double>(N - k)];
@@ -267,6 +279,8 @@ __device__ __forceinline__ void mask_and_invert(cx<double>* buf, const cx<double
       const double mk = mask_at(k), mn = (k != N - k) ? mask_at(N - k) : mk;
       cx<double> Yk = {(E.x + wO.x) * mk, (E.y + wO.y) * mk};
       cx<double> Yn = {(E.x - wO.x) * mn, (-E.y + wO.y) * mn};
+      emit(k, Yk, mk);
+      if (k != N - k) emit(N - k, Yn, mn);
       merge_bin_pair(buf, k, N, Yk, Yn, w);
     }
   }

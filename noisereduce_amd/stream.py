@@ -90,7 +90,28 @@ smoothing, lookahead, precision and gate parameters; another ``n_streams``, ``ma
 ``to_bytes`` / ``from_bytes``, process).  The stream goes on there bit for bit as it would have without the move; restoring
 one state twice forks a stream.  One launch per call, no host synchronisation for device states.
 
-Out of scope: ``TorchGate``, collectives between GPUs (a state's bytes are the transport), and ``n_fft`` other than a power
+``push_spectrum`` / ``flush_spectrum`` are ``push`` / ``flush`` that also hand out the gated spectrogram ``Y = Z * mask``, frame
+by frame: the product the step inverts, stored on its way to the inverse transform (sg_stream_push_spectrum; DESIGN section
+13e).  With ``lag = nt + lookahead_frames`` a stream has applied ``frames_applied(n, W, H, lag) = max(0, t_dec(n) - lag + 1)``
+frames after ``n`` samples (``emitted == max(0, frames * H - h)``); a step reports the newly applied ones, a flush all
+remaining ones up to ``T = (N + 2 h - W) // H + 1``.  The contract:
+
+* after any sequence of steps a stream's reported frames, concatenated, are frames ``0 .. A(n) - 1`` (``0 .. T - 1`` after the
+  flush); frame ``t`` is the frame of samples ``[t H - h, t H - h + W)``;
+* each frame is the offline ``Z * mask`` of the whole signal for ``padding=0`` -- ``Z`` scaled as ``scipy.signal.stft`` scales
+  it (``1 / sum(window)``), the mask evaluated once per band in float64, ``Y`` the float64 product rounded once to its type,
+  bins 0 and ``n_fft / 2`` with an imaginary part of exactly ``+0.0`` -- with the causal ``-top_db`` floor as the one designed
+  difference and a non-stationary bank's bounded lookahead exactly as for the audio; ``scipy.signal.istft`` of the concatenated
+  ``Y`` is the concatenated audio;
+* ``Y`` and ``mask`` are bitwise independent of the block split, the slot, the other streams of the step and their sample
+  types, and of whether earlier steps were ``push`` or ``push_spectrum`` (frames that pass in a ``push`` step are simply not
+  reported); the audio of a ``push_spectrum`` step is bitwise the audio of ``push``;
+* ``snapshot`` / ``restore`` between spectrum steps continues ``Y`` bit for bit; the payload does not change.
+
+``Y`` is complex64 for a float32 block and complex128 for a float64 / int16 / int32 one, on any bank kind: the transforms and
+the masks are float64 in every bank.  Same four launches per step, no host synchronisation for device tensors.
+
+Out of scope: spectrum-only steps that skip the inverse transform, gradients through a stream, ``TorchGate``, collectives between GPUs (a state's bytes are the transport), and ``n_fft`` other than a power
 of two from 256 to 4096 (``ValueError``).
 """
 import ctypes
@@ -119,6 +140,13 @@ def t_decided(n, W, H):
 def emitted(n, W, H, nt):
     """Samples a stream has emitted after receiving ``n`` (host arithmetic; no GPU)."""
     return max(0, (t_decided(n, W, H) - nt + 1) * H - W // 2)
+
+
+def frames_applied(n, W, H, lag):
+    """Frames a stream has applied -- gated, inverted and, in a spectrum step, reported -- after receiving ``n`` samples:
+    ``A(n) = max(0, t_dec(n) - lag + 1)``, ``lag`` = nt + lookahead_frames (host arithmetic; no GPU).  ``emitted(n, W, H,
+    lag) == max(0, A(n) * H - W // 2)``."""
+    return max(0, t_decided(n, W, H) - lag + 1)
 
 
 def iir_coefficient(time_constant_s, sr, H):
@@ -239,6 +267,15 @@ class StreamBank:
     float64 result at that type -- module docstring); device tensors in give device tensors out with no host synchronisation (output lengths are host
     arithmetic); numpy in gives numpy out.  ``flush(slots)`` -> ``{slot: tail}`` ends streams (fewer than ``win_length``
     samples in all: ``ValueError``) and leaves the slots empty; ``reset(slots)`` drops their state.
+
+    ``push_spectrum(blocks, return_mask=False)`` / ``flush_spectrum(slots, blocks=None, return_mask=False)`` are the same
+    steps -- bitwise the same samples, the same four launches -- that also report the gated spectrogram of the newly applied
+    frames: ``{slot: (samples, Y)}`` or ``{slot: (samples, Y, mask)}``, ``Y`` ``(F, k)`` complex for a flat mono stream and
+    ``(C, F, k)`` otherwise, ``k = frames(slot)`` after minus before (possibly 0), the bins contiguous in memory
+    (``torch.stft``'s layout).  Each frame is the offline ``Z * mask`` of the whole signal (``scipy.signal.stft``'s scaling,
+    ``padding=0``; the causal floor and the lookahead as for the audio), ``scipy.signal.istft`` of the concatenated frames is
+    the concatenated audio, and ``Y`` / ``mask`` are bitwise independent of the block split, the slot, the other streams and
+    of whether earlier steps were ``push`` or ``push_spectrum`` (module docstring: the contract).
 
     ``noise_from_stream=True`` takes no profile: every (stream, channel) learns its own from the frames it has seen, a
     running mean and standard deviation of the floored dB values per band (the recurrence in the module docstring),
@@ -442,8 +479,9 @@ class StreamBank:
             self._ensure()
 
     # -- steps -------------------------------------------------------------------------------------------------
-    def _step(self, blocks, flush):
-        """blocks: {slot: block or None}; every argument is checked before any device work."""
+    def _step(self, blocks, flush, spectrum=False, return_mask=False):
+        """blocks: {slot: block or None}; every argument is checked before any device work.  ``spectrum``: a spectrum
+        step (sg_stream_push_spectrum), every result a tuple (samples, Y[, mask])."""
         C, W = self.channels, self.win_length
         items, tensor_io = [], None
         for s, blk in blocks.items():
@@ -493,6 +531,8 @@ class StreamBank:
             travel = np.dtype(np.float64 if wide else np.float32)
         tdt = _TORCH[travel]
         recs, outs, in_off, out_off = [], [], 0, 0
+        srecs, frames, sp_off = [], [], 0      # spectrum steps: where every record's newly applied frames go
+        F, H = self.n_fft // 2 + 1, self.hop_length
         for s, a, n, flat in items:
             n1 = self._n[s] + n
             k = (n1 if flush else emitted(n1, W, self.hop_length, self._lag)) - self._e[s]
@@ -501,6 +541,16 @@ class StreamBank:
             outs.append((s, a, k, flat, out_off))
             in_off += C * n
             out_off += C * k
+            if spectrum:
+                kf = ((n1 + 2 * (W // 2) - W) // H + 1 if flush else frames_applied(n1, W, H, self._lag)) - \
+                    frames_applied(self._n[s], W, H, self._lag)
+                srecs.append(_ffi.SgStreamSpecRec(spec_offset=sp_off, mask_offset=sp_off, stride=kf * F))
+                frames.append((kf, sp_off))
+                sp_off += C * kf * F
+        if spectrum:      # complex64 where every slot's own block is float32; else complex128, a float32 slot rounded once
+            own = [np.dtype(str(a.dtype).replace("torch.", "")) if a is not None else self._kind[s][1] for s, a, _, _ in items]
+            narrow = all(dt == np.dtype(np.float32) for dt in own)
+            cdt, rdt = (torch.complex64, torch.float32) if narrow else (torch.complex128, torch.float64)
         with torch.cuda.device(self.device):
             parts = [a.reshape(-1) for _, a, n, _ in items if a is not None and n > 0]
             if tensor_io:
@@ -513,7 +563,12 @@ class StreamBank:
             if x.numel() == 0:
                 x = torch.empty(1, dtype=tdt, device=self.device)
             out = torch.empty(max(out_off, 1), dtype=tdt, device=self.device)
-            self._gate.stream_push(self._bank, x, out, recs)
+            if spectrum:
+                spec = torch.empty(max(sp_off, 1), dtype=cdt, device=self.device)
+                mask = torch.empty(max(sp_off, 1), dtype=rdt, device=self.device) if return_mask else None
+                self._gate.stream_push_spectrum(self._bank, x, out, spec, mask, recs, srecs)
+            else:
+                self._gate.stream_push(self._bank, x, out, recs)
             for (s, a, n, flat), (_, _, k, _, _) in zip(items, outs):
                 if flush:
                     self._n[s] = self._e[s] = 0
@@ -538,6 +593,27 @@ class StreamBank:
                     if o.dtype != dt:
                         o = torch.where(o != o, torch.zeros_like(o), o) if tensor_io else np.where(o != o, 0.0, o)
                 res[s] = o.to(dt) if tensor_io else o.astype(dt, copy=True)
+            if not spectrum:
+                return res
+            fields = [spec] + ([mask] if return_mask else [])
+            if not tensor_io:
+                fields = [f.cpu().numpy() for f in fields]
+            for (s, a, k, flat, _), (kf, off), dt in zip(outs, frames, own):
+                parts = []
+                for f in fields:      # (C, kf, F) as stored, bins contiguous; handed out as the (C, F, kf) view
+                    if tensor_io and (narrow or dt != np.dtype(np.float32)):      # (one view op per field: a step is host-bound)
+                        parts.append(f.as_strided((F, kf), (1, F), off) if flat and C == 1 else
+                                     f.as_strided((C, F, kf), (kf * F, 1, F), off))
+                        continue
+                    v = f[off:off + C * kf * F].reshape(C, kf, F)
+                    if dt == np.dtype(np.float32) and not narrow:
+                        if tensor_io:
+                            v = v.to(torch.complex64 if v.is_complex() else torch.float32)
+                        else:
+                            v = v.astype(np.complex64 if np.iscomplexobj(v) else np.float32)
+                    v = v.transpose(-1, -2) if tensor_io else v.swapaxes(-1, -2)
+                    parts.append(v[0] if flat and C == 1 else v)
+                res[s] = (res[s],) + tuple(parts)
             return res
 
     def push(self, blocks):
@@ -553,6 +629,41 @@ class StreamBank:
         if blocks:
             d.update(blocks)
         return self._step(d, flush=True)
+
+    def frames(self, slot):
+        """Frames of ``slot``'s stream applied so far: reported by the spectrum steps, or passed in plain ``push`` steps
+        (``frames_applied`` of ``received(slot)``; host arithmetic)."""
+        return frames_applied(self._n[self._slots(slot)[0]], self.win_length, self.hop_length, self._lag)
+
+    @staticmethod
+    def _block_map(blocks, who):
+        """{slot: block} of a mapping or of (slot, block) pairs; a slot listed twice is an error."""
+        pairs = list(blocks.items() if hasattr(blocks, "items") else blocks)
+        d = dict(pairs)
+        if len(d) != len(pairs):
+            raise ValueError(f"StreamBank: a slot appears twice in one {who}")
+        return d
+
+    def push_spectrum(self, blocks, return_mask=False):
+        """``push`` that also hands out the gated spectrogram: ``{slot: block}`` (or ``(slot, block)`` pairs) -> ``{slot:
+        (samples, Y)}`` or, ``return_mask=True``, ``{slot: (samples, Y, mask)}``.  ``samples`` is exactly what ``push``
+        returns.  ``Y`` holds the ``k = frames(slot) after - before`` newly applied frames (possibly 0) of ``Z * mask``, the
+        product the step inverts: ``(F, k)`` for a flat mono stream, ``(C, F, k)`` otherwise, ``F = n_fft // 2 + 1``; stored
+        ``(..., k, F)`` with the bins contiguous and returned as the transposed view (``torch.stft``'s layout).  complex64
+        for a float32 block, complex128 for float64 / int16 / int32, whatever the other streams of the step are; ``mask``
+        has ``Y``'s shape and its real type.  Same four launches, no host synchronisation for device tensors."""
+        return self._step(self._block_map(blocks, "step"), flush=False, spectrum=True, return_mask=bool(return_mask))
+
+    def flush_spectrum(self, slots, blocks=None, return_mask=False):
+        """``flush`` that also reports every remaining frame, up to ``T = (N + 2 (W // 2) - W) // H + 1`` of a stream of
+        ``N`` samples: ``{slot: (tail, Y[, mask])}``."""
+        slots = self._slots(slots)
+        if len(set(slots)) != len(slots):
+            raise ValueError("StreamBank: a slot appears twice in one flush")
+        d = {s: None for s in slots}
+        if blocks:
+            d.update(self._block_map(blocks, "flush"))
+        return self._step(d, flush=True, spectrum=True, return_mask=bool(return_mask))
 
     def reset(self, slots):
         slots = self._slots(slots)
@@ -687,6 +798,14 @@ class StreamGate:
 
     def flush(self):
         return self.bank.flush([0])[0]
+
+    def push_spectrum(self, block, return_mask=False):
+        """``(samples, Y)`` or ``(samples, Y, mask)`` (``StreamBank.push_spectrum``)."""
+        return self.bank.push_spectrum({0: block}, return_mask=return_mask)[0]
+
+    def flush_spectrum(self, block=None, return_mask=False):
+        """``(tail, Y)`` or ``(tail, Y, mask)``: the remaining samples and frames (``StreamBank.flush_spectrum``)."""
+        return self.bank.flush_spectrum([0], None if block is None else {0: block}, return_mask=return_mask)[0]
 
     def reset(self):
         self.bank.reset([0])
