@@ -452,6 +452,32 @@ SG_API int sg_gate_spectrum(sg_handle* h, const void* x_dev, int dtype, int64_t 
 SG_API int sg_gate_spectrum_backward(sg_handle* h, const void* grad_spec_dev, int dtype, int64_t B, int64_t L,
                                      const float* mask_dev, void* grad_x_dev, int64_t gx_stride, void* stream);
 
+/* ---- gated filterbank features, TorchGate.gated_filterbank ----
+ * sg_set_filterbank: the handle's filterbank, fb_host float[F][n_filters] (HOST memory, F = n_fft/2 + 1, filters
+ * contiguous), 1 <= n_filters <= 1024, every entry finite (SG_E_INVALID otherwise); a mel bank is the common case, any real
+ * matrix is taken.  Uploads the bank, its transpose and the hulls of its non-zeros per filter and per bin; replaces an
+ * earlier bank after a device synchronisation.  Synchronous.  Power-of-two n_fft from 256 to 4096 (SG_E_UNSUPPORTED
+ * otherwise). */
+SG_API int sg_set_filterbank(sg_handle* h, const float* fb_host, int32_t n_filters);
+
+/* x (B, L) -> feat [B][T][n_filters] of sample type dtype (SG_F32 / SG_F64), filters contiguous:
+ * lin[t][m] = sum_k fb[k][m] * (|X[t][k]| * mask[t][k]) ^ power, X and mask as in sg_gate_spectrum (same statistics,
+ * decisions and smoothing; xn / Bn / Ln / mask_out_dev as there), power 1 or 2; take_log != 0 stores ln(lin + eps).
+ * The transforms are float32, the sums over the bins run in dtype.  SG_E_INVALID when no filterbank is set or power is
+ * neither 1 nor 2; SG_E_UNSUPPORTED outside the power-of-two n_fft from 256 to 4096.  Sub-batches as sg_gate_spectrum.
+ * Enqueues only. */
+SG_API int sg_gate_features(sg_handle* h, const void* x_dev, int dtype, int64_t B, int64_t L, int64_t x_stride,
+                            const void* xn_dev, int64_t Bn, int64_t Ln, int64_t xn_stride, int32_t power, int32_t take_log,
+                            double eps, void* feat_dev, float* mask_out_dev, void* stream);
+
+/* Adjoint of sg_gate_features w.r.t. x with the mask and the filterbank held fixed: grad_feat [B][T][n_filters] of dtype ->
+ * grad_x (B, L) of dtype.  x, power, take_log, eps: what the forward call was given (the frames are transformed again;
+ * nothing of size B x T x F is kept but mask_dev, the buffer sg_gate_features filled).  For power 1 the derivative at
+ * |X[k]| = 0 is 0.  No atomics: the same bits on every run.  Enqueues only. */
+SG_API int sg_gate_features_backward(sg_handle* h, const void* x_dev, int dtype, int64_t B, int64_t L, int64_t x_stride,
+                                     const void* grad_feat_dev, const float* mask_dev, int32_t power, int32_t take_log,
+                                     double eps, void* grad_x_dev, int64_t gx_stride, void* stream);
+
 /* sg_process_batch for a PADDED batch: row i of x (B, L) holds lengths[i] samples of audio, 2 * win_length <= lengths[i] <= L,
  * and padding after them (host array of B entries; NULL: every row is full).  With T_i = 1 + lengths[i] / hop and
  * Lout_i = hop * (lengths[i] / hop): out[i][0 .. Lout_i) is what sg_process_batch returns for the row alone at length

@@ -150,6 +150,11 @@ _PROTOTYPES = {
                                  c_int64, c_void_p, c_void_p, c_void_p]),
     "sg_gate_spectrum_backward": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_int64,
                                           c_void_p]),
+    "sg_set_filterbank": (c_int, [c_void_p, c_void_p, c_int32]),
+    "sg_gate_features": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64,
+                                 c_int64, c_int32, c_int32, c_double, c_void_p, c_void_p, c_void_p]),
+    "sg_gate_features_backward": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                                          c_int32, c_int32, c_double, c_void_p, c_int64, c_void_p]),
     "sg_process_rows": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64,
                                 c_int64, c_int64, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p]),
     "sg_process_rows_backward": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p,
@@ -282,6 +287,7 @@ class Gate:
         # share a cached handle serialise on `lock`, and `thresh_owner` names the object whose threshold
         # the handle currently holds (None: unknown) -- see SpectralGateStationary._bind().
         self.lock = threading.RLock()
+        self.fb_key, self.n_filters = None, 0   # the filterbank the handle holds (set_filterbank)
         self.thresh_owner = None
         self._thresh_owner_ref = None    # weak reference to the owning object while its only copy is the handle's (claim_threshold)
         self._thr_stream = None          # stream the handle's current threshold was written on (noise_stats / set_noise_threshold*)
@@ -545,6 +551,66 @@ class Gate:
             self._check(self.lib.sg_gate_spectrum_backward(
                 self._h, grad.data_ptr(), _sg_dtype(grad), B, L, mask.data_ptr(), out.data_ptr(),
                 out.stride(0) if B > 1 else L, self._stream()))
+        return out
+
+    # -- variant T: gated filterbank features (sg_set_filterbank / sg_gate_features) ------------------
+    def set_filterbank(self, fb, key=None):
+        """The handle's filterbank: fb (F, M) float32, C-contiguous host array.  ``key`` is remembered as ``fb_key`` so
+        that callers sharing a cached handle can tell whose bank it holds.  Synchronises the device when it replaces a
+        bank."""
+        fb = np.ascontiguousarray(fb, dtype=np.float32)
+        if fb.ndim != 2 or fb.shape[0] != self.n_bins:
+            raise ValueError(f"filterbank must be ({self.n_bins}, M), got {fb.shape}")
+        with torch.cuda.device(self.device):
+            self._check(self.lib.sg_set_filterbank(self._h, fb.ctypes.data, fb.shape[1]))   # a refused bank leaves the earlier one
+        self.fb_key, self.n_filters = key, fb.shape[1]
+
+    def gate_features(self, x, xn=None, power=2, log=False, eps=1e-6, save_mask=False):
+        """TorchGate.gated_filterbank: x (B, L) float32 / float64 -> (B, T, M) of x.dtype, the filters contiguous
+        (``.transpose(1, 2)`` is the (B, M, T) feature map).  With save_mask=True also the final mask (B, T, FS) float32,
+        natural bin order, for gate_features_backward."""
+        if not self.n_filters:
+            raise RuntimeError("no filterbank set (set_filterbank)")
+        self._on_device(x)
+        x, xs = _rows(x)
+        B, L = x.shape
+        T = self.n_frames(L)
+        out = torch.empty((B, T, self.n_filters), dtype=x.dtype, device=self.device)
+        mask = None
+        if save_mask:
+            FS = (self.n_bins + 15) // 16 * 16
+            mask = torch.empty((B, T, FS), dtype=torch.float32, device=self.device)
+        if xn is not None:
+            self._on_device(xn)
+            if xn.dtype != x.dtype:
+                xn = xn.to(x.dtype)
+            xn, xns = _rows(xn)
+            xn_ptr, Bn, Ln = xn.data_ptr(), xn.shape[0], xn.shape[1]
+        else:
+            xn_ptr, Bn, Ln, xns = None, 0, 0, 0
+        with torch.cuda.device(self.device):
+            self._check(self.lib.sg_gate_features(
+                self._h, x.data_ptr(), _sg_dtype(x), B, L, xs, xn_ptr, Bn, Ln, xns, int(power), int(bool(log)), float(eps),
+                out.data_ptr(), None if mask is None else mask.data_ptr(), self._stream()))
+        return (out, mask) if save_mask else out
+
+    def gate_features_backward(self, x, grad, mask, power=2, log=False, eps=1e-6):
+        """Adjoint of gate_features w.r.t. x with the mask and the bank fixed: grad (B, T, M) -> (B, L) of x.dtype.  x,
+        power, log, eps: the forward call's."""
+        if not self.n_filters:
+            raise RuntimeError("no filterbank set (set_filterbank)")
+        self._on_device(x)
+        self._on_device(grad)
+        x, xs = _rows(x)
+        B, L = x.shape
+        grad = grad.to(x.dtype).contiguous()
+        if grad.shape != (B, self.n_frames(L), self.n_filters):
+            raise ValueError(f"grad must be (B, T, M) = {(B, self.n_frames(L), self.n_filters)}, got {tuple(grad.shape)}")
+        out = torch.empty((B, L), dtype=x.dtype, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.sg_gate_features_backward(
+                self._h, x.data_ptr(), _sg_dtype(x), B, L, xs, grad.data_ptr(), mask.data_ptr(), int(power),
+                int(bool(log)), float(eps), out.data_ptr(), L, self._stream()))
         return out
 
     # -- variant T: padded batches of different-length rows (sg_process_rows) ------------------------

@@ -43,6 +43,8 @@
 #include "rows.hpp"
 #include "stream.hpp"
 #include "spec.hpp"
+#include "feat.hpp"
+#include "feat_tables.hpp"
 
 // complex transform length from which a whole 256-thread workgroup (instead of one wavefront) works on ONE frame in
 // the general LDS kernels: at N = 2048 (n_fft = 4096) a wavefront holds 4 radix-8 butterflies = 64 complex values per
@@ -196,6 +198,8 @@ struct sg_handle {
   int rowgate_mode = 0;              // SG_OPT_FORCE_NOROWGATE: 0 = by batch size, 1 = never, 2 = whenever the shape is eligible
   int64_t n_floor_lazy = 0, n_floor_apriori = 0;   // sg_debug_counter 1 / 2
   int64_t smooth_route = 0;   // sg_debug_counter 17: SG_SMOOTH_* of the last smoothing launch | cell bytes << 8 | tile frames << 16
+  DevBuf fb_d, fbT_d, fb_khull, fb_mhull;   // sg_set_filterbank: the bank [F][M], its transpose and the two hull tables (feat.hpp)
+  int n_filters = 0;                        // 0: no bank set
   int64_t spec_route = 0;     // sg_debug_counter 18: SG_SPEC_* decide branch of the last sg_gate_spectrum call | flags | sub-batches << 16
   int tile_order = 0;                // SG_OPT_TILE_ORDER: 0 (default, round 6) = persistent workgroups looping over tickets (onepass.hpp PERSIST), 2 = one ticket-drawn tile per workgroup (the kernel of rounds 2-5), 1 = tile = block index
                                      // block index (no ticket), 0 = persistent workgroups looping over tickets (round 6: 1 % faster alone on the
@@ -1410,7 +1414,8 @@ extern "C" int sg_destroy(sg_handle* h) {
                     &h->need, &h->T2, &h->part, &h->tw512, &h->invn, &h->seam, &h->ftab, &h->xbits, &h->xpart,
                     &h->xticket, &h->xtick2, &h->ftab3, &h->xexp, &h->optab, &h->nsp, &h->nsc, &h->xin, &h->czt_tw64, &h->czt_ch64,
                     &h->czt_bh64, &h->czt_tw32, &h->czt_ch32, &h->czt_bh32, &h->logtab, &h->big_twM, &h->big_tw2,
-                    &h->big_ch, &h->big_bh, &h->big_W, &h->big_W2, &h->xP, &h->xraw, &h->xM, &h->xtmp, &h->xseg, &h->rg_count, &h->alim, &h->nss, &h->mr_pt32, &h->mr_pt64, &h->regtab})
+                    &h->big_ch, &h->big_bh, &h->big_W, &h->big_W2, &h->xP, &h->xraw, &h->xM, &h->xtmp, &h->xseg, &h->rg_count, &h->alim, &h->nss, &h->mr_pt32, &h->mr_pt64, &h->regtab,
+                    &h->fb_d, &h->fbT_d, &h->fb_khull, &h->fb_mhull})
     free_buf(*b);
   sg::rg_free(h->rg);
   sg::rw_free(h->rw);
@@ -3125,13 +3130,37 @@ static int stage_spectrum(sg_handle* h, const View& v, const Geom& g, int64_t u0
   return SG_OK;
 }
 
-// sg_process_batch and sg_gate_spectrum: the statistics, decisions and smoothing of a batch of rows, then either the
-// inverse transform (out_dev) or, with spec_dev set, the masked spectrogram itself.  With spec_dev the one-launch row gate is
-// not taken, and the bit-mask route hands its decisions to the float smoothing kernels instead of the integer ones: the
-// spectrogram's mask is then the float field of the general route (h->M) at every geometry.
+// What sg_gate_features asks of process_batch_impl: the features of the masked spectrogram instead of the spectrogram.
+struct FeatSink {
+  void* feat_dev;   // [B][T][M] of the input's dtype
+  int power, take_log;
+  double eps;
+};
+
+static FeatBank feat_bank(const sg_handle* h) {
+  return {(const float*)h->fb_d.p, (const float*)h->fbT_d.p, (const int2*)h->fb_khull.p, (const int2*)h->fb_mhull.p, h->n_filters};
+}
+
+// The filterbank features of one sub-batch (feat.hpp), where stage_spectrum stores the spectrogram: -> feat_dev[u0 ..][T][M].
+static int stage_features(sg_handle* h, const View& v, const Geom& g, int64_t u0, int64_t nb, const float* mask,
+                          const FeatSink& fs, int dtype, hipStream_t st) {
+  ProfScope ps(h, SG_STAGE_APPLY_ISTFT, st);
+  char* dst = (char*)fs.feat_dev + (size_t)u0 * g.T * h->n_filters * (dtype == SG_F64 ? 8 : 4);
+  HIPCHK(h, feat_forward(v, g, nb, h->tw32.p, (const float*)h->wa32.p, mask, feat_bank(h), fs.power, fs.take_log, fs.eps, dst,
+                         dtype, st));
+  return SG_OK;
+}
+
+// sg_process_batch, sg_gate_spectrum and sg_gate_features: the statistics, decisions and smoothing of a batch of rows, then
+// the inverse transform (out_dev), or with spec_dev set the masked spectrogram itself, or with feat set its filterbank
+// features.  With spec_dev or feat the one-launch row gate is not taken, and the bit-mask route hands its decisions to the
+// float smoothing kernels instead of the integer ones: the mask is then the float field of the general route (h->M) at
+// every geometry.
 static int process_batch_impl(sg_handle* h, const void* x_dev, int dtype, int64_t B, int64_t L, int64_t x_stride,
                               const void* xn_dev, int64_t Bn, int64_t Ln, int64_t xn_stride, void* out_dev,
-                              int out_dtype, int64_t out_stride, float* mask_out_dev, void* spec_dev, void* stream) {
+                              int out_dtype, int64_t out_stride, float* mask_out_dev, void* spec_dev, void* stream,
+                              const FeatSink* feat = nullptr) {
+  const bool sink = spec_dev || feat;   // the mask is wanted as a float field in natural bin order
   if (L < 2 * (int64_t)h->W) FAIL(h, SG_E_INVALID, "x must be bigger than %d", 2 * h->W);  // torchgate.py:215-216
   if (xn_dev) {
     if (Ln < 2 * (int64_t)h->W) FAIL(h, SG_E_INVALID, "xn must be bigger than %d", 2 * h->W);  // :219-220
@@ -3179,7 +3208,7 @@ static int process_batch_impl(sg_handle* h, const void* x_dev, int dtype, int64_
       } else {
         th = nullptr; ustride = g.FS;
       }
-      if (!spec_dev && !xn_dev && rowgate_ok(h, g, B)) {
+      if (!sink && !xn_dev && rowgate_ok(h, g, B)) {
         // one kernel per call: a workgroup per row (rowgate.hpp)
         v.unit0 = 0;
         View vr = v;
@@ -3231,7 +3260,7 @@ static int process_batch_impl(sg_handle* h, const void* x_dev, int dtype, int64_
                              nb);
           HIPCHK(h, hipGetLastError());
         }
-        if (!spec_dev) {
+        if (!sink) {
           if ((rc = stage_smooth_bits(h, g, nb, true, 0, g.T, st))) return rc;
           if (mask_out_dev) {  // float mask (natural bin order) for the backward pass
             hipLaunchKernelGGL(k_k16_to_mask_perm, dim3(grid_1d(nb * g.T * g.FS, 256)), dim3(256), 0, st,
@@ -3261,7 +3290,7 @@ static int process_batch_impl(sg_handle* h, const void* x_dev, int dtype, int64_
     }
     const bool geom_fast = h->fast_ok && !h->force_nofast;
     // the spectrogram reads the mask wherever it lies: smoothed straight into the caller's buffer, without the copy below
-    float* const mask_direct = (spec_dev && mask_out_dev && (h->p.stationary || !box_mask_ok(h)))
+    float* const mask_direct = (sink && mask_out_dev && (h->p.stationary || !box_mask_ok(h)))
                                    ? mask_out_dev + (size_t)u0 * g.T * g.FS : nullptr;
     if (h->p.stationary || !box_mask_ok(h))
       if ((rc = stage_smooth(h, g, nb, st, mask_direct))) return rc;
@@ -3271,6 +3300,8 @@ static int process_batch_impl(sg_handle* h, const void* x_dev, int dtype, int64_
     if (spec_dev) {
       if ((rc = stage_spectrum(h, v, g, u0, nb, mask_direct ? mask_direct : (const float*)h->M.p, spec_dev, dtype, st))) return rc;
       h->spec_route = branch | (mask_direct ? SG_SPEC_MASK_DIRECT : 0) | (++n_sub << 16);
+    } else if (feat) {
+      if ((rc = stage_features(h, v, g, u0, nb, mask_direct ? mask_direct : (const float*)h->M.p, *feat, dtype, st))) return rc;
     } else if (geom_fast) {
       if ((rc = stage_apply_fast(h, v, g, nb, om, (const float*)h->M.p, 1, st))) return rc;
     } else if (const RegGeom* r = reg_geom(h)) {
@@ -3339,6 +3370,90 @@ extern "C" int sg_gate_spectrum_backward(sg_handle* h, const void* grad_spec_dev
       ProfScope ps(h, SG_STAGE_APPLY_ISTFT, st);
       HIPCHK(h, spec_backward_frames(g, nb, h->tw32.p, (const float*)h->wa32.p, mask_dev + (size_t)u0 * g.T * g.FS,
                                      (const char*)grad_spec_dev + (size_t)u0 * g.T * g.F * 2 * esz, dtype, (float*)h->seg.p, st));
+    }
+    ProfScope ps(h, SG_STAGE_OLA, st);
+    HIPCHK(h, spec_backward_ola(g, nb, L, (const float*)h->seg.p, (char*)grad_x_dev + (size_t)u0 * gx_stride * esz, dtype,
+                                gx_stride, st));
+  }
+  return SG_OK;
+}
+
+// TorchGate.gated_filterbank (feat.hpp).  The bank is host data: validated, transposed and given its hull tables here.
+extern "C" int sg_set_filterbank(sg_handle* h, const float* fb_host, int32_t n_filters) {
+  if (!h) return SG_E_INVALID;
+  if (h->p.variant != SG_VARIANT_T) FAIL(h, SG_E_INVALID, "sg_set_filterbank is a variant-T entry point");
+  if (!fb_host || n_filters < 1 || n_filters > FEAT_MAX_FILTERS)
+    FAIL(h, SG_E_INVALID, "sg_set_filterbank: bad argument (1 <= n_filters <= %d)", FEAT_MAX_FILTERS);
+  if (!spectrum_geom_ok(h))
+    FAIL(h, SG_E_UNSUPPORTED, "sg_set_filterbank: n_fft=%d (powers of two from 256 to 4096 only)", h->n);
+  const int F = h->F, M = n_filters;
+  std::vector<float> fbT((size_t)F * M);
+  std::vector<int32_t> khull(2 * (size_t)M), mhull(2 * (size_t)F);
+  if (!feat_tables(fb_host, F, M, fbT.data(), khull.data(), mhull.data()))
+    FAIL(h, SG_E_INVALID, "sg_set_filterbank: the filterbank has a non-finite entry");
+  // launches of an earlier call may still read the tables about to be overwritten
+  if (h->n_filters) HIPCHK(h, hipDeviceSynchronize());
+  h->n_filters = 0;
+  int rc;
+  if ((rc = upload(h, h->fb_d, fb_host, (size_t)F * M * 4))) return rc;
+  if ((rc = upload(h, h->fbT_d, fbT.data(), (size_t)F * M * 4))) return rc;
+  if ((rc = upload(h, h->fb_khull, khull.data(), khull.size() * 4))) return rc;
+  if ((rc = upload(h, h->fb_mhull, mhull.data(), mhull.size() * 4))) return rc;
+  h->n_filters = M;
+  return SG_OK;
+}
+
+static int features_args_ok(sg_handle* h, const char* who, int power, double eps) {
+  if (power != 1 && power != 2) FAIL(h, SG_E_INVALID, "%s: power must be 1 or 2", who);
+  if (!(eps == eps)) FAIL(h, SG_E_INVALID, "%s: eps is NaN", who);
+  if (!spectrum_geom_ok(h)) FAIL(h, SG_E_UNSUPPORTED, "%s: n_fft=%d (powers of two from 256 to 4096 only)", who, h->n);
+  if (!h->n_filters) FAIL(h, SG_E_INVALID, "%s: no filterbank set (sg_set_filterbank)", who);
+  return SG_OK;
+}
+
+extern "C" int sg_gate_features(sg_handle* h, const void* x_dev, int dtype, int64_t B, int64_t L, int64_t x_stride,
+                                const void* xn_dev, int64_t Bn, int64_t Ln, int64_t xn_stride, int32_t power, int32_t take_log,
+                                double eps, void* feat_dev, float* mask_out_dev, void* stream) {
+  if (!h) return SG_E_INVALID;
+  if (h->p.variant != SG_VARIANT_T) FAIL(h, SG_E_INVALID, "sg_gate_features is a variant-T entry point");
+  if (!x_dev || !feat_dev || (dtype != SG_F32 && dtype != SG_F64) || B < 1)
+    FAIL(h, SG_E_INVALID, "sg_gate_features: bad argument");
+  int rc;
+  if ((rc = features_args_ok(h, "sg_gate_features", power, eps))) return rc;
+  const FeatSink fs{feat_dev, power, take_log != 0, eps};
+  return process_batch_impl(h, x_dev, dtype, B, L, x_stride, xn_dev, Bn, Ln, xn_stride, nullptr, dtype, 0, mask_out_dev,
+                            nullptr, stream, &fs);
+}
+
+// Adjoint of sg_gate_features w.r.t. x with mask and bank fixed: the frames are transformed again from x, G = dL/dX formed
+// in LDS, windowed adjoint frames into h->seg, then the gather of sg_gate_spectrum_backward.
+extern "C" int sg_gate_features_backward(sg_handle* h, const void* x_dev, int dtype, int64_t B, int64_t L, int64_t x_stride,
+                                         const void* grad_feat_dev, const float* mask_dev, int32_t power, int32_t take_log,
+                                         double eps, void* grad_x_dev, int64_t gx_stride, void* stream) {
+  if (!h) return SG_E_INVALID;
+  if (h->p.variant != SG_VARIANT_T) FAIL(h, SG_E_INVALID, "sg_gate_features_backward is a variant-T entry point");
+  if (!x_dev || !grad_feat_dev || !grad_x_dev || !mask_dev || B < 1 || (dtype != SG_F32 && dtype != SG_F64) || x_stride < L ||
+      gx_stride < L)
+    FAIL(h, SG_E_INVALID, "sg_gate_features_backward: bad argument");
+  if (L < 2 * (int64_t)h->W) FAIL(h, SG_E_INVALID, "x must be bigger than %d", 2 * h->W);
+  int rc;
+  if ((rc = features_args_ok(h, "sg_gate_features_backward", power, eps))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  View v{};
+  v.x = x_dev; v.dtype = dtype; v.stride = x_stride; v.N = L; v.lo = 0; v.hi = L; v.cs = 0; v.pad = 0; v.Lp = L; v.n_chunks = 1;
+  const Geom g = make_geom(h, L);
+  const int64_t ub = units_per_batch(h, g, B);
+  if ((rc = ensure(h, h->seg, (size_t)ub * g.T * g.n * 4))) return rc;
+  const size_t esz = dtype == SG_F64 ? 8 : 4;
+  for (int64_t u0 = 0; u0 < B; u0 += ub) {
+    const int64_t nb = std::min(ub, B - u0);
+    v.unit0 = u0;
+    {
+      ProfScope ps(h, SG_STAGE_APPLY_ISTFT, st);
+      HIPCHK(h, feat_backward_frames(v, g, nb, h->tw32.p, (const float*)h->wa32.p, mask_dev + (size_t)u0 * g.T * g.FS,
+                                     feat_bank(h), power, take_log != 0, eps,
+                                     (const char*)grad_feat_dev + (size_t)u0 * g.T * h->n_filters * esz, dtype,
+                                     (float*)h->seg.p, st));
     }
     ProfScope ps(h, SG_STAGE_OLA, st);
     HIPCHK(h, spec_backward_ola(g, nb, L, (const float*)h->seg.p, (char*)grad_x_dev + (size_t)u0 * gx_stride * esz, dtype,

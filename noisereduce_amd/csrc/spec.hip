@@ -14,6 +14,7 @@
 #include "fft_wave.hpp"
 #include "geom.hpp"
 #include "spec.hpp"
+#include "spec_team.hpp"
 
 namespace sg {
 
@@ -89,7 +90,7 @@ __global__ __launch_bounds__(WAVES * NT) void k_spec_fwd(View view, Geom g, cons
 // The adjoint frame.  With Y[k] = mask[k] grad[k] (0 < k < N), Y[0] = 2 mask[0] Re grad[0], Y[N] = 2 mask[N] Re grad[N] read
 // as the Hermitian half of a length-2N spectrum, the un-normalised half-size inverse transform of its merge is
 // N * irfft(Y)[j] = Re sum_{k=0}^{N} mask[k] grad[k] e^{+2 pi i k j / 2N}: every bin with weight 1, the imaginary parts of
-// grad[0] and grad[N] unused.  The merge is k_apply_istft's.
+// grad[0] and grad[N] unused.  The merge is k_apply_istft's (spec_team.hpp).
 template <int N, int WAVES, int FPW, int NT, typename TI>
 __global__ __launch_bounds__(WAVES * NT) void k_spec_bwd(Geom g, const cx<float>* __restrict__ tw_g,
                                                          const float* __restrict__ win, const float* __restrict__ mask,
@@ -115,20 +116,14 @@ __global__ __launch_bounds__(WAVES * NT) void k_spec_bwd(Geom g, const cx<float>
         if (k == 0) {
           const float y0 = 2.0f * (float)grow[0].x * Mrow[0];
           const float yN = 2.0f * (float)grow[N].x * Mrow[N];
-          buf[0] = {0.5f * (y0 + yN), 0.5f * (y0 - yN)};
+          merge_dc(buf, y0, yN);
         } else {
           const V2 gk = grow[k], gn = grow[N - k];
           const float mk = Mrow[k], mn = Mrow[N - k];
           const cx<float> w = tw[k];
           const cx<float> Yk = {(float)gk.x * mk, (float)gk.y * mk};
           const cx<float> Yn = {(float)gn.x * mn, (float)gn.y * mn};
-          // merge: E' = (Yk + conj Yn)/2 ; O' = (Yk - conj Yn)/2 * conj(w) ; Zc'[k] = E' + i O'
-          const cx<float> Ep = {(Yk.x + Yn.x) * 0.5f, (Yk.y - Yn.y) * 0.5f};
-          const cx<float> D = {(Yk.x - Yn.x) * 0.5f, (Yk.y + Yn.y) * 0.5f};
-          const cx<float> wc = {w.x, -w.y};
-          const cx<float> Op = cmul(D, wc);
-          buf[k] = {Ep.x - Op.y, Ep.y + Op.x};
-          if (k != N - k) buf[N - k] = {Ep.x + Op.y, -Ep.y + Op.x};   // Zc'[N-k] = conj(E') + i conj(O')
+          merge_pair(buf, w, k, N, Yk, Yn);
         }
       }
     }

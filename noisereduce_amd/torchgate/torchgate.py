@@ -5,11 +5,15 @@
 reference's.  The mask is computed without gradient (torchgate.py:126,167) and the output
 is differentiable w.r.t. ``x`` through STFT -> (x mask) -> ISTFT.
 """
+import hashlib
+import math
+import weakref
 from typing import Optional, Union
 
 import torch
 
 from noisereduce_amd import _ffi
+from noisereduce_amd.torchgate import filterbank as _fbank
 from noisereduce_amd.torchgate import rows as _rows
 from noisereduce_amd.torchgate.utils import linspace
 
@@ -102,6 +106,38 @@ class _SpectrumRowsFunction(torch.autograd.Function):
         return gx, None, None, None, None
 
 
+def _bind_bank(gate, bank):
+    """The handle holds this bank (handles are shared between modules of equal parameters: the caller holds gate.lock)."""
+    if gate.fb_key != bank["digest"]:
+        gate.set_filterbank(bank["host"], key=bank["digest"])
+
+
+class _FeaturesFunction(torch.autograd.Function):
+    """gated_filterbank on the native kernels (sg_gate_features): the features (B, T, M) and the mask, which carries no
+    gradient.  Saves x and the mask: the backward transforms the frames again (sg_gate_features_backward), so nothing of
+    size B x T x F is kept but the mask.  ``bank``: the entry of TorchGate._bank (host array and digest)."""
+
+    @staticmethod
+    def forward(ctx, x, xn, module, bank, power, log, eps):
+        gate = module._gate_for(x.device)
+        with gate.lock:
+            _bind_bank(gate, bank)
+            feat, mask = gate.gate_features(x.detach(), xn, power=power, log=log, eps=eps, save_mask=True)
+        ctx.gate, ctx.bank, ctx.args = gate, bank, (power, log, eps)
+        ctx.save_for_backward(x, mask)
+        ctx.mark_non_differentiable(mask)
+        return feat, mask
+
+    @staticmethod
+    def backward(ctx, grad_feat, _grad_mask):
+        x, mask = ctx.saved_tensors
+        power, log, eps = ctx.args
+        with ctx.gate.lock:
+            _bind_bank(ctx.gate, ctx.bank)
+            gx = ctx.gate.gate_features_backward(x.detach(), grad_feat, mask, power=power, log=log, eps=eps)
+        return gx, None, None, None, None, None, None
+
+
 class TorchGate(torch.nn.Module):
     """A PyTorch module that applies a spectral gate to an input signal (see the reference
     docstring, torchgate.py:8-29, for the arguments)."""
@@ -129,6 +165,7 @@ class TorchGate(torch.nn.Module):
         self._n_grad = (1, 1)
         self.register_buffer("smoothing_filter", self._generate_mask_smoothing_filter())
         self._gates = {}
+        self._banks = {}
 
     @torch.no_grad()
     def _generate_mask_smoothing_filter(self) -> Union[torch.Tensor, None]:
@@ -287,6 +324,104 @@ class TorchGate(torch.nn.Module):
         Y = Yt.transpose(1, 2)
         return (Y, mask[:, :, :F].transpose(1, 2)) if return_mask else Y
 
+    def _bank(self, fb):
+        """The validated host copy of a filterbank (``filterbank.check_filterbank``) and its digest, cached per
+        ``(data_ptr, _version, shape, device)`` of a tensor -- an in-place edit bumps ``_version`` and is seen; the entry
+        also remembers the tensor itself (weakly), so an address that a later tensor reuses is not mistaken for it.  Any
+        other array is converted on every call.  A device tensor is copied to the host once per entry, which
+        synchronises."""
+        F = self.n_fft // 2 + 1
+        key = None
+        if isinstance(fb, torch.Tensor):
+            if fb.requires_grad:
+                raise ValueError("the filterbank is a constant: fb.requires_grad must be False")
+            key = (fb.data_ptr(), fb._version, tuple(fb.shape), tuple(fb.stride()), fb.dtype, str(fb.device))
+            hit = self._banks.get(key)
+            if hit is not None and hit["ref"]() is fb:
+                return hit
+        host = _fbank.check_filterbank(fb, F)
+        bank = dict(host=host, digest=hashlib.sha1(host.tobytes()).hexdigest() + "/%d" % host.shape[1], dev={})
+        if key is not None:
+            bank["ref"] = weakref.ref(fb)
+            if len(self._banks) >= 8:
+                self._banks.clear()
+            self._banks[key] = bank
+        return bank
+
+    def gated_filterbank(self, x: torch.Tensor, fb, xn: Optional[torch.Tensor] = None, power: float = 2.0,
+                         log: bool = False, eps: float = 1e-6, return_mask: bool = False, lengths=None, xn_lengths=None):
+        """Filterbank features of the gated spectrogram -- gated log-mel features with ``fb = mel_filterbank(...)`` and
+        ``log=True`` -- without the (batch, bins, frames) spectrogram in memory.
+
+        With ``Y = gated_stft(x, xn)``: ``lin[b, m, t] = sum_k fb[k, m] * |Y[b, k, t]| ** power``, returned as it is
+        (``log=False``) or as ``ln(lin + eps)``.  Returns (batch, M, frames): float32 for float32 input, float64 for
+        float64 (the transforms are float32 as in ``gated_stft``, the sums over the bins run in the output type), other
+        dtypes go through ``.float()``.  Storage is (batch, frames, M) with the filters contiguous, returned as the
+        ``.transpose(1, 2)`` view, the way ``gated_stft`` returns Y.  ``return_mask=True`` adds the (batch, bins, frames)
+        float32 mask view exactly as ``gated_stft`` returns it.
+
+        fb: any real (n_fft // 2 + 1, M) array or tensor, 1 <= M <= 1024, finite; a constant (``fb.requires_grad`` raises
+        ValueError).  Entries may be negative when ``log=False``.  The uploaded tables are cached per
+        ``(data_ptr, _version, shape, device)`` of a tensor; a device tensor is copied to the host once to build them,
+        which synchronises.  power: 2.0 or 1.0.  Errors in ``fb`` or ``power`` raise ValueError before any device work.
+
+        Differentiable w.r.t. ``x`` with the mask detached, like ``gated_stft``; for ``power=1`` the derivative at
+        ``|X[k]| = 0`` is 0.
+
+        Power-of-two n_fft from 256 to 4096 on full-length rows run on the native kernels (sg_gate_features,
+        csrc/feat.hip): the frame stays in LDS between the transform and the features, and the backward transforms it
+        again.  Any other n_fft, and every call whose ``lengths`` / ``xn_lengths`` are not all full, takes the composed,
+        slow route: the formula above in torch on ``gated_stft(...)``, torch autograd for the backward.  With
+        ``lengths``, frames at and after ``stft_lengths(lengths)[i]`` hold what the formula gives for a zero spectrum: 0,
+        or ``ln(eps)`` with ``log=True``.  All-full lengths are bitwise ``gated_filterbank(x, fb, xn)``."""
+        assert x.ndim == 2
+        if power not in (1, 2, 1.0, 2.0) or isinstance(power, bool):
+            raise ValueError(f"power must be 1.0 or 2.0, got {power!r}")
+        eps = float(eps)
+        if math.isnan(eps):
+            raise ValueError("eps is NaN")
+        power = int(power)
+        bank = self._bank(fb)
+        rows_call = lengths is not None or xn_lengths is not None
+        if rows_call:
+            lengths, xn_lengths = self._check_rows(x, xn, lengths, xn_lengths, xn_rows=True)
+            if _rows.all_full(lengths, x.shape[-1]) and (xn is None or _rows.all_full(xn_lengths, xn.shape[-1])):
+                rows_call, lengths, xn_lengths = False, None, None
+        if not rows_call:
+            if x.shape[-1] < self.win_length * 2:
+                raise Exception(f"x must be bigger than {self.win_length * 2}")
+            assert xn is None or xn.ndim == 1 or xn.ndim == 2
+            if xn is not None and xn.shape[-1] < self.win_length * 2:
+                raise Exception(f"xn must be bigger than {self.win_length * 2}")
+            if x.device.type != "cuda":
+                raise RuntimeError("noisereduce_amd.TorchGate runs on the GPU only (no CPU fallback): "
+                                   "move the input with x.to('cuda')")
+        if x.dtype not in (torch.float32, torch.float64):
+            x = x.float()
+        F = self.n_fft // 2 + 1
+        if not rows_call and _rows.native(self.n_fft):
+            if xn is not None:
+                xn = xn.detach().to(device=x.device, dtype=x.dtype)
+                if xn.ndim == 1:
+                    xn = xn.unsqueeze(0)
+                if self.nonstationary:
+                    xn = None  # unused by the non-stationary mask (torchgate.py:235-236)
+            feat, mask = _FeaturesFunction.apply(x, xn, self, bank, power, bool(log), eps)
+        else:
+            Y, Mv = self.gated_stft(x, xn, return_mask=True, lengths=lengths, xn_lengths=xn_lengths)
+            mask = Mv.transpose(1, 2)
+            dkey = (str(x.device), x.dtype)
+            fbd = bank["dev"].get(dkey)
+            if fbd is None:
+                fbd = bank["dev"][dkey] = torch.from_numpy(bank["host"]).to(device=x.device, dtype=x.dtype)
+            Yt = Y.transpose(1, 2)                                  # (B, T, F), the storage order
+            p = Yt.real * Yt.real + Yt.imag * Yt.imag if power == 2 else Yt.abs()
+            feat = torch.matmul(p, fbd)
+            if log:
+                feat = torch.log(feat + eps)
+        out = feat.transpose(1, 2)
+        return (out, mask[:, :, :F].transpose(1, 2)) if return_mask else out
+
     def _check_rows(self, x, xn, lengths, xn_lengths, xn_rows=False):
         """Validation of a call with per-row lengths (forward and gated_stft alike), before any device work: the
         lengths as host int64 arrays (or None).  xn_rows: refuse a noise batch of neither 1 nor B rows here, whether
@@ -387,4 +522,5 @@ class TorchGate(torch.nn.Module):
         st = super().__getstate__() if hasattr(super(), "__getstate__") else self.__dict__.copy()
         st = dict(st)
         st["_gates"] = {}  # device handles are not picklable
+        st["_banks"] = {}  # weak references neither
         return st
