@@ -466,6 +466,40 @@ class Gate:
         return out
 
     # -- variant T -------------------------------------------------------------------
+    # Every wrapper below is marshalling (_noise, _mask, _grad_x, _lengths) and one library call.
+    def _noise(self, x, xn):
+        """The noise rows for the C ABI, in x's dtype: the tensor to keep alive and (ptr, Bn, Ln, stride)."""
+        if xn is None:
+            return None, (None, 0, 0, 0)
+        self._on_device(xn)
+        if xn.dtype != x.dtype:
+            xn = xn.to(x.dtype)
+        xn, xns = _rows(xn)
+        return xn, (xn.data_ptr(), xn.shape[0], xn.shape[1], xns)
+
+    def _mask(self, B, T, save_mask, mask_out=None):
+        """The final mask (B, T, FS) float32, natural bin order: None unless asked for, mask_out (validated) when given."""
+        if not save_mask and mask_out is None:
+            return None
+        FS = (self.n_bins + 15) // 16 * 16
+        mask = mask_out if mask_out is not None else torch.empty((B, T, FS), dtype=torch.float32, device=self.device)
+        if mask.shape != (B, T, FS) or mask.dtype != torch.float32 or not mask.is_contiguous():
+            raise ValueError("mask_out must be a contiguous (B, T, FS) float32 tensor")
+        return mask
+
+    def _grad_x(self, B, L, dtype):
+        return torch.empty((B, L), dtype=dtype, device=self.device)
+
+    @staticmethod
+    def _lengths(lengths, count):
+        """Host int64 array for the C ABI (None stays None: every row full)."""
+        if lengths is None:
+            return None, None
+        a = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1))
+        if a.shape[0] != count:
+            raise ValueError(f"expected {count} lengths, got {a.shape[0]}")
+        return a, a.ctypes.data_as(c_void_p)
+
     def process_batch(self, x, xn=None, out_dtype=None, save_mask=False):
         """TorchGate.forward.  With save_mask=True also returns the final mask
         (B, T, FS) float32 needed by process_batch_backward."""
@@ -474,22 +508,12 @@ class Gate:
         B, L = x.shape
         Lout = self.output_length(L)
         out = torch.empty((B, Lout), dtype=out_dtype or x.dtype, device=self.device)
-        mask = None
-        if save_mask:
-            FS = (self.n_bins + 15) // 16 * 16
-            mask = torch.empty((B, self.n_frames(L), FS), dtype=torch.float32, device=self.device)
-        if xn is not None:
-            self._on_device(xn)
-            if xn.dtype != x.dtype:
-                xn = xn.to(x.dtype)
-            xn, xns = _rows(xn)
-            xn_ptr, Bn, Ln = xn.data_ptr(), xn.shape[0], xn.shape[1]
-        else:
-            xn_ptr, Bn, Ln, xns = None, 0, 0, 0
+        mask = self._mask(B, self.n_frames(L), save_mask) if save_mask else None
+        xn, noise = self._noise(x, xn)
         with torch.cuda.device(self.device):
             self._check(self.lib.sg_process_batch(
-                self._h, x.data_ptr(), _sg_dtype(x), B, L, xs, xn_ptr, Bn, Ln, xns, out.data_ptr(),
-                _sg_dtype(out), Lout, None if mask is None else mask.data_ptr(), self._stream()))
+                self._h, x.data_ptr(), _sg_dtype(x), B, L, xs, *noise, out.data_ptr(), _sg_dtype(out), Lout,
+                None if mask is None else mask.data_ptr(), self._stream()))
         return (out, mask) if save_mask else out
 
     def process_batch_backward(self, grad_out, mask, L):
@@ -497,7 +521,7 @@ class Gate:
         self._on_device(grad_out)
         grad_out, gs = _rows(grad_out)
         B = grad_out.shape[0]
-        gx = torch.empty((B, L), dtype=grad_out.dtype, device=self.device)
+        gx = self._grad_x(B, L, grad_out.dtype)
         with torch.cuda.device(self.device):
             self._check(self.lib.sg_process_batch_backward(
                 self._h, grad_out.data_ptr(), _sg_dtype(grad_out), B, L, gs, mask.data_ptr(),
@@ -517,23 +541,11 @@ class Gate:
             out = torch.empty((B, T, self.n_bins, 2), dtype=x.dtype, device=self.device)
         elif out.shape != (B, T, self.n_bins, 2) or out.dtype != x.dtype or not out.is_contiguous():
             raise ValueError("out must be a contiguous (B, T, F, 2) tensor of x.dtype")
-        mask = None
-        if save_mask or mask_out is not None:
-            FS = (self.n_bins + 15) // 16 * 16
-            mask = mask_out if mask_out is not None else torch.empty((B, T, FS), dtype=torch.float32, device=self.device)
-            if mask.shape != (B, T, FS) or mask.dtype != torch.float32 or not mask.is_contiguous():
-                raise ValueError("mask_out must be a contiguous (B, T, FS) float32 tensor")
-        if xn is not None:
-            self._on_device(xn)
-            if xn.dtype != x.dtype:
-                xn = xn.to(x.dtype)
-            xn, xns = _rows(xn)
-            xn_ptr, Bn, Ln = xn.data_ptr(), xn.shape[0], xn.shape[1]
-        else:
-            xn_ptr, Bn, Ln, xns = None, 0, 0, 0
+        mask = self._mask(B, T, save_mask, mask_out)
+        xn, noise = self._noise(x, xn)
         with torch.cuda.device(self.device):
             self._check(self.lib.sg_gate_spectrum(
-                self._h, x.data_ptr(), _sg_dtype(x), B, L, xs, xn_ptr, Bn, Ln, xns, out.data_ptr(),
+                self._h, x.data_ptr(), _sg_dtype(x), B, L, xs, *noise, out.data_ptr(),
                 None if mask is None else mask.data_ptr(), self._stream()))
         return (out, mask) if mask is not None else out
 
@@ -544,7 +556,7 @@ class Gate:
         grad = grad.contiguous()
         B = grad.shape[0]
         if out is None:
-            out = torch.empty((B, L), dtype=grad.dtype, device=self.device)
+            out = self._grad_x(B, L, grad.dtype)
         elif out.shape != (B, L) or out.dtype != grad.dtype or (L > 1 and out.stride(1) != 1):
             raise ValueError("out must be a (B, L) tensor of grad.dtype with contiguous rows")
         with torch.cuda.device(self.device):
@@ -576,21 +588,11 @@ class Gate:
         B, L = x.shape
         T = self.n_frames(L)
         out = torch.empty((B, T, self.n_filters), dtype=x.dtype, device=self.device)
-        mask = None
-        if save_mask:
-            FS = (self.n_bins + 15) // 16 * 16
-            mask = torch.empty((B, T, FS), dtype=torch.float32, device=self.device)
-        if xn is not None:
-            self._on_device(xn)
-            if xn.dtype != x.dtype:
-                xn = xn.to(x.dtype)
-            xn, xns = _rows(xn)
-            xn_ptr, Bn, Ln = xn.data_ptr(), xn.shape[0], xn.shape[1]
-        else:
-            xn_ptr, Bn, Ln, xns = None, 0, 0, 0
+        mask = self._mask(B, T, save_mask)
+        xn, noise = self._noise(x, xn)
         with torch.cuda.device(self.device):
             self._check(self.lib.sg_gate_features(
-                self._h, x.data_ptr(), _sg_dtype(x), B, L, xs, xn_ptr, Bn, Ln, xns, int(power), int(bool(log)), float(eps),
+                self._h, x.data_ptr(), _sg_dtype(x), B, L, xs, *noise, int(power), int(bool(log)), float(eps),
                 out.data_ptr(), None if mask is None else mask.data_ptr(), self._stream()))
         return (out, mask) if save_mask else out
 
@@ -606,7 +608,7 @@ class Gate:
         grad = grad.to(x.dtype).contiguous()
         if grad.shape != (B, self.n_frames(L), self.n_filters):
             raise ValueError(f"grad must be (B, T, M) = {(B, self.n_frames(L), self.n_filters)}, got {tuple(grad.shape)}")
-        out = torch.empty((B, L), dtype=x.dtype, device=self.device)
+        out = self._grad_x(B, L, x.dtype)
         with torch.cuda.device(self.device):
             self._check(self.lib.sg_gate_features_backward(
                 self._h, x.data_ptr(), _sg_dtype(x), B, L, xs, grad.data_ptr(), mask.data_ptr(), int(power),
@@ -614,16 +616,6 @@ class Gate:
         return out
 
     # -- variant T: padded batches of different-length rows (sg_process_rows) ------------------------
-    @staticmethod
-    def _lengths(lengths, count):
-        """Host int64 array for the C ABI (None stays None: every row full)."""
-        if lengths is None:
-            return None, None
-        a = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1))
-        if a.shape[0] != count:
-            raise ValueError(f"expected {count} lengths, got {a.shape[0]}")
-        return a, a.ctypes.data_as(c_void_p)
-
     def process_rows(self, x, lengths, xn=None, xn_lengths=None, out_dtype=None, save_mask=False):
         """TorchGate.forward on a padded batch: row i holds lengths[i] samples (host integers) and padding after
         them.  Returns (B, output_length(L)); row i is the gate of x[i, :lengths[i]] alone, zeros beyond
@@ -634,18 +626,8 @@ class Gate:
         B, L = x.shape
         Lout = self.output_length(L)
         out = torch.empty((B, Lout), dtype=out_dtype or x.dtype, device=self.device)
-        mask = None
-        if save_mask:
-            FS = (self.n_bins + 15) // 16 * 16
-            mask = torch.empty((B, self.n_frames(L), FS), dtype=torch.float32, device=self.device)
-        if xn is not None:
-            self._on_device(xn)
-            if xn.dtype != x.dtype:
-                xn = xn.to(x.dtype)
-            xn, xns = _rows(xn)
-            xn_ptr, Bn, Ln = xn.data_ptr(), xn.shape[0], xn.shape[1]
-        else:
-            xn_ptr, Bn, Ln, xns = None, 0, 0, 0
+        mask = self._mask(B, self.n_frames(L), save_mask) if save_mask else None
+        xn, (xn_ptr, Bn, Ln, xns) = self._noise(x, xn)
         la, lp = self._lengths(lengths, B)
         na, np_ = self._lengths(xn_lengths if xn is not None else None, Bn)
         with torch.cuda.device(self.device):
@@ -659,7 +641,7 @@ class Gate:
         self._on_device(grad_out)
         grad_out, gs = _rows(grad_out)
         B = grad_out.shape[0]
-        gx = torch.empty((B, L), dtype=grad_out.dtype, device=self.device)
+        gx = self._grad_x(B, L, grad_out.dtype)
         la, lp = self._lengths(lengths, B)
         with torch.cuda.device(self.device):
             self._check(self.lib.sg_process_rows_backward(
@@ -678,18 +660,8 @@ class Gate:
         B, L = x.shape
         T = self.n_frames(L)
         out = torch.empty((B, T, self.n_bins, 2), dtype=x.dtype, device=self.device)
-        mask = None
-        if save_mask:
-            FS = (self.n_bins + 15) // 16 * 16
-            mask = torch.empty((B, T, FS), dtype=torch.float32, device=self.device)
-        if xn is not None:
-            self._on_device(xn)
-            if xn.dtype != x.dtype:
-                xn = xn.to(x.dtype)
-            xn, xns = _rows(xn)
-            xn_ptr, Bn, Ln = xn.data_ptr(), xn.shape[0], xn.shape[1]
-        else:
-            xn_ptr, Bn, Ln, xns = None, 0, 0, 0
+        mask = self._mask(B, T, save_mask)
+        xn, (xn_ptr, Bn, Ln, xns) = self._noise(x, xn)
         la, lp = self._lengths(lengths, B)
         na, np_ = self._lengths(xn_lengths if xn is not None else None, Bn)
         with torch.cuda.device(self.device):
@@ -704,7 +676,7 @@ class Gate:
         self._on_device(grad)
         grad = grad.contiguous()
         B = grad.shape[0]
-        gx = torch.empty((B, L), dtype=grad.dtype, device=self.device)
+        gx = self._grad_x(B, L, grad.dtype)
         la, lp = self._lengths(lengths, B)
         with torch.cuda.device(self.device):
             self._check(self.lib.sg_gate_spectrum_rows_backward(

@@ -2945,6 +2945,41 @@ static int stage_row_gate(sg_handle* h, const View& v, const Geom& g, int64_t nb
 
 static bool dtype_ok(int d) { return d >= SG_F32 && d <= SG_I32; }
 
+// Bytes of one float32 / float64 element (the dtypes of the variant-T outputs and gradients).
+static size_t elem_bytes(int dtype) { return dtype == SG_F64 ? 8 : 4; }
+
+// Rows of L samples read whole: one unit per row, no chunks, no padding, no halos, first unit 0.
+static View rows_view(const void* ptr, int dtype, int64_t stride, int64_t L) {
+  View v{};
+  v.x = ptr; v.dtype = dtype; v.stride = stride; v.N = L; v.lo = 0; v.hi = L; v.cs = 0; v.pad = 0; v.Lp = L; v.n_chunks = 1;
+  return v;
+}
+
+// Rows of n samples written whole: positions [0, n) of a unit to [0, n) of its row.
+static OutMap whole_out(void* ptr, int dtype, int64_t stride, int64_t n) {
+  OutMap om{};
+  om.out = ptr; om.dtype = dtype; om.stride = stride;
+  om.p0 = 0; om.p1 = n; om.g_step = 0; om.g0 = 0; om.g_lo = 0; om.g_hi = n;
+  return om;
+}
+
+// The head of every variant-T entry point: a handle, and one of variant T.
+static int t_entry(sg_handle* h, const char* who) {
+  if (!h) return SG_E_INVALID;
+  if (h->p.variant != SG_VARIANT_T) FAIL(h, SG_E_INVALID, "%s is a variant-T entry point", who);
+  return SG_OK;
+}
+
+// The reference's minimum lengths of x and xn, and the rows of xn (torchgate.py:215-220).
+static int t_min_lengths(sg_handle* h, int64_t B, int64_t L, const void* xn_dev, int64_t Bn, int64_t Ln) {
+  if (L < 2 * (int64_t)h->W) FAIL(h, SG_E_INVALID, "x must be bigger than %d", 2 * h->W);
+  if (xn_dev) {
+    if (Ln < 2 * (int64_t)h->W) FAIL(h, SG_E_INVALID, "xn must be bigger than %d", 2 * h->W);
+    if (Bn != 1 && Bn != B) FAIL(h, SG_E_INVALID, "xn rows (%lld) must be 1 or the batch size", (long long)Bn);
+  }
+  return SG_OK;
+}
+
 extern "C" int sg_workspace_bytes(const sg_handle* h, int64_t C, int64_t N, int32_t chunked, int64_t* bytes) {
   if (!h || !bytes || C < 1 || N < 1) return SG_E_INVALID;
   const int64_t cs = h->p.chunk_size, pad = h->p.padding;
@@ -3007,17 +3042,15 @@ extern "C" int sg_noise_stats(sg_handle* h, const void* noise_dev, int dtype, in
     ~Tag() { h->prof_override = -1; }
   } tag(h);
   int rc = SG_OK;
-  View v{};
-  v.x = noise_dev; v.dtype = dtype; v.stride = row_stride;  // one channel: its mean is the channel itself
+  View v = rows_view(noise_dev, dtype, row_stride, n);  // one channel: its mean is the channel itself
   if (C > 1) {
     if ((rc = ensure(h, h->yn, (size_t)n * sizeof(double)))) return rc;
     ProfScope ps(h, SG_STAGE_CHANNEL_MEAN, st);
     hipLaunchKernelGGL(k_channel_mean, dim3(grid_1d(n, 256)), dim3(256), 0, st, noise_dev, dtype, C, n,
                        row_stride, (double*)h->yn.p);
     HIPCHK(h, hipGetLastError());
-    v.x = h->yn.p; v.dtype = SG_F64; v.stride = n;
+    v = rows_view(h->yn.p, SG_F64, n, n);
   }
-  v.N = n; v.lo = 0; v.hi = n; v.cs = 0; v.pad = 0; v.Lp = n; v.n_chunks = 1; v.unit0 = 0;
   Geom g = make_geom(h, n);
   if ((rc = ensure_ws(h, g, 1))) return rc;
   h->t2_ready = false;
@@ -3110,12 +3143,8 @@ extern "C" int sg_filter_padded(sg_handle* h, const void* chunk_dev, int in_dtyp
   if (h->p.variant != SG_VARIANT_S) FAIL(h, SG_E_INVALID, "sg_filter_padded is a variant-S entry point");
   if (!chunk_dev || !out_dev || !dtype_ok(in_dtype) || !dtype_ok(out_dtype) || C < 1 || Lp < 1)
     FAIL(h, SG_E_INVALID, "sg_filter_padded: bad argument");
-  View v{};
-  v.x = chunk_dev; v.dtype = in_dtype; v.stride = in_stride; v.N = Lp; v.lo = 0; v.hi = Lp; v.cs = 0; v.pad = 0; v.Lp = Lp; v.n_chunks = 1;
-  OutMap om{};
-  om.out = out_dev; om.dtype = out_dtype; om.stride = out_stride;
-  om.p0 = 0; om.p1 = Lp; om.g_step = 0; om.g0 = 0; om.g_lo = 0; om.g_hi = Lp;
-  return run_S(h, v, C, om, (hipStream_t)stream);
+  return run_S(h, rows_view(chunk_dev, in_dtype, in_stride, Lp), C, whole_out(out_dev, out_dtype, out_stride, Lp),
+               (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3125,7 +3154,7 @@ extern "C" int sg_filter_padded(sg_handle* h, const void* chunk_dev, int in_dtyp
 static int stage_spectrum(sg_handle* h, const View& v, const Geom& g, int64_t u0, int64_t nb, const float* mask, void* spec_dev,
                           int dtype, hipStream_t st) {
   ProfScope ps(h, SG_STAGE_APPLY_ISTFT, st);
-  char* dst = (char*)spec_dev + (size_t)u0 * g.T * g.F * 2 * (dtype == SG_F64 ? 8 : 4);
+  char* dst = (char*)spec_dev + (size_t)u0 * g.T * g.F * 2 * elem_bytes(dtype);
   HIPCHK(h, spec_forward(v, g, nb, h->tw32.p, (const float*)h->wa32.p, mask, dst, dtype, st));
   return SG_OK;
 }
@@ -3145,142 +3174,162 @@ static FeatBank feat_bank(const sg_handle* h) {
 static int stage_features(sg_handle* h, const View& v, const Geom& g, int64_t u0, int64_t nb, const float* mask,
                           const FeatSink& fs, int dtype, hipStream_t st) {
   ProfScope ps(h, SG_STAGE_APPLY_ISTFT, st);
-  char* dst = (char*)fs.feat_dev + (size_t)u0 * g.T * h->n_filters * (dtype == SG_F64 ? 8 : 4);
+  char* dst = (char*)fs.feat_dev + (size_t)u0 * g.T * h->n_filters * elem_bytes(dtype);
   HIPCHK(h, feat_forward(v, g, nb, h->tw32.p, (const float*)h->wa32.p, mask, feat_bank(h), fs.power, fs.take_log, fs.eps, dst,
                          dtype, st));
   return SG_OK;
 }
 
-// sg_process_batch, sg_gate_spectrum and sg_gate_features: the statistics, decisions and smoothing of a batch of rows, then
-// the inverse transform (out_dev), or with spec_dev set the masked spectrogram itself, or with feat set its filterbank
-// features.  With spec_dev or feat the one-launch row gate is not taken, and the bit-mask route hands its decisions to the
+// Where process_batch_impl sends a gated batch: through the inverse transform to a waveform, or the masked spectrogram
+// itself, or its filterbank features.
+struct Sink {
+  enum Kind { WAVEFORM, SPECTRUM, FEATURES } kind;
+  void* out; int dtype; int64_t stride;   // WAVEFORM: [B][stride] of dtype
+  void* spec;                             // SPECTRUM: [B][T][F] pairs of the input's dtype
+  FeatSink feat;                          // FEATURES
+};
+
+// (host bookkeeping behind sg_debug_fetch: what the last sub-batch left in the workspace)
+static void note_batch(sg_handle* h, int64_t nb, const Geom& g, bool has_P, bool fused, bool fast) {
+  h->dbg_units = nb; h->dbg_T = g.T; h->dbg_has_P = has_P; h->dbg_fused = fused; h->dbg_fast = fast;
+}
+
+// default geometry, full reduction: decisions as bits -> exact integer smoothing -> uint16 sums
+// read by the fused apply kernel (same stages as the variant-S fused path)
+static bool bits_path_ok(const sg_handle* h) {
+  return h->fast_ok && !h->force_nofast && !h->force_unfused && h->p.prop_decrease == 1.0 &&
+         h->ktot <= 65535 && (!h->p.smooth_mask || (h->p.n_grad_time <= 96 && h->t_sm2_ok));
+}
+
+// The stationary decisions of one sub-batch (v.unit0 = u0): the thresholds (the shared noise row's in h->thresh, each
+// row's own noise, or the rows themselves), the power field and the compare.  With bits_path the decisions are bits in
+// h->bits, and with to_raw also the 0 / 1 float field in h->raw; without it the float field of stage_decide.  *branch:
+// which statement decided (sg_debug_counter 18), 0 when the bits are all that is left.
+static int decide_stationary(sg_handle* h, const View& v, View vn, const Geom& g, const Geom& gn, int64_t nb,
+                             const void* xn_dev, int64_t Bn, bool bits_path, bool to_raw, hipStream_t st, int64_t* branch) {
+  int rc;
+  double* thr = (double*)h->thr_rows.p;
+  const double* th;
+  int64_t ustride;
+  if (xn_dev && Bn == 1) {
+    th = (const double*)h->thresh.p; ustride = 0;
+  } else if (xn_dev) {
+    vn.unit0 = v.unit0;
+    if ((rc = stage_stats(h, vn, gn, nb, thr, st))) return rc;
+    th = thr; ustride = g.FS;
+  } else {
+    th = nullptr; ustride = g.FS;
+  }
+  // short rows: statistics + constants + decisions of a (row, 64 bands) tile in one kernel
+  const size_t tile_bytes = (size_t)g.T * 64 * sizeof(double);
+  const bool row_fused = bits_path && tile_bytes <= 64 * 1024;
+  if (row_fused) {
+    ProfScope ps(h, SG_STAGE_STFT_POWER, st);
+    HIPCHK(h, stft_any<double>(h, v, g, nb, (double*)h->P.p, nullptr, nullptr, 1.0, st));
+  } else {
+    if ((rc = stage_power(h, v, g, nb, st))) return rc;
+    if (!th) {
+      if ((rc = stage_colstats(h, g, nb, thr, st))) return rc;
+      th = thr;
+    }
+  }
+  if (!bits_path) {
+    *branch = SG_SPEC_DECIDE;
+    return stage_decide(h, g, nb, th, ustride, st);
+  }
+  const int wpr = (g.F + 63) / 64;
+  if ((rc = ensure(h, h->bits, (size_t)nb * g.T * wpr * 8))) return rc;
+  if ((rc = ensure(h, h->K16, (size_t)nb * g.T * g.FS * 2))) return rc;
+  if ((rc = ensure(h, h->T2, (size_t)nb * g.FS * 8))) return rc;
+  if (row_fused) {
+    ProfScope ps(h, SG_STAGE_DECIDE, st);
+    hipLaunchKernelGGL(k_row_decide, dim3((unsigned)wpr, (unsigned)nb), dim3(64 * STAT_TG), tile_bytes, st,
+                       (const double*)h->P.p, g, th, ustride, h->mag_scale, h->p.top_db, h->p.n_std_thresh,
+                       h->p.ddof, (double*)h->pmax.p, th ? nullptr : thr, (unsigned long long*)h->bits.p,
+                       wpr, db_fast_consts(h));
+    HIPCHK(h, hipGetLastError());
+  } else {
+    ProfScope ps(h, SG_STAGE_DECIDE, st);
+    // compare constants in the power domain per (row, band), then a pure compare per cell
+    hipLaunchKernelGGL(k_t2_rows, dim3(grid_1d(nb * g.FS, 256)), dim3(256), 0, st, th, ustride,
+                       (const double*)h->pmax.p, g, h->mag_scale, h->p.top_db, (double*)h->T2.p, nb);
+    HIPCHK(h, hipGetLastError());
+    hipLaunchKernelGGL(k_decide_bits_t2, dim3(grid_1d(nb * g.T * wpr * 64, 256)), dim3(256), 0, st,
+                       (const double*)h->P.p, g, (const double*)h->T2.p, (unsigned long long*)h->bits.p, wpr,
+                       nb);
+    HIPCHK(h, hipGetLastError());
+  }
+  *branch = 0;
+  if (!to_raw) return SG_OK;
+  // the spectrogram kernel reads a float mask in natural bin order: the decision bits as a 0 / 1 field, smoothed by
+  // the float kernels -- bitwise the mask process_batch_impl writes without the bit-mask route, at every geometry
+  ProfScope ps(h, SG_STAGE_DECIDE, st);
+  HIPCHK(h, spec_bits_to_raw((const unsigned long long*)h->bits.p, g, wpr, (float*)h->raw.p, nb, st));
+  *branch = (row_fused ? SG_SPEC_ROW_DECIDE : SG_SPEC_T2_BITS) | SG_SPEC_BITS_TO_RAW;
+  return SG_OK;
+}
+
+// sg_process_batch, sg_gate_spectrum and sg_gate_features: per sub-batch the decisions, the smoothing and the sink.  With
+// a spectrum or feature sink the one-launch row gate is not taken, and the bit-mask route hands its decisions to the
 // float smoothing kernels instead of the integer ones: the mask is then the float field of the general route (h->M) at
 // every geometry.
 static int process_batch_impl(sg_handle* h, const void* x_dev, int dtype, int64_t B, int64_t L, int64_t x_stride,
-                              const void* xn_dev, int64_t Bn, int64_t Ln, int64_t xn_stride, void* out_dev,
-                              int out_dtype, int64_t out_stride, float* mask_out_dev, void* spec_dev, void* stream,
-                              const FeatSink* feat = nullptr) {
-  const bool sink = spec_dev || feat;   // the mask is wanted as a float field in natural bin order
-  if (L < 2 * (int64_t)h->W) FAIL(h, SG_E_INVALID, "x must be bigger than %d", 2 * h->W);  // torchgate.py:215-216
-  if (xn_dev) {
-    if (Ln < 2 * (int64_t)h->W) FAIL(h, SG_E_INVALID, "xn must be bigger than %d", 2 * h->W);  // :219-220
-    if (Bn != 1 && Bn != B) FAIL(h, SG_E_INVALID, "xn rows (%lld) must be 1 or the batch size", (long long)Bn);
-  }
+                              const void* xn_dev, int64_t Bn, int64_t Ln, int64_t xn_stride, const Sink& sink,
+                              float* mask_out_dev, void* stream) {
+  const bool field = sink.kind != Sink::WAVEFORM;   // the mask is wanted as a float field in natural bin order
+  int rc;
+  if ((rc = t_min_lengths(h, B, L, xn_dev, Bn, Ln))) return rc;
   hipStream_t st = (hipStream_t)stream;
   h->dbg_rg = false;
   h->smooth_route = 0;   // (as in run_S)
-  View v{};
-  v.x = x_dev; v.dtype = dtype; v.stride = x_stride; v.N = L; v.lo = 0; v.hi = L; v.cs = 0; v.pad = 0; v.Lp = L; v.n_chunks = 1;
+  View v = rows_view(x_dev, dtype, x_stride, L);
   Geom g = make_geom(h, L);
-  OutMap om{};
-  om.out = out_dev; om.dtype = out_dtype; om.stride = out_stride;
-  om.p0 = 0; om.p1 = g.Lout; om.g_step = 0; om.g0 = 0; om.g_lo = 0; om.g_hi = g.Lout;
+  const OutMap om = whole_out(sink.out, sink.dtype, sink.stride, g.Lout);
+  const bool noise = xn_dev && h->p.stationary;
   View vn{};
   Geom gn{};
-  if (xn_dev && h->p.stationary) {
-    vn.x = xn_dev; vn.dtype = dtype; vn.stride = xn_stride; vn.N = Ln; vn.lo = 0; vn.hi = Ln; vn.cs = 0; vn.pad = 0; vn.Lp = Ln; vn.n_chunks = 1;
+  if (noise) {
+    vn = rows_view(xn_dev, dtype, xn_stride, Ln);
     gn = make_geom(h, Ln);
   }
   // size the workspace for the larger of the two geometries
-  Geom gbig = (xn_dev && h->p.stationary && gn.T > g.T) ? gn : g;
+  Geom gbig = (noise && gn.T > g.T) ? gn : g;
   int64_t ub = units_per_batch(h, gbig, B);
-  int rc = ensure_ws(h, gbig, ub);
-  if (rc) return rc;
-  double* thr = (double*)h->thr_rows.p;
-  if (xn_dev && h->p.stationary && Bn == 1) {
-    vn.unit0 = 0;
-    if ((rc = stage_stats(h, vn, gn, 1, (double*)h->thresh.p, st))) return rc;
-  }
+  if ((rc = ensure_ws(h, gbig, ub))) return rc;
+  if (noise && Bn == 1 && (rc = stage_stats(h, vn, gn, 1, (double*)h->thresh.p, st))) return rc;
+  const bool geom_fast = h->fast_ok && !h->force_nofast;
+  const bool smooths = h->p.stationary || !box_mask_ok(h);   // (the box mask comes smoothed out of its one kernel)
   int64_t n_sub = 0;
   for (int64_t u0 = 0; u0 < B; u0 += ub) {
     int64_t nb = std::min(ub, B - u0);
     int64_t branch = 0;   // (host bookkeeping behind sg_debug_counter 18: which statement below decided this sub-batch)
+    float* const mask_out = mask_out_dev ? mask_out_dev + (size_t)u0 * g.T * g.FS : nullptr;
     v.unit0 = u0;
+    // 1. the decisions
     if (h->p.stationary) {
-      const double* th;
-      int64_t ustride;
-      if (xn_dev && Bn == 1) {
-        th = (const double*)h->thresh.p; ustride = 0;
-      } else if (xn_dev) {
-        vn.unit0 = u0;
-        if ((rc = stage_stats(h, vn, gn, nb, thr, st))) return rc;
-        th = thr; ustride = g.FS;
-      } else {
-        th = nullptr; ustride = g.FS;
-      }
-      if (!sink && !xn_dev && rowgate_ok(h, g, B)) {
+      if (!field && !xn_dev && rowgate_ok(h, g, B)) {
         // one kernel per call: a workgroup per row (rowgate.hpp)
-        v.unit0 = 0;
-        View vr = v;
-        vr.unit0 = u0;
-        if ((rc = stage_row_gate(h, vr, g, nb, om, mask_out_dev ? mask_out_dev + (size_t)u0 * g.T * g.FS : nullptr, st)))
-          return rc;
-        h->dbg_units = nb; h->dbg_T = g.T; h->dbg_has_P = false; h->dbg_fused = true; h->dbg_fast = true;
+        if ((rc = stage_row_gate(h, v, g, nb, om, mask_out, st))) return rc;
+        note_batch(h, nb, g, false, true, true);
         h->dbg_has_raw = false; h->dbg_xbits = false; h->dbg_rg = true;
         h->dbg_db = 0; h->dbg_de = g.T;
         continue;
       }
-      // default geometry, full reduction: decisions as bits -> exact integer smoothing -> uint16 sums
-      // read by the fused apply kernel (same stages as the variant-S fused path)
-      const bool bits_path = h->fast_ok && !h->force_nofast && !h->force_unfused && h->p.prop_decrease == 1.0 &&
-                             h->ktot <= 65535 && (!h->p.smooth_mask || (h->p.n_grad_time <= 96 && h->t_sm2_ok));
-      // short rows: statistics + constants + decisions of a (row, 64 bands) tile in one kernel
-      const size_t tile_bytes = (size_t)g.T * 64 * sizeof(double);
-      const bool row_fused = bits_path && tile_bytes <= 64 * 1024;
-      if (row_fused) {
-        ProfScope ps(h, SG_STAGE_STFT_POWER, st);
-        HIPCHK(h, stft_any<double>(h, v, g, nb, (double*)h->P.p, nullptr, nullptr, 1.0, st));
-      } else {
-        if ((rc = stage_power(h, v, g, nb, st))) return rc;
-        if (!th) {
-          if ((rc = stage_colstats(h, g, nb, thr, st))) return rc;
-          th = thr;
+      const bool bits_path = bits_path_ok(h);
+      if ((rc = decide_stationary(h, v, vn, g, gn, nb, xn_dev, Bn, bits_path, field, st, &branch))) return rc;
+      if (bits_path && !field) {
+        // the bits straight through the integer smoothing into the fused apply kernel
+        if ((rc = stage_smooth_bits(h, g, nb, true, 0, g.T, st))) return rc;
+        if (mask_out) {  // float mask (natural bin order) for the backward pass
+          hipLaunchKernelGGL(k_k16_to_mask_perm, dim3(grid_1d(nb * g.T * g.FS, 256)), dim3(256), 0, st,
+                             (const unsigned short*)h->K16.p, g, 1.0f / (float)h->ktot, mask_out, nb);
+          HIPCHK(h, hipGetLastError());
         }
+        if ((rc = stage_apply_fast(h, v, g, nb, om, nullptr, 1, st))) return rc;
+        note_batch(h, nb, g, true, true, true);
+        h->dbg_db = 0; h->dbg_de = g.T;
+        continue;
       }
-      if (bits_path) {
-        const int wpr = (g.F + 63) / 64;
-        if ((rc = ensure(h, h->bits, (size_t)nb * g.T * wpr * 8))) return rc;
-        if ((rc = ensure(h, h->K16, (size_t)nb * g.T * g.FS * 2))) return rc;
-        if ((rc = ensure(h, h->T2, (size_t)nb * g.FS * 8))) return rc;
-        if (row_fused) {
-          ProfScope ps(h, SG_STAGE_DECIDE, st);
-          hipLaunchKernelGGL(k_row_decide, dim3((unsigned)wpr, (unsigned)nb), dim3(64 * STAT_TG), tile_bytes, st,
-                             (const double*)h->P.p, g, th, ustride, h->mag_scale, h->p.top_db, h->p.n_std_thresh,
-                             h->p.ddof, (double*)h->pmax.p, th ? nullptr : thr, (unsigned long long*)h->bits.p,
-                             wpr, db_fast_consts(h));
-          HIPCHK(h, hipGetLastError());
-        } else {
-          ProfScope ps(h, SG_STAGE_DECIDE, st);
-          // compare constants in the power domain per (row, band), then a pure compare per cell
-          hipLaunchKernelGGL(k_t2_rows, dim3(grid_1d(nb * g.FS, 256)), dim3(256), 0, st, th, ustride,
-                             (const double*)h->pmax.p, g, h->mag_scale, h->p.top_db, (double*)h->T2.p, nb);
-          HIPCHK(h, hipGetLastError());
-          hipLaunchKernelGGL(k_decide_bits_t2, dim3(grid_1d(nb * g.T * wpr * 64, 256)), dim3(256), 0, st,
-                             (const double*)h->P.p, g, (const double*)h->T2.p, (unsigned long long*)h->bits.p, wpr,
-                             nb);
-          HIPCHK(h, hipGetLastError());
-        }
-        if (!sink) {
-          if ((rc = stage_smooth_bits(h, g, nb, true, 0, g.T, st))) return rc;
-          if (mask_out_dev) {  // float mask (natural bin order) for the backward pass
-            hipLaunchKernelGGL(k_k16_to_mask_perm, dim3(grid_1d(nb * g.T * g.FS, 256)), dim3(256), 0, st,
-                               (const unsigned short*)h->K16.p, g, 1.0f / (float)h->ktot,
-                               mask_out_dev + (size_t)u0 * g.T * g.FS, nb);
-            HIPCHK(h, hipGetLastError());
-          }
-          if ((rc = stage_apply_fast(h, v, g, nb, om, nullptr, 1, st))) return rc;
-          h->dbg_units = nb; h->dbg_T = g.T; h->dbg_has_P = true; h->dbg_fused = true; h->dbg_fast = true;
-          h->dbg_db = 0; h->dbg_de = g.T;
-          continue;
-        }
-        // the spectrogram kernel reads a float mask in natural bin order: the decision bits as a 0 / 1 field, smoothed by
-        // the float kernels below -- bitwise the mask this function writes without the bit-mask route, at every geometry
-        ProfScope ps(h, SG_STAGE_DECIDE, st);
-        HIPCHK(h, spec_bits_to_raw((const unsigned long long*)h->bits.p, g, wpr, (float*)h->raw.p, nb, st));
-        branch = (row_fused ? SG_SPEC_ROW_DECIDE : SG_SPEC_T2_BITS) | SG_SPEC_BITS_TO_RAW;
-      }
-      if (!bits_path && (rc = stage_decide(h, g, nb, th, ustride, st))) return rc;
-      if (!bits_path) branch = SG_SPEC_DECIDE;
     } else if (box_mask_ok(h)) {
       if ((rc = stage_box_mask(h, v, g, nb, st))) return rc;
       branch = SG_SPEC_BOX_MASK;
@@ -3288,20 +3337,19 @@ static int process_batch_impl(sg_handle* h, const void* x_dev, int dtype, int64_
       if ((rc = stage_nonstat_raw(h, v, g, nb, st))) return rc;
       branch = SG_SPEC_NONSTAT_RAW;
     }
-    const bool geom_fast = h->fast_ok && !h->force_nofast;
-    // the spectrogram reads the mask wherever it lies: smoothed straight into the caller's buffer, without the copy below
-    float* const mask_direct = (sink && mask_out_dev && (h->p.stationary || !box_mask_ok(h)))
-                                   ? mask_out_dev + (size_t)u0 * g.T * g.FS : nullptr;
-    if (h->p.stationary || !box_mask_ok(h))
-      if ((rc = stage_smooth(h, g, nb, st, mask_direct))) return rc;
-    if (mask_out_dev && !mask_direct)
-      HIPCHK(h, hipMemcpyAsync(mask_out_dev + (size_t)u0 * g.T * g.FS, h->M.p, (size_t)nb * g.T * g.FS * 4,
-                               hipMemcpyDeviceToDevice, st));
-    if (spec_dev) {
-      if ((rc = stage_spectrum(h, v, g, u0, nb, mask_direct ? mask_direct : (const float*)h->M.p, spec_dev, dtype, st))) return rc;
+    // 2. the smoothing.  The spectrogram reads the mask wherever it lies: smoothed straight into the caller's buffer,
+    // without the copy below
+    float* const mask_direct = (field && smooths) ? mask_out : nullptr;
+    if (smooths && (rc = stage_smooth(h, g, nb, st, mask_direct))) return rc;
+    if (mask_out && !mask_direct)
+      HIPCHK(h, hipMemcpyAsync(mask_out, h->M.p, (size_t)nb * g.T * g.FS * 4, hipMemcpyDeviceToDevice, st));
+    // 3. the sink
+    const float* const mask = mask_direct ? mask_direct : (const float*)h->M.p;
+    if (sink.kind == Sink::SPECTRUM) {
+      if ((rc = stage_spectrum(h, v, g, u0, nb, mask, sink.spec, dtype, st))) return rc;
       h->spec_route = branch | (mask_direct ? SG_SPEC_MASK_DIRECT : 0) | (++n_sub << 16);
-    } else if (feat) {
-      if ((rc = stage_features(h, v, g, u0, nb, mask_direct ? mask_direct : (const float*)h->M.p, *feat, dtype, st))) return rc;
+    } else if (sink.kind == Sink::FEATURES) {
+      if ((rc = stage_features(h, v, g, u0, nb, mask, sink.feat, dtype, st))) return rc;
     } else if (geom_fast) {
       if ((rc = stage_apply_fast(h, v, g, nb, om, (const float*)h->M.p, 1, st))) return rc;
     } else if (const RegGeom* r = reg_geom(h)) {
@@ -3309,12 +3357,8 @@ static int process_batch_impl(sg_handle* h, const void* x_dev, int dtype, int64_
     } else {
       if ((rc = stage_apply_ola(h, v, g, nb, (const float*)h->M.p, om, 1, st))) return rc;
     }
-    h->dbg_units = nb;
-    h->dbg_T = g.T;
-    h->dbg_has_P = h->p.stationary != 0;
-    h->dbg_has_raw = h->p.stationary || !box_mask_ok(h);
-    h->dbg_fused = false;
-    h->dbg_fast = geom_fast;
+    note_batch(h, nb, g, h->p.stationary != 0, false, geom_fast);
+    h->dbg_has_raw = smooths;
   }
   return SG_OK;
 }
@@ -3322,12 +3366,11 @@ static int process_batch_impl(sg_handle* h, const void* x_dev, int dtype, int64_
 extern "C" int sg_process_batch(sg_handle* h, const void* x_dev, int dtype, int64_t B, int64_t L, int64_t x_stride,
                                 const void* xn_dev, int64_t Bn, int64_t Ln, int64_t xn_stride, void* out_dev,
                                 int out_dtype, int64_t out_stride, float* mask_out_dev, void* stream) {
-  if (!h) return SG_E_INVALID;
-  if (h->p.variant != SG_VARIANT_T) FAIL(h, SG_E_INVALID, "sg_process_batch is a variant-T entry point");
+  if (int rc = t_entry(h, "sg_process_batch")) return rc;
   if (!x_dev || !out_dev || !dtype_ok(dtype) || !dtype_ok(out_dtype) || B < 1)
     FAIL(h, SG_E_INVALID, "sg_process_batch: bad argument");
-  return process_batch_impl(h, x_dev, dtype, B, L, x_stride, xn_dev, Bn, Ln, xn_stride, out_dev, out_dtype, out_stride,
-                            mask_out_dev, nullptr, stream);
+  const Sink sink{Sink::WAVEFORM, out_dev, out_dtype, out_stride, nullptr, {}};
+  return process_batch_impl(h, x_dev, dtype, B, L, x_stride, xn_dev, Bn, Ln, xn_stride, sink, mask_out_dev, stream);
 }
 
 // TorchGate.gated_stft: X * mask in torch.stft's layout (spec.hpp)
@@ -3336,52 +3379,59 @@ static bool spectrum_geom_ok(const sg_handle* h) { return spec_native(h->n) && !
 extern "C" int sg_gate_spectrum(sg_handle* h, const void* x_dev, int dtype, int64_t B, int64_t L, int64_t x_stride,
                                 const void* xn_dev, int64_t Bn, int64_t Ln, int64_t xn_stride, void* spec_dev,
                                 float* mask_out_dev, void* stream) {
-  if (!h) return SG_E_INVALID;
-  h->spec_route = 0;   // (sg_debug_counter 18 speaks of THIS call)
-  if (h->p.variant != SG_VARIANT_T) FAIL(h, SG_E_INVALID, "sg_gate_spectrum is a variant-T entry point");
+  if (int rc = t_entry(h, "sg_gate_spectrum")) return rc;
+  h->spec_route = 0;   // (sg_debug_counter 18 speaks of THIS call; only a variant-T handle ever sets it)
   if (!x_dev || !spec_dev || (dtype != SG_F32 && dtype != SG_F64) || B < 1)
     FAIL(h, SG_E_INVALID, "sg_gate_spectrum: bad argument");
   if (!spectrum_geom_ok(h))
     FAIL(h, SG_E_UNSUPPORTED, "sg_gate_spectrum: n_fft=%d (powers of two from 256 to 4096 only)", h->n);
-  return process_batch_impl(h, x_dev, dtype, B, L, x_stride, xn_dev, Bn, Ln, xn_stride, nullptr, dtype, 0, mask_out_dev,
-                            spec_dev, stream);
+  const Sink sink{Sink::SPECTRUM, nullptr, dtype, 0, spec_dev, {}};
+  return process_batch_impl(h, x_dev, dtype, B, L, x_stride, xn_dev, Bn, Ln, xn_stride, sink, mask_out_dev, stream);
 }
 
-// Adjoint of Y = M .* rfft( Wa frames(x) ) with M fixed: g_x = frames^T( Wa Re sum_k M[k] g[k] e^{+2 pi i k j / n} ), every bin
-// with weight 1 and no envelope division (the adjoint of an STFT, not an ISTFT).  Windowed frames into h->seg, then one gather.
+// The backward of the spectrum and feature outputs, per sub-batch: `frames(u0, nb, mask, seg)` launches the windowed adjoint
+// frames of rows [u0, u0 + nb) into h->seg (mask: theirs), then one gather (the adjoint of an STFT: every bin with weight 1
+// and no envelope division) adds them onto grad_x.
+template <class Frames>
+static int spectrum_backward_loop(sg_handle* h, int dtype, int64_t B, int64_t L, const float* mask_dev, void* grad_x_dev,
+                                  int64_t gx_stride, hipStream_t st, Frames frames) {
+  const Geom g = make_geom(h, L);
+  const int64_t ub = units_per_batch(h, g, B);
+  int rc;
+  if ((rc = ensure(h, h->seg, (size_t)ub * g.T * g.n * 4))) return rc;
+  for (int64_t u0 = 0; u0 < B; u0 += ub) {
+    const int64_t nb = std::min(ub, B - u0);
+    {
+      ProfScope ps(h, SG_STAGE_APPLY_ISTFT, st);
+      HIPCHK(h, frames(g, u0, nb, mask_dev + (size_t)u0 * g.T * g.FS, (float*)h->seg.p));
+    }
+    ProfScope ps(h, SG_STAGE_OLA, st);
+    HIPCHK(h, spec_backward_ola(g, nb, L, (const float*)h->seg.p, (char*)grad_x_dev + (size_t)u0 * gx_stride * elem_bytes(dtype),
+                                dtype, gx_stride, st));
+  }
+  return SG_OK;
+}
+
+// Adjoint of Y = M .* rfft( Wa frames(x) ) with M fixed: g_x = frames^T( Wa Re sum_k M[k] g[k] e^{+2 pi i k j / n} ).
 extern "C" int sg_gate_spectrum_backward(sg_handle* h, const void* grad_spec_dev, int dtype, int64_t B, int64_t L,
                                          const float* mask_dev, void* grad_x_dev, int64_t gx_stride, void* stream) {
-  if (!h) return SG_E_INVALID;
-  if (h->p.variant != SG_VARIANT_T) FAIL(h, SG_E_INVALID, "sg_gate_spectrum_backward is a variant-T entry point");
+  if (int rc = t_entry(h, "sg_gate_spectrum_backward")) return rc;
   if (!grad_spec_dev || !grad_x_dev || !mask_dev || B < 1 || (dtype != SG_F32 && dtype != SG_F64))
     FAIL(h, SG_E_INVALID, "sg_gate_spectrum_backward: bad argument");
   if (L < 2 * (int64_t)h->W) FAIL(h, SG_E_INVALID, "x must be bigger than %d", 2 * h->W);
   if (!spectrum_geom_ok(h))
     FAIL(h, SG_E_UNSUPPORTED, "sg_gate_spectrum_backward: n_fft=%d (powers of two from 256 to 4096 only)", h->n);
   hipStream_t st = (hipStream_t)stream;
-  const Geom g = make_geom(h, L);
-  const int64_t ub = units_per_batch(h, g, B);
-  int rc;
-  if ((rc = ensure(h, h->seg, (size_t)ub * g.T * g.n * 4))) return rc;
-  const size_t esz = dtype == SG_F64 ? 8 : 4;
-  for (int64_t u0 = 0; u0 < B; u0 += ub) {
-    const int64_t nb = std::min(ub, B - u0);
-    {
-      ProfScope ps(h, SG_STAGE_APPLY_ISTFT, st);
-      HIPCHK(h, spec_backward_frames(g, nb, h->tw32.p, (const float*)h->wa32.p, mask_dev + (size_t)u0 * g.T * g.FS,
-                                     (const char*)grad_spec_dev + (size_t)u0 * g.T * g.F * 2 * esz, dtype, (float*)h->seg.p, st));
-    }
-    ProfScope ps(h, SG_STAGE_OLA, st);
-    HIPCHK(h, spec_backward_ola(g, nb, L, (const float*)h->seg.p, (char*)grad_x_dev + (size_t)u0 * gx_stride * esz, dtype,
-                                gx_stride, st));
-  }
-  return SG_OK;
+  return spectrum_backward_loop(h, dtype, B, L, mask_dev, grad_x_dev, gx_stride, st,
+                                [&](const Geom& g, int64_t u0, int64_t nb, const float* mask, float* seg) {
+    return spec_backward_frames(g, nb, h->tw32.p, (const float*)h->wa32.p, mask,
+                                (const char*)grad_spec_dev + (size_t)u0 * g.T * g.F * 2 * elem_bytes(dtype), dtype, seg, st);
+  });
 }
 
 // TorchGate.gated_filterbank (feat.hpp).  The bank is host data: validated, transposed and given its hull tables here.
 extern "C" int sg_set_filterbank(sg_handle* h, const float* fb_host, int32_t n_filters) {
-  if (!h) return SG_E_INVALID;
-  if (h->p.variant != SG_VARIANT_T) FAIL(h, SG_E_INVALID, "sg_set_filterbank is a variant-T entry point");
+  if (int rc = t_entry(h, "sg_set_filterbank")) return rc;
   if (!fb_host || n_filters < 1 || n_filters > FEAT_MAX_FILTERS)
     FAIL(h, SG_E_INVALID, "sg_set_filterbank: bad argument (1 <= n_filters <= %d)", FEAT_MAX_FILTERS);
   if (!spectrum_geom_ok(h))
@@ -3414,15 +3464,13 @@ static int features_args_ok(sg_handle* h, const char* who, int power, double eps
 extern "C" int sg_gate_features(sg_handle* h, const void* x_dev, int dtype, int64_t B, int64_t L, int64_t x_stride,
                                 const void* xn_dev, int64_t Bn, int64_t Ln, int64_t xn_stride, int32_t power, int32_t take_log,
                                 double eps, void* feat_dev, float* mask_out_dev, void* stream) {
-  if (!h) return SG_E_INVALID;
-  if (h->p.variant != SG_VARIANT_T) FAIL(h, SG_E_INVALID, "sg_gate_features is a variant-T entry point");
+  if (int rc = t_entry(h, "sg_gate_features")) return rc;
   if (!x_dev || !feat_dev || (dtype != SG_F32 && dtype != SG_F64) || B < 1)
     FAIL(h, SG_E_INVALID, "sg_gate_features: bad argument");
   int rc;
   if ((rc = features_args_ok(h, "sg_gate_features", power, eps))) return rc;
-  const FeatSink fs{feat_dev, power, take_log != 0, eps};
-  return process_batch_impl(h, x_dev, dtype, B, L, x_stride, xn_dev, Bn, Ln, xn_stride, nullptr, dtype, 0, mask_out_dev,
-                            nullptr, stream, &fs);
+  const Sink sink{Sink::FEATURES, nullptr, dtype, 0, nullptr, FeatSink{feat_dev, power, take_log != 0, eps}};
+  return process_batch_impl(h, x_dev, dtype, B, L, x_stride, xn_dev, Bn, Ln, xn_stride, sink, mask_out_dev, stream);
 }
 
 // Adjoint of sg_gate_features w.r.t. x with mask and bank fixed: the frames are transformed again from x, G = dL/dX formed
@@ -3430,8 +3478,7 @@ extern "C" int sg_gate_features(sg_handle* h, const void* x_dev, int dtype, int6
 extern "C" int sg_gate_features_backward(sg_handle* h, const void* x_dev, int dtype, int64_t B, int64_t L, int64_t x_stride,
                                          const void* grad_feat_dev, const float* mask_dev, int32_t power, int32_t take_log,
                                          double eps, void* grad_x_dev, int64_t gx_stride, void* stream) {
-  if (!h) return SG_E_INVALID;
-  if (h->p.variant != SG_VARIANT_T) FAIL(h, SG_E_INVALID, "sg_gate_features_backward is a variant-T entry point");
+  if (int rc = t_entry(h, "sg_gate_features_backward")) return rc;
   if (!x_dev || !grad_feat_dev || !grad_x_dev || !mask_dev || B < 1 || (dtype != SG_F32 && dtype != SG_F64) || x_stride < L ||
       gx_stride < L)
     FAIL(h, SG_E_INVALID, "sg_gate_features_backward: bad argument");
@@ -3439,27 +3486,14 @@ extern "C" int sg_gate_features_backward(sg_handle* h, const void* x_dev, int dt
   int rc;
   if ((rc = features_args_ok(h, "sg_gate_features_backward", power, eps))) return rc;
   hipStream_t st = (hipStream_t)stream;
-  View v{};
-  v.x = x_dev; v.dtype = dtype; v.stride = x_stride; v.N = L; v.lo = 0; v.hi = L; v.cs = 0; v.pad = 0; v.Lp = L; v.n_chunks = 1;
-  const Geom g = make_geom(h, L);
-  const int64_t ub = units_per_batch(h, g, B);
-  if ((rc = ensure(h, h->seg, (size_t)ub * g.T * g.n * 4))) return rc;
-  const size_t esz = dtype == SG_F64 ? 8 : 4;
-  for (int64_t u0 = 0; u0 < B; u0 += ub) {
-    const int64_t nb = std::min(ub, B - u0);
+  View v = rows_view(x_dev, dtype, x_stride, L);
+  return spectrum_backward_loop(h, dtype, B, L, mask_dev, grad_x_dev, gx_stride, st,
+                                [&](const Geom& g, int64_t u0, int64_t nb, const float* mask, float* seg) {
     v.unit0 = u0;
-    {
-      ProfScope ps(h, SG_STAGE_APPLY_ISTFT, st);
-      HIPCHK(h, feat_backward_frames(v, g, nb, h->tw32.p, (const float*)h->wa32.p, mask_dev + (size_t)u0 * g.T * g.FS,
-                                     feat_bank(h), power, take_log != 0, eps,
-                                     (const char*)grad_feat_dev + (size_t)u0 * g.T * h->n_filters * esz, dtype,
-                                     (float*)h->seg.p, st));
-    }
-    ProfScope ps(h, SG_STAGE_OLA, st);
-    HIPCHK(h, spec_backward_ola(g, nb, L, (const float*)h->seg.p, (char*)grad_x_dev + (size_t)u0 * gx_stride * esz, dtype,
-                                gx_stride, st));
-  }
-  return SG_OK;
+    return feat_backward_frames(v, g, nb, h->tw32.p, (const float*)h->wa32.p, mask, feat_bank(h), power, take_log != 0, eps,
+                                (const char*)grad_feat_dev + (size_t)u0 * g.T * h->n_filters * elem_bytes(dtype), dtype, seg,
+                                st);
+  });
 }
 
 // Adjoint of y = D^-1 OLA( Ws irfft( M .* rfft( Wa frames(x) ) ) ) with M fixed:
@@ -3469,8 +3503,7 @@ extern "C" int sg_gate_features_backward(sg_handle* h, const void* x_dev, int dt
 extern "C" int sg_process_batch_backward(sg_handle* h, const void* grad_out_dev, int dtype, int64_t B, int64_t L,
                                          int64_t go_stride, const float* mask_dev, void* grad_x_dev,
                                          int64_t gx_stride, void* stream) {
-  if (!h) return SG_E_INVALID;
-  if (h->p.variant != SG_VARIANT_T) FAIL(h, SG_E_INVALID, "sg_process_batch_backward is a variant-T entry point");
+  if (int rc = t_entry(h, "sg_process_batch_backward")) return rc;
   if (!grad_out_dev || !grad_x_dev || !mask_dev || B < 1 || (dtype != SG_F32 && dtype != SG_F64))
     FAIL(h, SG_E_INVALID, "sg_process_batch_backward: bad argument");
   hipStream_t st = (hipStream_t)stream;
@@ -3483,16 +3516,10 @@ extern "C" int sg_process_batch_backward(sg_handle* h, const void* grad_out_dev,
     h->dbg_bwd_route = SG_BWD_ROW;
     ProfScope ps(h, SG_STAGE_APPLY_FAST, st);
     fast::RowBwdArgs A;
-    View v{};
-    v.x = grad_out_dev; v.dtype = dtype; v.stride = go_stride; v.N = Lq; v.lo = 0; v.hi = Lq; v.cs = 0; v.pad = 0; v.Lp = Lq;
-    v.n_chunks = 1; v.unit0 = 0;
-    A.view = v;
+    A.view = rows_view(grad_out_dev, dtype, go_stride, Lq);
     A.g = g;
     A.g.Lout = L;   // the adjoint scatters back onto all L input samples
-    OutMap om{};
-    om.out = grad_x_dev; om.dtype = dtype; om.stride = gx_stride;
-    om.p0 = 0; om.p1 = L; om.g_step = 0; om.g0 = 0; om.g_lo = 0; om.g_hi = L;
-    A.om = om;
+    A.om = whole_out(grad_x_dev, dtype, gx_stride, L);
     A.win = (const float*)h->wa32.p;
     A.wsq = (const float*)h->wsq32.p;
     A.invn = (const float*)h->invn.p;
@@ -3514,20 +3541,15 @@ extern "C" int sg_process_batch_backward(sg_handle* h, const void* grad_out_dev,
     const int64_t nb = std::min(ub, B - u0);
     {
       dim3 grid((unsigned)((Lq + 255) / 256), (unsigned)nb);
-      const char* src = (const char*)grad_out_dev + (size_t)u0 * go_stride * (dtype == SG_F64 ? 8 : 4);
+      const char* src = (const char*)grad_out_dev + (size_t)u0 * go_stride * elem_bytes(dtype);
       hipLaunchKernelGGL(k_env_scale, grid, dim3(256), 0, st, (const void*)src, dtype, go_stride, g,
                          (const float*)h->wsq32.p, (float*)h->yn.p, Lq);
       HIPCHK(h, hipGetLastError());
     }
-    View v{};
-    v.x = h->yn.p; v.dtype = SG_F32; v.stride = Lq; v.N = Lq; v.lo = 0; v.hi = Lq; v.cs = 0; v.pad = 0; v.Lp = Lq;
-    v.n_chunks = 1; v.unit0 = 0;
+    const View v = rows_view(h->yn.p, SG_F32, Lq, Lq);
     Geom gb = g;
     gb.Lout = L;  // the adjoint scatters back onto all L input samples
-    OutMap om{};
-    om.out = (char*)grad_x_dev + (size_t)u0 * gx_stride * (dtype == SG_F64 ? 8 : 4);
-    om.dtype = dtype; om.stride = gx_stride;
-    om.p0 = 0; om.p1 = L; om.g_step = 0; om.g0 = 0; om.g_lo = 0; om.g_hi = L;
+    const OutMap om = whole_out((char*)grad_x_dev + (size_t)u0 * gx_stride * elem_bytes(dtype), dtype, gx_stride, L);
     const float* mk = mask_dev + (size_t)u0 * g.T * g.FS;
     if (h->fast_ok && !h->force_nofast) {
       h->dbg_bwd_route = SG_BWD_FAST;
@@ -3550,10 +3572,8 @@ extern "C" int sg_stft(sg_handle* h, const void* x_dev, int dtype, int64_t B, in
                        double* z_dev, void* stream) {
   if (!h) return SG_E_INVALID;
   if (!x_dev || !z_dev || !dtype_ok(dtype) || B < 1 || L < h->W) FAIL(h, SG_E_INVALID, "sg_stft: bad argument");
-  View v{};
-  v.x = x_dev; v.dtype = dtype; v.stride = stride; v.N = L; v.lo = 0; v.hi = L; v.cs = 0; v.pad = 0; v.Lp = L; v.n_chunks = 1; v.unit0 = 0;
   Geom g = make_geom(h, L);
-  HIPCHK(h, stft_any<double>(h, v, g, B, nullptr, nullptr, z_dev, h->mag_scale, (hipStream_t)stream));
+  HIPCHK(h, stft_any<double>(h, rows_view(x_dev, dtype, stride, L), g, B, nullptr, nullptr, z_dev, h->mag_scale, (hipStream_t)stream));
   return SG_OK;
 }
 
@@ -3891,16 +3911,11 @@ extern "C" int sg_process_rows(sg_handle* h, const void* x_dev, int dtype, int64
                                const int64_t* lengths, const void* xn_dev, int64_t Bn, int64_t Ln, int64_t xn_stride,
                                const int64_t* xn_lengths, void* out_dev, int out_dtype, int64_t out_stride,
                                float* mask_out_dev, void* stream) {
-  if (!h) return SG_E_INVALID;
-  if (h->p.variant != SG_VARIANT_T) FAIL(h, SG_E_INVALID, "sg_process_rows is a variant-T entry point");
+  if (int rc = t_entry(h, "sg_process_rows")) return rc;
   if (!x_dev || !out_dev || (dtype != SG_F32 && dtype != SG_F64) || (out_dtype != SG_F32 && out_dtype != SG_F64) || B < 1 ||
       x_stride < L || out_stride < 0)
     FAIL(h, SG_E_INVALID, "sg_process_rows: bad argument");
-  if (L < 2 * (int64_t)h->W) FAIL(h, SG_E_INVALID, "x must be bigger than %d", 2 * h->W);  // torchgate.py:215-216
-  if (xn_dev) {
-    if (Ln < 2 * (int64_t)h->W) FAIL(h, SG_E_INVALID, "xn must be bigger than %d", 2 * h->W);  // :219-220
-    if (Bn != 1 && Bn != B) FAIL(h, SG_E_INVALID, "xn rows (%lld) must be 1 or the batch size", (long long)Bn);
-  }
+  if (int rc = t_min_lengths(h, B, L, xn_dev, Bn, Ln)) return rc;
   return sg::rw_process(&h->rw, rg_ctx(h), h->p.n_movemean, x_dev, dtype, B, L, x_stride, lengths, xn_dev, Bn, Ln, xn_stride,
                         xn_lengths, out_dev, out_dtype, out_stride, mask_out_dev, rw_budget(h), (hipStream_t)stream, &h->err);
 }
@@ -3908,8 +3923,7 @@ extern "C" int sg_process_rows(sg_handle* h, const void* x_dev, int dtype, int64
 extern "C" int sg_process_rows_backward(sg_handle* h, const void* grad_out_dev, int dtype, int64_t B, int64_t L,
                                         int64_t go_stride, const int64_t* lengths, const float* mask_dev, void* grad_x_dev,
                                         int64_t gx_stride, void* stream) {
-  if (!h) return SG_E_INVALID;
-  if (h->p.variant != SG_VARIANT_T) FAIL(h, SG_E_INVALID, "sg_process_rows_backward is a variant-T entry point");
+  if (int rc = t_entry(h, "sg_process_rows_backward")) return rc;
   if (!grad_out_dev || !grad_x_dev || !mask_dev || B < 1 || (dtype != SG_F32 && dtype != SG_F64) || gx_stride < L ||
       L < 2 * (int64_t)h->W)
     FAIL(h, SG_E_INVALID, "sg_process_rows_backward: bad argument");
@@ -3922,15 +3936,10 @@ extern "C" int sg_process_rows_backward(sg_handle* h, const void* grad_out_dev, 
 extern "C" int sg_gate_spectrum_rows(sg_handle* h, const void* x_dev, int dtype, int64_t B, int64_t L, int64_t x_stride,
                                      const int64_t* lengths, const void* xn_dev, int64_t Bn, int64_t Ln, int64_t xn_stride,
                                      const int64_t* xn_lengths, void* spec_dev, float* mask_out_dev, void* stream) {
-  if (!h) return SG_E_INVALID;
-  if (h->p.variant != SG_VARIANT_T) FAIL(h, SG_E_INVALID, "sg_gate_spectrum_rows is a variant-T entry point");
+  if (int rc = t_entry(h, "sg_gate_spectrum_rows")) return rc;
   if (!x_dev || !spec_dev || (dtype != SG_F32 && dtype != SG_F64) || B < 1 || x_stride < L)
     FAIL(h, SG_E_INVALID, "sg_gate_spectrum_rows: bad argument");
-  if (L < 2 * (int64_t)h->W) FAIL(h, SG_E_INVALID, "x must be bigger than %d", 2 * h->W);  // torchgate.py:215-216
-  if (xn_dev) {
-    if (Ln < 2 * (int64_t)h->W) FAIL(h, SG_E_INVALID, "xn must be bigger than %d", 2 * h->W);  // :219-220
-    if (Bn != 1 && Bn != B) FAIL(h, SG_E_INVALID, "xn rows (%lld) must be 1 or the batch size", (long long)Bn);
-  }
+  if (int rc = t_min_lengths(h, B, L, xn_dev, Bn, Ln)) return rc;
   return sg::rw_spectrum(&h->rw, rg_ctx(h), h->p.n_movemean, x_dev, dtype, B, L, x_stride, lengths, xn_dev, Bn, Ln, xn_stride,
                          xn_lengths, spec_dev, mask_out_dev, rw_budget(h), (hipStream_t)stream, &h->err);
 }
@@ -3938,8 +3947,7 @@ extern "C" int sg_gate_spectrum_rows(sg_handle* h, const void* x_dev, int dtype,
 extern "C" int sg_gate_spectrum_rows_backward(sg_handle* h, const void* grad_spec_dev, int dtype, int64_t B, int64_t L,
                                               const int64_t* lengths, const float* mask_dev, void* grad_x_dev,
                                               int64_t gx_stride, void* stream) {
-  if (!h) return SG_E_INVALID;
-  if (h->p.variant != SG_VARIANT_T) FAIL(h, SG_E_INVALID, "sg_gate_spectrum_rows_backward is a variant-T entry point");
+  if (int rc = t_entry(h, "sg_gate_spectrum_rows_backward")) return rc;
   if (!grad_spec_dev || !grad_x_dev || !mask_dev || B < 1 || (dtype != SG_F32 && dtype != SG_F64) || gx_stride < L ||
       L < 2 * (int64_t)h->W)
     FAIL(h, SG_E_INVALID, "sg_gate_spectrum_rows_backward: bad argument");

@@ -4,7 +4,15 @@
 (1, 1, 2*n_grad_freq+1, 2*n_grad_time+1) (or None), so state_dicts round-trip with the
 reference's.  The mask is computed without gradient (torchgate.py:126,167) and the output
 is differentiable w.r.t. ``x`` through STFT -> (x mask) -> ISTFT.
+
+``forward``, ``gated_stft`` and ``gated_filterbank`` share one call path.  ``TorchGate._prepare`` validates and normalises
+every call (the errors and their order, the dtype promotion, the noise rows, the host lengths, whether the rows are in fact
+all full), and ``_NativeFunction`` is the one ``autograd.Function`` of the native routes, driven by a row of ``_ROUTES``
+(which ``_ffi.Gate`` methods, whether lengths ride along, whether the mask is an output, whether x is saved).  A further
+native output is a row of that table and a kernel.  The fallbacks for an n_fft without native kernels -- the per-row loops,
+the composed ``torch.stft * mask`` and the composed filterbank matmul -- take their inputs from the same ``_prepare``.
 """
+import collections
 import hashlib
 import math
 import weakref
@@ -18,92 +26,18 @@ from noisereduce_amd.torchgate import rows as _rows
 from noisereduce_amd.torchgate.utils import linspace
 
 
-class _GateFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, xn, module):
-        gate = module._gate_for(x.device)
-        if ctx.needs_input_grad[0]:
-            y, mask = gate.process_batch(x.detach(), xn, save_mask=True)
-            ctx.gate = gate
-            ctx.L = x.shape[-1]
-            ctx.save_for_backward(mask)
-        else:
-            y = gate.process_batch(x, xn)
-        return y
+# How a native route is called (_ffi.Gate): the forward and backward methods, whether the host lengths ride along, whether
+# the mask is an output of the call (else it is kept for the backward only), and whether the backward needs x again.
+_Route = collections.namedtuple("_Route", "fwd bwd lengths mask_out save_x")
+_ROUTES = {
+    "waveform": _Route("process_batch", "process_batch_backward", False, False, False),
+    "waveform_rows": _Route("process_rows", "process_rows_backward", True, False, False),        # csrc/rows.hip
+    "spectrum": _Route("gate_spectrum", "gate_spectrum_backward", False, True, False),           # csrc/spec.hip
+    "spectrum_rows": _Route("gate_spectrum_rows", "gate_spectrum_rows_backward", True, True, False),
+    "features": _Route("gate_features", "gate_features_backward", False, True, True),            # csrc/feat.hip
+}
 
-    @staticmethod
-    def backward(ctx, grad_out):
-        (mask,) = ctx.saved_tensors
-        gx = ctx.gate.process_batch_backward(grad_out.contiguous(), mask, ctx.L)
-        return gx, None, None
-
-
-class _RowsFunction(torch.autograd.Function):
-    """forward(x, lengths=...): the table-driven kernels of csrc/rows.hip.  ``lengths`` / ``xn_lengths`` are host int64
-    arrays (or None); the backward gets the same lengths."""
-
-    @staticmethod
-    def forward(ctx, x, xn, module, lengths, xn_lengths):
-        gate = module._gate_for(x.device)
-        if ctx.needs_input_grad[0]:
-            y, mask = gate.process_rows(x.detach(), lengths, xn, xn_lengths, save_mask=True)
-            ctx.gate = gate
-            ctx.L = x.shape[-1]
-            ctx.lengths = lengths
-            ctx.save_for_backward(mask)
-        else:
-            y = gate.process_rows(x, lengths, xn, xn_lengths)
-        return y
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        (mask,) = ctx.saved_tensors
-        gx = ctx.gate.process_rows_backward(grad_out.contiguous(), mask, ctx.L, ctx.lengths)
-        return gx, None, None, None, None
-
-
-class _SpectrumFunction(torch.autograd.Function):
-    """gated_stft on the native kernels (sg_gate_spectrum): returns the real pairs (B, T, F, 2) -- torch.view_as_complex is
-    applied outside, so the complex autograd convention stays torch's -- and the mask, which carries no gradient."""
-
-    @staticmethod
-    def forward(ctx, x, xn, module):
-        gate = module._gate_for(x.device)
-        pairs, mask = gate.gate_spectrum(x.detach(), xn, save_mask=True)
-        ctx.gate = gate
-        ctx.L = x.shape[-1]
-        ctx.save_for_backward(mask)
-        ctx.mark_non_differentiable(mask)
-        return pairs, mask
-
-    @staticmethod
-    def backward(ctx, grad_pairs, _grad_mask):
-        (mask,) = ctx.saved_tensors
-        gx = ctx.gate.gate_spectrum_backward(grad_pairs.contiguous(), mask, ctx.L)
-        return gx, None, None
-
-
-class _SpectrumRowsFunction(torch.autograd.Function):
-    """gated_stft(x, lengths=...) on the table-driven kernels (sg_gate_spectrum_rows): real pairs (B, T, F, 2) and the
-    mask, as _SpectrumFunction; ``lengths`` / ``xn_lengths`` are host int64 arrays (or None) and the backward gets the
-    same lengths."""
-
-    @staticmethod
-    def forward(ctx, x, xn, module, lengths, xn_lengths):
-        gate = module._gate_for(x.device)
-        pairs, mask = gate.gate_spectrum_rows(x.detach(), lengths, xn, xn_lengths, save_mask=True)
-        ctx.gate = gate
-        ctx.L = x.shape[-1]
-        ctx.lengths = lengths
-        ctx.save_for_backward(mask)
-        ctx.mark_non_differentiable(mask)
-        return pairs, mask
-
-    @staticmethod
-    def backward(ctx, grad_pairs, _grad_mask):
-        (mask,) = ctx.saved_tensors
-        gx = ctx.gate.gate_spectrum_rows_backward(grad_pairs.contiguous(), mask, ctx.L, ctx.lengths)
-        return gx, None, None, None, None
+_NO_KW = {}   # (the routes without keyword arguments)
 
 
 def _bind_bank(gate, bank):
@@ -112,30 +46,50 @@ def _bind_bank(gate, bank):
         gate.set_filterbank(bank["host"], key=bank["digest"])
 
 
-class _FeaturesFunction(torch.autograd.Function):
-    """gated_filterbank on the native kernels (sg_gate_features): the features (B, T, M) and the mask, which carries no
-    gradient.  Saves x and the mask: the backward transforms the frames again (sg_gate_features_backward), so nothing of
-    size B x T x F is kept but the mask.  ``bank``: the entry of TorchGate._bank (host array and digest)."""
+def _engine(gate, bank, method, args, kw):
+    """One call into the engine; with a bank (the features route) under gate.lock, the bank bound again first."""
+    if bank is None:
+        return getattr(gate, method)(*args, **kw)
+    with gate.lock:
+        _bind_bank(gate, bank)
+        return getattr(gate, method)(*args, **kw)
+
+
+class _NativeFunction(torch.autograd.Function):
+    """Every native route of forward, gated_stft and gated_filterbank.  ``call`` is one tuple (autograd's apply costs a
+    quarter of a microsecond per argument): the module, ``route`` (a row of _ROUTES), ``lengths`` / ``xn_lengths`` (host
+    int64 arrays or None; the backward gets the same lengths), ``bank`` (the entry of TorchGate._bank, host array and
+    digest, or None) and ``kw`` (the power / log / eps of the features route, {} otherwise).
+
+    The waveform routes return y and ask for the mask only when x needs a gradient: the call without one does not write
+    it.  The spectrum and feature routes always return the mask, which carries no gradient: the real pairs (B, T, F, 2)
+    -- torch.view_as_complex is applied outside, so the complex autograd convention stays torch's -- or the features
+    (B, T, M).  The features route saves x and the mask: its backward transforms the frames again, so nothing of size
+    B x T x F is kept but the mask."""
 
     @staticmethod
-    def forward(ctx, x, xn, module, bank, power, log, eps):
+    def forward(ctx, x, xn, call):
+        module, route, lengths, xn_lengths, bank, kw = call
         gate = module._gate_for(x.device)
-        with gate.lock:
-            _bind_bank(gate, bank)
-            feat, mask = gate.gate_features(x.detach(), xn, power=power, log=log, eps=eps, save_mask=True)
-        ctx.gate, ctx.bank, ctx.args = gate, bank, (power, log, eps)
-        ctx.save_for_backward(x, mask)
+        args = (x, lengths, xn, xn_lengths) if route.lengths else (x, xn)
+        if not (route.mask_out or ctx.needs_input_grad[0]):
+            return _engine(gate, bank, route.fwd, args, kw)
+        out, mask = _engine(gate, bank, route.fwd, args, dict(kw, save_mask=True))
+        ctx.gate, ctx.route, ctx.L, ctx.lengths, ctx.bank, ctx.kw = gate, route, x.shape[-1], lengths, bank, kw
+        ctx.save_for_backward(*((x, mask) if route.save_x else (mask,)))
+        if not route.mask_out:
+            return out
         ctx.mark_non_differentiable(mask)
-        return feat, mask
+        return out, mask
 
     @staticmethod
-    def backward(ctx, grad_feat, _grad_mask):
-        x, mask = ctx.saved_tensors
-        power, log, eps = ctx.args
-        with ctx.gate.lock:
-            _bind_bank(ctx.gate, ctx.bank)
-            gx = ctx.gate.gate_features_backward(x.detach(), grad_feat, mask, power=power, log=log, eps=eps)
-        return gx, None, None, None, None, None, None
+    def backward(ctx, grad, _grad_mask=None):
+        *x, mask = ctx.saved_tensors
+        route = ctx.route
+        args = (x[0].detach(), grad.contiguous(), mask) if route.save_x else (grad.contiguous(), mask, ctx.L)
+        if route.lengths:
+            args += (ctx.lengths,)
+        return _engine(ctx.gate, ctx.bank, route.bwd, args, ctx.kw), None, None
 
 
 class TorchGate(torch.nn.Module):
@@ -231,29 +185,17 @@ class TorchGate(torch.nn.Module):
         batch in a fixed number of launches (csrc/rows.hip); any other n_fft loops over the rows through the
         full-length path (correct, one call per row)."""
         assert x.ndim == 2
-        if lengths is not None or xn_lengths is not None:
-            return self._forward_rows(x, xn, lengths, xn_lengths)
-        if x.shape[-1] < self.win_length * 2:
-            raise Exception(f"x must be bigger than {self.win_length * 2}")
-        assert xn is None or xn.ndim == 1 or xn.ndim == 2
-        if xn is not None and xn.shape[-1] < self.win_length * 2:
-            raise Exception(f"xn must be bigger than {self.win_length * 2}")
-        if x.device.type != "cuda":
-            raise RuntimeError("noisereduce_amd.TorchGate runs on the GPU only (no CPU fallback): "
-                               "move the input with x.to('cuda')")
-        dtype = x.dtype
-        if dtype not in (torch.float32, torch.float64):
-            x = x.float()
-        if xn is not None:
-            xn = xn.detach().to(device=x.device, dtype=x.dtype)
-            if xn.ndim == 1:
-                # the reference crashes on 1-D xn in stationary mode (torchgate.py:164); a
-                # single noise row is the evident intent.
-                xn = xn.unsqueeze(0)
-            if self.nonstationary:
-                xn = None  # unused by the non-stationary mask (torchgate.py:235-236)
-        y = _GateFunction.apply(x, xn, self)
-        return y.to(dtype=dtype)
+        xf, dtype, xnf, lengths, xn_lengths, full = self._prepare(x, xn, lengths, xn_lengths, xn_rows=False)
+        if not full and not _rows.native(self.n_fft):
+            B, L = x.shape
+            H = self.hop_length
+            y = x.new_zeros((B, H * (L // H)))
+            for i in range(B):
+                n = L if lengths is None else int(lengths[i])
+                y[i, :H * (n // H)] = self.forward(x[i:i + 1, :n], self._noise_of_row(xn, xn_lengths, i))[0]
+            return y
+        route = _ROUTES["waveform" if full else "waveform_rows"]
+        return _NativeFunction.apply(xf, xnf, (self, route, lengths, xn_lengths, None, _NO_KW)).to(dtype=dtype)
 
     def stft_lengths(self, lengths):
         """Frames each row of a padded batch owns, ``1 + lengths // hop_length`` (``torch.stft(center=True)`` on the row
@@ -292,31 +234,26 @@ class TorchGate(torch.nn.Module):
         launches (sg_gate_spectrum_rows, csrc/rows.hip: float64 transforms, so complex128 is stored unrounded and
         complex64 rounded once); any other n_fft makes one ``gated_stft`` call per row (correct, slow)."""
         assert x.ndim == 2
-        if lengths is not None or xn_lengths is not None:
-            return self._gated_stft_rows(x, xn, return_mask, lengths, xn_lengths)
-        if x.shape[-1] < self.win_length * 2:
-            raise Exception(f"x must be bigger than {self.win_length * 2}")
-        assert xn is None or xn.ndim == 1 or xn.ndim == 2
-        if xn is not None and xn.shape[-1] < self.win_length * 2:
-            raise Exception(f"xn must be bigger than {self.win_length * 2}")
-        if x.device.type != "cuda":
-            raise RuntimeError("noisereduce_amd.TorchGate runs on the GPU only (no CPU fallback): "
-                               "move the input with x.to('cuda')")
-        if x.dtype not in (torch.float32, torch.float64):
-            x = x.float()
-        if xn is not None:
-            xn = xn.detach().to(device=x.device, dtype=x.dtype)
-            if xn.ndim == 1:
-                xn = xn.unsqueeze(0)
-            if self.nonstationary:
-                xn = None  # unused by the non-stationary mask (torchgate.py:235-236)
+        x, _, xnf, lengths, xn_lengths, full = self._prepare(x, xn, lengths, xn_lengths, xn_rows=True)
         F = self.n_fft // 2 + 1
-        if _rows.native(self.n_fft):
-            pairs, mask = _SpectrumFunction.apply(x, xn, self)
+        if not full and not _rows.native(self.n_fft):
+            B, L = x.shape
+            T = 1 + L // self.hop_length
+            Yt = torch.zeros((B, T, F), dtype=torch.complex64 if x.dtype == torch.float32 else torch.complex128,
+                             device=x.device)
+            mask = torch.zeros((B, T, F), dtype=torch.float32, device=x.device)
+            for i in range(B):
+                n = L if lengths is None else int(lengths[i])
+                Yi, Mi = self.gated_stft(x[i:i + 1, :n], self._noise_of_row(xn, xn_lengths, i), return_mask=True)
+                Yt[i, :Yi.shape[-1]] = Yi[0].transpose(0, 1)
+                mask[i, :Mi.shape[-1]] = Mi[0].transpose(0, 1)
+        elif _rows.native(self.n_fft):
+            route = _ROUTES["spectrum" if full else "spectrum_rows"]
+            pairs, mask = _NativeFunction.apply(x, xnf, (self, route, lengths, xn_lengths, None, _NO_KW))
             Yt = torch.view_as_complex(pairs)
         else:
             with torch.no_grad():
-                _, mask = self._gate_for(x.device).process_batch(x.detach(), xn, save_mask=True)
+                _, mask = self._gate_for(x.device).process_batch(x.detach(), xnf, save_mask=True)
             window = torch.hann_window(self.win_length, device=x.device).to(x.dtype)  # the float32 table, as _gate_for
             X = torch.stft(x, n_fft=self.n_fft, hop_length=self.hop_length, win_length=self.win_length, window=window,
                            center=True, pad_mode="constant", return_complex=True)
@@ -382,32 +319,14 @@ class TorchGate(torch.nn.Module):
             raise ValueError("eps is NaN")
         power = int(power)
         bank = self._bank(fb)
-        rows_call = lengths is not None or xn_lengths is not None
-        if rows_call:
-            lengths, xn_lengths = self._check_rows(x, xn, lengths, xn_lengths, xn_rows=True)
-            if _rows.all_full(lengths, x.shape[-1]) and (xn is None or _rows.all_full(xn_lengths, xn.shape[-1])):
-                rows_call, lengths, xn_lengths = False, None, None
-        if not rows_call:
-            if x.shape[-1] < self.win_length * 2:
-                raise Exception(f"x must be bigger than {self.win_length * 2}")
-            assert xn is None or xn.ndim == 1 or xn.ndim == 2
-            if xn is not None and xn.shape[-1] < self.win_length * 2:
-                raise Exception(f"xn must be bigger than {self.win_length * 2}")
-            if x.device.type != "cuda":
-                raise RuntimeError("noisereduce_amd.TorchGate runs on the GPU only (no CPU fallback): "
-                                   "move the input with x.to('cuda')")
-        if x.dtype not in (torch.float32, torch.float64):
-            x = x.float()
+        x, _, xnf, lengths, xn_lengths, full = self._prepare(x, xn, lengths, xn_lengths, xn_rows=True)
         F = self.n_fft // 2 + 1
-        if not rows_call and _rows.native(self.n_fft):
-            if xn is not None:
-                xn = xn.detach().to(device=x.device, dtype=x.dtype)
-                if xn.ndim == 1:
-                    xn = xn.unsqueeze(0)
-                if self.nonstationary:
-                    xn = None  # unused by the non-stationary mask (torchgate.py:235-236)
-            feat, mask = _FeaturesFunction.apply(x, xn, self, bank, power, bool(log), eps)
+        if full and _rows.native(self.n_fft):
+            kw = dict(power=power, log=bool(log), eps=eps)
+            feat, mask = _NativeFunction.apply(x, xnf, (self, _ROUTES["features"], None, None, bank, kw))
         else:
+            if full:
+                lengths, xn_lengths = None, None
             Y, Mv = self.gated_stft(x, xn, return_mask=True, lengths=lengths, xn_lengths=xn_lengths)
             mask = Mv.transpose(1, 2)
             dkey = (str(x.device), x.dtype)
@@ -422,18 +341,29 @@ class TorchGate(torch.nn.Module):
         out = feat.transpose(1, 2)
         return (out, mask[:, :, :F].transpose(1, 2)) if return_mask else out
 
-    def _check_rows(self, x, xn, lengths, xn_lengths, xn_rows=False):
-        """Validation of a call with per-row lengths (forward and gated_stft alike), before any device work: the
-        lengths as host int64 arrays (or None).  xn_rows: refuse a noise batch of neither 1 nor B rows here, whether
-        or not xn_lengths came with it (forward leaves that case to the engine)."""
-        assert xn is None or xn.ndim == 1 or xn.ndim == 2
+    def _prepare(self, x, xn, lengths, xn_lengths, xn_rows):
+        """The one validation and normalisation of a call of forward, gated_stft or gated_filterbank, before any device
+        work.  Returns x in float32 / float64 and the dtype to give back, xn as a detached 2-D tensor like x (None when
+        there is none or the gate is non-stationary; its lengths stay, the engine ignores them without xn), the lengths as
+        host int64 arrays (or None), and whether every row is in fact full.  The errors and their order are pinned by
+        tests/test_torchgate_entry_host.py."""
         B, L = x.shape
-        if xn_rows and xn is not None and xn.ndim == 2 and xn.shape[0] not in (1, B):
-            raise ValueError(f"xn rows ({xn.shape[0]}) must be 1 or the batch size")
-        if L < self.win_length * 2:
-            raise Exception(f"x must be bigger than {self.win_length * 2}")
-        if xn is not None and xn.shape[-1] < self.win_length * 2:
-            raise Exception(f"xn must be bigger than {self.win_length * 2}")
+        lo = self.win_length * 2
+        rows_call = lengths is not None or xn_lengths is not None
+        # (a full-length call looks at the length of x before the rank of xn, a call with lengths after it)
+        if not rows_call and L < lo:
+            raise Exception(f"x must be bigger than {lo}")
+        assert xn is None or xn.ndim == 1 or xn.ndim == 2
+        if rows_call:
+            # xn_rows: a noise batch of neither 1 nor B rows is refused here, whether or not xn_lengths came with it.
+            # gated_stft and gated_filterbank ask for that; forward does not and leaves the case to the engine, as it
+            # leaves it in a call without lengths (which is why the same input gets past this validation there).
+            if xn_rows and xn is not None and xn.ndim == 2 and xn.shape[0] not in (1, B):
+                raise ValueError(f"xn rows ({xn.shape[0]}) must be 1 or the batch size")
+            if L < lo:
+                raise Exception(f"x must be bigger than {lo}")
+        if xn is not None and xn.shape[-1] < lo:
+            raise Exception(f"xn must be bigger than {lo}")
         if lengths is not None:
             lengths = _rows.as_lengths(lengths, B)
             _rows.plan(lengths, L, self.win_length, self.hop_length)
@@ -448,7 +378,19 @@ class TorchGate(torch.nn.Module):
         if x.device.type != "cuda":
             raise RuntimeError("noisereduce_amd.TorchGate runs on the GPU only (no CPU fallback): "
                                "move the input with x.to('cuda')")
-        return lengths, xn_lengths
+        full = not rows_call or (_rows.all_full(lengths, L) and (xn is None or _rows.all_full(xn_lengths, xn.shape[-1])))
+        dtype = x.dtype
+        if dtype not in (torch.float32, torch.float64):
+            x = x.float()
+        if xn is not None:
+            xn = xn.detach().to(device=x.device, dtype=x.dtype)
+            if xn.ndim == 1:
+                # the reference crashes on 1-D xn in stationary mode (torchgate.py:164); a
+                # single noise row is the evident intent.
+                xn = xn.unsqueeze(0)
+            if self.nonstationary:
+                xn = None  # unused by the non-stationary mask (torchgate.py:235-236)
+        return x, dtype, xn, lengths, xn_lengths, full
 
     @staticmethod
     def _noise_of_row(xn, xn_lengths, i):
@@ -459,64 +401,6 @@ class TorchGate(torch.nn.Module):
         if xn_lengths is not None:
             xi = xi[..., :int(xn_lengths[i if len(xn_lengths) > 1 else 0])]
         return xi
-
-    def _gated_stft_rows(self, x, xn, return_mask, lengths, xn_lengths):
-        """gated_stft with per-row lengths, routed as _forward_rows: the full-length path (every row full), the
-        table-driven kernels, or -- for an n_fft they are not built for -- one gated_stft call per row."""
-        lengths, xn_lengths = self._check_rows(x, xn, lengths, xn_lengths, xn_rows=True)
-        B, L = x.shape
-        if _rows.all_full(lengths, L) and (xn is None or _rows.all_full(xn_lengths, xn.shape[-1])):
-            return self.gated_stft(x, xn, return_mask)
-        F = self.n_fft // 2 + 1
-        if x.dtype not in (torch.float32, torch.float64):
-            x = x.float()
-        if not _rows.native(self.n_fft):
-            T = 1 + L // self.hop_length
-            Yt = torch.zeros((B, T, F), dtype=torch.complex64 if x.dtype == torch.float32 else torch.complex128,
-                             device=x.device)
-            mask = torch.zeros((B, T, F), dtype=torch.float32, device=x.device)
-            for i in range(B):
-                n = L if lengths is None else int(lengths[i])
-                Yi, Mi = self.gated_stft(x[i:i + 1, :n], self._noise_of_row(xn, xn_lengths, i), return_mask=True)
-                Yt[i, :Yi.shape[-1]] = Yi[0].transpose(0, 1)
-                mask[i, :Mi.shape[-1]] = Mi[0].transpose(0, 1)
-        else:
-            if xn is not None:
-                xn = xn.detach().to(device=x.device, dtype=x.dtype)
-                if xn.ndim == 1:
-                    xn = xn.unsqueeze(0)
-                if self.nonstationary:
-                    xn, xn_lengths = None, None  # unused by the non-stationary mask (torchgate.py:235-236)
-            pairs, mask = _SpectrumRowsFunction.apply(x, xn, self, lengths, xn_lengths)
-            Yt = torch.view_as_complex(pairs)
-        Y = Yt.transpose(1, 2)
-        return (Y, mask[:, :, :F].transpose(1, 2)) if return_mask else Y
-
-    def _forward_rows(self, x, xn, lengths, xn_lengths):
-        """forward with per-row lengths: validation, then the full-length path (every row full), the table-driven
-        kernels, or -- for an n_fft they are not built for -- one full-length call per row."""
-        lengths, xn_lengths = self._check_rows(x, xn, lengths, xn_lengths)
-        B, L = x.shape
-        if _rows.all_full(lengths, L) and (xn is None or _rows.all_full(xn_lengths, xn.shape[-1])):
-            return self.forward(x, xn)
-        if not _rows.native(self.n_fft):
-            H = self.hop_length
-            y = x.new_zeros((B, H * (L // H)))
-            for i in range(B):
-                n = L if lengths is None else int(lengths[i])
-                y[i, :H * (n // H)] = self.forward(x[i:i + 1, :n], self._noise_of_row(xn, xn_lengths, i))[0]
-            return y
-        dtype = x.dtype
-        if dtype not in (torch.float32, torch.float64):
-            x = x.float()
-        if xn is not None:
-            xn = xn.detach().to(device=x.device, dtype=x.dtype)
-            if xn.ndim == 1:
-                xn = xn.unsqueeze(0)
-            if self.nonstationary:
-                xn, xn_lengths = None, None  # unused by the non-stationary mask (torchgate.py:235-236)
-        y = _RowsFunction.apply(x, xn, self, lengths, xn_lengths)
-        return y.to(dtype=dtype)
 
     def __getstate__(self):
         st = super().__getstate__() if hasattr(super(), "__getstate__") else self.__dict__.copy()
