@@ -523,6 +523,34 @@ SG_API int sg_gate_spectrum_rows_backward(sg_handle* h, const void* grad_spec_de
                                           const int64_t* lengths, const float* mask_dev, void* grad_x_dev,
                                           int64_t gx_stride, void* stream);
 
+/* sg_gate_features for a PADDED batch (lengths / xn_lengths as in sg_process_rows; the bank is sg_set_filterbank's):
+ * feat [B][T][n_filters] of dtype, filters contiguous, T = sg_n_frames(L).  With T_i = 1 + lengths[i] / hop:
+ * feat[i][t][m] = sum_k fb[k][m] * (|X_i[t][k]| * mask_i[t][k]) ^ power for t < T_i, X_i and mask_i what
+ * sg_gate_spectrum_rows computes for the row alone (the same launches up to the mask smoothing), power 1 or 2;
+ * take_log != 0 stores ln(. + eps).  feat[i][T_i .. T) is what the formula gives for a zero spectrum: +0.0, or ln(eps)
+ * rounded to dtype.  Samples at or beyond lengths[i] / xn_lengths[j] are never read.  A row's result does not depend on
+ * the other rows, their order or L.  mask_out_dev: NULL or float[B][T][FS], bit for bit the mask sg_gate_spectrum_rows
+ * writes for the same input (frames >= T_i are 0), for sg_gate_features_rows_backward; the powers take this float32 mask.
+ * Float64 transforms and sums for both sample types: a float64 result is stored unrounded, a float32 result rounded
+ * once.  SG_E_INVALID when no filterbank is set or power is neither 1 nor 2; SG_E_UNSUPPORTED outside the power-of-two
+ * n_fft from 256 to 4096.  Rows are packed into sub-batches under the handle's max_workspace_bytes (0: 4 GiB) with the
+ * same bits as unsplit; a fixed number of launches per sub-batch.  Enqueues only. */
+SG_API int sg_gate_features_rows(sg_handle* h, const void* x_dev, int dtype, int64_t B, int64_t L, int64_t x_stride,
+                                 const int64_t* lengths, const void* xn_dev, int64_t Bn, int64_t Ln, int64_t xn_stride,
+                                 const int64_t* xn_lengths, int32_t power, int32_t take_log, double eps,
+                                 void* feat_dev, float* mask_out_dev, void* stream);
+
+/* Adjoint of sg_gate_features_rows w.r.t. x with the mask and the filterbank held fixed: grad_feat [B][T][n_filters] of
+ * dtype -> grad_x (B, L) of dtype, as sg_gate_features_backward on every row alone: grad_x[i][0 .. lengths[i]) is the
+ * gradient of the row alone, grad_x[i][lengths[i] .. L) is 0, and grad_feat[i][T_i .. T) is never read.  x, lengths, power,
+ * take_log, eps: what the forward call was given (the frames are transformed again; nothing of size B x T x F is kept
+ * but mask_dev).  For power 1 the derivative at |X[k]| = 0 is 0.  No atomics: the same bits on every run.  Sub-batches
+ * as above.  Enqueues only. */
+SG_API int sg_gate_features_rows_backward(sg_handle* h, const void* x_dev, int dtype, int64_t B, int64_t L, int64_t x_stride,
+                                          const int64_t* lengths, const void* grad_feat_dev, const float* mask_dev,
+                                          int32_t power, int32_t take_log, double eps, void* grad_x_dev,
+                                          int64_t gx_stride, void* stream);
+
 /* ---- stage taps (used by the parity tests; also plain STFT/ISTFT operators) ------ */
 
 /* Forward STFT of (B, L) rows -> complex float64 Z[B][T][F] (interleaved re,im), same

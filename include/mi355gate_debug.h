@@ -137,7 +137,8 @@ SG_API int sg_debug_backward_route(const sg_handle* h, int64_t* value);
 #define SG_STAGE_IIR_MASK 19  /* non-stationary gate: k_iir_mask<nt> -- recurrence, sigmoid and both smoothing passes in one kernel */
 /* ragged batches (sg_process_clips, ragged.hip): one launch of each per sub-batch.  sg_process_rows (rows.hip) books its
  * launches under the same seven stages (its moving mean under SG_STAGE_RG_IIR), and so does sg_gate_spectrum_rows: its
- * spectrum store and its adjoint frames under SG_STAGE_RG_APPLY, the adjoint's overlap-add under SG_STAGE_RG_OLA. */
+ * spectrum store and its adjoint frames under SG_STAGE_RG_APPLY, the adjoint's overlap-add under SG_STAGE_RG_OLA.
+ * sg_gate_features_rows books its feature store and its adjoint frames the same way. */
 #define SG_STAGE_RG_NOISE_POWER 20 /* stationary: float64 transform of every noise frame */
 #define SG_STAGE_RG_NOISE_FINAL 21 /* stationary: per-source band maxima, moments, thresholds, compare constants */
 #define SG_STAGE_RG_DECIDE 22      /* float64 transform of every data frame: decision bits + band maxima (stationary) / magnitudes */

@@ -163,6 +163,10 @@ _PROTOTYPES = {
                                       c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sg_gate_spectrum_rows_backward": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p,
                                                c_void_p, c_int64, c_void_p]),
+    "sg_gate_features_rows": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64,
+                                      c_int64, c_int64, c_void_p, c_int32, c_int32, c_double, c_void_p, c_void_p, c_void_p]),
+    "sg_gate_features_rows_backward": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                                               c_void_p, c_int32, c_int32, c_double, c_void_p, c_int64, c_void_p]),
     "sg_debug_rows_batches": (c_int, [c_void_p, POINTER(c_int64)]),
     "sg_debug_backward_route": (c_int, [c_void_p, POINTER(c_int64)]),
     "sg_stft": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
@@ -682,6 +686,50 @@ class Gate:
             self._check(self.lib.sg_gate_spectrum_rows_backward(
                 self._h, grad.data_ptr(), _sg_dtype(grad), B, L, lp, mask.data_ptr(), gx.data_ptr(), L,
                 self._stream()))
+        return gx
+
+    def gate_features_rows(self, x, lengths, xn=None, xn_lengths=None, power=2, log=False, eps=1e-6, save_mask=False):
+        """TorchGate.gated_filterbank on a padded batch (sg_gate_features_rows): row i holds lengths[i] samples (host
+        integers) and padding after them.  Returns (B, T, M) of x.dtype, the filters contiguous; frames
+        [0, 1 + lengths[i] // hop) of row i are the features of x[i, :lengths[i]] alone, the frames after them 0 (ln(eps)
+        with log).  With save_mask=True also the (B, T, FS) float32 mask gate_spectrum_rows returns, for
+        gate_features_rows_backward."""
+        if not self.n_filters:
+            raise RuntimeError("no filterbank set (set_filterbank)")
+        self._on_device(x)
+        x, xs = _rows(x)
+        B, L = x.shape
+        T = self.n_frames(L)
+        out = torch.empty((B, T, self.n_filters), dtype=x.dtype, device=self.device)
+        mask = self._mask(B, T, save_mask)
+        xn, (xn_ptr, Bn, Ln, xns) = self._noise(x, xn)
+        la, lp = self._lengths(lengths, B)
+        na, np_ = self._lengths(xn_lengths if xn is not None else None, Bn)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.sg_gate_features_rows(
+                self._h, x.data_ptr(), _sg_dtype(x), B, L, xs, lp, xn_ptr, Bn, Ln, xns, np_, int(power), int(bool(log)),
+                float(eps), out.data_ptr(), None if mask is None else mask.data_ptr(), self._stream()))
+        return (out, mask) if save_mask else out
+
+    def gate_features_rows_backward(self, x, grad, mask, lengths, power=2, log=False, eps=1e-6):
+        """Adjoint of gate_features_rows w.r.t. x with the mask and the bank fixed: grad (B, T, M) -> (B, L) of x.dtype,
+        zero at and beyond lengths[i]; grad[i, 1 + lengths[i] // hop:] is never read.  x, lengths, power, log, eps: the
+        forward call's."""
+        if not self.n_filters:
+            raise RuntimeError("no filterbank set (set_filterbank)")
+        self._on_device(x)
+        self._on_device(grad)
+        x, xs = _rows(x)
+        B, L = x.shape
+        grad = grad.to(x.dtype).contiguous()
+        if grad.shape != (B, self.n_frames(L), self.n_filters):
+            raise ValueError(f"grad must be (B, T, M) = {(B, self.n_frames(L), self.n_filters)}, got {tuple(grad.shape)}")
+        gx = self._grad_x(B, L, x.dtype)
+        la, lp = self._lengths(lengths, B)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.sg_gate_features_rows_backward(
+                self._h, x.data_ptr(), _sg_dtype(x), B, L, xs, lp, grad.data_ptr(), mask.data_ptr(), int(power),
+                int(bool(log)), float(eps), gx.data_ptr(), L, self._stream()))
         return gx
 
     def rows_batches(self):

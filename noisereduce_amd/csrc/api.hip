@@ -3955,6 +3955,37 @@ extern "C" int sg_gate_spectrum_rows_backward(sg_handle* h, const void* grad_spe
                                   rw_budget(h), (hipStream_t)stream, &h->err);
 }
 
+// TorchGate.gated_filterbank(lengths=): the rows pipeline with the features of the masked frame stored instead of the
+// frame (rows.hpp; the bank is sg_set_filterbank's)
+extern "C" int sg_gate_features_rows(sg_handle* h, const void* x_dev, int dtype, int64_t B, int64_t L, int64_t x_stride,
+                                     const int64_t* lengths, const void* xn_dev, int64_t Bn, int64_t Ln, int64_t xn_stride,
+                                     const int64_t* xn_lengths, int32_t power, int32_t take_log, double eps,
+                                     void* feat_dev, float* mask_out_dev, void* stream) {
+  if (int rc = t_entry(h, "sg_gate_features_rows")) return rc;
+  if (!x_dev || !feat_dev || (dtype != SG_F32 && dtype != SG_F64) || B < 1 || x_stride < L)
+    FAIL(h, SG_E_INVALID, "sg_gate_features_rows: bad argument");
+  if (int rc = features_args_ok(h, "sg_gate_features_rows", power, eps)) return rc;
+  if (int rc = t_min_lengths(h, B, L, xn_dev, Bn, Ln)) return rc;
+  return sg::rw_features(&h->rw, rg_ctx(h), h->p.n_movemean, feat_bank(h), x_dev, dtype, B, L, x_stride, lengths, xn_dev, Bn,
+                         Ln, xn_stride, xn_lengths, power, take_log != 0, eps, feat_dev, mask_out_dev, rw_budget(h),
+                         (hipStream_t)stream, &h->err);
+}
+
+extern "C" int sg_gate_features_rows_backward(sg_handle* h, const void* x_dev, int dtype, int64_t B, int64_t L,
+                                              int64_t x_stride, const int64_t* lengths, const void* grad_feat_dev,
+                                              const float* mask_dev, int32_t power, int32_t take_log, double eps,
+                                              void* grad_x_dev, int64_t gx_stride, void* stream) {
+  if (int rc = t_entry(h, "sg_gate_features_rows_backward")) return rc;
+  if (!x_dev || !grad_feat_dev || !grad_x_dev || !mask_dev || B < 1 || (dtype != SG_F32 && dtype != SG_F64) || x_stride < L ||
+      gx_stride < L)
+    FAIL(h, SG_E_INVALID, "sg_gate_features_rows_backward: bad argument");
+  if (int rc = features_args_ok(h, "sg_gate_features_rows_backward", power, eps)) return rc;
+  if (L < 2 * (int64_t)h->W) FAIL(h, SG_E_INVALID, "x must be bigger than %d", 2 * h->W);
+  return sg::rw_features_backward(&h->rw, rg_ctx(h), feat_bank(h), x_dev, dtype, B, L, x_stride, lengths, grad_feat_dev,
+                                  mask_dev, power, take_log != 0, eps, grad_x_dev, gx_stride, rw_budget(h),
+                                  (hipStream_t)stream, &h->err);
+}
+
 extern "C" int sg_debug_rows_batches(const sg_handle* h, int64_t* value) {
   if (!h || !value) return SG_E_INVALID;
   *value = sg::rw_last_batches(h->rw);

@@ -1,5 +1,7 @@
-// Padded batches of different-length rows (sg_process_rows, sg_gate_spectrum_rows): tables, kernels and the host side.
-// See rows.hpp and DESIGN sections 12 and 14.
+// Padded batches of different-length rows (sg_process_rows, sg_gate_spectrum_rows, sg_gate_features_rows): kernels and
+// the host side.  See rows.hpp and DESIGN sections 12 and 14.  The row / noise / argument tables and the frame loader
+// are rows_kernels.hpp's, shared with rows_feat.hip, which holds the two feature kernels (in this
+// file they changed the code the compiler builds for the kernels below); run() launches them through rw_feat_launch.
 //
 // Variant T throughout (torch.stft(center=True, pad_mode="constant"): frame t is centred on sample t H; the window is
 // embedded in an n_fft frame; torch.istft's trimming and envelope).  Row i owns T_i = 1 + len_i / H frames; samples at
@@ -20,87 +22,10 @@
 
 #include "tile_core.hpp"
 #include "rows.hpp"
+#include "rows_kernels.hpp"
 #include "../../include/mi355gate_debug.h"
 
 namespace sg {
-
-// ---- tables ------------------------------------------------------------------------------------------------------
-struct RwRow {
-  int64_t x_off;       // element of the source (x; backward: grad_out; spectrum backward: complex element of grad_spec)
-                       // holding sample 0 (frame 0, bin 0) of the row
-  int64_t len;         // readable samples (forward: lengths[i]; backward: H * (lengths[i] / H))
-  int64_t T;           // frames: 1 + lengths[i] / H
-  int64_t Lout;        // positions that receive a value (forward: H * (lengths[i] / H); backward: lengths[i])
-  int64_t full;        // positions written, [Lout, full) with zeros (forward: H * (L / H); backward: L; spectrum forward: 0)
-  int64_t out_off;     // element of out receiving position 0 (spectrum forward: complex element of frame 0, bin 0)
-  int64_t frow;        // first row of this row's frames in the bits / magnitude / mask / segment fields
-  int64_t mask_off;    // element of the caller's mask holding frame 0, band 0
-  int32_t noise;       // local noise index (stationary)
-  int32_t pad_;
-};
-struct RwNoise {
-  int64_t off, len, T; // element of sample 0, readable samples, frames
-  int64_t prow;        // first row in the noise power field
-  int32_t in_x, pad_;  // 1: the row's own samples (xn = None)
-};
-
-struct RwArgs {
-  const void* x; int in_dtype;
-  const void* xn; int noise_dtype;
-  void* out; int out_dtype;
-  const RwRow* rows;
-  const RwNoise* noises;
-  const Tile* tiles;             // all tile lists, back to back
-  int64_t t_np, n_np;            // noise power tiles (noise row, frames)
-  int64_t t_nf, n_nf;            // noise final tiles (noise row, band block)
-  int64_t t_dec, n_dec;          // frame tiles (row, frames)
-  int64_t t_box, n_box;          // moving-mean tiles (row, band block)
-  int64_t t_fs, n_fs;            // frequency smoothing tiles (row, frames)
-  int64_t t_ap, n_ap;            // frame tiles of the apply stage
-  int64_t t_ola, n_ola;          // output tiles (row, positions)
-  double* Pn;                    // [noise rows][FS] float64 noise power
-  double* T2n;                   // [local noise][FS] compare constant from the threshold alone
-  double* thr;                   // [local noise][FS] thresholds (dB)
-  unsigned long long* pmax;      // [rows][FS] band maxima of the row's power (bit patterns)
-  unsigned long long* bits;      // [frame rows][wpr]
-  float* mag;                    // [frame rows][FS] (non-stationary)
-  float* sig;                    // [frame rows][FS] (non-stationary raw mask)
-  float* R;                      // [frame rows][FS] frequency-smoothed mask
-  float* seg;                    // [frame rows][n]
-  float* mask_out;               // forward: nullptr or the caller's float[B][T][FS]
-  const float* mask_in;          // backward: the mask of the forward call
-  int kbox, bwd;
-  TileConsts c;
-};
-
-// sum of w^2 over the row's OWN frames that cover output position p (torch.istft's envelope for a row of T frames)
-__device__ __forceinline__ double rw_envelope(const RwArgs& A, int64_t T, int64_t p) {
-  const int64_t e = p + A.c.padL;
-  int64_t t_lo, t_hi;
-  ola_span(e, A.c.n, A.c.H, T, &t_lo, &t_hi);
-  return ola_envelope(A.c.wfull, e, A.c.H, t_lo, t_hi);
-}
-
-// sample g of a source of `len` readable samples starting at element off: 0 outside [0, len), never loaded there.
-// Backward: the source is grad_out divided by the row's envelope.
-__device__ __forceinline__ double rw_sample(const RwArgs& A, const void* src, int dt, int64_t off, int64_t len, int64_t T,
-                                            int64_t g) {
-  if (g < 0 || g >= len) return 0.0;
-  double v = load_sample(src, dt, off + g);
-  if (A.bwd) {
-    const double norm = rw_envelope(A, T, g);
-    v = norm > 1e-10 ? v / norm : v;
-  }
-  return v;
-}
-
-// window * frame t (samples [t H - padL, t H - padL + n)) into the team's buffer, forward transform, in place
-template <int N>
-__device__ __forceinline__ void rw_frame_fft(const RwArgs& A, const void* src, int dt, int64_t off, int64_t len, int64_t T,
-                                             int64_t t, cx<double>* buf, const cx<double>* tw, int lane) {
-  const int64_t s0 = t * A.c.H - A.c.padL;
-  frame_fft<N>(buf, tw, lane, [&](int jj) -> double { return rw_sample(A, src, dt, off, len, T, s0 + jj) * A.c.wfull[jj]; });
-}
 
 // ---- stationary: noise statistics ----------------------------------------------------------------------------------
 // power of every frame of every noise row (xn's rows, or the rows themselves when xn is None)
@@ -413,9 +338,11 @@ int check_lengths(const RgCtx& c, const char* who, const char* what, const int64
 
 // one call of either direction: rows [0, B) packed greedily into sub-batches under the budget.  spec: the gated
 // spectrogram -- forward: out is [B][T][F] complex of out_dtype, out_stride = T * F; backward: x is the gradient in that
-// layout, x_stride = T * F
+// layout, x_stride = T * F.  feat: the filterbank features -- forward: out is [B][T][M] of out_dtype, out_stride = T * M;
+// backward: x is the samples again and Q.grad the gradient in that layout
 struct Call {
-  bool bwd, spec;
+  bool bwd, spec, feat;
+  RwFeat Q;
   const void* x; int dtype; int64_t B, L, x_stride; const int64_t* lengths;
   const void* xn; int64_t Bn, Ln, xn_stride; const int64_t* xn_lengths;
   void* out; int out_dtype; int64_t out_stride;
@@ -431,7 +358,7 @@ int run(RwState** sp, const RgCtx& c, int kbox, const Call& q, int64_t max_ws, h
   const int64_t H = c.H;
   const int64_t Tfull = 1 + q.L / H, Lq = H * (q.L / H);
   const bool stat = c.stationary && !q.bwd;
-  const bool spec_fwd = q.spec && !q.bwd;
+  const bool spec_fwd = (q.spec || q.feat) && !q.bwd;   // a frame sink: no segments, no overlap-add, tiles over [0, T)
   const int noise_mode = !stat ? 0 : (!q.xn ? 1 : (q.Bn == 1 ? 2 : 3));   // 1: the row itself, 2: one shared row, 3: per row
   auto len_of = [&](int64_t i) { return q.lengths ? q.lengths[i] : q.L; };
   auto nlen_of = [&](int64_t i) { return q.xn_lengths ? q.xn_lengths[i] : q.Ln; };
@@ -470,7 +397,7 @@ int run(RwState** sp, const RgCtx& c, int kbox, const Call& q, int64_t max_ws, h
       RwRow U{};
       U.x_off = i * q.x_stride;
       U.T = 1 + len / H;
-      U.len = q.bwd ? H * (len / H) : len;
+      U.len = (q.bwd && !q.feat) ? H * (len / H) : len;   // (the features' backward reads the samples, not grad_out)
       U.Lout = spec_fwd ? 0 : (q.bwd ? len : H * (len / H));
       U.full = spec_fwd ? 0 : (q.bwd ? q.L : Lq);
       U.out_off = i * q.out_stride;
@@ -549,7 +476,8 @@ int run(RwState** sp, const RgCtx& c, int kbox, const Call& q, int64_t max_ws, h
     }
     if (e == hipSuccess) {
       Prof pr(c, SG_STAGE_RG_APPLY, st);
-      if (spec_fwd) e = dispatch_N(c.N, [&](auto n) { return launch_tile_kernel<n()>(k_rw_spec<n()>, A.n_ap, st, A); });
+      if (q.feat) e = rw_feat_launch(c.N, q.bwd, A, q.Q, st);
+      else if (spec_fwd) e = dispatch_N(c.N, [&](auto n) { return launch_tile_kernel<n()>(k_rw_spec<n()>, A.n_ap, st, A); });
       else if (q.spec) e = dispatch_N(c.N, [&](auto n) { return launch_tile_kernel<n()>(k_rw_spec_bwd<n()>, A.n_ap, st, A); });
       else e = dispatch_N(c.N, [&](auto n) { return launch_tile_kernel<n()>(k_rw_apply<n()>, A.n_ap, st, A); });
     }
@@ -630,6 +558,55 @@ int rw_spectrum_backward(RwState** sp, const RgCtx& c, const void* gs_dev, int d
   Call q{};
   q.bwd = true; q.spec = true;
   q.x = gs_dev; q.dtype = dtype; q.B = B; q.L = L; q.x_stride = (1 + L / c.H) * (int64_t)c.F; q.lengths = lengths;
+  q.out = gx_dev; q.out_dtype = dtype; q.out_stride = gx_stride;
+  q.mask_in = mask;
+  return run(sp, c, 0, q, max_ws, st, who, err);
+}
+namespace {
+int feat_args(const RgCtx& c, const char* who, const FeatBank& bank, int power, std::string* err) {
+  if (!geom_ok(c, who, err)) return SG_E_UNSUPPORTED;
+  if (power != 1 && power != 2) { *err = std::string(who) + ": power must be 1 or 2"; return SG_E_INVALID; }
+  if (bank.M < 1 || bank.M > FEAT_MAX_FILTERS || !bank.fb || !bank.fbT || !bank.khull || !bank.mhull) {
+    *err = std::string(who) + ": no filterbank set (sg_set_filterbank)";
+    return SG_E_INVALID;
+  }
+  return SG_OK;
+}
+}  // namespace
+
+int rw_features(RwState** sp, const RgCtx& c, int kbox, const FeatBank& bank, const void* x_dev, int dtype, int64_t B,
+                int64_t L, int64_t x_stride, const int64_t* lengths, const void* xn_dev, int64_t Bn, int64_t Ln,
+                int64_t xn_stride, const int64_t* xn_lengths, int power, int take_log, double eps, void* feat_dev,
+                float* mask_out, int64_t max_ws, hipStream_t st, std::string* err) {
+  const char* who = "sg_gate_features_rows";
+  int rc = feat_args(c, who, bank, power, err);
+  if (rc) return rc;
+  if ((rc = check_lengths(c, who, "lengths", lengths, B, L, err))) return rc;
+  const bool use_xn = xn_dev && c.stationary;
+  if (use_xn && (rc = check_lengths(c, who, "xn_lengths", xn_lengths, Bn, Ln, err))) return rc;
+  if (!c.stationary && kbox < 1) { *err = std::string(who) + ": n_movemean must be at least 1"; return SG_E_INVALID; }
+  Call q{};
+  q.bwd = false; q.spec = false; q.feat = true;
+  q.Q = RwFeat{bank, nullptr, eps, take_log ? std::log(eps) : 0.0, power, take_log ? 1 : 0};
+  q.x = x_dev; q.dtype = dtype; q.B = B; q.L = L; q.x_stride = x_stride; q.lengths = lengths;
+  q.xn = use_xn ? xn_dev : nullptr; q.Bn = Bn; q.Ln = Ln; q.xn_stride = xn_stride; q.xn_lengths = use_xn ? xn_lengths : nullptr;
+  q.out = feat_dev; q.out_dtype = dtype; q.out_stride = (1 + L / c.H) * (int64_t)bank.M;
+  q.mask_out = mask_out; q.mask_in = nullptr;
+  return run(sp, c, kbox, q, max_ws, st, who, err);
+}
+
+int rw_features_backward(RwState** sp, const RgCtx& c, const FeatBank& bank, const void* x_dev, int dtype, int64_t B,
+                         int64_t L, int64_t x_stride, const int64_t* lengths, const void* grad_feat_dev, const float* mask,
+                         int power, int take_log, double eps, void* gx_dev, int64_t gx_stride, int64_t max_ws,
+                         hipStream_t st, std::string* err) {
+  const char* who = "sg_gate_features_rows_backward";
+  int rc = feat_args(c, who, bank, power, err);
+  if (rc) return rc;
+  if ((rc = check_lengths(c, who, "lengths", lengths, B, L, err))) return rc;
+  Call q{};
+  q.bwd = true; q.spec = false; q.feat = true;
+  q.Q = RwFeat{bank, grad_feat_dev, eps, 0.0, power, take_log ? 1 : 0};
+  q.x = x_dev; q.dtype = dtype; q.B = B; q.L = L; q.x_stride = x_stride; q.lengths = lengths;
   q.out = gx_dev; q.out_dtype = dtype; q.out_stride = gx_stride;
   q.mask_in = mask;
   return run(sp, c, 0, q, max_ws, st, who, err);

@@ -35,6 +35,7 @@ _ROUTES = {
     "spectrum": _Route("gate_spectrum", "gate_spectrum_backward", False, True, False),           # csrc/spec.hip
     "spectrum_rows": _Route("gate_spectrum_rows", "gate_spectrum_rows_backward", True, True, False),
     "features": _Route("gate_features", "gate_features_backward", False, True, True),            # csrc/feat.hip
+    "features_rows": _Route("gate_features_rows", "gate_features_rows_backward", True, True, True),   # csrc/rows_feat.hip
 }
 
 _NO_KW = {}   # (the routes without keyword arguments)
@@ -305,12 +306,16 @@ class TorchGate(torch.nn.Module):
         Differentiable w.r.t. ``x`` with the mask detached, like ``gated_stft``; for ``power=1`` the derivative at
         ``|X[k]| = 0`` is 0.
 
-        Power-of-two n_fft from 256 to 4096 on full-length rows run on the native kernels (sg_gate_features,
-        csrc/feat.hip): the frame stays in LDS between the transform and the features, and the backward transforms it
-        again.  Any other n_fft, and every call whose ``lengths`` / ``xn_lengths`` are not all full, takes the composed,
-        slow route: the formula above in torch on ``gated_stft(...)``, torch autograd for the backward.  With
-        ``lengths``, frames at and after ``stft_lengths(lengths)[i]`` hold what the formula gives for a zero spectrum: 0,
-        or ``ln(eps)`` with ``log=True``.  All-full lengths are bitwise ``gated_filterbank(x, fb, xn)``."""
+        Power-of-two n_fft from 256 to 4096 run on the native kernels: the frame stays in LDS between the transform and
+        the features, and the backward transforms it again.  Full-length rows take sg_gate_features (csrc/feat.hip).  A
+        call whose ``lengths`` / ``xn_lengths`` are not all full takes sg_gate_features_rows (csrc/rows_feat.hip): row i is
+        gated and reduced alone as in ``gated_stft(lengths=)`` -- the padding never read, a row independent of the other
+        rows, the gradient that of the row alone up to ``lengths[i]`` and 0 after it, the gradient of the frames at and
+        after ``stft_lengths(lengths)[i]`` ignored -- with float64 transforms and sums, so a float64 result is stored
+        unrounded and a float32 result rounded once.  Any other n_fft takes the composed, slow route
+        (``_filterbank_composed``): the formula above in torch on ``gated_stft(...)``, torch autograd for the backward.
+        With ``lengths``, frames at and after ``stft_lengths(lengths)[i]`` hold what the formula gives for a zero
+        spectrum: 0, or ``ln(eps)`` with ``log=True``.  All-full lengths are bitwise ``gated_filterbank(x, fb, xn)``."""
         assert x.ndim == 2
         if power not in (1, 2, 1.0, 2.0) or isinstance(power, bool):
             raise ValueError(f"power must be 1.0 or 2.0, got {power!r}")
@@ -321,25 +326,36 @@ class TorchGate(torch.nn.Module):
         bank = self._bank(fb)
         x, _, xnf, lengths, xn_lengths, full = self._prepare(x, xn, lengths, xn_lengths, xn_rows=True)
         F = self.n_fft // 2 + 1
-        if full and _rows.native(self.n_fft):
+        if _rows.native(self.n_fft):
             kw = dict(power=power, log=bool(log), eps=eps)
-            feat, mask = _NativeFunction.apply(x, xnf, (self, _ROUTES["features"], None, None, bank, kw))
+            if full:
+                call = (self, _ROUTES["features"], None, None, bank, kw)
+            else:
+                call = (self, _ROUTES["features_rows"], lengths, xn_lengths, bank, kw)
+            feat, mask = _NativeFunction.apply(x, xnf, call)
         else:
             if full:
                 lengths, xn_lengths = None, None
-            Y, Mv = self.gated_stft(x, xn, return_mask=True, lengths=lengths, xn_lengths=xn_lengths)
-            mask = Mv.transpose(1, 2)
-            dkey = (str(x.device), x.dtype)
-            fbd = bank["dev"].get(dkey)
-            if fbd is None:
-                fbd = bank["dev"][dkey] = torch.from_numpy(bank["host"]).to(device=x.device, dtype=x.dtype)
-            Yt = Y.transpose(1, 2)                                  # (B, T, F), the storage order
-            p = Yt.real * Yt.real + Yt.imag * Yt.imag if power == 2 else Yt.abs()
-            feat = torch.matmul(p, fbd)
-            if log:
-                feat = torch.log(feat + eps)
+            feat, mask = self._filterbank_composed(x, xn, bank, power, log, eps, lengths, xn_lengths)
         out = feat.transpose(1, 2)
         return (out, mask[:, :, :F].transpose(1, 2)) if return_mask else out
+
+    def _filterbank_composed(self, x, xn, bank, power, log, eps, lengths, xn_lengths):
+        """The composed route of ``gated_filterbank``: the formula in torch on ``gated_stft(...)``, torch autograd for the
+        backward.  Returns the features (B, T, M) and the mask (B, T, F), both in storage order.  Serves every n_fft
+        without native kernels (tools/bench_gated_filterbank_rows.py times it against the native route)."""
+        Y, Mv = self.gated_stft(x, xn, return_mask=True, lengths=lengths, xn_lengths=xn_lengths)
+        mask = Mv.transpose(1, 2)
+        dkey = (str(x.device), x.dtype)
+        fbd = bank["dev"].get(dkey)
+        if fbd is None:
+            fbd = bank["dev"][dkey] = torch.from_numpy(bank["host"]).to(device=x.device, dtype=x.dtype)
+        Yt = Y.transpose(1, 2)                                  # (B, T, F), the storage order
+        p = Yt.real * Yt.real + Yt.imag * Yt.imag if power == 2 else Yt.abs()
+        feat = torch.matmul(p, fbd)
+        if log:
+            feat = torch.log(feat + eps)
+        return feat, mask
 
     def _prepare(self, x, xn, lengths, xn_lengths, xn_rows):
         """The one validation and normalisation of a call of forward, gated_stft or gated_filterbank, before any device
