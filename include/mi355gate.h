@@ -264,6 +264,41 @@ SG_API int sg_stream_push_spectrum(sg_stream_bank* b, const void* in_dev, int in
                                    const sg_stream_spec_rec* spec_recs, int32_t n_recs, void* stream);
 /* A(n) of the bank (nt + L): the frames a stream has applied after n samples.  Host arithmetic only. */
 SG_API int sg_stream_bank_frames(const sg_stream_bank* b, int64_t n, int64_t* frames);
+/* Filterbank (log-mel) features of live streams.  sg_stream_set_filterbank gives the bank a filterbank of its own
+ * (sg_set_filterbank is a variant-T entry point and does not take a stream bank's handle): fb_host is float[F][n_filters]
+ * on the host, F = n_fft / 2 + 1, 1 <= n_filters <= 1024, entries finite (negative ones are allowed); SG_E_INVALID
+ * otherwise, and the bank keeps the filterbank it had.  The bank owns the device tables (the filterbank, its transpose and
+ * the two hull tables of sg_set_filterbank) until sg_stream_destroy; replacing a filterbank synchronises the device first.
+ * The filterbank is no part of a stream's state: sg_stream_export / sg_stream_import payloads do not carry it, and a moved
+ * stream continues its features where the destination bank holds the same filterbank.
+ *
+ * sg_stream_push_features is sg_stream_push_spectrum -- same records, same checks, same four launches and one table upload,
+ * bitwise the same audio and the same state afterwards, the same frames reported -- with every applied frame's spectrum
+ * reduced over the filters while the frame is still on chip instead of being stored:
+ *   lin[t, m] = sum_k fb[k][m] * |s * Z[t, k] * mask[t, k]| ^ power        feat = take_log ? ln(lin + eps) : lin
+ * power is 1 or 2, eps any number but NaN.  s = scale multiplies the UNSCALED transform (torch.stft's convention at
+ * scale = 1); scale = 0 stands for the bank's own 1 / sum(window), the very factor sg_stream_push_spectrum applies, so that
+ * the features are those of exactly the Y it reports.  scale is finite and not negative.  Transform, mask, powers and sums
+ * are float64, the weights float32 values widened; filter m sums in ascending k over the hull of its non-zero bins, and
+ * the value is rounded once at the store (feat_dtype: SG_F32 or SG_F64; mask_dev, which may be NULL, holds reals of that
+ * type: exactly the mask rows of sg_stream_push_spectrum).  A frame's features do not depend, bitwise, on the block split,
+ * the slot, the other streams of the step, or on whether earlier steps were sg_stream_push, _push_spectrum or
+ * _push_features.  feat_recs[i] places record i's frames: filter m of frame j of channel c goes to element feat_offset +
+ * c * feat_stride + j * n_filters + m of feat_dev, its mask row to mask_offset + c * mask_stride + j * F + k of mask_dev;
+ * feat_stride >= frames * n_filters and mask_stride >= frames * F for a multichannel bank.  Nothing else is written.
+ * Without a filterbank: SG_E_INVALID ("no filterbank set").  Every argument is checked before any device work; enqueues
+ * only; counters commit at enqueue. */
+typedef struct sg_stream_feat_rec {   /* where one stream's newly applied frames go */
+  int64_t feat_offset;     /* element of feat_dev holding filter 0 of channel 0's first new frame */
+  int64_t feat_stride;     /* elements from a channel's first new frame to the next channel's in feat_dev */
+  int64_t mask_offset;     /* element of mask_dev holding bin 0 of the same frame; ignored when mask_dev is NULL */
+  int64_t mask_stride;     /* elements from a channel's first new frame to the next channel's in mask_dev */
+} sg_stream_feat_rec;
+SG_API int sg_stream_set_filterbank(sg_stream_bank* b, const float* fb_host, int32_t n_filters);
+SG_API int sg_stream_push_features(sg_stream_bank* b, const void* in_dev, int in_dtype, void* out_dev, int out_dtype,
+                                   void* feat_dev, int feat_dtype, void* mask_dev, int32_t power, int32_t take_log,
+                                   double eps, double scale, const sg_stream_rec* recs,
+                                   const sg_stream_feat_rec* feat_recs, int32_t n_recs, void* stream);
 /* Empties the listed slots (their thresholds stay). */
 SG_API int sg_stream_reset(sg_stream_bank* b, const int32_t* slots, int32_t n_slots, void* stream);
 /* E(n) for the handle's geometry; samples received / emitted so far on a slot.  Host arithmetic only. */

@@ -93,6 +93,11 @@ class SgStreamSpecRec(Structure):
     _fields_ = [("spec_offset", c_int64), ("mask_offset", c_int64), ("stride", c_int64)]
 
 
+class SgStreamFeatRec(Structure):
+    """struct sg_stream_feat_rec (include/mi355gate.h): where one record's feature rows and mask rows go."""
+    _fields_ = [("feat_offset", c_int64), ("feat_stride", c_int64), ("mask_offset", c_int64), ("mask_stride", c_int64)]
+
+
 SG_STREAM_FIXED, SG_STREAM_NONSTATIONARY, SG_STREAM_ADAPTIVE = 0, 1, 2
 
 
@@ -182,6 +187,9 @@ _PROTOTYPES = {
     "sg_stream_push_spectrum": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                         c_void_p, c_int32, c_void_p]),
     "sg_stream_bank_frames": (c_int, [c_void_p, c_int64, POINTER(c_int64)]),
+    "sg_stream_set_filterbank": (c_int, [c_void_p, c_void_p, c_int32]),
+    "sg_stream_push_features": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int32,
+                                        c_int32, c_double, c_double, c_void_p, c_void_p, c_int32, c_void_p]),
     "sg_stream_reset": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
     "sg_stream_emitted": (c_int, [c_void_p, c_int64, POINTER(c_int64)]),
     "sg_stream_counters": (c_int, [c_void_p, c_int32, POINTER(c_int64), POINTER(c_int64)]),
@@ -894,6 +902,32 @@ class Gate:
             self._check(self.lib.sg_stream_push_spectrum(
                 bank, x.data_ptr(), _sg_dtype(x), out.data_ptr(), _sg_dtype(out), spec.data_ptr(),
                 _TORCH_DTYPES[real], None if mask is None else mask.data_ptr(), arr, sarr, len(recs), self._stream()))
+
+    def stream_set_filterbank(self, bank, fb):
+        """fb: C-contiguous (n_bins, M) float32 numpy array (torchgate.filterbank.check_filterbank's result).  Replacing a
+        filterbank synchronises the device."""
+        with torch.cuda.device(self.device):
+            self._check(self.lib.sg_stream_set_filterbank(bank, fb.ctypes.data_as(c_void_p), int(fb.shape[1])))
+
+    def stream_push_features(self, bank, x, out, feat, mask, recs, feat_recs, power, take_log, eps, scale):
+        """stream_push that also stores every newly applied frame's filterbank features: feat a 1-D float32 / float64
+        device tensor, mask None or a 1-D tensor of feat's type, feat_recs a sequence of SgStreamFeatRec parallel to recs;
+        scale 0.0: the bank's own 1 / sum(window).  Enqueues only."""
+        if feat.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"stream_push_features: feat is float32 or float64 (got {feat.dtype})")
+        if mask is not None and mask.dtype != feat.dtype:
+            raise TypeError(f"stream_push_features: mask must be {feat.dtype} next to such a feat (got {mask.dtype})")
+        if len(feat_recs) != len(recs):
+            raise ValueError("stream_push_features: recs and feat_recs must have the same length")
+        for t in (x, out, feat) + (() if mask is None else (mask,)):
+            self._on_device(t)
+        arr = (SgStreamRec * max(1, len(recs)))(*recs)
+        farr = (SgStreamFeatRec * max(1, len(feat_recs)))(*feat_recs)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.sg_stream_push_features(
+                bank, x.data_ptr(), _sg_dtype(x), out.data_ptr(), _sg_dtype(out), feat.data_ptr(), _TORCH_DTYPES[feat.dtype],
+                None if mask is None else mask.data_ptr(), int(power), int(bool(take_log)), float(eps), float(scale),
+                arr, farr, len(recs), self._stream()))
 
     def stream_bank_frames(self, bank, n):
         v = c_int64(0)

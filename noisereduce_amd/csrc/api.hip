@@ -4136,6 +4136,24 @@ extern "C" int sg_stream_push_spectrum(sg_stream_bank* b, const void* in_dev, in
   return sg::st_push(b->b, in_dev, in_dtype, out_dev, out_dtype, recs, n_recs, (hipStream_t)stream, &h->err, &so);
 }
 
+// the stream bank's own filterbank (sg_set_filterbank above is a variant-T entry point: t_entry refuses this handle)
+extern "C" int sg_stream_set_filterbank(sg_stream_bank* b, const float* fb_host, int32_t n_filters) {
+  if (!b) return SG_E_INVALID;
+  return sg::st_set_filterbank(b->b, fb_host, n_filters, &b->h->err);
+}
+
+extern "C" int sg_stream_push_features(sg_stream_bank* b, const void* in_dev, int in_dtype, void* out_dev, int out_dtype,
+                                       void* feat_dev, int feat_dtype, void* mask_dev, int32_t power, int32_t take_log,
+                                       double eps, double scale, const sg_stream_rec* recs,
+                                       const sg_stream_feat_rec* feat_recs, int32_t n_recs, void* stream) {
+  if (!b) return SG_E_INVALID;
+  sg_handle* h = b->h;
+  if (n_recs < 0 || (n_recs > 0 && !recs) || !dtype_ok(in_dtype) || !dtype_ok(out_dtype))
+    FAIL(h, SG_E_INVALID, "sg_stream_push_features: bad argument (float32 / float64 buffers)");
+  const sg::StFeatOut fo{feat_dev, feat_dtype, mask_dev, feat_recs, power, take_log, eps, scale};
+  return sg::st_push(b->b, in_dev, in_dtype, out_dev, out_dtype, recs, n_recs, (hipStream_t)stream, &h->err, nullptr, &fo);
+}
+
 extern "C" int sg_stream_bank_frames(const sg_stream_bank* b, int64_t n, int64_t* frames) {
   if (!b || !frames || n < 0) return SG_E_INVALID;
   *frames = sg::st_bank_frames(b->b, n);

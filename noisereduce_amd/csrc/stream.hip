@@ -30,6 +30,10 @@
 // A spectrum step (sg_stream_push_spectrum) is the same four launches with k_st_apply<N, NS, EX, true> in the third place:
 // it also stores every applied frame's gated spectrum Y = Z * mask (and, on request, the mask row) to the caller's buffers
 // on its way to the inverse transform.  No state, workspace or stage of its own.
+// A feature step (sg_stream_push_features) puts k_st_feat<N, NS, EX> in the third place instead: the same frame, mask and
+// inverse, with the powers |s Y|^power of the frame's bins written to an LDS row of their own and reduced over the bank's
+// filterbank (sg_stream_set_filterbank; feat_sum.hpp's filter sum, shared with rows_feat.hip) before the next frame reuses
+// the row.  What it needs beyond StArgs is a second kernel argument: StArgs does not move.
 // Nothing waits on another workgroup.  No workgroup reads state that another workgroup of the same launch writes: the
 // ring is only written by k_st_finish (which does not read it), the carry is double buffered, the bit rows of a unit are
 // written by its one decide workgroup.  One fixed evaluation order per frame and per output sample: a stream's output
@@ -44,6 +48,8 @@
 #include <vector>
 
 #include "tile_core.hpp"
+#include "feat_sum.hpp"
+#include "feat_tables.hpp"
 #include "stream.hpp"
 #include "../../include/mi355gate_debug.h"
 
@@ -72,6 +78,22 @@ enum { ST_OLA = 0, ST_APPEND = 1, ST_CLEAR = 2 };   // Tile::kind of the finish 
 // the frames follow as consecutive rows of F bins
 struct StSpec {
   int64_t spec_off, mask_off;
+};
+
+// a unit's part of a feature step: the element of feat holding filter 0 / of fmask holding bin 0 of its first newly applied
+// frame; the frames follow as consecutive rows of M filters / F bins
+struct StFeatUnit {
+  int64_t feat_off, mask_off;
+};
+// What k_st_feat needs beyond StArgs, as a second kernel argument (as RwFeat is k_rw_feat's).
+struct StFeat {
+  FeatBank bank;          // the bank's own filterbank (sg_stream_set_filterbank)
+  void* feat;             // [unit][frame][M] of dtype
+  void* fmask;            // final mask rows [unit][frame][F] of dtype, or null
+  const StFeatUnit* fu;   // [unit]
+  double eps;
+  double scale;           // s of |s Z mask|^power: mag_scale (the spectrum step's factor) or the caller's
+  int32_t dtype, power, take_log;
 };
 
 struct StArgs {
@@ -402,6 +424,54 @@ __global__ __launch_bounds__(tile_nt<N>()) void k_st_apply(StArgs A) {
   }
 }
 
+// ---- applied frames of a feature step: k_st_apply's frame, mask and inverse, plus the filterbank features ---------------
+// The callback of mask_and_invert sees every band's product Y[k] = X[k] * mask once and writes p[k] = |s Y[k]|^power
+// (feat_power: the real and imaginary parts are scaled first, as the spectrum step scales them at its store, then
+// squared) into prow, an LDS row of N + 1 doubles behind the frame buffer -- the frame itself has to survive for the
+// inverse, so the powers cannot go into buf as in k_rw_feat.  The inverse's closing team_sync makes the row visible to
+// the team; then lane m, m + NT, ... sums filter m over its hull (feat_filter_sum: ascending k, float64) and stores it,
+// consecutive lanes consecutive filters, rounded once to the output type.  A second team_sync keeps the next frame's
+// powers off the row until every lane has read it.  Power, log and the output type are run-time switches (uniform
+// branches).  LDS: launch_tile_kernel's + (N + 1) doubles.
+template <int N, bool NS, bool EX>
+__global__ __launch_bounds__(tile_nt<N>()) void k_st_feat(StArgs A, StFeat Q) {
+  using ST = typename std::conditional<EX, double, float>::type;
+  using RT = typename std::conditional<EX && NS, double, float>::type;
+  constexpr int NT = tile_nt<N>(), SY = tile_sy<N>();
+  if ((int64_t)blockIdx.x >= A.n_ap) return;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  cx<double>* tw = reinterpret_cast<cx<double>*>(smem);
+  cx<double>* buf = tw + N;
+  double* prow = reinterpret_cast<double*>(buf + lpn<double>(N));
+  const int lane = threadIdx.x;
+  const Tile tl = A.tiles[A.t_ap + blockIdx.x];
+  const StUnit U = A.units[tl.idx];
+  const int M = Q.bank.M;
+  stage_tile_twiddles<N>(tw, A.c.tw);
+  for (int64_t t = tl.a; t < tl.b; ++t) {
+    st_frame_fft<N>(A, U, t, buf, tw, lane);
+    const TimeTaps tp = time_taps(t, A.c.nt, U.Tend);
+    auto mask_at = [&](int k) -> double {
+      const double K = time_smooth((const RT*)A.R, A.c.FS, [&](int64_t q) { return U.mrow + q - U.r0; }, tp, t, A.c.nt, k);
+      return NS ? mask_nonstationary(A.c, K) : mask_stationary(A.c, K, tp.Et, k);
+    };
+    ST* seg_row = (ST*)A.seg + (U.srow + t - (U.ta0 + 1)) * (int64_t)A.c.n;
+    const StFeatUnit S = Q.fu[tl.idx];
+    const int64_t fr = t - (U.ta0 + 1);
+    const int64_t mrow = S.mask_off + fr * (int64_t)A.c.F;
+    mask_and_invert<N>(buf, tw, lane, mask_at, A.c.wfull, seg_row, [&](int k, cx<double> Y, double m) {
+      prow[k] = feat_power(Y, Q.scale, Q.power);
+      if (Q.fmask) feat_store(Q.fmask, Q.dtype, mrow + k, m);
+    });
+    const int64_t frow = S.feat_off + fr * (int64_t)M;
+    for (int m = fresh_lane(lane); m < M; m += NT) {
+      const double lin = feat_filter_sum(Q.bank, A.c.F, m, [&](int k) { return prow[k]; }, prow[N]);
+      feat_store(Q.feat, Q.dtype, frow + m, Q.take_log ? log(lin + Q.eps) : lin);
+    }
+    team_sync<SY>();
+  }
+}
+
 // ---- overlap-add of the newly final samples, partial sums of the open ones, state update ----------------------------
 // Sample p sums its frames in frame order, continuing the partial sum an earlier step left in the carry: the additions
 // are the same whatever the block split.  out = sum seg / sum w^2; positions >= Lout are the zero tail.
@@ -525,6 +595,9 @@ struct StBank {
   size_t tabs_bytes = 0;
   void* ws = nullptr;
   size_t ws_bytes = 0;
+  // the bank's own filterbank (st_set_filterbank): one allocation holding fb [F][M], fbT [M][F], khull [M] and mhull [F]
+  void* fbank = nullptr;
+  FeatBank fb{};   // pointers into fbank; M == 0: none set
   std::vector<StSlot> slots;
 };
 
@@ -541,7 +614,7 @@ int64_t st_emitted(int W, int H, int nt, int64_t n) {
 void st_destroy(StBank* b) {
   if (!b) return;
   for (void* p : {(void*)b->ring, (void*)b->rmax, (void*)b->carry, (void*)b->thr, (void*)b->T2, (void*)b->stage, (void*)b->bits,
-                  (void*)b->fst, (void*)b->fa, (void*)b->nst, (void*)b->mk, (void*)b->slot_list, b->tabs, b->ws})
+                  (void*)b->fst, (void*)b->fa, (void*)b->nst, (void*)b->mk, (void*)b->slot_list, b->tabs, b->ws, b->fbank})
     if (p) (void)hipFree(p);
   delete b;
 }
@@ -564,6 +637,22 @@ int check_slots(const StBank* b, const int32_t* slots, int32_t n, const char* wh
       return SG_E_INVALID;
     }
   return SG_OK;
+}
+}  // namespace
+
+namespace {
+// k_st_feat of geometry N: launch_tile_kernel's LDS plus the row of N + 1 powers (16-byte granules).  At n_fft = 4096
+// that is 32 KiB of twiddles, 36 KiB of padded frame and 16 KiB of powers, 86032 bytes: one workgroup per CU where the
+// spectrum step's 69632 bytes allow two (160 KiB per CU); 43024 bytes (three per CU against four) at n_fft = 2048
+template <int N>
+hipError_t launch_feat_kernel(void (*kernel)(StArgs, StFeat), int64_t ntiles, hipStream_t st, const StArgs& A, const StFeat& Q) {
+  const size_t lds = (size_t)(N + lpn<double>(N)) * sizeof(cx<double>) + ((size_t)(N + 1) * sizeof(double) + 15) / 16 * 16;
+  if (lds > 65536) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kernel, tile_grid(ntiles), dim3(tile_nt<N>()), lds, st, A, Q);
+  return hipGetLastError();
 }
 }  // namespace
 
@@ -710,6 +799,44 @@ int st_set_threshold(StBank* b, const int32_t* slots, int32_t n, const double* t
   return SG_OK;
 }
 
+int st_set_filterbank(StBank* b, const float* fb_host, int32_t n_filters, std::string* err) {
+  if (!fb_host || n_filters < 1 || n_filters > FEAT_MAX_FILTERS) {
+    char m[120];
+    snprintf(m, sizeof m, "sg_stream_set_filterbank: bad argument (1 <= n_filters <= %d)", FEAT_MAX_FILTERS);
+    *err = m;
+    return SG_E_INVALID;
+  }
+  const int F = b->c.F, M = n_filters;
+  // one host image of the four tables, each part 256-byte aligned: fb, fbT, khull, mhull
+  const size_t fbb = align256((size_t)F * M * 4), khb = align256((size_t)M * 8), mhb = align256((size_t)F * 8);
+  std::vector<char> host(2 * fbb + khb + mhb, 0);
+  memcpy(host.data(), fb_host, (size_t)F * M * 4);
+  if (!feat_tables(fb_host, F, M, (float*)(host.data() + fbb), (int32_t*)(host.data() + 2 * fbb),
+                   (int32_t*)(host.data() + 2 * fbb + khb))) {
+    *err = "sg_stream_set_filterbank: the filterbank has a non-finite entry";
+    return SG_E_INVALID;
+  }
+  void* dev = nullptr;
+  if (hipMalloc(&dev, host.size()) != hipSuccess) { *err = "sg_stream_set_filterbank: device allocation failed"; return SG_E_NOMEM; }
+  if (hipMemcpy(dev, host.data(), host.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(dev);
+    *err = "sg_stream_set_filterbank: table upload failed";
+    return SG_E_HIP;
+  }
+  if (b->fbank) {   // launches of an earlier step may still read the tables about to be freed
+    if (hipDeviceSynchronize() != hipSuccess) {
+      (void)hipFree(dev);
+      *err = "sg_stream_set_filterbank: hipDeviceSynchronize failed";
+      return SG_E_HIP;
+    }
+    (void)hipFree(b->fbank);
+  }
+  b->fbank = dev;
+  char* d = (char*)dev;
+  b->fb = FeatBank{(const float*)d, (const float*)(d + fbb), (const int2*)(d + 2 * fbb), (const int2*)(d + 2 * fbb + khb), M};
+  return SG_OK;
+}
+
 int st_reset(StBank* b, const int32_t* slots, int32_t n, hipStream_t st, std::string* err) {
   int rc = check_slots(b, slots, n, "sg_stream_reset", err);
   if (rc) return rc;
@@ -771,10 +898,10 @@ int st_counters(const StBank* b, int32_t slot, int64_t* n, int64_t* emitted, std
 }
 
 int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_dtype, const sg_stream_rec* recs,
-            int32_t n_recs, hipStream_t st, std::string* err, const StSpecOut* so) {
+            int32_t n_recs, hipStream_t st, std::string* err, const StSpecOut* so, const StFeatOut* fo) {
   const RgCtx& c = b->c;
   const int h = c.W / 2;
-  const char* who = so ? "sg_stream_push_spectrum" : "sg_stream_push";
+  const char* who = fo ? "sg_stream_push_features" : so ? "sg_stream_push_spectrum" : "sg_stream_push";
   char msg[200];
   // ---- every argument is checked before any device work or state change
   auto dtype_ok = [&](int d) { return d == SG_F32 || d == SG_F64 || (b->exact && (d == SG_I16 || d == SG_I32)); };
@@ -785,6 +912,20 @@ int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_
   if (so && ((so->dtype != SG_F32 && so->dtype != SG_F64) || (n_recs > 0 && (!so->spec || !so->recs)))) {
     *err = std::string(who) + ": bad argument (spec_dev and spec_recs are needed; spec_dtype is SG_F32 or SG_F64)";
     return SG_E_INVALID;
+  }
+  if (fo) {
+    if (so) { *err = std::string(who) + ": bad argument (a step stores the spectrum or the features)"; return SG_E_INVALID; }
+    if ((fo->dtype != SG_F32 && fo->dtype != SG_F64) || (n_recs > 0 && (!fo->feat || !fo->recs))) {
+      *err = std::string(who) + ": bad argument (feat_dev and feat_recs are needed; feat_dtype is SG_F32 or SG_F64)";
+      return SG_E_INVALID;
+    }
+    if (fo->power != 1 && fo->power != 2) { *err = std::string(who) + ": power must be 1 or 2"; return SG_E_INVALID; }
+    if (!(fo->eps == fo->eps)) { *err = std::string(who) + ": eps is NaN"; return SG_E_INVALID; }
+    if (!(fo->scale >= 0.0 && fo->scale <= 1.79769313486231570e308)) {
+      *err = std::string(who) + ": scale must be finite and not negative (0: the bank's 1 / sum(window))";
+      return SG_E_INVALID;
+    }
+    if (!b->fb.M) { *err = std::string(who) + ": no filterbank set (sg_stream_set_filterbank)"; return SG_E_INVALID; }
   }
   std::vector<char> seen(b->n_slots, 0);
   for (int32_t i = 0; i < n_recs; ++i) {
@@ -834,10 +975,24 @@ int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_
         return SG_E_INVALID;
       }
     }
+    if (fo) {
+      // (the frames the record reports: the spectrum step's arithmetic)
+      const StSlot& S = b->slots[r.slot];
+      const int64_t n1 = S.n + r.n_samples;
+      const int64_t ta1 = r.flush ? (n1 + 2 * (int64_t)h - c.W) / c.H : std::max(S.ta, st_bank_frames(b, n1) - 1);
+      const sg_stream_feat_rec& q = fo->recs[i];
+      if (q.feat_offset < 0 || (fo->mask && q.mask_offset < 0) ||
+          (b->C > 1 && (q.feat_stride < (ta1 - S.ta) * b->fb.M || (fo->mask && q.mask_stride < (ta1 - S.ta) * c.F)))) {
+        snprintf(msg, sizeof msg, "%s: slot %d: bad feature offsets / strides", who, r.slot);
+        *err = msg;
+        return SG_E_INVALID;
+      }
+    }
   }
   // ---- plan
   std::vector<StUnit> units;
   std::vector<StSpec> specs;
+  std::vector<StFeatUnit> feats;
   std::vector<StSlot> after(n_recs);
   int64_t mrows = 0, sframes = 0;
   const int64_t UNBOUNDED = (int64_t)1 << 60;
@@ -884,6 +1039,7 @@ int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_
       V.srow = sframes; sframes += V.ta1 - V.ta0;
       units.push_back(V);
       if (so) specs.push_back(StSpec{so->recs[i].spec_offset + ch * so->recs[i].stride, so->recs[i].mask_offset + ch * so->recs[i].stride});
+      if (fo) feats.push_back(StFeatUnit{fo->recs[i].feat_offset + ch * fo->recs[i].feat_stride, fo->recs[i].mask_offset + ch * fo->recs[i].mask_stride});
     }
     StSlot& N = after[i];
     N.has_thr = true;
@@ -917,7 +1073,10 @@ int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_
   A.n_fin = tl.count_since(A.t_fin);
   // ---- tables and scratch
   const size_t ub = align256(units.size() * sizeof(StUnit)), tb = align256(tl.tiles.size() * sizeof(Tile));
-  const size_t sb = align256(specs.size() * sizeof(StSpec));
+  // (one optional third table: the spectrum step's or the feature step's)
+  const void* third = fo ? (const void*)feats.data() : (const void*)specs.data();
+  const size_t third_bytes = fo ? feats.size() * sizeof(StFeatUnit) : specs.size() * sizeof(StSpec);
+  const size_t sb = align256(third_bytes);
   int rc = grow_device_buffer(&b->tabs, &b->tabs_bytes, ub + tb + sb, st, who, "table", err);
   if (rc) return rc;
   const bool ex = b->exact != 0;
@@ -925,7 +1084,7 @@ int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_
   if ((rc = grow_device_buffer(&b->ws, &b->ws_bytes, Rb + Sb, st, who, "workspace", err))) return rc;
   if (upload_tables(b->tabs, st, {{units.data(), units.size() * sizeof(StUnit), ub},
                                   {tl.tiles.data(), tl.tiles.size() * sizeof(Tile), tb},
-                                  {specs.data(), specs.size() * sizeof(StSpec), sb}}) != hipSuccess) {
+                                  {third, third_bytes, sb}}) != hipSuccess) {
     *err = std::string(who) + ": table upload failed";
     return SG_E_HIP;
   }
@@ -941,6 +1100,14 @@ int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_
   if (so) {
     A.spec = so->spec; A.smask = so->mask; A.spec_dtype = so->dtype;
     A.sp = (const StSpec*)((char*)b->tabs + ub + tb);
+  }
+  StFeat Q{};
+  if (fo) {
+    Q.bank = b->fb;
+    Q.feat = fo->feat; Q.fmask = fo->mask; Q.dtype = fo->dtype;
+    Q.fu = (const StFeatUnit*)((char*)b->tabs + ub + tb);
+    Q.eps = fo->eps; Q.scale = fo->scale == 0.0 ? c.mag_scale : fo->scale;
+    Q.power = fo->power; Q.take_log = fo->take_log ? 1 : 0;
   }
   const bool ns = b->ns != 0;
   // ---- the step: the same four launches whatever was pushed
@@ -960,6 +1127,10 @@ int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_
   if (e == hipSuccess) {
     Prof pr(c, SG_STAGE_RG_APPLY, st);
     e = dispatch_N(c.N, [&](auto n) {
+      if (fo) {
+        if (ex) return ns ? launch_feat_kernel<n()>(k_st_feat<n(), true, true>, A.n_ap, st, A, Q) : launch_feat_kernel<n()>(k_st_feat<n(), false, true>, A.n_ap, st, A, Q);
+        return ns ? launch_feat_kernel<n()>(k_st_feat<n(), true, false>, A.n_ap, st, A, Q) : launch_feat_kernel<n()>(k_st_feat<n(), false, false>, A.n_ap, st, A, Q);
+      }
       if (so) {
         if (ex) return ns ? launch_tile_kernel<n()>(k_st_apply<n(), true, true, true>, A.n_ap, st, A) : launch_tile_kernel<n()>(k_st_apply<n(), false, true, true>, A.n_ap, st, A);
         return ns ? launch_tile_kernel<n()>(k_st_apply<n(), true, false, true>, A.n_ap, st, A) : launch_tile_kernel<n()>(k_st_apply<n(), false, false, true>, A.n_ap, st, A);

@@ -72,9 +72,24 @@ struct StSpecOut {
   void* mask;
   const sg_stream_spec_rec* recs;
 };
-// so == nullptr: sg_stream_push.  Otherwise the same plan and launches, the apply launch in its spectrum-storing form
+// what a feature step (sg_stream_push_features) stores on top of a push: feat / mask buffers (mask may be null), the
+// element type of both (SG_F32 / SG_F64), the table parallel to the step's records and the switches of the reduction
+// (scale == 0: the handle's 1 / sum(window))
+struct StFeatOut {
+  void* feat;
+  int dtype;
+  void* mask;
+  const sg_stream_feat_rec* recs;
+  int32_t power, take_log;
+  double eps, scale;
+};
+// so == fo == nullptr: sg_stream_push.  Otherwise the same plan and launches, the apply launch in its spectrum-storing
+// form (so) or its feature form (fo); at most one of the two is non-null
 int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_dtype, const sg_stream_rec* recs,
-            int32_t n_recs, hipStream_t st, std::string* err, const StSpecOut* so = nullptr);
+            int32_t n_recs, hipStream_t st, std::string* err, const StSpecOut* so = nullptr, const StFeatOut* fo = nullptr);
+// the bank's own filterbank (sg_stream_set_filterbank): fb_host float[F][M]; the device tables are feat_tables.hpp's four
+// arrays, owned by the bank.  Synchronises the device when it replaces a filterbank; a refused one leaves the earlier in place
+int st_set_filterbank(StBank* b, const float* fb_host, int32_t n_filters, std::string* err);
 int st_reset(StBank* b, const int32_t* slots, int32_t n, hipStream_t st, std::string* err);
 int st_counters(const StBank* b, int32_t slot, int64_t* n, int64_t* emitted, std::string* err);
 // state transfer (sg_stream_export_bytes / _export / _import): `sig` carries the handle's part of the signature (the gate's

@@ -111,6 +111,12 @@ remaining ones up to ``T = (N + 2 h - W) // H + 1``.  The contract:
 ``Y`` is complex64 for a float32 block and complex128 for a float64 / int16 / int32 one, on any bank kind: the transforms and
 the masks are float64 in every bank.  Same four launches per step, no host synchronisation for device tensors.
 
+``set_filterbank(fb)`` and ``push_features`` / ``flush_features`` are the same steps with every applied frame reduced to
+filterbank (log-mel) features on the device, ``sum_k fb[k, m] |s Z mask| ** power`` or its ``ln(. + eps)``, instead of
+stored as ``F`` complex bins (sg_stream_set_filterbank / sg_stream_push_features): the frames, the audio
+and the mask of ``push_spectrum``, float64 sums in a fixed order rounded once, bitwise independent of the block split, the
+slot, the other streams and the kind of the earlier steps.  The filterbank belongs to the bank, not to a stream's state.
+
 Out of scope: spectrum-only steps that skip the inverse transform, gradients through a stream, ``TorchGate``, collectives between GPUs (a state's bytes are the transport), and ``n_fft`` other than a power
 of two from 256 to 4096 (``ValueError``).
 """
@@ -120,6 +126,7 @@ import numpy as np
 import torch
 
 from noisereduce_amd import _ffi
+from noisereduce_amd.torchgate.filterbank import check_filterbank
 
 _NONE_CHUNK = 1 << 62
 _N_FFTS = (256, 512, 1024, 2048, 4096)
@@ -361,6 +368,8 @@ class StreamBank:
         self._kind = [(False, np.dtype(np.float32), True)] * self.n_streams   # (tensor I/O, dtype, flat) of the last block
         self._bank = self._gate = None
         self._pending = []                    # noise profiles set before the first device call
+        self._fb = None                       # the filterbank (set_filterbank): (F, M) float32, validated
+        self._fb_pending = False              # ... set before the first device call: uploaded by _ensure
         self._device_arg = device
         self._gate_kw = dict(variant=_ffi.SG_VARIANT_S, stationary=stationary, n_fft=n_fft, win_length=W, hop_length=H,
                              n_grad_freq=nf if smooth else 1, n_grad_time=nt if smooth else 1, smooth_mask=smooth,
@@ -392,6 +401,9 @@ class StreamBank:
             else:
                 self._bank = self._gate.stream_create_nonstationary(self.n_streams, self.channels, self.max_block,
                                                                     self.lookahead_frames)
+        if self._fb_pending:
+            self._fb_pending = False
+            self._gate.stream_set_filterbank(self._bank, self._fb)
         pending, self._pending = self._pending, []
         for slots, kind, val in pending:
             if kind == "db":
@@ -478,10 +490,41 @@ class StreamBank:
         if self._bank is not None:
             self._ensure()
 
+    # -- filterbank --------------------------------------------------------------------------------------------
+    def set_filterbank(self, fb):
+        """The bank's filterbank for ``push_features`` / ``flush_features``: any real ``(n_fft // 2 + 1, M)`` array or tensor,
+        ``1 <= M <= 1024``, finite entries (negative ones are fine for ``log=False``); a constant, validated with
+        ``torchgate.filterbank.check_filterbank`` (``ValueError``; the bank then keeps the filterbank it had).
+        ``noisereduce_amd.torchgate.mel_filterbank(sr, n_fft, n_mels)`` is the common case.  Before the first device call it
+        is kept pending, like ``set_noise``; replacing a filterbank synchronises the device.  The filterbank belongs to the
+        bank, not to a stream: ``snapshot`` / ``restore`` do not carry it, and a moved stream continues its features where
+        the destination bank holds the same filterbank."""
+        a = check_filterbank(fb, self.n_fft // 2 + 1)
+        if self._bank is not None:
+            self._gate.stream_set_filterbank(self._bank, a)      # (raises before self._fb changes)
+            self._fb, self._fb_pending = a, False
+        else:
+            self._fb, self._fb_pending = a, True
+
+    def _feature_args(self, power, log, eps, scale):
+        """(power, log, eps, the C ABI's scale) of a feature step, or ValueError -- before any device work."""
+        if isinstance(power, bool) or power not in (1, 2):
+            raise ValueError(f"StreamBank: power must be 1 or 2 (got {power!r})")
+        eps = float(eps)
+        if eps != eps:
+            raise ValueError("StreamBank: eps is NaN")
+        if scale not in ("scipy", "torch"):
+            raise ValueError(f"StreamBank: scale must be 'scipy' or 'torch' (got {scale!r})")
+        if self._fb is None:
+            raise ValueError("StreamBank: no filterbank set (set_filterbank)")
+        # (0.0: the bank's own 1 / sum(window), the very factor push_spectrum applies; 1.0: the unscaled transform)
+        return int(power), bool(log), eps, 0.0 if scale == "scipy" else 1.0
+
     # -- steps -------------------------------------------------------------------------------------------------
-    def _step(self, blocks, flush, spectrum=False, return_mask=False):
+    def _step(self, blocks, flush, spectrum=False, return_mask=False, features=None):
         """blocks: {slot: block or None}; every argument is checked before any device work.  ``spectrum``: a spectrum
-        step (sg_stream_push_spectrum), every result a tuple (samples, Y[, mask])."""
+        step (sg_stream_push_spectrum), every result a tuple (samples, Y[, mask]).  ``features``: ``_feature_args``'
+        result, a feature step (sg_stream_push_features), every result a tuple (samples, feat[, mask])."""
         C, W = self.channels, self.win_length
         items, tensor_io = [], None
         for s, blk in blocks.items():
@@ -532,7 +575,9 @@ class StreamBank:
         tdt = _TORCH[travel]
         recs, outs, in_off, out_off = [], [], 0, 0
         srecs, frames, sp_off = [], [], 0      # spectrum steps: where every record's newly applied frames go
+        ft_off = 0                             # feature steps: the feature rows (M wide) next to the mask rows (F wide)
         F, H = self.n_fft // 2 + 1, self.hop_length
+        M = self._fb.shape[1] if features else 0
         for s, a, n, flat in items:
             n1 = self._n[s] + n
             k = (n1 if flush else emitted(n1, W, self.hop_length, self._lag)) - self._e[s]
@@ -541,13 +586,18 @@ class StreamBank:
             outs.append((s, a, k, flat, out_off))
             in_off += C * n
             out_off += C * k
-            if spectrum:
+            if spectrum or features:
                 kf = ((n1 + 2 * (W // 2) - W) // H + 1 if flush else frames_applied(n1, W, H, self._lag)) - \
                     frames_applied(self._n[s], W, H, self._lag)
-                srecs.append(_ffi.SgStreamSpecRec(spec_offset=sp_off, mask_offset=sp_off, stride=kf * F))
-                frames.append((kf, sp_off))
+                if features:
+                    srecs.append(_ffi.SgStreamFeatRec(feat_offset=ft_off, feat_stride=kf * M, mask_offset=sp_off,
+                                                      mask_stride=kf * F))
+                else:
+                    srecs.append(_ffi.SgStreamSpecRec(spec_offset=sp_off, mask_offset=sp_off, stride=kf * F))
+                frames.append((kf, sp_off, ft_off))
                 sp_off += C * kf * F
-        if spectrum:      # complex64 where every slot's own block is float32; else complex128, a float32 slot rounded once
+                ft_off += C * kf * M
+        if spectrum or features:      # complex64 where every slot's own block is float32; else complex128, a float32 slot rounded once
             own = [np.dtype(str(a.dtype).replace("torch.", "")) if a is not None else self._kind[s][1] for s, a, _, _ in items]
             narrow = all(dt == np.dtype(np.float32) for dt in own)
             cdt, rdt = (torch.complex64, torch.float32) if narrow else (torch.complex128, torch.float64)
@@ -563,7 +613,11 @@ class StreamBank:
             if x.numel() == 0:
                 x = torch.empty(1, dtype=tdt, device=self.device)
             out = torch.empty(max(out_off, 1), dtype=tdt, device=self.device)
-            if spectrum:
+            if features:      # (feat is real: float32 where every slot's own block is float32, else float64)
+                spec = torch.empty(max(ft_off, 1), dtype=rdt, device=self.device)
+                mask = torch.empty(max(sp_off, 1), dtype=rdt, device=self.device) if return_mask else None
+                self._gate.stream_push_features(self._bank, x, out, spec, mask, recs, srecs, *features)
+            elif spectrum:
                 spec = torch.empty(max(sp_off, 1), dtype=cdt, device=self.device)
                 mask = torch.empty(max(sp_off, 1), dtype=rdt, device=self.device) if return_mask else None
                 self._gate.stream_push_spectrum(self._bank, x, out, spec, mask, recs, srecs)
@@ -593,19 +647,22 @@ class StreamBank:
                     if o.dtype != dt:
                         o = torch.where(o != o, torch.zeros_like(o), o) if tensor_io else np.where(o != o, 0.0, o)
                 res[s] = o.to(dt) if tensor_io else o.astype(dt, copy=True)
-            if not spectrum:
+            if not (spectrum or features):
                 return res
             fields = [spec] + ([mask] if return_mask else [])
             if not tensor_io:
                 fields = [f.cpu().numpy() for f in fields]
-            for (s, a, k, flat, _), (kf, off), dt in zip(outs, frames, own):
-                parts = []
-                for f in fields:      # (C, kf, F) as stored, bins contiguous; handed out as the (C, F, kf) view
+            # (field, width of its rows -- M filters or F bins --, which of a record's two offsets places it)
+            cols = [(f, M, 2) if features and i == 0 else (f, F, 1) for i, f in enumerate(fields)]
+            for (s, a, k, flat, _), fr, dt in zip(outs, frames, own):
+                parts, kf = [], fr[0]
+                for f, R, j in cols:      # (C, kf, R) as stored, rows contiguous; handed out as the (C, R, kf) view
+                    off = fr[j]
                     if tensor_io and (narrow or dt != np.dtype(np.float32)):      # (one view op per field: a step is host-bound)
-                        parts.append(f.as_strided((F, kf), (1, F), off) if flat and C == 1 else
-                                     f.as_strided((C, F, kf), (kf * F, 1, F), off))
+                        parts.append(f.as_strided((R, kf), (1, R), off) if flat and C == 1 else
+                                     f.as_strided((C, R, kf), (kf * R, 1, R), off))
                         continue
-                    v = f[off:off + C * kf * F].reshape(C, kf, F)
+                    v = f[off:off + C * kf * R].reshape(C, kf, R)
                     if dt == np.dtype(np.float32) and not narrow:
                         if tensor_io:
                             v = v.to(torch.complex64 if v.is_complex() else torch.float32)
@@ -664,6 +721,44 @@ class StreamBank:
         if blocks:
             d.update(self._block_map(blocks, "flush"))
         return self._step(d, flush=True, spectrum=True, return_mask=bool(return_mask))
+
+    def push_features(self, blocks, power=2.0, log=False, eps=1e-10, scale="scipy", return_mask=False):
+        """``push`` that also hands out filterbank (log-mel) features of the newly applied frames, reduced on the device
+        while each frame is still on chip: ``{slot: block}`` (or ``(slot, block)`` pairs) -> ``{slot: (samples, feat)}`` or,
+        ``return_mask=True``, ``{slot: (samples, feat, mask)}``.  ``samples`` is exactly what ``push`` returns and ``mask``
+        exactly what ``push_spectrum(return_mask=True)`` returns.  ``feat`` holds the ``k`` newly applied frames
+        (``push_spectrum``'s ``k``; ``frames(slot)`` counts them) of
+
+            lin[m, t] = sum_k fb[k, m] * |s * Z[k, t] * mask[k, t]| ** power        feat = ln(lin + eps) if log else lin
+
+        with ``fb`` the bank's filterbank (``set_filterbank``; none set: ``ValueError``) and ``power`` 1 or 2.
+        ``scale="scipy"``: ``s = 1 / sum(window)``, the features of exactly the ``Y`` that ``push_spectrum`` returns;
+        ``scale="torch"``: ``s = 1``, the unscaled ``torch.stft`` convention of ``TorchGate.gated_filterbank``, so that a
+        model trained on offline features can read live ones.  The default ``eps`` is 1e-10, not ``gated_filterbank``'s
+        1e-6: under the scipy scaling a full-scale sine has power 0.25 per bin, so 1e-6 would sit above quiet speech.
+
+        ``(M, k)`` for a flat mono stream and ``(C, M, k)`` otherwise; stored ``(..., k, M)`` with the filters contiguous
+        and returned as the transposed view, as ``gated_filterbank`` returns its result.  float32 where the slot's own
+        block is float32 and float64 otherwise.  Transform, mask, powers and sums are float64, the weights float32 values
+        widened; every filter sums in ascending ``k`` over the hull of its non-zero bins and the value is rounded once at
+        the store.  Each frame's features are bitwise independent of the block split, the slot, the other streams and of
+        whether earlier steps were ``push``, ``push_spectrum`` or ``push_features``; ``snapshot`` / ``restore`` continue
+        them where the destination bank holds the same filterbank (the filterbank is not part of a stream's state).  Same
+        four launches, no host synchronisation for device tensors."""
+        args = self._feature_args(power, log, eps, scale)
+        return self._step(self._block_map(blocks, "step"), flush=False, return_mask=bool(return_mask), features=args)
+
+    def flush_features(self, slots, blocks=None, power=2.0, log=False, eps=1e-10, scale="scipy", return_mask=False):
+        """``flush`` that also reports the features of every remaining frame, up to ``T = (N + 2 (W // 2) - W) // H + 1`` of
+        a stream of ``N`` samples: ``{slot: (tail, feat[, mask])}`` (``push_features``)."""
+        args = self._feature_args(power, log, eps, scale)
+        slots = self._slots(slots)
+        if len(set(slots)) != len(slots):
+            raise ValueError("StreamBank: a slot appears twice in one flush")
+        d = {s: None for s in slots}
+        if blocks:
+            d.update(self._block_map(blocks, "flush"))
+        return self._step(d, flush=True, return_mask=bool(return_mask), features=args)
 
     def reset(self, slots):
         slots = self._slots(slots)
@@ -806,6 +901,17 @@ class StreamGate:
     def flush_spectrum(self, block=None, return_mask=False):
         """``(tail, Y)`` or ``(tail, Y, mask)``: the remaining samples and frames (``StreamBank.flush_spectrum``)."""
         return self.bank.flush_spectrum([0], None if block is None else {0: block}, return_mask=return_mask)[0]
+
+    def set_filterbank(self, fb):
+        self.bank.set_filterbank(fb)
+
+    def push_features(self, block, **kw):
+        """``(samples, feat)`` or ``(samples, feat, mask)`` (``StreamBank.push_features``; the same keywords)."""
+        return self.bank.push_features({0: block}, **kw)[0]
+
+    def flush_features(self, block=None, **kw):
+        """``(tail, feat)`` or ``(tail, feat, mask)``: the remaining samples and frames (``StreamBank.flush_features``)."""
+        return self.bank.flush_features([0], None if block is None else {0: block}, **kw)[0]
 
     def reset(self):
         self.bank.reset([0])
