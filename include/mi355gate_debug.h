@@ -56,7 +56,14 @@ SG_API int sg_debug_range(const sg_handle* h, int64_t range[2]);
 #define SG_SPEC_NONSTAT_RAW 5   /* stage_nonstat_raw: the raw sigmoid field, smoothed by the general kernels */
 #define SG_SPEC_BITS_TO_RAW 0x100 /* the decision bits went through k_spec_bits_to_raw into the float smoothing kernels */
 #define SG_SPEC_MASK_DIRECT 0x200 /* the smoothing wrote straight into the caller's mask buffer (no copy from the workspace) */
+/* which = 19: the form of the last noise statistics of fewer than 16 units on the handle (sg_noise_stats, the noise rows of
+ * sg_process_batch), 0 when there were none (host bookkeeping, no synchronisation; no kernel reads or writes it). */
+#define SG_STATS_THREE_LAUNCH 1 /* k_stft<double>, k_colstats1, k_colstats1_final */
+#define SG_STATS_TWO_LAUNCH 2   /* k_noise_moments (transform + slice partials), k_colstats1_final over its slices */
 SG_API int sg_debug_counter(sg_handle* h, int32_t which, int64_t* value, void* stream);
+/* what = 5: the stationary gate's compare constants as the last sg_noise_stats call left them: T2 double[n_bins] (power-domain
+ * threshold per band), then the 64 words of the floor-test block (word 2 + b: bit pattern of band block b's float bound on
+ * max|x|); bytes = 8 n_bins + 256.  Needs no processed batch. */
 SG_API int sg_debug_fetch(sg_handle* h, int32_t what, void* host, int64_t bytes, void* stream);
 
 /* Per-noise-source thresholds in dB of the last sg_process_clips call, [n_noise][n_bins] float64 (stationary gate;
@@ -112,6 +119,10 @@ SG_API int sg_debug_backward_route(const sg_handle* h, int64_t* value);
                                       * field materialised, the recurrence serial per band, two direct smoothing passes, masked frames + gather --
                                       * also where the fused float64 apply (k_apply_fast64), the tile-parallel recurrence and the LDS-tiled
                                       * smoothing would do: A/B and parity of the two */
+#define SG_OPT_STATS_THREE_LAUNCH 17 /* value != 0: the noise statistics of one clip always in three launches (k_stft<double>, k_colstats1,
+                                      * k_colstats1_final), also where k_noise_moments + k_colstats1_final would do (variant S, one clip of
+                                      * >= 512 frames at n_fft = 256 / 512 / 1024 / 2048, at most 256 slices): A/B and parity of the two.
+                                      * Thresholds differ by summation order only */
 #define SG_OPT_FORCE_NOFAST 2  /* value != 0: keep the bit-mask stages but use the general apply kernels */
 
 /* ---- per-kernel timing (bench.py's roofline leg) ------------------------------------- */

@@ -38,6 +38,7 @@ SG_OPT_ROWGATE_SHAPE = 12
 SG_OPT_FLOOR_TEST = 13
 SG_OPT_TILE_ORDER = 15
 SG_OPT_EXACT_MATERIALISED = 16
+SG_OPT_STATS_THREE_LAUNCH = 17
 SG_OPT_FORCE_UNFUSED = 1
 SG_OPT_FORCE_NOFAST = 2
 SG_BWD_ROW, SG_BWD_FAST, SG_BWD_REG, SG_BWD_OLA, SG_BWD_ROWS = 1, 2, 3, 4, 5
@@ -1078,6 +1079,21 @@ class Gate:
         with torch.cuda.device(self.device):
             self._check(self.lib.sg_debug_counter(self._h, int(which), ctypes.byref(v), self._stream()))
         return int(v.value)
+
+    def stats_route(self):
+        """The form of the last noise statistics of fewer than 16 units on this handle: 1 = k_stft<double> + k_colstats1 +
+        k_colstats1_final, 2 = k_noise_moments + k_colstats1_final, 0 = none yet -- sg_debug_counter(19), host bookkeeping only."""
+        return self.debug_counter(19)
+
+    def gate_consts(self):
+        """``(T2, alim)`` of the last noise_stats call: the power-domain compare constant per band (n_bins,) float64 and the
+        float32 bounds on max|x| of the floor test per block of 64 bands -- sg_debug_fetch(5)."""
+        host = np.empty(self.n_bins * 8 + 256, dtype=np.uint8)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.sg_debug_fetch(self._h, 5, host.ctypes.data_as(c_void_p), host.nbytes, self._stream()))
+        t2 = host[:self.n_bins * 8].view(np.float64).copy()
+        words = host[self.n_bins * 8:].view(np.uint32)
+        return t2, words[2:2 + (self.n_bins + 63) // 64].view(np.float32).copy()
 
     def smooth_route(self):
         """The mask smoothing of the last gate call on this handle: ``(kernel name, bytes of the cell it sums in, output

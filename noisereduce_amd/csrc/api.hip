@@ -200,6 +200,8 @@ struct sg_handle {
   int64_t smooth_route = 0;   // sg_debug_counter 17: SG_SMOOTH_* of the last smoothing launch | cell bytes << 8 | tile frames << 16
   DevBuf fb_d, fbT_d, fb_khull, fb_mhull;   // sg_set_filterbank: the bank [F][M], its transpose and the two hull tables (feat.hpp)
   int n_filters = 0;                        // 0: no bank set
+  bool stats_three = false;   // SG_OPT_STATS_THREE_LAUNCH: the noise statistics always as k_stft<double> + k_colstats1 + k_colstats1_final
+  int64_t stats_route = 0;    // sg_debug_counter 19: SG_STATS_* form of the last stage_stats call of fewer than 16 units
   int64_t spec_route = 0;     // sg_debug_counter 18: SG_SPEC_* decide branch of the last sg_gate_spectrum call | flags | sub-batches << 16
   int tile_order = 0;                // SG_OPT_TILE_ORDER: 0 (default, round 6) = persistent workgroups looping over tickets (onepass.hpp PERSIST), 2 = one ticket-drawn tile per workgroup (the kernel of rounds 2-5), 1 = tile = block index
                                      // block index (no ticket), 0 = persistent workgroups looping over tickets (round 6: 1 % faster alone on the
@@ -1535,11 +1537,88 @@ static int stage_colstats(sg_handle* h, const Geom& g, int64_t ub, double* thres
   return SG_OK;
 }
 
+// Noise statistics in two launches (k_noise_moments + k_colstats1_final on 16-band workgroups): one noise clip of a register
+// geometry.  A slice is the TEAMS - 1 frames of one k_noise_moments workgroup, and the final stage holds at most
+// NM_TG * (64 / NM_BW) * NM_MAXS = 256 slices in registers; clips beyond that keep the three launches (n_fft = 2048, whose 256-thread
+// teams leave 3 frames per slice: beyond 768 frames).  Below 512 frames the three-launch route stays too: its slicing
+// is what the short statistics clips of the tests were built against, and one round of workgroups has nothing to gain there.
+constexpr int NM_TG = 4;       // wavefronts of the final stage's workgroup
+constexpr int NM_BW = 16;      // bands of the final stage's workgroup: 4 slice groups per wavefront
+constexpr int NM_MAXS = 16;    // slices per thread
+constexpr int NM_MIN_FRAMES = 512;
+template <int N>
+constexpr int nm_team_threads() { return N >= 1024 ? 256 : team_threads<N>(); }   // (n_fft = 2048: the SG_STATS_TEAM shape of launch_stft_n)
+template <int N>
+constexpr int nm_frames_per_slice() { return 1024 / nm_team_threads<N>() - 1; }
+static int nm_fps(int N) {
+  switch (N) {
+    case 128: return nm_frames_per_slice<128>();
+    case 256: return nm_frames_per_slice<256>();
+    case 512: return nm_frames_per_slice<512>();
+    case 1024: return nm_frames_per_slice<1024>();
+  }
+  return 0;
+}
+static bool stats_two_launch(const sg_handle* h, const Geom& g, int64_t ub) {
+  if (h->stats_three || ub != 1 || h->p.variant != SG_VARIANT_S || !(h->fast_ok || h->reg) || h->big_M || h->czt_M) return false;
+  const int fps = nm_fps(h->N);
+  return fps > 0 && g.T >= NM_MIN_FRAMES && (g.T + fps - 1) / fps <= NM_TG * (64 / NM_BW) * NM_MAXS;
+}
+template <int N>
+static hipError_t launch_noise_moments_n(const sg_handle* h, const View& v, const Geom& g, int nts, hipStream_t st,
+                                         unsigned* alim_b, int n_alim) {
+  constexpr int NT = nm_team_threads<N>(), TEAMS = 1024 / NT;
+  const size_t lds = (size_t)(N + TEAMS * lpn<double>(N)) * sizeof(cx<double>);
+  auto kern = k_noise_moments<N, NT, TEAMS>;
+  hipError_t e = set_lds(reinterpret_cast<const void*>(kern), lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kern, dim3((unsigned)nts, 1), dim3(TEAMS * NT), lds, st, v, g, (const cx<double>*)h->tw64.p,
+                     (const double*)h->wfull64.p, (double*)h->P.p, h->mag_scale, (double*)h->part.p, db_fast_consts(h),
+                     alim_b, n_alim);
+  return hipGetLastError();
+}
+static hipError_t launch_noise_moments(const sg_handle* h, const View& v, const Geom& g, int nts, hipStream_t st,
+                                       unsigned* alim_b, int n_alim) {
+  switch (h->N) {
+    case 128: return launch_noise_moments_n<128>(h, v, g, nts, st, alim_b, n_alim);
+    case 256: return launch_noise_moments_n<256>(h, v, g, nts, st, alim_b, n_alim);
+    case 512: return launch_noise_moments_n<512>(h, v, g, nts, st, alim_b, n_alim);
+    case 1024: return launch_noise_moments_n<1024>(h, v, g, nts, st, alim_b, n_alim);
+  }
+  return hipErrorInvalidValue;
+}
+
 // power field + band statistics -> threshold
 static int stage_stats(sg_handle* h, const View& v, const Geom& g, int64_t ub, double* thresh_out, hipStream_t st,
                        bool gate_consts = false) {
+  if (ub < 16 && stats_two_launch(h, g, ub)) {
+    // one noise clip of a register geometry: transform + slice partials -> final (2 launches instead of 3)
+    const int fps = nm_fps(h->N);
+    const int nts = (int)((g.T + fps - 1) / fps);
+    int rc = ensure(h, h->part, (size_t)nts * STAT1_NP * g.FS * 8);
+    if (rc) return rc;
+    GateConsts gc{};
+    if (gate_consts && (g.FS + 63) / 64 <= 62) {
+      if ((rc = ensure(h, h->T2, (size_t)g.FS * 8))) return rc;
+      if ((rc = ensure_zeroed(h, h->alim, 256, st))) return rc;
+      gc.T2 = (double*)h->T2.p; gc.alim_b = (unsigned*)h->alim.p + 2; gc.sum_abs_w = h->sum_abs_w;
+    }
+    {
+      ProfScope ps(h, SG_STAGE_STFT_POWER, st);
+      HIPCHK(h, launch_noise_moments(h, v, g, nts, st, gc.alim_b, (g.FS + 63) / 64));
+    }
+    ProfScope ps(h, SG_STAGE_COLSTATS, st);
+    hipLaunchKernelGGL((k_colstats1_final<NM_TG, true, NM_BW, NM_MAXS>), dim3((unsigned)((g.FS + NM_BW - 1) / NM_BW), 1), dim3(64 * NM_TG), 0, st,
+                       (const double*)h->part.p, (const double*)h->P.p, g, nts, h->mag_scale, h->p.top_db,
+                       h->p.n_std_thresh, h->p.ddof, (double*)h->pmax.p, thresh_out, gc, fps);
+    HIPCHK(h, hipGetLastError());
+    if (gc.T2 != nullptr) h->t2_ready = true;
+    h->stats_route = SG_STATS_TWO_LAUNCH;
+    return SG_OK;
+  }
   if (ub < 16) {
     // few units (the noise clip): STFT -> one pass over the power field -> final (3 launches instead of 5)
+    h->stats_route = SG_STATS_THREE_LAUNCH;
     {
       ProfScope ps(h, SG_STAGE_STFT_POWER, st);
       HIPCHK(h, stft_any<double>(h, v, g, ub, (double*)h->P.p, nullptr, nullptr, 1.0, st));
@@ -1567,9 +1646,9 @@ static int stage_stats(sg_handle* h, const View& v, const Geom& g, int64_t ub, d
       if ((rc = ensure_zeroed(h, h->alim, 256, st))) return rc;
       gc.T2 = (double*)h->T2.p; gc.alim_b = (unsigned*)h->alim.p + 2; gc.sum_abs_w = h->sum_abs_w;
     }
-    hipLaunchKernelGGL(k_colstats1_final, dim3((unsigned)((g.FS + 63) / 64), (unsigned)ub), dim3(64 * STAT_TG), 0, st,
+    hipLaunchKernelGGL((k_colstats1_final<STAT_TG, false>), dim3((unsigned)((g.FS + 63) / 64), (unsigned)ub), dim3(64 * STAT_TG), 0, st,
                        (const double*)h->part.p, (const double*)h->P.p, g, nts, h->mag_scale, h->p.top_db,
-                       h->p.n_std_thresh, h->p.ddof, (double*)h->pmax.p, thresh_out, gc);
+                       h->p.n_std_thresh, h->p.ddof, (double*)h->pmax.p, thresh_out, gc, 0);
     HIPCHK(h, hipGetLastError());
     if (gc.T2 != nullptr) h->t2_ready = true;
     return SG_OK;
@@ -3603,6 +3682,7 @@ extern "C" int sg_set_option(sg_handle* h, int32_t option, int64_t value) {
       h->tile_order = (int)value;
       return SG_OK;
     case SG_OPT_EXACT_MATERIALISED: h->exact_materialised = value != 0; return SG_OK;
+    case SG_OPT_STATS_THREE_LAUNCH: h->stats_three = value != 0; return SG_OK;
     case SG_OPT_FLOOR_TEST:
       if (value < 0 || value > 2) FAIL(h, SG_E_INVALID, "SG_OPT_FLOOR_TEST: 0 (predicted), 1 (a priori) or 2 (in the gate kernel)");
       h->floor_test = (int)value;
@@ -3628,6 +3708,7 @@ extern "C" int sg_get_option(const sg_handle* h, int32_t option, int64_t* value)
     case SG_OPT_INJECT_HANDOFF_FAULT: *value = h->inject_fault; return SG_OK;
     case SG_OPT_TILE_ORDER: *value = h->tile_order; return SG_OK;
     case SG_OPT_EXACT_MATERIALISED: *value = h->exact_materialised; return SG_OK;
+    case SG_OPT_STATS_THREE_LAUNCH: *value = h->stats_three; return SG_OK;
     case SG_OPT_FLOOR_TEST: *value = h->floor_test; return SG_OK;
   }
   return SG_E_INVALID;   // (no message: the handle is const here)
@@ -3719,6 +3800,10 @@ extern "C" int sg_debug_counter(sg_handle* h, int32_t which, int64_t* value, voi
     *value = h->spec_route;
     return SG_OK;
   }
+  if (which == 19) {   // SG_STATS_* form of the last noise statistics of fewer than 16 units (host bookkeeping)
+    *value = h->stats_route;
+    return SG_OK;
+  }
   if (which == 3) {   // launch epoch of the last gate call in which a chunk's floor test fired / flag was set (0: never)
     HIPCHK(h, hipStreamSynchronize((hipStream_t)stream));
     *value = h->err_host ? (int64_t)h->err_host[1] : 0;
@@ -3786,6 +3871,14 @@ extern "C" int sg_debug_counter(sg_handle* h, int32_t which, int64_t* value, voi
 
 extern "C" int sg_debug_fetch(sg_handle* h, int32_t what, void* host, int64_t bytes, void* stream) {
   if (!h) return SG_E_INVALID;
+  if (what == 5) {   // the gate's compare constants of the last noise statistics: T2 double[F], then the 64 words of the alim block
+    if (!host || !h->t2_ready) FAIL(h, SG_E_STATE, "sg_debug_fetch: no compare constants from noise statistics");
+    if ((size_t)bytes != (size_t)h->F * 8 + 256) FAIL(h, SG_E_INVALID, "sg_debug_fetch: need %zu bytes, got %lld", (size_t)h->F * 8 + 256, (long long)bytes);
+    HIPCHK(h, hipMemcpyAsync(host, h->T2.p, (size_t)h->F * 8, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(h, hipMemcpyAsync((char*)host + (size_t)h->F * 8, h->alim.p, 256, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(h, hipStreamSynchronize((hipStream_t)stream));
+    return SG_OK;
+  }
   if (!host || h->dbg_units == 0) FAIL(h, SG_E_STATE, "sg_debug_fetch: nothing processed yet");
   size_t cells = (size_t)h->dbg_units * h->dbg_T * h->FS;
   const void* src;

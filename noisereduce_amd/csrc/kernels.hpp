@@ -459,6 +459,150 @@ __global__ __launch_bounds__(64 * STAT_TG) void k_colstats1(const double* __rest
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// Transform and slice partials of the noise clip in ONE launch (k_stft<double> + k_colstats1): a k_colstats1 workgroup
+// reads only its own slice's frames, so the launch boundary between the two is no global dependency.  One workgroup of
+// TEAMS teams owns one slice of TEAMS - 1 consecutive frames: team j < TEAMS - 1 transforms frame ts (TEAMS - 1) + j
+// exactly as k_stft<double> does (same tables, same passes: P is bit-identical) and stores its row of P, which
+// k_colstats1_final's floor rescan reads; the LAST team transforms frame 0, whose dB is every band's pivot (k_colstats1
+// loads that cell from the field another launch wrote).  The pivot is db_fast's value here and cell_db's in the final
+// stage: a few 1e-14 dB apart, which moves the threshold by as much (the plain logarithm of 513 cells was the longest
+// wavefront of the workgroup).  Every team then leaves {P, dB} of its frame in
+// its own transform buffer and the workgroup reduces the slice per band to k_colstats1's five partials in a fixed
+// order: no atomics, two runs give the same bits.  The slice of a band is summed frame by frame, where k_colstats1
+// sums four interleaved runs: thresholds differ from the three-launch route by summation order only.
+// ---------------------------------------------------------------------------------------
+template <int N, int NT, int TEAMS>
+__global__ __launch_bounds__(TEAMS * NT) void k_noise_moments(View view, Geom g, const cx<double>* __restrict__ tw_g,
+                                                              const double* __restrict__ wfull,
+                                                              double* __restrict__ P_out, double mag_scale,
+                                                              double* __restrict__ part /* [u][nts][NP][FS] */,
+                                                              DbFast dbk, unsigned* __restrict__ alim_b, int n_alim) {
+  constexpr int SY = NT <= 64 ? 1 : NT;   // (as in k_stft)
+  constexpr int NTHR = TEAMS * NT;
+  constexpr int FPS = TEAMS - 1;          // frames per slice
+  constexpr int F = N + 1;                // bands (= g.F)
+  constexpr int LPD = 2 * lpn<double>(N); // doubles per transform buffer: holds P[0..F) and dB[F..2F) of its frame
+  static_assert(2 * F <= LPD, "the frame's {P, dB} pair must fit its transform buffer");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  __shared__ __attribute__((aligned(16))) double s_tab[256];
+  cx<double>* tw = reinterpret_cast<cx<double>*>(smem);
+  cx<double>* bufs = tw + N;
+  const int tid = (int)threadIdx.x;
+  const int lane = tid % NT;
+  const int team = tid / NT;
+  cx<double>* buf = bufs + team * lpn<double>(N);
+  for (int i = tid; i < 256; i += NTHR) s_tab[i] = dbk.tab[i];
+  // the floor test's bounds start at +Inf: the final stage's workgroups lower them (k_colstats1_final, BW < 64)
+  if (blockIdx.x == 0 && alim_b != nullptr && tid < n_alim) alim_b[tid] = 0x7f800000u;
+  stage_twiddles<NTHR, N>(tw, tw_g, tid);
+  const int64_t u = blockIdx.y;
+  const int64_t row = (view.unit0 + u) / view.n_chunks;
+  const int64_t chunk = view.c0 + (view.unit0 + u) % view.n_chunks;
+  const int ts = blockIdx.x, nts = gridDim.x;
+  const bool pivot_team = team == FPS;
+  const int64_t t = pivot_team ? 0 : (int64_t)ts * FPS + team;
+  const bool valid = t < g.T;
+  __syncthreads();
+  {
+    // gather window * frame as complex pairs (x[2j], x[2j+1]).  (Loading the frame and its window into registers BEFORE the
+    // tables are staged, to share one memory round trip, measured 21.8 against 17.8 us at n_fft = 1024.)
+    const int64_t s0 = t * g.H - g.padL;
+    const float* fp = valid ? frame_ptr_f32(view, row, chunk, s0, 2 * N) : nullptr;  // team-uniform
+    if (fp) {
+      for (int j = lane; j < N; j += NT)
+        buf[lp<double>(j)] = {(double)fp[2 * j] * wfull[2 * j], (double)fp[2 * j + 1] * wfull[2 * j + 1]};
+    } else {
+      for (int j = lane; j < N; j += NT) {
+        cx<double> z = {0.0, 0.0};
+        if (valid) {
+          z.x = (double)view_sample(view, row, chunk, s0 + 2 * j) * wfull[2 * j];
+          z.y = (double)view_sample(view, row, chunk, s0 + 2 * j + 1) * wfull[2 * j + 1];
+        }
+        buf[lp<double>(j)] = z;
+      }
+    }
+  }
+  team_sync<SY>();
+  wave_fft<double, N, false, NT, SY>(buf, tw, lane);
+  double Pk[N / NT + 1];
+#pragma unroll
+  for (int m = 0; m <= N / NT; ++m) {
+    const int k = lane + NT * m;
+    Pk[m] = 0.0;
+    if (k > N) continue;
+    cx<double> a = buf[lp<double>(k == N ? 0 : k)];
+    cx<double> b = buf[lp<double>((k == 0 || k == N) ? 0 : N - k)];
+    cx<double> w = tw[k == N ? 0 : k];
+    cx<double> X = rfft_bin(a, b, w, k, N);
+    Pk[m] = X.x * X.x + X.y * X.y;
+  }
+  team_sync<SY>();   // the team has read its transform: the buffer becomes the frame's {P, dB} rows
+  double* tile = reinterpret_cast<double*>(bufs);
+  {
+    double* mine = tile + team * LPD;
+    const int64_t rowoff = (u * g.T + t) * g.FS;
+#pragma unroll
+    for (int m = 0; m <= N / NT; ++m) {
+      const int k = lane + NT * m;
+      if (k > N) continue;
+      if (valid && !pivot_team) P_out[rowoff + k] = Pk[m];
+      mine[k] = Pk[m];
+      mine[F + k] = db_fast(Pk[m], s_tab, dbk, mag_scale);
+    }
+  }
+  __syncthreads();
+  // ---- the slice's partials per band; frames in order within a frame group, groups in order ----
+  const int64_t left = g.T - (int64_t)ts * FPS;
+  const int nfr = left < FPS ? (int)left : FPS;   // (>= 1: the grid is ceil(T / FPS))
+  constexpr int FR = (F + 63) / 64 * 64;
+  constexpr int G = FR <= NTHR ? (NTHR / FR < FPS ? NTHR / FR : FPS) : 1;   // frame groups that reduce side by side
+  const double* pivots = tile + FPS * LPD + F;
+  auto reduce_band = [&](int f, int j0, int jstep, double& mx, double& m1, double& m2, double& s1, double& s2) {
+    const double pivot = pivots[f];
+    for (int j = j0; j < nfr; j += jstep) {
+      const double p = tile[j * LPD + f], d = tile[j * LPD + F + f] - pivot;
+      mx = fmax(mx, p);
+      min2_push(m1, m2, p);
+      s1 += d;
+      s2 += d * d;
+    }
+  };
+  double* out = part + ((u * nts + ts) * STAT1_NP) * (int64_t)g.FS;
+  if constexpr (G == 1) {
+    for (int f = tid; f < F; f += NTHR) {
+      double mx = 0.0, m1 = 1e300, m2 = 1e300, s1 = 0.0, s2 = 0.0;
+      reduce_band(f, 0, 1, mx, m1, m2, s1, s2);
+      double* o = out + f;
+      o[0] = mx; o[g.FS] = m1; o[2 * g.FS] = m2; o[3 * g.FS] = s1; o[4 * g.FS] = s2;
+    }
+  } else {
+    const int grp = tid / FR, f = tid % FR;
+    const bool on = grp < G && f < F;
+    double mx = 0.0, m1 = 1e300, m2 = 1e300, s1 = 0.0, s2 = 0.0;
+    if (on) reduce_band(f, grp, G, mx, m1, m2, s1, s2);
+    __syncthreads();   // every tile read is done: the buffers take the groups' partials, [grp][5][FR]
+    static_assert((size_t)G * STAT1_NP * FR <= (size_t)TEAMS * LPD, "group partials must fit the transform buffers");
+    if (on && grp > 0) {
+      double* q = tile + (grp * STAT1_NP) * FR + f;
+      q[0] = mx; q[FR] = m1; q[2 * FR] = m2; q[3 * FR] = s1; q[4 * FR] = s2;
+    }
+    __syncthreads();
+    if (on && grp == 0) {
+      for (int i = 1; i < G; ++i) {
+        const double* q = tile + (i * STAT1_NP) * FR + f;
+        mx = fmax(mx, q[0]);
+        min2_push(m1, m2, q[FR]);
+        min2_push(m1, m2, q[2 * FR]);
+        s1 += q[3 * FR];
+        s2 += q[4 * FR];
+      }
+      double* o = out + f;
+      o[0] = mx; o[g.FS] = m1; o[2 * g.FS] = m2; o[3 * g.FS] = s1; o[4 * g.FS] = s2;
+    }
+  }
+}
+
 // one workgroup = 64 bands of one unit; the STAT_TG thread groups split the slices
 constexpr int STAT1_MAXS = 16;  // slices per thread group (nts <= STAT_TG * STAT1_MAXS).  (round 6: 32 -- 128 slices -- measured: k_colstats1
                                 // 13.7 -> 10.1 us at n_fft = 256, 8.4 -> 7.5 at 1024, but k_colstats1_final 11 - 13 -> 16.6 us everywhere: reverted)
@@ -471,51 +615,66 @@ struct GateConsts {
   unsigned* alim_b;     // [band blocks] bit patterns of the bounds
   double sum_abs_w;
 };
-__global__ __launch_bounds__(64 * STAT_TG) void k_colstats1_final(const double* __restrict__ part,
+// TG wavefronts on BW bands split the slices: a wavefront is 64 / BW slice groups of BW bands, a thread holds MAXS slices
+// (nts <= TG * (64 / BW) * MAXS).  FIXED: the slices of k_noise_moments -- slice ts is the fps frames from ts * fps on -- instead
+// of k_colstats1's nts even shares of T.  BW < 64 is for MANY slices: a workgroup pulls its partials through one compute
+// unit at some 40 GB/s (1.5 ns per 64-byte line, measured: 64 slices 8.8 us, 157 slices 17.2 us on nine 64-band workgroups), so
+// narrower workgroups spread them over more units; the 64-band block's floor-test bound is then the integer minimum of its
+// workgroups' bit patterns (the patterns of non-negative floats order like the floats), preset to +Inf by k_noise_moments.
+template <int TG, bool FIXED, int BW = 64, int MAXS = STAT1_MAXS>
+__global__ __launch_bounds__(64 * TG) void k_colstats1_final(const double* __restrict__ part,
                                                                   const double* __restrict__ P, Geom g, int nts,
                                                                   double mag_scale, double top_db, double n_std,
                                                                   int ddof, double* __restrict__ pmax,
-                                                                  double* __restrict__ thresh, GateConsts gc) {
-  __shared__ double r[3][STAT_TG][64];
+                                                                  double* __restrict__ thresh, GateConsts gc, int fps) {
+  constexpr int SUB = 64 / BW, TGX = TG * SUB;   // slice groups per wavefront / per workgroup
+  constexpr int UNR = TGX > 16 ? 8 : TGX;        // (64 groups unrolled whole spill at 128 registers)
+  __shared__ double r[3][TGX][BW];
   const int l = threadIdx.x & 63, tg = threadIdx.x >> 6;
-  const int f = blockIdx.x * 64 + l;
+  const int lb = l % BW, tgx = tg * SUB + l / BW;
+  const int f = blockIdx.x * BW + lb;
   const int64_t u = blockIdx.y;
   const int64_t i = u * g.FS + f;
   const bool live = f < g.F;
   const double Tn = (double)g.T;
   double mx = 0.0, s1 = 0.0, s2 = 0.0;
   const double p0 = live ? P[(u * g.T) * g.FS + f] : 1.0;   // pivot cell: loaded with the partials, one round trip
-  double m1[STAT1_MAXS];
+  double m1[MAXS];
   {
     // (round 6) every slice's four partials loaded UNCONDITIONALLY from a clamped address, selected afterwards: behind
     // `if (live && ts < nts)` the loads of one slice waited for the previous slice's -- sixteen dependent round trips
     const int fc = live ? f : g.F - 1;
-    double a0[STAT1_MAXS], a3[STAT1_MAXS], a4[STAT1_MAXS];
+    // (sixteen wavefronts per workgroup have 128 registers each: their loads go out in two batches of eight slices)
+    constexpr int LB = TG > 8 && MAXS > 8 ? MAXS / 2 : MAXS;
 #pragma unroll
-    for (int k = 0; k < STAT1_MAXS; ++k) {
-      const int ts = tg + STAT_TG * k;
-      const double* o = part + ((u * nts + (ts < nts ? ts : nts - 1)) * STAT1_NP) * (int64_t)g.FS + fc;
-      a0[k] = o[0];
-      m1[k] = o[g.FS];
-      a3[k] = o[3 * g.FS];
-      a4[k] = o[4 * g.FS];
-    }
+    for (int k0 = 0; k0 < MAXS; k0 += LB) {
+      double a0[LB], a3[LB], a4[LB];
 #pragma unroll
-    for (int k = 0; k < STAT1_MAXS; ++k) {
-      const bool on = live && tg + STAT_TG * k < nts;
-      if (on) {
-        mx = fmax(mx, a0[k]);
-        s1 += a3[k];
-        s2 += a4[k];
-      } else {
-        m1[k] = 1e300;
+      for (int k = 0; k < LB; ++k) {
+        const int ts = tgx + TGX * (k0 + k);
+        const double* o = part + ((u * nts + (ts < nts ? ts : nts - 1)) * STAT1_NP) * (int64_t)g.FS + fc;
+        a0[k] = o[0];
+        m1[k0 + k] = o[g.FS];
+        a3[k] = o[3 * g.FS];
+        a4[k] = o[4 * g.FS];
+      }
+#pragma unroll
+      for (int k = 0; k < LB; ++k) {
+        const bool on = live && tgx + TGX * (k0 + k) < nts;
+        if (on) {
+          mx = fmax(mx, a0[k]);
+          s1 += a3[k];
+          s2 += a4[k];
+        } else {
+          m1[k0 + k] = 1e300;
+        }
       }
     }
   }
-  r[0][tg][l] = mx;
+  r[0][tgx][lb] = mx;
   __syncthreads();
-#pragma unroll
-  for (int k = 0; k < STAT_TG; ++k) mx = fmax(mx, r[0][k][l]);
+#pragma unroll UNR
+  for (int k = 0; k < TGX; ++k) mx = fmax(mx, r[0][k][lb]);
   const double mdb = cell_db(mx, mag_scale);
   const double pivot = live ? cell_db(p0, mag_scale) : 0.0;
   {
@@ -533,14 +692,14 @@ __global__ __launch_bounds__(64 * STAT_TG) void k_colstats1_final(const double* 
     // kernel's duration)
     unsigned km = 0u;
 #pragma unroll
-    for (int k = 0; k < STAT1_MAXS; ++k) km |= (m1[k] < Pfl ? 1u : 0u) << k;
+    for (int k = 0; k < MAXS; ++k) km |= (m1[k] < Pfl ? 1u : 0u) << k;
     unsigned wor = km;
     for (int off = 32; off > 0; off >>= 1) wor |= (unsigned)__shfl_xor((int)wor, off);
     {
       while (wor) {                            // wave-uniform
         const int k = __ffs((int)wor) - 1;
         wor &= wor - 1u;
-        const int ts = tg + STAT_TG * k;     // (< nts: slices beyond it never set a bit)
+        const int ts = tgx + TGX * k;     // (< nts: slices beyond it never set a bit)
         bool both = false;
         if ((km >> k) & 1u) {
           const double* o = part + ((u * nts + ts) * STAT1_NP) * (int64_t)g.FS + f;
@@ -563,9 +722,11 @@ __global__ __launch_bounds__(64 * STAT_TG) void k_colstats1_final(const double* 
         while (todo) {
           const int src = __ffsll((long long)todo) - 1;
           todo &= todo - 1;
-          const int fb = blockIdx.x * 64 + src;
+          const int fb = blockIdx.x * BW + src % BW;
+          const int ts_s = SUB > 1 ? __shfl(ts, src) : ts;   // (the slice is the source lane's: wave-uniform only at BW = 64)
           const double Pfl_s = __shfl(Pfl, src), piv_s = __shfl(pivot, src), dfl_s = __shfl(dfl, src);
-          const int64_t tb = g.T * ts / nts, te = g.T * (ts + 1) / nts;
+          const int64_t tb = FIXED ? (int64_t)ts_s * fps : g.T * ts_s / nts;
+          const int64_t te = FIXED ? (tb + fps < g.T ? tb + fps : g.T) : g.T * (ts_s + 1) / nts;
           double c1 = 0.0, c2 = 0.0;
           for (int64_t t0 = tb + l; t0 < te; t0 += 64 * 4) {
             double pv[4];
@@ -597,16 +758,17 @@ __global__ __launch_bounds__(64 * STAT_TG) void k_colstats1_final(const double* 
     }
   }
   __syncthreads();
-  r[1][tg][l] = s1; r[2][tg][l] = s2;
+  r[1][tgx][lb] = s1; r[2][tgx][lb] = s2;
   __syncthreads();
   if (tg != 0) return;
   double thr_out = (double)NAN;
   s1 = 0.0; s2 = 0.0;
-#pragma unroll
-  for (int k = 0; k < STAT_TG; ++k) {  // fixed order: deterministic
-    s1 += r[1][k][l];
-    s2 += r[2][k][l];
+#pragma unroll UNR
+  for (int k = 0; k < TGX; ++k) {  // fixed order: deterministic
+    s1 += r[1][k][lb];
+    s2 += r[2][k][lb];
   }
+  if (SUB > 1 && l >= BW) return;   // (the wavefront's other slice groups hold copies of the same bands)
   if (live) {
     pmax[i] = mx;
     double var = (s2 - s1 * s1 / Tn) / (Tn - (double)ddof);
@@ -634,13 +796,14 @@ __global__ __launch_bounds__(64 * STAT_TG) void k_colstats1_final(const double* 
     gc.T2[f] = t2;
     mn = fmin(mn, thr_out);
   }
-  for (int off = 32; off > 0; off >>= 1) mn = fmin(mn, __shfl_xor(mn, off));
+  for (int off = BW / 2; off > 0; off >>= 1) mn = fmin(mn, __shfl_xor(mn, off));
   if (l == 0) {
     // need  <=>  20 log10(max|x| sum|w| mag_scale + eps) + 1e-6 - top_db > min thresh   <=>   max|x| > lim
     const double lim = (exp10((mn + top_db - 1e-6) / 20.0) - eps) / (gc.sum_abs_w * mag_scale);
     unsigned bits = 0u;                        // lim <= 0 or NaN: every tile reports (the floor path is exact for every unit)
     if (lim > 0.0) bits = __float_as_uint(__double2float_rd(lim * (1.0 - 1e-6)));   // +Inf: only non-finite samples report
-    gc.alim_b[blockIdx.x] = bits;
+    if constexpr (BW == 64) gc.alim_b[blockIdx.x] = bits;
+    else atomicMin(&gc.alim_b[blockIdx.x * BW / 64], bits);
   }
 }
 
