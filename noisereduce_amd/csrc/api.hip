@@ -1,17 +1,16 @@
-// libmi355gate.so -- host side of the C ABI declared in include/mi355gate.h.
-// Builds tables, owns the workspace, batches (channel, chunk) units and enqueues the
-// kernels of kernels.hpp on the caller's HIP stream.  gfx950 only.
+// libmi355gate.so -- the gate engine behind the C ABI of include/mi355gate.h: the FFT-size dispatchers, the workspace,
+// every stage and pipeline (statistics, decide, smooth, apply, the one-pass and row gates) and the entry points that run
+// them, enqueued on the caller's HIP stream.  gfx950 only.  The one unit that includes the gate's kernel headers.
+// The rest of the host side: create.hip (handle, tables, buffers), debug.hip (options, profiler, taps), shims.hip
+// (clips / rows / stream entry points); handle.hpp is what the four share.
 #include <hip/hip_runtime.h>
-#include <dlfcn.h>
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <map>
-#include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mi355gate_debug.h"
@@ -45,6 +44,8 @@
 #include "spec.hpp"
 #include "feat.hpp"
 #include "feat_tables.hpp"
+#include "handle.hpp"
+#include "launch.hpp"
 
 // complex transform length from which a whole 256-thread workgroup (instead of one wavefront) works on ONE frame in
 // the general LDS kernels: at N = 2048 (n_fft = 4096) a wavefront holds 4 radix-8 butterflies = 64 complex values per
@@ -134,132 +135,7 @@ constexpr int team_count(size_t elem) {
 #endif
 
 using namespace sg;
-
-namespace {
-thread_local std::string g_create_error;
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
-
-std::string fmt(const char* f, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, f);
-  vsnprintf(buf, sizeof buf, f, ap);
-  va_end(ap);
-  return buf;
-}
-}  // namespace
-
-struct RegGeom;
-struct sg_handle {
-  sg_params p{};
-  int n = 0, N = 0, W = 0, H = 0, F = 0, FS = 0, padL = 0;
-  double sum_w = 0.0;   // sum of the analysis window (scipy 'spectrum' scaling)
-  double mag_scale = 1; // |Z| = sqrt(P) * mag_scale  (S: 1/sum_w, T: 1)
-  // device tables
-  DevBuf tw64, tw32, wfull64, wa32, ws32, wsq32, kf, kt;
-  // per-band threshold (S stationary): double[FS]
-  DevBuf thresh;
-  bool has_thresh = false;
-  // workspace
-  DevBuf P, pmax, thr_rows, raw, M, seg, yn;
-  DevBuf bits, K16, umax, need, T2;  // fused stationary path
-  DevBuf nss;                        // non-stationary gate: recurrence partials of k_mag_fast's 16-frame blocks
-  DevBuf alim;                       // one-pass gate, in-kernel floor test: [1] tag of the last call that reported, [2..11) bounds on max|x| (k_colstats1_final / k_prep_thresh_lazy)
-  bool t2_ready = false;             // T2 / alim hold the compare constants of the CURRENT threshold (any writer of thresh clears it)
-  DevBuf logtab;                     // db_fast (kernels.hpp): {rd(1 / c_i), -log2 of it} for 128 mantissa centres
-  DevBuf part;                       // partial reductions of the column statistics
-  DevBuf tw512, invn;                // fast path tables (n_fft = 1024, hop = 256; 512 / 256 / 2048, hop = n_fft / 4): invn = 1 / window envelope per hop phase
-  DevBuf seam;                       // partial seam hops of abutting apply tiles
-  DevBuf ftab;                       // k_smooth_bits2 phase-1 lookup tables (nf <= 5)
-  int sm2_tt = 64;                   // k_smooth_bits2 tile height (frames)
-  bool t_sm2_ok = true;              // variant T: the smoothing filter's tile of k_smooth_bits2 fits the LDS (sg_process_batch's bit-mask route)
-  // one-pass gate (onepass.hpp): published mask bits per tile, publication flags, work counter, tables
-  DevBuf xbits, xpart, xticket, xtick2, ftab3, xexp, optab;
-  DevBuf xin;                        // float32 copy of a recording held in another sample dtype
-  DevBuf nsp, nsc;                   // non-stationary mask: per-sub-tile partials / carries (nonstat.hpp)  // ftab3: per-lane MFMA operands, xexp: bit -> byte table
-  unsigned* err_host = nullptr;      // host-mapped error word written by k_gate_onepass when a hand-off times out
-  unsigned* err_dev = nullptr;
-  unsigned inject_fault = 0;         // SG_OPT_INJECT_HANDOFF_FAULT (tests): error bits the next hand-off launch reports
-  unsigned lose_now = 0;             // bits 3..5 of the option, consumed by the next hand-off launch: the kernel itself treats
-                                     // the hand-off as lost (bounded-poll timeout path: error word + NaN-poisoned hops)
-  unsigned ticket_base = 0;          // tickets handed out by all previous launches
-  unsigned epoch = 0;                // launch counter: the value a tile's flag must carry to be current
-  bool fast_integer = false;         // SG_OPT_FAST_INTEGER: integer outputs from the float32 kernels (<= 1 LSB off)
-  bool force_exact = false;          // SG_OPT_FORCE_EXACT: float64 pipeline (exact.hpp) whatever the output dtype
-  bool exact_materialised = false;   // SG_OPT_EXACT_MATERIALISED: the float64 pipeline always through exact.hpp's materialised fields
-  DevBuf norm64;                     // sum_q win^2[256 q + s] as doubles (default geometry: k_apply_fast64's window envelope)
-  unsigned need_era = 0;             // epoch >> 30 of the last one-pass gate call (tagged floor-test flags, stage_onepass)
-  DevBuf xP, xraw, xM, xtmp, xseg;   // fields of the exact path
-  bool force_split = false;          // SG_OPT_FORCE_SPLIT: decide / smooth / apply as three kernels
-  int rowgate_mode = 0;              // SG_OPT_FORCE_NOROWGATE: 0 = by batch size, 1 = never, 2 = whenever the shape is eligible
-  int64_t n_floor_lazy = 0, n_floor_apriori = 0;   // sg_debug_counter 1 / 2
-  int64_t smooth_route = 0;   // sg_debug_counter 17: SG_SMOOTH_* of the last smoothing launch | cell bytes << 8 | tile frames << 16
-  DevBuf fb_d, fbT_d, fb_khull, fb_mhull;   // sg_set_filterbank: the bank [F][M], its transpose and the two hull tables (feat.hpp)
-  int n_filters = 0;                        // 0: no bank set
-  bool stats_three = false;   // SG_OPT_STATS_THREE_LAUNCH: the noise statistics always as k_stft<double> + k_colstats1 + k_colstats1_final
-  int64_t stats_route = 0;    // sg_debug_counter 19: SG_STATS_* form of the last stage_stats call of fewer than 16 units
-  int64_t spec_route = 0;     // sg_debug_counter 18: SG_SPEC_* decide branch of the last sg_gate_spectrum call | flags | sub-batches << 16
-  int tile_order = 0;                // SG_OPT_TILE_ORDER: 0 (default, round 6) = persistent workgroups looping over tickets (onepass.hpp PERSIST), 2 = one ticket-drawn tile per workgroup (the kernel of rounds 2-5), 1 = tile = block index
-                                     // block index (no ticket), 0 = persistent workgroups looping over tickets (round 6: 1 % faster alone on the
-                                     // GPU, NOT the default -- next to TorchGate's row gate on a second stream it mis-gates a tile now and then:
-                                     // tests/tools/soak_handoff.py)
-  int n_cu = 0;                      // compute units of the handle's device (persistent grids)
-  int floor_test = 0;                // SG_OPT_FLOOR_TEST: one-pass gate's floor test 0 = predicted, 1 = a priori, 2 = in the gate kernel
-  int rg_shape = 16;                 // SG_OPT_ROWGATE_SHAPE: waves per workgroup of the row gate (16 x 1 quad, or 8 x 2 quads)
-  bool rg_tap = false;               // SG_OPT_ROWGATE_TAP: keep the row gate's float32 power tile (stage tap 4)
-  bool dbg_rg = false;               // the last batch ran on the row gate
-  int dbg_bwd_route = 0;             // sg_debug_backward_route: SG_BWD_* of the last backward call (0: none yet)
-  DevBuf rg_count;                   // k_row_gate: number of (row, band) pairs that took the exact path (one counter, never reset)
-  bool dbg_xbits = false;            // the last batch's mask bits live in xbits (tile-blocked)
-  int dbg_trows = 16, dbg_tstep = 16, dbg_twords = 0, dbg_txw = 9;   // ... in tiles of trows frames every tstep frames, twords granule halves, txw words per row
-  int64_t dbg_tf0 = 0;               // first frame of tile 0 of that batch
-  int dbg_ntt = 0;                   // tiles per unit incl. the two halo tiles
-  int big_M = 0;                     // > 0: long frames (n_fft > 8192, or > 4096 and not a power of two): four-step
-                                     // transform of size M through HBM (big.hpp); big_czt: chirp-z on top of it
-  int big_czt = 0;
-  DevBuf big_twM, big_tw2, big_ch, big_bh, big_W, big_W2;
-  int czt_M = 0;                     // > 0: n_fft is not a power of two -> chirp-z kernels (czt.hpp) of size M
-  bool mr_ok = false;                // n_fft even, n_fft / 2 <= 2048 with prime factors <= 13, not a power of two: the float32 and
-  MrPlan mr{};                       // float64 STFT / decision / apply kernels of mixed.hpp (run-time radix schedule) instead of chirp-z
-  DevBuf mr_pt32, mr_pt64;           // the plan's per-pass twiddle tables (mr_pass_tables)
-  DevBuf regtab;                     // k_gate_onepass512 / 256 / 2048: MFMA operands + byte expansion (onepass512.hpp, onepass256.hpp, onepass2048.hpp)
-  DevBuf czt_tw64, czt_ch64, czt_bh64, czt_tw32, czt_ch32, czt_bh32;
-  bool force_noseam = false;
-  bool force_nolean = false;         // SG_OPT_FORCE_NOLEAN: full-size slices + stored frames (2 waves/SIMD)
-  bool fast_ok = false;              // default geometry: fused apply kernel available
-  const RegGeom* reg = nullptr;      // n_fft = win = 512 / 256 / 2048, hop = n_fft / 4: register-transform kernels (reg_geom)
-  bool force_nofast = false;
-  bool force_f64_decide = false;     // SG_OPT_FORCE_F64_DECIDE: float64 STFT for every mask decision
-  int64_t ktot = 1;                  // (nf+1)^2 (nt+1)^2: integer weight total of the smoothing filter
-  bool fused_ok = false;
-  double sum_abs_w = 0.0;
-  int64_t dbg_units = 0, dbg_T = 0;
-  bool dbg_has_P = false;
-  bool dbg_has_raw = true;           // the unsmoothed mask field exists (not when k_iir_mask / k_box_mask produced the mask in one kernel)
-  bool dbg_fused = false;
-  bool dbg_fast = false;
-  bool dbg_k16_only = false;         // the last fused general-geometry batch left K counts only (no float mask field): dbg_g
-  Geom dbg_g{};
-  int64_t dbg_db = 0, dbg_de = 0;  // frames whose mask bits were decided in the last batch
-  bool force_unfused = false;  // sg_set_option(SG_OPT_FORCE_UNFUSED): materialised v1 path
-  // per-kernel timing with HIP events on the launch stream (sg_profile_*)
-  bool roctx_on = false;       // SG_ROCTX=1: a roctx range around every stage's enqueue
-  bool prof_on = false;
-  uint64_t prof_mask = ~0ull;  // stages that get an event pair (sg_profile_select)
-  int prof_override = -1;  // >= 0: book every launch under this stage (noise statistics)
-  struct ProfRec { int stage; hipEvent_t a, b; };
-  std::vector<ProfRec> prof_live;
-  std::vector<hipEvent_t> prof_pool;
-  double prof_ms[SG_N_STAGES_ALL] = {0};
-  int64_t prof_cnt[SG_N_STAGES_ALL] = {0};
-  sg::RgState* rg = nullptr;        // ragged batches (sg_process_clips, ragged.hip): workspace and threshold tap
-  sg::RwState* rw = nullptr;        // padded batches of different-length rows (sg_process_rows, rows.hip): workspace
-  std::string err;
-};
+using namespace sg::host;
 
 // Register geometries: n_fft = win = 512 / 256 / 2048, hop = n_fft / 4 (fast512.hpp, fast256.hpp, fast2048.hpp and the
 // one-pass gates of onepass512.hpp, onepass256.hpp, onepass2048.hpp).  One descriptor per geometry holds its constants and
@@ -276,36 +152,12 @@ static HopRange hop_range(const OutMap& om, const Geom& g, int hop) {
 // abutting tiles of `frames` frames over nh hops: the last tile must reach 3 hops past the range (its leading partials)
 static int64_t abutting_tiles(int64_t nh, int frames) { return (nh + 3 + frames - 1) / frames; }
 
-// geometry constants of a one-pass gate: tiles of NF frames every NH frames
-struct OnePassGeom {
-  int hop, NF, NH, tile_words, xw, max_nf, max_nt, F;
-  size_t lds;      // dynamic LDS (n_fft = 1024: + OP_PROP_LDS when prop_decrease != 1)
-  int extra = 0;   // 3 when the tiles abut (NH == NF, abutting_tiles), 0 when they overlap by 3 frames
-  int64_t tiles(int64_t nh) const { return (nh + extra + NH - 1) / NH; }
-};
-
-struct RegGeom {
-  int n_fft, hop;
-  int frames;                 // frames per decide / magnitude tile and per abutting apply tile
-  int hops;                   // complete hops per overlapping apply tile (frames - 3)
-  size_t lds;                 // dynamic LDS of the decide / magnitude / apply kernels
-  DevBuf sg_handle::*tw;      // twiddle table (RegArgs::tw): tw512, or tw32 at n_fft = 2048
-  OnePassGeom op, op_seam;    // one-pass gate on overlapping tiles (SG_OPT_FORCE_NOSEAM) / abutting tiles + k_ola_seam
-  bool abut;                  // the one-pass gate needs abutting tiles (2048: op_seam only)
-  int tab_kb;                 // k-blocks of time weights in the gate's MFMA table (sg_create; 2048 lays its table out apart)
-  void (*decide[2])(fast::RegArgs);        // <4, false>, <4, true>: REDO (the units whose floor test fired)
-  void (*mag)(fast::RegArgs);
-  void (*apply[2])(fast::RegArgs);         // <4, false>: float mask, <4, true>: uint16 weight sums in K
-  void (*gate[2])(fast::OnePassRegArgs);   // <4, false>, <4, true>: REDO
-  void (*seam)(fast::SeamArgs);            // k_ola_seam<hop, frames>
-};
-
 constexpr size_t FAST5_LDS = (size_t)(fast::FN + 4 * fast::WAVE_CX_H) * sizeof(fast::cf) + (512 + 264) * sizeof(float);
 constexpr size_t FAST25_LDS = (size_t)(fast::FN + 4 * fast::WAVE_CX_H) * sizeof(fast::cf) + (256 + fast::F25_T2) * sizeof(float);
 constexpr size_t FAST20_LDS = (size_t)(1024 + 4 * fast::WAVE_CX_H) * sizeof(fast::cf) + 1028 * sizeof(float);
 
 // n_fft = 512: the 512-point complex transform of the default geometry carries two real frames
-static const RegGeom REG512{
+const RegGeom sg::host::REG512{
     512, 128, 32, 29, FAST5_LDS, &sg_handle::tw512,
     {128, fast::O5_NF, fast::O5_NH, fast::O5_TILE_WORDS, fast::O5_XW, fast::O5_MAX_NF, fast::O5_MAX_NT, 257, FAST5_LDS + 16 + 2048},
     {128, fast::O5_NF, fast::O5_NF, fast::O5_TILE_WORDS, fast::O5_XW, fast::O5_MAX_NF, fast::O5_MAX_NT, 257, FAST5_LDS + 16 + 2048, 3},
@@ -314,7 +166,7 @@ static const RegGeom REG512{
     {fast::k_apply_fast512<4, false>, fast::k_apply_fast512<4, true>},
     {fast::k_gate_onepass512<4, false>, fast::k_gate_onepass512<4, true>}, fast::k_ola_seam<128, 32>};
 // n_fft = 256 (round 5): the same transform carries four real frames
-static const RegGeom REG256{
+const RegGeom sg::host::REG256{
     256, 64, 64, 61, FAST25_LDS, &sg_handle::tw512,
     {64, fast::O25_NF, fast::O25_NH, fast::O25_TILE_WORDS, fast::O25_XW, fast::O25_MAX_NF, fast::O25_MAX_NT, 129, FAST25_LDS + 16 + 2048},
     {64, fast::O25_NF, fast::O25_NF, fast::O25_TILE_WORDS, fast::O25_XW, fast::O25_MAX_NF, fast::O25_MAX_NT, 129, FAST25_LDS + 16 + 2048, 3},
@@ -323,7 +175,7 @@ static const RegGeom REG256{
     {fast::k_apply_fast256<4, false>, fast::k_apply_fast256<4, true>},
     {fast::k_gate_onepass256<4, false>, fast::k_gate_onepass256<4, true>}, fast::k_ola_seam<64, 64>};
 // n_fft = 2048: one real frame per 32 lanes (1024-point transform); the one-pass gate's tiles always abut
-static const RegGeom REG2048{
+const RegGeom sg::host::REG2048{
     2048, 512, 8, 5, FAST20_LDS, &sg_handle::tw32,
     {512, fast::O20_NF, fast::O20_NF, fast::O20_TILE_WORDS, fast::O20_XW, fast::O20_MAX_NF, fast::O20_MAX_NT, 1025, FAST20_LDS + 16 + 2048, 3},
     {512, fast::O20_NF, fast::O20_NF, fast::O20_TILE_WORDS, fast::O20_XW, fast::O20_MAX_NF, fast::O20_MAX_NT, 1025, FAST20_LDS + 16 + 2048, 3},
@@ -346,179 +198,17 @@ static void note_smooth(sg_handle* h, int id, int cell_bytes, int tile_frames) {
   h->smooth_route = (int64_t)id | ((int64_t)cell_bytes << 8) | ((int64_t)tile_frames << 16);
 }
 
-namespace {
-// Optional roctx ranges around every stage's enqueue (SG_ROCTX=1 in the environment at sg_create): the stages show
-// up by name in `rocprofv3 --marker-trace` next to the kernel trace.  libroctx64 is looked up at run time: the library
-// does not depend on it.
-struct Roctx {
-  int (*push)(const char*) = nullptr;
-  int (*pop)() = nullptr;
-  Roctx() {
-    // rocprofv3 listens to the rocprofiler-sdk flavour; libroctx64 is the roctracer one (older tools)
-    void* lib = dlopen("librocprofiler-sdk-roctx.so", RTLD_NOW | RTLD_GLOBAL);
-    if (!lib) lib = dlopen("librocprofiler-sdk-roctx.so.1", RTLD_NOW | RTLD_GLOBAL);
-    if (!lib) lib = dlopen("libroctx64.so", RTLD_NOW | RTLD_GLOBAL);
-    if (!lib) lib = dlopen("libroctx64.so.4", RTLD_NOW | RTLD_GLOBAL);
-    if (!lib) return;
-    push = reinterpret_cast<int (*)(const char*)>(dlsym(lib, "roctxRangePushA"));
-    pop = reinterpret_cast<int (*)()>(dlsym(lib, "roctxRangePop"));
-    if (!push || !pop) push = nullptr, pop = nullptr;
-  }
-};
-const Roctx& roctx() {
-  static const Roctx r;
-  return r;
-}
-
-// RAII: records an event pair around one kernel launch when profiling is enabled.
-struct ProfScope {
-  sg_handle* h;
-  hipStream_t st;
-  int idx = -1;
-  static hipEvent_t get(sg_handle* h) {
-    if (!h->prof_pool.empty()) {
-      hipEvent_t e = h->prof_pool.back();
-      h->prof_pool.pop_back();
-      return e;
-    }
-    hipEvent_t e = nullptr;
-    (void)hipEventCreate(&e);
-    return e;
-  }
-  bool ranged = false;
-  ProfScope(sg_handle* h_, int stage, hipStream_t st_) : h(h_), st(st_) {
-    if (h->roctx_on && roctx().push) {
-      roctx().push(sg_stage_name(h->prof_override >= 0 ? h->prof_override : stage));
-      ranged = true;
-    }
-    if (!h->prof_on) return;
-    const int booked = h->prof_override >= 0 ? h->prof_override : stage;
-    if (!((h->prof_mask >> booked) & 1ull)) return;
-    sg_handle::ProfRec r{h->prof_override >= 0 ? h->prof_override : stage, get(h), get(h)};
-    (void)hipEventRecord(r.a, st);
-    h->prof_live.push_back(r);
-    idx = (int)h->prof_live.size() - 1;
-  }
-  ~ProfScope() {
-    if (idx >= 0) (void)hipEventRecord(h->prof_live[idx].b, st);
-    if (ranged) roctx().pop();
-  }
-};
-}  // namespace
-
-#define HIPCHK(h, call)                                                                      \
-  do {                                                                                       \
-    hipError_t e_ = (call);                                                                  \
-    if (e_ != hipSuccess) {                                                                  \
-      (h)->err = fmt("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-      (void)hipGetLastError(); /* reported here: not once more by the next launch check of any handle */ \
-      return SG_E_HIP;                                                                       \
-    }                                                                                        \
-  } while (0)
-
-#define FAIL(h, code, ...)      \
-  do {                          \
-    (h)->err = fmt(__VA_ARGS__); \
-    return (code);              \
-  } while (0)
-
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (device, kernel, size): the call costs microseconds of host
-// time, and a short call enqueues ten launches
-static hipError_t set_lds(const void* kern, size_t bytes) {
-  static std::mutex mu;
-  static std::map<std::pair<int, const void*>, size_t> done;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  std::lock_guard<std::mutex> lk(mu);
-  size_t& have = done[{dev, kern}];
-  if (have >= bytes) return hipSuccess;
-  hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e == hipSuccess) have = bytes;
-  return e;
-}
-
-// One kernel launch with `lds` bytes of dynamic LDS.  `raise`: the size may exceed the 64 KiB a kernel gets without asking
-// (set_lds first); a caller that knows its size is below passes false and saves the mutex and the map lookup.
-template <typename... KA, typename... A>
-static hipError_t launch_lds_if(bool raise, void (*kern)(KA...), dim3 grid, dim3 block, size_t lds, hipStream_t st, const A&... a) {
-  if (raise) {
-    hipError_t e = set_lds(reinterpret_cast<const void*>(kern), lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(kern, grid, block, lds, st, a...);
-  return hipGetLastError();
-}
-template <typename... KA, typename... A>
-static hipError_t launch_lds(void (*kern)(KA...), dim3 grid, dim3 block, size_t lds, hipStream_t st, const A&... a) {
-  return launch_lds_if(true, kern, grid, block, lds, st, a...);
-}
-
-static int ensure(sg_handle* h, DevBuf& b, size_t bytes) {
-  if (b.bytes >= bytes) return SG_OK;
-  if (b.p) {
-    HIPCHK(h, hipDeviceSynchronize());  // buffer may still be in use by enqueued work
-    HIPCHK(h, hipFree(b.p));
-    b.p = nullptr;
-    b.bytes = 0;
-  }
-  hipError_t e = hipMalloc(&b.p, bytes);
-  if (e != hipSuccess) {
-    b.p = nullptr;
-    FAIL(h, SG_E_NOMEM, "workspace allocation of %zu bytes failed: %s", bytes, hipGetErrorString(e));
-  }
-  b.bytes = bytes;
-  return SG_OK;
-}
-
-// ensure() + zero fill when the buffer was (re)allocated: for state that kernels keep clean themselves
-static int ensure_zeroed(sg_handle* h, DevBuf& b, size_t bytes, hipStream_t st, bool* fresh = nullptr) {
-  // freshness from the SIZE, not the pointer: the allocator may hand the freed address straight back
-  const bool grow = b.bytes < bytes;
-  int rc = ensure(h, b, bytes);
-  if (rc) return rc;
-  if (fresh) *fresh = grow;
-  if (grow) HIPCHK(h, hipMemsetAsync(b.p, 0, b.bytes, st));
-  return SG_OK;
-}
-
-static int upload(sg_handle* h, DevBuf& b, const void* src, size_t bytes) {
-  int rc = ensure(h, b, bytes);
-  if (rc) return rc;
-  HIPCHK(h, hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
-  return SG_OK;
-}
-
-static void free_buf(DevBuf& b) {
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.bytes = 0;
-}
-
-static int64_t frames_for(const sg_handle* h, int64_t L) {
-  // S: zero extension W//2 per side, padded=False (scipy/_spectral_py.py:2052,2185-2189).
-  // T: torch.stft(center=True) pads n_fft//2 per side: 1 + (L + 2 (n//2) - n) // hop
-  //    (= 1 + L // hop for even n_fft).
-  if (h->p.variant == SG_VARIANT_S) return (L + 2 * (int64_t)(h->W / 2) - h->W) / h->H + 1;
-  return 1 + (L + 2 * (int64_t)(h->n / 2) - h->n) / h->H;
-}
-static int64_t outlen_for(const sg_handle* h, int64_t L) {
-  int64_t T = frames_for(h, L);
-  if (h->p.variant == SG_VARIANT_S) return (T - 1) * h->H + h->W - 2 * (int64_t)(h->W / 2);
-  // torch.istft(center=True) trims n_fft//2 from both ends of the n_fft + (T-1) hop buffer
-  return (T - 1) * (int64_t)h->H + (h->n - 2 * (int64_t)(h->n / 2));
-}
-
-static Geom make_geom(const sg_handle* h, int64_t Lp) {
-  Geom g;
-  g.n = h->n; g.W = h->W; g.H = h->H; g.F = h->F; g.FS = h->FS; g.padL = h->padL;
-  g.T = frames_for(h, Lp);
-  g.Lout = outlen_for(h, Lp);
-  return g;
-}
-
 // ------------------------------------------------------------------------------------------
 // kernel dispatch on the FFT size
 // ------------------------------------------------------------------------------------------
+// f(std::integral_constant<int, N>{}) for the half transform length n = N, a power of two in [32, MAX]  (tile_core.hpp: dispatch_N)
+template <int MAX, int N = 32, class F>
+static hipError_t dispatch_pow2(int n, F&& f) {
+  if (n == N) return f(std::integral_constant<int, N>{});
+  if constexpr (N < MAX) return dispatch_pow2<MAX, 2 * N>(n, f);
+  else return hipErrorInvalidValue;
+}
+
 template <typename TC, int N>
 static hipError_t launch_stft_n(const View& v, const Geom& g, int64_t units, const void* tw, const void* wfull,
                                 double* P, float* mag, double* z, double zscale, hipStream_t st,
@@ -530,14 +220,9 @@ static hipError_t launch_stft_n(const View& v, const Geom& g, int64_t units, con
   // few units (the noise clip): one frame per wave so that the grid still covers the chip
   const bool small = units * ((g.T + WAVES * 4 - 1) / (WAVES * 4)) < 1024;
   auto launch = [&](auto kern, int fpw) -> hipError_t {
-    if (lds > 65536) {
-      hipError_t e = set_lds(reinterpret_cast<const void*>(kern), lds);
-      if (e != hipSuccess) return e;
-    }
     dim3 grid((unsigned)((g.T + WAVES * fpw - 1) / (WAVES * fpw)), (unsigned)units);
-    hipLaunchKernelGGL(kern, grid, dim3(WAVES * NT), lds, st, v, g, (const cx<TC>*)tw, (const TC*)wfull, P, mag,
-                       z, zscale, pmax_bits);
-    return hipGetLastError();
+    return launch_lds_if(lds > 65536, kern, grid, dim3(WAVES * NT), lds, st, v, g, (const cx<TC>*)tw, (const TC*)wfull, P, mag,
+                         z, zscale, pmax_bits);
   };
   if constexpr (sizeof(TC) == 8 && N >= 1024 && N < SG_TEAM_N && SG_STATS_TEAM) {
     // (round 5) the noise clip in float64 at n_fft = 2048: 293 workgroups of four one-frame wavefronts are one
@@ -545,14 +230,8 @@ static hipError_t launch_stft_n(const View& v, const Geom& g, int64_t units, con
     // workgroups, each transform split over 256 threads: 16.5 us.  (n_fft = 1024 measured too: 14.0 -> 15.9 us, so not there.)
     if (small && units * g.T <= 16384) {
       const size_t lds1 = (size_t)(N + lpn<TC>(N)) * sizeof(cx<TC>);
-      auto kern = k_stft<TC, N, 1, 1, 256>;
-      if (lds1 > 65536) {
-        hipError_t e = set_lds(reinterpret_cast<const void*>(kern), lds1);
-        if (e != hipSuccess) return e;
-      }
-      hipLaunchKernelGGL(kern, dim3((unsigned)g.T, (unsigned)units), dim3(256), lds1, st, v, g, (const cx<TC>*)tw,
-                         (const TC*)wfull, P, mag, z, zscale, pmax_bits);
-      return hipGetLastError();
+      return launch_lds_if(lds1 > 65536, k_stft<TC, N, 1, 1, 256>, dim3((unsigned)g.T, (unsigned)units), dim3(256), lds1, st, v, g,
+                           (const cx<TC>*)tw, (const TC*)wfull, P, mag, z, zscale, pmax_bits);
     }
   }
   if (small) return launch(k_stft<TC, N, WAVES, 1, NT>, 1);
@@ -563,17 +242,7 @@ template <typename TC>
 static hipError_t launch_stft(int N, const View& v, const Geom& g, int64_t units, const void* tw,
                               const void* wfull, double* P, float* mag, double* z, double zscale,
                               hipStream_t st, unsigned long long* pmax_bits = nullptr) {
-  switch (N) {
-    case 32: return launch_stft_n<TC, 32>(v, g, units, tw, wfull, P, mag, z, zscale, st, pmax_bits);
-    case 64: return launch_stft_n<TC, 64>(v, g, units, tw, wfull, P, mag, z, zscale, st, pmax_bits);
-    case 128: return launch_stft_n<TC, 128>(v, g, units, tw, wfull, P, mag, z, zscale, st, pmax_bits);
-    case 256: return launch_stft_n<TC, 256>(v, g, units, tw, wfull, P, mag, z, zscale, st, pmax_bits);
-    case 512: return launch_stft_n<TC, 512>(v, g, units, tw, wfull, P, mag, z, zscale, st, pmax_bits);
-    case 1024: return launch_stft_n<TC, 1024>(v, g, units, tw, wfull, P, mag, z, zscale, st, pmax_bits);
-    case 2048: return launch_stft_n<TC, 2048>(v, g, units, tw, wfull, P, mag, z, zscale, st, pmax_bits);
-    case 4096: return launch_stft_n<TC, 4096>(v, g, units, tw, wfull, P, mag, z, zscale, st, pmax_bits);
-  }
-  return hipErrorInvalidValue;
+  return dispatch_pow2<4096>(N, [&](auto n) { return launch_stft_n<TC, decltype(n)::value>(v, g, units, tw, wfull, P, mag, z, zscale, st, pmax_bits); });
 }
 
 template <int N, int MODE>
@@ -588,30 +257,16 @@ static hipError_t launch_bits_n(const View& v, const Geom& g, int64_t units, con
   constexpr int FPW = 4;
   size_t lds = (size_t)(N + WAVES * lpn<double>(N)) * sizeof(cx<double>) + (size_t)(N + 1) * sizeof(double);
   auto kern = k_stft_bits<N, WAVES, FPW, MODE, NT>;
-  if (lds > 65536) {
-    hipError_t e = set_lds(reinterpret_cast<const void*>(kern), lds);
-    if (e != hipSuccess) return e;
-  }
   dim3 grid((unsigned)((g.T + WAVES * FPW - 1) / (WAVES * FPW)), (unsigned)units);
-  hipLaunchKernelGGL(kern, grid, dim3(WAVES * NT), lds, st, v, g, (const cx<double>*)tw, (const double*)wfull, tc,
-                     mag_scale, top_db, pmax_bits, bits, wpr);
-  return hipGetLastError();
+  return launch_lds_if(lds > 65536, kern, grid, dim3(WAVES * NT), lds, st, v, g, (const cx<double>*)tw, (const double*)wfull, tc,
+                       mag_scale, top_db, pmax_bits, bits, wpr);
 }
 
 template <int MODE>
 static hipError_t launch_bits(int N, const View& v, const Geom& g, int64_t units, const void* tw,
                               const void* wfull, const ThreshConsts& tc, double mag_scale, double top_db,
                               unsigned long long* pmax_bits, unsigned long long* bits, int wpr, hipStream_t st) {
-  switch (N) {
-    case 32: return launch_bits_n<32, MODE>(v, g, units, tw, wfull, tc, mag_scale, top_db, pmax_bits, bits, wpr, st);
-    case 64: return launch_bits_n<64, MODE>(v, g, units, tw, wfull, tc, mag_scale, top_db, pmax_bits, bits, wpr, st);
-    case 128: return launch_bits_n<128, MODE>(v, g, units, tw, wfull, tc, mag_scale, top_db, pmax_bits, bits, wpr, st);
-    case 256: return launch_bits_n<256, MODE>(v, g, units, tw, wfull, tc, mag_scale, top_db, pmax_bits, bits, wpr, st);
-    case 512: return launch_bits_n<512, MODE>(v, g, units, tw, wfull, tc, mag_scale, top_db, pmax_bits, bits, wpr, st);
-    case 1024: return launch_bits_n<1024, MODE>(v, g, units, tw, wfull, tc, mag_scale, top_db, pmax_bits, bits, wpr, st);
-    case 2048: return launch_bits_n<2048, MODE>(v, g, units, tw, wfull, tc, mag_scale, top_db, pmax_bits, bits, wpr, st);
-  }
-  return hipErrorInvalidValue;
+  return dispatch_pow2<2048>(N, [&](auto n) { return launch_bits_n<decltype(n)::value, MODE>(v, g, units, tw, wfull, tc, mag_scale, top_db, pmax_bits, bits, wpr, st); });
 }
 
 template <int N>
@@ -622,15 +277,10 @@ static hipError_t launch_decide_lds_n(const sg_handle* h, const View& v, const G
   constexpr int FPW = 4;
   const size_t lds = (size_t)(N + WAVES * N) * sizeof(cx<float>) + (size_t)(N + 1) * sizeof(float);
   auto kern = k_decide_lds<N, WAVES, FPW, NT>;
-  if (lds > 65536) {
-    hipError_t e = set_lds(reinterpret_cast<const void*>(kern), lds);
-    if (e != hipSuccess) return e;
-  }
   dim3 grid((unsigned)((g.T + WAVES * FPW - 1) / (WAVES * FPW)), (unsigned)units);
-  hipLaunchKernelGGL(kern, grid, dim3(WAVES * NT), lds, st, v, g, (const cx<float>*)h->tw32.p,
-                     (const float*)h->wa32.p, (const cx<double>*)h->tw64.p, (const double*)h->wfull64.p, tc,
-                     h->mag_scale, h->p.top_db, bits, wpr);
-  return hipGetLastError();
+  return launch_lds_if(lds > 65536, kern, grid, dim3(WAVES * NT), lds, st, v, g, (const cx<float>*)h->tw32.p,
+                       (const float*)h->wa32.p, (const cx<double>*)h->tw64.p, (const double*)h->wfull64.p, tc,
+                       h->mag_scale, h->p.top_db, bits, wpr);
 }
 
 // (mixed-radix frame lengths, mixed.hpp: see the section below)
@@ -642,16 +292,7 @@ static hipError_t launch_decide_mr(const sg_handle* h, const View& v, const Geom
 static hipError_t launch_decide_lds(const sg_handle* h, const View& v, const Geom& g, int64_t units,
                                     const ThreshConsts& tc, unsigned long long* bits, int wpr, hipStream_t st) {
   if (h->mr_ok) return launch_decide_mr(h, v, g, units, tc, bits, wpr, st);
-  switch (h->N) {
-    case 32: return launch_decide_lds_n<32>(h, v, g, units, tc, bits, wpr, st);
-    case 64: return launch_decide_lds_n<64>(h, v, g, units, tc, bits, wpr, st);
-    case 128: return launch_decide_lds_n<128>(h, v, g, units, tc, bits, wpr, st);
-    case 256: return launch_decide_lds_n<256>(h, v, g, units, tc, bits, wpr, st);
-    case 512: return launch_decide_lds_n<512>(h, v, g, units, tc, bits, wpr, st);
-    case 1024: return launch_decide_lds_n<1024>(h, v, g, units, tc, bits, wpr, st);
-    case 2048: return launch_decide_lds_n<2048>(h, v, g, units, tc, bits, wpr, st);
-  }
-  return hipErrorInvalidValue;
+  return dispatch_pow2<2048>(h->N, [&](auto n) { return launch_decide_lds_n<decltype(n)::value>(h, v, g, units, tc, bits, wpr, st); });
 }
 
 template <int N>
@@ -663,29 +304,14 @@ static hipError_t launch_apply_n(const View& v, const Geom& g, int64_t units, co
   constexpr int FPW = 4;
   size_t lds = (size_t)(N + WAVES * lpn<float>(N)) * sizeof(cx<float>);
   auto kern = k_apply_istft<N, WAVES, FPW, NT>;
-  if (lds > 65536) {
-    hipError_t e = set_lds(reinterpret_cast<const void*>(kern), lds);
-    if (e != hipSuccess) return e;
-  }
   dim3 grid((unsigned)((g.T + WAVES * FPW - 1) / (WAVES * FPW)), (unsigned)units);
-  hipLaunchKernelGGL(kern, grid, dim3(WAVES * NT), lds, st, v, g, (const cx<float>*)tw, wa, ws, M, seg, K16, kscale);
-  return hipGetLastError();
+  return launch_lds_if(lds > 65536, kern, grid, dim3(WAVES * NT), lds, st, v, g, (const cx<float>*)tw, wa, ws, M, seg, K16, kscale);
 }
 
 static hipError_t launch_apply(int N, const View& v, const Geom& g, int64_t units, const void* tw,
                                const float* wa, const float* ws, const float* M, float* seg, hipStream_t st,
                                const unsigned short* K16 = nullptr, float kscale = 0.f) {
-  switch (N) {
-    case 32: return launch_apply_n<32>(v, g, units, tw, wa, ws, M, seg, st, K16, kscale);
-    case 64: return launch_apply_n<64>(v, g, units, tw, wa, ws, M, seg, st, K16, kscale);
-    case 128: return launch_apply_n<128>(v, g, units, tw, wa, ws, M, seg, st, K16, kscale);
-    case 256: return launch_apply_n<256>(v, g, units, tw, wa, ws, M, seg, st, K16, kscale);
-    case 512: return launch_apply_n<512>(v, g, units, tw, wa, ws, M, seg, st, K16, kscale);
-    case 1024: return launch_apply_n<1024>(v, g, units, tw, wa, ws, M, seg, st, K16, kscale);
-    case 2048: return launch_apply_n<2048>(v, g, units, tw, wa, ws, M, seg, st, K16, kscale);
-    case 4096: return launch_apply_n<4096>(v, g, units, tw, wa, ws, M, seg, st, K16, kscale);
-  }
-  return hipErrorInvalidValue;
+  return dispatch_pow2<4096>(N, [&](auto n) { return launch_apply_n<decltype(n)::value>(v, g, units, tw, wa, ws, M, seg, st, K16, kscale); });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -735,15 +361,10 @@ static hipError_t launch_stft_czt_m(const View& v, const Geom& g, int64_t units,
   constexpr int NT = CztShape<M>::NT, FR = CztShape<M>::FR;
   const size_t lds = (size_t)FR * lpn<TC>(M) * sizeof(cx<TC>);
   auto kern = k_stft_czt<TC, M, NT, FR>;
-  if (lds > 65536) {
-    hipError_t e = set_lds(reinterpret_cast<const void*>(kern), lds);
-    if (e != hipSuccess) return e;
-  }
   const int fpb = units * ((g.T + FR * 4 - 1) / (FR * 4)) < 1024 ? 1 : 4;
   dim3 grid((unsigned)((g.T + FR * fpb - 1) / (FR * fpb)), (unsigned)units);
-  hipLaunchKernelGGL(kern, grid, dim3(NT * FR), lds, st, v, g, tb, (const TC*)wfull, P, mag, z, zscale, pmax_bits,
-                     fpb);
-  return hipGetLastError();
+  return launch_lds_if(lds > 65536, kern, grid, dim3(NT * FR), lds, st, v, g, tb, (const TC*)wfull, P, mag, z, zscale, pmax_bits,
+                       fpb);
 }
 
 template <int M>
@@ -753,14 +374,9 @@ static hipError_t launch_apply_czt_m(const View& v, const Geom& g, int64_t units
   constexpr int NT = CztShape<M>::NT, FR = CztShape<M>::FR;
   const size_t lds = (size_t)FR * lpn<float>(M) * sizeof(cx<float>);
   auto kern = k_apply_istft_czt<M, NT, FR>;
-  if (lds > 65536) {
-    hipError_t e = set_lds(reinterpret_cast<const void*>(kern), lds);
-    if (e != hipSuccess) return e;
-  }
   const int fpb = 4;
   dim3 grid((unsigned)((g.T + FR * fpb - 1) / (FR * fpb)), (unsigned)units);
-  hipLaunchKernelGGL(kern, grid, dim3(NT * FR), lds, st, v, g, tb, wa, ws, Mk, seg, fpb);
-  return hipGetLastError();
+  return launch_lds_if(lds > 65536, kern, grid, dim3(NT * FR), lds, st, v, g, tb, wa, ws, Mk, seg, fpb);
 }
 
 #define SG_CZT_SWITCH(M_, CALL)            \
@@ -795,12 +411,7 @@ template <int M2>
 static hipError_t big_rows_m2(big::cd* W, const big::BigTabs& tb, int64_t nf, int mode, hipStream_t st) {
   const size_t lds = (size_t)lpn<double>(M2) * sizeof(big::cd);
   auto go = [&](auto kern) -> hipError_t {
-    if (lds > 65536) {
-      hipError_t e = set_lds(reinterpret_cast<const void*>(kern), lds);
-      if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(nf * 16)), dim3(256), lds, st, W, tb, nf);
-    return hipGetLastError();
+    return launch_lds_if(lds > 65536, kern, dim3((unsigned)(nf * 16)), dim3(256), lds, st, W, tb, nf);
   };
   if (mode == 0) return go(big::k_big_rows<M2, false, false>);
   if (mode == 1) return go(big::k_big_rows<M2, true, false>);
@@ -907,10 +518,7 @@ static hipError_t stft_any(const sg_handle* h, const View& v, const Geom& g, int
     const size_t lds = (size_t)(fast::FN + WAVES * 4 * fast::FSLOTS_D + 32) * sizeof(fast::cd);
     dim3 grid((unsigned)((g.T + WAVES * 4 - 1) / (WAVES * 4)), (unsigned)units);
     auto go = [&](auto kern) -> hipError_t {
-      hipError_t e = set_lds(reinterpret_cast<const void*>(kern), lds);
-      if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(kern, grid, dim3(WAVES * 64), lds, st, A);
-      return hipGetLastError();
+      return launch_lds(kern, grid, dim3(WAVES * 64), lds, st, A);
     };
     if (v.dtype == SG_F32 || v.dtype == SG_I16)
       return pmax_bits ? go(fast::k_power_fast64<WAVES, true>) : go(fast::k_power_fast64<WAVES, false>);
@@ -955,485 +563,6 @@ static DbFast db_fast_consts(const sg_handle* h) {
 static unsigned grid_1d(int64_t work, int block) {
   int64_t b = (work + block - 1) / block;
   return (unsigned)std::min<int64_t>(std::max<int64_t>(b, 1), 256 * 32);
-}
-
-// ------------------------------------------------------------------------------------------
-// create / destroy
-// ------------------------------------------------------------------------------------------
-extern "C" int sg_version(void) { return SG_VERSION; }
-
-extern "C" const char* sg_last_error(const sg_handle* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
-
-static std::vector<double> triangle(int m) {
-  // base.py:7-29 one axis: [1..m, m+1, m..1] / (m+1)
-  std::vector<double> v(2 * m + 1);
-  for (int i = 0; i <= 2 * m; ++i) v[i] = (double)(i <= m ? i + 1 : 2 * m + 1 - i) / (double)(m + 1);
-  return v;
-}
-
-// Tables of the chirp-z kernels (czt.hpp) for a frame length n that is not a power of two:
-// chirp conj(b[j]) = exp(-i pi j^2 / n) (j^2 reduced mod 2n in integers), B = FFT_M(b wrapped) / M
-// (host radix-2 transform in long double), master twiddles w_{2M}^k of the M-point device core.
-static int build_czt(sg_handle* h) {
-  typedef long double ld;
-  const ld PI = 3.14159265358979323846264338327950288L;
-  const int n = h->n;
-  int M = 64;
-  while (M < 2 * n - 1) M *= 2;
-  h->czt_M = M;
-  std::vector<ld> br(M, 0.0L), bi(M, 0.0L), cr(n), ci(n);
-  for (int j = 0; j < n; ++j) {
-    const int64_t q = ((int64_t)j * j) % (2 * (int64_t)n);
-    const ld a = PI * (ld)q / (ld)n;
-    cr[j] = cosl(a);
-    ci[j] = -sinl(a);
-    br[j] = cr[j];
-    bi[j] = -ci[j];
-    if (j) {
-      br[M - j] = br[j];
-      bi[M - j] = bi[j];
-    }
-  }
-  // in-place iterative radix-2 DIT
-  for (int i = 1, j = 0; i < M; ++i) {
-    int bit = M >> 1;
-    for (; j & bit; bit >>= 1) j ^= bit;
-    j ^= bit;
-    if (i < j) {
-      std::swap(br[i], br[j]);
-      std::swap(bi[i], bi[j]);
-    }
-  }
-  for (int len = 2; len <= M; len <<= 1) {
-    for (int k = 0; k < len / 2; ++k) {
-      const ld a = -2.0L * PI * (ld)k / (ld)len;
-      const ld wr = cosl(a), wi = sinl(a);
-      for (int i = k; i < M; i += len) {
-        const int j = i + len / 2;
-        const ld xr = br[j] * wr - bi[j] * wi, xi = br[j] * wi + bi[j] * wr;
-        br[j] = br[i] - xr;
-        bi[j] = bi[i] - xi;
-        br[i] += xr;
-        bi[i] += xi;
-      }
-    }
-  }
-  std::vector<cx<double>> tw64(M), ch64(n), bh64(M);
-  std::vector<cx<float>> tw32(M), ch32(n), bh32(M);
-  for (int k = 0; k < M; ++k) {
-    const ld a = -PI * (ld)k / (ld)M;
-    tw64[k] = {(double)cosl(a), (double)sinl(a)};
-    tw32[k] = {(float)cosl(a), (float)sinl(a)};
-    bh64[k] = {(double)(br[k] / (ld)M), (double)(bi[k] / (ld)M)};
-    bh32[k] = {(float)(br[k] / (ld)M), (float)(bi[k] / (ld)M)};
-  }
-  for (int j = 0; j < n; ++j) {
-    ch64[j] = {(double)cr[j], (double)ci[j]};
-    ch32[j] = {(float)cr[j], (float)ci[j]};
-  }
-  int rc = upload(h, h->czt_tw64, tw64.data(), tw64.size() * sizeof(cx<double>));
-  if (!rc) rc = upload(h, h->czt_ch64, ch64.data(), ch64.size() * sizeof(cx<double>));
-  if (!rc) rc = upload(h, h->czt_bh64, bh64.data(), bh64.size() * sizeof(cx<double>));
-  if (!rc) rc = upload(h, h->czt_tw32, tw32.data(), tw32.size() * sizeof(cx<float>));
-  if (!rc) rc = upload(h, h->czt_ch32, ch32.data(), ch32.size() * sizeof(cx<float>));
-  if (!rc) rc = upload(h, h->czt_bh32, bh32.data(), bh32.size() * sizeof(cx<float>));
-  return rc;
-}
-
-// Host radix-2 transform in long double (tables only)
-static void host_fft(std::vector<long double>& br, std::vector<long double>& bi) {
-  typedef long double ld;
-  const ld PI = 3.14159265358979323846264338327950288L;
-  const int M = (int)br.size();
-  for (int i = 1, j = 0; i < M; ++i) {
-    int bit = M >> 1;
-    for (; j & bit; bit >>= 1) j ^= bit;
-    j ^= bit;
-    if (i < j) {
-      std::swap(br[i], br[j]);
-      std::swap(bi[i], bi[j]);
-    }
-  }
-  for (int len = 2; len <= M; len <<= 1) {
-    for (int k = 0; k < len / 2; ++k) {
-      const ld a = -2.0L * PI * (ld)k / (ld)len;
-      const ld wr = cosl(a), wi = sinl(a);
-      for (int i = k; i < M; i += len) {
-        const int j = i + len / 2;
-        const ld xr = br[j] * wr - bi[j] * wi, xi = br[j] * wi + bi[j] * wr;
-        br[j] = br[i] - xr;
-        bi[j] = bi[i] - xi;
-        br[i] += xr;
-        bi[i] += xi;
-      }
-    }
-  }
-}
-
-// Tables of the long-frame kernels (big.hpp): w_M^j, the master twiddles of the M2-point row transform and, for a
-// frame length that is not a power of two, the chirp exp(-i pi j^2 / n) and B = FFT_M(b wrapped) / M in the PERMUTED
-// order pos(k) = (k & 15) * M2 + (k >> 4) the four-step transform leaves its output in.
-static int build_big(sg_handle* h, bool pow2) {
-  typedef long double ld;
-  const ld PI = 3.14159265358979323846264338327950288L;
-  const int n = h->n;
-  int M = n;
-  if (!pow2) {
-    M = 16384;
-    while (M < 2 * n - 1) M *= 2;
-  }
-  const int M2 = M / 16;
-  h->big_M = M;
-  h->big_czt = pow2 ? 0 : 1;
-  std::vector<cx<double>> twM(M), tw2(M2);
-  for (int j = 0; j < M; ++j) {
-    const ld a = -2.0L * PI * (ld)j / (ld)M;
-    twM[j] = {(double)cosl(a), (double)sinl(a)};
-  }
-  for (int k = 0; k < M2; ++k) {
-    const ld a = -PI * (ld)k / (ld)M2;
-    tw2[k] = {(double)cosl(a), (double)sinl(a)};
-  }
-  int rc = upload(h, h->big_twM, twM.data(), twM.size() * sizeof(cx<double>));
-  if (!rc) rc = upload(h, h->big_tw2, tw2.data(), tw2.size() * sizeof(cx<double>));
-  if (rc || pow2) return rc;
-  std::vector<ld> br(M, 0.0L), bi(M, 0.0L);
-  std::vector<cx<double>> ch(n), bh(M);
-  for (int j = 0; j < n; ++j) {
-    const int64_t q = ((int64_t)j * j) % (2 * (int64_t)n);
-    const ld a = PI * (ld)q / (ld)n;
-    ch[j] = {(double)cosl(a), (double)-sinl(a)};
-    br[j] = cosl(a);
-    bi[j] = sinl(a);
-    if (j) {
-      br[M - j] = br[j];
-      bi[M - j] = bi[j];
-    }
-  }
-  host_fft(br, bi);
-  for (int k = 0; k < M; ++k)
-    bh[(size_t)(k & 15) * M2 + (k >> 4)] = {(double)(br[k] / (ld)M), (double)(bi[k] / (ld)M)};
-  rc = upload(h, h->big_ch, ch.data(), ch.size() * sizeof(cx<double>));
-  if (!rc) rc = upload(h, h->big_bh, bh.data(), bh.size() * sizeof(cx<double>));
-  return rc;
-}
-
-extern "C" int sg_create(const sg_params* p, const double* window_host, sg_handle** out) {
-  if (!p || !out) {
-    g_create_error = "sg_create: null argument";
-    return SG_E_INVALID;
-  }
-  auto bad = [&](int code, const std::string& m) {
-    g_create_error = m;
-    return code;
-  };
-  int n = p->n_fft;
-  // powers of two 64..8192 run on the Stockham kernels; every other length 4..4096 on the chirp-z
-  // kernels (czt.hpp); longer frames -- powers of two up to 65536, any other length up to 32768 -- on the
-  // four-step transform through HBM (big.hpp)
-  const bool pow2 = n >= 64 && (n & (n - 1)) == 0;
-  const bool bigf = (pow2 && n > 8192) || (!pow2 && n > 4096);
-  if (n < 4 || (pow2 && n > 65536) || (!pow2 && n > 32768))
-    return bad(SG_E_UNSUPPORTED,
-               fmt("n_fft=%d unsupported: must be in [4, 32768], or a power of two up to 65536", n));
-  if (p->win_length < 2 || p->win_length > n)
-    return bad(SG_E_INVALID, fmt("win_length=%d must be in [2, n_fft=%d]", p->win_length, n));
-  if (p->hop_length < 1 || p->hop_length > p->win_length)
-    return bad(SG_E_INVALID, fmt("hop_length=%d must be in [1, win_length]", p->hop_length));
-  if (p->variant != SG_VARIANT_S && p->variant != SG_VARIANT_T) return bad(SG_E_INVALID, "bad variant");
-  if (p->smooth_mask && (p->n_grad_freq < 1 || p->n_grad_time < 1))
-    return bad(SG_E_INVALID, "n_grad_freq / n_grad_time must be >= 1");
-  if (p->variant == SG_VARIANT_S && (p->padding < 0 || p->chunk_size < 1))
-    return bad(SG_E_INVALID, "chunk_size must be >= 1 and padding >= 0");
-  if (!p->stationary && p->variant == SG_VARIANT_T && p->n_movemean < 1)
-    return bad(SG_E_INVALID, "n_movemean must be >= 1");
-
-  sg_handle* h = new sg_handle();
-  h->p = *p;
-  {
-    const char* e = getenv("SG_ROCTX");
-    h->roctx_on = e && e[0] == '1';
-  }
-  h->n = n;
-  h->N = n / 2;
-  h->W = p->win_length;
-  h->H = p->hop_length;
-  h->F = n / 2 + 1;
-  h->FS = (h->F + 15) / 16 * 16;
-  const int W = h->W;
-  std::vector<double> w(W);
-  if (window_host) {
-    for (int k = 0; k < W; ++k) w[k] = window_host[k];
-  } else {
-    for (int k = 0; k < W; ++k) w[k] = 0.5 - 0.5 * std::cos(2.0 * M_PI * (double)k / (double)W);
-  }
-  h->sum_w = 0.0;
-  for (int k = 0; k < W; ++k) h->sum_w += w[k];
-  for (int k = 0; k < W; ++k) h->sum_abs_w += std::fabs(w[k]);
-  {
-    int64_t a = p->smooth_mask ? (int64_t)(p->n_grad_freq + 1) * (p->n_grad_freq + 1) : 1;
-    int64_t b = p->smooth_mask ? (int64_t)(p->n_grad_time + 1) * (p->n_grad_time + 1) : 1;
-    h->ktot = a * b;
-    // fused (bit-mask) path: variant-S stationary gate whose integer smoothing sums fit uint16
-    // frame lengths 2 N, N a product of 2, 3, 5, 7, 11, 13: the mixed-radix kernels (mixed.hpp) -- and with them the fused
-    // (bit-mask) path -- instead of chirp-z
-    h->mr_ok = !pow2 && !bigf && n % 2 == 0 && n >= 8 && mr_make_plan(n / 2, &h->mr) && getenv("SG_NO_MIXED_RADIX") == nullptr;
-    h->fused_ok = p->variant == SG_VARIANT_S && p->stationary && h->ktot <= 65535 && (pow2 || h->mr_ok) && n <= 4096 &&
-                  (!p->smooth_mask || p->n_grad_time <= 96);
-    // the integer smoothing kernel holds (tt + 2 nt) rows of all F bins in LDS: 64-frame tiles, lower ones for long rows
-    // and wide time smoothing; returns the bytes of the tile it settled on
-    auto fit_sm2_tile = [&](int tt_max) {
-      const int wpr = (h->F + 63) / 64;
-      const bool small = (p->n_grad_freq + 1) * (p->n_grad_freq + 1) <= 255;
-      size_t lds = 0;
-      for (h->sm2_tt = tt_max; h->sm2_tt >= 16; h->sm2_tt >>= 1) {
-        const int rows = h->sm2_tt + 2 * p->n_grad_time;
-        lds = smooth2_cf_bytes(rows + 2, h->F, small ? 1 : 2) + (size_t)rows * (wpr + 2) * 8 + 8192;
-        if (lds <= 150 * 1024) break;
-      }
-      return lds;
-    };
-    if (h->fused_ok && p->smooth_mask) {
-      if (fit_sm2_tile(smooth2_tt_max(h->F)) > 150 * 1024 || p->n_grad_freq > 30) h->fused_ok = false;
-    }
-    // variant T's bit-mask route (sg_process_batch) smooths with the same kernel and used to launch it with 64-frame tiles
-    // whatever the filter: from n_grad_time = 82 on (n_fft = 1024) the tile exceeds the LDS and the call failed.  The same
-    // search, from the 64 frames it always ran with; a filter no tile fits keeps the float smoothing kernels.
-    if (p->variant == SG_VARIANT_T && p->stationary && p->smooth_mask && p->n_grad_freq <= 30 && h->ktot <= 65535 &&
-        p->n_grad_time <= 96)
-      h->t_sm2_ok = fit_sm2_tile(SM2_TT) <= 150 * 1024;
-  }
-  // window embedded in an n_fft frame: scipy zero-pads the windowed frame at the END
-  // (scipy/_spectral_py.py:2202) and extends the signal by W//2; torch centres the window
-  // inside n_fft and pads the signal by n_fft//2.
-  std::vector<double> wfull(n, 0.0);
-  int left = (p->variant == SG_VARIANT_S) ? 0 : (n - W) / 2;
-  for (int k = 0; k < W; ++k) wfull[left + k] = w[k];
-  h->padL = (p->variant == SG_VARIANT_S) ? W / 2 : n / 2;
-  h->mag_scale = (p->variant == SG_VARIANT_S) ? 1.0 / h->sum_w : 1.0;
-
-  std::vector<cx<double>> tw64(h->N);
-  std::vector<cx<float>> tw32(h->N);
-  for (int k = 0; k < h->N; ++k) {
-    long double a = -2.0L * 3.14159265358979323846264338327950288L * (long double)k / (long double)n;
-    tw64[k] = {(double)cosl(a), (double)sinl(a)};
-    tw32[k] = {(float)cosl(a), (float)sinl(a)};
-  }
-  std::vector<float> wa32(n), ws32(n), wsq32(n);
-  for (int k = 0; k < n; ++k) {
-    wa32[k] = (float)wfull[k];
-    // synthesis window incl. the inverse-transform normalisation: the half-size complex core leaves
-    // a factor n/2, the chirp-z inverse a factor n
-    ws32[k] = (float)(wfull[k] / ((pow2 || h->mr_ok) ? (double)h->N : (double)n));
-    wsq32[k] = (float)(wfull[k] * wfull[k]);
-  }
-  int rc = SG_OK;
-  if (!rc) rc = upload(h, h->tw64, tw64.data(), tw64.size() * sizeof(cx<double>));
-  if (!rc && h->mr_ok) {
-    std::vector<double> pt((size_t)std::max(1, h->mr.ptotal) * 2, 0.0);
-    mr_pass_tables(h->mr, pt.data());
-    std::vector<float> pt32(pt.begin(), pt.end());
-    rc = upload(h, h->mr_pt64, pt.data(), pt.size() * sizeof(double));
-    if (!rc) rc = upload(h, h->mr_pt32, pt32.data(), pt32.size() * sizeof(float));
-  }
-  {
-    // db_fast: centre c_i = 1 + (i + 1/2) / 128 of the i-th mantissa slice; the logarithm is that of the ROUNDED
-    // reciprocal, so that log2(m) = -log2(t_i) + log2(1 + (m t_i - 1)) holds exactly
-    std::vector<double> lt(256);
-    for (int i = 0; i < 128; ++i) {
-      const double ti = (double)(1.0L / (1.0L + ((long double)i + 0.5L) / 128.0L));
-      lt[2 * i] = ti;
-      lt[2 * i + 1] = (double)(-log2l((long double)ti));
-    }
-    if (!rc) rc = upload(h, h->logtab, lt.data(), lt.size() * sizeof(double));
-  }
-  if (!rc) rc = upload(h, h->tw32, tw32.data(), tw32.size() * sizeof(cx<float>));
-  if (!rc) rc = upload(h, h->wfull64, wfull.data(), wfull.size() * sizeof(double));
-  if (!rc) rc = upload(h, h->wa32, wa32.data(), wa32.size() * sizeof(float));
-  if (!rc) rc = upload(h, h->ws32, ws32.data(), ws32.size() * sizeof(float));
-  if (!rc) rc = upload(h, h->wsq32, wsq32.data(), wsq32.size() * sizeof(float));
-  if (!rc && bigf) rc = build_big(h, pow2);
-  else if (!rc && !pow2) rc = build_czt(h);
-  if (!rc && p->smooth_mask) {
-    auto vf = triangle(p->n_grad_freq), vt = triangle(p->n_grad_time);
-    double sf = 0, stt = 0;
-    for (double x : vf) sf += x;
-    for (double x : vt) stt += x;
-    std::vector<float> kf(vf.size()), kt(vt.size());
-    for (size_t i = 0; i < vf.size(); ++i) kf[i] = (float)(vf[i] / sf);
-    for (size_t i = 0; i < vt.size(); ++i) kt[i] = (float)(vt[i] / stt);
-    if (!rc) rc = upload(h, h->kf, kf.data(), kf.size() * sizeof(float));
-    if (!rc) rc = upload(h, h->kt, kt.data(), kt.size() * sizeof(float));
-  }
-  // 1 / window envelope per hop phase of the geometries with hop = n_fft / 4 (sum over the 4 frames that overlap a hop)
-  auto upload_invn = [&](int hop) {
-    std::vector<float> invn(hop);
-    for (int s2 = 0; s2 < hop; ++s2) {
-      double acc = 0.0;
-      for (int q = 0; q < 4; ++q) acc += wfull[hop * q + s2] * wfull[hop * q + s2];
-      invn[s2] = (float)(acc > 1e-10 ? 1.0 / acc : 1.0);
-    }
-    return upload(h, h->invn, invn.data(), invn.size() * sizeof(float));
-  };
-  // w_512^j: the 512-point register transform of n_fft = 1024 / 512 / 256 (fastpath.hpp)
-  auto upload_tw512 = [&]() {
-    std::vector<cx<float>> t512(512);
-    for (int j = 0; j < 512; ++j) {
-      long double a = -2.0L * 3.14159265358979323846264338327950288L * (long double)j / 512.0L;
-      t512[j] = {(float)cosl(a), (float)sinl(a)};
-    }
-    return upload(h, h->tw512, t512.data(), t512.size() * sizeof(cx<float>));
-  };
-  if (!rc && n == 1024 && W == 1024 && h->H == 256) {
-    std::vector<double> norm64(256);
-    for (int s2 = 0; s2 < 256; ++s2) {
-      double acc = 0.0;
-      for (int q = 0; q < 4; ++q) acc += wfull[256 * q + s2] * wfull[256 * q + s2];   // frames t-3 .. t in scipy's order
-      norm64[s2] = acc;
-    }
-    rc = upload_tw512();
-    if (!rc) rc = upload_invn(256);
-    if (!rc) rc = upload(h, h->norm64, norm64.data(), norm64.size() * sizeof(double));
-    h->fast_ok = true;
-  }
-  for (const RegGeom* r : {&REG512, &REG256, &REG2048})
-    if (!rc && n == r->n_fft && W == r->n_fft && h->H == r->hop) {
-      if (r->tw == &sg_handle::tw512) rc = upload_tw512();   // (2048 reads tw32)
-      if (!rc) rc = upload_invn(r->hop);
-      h->reg = r;
-    }
-  if (!rc && p->smooth_mask && 8 + 2 * p->n_grad_freq <= 18) {
-    // counts of 8 adjacent bins f..f+7 from the 18-bit window b[f-nf .. f-nf+17]: two 9-bit tables
-    const int nf = p->n_grad_freq;
-    std::vector<unsigned long long> tab(1024, 0ull);
-    for (int half = 0; half < 2; ++half)
-      for (int v = 0; v < 512; ++v) {
-        unsigned long long packed = 0;
-        for (int e = 0; e < 8; ++e) {
-          int cnt = 0;
-          for (int b = 0; b < 9; ++b)
-            if ((v >> b) & 1) {
-              int a = (half * 9 + b) - nf - e;  // tap offset of window bit relative to bin f+e
-              if (a >= -nf && a <= nf) cnt += nf + 1 - (a < 0 ? -a : a);
-            }
-          packed |= (unsigned long long)cnt << (8 * e);
-        }
-        tab[half * 512 + v] = packed;
-      }
-    rc = upload(h, h->ftab, tab.data(), tab.size() * sizeof(unsigned long long));
-  }
-  if (!rc && h->fast_ok && p->smooth_mask && p->n_grad_freq <= 8 && p->n_grad_time <= fast::OP_MAX_NT) {
-    // per-lane operands of the one-pass kernel's MFMA smoothing (onepass.hpp), v_mfma_i32_16x16x32_i8 layout:
-    // lane l = (q = l / 16, j = l % 16) supplies bytes e = 0..7 = k slots 8 q + e of row/column j
-    const int nf = p->n_grad_freq, nt = p->n_grad_time;
-    std::vector<unsigned long long> mc(192, 0ull), ex(256, 0ull);
-    auto wt = [&](int r, int i) {  // time weight of tile row r (frame r - nt) for output frame i
-      const int d = r - i - nt, ad = d < 0 ? -d : d;
-      return ad <= nt ? nt + 1 - ad : 0;
-    };
-    auto trow = [&](int m) { return m < nt ? m : 16 + m; };  // neighbour-list index -> tile row
-    for (int l = 0; l < 64; ++l) {
-      const int q = l / 16, j = l % 16;
-      for (int e = 0; e < 8; ++e) {
-        const int a = 8 * q + e - 8 - j, aa = a < 0 ? -a : a;
-        mc[l] |= (unsigned long long)(aa <= nf ? nf + 1 - aa : 0) << (8 * e);
-        int w1;
-        if (e < 4) w1 = wt(nt + 4 * q + e, j);
-        else { const int m = 4 * q + e - 4; w1 = m < 2 * nt ? wt(trow(m), j) : 0; }
-        mc[64 + l] |= (unsigned long long)w1 << (8 * e);
-        if (e < 4) { const int m = 16 + 4 * q + e; mc[128 + l] |= (unsigned long long)(m < 2 * nt ? wt(trow(m), j) : 0) << (8 * e); }
-      }
-    }
-    for (int v = 0; v < 256; ++v)
-      for (int e = 0; e < 8; ++e) ex[v] |= (unsigned long long)((v >> e) & 1) << (8 * e);
-    rc = upload(h, h->ftab3, mc.data(), mc.size() * 8);
-    if (!rc) rc = upload(h, h->xexp, ex.data(), ex.size() * 8);
-    // the one-pass kernel reads all of its constant tables through ONE base pointer (onepass.hpp: OP_TAB_*)
-    if (!rc) rc = ensure(h, h->optab, fast::OP_TAB_BYTES);
-    if (!rc) {
-      struct { const DevBuf* b; int off; size_t bytes; } parts[] = {
-          {&h->wa32, fast::OP_TAB_WIN, 4096}, {&h->wsq32, fast::OP_TAB_WSQ, 4096}, {&h->invn, fast::OP_TAB_INVN, 1024},
-          {&h->tw512, fast::OP_TAB_TW512, 4096}, {&h->tw32, fast::OP_TAB_TW1024, 4096}, {&h->wfull64, fast::OP_TAB_WIN64, 8192},
-          {&h->tw64, fast::OP_TAB_TW64, 8192}, {&h->ftab3, fast::OP_TAB_MCONST, 1536}, {&h->xexp, fast::OP_TAB_EXP8, 2048}};
-      for (const auto& pt : parts) {
-        if (!pt.b->p || pt.b->bytes < pt.bytes) { h->err = "one-pass table arena: a source table is missing"; rc = SG_E_STATE; break; }
-        if (hipMemcpy((char*)h->optab.p + pt.off, pt.b->p, pt.bytes, hipMemcpyDeviceToDevice) != hipSuccess) {
-          h->err = "one-pass table arena: hipMemcpy failed"; rc = SG_E_HIP; break;
-        }
-      }
-    }
-  }
-  const RegGeom* rg = h->reg;
-  if (!rc && rg && p->smooth_mask && p->n_grad_freq <= rg->op.max_nf && p->n_grad_time <= rg->op.max_nt) {
-    // operands of the one-pass gate's MFMA smoothing (onepass512.hpp, onepass256.hpp, onepass2048.hpp), v_mfma_i32_16x16x32_i8
-    // layout: lane l = (q = l / 16, j = l % 16) supplies bytes e = 0..7 = k slots 8 q + e of row / column j
-    const int nf = p->n_grad_freq, nt = p->n_grad_time;
-    auto wt = [&](int d) { const int ad = d < 0 ? -d : d; return ad <= nt ? nt + 1 - ad : 0; };
-    auto wf = [&](int d) { const int ad = d < 0 ? -d : d; return ad <= nf ? nf + 1 - ad : 0; };
-    const bool two = rg == &REG2048;
-    const int ex = 64 * (two ? 3 : 1 + rg->tab_kb);   // the byte expansion follows the operands
-    std::vector<unsigned long long> tb(ex + 256, 0ull);
-    for (int l = 0; l < 64; ++l) {
-      const int q = l / 16, j = l % 16;
-      for (int e = 0; e < 8; ++e) {
-        const int k = 8 * q + e;
-        // k slot 8 q + e: row 4 q + e of the first block (e < 4) / 16 + 4 q + (e - 4) of the second; output frame j at row nt + j
-        const int r1 = e < 4 ? 4 * q + e : 16 + 4 * q + (e - 4);
-        if (two) {
-          // 2048: TWO band matrices (bins 16 b - 24 + k and 16 b + 8 + k against output bin 16 b + j), one k-block of time weights
-          tb[l] |= (unsigned long long)wf(k - 24 - j) << (8 * e);
-          tb[64 + l] |= (unsigned long long)wf(k + 8 - j) << (8 * e);
-          tb[128 + l] |= (unsigned long long)wt(r1 - nt - j) << (8 * e);
-        } else {
-          // 512 / 256: one band matrix, tab_kb k-blocks of time weights
-          tb[l] |= (unsigned long long)wf(k - 8 - j) << (8 * e);
-          for (int b = 0; b < rg->tab_kb; ++b) tb[64 * (1 + b) + l] |= (unsigned long long)wt(32 * b + r1 - nt - j) << (8 * e);
-        }
-      }
-    }
-    for (int v = 0; v < 256; ++v)
-      for (int e = 0; e < 8; ++e) tb[ex + v] |= (unsigned long long)((v >> e) & 1) << (8 * e);
-    rc = upload(h, h->regtab, tb.data(), tb.size() * 8);
-  }
-  if (!rc) rc = ensure(h, h->thresh, (size_t)h->FS * sizeof(double));
-  if (rc) {
-    g_create_error = h->err;
-    sg_destroy(h);
-    return rc;
-  }
-  *out = h;
-  return SG_OK;
-}
-
-extern "C" int sg_destroy(sg_handle* h) {
-  if (!h) return SG_OK;
-  (void)hipDeviceSynchronize();
-  for (auto& r : h->prof_live) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-  for (auto e : h->prof_pool) (void)hipEventDestroy(e);
-  if (h->err_host) (void)hipHostFree(h->err_host);
-  for (DevBuf* b : {&h->tw64, &h->tw32, &h->wfull64, &h->wa32, &h->ws32, &h->wsq32, &h->kf, &h->kt, &h->thresh,
-                    &h->P, &h->pmax, &h->thr_rows, &h->raw, &h->M, &h->seg, &h->yn, &h->bits, &h->K16, &h->umax,
-                    &h->need, &h->T2, &h->part, &h->tw512, &h->invn, &h->seam, &h->ftab, &h->xbits, &h->xpart,
-                    &h->xticket, &h->xtick2, &h->ftab3, &h->xexp, &h->optab, &h->nsp, &h->nsc, &h->xin, &h->czt_tw64, &h->czt_ch64,
-                    &h->czt_bh64, &h->czt_tw32, &h->czt_ch32, &h->czt_bh32, &h->logtab, &h->big_twM, &h->big_tw2,
-                    &h->big_ch, &h->big_bh, &h->big_W, &h->big_W2, &h->xP, &h->xraw, &h->xM, &h->xtmp, &h->xseg, &h->rg_count, &h->alim, &h->nss, &h->mr_pt32, &h->mr_pt64, &h->regtab,
-                    &h->fb_d, &h->fbT_d, &h->fb_khull, &h->fb_mhull})
-    free_buf(*b);
-  sg::rg_free(h->rg);
-  sg::rw_free(h->rw);
-  delete h;
-  return SG_OK;
-}
-
-extern "C" int sg_n_frames(const sg_handle* h, int64_t L, int64_t* n_frames) {
-  if (!h || !n_frames) return SG_E_INVALID;
-  *n_frames = frames_for(h, L);
-  return SG_OK;
-}
-extern "C" int sg_output_length(const sg_handle* h, int64_t L, int64_t* out_len) {
-  if (!h || !out_len) return SG_E_INVALID;
-  *out_len = outlen_for(h, L);
-  return SG_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1570,12 +699,9 @@ static hipError_t launch_noise_moments_n(const sg_handle* h, const View& v, cons
   constexpr int NT = nm_team_threads<N>(), TEAMS = 1024 / NT;
   const size_t lds = (size_t)(N + TEAMS * lpn<double>(N)) * sizeof(cx<double>);
   auto kern = k_noise_moments<N, NT, TEAMS>;
-  hipError_t e = set_lds(reinterpret_cast<const void*>(kern), lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3((unsigned)nts, 1), dim3(TEAMS * NT), lds, st, v, g, (const cx<double>*)h->tw64.p,
-                     (const double*)h->wfull64.p, (double*)h->P.p, h->mag_scale, (double*)h->part.p, db_fast_consts(h),
-                     alim_b, n_alim);
-  return hipGetLastError();
+  return launch_lds(kern, dim3((unsigned)nts, 1), dim3(TEAMS * NT), lds, st, v, g, (const cx<double>*)h->tw64.p,
+                    (const double*)h->wfull64.p, (double*)h->P.p, h->mag_scale, (double*)h->part.p, db_fast_consts(h),
+                    alim_b, n_alim);
 }
 static hipError_t launch_noise_moments(const sg_handle* h, const View& v, const Geom& g, int nts, hipStream_t st,
                                        unsigned* alim_b, int n_alim) {
@@ -1715,7 +841,7 @@ static int handoff_prepare(sg_handle* h, hipStream_t st) {
 }
 
 // After the stream has been synchronised: did a hand-off of the work just completed time out?
-static int handoff_verdict(sg_handle* h) {
+int sg::host::handoff_verdict(sg_handle* h) {
   if (h->err_host && *h->err_host != 0u) {
     const unsigned e = *h->err_host;
     *h->err_host = 0u;
@@ -2013,10 +1139,8 @@ static int stage_mag(sg_handle* h, const View& v, const Geom& g, int64_t ub, hip
     M.iir_b = iir_b; M.sub = sub;
     size_t lds = (size_t)(fast::FN + WAVES * fast::WAVE_CX_H) * sizeof(fast::cf) + 1024 * sizeof(float);
     auto kern = fast::k_mag_fast<WAVES>;
-    HIPCHK(h, set_lds(reinterpret_cast<const void*>(kern), lds));
     dim3 grid((unsigned)((g.T + 4 * WAVES - 1) / (4 * WAVES)), (unsigned)ub);
-    hipLaunchKernelGGL(kern, grid, dim3(WAVES * 64), lds, st, M);
-    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, launch_lds(kern, grid, dim3(WAVES * 64), lds, st, M));
   } else {
     ProfScope ps(h, SG_STAGE_STFT_MAG, st);
     HIPCHK(h, stft_any<float>(h, v, g, ub, nullptr, mag, nullptr, 1.0, st));
@@ -2196,12 +1320,9 @@ static int stage_smooth(sg_handle* h, const Geom& g, int64_t ub, hipStream_t st,
     // and used to fall through to the two direct global-memory convolutions below: 0.73 ms of a 1.09 ms call)
     if (lds <= 150 * 1024 && ub <= 65535 && nf <= 30 && 2 * nt + 4 <= SMF_KT && SMF_FB + 2 * nf <= 192) {
       auto kern = k_smooth_tiled;
-      if (lds > 65536)
-        HIPCHK(h, set_lds(reinterpret_cast<const void*>(kern), lds));
       dim3 grid((g.F + SMF_FB - 1) / SMF_FB, (unsigned)((g.T + SMF_TT - 1) / SMF_TT), (unsigned)ub);
-      hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, (const float*)h->raw.p, g, (const float*)h->kf.p, nf,
-                         (const float*)h->kt.p, nt, p, prop_before0, Mdst);
-      HIPCHK(h, hipGetLastError());
+      HIPCHK(h, launch_lds_if(lds > 65536, kern, grid, dim3(256), lds, st, (const float*)h->raw.p, g, (const float*)h->kf.p, nf,
+                              (const float*)h->kt.p, nt, p, prop_before0, Mdst));
       note_smooth(h, SG_SMOOTH_TILED, 4, SMF_TT);
       return SG_OK;
     }
@@ -2361,10 +1482,8 @@ static int stage_fused_mask(sg_handle* h, const View& v, const Geom& g, int64_t 
     const int64_t per_block = (int64_t)WAVES * D.quads_per_wave;
     size_t lds = (size_t)(fast::FN + WAVES * fast::WAVE_CX_H) * sizeof(fast::cf) + (T2_FLOATS + 1024) * sizeof(float);
     auto kern = fast::k_decide_fast<WAVES>;
-    HIPCHK(h, set_lds(reinterpret_cast<const void*>(kern), lds));
     dim3 grid((unsigned)((quads + per_block - 1) / per_block), (unsigned)ub);
-    hipLaunchKernelGGL(kern, grid, dim3(WAVES * 64), lds, st, D);
-    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, launch_lds(kern, grid, dim3(WAVES * 64), lds, st, D));
   } else if (r) {
     if ((rc = stage_decide_reg(h, r, v, g, ub, tc, (unsigned long long*)h->bits.p, st, fs.fl))) return rc;
   } else if (!h->force_f64_decide) {
@@ -2646,13 +1765,8 @@ static hipError_t launch_xapply_n(const View& v, const Geom& g, int64_t units, c
   constexpr int FPW = 4;
   const size_t lds = (size_t)(N + WAVES * lpn<double>(N)) * sizeof(cx<double>);
   auto kern = exact::kx_apply_istft<N, WAVES, FPW, NT>;
-  if (lds > 65536) {
-    hipError_t e = set_lds(reinterpret_cast<const void*>(kern), lds);
-    if (e != hipSuccess) return e;
-  }
   dim3 grid((unsigned)((g.T + WAVES * FPW - 1) / (WAVES * FPW)), (unsigned)units);
-  hipLaunchKernelGGL(kern, grid, dim3(WAVES * NT), lds, st, v, g, (const cx<double>*)tw, win, M, seg);
-  return hipGetLastError();
+  return launch_lds_if(lds > 65536, kern, grid, dim3(WAVES * NT), lds, st, v, g, (const cx<double>*)tw, win, M, seg);
 }
 
 template <int M>
@@ -2661,14 +1775,9 @@ static hipError_t launch_xapply_czt_m(const View& v, const Geom& g, int64_t unit
   constexpr int NT = CztShape<M>::NT, FR = CztShape<M>::FR;
   const size_t lds = (size_t)FR * lpn<double>(M) * sizeof(cx<double>);
   auto kern = exact::kx_apply_istft_czt<M, NT, FR>;
-  if (lds > 65536) {
-    hipError_t e = set_lds(reinterpret_cast<const void*>(kern), lds);
-    if (e != hipSuccess) return e;
-  }
   const int fpb = 4;
   dim3 grid((unsigned)((g.T + FR * fpb - 1) / (FR * fpb)), (unsigned)units);
-  hipLaunchKernelGGL(kern, grid, dim3(NT * FR), lds, st, v, g, tb, win, Mk, seg, fpb);
-  return hipGetLastError();
+  return launch_lds_if(lds > 65536, kern, grid, dim3(NT * FR), lds, st, v, g, tb, win, Mk, seg, fpb);
 }
 
 static hipError_t xapply_any(sg_handle* h, const View& v, const Geom& g, int64_t units, const double* Mk, double* seg,
@@ -2780,15 +1889,10 @@ static int run_S_exact(sg_handle* h, View v, int64_t total_units, const OutMap& 
         const size_t lds = exact::xsm_lds_bytes(nf, nt);
         note_smooth(h, SG_SMOOTH_X_TILED, 8, exact::XSM_TT);
         const dim3 gt((unsigned)((g.F + exact::XSM_FB - 1) / exact::XSM_FB), (unsigned)((g.T + exact::XSM_TT - 1) / exact::XSM_TT), (unsigned)nb);
-        if (h->p.stationary) {
-          auto kern = exact::kx_smooth_tiled<float>;
-          HIPCHK(h, set_lds(reinterpret_cast<const void*>(kern), lds));
-          hipLaunchKernelGGL(kern, gt, dim3(exact::XSM_THREADS), lds, st, (const float*)h->xraw.p, g, nf, nt, p, prop_before, (double*)h->xM.p);
-        } else {
-          auto kern = exact::kx_smooth_tiled<double>;
-          HIPCHK(h, set_lds(reinterpret_cast<const void*>(kern), lds));
-          hipLaunchKernelGGL(kern, gt, dim3(exact::XSM_THREADS), lds, st, (const double*)h->xraw.p, g, nf, nt, p, prop_before, (double*)h->xM.p);
-        }
+        if (h->p.stationary)
+          HIPCHK(h, launch_lds(exact::kx_smooth_tiled<float>, gt, dim3(exact::XSM_THREADS), lds, st, (const float*)h->xraw.p, g, nf, nt, p, prop_before, (double*)h->xM.p));
+        else
+          HIPCHK(h, launch_lds(exact::kx_smooth_tiled<double>, gt, dim3(exact::XSM_THREADS), lds, st, (const double*)h->xraw.p, g, nf, nt, p, prop_before, (double*)h->xM.p));
       } else {
         if (h->p.stationary)
           hipLaunchKernelGGL(exact::kx_smooth_f<float>, gr, dim3(256), 0, st, (const float*)h->xraw.p, g, nf, (double*)h->xtmp.p, nb);
@@ -3011,21 +2115,13 @@ static int stage_row_gate(sg_handle* h, const View& v, const Geom& g, int64_t nb
   ProfScope ps(h, SG_STAGE_ROW_GATE, st);
   const size_t lds = fast::rowgate_lds_bytes();
   if (h->rg_shape == 8) {     // SG_OPT_ROWGATE_SHAPE: 8 waves x 2 quads (256 VGPRs, no scratch)
-    HIPCHK(h, set_lds(reinterpret_cast<const void*>(fast::k_row_gate<8, 2>), lds));
-    hipLaunchKernelGGL((fast::k_row_gate<8, 2>), dim3((unsigned)nb), dim3(512), lds, st, A);
+    HIPCHK(h, launch_lds(fast::k_row_gate<8, 2>, dim3((unsigned)nb), dim3(512), lds, st, A));
   } else {                    // default: 16 waves x 1 quad
-    HIPCHK(h, set_lds(reinterpret_cast<const void*>(fast::k_row_gate<16, 1>), lds));
-    hipLaunchKernelGGL((fast::k_row_gate<16, 1>), dim3((unsigned)nb), dim3(1024), lds, st, A);
+    HIPCHK(h, launch_lds(fast::k_row_gate<16, 1>, dim3((unsigned)nb), dim3(1024), lds, st, A));
   }
-  HIPCHK(h, hipGetLastError());
   note_smooth(h, SG_SMOOTH_ROW_GATE, 1, fast::RG_FRAMES);
   return SG_OK;
 }
-
-static bool dtype_ok(int d) { return d >= SG_F32 && d <= SG_I32; }
-
-// Bytes of one float32 / float64 element (the dtypes of the variant-T outputs and gradients).
-static size_t elem_bytes(int dtype) { return dtype == SG_F64 ? 8 : 4; }
 
 // Rows of L samples read whole: one unit per row, no chunks, no padding, no halos, first unit 0.
 static View rows_view(const void* ptr, int dtype, int64_t stride, int64_t L) {
@@ -3040,23 +2136,6 @@ static OutMap whole_out(void* ptr, int dtype, int64_t stride, int64_t n) {
   om.out = ptr; om.dtype = dtype; om.stride = stride;
   om.p0 = 0; om.p1 = n; om.g_step = 0; om.g0 = 0; om.g_lo = 0; om.g_hi = n;
   return om;
-}
-
-// The head of every variant-T entry point: a handle, and one of variant T.
-static int t_entry(sg_handle* h, const char* who) {
-  if (!h) return SG_E_INVALID;
-  if (h->p.variant != SG_VARIANT_T) FAIL(h, SG_E_INVALID, "%s is a variant-T entry point", who);
-  return SG_OK;
-}
-
-// The reference's minimum lengths of x and xn, and the rows of xn (torchgate.py:215-220).
-static int t_min_lengths(sg_handle* h, int64_t B, int64_t L, const void* xn_dev, int64_t Bn, int64_t Ln) {
-  if (L < 2 * (int64_t)h->W) FAIL(h, SG_E_INVALID, "x must be bigger than %d", 2 * h->W);
-  if (xn_dev) {
-    if (Ln < 2 * (int64_t)h->W) FAIL(h, SG_E_INVALID, "xn must be bigger than %d", 2 * h->W);
-    if (Bn != 1 && Bn != B) FAIL(h, SG_E_INVALID, "xn rows (%lld) must be 1 or the batch size", (long long)Bn);
-  }
-  return SG_OK;
 }
 
 extern "C" int sg_workspace_bytes(const sg_handle* h, int64_t C, int64_t N, int32_t chunked, int64_t* bytes) {
@@ -3244,10 +2323,6 @@ struct FeatSink {
   int power, take_log;
   double eps;
 };
-
-static FeatBank feat_bank(const sg_handle* h) {
-  return {(const float*)h->fb_d.p, (const float*)h->fbT_d.p, (const int2*)h->fb_khull.p, (const int2*)h->fb_mhull.p, h->n_filters};
-}
 
 // The filterbank features of one sub-batch (feat.hpp), where stage_spectrum stores the spectrogram: -> feat_dev[u0 ..][T][M].
 static int stage_features(sg_handle* h, const View& v, const Geom& g, int64_t u0, int64_t nb, const float* mask,
@@ -3453,8 +2528,6 @@ extern "C" int sg_process_batch(sg_handle* h, const void* x_dev, int dtype, int6
 }
 
 // TorchGate.gated_stft: X * mask in torch.stft's layout (spec.hpp)
-static bool spectrum_geom_ok(const sg_handle* h) { return spec_native(h->n) && !h->czt_M && !h->big_M && !h->mr_ok; }
-
 extern "C" int sg_gate_spectrum(sg_handle* h, const void* x_dev, int dtype, int64_t B, int64_t L, int64_t x_stride,
                                 const void* xn_dev, int64_t Bn, int64_t Ln, int64_t xn_stride, void* spec_dev,
                                 float* mask_out_dev, void* stream) {
@@ -3532,14 +2605,6 @@ extern "C" int sg_set_filterbank(sg_handle* h, const float* fb_host, int32_t n_f
   return SG_OK;
 }
 
-static int features_args_ok(sg_handle* h, const char* who, int power, double eps) {
-  if (power != 1 && power != 2) FAIL(h, SG_E_INVALID, "%s: power must be 1 or 2", who);
-  if (!(eps == eps)) FAIL(h, SG_E_INVALID, "%s: eps is NaN", who);
-  if (!spectrum_geom_ok(h)) FAIL(h, SG_E_UNSUPPORTED, "%s: n_fft=%d (powers of two from 256 to 4096 only)", who, h->n);
-  if (!h->n_filters) FAIL(h, SG_E_INVALID, "%s: no filterbank set (sg_set_filterbank)", who);
-  return SG_OK;
-}
-
 extern "C" int sg_gate_features(sg_handle* h, const void* x_dev, int dtype, int64_t B, int64_t L, int64_t x_stride,
                                 const void* xn_dev, int64_t Bn, int64_t Ln, int64_t xn_stride, int32_t power, int32_t take_log,
                                 double eps, void* feat_dev, float* mask_out_dev, void* stream) {
@@ -3607,9 +2672,7 @@ extern "C" int sg_process_batch_backward(sg_handle* h, const void* grad_out_dev,
     A.mask = mask_dev;
     A.kscale = (float)(1.0 / 512.0);
     const size_t lds = fast::rowbwd_lds_bytes();
-    HIPCHK(h, set_lds(reinterpret_cast<const void*>(fast::k_row_backward), lds));
-    hipLaunchKernelGGL(fast::k_row_backward, dim3((unsigned)B), dim3(1024), lds, st, A);
-    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, launch_lds(fast::k_row_backward, dim3((unsigned)B), dim3(1024), lds, st, A));
     return SG_OK;
   }
   int64_t ub = units_per_batch(h, g, B);
@@ -3656,159 +2719,21 @@ extern "C" int sg_stft(sg_handle* h, const void* x_dev, int dtype, int64_t B, in
   return SG_OK;
 }
 
-extern "C" int sg_set_option(sg_handle* h, int32_t option, int64_t value) {
-  if (!h) return SG_E_INVALID;
-  switch (option) {
-    case SG_OPT_FORCE_UNFUSED: h->force_unfused = value != 0; return SG_OK;
-    case SG_OPT_FORCE_NOFAST: h->force_nofast = value != 0; return SG_OK;
-    case SG_OPT_FORCE_F64_DECIDE: h->force_f64_decide = value != 0; return SG_OK;
-    case SG_OPT_FORCE_NOSEAM: h->force_noseam = value != 0; return SG_OK;
-    case SG_OPT_FORCE_NOLEAN: h->force_nolean = value != 0; return SG_OK;
-    case SG_OPT_FORCE_SPLIT: h->force_split = value != 0; return SG_OK;
-    case SG_OPT_FAST_INTEGER: h->fast_integer = value != 0; return SG_OK;
-    case SG_OPT_FORCE_EXACT: h->force_exact = value != 0; return SG_OK;
-    case SG_OPT_FORCE_NOROWGATE:
-      if (value < 0 || value > 2) FAIL(h, SG_E_INVALID, "SG_OPT_FORCE_NOROWGATE: 0 (auto), 1 (never) or 2 (always)");
-      h->rowgate_mode = (int)value;
-      return SG_OK;
-    case SG_OPT_ROWGATE_TAP: h->rg_tap = value != 0; return SG_OK;
-    case SG_OPT_ROWGATE_SHAPE:
-      if (value != 8 && value != 16) FAIL(h, SG_E_INVALID, "SG_OPT_ROWGATE_SHAPE: 8 or 16 waves");
-      h->rg_shape = (int)value;
-      return SG_OK;
-    case SG_OPT_INJECT_HANDOFF_FAULT: h->inject_fault = (unsigned)value & 63u; return SG_OK;
-    case SG_OPT_TILE_ORDER:
-      if (value < 0 || value > 2) FAIL(h, SG_E_INVALID, "SG_OPT_TILE_ORDER: 0 (persistent workgroups), 1 (block index) or 2 (one ticket per workgroup)");
-      h->tile_order = (int)value;
-      return SG_OK;
-    case SG_OPT_EXACT_MATERIALISED: h->exact_materialised = value != 0; return SG_OK;
-    case SG_OPT_STATS_THREE_LAUNCH: h->stats_three = value != 0; return SG_OK;
-    case SG_OPT_FLOOR_TEST:
-      if (value < 0 || value > 2) FAIL(h, SG_E_INVALID, "SG_OPT_FLOOR_TEST: 0 (predicted), 1 (a priori) or 2 (in the gate kernel)");
-      h->floor_test = (int)value;
-      return SG_OK;
-  }
-  FAIL(h, SG_E_INVALID, "sg_set_option: unknown option %d", option);
-}
-
-extern "C" int sg_get_option(const sg_handle* h, int32_t option, int64_t* value) {
-  if (!h || !value) return SG_E_INVALID;
-  switch (option) {
-    case SG_OPT_FORCE_UNFUSED: *value = h->force_unfused; return SG_OK;
-    case SG_OPT_FORCE_NOFAST: *value = h->force_nofast; return SG_OK;
-    case SG_OPT_FORCE_F64_DECIDE: *value = h->force_f64_decide; return SG_OK;
-    case SG_OPT_FORCE_NOSEAM: *value = h->force_noseam; return SG_OK;
-    case SG_OPT_FORCE_NOLEAN: *value = h->force_nolean; return SG_OK;
-    case SG_OPT_FORCE_SPLIT: *value = h->force_split; return SG_OK;
-    case SG_OPT_FAST_INTEGER: *value = h->fast_integer; return SG_OK;
-    case SG_OPT_FORCE_EXACT: *value = h->force_exact; return SG_OK;
-    case SG_OPT_FORCE_NOROWGATE: *value = h->rowgate_mode; return SG_OK;
-    case SG_OPT_ROWGATE_TAP: *value = h->rg_tap; return SG_OK;
-    case SG_OPT_ROWGATE_SHAPE: *value = h->rg_shape; return SG_OK;
-    case SG_OPT_INJECT_HANDOFF_FAULT: *value = h->inject_fault; return SG_OK;
-    case SG_OPT_TILE_ORDER: *value = h->tile_order; return SG_OK;
-    case SG_OPT_EXACT_MATERIALISED: *value = h->exact_materialised; return SG_OK;
-    case SG_OPT_STATS_THREE_LAUNCH: *value = h->stats_three; return SG_OK;
-    case SG_OPT_FLOOR_TEST: *value = h->floor_test; return SG_OK;
-  }
-  return SG_E_INVALID;   // (no message: the handle is const here)
-}
-
-extern "C" int sg_profile_enable(sg_handle* h, int32_t on) {
-  if (!h) return SG_E_INVALID;
-  h->prof_on = on != 0;
+// ---- what debug.hip's taps need of this unit (handle.hpp) ----
+int sg::host::expand_k16_mask(sg_handle* h, size_t cells, hipStream_t st) {
+  // same kernel, same arithmetic as the materialising path.
+  // (a debug entry point: whatever stream produced the counts has to be done first)
+  HIPCHK(h, hipDeviceSynchronize());
+  hipLaunchKernelGGL(k_k16_to_mask, dim3(grid_1d((int64_t)cells / 8, 256)), dim3(256), 0, st,
+                     (const unsigned short*)h->K16.p, h->dbg_g, h->p.n_grad_freq, h->p.n_grad_time, 1.0f / (float)h->ktot,
+                     (float)h->p.prop_decrease, 1, h->p.smooth_mask ? 1 : 0, (float*)h->M.p, (int64_t)h->dbg_units);
+  HIPCHK(h, hipGetLastError());
   return SG_OK;
 }
 
-extern "C" int sg_profile_select(sg_handle* h, int64_t stage_mask) {
-  if (!h) return SG_E_INVALID;
-  h->prof_mask = stage_mask == 0 ? ~0ull : (uint64_t)stage_mask;
-  return SG_OK;
-}
-
-extern "C" int sg_profile_read(sg_handle* h, double* ms, int64_t* counts, int32_t n_stages, int32_t reset) {
-  if (!h) return SG_E_INVALID;
-  if (n_stages != SG_N_STAGES && n_stages != SG_N_STAGES_ALL)
-    FAIL(h, SG_E_INVALID, "sg_profile_read: n_stages must be %d (or %d)", SG_N_STAGES, SG_N_STAGES_ALL);
-  for (auto& r : h->prof_live) {
-    HIPCHK(h, hipEventSynchronize(r.b));
-    float t = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&t, r.a, r.b));
-    h->prof_ms[r.stage] += (double)t;
-    h->prof_cnt[r.stage] += 1;
-    h->prof_pool.push_back(r.a);
-    h->prof_pool.push_back(r.b);
-  }
-  h->prof_live.clear();
-  for (int i = 0; i < SG_N_STAGES_ALL; ++i) {
-    if (ms && i < n_stages) ms[i] = h->prof_ms[i];
-    if (counts && i < n_stages) counts[i] = h->prof_cnt[i];
-    if (reset) { h->prof_ms[i] = 0; h->prof_cnt[i] = 0; }
-  }
-  return SG_OK;
-}
-
-extern "C" const char* sg_stage_name(int32_t stage) {
-  static const char* names[SG_N_STAGES_ALL] = {"k_channel_mean", "k_stft<double> (power)", "k_colmax", "k_colstats",
-                                           "k_decide", "k_mag_fast* / k_stft<float> (magnitude)",
-                                           "k_box_mask / k_iir_sigmoid / k_boxcar_sigmoid (non-stationary mask, other paths)",
-                                           "mask smoothing (k_smooth_bits2 / k_smooth_tiled / k_smooth_f+k_smooth_t)",
-                                           "k_apply_istft", "k_ola",
-                                           "noise statistics (all kernels)", "k_unit_absmax+k_prep_thresh",
-                                           "k_stft_bits<max> (floor pre-pass)", "k_stft_bits<decide>",
-                                           "k_apply_fast (fft+mask+ifft+ola)",
-                                           "k_decide_fast (f32 stft + exact f64 refine)",
-                                           "k_gate_onepass (fft+decide+smooth+mask+ifft+ola)",
-                                           "k_row_gate (fft+row stats+decide+smooth+mask+ifft+ola)",
-                                           "k_iir_chain_par (tile carries; serial: k_iir_part / k_iir_comb + k_iir_chain)",
-                                           "k_iir_mask<nt> (recurrence+sigmoid+smoothing)",
-                                           "k_rg_noise_power (clips: noise transform)",
-                                           "k_rg_noise_final (clips: thresholds)",
-                                           "k_rg_decide (clips: transform + bits / magnitudes)",
-                                           "k_rg_iir (clips: recurrence + sigmoid)",
-                                           "k_rg_fsmooth (clips: frequency smoothing)",
-                                           "k_rg_apply (clips: time smoothing + mask + inverse transform)",
-                                           "k_rg_ola (clips: overlap-add)",
-                                           "k_st_export (stream state -> payload)",
-                                           "k_st_import (payload -> stream state)"};
-  return (stage >= 0 && stage < SG_N_STAGES_ALL) ? names[stage] : "?";
-}
-
-extern "C" int sg_debug_dims(const sg_handle* h, int64_t dims[3]) {
-  if (!h || !dims) return SG_E_INVALID;
-  dims[0] = h->dbg_units; dims[1] = h->dbg_T; dims[2] = h->FS;
-  return SG_OK;
-}
-
-extern "C" int sg_debug_range(const sg_handle* h, int64_t range[2]) {
-  if (!h || !range) return SG_E_INVALID;
-  range[0] = h->dbg_db; range[1] = h->dbg_de;
-  return SG_OK;
-}
-
-extern "C" int sg_debug_counter(sg_handle* h, int32_t which, int64_t* value, void* stream) {
-  if (!h || !value) return SG_E_INVALID;
-  if (which == 1 || which == 2) {   // host counters: one-pass gate calls with the in-kernel (1) / a-priori (2) floor test
-    *value = which == 1 ? h->n_floor_lazy : h->n_floor_apriori;
-    return SG_OK;
-  }
-  if (which == 17) {   // SG_SMOOTH_* of the last smoothing launch | cell bytes << 8 | tile frames << 16 (host bookkeeping)
-    *value = h->smooth_route;
-    return SG_OK;
-  }
-  if (which == 18) {   // SG_SPEC_* of the last sg_gate_spectrum call | flags | sub-batches << 16 (host bookkeeping)
-    *value = h->spec_route;
-    return SG_OK;
-  }
-  if (which == 19) {   // SG_STATS_* form of the last noise statistics of fewer than 16 units (host bookkeeping)
-    *value = h->stats_route;
-    return SG_OK;
-  }
-  if (which == 3) {   // launch epoch of the last gate call in which a chunk's floor test fired / flag was set (0: never)
-    HIPCHK(h, hipStreamSynchronize((hipStream_t)stream));
-    *value = h->err_host ? (int64_t)h->err_host[1] : 0;
-    return SG_OK;
-  }
+#if OP_TRACE || OP_WHO
+static int onepass_dev_counter_impl(sg_handle* h, int which, int64_t* value, void* stream, bool* done) {
+  *done = true;
 #if OP_TRACE
   if (which == 8) {
     // (diagnosis) after a call that lost a hand-off: the tiles of the last first launch that did not run to the end -- who took
@@ -3854,449 +2779,18 @@ extern "C" int sg_debug_counter(sg_handle* h, int32_t which, int64_t* value, voi
     return SG_OK;
   }
 #endif
-  if (which >= 4 && which <= 15) {   // development (-DOP_TILECOUNT=1 builds): tiles completed / sum of their tickets, persistent gate
-    HIPCHK(h, hipStreamSynchronize((hipStream_t)stream));
-    *value = h->err_host ? (int64_t)h->err_host[which] : 0;
-    return SG_OK;
-  }
-  if (which != 0) FAIL(h, SG_E_INVALID, "sg_debug_counter: unknown counter %d", which);
-  *value = 0;
-  if (!h->rg_count.p) return SG_OK;
-  HIPCHK(h, hipStreamSynchronize((hipStream_t)stream));
-  unsigned v = 0;
-  HIPCHK(h, hipMemcpy(&v, h->rg_count.p, sizeof(v), hipMemcpyDeviceToHost));
-  *value = (int64_t)v;
+  *done = false;
   return SG_OK;
 }
-
-extern "C" int sg_debug_fetch(sg_handle* h, int32_t what, void* host, int64_t bytes, void* stream) {
-  if (!h) return SG_E_INVALID;
-  if (what == 5) {   // the gate's compare constants of the last noise statistics: T2 double[F], then the 64 words of the alim block
-    if (!host || !h->t2_ready) FAIL(h, SG_E_STATE, "sg_debug_fetch: no compare constants from noise statistics");
-    if ((size_t)bytes != (size_t)h->F * 8 + 256) FAIL(h, SG_E_INVALID, "sg_debug_fetch: need %zu bytes, got %lld", (size_t)h->F * 8 + 256, (long long)bytes);
-    HIPCHK(h, hipMemcpyAsync(host, h->T2.p, (size_t)h->F * 8, hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIPCHK(h, hipMemcpyAsync((char*)host + (size_t)h->F * 8, h->alim.p, 256, hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIPCHK(h, hipStreamSynchronize((hipStream_t)stream));
-    return SG_OK;
-  }
-  if (!host || h->dbg_units == 0) FAIL(h, SG_E_STATE, "sg_debug_fetch: nothing processed yet");
-  size_t cells = (size_t)h->dbg_units * h->dbg_T * h->FS;
-  const void* src;
-  size_t need;
-  switch (what) {
-    case 0:
-      if (h->dbg_fused) FAIL(h, SG_E_STATE, "fused path keeps the raw mask as bits: fetch field 3");
-      if (!h->dbg_has_raw)
-        FAIL(h, SG_E_STATE, "the one-kernel non-stationary mask does not materialise the raw mask: set SG_OPT_FORCE_UNFUSED");
-      src = h->raw.p; need = cells * 4; break;
-    case 3:
-      if (!h->dbg_fused) FAIL(h, SG_E_STATE, "bit field only exists on the fused path");
-      src = h->bits.p; need = (size_t)h->dbg_units * h->dbg_T * ((h->F + 63) / 64) * 8; break;
-    case 1:
-      if (h->dbg_fast && h->dbg_fused)
-        FAIL(h, SG_E_STATE, "fast path keeps the smoothed mask as uint16 counts in the apply kernel's lane order");
-      if (h->dbg_fused && h->dbg_k16_only) {
-        // the apply kernel read the K counts directly: expand them now (same kernel, same arithmetic as the materialising path).
-        // (a debug entry point: whatever stream produced the counts has to be done first)
-        HIPCHK(h, hipDeviceSynchronize());
-        hipLaunchKernelGGL(k_k16_to_mask, dim3(grid_1d((int64_t)cells / 8, 256)), dim3(256), 0, (hipStream_t)stream,
-                           (const unsigned short*)h->K16.p, h->dbg_g, h->p.n_grad_freq, h->p.n_grad_time, 1.0f / (float)h->ktot,
-                           (float)h->p.prop_decrease, 1, h->p.smooth_mask ? 1 : 0, (float*)h->M.p, (int64_t)h->dbg_units);
-        HIPCHK(h, hipGetLastError());
-      }
-      src = h->M.p; need = cells * 4; break;
-    case 2:
-      if (!h->dbg_has_P) FAIL(h, SG_E_STATE, "power field only exists for stationary gates");
-      src = h->P.p; need = cells * 8; break;
-    case 4:
-      if (!h->dbg_rg || !h->rg_tap) FAIL(h, SG_E_STATE, "row-gate power tile: set SG_OPT_ROWGATE_TAP and run TorchGate.forward");
-      src = h->M.p; need = (size_t)h->dbg_units * 64 * fast::RG_PP * 4; break;
-    default: FAIL(h, SG_E_INVALID, "sg_debug_fetch: unknown field %d", what);
-  }
-  if ((size_t)bytes != need) FAIL(h, SG_E_INVALID, "sg_debug_fetch: need %zu bytes, got %lld", need, (long long)bytes);
-  HIPCHK(h, hipStreamSynchronize((hipStream_t)stream));
-  { int rc = handoff_verdict(h); if (rc) return rc; }
-  if (what == 3 && h->dbg_xbits) {
-    // one-pass path: the bits live tile-blocked in the exchange buffer [unit][tile][16][9]; rearrange into
-    // the natural [unit][T][wpr] layout (frames outside sg_debug_range stay zero)
-    const int wpr = (h->F + 63) / 64;
-    const int TW = h->dbg_twords ? h->dbg_twords : fast::OP_TILE_WORDS, XW = h->dbg_txw;
-    const size_t words = (size_t)h->dbg_units * h->dbg_ntt * TW;
-    std::vector<unsigned long long> tmp(words);
-    HIPCHK(h, hipMemcpy(tmp.data(), h->xbits.p, words * 8, hipMemcpyDeviceToHost));
-    unsigned long long* dst = (unsigned long long*)host;
-    std::memset(dst, 0, need);
-    for (int64_t u = 0; u < h->dbg_units; ++u)
-      for (int64_t j = 0; j < h->dbg_ntt; ++j)
-        for (int i = 0; i < h->dbg_trows; ++i) {
-          const int64_t t = h->dbg_tf0 + (j - 1) * h->dbg_tstep + i;
-          if (t < 0 || t >= h->dbg_T) continue;
-          for (int w = 0; w < wpr; ++w)
-          {
-            const unsigned long long* gr = &tmp[((size_t)u * h->dbg_ntt + j) * TW + (i * XW + w) * 2];
-            dst[(u * h->dbg_T + t) * wpr + w] = (gr[0] & 0xffffffffull) | (gr[1] << 32);
-          }
-        }
-    return SG_OK;
-  }
-  HIPCHK(h, hipMemcpy(host, src, need, hipMemcpyDeviceToHost));
-  return SG_OK;
+#endif
+bool sg::host::onepass_dev_counter(sg_handle* h, int which, int64_t* value, hipStream_t st, int* rc) {
+#if OP_TRACE || OP_WHO
+  bool done = false;
+  *rc = onepass_dev_counter_impl(h, which, value, (void*)st, &done);
+  return done;
+#else
+  (void)h; (void)which; (void)value; (void)st; (void)rc;
+  return false;
+#endif
 }
 
-// ---- ragged batches: thin wrappers over ragged.hip ------------------------------------------------------------------
-static void* rg_prof_begin(void* ctx, int stage, hipStream_t st) { return new ProfScope((sg_handle*)ctx, stage, st); }
-static void rg_prof_end(void* tok) { delete (ProfScope*)tok; }
-
-static sg::RgCtx rg_ctx(sg_handle* h) {
-  sg::RgCtx c{};
-  c.n = h->n; c.N = h->N; c.W = h->W; c.H = h->H; c.F = h->F; c.FS = h->FS; c.padL = h->padL;
-  c.mag_scale = h->mag_scale; c.tw64 = h->tw64.p; c.wfull64 = (const double*)h->wfull64.p;
-  c.stationary = h->p.stationary; c.cs = h->p.chunk_size; c.pad = h->p.padding;
-  c.nf = h->p.smooth_mask ? h->p.n_grad_freq : 0;
-  c.nt = h->p.smooth_mask ? h->p.n_grad_time : 0;
-  c.prop = h->p.prop_decrease; c.top_db = h->p.top_db; c.n_std = h->p.n_std_thresh; c.iir_b = h->p.iir_b;
-  c.nthresh = h->p.nonstat_thresh; c.slope = h->p.nonstat_slope; c.ddof = h->p.ddof;
-  c.hook_ctx = h; c.prof_begin = rg_prof_begin; c.prof_end = rg_prof_end;
-  return c;
-}
-
-static bool rg_variant_ok(sg_handle* h) {
-  if (h->p.variant != SG_VARIANT_S) { h->err = "sg_process_clips is a variant-S entry point"; return false; }
-  return true;
-}
-
-extern "C" int sg_clips_workspace_bytes(const sg_handle* h, const sg_noise_src* noise, int32_t n_noise, const sg_clip* clips,
-                                        int64_t n_clips, int64_t* bytes) {
-  if (!h || !bytes || n_clips < 0 || (n_clips > 0 && !clips) || n_noise < 0 || (n_noise > 0 && !noise)) return SG_E_INVALID;
-  sg_handle* hm = const_cast<sg_handle*>(h);
-  if (!rg_variant_ok(hm)) return SG_E_INVALID;
-  return sg::rg_workspace_bytes(rg_ctx(hm), noise, n_noise, clips, n_clips, bytes, &hm->err);
-}
-
-extern "C" int sg_process_clips(sg_handle* h, const void* x_dev, int in_dtype, const void* noise_dev, int noise_dtype,
-                                const sg_noise_src* noise, int32_t n_noise, const sg_clip* clips, int64_t n_clips,
-                                void* out_dev, int out_dtype, int64_t max_workspace_bytes, void* stream) {
-  if (!h) return SG_E_INVALID;
-  if (!rg_variant_ok(h)) return SG_E_INVALID;
-  if (n_clips < 0 || (n_clips > 0 && (!clips || !x_dev || !out_dev)) || !dtype_ok(in_dtype) || !dtype_ok(out_dtype) ||
-      n_noise < 0 || (n_noise > 0 && !noise) || (h->p.stationary && n_noise > 0 && !dtype_ok(noise_dtype) && noise_dev))
-    FAIL(h, SG_E_INVALID, "sg_process_clips: bad argument");
-  if (n_clips == 0) return SG_OK;
-  return sg::rg_process(&h->rg, rg_ctx(h), x_dev, in_dtype, noise_dev, noise_dtype, noise, n_noise, clips, n_clips, out_dev,
-                        out_dtype, max_workspace_bytes, (hipStream_t)stream, &h->err);
-}
-
-extern "C" int sg_debug_clip_thresholds(sg_handle* h, double* host, int32_t n_noise, int32_t n_bins, void* stream) {
-  if (!h || !host || n_bins != h->F) return SG_E_INVALID;
-  return sg::rg_thresholds(h->rg, host, n_noise, n_bins, (hipStream_t)stream, &h->err);
-}
-
-extern "C" int sg_debug_clip_batches(const sg_handle* h, int64_t* value) {
-  if (!h || !value) return SG_E_INVALID;
-  *value = sg::rg_last_batches(h->rg);
-  return SG_OK;
-}
-
-// ---- padded batches of different-length rows: thin wrappers over rows.hip ---------------------------------------------
-static int64_t rw_budget(const sg_handle* h) { return h->p.max_workspace_bytes > 0 ? h->p.max_workspace_bytes : 0; }
-
-extern "C" int sg_process_rows(sg_handle* h, const void* x_dev, int dtype, int64_t B, int64_t L, int64_t x_stride,
-                               const int64_t* lengths, const void* xn_dev, int64_t Bn, int64_t Ln, int64_t xn_stride,
-                               const int64_t* xn_lengths, void* out_dev, int out_dtype, int64_t out_stride,
-                               float* mask_out_dev, void* stream) {
-  if (int rc = t_entry(h, "sg_process_rows")) return rc;
-  if (!x_dev || !out_dev || (dtype != SG_F32 && dtype != SG_F64) || (out_dtype != SG_F32 && out_dtype != SG_F64) || B < 1 ||
-      x_stride < L || out_stride < 0)
-    FAIL(h, SG_E_INVALID, "sg_process_rows: bad argument");
-  if (int rc = t_min_lengths(h, B, L, xn_dev, Bn, Ln)) return rc;
-  return sg::rw_process(&h->rw, rg_ctx(h), h->p.n_movemean, x_dev, dtype, B, L, x_stride, lengths, xn_dev, Bn, Ln, xn_stride,
-                        xn_lengths, out_dev, out_dtype, out_stride, mask_out_dev, rw_budget(h), (hipStream_t)stream, &h->err);
-}
-
-extern "C" int sg_process_rows_backward(sg_handle* h, const void* grad_out_dev, int dtype, int64_t B, int64_t L,
-                                        int64_t go_stride, const int64_t* lengths, const float* mask_dev, void* grad_x_dev,
-                                        int64_t gx_stride, void* stream) {
-  if (int rc = t_entry(h, "sg_process_rows_backward")) return rc;
-  if (!grad_out_dev || !grad_x_dev || !mask_dev || B < 1 || (dtype != SG_F32 && dtype != SG_F64) || gx_stride < L ||
-      L < 2 * (int64_t)h->W)
-    FAIL(h, SG_E_INVALID, "sg_process_rows_backward: bad argument");
-  h->dbg_bwd_route = SG_BWD_ROWS;
-  return sg::rw_backward(&h->rw, rg_ctx(h), grad_out_dev, dtype, B, L, go_stride, lengths, mask_dev, grad_x_dev, gx_stride,
-                         rw_budget(h), (hipStream_t)stream, &h->err);
-}
-
-// TorchGate.gated_stft(lengths=): the rows pipeline with the masked spectrum stored instead of inverted (rows.hpp)
-extern "C" int sg_gate_spectrum_rows(sg_handle* h, const void* x_dev, int dtype, int64_t B, int64_t L, int64_t x_stride,
-                                     const int64_t* lengths, const void* xn_dev, int64_t Bn, int64_t Ln, int64_t xn_stride,
-                                     const int64_t* xn_lengths, void* spec_dev, float* mask_out_dev, void* stream) {
-  if (int rc = t_entry(h, "sg_gate_spectrum_rows")) return rc;
-  if (!x_dev || !spec_dev || (dtype != SG_F32 && dtype != SG_F64) || B < 1 || x_stride < L)
-    FAIL(h, SG_E_INVALID, "sg_gate_spectrum_rows: bad argument");
-  if (int rc = t_min_lengths(h, B, L, xn_dev, Bn, Ln)) return rc;
-  return sg::rw_spectrum(&h->rw, rg_ctx(h), h->p.n_movemean, x_dev, dtype, B, L, x_stride, lengths, xn_dev, Bn, Ln, xn_stride,
-                         xn_lengths, spec_dev, mask_out_dev, rw_budget(h), (hipStream_t)stream, &h->err);
-}
-
-extern "C" int sg_gate_spectrum_rows_backward(sg_handle* h, const void* grad_spec_dev, int dtype, int64_t B, int64_t L,
-                                              const int64_t* lengths, const float* mask_dev, void* grad_x_dev,
-                                              int64_t gx_stride, void* stream) {
-  if (int rc = t_entry(h, "sg_gate_spectrum_rows_backward")) return rc;
-  if (!grad_spec_dev || !grad_x_dev || !mask_dev || B < 1 || (dtype != SG_F32 && dtype != SG_F64) || gx_stride < L ||
-      L < 2 * (int64_t)h->W)
-    FAIL(h, SG_E_INVALID, "sg_gate_spectrum_rows_backward: bad argument");
-  return sg::rw_spectrum_backward(&h->rw, rg_ctx(h), grad_spec_dev, dtype, B, L, lengths, mask_dev, grad_x_dev, gx_stride,
-                                  rw_budget(h), (hipStream_t)stream, &h->err);
-}
-
-// TorchGate.gated_filterbank(lengths=): the rows pipeline with the features of the masked frame stored instead of the
-// frame (rows.hpp; the bank is sg_set_filterbank's)
-extern "C" int sg_gate_features_rows(sg_handle* h, const void* x_dev, int dtype, int64_t B, int64_t L, int64_t x_stride,
-                                     const int64_t* lengths, const void* xn_dev, int64_t Bn, int64_t Ln, int64_t xn_stride,
-                                     const int64_t* xn_lengths, int32_t power, int32_t take_log, double eps,
-                                     void* feat_dev, float* mask_out_dev, void* stream) {
-  if (int rc = t_entry(h, "sg_gate_features_rows")) return rc;
-  if (!x_dev || !feat_dev || (dtype != SG_F32 && dtype != SG_F64) || B < 1 || x_stride < L)
-    FAIL(h, SG_E_INVALID, "sg_gate_features_rows: bad argument");
-  if (int rc = features_args_ok(h, "sg_gate_features_rows", power, eps)) return rc;
-  if (int rc = t_min_lengths(h, B, L, xn_dev, Bn, Ln)) return rc;
-  return sg::rw_features(&h->rw, rg_ctx(h), h->p.n_movemean, feat_bank(h), x_dev, dtype, B, L, x_stride, lengths, xn_dev, Bn,
-                         Ln, xn_stride, xn_lengths, power, take_log != 0, eps, feat_dev, mask_out_dev, rw_budget(h),
-                         (hipStream_t)stream, &h->err);
-}
-
-extern "C" int sg_gate_features_rows_backward(sg_handle* h, const void* x_dev, int dtype, int64_t B, int64_t L,
-                                              int64_t x_stride, const int64_t* lengths, const void* grad_feat_dev,
-                                              const float* mask_dev, int32_t power, int32_t take_log, double eps,
-                                              void* grad_x_dev, int64_t gx_stride, void* stream) {
-  if (int rc = t_entry(h, "sg_gate_features_rows_backward")) return rc;
-  if (!x_dev || !grad_feat_dev || !grad_x_dev || !mask_dev || B < 1 || (dtype != SG_F32 && dtype != SG_F64) || x_stride < L ||
-      gx_stride < L)
-    FAIL(h, SG_E_INVALID, "sg_gate_features_rows_backward: bad argument");
-  if (int rc = features_args_ok(h, "sg_gate_features_rows_backward", power, eps)) return rc;
-  if (L < 2 * (int64_t)h->W) FAIL(h, SG_E_INVALID, "x must be bigger than %d", 2 * h->W);
-  return sg::rw_features_backward(&h->rw, rg_ctx(h), feat_bank(h), x_dev, dtype, B, L, x_stride, lengths, grad_feat_dev,
-                                  mask_dev, power, take_log != 0, eps, grad_x_dev, gx_stride, rw_budget(h),
-                                  (hipStream_t)stream, &h->err);
-}
-
-extern "C" int sg_debug_rows_batches(const sg_handle* h, int64_t* value) {
-  if (!h || !value) return SG_E_INVALID;
-  *value = sg::rw_last_batches(h->rw);
-  return SG_OK;
-}
-
-extern "C" int sg_debug_backward_route(const sg_handle* h, int64_t* value) {
-  if (!h || !value) return SG_E_INVALID;
-  *value = h->dbg_bwd_route;
-  return SG_OK;
-}
-
-// ---- banks of live streams: thin wrappers over stream.hip --------------------------------------------------------------
-struct sg_stream_bank {
-  sg_handle* h;
-  sg::StBank* b;
-};
-
-// the one create call behind the four entry points; `who` names the caller in the variant message
-static int stream_create(sg_handle* h, const sg_stream_desc& d, const char* who, sg_stream_bank** out) {
-  if (h->p.variant != SG_VARIANT_S) FAIL(h, SG_E_INVALID, "%s is a variant-S entry point", who);
-  sg::StBank* b = nullptr;
-  const sg::StAdaptive ad{d.forget, d.learn_frames};
-  const bool ns = d.kind == SG_STREAM_NONSTATIONARY;
-  int rc = sg::st_create(&b, rg_ctx(h), d.n_slots, d.channels, d.max_block, ns, ns ? d.lookahead_frames : 0,
-                         d.kind == SG_STREAM_ADAPTIVE ? &ad : nullptr, d.exact != 0, &h->err);
-  if (rc) return rc;
-  *out = new sg_stream_bank{h, b};
-  return SG_OK;
-}
-
-extern "C" int sg_stream_create_ex(sg_handle* h, const sg_stream_desc* desc, sg_stream_bank** out) {
-  if (!h || !out) return SG_E_INVALID;
-  if (!desc) FAIL(h, SG_E_INVALID, "sg_stream_create_ex: desc is null");
-  if (desc->kind != SG_STREAM_FIXED && desc->kind != SG_STREAM_NONSTATIONARY && desc->kind != SG_STREAM_ADAPTIVE)
-    FAIL(h, SG_E_INVALID, "sg_stream_create_ex: unknown kind %d", desc->kind);
-  return stream_create(h, *desc, "sg_stream_create_ex", out);
-}
-
-extern "C" int sg_stream_state_bytes_ex(const sg_handle* h, const sg_stream_desc* d, int64_t* bytes) {
-  if (!h || !d || !bytes || d->n_slots < 1 || d->channels < 1 || d->max_block < 1) return SG_E_INVALID;
-  const bool ns = d->kind == SG_STREAM_NONSTATIONARY, ad = d->kind == SG_STREAM_ADAPTIVE;
-  if ((!ns && !ad && d->kind != SG_STREAM_FIXED) || (ns && d->lookahead_frames < 0) || ns == (h->p.stationary != 0))
-    return SG_E_INVALID;
-  sg_handle* hm = const_cast<sg_handle*>(h);
-  *bytes = sg::st_state_bytes(rg_ctx(hm), ns, d->n_slots, d->channels, d->max_block, ns ? d->lookahead_frames : 0, ad, d->exact != 0);
-  return SG_OK;
-}
-
-extern "C" int sg_stream_create(sg_handle* h, int32_t n_slots, int32_t channels, int64_t max_block, sg_stream_bank** out) {
-  if (!h || !out) return SG_E_INVALID;
-  if (h->p.variant != SG_VARIANT_S) FAIL(h, SG_E_INVALID, "sg_stream_create is a variant-S entry point");
-  sg::StBank* b = nullptr;
-  int rc = sg::st_create(&b, rg_ctx(h), n_slots, channels, max_block, false, 0, nullptr, false, &h->err);
-  if (rc) return rc;
-  *out = new sg_stream_bank{h, b};
-  return SG_OK;
-}
-
-extern "C" int sg_stream_create_nonstationary(sg_handle* h, int32_t n_slots, int32_t channels, int64_t max_block,
-                                              int32_t lookahead_frames, sg_stream_bank** out) {
-  if (!h || !out) return SG_E_INVALID;
-  if (h->p.variant != SG_VARIANT_S) FAIL(h, SG_E_INVALID, "sg_stream_create_nonstationary is a variant-S entry point");
-  sg::StBank* b = nullptr;
-  int rc = sg::st_create(&b, rg_ctx(h), n_slots, channels, max_block, true, lookahead_frames, nullptr, false, &h->err);
-  if (rc) return rc;
-  *out = new sg_stream_bank{h, b};
-  return SG_OK;
-}
-
-extern "C" int sg_stream_state_bytes(const sg_handle* h, int32_t n_slots, int32_t channels, int64_t max_block,
-                                     int32_t lookahead_frames, int64_t* bytes) {
-  if (!h || !bytes || n_slots < 1 || channels < 1 || max_block < 1 || lookahead_frames < 0) return SG_E_INVALID;
-  sg_handle* hm = const_cast<sg_handle*>(h);
-  *bytes = sg::st_state_bytes(rg_ctx(hm), !h->p.stationary, n_slots, channels, max_block, h->p.stationary ? 0 : lookahead_frames);
-  return SG_OK;
-}
-
-extern "C" int sg_stream_create_adaptive(sg_handle* h, int32_t n_slots, int32_t channels, int64_t max_block, double forget,
-                                         int64_t learn_frames, sg_stream_bank** out) {
-  if (!h || !out) return SG_E_INVALID;
-  if (h->p.variant != SG_VARIANT_S) FAIL(h, SG_E_INVALID, "sg_stream_create_adaptive is a variant-S entry point");
-  sg::StBank* b = nullptr;
-  const sg::StAdaptive ad{forget, learn_frames};
-  int rc = sg::st_create(&b, rg_ctx(h), n_slots, channels, max_block, false, 0, &ad, false, &h->err);
-  if (rc) return rc;
-  *out = new sg_stream_bank{h, b};
-  return SG_OK;
-}
-
-extern "C" int sg_stream_state_bytes_adaptive(const sg_handle* h, int32_t n_slots, int32_t channels, int64_t max_block,
-                                              int64_t* bytes) {
-  if (!h || !bytes || n_slots < 1 || channels < 1 || max_block < 1 || !h->p.stationary) return SG_E_INVALID;
-  sg_handle* hm = const_cast<sg_handle*>(h);
-  *bytes = sg::st_state_bytes(rg_ctx(hm), false, n_slots, channels, max_block, 0, true);
-  return SG_OK;
-}
-
-extern "C" int sg_stream_noise_profile(sg_stream_bank* b, int32_t slot, double* thresh_host, int32_t n_bins, void* stream) {
-  if (!b) return SG_E_INVALID;
-  sg_handle* h = b->h;
-  if (!thresh_host) FAIL(h, SG_E_INVALID, "sg_stream_noise_profile: thresh_host is null");
-  if (n_bins != h->F) FAIL(h, SG_E_INVALID, "sg_stream_noise_profile: n_bins must be %d", h->F);
-  return sg::st_noise_profile(b->b, slot, thresh_host, (hipStream_t)stream, &h->err);
-}
-
-extern "C" int sg_stream_bank_emitted(const sg_stream_bank* b, int64_t n, int64_t* emitted) {
-  if (!b || !emitted || n < 0) return SG_E_INVALID;
-  *emitted = sg::st_bank_emitted(b->b, n);
-  return SG_OK;
-}
-
-extern "C" int sg_stream_destroy(sg_stream_bank* b) {
-  if (!b) return SG_OK;
-  sg::st_destroy(b->b);
-  delete b;
-  return SG_OK;
-}
-
-extern "C" int sg_stream_set_threshold(sg_stream_bank* b, const int32_t* slots, int32_t n_slots, const double* thresh_host,
-                                       int32_t n_bins, void* stream) {
-  if (!b) return SG_E_INVALID;
-  sg_handle* h = b->h;
-  if (n_bins != h->F) FAIL(h, SG_E_INVALID, "sg_stream_set_threshold: n_bins must be %d", h->F);
-  if (!thresh_host && !h->has_thresh) FAIL(h, SG_E_STATE, "no noise threshold set");
-  return sg::st_set_threshold(b->b, slots, n_slots, thresh_host ? nullptr : (const double*)h->thresh.p, thresh_host,
-                              (hipStream_t)stream, &h->err);
-}
-
-extern "C" int sg_stream_push(sg_stream_bank* b, const void* in_dev, int in_dtype, void* out_dev, int out_dtype,
-                              const sg_stream_rec* recs, int32_t n_recs, void* stream) {
-  if (!b) return SG_E_INVALID;
-  sg_handle* h = b->h;
-  // (the sample codes an exact bank takes beyond float32 / float64 are st_push's to check: it knows the bank)
-  if (n_recs < 0 || (n_recs > 0 && !recs) || !dtype_ok(in_dtype) || !dtype_ok(out_dtype))
-    FAIL(h, SG_E_INVALID, "sg_stream_push: bad argument (float32 / float64 buffers)");
-  return sg::st_push(b->b, in_dev, in_dtype, out_dev, out_dtype, recs, n_recs, (hipStream_t)stream, &h->err);
-}
-
-extern "C" int sg_stream_push_spectrum(sg_stream_bank* b, const void* in_dev, int in_dtype, void* out_dev, int out_dtype,
-                                       void* spec_dev, int spec_dtype, void* mask_dev, const sg_stream_rec* recs,
-                                       const sg_stream_spec_rec* spec_recs, int32_t n_recs, void* stream) {
-  if (!b) return SG_E_INVALID;
-  sg_handle* h = b->h;
-  if (n_recs < 0 || (n_recs > 0 && !recs) || !dtype_ok(in_dtype) || !dtype_ok(out_dtype))
-    FAIL(h, SG_E_INVALID, "sg_stream_push_spectrum: bad argument (float32 / float64 buffers)");
-  const sg::StSpecOut so{spec_dev, spec_dtype, mask_dev, spec_recs};
-  return sg::st_push(b->b, in_dev, in_dtype, out_dev, out_dtype, recs, n_recs, (hipStream_t)stream, &h->err, &so);
-}
-
-// the stream bank's own filterbank (sg_set_filterbank above is a variant-T entry point: t_entry refuses this handle)
-extern "C" int sg_stream_set_filterbank(sg_stream_bank* b, const float* fb_host, int32_t n_filters) {
-  if (!b) return SG_E_INVALID;
-  return sg::st_set_filterbank(b->b, fb_host, n_filters, &b->h->err);
-}
-
-extern "C" int sg_stream_push_features(sg_stream_bank* b, const void* in_dev, int in_dtype, void* out_dev, int out_dtype,
-                                       void* feat_dev, int feat_dtype, void* mask_dev, int32_t power, int32_t take_log,
-                                       double eps, double scale, const sg_stream_rec* recs,
-                                       const sg_stream_feat_rec* feat_recs, int32_t n_recs, void* stream) {
-  if (!b) return SG_E_INVALID;
-  sg_handle* h = b->h;
-  if (n_recs < 0 || (n_recs > 0 && !recs) || !dtype_ok(in_dtype) || !dtype_ok(out_dtype))
-    FAIL(h, SG_E_INVALID, "sg_stream_push_features: bad argument (float32 / float64 buffers)");
-  const sg::StFeatOut fo{feat_dev, feat_dtype, mask_dev, feat_recs, power, take_log, eps, scale};
-  return sg::st_push(b->b, in_dev, in_dtype, out_dev, out_dtype, recs, n_recs, (hipStream_t)stream, &h->err, nullptr, &fo);
-}
-
-extern "C" int sg_stream_bank_frames(const sg_stream_bank* b, int64_t n, int64_t* frames) {
-  if (!b || !frames || n < 0) return SG_E_INVALID;
-  *frames = sg::st_bank_frames(b->b, n);
-  return SG_OK;
-}
-
-extern "C" int sg_stream_reset(sg_stream_bank* b, const int32_t* slots, int32_t n_slots, void* stream) {
-  if (!b) return SG_E_INVALID;
-  return sg::st_reset(b->b, slots, n_slots, (hipStream_t)stream, &b->h->err);
-}
-
-extern "C" int sg_stream_emitted(const sg_handle* h, int64_t n, int64_t* emitted) {
-  if (!h || !emitted || n < 0) return SG_E_INVALID;
-  *emitted = sg::st_emitted(h->W, h->H, h->p.smooth_mask ? h->p.n_grad_time : 0, n);
-  return SG_OK;
-}
-
-extern "C" int sg_stream_counters(const sg_stream_bank* b, int32_t slot, int64_t* n, int64_t* emitted) {
-  if (!b || !n || !emitted) return SG_E_INVALID;
-  return sg::st_counters(b->b, slot, n, emitted, &b->h->err);
-}
-
-// the handle's part of a stream state's signature (the bank's part is stream.hip's)
-static sg_stream_head stream_signature(const sg_handle* h) {
-  sg_stream_head s{};
-  s.n_fft = h->p.n_fft; s.win_length = h->W; s.hop_length = h->H;
-  s.n_grad_freq = h->p.n_grad_freq; s.n_grad_time = h->p.n_grad_time; s.smooth_mask = h->p.smooth_mask ? 1 : 0;
-  s.prop_decrease = h->p.prop_decrease; s.n_std_thresh = h->p.n_std_thresh; s.top_db = h->p.top_db;
-  s.iir_b = h->p.iir_b; s.nonstat_thresh = h->p.nonstat_thresh; s.nonstat_slope = h->p.nonstat_slope;
-  return s;
-}
-
-extern "C" int sg_stream_export_bytes(const sg_stream_bank* b, int32_t slot, int64_t* bytes) {
-  if (!b || !bytes) return SG_E_INVALID;
-  return sg::st_export_bytes(b->b, slot, bytes, &b->h->err);
-}
-
-extern "C" int sg_stream_head_bytes(const sg_stream_head* head, int64_t* bytes) {
-  if (!head || !bytes) return SG_E_INVALID;
-  return sg::st_head_bytes(*head, bytes);
-}
-
-extern "C" int sg_stream_export(sg_stream_bank* b, const int32_t* slots, int32_t n_slots, void* blob_dev, const int64_t* offsets,
-                                sg_stream_head* heads_out, void* stream) {
-  if (!b) return SG_E_INVALID;
-  return sg::st_export(b->b, slots, n_slots, blob_dev, offsets, stream_signature(b->h), heads_out, (hipStream_t)stream, &b->h->err);
-}
-
-extern "C" int sg_stream_import(sg_stream_bank* b, const int32_t* slots, int32_t n_slots, const void* blob_dev,
-                                const int64_t* offsets, const sg_stream_head* heads_in, void* stream) {
-  if (!b) return SG_E_INVALID;
-  return sg::st_import(b->b, slots, n_slots, blob_dev, offsets, stream_signature(b->h), heads_in, (hipStream_t)stream, &b->h->err);
-}

@@ -23,6 +23,7 @@
 #include "feat.hpp"
 #include "fft_wave.hpp"
 #include "geom.hpp"
+#include "launch.hpp"
 #include "spec_team.hpp"
 
 namespace sg {
@@ -264,13 +265,6 @@ namespace {
 
 FeatRows rows_of(const View& v) { return {v.x, v.dtype, v.stride, v.N, v.unit0}; }
 
-// dynamic LDS beyond 64 KiB (many filters on the 16-team shapes) has to be asked for
-template <typename K>
-hipError_t allow_lds(K kern, size_t lds) {
-  if (lds <= 64 * 1024) return hipSuccess;
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-}
-
 // one launch per (sample type, power, log): the two switches are compile-time, so neither costs the frame loop a register
 template <int N, typename T, bool POW2, bool LOG>
 hipError_t fwd_launch(const View& v, const Geom& g, int64_t units, const void* tw, const float* win, const float* mask,
@@ -289,11 +283,9 @@ hipError_t bwd_launch(const View& v, const Geom& g, int64_t units, const void* t
   constexpr int NT = spec_nt<N>(), WAVES = spec_teams<N>();
   const size_t lds = (size_t)(N + WAVES * N) * sizeof(cx<float>) + (size_t)WAVES * ((LOG ? N + 1 : 0) + bank.M) * sizeof(float);
   const dim3 grid((unsigned)((g.T + WAVES * SPEC_FPW - 1) / (WAVES * SPEC_FPW)), (unsigned)units);
-  const hipError_t e = allow_lds(k_feat_bwd<N, WAVES, SPEC_FPW, NT, T, POW2, LOG>, lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((k_feat_bwd<N, WAVES, SPEC_FPW, NT, T, POW2, LOG>), grid, dim3(WAVES * NT), lds, st, rows_of(v), g,
-                     (const cx<float>*)tw, win, mask, bank, eps, (const T*)grad, seg);
-  return hipGetLastError();
+  // dynamic LDS beyond 64 KiB (many filters on the 16-team shapes) has to be asked for
+  return host::launch_lds_if(lds > 64 * 1024, k_feat_bwd<N, WAVES, SPEC_FPW, NT, T, POW2, LOG>, grid, dim3(WAVES * NT), lds, st, rows_of(v), g,
+                             (const cx<float>*)tw, win, mask, bank, eps, (const T*)grad, seg);
 }
 
 #define FEAT_SWITCH(fn, N, ...)                                                          \

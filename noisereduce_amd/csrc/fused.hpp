@@ -13,6 +13,7 @@
 #pragma once
 #include "kernels.hpp"
 #include "fastpath.hpp"
+#include "limits.hpp"
 
 namespace sg {
 
@@ -511,23 +512,12 @@ __global__ __launch_bounds__(256) void k_smooth_bits(const unsigned long long* _
 // phase 2 walks one output column per thread over the whole tile with batched LDS reads.
 // Frames outside [t_begin, t_end) are neither read as outputs nor written.  The tile height tt (<= SM2_TT frames) is a
 // launch parameter: long frames (n_fft = 4096: 2049 bins per row) take lower tiles so that the tile fits the LDS.
-constexpr int SM2_TT = 64;
-constexpr int SM2_THREADS = 576;
-// (round 5) tallest tile tried for a row of F bins: short rows take tall tiles (fewer halo rows per output -- the time
-// half-width of n_fft = 256 at 48 kHz is 37 frames: 64-frame tiles ran phase 1 over 2.2 x the rows) and split them into
-// segments for phase 2
-__host__ __device__ inline int smooth2_tt_max(int F) { return F <= 160 ? 256 : (F <= 320 ? 128 : SM2_TT); }
 
 __device__ __forceinline__ unsigned long long funnel_r(unsigned long long lo, unsigned long long hi, int sh) {
   // bits [sh, sh+64) of the 128-bit value hi:lo, 0 <= sh < 64
   return sh == 0 ? lo : ((lo >> sh) | (hi << (64 - sh)));
 }
 
-__host__ __device__ inline int smooth2_pitch(int F) { return ((F + 3) & ~3) + 4 * ((F + 31) / 32) + 4; }
-__host__ __device__ inline size_t smooth2_cf_bytes(int rows, int F, int ct_size) {
-  size_t b = (size_t)rows * smooth2_pitch(F) * ct_size;
-  return (b + 15) & ~(size_t)15;
-}
 
 template <typename CT>
 __global__ __launch_bounds__(SM2_THREADS) void k_smooth_bits2(const unsigned long long* __restrict__ bits, Geom g,

@@ -2,9 +2,8 @@
 // __graft_entry__.build() compiles it beside api.hip (four team sizes x two precisions x eight radix bodies each).
 #include <algorithm>
 #include <cstdlib>
-#include <map>
-#include <mutex>
 #include "mixed_kernels.hpp"
+#include "launch.hpp"
 
 namespace sg {
 
@@ -49,20 +48,6 @@ void mr_pass_tables(const MrPlan& pl, double* out) {
 }
 
 namespace {
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (device, kernel, size)  (api.hip: set_lds)
-hipError_t mr_set_lds(const void* kern, size_t bytes) {
-  static std::mutex mu;
-  static std::map<std::pair<int, const void*>, size_t> done;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = done.find({dev, kern});
-  if (it != done.end() && it->second >= bytes) return hipSuccess;
-  hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e == hipSuccess) done[{dev, kern}] = bytes;
-  return e;
-}
-
 // Threads per frame (a "team") and frames in flight per workgroup.  A pass of radix R has N / R butterflies; a team of NT
 // lanes takes ceil(N / R / NT) sweeps of NT lanes over them: the team size with the fewest padded lane-slots over all
 // passes wins (N = 200 = 8 5 5: 25 + 40 + 40 butterflies are 192 slots of a 64-lane team, 128 of a 16-lane one), smaller
@@ -95,13 +80,8 @@ MrShape mr_team(const MrPlan& pl, size_t cx_bytes, size_t pad_len, int sweeps, s
 }
 template <typename K, typename... Args>
 hipError_t mr_go(K kern, const MrShape& s, const Geom& g, int64_t units, int fpw, hipStream_t st, Args... args) {
-  if (s.lds > 65536) {
-    hipError_t e = mr_set_lds(reinterpret_cast<const void*>(kern), s.lds);
-    if (e != hipSuccess) return e;
-  }
   dim3 grid((unsigned)((g.T + (int64_t)s.teams * fpw - 1) / ((int64_t)s.teams * fpw)), (unsigned)units);
-  hipLaunchKernelGGL(kern, grid, dim3(s.teams * s.NT), s.lds, st, args..., fpw);
-  return hipGetLastError();
+  return host::launch_lds_if(s.lds > 65536, kern, grid, dim3(s.teams * s.NT), s.lds, st, args..., fpw);
 }
 // few units (the noise clip): one frame per team so that the grid still covers the chip
 int mr_fpw(const MrShape& s, const Geom& g, int64_t units) {

@@ -29,18 +29,11 @@
 // every other resident workgroup finishes and frees its slot.
 #pragma once
 #include "fastpath.hpp"
+#include "limits.hpp"
 
 namespace sg {
 namespace fast {
 
-constexpr int OP_XW = 9;                 // 64-bit words per frame row (513 bins)
-constexpr int OP_TILE_WORDS = 16 * OP_XW * 2;  // payload of one tile: 288 tagged granules = 2304 B (18 x 128 B)
-constexpr int OP_MAX_NT = 16;            // neighbours hold 16 frames each
-constexpr int OP_KP = 528;               // K row pitch (uint16 entries) of a wave's private K tile
-// The kernel's nine constant tables live in ONE device buffer at fixed offsets (OnePassArgs::tab): one base pointer in the
-// kernel arguments instead of nine -- 16 scalar registers fewer in a kernel that spilled 44 of them.
-constexpr int OP_TAB_WIN = 0, OP_TAB_WSQ = 4096, OP_TAB_INVN = 8192, OP_TAB_TW512 = 9216, OP_TAB_TW1024 = 13312,
-              OP_TAB_WIN64 = 17408, OP_TAB_TW64 = 25600, OP_TAB_MCONST = 33792, OP_TAB_EXP8 = 35328, OP_TAB_BYTES = 37376;
 
 #ifndef OP_LATE_ARGS
 #define OP_LATE_ARGS 1   // 1: the epilogue re-reads its arguments from the kernel-argument segment (see "LATE ARGUMENTS" in the kernel)

@@ -18,7 +18,7 @@
 
 namespace sg {
 
-// what the table-driven paths (ragged.hip, rows.hip, stream.hip) need of a handle (filled by api.hip: sg_handle stays private to that translation unit)
+// what the table-driven paths (ragged.hip, rows.hip, stream.hip) need of a handle (filled by handle.hpp's rg_ctx: sg_handle stays private to the host units that include that header)
 struct RgCtx {
   int n, N, W, H, F, FS, padL;       // n_fft, n_fft / 2, win_length, hop, bins, padded bins, zero extension W / 2
   double mag_scale;                  // 1 / sum(w)

@@ -35,6 +35,7 @@
 // Sums run in float64, so their own rounding does not count.  Ambiguous: ~0.3 % of the (row, band) pairs of noise + tone.
 #pragma once
 #include "fastpath.hpp"
+#include "limits.hpp"
 #include "fused.hpp"   // funnel_r
 
 namespace sg {
@@ -48,7 +49,6 @@ namespace fast {
 constexpr int RG_FRAMES = 64;
 constexpr int RG_NTMAX = 16;             // time half-width of the smoothing filter
 constexpr int RG_NFMAX = 30;             // frequency half-width (128-bit sliding window)
-constexpr int RG_PP = 528;               // float pitch of the power tile: rows 4w+g of a wave land on disjoint bank quarters
 constexpr int RG_WP = 11;                // 64-bit words per bit row: 9 + one zero word on each side
 constexpr int RG_FP = 584;               // uint16 pitch of the count / K tile: column(f) = f + 4 (f / 32)  (smooth2_pitch(513))
 constexpr int RG_ROWS_MAX = 64 + 2 * RG_NTMAX;

@@ -134,12 +134,7 @@ template <int N>
 hipError_t launch_feat_kernel(void (*kernel)(RwArgs, RwFeat), int64_t ntiles, size_t extra, hipStream_t st, const RwArgs& A,
                               const RwFeat& Q) {
   const size_t lds = (size_t)(N + lpn<double>(N)) * sizeof(cx<double>) + extra;
-  if (lds > 65536) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(kernel, tile_grid(ntiles), dim3(tile_nt<N>()), lds, st, A, Q);
-  return hipGetLastError();
+  return host::launch_lds_if(lds > 65536, kernel, tile_grid(ntiles), dim3(tile_nt<N>()), lds, st, A, Q);
 }
 // g'[M] and, with log, p[N + 1], in doubles: 24584 bytes at M = 1024, N = 2048 (94216 with the transform's, under 160 KB)
 size_t feat_bwd_lds(int N, const RwFeat& Q) { return ((size_t)Q.bank.M + (Q.take_log ? (size_t)N + 1 : 0)) * sizeof(double); }

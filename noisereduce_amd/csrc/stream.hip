@@ -647,12 +647,7 @@ namespace {
 template <int N>
 hipError_t launch_feat_kernel(void (*kernel)(StArgs, StFeat), int64_t ntiles, hipStream_t st, const StArgs& A, const StFeat& Q) {
   const size_t lds = (size_t)(N + lpn<double>(N)) * sizeof(cx<double>) + ((size_t)(N + 1) * sizeof(double) + 15) / 16 * 16;
-  if (lds > 65536) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(kernel, tile_grid(ntiles), dim3(tile_nt<N>()), lds, st, A, Q);
-  return hipGetLastError();
+  return host::launch_lds_if(lds > 65536, kernel, tile_grid(ntiles), dim3(tile_nt<N>()), lds, st, A, Q);
 }
 }  // namespace
 

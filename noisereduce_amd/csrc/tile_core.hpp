@@ -24,6 +24,7 @@
 #include "geom.hpp"
 #include "thresh.hpp"
 #include "ragged.hpp"
+#include "launch.hpp"
 
 namespace sg {
 
@@ -430,12 +431,7 @@ inline dim3 tile_grid(int64_t ntiles) { return dim3((unsigned)std::max<int64_t>(
 template <int N, class Args>
 hipError_t launch_tile_kernel(void (*kernel)(Args), int64_t ntiles, hipStream_t st, const Args& A) {
   const size_t lds = (size_t)(N + lpn<double>(N)) * sizeof(cx<double>);
-  if (lds > 65536) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(kernel, tile_grid(ntiles), dim3(tile_nt<N>()), lds, st, A);
-  return hipGetLastError();
+  return host::launch_lds_if(lds > 65536, kernel, tile_grid(ntiles), dim3(tile_nt<N>()), lds, st, A);
 }
 // a kernel without dynamic LDS, one workgroup of `block` threads per tile
 template <class Args>

@@ -3,8 +3,10 @@
 # __graft_entry__.build(); run variants on the GPU box with
 #   for f in noisereduce_amd/_ab/*.so; do SG_LIB_PATH=$PWD/$f python tools/time_onepass.py; done
 # usage: tools/ab_build.sh <tag> [extra hipcc flags]
-# The extra flags go to the units named in AB_UNITS (default: api.hip, which holds every gate kernel); the other units'
-# objects are built once without them into noisereduce_amd/_ab/obj/ and reused while newer than everything they include.
+# The extra flags go to the units named in AB_UNITS (default: api.hip, the gate engine: the one unit that includes the gate's
+# kernel headers; create.hip, debug.hip and shims.hip are host code only, the table-driven paths have units of their own);
+# the other units' objects are built once without them into noisereduce_amd/_ab/obj/ and reused while newer than
+# everything they include.
 set -e
 cd "$(dirname "$0")/.."
 TAG=$1; shift

@@ -5,7 +5,9 @@ gfx950 does not wait before a barrier by itself; the compiler normally emits the
 __syncthreads()), but round 6 found one path -- `LDS store; continue;` to a barrier at a loop head -- where it did not
 (onepass.hpp, persistent loop).  Forward data-flow over basic blocks, per kernel.
 
-  hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-slp-vectorize -I noisereduce_amd/csrc --cuda-device-only -S noisereduce_amd/csrc/api.hip -o /tmp/api.s
+  for u in api mixed nonstat_mask ragged rows rows_feat spec feat stream; do    # (create, debug and shims hold no kernels)
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-slp-vectorize -I noisereduce_amd/csrc --cuda-device-only -S noisereduce_amd/csrc/$u.hip -o /tmp/$u.s
+  done
   python tools/audit_barrier_waits.py /tmp/api.s [more .s files]
 """
 import re, sys
