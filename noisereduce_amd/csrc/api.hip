@@ -1633,6 +1633,21 @@ static int stage_onepass(sg_handle* h, const View& v, const View& vx, const Geom
     Q.tc = C.fs.tc;
     Q.alim = C.fs.lazy ? (unsigned*)h->alim.p : nullptr;
     Q.total_tiles = C.total;
+    {
+      // the launch plan (onepass_plan.hpp): quotients as multiply-highs, the interior units and the tile ranges in which
+      // blk_vec and tile_fast hold for them, folded source and output addresses
+      fast::OpPlanIn I{};
+      const View& w = Q.A.view;
+      const OutMap& m = Q.A.om;
+      I.x = (uint64_t)(uintptr_t)w.x; I.out = (uint64_t)(uintptr_t)m.out;
+      I.in_dtype = w.dtype; I.out_dtype = m.dtype; I.normalize = Q.A.normalize;
+      I.stride = w.stride; I.lo = w.lo; I.hi = w.hi; I.cs = w.cs; I.pad = w.pad; I.Lp = w.Lp; I.c0 = w.c0; I.unit0 = w.unit0;
+      I.n_chunks = w.n_chunks;
+      I.ostride = m.stride; I.p0 = m.p0; I.p1 = m.p1; I.g_step = m.g_step; I.g0 = m.g0; I.g_lo = m.g_lo; I.g_hi = m.g_hi;
+      I.padL = Q.A.g.padL; I.T = Q.A.g.T; I.Lout = Q.A.g.Lout; I.h_begin = Q.A.h_begin; I.h_end = Q.A.h_end;
+      I.n_tiles = Q.A.n_tiles; I.scan_q = Q.scan_q;
+      Q.plan = fast::op_plan_build(I);
+    }
     // persistent workgroups (onepass.hpp "PERSIST"): the lazy first launch only -- its compare constants do not depend on the unit
     persist = C.fs.lazy && h->tile_order == 0 && !(h->lose_now & 3u) && C.total >= 2;
     if (persist && h->n_cu == 0) {

@@ -30,6 +30,7 @@
 #pragma once
 #include "fastpath.hpp"
 #include "limits.hpp"
+#include "onepass_plan.hpp"
 
 namespace sg {
 namespace fast {
@@ -110,6 +111,7 @@ struct OnePassArgs {
   unsigned* alim;
   int scan_q;                 // in-kernel floor test: samples of the unit window's unstaged part that each tile scans
   unsigned total_tiles;       // units * (n_tiles + 2): PERSIST workgroups draw tickets until they get one >= this
+  OpPlan plan;                // what a tile's coordinates need that does not depend on the tile (onepass_plan.hpp; stage_onepass fills it)
 #if OP_TRACE
   unsigned* trace;                   // [workgroups][4 waves][16] shader cycles per phase (slot 15 = 1: tile completed): development builds
 #endif
@@ -211,6 +213,14 @@ __device__ __forceinline__ int op_xor_lanes(int v) {
 // neighbours' flags, 8 no exact refinement, 16 no wait for the previous tile's trailing hops
 #ifndef OP_ABLATE
 #define OP_ABLATE 0
+#endif
+// OP_PLAN_SITES: the places of the PERSIST instantiations that evaluate a ticket against the launch plan (onepass_plan.hpp)
+// instead of deriving the tile's coordinates field by field: 1 loop top (u, jt, row, chunk by multiply-high), 4 prefetch_next,
+// 16 epilogue.  The publish stage and seam_issue measured below 1 % of a step as ceilings and are left alone; the loop top keeps
+// its own tile_src: from the plan it cost 30 scalar registers and time (profiles/onepass_tile_plan.txt; the builds that
+// measured both: tools/experiments/onepass_plan_ablate.patch).
+#ifndef OP_PLAN_SITES
+#define OP_PLAN_SITES 21
 #endif
 // OP_TRACE (development only): per-phase shader-clock stamps of every non-halo wave, summed into P.trace (tools/
 // trace_onepass.sh): where a tile's lifetime goes
@@ -412,6 +422,24 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
     }
     return S;
   };
+  // the same for a tile the launch plan knows as blk_vec (an interior unit's: nothing of the view is read)
+  static_assert(NF == OP_PLAN_NF && SPAN == OP_PLAN_SPAN && SCAN_REG * WAVES * 64 == OP_PLAN_SCAN_MAX, "onepass_plan.hpp");
+  [[maybe_unused]] auto tile_src_plan = [](const OpPlan& L, const OpTile& tl) -> TileSrc {
+    TileSrc S;
+    const float* base = (const float*)(const __attribute__((address_space(1))) float*)(uintptr_t)L.src;
+    S.sp = base + op_plan_src_off(L, tl);
+    S.blk_vec = true;
+    S.s0b = (int64_t)L.s0b0 + (int64_t)tl.jt * OP_PLAN_TILE;
+    const OpScan sc = op_plan_scan(L, tl);
+    S.sc_lo = 0;
+    S.sc_last = L.sc_last;
+    S.sc_lenA = L.sc_lenA;
+    S.sc_c0 = sc.c0;
+    S.sc_c1 = sc.c1;
+    S.sc_base = sc.has ? base + sc.off : nullptr;
+    S.sc_n1 = sc.has ? (int)(sc.c1 - sc.c0) - 1 : 0;
+    return S;
+  };
   // loop-carried (PERSIST): the samples of the tile at hand, issued by the previous iteration
   float q[NQ];
   float sc[SCAN_REG];
@@ -547,7 +575,6 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
   const int lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, c = lane & 15;
   const unsigned tk_slot = PERSIST ? 4u + (iter & 1u) : 0u;
-  const int ntt = A.n_tiles + 2;                 // tiles per unit incl. one decide-only halo tile per side
   const unsigned ticket = PERSIST ? (unsigned)__builtin_amdgcn_readfirstlane((int)s_misc[tk_slot]) : s_misc[0];
 #if OP_TILECOUNT == 2
   // (diagnosis) does the late read of total_tiles still equal what the workgroup saw when it started?  Reported through the err pointer
@@ -599,13 +626,29 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
   if (lane == 0) t_slot_[14] = (blockIdx.x + 1u) | (iter << 16);   // who took the ticket up (sg_debug_counter 8 reads it after a lost hand-off)
 #endif
   OP_STAMP(0);   // tables + ticket
-  const int64_t u = ticket / (unsigned)ntt;
-  const int jt = (int)(ticket % (unsigned)ntt) - 1;   // -1 and n_tiles: halo tiles
-  const bool halo_tile = jt < 0 || jt >= A.n_tiles;
-  // (32-bit division: unit indices fit, and a 64-bit divide is ~150 instructions of every workgroup's prologue)
-  const unsigned gu = (unsigned)(A.view.unit0 + u), nch = (unsigned)A.view.n_chunks;
-  const int64_t row = gu / nch;
-  const int64_t chunk = A.view.c0 + gu % nch;
+  [[maybe_unused]] int ntt;   // tiles per unit incl. one decide-only halo tile per side
+  int64_t u, row, chunk;
+  int jt;                     // -1 and n_tiles: halo tiles
+  bool halo_tile;
+  if constexpr (PERSIST && (OP_PLAN_SITES & 1) != 0) {
+    // the launch plan: both quotients by multiply-high and shifts
+    const OpTile tl = op_plan_tile(P.plan, ticket);
+    ntt = (int)P.plan.ntt;
+    u = tl.u;
+    jt = tl.jt;
+    halo_tile = jt < 0 || jt >= ntt - 2;
+    row = tl.row;
+    chunk = P.plan.c0 + tl.k;
+  } else {
+    ntt = A.n_tiles + 2;
+    u = ticket / (unsigned)ntt;
+    jt = (int)(ticket % (unsigned)ntt) - 1;
+    halo_tile = jt < 0 || jt >= A.n_tiles;
+    // (32-bit division: unit indices fit, and a 64-bit divide is ~150 instructions of every workgroup's prologue)
+    const unsigned gu = (unsigned)(A.view.unit0 + u), nch = (unsigned)A.view.n_chunks;
+    row = gu / nch;
+    chunk = A.view.c0 + gu % nch;
+  }
   // Floor flags of the unit.  lazy (P.alim set): the first launch assumes "not live" and runs the floor test on the
   // samples it stages (below); the second launch (REDO) serves exactly the units whose test fired.
   const bool lazy = PERSIST || P.alim != nullptr;
@@ -1270,12 +1313,20 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
     // thread -- keeps the previous tile's values alive through a whole iteration, and the allocator then parks all 24
     // in scratch: a store that waits for the very load it was meant to hide)
     const bool n_live = nx < Pn.total_tiles;
-    const unsigned n_ntt = (unsigned)(Pn.A.n_tiles + 2);
     const unsigned n_tk = n_live ? nx : 0u;
-    const unsigned n_u = n_tk / n_ntt;
-    const int n_jt = (int)(n_tk % n_ntt) - 1;
-    const unsigned n_gu = (unsigned)(Pn.A.view.unit0 + n_u), n_nch = (unsigned)Pn.A.view.n_chunks;
-    const TileSrc N = tile_src(Pn, (int64_t)(n_gu / n_nch), Pn.A.view.c0 + n_gu % n_nch, n_jt, true);
+    TileSrc N;
+    if constexpr ((OP_PLAN_SITES & 4) != 0) {
+      // the launch plan: an interior unit's tile is base + strides and two range compares, nothing of the view is read
+      const OpTile nl = op_plan_tile(Pn.plan, n_tk);
+      if (op_plan_blk_vec(Pn.plan, nl)) N = tile_src_plan(Pn.plan, nl);
+      else N = tile_src(Pn, (int64_t)nl.row, Pn.plan.c0 + nl.k, nl.jt, true);
+    } else {
+      const unsigned n_ntt = (unsigned)(Pn.A.n_tiles + 2);
+      const unsigned n_u = n_tk / n_ntt;
+      const int n_jt = (int)(n_tk % n_ntt) - 1;
+      const unsigned n_gu = (unsigned)(Pn.A.view.unit0 + n_u), n_nch = (unsigned)Pn.A.view.n_chunks;
+      N = tile_src(Pn, (int64_t)(n_gu / n_nch), Pn.A.view.c0 + n_gu % n_nch, n_jt, true);
+    }
     // NO BRANCH around the loads: at the join with a path that issued none the compiler has to assume the least number of loads
     // behind n4, and the epilogue's wait for n4 is vmcnt(0) again -- for the whole span.  A next tile that stages sample by
     // sample (a unit's edge, a halo tile: two in 149) or no tile at all never reads q / sc: its loads go to the constant
@@ -1381,14 +1432,30 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
   const int64_t e_T = OP_KARG(int64_t, A.g.T), e_Lout = OP_KARG(int64_t, A.g.Lout);
 #if OP_LATE_ARGS
   const unsigned e_ticket = (unsigned)__builtin_amdgcn_readfirstlane((int)s_misc[tk_slot]);
-  const unsigned e_ntt = (unsigned)(e_ntiles + 2);
-  const int64_t e_u = e_ticket / e_ntt;
-  const int e_jt = (int)(e_ticket % e_ntt) - 1;
-  const unsigned e_gu = (unsigned)(OP_KARG(int64_t, A.view.unit0) + e_u), e_nch = (unsigned)OP_KARG(int32_t, A.view.n_chunks);
-  const int64_t e_row = e_gu / e_nch;
-  const int64_t e_chunk = OP_KARG(int64_t, A.view.c0) + e_gu % e_nch;
+  constexpr bool PLAN16 = PERSIST && (OP_PLAN_SITES & 16) != 0;
+  [[maybe_unused]] const OpPlan& e_plan = *reinterpret_cast<const OpPlan*>((const char*)kp4 + __builtin_offsetof(OnePassArgs, plan));
+  [[maybe_unused]] OpTile el{};
+  int64_t e_u, e_row, e_chunk;
+  int e_jt;
+  if constexpr (PLAN16) {
+    el = op_plan_tile(e_plan, e_ticket);
+    e_u = el.u;
+    e_jt = el.jt;
+    e_row = el.row;
+    e_chunk = e_plan.c0 + el.k;
+  } else {
+    const unsigned e_ntt = (unsigned)(e_ntiles + 2);
+    e_u = e_ticket / e_ntt;
+    e_jt = (int)(e_ticket % e_ntt) - 1;
+    const unsigned e_gu = (unsigned)(OP_KARG(int64_t, A.view.unit0) + e_u), e_nch = (unsigned)OP_KARG(int32_t, A.view.n_chunks);
+    e_row = e_gu / e_nch;
+    e_chunk = OP_KARG(int64_t, A.view.c0) + e_gu % e_nch;
+  }
   const int64_t e_tf = e_hbegin - 3 + (int64_t)e_jt * NF;
 #else
+  constexpr bool PLAN16 = false;
+  [[maybe_unused]] const OpPlan& e_plan = P.plan;
+  [[maybe_unused]] const OpTile el{};
   const int64_t e_u = u, e_row = row, e_chunk = chunk, e_tf = tf_tile;
   const int e_jt = jt;
   [[maybe_unused]] const unsigned e_ticket = ticket;
@@ -1411,12 +1478,23 @@ __global__ __launch_bounds__(WAVES * 64, OP_OCC) void k_gate_onepass(OnePassArgs
   {
     const int64_t pb0 = e_tf * 256 - e_padL;
     const int64_t gi00 = e_chunk * e_gstep + (pb0 - e_p0);
-    float* dbase = (float*)e_out + (e_row * e_ostride + gi00 - e_g0);
+    float* dbase;
+    bool tile_fast = false;
+    if constexpr (PLAN16) {
+      // an interior unit's tile inside the plan's range: the flag is one compare, the address base + strides -- none of the
+      // output map's fields is waited for (they serve the tiles below: a unit's edge, another sample type, unaligned rows)
+      tile_fast = op_plan_tile_fast(e_plan, el);
+    }
+    if (tile_fast) {
+      dbase = (float*)(__attribute__((address_space(1))) float*)(uintptr_t)e_plan.dst + op_plan_dst_off(e_plan, el);
+    } else {
+      dbase = (float*)e_out + (e_row * e_ostride + gi00 - e_g0);
+      tile_fast = e_odtype == 0 && e_normalize && e_tf >= 3 && e_tf + NF + 2 < e_T &&
+                  e_tf >= e_hbegin && e_tf + NF + 2 < e_hend && pb0 >= e_p0 &&
+                  pb0 + NF * 256 <= e_p1 && pb0 + NF * 256 <= e_Lout && gi00 >= e_glo &&
+                  gi00 + NF * 256 <= e_ghi && (reinterpret_cast<uintptr_t>(dbase) & 15) == 0 && WAVES == 4;
+    }
     float* dst0 = dbase + s4;
-    const bool tile_fast = e_odtype == 0 && e_normalize && e_tf >= 3 && e_tf + NF + 2 < e_T &&
-                           e_tf >= e_hbegin && e_tf + NF + 2 < e_hend && pb0 >= e_p0 &&
-                           pb0 + NF * 256 <= e_p1 && pb0 + NF * 256 <= e_Lout && gi00 >= e_glo &&
-                           gi00 + NF * 256 <= e_ghi && (reinterpret_cast<uintptr_t>(dbase) & 15) == 0 && WAVES == 4;
     if (tile_fast) {
       constexpr int R = WAVE_CX_H * 2;
       auto ld4 = [&](int off) { return *reinterpret_cast<const float4*>(&fr[off + s4]); };
