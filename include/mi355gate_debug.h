@@ -60,6 +60,11 @@ SG_API int sg_debug_range(const sg_handle* h, int64_t range[2]);
  * sg_process_batch), 0 when there were none (host bookkeeping, no synchronisation; no kernel reads or writes it). */
 #define SG_STATS_THREE_LAUNCH 1 /* k_stft<double>, k_colstats1, k_colstats1_final */
 #define SG_STATS_TWO_LAUNCH 2   /* k_noise_moments (transform + slice partials), k_colstats1_final over its slices */
+/* which = 20: the form of the floor fix-up of the last one-pass gate call on the handle (the launches behind the gate launch of
+ * a call whose floor test ran in the gate kernel, SG_OPT_FLOOR_TEST), 0 when that call took the a-priori test or there was
+ * none (host bookkeeping, no synchronisation; no kernel reads or writes it). */
+#define SG_FLOOR_ONE_LAUNCH 1 /* k_floor_fix: band maxima and the second gate pass of the chunks that reported, one launch */
+#define SG_FLOOR_TWO_LAUNCH 2 /* k_stft_bits<max>, then the gate's REDO instantiation */
 SG_API int sg_debug_counter(sg_handle* h, int32_t which, int64_t* value, void* stream);
 /* what = 5: the stationary gate's compare constants as the last sg_noise_stats call left them: T2 double[n_bins] (power-domain
  * threshold per band), then the 64 words of the floor-test block (word 2 + b: bit pattern of band block b's float bound on
@@ -90,8 +95,9 @@ SG_API int sg_debug_backward_route(const sg_handle* h, int64_t* value);
 #define SG_OPT_FORCE_NOLEAN 5   /* value != 0: apply kernel with full-size LDS slices and stored frames */
 #define SG_OPT_FORCE_SPLIT 6    /* value != 0: default geometry: decide / smooth / apply as three kernels instead of the one-pass kernel; non-stationary gate: the serial tile chain (k_iir_comb + k_iir_chain) instead of k_iir_chain_par */
 #define SG_OPT_INJECT_HANDOFF_FAULT 7 /* tests: the next launch with in-launch hand-offs reports `value` (bits 0..2) as lost hand-offs
-                                       * (the output is fine); bits 3..5 make the KERNEL lose its hand-offs (3 or 4: the one-pass
-                                       * gate, 5: the fused apply): the producers' tags are never accepted and the polls give up --
+                                       * (the output is fine); bits 3..6 make the KERNEL lose its hand-offs (3 or 4: the one-pass
+                                       * gate, 5: the fused apply, 6: only the one-launch floor fix-up's wait for a chunk's band maxima,
+                                       * which bits 3 and 4 lose too): the producers' tags are never accepted and the polls give up --
                                        * the bounded-poll timeout path itself: error word set by the kernel, affected hops NaN */
 #define SG_OPT_FORCE_NOROWGATE 10 /* variant T, stationary, rows of <= 64 frames: 0 (default) = the one-kernel row gate for calls of >= 160
                                    * rows, the four-kernel path (float64 transform of every frame, k_row_decide, k_smooth_bits2,
@@ -123,6 +129,9 @@ SG_API int sg_debug_backward_route(const sg_handle* h, int64_t* value);
                                       * k_colstats1_final), also where k_noise_moments + k_colstats1_final would do (variant S, one clip of
                                       * >= 512 frames at n_fft = 256 / 512 / 1024 / 2048, at most 256 slices): A/B and parity of the two.
                                       * Thresholds differ by summation order only */
+#define SG_OPT_FLOOR_TWO_LAUNCH 18 /* value != 0: the floor fix-up of a one-pass gate call always as two launches (k_stft_bits<max>, then
+                                    * the gate's REDO instantiation), also where the n_fft = 1024 gate would enqueue k_floor_fix once: A/B
+                                    * and parity of the two.  Bit-identical output; n_fft = 512 / 256 / 2048 always take the two launches */
 #define SG_OPT_FORCE_NOFAST 2  /* value != 0: keep the bit-mask stages but use the general apply kernels */
 
 /* ---- per-kernel timing (bench.py's roofline leg) ------------------------------------- */

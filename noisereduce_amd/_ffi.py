@@ -39,6 +39,7 @@ SG_OPT_FLOOR_TEST = 13
 SG_OPT_TILE_ORDER = 15
 SG_OPT_EXACT_MATERIALISED = 16
 SG_OPT_STATS_THREE_LAUNCH = 17
+SG_OPT_FLOOR_TWO_LAUNCH = 18
 SG_OPT_FORCE_UNFUSED = 1
 SG_OPT_FORCE_NOFAST = 2
 SG_BWD_ROW, SG_BWD_FAST, SG_BWD_REG, SG_BWD_OLA, SG_BWD_ROWS = 1, 2, 3, 4, 5
@@ -1084,6 +1085,12 @@ class Gate:
         """The form of the last noise statistics of fewer than 16 units on this handle: 1 = k_stft<double> + k_colstats1 +
         k_colstats1_final, 2 = k_noise_moments + k_colstats1_final, 0 = none yet -- sg_debug_counter(19), host bookkeeping only."""
         return self.debug_counter(19)
+
+    def floor_route(self):
+        """The floor fix-up of the last one-pass gate call on this handle: 1 = one launch (k_floor_fix), 2 = two launches
+        (k_stft_bits<max> + the gate's REDO instantiation, SG_OPT_FLOOR_TWO_LAUNCH), 0 = that call took the a-priori floor
+        test, or none yet -- sg_debug_counter(20), host bookkeeping only."""
+        return self.debug_counter(20)
 
     def gate_consts(self):
         """``(T2, alim)`` of the last noise_stats call: the power-domain compare constant per band (n_bins,) float64 and the

@@ -802,6 +802,7 @@ static int handoff_next_epoch(sg_handle* h, hipStream_t st) {
   if (++h->epoch == 0) {  // wrapped: tags of 2^32 launches ago could alias
     if (h->xbits.p) HIPCHK(h, hipMemsetAsync(h->xbits.p, 0, h->xbits.bytes, st));
     if (h->xpart.p) HIPCHK(h, hipMemsetAsync(h->xpart.p, 0, h->xpart.bytes, st));
+    if (h->farrive.p) HIPCHK(h, hipMemsetAsync(h->farrive.p, 0, h->farrive.bytes, st));
     h->epoch = 1;
     if (h->err_host) h->err_host[1] = 0u;   // the floor-test stamp is an epoch too
   }
@@ -834,7 +835,7 @@ static int handoff_prepare(sg_handle* h, hipStream_t st) {
   h->lose_now = 0;
   if (h->inject_fault) {  // test hook: this launch "loses" a hand-off
     *h->err_host = h->inject_fault & 7u;          // bits 0..2: reported only (the output is fine)
-    h->lose_now = (h->inject_fault >> 3) & 7u;    // bits 3..5: lost INSIDE the kernel (the output is poisoned)
+    h->lose_now = (h->inject_fault >> 3) & 15u;   // bits 3..6: lost INSIDE the kernel (the output is poisoned)
     h->inject_fault = 0;
   }
   return handoff_next_epoch(h, st);
@@ -849,7 +850,7 @@ int sg::host::handoff_verdict(sg_handle* h) {
                           "last check is invalid; re-run them (SG_OPT_FORCE_SPLIT + SG_OPT_FORCE_NOLEAN select the "
                           "kernels without in-launch hand-offs)",
          e, (e & 1u) ? "mask bits " : "", (e & 2u) ? "partial hops (one-pass gate) " : "",
-         (e & 4u) ? "partial hops (fused apply)" : "");
+         (e & 4u) ? "partial hops (fused apply)" : ((e & 8u) ? "band maxima (floor fix-up)" : ""));
   }
   return SG_OK;
 }
@@ -1017,9 +1018,11 @@ struct OnePassCall {
 // ARGS: the kernel's argument struct (fast::OnePassArgs / fast::OnePassRegArgs) with the geometry's tables filled in.
 // first(P, C) completes it before the first launch (compare constants, what only that kernel has) and returns SG_OK or an
 // error; launch(P, redo, grid) enqueues the kernel.  nb: bounds of the in-kernel floor test (floor_setup).
-template <typename ARGS, typename FIRST, typename LAUNCH>
+// fix(P, plan, lose): the geometry's one-launch floor fix-up (n_fft = 1024: k_floor_fix), or nullptr -- the register geometries'
+// REDO bodies take their own argument struct and keep the two launches.
+template <typename ARGS, typename FIRST, typename LAUNCH, typename FIX>
 static int onepass_run(sg_handle* h, const View& v, const View& vx, const Geom& g, int64_t ub, const OutMap& om, hipStream_t st,
-                       const OnePassGeom& S, int nb, ARGS P, FIRST first, LAUNCH launch) {
+                       const OnePassGeom& S, int nb, ARGS P, FIRST first, LAUNCH launch, FIX fix) {
   int rc;
   OnePassCall C;
   if ((rc = floor_setup(h, g, ub, nb, st, &C.fs))) return rc;
@@ -1058,17 +1061,31 @@ static int onepass_run(sg_handle* h, const View& v, const View& vx, const Geom& 
     ProfScope ps(h, SG_STAGE_ONEPASS, st);
     HIPCHK(h, launch(P, false, dim3(C.grid)));
   }
+  h->floor_route = 0;
   if (lazy) {
-    // the units whose floor test fired: float64 band maxima, then the gate again with them.  Both launches return at once
-    // when no unit reported (the common case)
+    // the units whose floor test fired: float64 band maxima, then the gate again with them.  Every launch here returns at
+    // once when no unit reported (the common case)
     ProfScope ps(h, SG_STAGE_STFT_MAX, st);
-    HIPCHK(h, launch_bits_any<0>(h, vx, g, ub, C.fs.tc, (unsigned long long*)h->pmax.p, (unsigned long long*)h->bits.p,
-                                 (g.F + 63) / 64, st));
+    fast::FloorFixPlan fp{};
+    if constexpr (!std::is_same<FIX, std::nullptr_t>::value) {
+      if (!h->floor_two && !h->mr_ok) fp = fast::floor_fix_plan(ub, g.T, C.total);
+    }
+    if (!fp.ok) {
+      HIPCHK(h, launch_bits_any<0>(h, vx, g, ub, C.fs.tc, (unsigned long long*)h->pmax.p, (unsigned long long*)h->bits.p,
+                                   (g.F + 63) / 64, st));
+    } else if ((rc = ensure_zeroed(h, h->farrive, (size_t)ub * 8, st))) {
+      return rc;
+    }
     if ((rc = handoff_next_epoch(h, st))) return rc;
     P.epoch = h->epoch;
     P.ticket = (unsigned*)h->xticket.p + 8;   // its own counter (zeroed by the first launch's ticket-0 workgroup): it takes tickets only if a unit reported
     P.ticket_base = 0;
-    HIPCHK(h, launch(P, true, dim3(C.total)));
+    if constexpr (!std::is_same<FIX, std::nullptr_t>::value) {
+      // (SG_OPT_INJECT_HANDOFF_FAULT bits 3..4 lose every poll of the one-pass gate, bit 6 the wait for the maxima alone)
+      if (fp.ok) HIPCHK(h, fix(P, fp, (h->lose_now & (3u | 8u)) != 0u));
+    }
+    if (!fp.ok) HIPCHK(h, launch(P, true, dim3(C.total)));
+    h->floor_route = fp.ok ? SG_FLOOR_ONE_LAUNCH : SG_FLOOR_TWO_LAUNCH;
   }
   h->dbg_xbits = true;
   h->dbg_trows = S.NF; h->dbg_tstep = S.NH; h->dbg_twords = S.tile_words; h->dbg_txw = S.xw;
@@ -1115,7 +1132,7 @@ static int stage_onepass_reg(sg_handle* h, const RegGeom* r, const View& v, cons
     last = Q.A;
     return launch_lds(r->gate[redo], grid, dim3(256), S.lds, st, Q);
   };
-  if ((rc = onepass_run(h, v, vx, g, ub, om, st, S, (g.FS + 63) / 64, P, first, launch))) return rc;
+  if ((rc = onepass_run(h, v, vx, g, ub, om, st, S, (g.FS + 63) / 64, P, first, launch, nullptr))) return rc;
   note_smooth(h, SG_SMOOTH_ONEPASS_REG, 1, S.NF);
   if (!seam) return SG_OK;
   if (r->abut && P.A.n_tiles < 2) return SG_OK;   // (2048 books no seam stage for a single tile)
@@ -1692,7 +1709,22 @@ static int stage_onepass(sg_handle* h, const View& v, const View& vx, const Geom
     else kern = fast::k_gate_onepass<WAVES, false, false, true>;
     return launch_lds(kern, grid, dim3(WAVES * 64), lds, st, Q);
   };
-  const int rc = onepass_run(h, v, vx, g, ub, om, st, S, OP_ALIM_BLOCKS, P, first, launch);
+  // the floor fix-up of a lazy call as one launch (onepass.hpp: k_floor_fix): the larger of the two roles' LDS
+  auto fix = [&](const fast::OnePassArgs& Q, const fast::FloorFixPlan& fp, bool lose) {
+    fast::FloorFixArgs X{};
+    X.P = Q;
+    X.vx = vx;
+    X.tw64 = (const cx<double>*)h->tw64.p;
+    X.wfull64 = (const double*)h->wfull64.p;
+    X.arrive = (unsigned long long*)h->farrive.p;
+    X.n_max = fp.n_max; X.blocks = fp.blocks;
+    X.lose = lose ? 1u : 0u;
+    constexpr size_t lds_max = (size_t)(fast::FFX_N + fast::FFX_WAVES * lpn<double>(fast::FFX_N)) * sizeof(cx<double>);
+    const size_t lds_fix = std::max(lds, lds_max);
+    if (prop) return launch_lds(fast::k_floor_fix<WAVES, true>, dim3(fp.grid), dim3(WAVES * 64), lds_fix, st, X);
+    return launch_lds(fast::k_floor_fix<WAVES, false>, dim3(fp.grid), dim3(WAVES * 64), lds_fix, st, X);
+  };
+  const int rc = onepass_run(h, v, vx, g, ub, om, st, S, OP_ALIM_BLOCKS, P, first, launch, fix);
   if (!rc) note_smooth(h, SG_SMOOTH_ONEPASS, 1, S.NF);
   return rc;
 }

@@ -28,13 +28,14 @@ extern "C" int sg_set_option(sg_handle* h, int32_t option, int64_t value) {
       if (value != 8 && value != 16) FAIL(h, SG_E_INVALID, "SG_OPT_ROWGATE_SHAPE: 8 or 16 waves");
       h->rg_shape = (int)value;
       return SG_OK;
-    case SG_OPT_INJECT_HANDOFF_FAULT: h->inject_fault = (unsigned)value & 63u; return SG_OK;
+    case SG_OPT_INJECT_HANDOFF_FAULT: h->inject_fault = (unsigned)value & 127u; return SG_OK;
     case SG_OPT_TILE_ORDER:
       if (value < 0 || value > 2) FAIL(h, SG_E_INVALID, "SG_OPT_TILE_ORDER: 0 (persistent workgroups), 1 (block index) or 2 (one ticket per workgroup)");
       h->tile_order = (int)value;
       return SG_OK;
     case SG_OPT_EXACT_MATERIALISED: h->exact_materialised = value != 0; return SG_OK;
     case SG_OPT_STATS_THREE_LAUNCH: h->stats_three = value != 0; return SG_OK;
+    case SG_OPT_FLOOR_TWO_LAUNCH: h->floor_two = value != 0; return SG_OK;
     case SG_OPT_FLOOR_TEST:
       if (value < 0 || value > 2) FAIL(h, SG_E_INVALID, "SG_OPT_FLOOR_TEST: 0 (predicted), 1 (a priori) or 2 (in the gate kernel)");
       h->floor_test = (int)value;
@@ -61,6 +62,7 @@ extern "C" int sg_get_option(const sg_handle* h, int32_t option, int64_t* value)
     case SG_OPT_TILE_ORDER: *value = h->tile_order; return SG_OK;
     case SG_OPT_EXACT_MATERIALISED: *value = h->exact_materialised; return SG_OK;
     case SG_OPT_STATS_THREE_LAUNCH: *value = h->stats_three; return SG_OK;
+    case SG_OPT_FLOOR_TWO_LAUNCH: *value = h->floor_two; return SG_OK;
     case SG_OPT_FLOOR_TEST: *value = h->floor_test; return SG_OK;
   }
   return SG_E_INVALID;   // (no message: the handle is const here)
@@ -154,6 +156,10 @@ extern "C" int sg_debug_counter(sg_handle* h, int32_t which, int64_t* value, voi
   }
   if (which == 19) {   // SG_STATS_* form of the last noise statistics of fewer than 16 units (host bookkeeping)
     *value = h->stats_route;
+    return SG_OK;
+  }
+  if (which == 20) {   // SG_FLOOR_* form of the last one-pass gate call's floor fix-up (host bookkeeping)
+    *value = h->floor_route;
     return SG_OK;
   }
   if (which == 3) {   // launch epoch of the last gate call in which a chunk's floor test fired / flag was set (0: never)

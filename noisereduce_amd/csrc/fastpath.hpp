@@ -901,6 +901,12 @@ __device__ __forceinline__ op_v4u op_ld16_sc1(const void* p) {
   asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(p) : "memory");
   return v;
 }
+// (one 8-byte word the same way: the arrival word and the band maxima of the one-launch floor fix-up, onepass.hpp)
+__device__ __forceinline__ unsigned long long op_ld8_sc1(const void* p) {
+  unsigned long long v;
+  asm volatile("global_load_dwordx2 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(p) : "memory");
+  return v;
+}
 
 struct ApplyArgs {
   View view;

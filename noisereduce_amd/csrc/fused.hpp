@@ -205,12 +205,17 @@ __global__ void k_prep_thresh_lazy(const double* __restrict__ thresh, int F, dou
 // ---------------------------------------------------------------------------------------
 // NT: threads per frame (64: one wavefront; 256: the whole workgroup shares a frame -- from N = 2048 on, where a single
 // wave's 32 float64 points per pass cost 256 VGPRs + scratch).  WAVES = frames in flight per workgroup.
-template <int N, int WAVES, int FPW, int MODE, int NT = 64>
-__global__ __launch_bounds__(WAVES * NT) void k_stft_bits(View view, Geom g, const cx<double>* __restrict__ tw_g,
-                                                          const double* __restrict__ wfull, ThreshConsts tc,
-                                                          double mag_scale, double top_db,
-                                                          unsigned long long* __restrict__ pmax_bits,
-                                                          unsigned long long* __restrict__ bits, int wpr) {
+// The kernel's body: the workgroup of frame block `bx` of unit `u` (k_stft_bits: its block indices; the one-launch floor
+// fix-up of the n_fft = 1024 one-pass gate, onepass.hpp k_floor_fix: a ticket).  Returns false when the workgroup had nothing
+// to do (MODE 0 and the unit's floor is not live).  ACK (MODE 0): the band maxima's atomics are the RETURNING form and the
+// wave has waited for every one of them when the function returns -- each has been carried out where every XCD sees it
+// (the same atomic on the same value: pmax does not change).
+template <int N, int WAVES, int FPW, int MODE, int NT, bool ACK>
+__device__ __forceinline__ bool stft_bits_block(const View& view, const Geom& g, const cx<double>* __restrict__ tw_g,
+                                                const double* __restrict__ wfull, const ThreshConsts& tc,
+                                                double mag_scale, double top_db,
+                                                unsigned long long* __restrict__ pmax_bits,
+                                                unsigned long long* __restrict__ bits, int wpr, unsigned bx, int64_t u) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   cx<double>* tw = reinterpret_cast<cx<double>*>(smem);
   cx<double>* bufs = tw + N;
@@ -218,10 +223,9 @@ __global__ __launch_bounds__(WAVES * NT) void k_stft_bits(View view, Geom g, con
   const int lane = threadIdx.x % NT;   // thread within the frame's team
   const int wave = threadIdx.x / NT;
   cx<double>* buf = bufs + wave * lpn<double>(N);
-  const int64_t u = blockIdx.y;
   const int need = need_of(tc, u);
   const bool floor_live = need == 1;
-  if (MODE == 0 && !floor_live) return;  // whole block: uniform
+  if (MODE == 0 && !floor_live) return false;  // whole block: uniform
   stage_twiddles<WAVES * NT, N>(tw, tw_g, (int)threadIdx.x);
   if (MODE == 1) {
     for (int i = threadIdx.x; i <= N; i += WAVES * NT) {
@@ -242,7 +246,7 @@ __global__ __launch_bounds__(WAVES * NT) void k_stft_bits(View view, Geom g, con
 #pragma unroll
   for (int m = 0; m <= N / NT; ++m) vmax[m] = 0.0;
   for (int fi = 0; fi < FPW; ++fi) {
-    const int64_t t = ((int64_t)blockIdx.x * FPW + fi) * WAVES + wave;
+    const int64_t t = ((int64_t)bx * FPW + fi) * WAVES + wave;
     const bool valid = t < g.T;
     const int64_t s0 = t * g.H - g.padL;
     for (int j = lane; j < N; j += NT) {
@@ -278,12 +282,27 @@ __global__ __launch_bounds__(WAVES * NT) void k_stft_bits(View view, Geom g, con
     SG_PASS_SYNC();
   }
   if (MODE == 0) {
+    [[maybe_unused]] unsigned long long seen = 0ull;
 #pragma unroll
     for (int m = 0; m <= N / NT; ++m) {
       const int k = lane + NT * m;
-      if (k <= N) atomicMax(&pmax_bits[u * g.FS + k], (unsigned long long)__double_as_longlong(vmax[m]));
+      if (k <= N) {
+        if constexpr (ACK) seen |= atomicMax(&pmax_bits[u * g.FS + k], (unsigned long long)__double_as_longlong(vmax[m]));
+        else atomicMax(&pmax_bits[u * g.FS + k], (unsigned long long)__double_as_longlong(vmax[m]));
+      }
     }
+    if constexpr (ACK) asm volatile("" : : "v"(seen) : "memory");   // (a use of every returned value: the compiler waits for them here)
   }
+  return true;
+}
+template <int N, int WAVES, int FPW, int MODE, int NT = 64>
+__global__ __launch_bounds__(WAVES * NT) void k_stft_bits(View view, Geom g, const cx<double>* __restrict__ tw_g,
+                                                          const double* __restrict__ wfull, ThreshConsts tc,
+                                                          double mag_scale, double top_db,
+                                                          unsigned long long* __restrict__ pmax_bits,
+                                                          unsigned long long* __restrict__ bits, int wpr) {
+  stft_bits_block<N, WAVES, FPW, MODE, NT, false>(view, g, tw_g, wfull, tc, mag_scale, top_db, pmax_bits, bits, wpr, blockIdx.x,
+                                                  (int64_t)blockIdx.y);
 }
 
 // ---------------------------------------------------------------------------------------

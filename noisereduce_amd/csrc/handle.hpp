@@ -109,7 +109,7 @@ struct sg_handle {
   unsigned* err_host = nullptr;      // host-mapped error word written by k_gate_onepass when a hand-off times out
   unsigned* err_dev = nullptr;
   unsigned inject_fault = 0;         // SG_OPT_INJECT_HANDOFF_FAULT (tests): error bits the next hand-off launch reports
-  unsigned lose_now = 0;             // bits 3..5 of the option, consumed by the next hand-off launch: the kernel itself treats
+  unsigned lose_now = 0;             // bits 3..6 of the option, consumed by the next hand-off launch: the kernel itself treats
                                      // the hand-off as lost (bounded-poll timeout path: error word + NaN-poisoned hops)
   unsigned ticket_base = 0;          // tickets handed out by all previous launches
   unsigned epoch = 0;                // launch counter: the value a tile's flag must carry to be current
@@ -127,6 +127,9 @@ struct sg_handle {
   int n_filters = 0;                        // 0: no bank set
   bool stats_three = false;   // SG_OPT_STATS_THREE_LAUNCH: the noise statistics always as k_stft<double> + k_colstats1 + k_colstats1_final
   int64_t stats_route = 0;    // sg_debug_counter 19: SG_STATS_* form of the last stage_stats call of fewer than 16 units
+  bool floor_two = false;     // SG_OPT_FLOOR_TWO_LAUNCH: a lazy one-pass call's floor fix-up always as k_stft_bits<max> + the REDO launch
+  int64_t floor_route = 0;    // sg_debug_counter 20: SG_FLOOR_* form of the last one-pass gate call's floor fix-up (0: a-priori floor test)
+  DevBuf farrive;             // k_floor_fix: per-unit arrival words {count, epoch} of the maxima workgroups
   int64_t spec_route = 0;     // sg_debug_counter 18: SG_SPEC_* decide branch of the last sg_gate_spectrum call | flags | sub-batches << 16
   int tile_order = 0;                // SG_OPT_TILE_ORDER: 0 (default) = persistent workgroups looping over tickets (onepass.hpp PERSIST),
                                      // 1 = tile = block index (no ticket), 2 = one ticket-drawn tile per workgroup

@@ -200,5 +200,28 @@ inline OpPlan op_plan_build(const OpPlanIn& I) {
   return P;
 }
 
+// ---- host: the tickets of the one-launch floor fix-up (k_floor_fix, onepass.hpp) ----
+// Tickets [0, n_max) are the frame blocks of the float64 band maxima, unit-major (ticket = unit * blocks + block), tickets
+// [n_max, n_max + tiles) the REDO tiles in the first launch's order; one workgroup per ticket.  ok == false: the counts do not
+// fit 32 bits (the caller keeps the two launches).
+constexpr int OP_PLAN_FIX_FRAMES = 16;   // frames per maxima block (k_stft_bits<512, 4, 4>: 4 waves x 4 frames)
+struct FloorFixPlan {
+  uint32_t blocks;   // maxima blocks per unit: ceil(T / 16)
+  uint32_t n_max;    // units * blocks: the first tile ticket
+  uint32_t grid;     // n_max + tiles
+  bool ok;
+};
+inline FloorFixPlan floor_fix_plan(int64_t units, int64_t T, int64_t tiles /* units * (n_tiles + 2) */) {
+  FloorFixPlan p{};
+  if (units < 1 || T < 1 || tiles < 1) return p;
+  const int64_t blocks = (T + OP_PLAN_FIX_FRAMES - 1) / OP_PLAN_FIX_FRAMES;
+  if (blocks > 0x7fffffff / units || tiles > 0x7fffffff - units * blocks) return p;
+  p.blocks = (uint32_t)blocks;
+  p.n_max = (uint32_t)(units * blocks);
+  p.grid = (uint32_t)(units * blocks + tiles);
+  p.ok = true;
+  return p;
+}
+
 }  // namespace fast
 }  // namespace sg
