@@ -193,6 +193,57 @@ static const OnePassGeom OP1024{
 
 // the handle's register geometry, or nullptr (another geometry, or SG_OPT_FORCE_NOFAST)
 static const RegGeom* reg_geom(const sg_handle* h) { return h->force_nofast ? nullptr : h->reg; }
+
+// Routing (route.hpp): what plan_S / plan_T read of the handle, copied once per call.  The one place where a capability flag
+// or a force_* option is read for the choice of a route; the stages take the plan.
+static_assert(route::NS_TT == NS_TT && route::NS_MAX_NF == NS_MAX_NF && route::NS_IIR_MAX_NT == NS_IIR_MAX_NT &&
+              route::NS_BOX_MAX_NT == NS_BOX_MAX_NT && route::NS_BOX_KB == NS_BOX_KB && route::XIIR_TT == exact::XIIR_TT &&
+              route::RG_FRAMES == fast::RG_FRAMES && route::RG_NFMAX == fast::RG_NFMAX && route::RG_NTMAX == fast::RG_NTMAX &&
+              route::ns_iir_nt_ok(25) == ns_iir_nt_ok(25) && route::ns_iir_nt_ok(21) == ns_iir_nt_ok(21),
+              "route.hpp states the limits of the kernel headers");
+static int64_t ws_budget(const sg_handle* h) {
+  return h->p.max_workspace_bytes > 0 ? h->p.max_workspace_bytes : (int64_t)8 << 30;
+}
+static route::RouteCaps route_caps(const sg_handle* h) {
+  route::RouteCaps c;
+  c.variant = h->p.variant; c.stationary = h->p.stationary != 0; c.smooth_mask = h->p.smooth_mask != 0;
+  c.prop_decrease = h->p.prop_decrease; c.iir_b = h->p.iir_b;
+  c.nf = h->p.n_grad_freq; c.nt = h->p.n_grad_time; c.n_movemean = h->p.n_movemean;
+  c.ktot = h->ktot; c.fused_ok = h->fused_ok; c.t_sm2_ok = h->t_sm2_ok;
+  using route::GeomClass;
+  c.geom = h->big_M ? GeomClass::LONG : h->mr_ok ? GeomClass::MIXED : h->czt_M ? GeomClass::CZT :
+           h->fast_ok ? GeomClass::DEFAULT : h->reg ? GeomClass::REG : GeomClass::POW2;
+  if (c.geom == GeomClass::DEFAULT) c.op = c.op_seam = &OP1024;
+  if (c.geom == GeomClass::REG) { c.op = &h->reg->op; c.op_seam = &h->reg->op_seam; c.reg_abut = h->reg->abut; c.reg_frames = h->reg->frames; }
+  c.ftab3 = h->ftab3.p != nullptr; c.optab = h->optab.p != nullptr; c.regtab = h->regtab.p != nullptr; c.norm64 = h->norm64.p != nullptr;
+  c.force_unfused = h->force_unfused; c.force_nofast = h->force_nofast; c.force_f64_decide = h->force_f64_decide;
+  c.force_noseam = h->force_noseam; c.force_nolean = h->force_nolean; c.force_split = h->force_split;
+  c.fast_integer = h->fast_integer; c.force_exact = h->force_exact; c.exact_materialised = h->exact_materialised;
+  c.rowgate_mode = h->rowgate_mode; c.tile_order = h->tile_order;
+  c.ws_budget = ws_budget(h);
+  return c;
+}
+// ... and of the call: the geometry of its units and the hops of the handle's tile geometry under the output map
+static route::RouteShape route_shape(const route::RouteCaps& c, const Geom& g, int64_t p0, int64_t p1, int in_dtype, int out_dtype,
+                                     int64_t units) {
+  route::RouteShape s;
+  s.F = g.F; s.FS = g.FS; s.n = g.n; s.T = g.T;
+  if (c.op) s.nh = (p1 - 1 + g.padL) / c.op->hop + 1 - (p0 + g.padL) / c.op->hop;   // hop_range(om, g, hop).count()
+  s.in_dtype = in_dtype; s.out_dtype = out_dtype; s.units = units;
+  return s;
+}
+// (host bookkeeping behind sg_debug_fetch / sg_debug_dims / sg_debug_range: what a batch left in the workspace.  A route
+// that keeps no fields reports 0 units; one that decides no bits leaves the range of the last one that did.)
+static void note_batch(sg_handle* h, const route::BatchFacts& f, int64_t nb, const Geom& g, const Decided& d = Decided{}) {
+  LastBatch& b = h->last;
+  if (!f.keeps) { b.units = 0; return; }
+  b.units = nb; b.T = g.T; b.g = g;
+  b.has_P = f.has_P; b.has_raw = f.has_raw; b.fused = f.fused; b.fast = f.fast; b.k16_only = f.k16_only; b.rg = f.rg;
+  b.xbits = f.range == route::Range::TILES;
+  if (b.xbits) b.tiles = d.tiles;
+  if (f.range == route::Range::ALL) { b.db = 0; b.de = g.T; }
+  else if (f.range != route::Range::KEEP) { b.db = d.db; b.de = d.de; }
+}
 // host bookkeeping behind sg_debug_counter 17 (no kernel reads or writes it)
 static void note_smooth(sg_handle* h, int id, int cell_bytes, int tile_frames) {
   h->smooth_route = (int64_t)id | ((int64_t)cell_bytes << 8) | ((int64_t)tile_frames << 16);
@@ -535,9 +586,6 @@ static hipError_t stft_any(const sg_handle* h, const View& v, const Geom& g, int
 #undef SG_CALL
 }
 
-// the general apply kernel that can read the K counts of the fused bit-mask stages directly (k16_apply_ok)
-static bool k16_apply_geom(const sg_handle* h) { return !h->big_M && (!h->czt_M || h->mr_ok); }
-
 static hipError_t apply_any(const sg_handle* h, const View& v, const Geom& g, int64_t units, const float* Mk,
                             float* seg, hipStream_t st, const unsigned short* K16 = nullptr, float kscale = 0.f) {
   if (h->big_M) {
@@ -568,13 +616,10 @@ static unsigned grid_1d(int64_t work, int block) {
 // ------------------------------------------------------------------------------------------
 // workspace
 // ------------------------------------------------------------------------------------------
-static int64_t ws_budget(const sg_handle* h) {
-  return h->p.max_workspace_bytes > 0 ? h->p.max_workspace_bytes : (int64_t)8 << 30;
-}
-
-// Workspace per unit.  lean: the fused stationary path with the fused apply kernel only keeps the
-// bit mask (T*wpr*8 B) and the uint16 weight sums (T*FS*2 B).
-static size_t unit_bytes(const sg_handle* h, const Geom& g, bool lean) {
+// Workspace per unit, for the callers that plan no route (variant T, the backward passes).  lean: the fused stationary path with
+// the fused apply kernel only keeps the bit mask (T*wpr*8 B) and the uint16 weight sums (T*FS*2 B).  route.hpp's unit_bytes, which
+// sizes run_S's batches and sg_workspace_bytes, states the same bytes for a RouteShape: asserted below.
+static constexpr size_t unit_bytes(const sg_handle* h, const Geom& g, bool lean) {
   size_t cells = (size_t)g.T * g.FS;
   if (lean) return (size_t)g.T * ((g.F + 63) / 64) * 8 + cells * 2 + (size_t)g.FS * 16 + 64 +
            (size_t)(g.T / 16 + 2) * 6 * 256 * 4;
@@ -582,6 +627,15 @@ static size_t unit_bytes(const sg_handle* h, const Geom& g, bool lean) {
          (size_t)(g.T / NS_TT + 1) * 2 * g.FS * 8 * 2 +  // + partials and carries of the two-pass non-stationary mask
          (size_t)(g.T / 8 + 1) * 2 * g.FS * 8;           // + the magnitude kernels' per-tile partials (tiles of 8 frames at n_fft = 2048)
 }
+constexpr bool unit_bytes_agree(int n, int64_t T) {
+  Geom g{};
+  g.n = n; g.F = n / 2 + 1; g.FS = (g.F + 15) / 16 * 16; g.T = T;
+  route::RouteShape s;
+  s.n = g.n; s.F = g.F; s.FS = g.FS; s.T = g.T;
+  return unit_bytes(nullptr, g, false) == route::unit_bytes(s, false) && unit_bytes(nullptr, g, true) == route::unit_bytes(s, true);
+}
+static_assert(unit_bytes_agree(1024, 2579) && unit_bytes_agree(256, 7) && unit_bytes_agree(2048, 65) && unit_bytes_agree(1000, 128),
+              "route.hpp and api.hip state the same bytes per unit");
 
 static int64_t units_per_batch(const sg_handle* h, const Geom& g, int64_t total, bool lean = false) {
   int64_t ub = ws_budget(h) / (int64_t)unit_bytes(h, g, lean);
@@ -1022,7 +1076,7 @@ struct OnePassCall {
 // REDO bodies take their own argument struct and keep the two launches.
 template <typename ARGS, typename FIRST, typename LAUNCH, typename FIX>
 static int onepass_run(sg_handle* h, const View& v, const View& vx, const Geom& g, int64_t ub, const OutMap& om, hipStream_t st,
-                       const OnePassGeom& S, int nb, ARGS P, FIRST first, LAUNCH launch, FIX fix) {
+                       const OnePassGeom& S, int nb, ARGS P, FIRST first, LAUNCH launch, FIX fix, Decided* dec) {
   int rc;
   OnePassCall C;
   if ((rc = floor_setup(h, g, ub, nb, st, &C.fs))) return rc;
@@ -1087,34 +1141,20 @@ static int onepass_run(sg_handle* h, const View& v, const View& vx, const Geom& 
     if (!fp.ok) HIPCHK(h, launch(P, true, dim3(C.total)));
     h->floor_route = fp.ok ? SG_FLOOR_ONE_LAUNCH : SG_FLOOR_TWO_LAUNCH;
   }
-  h->dbg_xbits = true;
-  h->dbg_trows = S.NF; h->dbg_tstep = S.NH; h->dbg_twords = S.tile_words; h->dbg_txw = S.xw;
-  h->dbg_tf0 = hr.h_begin - 3;
-  h->dbg_ntt = (int)ntt;
-  h->dbg_db = std::max<int64_t>(0, hr.h_begin - 3 - S.NH);
-  h->dbg_de = std::min<int64_t>(g.T, hr.h_begin - 3 + (int64_t)S.NH * (n_tiles + 1) + (S.NF - S.NH));
+  dec->tiles = TileLayout{S.NF, S.NH, S.tile_words, S.xw, (int)ntt, hr.h_begin - 3};
+  dec->db = std::max<int64_t>(0, hr.h_begin - 3 - S.NH);
+  dec->de = std::min<int64_t>(g.T, hr.h_begin - 3 + (int64_t)S.NH * (n_tiles + 1) + (S.NF - S.NH));
   return SG_OK;
 }
 
-// (round 6) one-pass gate of a register geometry
-static bool onepass_geom_ok(const sg_handle* h, const Geom& g, const OutMap& om, const OnePassGeom& S, const DevBuf& tab) {
-  if (h->force_nofast || h->force_split || h->force_f64_decide || h->force_unfused || !h->fused_ok) return false;
-  if (h->p.variant != SG_VARIANT_S || !h->p.stationary || !h->p.smooth_mask) return false;
-  if (h->p.n_grad_freq > S.max_nf || h->p.n_grad_time > S.max_nt || g.F != S.F || !tab.p) return false;
-  if (h->tile_order == 1) return false;
-  return hop_range(om, g, S.hop).count() > 0;
-}
-static bool onepass_reg_ok(const sg_handle* h, const RegGeom* r, const Geom& g, const OutMap& om) {
-  return !(r->abut && h->force_noseam) && onepass_geom_ok(h, g, om, r->op, h->regtab);
-}
+// (round 6) one-pass gate of a register geometry (seam: abutting tiles + k_ola_seam, the default; SG_OPT_FORCE_NOSEAM keeps
+// overlapping tiles where the geometry has them)
 static int stage_onepass_reg(sg_handle* h, const RegGeom* r, const View& v, const View& vx, const Geom& g, int64_t ub,
-                             const OutMap& om, hipStream_t st) {
+                             const OutMap& om, bool seam, hipStream_t st, Decided* dec) {
   fast::OnePassRegArgs P{};
   P.A = reg_args(h, r, v, g);
   P.A.inv_ktot = (float)(1.0 / (double)h->ktot);
   P.tab = (const unsigned long long*)h->regtab.p;
-  // (abutting tiles + k_ola_seam: the default; SG_OPT_FORCE_NOSEAM keeps overlapping tiles where the geometry has them)
-  const bool seam = r->abut || !h->force_noseam;
   int rc;
   if (seam && (rc = reg_seam_tiles(h, r, hop_range(om, g, r->hop).count(), ub, &P.A))) return rc;
   const OnePassGeom& S = seam ? r->op_seam : r->op;
@@ -1132,7 +1172,7 @@ static int stage_onepass_reg(sg_handle* h, const RegGeom* r, const View& v, cons
     last = Q.A;
     return launch_lds(r->gate[redo], grid, dim3(256), S.lds, st, Q);
   };
-  if ((rc = onepass_run(h, v, vx, g, ub, om, st, S, (g.FS + 63) / 64, P, first, launch, nullptr))) return rc;
+  if ((rc = onepass_run(h, v, vx, g, ub, om, st, S, (g.FS + 63) / 64, P, first, launch, nullptr, dec))) return rc;
   note_smooth(h, SG_SMOOTH_ONEPASS_REG, 1, S.NF);
   if (!seam) return SG_OK;
   if (r->abut && P.A.n_tiles < 2) return SG_OK;   // (2048 books no seam stage for a single tile)
@@ -1166,26 +1206,18 @@ static int stage_mag(sg_handle* h, const View& v, const Geom& g, int64_t ub, hip
 }
 
 // Variant-S non-stationary mask in two passes over |X| (nonstat.hpp): partials -> chain -> IIR + sigmoid (+ smoothing).
-//   nonstat2_chain_ok: the recurrence can run tile-parallel (k_iir_part / k_iir_chain / k_iir_mask)
-//   nonstat2_ok:       ... and k_iir_mask also smooths (nt instantiated, nf <= NS_MAX_NF): the mask in one kernel
-// Other smoothing widths take k_iir_mask<0> for the raw sigmoid field and the general smoothing kernels after it.
-static bool nonstat2_chain_ok(const sg_handle* h, const Geom& g) {
-  if (h->p.variant != SG_VARIANT_S || h->p.stationary || h->force_unfused) return false;
-  const double b = h->p.iir_b, c = 1.0 - b;
-  if (!(b > 0.0 && b < 1.0)) return false;
-  // the backward sweep regenerates the forward values in reverse: error growth c^-rows must stay small
-  return std::pow(c, (double)(NS_TT + 2 * NS_IIR_MAX_NT)) >= 1e-3 && g.T >= 1;
-}
-static bool nonstat2_ok(const sg_handle* h, const Geom& g) {
-  if (!nonstat2_chain_ok(h, g) || !h->p.smooth_mask) return false;
-  const int nf = h->p.n_grad_freq, nt = h->p.n_grad_time;
-  if (nt > NS_IIR_MAX_NT && !(std::pow(1.0 - h->p.iir_b, (double)(NS_TT + 2 * nt)) >= 1e-3)) return false;   // (as above, for the longer column)
-  return nf <= NS_MAX_NF && ns_iir_nt_ok(nt);   // instantiated time half-widths (the tile column lives in registers)
-}
+// (route.hpp: NsMask::SMOOTHED -- k_iir_mask also smooths, the mask in one kernel; NsMask::CHAIN -- other smoothing widths
+// take k_iir_mask<0> for the raw sigmoid field and the general smoothing kernels after it.)
 
 // smooth: IIR + sigmoid + smoothing + prop_decrease -> M;  !smooth: the raw sigmoid field -> raw (smoothing follows),
 // or, without a smoothing filter, p * sigmoid + (1 - p) -> M
-static int stage_nonstat_mask2(sg_handle* h, const View& v, const Geom& g, int64_t ub, bool smooth, hipStream_t st) {
+// pp: c^len and 1 - c^(2 len) of the chain's pieces, worked out in the call's first batch and kept for the others
+struct PiecePows {
+  int plen = 0;
+  int64_t np = 0;
+  double o[4];
+};
+static int stage_nonstat_mask2(sg_handle* h, const View& v, const Geom& g, int64_t ub, bool smooth, hipStream_t st, PiecePows* pp) {
   // register geometries: the magnitude kernel also leaves the recurrence partials of its tiles -- 16 frames at n_fft = 1024,
   // (round 6) 32 / 64 / 8 at 512 / 256 / 2048 -- no second pass over |X| (k_iir_part); PER pieces per 64-frame tile of the chain
   const RegGeom* r = reg_geom(h);
@@ -1213,9 +1245,13 @@ static int stage_nonstat_mask2(sg_handle* h, const View& v, const Geom& g, int64
     const dim3 pgrid((unsigned)((g.F + 63) / 64), (unsigned)ub);
     // c^len and 1 - c^(2 len) of a full piece and of the unit's last one (uniform: computed here, not per thread)
     auto piece_pows = [&](int plen, int64_t np, double* o) {
-      const double c = 1.0 - h->p.iir_b, len_last = (double)(g.T - (np - 1) * plen);
-      o[0] = std::pow(c, (double)plen); o[1] = 1.0 - std::pow(c, 2.0 * plen);
-      o[2] = std::pow(c, len_last); o[3] = 1.0 - std::pow(c, 2.0 * len_last);
+      if (pp->plen != plen || pp->np != np) {
+        const double c = 1.0 - h->p.iir_b, len_last = (double)(g.T - (np - 1) * plen);
+        pp->o[0] = std::pow(c, (double)plen); pp->o[1] = 1.0 - std::pow(c, 2.0 * plen);
+        pp->o[2] = std::pow(c, len_last); pp->o[3] = 1.0 - std::pow(c, 2.0 * len_last);
+        pp->plen = plen; pp->np = np;
+      }
+      std::copy(pp->o, pp->o + 4, o);
     };
     double pw[4];
     if (sub_ok && par && nsp_ok(nk, per)) {
@@ -1266,12 +1302,8 @@ static int stage_nonstat_mask2(sg_handle* h, const View& v, const Geom& g, int64
 }
 
 // Variant-T non-stationary mask in one kernel (nonstat.hpp: k_box_mask): the default moving-mean length and the
-// smoothing widths k_iir_mask also covers; other settings keep k_boxcar_sigmoid + the general smoothing kernels.
-static bool box_mask_ok(const sg_handle* h) {
-  if (h->p.variant != SG_VARIANT_T || h->p.stationary || h->force_unfused || h->p.n_movemean != NS_BOX_KB) return false;
-  if (!h->p.smooth_mask) return true;
-  return h->p.n_grad_freq <= NS_MAX_NF && h->p.n_grad_time >= 1 && h->p.n_grad_time <= NS_BOX_MAX_NT;
-}
+// smoothing widths k_iir_mask also covers; other settings keep k_boxcar_sigmoid + the general smoothing kernels
+// (route.hpp: NsMask::BOX).
 
 static int stage_box_mask(sg_handle* h, const View& v, const Geom& g, int64_t ub, hipStream_t st) {
   int rc = stage_mag(h, v, g, ub, st);
@@ -1456,14 +1488,15 @@ static int stage_prep_floor(sg_handle* h, const View& v, const Geom& g, int64_t 
 }
 
 // Fused stationary mask (variant S): STFT(f64) -> bits -> integer smoothing -> K16 -> float mask.
-static int stage_fused_mask(sg_handle* h, const View& v, const Geom& g, int64_t ub, bool fast, int64_t tb,
-                            int64_t te, hipStream_t st) {
+// pl.decide names the decision kernel; K in the fused apply kernel's lane order unless pl.pipe is the general FUSED one.
+static int stage_fused_mask(sg_handle* h, const route::SPlan& pl, const View& v, const Geom& g, int64_t ub, int64_t tb,
+                            int64_t te, hipStream_t st, Decided* dec) {
+  using route::Decide;
+  const bool fast = pl.pipe != route::Pipe::FUSED;
   // [tb, te): frames whose smoothed mask is needed; decisions are needed nt frames further out
   const int64_t nt_halo = h->p.smooth_mask ? h->p.n_grad_time : 0;
   const int64_t db = std::max<int64_t>(0, tb - nt_halo), de = std::min<int64_t>(g.T, te + nt_halo);
-  h->dbg_db = (fast && !h->force_f64_decide) ? db : 0;
-  h->dbg_de = (fast && !h->force_f64_decide) ? de : g.T;
-  h->dbg_xbits = false;
+  dec->db = db; dec->de = de;   // (reported where k_decide_fast decides: every other kernel decides all frames)
   const int wpr = (g.F + 63) / 64;
   int rc;
   if ((rc = ensure(h, h->K16, (size_t)ub * g.T * g.FS * 2))) return rc;
@@ -1471,7 +1504,7 @@ static int stage_fused_mask(sg_handle* h, const View& v, const Geom& g, int64_t 
   // run the floor test themselves (thresh.hpp: FloorLazy -- the one-pass gate's protocol) instead of k_unit_absmax +
   // k_prep_thresh reading the recording once more before the gate.  Same prediction as the one-pass gates (floor_setup);
   // both end in exact band maxima.
-  const RegGeom* r = !fast && !h->force_f64_decide ? reg_geom(h) : nullptr;
+  const RegGeom* r = pl.decide == Decide::REG ? h->reg : nullptr;
   FloorSetup fs;
   if (r && h->floor_test != 1 && (rc = floor_setup(h, g, ub, (g.FS + 63) / 64, st, &fs))) return rc;
   const bool lazy = fs.lazy;
@@ -1479,7 +1512,7 @@ static int stage_fused_mask(sg_handle* h, const View& v, const Geom& g, int64_t 
   if (r) ++(lazy ? h->n_floor_lazy : h->n_floor_apriori);
   if (!lazy && (rc = stage_prep_floor(h, v, g, ub, &fs.tc, st, nullptr, r && h->err_dev ? h->err_dev + 1 : nullptr, h->epoch)))
     return rc;
-  if (fast && !h->force_f64_decide) {
+  if (pl.decide == Decide::FAST) {
     ProfScope ps(h, SG_STAGE_DECIDE_FAST, st);
     constexpr int WAVES = 4;
     fast::DecideArgs D;
@@ -1503,7 +1536,7 @@ static int stage_fused_mask(sg_handle* h, const View& v, const Geom& g, int64_t 
     HIPCHK(h, launch_lds(kern, grid, dim3(WAVES * 64), lds, st, D));
   } else if (r) {
     if ((rc = stage_decide_reg(h, r, v, g, ub, tc, (unsigned long long*)h->bits.p, st, fs.fl))) return rc;
-  } else if (!h->force_f64_decide) {
+  } else if (pl.decide == Decide::LDS) {
     // other power-of-two frame lengths: float32 LDS transform + exact refinement
     ProfScope ps(h, SG_STAGE_STFT_BITS, st);
     HIPCHK(h, launch_decide_lds(h, v, g, ub, tc, (unsigned long long*)h->bits.p, wpr, st));
@@ -1524,13 +1557,10 @@ static int stage_fused_mask(sg_handle* h, const View& v, const Geom& g, int64_t 
   { int rc2 = stage_smooth_bits(h, g, ub, fast, tb, te, st); if (rc2) return rc2; }
   const int nf = h->p.n_grad_freq, nt = h->p.n_grad_time;
   int64_t cells = ub * g.T * g.FS;
-  if (fast) return SG_OK;  // the fused apply kernel reads K directly
-  if (reg_geom(h) && h->p.prop_decrease == 1.0) return SG_OK;   // so do k_apply_fast512 / 256 / 2048<K>
-  // (round 5) ... and k_apply_istft (power-of-two frames on the LDS transform): the float mask field is only written when
-  // somebody asks for it (sg_debug_fetch field 1 expands the K counts of the last batch then)
-  h->dbg_k16_only = k16_apply_geom(h) && h->p.prop_decrease == 1.0;
-  h->dbg_g = g;
-  if (h->dbg_k16_only) return SG_OK;
+  // The fused apply kernel reads K directly; so do k_apply_fast512 / 256 / 2048<K> and (round 5) k_apply_istft (power-of-two
+  // frames on the LDS transform): the float mask field is only written when somebody asks for it (sg_debug_fetch field 1
+  // expands the K counts of the last batch then)
+  if (!pl.k16_to_mask) return SG_OK;
   hipLaunchKernelGGL(k_k16_to_mask, dim3(grid_1d(cells / 8, 256)), dim3(256), 0, st, (const unsigned short*)h->K16.p,
                      g, nf, nt, 1.0f / (float)h->ktot, (float)h->p.prop_decrease, 1, h->p.smooth_mask ? 1 : 0,
                      (float*)h->M.p, ub);
@@ -1613,18 +1643,11 @@ static int stage_apply_fast(sg_handle* h, const View& v, const Geom& g, int64_t 
 
 // One-pass stationary gate (default geometry, onepass.hpp): forward transform once per frame; decide,
 // publish the tile's bits, smooth in LDS, x mask, inverse transform, overlap-add -- one kernel (+ the
-// seam kernel for the 3 hops that straddle two tiles).  Returns 1 when the shape is not eligible
-// (the caller then runs the three-kernel path).
-static bool onepass_ok(const sg_handle* h, const Geom& g, const OutMap& om) {
-  const OnePassGeom& S = OP1024;
-  if (h->force_split || h->force_f64_decide || h->force_noseam || h->force_nolean) return false;
-  if (!h->p.smooth_mask || h->p.n_grad_freq > S.max_nf || h->p.n_grad_time > S.max_nt || !h->ftab3.p || !h->optab.p) return false;
-  if (g.F != S.F) return false;
-  return S.tiles(hop_range(om, g, S.hop).count()) >= 2;  // at least two abutting tiles (seam mode)
-}
+// seam kernel for the 3 hops that straddle two tiles).  (route.hpp: onepass_ok -- a shape that is not eligible runs the
+// three-kernel path.)
 
 static int stage_onepass(sg_handle* h, const View& v, const View& vx, const Geom& g, int64_t ub, const OutMap& om,
-                         hipStream_t st) {
+                         hipStream_t st, Decided* dec) {
   constexpr int WAVES = 4;
   const OnePassGeom& S = OP1024;
   fast::OnePassArgs P{};
@@ -1724,7 +1747,7 @@ static int stage_onepass(sg_handle* h, const View& v, const View& vx, const Geom
     if (prop) return launch_lds(fast::k_floor_fix<WAVES, true>, dim3(fp.grid), dim3(WAVES * 64), lds_fix, st, X);
     return launch_lds(fast::k_floor_fix<WAVES, false>, dim3(fp.grid), dim3(WAVES * 64), lds_fix, st, X);
   };
-  const int rc = onepass_run(h, v, vx, g, ub, om, st, S, OP_ALIM_BLOCKS, P, first, launch, fix);
+  const int rc = onepass_run(h, v, vx, g, ub, om, st, S, OP_ALIM_BLOCKS, P, first, launch, fix, dec);
   if (!rc) note_smooth(h, SG_SMOOTH_ONEPASS, 1, S.NF);
   return rc;
 }
@@ -1775,15 +1798,10 @@ static int stage_apply_fast64(sg_handle* h, const View& v, const Geom& g, int64_
 // from the fused bit path -- decisions bit-identical to float64 decisions (k_decide_fast: float32 transform + exact
 // refinement of ambiguous cells on the ORIGINAL samples), integer smoothing -- and k_apply_fast64 does the transforms,
 // the mask multiply and the overlap-add in double.  Integer outputs (trunc(float64 result), base.py:217-226) and
-// precision="float64" take it; everything else of the float64 contract stays on run_S_exact.
-static bool exact_fused_ok(const sg_handle* h, const Geom& g) {
-  return h->p.stationary && h->fused_ok && !h->force_unfused && h->fast_ok && !h->force_nofast && !h->force_f64_decide &&
-         g.F == 513 && h->norm64.p != nullptr && !h->exact_materialised;   // (any prop_decrease: k_apply_fast64 forms p K + (1 - p) edge)
-}
-
-static int run_S_exact_fused(sg_handle* h, View v, int64_t total_units, const OutMap& om, hipStream_t st) {
-  const Geom g = make_geom(h, v.Lp);
-  int64_t ub = units_per_batch(h, g, total_units, true);
+// precision="float64" take it (route.hpp: exact_fused_ok; any prop_decrease: k_apply_fast64 forms p K + (1 - p) edge);
+// everything else of the float64 contract stays on run_S_exact.
+static int run_S_exact_fused(sg_handle* h, const route::SPlan& pl, View v, const Geom& g, int64_t total_units, int64_t ub,
+                             const OutMap& om, hipStream_t st) {
   int rc = ensure_ws(h, g, ub, true);
   if (rc) return rc;
   // (other sample types than float32 are NOT converted to a float32 copy here: k_decide_fast stages (float)sample per tile
@@ -1794,9 +1812,10 @@ static int run_S_exact_fused(sg_handle* h, View v, int64_t total_units, const Ou
     v.unit0 = u0;
     const HopRange hr = hop_range(om, g, 256);
     const int64_t tb = std::max<int64_t>(0, hr.h_begin - 3), te = std::min<int64_t>(g.T, hr.h_end);
-    if ((rc = stage_fused_mask(h, v, g, nb, true, tb, std::max(te, tb + 1), st))) return rc;
+    Decided dec;
+    if ((rc = stage_fused_mask(h, pl, v, g, nb, tb, std::max(te, tb + 1), st, &dec))) return rc;
     if ((rc = stage_apply_fast64(h, v, g, nb, om, st))) return rc;
-    h->dbg_units = nb; h->dbg_T = g.T; h->dbg_has_P = false; h->dbg_fused = true; h->dbg_fast = true;
+    note_batch(h, pl.facts, nb, g, dec);
   }
   return SG_OK;
 }
@@ -1853,20 +1872,10 @@ static hipError_t xapply_any(sg_handle* h, const View& v, const Geom& g, int64_t
   return hipErrorInvalidValue;
 }
 
-// float64 pipeline (exact.hpp): bytes per unit -- P, raw, M, tmp (8 B per cell each) + frames (8 B per sample of every
-// frame) + the statistics rows -- and units per batch.  Shared with sg_workspace_bytes.
-static size_t exact_unit_bytes(const Geom& g) {
-  // (+ the non-stationary gate's tile partials and carries: 2 x 2 doubles per band and 32-frame tile, one tile more than T / 32)
-  return (size_t)g.T * g.FS * 32 + (size_t)g.T * g.n * 8 + (size_t)g.FS * 16 + (size_t)(g.T / 32 + 2) * g.FS * 32;
-}
-static int64_t exact_units_per_batch(const sg_handle* h, const Geom& g, int64_t total_units) {
-  return std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(ws_budget(h) / (int64_t)exact_unit_bytes(g), 32768), total_units));
-}
-
-static int run_S_exact(sg_handle* h, View v, int64_t total_units, const OutMap& om, hipStream_t st) {
-  const Geom g = make_geom(h, v.Lp);
+// float64 pipeline (exact.hpp; bytes per unit and units per batch: route.hpp, exact_unit_bytes)
+static int run_S_exact(sg_handle* h, const route::SPlan& pl, View v, const Geom& g, int64_t total_units, int64_t ub,
+                       const OutMap& om, hipStream_t st) {
   const size_t cells1 = (size_t)g.T * g.FS;
-  int64_t ub = exact_units_per_batch(h, g, total_units);
   int rc;
   const size_t cells = (size_t)ub * cells1;
   if ((rc = ensure(h, h->xP, cells * 8))) return rc;
@@ -1874,7 +1883,7 @@ static int run_S_exact(sg_handle* h, View v, int64_t total_units, const OutMap& 
   if ((rc = ensure(h, h->xM, cells * 8))) return rc;
   if ((rc = ensure(h, h->xtmp, cells * 8))) return rc;
   // default geometry: k_apply_fast64 reads the float64 mask field and writes samples (no masked frames through HBM)
-  const bool apply64 = h->fast_ok && !h->force_nofast && g.F == 513 && h->norm64.p && !h->exact_materialised;
+  const bool apply64 = pl.apply == route::Apply::FAST64_M;
   if (!apply64 && (rc = ensure(h, h->xseg, (size_t)ub * g.T * g.n * 8))) return rc;
   if ((rc = ensure(h, h->pmax, (size_t)ub * g.FS * 8))) return rc;
   const int nf = h->p.n_grad_freq, nt = h->p.n_grad_time;
@@ -1897,7 +1906,7 @@ static int run_S_exact(sg_handle* h, View v, int64_t total_units, const OutMap& 
                          (const double*)h->pmax.p, (const double*)h->thresh.p, (int64_t)0, h->mag_scale, h->p.top_db,
                          (float*)h->xraw.p, nb);
       HIPCHK(h, hipGetLastError());
-    } else if (g.T >= 4 * exact::XIIR_TT && nb <= 65535 && !h->exact_materialised) {
+    } else if (g.T >= 4 * exact::XIIR_TT && nb <= 65535 && pl.exact_tiled) {
       // (round 5) tile-parallel: partials of 32-frame tiles -> chain -> both sweeps per tile from the entering states
       ProfScope ps(h, SG_STAGE_NONSTAT_MASK, st);
       NsTiling tl{g.T, 0};
@@ -1930,7 +1939,7 @@ static int run_S_exact(sg_handle* h, View v, int64_t total_units, const OutMap& 
         else
           hipLaunchKernelGGL(exact::kx_prop_only<double>, gr, dim3(256), 0, st, (const double*)h->xraw.p, g, p, (double*)h->xM.p, nb);
         note_smooth(h, SG_SMOOTH_OFF, 8, 0);
-      } else if (!h->exact_materialised && exact::xsm_lds_bytes(nf, nt) <= 150 * 1024 && 2 * nf < exact::XSM_KMAX && 2 * nt < exact::XSM_KMAX && nb <= 65535 &&
+      } else if (pl.exact_tiled && exact::xsm_lds_bytes(nf, nt) <= 150 * 1024 && 2 * nf < exact::XSM_KMAX && 2 * nt < exact::XSM_KMAX && nb <= 65535 &&
                  (g.T + exact::XSM_TT - 1) / exact::XSM_TT <= 65535) {
         // (round 5) both passes in one LDS-tiled kernel, taps computed once per block
         const size_t lds = exact::xsm_lds_bytes(nf, nt);
@@ -1956,7 +1965,7 @@ static int run_S_exact(sg_handle* h, View v, int64_t total_units, const OutMap& 
     // instead of masked frames through HBM + a gather
     if (apply64) {
       if ((rc = stage_apply_fast64(h, v, g, nb, om, st, (const double*)h->xM.p))) return rc;
-      h->dbg_units = 0;
+      note_batch(h, pl.facts, nb, g);
       continue;
     }
     {
@@ -1970,37 +1979,39 @@ static int run_S_exact(sg_handle* h, View v, int64_t total_units, const OutMap& 
                          (const double*)h->xseg.p, (const double*)h->wfull64.p);
       HIPCHK(h, hipGetLastError());
     }
-    h->dbg_units = 0;   // the exact path keeps no debug fields
+    note_batch(h, pl.facts, nb, g);   // the exact path keeps no debug fields
   }
   return SG_OK;
 }
 
-// Variant S over a set of units described by `v` (unit0 filled per batch).
+// Variant S over a set of units described by `v` (unit0 filled per batch).  The route -- pipeline, stages, workspace form --
+// is planned once (route.hpp: plan_S) and holds for every batch of the call.
 static int run_S(sg_handle* h, View v, int64_t total_units, const OutMap& om, hipStream_t st) {
+  using route::Pipe;
+  using route::Apply;
+  using route::NsMask;
   h->smooth_route = 0;   // (sg_debug_counter 17 speaks of THIS call: a path that notes nothing reports "none", not the call before)
   Geom g = make_geom(h, v.Lp);
   if (v.Lp < h->W) FAIL(h, SG_E_INVALID, "signal window of %lld samples is shorter than win_length=%d",
                         (long long)v.Lp, h->W);
   if (h->p.stationary && !h->has_thresh)
     FAIL(h, SG_E_STATE, "stationary gate: call sg_noise_stats or sg_set_noise_threshold first");
+  const route::RouteCaps caps = route_caps(h);
+  const route::RouteShape shape = route_shape(caps, g, om.p0, om.p1, v.dtype, om.dtype, total_units);
+  const route::SPlan pl = route::plan_S(caps, shape);
+  const int64_t ub = route::workspace_S(caps, pl, shape, total_units).ub;
   // integer outputs are the TRUNCATED float64 result of the reference (base.py:217-226): float64 pipeline
-  if (h->force_exact || ((om.dtype == SG_I16 || om.dtype == SG_I32) && !h->fast_integer))
-    return exact_fused_ok(h, g) ? run_S_exact_fused(h, v, total_units, om, st) : run_S_exact(h, v, total_units, om, st);
-  // one-pass gate (any prop_decrease) or, with prop_decrease == 1, the three-kernel bit-mask path: only bit /
+  if (pl.pipe == Pipe::EXACT_FUSED) return run_S_exact_fused(h, pl, v, g, total_units, ub, om, st);
+  if (pl.pipe == Pipe::EXACT) return run_S_exact(h, pl, v, g, total_units, ub, om, st);
+  // lean -- the one-pass gates (any prop_decrease) or, with prop_decrease == 1, the three-kernel bit-mask path: only bit /
   // count fields in the workspace
-  const bool onepass = h->fused_ok && !h->force_unfused && h->fast_ok && !h->force_nofast && onepass_ok(h, g, om);
-  const RegGeom* r = reg_geom(h);
-  const bool onepass_r = r && onepass_reg_ok(h, r, g, om);   // (the one-pass gate of a register geometry)
-  const bool lean = onepass || onepass_r || (h->fused_ok && !h->force_unfused && h->fast_ok && !h->force_nofast &&
-                                             h->p.prop_decrease == 1.0);
-  int64_t ub = units_per_batch(h, g, total_units, lean);
-  int rc = ensure_ws(h, g, ub, lean);
+  int rc = ensure_ws(h, g, ub, pl.lean);
   if (rc) return rc;
   // Samples that are not float32: the register-FFT kernels would take the checked per-sample path for every
   // frame (in every kernel).  Convert the readable part of the rows ONCE -- (float)sample is what those kernels
   // compute anyway -- and keep the original view for the float64 work (exact refinement, floor pre-pass).
   const View vx = v;
-  if (v.dtype != SG_F32 && ((h->fast_ok && !h->force_nofast && (onepass || (!h->p.stationary && nonstat2_ok(h, g)))) || onepass_r)) {
+  if (pl.f32_copy) {
     const int64_t rows = total_units / std::max<int64_t>(1, v.n_chunks), len = v.hi - v.lo;
     const size_t bytes = (size_t)rows * len * sizeof(float);
     if (len > 0 && bytes <= ((size_t)16 << 30)) {
@@ -2014,87 +2025,56 @@ static int run_S(sg_handle* h, View v, int64_t total_units, const OutMap& om, hi
       v.stride = len;
     }
   }
+  const RegGeom* r = pl.reg ? h->reg : nullptr;
+  const float* const Mf = (const float*)h->M.p;
+  PiecePows pows;
   for (int64_t u0 = 0; u0 < total_units; u0 += ub) {
     int64_t nb = std::min(ub, total_units - u0);
     v.unit0 = u0;
-    const bool fused = h->fused_ok && !h->force_unfused;
-    const bool geom_fast = h->fast_ok && !h->force_nofast;  // default geometry: fused apply kernel
-    const bool fast = fused && geom_fast && h->p.prop_decrease == 1.0;
-    if (onepass) {
+    Decided dec;
+    if (pl.pipe == Pipe::ONEPASS || pl.pipe == Pipe::ONEPASS_REG) {
       View vxb = vx;
       vxb.unit0 = u0;
-      if ((rc = stage_onepass(h, v, vxb, g, nb, om, st))) return rc;
-      h->dbg_units = nb; h->dbg_T = g.T; h->dbg_has_P = false; h->dbg_fused = true; h->dbg_fast = true;
+      if (pl.pipe == Pipe::ONEPASS) rc = stage_onepass(h, v, vxb, g, nb, om, st, &dec);
+      else rc = stage_onepass_reg(h, r, v, vxb, g, nb, om, pl.seam, st, &dec);
+      if (rc) return rc;
+      note_batch(h, pl.facts, nb, g, dec);
       continue;
     }
-    if (onepass_r) {
-      View vxb = vx;
-      vxb.unit0 = u0;
-      if ((rc = stage_onepass_reg(h, r, v, vxb, g, nb, om, st))) return rc;
-      h->dbg_units = nb; h->dbg_T = g.T; h->dbg_has_P = false; h->dbg_fused = true; h->dbg_fast = true; h->dbg_k16_only = false;
-      continue;
-    }
-    if (fast) {
+    if (pl.pipe == Pipe::BITS3) {
       // frames the fused apply kernel touches: hops [h_begin, h_end) need frames h-3 .. h
       const HopRange hr = hop_range(om, g, 256);
       const int64_t tb = std::max<int64_t>(0, hr.h_begin - 3), te = std::min<int64_t>(g.T, hr.h_end);
-      if ((rc = stage_fused_mask(h, v, g, nb, true, tb, std::max(te, tb + 1), st))) return rc;
-      if ((rc = stage_apply_fast(h, v, g, nb, om, nullptr, 1, st))) return rc;
-      h->dbg_units = nb; h->dbg_T = g.T; h->dbg_has_P = false; h->dbg_fused = true; h->dbg_fast = true;
-      continue;
-    }
-    // float mask field (natural bin order for the general apply kernels, lane order for the fused one)
-    h->dbg_fast = geom_fast || (fused && r && h->p.prop_decrease == 1.0);
-    if (fused) {
-      if ((rc = stage_fused_mask(h, v, g, nb, false, 0, g.T, st))) return rc;
+      if ((rc = stage_fused_mask(h, pl, v, g, nb, tb, std::max(te, tb + 1), st, &dec))) return rc;
+    } else if (pl.pipe == Pipe::FUSED) {
+      // float mask field (natural bin order for the general apply kernels, lane order for the fused one), or K counts
+      if ((rc = stage_fused_mask(h, pl, v, g, nb, 0, g.T, st, &dec))) return rc;
     } else {
-      if (h->p.stationary) {
+      if (pl.ns == NsMask::NONE) {
         if ((rc = stage_power(h, v, g, nb, st))) return rc;
         if ((rc = stage_decide(h, g, nb, (const double*)h->thresh.p, 0, st))) return rc;
-      } else if (nonstat2_ok(h, g)) {
-        if ((rc = stage_nonstat_mask2(h, v, g, nb, true, st))) return rc;
-      } else if (nonstat2_chain_ok(h, g)) {
-        if ((rc = stage_nonstat_mask2(h, v, g, nb, false, st))) return rc;
-      } else {
+      } else if (pl.ns == NsMask::RAW) {
         if ((rc = stage_nonstat_raw(h, v, g, nb, st))) return rc;
+      } else {
+        if ((rc = stage_nonstat_mask2(h, v, g, nb, pl.ns == NsMask::SMOOTHED, st, &pows))) return rc;
       }
-      if (h->p.stationary || !(nonstat2_ok(h, g) || (nonstat2_chain_ok(h, g) && !h->p.smooth_mask)))
-        if ((rc = stage_smooth(h, g, nb, st))) return rc;
+      if (pl.smooth_stage && (rc = stage_smooth(h, g, nb, st))) return rc;
     }
-    if (geom_fast) {
-      if ((rc = stage_apply_fast(h, v, g, nb, om, (const float*)h->M.p, 1, st))) return rc;
-    } else if (r) {
-      const bool kmask = fused && h->p.prop_decrease == 1.0;   // the bit-mask stages left uint16 sums, no float mask
-      if ((rc = stage_apply_reg(h, r, v, g, nb, om, kmask ? nullptr : (const float*)h->M.p, 1, st))) return rc;
-    } else if (fused && h->dbg_k16_only) {
-      if ((rc = stage_apply_ola(h, v, g, nb, nullptr, om, 1, st, (const unsigned short*)h->K16.p, 1.0f / (float)h->ktot))) return rc;
-    } else {
-      if ((rc = stage_apply_ola(h, v, g, nb, (const float*)h->M.p, om, 1, st))) return rc;
+    switch (pl.apply) {
+      case Apply::FAST_K: rc = stage_apply_fast(h, v, g, nb, om, nullptr, 1, st); break;
+      case Apply::FAST_M: rc = stage_apply_fast(h, v, g, nb, om, Mf, 1, st); break;
+      case Apply::REG_K: rc = stage_apply_reg(h, r, v, g, nb, om, nullptr, 1, st); break;   // the bit-mask stages left uint16 sums, no float mask
+      case Apply::REG_M: rc = stage_apply_reg(h, r, v, g, nb, om, Mf, 1, st); break;
+      case Apply::OLA_K: rc = stage_apply_ola(h, v, g, nb, nullptr, om, 1, st, (const unsigned short*)h->K16.p, 1.0f / (float)h->ktot); break;
+      default: rc = stage_apply_ola(h, v, g, nb, Mf, om, 1, st); break;
     }
-    h->dbg_units = nb;
-    h->dbg_T = g.T;
-    h->dbg_has_P = h->p.stationary != 0 && !fused;
-    h->dbg_has_raw = h->p.stationary || !nonstat2_chain_ok(h, g) || (!nonstat2_ok(h, g) && h->p.smooth_mask);
-    h->dbg_fused = fused;
+    if (rc) return rc;
+    note_batch(h, pl.facts, nb, g, dec);
   }
   return SG_OK;
 }
 
-// TorchGate.forward of whole rows in one kernel (rowgate.hpp): variant T, stationary, statistics from the row itself,
-// default geometry, rows of at most 64 frames (1 s clips at 16 kHz: 63), full reduction, smoothing filter within the
-// kernel's sliding-window limits.
-// One workgroup per row and one workgroup per CU at a time: a call of fewer rows than ~2/3 of the CUs is faster on the
-// four-kernel path, which spreads a row over 5 workgroups (256 x 16000: 0.110 vs 0.146 ms; 128 rows: ~0.105 vs 0.097;
-// 1024 rows: 0.45 vs 0.52; profiles/r04_rowgate_scale.json).
-constexpr int64_t RG_MIN_ROWS = 160;
-static bool rowgate_ok(const sg_handle* h, const Geom& g, int64_t rows) {
-  if (h->rowgate_mode == 1 || (h->rowgate_mode == 0 && rows < RG_MIN_ROWS)) return false;
-  return h->fast_ok && !h->force_nofast && !h->force_unfused && h->p.stationary &&
-         h->p.prop_decrease == 1.0 && h->p.smooth_mask && h->ktot <= 65535 && g.F == 513 && g.T >= 1 &&
-         g.T <= fast::RG_FRAMES && h->p.n_grad_freq >= 1 && h->p.n_grad_freq <= fast::RG_NFMAX &&
-         h->p.n_grad_time >= 1 && h->p.n_grad_time <= fast::RG_NTMAX;
-}
-
+// (TorchGate.forward of whole rows in one kernel, rowgate.hpp: route.hpp, rowgate_ok)
 static int stage_row_gate(sg_handle* h, const View& v, const Geom& g, int64_t nb, const OutMap& om, float* mask_out,
                           hipStream_t st) {
   int rc;
@@ -2192,38 +2172,28 @@ extern "C" int sg_workspace_bytes(const sg_handle* h, int64_t C, int64_t N, int3
   const int64_t units = chunked ? C * ((N + cs - 1) / cs) : C;
   if (Lp < h->W) return SG_E_INVALID;
   const Geom g = make_geom(h, Lp);
-  // the decisions of run_S: one-pass gate (any prop_decrease) or the three-kernel bit-mask path -> lean workspace
-  const bool geom_fast = h->fast_ok && !h->force_nofast;
-  const bool onepass = h->p.variant == SG_VARIANT_S && h->fused_ok && !h->force_unfused && geom_fast && !h->force_split &&
-                       !h->force_f64_decide && !h->force_noseam && !h->force_nolean && h->p.smooth_mask &&
-                       h->p.n_grad_freq <= 8 && h->p.n_grad_time <= fast::OP_MAX_NT && h->ftab3.p != nullptr;
-  const bool lean = h->p.variant == SG_VARIANT_S && h->fused_ok && !h->force_unfused && geom_fast &&
-                    (onepass || h->p.prop_decrease == 1.0);
-  const int64_t ub = units_per_batch(h, g, units, lean);
-  int64_t total = ub * (int64_t)unit_bytes(h, g, lean);
-  if (geom_fast) {
-    // exchange buffers of the in-launch hand-offs (tagged granules): mask bits (one-pass gate) and partial hops
-    const int64_t kept = chunked ? cs : N;
-    const int64_t n_tiles = (kept / 256 + 1 + 3 + 15) / 16 + 1;
-    total += ub * n_tiles * 3 * 256 * 8 + ub * 64;
-    if (onepass) total += ub * (n_tiles + 2) * (int64_t)fast::OP_TILE_WORDS * 8;
-    // a recording that is not float32 is converted once (UPPER bound: float32 recordings do not pay this)
-    total += C * N * (int64_t)sizeof(float);
-  }
-  if (h->big_M) {   // long frames: two work buffers of <= 256 MB (big.hpp)
-    const int64_t nb = big_batch(h, units * g.T);
-    total += 2 * nb * (int64_t)h->big_M * (int64_t)sizeof(big::cd);
-  }
-  // Integer (SG_I16 / SG_I32) outputs take the float64 pipeline by default, SG_OPT_FORCE_EXACT selects it for every dtype
-  // (run_S_exact: 32 B per cell + float64 frames).  The entry point has no dtype argument, so the figure is the LARGER
-  // of the two pipelines unless the handle can never take the float64 one for this call (SG_OPT_FAST_INTEGER set and
-  // SG_OPT_FORCE_EXACT clear) -- an upper bound, as documented in the header.
-  if (h->p.variant == SG_VARIANT_S && (h->force_exact || !h->fast_integer)) {
-    int64_t ex = exact_units_per_batch(h, g, units) * (int64_t)exact_unit_bytes(g);
-    if (h->big_M) ex += 2 * big_batch(h, units * g.T) * (int64_t)h->big_M * (int64_t)sizeof(big::cd);
-    if (h->force_exact) total = ex;
-    else total = std::max(total, ex);
-  }
+  // What run_S's route allocates (route.hpp: plan_S, workspace_S), for the whole range of the recording: the fields of a
+  // batch, the exchange buffers of the in-launch hand-offs and seams, the float32 copy of a recording that is not float32
+  // (UPPER bound: the entry point has no dtype argument, and float32 recordings do not pay it), the long frames' two work
+  // buffers of <= 256 MB (big.hpp).
+  const route::RouteCaps caps = route_caps(h);
+  route::RouteShape shape = route_shape(caps, g, pad, pad + (chunked ? cs : N), SG_I16, SG_F32, units);
+  auto figure = [&](route::SPlan pl) {
+    // (the float64 pipeline at its materialised figure, 32 B per cell + float64 frames, whichever of its forms would run)
+    if (pl.pipe == route::Pipe::EXACT_FUSED) { pl = route::SPlan{}; pl.pipe = route::Pipe::EXACT; }
+    const route::Workspace w = route::workspace_S(caps, pl, shape, units);
+    int64_t t = w.total();
+    if (pl.f32_copy) t += C * N * (int64_t)sizeof(float);
+    if (caps.geom == route::GeomClass::LONG) t += 2 * big_batch(h, units * g.T) * (int64_t)h->big_M * (int64_t)sizeof(big::cd);
+    return t;
+  };
+  int64_t total = figure(route::plan_S(caps, shape));
+  // Integer (SG_I16 / SG_I32) outputs take the float64 pipeline by default, SG_OPT_FORCE_EXACT selects it for every dtype.
+  // No dtype argument here either, so the figure is the LARGER of the two outputs' routes (they are one route when the
+  // handle can never take the float64 pipeline for this call, SG_OPT_FAST_INTEGER, or always does) -- an upper bound, as
+  // documented in the header.
+  shape.out_dtype = SG_I16;
+  if (caps.variant == SG_VARIANT_S) total = std::max(total, figure(route::plan_S(caps, shape)));
   *bytes = total;
   return SG_OK;
 }
@@ -2390,31 +2360,21 @@ struct Sink {
   FeatSink feat;                          // FEATURES
 };
 
-// (host bookkeeping behind sg_debug_fetch: what the last sub-batch left in the workspace)
-static void note_batch(sg_handle* h, int64_t nb, const Geom& g, bool has_P, bool fused, bool fast) {
-  h->dbg_units = nb; h->dbg_T = g.T; h->dbg_has_P = has_P; h->dbg_fused = fused; h->dbg_fast = fast;
-}
-
-// default geometry, full reduction: decisions as bits -> exact integer smoothing -> uint16 sums
-// read by the fused apply kernel (same stages as the variant-S fused path)
-static bool bits_path_ok(const sg_handle* h) {
-  return h->fast_ok && !h->force_nofast && !h->force_unfused && h->p.prop_decrease == 1.0 &&
-         h->ktot <= 65535 && (!h->p.smooth_mask || (h->p.n_grad_time <= 96 && h->t_sm2_ok));
-}
-
-// The stationary decisions of one sub-batch (v.unit0 = u0): the thresholds (the shared noise row's in h->thresh, each
-// row's own noise, or the rows themselves), the power field and the compare.  With bits_path the decisions are bits in
-// h->bits, and with to_raw also the 0 / 1 float field in h->raw; without it the float field of stage_decide.  *branch:
-// which statement decided (sg_debug_counter 18), 0 when the bits are all that is left.
-static int decide_stationary(sg_handle* h, const View& v, View vn, const Geom& g, const Geom& gn, int64_t nb,
-                             const void* xn_dev, int64_t Bn, bool bits_path, bool to_raw, hipStream_t st, int64_t* branch) {
+// The stationary decisions of one sub-batch (v.unit0 = u0): the thresholds (pl.thresh: the shared noise row's in h->thresh,
+// each row's own noise, or the rows themselves), the power field and the compare.  With pl.bits_path (default geometry, full
+// reduction: the stages of the variant-S fused path) the decisions are bits in h->bits, and with pl.to_raw also the 0 / 1
+// float field in h->raw; without it the float field of stage_decide.  *branch: which statement decided (sg_debug_counter
+// 18), 0 when the bits are all that is left.
+static int decide_stationary(sg_handle* h, const route::TPlan& pl, const View& v, View vn, const Geom& g, const Geom& gn,
+                             int64_t nb, hipStream_t st, int64_t* branch) {
   int rc;
   double* thr = (double*)h->thr_rows.p;
   const double* th;
   int64_t ustride;
-  if (xn_dev && Bn == 1) {
+  const bool bits_path = pl.bits_path, row_fused = pl.row_fused, to_raw = pl.to_raw;
+  if (pl.thresh == route::Thresh::SHARED) {
     th = (const double*)h->thresh.p; ustride = 0;
-  } else if (xn_dev) {
+  } else if (pl.thresh == route::Thresh::PER_ROW) {
     vn.unit0 = v.unit0;
     if ((rc = stage_stats(h, vn, gn, nb, thr, st))) return rc;
     th = thr; ustride = g.FS;
@@ -2423,7 +2383,6 @@ static int decide_stationary(sg_handle* h, const View& v, View vn, const Geom& g
   }
   // short rows: statistics + constants + decisions of a (row, 64 bands) tile in one kernel
   const size_t tile_bytes = (size_t)g.T * 64 * sizeof(double);
-  const bool row_fused = bits_path && tile_bytes <= 64 * 1024;
   if (row_fused) {
     ProfScope ps(h, SG_STAGE_STFT_POWER, st);
     HIPCHK(h, stft_any<double>(h, v, g, nb, (double*)h->P.p, nullptr, nullptr, 1.0, st));
@@ -2481,7 +2440,6 @@ static int process_batch_impl(sg_handle* h, const void* x_dev, int dtype, int64_
   int rc;
   if ((rc = t_min_lengths(h, B, L, xn_dev, Bn, Ln))) return rc;
   hipStream_t st = (hipStream_t)stream;
-  h->dbg_rg = false;
   h->smooth_route = 0;   // (as in run_S)
   View v = rows_view(x_dev, dtype, x_stride, L);
   Geom g = make_geom(h, L);
@@ -2498,8 +2456,11 @@ static int process_batch_impl(sg_handle* h, const void* x_dev, int dtype, int64_
   int64_t ub = units_per_batch(h, gbig, B);
   if ((rc = ensure_ws(h, gbig, ub))) return rc;
   if (noise && Bn == 1 && (rc = stage_stats(h, vn, gn, 1, (double*)h->thresh.p, st))) return rc;
-  const bool geom_fast = h->fast_ok && !h->force_nofast;
-  const bool smooths = h->p.stationary || !box_mask_ok(h);   // (the box mask comes smoothed out of its one kernel)
+  const route::RouteCaps caps = route_caps(h);
+  route::RouteShape shape = route_shape(caps, g, om.p0, om.p1, dtype, sink.dtype, B);
+  shape.field = field; shape.noise_rows = xn_dev ? Bn : 0;
+  const route::TPlan pl = route::plan_T(caps, shape);
+  const bool smooths = pl.smooths;
   int64_t n_sub = 0;
   for (int64_t u0 = 0; u0 < B; u0 += ub) {
     int64_t nb = std::min(ub, B - u0);
@@ -2507,18 +2468,15 @@ static int process_batch_impl(sg_handle* h, const void* x_dev, int dtype, int64_
     float* const mask_out = mask_out_dev ? mask_out_dev + (size_t)u0 * g.T * g.FS : nullptr;
     v.unit0 = u0;
     // 1. the decisions
-    if (h->p.stationary) {
-      if (!field && !xn_dev && rowgate_ok(h, g, B)) {
-        // one kernel per call: a workgroup per row (rowgate.hpp)
-        if ((rc = stage_row_gate(h, v, g, nb, om, mask_out, st))) return rc;
-        note_batch(h, nb, g, false, true, true);
-        h->dbg_has_raw = false; h->dbg_xbits = false; h->dbg_rg = true;
-        h->dbg_db = 0; h->dbg_de = g.T;
-        continue;
-      }
-      const bool bits_path = bits_path_ok(h);
-      if ((rc = decide_stationary(h, v, vn, g, gn, nb, xn_dev, Bn, bits_path, field, st, &branch))) return rc;
-      if (bits_path && !field) {
+    if (pl.rowgate) {
+      // one kernel per call: a workgroup per row (rowgate.hpp)
+      if ((rc = stage_row_gate(h, v, g, nb, om, mask_out, st))) return rc;
+      note_batch(h, pl.facts, nb, g);
+      continue;
+    }
+    if (pl.ns == route::NsMask::NONE) {
+      if ((rc = decide_stationary(h, pl, v, vn, g, gn, nb, st, &branch))) return rc;
+      if (pl.apply == route::Apply::FAST_K) {
         // the bits straight through the integer smoothing into the fused apply kernel
         if ((rc = stage_smooth_bits(h, g, nb, true, 0, g.T, st))) return rc;
         if (mask_out) {  // float mask (natural bin order) for the backward pass
@@ -2527,11 +2485,10 @@ static int process_batch_impl(sg_handle* h, const void* x_dev, int dtype, int64_
           HIPCHK(h, hipGetLastError());
         }
         if ((rc = stage_apply_fast(h, v, g, nb, om, nullptr, 1, st))) return rc;
-        note_batch(h, nb, g, true, true, true);
-        h->dbg_db = 0; h->dbg_de = g.T;
+        note_batch(h, pl.facts, nb, g);
         continue;
       }
-    } else if (box_mask_ok(h)) {
+    } else if (pl.ns == route::NsMask::BOX) {
       if ((rc = stage_box_mask(h, v, g, nb, st))) return rc;
       branch = SG_SPEC_BOX_MASK;
     } else {
@@ -2551,15 +2508,14 @@ static int process_batch_impl(sg_handle* h, const void* x_dev, int dtype, int64_
       h->spec_route = branch | (mask_direct ? SG_SPEC_MASK_DIRECT : 0) | (++n_sub << 16);
     } else if (sink.kind == Sink::FEATURES) {
       if ((rc = stage_features(h, v, g, u0, nb, mask, sink.feat, dtype, st))) return rc;
-    } else if (geom_fast) {
+    } else if (pl.apply == route::Apply::FAST_M) {
       if ((rc = stage_apply_fast(h, v, g, nb, om, (const float*)h->M.p, 1, st))) return rc;
-    } else if (const RegGeom* r = reg_geom(h)) {
-      if ((rc = stage_apply_reg(h, r, v, g, nb, om, (const float*)h->M.p, 1, st))) return rc;
+    } else if (pl.apply == route::Apply::REG_M) {
+      if ((rc = stage_apply_reg(h, h->reg, v, g, nb, om, (const float*)h->M.p, 1, st))) return rc;
     } else {
       if ((rc = stage_apply_ola(h, v, g, nb, (const float*)h->M.p, om, 1, st))) return rc;
     }
-    note_batch(h, nb, g, h->p.stationary != 0, false, geom_fast);
-    h->dbg_has_raw = smooths;
+    note_batch(h, pl.facts, nb, g);
   }
   return SG_OK;
 }
@@ -2772,8 +2728,8 @@ int sg::host::expand_k16_mask(sg_handle* h, size_t cells, hipStream_t st) {
   // (a debug entry point: whatever stream produced the counts has to be done first)
   HIPCHK(h, hipDeviceSynchronize());
   hipLaunchKernelGGL(k_k16_to_mask, dim3(grid_1d((int64_t)cells / 8, 256)), dim3(256), 0, st,
-                     (const unsigned short*)h->K16.p, h->dbg_g, h->p.n_grad_freq, h->p.n_grad_time, 1.0f / (float)h->ktot,
-                     (float)h->p.prop_decrease, 1, h->p.smooth_mask ? 1 : 0, (float*)h->M.p, (int64_t)h->dbg_units);
+                     (const unsigned short*)h->K16.p, h->last.g, h->p.n_grad_freq, h->p.n_grad_time, 1.0f / (float)h->ktot,
+                     (float)h->p.prop_decrease, 1, h->p.smooth_mask ? 1 : 0, (float*)h->M.p, (int64_t)h->last.units);
   HIPCHK(h, hipGetLastError());
   return SG_OK;
 }

@@ -130,13 +130,13 @@ extern "C" const char* sg_stage_name(int32_t stage) {
 
 extern "C" int sg_debug_dims(const sg_handle* h, int64_t dims[3]) {
   if (!h || !dims) return SG_E_INVALID;
-  dims[0] = h->dbg_units; dims[1] = h->dbg_T; dims[2] = h->FS;
+  dims[0] = h->last.units; dims[1] = h->last.T; dims[2] = h->FS;
   return SG_OK;
 }
 
 extern "C" int sg_debug_range(const sg_handle* h, int64_t range[2]) {
   if (!h || !range) return SG_E_INVALID;
-  range[0] = h->dbg_db; range[1] = h->dbg_de;
+  range[0] = h->last.db; range[1] = h->last.de;
   return SG_OK;
 }
 
@@ -196,57 +196,57 @@ extern "C" int sg_debug_fetch(sg_handle* h, int32_t what, void* host, int64_t by
     HIPCHK(h, hipStreamSynchronize((hipStream_t)stream));
     return SG_OK;
   }
-  if (!host || h->dbg_units == 0) FAIL(h, SG_E_STATE, "sg_debug_fetch: nothing processed yet");
-  size_t cells = (size_t)h->dbg_units * h->dbg_T * h->FS;
+  if (!host || h->last.units == 0) FAIL(h, SG_E_STATE, "sg_debug_fetch: nothing processed yet");
+  size_t cells = (size_t)h->last.units * h->last.T * h->FS;
   const void* src;
   size_t need;
   switch (what) {
     case 0:
-      if (h->dbg_fused) FAIL(h, SG_E_STATE, "fused path keeps the raw mask as bits: fetch field 3");
-      if (!h->dbg_has_raw)
+      if (h->last.fused) FAIL(h, SG_E_STATE, "fused path keeps the raw mask as bits: fetch field 3");
+      if (!h->last.has_raw)
         FAIL(h, SG_E_STATE, "the one-kernel non-stationary mask does not materialise the raw mask: set SG_OPT_FORCE_UNFUSED");
       src = h->raw.p; need = cells * 4; break;
     case 3:
-      if (!h->dbg_fused) FAIL(h, SG_E_STATE, "bit field only exists on the fused path");
-      src = h->bits.p; need = (size_t)h->dbg_units * h->dbg_T * ((h->F + 63) / 64) * 8; break;
+      if (!h->last.fused) FAIL(h, SG_E_STATE, "bit field only exists on the fused path");
+      src = h->bits.p; need = (size_t)h->last.units * h->last.T * ((h->F + 63) / 64) * 8; break;
     case 1:
-      if (h->dbg_fast && h->dbg_fused)
+      if (h->last.fast && h->last.fused)
         FAIL(h, SG_E_STATE, "fast path keeps the smoothed mask as uint16 counts in the apply kernel's lane order");
-      if (h->dbg_fused && h->dbg_k16_only) {
+      if (h->last.fused && h->last.k16_only) {
         // the apply kernel read the K counts directly: expand them now (api.hip)
         if (int rc = expand_k16_mask(h, cells, (hipStream_t)stream)) return rc;
       }
       src = h->M.p; need = cells * 4; break;
     case 2:
-      if (!h->dbg_has_P) FAIL(h, SG_E_STATE, "power field only exists for stationary gates");
+      if (!h->last.has_P) FAIL(h, SG_E_STATE, "power field only exists for stationary gates");
       src = h->P.p; need = cells * 8; break;
     case 4:
-      if (!h->dbg_rg || !h->rg_tap) FAIL(h, SG_E_STATE, "row-gate power tile: set SG_OPT_ROWGATE_TAP and run TorchGate.forward");
-      src = h->M.p; need = (size_t)h->dbg_units * 64 * fast::RG_PP * 4; break;
+      if (!h->last.rg || !h->rg_tap) FAIL(h, SG_E_STATE, "row-gate power tile: set SG_OPT_ROWGATE_TAP and run TorchGate.forward");
+      src = h->M.p; need = (size_t)h->last.units * 64 * fast::RG_PP * 4; break;
     default: FAIL(h, SG_E_INVALID, "sg_debug_fetch: unknown field %d", what);
   }
   if ((size_t)bytes != need) FAIL(h, SG_E_INVALID, "sg_debug_fetch: need %zu bytes, got %lld", need, (long long)bytes);
   HIPCHK(h, hipStreamSynchronize((hipStream_t)stream));
   { int rc = handoff_verdict(h); if (rc) return rc; }
-  if (what == 3 && h->dbg_xbits) {
+  if (what == 3 && h->last.xbits) {
     // one-pass path: the bits live tile-blocked in the exchange buffer [unit][tile][16][9]; rearrange into
     // the natural [unit][T][wpr] layout (frames outside sg_debug_range stay zero)
     const int wpr = (h->F + 63) / 64;
-    const int TW = h->dbg_twords ? h->dbg_twords : fast::OP_TILE_WORDS, XW = h->dbg_txw;
-    const size_t words = (size_t)h->dbg_units * h->dbg_ntt * TW;
+    const int TW = h->last.tiles.words ? h->last.tiles.words : fast::OP_TILE_WORDS, XW = h->last.tiles.xw;
+    const size_t words = (size_t)h->last.units * h->last.tiles.ntt * TW;
     std::vector<unsigned long long> tmp(words);
     HIPCHK(h, hipMemcpy(tmp.data(), h->xbits.p, words * 8, hipMemcpyDeviceToHost));
     unsigned long long* dst = (unsigned long long*)host;
     std::memset(dst, 0, need);
-    for (int64_t u = 0; u < h->dbg_units; ++u)
-      for (int64_t j = 0; j < h->dbg_ntt; ++j)
-        for (int i = 0; i < h->dbg_trows; ++i) {
-          const int64_t t = h->dbg_tf0 + (j - 1) * h->dbg_tstep + i;
-          if (t < 0 || t >= h->dbg_T) continue;
+    for (int64_t u = 0; u < h->last.units; ++u)
+      for (int64_t j = 0; j < h->last.tiles.ntt; ++j)
+        for (int i = 0; i < h->last.tiles.rows; ++i) {
+          const int64_t t = h->last.tiles.f0 + (j - 1) * h->last.tiles.step + i;
+          if (t < 0 || t >= h->last.T) continue;
           for (int w = 0; w < wpr; ++w)
           {
-            const unsigned long long* gr = &tmp[((size_t)u * h->dbg_ntt + j) * TW + (i * XW + w) * 2];
-            dst[(u * h->dbg_T + t) * wpr + w] = (gr[0] & 0xffffffffull) | (gr[1] << 32);
+            const unsigned long long* gr = &tmp[((size_t)u * h->last.tiles.ntt + j) * TW + (i * XW + w) * 2];
+            dst[(u * h->last.T + t) * wpr + w] = (gr[0] & 0xffffffffull) | (gr[1] << 32);
           }
         }
     return SG_OK;

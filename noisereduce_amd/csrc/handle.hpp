@@ -14,6 +14,7 @@
 #include "geom.hpp"
 #include "mixed.hpp"
 #include "ragged.hpp"
+#include "route.hpp"
 #include "rows.hpp"
 #include "spec.hpp"
 
@@ -46,14 +47,7 @@ inline std::string fmt(const char* f, ...) {
   return buf;
 }
 
-// geometry constants of a one-pass gate: tiles of NF frames every NH frames
-struct OnePassGeom {
-  int hop, NF, NH, tile_words, xw, max_nf, max_nt, F;
-  size_t lds;      // dynamic LDS (n_fft = 1024: + OP_PROP_LDS when prop_decrease != 1)
-  int extra = 0;   // 3 when the tiles abut (NH == NF, abutting_tiles), 0 when they overlap by 3 frames
-  int64_t tiles(int64_t nh) const { return (nh + extra + NH - 1) / NH; }
-};
-
+// (OnePassGeom, the geometry constants of a one-pass gate: route.hpp)
 struct RegGeom {
   int n_fft, hop;
   int frames;                 // frames per decide / magnitude tile and per abutting apply tile
@@ -71,6 +65,32 @@ struct RegGeom {
 };
 // (defined next to the kernels they point to: api.hip)
 extern const RegGeom REG512, REG256, REG2048;
+
+// What only a stage knows of the batch it ran: the frames whose mask bits it decided and, for a one-pass gate, how its tiles
+// lie in the exchange buffer xbits -- tiles of `rows` frames every `step` frames, `words` granule halves each, `xw` words per
+// row, tile 0 starting at frame f0, ntt tiles per unit incl. the two halo tiles
+struct TileLayout {
+  int rows = 16, step = 16, words = 0, xw = 9, ntt = 0;
+  int64_t f0 = 0;
+};
+struct Decided {
+  int64_t db = 0, de = 0;
+  TileLayout tiles;
+};
+// What the last batch left in the workspace: the state behind sg_debug_fetch, sg_debug_dims and sg_debug_range (debug.hip).
+// Written by note_batch (api.hip) and nowhere else, from the plan's BatchFacts (route.hpp) and the stage's Decided.
+struct LastBatch {
+  int64_t units = 0, T = 0;
+  bool has_P = false;
+  bool has_raw = true;    // the unsmoothed mask field exists (not when k_iir_mask / k_box_mask produced the mask in one kernel)
+  bool fused = false, fast = false;
+  bool k16_only = false;  // a fused general-geometry batch that left K counts only (no float mask field): g is its geometry
+  bool rg = false;        // the batch ran on the row gate
+  bool xbits = false;     // the mask bits live in xbits, tile-blocked as `tiles` says
+  int64_t db = 0, de = 0; // frames whose mask bits were decided
+  TileLayout tiles;
+  sg::Geom g{};
+};
 
 }  // namespace host
 }  // namespace sg
@@ -137,13 +157,8 @@ struct sg_handle {
   int floor_test = 0;                // SG_OPT_FLOOR_TEST: one-pass gate's floor test 0 = predicted, 1 = a priori, 2 = in the gate kernel
   int rg_shape = 16;                 // SG_OPT_ROWGATE_SHAPE: waves per workgroup of the row gate (16 x 1 quad, or 8 x 2 quads)
   bool rg_tap = false;               // SG_OPT_ROWGATE_TAP: keep the row gate's float32 power tile (stage tap 4)
-  bool dbg_rg = false;               // the last batch ran on the row gate
   int dbg_bwd_route = 0;             // sg_debug_backward_route: SG_BWD_* of the last backward call (0: none yet)
   DevBuf rg_count;                   // k_row_gate: number of (row, band) pairs that took the exact path (one counter, never reset)
-  bool dbg_xbits = false;            // the last batch's mask bits live in xbits (tile-blocked)
-  int dbg_trows = 16, dbg_tstep = 16, dbg_twords = 0, dbg_txw = 9;   // ... in tiles of trows frames every tstep frames, twords granule halves, txw words per row
-  int64_t dbg_tf0 = 0;               // first frame of tile 0 of that batch
-  int dbg_ntt = 0;                   // tiles per unit incl. the two halo tiles
   int big_M = 0;                     // > 0: long frames (n_fft > 8192, or > 4096 and not a power of two): four-step
                                      // transform of size M through HBM (big.hpp); big_czt: chirp-z on top of it
   int big_czt = 0;
@@ -163,14 +178,7 @@ struct sg_handle {
   int64_t ktot = 1;                  // (nf+1)^2 (nt+1)^2: integer weight total of the smoothing filter
   bool fused_ok = false;
   double sum_abs_w = 0.0;
-  int64_t dbg_units = 0, dbg_T = 0;
-  bool dbg_has_P = false;
-  bool dbg_has_raw = true;           // the unsmoothed mask field exists (not when k_iir_mask / k_box_mask produced the mask in one kernel)
-  bool dbg_fused = false;
-  bool dbg_fast = false;
-  bool dbg_k16_only = false;         // the last fused general-geometry batch left K counts only (no float mask field): dbg_g
-  Geom dbg_g{};
-  int64_t dbg_db = 0, dbg_de = 0;  // frames whose mask bits were decided in the last batch
+  sg::host::LastBatch last;    // sg_debug_fetch / sg_debug_dims / sg_debug_range: what the last batch left (note_batch)
   bool force_unfused = false;  // sg_set_option(SG_OPT_FORCE_UNFUSED): materialised v1 path
   // per-kernel timing with HIP events on the launch stream (sg_profile_*)
   bool roctx_on = false;       // SG_ROCTX=1: a roctx range around every stage's enqueue
