@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/mi355gate_debug.h"
+#include "devbuf.hpp"
 #include "feat.hpp"
 #include "geom.hpp"
 #include "mixed.hpp"
@@ -25,18 +26,6 @@ struct OnePassRegArgs;
 struct SeamArgs;
 }  // namespace fast
 namespace host {
-
-// A device allocation its holder owns: freed with the holder (sg_destroy deletes the handle after a device synchronise)
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
 
 inline std::string fmt(const char* f, ...) {
   char buf[512];

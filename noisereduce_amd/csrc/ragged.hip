@@ -254,20 +254,12 @@ __global__ __launch_bounds__(256) void k_rg_ola(RgArgs A) {
 
 // ---- host side ---------------------------------------------------------------------------------------------------
 struct RgState {
-  void* ws = nullptr;
-  size_t ws_bytes = 0;
-  double* thr = nullptr;
-  size_t thr_bytes = 0;
+  host::DevBuf ws, thr;
   int64_t last_noise = 0, last_batches = 0;
   int FS = 0;
 };
 
-void rg_free(RgState* s) {
-  if (!s) return;
-  if (s->ws) (void)hipFree(s->ws);
-  if (s->thr) (void)hipFree(s->thr);
-  delete s;
-}
+void rg_free(RgState* s) { delete s; }
 
 int64_t rg_last_batches(const RgState* s) { return s ? s->last_batches : 0; }
 
@@ -419,13 +411,13 @@ int rg_workspace_bytes(const RgCtx& c, const sg_noise_src* noise, int32_t n_nois
 }
 
 int rg_thresholds(RgState* s, double* host, int32_t n_noise, int32_t n_bins, hipStream_t st, std::string* err) {
-  if (!s || !s->thr || n_noise != s->last_noise) {
+  if (!s || !s->thr.p || n_noise != s->last_noise) {
     *err = "sg_debug_clip_thresholds: n_noise does not match the last sg_process_clips call";
     return SG_E_STATE;
   }
   if (hipStreamSynchronize(st) != hipSuccess) { *err = "hipStreamSynchronize failed"; return SG_E_HIP; }
   std::vector<double> tmp((size_t)n_noise * s->FS);
-  if (!tmp.empty() && hipMemcpy(tmp.data(), s->thr, tmp.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) {
+  if (!tmp.empty() && hipMemcpy(tmp.data(), s->thr.p, tmp.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) {
     *err = "hipMemcpy failed";
     return SG_E_HIP;
   }
@@ -459,10 +451,10 @@ int rg_process(RgState** sp, const RgCtx& c, const void* x_dev, int in_dtype, co
   S->last_batches = 0;
   if (c.stationary && n_noise > 0) {
     const size_t tb = (size_t)n_noise * c.FS * 8;
-    if (S->thr_bytes < tb) {
-      if (S->thr) { (void)hipStreamSynchronize(st); (void)hipFree(S->thr); S->thr = nullptr; S->thr_bytes = 0; }
-      if (hipMalloc(&S->thr, tb) != hipSuccess) { S->thr = nullptr; *err = "threshold buffer allocation failed"; return SG_E_NOMEM; }
-      S->thr_bytes = tb;
+    if (S->thr.bytes < tb) {
+      if (S->thr.p) { (void)hipStreamSynchronize(st); S->thr.release(); }
+      if (hipMalloc(&S->thr.p, tb) != hipSuccess) { S->thr.p = nullptr; *err = "threshold buffer allocation failed"; return SG_E_NOMEM; }
+      S->thr.bytes = tb;
     }
   }
   if (max_ws <= 0) max_ws = (int64_t)4 << 30;
@@ -542,8 +534,8 @@ int rg_process(RgState** sp, const RgCtx& c, const void* x_dev, int in_dtype, co
       return SG_E_STATE;
     }
     Layout L = layout(c, nu, nn, noise_rows, P.drows, P.frows, P.mrows, P.sframes, ntl);
-    if ((rc = grow_device_buffer(&S->ws, &S->ws_bytes, L.total, st, "sg_process_clips", "workspace", err))) return rc;
-    char* w = (char*)S->ws;
+    if ((rc = grow_device_buffer(S->ws, L.total, st, "sg_process_clips", "workspace", err))) return rc;
+    char* w = S->ws.as<char>();
     const size_t ub = nu * sizeof(RgUnit), nb = nn * sizeof(RgNoise), tb = ntl * sizeof(Tile);
     if (upload_tables(w + L.tabs, st, {{P.units.data(), ub, ub}, {noises.data(), nb, nb}, {tl.tiles.data(), tb, tb}}) != hipSuccess) {
       *err = "sg_process_clips: table upload failed";
@@ -558,7 +550,7 @@ int rg_process(RgState** sp, const RgCtx& c, const void* x_dev, int in_dtype, co
     A.units = (const RgUnit*)(w + L.tabs);
     A.noises = (const RgNoise*)(w + L.tabs + ub);
     A.tiles = (const Tile*)(w + L.tabs + ub + nb);
-    A.Pn = (double*)(w + L.Pn); A.T2n = (double*)(w + L.T2n); A.thr_all = S->thr;
+    A.Pn = (double*)(w + L.Pn); A.T2n = (double*)(w + L.T2n); A.thr_all = S->thr.as<double>();
     A.pmax = (unsigned long long*)(w + L.pmax); A.bits = (unsigned long long*)(w + L.bits);
     A.mag = (float*)(w + L.mag); A.fw = (float*)(w + L.fw); A.sig = (float*)(w + L.sig); A.R = (float*)(w + L.R);
     A.seg = (float*)(w + L.seg);

@@ -256,16 +256,11 @@ __global__ __launch_bounds__(256) void k_rw_ola(RwArgs A) {
 
 // ---- host side ---------------------------------------------------------------------------------------------------
 struct RwState {
-  void* ws = nullptr;
-  size_t ws_bytes = 0;
+  host::DevBuf ws;
   int64_t last_batches = 0;
 };
 
-void rw_free(RwState* s) {
-  if (!s) return;
-  if (s->ws) (void)hipFree(s->ws);
-  delete s;
-}
+void rw_free(RwState* s) { delete s; }
 
 int64_t rw_last_batches(const RwState* s) { return s ? s->last_batches : 0; }
 
@@ -439,9 +434,9 @@ int run(RwState** sp, const RgCtx& c, int kbox, const Call& q, int64_t max_ws, h
       return SG_E_STATE;
     }
     const Layout Ly = z.layout(c, q.bwd, spec_fwd);
-    int rc = grow_device_buffer(&S->ws, &S->ws_bytes, Ly.total, st, who, "workspace", err);
+    int rc = grow_device_buffer(S->ws, Ly.total, st, who, "workspace", err);
     if (rc) return rc;
-    char* w = (char*)S->ws;
+    char* w = S->ws.as<char>();
     const size_t ub = nu * sizeof(RwRow), nb = nn * sizeof(RwNoise), tb = ntl * sizeof(Tile);
     if (upload_tables(w + Ly.tabs, st, {{rows.data(), ub, ub}, {noises.data(), nb, nb}, {tl.tiles.data(), tb, tb}}) != hipSuccess) {
       *err = std::string(who) + ": table upload failed";

@@ -56,35 +56,6 @@
 namespace sg {
 
 // ---- tables ------------------------------------------------------------------------------------------------------
-struct StUnit {
-  int64_t in_off, out_off;   // element of in holding the block's first sample / of out receiving sample E0
-  int64_t n0, n1;            // samples received before / after this step
-  int64_t td0, td1;          // last decided (transformed) frame before / after (-1: none)
-  int64_t ts0, ts1;          // non-stationary: last frame with a raw mask row before / after (td - lookahead; td at a flush)
-  int64_t ta0, ta1;          // last applied frame before / after
-  int64_t Tend;              // frames of the whole stream when flushing, else "unbounded"
-  int64_t Lout;              // flush: valid samples of the inverse transform (zero tail beyond)
-  int64_t E0, E1;            // emitted before / after
-  int64_t cov0;              // end of the samples the applied frames of earlier steps reach (carry valid below it)
-  int64_t r0, r1;            // mask rows the applied frames read
-  int64_t mrow, srow;        // first row of this unit in the smoothed-row / segment scratch
-  int32_t state;             // slot * channels + channel
-  int32_t slot;
-  int32_t par;               // carry buffer to read (the other one is written)
-  int32_t flush;
-};
-enum { ST_OLA = 0, ST_APPEND = 1, ST_CLEAR = 2 };   // Tile::kind of the finish stage
-// a unit's part of a spectrum step: the element of spec / smask holding bin 0 of its first newly applied frame (ta0 + 1);
-// the frames follow as consecutive rows of F bins
-struct StSpec {
-  int64_t spec_off, mask_off;
-};
-
-// a unit's part of a feature step: the element of feat holding filter 0 / of fmask holding bin 0 of its first newly applied
-// frame; the frames follow as consecutive rows of M filters / F bins
-struct StFeatUnit {
-  int64_t feat_off, mask_off;
-};
 // What k_st_feat needs beyond StArgs, as a second kernel argument (as RwFeat is k_rw_feat's).
 struct StFeat {
   FeatBank bank;          // the bank's own filterbank (sg_stream_set_filterbank)
@@ -571,12 +542,6 @@ __global__ __launch_bounds__(256) void k_st_export(StXArgs A) { st_copy_tile<fal
 __global__ __launch_bounds__(256) void k_st_import(StXArgs A) { st_copy_tile<true>(A); }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
-struct StSlot {
-  int64_t n = 0, td = -1, ts = -1, ta = -1, E = 0;
-  int par = 0;
-  bool has_thr = false;
-};
-
 struct StBank {
   RgCtx c{};
   int n_slots = 0, C = 0, RC = 0, RB = 0, wpr = 0;
@@ -586,46 +551,22 @@ struct StBank {
   double lam = 1.0;
   int64_t learn = -1;
   int64_t max_block = 0;
-  double *ring = nullptr, *rmax = nullptr, *carry = nullptr, *thr = nullptr, *T2 = nullptr, *stage = nullptr;
-  double *fst = nullptr, *fa = nullptr, *nst = nullptr;
-  void* mk = nullptr;
-  unsigned long long* bits = nullptr;
-  int32_t* slot_list = nullptr;
-  void* tabs = nullptr;
-  size_t tabs_bytes = 0;
-  void* ws = nullptr;
-  size_t ws_bytes = 0;
+  // the buffers of stream_plan.hpp's StLayout (a kind of bank leaves those it does not have empty); tabs and ws grow
+  host::DevBuf ring, carry, fst, fa, mk, rmax, bits, nst, thr, T2, stage, slot_list, tabs, ws;
   // the bank's own filterbank (st_set_filterbank): one allocation holding fb [F][M], fbT [M][F], khull [M] and mhull [F]
-  void* fbank = nullptr;
+  host::DevBuf fbank;
   FeatBank fb{};   // pointers into fbank; M == 0: none set
   std::vector<StSlot> slots;
 };
 
-static int64_t st_tdec(int W, int H, int64_t n) {
-  const int64_t a = n + W / 2 - W;
-  return a < 0 ? -1 : a / H;
-}
-
-int64_t st_emitted(int W, int H, int nt, int64_t n) {
-  const int64_t e = (st_tdec(W, H, n) - nt + 1) * (int64_t)H - W / 2;
-  return e > 0 ? e : 0;
-}
-
-void st_destroy(StBank* b) {
-  if (!b) return;
-  for (void* p : {(void*)b->ring, (void*)b->rmax, (void*)b->carry, (void*)b->thr, (void*)b->T2, (void*)b->stage, (void*)b->bits,
-                  (void*)b->fst, (void*)b->fa, (void*)b->nst, (void*)b->mk, (void*)b->slot_list, b->tabs, b->ws, b->fbank})
-    if (p) (void)hipFree(p);
-  delete b;
-}
+void st_destroy(StBank* b) { delete b; }
 
 namespace {
-constexpr int FPT = 2;     // frames per apply tile
-constexpr int RPT = 16;    // rows per smoothing tile
-constexpr size_t WS_PREALLOC = (size_t)256 << 20;
-
-// frames one step can decide or apply for a stream: those of max_block samples plus the zero-extended ones of a flush
-int64_t max_frames(const RgCtx& c, int64_t max_block) { return (max_block + c.W / 2) / c.H + 3; }
+StGeo st_geo(const RgCtx& c, int64_t channels, bool ns, int64_t lookahead, bool adaptive, bool exact) {
+  return st_make_geo(c.n, c.F, c.FS, c.W, c.H, c.nt, lookahead, channels,
+                     adaptive ? SG_STREAM_ADAPTIVE : ns ? SG_STREAM_NONSTATIONARY : SG_STREAM_FIXED, exact);
+}
+StGeo st_geo(const StBank* b) { return st_geo(b->c, b->C, b->ns != 0, b->L, b->ad != 0, b->exact != 0); }
 
 int check_slots(const StBank* b, const int32_t* slots, int32_t n, const char* who, std::string* err) {
   if (n < 0 || (n > 0 && !slots)) { *err = std::string(who) + ": bad slot list"; return SG_E_INVALID; }
@@ -653,13 +594,7 @@ hipError_t launch_feat_kernel(void (*kernel)(StArgs, StFeat), int64_t ntiles, hi
 
 int64_t st_state_bytes(const RgCtx& c, bool ns, int64_t n_slots, int64_t channels, int64_t max_block, int64_t L, bool adaptive,
                        bool exact) {
-  const int64_t nu = n_slots * channels, mf = max_frames(c, max_block);
-  const int64_t RC = c.W + (c.nt + L + 1) * c.H, RB = 2 * (int64_t)c.nt + 1 + L + mf;
-  int64_t per = RC * 8 + 2 * (int64_t)c.W * 8;
-  if (ns) per += (int64_t)c.FS * 8 + (L + 1 + mf) * 2 * c.FS * 8 + RB * c.FS * (exact ? 8 : 4);
-  else per += (int64_t)c.FS * 8 + RB * ((c.F + 63) / 64) * 8;
-  if (adaptive) per += 3 * (int64_t)c.FS * 8;
-  return nu * per;
+  return st_layout(st_geo(c, channels, ns, L, adaptive, exact), n_slots, max_block).state_bytes();
 }
 
 int st_create(StBank** out, const RgCtx& c, int32_t n_slots, int32_t channels, int64_t max_block, bool ns, int32_t lookahead,
@@ -705,10 +640,8 @@ int st_create(StBank** out, const RgCtx& c, int32_t n_slots, int32_t channels, i
     b->lam = ad->forget;
     b->learn = ad->learn_frames < 0 ? -1 : ad->learn_frames;
   }
-  // (a flush decides the L frames a push holds back on top of the block's own: the mask rows are L deeper for it)
-  const int64_t RC = c.W + ((int64_t)c.nt + b->L + 1) * c.H, RB = 2 * (int64_t)c.nt + 1 + b->L + max_frames(c, max_block);
-  const int64_t RF = (int64_t)b->L + 1 + max_frames(c, max_block);
-  if (ns && (RC > INT32_MAX || RF > INT32_MAX || RB > INT32_MAX)) {
+  const StLayout y = st_layout(st_geo(b), n_slots, max_block);
+  if (ns && (y.RC > INT32_MAX || y.RF > INT32_MAX || y.RB > INT32_MAX)) {
     char m[200];
     snprintf(m, sizeof m, "sg_stream_create_nonstationary: max_block = %lld with lookahead_frames = %d needs rings deeper than 2^31",
              (long long)max_block, b->L);
@@ -716,49 +649,29 @@ int st_create(StBank** out, const RgCtx& c, int32_t n_slots, int32_t channels, i
     delete b;
     return SG_E_INVALID;
   }
-  b->RC = (int)RC;
-  b->RB = (int)std::min<int64_t>(INT32_MAX, RB);
-  b->RF = (int)RF;
+  b->RC = (int)y.RC;
+  b->RB = (int)y.RB_ring;
+  b->RF = (int)y.RF;
   b->wpr = (c.F + 63) / 64;
   b->slots.assign(n_slots, StSlot());
   if (ns || ad)
     for (auto& sl : b->slots) sl.has_thr = true;   // a non-stationary or adaptive stream needs no noise profile
-  const size_t nu = (size_t)n_slots * channels;
+  // every buffer of the layout that this kind of bank has (the state that a fresh stream reads before writing it: zeroed)
+  const struct { host::DevBuf& buf; int64_t bytes; bool zero; } bufs[] = {
+      {b->ring, y.ring, false}, {b->carry, y.carry, false}, {b->fst, y.fst, true},     {b->fa, y.fa, false},
+      {b->mk, y.mk, false},     {b->rmax, y.rmax, true},    {b->bits, y.bits_alloc, false}, {b->nst, y.nst, true},
+      {b->thr, y.thr, true},    {b->T2, y.T2, true},        {b->stage, y.stage, true}, {b->slot_list, y.slot_list, true},
+      {b->tabs, y.tabs, false}, {b->ws, y.ws, false}};
   bool ok = true;
-  auto take = [&](void** p, size_t bytes, bool zero) {
-    if (!ok) return;
-    if (hipMalloc(p, bytes) != hipSuccess) { *p = nullptr; ok = false; return; }
-    if (zero && hipMemset(*p, 0, bytes) != hipSuccess) ok = false;
-  };
-  take((void**)&b->ring, nu * b->RC * 8, false);
-  take((void**)&b->carry, nu * 2 * c.W * 8, false);
-  if (ns) {
-    take((void**)&b->fst, nu * c.FS * 8, true);
-    take((void**)&b->fa, nu * (size_t)b->RF * 2 * c.FS * 8, false);
-    take(&b->mk, nu * (size_t)b->RB * c.FS * (exact ? 8 : 4), false);
-  } else {
-    take((void**)&b->rmax, nu * c.FS * 8, true);
-    take((void**)&b->bits, nu * (size_t)b->RB * b->wpr * 8, false);
-    if (ad) {
-      take((void**)&b->nst, nu * 3 * c.FS * 8, true);
-    } else {
-      take((void**)&b->thr, (size_t)n_slots * c.FS * 8, true);
-      take((void**)&b->T2, (size_t)n_slots * c.FS * 8, true);
-      take((void**)&b->stage, (size_t)c.FS * 8, true);
-    }
+  for (const auto& q : bufs) {
+    if (!q.bytes) continue;
+    if (hipMalloc(&q.buf.p, (size_t)q.bytes) != hipSuccess) { q.buf.p = nullptr; ok = false; break; }
+    q.buf.bytes = (size_t)q.bytes;
+    if (q.zero && hipMemset(q.buf.p, 0, (size_t)q.bytes) != hipSuccess) { ok = false; break; }
   }
-  take((void**)&b->slot_list, (size_t)n_slots * 4, true);
-  // tables and scratch of a typical step up front (a larger step grows them, which synchronises once)
-  const int64_t mf = max_frames(c, max_block);
-  b->tabs_bytes = align256(nu * sizeof(StUnit)) + align256(nu * 16 * sizeof(Tile)) + align256(nu * sizeof(StSpec));
-  take(&b->tabs, b->tabs_bytes, false);
-  const size_t per_unit = align256((size_t)(mf + 2 * c.nt) * c.FS * (exact && ns ? 8 : 4)) + align256((size_t)mf * c.n * (exact ? 8 : 4));
-  b->ws_bytes = std::min<size_t>(WS_PREALLOC, nu * per_unit);
-  take(&b->ws, b->ws_bytes, false);
   if (!ok) {
     char m[200];
-    snprintf(m, sizeof m, "sg_stream_create: device allocation failed (the bank's state is %lld bytes)",
-             (long long)st_state_bytes(c, ns, n_slots, channels, max_block, b->L, ad != nullptr, exact));
+    snprintf(m, sizeof m, "sg_stream_create: device allocation failed (the bank's state is %lld bytes)", (long long)y.state_bytes());
     st_destroy(b);
     *err = m;
     return SG_E_NOMEM;
@@ -777,17 +690,17 @@ int st_set_threshold(StBank* b, const int32_t* slots, int32_t n, const double* t
   if (n == 0) return SG_OK;
   const double* src = thresh_dev;
   if (thresh_host) {
-    if (hipMemcpyAsync(b->stage, thresh_host, (size_t)b->c.F * 8, hipMemcpyHostToDevice, st) != hipSuccess) {
+    if (hipMemcpyAsync(b->stage.p, thresh_host, (size_t)b->c.F * 8, hipMemcpyHostToDevice, st) != hipSuccess) {
       *err = "sg_stream_set_threshold: threshold upload failed";
       return SG_E_HIP;
     }
-    src = b->stage;
+    src = b->stage.as<double>();
   }
-  if (hipMemcpyAsync(b->slot_list, slots, (size_t)n * 4, hipMemcpyHostToDevice, st) != hipSuccess) {
+  if (hipMemcpyAsync(b->slot_list.p, slots, (size_t)n * 4, hipMemcpyHostToDevice, st) != hipSuccess) {
     *err = "sg_stream_set_threshold: slot list upload failed";
     return SG_E_HIP;
   }
-  hipLaunchKernelGGL(k_st_thresh, dim3(n), dim3(64), 0, st, src, b->slot_list, b->thr, b->T2, b->c.F,
+  hipLaunchKernelGGL(k_st_thresh, dim3(n), dim3(64), 0, st, src, b->slot_list.as<int32_t>(), b->thr.as<double>(), b->T2.as<double>(), b->c.F,
                      b->c.FS, b->c.mag_scale);
   if (hipGetLastError() != hipSuccess) { *err = "sg_stream_set_threshold: launch failed"; return SG_E_HIP; }
   for (int32_t i = 0; i < n; ++i) b->slots[slots[i]].has_thr = true;
@@ -811,23 +724,20 @@ int st_set_filterbank(StBank* b, const float* fb_host, int32_t n_filters, std::s
     *err = "sg_stream_set_filterbank: the filterbank has a non-finite entry";
     return SG_E_INVALID;
   }
-  void* dev = nullptr;
-  if (hipMalloc(&dev, host.size()) != hipSuccess) { *err = "sg_stream_set_filterbank: device allocation failed"; return SG_E_NOMEM; }
-  if (hipMemcpy(dev, host.data(), host.size(), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(dev);
+  host::DevBuf dev;   // (a refused filterbank: freed on return, the earlier one stays)
+  if (hipMalloc(&dev.p, host.size()) != hipSuccess) { dev.p = nullptr; *err = "sg_stream_set_filterbank: device allocation failed"; return SG_E_NOMEM; }
+  dev.bytes = host.size();
+  if (hipMemcpy(dev.p, host.data(), host.size(), hipMemcpyHostToDevice) != hipSuccess) {
     *err = "sg_stream_set_filterbank: table upload failed";
     return SG_E_HIP;
   }
-  if (b->fbank) {   // launches of an earlier step may still read the tables about to be freed
-    if (hipDeviceSynchronize() != hipSuccess) {
-      (void)hipFree(dev);
-      *err = "sg_stream_set_filterbank: hipDeviceSynchronize failed";
-      return SG_E_HIP;
-    }
-    (void)hipFree(b->fbank);
+  // launches of an earlier step may still read the tables about to be freed
+  if (b->fbank.p && hipDeviceSynchronize() != hipSuccess) {
+    *err = "sg_stream_set_filterbank: hipDeviceSynchronize failed";
+    return SG_E_HIP;
   }
-  b->fbank = dev;
-  char* d = (char*)dev;
+  b->fbank.take(dev);
+  char* d = b->fbank.as<char>();
   b->fb = FeatBank{(const float*)d, (const float*)(d + fbb), (const int2*)(d + 2 * fbb), (const int2*)(d + 2 * fbb + khb), M};
   return SG_OK;
 }
@@ -839,12 +749,12 @@ int st_reset(StBank* b, const int32_t* slots, int32_t n, hipStream_t st, std::st
     // (the ring, the bit rows and the carry need no clearing: a fresh stream reads none of them before it writes them)
     // (nor does the forward state of a non-stationary unit: frame 0 seeds it)
     if (!b->ns &&
-        hipMemsetAsync(b->rmax + (size_t)slots[i] * b->C * b->c.FS, 0, (size_t)b->C * b->c.FS * 8, st) != hipSuccess) {
+        hipMemsetAsync(b->rmax.as<double>() + (size_t)slots[i] * b->C * b->c.FS, 0, (size_t)b->C * b->c.FS * 8, st) != hipSuccess) {
       *err = "sg_stream_reset: hipMemsetAsync failed";
       return SG_E_HIP;
     }
     if (b->ad &&
-        hipMemsetAsync(b->nst + (size_t)slots[i] * b->C * 3 * b->c.FS, 0, (size_t)b->C * 3 * b->c.FS * 8, st) != hipSuccess) {
+        hipMemsetAsync(b->nst.as<double>() + (size_t)slots[i] * b->C * 3 * b->c.FS, 0, (size_t)b->C * 3 * b->c.FS * 8, st) != hipSuccess) {
       *err = "sg_stream_reset: hipMemsetAsync failed";
       return SG_E_HIP;
     }
@@ -865,7 +775,7 @@ int st_noise_profile(StBank* b, int32_t slot, double* thresh_host, hipStream_t s
   }
   const int FS = b->c.FS, F = b->c.F;
   std::vector<double> host((size_t)b->C * 3 * FS);
-  if (hipMemcpyAsync(host.data(), b->nst + (size_t)slot * b->C * 3 * FS, host.size() * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+  if (hipMemcpyAsync(host.data(), b->nst.as<double>() + (size_t)slot * b->C * 3 * FS, host.size() * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipStreamSynchronize(st) != hipSuccess) {
     *err = "sg_stream_noise_profile: copy of the statistics failed";
     return SG_E_HIP;
@@ -878,337 +788,122 @@ int st_noise_profile(StBank* b, int32_t slot, double* thresh_host, hipStream_t s
   return SG_OK;
 }
 
-int64_t st_bank_emitted(const StBank* b, int64_t n) { return st_emitted(b->c.W, b->c.H, b->c.nt + b->L, n); }
+int64_t st_bank_emitted(const StBank* b, int64_t n) { return st_counters_at(st_geo(b), n).E; }
 
-int64_t st_bank_frames(const StBank* b, int64_t n) {
-  const int64_t a = st_tdec(b->c.W, b->c.H, n) - b->c.nt - b->L + 1;
-  return a > 0 ? a : 0;
-}
+int64_t st_bank_frames(const StBank* b, int64_t n) { return st_counters_at(st_geo(b), n).ta + 1; }
 
 int st_counters(const StBank* b, int32_t slot, int64_t* n, int64_t* emitted, std::string* err) {
   if (slot < 0 || slot >= b->n_slots) { *err = "sg_stream_counters: unknown slot"; return SG_E_INVALID; }
   *n = b->slots[slot].n;
-  *emitted = b->slots[slot].E;
+  *emitted = st_counters_at(st_geo(b), *n).E;
   return SG_OK;
 }
 
+// A step: check (st_check_step), plan (st_plan_step: both stream_plan.hpp's, host arithmetic on plain data), the tables to
+// the device, four launches, then the slots' new state.
 int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_dtype, const sg_stream_rec* recs,
             int32_t n_recs, hipStream_t st, std::string* err, const StSpecOut* so, const StFeatOut* fo) {
   const RgCtx& c = b->c;
-  const int h = c.W / 2;
-  const char* who = fo ? "sg_stream_push_features" : so ? "sg_stream_push_spectrum" : "sg_stream_push";
-  char msg[200];
-  // ---- every argument is checked before any device work or state change
-  auto dtype_ok = [&](int d) { return d == SG_F32 || d == SG_F64 || (b->exact && (d == SG_I16 || d == SG_I32)); };
-  if (!dtype_ok(in_dtype) || !dtype_ok(out_dtype)) {
-    *err = std::string(who) + ": bad argument (float32 / float64 buffers)";
-    return SG_E_INVALID;
-  }
-  if (so && ((so->dtype != SG_F32 && so->dtype != SG_F64) || (n_recs > 0 && (!so->spec || !so->recs)))) {
-    *err = std::string(who) + ": bad argument (spec_dev and spec_recs are needed; spec_dtype is SG_F32 or SG_F64)";
-    return SG_E_INVALID;
-  }
-  if (fo) {
-    if (so) { *err = std::string(who) + ": bad argument (a step stores the spectrum or the features)"; return SG_E_INVALID; }
-    if ((fo->dtype != SG_F32 && fo->dtype != SG_F64) || (n_recs > 0 && (!fo->feat || !fo->recs))) {
-      *err = std::string(who) + ": bad argument (feat_dev and feat_recs are needed; feat_dtype is SG_F32 or SG_F64)";
-      return SG_E_INVALID;
-    }
-    if (fo->power != 1 && fo->power != 2) { *err = std::string(who) + ": power must be 1 or 2"; return SG_E_INVALID; }
-    if (!(fo->eps == fo->eps)) { *err = std::string(who) + ": eps is NaN"; return SG_E_INVALID; }
-    if (!(fo->scale >= 0.0 && fo->scale <= 1.79769313486231570e308)) {
-      *err = std::string(who) + ": scale must be finite and not negative (0: the bank's 1 / sum(window))";
-      return SG_E_INVALID;
-    }
-    if (!b->fb.M) { *err = std::string(who) + ": no filterbank set (sg_stream_set_filterbank)"; return SG_E_INVALID; }
-  }
-  std::vector<char> seen(b->n_slots, 0);
-  for (int32_t i = 0; i < n_recs; ++i) {
-    const sg_stream_rec& r = recs[i];
-    if (r.slot < 0 || r.slot >= b->n_slots) {
-      snprintf(msg, sizeof msg, "%s: record %d: unknown slot %d (the bank has %d)", who, i, r.slot, b->n_slots);
-      *err = msg;
-      return SG_E_INVALID;
-    }
-    if (seen[r.slot]) {
-      snprintf(msg, sizeof msg, "%s: slot %d appears twice in one step", who, r.slot);
-      *err = msg;
-      return SG_E_INVALID;
-    }
-    seen[r.slot] = 1;
-    if (r.n_samples < 0 || r.n_samples > b->max_block) {
-      snprintf(msg, sizeof msg, "%s: slot %d: block of %lld samples (max_block is %lld)", who, r.slot,
-               (long long)r.n_samples, (long long)b->max_block);
-      *err = msg;
-      return SG_E_INVALID;
-    }
-    if (r.in_offset < 0 || r.out_offset < 0 || (b->C > 1 && (r.in_stride < r.n_samples || r.out_stride < 0))) {
-      snprintf(msg, sizeof msg, "%s: slot %d: bad offsets / strides", who, r.slot);
-      *err = msg;
-      return SG_E_INVALID;
-    }
-    if (!b->slots[r.slot].has_thr) {
-      snprintf(msg, sizeof msg, "%s: slot %d has no noise threshold yet", who, r.slot);
-      *err = msg;
-      return SG_E_STATE;
-    }
-    if (r.flush && b->slots[r.slot].n + r.n_samples < c.W) {
-      snprintf(msg, sizeof msg, "%s: slot %d: a stream of %lld samples is shorter than win_length=%d", who, r.slot,
-               (long long)(b->slots[r.slot].n + r.n_samples), c.W);
-      *err = msg;
-      return SG_E_INVALID;
-    }
-    if (so) {
-      // (the frames the record reports: those the plan below applies -- the same arithmetic)
-      const StSlot& S = b->slots[r.slot];
-      const int64_t n1 = S.n + r.n_samples;
-      const int64_t ta1 = r.flush ? (n1 + 2 * (int64_t)h - c.W) / c.H : std::max(S.ta, st_bank_frames(b, n1) - 1);
-      const sg_stream_spec_rec& q = so->recs[i];
-      if (q.spec_offset < 0 || (so->mask && q.mask_offset < 0) || (b->C > 1 && q.stride < (ta1 - S.ta) * c.F)) {
-        snprintf(msg, sizeof msg, "%s: slot %d: bad spectrum offsets / stride", who, r.slot);
-        *err = msg;
-        return SG_E_INVALID;
-      }
-    }
-    if (fo) {
-      // (the frames the record reports: the spectrum step's arithmetic)
-      const StSlot& S = b->slots[r.slot];
-      const int64_t n1 = S.n + r.n_samples;
-      const int64_t ta1 = r.flush ? (n1 + 2 * (int64_t)h - c.W) / c.H : std::max(S.ta, st_bank_frames(b, n1) - 1);
-      const sg_stream_feat_rec& q = fo->recs[i];
-      if (q.feat_offset < 0 || (fo->mask && q.mask_offset < 0) ||
-          (b->C > 1 && (q.feat_stride < (ta1 - S.ta) * b->fb.M || (fo->mask && q.mask_stride < (ta1 - S.ta) * c.F)))) {
-        snprintf(msg, sizeof msg, "%s: slot %d: bad feature offsets / strides", who, r.slot);
-        *err = msg;
-        return SG_E_INVALID;
-      }
-    }
-  }
-  // ---- plan
-  std::vector<StUnit> units;
-  std::vector<StSpec> specs;
-  std::vector<StFeatUnit> feats;
-  std::vector<StSlot> after(n_recs);
-  int64_t mrows = 0, sframes = 0;
-  const int64_t UNBOUNDED = (int64_t)1 << 60;
-  for (int32_t i = 0; i < n_recs; ++i) {
-    const sg_stream_rec& r = recs[i];
-    const StSlot& S = b->slots[r.slot];
-    StUnit U{};
-    U.n0 = S.n;
-    U.n1 = S.n + r.n_samples;
-    U.td0 = S.td;
-    U.ts0 = S.ts;
-    U.ta0 = S.ta;
-    U.E0 = S.E;
-    U.flush = r.flush ? 1 : 0;
-    if (r.flush) {
-      const int64_t T = (U.n1 + 2 * (int64_t)h - c.W) / c.H + 1;
-      U.Tend = T;
-      U.Lout = (T - 1) * c.H + c.W - 2 * (int64_t)h;
-      U.td1 = T - 1;
-      U.ts1 = T - 1;
-      U.ta1 = T - 1;
-      U.E1 = U.n1;
-    } else {
-      U.Tend = UNBOUNDED;
-      U.Lout = UNBOUNDED;
-      U.td1 = std::max(U.td0, st_tdec(c.W, c.H, U.n1));
-      U.ts1 = std::max(U.ts0, U.td1 - b->L);
-      U.ta1 = std::max(U.ta0, U.ts1 - c.nt);
-      U.E1 = std::max<int64_t>(0, (U.ta1 + 1) * c.H - h);
-    }
-    U.cov0 = U.ta0 >= 0 ? U.ta0 * c.H - h + c.W : 0;
-    if (U.ta1 > U.ta0) {
-      U.r0 = std::max<int64_t>(0, U.ta0 + 1 - c.nt);
-      U.r1 = std::min<int64_t>(U.Tend, U.ta1 + c.nt + 1);
-    }
-    U.slot = r.slot;
-    U.par = S.par;
-    for (int ch = 0; ch < b->C; ++ch) {
-      StUnit V = U;
-      V.state = r.slot * b->C + ch;
-      V.in_off = r.in_offset + (int64_t)ch * r.in_stride;
-      V.out_off = r.out_offset + (int64_t)ch * r.out_stride;
-      V.mrow = mrows; mrows += V.r1 - V.r0;
-      V.srow = sframes; sframes += V.ta1 - V.ta0;
-      units.push_back(V);
-      if (so) specs.push_back(StSpec{so->recs[i].spec_offset + ch * so->recs[i].stride, so->recs[i].mask_offset + ch * so->recs[i].stride});
-      if (fo) feats.push_back(StFeatUnit{fo->recs[i].feat_offset + ch * fo->recs[i].feat_stride, fo->recs[i].mask_offset + ch * fo->recs[i].mask_stride});
-    }
-    StSlot& N = after[i];
-    N.has_thr = true;
-    if (!r.flush) {
-      N.n = U.n1; N.td = U.td1; N.ts = U.ts1; N.ta = U.ta1; N.E = U.E1;
-      N.par = U.ta1 > U.ta0 ? (S.par ^ 1) : S.par;
-    }
-  }
-  TileList tl;
-  StArgs A{};
-  A.t_dec = tl.begin_stage();
-  for (size_t u = 0; u < units.size(); ++u)
-    if (units[u].td1 > units[u].td0 || units[u].ts1 > units[u].ts0) tl.push(u, units[u].td0 + 1, units[u].td1 + 1);
-  A.n_dec = tl.count_since(A.t_dec);
-  A.t_fs = tl.begin_stage();
-  for (size_t u = 0; u < units.size(); ++u) tl.push_ranges(u, units[u].r0, units[u].r1, RPT);
-  A.n_fs = tl.count_since(A.t_fs);
-  A.t_ap = tl.begin_stage();
-  for (size_t u = 0; u < units.size(); ++u) tl.push_ranges(u, units[u].ta0 + 1, units[u].ta1 + 1, FPT);
-  A.n_ap = tl.count_since(A.t_ap);
-  A.t_fin = tl.begin_stage();
-  for (size_t u = 0; u < units.size(); ++u) {
-    const StUnit& U = units[u];
-    // newly final samples [E0, E1) and the open ones up to the last applied frame's end (a flush closes every sample,
-    // also when its last frame was applied before)
-    if (U.ta1 > U.ta0 || U.flush)
-      tl.push_ranges(u, U.E0, U.flush ? U.E1 : std::max(U.E1, U.ta1 * c.H - h + c.W), 256, true, ST_OLA);
-    if (!U.flush) tl.push_ranges(u, std::max(U.n0, U.n1 - b->RC), U.n1, 256, true, ST_APPEND);
-    else if (!b->ns) tl.push(u, 0, 0, ST_CLEAR);
-  }
-  A.n_fin = tl.count_since(A.t_fin);
-  // ---- tables and scratch
-  const size_t ub = align256(units.size() * sizeof(StUnit)), tb = align256(tl.tiles.size() * sizeof(Tile));
-  // (one optional third table: the spectrum step's or the feature step's)
-  const void* third = fo ? (const void*)feats.data() : (const void*)specs.data();
-  const size_t third_bytes = fo ? feats.size() * sizeof(StFeatUnit) : specs.size() * sizeof(StSpec);
-  const size_t sb = align256(third_bytes);
-  int rc = grow_device_buffer(&b->tabs, &b->tabs_bytes, ub + tb + sb, st, who, "table", err);
+  const StGeo g = st_geo(b);
+  const char* who = st_step_name(so, fo);
+  int rc = st_check_step(g, b->max_block, b->fb.M, b->slots, in_dtype, out_dtype, recs, n_recs, so, fo, err);
   if (rc) return rc;
-  const bool ex = b->exact != 0;
-  const size_t Rb = align256((size_t)mrows * c.FS * (ex && b->ns ? 8 : 4)), Sb = align256((size_t)sframes * c.n * (ex ? 8 : 4));
-  if ((rc = grow_device_buffer(&b->ws, &b->ws_bytes, Rb + Sb, st, who, "workspace", err))) return rc;
-  if (upload_tables(b->tabs, st, {{units.data(), units.size() * sizeof(StUnit), ub},
-                                  {tl.tiles.data(), tl.tiles.size() * sizeof(Tile), tb},
-                                  {third, third_bytes, sb}}) != hipSuccess) {
+  const StStep P = st_plan_step(g, b->slots, recs, n_recs, so, fo);
+  // ---- tables and scratch
+  const size_t ub = align256(P.units.size() * sizeof(StUnit)), tb = align256(P.tl.tiles.size() * sizeof(Tile));
+  // (one optional third table: the spectrum step's or the feature step's)
+  const void* third = fo ? (const void*)P.feats.data() : (const void*)P.specs.data();
+  const size_t third_bytes = fo ? P.feats.size() * sizeof(StFeatUnit) : P.specs.size() * sizeof(StSpec);
+  const size_t sb = align256(third_bytes);
+  if ((rc = grow_device_buffer(b->tabs, ub + tb + sb, st, who, "table", err))) return rc;
+  const bool ex = b->exact != 0, ns = b->ns != 0;
+  const size_t Rb = align256((size_t)P.mrows * c.FS * (ex && ns ? 8 : 4)), Sb = align256((size_t)P.sframes * c.n * (ex ? 8 : 4));
+  if ((rc = grow_device_buffer(b->ws, Rb + Sb, st, who, "workspace", err))) return rc;
+  if (upload_tables(b->tabs.p, st, {{P.units.data(), P.units.size() * sizeof(StUnit), ub},
+                                    {P.tl.tiles.data(), P.tl.tiles.size() * sizeof(Tile), tb},
+                                    {third, third_bytes, sb}}) != hipSuccess) {
     *err = std::string(who) + ": table upload failed";
     return SG_E_HIP;
   }
+  char* tabs = b->tabs.as<char>();
+  StArgs A{};
   A.x = in_dev; A.in_dtype = in_dtype; A.out = out_dev; A.out_dtype = out_dtype;
-  A.units = (const StUnit*)b->tabs;
-  A.tiles = (const Tile*)((char*)b->tabs + ub);
-  A.ring = b->ring; A.bits = b->bits; A.rmax = b->rmax; A.carry = b->carry; A.thr = b->thr; A.T2 = b->T2;
-  A.R = b->ws; A.seg = (char*)b->ws + Rb;
+  A.units = (const StUnit*)tabs;
+  A.tiles = (const Tile*)(tabs + ub);
+  A.t_dec = P.t_dec; A.n_dec = P.n_dec; A.t_fs = P.t_fs; A.n_fs = P.n_fs;
+  A.t_ap = P.t_ap; A.n_ap = P.n_ap; A.t_fin = P.t_fin; A.n_fin = P.n_fin;
+  A.ring = b->ring.as<double>(); A.bits = b->bits.as<unsigned long long>(); A.rmax = b->rmax.as<double>();
+  A.carry = b->carry.as<double>(); A.thr = b->thr.as<double>(); A.T2 = b->T2.as<double>();
+  A.R = b->ws.p; A.seg = b->ws.as<char>() + Rb;
   A.RC = b->RC; A.RB = b->RB;
-  A.fst = b->fst; A.fa = b->fa; A.mk = b->mk; A.RF = b->RF; A.L = b->L;
-  A.nst = b->nst; A.lam = b->lam; A.learn = b->learn;
+  A.fst = b->fst.as<double>(); A.fa = b->fa.as<double>(); A.mk = b->mk.p; A.RF = b->RF; A.L = b->L;
+  A.nst = b->nst.as<double>(); A.lam = b->lam; A.learn = b->learn;
   A.c = fill_consts(c);
   if (so) {
     A.spec = so->spec; A.smask = so->mask; A.spec_dtype = so->dtype;
-    A.sp = (const StSpec*)((char*)b->tabs + ub + tb);
+    A.sp = (const StSpec*)(tabs + ub + tb);
   }
   StFeat Q{};
   if (fo) {
     Q.bank = b->fb;
     Q.feat = fo->feat; Q.fmask = fo->mask; Q.dtype = fo->dtype;
-    Q.fu = (const StFeatUnit*)((char*)b->tabs + ub + tb);
+    Q.fu = (const StFeatUnit*)(tabs + ub + tb);
     Q.eps = fo->eps; Q.scale = fo->scale == 0.0 ? c.mag_scale : fo->scale;
     Q.power = fo->power; Q.take_log = fo->take_log ? 1 : 0;
   }
-  const bool ns = b->ns != 0;
-  // ---- the step: the same four launches whatever was pushed
+  // ---- the step: the same four launches whatever was pushed.  A kernel's flags (EX: exact bank, NS: non-stationary
+  // bank) are template arguments, chosen by dispatch_flag(s); only the instantiations named here exist
   hipError_t e = hipSuccess;
   {
     Prof pr(c, SG_STAGE_RG_DECIDE, st);
     e = dispatch_N(c.N, [&](auto n) {
-      if (b->ad) return launch_tile_kernel<n()>(k_sa_decide<n()>, A.n_dec, st, A);
-      if (ns) return ex ? launch_tile_kernel<n()>(k_sn_decide<n(), true>, A.n_dec, st, A) : launch_tile_kernel<n()>(k_sn_decide<n(), false>, A.n_dec, st, A);
-      return launch_tile_kernel<n()>(k_st_decide<n()>, A.n_dec, st, A);
+      constexpr int N = decltype(n)::value;
+      if (b->ad) return launch_tile_kernel<N>(k_sa_decide<N>, A.n_dec, st, A);
+      if (ns) return dispatch_flag(ex, [&](auto EX) { return launch_tile_kernel<N>(k_sn_decide<N, decltype(EX)::value>, A.n_dec, st, A); });
+      return launch_tile_kernel<N>(k_st_decide<N>, A.n_dec, st, A);
     });
   }
   if (e == hipSuccess) {
     Prof pr(c, SG_STAGE_RG_FSMOOTH, st);
-    e = launch_flat_kernel(ns ? (ex ? k_st_fsmooth<true, true> : k_st_fsmooth<true, false>) : k_st_fsmooth<false, false>, A.n_fs, 256, st, A);
+    e = ns ? dispatch_flag(ex, [&](auto EX) { return launch_flat_kernel(k_st_fsmooth<true, decltype(EX)::value>, A.n_fs, 256, st, A); })
+           : launch_flat_kernel(k_st_fsmooth<false, false>, A.n_fs, 256, st, A);
   }
   if (e == hipSuccess) {
     Prof pr(c, SG_STAGE_RG_APPLY, st);
     e = dispatch_N(c.N, [&](auto n) {
-      if (fo) {
-        if (ex) return ns ? launch_feat_kernel<n()>(k_st_feat<n(), true, true>, A.n_ap, st, A, Q) : launch_feat_kernel<n()>(k_st_feat<n(), false, true>, A.n_ap, st, A, Q);
-        return ns ? launch_feat_kernel<n()>(k_st_feat<n(), true, false>, A.n_ap, st, A, Q) : launch_feat_kernel<n()>(k_st_feat<n(), false, false>, A.n_ap, st, A, Q);
-      }
-      if (so) {
-        if (ex) return ns ? launch_tile_kernel<n()>(k_st_apply<n(), true, true, true>, A.n_ap, st, A) : launch_tile_kernel<n()>(k_st_apply<n(), false, true, true>, A.n_ap, st, A);
-        return ns ? launch_tile_kernel<n()>(k_st_apply<n(), true, false, true>, A.n_ap, st, A) : launch_tile_kernel<n()>(k_st_apply<n(), false, false, true>, A.n_ap, st, A);
-      }
-      if (ex) return ns ? launch_tile_kernel<n()>(k_st_apply<n(), true, true>, A.n_ap, st, A) : launch_tile_kernel<n()>(k_st_apply<n(), false, true>, A.n_ap, st, A);
-      return ns ? launch_tile_kernel<n()>(k_st_apply<n(), true, false>, A.n_ap, st, A) : launch_tile_kernel<n()>(k_st_apply<n(), false, false>, A.n_ap, st, A);
+      constexpr int N = decltype(n)::value;
+      if (fo) return dispatch_flags(ex, ns, [&](auto EX, auto NS) {
+        return launch_feat_kernel<N>(k_st_feat<N, decltype(NS)::value, decltype(EX)::value>, A.n_ap, st, A, Q);
+      });
+      if (so) return dispatch_flags(ex, ns, [&](auto EX, auto NS) {
+        return launch_tile_kernel<N>(k_st_apply<N, decltype(NS)::value, decltype(EX)::value, true>, A.n_ap, st, A);
+      });
+      return dispatch_flags(ex, ns, [&](auto EX, auto NS) {
+        return launch_tile_kernel<N>(k_st_apply<N, decltype(NS)::value, decltype(EX)::value>, A.n_ap, st, A);
+      });
     });
   }
-  if (e == hipSuccess) { Prof pr(c, SG_STAGE_RG_OLA, st); e = launch_flat_kernel(ex ? k_st_finish<true> : k_st_finish<false>, A.n_fin, 256, st, A); }
+  if (e == hipSuccess) {
+    Prof pr(c, SG_STAGE_RG_OLA, st);
+    e = dispatch_flag(ex, [&](auto EX) { return launch_flat_kernel(k_st_finish<decltype(EX)::value>, A.n_fin, 256, st, A); });
+  }
   if (e != hipSuccess) {
     *err = std::string(who) + ": launch failed: " + hipGetErrorString(e);
     return SG_E_HIP;
   }
-  for (int32_t i = 0; i < n_recs; ++i) b->slots[recs[i].slot] = after[i];
+  for (int32_t i = 0; i < n_recs; ++i) b->slots[recs[i].slot] = P.after[i];
   return SG_OK;
 }
 
 // ---- state transfer ------------------------------------------------------------------------------------------------
 namespace {
-// what of a stream that has received n samples a later step can still read (every counter follows from n)
-struct StLive {
-  int64_t td, ts, ta, E;
-  int64_t ring_lo, ring_n;   // samples [ring_lo, n)
-  int64_t car_n;             // carry positions [E, E + car_n)
-  int64_t row_lo, bit_rows;  // bit rows [row_lo, td] (stationary / adaptive)
-  int64_t mk_rows;           // sigmoid rows [row_lo, ts] (non-stationary)
-  int64_t fa_rows;           // A / fwd rows (ts, td] (non-stationary)
-};
-// what the arithmetic needs of a bank -- or of a header alone (sg_stream_head_bytes)
-struct StGeo {
-  int64_t W, H, nt, L, RC, FS, wpr, C;
-  bool ns, ad, fixed, exact;
-};
-StGeo st_geo(const StBank* b) {
-  return StGeo{b->c.W, b->c.H, b->c.nt, b->L, b->RC, b->c.FS, b->wpr, b->C, b->ns != 0, b->ad != 0, b->thr != nullptr, b->exact != 0};
-}
-StGeo st_geo(const sg_stream_head& hd) {
-  StGeo g{};
-  const int64_t F = hd.n_fft / 2 + 1;
-  g.W = hd.win_length; g.H = hd.hop_length; g.C = hd.channels;
-  g.nt = hd.smooth_mask ? hd.n_grad_time : 0;
-  g.ns = hd.kind == SG_STREAM_NONSTATIONARY; g.ad = hd.kind == SG_STREAM_ADAPTIVE; g.fixed = hd.kind == SG_STREAM_FIXED;
-  g.exact = hd.exact != 0;
-  g.L = g.ns ? hd.lookahead_frames : 0;
-  g.RC = g.W + (g.nt + g.L + 1) * g.H;
-  g.FS = (F + 15) / 16 * 16;
-  g.wpr = (F + 63) / 64;
-  return g;
-}
-StLive st_live(const StGeo& g, int64_t n) {
-  const int64_t h = g.W / 2;
-  StLive v{};
-  v.td = st_tdec((int)g.W, (int)g.H, n);
-  v.ts = std::max<int64_t>(-1, v.td - g.L);
-  v.ta = std::max<int64_t>(-1, v.ts - g.nt);
-  v.E = std::max<int64_t>(0, (v.ta + 1) * g.H - h);
-  v.ring_lo = std::max<int64_t>(0, n - g.RC);
-  v.ring_n = n - v.ring_lo;
-  v.car_n = v.ta >= 0 ? std::max<int64_t>(0, v.ta * g.H - h + g.W - v.E) : 0;
-  v.row_lo = std::max<int64_t>(0, v.ta + 1 - g.nt);
-  v.bit_rows = g.ns ? 0 : v.td - v.row_lo + 1;
-  v.mk_rows = g.ns ? v.ts - v.row_lo + 1 : 0;
-  v.fa_rows = g.ns ? v.td - v.ts : 0;
-  return v;
-}
-StLive st_live(const StBank* b, int64_t n) { return st_live(st_geo(b), n); }
-// words of a float mask row / a double one
-int64_t mk_words(const StGeo& g) { return g.exact ? g.FS : g.FS / 2; }
-int64_t mk_words(const StBank* b) { return mk_words(st_geo(b)); }
-
-int64_t st_payload_words(const StGeo& g, int64_t n) {
-  const StLive v = st_live(g, n);
-  int64_t per = v.ring_n + v.car_n;
-  if (g.ns) per += g.FS + v.fa_rows * 2 * g.FS + v.mk_rows * mk_words(g);
-  else per += g.FS + v.bit_rows * g.wpr;
-  if (g.ad) per += 3 * g.FS;
-  return (g.fixed ? 2 * g.FS : 0) + g.C * per;
-}
 int64_t st_payload_words(const StBank* b, int64_t n) { return st_payload_words(st_geo(b), n); }
 
 // the fields of one slot in payload order, word 0 of the payload at `blob`; the tiles of each
 void st_fields(const StBank* b, int32_t slot, int64_t n, int par, int64_t blob, std::vector<StXField>* fields, TileList* tl) {
-  const StLive v = st_live(b, n);
+  const StGeo g = st_geo(b);
+  const StLive v = st_live(g, n);
+  const int64_t mkw = mk_words(g);
   const RgCtx& c = b->c;
   const int64_t FS = c.FS;
   auto field = [&](void* dev, int64_t first, int64_t R, int64_t rw, int64_t rows) {
@@ -1218,23 +913,23 @@ void st_fields(const StBank* b, int32_t slot, int64_t n, int par, int64_t blob, 
     }
     blob += rows * rw;
   };
-  if (b->thr) {
-    field(b->thr + (int64_t)slot * FS, 0, 1, FS, 1);
-    field(b->T2 + (int64_t)slot * FS, 0, 1, FS, 1);
+  if (g.fixed) {
+    field(b->thr.as<double>() + (int64_t)slot * FS, 0, 1, FS, 1);
+    field(b->T2.as<double>() + (int64_t)slot * FS, 0, 1, FS, 1);
   }
   for (int ch = 0; ch < b->C; ++ch) {
     const int64_t u = (int64_t)slot * b->C + ch;
-    field(b->ring + u * b->RC, v.ring_lo, b->RC, 1, v.ring_n);
-    field(b->carry + (u * 2 + par) * c.W, v.E, c.W, 1, v.car_n);
+    field(b->ring.as<double>() + u * b->RC, v.ring_lo, b->RC, 1, v.ring_n);
+    field(b->carry.as<double>() + (u * 2 + par) * c.W, v.E, c.W, 1, v.car_n);
     if (b->ns) {
-      field(b->fst + u * FS, 0, 1, FS, 1);
-      field(b->fa + u * b->RF * 2 * FS, v.ts + 1, b->RF, 2 * FS, v.fa_rows);
-      field((unsigned long long*)b->mk + u * b->RB * mk_words(b), v.row_lo, b->RB, mk_words(b), v.mk_rows);
+      field(b->fst.as<double>() + u * FS, 0, 1, FS, 1);
+      field(b->fa.as<double>() + u * b->RF * 2 * FS, v.ts + 1, b->RF, 2 * FS, v.fa_rows);
+      field(b->mk.as<unsigned long long>() + u * b->RB * mkw, v.row_lo, b->RB, mkw, v.mk_rows);
     } else {
-      field(b->rmax + u * FS, 0, 1, FS, 1);
-      field(b->bits + u * b->RB * b->wpr, v.row_lo, b->RB, b->wpr, v.bit_rows);
+      field(b->rmax.as<double>() + u * FS, 0, 1, FS, 1);
+      field(b->bits.as<unsigned long long>() + u * b->RB * b->wpr, v.row_lo, b->RB, b->wpr, v.bit_rows);
     }
-    if (b->ad) field(b->nst + u * 3 * FS, 0, 1, 3 * FS, 1);
+    if (b->ad) field(b->nst.as<double>() + u * 3 * FS, 0, 1, 3 * FS, 1);
   }
 }
 
@@ -1290,17 +985,17 @@ template <class K>
 int st_transfer(StBank* b, K kernel, int stage, void* blob_dev, const std::vector<StXField>& fields, const TileList& tl,
                 hipStream_t st, const char* who, std::string* err) {
   const size_t fb = align256(fields.size() * sizeof(StXField)), tb = align256(tl.tiles.size() * sizeof(Tile));
-  int rc = grow_device_buffer(&b->tabs, &b->tabs_bytes, fb + tb, st, who, "table", err);
+  int rc = grow_device_buffer(b->tabs, fb + tb, st, who, "table", err);
   if (rc) return rc;
-  if (upload_tables(b->tabs, st, {{fields.data(), fields.size() * sizeof(StXField), fb},
+  if (upload_tables(b->tabs.p, st, {{fields.data(), fields.size() * sizeof(StXField), fb},
                                   {tl.tiles.data(), tl.tiles.size() * sizeof(Tile), tb}}) != hipSuccess) {
     *err = std::string(who) + ": table upload failed";
     return SG_E_HIP;
   }
   StXArgs A{};
   A.blob = (unsigned long long*)blob_dev;
-  A.fields = (const StXField*)b->tabs;
-  A.tiles = (const Tile*)((char*)b->tabs + fb);
+  A.fields = b->tabs.as<const StXField>();
+  A.tiles = (const Tile*)(b->tabs.as<char>() + fb);
   A.n_tiles = tl.size();
   hipError_t e;
   { Prof pr(b->c, stage, st); e = launch_flat_kernel(kernel, A.n_tiles, 256, st, A); }
@@ -1347,7 +1042,8 @@ int st_export(StBank* b, const int32_t* slots, int32_t n, void* blob_dev, const 
     const StSlot& S = b->slots[slots[i]];
     sg_stream_head hd = sig;
     st_sign(b, &hd);
-    hd.n = S.n; hd.td = S.td; hd.ts = S.ts; hd.ta = S.ta; hd.E = S.E;
+    const StCounters k = st_counters_at(st_geo(b), S.n);
+    hd.n = S.n; hd.td = k.td; hd.ts = k.ts; hd.ta = k.ta; hd.E = k.E;
     hd.par = S.par;
     hd.has_thr = S.has_thr ? 1 : 0;
     hd.payload_bytes = 8 * st_payload_words(b, S.n);
@@ -1381,7 +1077,7 @@ int st_import(StBank* b, const int32_t* slots, int32_t n, const void* blob_dev, 
       return SG_E_INVALID;
     }
     // (the sizes of every write below follow from n alone; the other counters have to be the ones n gives)
-    const StLive v = hd.n >= 0 ? st_live(b, hd.n) : StLive{};
+    const StCounters v = hd.n >= 0 ? st_counters_at(st_geo(b), hd.n) : StCounters{};
     if (hd.n < 0 || hd.td != v.td || hd.ts != v.ts || hd.ta != v.ta || hd.E != v.E || (hd.par != 0 && hd.par != 1) ||
         hd.payload_bytes != 8 * st_payload_words(b, hd.n)) {
       snprintf(m, sizeof m, "sg_stream_import: slot %d: the state's counters or payload size do not fit together", slots[i]);
@@ -1397,9 +1093,9 @@ int st_import(StBank* b, const int32_t* slots, int32_t n, const void* blob_dev, 
   for (int32_t i = 0; i < n; ++i) {
     const sg_stream_head& hd = heads[i];
     StSlot& S = b->slots[slots[i]];
-    S.n = hd.n; S.td = hd.td; S.ts = hd.ts; S.ta = hd.ta; S.E = hd.E;
+    S.n = hd.n;   // (td, ts, ta, E: checked above to be the ones n gives)
     S.par = hd.par;
-    S.has_thr = b->thr ? hd.has_thr != 0 : true;
+    S.has_thr = b->thr.p ? hd.has_thr != 0 : true;
   }
   return SG_OK;
 }

@@ -17,7 +17,10 @@
 // and its ring is RC = W + (nt + L + 1) H samples.
 // An adaptive bank (the stationary gate with the noise profile learnt from the stream itself) holds no thr / T2 but
 //   nst    [unit][3][FS]       Wn, mu, M2: weight sum, mean and weighted squared deviations of the floored dB values, float64
-// (unit = slot * channels + channel).  The counters n, t_dec, t_applied, E are host arithmetic, mirrored in the bank.
+// (unit = slot * channels + channel).  Of a slot the bank remembers n, the samples received (and which carry buffer is
+// current, and whether a threshold is set): t_dec, t_applied and E are functions of n, stated once (stream_plan.hpp's
+// st_counters_at).  That header holds all host arithmetic of a bank -- counters, the bytes of every buffer (StLayout), the
+// checks and the plan of a step -- as plain C++ without HIP.
 // st_export / st_import move the live part of all this between banks of the same gate.
 //
 // The frame work of the kernels is tile_core.hpp's, shared with the clips and the rows.
@@ -30,13 +33,11 @@
 
 #include "../../include/mi355gate.h"
 #include "ragged.hpp"   // RgCtx
+#include "stream_plan.hpp"
 
 namespace sg {
 
 struct StBank;
-
-// samples emitted after n received: max(0, (t_dec(n) - nt + 1) H - h), t_dec(n) = floor((n + h - W) / H)
-int64_t st_emitted(int W, int H, int nt, int64_t n);
 
 // an adaptive bank's estimate: forgetting factor per frame in (0, 1], frames that update it (>= 1; negative: all)
 struct StAdaptive {
@@ -64,25 +65,6 @@ void st_destroy(StBank* b);
 // thresh_dev: F dB values on the device (the handle's); thresh_host: F dB values on the host; exactly one is non-null
 int st_set_threshold(StBank* b, const int32_t* slots, int32_t n, const double* thresh_dev, const double* thresh_host,
                      hipStream_t st, std::string* err);
-// what a spectrum step (sg_stream_push_spectrum) stores on top of a push: spec / mask buffers (mask may be null), the
-// element type of both (SG_F32: float2 / float, SG_F64: double2 / double), and the table parallel to the step's records
-struct StSpecOut {
-  void* spec;
-  int dtype;
-  void* mask;
-  const sg_stream_spec_rec* recs;
-};
-// what a feature step (sg_stream_push_features) stores on top of a push: feat / mask buffers (mask may be null), the
-// element type of both (SG_F32 / SG_F64), the table parallel to the step's records and the switches of the reduction
-// (scale == 0: the handle's 1 / sum(window))
-struct StFeatOut {
-  void* feat;
-  int dtype;
-  void* mask;
-  const sg_stream_feat_rec* recs;
-  int32_t power, take_log;
-  double eps, scale;
-};
 // so == fo == nullptr: sg_stream_push.  Otherwise the same plan and launches, the apply launch in its spectrum-storing
 // form (so) or its feature form (fo); at most one of the two is non-null
 int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_dtype, const sg_stream_rec* recs,

@@ -25,6 +25,8 @@
 #include "thresh.hpp"
 #include "ragged.hpp"
 #include "launch.hpp"
+#include "devbuf.hpp"
+#include "tile_tables.hpp"   // Tile, TileList, tile_fdiv / tile_cdiv, align256
 
 namespace sg {
 
@@ -36,12 +38,6 @@ struct TileConsts {
   double ktot;                     // (nf + 1)^2 (nt + 1)^2: weight of the whole smoothing triangle
   const cx<double>* tw;            // cx<double>[N]: w_2N^k
   const double* wfull;             // window embedded in an n_fft frame
-};
-
-// tile i of a stage: {unit / row / noise source, first, end}; kind is 0 except in the stream's finish stage
-struct Tile {
-  int32_t idx, kind;
-  int64_t a, b;
 };
 
 // ---- device side -------------------------------------------------------------------------------------------------
@@ -340,10 +336,6 @@ __device__ __forceinline__ void ola_sum(const TileConsts& C, const ST* seg, SegR
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
-inline int64_t tile_fdiv(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
-inline int64_t tile_cdiv(int64_t a, int64_t b) { return -tile_fdiv(-a, b); }
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 inline bool tile_geom_ok(int N) { return N == 128 || N == 256 || N == 512 || N == 1024 || N == 2048; }
 
 inline TileConsts fill_consts(const RgCtx& c) {
@@ -356,19 +348,6 @@ inline TileConsts fill_consts(const RgCtx& c) {
   return C;
 }
 
-// all tile lists of a call, back to back: a stage is the tiles pushed between its begin_stage() and the next one
-struct TileList {
-  std::vector<Tile> tiles;
-  int64_t size() const { return (int64_t)tiles.size(); }
-  int64_t begin_stage() const { return size(); }
-  int64_t count_since(int64_t first) const { return size() - first; }
-  void push(int64_t idx, int64_t a, int64_t b, int kind = 0) { tiles.push_back(Tile{(int32_t)idx, kind, a, b}); }
-  // [lo, hi) in pieces of `step`; the last piece ends at hi, or runs its full step where clamp is false (band blocks)
-  void push_ranges(int64_t idx, int64_t lo, int64_t hi, int64_t step, bool clamp = true, int kind = 0) {
-    for (int64_t a = lo; a < hi; a += step) push(idx, a, clamp ? std::min(hi, a + step) : a + step, kind);
-  }
-};
-
 // profiler scope of one stage (api.hip's hooks, RgCtx)
 struct Prof {
   const RgCtx& c;
@@ -378,18 +357,17 @@ struct Prof {
 };
 
 // a device buffer of at least `need` bytes; growing it synchronises the stream once and drops the old contents
-inline int grow_device_buffer(void** p, size_t* have, size_t need, hipStream_t st, const char* who, const char* what,
-                              std::string* err) {
-  if (*have >= need) return SG_OK;
-  if (*p) { (void)hipStreamSynchronize(st); (void)hipFree(*p); *p = nullptr; *have = 0; }
-  if (hipMalloc(p, need) != hipSuccess) {
-    *p = nullptr;
+inline int grow_device_buffer(host::DevBuf& buf, size_t need, hipStream_t st, const char* who, const char* what, std::string* err) {
+  if (buf.bytes >= need) return SG_OK;
+  if (buf.p) { (void)hipStreamSynchronize(st); buf.release(); }
+  if (hipMalloc(&buf.p, need) != hipSuccess) {
+    buf.p = nullptr;
     char b[160];
     snprintf(b, sizeof b, "%s: %s allocation of %zu bytes failed", who, what, need);
     *err = b;
     return SG_E_NOMEM;
   }
-  *have = need;
+  buf.bytes = need;
   return SG_OK;
 }
 
@@ -423,6 +401,17 @@ hipError_t dispatch_N(int N, F&& f) {
     case 2048: return f(std::integral_constant<int, 2048>{});
   }
   return hipErrorInvalidValue;
+}
+
+// f(std::true_type{}) or f(std::false_type{}): a run-time switch as a template argument of what f launches.  The true
+// branch is named first; dispatch_flags(a, b, f) calls f(A, B) and names (1, 1), (1, 0), (0, 1), (0, 0) in that order
+template <class F>
+auto dispatch_flag(bool on, F&& f) {
+  return on ? f(std::true_type{}) : f(std::false_type{});
+}
+template <class F>
+auto dispatch_flags(bool a, bool b, F&& f) {
+  return dispatch_flag(a, [&](auto A) { return dispatch_flag(b, [&](auto B) { return f(A, B); }); });
 }
 
 inline dim3 tile_grid(int64_t ntiles) { return dim3((unsigned)std::max<int64_t>(1, ntiles)); }
