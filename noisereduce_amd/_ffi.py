@@ -269,9 +269,12 @@ def _sg_dtype(t):
 
 
 def _rows(t):
-    """(data_ptr, row_stride) of a 2-D tensor whose last dim is contiguous."""
+    """(tensor, row_stride) for the C ABI: a 2-D tensor whose rows are contiguous and do not overlap goes as it is (any
+    base address, any row pitch >= the row length); a non-unit last stride, and rows that overlap or repeat (row stride
+    below the row length: ``expand``, ``unfold``), are copied -- the entry points disagree about such rows
+    (sg_process_batch takes any stride, sg_process_rows and sg_gate_features_backward refuse one below L)."""
     assert t.dim() == 2
-    if t.shape[1] > 1 and t.stride(1) != 1:
+    if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
         t = t.contiguous()
     return t, t.stride(0) if t.shape[0] > 1 else t.shape[1]
 
