@@ -279,6 +279,30 @@ def _rows(t):
     return t, t.stride(0) if t.shape[0] > 1 else t.shape[1]
 
 
+def _dense(t, name, rows=False, dtype=None):
+    """``t`` for an argument of the C ABI that carries no strides of its own: the library reads (writes) ``numel()``
+    elements from ``data_ptr()`` on, so the tensor must be contiguous -- a ``[::2]`` view, a transpose or an ``expand`` would be
+    taken for other samples without anybody noticing.  ``rows=True``: an output the ABI takes with a row stride
+    (sg_process_chunks' ``out``): 2-D, unit stride inside a row, rows that do not overlap; any base address and any pitch
+    >= the row length go as they are (``_rows`` is the same rule for inputs, which it may copy; an output cannot be
+    copied).  ``dtype``: the one element type the ABI reads there.  Raises ValueError naming the argument; never copies.
+    Works on CPU tensors: no device is touched."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name} must be a tensor (got {type(t).__name__})")
+    if dtype is not None and t.dtype != dtype:
+        raise ValueError(f"{name} must be {dtype} (got {t.dtype})")
+    if rows:
+        ok = t.dim() == 2 and (t.shape[1] <= 1 or t.stride(1) == 1) and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1])
+        what = "a 2-D tensor whose rows are contiguous and do not overlap"
+    else:
+        ok = t.is_contiguous()
+        what = "contiguous"
+    if not ok:
+        raise ValueError(f"{name} must be {what}: the library reads it from data_ptr() on as dense memory (got shape "
+                         f"{tuple(t.shape)} with strides {tuple(t.stride())})")
+    return t
+
+
 class Gate:
     """One sg_handle bound to one device (and used on that device's current stream)."""
 
@@ -445,7 +469,7 @@ class Gate:
     def set_noise_threshold_tensor(self, t):
         self.evict_threshold()
         self._on_device(t)
-        t = t.to(torch.float64).contiguous()
+        t = _dense(t, "t").to(torch.float64)
         with torch.cuda.device(self.device):
             self._check(self.lib.sg_set_noise_threshold_dev(self._h, t.data_ptr(), int(t.numel()),
                                                             self._stream()))
@@ -464,6 +488,8 @@ class Gate:
         n_out = end_frame if not chunked else end_frame - int(start_frame)
         if out is None:
             out = torch.empty((C, n_out), dtype=out_dtype or x.dtype, device=self.device)
+        elif tuple(_dense(out, "out", rows=True).shape) != (C, n_out):
+            raise ValueError(f"out must be a (C, n) = {(C, n_out)} tensor, got {tuple(out.shape)}")
         with torch.cuda.device(self.device):
             self._check(self.lib.sg_process_chunks(
                 self._h, x_ptr, _sg_dtype(x), out.data_ptr(), _sg_dtype(out), C, N, stride,
@@ -504,6 +530,11 @@ class Gate:
             raise ValueError("mask_out must be a contiguous (B, T, FS) float32 tensor")
         return mask
 
+    def _saved_mask(self, mask):
+        """The mask a backward call is given: the library reads B x T x FS float32 from its data_ptr()."""
+        self._on_device(mask)
+        return _dense(mask, "mask", dtype=torch.float32)
+
     def _grad_x(self, B, L, dtype):
         return torch.empty((B, L), dtype=dtype, device=self.device)
 
@@ -536,6 +567,7 @@ class Gate:
     def process_batch_backward(self, grad_out, mask, L):
         """Adjoint of process_batch with the mask fixed: (B, Lout) -> (B, L)."""
         self._on_device(grad_out)
+        self._saved_mask(mask)
         grad_out, gs = _rows(grad_out)
         B = grad_out.shape[0]
         gx = self._grad_x(B, L, grad_out.dtype)
@@ -570,6 +602,7 @@ class Gate:
         """Adjoint of gate_spectrum with the mask fixed: grad (B, T, F, 2) real pairs -> (B, L) of grad.dtype.
         out: a (B, L) tensor (rows may be strided) to write into."""
         self._on_device(grad)
+        self._saved_mask(mask)
         grad = grad.contiguous()
         B = grad.shape[0]
         if out is None:
@@ -620,6 +653,7 @@ class Gate:
             raise RuntimeError("no filterbank set (set_filterbank)")
         self._on_device(x)
         self._on_device(grad)
+        self._saved_mask(mask)
         x, xs = _rows(x)
         B, L = x.shape
         grad = grad.to(x.dtype).contiguous()
@@ -656,6 +690,7 @@ class Gate:
     def process_rows_backward(self, grad_out, mask, L, lengths):
         """Adjoint of process_rows with the mask fixed: (B, Lout) -> (B, L), zero at and beyond lengths[i]."""
         self._on_device(grad_out)
+        self._saved_mask(mask)
         grad_out, gs = _rows(grad_out)
         B = grad_out.shape[0]
         gx = self._grad_x(B, L, grad_out.dtype)
@@ -691,6 +726,7 @@ class Gate:
         """Adjoint of gate_spectrum_rows with the mask fixed: grad (B, T, F, 2) real pairs -> (B, L) of grad.dtype, zero
         at and beyond lengths[i]; grad[i, 1 + lengths[i] // hop:] is never read."""
         self._on_device(grad)
+        self._saved_mask(mask)
         grad = grad.contiguous()
         B = grad.shape[0]
         gx = self._grad_x(B, L, grad.dtype)
@@ -732,6 +768,7 @@ class Gate:
             raise RuntimeError("no filterbank set (set_filterbank)")
         self._on_device(x)
         self._on_device(grad)
+        self._saved_mask(mask)
         x, xs = _rows(x)
         B, L = x.shape
         grad = grad.to(x.dtype).contiguous()
@@ -763,11 +800,14 @@ class Gate:
         noise: 1-D device tensor or None; noise_srcs: sequence of SgNoiseSrc."""
         self._on_device(x)
         self._on_device(out)
+        _dense(x, "x")
+        _dense(out, "out")
         n_clips = len(clips)
         carr = (SgClip * max(1, n_clips))(*clips)
         narr = (SgNoiseSrc * max(1, len(noise_srcs)))(*noise_srcs)
         if noise is not None:
             self._on_device(noise)
+            _dense(noise, "noise")
         with torch.cuda.device(self.device):
             self._check(self.lib.sg_process_clips(
                 self._h, x.data_ptr(), _sg_dtype(x), None if noise is None else noise.data_ptr(),
@@ -883,6 +923,8 @@ class Gate:
         Enqueues only."""
         self._on_device(x)
         self._on_device(out)
+        _dense(x, "x")
+        _dense(out, "out")
         arr = (SgStreamRec * max(1, len(recs)))(*recs)
         with torch.cuda.device(self.device):
             self._check(self.lib.sg_stream_push(bank, x.data_ptr(), _sg_dtype(x), out.data_ptr(), _sg_dtype(out), arr,
@@ -899,8 +941,9 @@ class Gate:
             raise TypeError(f"stream_push_spectrum: mask must be {real} next to a {spec.dtype} spec (got {mask.dtype})")
         if len(spec_recs) != len(recs):
             raise ValueError("stream_push_spectrum: recs and spec_recs must have the same length")
-        for t in (x, out, spec) + (() if mask is None else (mask,)):
+        for name, t in (("x", x), ("out", out), ("spec", spec)) + (() if mask is None else (("mask", mask),)):
             self._on_device(t)
+            _dense(t, name)
         arr = (SgStreamRec * max(1, len(recs)))(*recs)
         sarr = (SgStreamSpecRec * max(1, len(spec_recs)))(*spec_recs)
         with torch.cuda.device(self.device):
@@ -924,8 +967,9 @@ class Gate:
             raise TypeError(f"stream_push_features: mask must be {feat.dtype} next to such a feat (got {mask.dtype})")
         if len(feat_recs) != len(recs):
             raise ValueError("stream_push_features: recs and feat_recs must have the same length")
-        for t in (x, out, feat) + (() if mask is None else (mask,)):
+        for name, t in (("x", x), ("out", out), ("feat", feat)) + (() if mask is None else (("mask", mask),)):
             self._on_device(t)
+            _dense(t, name)
         arr = (SgStreamRec * max(1, len(recs)))(*recs)
         farr = (SgStreamFeatRec * max(1, len(feat_recs)))(*feat_recs)
         with torch.cuda.device(self.device):

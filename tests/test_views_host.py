@@ -143,6 +143,76 @@ def test_rows_copies_what_the_library_cannot_read_and_nothing_else(dtype):
     assert t.is_contiguous() and stride == a.shape[1]
 
 
+# ---- _ffi._dense: the tensors the C ABI takes without strides ---------------------------------------------------------
+def _raises_naming(name, fn):
+    with pytest.raises(ValueError) as e:
+        fn()
+    assert str(e.value).startswith(name + " must be"), str(e.value)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_dense_accepts_what_the_library_reads_as_it_is_and_refuses_the_rest(dtype):
+    from noisereduce_amd import _ffi
+    tdt = V._TORCH[dtype]
+    flat = torch.from_numpy(_samples(dtype, 1, 240)[0])
+    cube = flat.view(3, 5, 16)
+    # dense, whatever the base address: the tensor itself comes back, nothing is copied
+    for t in (flat, flat[7:], flat[:0], flat[3:4], cube, cube[1:], cube[:, :1].expand(3, 1, 16)[:1], flat[::2][:1],
+              V.make_flat(flat, 3).view):
+        assert _ffi._dense(t, "t") is t
+    assert _ffi._dense(cube, "mask", dtype=tdt) is cube
+    # not dense: every other element, a transpose, repeated rows, a narrowed last axis, rows at a pitch
+    for t in (flat[::2], cube.transpose(1, 2), cube[:, :, :13], cube[:1].expand(3, 5, 16), cube[:, ::2], flat.view(15, 16).t(),
+              flat.view(15, 16)[:, :8]):
+        assert not t.is_contiguous()
+        _raises_naming("mask", lambda: _ffi._dense(t, "mask"))
+    other = torch.float64 if tdt != torch.float64 else torch.float32
+    _raises_naming("mask", lambda: _ffi._dense(cube, "mask", dtype=other))
+    _raises_naming("x", lambda: _ffi._dense(flat.numpy(), "x"))
+    _raises_naming("x", lambda: _ffi._dense(None, "x"))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_dense_rows_is_the_rule_of_rows_for_an_output(dtype):
+    """An output cannot be copied: what ``_rows`` passes on untouched is accepted, what it copies is refused."""
+    from noisereduce_amd import _ffi
+    a = _samples(dtype, 4, 120)
+    for name in _layout_names(dtype):
+        lay = V.make(name, V.odd_rows(a) if name == "oddL" else a)
+        if name in V.COPY_LAYOUTS:
+            _raises_naming("out", lambda: _ffi._dense(lay.view, "out", rows=True))
+        else:
+            assert _ffi._dense(lay.view, "out", rows=True) is lay.view
+            assert _ffi._rows(lay.view)[0] is lay.view
+    t = torch.from_numpy(a)
+    # a column range of a wider buffer (the pipelined upload's out=), one row of any stride, one column
+    for ok in (t[:, 10:50], t[1:2, ::1], t[:1].expand(1, 120), t[:, :1], t[:, ::2][:, :1], t[:0]):
+        assert _ffi._dense(ok, "out", rows=True) is ok
+    for bad in (t[0], t.view(2, 2, 120), t[:, ::2], t.t(), t[:1, ::3]):
+        _raises_naming("out", lambda: _ffi._dense(bad, "out", rows=True))
+
+
+def test_every_strideless_argument_of_the_wrappers_goes_through_dense():
+    """The wrappers named below hand over data_ptr() alone; each checks the tensors it hands over (read from the source:
+    the calls themselves need a device and are made by tests/test_gpu_views.py)."""
+    import inspect
+    from noisereduce_amd import _ffi
+    want = {"process_batch_backward": ["mask"], "process_rows_backward": ["mask"], "gate_spectrum_backward": ["mask"],
+            "gate_spectrum_rows_backward": ["mask"], "gate_features_backward": ["mask"],
+            "gate_features_rows_backward": ["mask"], "process_clips": ["x", "out", "noise"],
+            "stream_push": ["x", "out"], "stream_push_spectrum": ["x", "out", "spec", "mask"],
+            "stream_push_features": ["x", "out", "feat", "mask"], "process_chunks": ["out"],
+            "set_noise_threshold_tensor": ["t"]}
+    for fn, names in want.items():
+        src = inspect.getsource(getattr(_ffi.Gate, fn))
+        for n in names:
+            hit = ('_dense(%s, "%s"' % (n, n)) in src or ('("%s", %s)' % (n, n)) in src and "_dense(t, name)" in src or \
+                (n == "mask" and "self._saved_mask(mask)" in src)
+            assert hit, "%s hands %s to the library unchecked" % (fn, n)
+        assert src.index("_dense(") < src.index("self.lib.") if "_dense(" in src else src.index("_saved_mask(") < src.index("self.lib.")
+    assert '_dense(mask, "mask", dtype=torch.float32)' in inspect.getsource(_ffi.Gate._saved_mask)
+
+
 # ---- the floor's unit maximum ------------------------------------------------------------------------------------------
 U_CELLS = [(dt, where, k) for dt in ("float32", "int16") for where in ("first", "last") for k in V.U_OFFSETS[dt]]
 
