@@ -27,10 +27,10 @@ SG_API int sg_debug_range(const sg_handle* h, int64_t range[2]);
  * re-evaluated in float64 since the handle was created (the float32 statistics could not decide them within their error
  * bound); divide by rows x 513 for the rate.  which = 1 / 2: batches of the one-pass gate that took the in-kernel / the a-priori
  * floor test (SG_OPT_FLOOR_TEST) since the handle was created (host counters, no synchronisation); which = 3: launch epoch of the
- * last gate call in which some chunk's floor test fired (0: never; synchronises).  which = 4 .. 16: development builds of the
- * persistent one-pass gate only (-DOP_TILECOUNT / -DOP_WHO / -DOP_TRACE libraries, tools/experiments/persist_*.py: words of the
- * host-mapped error block; 8: unfinished tiles of the phase trace; 16: the per-ticket draw / start record around ticket *value,
- * on stderr) -- they return 0 or SG_E_INVALID in the product library.  which = 17: the mask smoothing of the last
+ * last gate call in which some chunk's floor test fired (0: never; synchronises).  which = 4 .. 15: word `which` of the host-mapped
+ * error block (synchronises; no kernel of the product library writes these words: 0), except which = 8 in a -DOP_TRACE=1
+ * development library of the persistent one-pass gate (tools/trace_onepass.py, tools/ab_persist.py): the unfinished tiles of the
+ * last first launch's phase trace, listed on stderr.  which = 16: SG_E_INVALID.  which = 17: the mask smoothing of the last
  * variant-S gate call or sg_process_batch call on the handle, 0 when that call launched none or failed before it (host
  * bookkeeping, no synchronisation; sg_process_rows / sg_process_clips / streams do not route on the widths and leave it alone): bits 0..7 the SG_SMOOTH_* kernel below, bits 8..15 the bytes of the cell it sums in (1 / 2: integer counts,
  * 4 / 8: float / double), bits 16.. the output frames of one of its tiles (0: no tile). */

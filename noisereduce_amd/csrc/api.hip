@@ -60,67 +60,6 @@
 #ifndef SG_SHORT_TEAMS
 #define SG_SHORT_TEAMS 1
 #endif
-#ifndef SG_CHAIN_PAR
-#define SG_CHAIN_PAR 1    // the non-stationary gate's tile chain in 16 parallel runs per band (nonstat.hpp: k_iir_chain_par); 0: A/B
-#endif
-// Development builds of the n_fft = 1024 one-pass gate (-DOP_WHO=1, -DOP_TRACE=1): process-wide device buffers that
-// stage_onepass attaches to the first launch's arguments; sg_debug_counter 16 / 8 read them back.
-#if OP_WHO
-static unsigned* g_who_dev = nullptr;     // per workgroup of the persistent gate: ticket started, iteration, ticket drawn next, stage
-static hipError_t op_who_attach(sg::fast::OnePassArgs& P, hipStream_t st) {
-  hipError_t e;
-  if (!g_who_dev && (e = hipMalloc((void**)&g_who_dev, 4096 * 16)) != hipSuccess) return e;
-  P.who = g_who_dev;
-  return hipMemsetAsync(g_who_dev, 0, 4096 * 16, st);
-}
-#endif
-#if OP_TRACE
-static unsigned* g_trace_dev = nullptr;   // the one-pass gate's phase trace of the last first launch: sg_debug_counter 8
-static size_t g_trace_tiles = 0;
-static int g_trace_ntt = 1;
-static size_t g_trace_slots = 0;
-// at exit: the average shader cycles per wave and phase of the last traced launch (tools/trace_onepass.py --table reads these lines)
-static void op_trace_report() {
-  std::vector<unsigned> hst(g_trace_slots * 16);
-  if (hipMemcpy(hst.data(), g_trace_dev, hst.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return;
-  double sum[14] = {0}, w = 0, mx = 0;
-  double wsum[4][14] = {{0}}, ww[4] = {0};   // the same per wave index (slot = ticket * 4 + wave)
-  for (size_t i = 0; i < g_trace_slots; ++i) {
-    if (hst[i * 16 + 15] != 1u) continue;
-    w += 1;
-    ww[i & 3] += 1;
-    double tot = 0;
-    for (int k = 0; k < 14; ++k) { sum[k] += hst[i * 16 + k]; wsum[i & 3][k] += hst[i * 16 + k]; tot += hst[i * 16 + k]; }
-    mx = std::max(mx, tot);
-  }
-  for (int wv = 0; wv < 4; ++wv) {
-    fprintf(stderr, "[OP_TRACE] wave %d (%.0f completed):", wv, ww[wv]);
-    for (int k = 0; k < 14; ++k) fprintf(stderr, " %d:%.0f", k, wsum[wv][k] / (ww[wv] > 0 ? ww[wv] : 1));
-    fprintf(stderr, "\n");
-  }
-  fprintf(stderr, "[OP_TRACE] completed waves %.0f; average shader cycles per wave and phase:", w);
-  double tot = 0;
-  for (int k = 0; k < 14; ++k) { fprintf(stderr, " %d:%.0f", k, sum[k] / (w > 0 ? w : 1)); tot += sum[k] / (w > 0 ? w : 1); }
-  fprintf(stderr, "  sum %.0f  longest wave %.0f\n", tot, mx);
-}
-// one device trace [workgroup][wave][16] of `tiles` tiles (`ntt` per unit), overwritten by every launch
-static hipError_t op_trace_attach(sg::fast::OnePassArgs& P, size_t tiles, int ntt, hipStream_t st) {
-  const size_t slots = tiles * 4;
-  if (!g_trace_dev || g_trace_slots < slots) {
-    hipError_t e = hipMalloc((void**)&g_trace_dev, slots * 64);   // (the smaller one stays allocated, as the trace of a launch that may still run)
-    if (e != hipSuccess) return e;
-    g_trace_slots = slots;
-    static const int registered = atexit(op_trace_report);
-    (void)registered;
-  }
-  P.trace = g_trace_dev;
-  g_trace_tiles = tiles; g_trace_ntt = ntt;
-  return hipMemsetAsync(g_trace_dev, 0, slots * 64, st);
-}
-#endif
-#ifndef SG_STATS_TEAM
-#define SG_STATS_TEAM 1   // float64 noise-clip transform of 1024 points (n_fft = 2048) by a whole workgroup (launch_stft_n); 0: A/B
-#endif
 template <int N>
 constexpr int team_threads() {
   return N >= SG_TEAM_N ? 256 : (!SG_SHORT_TEAMS ? 64 : (N <= 128 ? 16 : (N == 256 ? 32 : 64)));
@@ -275,7 +214,7 @@ static hipError_t launch_stft_n(const View& v, const Geom& g, int64_t units, con
     return launch_lds_if(lds > 65536, kern, grid, dim3(WAVES * NT), lds, st, v, g, (const cx<TC>*)tw, (const TC*)wfull, P, mag,
                          z, zscale, pmax_bits);
   };
-  if constexpr (sizeof(TC) == 8 && N >= 1024 && N < SG_TEAM_N && SG_STATS_TEAM) {
+  if constexpr (sizeof(TC) == 8 && N >= 1024 && N < SG_TEAM_N) {
     // (round 5) the noise clip in float64 at n_fft = 2048: 293 workgroups of four one-frame wavefronts are one
     // latency-bound round of 32 us.  The whole workgroup on one frame (the N >= SG_TEAM_N shape): four times the
     // workgroups, each transform split over 256 threads: 16.5 us.  (n_fft = 1024 measured too: 14.0 -> 15.9 us, so not there.)
@@ -730,7 +669,7 @@ constexpr int NM_BW = 16;      // bands of the final stage's workgroup: 4 slice 
 constexpr int NM_MAXS = 16;    // slices per thread
 constexpr int NM_MIN_FRAMES = 512;
 template <int N>
-constexpr int nm_team_threads() { return N >= 1024 ? 256 : team_threads<N>(); }   // (n_fft = 2048: the SG_STATS_TEAM shape of launch_stft_n)
+constexpr int nm_team_threads() { return N >= 1024 ? 256 : team_threads<N>(); }   // (n_fft = 2048: the whole-workgroup shape of launch_stft_n)
 template <int N>
 constexpr int nm_frames_per_slice() { return 1024 / nm_team_threads<N>() - 1; }
 static int nm_fps(int N) {
@@ -1223,7 +1162,7 @@ static int stage_nonstat_mask2(sg_handle* h, const View& v, const Geom& g, int64
   const RegGeom* r = reg_geom(h);
   const int plen = r ? r->frames : 16, per = NS_TT / plen;
   const int64_t nsub = (g.T + plen - 1) / plen;
-  const bool sub_ok = r ? SG_CHAIN_PAR && !h->force_split && ub <= 65535 &&
+  const bool sub_ok = r ? !h->force_split && ub <= 65535 &&
                               nsp_ok((g.T + NS_TT - 1) / NS_TT, per)   // (the serial chain kernels know 16-frame pieces only)
                         : h->fast_ok && !h->force_nofast;
   int rc;
@@ -1241,7 +1180,7 @@ static int stage_nonstat_mask2(sg_handle* h, const View& v, const Geom& g, int64
     ProfScope ps(h, SG_STAGE_IIR_CHAIN, st);
     // (round 5) k_iir_chain_par: the chain in 16 runs per band, straight from the 16-frame sub-tile partials where
     // k_mag_fast left them (no k_iir_comb); SG_OPT_FORCE_SPLIT keeps the serial kernels (A/B)
-    const bool par = SG_CHAIN_PAR && !h->force_split && ub <= 65535;
+    const bool par = !h->force_split && ub <= 65535;
     const dim3 pgrid((unsigned)((g.F + 63) / 64), (unsigned)ub);
     // c^len and 1 - c^(2 len) of a full piece and of the unit's last one (uniform: computed here, not per thread)
     auto piece_pows = [&](int plen, int64_t np, double* o) {
@@ -1641,6 +1580,54 @@ static int stage_apply_fast(sg_handle* h, const View& v, const Geom& g, int64_t 
   return SG_OK;
 }
 
+// The -DOP_TRACE=1 development build of the n_fft = 1024 one-pass gate (onepass.hpp; tools/trace_onepass.py, tools/ab_persist.py):
+// one process-wide device buffer that stage_onepass attaches to the first launch's arguments; sg_debug_counter 8 reads it back
+// (onepass_dev_counter_impl).
+#if OP_TRACE
+static unsigned* g_trace_dev = nullptr;   // the one-pass gate's phase trace of the last first launch: sg_debug_counter 8
+static size_t g_trace_tiles = 0;
+static int g_trace_ntt = 1;
+static size_t g_trace_slots = 0;
+// at exit: the average shader cycles per wave and phase of the last traced launch (tools/trace_onepass.py --table reads these lines)
+static void op_trace_report() {
+  std::vector<unsigned> hst(g_trace_slots * 16);
+  if (hipMemcpy(hst.data(), g_trace_dev, hst.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return;
+  double sum[14] = {0}, w = 0, mx = 0;
+  double wsum[4][14] = {{0}}, ww[4] = {0};   // the same per wave index (slot = ticket * 4 + wave)
+  for (size_t i = 0; i < g_trace_slots; ++i) {
+    if (hst[i * 16 + 15] != 1u) continue;
+    w += 1;
+    ww[i & 3] += 1;
+    double tot = 0;
+    for (int k = 0; k < 14; ++k) { sum[k] += hst[i * 16 + k]; wsum[i & 3][k] += hst[i * 16 + k]; tot += hst[i * 16 + k]; }
+    mx = std::max(mx, tot);
+  }
+  for (int wv = 0; wv < 4; ++wv) {
+    fprintf(stderr, "[OP_TRACE] wave %d (%.0f completed):", wv, ww[wv]);
+    for (int k = 0; k < 14; ++k) fprintf(stderr, " %d:%.0f", k, wsum[wv][k] / (ww[wv] > 0 ? ww[wv] : 1));
+    fprintf(stderr, "\n");
+  }
+  fprintf(stderr, "[OP_TRACE] completed waves %.0f; average shader cycles per wave and phase:", w);
+  double tot = 0;
+  for (int k = 0; k < 14; ++k) { fprintf(stderr, " %d:%.0f", k, sum[k] / (w > 0 ? w : 1)); tot += sum[k] / (w > 0 ? w : 1); }
+  fprintf(stderr, "  sum %.0f  longest wave %.0f\n", tot, mx);
+}
+// one device trace [workgroup][wave][16] of `tiles` tiles (`ntt` per unit), overwritten by every launch
+static hipError_t op_trace_attach(sg::fast::OnePassArgs& P, size_t tiles, int ntt, hipStream_t st) {
+  const size_t slots = tiles * 4;
+  if (!g_trace_dev || g_trace_slots < slots) {
+    hipError_t e = hipMalloc((void**)&g_trace_dev, slots * 64);   // (the smaller one stays allocated, as the trace of a launch that may still run)
+    if (e != hipSuccess) return e;
+    g_trace_slots = slots;
+    static const int registered = atexit(op_trace_report);
+    (void)registered;
+  }
+  P.trace = g_trace_dev;
+  g_trace_tiles = tiles; g_trace_ntt = ntt;
+  return hipMemsetAsync(g_trace_dev, 0, slots * 64, st);
+}
+#endif
+
 // One-pass stationary gate (default geometry, onepass.hpp): forward transform once per frame; decide,
 // publish the tile's bits, smooth in LDS, x mask, inverse transform, overlap-add -- one kernel (+ the
 // seam kernel for the 3 hops that straddle two tiles).  (route.hpp: onepass_ok -- a shape that is not eligible runs the
@@ -1698,21 +1685,14 @@ static int stage_onepass(sg_handle* h, const View& v, const View& vx, const Geom
     }
     // three workgroups per CU (LDS) is what is resident at once; every workgroup ends on one ticket past the last tile
     static const int pg_per_cu = [] { const char* e = getenv("SG_ONEPASS_WG_PER_CU"); int v = e ? atoi(e) : 3; return v >= 1 && v <= 3 ? v : 3; }();   // (experiments: fewer resident workgroups)
-#if OP_MAX_ITERS == 1
-    (void)pg_per_cu;   // (diagnosis) one workgroup per tile, each draws its one ticket
-#else
     if (persist) {
       C.grid = (unsigned)std::min<int64_t>(C.total, (int64_t)pg_per_cu * h->n_cu);
       C.tickets = C.total + C.grid;
     }
-#endif
     if (h->tile_order == 1) {   // SG_OPT_TILE_ORDER 1: tile = block index (no ticket)
       Q.ticket_base = 0xffffffffu;
       C.tickets = 0;
     }
-#if OP_WHO
-    HIPCHK(h, op_who_attach(Q, st));
-#endif
 #if OP_TRACE
     HIPCHK(h, op_trace_attach(Q, C.total, (int)C.n_tiles + 2, st));
 #endif
@@ -2207,9 +2187,6 @@ extern "C" int sg_noise_stats(sg_handle* h, const void* noise_dev, int dtype, in
   if (!noise_dev || !dtype_ok(dtype) || C < 1 || n < 1) FAIL(h, SG_E_INVALID, "sg_noise_stats: bad argument");
   if (h->p.variant != SG_VARIANT_S) FAIL(h, SG_E_INVALID, "sg_noise_stats is a variant-S entry point");
   if (n < h->W) FAIL(h, SG_E_INVALID, "noise clip of %lld samples is shorter than win_length=%d", (long long)n, h->W);
-#ifdef SG_EXP_SKIP_STATS   // development experiment (tools/experiments/stats_in_launch.sh): the step without its statistics launches
-  if (h->has_thresh && h->t2_ready) return SG_OK;
-#endif
   hipStream_t st = (hipStream_t)stream;
   struct Tag {
     sg_handle* h;
@@ -2734,10 +2711,9 @@ int sg::host::expand_k16_mask(sg_handle* h, size_t cells, hipStream_t st) {
   return SG_OK;
 }
 
-#if OP_TRACE || OP_WHO
+#if OP_TRACE
 static int onepass_dev_counter_impl(sg_handle* h, int which, int64_t* value, void* stream, bool* done) {
   *done = true;
-#if OP_TRACE
   if (which == 8) {
     // (diagnosis) after a call that lost a hand-off: the tiles of the last first launch that did not run to the end -- who took
     // their ticket (workgroup, iteration) and the last phase each of their four waves stamped -- on stderr; *value = their number
@@ -2763,31 +2739,12 @@ static int onepass_dev_counter_impl(sg_handle* h, int which, int64_t* value, voi
     *value = bad;
     return SG_OK;
   }
-#endif
-#if OP_WHO
-  if (which == 16) {   // (diagnosis) the tickets around *value (in): who drew them while on which tile, who started them, on stderr
-    HIPCHK(h, hipStreamSynchronize((hipStream_t)stream));
-    std::vector<unsigned> w(4096 * 4);
-    HIPCHK(h, hipMemcpy(w.data(), g_who_dev, w.size() * 4, hipMemcpyDeviceToHost));
-    const long long T = *value;
-    if (T < 0) {   // everything, one line per ticket: ticket, drawer workgroup, its iteration, the tile it was on, starter workgroup, its iteration, past-bits flag
-      for (long long t = 0; t < 4096; ++t)
-        if (w[t * 4] | w[t * 4 + 2])
-          fprintf(stderr, "[whoall] %lld %d %u %u %d %u %u\n", t, (int)(w[t * 4] & 0xffffu) - 1, w[t * 4] >> 16, w[t * 4 + 1], (int)(w[t * 4 + 2] & 0xffffu) - 1, w[t * 4 + 2] >> 16, w[t * 4 + 3]);
-      return SG_OK;
-    }
-    for (long long t = std::max<long long>(0, T - 14); t <= std::min<long long>(4095, T + 3); ++t)
-      fprintf(stderr, "[who] ticket %lld: drawn by wg %d (iteration %u) while on tile %u; started by wg %d (iteration %u); past its bits poll: %u\n", t,
-              (int)(w[t * 4] & 0xffffu) - 1, w[t * 4] >> 16, w[t * 4 + 1], (int)(w[t * 4 + 2] & 0xffffu) - 1, w[t * 4 + 2] >> 16, w[t * 4 + 3]);
-    return SG_OK;
-  }
-#endif
   *done = false;
   return SG_OK;
 }
 #endif
 bool sg::host::onepass_dev_counter(sg_handle* h, int which, int64_t* value, hipStream_t st, int* rc) {
-#if OP_TRACE || OP_WHO
+#if OP_TRACE
   bool done = false;
   *rc = onepass_dev_counter_impl(h, which, value, (void*)st, &done);
   return done;

@@ -167,11 +167,11 @@ extern "C" int sg_debug_counter(sg_handle* h, int32_t which, int64_t* value, voi
     *value = h->err_host ? (int64_t)h->err_host[1] : 0;
     return SG_OK;
   }
-  if (which == 8 || which == 16) {   // the OP_TRACE / OP_WHO development builds keep their buffers next to the gate (api.hip)
+  if (which == 8) {   // the OP_TRACE development build keeps its buffer next to the gate (api.hip); the product library goes on to the error block
     int rc = SG_OK;
     if (onepass_dev_counter(h, which, value, (hipStream_t)stream, &rc)) return rc;
   }
-  if (which >= 4 && which <= 15) {   // development (-DOP_TILECOUNT=1 builds): tiles completed / sum of their tickets, persistent gate
+  if (which >= 4 && which <= 15) {   // word `which` of the host-mapped error block (diagnosis builds of the persistent gate wrote them; 0 now)
     HIPCHK(h, hipStreamSynchronize((hipStream_t)stream));
     *value = h->err_host ? (int64_t)h->err_host[which] : 0;
     return SG_OK;

@@ -229,7 +229,7 @@ void rg_prof_end(void* tok);
 int handoff_verdict(sg_handle* h);
 // sg_debug_fetch field 1 after a fused batch that left K counts only: expands them into the float mask field M
 int expand_k16_mask(sg_handle* h, size_t cells, hipStream_t st);
-// sg_debug_counter 8 / 16 of the OP_TRACE / OP_WHO development builds; false: not such a build, nothing done
+// sg_debug_counter 8 of the OP_TRACE development build (api.hip, next to stage_onepass); false: not such a build, nothing done
 bool onepass_dev_counter(sg_handle* h, int which, int64_t* value, hipStream_t st, int* rc);
 
 inline int64_t frames_for(const sg_handle* h, int64_t L) {

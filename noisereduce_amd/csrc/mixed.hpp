@@ -23,14 +23,11 @@ namespace sg {
 // LDS index padding of the transform buffers: float64 as fft_wave.hpp's lp (one spare element per 8); float32 NONE.  A
 // Stockham pass reads lane-contiguous and WRITES with strides of R (first pass) or in runs of S elements R S apart: unpadded,
 // the 8-byte float32 elements of a wavefront land on a few banks (radix 8, first pass: a 16-way conflict by address).
-// Measured (round 6, MR_PAD32 = 1: one spare element per 32, i.e. per bank cycle, which moves successive 256-byte rows two
+// Measured (round 6, with one spare float32 element per 32, i.e. per bank cycle, which moves successive 256-byte rows two
 // banks apart): k_decide_mr 112 -> 118 us, k_apply_istft_mr 136 -> 176 us at n_fft = 1000 -- the index arithmetic costs more
 // than the conflicts did, as fft_wave.hpp found for its own per-8 padding.
-#ifndef MR_PAD32
-#define MR_PAD32 0
-#endif
 template <typename T>
-__host__ __device__ constexpr int mlp(int e) { return sizeof(T) == 8 ? e + (e >> 3) : (MR_PAD32 ? e + (e >> 5) : e); }
+__host__ __device__ constexpr int mlp(int e) { return sizeof(T) == 8 ? e + (e >> 3) : e; }
 template <typename T>
 __host__ __device__ constexpr int mlpn(int n) { return mlp<T>(n) + 1; }
 

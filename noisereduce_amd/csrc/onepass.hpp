@@ -36,53 +36,15 @@
 namespace sg {
 namespace fast {
 
-
-#ifndef OP_LATE_ARGS
-#define OP_LATE_ARGS 1   // 1: the epilogue re-reads its arguments from the kernel-argument segment (see "LATE ARGUMENTS" in the kernel)
-#endif
+// Build-time switches of this kernel (tools/README.md lists every switch of csrc/ with what builds with it)
 #ifndef OP_TRACE
-#define OP_TRACE 0
-#endif
-#ifndef OP_ARGCHECK
-#define OP_ARGCHECK 0
-#endif
-#ifndef OP_TILECOUNT
-#define OP_TILECOUNT 0
+#define OP_TRACE 0   // (development) 1: per-phase shader-clock stamps, see OP_STAMP below
 #endif
 #ifndef OP_NO_LOOPTOP_WAIT
 #define OP_NO_LOOPTOP_WAIT 0   // (diagnosis) 1: without the explicit LDS wait before the persistent loop's top barrier (the state that lost hand-offs)
 #endif
-#ifndef OP_BACKOFF
-#define OP_BACKOFF 0   // (diagnosis) 1: a poll that has missed 8 times sleeps ~3.5 us between tries instead of 64 cycles (is it the polls' own traffic?)
-#endif
-#if OP_BACKOFF
-#define OP_POLL_SLEEP(spin) do { if ((spin) >= 8) __builtin_amdgcn_s_sleep(127); else __builtin_amdgcn_s_sleep(1); } while (0)
-#else
-#define OP_POLL_SLEEP(spin) __builtin_amdgcn_s_sleep(1)
-#endif
-#ifndef OP_WHO
-#define OP_WHO 0   // (diagnosis) 1: a poll that gives up leaves its tile's ticket, what it waited for and the tag it saw in the error words 8..13
-#endif
-#ifndef OP_DRAW_TOP
-#define OP_DRAW_TOP 0   // (diagnosis, with -DOP_PF_AT=6) 1: the persistent loop draws its next ticket at the loop top -- no ticket is held while the previous tile is finished
-#endif
-#ifndef OP_RESTAGE
-#define OP_RESTAGE 0   // (diagnosis) 1: the persistent loop stages its LDS tables again in every iteration (is a table overwritten between tiles?)
-#endif
-#ifndef OP_MAX_ITERS
-#define OP_MAX_ITERS 0   // (diagnosis) 1: the persistent instantiation on a grid of one workgroup per tile, no second iteration -- is it the LOOP or the code?
-#endif
-#ifndef OP_LATE_START_US
-#define OP_LATE_START_US 0
-#endif
-#ifndef OP_EXP_STALL_NS
-#define OP_EXP_STALL_NS 0   // development experiment (see OP_STAMP(4))
-#endif
-#ifndef OP_INPLACE
-#define OP_INPLACE 0   // 1: split / merge in place after a one-off permutation of lane 0's registers (k_row_gate's formulation)
-                       // instead of operand selects per pair.  Round 4: same instruction count (96 + 8 v_cndmask either way),
-                       // same 168 VGPRs and SGPR spills in this kernel -- no gain here, kept for A/B builds
-#endif
+// between two tries of a bounded poll: 64 cycles
+__device__ __forceinline__ void op_poll_sleep() { __builtin_amdgcn_s_sleep(1); }
 struct OnePassArgs {
   ApplyArgs A;              // view, geometry, output map, tables, seam buffer (A.K / A.Mf unused)
   // the caller's samples in their own dtype (A.view may be a float32 copy): exact refinement.  Only these three fields
@@ -116,31 +78,36 @@ struct OnePassArgs {
 #if OP_TRACE
   unsigned* trace;                   // [workgroups][4 waves][16] shader cycles per phase (slot 15 = 1: tile completed): development builds
 #endif
-#if OP_WHO
-  unsigned* who;                     // [ticket < 4096][4]: drawn by (workgroup + 1 | iteration << 16), while on tile, started by, past its bits poll -- development builds
-#endif
 };
 
-// exact float64 |X[f]|^2 of frame t (see k_decide_fast).  A rare path (about one wave in fifty): with OP_LATE_ARGS its
-// arguments -- a dozen 64-bit values of the view -- are read from the kernel-argument segment HERE (scalar loads through an
-// opaque pointer) instead of staying live in scalar registers from the entry block to the decision stage.
-#if OP_LATE_ARGS
-#define OP_XARG(type, member) (*(const __attribute__((address_space(4))) type*)(kp4 + __builtin_offsetof(OnePassArgs, member)))
-#else
-#define OP_XARG(type, member) (P.member)
-#endif
+// LATE ARGUMENTS.  Whatever the kernel needs of its arguments after the entry block it reads again from the kernel-argument
+// segment, where it needs it: scalar loads through an OPAQUE pointer (the compiler cannot merge them with the entry block's
+// loads or hoist them above the place where the pointer is made), instead of values that stay live in scalar registers
+// across the phases in between.  op_late_ptr() makes such a pointer -- every site makes its own, at its own place in the
+// text --, OP_LATE reads a member of OnePassArgs through it, OP_LATE_PTR a member that is a pointer (rebuilt from its
+// 64 bits: a generic pointer to the compiler, see "GLOBAL accesses" below).  OnePassArgs lies at the start of the segment
+// in both kernels (k_floor_fix: FloorFixArgs::P).
+typedef const __attribute__((address_space(4))) char* op_late_t;
+__device__ __forceinline__ op_late_t op_late_ptr() {
+  op_late_t kp = (op_late_t)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(kp));
+  return kp;
+}
+#define OP_LATE(kp, type, member) (*(const __attribute__((address_space(4))) type*)((kp) + __builtin_offsetof(OnePassArgs, member)))
+#define OP_LATE_PTR(kp, type, member) ((type)(uintptr_t)OP_LATE(kp, unsigned long long, member))
+
+// exact float64 |X[f]|^2 of frame t (see k_decide_fast).  A rare path (about one wave in fifty): its arguments -- a dozen
+// 64-bit values of the view -- are late arguments, read HERE instead of staying live in scalar registers from the entry
+// block to the decision stage.
 __device__ __forceinline__ double op_exact_power(const OnePassArgs& P, int64_t row, int64_t chunk, int64_t t, int f,
                                                  int lane) {
-#if OP_LATE_ARGS
-  const __attribute__((address_space(4))) char* kp4 = (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(kp4));
-#endif
-  const int64_t s0 = t * OP_XARG(int32_t, A.g.H) - OP_XARG(int32_t, A.g.padL);
-  const int64_t v_cs = OP_XARG(int64_t, A.view.cs), v_pad = OP_XARG(int64_t, A.view.pad), v_Lp = OP_XARG(int64_t, A.view.Lp),
-                v_lo = OP_XARG(int64_t, A.view.lo), v_hi = OP_XARG(int64_t, A.view.hi), x_stride = OP_XARG(int64_t, stride_exact);
-  const void* const x_exact = (const void*)(uintptr_t)OP_XARG(unsigned long long, x_exact);
-  const int x_dtype = OP_XARG(int, dtype_exact);
-  const char* const tab = (const char*)(uintptr_t)OP_XARG(unsigned long long, tab);
+  const op_late_t kp4 = op_late_ptr();
+  const int64_t s0 = t * OP_LATE(kp4, int32_t, A.g.H) - OP_LATE(kp4, int32_t, A.g.padL);
+  const int64_t v_cs = OP_LATE(kp4, int64_t, A.view.cs), v_pad = OP_LATE(kp4, int64_t, A.view.pad), v_Lp = OP_LATE(kp4, int64_t, A.view.Lp),
+                v_lo = OP_LATE(kp4, int64_t, A.view.lo), v_hi = OP_LATE(kp4, int64_t, A.view.hi), x_stride = OP_LATE(kp4, int64_t, stride_exact);
+  const void* const x_exact = OP_LATE_PTR(kp4, const void*, x_exact);
+  const int x_dtype = OP_LATE(kp4, int, dtype_exact);
+  const char* const tab = OP_LATE_PTR(kp4, const char*, tab);
   // the ORIGINAL samples: view_sample on A.view's geometry with the caller's pointer / dtype / stride
   const int64_t e = chunk * v_cs - v_pad + s0;   // the frame's first sample in its row
   int a, b;
@@ -161,16 +128,10 @@ __device__ __forceinline__ unsigned op_nan_bits() {
 // the compiler, its accesses are FLAT, and while a FLAT access is pending every wait the compiler emits is vmcnt(0) / lgkmcnt(0)
 // -- never a partial vmcnt(N) -- which also waits for whatever the wave issued AFTER the value it needs (the next tile's
 // prefetched samples, the open seam's loads) and for the write-through acknowledgements of the inline-asm sc1 stores.
-#ifndef OP_WAIT_SITES
-#define OP_WAIT_SITES 7   // (A/B builds) bit 0: the mid-tile ticket draw is a global atomic, bit 1: the epilogue's 1 / envelope load and output
-                          // stores are global accesses, bit 2: the smoothing stage's MFMA operands come from LDS (0: the parent's forms)
-#endif
+// So the epilogue's 1 / envelope load and output stores, the mid-tile ticket draw and the error word go through
+// address_space(1) pointers, and the smoothing stage's MFMA operands come from LDS (s_mc): profiles/onepass_chain.txt, D.
 typedef float op_v4f __attribute__((ext_vector_type(4)));
-#if OP_WAIT_SITES & 2
 #define OP_G4 __attribute__((address_space(1)))
-#else
-#define OP_G4
-#endif
 __device__ __forceinline__ float4 op_ldg4(const float* p) {
   const op_v4f v = *(const OP_G4 op_v4f*)p;
   return make_float4(v[0], v[1], v[2], v[3]);
@@ -183,12 +144,8 @@ __device__ __forceinline__ void op_stg4(float* p, float4 a) {
 // passes through a vector register the compiler cannot see into: to a wave-uniform address the atomic optimizer applies its
 // wave reduction (v_mbcnt / s_bcnt1 / v_readfirstlane), and the readfirstlane waits for the atomic three instructions later.
 __device__ __forceinline__ unsigned op_draw_ticket_late(unsigned long long p64) {
-#if OP_WAIT_SITES & 1
   asm volatile("" : "+v"(p64));
   return __hip_atomic_fetch_add((__attribute__((address_space(1))) unsigned*)p64, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-  return atomicAdd((unsigned*)(uintptr_t)p64, 1u);
-#endif
 }
 
 // a lost hand-off's bit in the host-mapped error word (atomicOr_system on a GLOBAL pointer: cold, but its block lies inside
@@ -215,19 +172,13 @@ __device__ __forceinline__ int op_xor_lanes(int v) {
 #ifndef OP_ABLATE
 #define OP_ABLATE 0
 #endif
-// OP_PLAN_SITES: the places of the PERSIST instantiations that evaluate a ticket against the launch plan (onepass_plan.hpp)
-// instead of deriving the tile's coordinates field by field: 1 loop top (u, jt, row, chunk by multiply-high), 4 prefetch_next,
-// 16 epilogue.  The publish stage and seam_issue measured below 1 % of a step as ceilings and are left alone; the loop top keeps
+// LAUNCH PLAN: three places of the PERSIST instantiations evaluate a ticket against the launch plan (onepass_plan.hpp) instead
+// of deriving the tile's coordinates field by field: the loop top (u, jt, row, chunk by multiply-high), prefetch_next and the
+// epilogue.  The publish stage and seam_issue measured below 1 % of a step as ceilings and are left alone; the loop top keeps
 // its own tile_src: from the plan it cost 30 scalar registers and time (profiles/onepass_tile_plan.txt; the builds that
 // measured both: tools/experiments/onepass_plan_ablate.patch).
-#ifndef OP_PLAN_SITES
-#define OP_PLAN_SITES 21
-#endif
 // OP_TRACE (development only): per-phase shader-clock stamps of every non-halo wave, summed into P.trace (tools/
-// trace_onepass.sh): where a tile's lifetime goes
-#ifndef OP_TRACE
-#define OP_TRACE 0
-#endif
+// trace_onepass.py): where a tile's lifetime goes
 #if OP_TRACE
 #define OP_STAMP(i)                                                                                   \
   do {                                                                                                \
@@ -267,7 +218,7 @@ __device__ __forceinline__ int op_xor_lanes(int v) {
 // Deadlock freedom as before (tickets; publish before wait); a launch needs two resident workgroups, and draws
 // total_tiles + gridDim.x tickets (every workgroup ends on one ticket >= total_tiles).
 // Not for REDO / LOSE / a-priori floor flags (compare constants depend on the unit there) / SG_OPT_TILE_ORDER 1.
-// DEFERRED SEAM (OP_DEFER_SEAM, PERSIST only).  An interior (tile_fast) tile j used to end by polling for tile j - 1's three
+// DEFERRED SEAM (PERSIST only; profiles/onepass_chain.txt, B).  An interior (tile_fast) tile j used to end by polling for tile j - 1's three
 // trailing partial hops.  Tile j - 1 runs in near lockstep and publishes them in its own last phase, so tile j always paid a
 // write-through plus a read round trip with nothing left to hide it behind (phase 13 of the trace).  Now tile j publishes its
 // trailing partials as before but leaves its three LEADING hops open: waves 0 - 2 write their un-normalised partial sums where
@@ -279,16 +230,10 @@ __device__ __forceinline__ int op_xor_lanes(int v) {
 // open seam is closed on the spot before the workgroup leaves, in a halo tile's early exit, and in the epilogue of a tile
 // that is not tile_fast (those keep the immediate protocol for their own hops).  Deadlock freedom: a seam waits for a tile
 // with a LOWER ticket than any this workgroup has held since, and publishing never waits.
-#ifndef OP_LATE_P
-#define OP_LATE_P 1   // 1: every instantiation reads its arguments through late_args() (0 SGPR spills; 0: the by-value struct outside PERSIST)
-#endif
 #ifndef OP_OCC
 #define OP_OCC 3   // workgroups per CU the register budget is set for (development builds: 2 shows the unconstrained pressure)
 #endif
 #define OP_DONE { if (PERSIST) continue; return; }
-#ifndef OP_DEFER_SEAM
-#define OP_DEFER_SEAM 1   // 1: PERSIST instantiations finish a tile_fast tile's leading hops one tile late (0: the immediate poll, A/B builds)
-#endif
 constexpr unsigned OP_SEAM_NONE = 0xffffffffu;   // s_misc[0] (PERSIST): ticket | poison << 31 of the tile whose leading hops are open
 // MERGED (REDO only): the tile runs inside k_floor_fix (below), the one launch that follows the first launch of a lazy call.
 // Its ticket was drawn by the wrapper (`pre_ticket`), it waits for the float64 band maxima of its unit (FloorWait) before it

@@ -30,13 +30,6 @@
   constexpr int SCAN_REG = 5;                     // floor-test slices up to 5 x 256 samples ride in registers
 
   if (REDO && Pk.alim[1] != Pk.tc.need_tag) return;   // second launch of a call none of whose units reported (the common case)
-#if OP_LATE_START_US
-  // (diagnosis) some workgroups of the persistent grid start late, as they do when another kernel holds their compute unit
-  if (PERSIST && (blockIdx.x % 5u) == 1u) {
-    const unsigned long long t0_ = wall_clock64();
-    while ((long long)(wall_clock64() - t0_) < (long long)OP_LATE_START_US * 100 * (1 + (blockIdx.x % 7u))) __builtin_amdgcn_s_sleep(8);
-  }
-#endif
   double t2pre[3];   // compare constants of entries tid, tid + 256 and 512 (they do not depend on the ticket)
   unsigned alim_v = 0u;
   {
@@ -89,9 +82,6 @@
       }
       for (int off = 1; off < 16; off <<= 1) alim_v = min(alim_v, (unsigned)__shfl_xor((int)alim_v, off));
       if (tid == 0) s_misc[2] = alim_v;   // (not a loop-carried register: it would live in scratch)
-#if OP_TILECOUNT == 2
-      if (tid == 0) { s_misc[3] = Pk.total_tiles; s_misc[6] = (unsigned)(uintptr_t)Pk.err; s_misc[7] = (unsigned)((uintptr_t)Pk.err >> 32); }
-#endif
     }
   }
   __syncthreads();
@@ -139,7 +129,7 @@
   };
   // the same for a tile the launch plan knows as blk_vec (an interior unit's: nothing of the view is read)
   static_assert(NF == OP_PLAN_NF && SPAN == OP_PLAN_SPAN && SCAN_REG * WAVES * 64 == OP_PLAN_SCAN_MAX, "onepass_plan.hpp");
-  [[maybe_unused]] auto tile_src_plan = [](const OpPlan& L, const OpTile& tl) -> TileSrc {
+  auto tile_src_plan = [](const OpPlan& L, const OpTile& tl) -> TileSrc {
     TileSrc S;
     const float* base = (const float*)(const __attribute__((address_space(1))) float*)(uintptr_t)L.src;
     S.sp = base + op_plan_src_off(L, tl);
@@ -159,31 +149,28 @@
   float q[NQ];
   float sc[SCAN_REG];
   bool pf = false;
-  constexpr bool DEFER = PERSIST && OP_DEFER_SEAM;
+  constexpr bool DEFER = PERSIST;   // the deferred seam (onepass.hpp)
   // where the open seam of tile `pend` lives: the previous tile's trailing granules of hop `wv`, the output samples
   auto seam_where = [](unsigned pend, const unsigned long long*& src, float*& dst) {
-    typedef const __attribute__((address_space(4))) char* kq_t;
-    kq_t kq = (kq_t)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(kq));
-#define OP_QARG(type, member) (*(const __attribute__((address_space(4))) type*)(kq + __builtin_offsetof(OnePassArgs, member)))
+    const op_late_t kq = op_late_ptr();
     const unsigned tk = pend & 0x7fffffffu;
-    const unsigned ntl = (unsigned)OP_QARG(int, A.n_tiles), nttq = ntl + 2u;
+    const unsigned ntl = (unsigned)OP_LATE(kq, int, A.n_tiles), nttq = ntl + 2u;
     const unsigned uq = tk / nttq;
     const int jq = (int)(tk % nttq) - 1;
-    const unsigned guq = (unsigned)(OP_QARG(int64_t, A.view.unit0) + uq), nchq = (unsigned)OP_QARG(int32_t, A.view.n_chunks);
-    const int64_t rowq = guq / nchq, chunkq = OP_QARG(int64_t, A.view.c0) + guq % nchq;
-    const int64_t tfq = OP_QARG(int64_t, A.h_begin) - 3 + (int64_t)jq * NF;
-    const int64_t pb0 = tfq * 256 - OP_QARG(int32_t, A.g.padL);
-    const int64_t gi00 = chunkq * OP_QARG(int64_t, A.om.g_step) + (pb0 - OP_QARG(int64_t, A.om.p0));
+    const unsigned guq = (unsigned)(OP_LATE(kq, int64_t, A.view.unit0) + uq), nchq = (unsigned)OP_LATE(kq, int32_t, A.view.n_chunks);
+    const int64_t rowq = guq / nchq, chunkq = OP_LATE(kq, int64_t, A.view.c0) + guq % nchq;
+    const int64_t tfq = OP_LATE(kq, int64_t, A.h_begin) - 3 + (int64_t)jq * NF;
+    const int64_t pb0 = tfq * 256 - OP_LATE(kq, int32_t, A.g.padL);
+    const int64_t gi00 = chunkq * OP_LATE(kq, int64_t, A.om.g_step) + (pb0 - OP_LATE(kq, int64_t, A.om.p0));
     // (the tile's part is wave-uniform: two scalar registers each, the lane's offset is added where it is used)
     auto uni = [](const void* p_) -> char* {
       const unsigned long long v_ = (unsigned long long)(uintptr_t)p_;
       return (char*)(uintptr_t)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(v_ >> 32)) << 32) |
                                 (unsigned)__builtin_amdgcn_readfirstlane((int)v_));
     };
-    dst = (float*)uni((float*)(uintptr_t)OP_QARG(unsigned long long, A.om.out) +
-                      (rowq * OP_QARG(int64_t, A.om.stride) + gi00 - OP_QARG(int64_t, A.om.g0)));
-    src = (const unsigned long long*)uni((const unsigned long long*)(uintptr_t)OP_QARG(unsigned long long, part2) +
+    dst = (float*)uni(OP_LATE_PTR(kq, float*, A.om.out) +
+                      (rowq * OP_LATE(kq, int64_t, A.om.stride) + gi00 - OP_LATE(kq, int64_t, A.om.g0)));
+    src = (const unsigned long long*)uni(OP_LATE_PTR(kq, const unsigned long long*, part2) +
                                          ((size_t)uq * ntl + jq - 1) * 3 * 256);
   };
   auto seam_off = [](int wv, int s4_) -> int { return wv * 256 + s4_; };   // a lane's four samples of hop `wv`
@@ -193,10 +180,8 @@
                         unsigned long long g3_, float* dst, float4 ld, float4 nrm) {
     op_v4u ga = {(unsigned)g0_, (unsigned)(g0_ >> 32), (unsigned)g1_, (unsigned)(g1_ >> 32)};
     op_v4u gb = {(unsigned)g2_, (unsigned)(g2_ >> 32), (unsigned)g3_, (unsigned)(g3_ >> 32)};
-    typedef const __attribute__((address_space(4))) char* kq_t;
-    kq_t kq = (kq_t)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(kq));
-    const unsigned e = OP_QARG(unsigned, epoch);
+    const op_late_t kq = op_late_ptr();
+    const unsigned e = OP_LATE(kq, unsigned, epoch);
     if (!(ga[1] == e && ga[3] == e && gb[1] == e && gb[3] == e)) {   // (cold)
       const unsigned long long* src;
       float* d2_;
@@ -207,11 +192,11 @@
                      : "=&v"(ga), "=&v"(gb) : "v"(src) : "memory");
         if (ga[1] == e && ga[3] == e && gb[1] == e && gb[3] == e) break;
         if (spin >= OP_SPIN_MAX) {
-          op_err_or((unsigned*)(uintptr_t)OP_QARG(unsigned long long, err), 2u);
+          op_err_or(OP_LATE_PTR(kq, unsigned*, err), 2u);
           ga[0] = ga[2] = gb[0] = gb[2] = op_nan_bits();   // the previous tile's share is unknown: NaN, not a partial sum
           break;
         }
-        OP_POLL_SLEEP(spin);
+        op_poll_sleep();
       }
     }
     const float psn = __uint_as_float((pend >> 31) * 0x7fc00000u);   // NaN or 0 (scalar arithmetic: as a select the constant was hoisted out of the tile loop and spilled)
@@ -227,10 +212,8 @@
   auto seam_close = [&](unsigned pend, int tid_) {
     const int wv = tid_ >> 6, s4_ = (tid_ & 63) * 4;
     if (pend == OP_SEAM_NONE || wv >= 3) return;
-    typedef const __attribute__((address_space(4))) char* kq_t;
-    kq_t kq = (kq_t)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(kq));
-    const float4 nrm = op_ldg4(&reinterpret_cast<const float*>((const char*)(uintptr_t)OP_QARG(unsigned long long, tab) + OP_TAB_INVN)[s4_]);
+    const op_late_t kq = op_late_ptr();
+    const float4 nrm = op_ldg4(&reinterpret_cast<const float*>(OP_LATE_PTR(kq, const char*, tab) + OP_TAB_INVN)[s4_]);
     const unsigned long long* src;
     float* dst;
     seam_where(pend, src, dst);
@@ -238,28 +221,10 @@
     seam_finish(pend, wv, s4_, 0ull, 0ull, 0ull, 0ull, dst, ld, nrm);   // (tag 0 is never current: the epoch starts at 1 -- straight to the poll)
   };
 
-#if OP_EXP_STALL_NS
-  const unsigned long long op_exp_t0_ = wall_clock64();
-#endif
   for (unsigned iter = 0; iter == 0u || PERSIST; ++iter) {
   // ---- PERSIST: nothing of the arguments or the thread's indices survives an iteration (see above) ----
-  const OnePassArgs& P = (PERSIST || OP_LATE_P) ? *late_args<OnePassArgs>() : Pk;
+  const OnePassArgs& P = *late_args<OnePassArgs>();   // (every instantiation: 0 spilled SGPRs; by value, outside PERSIST, they spilled)
   int tid = threadIdx.x;
-#if OP_ARGCHECK
-  // (diagnosis) do the arguments re-read from the kernel-argument segment still equal the ones the kernel started with?
-#if OP_ARGCHECK == 2
-  if (PERSIST && threadIdx.x == 1) {   // every word of the argument struct, by a thread that draws no ticket
-    const unsigned* a_ = reinterpret_cast<const unsigned*>(&P);
-    const unsigned* b_ = reinterpret_cast<const unsigned*>(&Pk);
-    bool same_ = true;
-    for (unsigned w_ = 0; w_ < sizeof(OnePassArgs) / 4; ++w_) same_ = same_ && a_[w_] == b_[w_];
-    if (!same_) atomicOr_system(Pk.err, 0x80u);
-  }
-#else
-  if (PERSIST && threadIdx.x == 0 && (P.total_tiles != Pk.total_tiles || P.epoch != Pk.epoch || P.xbits != Pk.xbits || P.A.view.x != Pk.A.view.x))
-    atomicOr_system(Pk.err, 0x80u);
-#endif
-#endif
 #if OP_TRACE
   long long t_prev_ = clock64();   // (PERSIST: phase 0 = the wait at the loop-top barrier)
   unsigned* t_slot_ = nullptr;   // known once the ticket is
@@ -278,12 +243,6 @@
 #endif
       __syncthreads();   // the previous tile's epilogue has read every hop accumulator: the slices are free
     }
-#if OP_DRAW_TOP
-    if (iter != 0u) {
-      if (threadIdx.x == 0) s_misc[4u + (iter & 1u)] = atomicAdd(P.ticket, 1u) - P.ticket_base;
-      __syncthreads();
-    }
-#endif
   }
   const ApplyArgs& A = P.A;
   const Geom& G = A.g;
@@ -291,51 +250,11 @@
   const int g = lane >> 4, c = lane & 15;
   const unsigned tk_slot = PERSIST ? 4u + (iter & 1u) : 0u;
   const unsigned ticket = PERSIST ? (unsigned)__builtin_amdgcn_readfirstlane((int)s_misc[tk_slot]) : s_misc[0];
-#if OP_TILECOUNT == 2
-  // (diagnosis) does the late read of total_tiles still equal what the workgroup saw when it started?  Reported through the err pointer
-  // stashed in LDS at the start (not a late read, and no by-value argument inside the loop)
-  if (PERSIST && threadIdx.x == 0 && P.total_tiles != s_misc[3]) {
-    unsigned* e_ = (unsigned*)(((uintptr_t)s_misc[7] << 32) | (uintptr_t)s_misc[6]);
-    atomicOr_system(e_, 0x40u);
-    atomicMax_system(e_ + 6, P.total_tiles);
-    atomicMax_system(e_ + 7, iter);
-  }
-  if (PERSIST && ticket >= s_misc[3]) return;
-#endif
-#if OP_WHO
-  if (PERSIST && threadIdx.x == 0 && ticket < 4096u) P.who[ticket * 4 + 2] = (blockIdx.x + 1u) | (iter << 16);   // who started the tile
-#endif
   if (PERSIST && ticket >= P.total_tiles) {   // (workgroup-uniform)
     if constexpr (DEFER) seam_close((unsigned)__builtin_amdgcn_readfirstlane((int)s_misc[0]), tid);
     return;
   }
-#if OP_TILECOUNT == 1
-  if (PERSIST && threadIdx.x == 0) { atomicAdd_system(P.err + 4, 1u); atomicAdd_system(P.err + 5, ticket); }   // (diagnosis) every ticket taken up
-#endif
-#if OP_RESTAGE
-  if (PERSIST && iter != 0u) {
-    const int t_ = threadIdx.x;
-    tw512[t_] = reinterpret_cast<const cf*>(P.tab + OP_TAB_TW512)[(t_ >> 4) * (t_ & 15)];
-    tw512[t_ + 256] = reinterpret_cast<const cf*>(P.tab + OP_TAB_TW512)[((t_ + 256) >> 4) * (t_ & 15)];
-    reinterpret_cast<float4*>(swin)[t_] = reinterpret_cast<const float4*>(P.tab + OP_TAB_WIN)[t_];
-    s_exp[t_] = reinterpret_cast<const unsigned long long*>(P.tab + OP_TAB_EXP8)[t_];
-    if (t_ < 192) s_mc[t_] = reinterpret_cast<const unsigned long long*>(P.tab + OP_TAB_MCONST)[t_];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const int i = t_ + k * WAVES * 64;
-      if (i > 512) break;
-      const double v_ = P.tc.T2[perm_inv(i)];
-      s_t2[t2_pos(i)] = t2_to_f32(v_, 4.0);
-      s_t2d[i] = v_;
-    }
-  }
-#endif
-  if (PERSIST && tid == 0) {
-    s_misc[1] = 0u;
-#if OP_TK_LATE
-    s_misc[tk_slot ^ 1u] = 0xffffffffu;   // "the next ticket has not arrived yet"
-#endif
-  }
+  if (PERSIST && tid == 0) s_misc[1] = 0u;
 #if OP_TRACE
   t_slot_ = P.trace + ((size_t)ticket * 4 + wave) * 16;
   if (lane == 0) t_slot_[14] = (blockIdx.x + 1u) | (iter << 16);   // who took the ticket up (sg_debug_counter 8 reads it after a lost hand-off)
@@ -345,7 +264,7 @@
   int64_t u, row, chunk;
   int jt;                     // -1 and n_tiles: halo tiles
   bool halo_tile;
-  if constexpr (PERSIST && (OP_PLAN_SITES & 1) != 0) {
+  if constexpr (PERSIST) {
     // the launch plan: both quotients by multiply-high and shifts
     const OpTile tl = op_plan_tile(P.plan, ticket);
     ntt = (int)P.plan.ntt;
@@ -391,7 +310,7 @@
           s_misc[1] = 1u;   // the unit's maxima are unknown: every hop the tile finalises or hands on becomes NaN
           break;
         }
-        OP_POLL_SLEEP(spin);
+        op_poll_sleep();
       }
     }
   }
@@ -548,40 +467,6 @@
   // X2n = E - w O (both 2x the spectrum; E = a + conj b, O = (a - conj b)/i).  Slot order (see k_apply_fast):
   // lanes >= 1 pair registers (sl, 31 - sl); lane 0 pairs its self-conjugate rows differently, handled by
   // selects on the way in HERE only -- the decision stage and the mask stage both read pa/pb in slot order.
-#if OP_INPLACE
-  // In place (rowgate.hpp's formulation): lane 0 permutes its registers ONCE so that register index == entry index in
-  // every lane, then split / merge work on (v[s], v[31 - s]) without operand selects -- ~100 v_cndmask fewer per wave
-  // and the 64 registers of the transform are the 64 split values (no second array alive beside them).
-  // pa[sl] / pb[sl] below are v[sl] / v[31 - sl]; lane 0 keeps its unpaired registers raw in v[0] (bins 0 / 512) and
-  // v[31] (bin 256).  Same split_pair / merge_pair arithmetic in the same order: bit-identical results.
-  const bool l0 = c == 0;
-  cf wlo = reinterpret_cast<const cf*>(P.tab + OP_TAB_TW1024)[c];
-  asm volatile("" : "+v"(wlo.x), "+v"(wlo.y));
-  cf whi = wlo;
-  {
-    const cf w16 = reinterpret_cast<const cf*>(P.tab + OP_TAB_TW1024)[16];
-    if (l0) whi = {-w16.y, w16.x};  // i * w_1024^16
-  }
-  rg_lane0_to_entries(v, l0);
-  {
-    const cf r0 = v[0], r31 = v[31];
-    cf xa, xb;
-    split_pair(r0, r31, wlo, xa, xb);
-    v[0] = {l0 ? r0.x : xa.x, l0 ? r0.y : xa.y};
-    v[31] = {l0 ? r31.x : xb.x, l0 ? r31.y : xb.y};
-#pragma unroll
-    for (int sl = 1; sl < 16; ++sl) {
-      const cf w = mul_tw<false>(sl < 8 ? wlo : whi, twc<32>(sl), tws<32>(sl));
-      cf ya, yb;
-      split_pair(v[sl], v[31 - sl], w, ya, yb);
-      v[sl] = ya;
-      v[31 - sl] = yb;
-    }
-  }
-#define OP_PA(sl) v[sl]
-#define OP_PB(sl) v[31 - (sl)]
-  const cf raw0 = v[0], raw8 = v[31];   // (lane 0 only: the same registers)
-#else
   cf pa[16], pb[16];
   const cf raw0 = v[0], raw8 = v[8];   // lane 0: bins 0 / 512 and bin 256 are not part of a pair
   const bool l0 = c == 0;
@@ -607,14 +492,7 @@
 
 #define OP_PA(sl) pa[sl]
 #define OP_PB(sl) pb[sl]
-#endif
   OP_STAMP(4);   // split
-#if OP_EXP_STALL_NS
-  // (experiment, tools/experiments/stats_in_launch.sh: what a first-round tile would lose waiting at its decision stage for
-  // thresholds that an in-launch statistics chain publishes OP_EXP_STALL_NS after the launch starts; results unchanged)
-  if (PERSIST && iter == 0u)
-    while ((long long)(wall_clock64() - op_exp_t0_) * 10 < (long long)OP_EXP_STALL_NS) __builtin_amdgcn_s_sleep(2);
-#endif
   // ---- decide (k_decide_fast): mask bits of this lane's 32 entries -----------------------------------
   unsigned long long myword;  // lane c < 9 of group g: word c of frame tq + g
   {
@@ -740,28 +618,18 @@
   // ---- publish this tile's bits; the spectra stay in v[] ---------------------------------------------
   // (LATE ARGUMENTS, see the epilogue: what the middle of the kernel needs -- exchange buffer, epoch, error word, tables,
   // mask scale, smoothing width -- is read from the kernel-argument segment here, after the prologue's peak of live scalars)
-#if OP_LATE_ARGS
-  typedef const __attribute__((address_space(4))) char* op_kpm_t;
-  op_kpm_t kpm = (op_kpm_t)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(kpm));
-#define OP_MARG(type, member) (*(const __attribute__((address_space(4))) type*)(kpm + __builtin_offsetof(OnePassArgs, member)))
+  const op_late_t kpm = op_late_ptr();
   const unsigned m_ticket = (unsigned)__builtin_amdgcn_readfirstlane((int)s_misc[tk_slot]);
-  const unsigned m_ntt = (unsigned)(OP_MARG(int, A.n_tiles) + 2);
+  const unsigned m_ntt = (unsigned)(OP_LATE(kpm, int, A.n_tiles) + 2);
   const int64_t m_u = m_ticket / m_ntt;
   const int m_jt = (int)(m_ticket % m_ntt) - 1;
-#else
-#define OP_MARG(type, member) (P.member)
-  const unsigned m_ntt = (unsigned)ntt;
-  const int64_t m_u = u;
-  const int m_jt = jt;
-#endif
-  unsigned long long* const m_xbits = (unsigned long long*)(uintptr_t)OP_MARG(unsigned long long, xbits);
-  const unsigned m_epoch = OP_MARG(unsigned, epoch);
-  unsigned* const m_err = (unsigned*)(uintptr_t)OP_MARG(unsigned long long, err);
-  const char* const m_tab = (const char*)(uintptr_t)OP_MARG(unsigned long long, tab);
-  const float m_kscale = OP_MARG(float, A.kscale);
-  const int m_nt = OP_MARG(int, nt);
-  [[maybe_unused]] const float m_inv_ktot = OP_MARG(float, inv_ktot), m_prop = OP_MARG(float, prop);
+  unsigned long long* const m_xbits = OP_LATE_PTR(kpm, unsigned long long*, xbits);
+  const unsigned m_epoch = OP_LATE(kpm, unsigned, epoch);
+  unsigned* const m_err = OP_LATE_PTR(kpm, unsigned*, err);
+  const char* const m_tab = OP_LATE_PTR(kpm, const char*, tab);
+  const float m_kscale = OP_LATE(kpm, float, A.kscale);
+  const int m_nt = OP_LATE(kpm, int, nt);
+  [[maybe_unused]] const float m_inv_ktot = OP_LATE(kpm, float, inv_ktot), m_prop = OP_LATE(kpm, float, prop);
   unsigned long long* xb_mine = m_xbits + ((size_t)m_u * m_ntt + (m_jt + 1)) * OP_TILE_WORDS;
   // data-tagged granules: every 8-byte store carries 32 mask bits and the launch epoch.  A consumer polls the
   // granules it needs until their tags are current: no separate flag, no drain of the stores, one write-through
@@ -782,11 +650,7 @@
     }
     if constexpr (PERSIST) {
       // a halo tile ends here: its next ticket is drawn on the spot (two tiles in 149 at the default chunking)
-#if OP_MAX_ITERS == 1 || OP_DRAW_TOP
-      if (tid == 0) s_misc[tk_slot ^ 1u] = 0xffffffffu;
-#else
-      if (tid == 0) s_misc[tk_slot ^ 1u] = op_draw_ticket_late(OP_MARG(unsigned long long, ticket)) - OP_MARG(unsigned, ticket_base);
-#endif
+      if (tid == 0) s_misc[tk_slot ^ 1u] = op_draw_ticket_late(OP_LATE(kpm, unsigned long long, ticket)) - OP_LATE(kpm, unsigned, ticket_base);
       pf = false;
       // (defined on this path too: left alone, the registers of the samples staged at the loop top would stay live up to here)
 #pragma unroll
@@ -821,12 +685,7 @@
     wb[r * WP + WP - 1] = 0ull;
   }
   const int q4 = lane >> 4, j16 = lane & 15;
-#if OP_WAIT_SITES & 4
   const long Bf = (long)s_mc[lane], At1 = (long)s_mc[64 + lane], At2 = (long)s_mc[128 + lane];
-#else
-  const unsigned long long* const mc_ = reinterpret_cast<const unsigned long long*>(m_tab + OP_TAB_MCONST);
-  const long Bf = (long)mc_[lane], At1 = (long)mc_[64 + lane], At2 = (long)mc_[128 + lane];
-#endif
   const bool three = 2 * m_nt > 16;      // a third row block (wave-uniform)
   // neighbour-list index m -> tile row: m < m_nt: row m (previous tile), else row m_nt + 16 + (m - m_nt) (next tile)
   const int m1 = j16, m2 = 16 + j16;
@@ -862,13 +721,10 @@
     for (int spin = 0; !(OP_ABLATE & 2) && (LOSE || gr[1] != m_epoch || gr[3] != m_epoch); ++spin) {
       if (LOSE || spin >= OP_SPIN_MAX) {   // every spin is bounded: report instead of hanging the device
         op_err_or(m_err, 1u);
-#if OP_WHO
-        if (atomicAdd_system(m_err + 14, 1u) == 0u) { m_err[8] = m_ticket; m_err[9] = (unsigned)i; m_err[10] = gr[1]; m_err[11] = m_epoch; }
-#endif
         s_misc[1] = 1u;            // the tile's mask is unknown: every hop it finalises or hands on becomes NaN
         break;
       }
-      OP_POLL_SLEEP(spin);
+      op_poll_sleep();
       gr = op_ld16_sc1(src);
     }
     wb[(side ? m_nt + NF + rr : rr) * WP + 1 + w] = (unsigned long long)gr[0] | ((unsigned long long)gr[2] << 32);
@@ -880,11 +736,7 @@
   // FLAT access pending: as flat_atomic_add wave 0's first MFMA of this stage waited vmcnt(0) for it -- op_draw_ticket_late)
   [[maybe_unused]] unsigned nx_raw = 0u;
   if constexpr (PERSIST) {
-#if OP_MAX_ITERS == 1 || OP_DRAW_TOP
-    if (tid == 0) nx_raw = 0xffffffffu + OP_MARG(unsigned, ticket_base);   // "past the last tile": the workgroup leaves at the loop top
-#else
-    if (tid == 0) nx_raw = op_draw_ticket_late(OP_MARG(unsigned long long, ticket));
-#endif
+    if (tid == 0) nx_raw = op_draw_ticket_late(OP_LATE(kpm, unsigned long long, ticket));
   }
   {
     const unsigned char* rp1 = wbb + r1 * WPB + 7 + q4;
@@ -913,19 +765,9 @@
       }
     }
   }
-#if !OP_TK_LATE
   if constexpr (PERSIST) {
-    if (tid == 0) s_misc[tk_slot ^ 1u] = nx_raw - OP_MARG(unsigned, ticket_base);
-#if OP_WHO
-    if (tid == 0) {   // who drew the ticket, and while working on which tile
-      unsigned* w_ = (unsigned*)(uintptr_t)OP_MARG(unsigned long long, who);
-      const unsigned nx_ = nx_raw - OP_MARG(unsigned, ticket_base);
-      if (nx_ < 4096u) { w_[nx_ * 4] = (blockIdx.x + 1u) | (iter << 16); w_[nx_ * 4 + 1] = m_ticket; }
-      if (m_ticket < 4096u) w_[m_ticket * 4 + 3] = 1u;   // this tile is past its neighbours' bits
-    }
-#endif
+    if (tid == 0) s_misc[tk_slot ^ 1u] = nx_raw - OP_LATE(kpm, unsigned, ticket_base);
   }
-#endif
   __syncthreads();  // K of all 16 frames complete; from here every wave touches only its own slice
   OP_STAMP(9);   // smoothing on the matrix cores + barrier
 
@@ -964,28 +806,6 @@
     // mask -> merge (the second half of pair_mask): Yk = X2[k] mk, Yn = conj-pair value x mn, then back to the
     // half-size complex spectrum.  The four 1/2 factors of split and merge ride in the mask scale.
     const float ks = m_kscale * 0.25f;
-#if OP_INPLACE
-    {
-      // slot 0: lanes >= 1 merge the pair (v[0], v[31]); lane 0: bins 0 / 512 from v[0], bin 256 = v[31] scaled
-      const cf r0 = v[0], r31 = v[31];
-      cf xa = r0, xb = r31;
-      merge_pair(xa, xb, wlo, mval(0, ks), mval(31, ks));
-      const float y0 = (r0.x + r0.y) * mval(0, m_kscale);
-      const float yN = (r0.x - r0.y) * k512;
-      const cf z0 = {0.5f * (y0 + yN), 0.5f * (y0 - yN)};
-      const float m8 = mval(31, m_kscale);  // entry 31 of lane 0 = bin 256
-      const cf z8 = {r31.x * m8, r31.y * m8};
-      v[0] = {l0 ? z0.x : xa.x, l0 ? z0.y : xa.y};
-      v[31] = {l0 ? z8.x : xb.x, l0 ? z8.y : xb.y};
-    }
-#pragma unroll
-    for (int sl = 1; sl < 16; ++sl) {
-      const cf w = mul_tw<false>(sl < 8 ? wlo : whi, twc<32>(sl), tws<32>(sl));
-      merge_pair(v[sl], v[31 - sl], w, mval(sl, ks), mval(31 - sl, ks));
-    }
-    rg_lane0_from_entries(v, l0);   // back to the transform's register order
-  }
-#else
     auto sel = [&](cf a0, cf a1) -> cf { return {l0 ? a0.x : a1.x, l0 ? a0.y : a1.y}; };
     auto merge = [&](cf& xa, cf& xb, cf w, float mk, float mn) { merge_pair(xa, xb, w, mk, mn); };
     merge(pa[0], pb[0], wlo, mval(0, ks), mval(31, ks));
@@ -1015,15 +835,8 @@
     for (int i = 24; i < 31; ++i) v[i] = sel(pb[39 - i], pb[31 - i]);
     v[31] = sel(pb[8], pb[0]);
   }
-#endif
   wave_lds_sync();  // K tile consumed: the slice is reused by the inverse transform
   OP_STAMP(10);  // mask + merge
-#if OP_TK_LATE
-  if constexpr (PERSIST) {
-    // the next ticket, from thread 0 to the other waves through a polled LDS word (no barrier between here and the prefetch)
-    if (tid == 0) *(volatile unsigned*)&s_misc[tk_slot ^ 1u] = nx_raw - OP_MARG(unsigned, ticket_base);
-  }
-#endif
 
   // ---- inverse transform, synthesis window, wave-private overlap-add (k_apply_fast<LEAN>) -------------
   {
@@ -1040,13 +853,7 @@
   auto prefetch_next = [&]() {
     // ---- the NEXT tile's samples: loads issued here, consumed at the loop top (see PERSIST above) ----
     const OnePassArgs& Pn = *late_args<OnePassArgs>();
-#if OP_TK_LATE
-    unsigned nx_v;
-    while ((nx_v = *(volatile unsigned*)&s_misc[tk_slot ^ 1u]) == 0xffffffffu) __builtin_amdgcn_s_sleep(1);
-    const unsigned nx = (unsigned)__builtin_amdgcn_readfirstlane((int)nx_v);
-#else
     const unsigned nx = (unsigned)__builtin_amdgcn_readfirstlane((int)s_misc[tk_slot ^ 1u]);
-#endif
     pf = true;
     // (every path DEFINES q / sc: a conditional assignment would keep the previous tile's values alive -- 24 registers --
     // through a whole iteration)
@@ -1056,17 +863,11 @@
     const bool n_live = nx < Pn.total_tiles;
     const unsigned n_tk = n_live ? nx : 0u;
     TileSrc N;
-    if constexpr ((OP_PLAN_SITES & 4) != 0) {
+    {
       // the launch plan: an interior unit's tile is base + strides and two range compares, nothing of the view is read
       const OpTile nl = op_plan_tile(Pn.plan, n_tk);
       if (op_plan_blk_vec(Pn.plan, nl)) N = tile_src_plan(Pn.plan, nl);
       else N = tile_src(Pn, (int64_t)nl.row, Pn.plan.c0 + nl.k, nl.jt, true);
-    } else {
-      const unsigned n_ntt = (unsigned)(Pn.A.n_tiles + 2);
-      const unsigned n_u = n_tk / n_ntt;
-      const int n_jt = (int)(n_tk % n_ntt) - 1;
-      const unsigned n_gu = (unsigned)(Pn.A.view.unit0 + n_u), n_nch = (unsigned)Pn.A.view.n_chunks;
-      N = tile_src(Pn, (int64_t)(n_gu / n_nch), Pn.A.view.c0 + n_gu % n_nch, n_jt, true);
     }
     // NO BRANCH around the loads: at the join with a path that issued none the compiler has to assume the least number of loads
     // behind n4, and the epilogue's wait for n4 is vmcnt(0) again -- for the whole span.  A next tile that stages sample by
@@ -1082,17 +883,8 @@
 #pragma unroll
     for (int k = 0; k < SCAN_REG; ++k) sc[k] = n_sc[min(tid + k * WAVES * 64, n_sc1)];
   };
-#ifndef OP_PF_AT
-#define OP_PF_AT 2   // where the prefetch is issued: 0 before the overlap-add, 1 / 2 / 3 after that many quarters of it, 4 after it, 5 at the end of the epilogue
-#endif
-#ifndef OP_TK_LATE
-#define OP_TK_LATE 0  // 1: the next ticket reaches the other waves through a polled LDS word after the mask stage, not under the smoothing stage's barrier
-#endif
-#ifndef OP_SEAM_AT
-#define OP_SEAM_AT 4   // where the open seam's loads are issued: after that many quarters of the overlap-add (4: behind it)
-#endif
   // DEFERRED SEAM: the open seam's granules (the tile before it published them a whole tile ago) are loaded during the
-  // overlap-add (after OP_SEAM_AT quarters of it) and used at the end of the epilogue
+  // overlap-add (behind all four quarters of it) and used at the end of the epilogue
   [[maybe_unused]] unsigned sm_pend = OP_SEAM_NONE;
   [[maybe_unused]] unsigned long long sm_g0 = 0ull, sm_g1 = 0ull, sm_g2 = 0ull, sm_g3 = 0ull;
   [[maybe_unused]] float* sm_dst = nullptr;
@@ -1110,7 +902,6 @@
       sm_lead = op_ldg4(sm_dst + seam_off(wave, (tid & 63) * 4));
     }
   };
-  if constexpr (PERSIST && OP_PF_AT == 0) prefetch_next();
   float* acc = reinterpret_cast<float*>(regions + wave * WAVE_CX_H);
   {
     const float2* wsrc2 = reinterpret_cast<const float2*>(swin + 2 * c);
@@ -1131,8 +922,9 @@
         *dst = nw;
       }
       wave_lds_sync();
-      if constexpr (PERSIST) { if (j + 1 == OP_PF_AT) prefetch_next(); }
-      if constexpr (DEFER) { if (j + 1 == OP_SEAM_AT) seam_issue(); }
+      // the prefetch after two quarters of the overlap-add, the open seam's loads behind all four (profiles/onepass_chain.txt)
+      if constexpr (PERSIST) { if (j + 1 == 2) prefetch_next(); }
+      if constexpr (DEFER) { if (j + 1 == 4) seam_issue(); }
     }
   }
   if constexpr (!PERSIST) load_n4();
@@ -1149,31 +941,21 @@
   // of the vector pipe, the kernel's binding resource: profiles/r05_valu_classes.txt).  Here they are read again from the
   // kernel-argument segment through an OPAQUE pointer (scalar loads, off the vector pipe; not mergeable with the entry
   // block's loads), and the tile's coordinates are recomputed from the ticket, which is still in LDS.
-#if OP_LATE_ARGS
-  typedef const __attribute__((address_space(4))) char* op_kp_t;
-  op_kp_t kp4 = (op_kp_t)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(kp4));
-#define OP_KARG(type, member) (*(const __attribute__((address_space(4))) type*)(kp4 + __builtin_offsetof(OnePassArgs, member)))
-#define OP_KPTR(type, member) ((type)(uintptr_t)OP_KARG(unsigned long long, member))
-#else
-#define OP_KARG(type, member) (P.member)
-#define OP_KPTR(type, member) ((type)P.member)
-#endif
-  const int64_t e_gstep = OP_KARG(int64_t, A.om.g_step), e_p0 = OP_KARG(int64_t, A.om.p0), e_p1 = OP_KARG(int64_t, A.om.p1);
-  void* const e_out = OP_KPTR(void*, A.om.out);
-  const int64_t e_ostride = OP_KARG(int64_t, A.om.stride), e_g0 = OP_KARG(int64_t, A.om.g0), e_glo = OP_KARG(int64_t, A.om.g_lo),
-                e_ghi = OP_KARG(int64_t, A.om.g_hi);
-  const int e_odtype = OP_KARG(int, A.om.dtype), e_normalize = OP_KARG(int, A.normalize), e_ntiles = OP_KARG(int, A.n_tiles);
-  const int64_t e_hbegin = OP_KARG(int64_t, A.h_begin), e_hend = OP_KARG(int64_t, A.h_end);
-  unsigned long long* const e_part2 = OP_KPTR(unsigned long long*, part2);
-  const unsigned e_epoch = OP_KARG(unsigned, epoch);
-  unsigned* const e_err = OP_KPTR(unsigned*, err);
-  const char* const e_tab = OP_KPTR(const char*, tab);
-  const int e_padL = OP_KARG(int32_t, A.g.padL);
-  const int64_t e_T = OP_KARG(int64_t, A.g.T), e_Lout = OP_KARG(int64_t, A.g.Lout);
-#if OP_LATE_ARGS
+  const op_late_t kp4 = op_late_ptr();
+  const int64_t e_gstep = OP_LATE(kp4, int64_t, A.om.g_step), e_p0 = OP_LATE(kp4, int64_t, A.om.p0), e_p1 = OP_LATE(kp4, int64_t, A.om.p1);
+  void* const e_out = OP_LATE_PTR(kp4, void*, A.om.out);
+  const int64_t e_ostride = OP_LATE(kp4, int64_t, A.om.stride), e_g0 = OP_LATE(kp4, int64_t, A.om.g0), e_glo = OP_LATE(kp4, int64_t, A.om.g_lo),
+                e_ghi = OP_LATE(kp4, int64_t, A.om.g_hi);
+  const int e_odtype = OP_LATE(kp4, int, A.om.dtype), e_normalize = OP_LATE(kp4, int, A.normalize), e_ntiles = OP_LATE(kp4, int, A.n_tiles);
+  const int64_t e_hbegin = OP_LATE(kp4, int64_t, A.h_begin), e_hend = OP_LATE(kp4, int64_t, A.h_end);
+  unsigned long long* const e_part2 = OP_LATE_PTR(kp4, unsigned long long*, part2);
+  const unsigned e_epoch = OP_LATE(kp4, unsigned, epoch);
+  unsigned* const e_err = OP_LATE_PTR(kp4, unsigned*, err);
+  const char* const e_tab = OP_LATE_PTR(kp4, const char*, tab);
+  const int e_padL = OP_LATE(kp4, int32_t, A.g.padL);
+  const int64_t e_T = OP_LATE(kp4, int64_t, A.g.T), e_Lout = OP_LATE(kp4, int64_t, A.g.Lout);
   const unsigned e_ticket = (unsigned)__builtin_amdgcn_readfirstlane((int)s_misc[tk_slot]);
-  constexpr bool PLAN16 = PERSIST && (OP_PLAN_SITES & 16) != 0;
+  constexpr bool PLAN16 = PERSIST;   // the epilogue takes its coordinates from the launch plan
   [[maybe_unused]] const OpPlan& e_plan = *reinterpret_cast<const OpPlan*>((const char*)kp4 + __builtin_offsetof(OnePassArgs, plan));
   [[maybe_unused]] OpTile el{};
   int64_t e_u, e_row, e_chunk;
@@ -1188,19 +970,11 @@
     const unsigned e_ntt = (unsigned)(e_ntiles + 2);
     e_u = e_ticket / e_ntt;
     e_jt = (int)(e_ticket % e_ntt) - 1;
-    const unsigned e_gu = (unsigned)(OP_KARG(int64_t, A.view.unit0) + e_u), e_nch = (unsigned)OP_KARG(int32_t, A.view.n_chunks);
+    const unsigned e_gu = (unsigned)(OP_LATE(kp4, int64_t, A.view.unit0) + e_u), e_nch = (unsigned)OP_LATE(kp4, int32_t, A.view.n_chunks);
     e_row = e_gu / e_nch;
-    e_chunk = OP_KARG(int64_t, A.view.c0) + e_gu % e_nch;
+    e_chunk = OP_LATE(kp4, int64_t, A.view.c0) + e_gu % e_nch;
   }
   const int64_t e_tf = e_hbegin - 3 + (int64_t)e_jt * NF;
-#else
-  constexpr bool PLAN16 = false;
-  [[maybe_unused]] const OpPlan& e_plan = P.plan;
-  [[maybe_unused]] const OpTile el{};
-  const int64_t e_u = u, e_row = row, e_chunk = chunk, e_tf = tf_tile;
-  const int e_jt = jt;
-  [[maybe_unused]] const unsigned e_ticket = ticket;
-#endif
   const float* fr = reinterpret_cast<const float*>(regions);
   const int s4 = (tid & 63) * 4;
   // A lost hand-off must not look like audio: a tile whose neighbour bits never arrived writes NaN to every hop it
@@ -1247,7 +1021,6 @@
 #pragma unroll
         for (int it = 0; it < 4; ++it) fin(ld4(it * R + 3 * HPITCH), 3 + 4 * it);
         OP_STAMP(13);
-        if constexpr (PERSIST && OP_PF_AT == 5) prefetch_next();
         OP_DONE;
       }
       {
@@ -1281,13 +1054,10 @@
           if ((OP_ABLATE & 16) || (!LOSE && ga[1] == e && ga[3] == e && gb[1] == e && gb[3] == e)) break;
           if (LOSE || spin >= OP_SPIN_MAX) {
             op_err_or(e_err, 2u);
-#if OP_WHO
-            if (atomicAdd_system(e_err + 15, 1u) == 0u) { e_err[12] = e_ticket; e_err[13] = ga[1]; }
-#endif
             ga[0] = ga[2] = gb[0] = gb[2] = op_nan_bits();   // the previous tile's share is unknown: NaN, not a partial sum
             break;
           }
-          OP_POLL_SLEEP(spin);
+          op_poll_sleep();
         }
         a4.x = __uint_as_float(ga[0]) + a4.x;
         a4.y = __uint_as_float(ga[2]) + a4.y;
@@ -1296,7 +1066,6 @@
         fin(a4, wave);
       }
       OP_STAMP(13);  // cross-wave combine, hand-off of the straddling hops, stores
-      if constexpr (PERSIST && OP_PF_AT == 5) prefetch_next();
       OP_DONE;
     }
   }
@@ -1351,7 +1120,7 @@
           ga[0] = ga[2] = gb[0] = gb[2] = op_nan_bits();
           break;
         }
-        OP_POLL_SLEEP(spin);
+        op_poll_sleep();
       }
       // trailing partial of the previous tile + leading partial of this one (the order k_ola_seam adds them in)
       a4.x = __uint_as_float(ga[0]) + a4.x;
@@ -1400,5 +1169,4 @@
       store_sample(e_out, e_odtype, e_row * e_ostride + gi - e_g0, p < e_Lout ? vals[e] : 0.f);
     }
   }
-  if constexpr (PERSIST && OP_PF_AT == 5) prefetch_next();
   }   // tile loop (one iteration unless PERSIST)
