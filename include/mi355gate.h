@@ -366,7 +366,26 @@ SG_API int sg_stream_state_bytes_adaptive(const sg_handle* h, int32_t n_slots, i
  * SG_STREAM_ADAPTIVE: forget and learn_frames are read; fields a kind does not read are ignored).  With exact == 0 the
  * bank is the one the matching create call makes.  sg_stream_state_bytes_ex: the device memory such a bank would hold --
  * an exact non-stationary bank keeps its mask rows at 8 bytes, nothing else differs (host arithmetic; SG_E_INVALID when
- * kind does not fit the handle). */
+ * kind does not fit the handle).
+ * A handle of variant T (TorchGate) streams too, its NON-STATIONARY gate alone: sg_stream_create_ex makes, and
+ * sg_stream_state_bytes_ex sizes, a bank of kind SG_STREAM_NONSTATIONARY whose level is TorchGate's moving mean instead of
+ * the one-pole smoother.  With K = the handle's n_movemean (1 .. SG_STREAM_MAX_LOOKAHEAD), lo = (K - 1) / 2 and
+ * L = K - 1 - lo:  S[f, t] = (1 / K) sum of A[f, q] over q in [t - lo, t - lo + K) cut to [0, last frame of the stream],
+ * every sum taken afresh in ascending q in float64, A = |X| unscaled;  raw = sigmoid(((A - S) / S - nonstat_thresh) *
+ * nonstat_slope);  the mask is prop_decrease * (raw - 1) + 1 smoothed with the zero-padded triangle over the stream's own
+ * field (prop_decrease first: TorchGate's order).  That mean reads nothing beyond frame t + L, so with a lookahead of L
+ * frames the stream EQUALS the offline gate of the whole signal: E(n) and the delay are the non-stationary bank's with
+ * this L, and desc->lookahead_frames must be 0 (n_movemean decides it; SG_E_INVALID otherwise).  Frame t is the frame of
+ * samples [t hop - win_length / 2, .. + win_length) -- the samples torch.stft(center = 1) windows; win_length must be even
+ * -- and a flushed stream of N samples has emitted N samples: hop * (N / hop) of them are sg_process_batch's, the rest the
+ * same overlap-add over the window envelope continued.  exact != 0 works as for the non-stationary bank.  It stays
+ * SG_E_INVALID, with a message that says so, for a stationary variant-T handle (its statistics need xn or the whole
+ * recording), for any other kind on a variant-T handle and for an odd win_length.  On such a bank sg_stream_export_bytes,
+ * sg_stream_export and sg_stream_import (a header of kind 1 could not tell the two non-stationary gates apart; the header
+ * format does not change) and sg_stream_push_spectrum (it would have to take torch.stft's phase and scale) return
+ * SG_E_INVALID and leave the bank untouched; sg_stream_push_features with scale = 1 gives sg_gate_features' features.
+ * sg_stream_create, sg_stream_create_nonstationary and sg_stream_create_adaptive answer a variant-T handle as before
+ * ("... is a variant-S entry point"). */
 #define SG_STREAM_FIXED 0
 #define SG_STREAM_NONSTATIONARY 1
 #define SG_STREAM_ADAPTIVE 2

@@ -122,13 +122,39 @@ struct sg_stream_bank {
 };
 
 // the one create call behind the four entry points; `who` names the caller in the variant message
-static int stream_create(sg_handle* h, const sg_stream_desc& d, const char* who, sg_stream_bank** out) {
-  if (h->p.variant != SG_VARIANT_S) FAIL(h, SG_E_INVALID, "%s is a variant-S entry point", who);
+// A handle of variant T streams its non-stationary gate alone (a box bank): kind
+// SG_STREAM_NONSTATIONARY, the moving mean's n_movemean frames deciding the lookahead.  0: the handle is of variant S.
+static int stream_box_check(sg_handle* h, const sg_stream_desc& d, const char* who) {
+  if (h->p.stationary)
+    FAIL(h, SG_E_INVALID, "%s: a variant-T handle streams its non-stationary gate only (this one is stationary: its noise "
+         "statistics need the whole recording or xn)", who);
+  if (d.kind != SG_STREAM_NONSTATIONARY)
+    FAIL(h, SG_E_INVALID, "%s: a variant-T handle takes kind SG_STREAM_NONSTATIONARY only (got kind %d)", who, d.kind);
+  if (h->W & 1)
+    FAIL(h, SG_E_INVALID, "%s: a variant-T handle streams with an even win_length only (got %d: the stream's frames would "
+         "not be the samples torch.stft windows)", who, h->W);
+  if (h->p.n_movemean < 1 || h->p.n_movemean > SG_STREAM_MAX_LOOKAHEAD)
+    FAIL(h, SG_E_INVALID, "%s: n_movemean must be 1 .. %d on a variant-T handle (got %d)", who, SG_STREAM_MAX_LOOKAHEAD,
+         h->p.n_movemean);
+  if (d.lookahead_frames != 0)
+    FAIL(h, SG_E_INVALID, "%s: lookahead_frames must be 0 on a variant-T handle (n_movemean = %d decides it: %d frames)", who,
+         h->p.n_movemean, h->p.n_movemean - 1 - (h->p.n_movemean - 1) / 2);
+  return SG_OK;
+}
+
+// (a variant-T handle makes its box bank through sg_stream_create_ex alone: the three older entry points answer it as before)
+static int stream_create(sg_handle* h, const sg_stream_desc& d, const char* who, sg_stream_bank** out, bool ex = false) {
+  const bool box = h->p.variant != SG_VARIANT_S;
+  if (box && !ex) FAIL(h, SG_E_INVALID, "%s is a variant-S entry point", who);
+  if (box) {
+    int rc = stream_box_check(h, d, who);
+    if (rc) return rc;
+  }
   sg::StBank* b = nullptr;
   const sg::StAdaptive ad{d.forget, d.learn_frames};
   const bool ns = d.kind == SG_STREAM_NONSTATIONARY;
   int rc = sg::st_create(&b, rg_ctx(h), d.n_slots, d.channels, d.max_block, ns, ns ? d.lookahead_frames : 0,
-                         d.kind == SG_STREAM_ADAPTIVE ? &ad : nullptr, d.exact != 0, &h->err);
+                         d.kind == SG_STREAM_ADAPTIVE ? &ad : nullptr, d.exact != 0, &h->err, box ? h->p.n_movemean : 0);
   if (rc) return rc;
   *out = new sg_stream_bank{h, b};
   return SG_OK;
@@ -136,8 +162,8 @@ static int stream_create(sg_handle* h, const sg_stream_desc& d, const char* who,
 
 // the one size call behind the three entry points
 static int64_t stream_state_bytes(const sg_handle* h, bool ns, int64_t n_slots, int64_t channels, int64_t max_block, int64_t L,
-                                  bool adaptive, bool exact) {
-  return sg::st_state_bytes(rg_ctx(const_cast<sg_handle*>(h)), ns, n_slots, channels, max_block, L, adaptive, exact);
+                                  bool adaptive, bool exact, int32_t box_k = 0) {
+  return sg::st_state_bytes(rg_ctx(const_cast<sg_handle*>(h)), ns, n_slots, channels, max_block, L, adaptive, exact, box_k);
 }
 
 extern "C" int sg_stream_create_ex(sg_handle* h, const sg_stream_desc* desc, sg_stream_bank** out) {
@@ -145,12 +171,17 @@ extern "C" int sg_stream_create_ex(sg_handle* h, const sg_stream_desc* desc, sg_
   if (!desc) FAIL(h, SG_E_INVALID, "sg_stream_create_ex: desc is null");
   if (desc->kind != SG_STREAM_FIXED && desc->kind != SG_STREAM_NONSTATIONARY && desc->kind != SG_STREAM_ADAPTIVE)
     FAIL(h, SG_E_INVALID, "sg_stream_create_ex: unknown kind %d", desc->kind);
-  return stream_create(h, *desc, "sg_stream_create_ex", out);
+  return stream_create(h, *desc, "sg_stream_create_ex", out, true);
 }
 
 extern "C" int sg_stream_state_bytes_ex(const sg_handle* h, const sg_stream_desc* d, int64_t* bytes) {
   if (!h || !d || !bytes || d->n_slots < 1 || d->channels < 1 || d->max_block < 1) return SG_E_INVALID;
   const bool ns = d->kind == SG_STREAM_NONSTATIONARY, ad = d->kind == SG_STREAM_ADAPTIVE;
+  if (h->p.variant != SG_VARIANT_S) {   // (the box bank: the one a variant-T handle creates)
+    if (int rc = stream_box_check(const_cast<sg_handle*>(h), *d, "sg_stream_state_bytes_ex")) return rc;
+    *bytes = stream_state_bytes(h, true, d->n_slots, d->channels, d->max_block, 0, false, d->exact != 0, h->p.n_movemean);
+    return SG_OK;
+  }
   if ((!ns && !ad && d->kind != SG_STREAM_FIXED) || (ns && d->lookahead_frames < 0) || ns == (h->p.stationary != 0))
     return SG_E_INVALID;
   *bytes = stream_state_bytes(h, ns, d->n_slots, d->channels, d->max_block, ns ? d->lookahead_frames : 0, ad, d->exact != 0);

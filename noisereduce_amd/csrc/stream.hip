@@ -12,6 +12,10 @@
 // float64 transform, A = |X|, the forward one-pole pass carried per band, the A / fwd rows of the last L + 1 frames kept,
 // and for every frame that has L frames after it (or the stream's end, at a flush) the backward pass over those L + 1
 // rows and the sigmoid into a ring of float mask rows, which k_st_fsmooth<true> / k_st_apply<N, true> read instead of bits.
+// A box bank (a handle of variant T) is a non-stationary bank with k_sb_decide in the first place: the
+// level of a frame is TorchGate's moving mean over the K rows of A around it (no forward pass, no fwd rows), the sigmoid rows
+// go to the same mk ring, k_st_fsmooth<true> is unchanged and k_st_apply / k_st_feat take their BX form, TorchGate's mask
+// formula on those rows.
 // An adaptive bank (sg_stream_create_adaptive) is a stationary bank without a noise profile: k_sa_decide takes the first
 // place and learns the threshold of every band from the stream itself, a running weighted mean and deviation of the
 // floored dB values carried per band (nst), evaluated frame by frame before the compare.  The other three launches are the
@@ -84,7 +88,7 @@ struct StArgs {
   int RC, RB;
   // non-stationary banks
   double* fst;     // [unit][FS] forward state fwd[f, td]
-  double* fa;      // [unit][RF][2][FS] A and fwd rows of the last transformed frames, frame t at t % RF
+  double* fa;      // [unit][RF][2][FS] A and fwd rows of the last transformed frames, frame t at t % RF (box bank: [unit][RF][FS], A alone)
   void* mk;        // [unit][RB][FS] raw (sigmoid) mask rows, frame t at t % RB: float, double in an exact bank
   int RF, L;
   // adaptive banks
@@ -97,6 +101,8 @@ struct StArgs {
   void* smask;       // final mask rows in the real type of spec_dtype, or null
   const StSpec* sp;  // [unit]
   int spec_dtype;
+  // box banks (k_sb_decide alone reads these): frames of the moving mean, and how many of them lie behind the decided one
+  int K, Lb;
 };
 
 // sample s of the stream: zeros before 0 and from n1 on, the ring below n0, the caller's block from n0 on
@@ -332,6 +338,66 @@ __global__ __launch_bounds__(tile_nt<N>()) void k_sn_decide(StArgs A) {
   }
 }
 
+// ---- box decide: TorchGate's non-stationary gate, the level a moving mean over K frames --------------------------------
+// The first loop is k_sn_decide's without the forward pass: a row of the fa ring is the FS magnitudes A = |X| of one frame
+// (no fwd half, no fst).  The level of frame t is rows.hip's k_rw_box on the ring: S = (1 / K) sum of A[q], q ascending over
+// [t - Lb, t - Lb + K) cut to [0, last frame], every window summed afresh in float64 -- frames outside the stream count as
+// 0, the divisor stays K (conv1d(|X|, ones(K) / K, padding="same")).  A push decides t once t + L = t - Lb + K - 1 is in, so
+// only a flush cuts the window at its upper end (U.td1 is the stream's last frame then).  The ring keeps rows (ts - Lb, td]
+// (stream_plan.hpp's RF): frame ts0 + 1 still finds its Lb rows behind it, whatever the block split.  Band k belongs to one
+// thread for the whole launch, as in k_sn_decide: no barrier between the loops.
+template <int N, bool EX>
+__global__ __launch_bounds__(tile_nt<N>()) void k_sb_decide(StArgs A) {
+  using MT = typename std::conditional<EX, double, float>::type;
+  constexpr int NT = tile_nt<N>(), SY = tile_sy<N>();
+  if ((int64_t)blockIdx.x >= A.n_dec) return;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  cx<double>* tw = reinterpret_cast<cx<double>*>(smem);
+  cx<double>* buf = tw + N;
+  const int lane = threadIdx.x;
+  const Tile tl = A.tiles[A.t_dec + blockIdx.x];
+  const StUnit U = A.units[tl.idx];
+  stage_tile_twiddles<N>(tw, A.c.tw);
+  constexpr int M = tile_bins<N>();
+  const int FS = A.c.FS;
+  const float nthresh = (float)A.c.nthresh, slope = (float)A.c.slope;
+  double* fa = A.fa + (int64_t)U.state * A.RF * FS;
+  for (int64_t t = U.td0 + 1; t <= U.td1; ++t) {
+    st_frame_fft<N>(A, U, t, buf, tw, lane);
+    double* row = fa + (t % A.RF) * FS;
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+      const int k = lane + NT * m;
+      if (k <= N) row[k] = sqrt(bin_power<N>(buf, tw, k));
+    }
+    team_sync<SY>();
+  }
+  const double kbox = (double)A.K;
+  for (int64_t t = U.ts0 + 1; t <= U.ts1; ++t) {
+    const int64_t ja = t - A.Lb < 0 ? 0 : t - A.Lb;
+    const int64_t jb = t - A.Lb + A.K > U.td1 + 1 ? U.td1 + 1 : t - A.Lb + A.K;
+    const int r0 = (int)(ja % A.RF), nq = (int)(jb - ja);
+    const double* arow = fa + (t % A.RF) * FS;
+    MT* mrow = (MT*)A.mk + ((int64_t)U.state * A.RB + t % A.RB) * FS;
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+      const int k = lane + NT * m;
+      if (k <= N) {
+        double s = 0.0;
+        int r = r0;
+        for (int q = 0; q < nq; ++q) {
+          s += fa[(int64_t)r * FS + k];
+          if (++r == A.RF) r = 0;
+        }
+        s = s / kbox;
+        const double a = arow[k];
+        if constexpr (EX) mrow[k] = 1.0 / (1.0 + exp(-((a - s) / s - A.c.nthresh) * A.c.slope));
+        else mrow[k] = sigmoid_ratio(a, s, nthresh, slope);
+      }
+    }
+  }
+}
+
 // ---- mask smoothing along frequency (fsmooth_row) -------------------------------------------------------------------
 // NS: the raw mask is a row of floats (the sigmoid) instead of a row of final bits; EX (with NS): a row of doubles,
 // summed in double in the same ascending df order
@@ -356,7 +422,52 @@ __global__ __launch_bounds__(256) void k_st_fsmooth(StArgs A) {
 // the store applies it), rounded once to spec's type; the mask value is the float64 one of that product.  Bins 0 and
 // n_fft / 2 carry an imaginary part of +0.0.  A lane's bins are lane + NT i and N - (lane + NT i): consecutive lanes
 // store consecutive float2 / double2 of the row in both halves.
-template <int N, bool NS, bool EX, bool SP = false>
+// BX (with NS): a box bank.  Its rows are sigmoid rows as any non-stationary bank's, its mask is TorchGate's:
+// mask_stationary's formula on them, prop_decrease first, then the zero-padded smoothing.
+// A box bank's mask, split, product and merge are evaluated WITHOUT contraction (mask_box, mask_and_invert_pinned: the
+// arithmetic of tile_core.hpp's mask_stationary and mask_and_invert, one rounding per operation as written).  Under
+// contraction the compiler fuses a product into a following addition when the product has no other use: Y = X * mask has one
+// use in k_st_apply and two in k_st_feat (the merge and the feature callback), and a * b + c * d leaves it the choice of the
+// product.  An exact bank keeps its segments in float64, so its push and push_features audio then differed in the last bit
+// (4.4e-16 of peak on 3626 of 6733 samples, measured), which the contract of a stream forbids.  tile_core.hpp's own
+// functions stay as they are: every existing kernel keeps its bits.
+__device__ __forceinline__ double mask_box(const TileConsts& C, double K, double Et, int k) {
+#pragma clang fp contract(off)
+  return (C.prop * K + (1.0 - C.prop) * Et * (double)tri_valid(C.nf, k, C.F)) / C.ktot;
+}
+template <int N, class ST, class MaskAt, class Emit = NoEmit>
+__device__ __forceinline__ void mask_and_invert_pinned(cx<double>* buf, const cx<double>* tw, int lane, MaskAt&& mask_at,
+                                                       const double* wfull, ST* seg_row, Emit&& emit = Emit()) {
+#pragma clang fp contract(off)
+  constexpr int NT = tile_nt<N>();
+  for (int k = lane; k <= N / 2; k += NT) {
+    if (k == 0) {
+      const cx<double> a = buf[lp<double>(0)];
+      const double m0 = mask_at(0), mN = mask_at(N);
+      const double y0 = (a.x + a.y) * m0, yN = (a.x - a.y) * mN;
+      emit(0, cx<double>{y0, 0.0}, m0);
+      emit(N, cx<double>{yN, 0.0}, mN);
+      buf[lp<double>(0)] = {0.5 * (y0 + yN), 0.5 * (y0 - yN)};
+    } else {
+      const cx<double> a = buf[lp<double>(k)], b = buf[lp<double>(N - k)], w = tw[k];
+      const cx<double> E = {(a.x + b.x) * 0.5, (a.y - b.y) * 0.5};
+      const cx<double> O = {(a.y + b.y) * 0.5, (b.x - a.x) * 0.5};
+      const cx<double> wO = {w.x * O.x - w.y * O.y, w.x * O.y + w.y * O.x};
+      const double mk = mask_at(k), mn = (k != N - k) ? mask_at(N - k) : mk;
+      const cx<double> Yk = {(E.x + wO.x) * mk, (E.y + wO.y) * mk};
+      const cx<double> Yn = {(E.x - wO.x) * mn, (-E.y + wO.y) * mn};
+      emit(k, Yk, mk);
+      if (k != N - k) emit(N - k, Yn, mn);
+      const cx<double> Ep = {(Yk.x + Yn.x) * 0.5, (Yk.y - Yn.y) * 0.5};
+      const cx<double> D = {(Yk.x - Yn.x) * 0.5, (Yk.y + Yn.y) * 0.5};
+      const cx<double> Op = {D.x * w.x + D.y * w.y, D.y * w.x - D.x * w.y};   // D * conj(w)
+      buf[lp<double>(k)] = {Ep.x - Op.y, Ep.y + Op.x};
+      if (k != N - k) buf[lp<double>(N - k)] = {Ep.x + Op.y, -Ep.y + Op.x};
+    }
+  }
+  invert_and_window<N, ST>(buf, tw, lane, wfull, 1.0 / (double)N, seg_row);
+}
+template <int N, bool NS, bool EX, bool SP = false, bool BX = false>
 __global__ __launch_bounds__(tile_nt<N>()) void k_st_apply(StArgs A) {
   using ST = typename std::conditional<EX, double, float>::type;
   using RT = typename std::conditional<EX && NS, double, float>::type;
@@ -373,6 +484,7 @@ __global__ __launch_bounds__(tile_nt<N>()) void k_st_apply(StArgs A) {
     const TimeTaps tp = time_taps(t, A.c.nt, U.Tend);
     auto mask_at = [&](int k) -> double {
       const double K = time_smooth((const RT*)A.R, A.c.FS, [&](int64_t q) { return U.mrow + q - U.r0; }, tp, t, A.c.nt, k);
+      if constexpr (BX) return mask_box(A.c, K, tp.Et, k);
       return NS ? mask_nonstationary(A.c, K) : mask_stationary(A.c, K, tp.Et, k);
     };
     ST* seg_row = (ST*)A.seg + (U.srow + t - (U.ta0 + 1)) * (int64_t)A.c.n;
@@ -389,6 +501,8 @@ __global__ __launch_bounds__(tile_nt<N>()) void k_st_apply(StArgs A) {
           else reinterpret_cast<float*>(A.smask)[S.mask_off + row + k] = (float)m;
         }
       });
+    } else if constexpr (BX) {
+      mask_and_invert_pinned<N>(buf, tw, lane, mask_at, A.c.wfull, seg_row);
     } else {
       mask_and_invert<N>(buf, tw, lane, mask_at, A.c.wfull, seg_row);
     }
@@ -404,7 +518,7 @@ __global__ __launch_bounds__(tile_nt<N>()) void k_st_apply(StArgs A) {
 // consecutive lanes consecutive filters, rounded once to the output type.  A second team_sync keeps the next frame's
 // powers off the row until every lane has read it.  Power, log and the output type are run-time switches (uniform
 // branches).  LDS: launch_tile_kernel's + (N + 1) doubles.
-template <int N, bool NS, bool EX>
+template <int N, bool NS, bool EX, bool BX = false>
 __global__ __launch_bounds__(tile_nt<N>()) void k_st_feat(StArgs A, StFeat Q) {
   using ST = typename std::conditional<EX, double, float>::type;
   using RT = typename std::conditional<EX && NS, double, float>::type;
@@ -424,16 +538,19 @@ __global__ __launch_bounds__(tile_nt<N>()) void k_st_feat(StArgs A, StFeat Q) {
     const TimeTaps tp = time_taps(t, A.c.nt, U.Tend);
     auto mask_at = [&](int k) -> double {
       const double K = time_smooth((const RT*)A.R, A.c.FS, [&](int64_t q) { return U.mrow + q - U.r0; }, tp, t, A.c.nt, k);
+      if constexpr (BX) return mask_box(A.c, K, tp.Et, k);
       return NS ? mask_nonstationary(A.c, K) : mask_stationary(A.c, K, tp.Et, k);
     };
     ST* seg_row = (ST*)A.seg + (U.srow + t - (U.ta0 + 1)) * (int64_t)A.c.n;
     const StFeatUnit S = Q.fu[tl.idx];
     const int64_t fr = t - (U.ta0 + 1);
     const int64_t mrow = S.mask_off + fr * (int64_t)A.c.F;
-    mask_and_invert<N>(buf, tw, lane, mask_at, A.c.wfull, seg_row, [&](int k, cx<double> Y, double m) {
+    auto emit = [&](int k, cx<double> Y, double m) {
       prow[k] = feat_power(Y, Q.scale, Q.power);
       if (Q.fmask) feat_store(Q.fmask, Q.dtype, mrow + k, m);
-    });
+    };
+    if constexpr (BX) mask_and_invert_pinned<N>(buf, tw, lane, mask_at, A.c.wfull, seg_row, emit);
+    else mask_and_invert<N>(buf, tw, lane, mask_at, A.c.wfull, seg_row, emit);
     const int64_t frow = S.feat_off + fr * (int64_t)M;
     for (int m = fresh_lane(lane); m < M; m += NT) {
       const double lin = feat_filter_sum(Q.bank, A.c.F, m, [&](int k) { return prow[k]; }, prow[N]);
@@ -548,6 +665,8 @@ struct StBank {
   int ns = 0, L = 0, RF = 0;   // non-stationary bank, its lookahead in frames, depth of the A / fwd ring
   int ad = 0;                  // adaptive bank: the noise statistics are learnt from the stream (nst)
   int exact = 0;               // exact bank: float64 segments (and sigmoid rows), any sample type in and out
+  int box = 0, K = 0, Lb = 0;  // box bank (ns too): frames of the moving mean, those of them behind the decided frame
+  host::DevBuf wleft;          // box bank with win_length < n_fft: the window at the START of an n_fft frame (c.wfull64)
   double lam = 1.0;
   int64_t learn = -1;
   int64_t max_block = 0;
@@ -562,11 +681,18 @@ struct StBank {
 void st_destroy(StBank* b) { delete b; }
 
 namespace {
-StGeo st_geo(const RgCtx& c, int64_t channels, bool ns, int64_t lookahead, bool adaptive, bool exact) {
+StGeo st_geo(const RgCtx& c, int64_t channels, bool ns, int64_t lookahead, bool adaptive, bool exact, int64_t box_k = 0) {
+  if (box_k) return st_make_geo_box(c.n, c.F, c.FS, c.W, c.H, c.nt, box_k, channels, exact);
   return st_make_geo(c.n, c.F, c.FS, c.W, c.H, c.nt, lookahead, channels,
                      adaptive ? SG_STREAM_ADAPTIVE : ns ? SG_STREAM_NONSTATIONARY : SG_STREAM_FIXED, exact);
 }
-StGeo st_geo(const StBank* b) { return st_geo(b->c, b->C, b->ns != 0, b->L, b->ad != 0, b->exact != 0); }
+StGeo st_geo(const StBank* b) { return st_geo(b->c, b->C, b->ns != 0, b->L, b->ad != 0, b->exact != 0, b->box ? b->K : 0); }
+// what a box bank refuses
+int box_refuses(const StBank* b, const char* who, const char* why, std::string* err) {
+  if (!b->box) return SG_OK;
+  *err = std::string(who) + ": not on a bank of TorchGate's gate (" + why + ")";
+  return SG_E_INVALID;
+}
 
 int check_slots(const StBank* b, const int32_t* slots, int32_t n, const char* who, std::string* err) {
   if (n < 0 || (n > 0 && !slots)) { *err = std::string(who) + ": bad slot list"; return SG_E_INVALID; }
@@ -593,12 +719,16 @@ hipError_t launch_feat_kernel(void (*kernel)(StArgs, StFeat), int64_t ntiles, hi
 }  // namespace
 
 int64_t st_state_bytes(const RgCtx& c, bool ns, int64_t n_slots, int64_t channels, int64_t max_block, int64_t L, bool adaptive,
-                       bool exact) {
-  return st_layout(st_geo(c, channels, ns, L, adaptive, exact), n_slots, max_block).state_bytes();
+                       bool exact, int32_t box_k) {
+  return st_layout(st_geo(c, channels, ns, L, adaptive, exact, box_k), n_slots, max_block).state_bytes();
 }
 
 int st_create(StBank** out, const RgCtx& c, int32_t n_slots, int32_t channels, int64_t max_block, bool ns, int32_t lookahead,
-              const StAdaptive* ad, bool exact, std::string* err) {
+              const StAdaptive* ad, bool exact, std::string* err, int32_t box_k) {
+  if (box_k && (!ns || ad || c.stationary || (c.W & 1) || box_k > SG_STREAM_MAX_LOOKAHEAD)) {
+    *err = "sg_stream_create_ex: a bank of TorchGate's gate needs a non-stationary handle, an even win_length and 1 <= n_movemean <= 4096";
+    return SG_E_INVALID;
+  }
   if (ad && !c.stationary) { *err = "sg_stream_create_adaptive: the handle is not stationary"; return SG_E_INVALID; }
   if (ad && !(ad->forget > 0.0 && ad->forget <= 1.0)) {
     char m[120];
@@ -635,6 +765,15 @@ int st_create(StBank** out, const RgCtx& c, int32_t n_slots, int32_t channels, i
   b->ns = ns ? 1 : 0;
   b->L = ns ? lookahead : 0;
   b->exact = exact ? 1 : 0;
+  if (box_k) {   // the lookahead is the part of the moving mean ahead of the frame: st_make_geo_box's
+    b->box = 1;
+    b->K = box_k;
+    b->Lb = (box_k - 1) / 2;
+    b->L = box_k - 1 - b->Lb;
+    // the bank's frames are [t H - W / 2, t H - W / 2 + W) with the window at the start of the n_fft frame; the handle of
+    // variant T centres the window and extends by n_fft / 2: the same samples, another phase
+    b->c.padL = c.W / 2;
+  }
   if (ad) {
     b->ad = 1;
     b->lam = ad->forget;
@@ -668,6 +807,15 @@ int st_create(StBank** out, const RgCtx& c, int32_t n_slots, int32_t channels, i
     if (hipMalloc(&q.buf.p, (size_t)q.bytes) != hipSuccess) { q.buf.p = nullptr; ok = false; break; }
     q.buf.bytes = (size_t)q.bytes;
     if (q.zero && hipMemset(q.buf.p, 0, (size_t)q.bytes) != hipSuccess) { ok = false; break; }
+  }
+  if (ok && b->box && c.W < c.n) {
+    const size_t nb = (size_t)c.n * 8;
+    ok = hipMalloc(&b->wleft.p, nb) == hipSuccess;
+    if (ok) b->wleft.bytes = nb;
+    else b->wleft.p = nullptr;
+    ok = ok && hipMemset(b->wleft.p, 0, nb) == hipSuccess &&
+         hipMemcpy(b->wleft.p, c.wfull64 + (c.n - c.W) / 2, (size_t)c.W * 8, hipMemcpyDeviceToDevice) == hipSuccess;
+    if (ok) b->c.wfull64 = b->wleft.as<double>();
   }
   if (!ok) {
     char m[200];
@@ -806,8 +954,9 @@ int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_
   const RgCtx& c = b->c;
   const StGeo g = st_geo(b);
   const char* who = st_step_name(so, fo);
-  int rc = st_check_step(g, b->max_block, b->fb.M, b->slots, in_dtype, out_dtype, recs, n_recs, so, fo, err);
+  int rc = so ? box_refuses(b, who, "the spectrum would need torch.stft's phase and scale", err) : SG_OK;
   if (rc) return rc;
+  if ((rc = st_check_step(g, b->max_block, b->fb.M, b->slots, in_dtype, out_dtype, recs, n_recs, so, fo, err))) return rc;
   const StStep P = st_plan_step(g, b->slots, recs, n_recs, so, fo);
   // ---- tables and scratch
   const size_t ub = align256(P.units.size() * sizeof(StUnit)), tb = align256(P.tl.tiles.size() * sizeof(Tile));
@@ -838,6 +987,7 @@ int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_
   A.RC = b->RC; A.RB = b->RB;
   A.fst = b->fst.as<double>(); A.fa = b->fa.as<double>(); A.mk = b->mk.p; A.RF = b->RF; A.L = b->L;
   A.nst = b->nst.as<double>(); A.lam = b->lam; A.learn = b->learn;
+  A.K = b->K; A.Lb = b->Lb;
   A.c = fill_consts(c);
   if (so) {
     A.spec = so->spec; A.smask = so->mask; A.spec_dtype = so->dtype;
@@ -859,6 +1009,7 @@ int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_
     e = dispatch_N(c.N, [&](auto n) {
       constexpr int N = decltype(n)::value;
       if (b->ad) return launch_tile_kernel<N>(k_sa_decide<N>, A.n_dec, st, A);
+      if (b->box) return dispatch_flag(ex, [&](auto EX) { return launch_tile_kernel<N>(k_sb_decide<N, decltype(EX)::value>, A.n_dec, st, A); });
       if (ns) return dispatch_flag(ex, [&](auto EX) { return launch_tile_kernel<N>(k_sn_decide<N, decltype(EX)::value>, A.n_dec, st, A); });
       return launch_tile_kernel<N>(k_st_decide<N>, A.n_dec, st, A);
     });
@@ -872,6 +1023,10 @@ int st_push(StBank* b, const void* in_dev, int in_dtype, void* out_dev, int out_
     Prof pr(c, SG_STAGE_RG_APPLY, st);
     e = dispatch_N(c.N, [&](auto n) {
       constexpr int N = decltype(n)::value;
+      if (b->box) return dispatch_flag(ex, [&](auto EX) {   // (no spectrum step on a box bank: refused above)
+        if (fo) return launch_feat_kernel<N>(k_st_feat<N, true, decltype(EX)::value, true>, A.n_ap, st, A, Q);
+        return launch_tile_kernel<N>(k_st_apply<N, true, decltype(EX)::value, false, true>, A.n_ap, st, A);
+      });
       if (fo) return dispatch_flags(ex, ns, [&](auto EX, auto NS) {
         return launch_feat_kernel<N>(k_st_feat<N, decltype(NS)::value, decltype(EX)::value>, A.n_ap, st, A, Q);
       });
@@ -1019,6 +1174,8 @@ int st_head_bytes(const sg_stream_head& hd, int64_t* bytes) {
 }
 
 int st_export_bytes(const StBank* b, int32_t slot, int64_t* bytes, std::string* err) {
+  const char* no_head = "a kind-1 header cannot tell the two non-stationary gates apart";
+  if (int rc = box_refuses(b, "sg_stream_export_bytes", no_head, err)) return rc;
   if (slot < 0 || slot >= b->n_slots) { *err = "sg_stream_export_bytes: unknown slot"; return SG_E_INVALID; }
   *bytes = 8 * st_payload_words(b, b->slots[slot].n);
   return SG_OK;
@@ -1027,7 +1184,9 @@ int st_export_bytes(const StBank* b, int32_t slot, int64_t* bytes, std::string* 
 int st_export(StBank* b, const int32_t* slots, int32_t n, void* blob_dev, const int64_t* offsets, const sg_stream_head& sig,
               sg_stream_head* heads, hipStream_t st, std::string* err) {
   const char* who = "sg_stream_export";
-  int rc = st_check_transfer(b, slots, n, blob_dev, offsets, heads, who, err);
+  int rc = box_refuses(b, who, "a kind-1 header cannot tell the two non-stationary gates apart", err);
+  if (rc) return rc;
+  rc = st_check_transfer(b, slots, n, blob_dev, offsets, heads, who, err);
   if (rc) return rc;
   if (n == 0) return SG_OK;
   // (payloads that overlap would make two workgroups write the same words)
@@ -1057,7 +1216,9 @@ int st_export(StBank* b, const int32_t* slots, int32_t n, void* blob_dev, const 
 int st_import(StBank* b, const int32_t* slots, int32_t n, const void* blob_dev, const int64_t* offsets, const sg_stream_head& sig,
               const sg_stream_head* heads, hipStream_t st, std::string* err) {
   const char* who = "sg_stream_import";
-  int rc = st_check_transfer(b, slots, n, blob_dev, offsets, heads, who, err);
+  int rc = box_refuses(b, who, "a kind-1 header cannot tell the two non-stationary gates apart", err);
+  if (rc) return rc;
+  rc = st_check_transfer(b, slots, n, blob_dev, offsets, heads, who, err);
   if (rc) return rc;
   if (n == 0) return SG_OK;
   char m[200];

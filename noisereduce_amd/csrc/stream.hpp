@@ -15,6 +15,11 @@
 //   mk     [unit][RB][FS]      raw sigmoid mask rows, float32 -- float64 in an exact bank -- (RB = 2 nt + 1 + L + frames of
 //                              max_block)
 // and its ring is RC = W + (nt + L + 1) H samples.
+// A box bank (a handle of variant T: TorchGate's non-stationary gate, the level a moving mean over K = Lb + 1 + L frames) is
+// a non-stationary bank without fst and without the fwd half of fa:
+//   fa     [unit][RF][FS]      A = |X| of the last transformed frames AND of the Lb frames behind the next one to decide,
+//                              float64 (RF = L + Lb + 1 + frames of max_block)
+// (DESIGN section 13h).
 // An adaptive bank (the stationary gate with the noise profile learnt from the stream itself) holds no thr / T2 but
 //   nst    [unit][3][FS]       Wn, mu, M2: weight sum, mean and weighted squared deviations of the floored dB values, float64
 // (unit = slot * channels + channel).  Of a slot the bank remembers n, the samples received (and which carry buffer is
@@ -47,13 +52,15 @@ struct StAdaptive {
 
 // ns: a non-stationary bank with `lookahead` frames (the handle must be non-stationary); else lookahead is ignored.
 // ad: non-null for an adaptive bank (the handle must be stationary)
+// box_k: non-zero for a box bank (TorchGate's non-stationary gate: the level is the moving mean over box_k frames; ns must be
+// set, `lookahead` is ignored: it is box_k - 1 - (box_k - 1) / 2; the handle may be of variant T, its window is re-embedded)
 // exact: float64 segments (and, non-stationary, float64 mk rows): the bank takes and returns every sample type, each
 // exactly (sg_stream_create_ex)
 int st_create(StBank** out, const RgCtx& c, int32_t n_slots, int32_t channels, int64_t max_block, bool ns, int32_t lookahead,
-              const StAdaptive* ad, bool exact, std::string* err);
+              const StAdaptive* ad, bool exact, std::string* err, int32_t box_k = 0);
 // bytes of device state st_create allocates for such a bank (host arithmetic)
 int64_t st_state_bytes(const RgCtx& c, bool ns, int64_t n_slots, int64_t channels, int64_t max_block, int64_t L,
-                       bool adaptive = false, bool exact = false);
+                       bool adaptive = false, bool exact = false, int32_t box_k = 0);
 // adaptive banks: the threshold (dB) after the last decided frame of every channel of `slot`, channels x F values, NaN
 // where no frame was decided yet.  Synchronises the stream.
 int st_noise_profile(StBank* b, int32_t slot, double* thresh_host, hipStream_t st, std::string* err);

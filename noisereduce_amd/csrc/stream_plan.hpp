@@ -43,6 +43,10 @@ struct StFeatOut {
 struct StGeo {
   int64_t n, F, FS, W, H, nt, L, RC, wpr, C;   // n_fft, bins, padded bins, window, hop, time half width, lookahead, ring, ...
   bool ns, ad, fixed, exact;
+  // a box bank (TorchGate's non-stationary gate: the level is a moving mean over K = Lb + 1 + L frames): a non-stationary
+  // bank whose decide step also reads Lb frames BEHIND the one it decides; 0 / false for every other bank
+  int64_t Lb;
+  bool box;
 };
 // kind: SG_STREAM_FIXED / _NONSTATIONARY / _ADAPTIVE; the lookahead counts for a non-stationary bank only
 inline StGeo st_make_geo(int64_t n_fft, int64_t F, int64_t FS, int64_t W, int64_t H, int64_t nt, int64_t lookahead, int64_t C,
@@ -54,6 +58,16 @@ inline StGeo st_make_geo(int64_t n_fft, int64_t F, int64_t FS, int64_t W, int64_
   g.L = g.ns ? lookahead : 0;
   g.RC = W + (nt + g.L + 1) * H;
   g.wpr = (F + 63) / 64;
+  return g;
+}
+// the box bank of a moving mean over K frames, frames [t - (K - 1) / 2, t - (K - 1) / 2 + K): look-back Lb = (K - 1) / 2,
+// lookahead L = K - 1 - Lb
+inline StGeo st_make_geo_box(int64_t n_fft, int64_t F, int64_t FS, int64_t W, int64_t H, int64_t nt, int64_t K, int64_t C,
+                             bool exact) {
+  const int64_t lo = (K - 1) / 2;
+  StGeo g = st_make_geo(n_fft, F, FS, W, H, nt, K - 1 - lo, C, SG_STREAM_NONSTATIONARY, exact);
+  g.Lb = lo;
+  g.box = true;
   return g;
 }
 inline StGeo st_geo(const sg_stream_head& hd) {
@@ -91,7 +105,7 @@ struct StLive {
   int64_t car_n;             // carry positions [E, E + car_n)
   int64_t row_lo, bit_rows;  // bit rows [row_lo, td] (stationary / adaptive)
   int64_t mk_rows;           // sigmoid rows [row_lo, ts] (non-stationary)
-  int64_t fa_rows;           // A / fwd rows (ts, td] (non-stationary)
+  int64_t fa_rows;           // A / fwd rows (ts, td] (non-stationary); A rows (ts - Lb, td] of a box bank
 };
 inline StLive st_live(const StGeo& g, int64_t n) {
   const int64_t h = g.W / 2;
@@ -104,7 +118,7 @@ inline StLive st_live(const StGeo& g, int64_t n) {
   v.row_lo = std::max<int64_t>(0, v.ta + 1 - g.nt);
   v.bit_rows = g.ns ? 0 : v.td - v.row_lo + 1;
   v.mk_rows = g.ns ? v.ts - v.row_lo + 1 : 0;
-  v.fa_rows = g.ns ? v.td - v.ts : 0;
+  v.fa_rows = g.ns ? v.td - std::max<int64_t>(-1, v.ts - g.Lb) : 0;
   return v;
 }
 // 8-byte words of a float mask row / a double one
@@ -114,7 +128,8 @@ inline int64_t mk_words(const StGeo& g) { return g.exact ? g.FS : g.FS / 2; }
 inline int64_t st_payload_words(const StGeo& g, int64_t n) {
   const StLive v = st_live(g, n);
   int64_t per = v.ring_n + v.car_n;
-  if (g.ns) per += g.FS + v.fa_rows * 2 * g.FS + v.mk_rows * mk_words(g);
+  if (g.box) per += v.fa_rows * g.FS + v.mk_rows * mk_words(g);   // (no snapshot of a box bank yet: sg_stream_export refuses)
+  else if (g.ns) per += g.FS + v.fa_rows * 2 * g.FS + v.mk_rows * mk_words(g);
   else per += g.FS + v.bit_rows * g.wpr;
   if (g.ad) per += 3 * g.FS;
   return (g.fixed ? 2 * g.FS : 0) + g.C * per;
@@ -150,13 +165,15 @@ inline StLayout st_layout(const StGeo& g, int64_t n_slots, int64_t max_block) {
   y.RC = g.RC;
   // (a flush decides the L frames a push holds back on top of the block's own: the mask rows are L deeper for it)
   y.RB = 2 * g.nt + 1 + g.L + mf;
-  y.RF = g.L + 1 + mf;
+  // (the A rows: the L + 1 a decision reads ahead, the Lb it reads behind -- a box bank's alone -- and the step's own)
+  y.RF = g.L + g.Lb + 1 + mf;
   y.RB_ring = std::min<int64_t>(INT32_MAX, y.RB);
   y.ring = nu * y.RC * 8;
   y.carry = nu * 2 * g.W * 8;
   if (g.ns) {
-    y.fst = nu * g.FS * 8;
-    y.fa = nu * y.RF * 2 * g.FS * 8;
+    // (a box bank carries no forward pass: no fst, and its fa rows hold A alone)
+    y.fst = g.box ? 0 : nu * g.FS * 8;
+    y.fa = nu * y.RF * (g.box ? 1 : 2) * g.FS * 8;
     y.mk = nu * y.RB * g.FS * (g.exact ? 8 : 4);
   } else {
     y.rmax = nu * g.FS * 8;
@@ -200,7 +217,8 @@ inline StAdvance st_advance(const StGeo& g, int64_t n0, int64_t n_samples, bool 
   if (flush) {
     const int64_t T = (a.n1 + 2 * h - g.W) / g.H + 1;
     a.Tend = T;
-    a.Lout = (T - 1) * g.H + g.W - 2 * h;
+    // (a box bank has no zero tail: its last N mod H samples are the overlap-add over the window envelope continued)
+    a.Lout = g.box ? a.n1 : (T - 1) * g.H + g.W - 2 * h;
     a.td1 = a.ts1 = a.ta1 = T - 1;
     a.E1 = a.n1;
   } else {

@@ -117,8 +117,37 @@ stored as ``F`` complex bins (sg_stream_set_filterbank / sg_stream_push_features
 and the mask of ``push_spectrum``, float64 sums in a fixed order rounded once, bitwise independent of the block split, the
 slot, the other streams and the kind of the earlier steps.  The filterbank belongs to the bank, not to a stream's state.
 
-Out of scope: spectrum-only steps that skip the inverse transform, gradients through a stream, ``TorchGate``, collectives between GPUs (a state's bytes are the transport), and ``n_fft`` other than a power
-of two from 256 to 4096 (``ValueError``).
+``algorithm="torchgate"`` (with ``stationary=False``; or ``StreamBank.from_torchgate(tg, n_streams)``) streams the other gate
+of the package, ``TorchGate(nonstationary=True)``, and this one EQUALS the offline gate: there is no designed difference.  Its
+level is a moving mean over ``K = n_movemean_nonstationary`` frames that reads ``lo = (K - 1) // 2`` frames behind a frame and
+``L = K - 1 - lo`` ahead of it and nothing else, so a lookahead of ``L`` frames is all it needs.  The definition, with the
+float32 Hann table ``TorchGate`` hands the engine and ``A = |X|`` of the unscaled transform:
+
+* frame ``t`` is the frame of samples ``[t H - h, t H - h + W)``, ``W`` even: the samples ``torch.stft(center=True)`` windows
+  (for ``W < n_fft`` torch centres the window in the ``n_fft`` frame and the bank puts it first: another phase, which audio,
+  mask and features do not see);
+* ``S[f, t] = (1 / K) * sum of A[f, q]`` over ``q`` in ``[t - lo, t - lo + K)`` cut to ``[0, T)``, every sum taken afresh in
+  ascending ``q`` in float64, ``T - 1`` the stream's last frame; ``raw = sigmoid(((A - S) / S - n_thresh_nonstationary) /
+  temp_coeff_nonstationary)``, ``0 / 0`` = NaN as offline;
+* the mask is ``prop_decrease * (raw - 1) + 1`` smoothed with the zero-padded triangle over the stream's own ``(F, T)`` field
+  -- ``prop_decrease`` FIRST, the value outside the field 0: TorchGate's order, not the scipy gate's;
+* a frame is decided once frame ``t + L`` is in, or at the flush: ``lookahead_frames == L``, ``emitted(n, W, H, nt + L)``,
+  ``latency_samples = W + (nt + L + 1) * H`` (``K = 20``, n_fft 1024 at 16 kHz: 14 frames, 288 ms);
+* after the flush a stream of ``N >= 2 W`` samples has emitted ``N`` samples: the first ``H * (N // H)`` are
+  ``TorchGate(...)(x[None])[0]``, the other ``N mod H`` the same overlap-add over the window envelope continued (no zero tail);
+* ``push_features(..., scale="torch")`` / ``flush_features`` return, frame by frame, ``TorchGate.gated_filterbank(x, fb, power,
+  log, eps)`` of the whole signal, and ``return_mask=True`` the mask above (``scale="scipy"``: ``ValueError``);
+* output, mask and features are bitwise independent of the block split, the slot, the other streams and the kind of the
+  earlier steps; ``precision="float64"`` works as for the non-stationary bank (float64 mask rows, all four sample types).
+
+Such a bank takes no noise profile, no ``lookahead_ms`` and none of the scipy gate's ``time_constant_s`` /
+``thresh_n_mult_nonstationary`` / ``sigmoid_slope_nonstationary``; ``snapshot`` / ``restore`` (a state header of kind 1 could
+not tell the two non-stationary gates apart, and its format is pinned) and ``push_spectrum`` (it would have to take
+``torch.stft``'s phase and scale) raise ``ValueError`` before any device work.
+
+Out of scope: spectrum-only steps that skip the inverse transform, gradients through a stream, ``TorchGate``'s stationary gate
+(its statistics need ``xn`` or the whole recording) and ``push_spectrum`` / snapshots of its non-stationary one, collectives
+between GPUs (a state's bytes are the transport), and ``n_fft`` other than a power of two from 256 to 4096 (``ValueError``).
 """
 import ctypes
 
@@ -162,19 +191,30 @@ def iir_coefficient(time_constant_s, sr, H):
     return (np.sqrt(1 + 4 * t_frames ** 2) - 1) / (2 * t_frames ** 2)
 
 
-def state_bytes(n_units, n_fft, W, H, nt, L, max_block, stationary, noise_from_stream=False, exact=False):
+def box_frames(K):
+    """``(lo, L)`` of TorchGate's moving mean over ``K`` frames, frames ``t - lo .. t + L`` (``conv1d(padding="same")``
+    puts the shorter half of an even ``K`` behind the frame)."""
+    lo = (K - 1) // 2
+    return lo, K - 1 - lo
+
+
+def state_bytes(n_units, n_fft, W, H, nt, L, max_block, stationary, noise_from_stream=False, exact=False, movemean=0):
     """Device memory a bank holds between steps (sg_stream_state_bytes_ex's arithmetic; DESIGN section 13's state table).
     ``noise_from_stream``: the three float64 rows of noise statistics per unit of an adaptive bank.  ``exact``: the
-    sigmoid rows of a non-stationary bank at 8 bytes (nothing else of the state differs)."""
+    sigmoid rows of a non-stationary bank at 8 bytes (nothing else of the state differs).  ``movemean``: ``K`` of an
+    ``algorithm="torchgate"`` bank (``stationary=False``; ``L`` must be ``box_frames(K)[1]``): its ``|X|`` rows reach
+    ``(K - 1) // 2`` frames further back, and it keeps neither a forward level nor the forward rows."""
     F = n_fft // 2 + 1
     FS = (F + 15) // 16 * 16
     mf = (max_block + W // 2) // H + 3
-    per = (W + (nt + L + 1) * H) * 8 + 2 * W * 8 + FS * 8
+    per = (W + (nt + L + 1) * H) * 8 + 2 * W * 8
     RB = 2 * nt + 1 + L + mf
     if stationary:
-        per += RB * ((F + 63) // 64) * 8
+        per += FS * 8 + RB * ((F + 63) // 64) * 8
+    elif movemean:
+        per += (L + box_frames(movemean)[0] + 1 + mf) * FS * 8 + RB * FS * (8 if exact else 4)
     else:
-        per += (L + 1 + mf) * 2 * FS * 8 + RB * FS * (8 if exact else 4)
+        per += FS * 8 + (L + 1 + mf) * 2 * FS * 8 + RB * FS * (8 if exact else 4)
     if noise_from_stream:
         per += 3 * FS * 8
     return n_units * per
@@ -243,6 +283,16 @@ class StreamState:
         return cls(head, payload)
 
 
+class _Default:
+    """A default that can be told from the same value given explicitly (it shows as the value in a signature)."""
+
+    def __init__(self, value):
+        self.value = value
+
+    def __repr__(self):
+        return repr(self.value)
+
+
 def _widths(sr, n_fft, H, freq_mask_smooth_hz, time_mask_smooth_ms):
     """(n_grad_freq, n_grad_time, smooth) with the reference's errors (SpectralGate._generate_mask_smoothing_filter)."""
     if freq_mask_smooth_hz is None and time_mask_smooth_ms is None:
@@ -262,7 +312,9 @@ def _widths(sr, n_fft, H, freq_mask_smooth_hz, time_mask_smooth_ms):
 class StreamBank:
     """``n_streams`` live streams of ``channels`` channels each, gated with the stationary gate or, ``stationary=False``,
     the non-stationary one with ``lookahead_ms`` of lookahead (module docstring; no noise profile then, and
-    ``time_constant_s``, ``thresh_n_mult_nonstationary``, ``sigmoid_slope_nonstationary`` as ``reduce_noise``).
+    ``time_constant_s``, ``thresh_n_mult_nonstationary``, ``sigmoid_slope_nonstationary`` as ``reduce_noise``).  ``algorithm="torchgate", stationary=False`` streams ``TorchGate``'s non-stationary gate instead,
+    exactly (``n_movemean_nonstationary``, ``n_thresh_nonstationary``, ``temp_coeff_nonstationary`` as ``TorchGate``;
+    ``from_torchgate`` reads them from a module; module docstring for what such a bank refuses).
 
     The noise profile is fixed per stream: ``y_noise`` (a noise clip, ``(n,)`` or ``(C, n)``; channel mean, whole clip,
     the float64 statistics ``reduce_noise`` uses) or ``thresholds_db`` (``n_fft // 2 + 1`` dB values) sets it for every
@@ -294,14 +346,52 @@ class StreamBank:
     def __init__(self, sr, n_streams, channels=1, y_noise=None, thresholds_db=None, prop_decrease=1.0,
                  n_std_thresh_stationary=1.5, freq_mask_smooth_hz=500, time_mask_smooth_ms=50, n_fft=1024,
                  win_length=None, hop_length=None, max_block=None, device="cuda", stationary=True, lookahead_ms=0.0,
-                 time_constant_s=2.0, thresh_n_mult_nonstationary=2, sigmoid_slope_nonstationary=10,
+                 time_constant_s=_Default(2.0), thresh_n_mult_nonstationary=_Default(2),
+                 sigmoid_slope_nonstationary=_Default(10),
                  max_state_bytes=MAX_STATE_BYTES, noise_from_stream=False, noise_memory_s=None, noise_learn_s=None,
-                 precision=None):
+                 precision=None, algorithm="scipy", n_movemean_nonstationary=20, n_thresh_nonstationary=1.3,
+                 temp_coeff_nonstationary=0.1):
         if precision not in (None, "float32", "float64"):
             raise ValueError(f"StreamBank: precision must be None, 'float32' or 'float64' (got {precision!r})")
         self.exact = precision == "float64"
+        if algorithm not in ("scipy", "torchgate"):
+            raise ValueError(f"StreamBank: algorithm must be 'scipy' or 'torchgate' (got {algorithm!r})")
+        self.algorithm = algorithm
         stationary = bool(stationary)
         noise_from_stream = bool(noise_from_stream)
+        # (the scipy gate's parameters: given explicitly they are an error for algorithm="torchgate", which has its own)
+        scipy_only = dict(time_constant_s=time_constant_s, thresh_n_mult_nonstationary=thresh_n_mult_nonstationary,
+                          sigmoid_slope_nonstationary=sigmoid_slope_nonstationary)
+        time_constant_s, thresh_n_mult_nonstationary, sigmoid_slope_nonstationary = (
+            v.value if isinstance(v, _Default) else v for v in scipy_only.values())
+        self.movemean = 0
+        if algorithm == "torchgate":
+            if stationary:
+                raise ValueError("StreamBank: algorithm='torchgate' streams TorchGate's non-stationary gate: pass "
+                                 "stationary=False (its stationary gate needs the whole recording's statistics or xn)")
+            if y_noise is not None or thresholds_db is not None or noise_from_stream:
+                raise ValueError("StreamBank: algorithm='torchgate' takes no noise profile (y_noise / thresholds_db / "
+                                 "noise_from_stream)")
+            if lookahead_ms:
+                raise ValueError("StreamBank: algorithm='torchgate' takes no lookahead_ms: n_movemean_nonstationary decides "
+                                 "the lookahead, K - 1 - (K - 1) // 2 frames")
+            given = [k for k, v in scipy_only.items() if not isinstance(v, _Default)]
+            if given:
+                raise ValueError(f"StreamBank: {', '.join(given)} belong to algorithm='scipy' (TorchGate's gate takes "
+                                 f"n_movemean_nonstationary, n_thresh_nonstationary, temp_coeff_nonstationary)")
+            if isinstance(n_movemean_nonstationary, bool) or int(n_movemean_nonstationary) != n_movemean_nonstationary or \
+                    not 1 <= n_movemean_nonstationary <= MAX_LOOKAHEAD_FRAMES:
+                raise ValueError(f"StreamBank: n_movemean_nonstationary must be an integer from 1 to {MAX_LOOKAHEAD_FRAMES} "
+                                 f"(got {n_movemean_nonstationary!r})")
+            if not temp_coeff_nonstationary > 0:
+                raise ValueError("StreamBank: temp_coeff_nonstationary must be positive")
+            if win_length is not None and int(win_length) % 2:
+                raise ValueError(f"StreamBank: algorithm='torchgate' needs an even win_length (got {win_length}): the "
+                                 f"stream's frames would not be the samples torch.stft windows")
+            self.movemean = int(n_movemean_nonstationary)
+        elif (n_movemean_nonstationary, n_thresh_nonstationary, temp_coeff_nonstationary) != (20, 1.3, 0.1):
+            raise ValueError("StreamBank: n_movemean_nonstationary, n_thresh_nonstationary and temp_coeff_nonstationary "
+                             "belong to algorithm='torchgate'")
         if noise_from_stream and (y_noise is not None or thresholds_db is not None):
             raise ValueError("StreamBank: noise_from_stream learns the profile; give no y_noise / thresholds_db with it")
         if noise_from_stream and not stationary:
@@ -351,10 +441,12 @@ class StreamBank:
             if self.noise_learn_frames < 1:
                 raise ValueError(f"StreamBank: noise_learn_s={noise_learn_s!r} is shorter than one hop ({H / sr:g} s)")
         self.lookahead_frames = 0 if stationary else int(lookahead_ms / ((H / sr) * 1000))
+        if self.movemean:      # the part of the moving mean ahead of the frame
+            self.lookahead_frames = box_frames(self.movemean)[1]
         self._lag = self.nt + self.lookahead_frames      # frames between the last one inside the audio and the last applied
         self.latency_samples = W + (self._lag + 1) * H
         self.state_bytes = state_bytes(self.n_streams * self.channels, n_fft, W, H, self.nt, self.lookahead_frames,
-                                       self.max_block, stationary, noise_from_stream, self.exact)
+                                       self.max_block, stationary, noise_from_stream, self.exact, self.movemean)
         if not stationary and self.state_bytes > max_state_bytes:
             raise ValueError(f"StreamBank: {self.n_streams} x {self.channels} streams with lookahead_frames="
                              f"{self.lookahead_frames} and max_block={self.max_block} need {self.state_bytes} bytes of "
@@ -375,11 +467,31 @@ class StreamBank:
                              n_grad_freq=nf if smooth else 1, n_grad_time=nt if smooth else 1, smooth_mask=smooth,
                              chunk_size=_NONE_CHUNK, padding=0, prop_decrease=prop_decrease,
                              n_std_thresh=n_std_thresh_stationary, top_db=80.0, ddof=0)
-        if not stationary:
+        if self.movemean:      # the handle TorchGate._gate_for makes: variant T, the float32 Hann table, 1 / temp as slope
+            self._gate_kw = dict(variant=_ffi.SG_VARIANT_T, stationary=False, n_fft=n_fft, win_length=W, hop_length=H,
+                                 n_grad_freq=nf if smooth else 1, n_grad_time=nt if smooth else 1, smooth_mask=smooth,
+                                 prop_decrease=prop_decrease, n_std_thresh=n_std_thresh_stationary, top_db=40.0, ddof=1,
+                                 n_movemean=self.movemean, nonstat_thresh=n_thresh_nonstationary,
+                                 nonstat_slope=1.0 / temp_coeff_nonstationary,
+                                 window=torch.hann_window(W).double().numpy())
+        elif not stationary:
             self._gate_kw.update(iir_b=float(iir_coefficient(time_constant_s, sr, H)),
                                  nonstat_thresh=thresh_n_mult_nonstationary, nonstat_slope=sigmoid_slope_nonstationary)
         if y_noise is not None or thresholds_db is not None:
             self.set_noise(range(self.n_streams), y_noise=y_noise, thresholds_db=thresholds_db)
+
+    @classmethod
+    def from_torchgate(cls, tg, n_streams, channels=1, max_block=None, precision=None, device="cuda"):
+        """The bank that streams ``tg``, a ``TorchGate(nonstationary=True)`` module: every gate parameter is read from the
+        module (a stationary one: ``ValueError``).  The concatenated output of a stream is ``tg(x[None])[0]``."""
+        if not getattr(tg, "nonstationary", False):
+            raise ValueError("StreamBank.from_torchgate: the module is stationary; only TorchGate(nonstationary=True) "
+                             "can be streamed")
+        return cls(tg.sr, n_streams, channels=channels, max_block=max_block, precision=precision, device=device,
+                   algorithm="torchgate", stationary=False, prop_decrease=tg.prop_decrease, n_fft=tg.n_fft,
+                   win_length=tg.win_length, hop_length=tg.hop_length, freq_mask_smooth_hz=tg.freq_mask_smooth_hz,
+                   time_mask_smooth_ms=tg.time_mask_smooth_ms, n_movemean_nonstationary=tg.n_movemean_nonstationary,
+                   n_thresh_nonstationary=tg.n_thresh_nonstationary, temp_coeff_nonstationary=tg.temp_coeff_nonstationary)
 
     def _ensure(self):
         """The engine handle and the bank's device state, created at the first call that needs the GPU (arguments are
@@ -387,7 +499,10 @@ class StreamBank:
         if self._bank is None:
             self._gate = _ffi.Gate(self._device_arg, **self._gate_kw)
             self.device = self._gate.device
-            if self.exact:
+            if self.movemean:      # (the handle's n_movemean decides the lookahead: the descriptor's stays 0)
+                self._bank = self._gate.stream_create_ex(_ffi.Gate.stream_desc(
+                    self.n_streams, self.channels, self.max_block, _ffi.SG_STREAM_NONSTATIONARY, 0, exact=self.exact))
+            elif self.exact:
                 kind = (_ffi.SG_STREAM_ADAPTIVE if self.noise_from_stream else
                         _ffi.SG_STREAM_FIXED if self.stationary else _ffi.SG_STREAM_NONSTATIONARY)
                 self._bank = self._gate.stream_create_ex(_ffi.Gate.stream_desc(
@@ -515,6 +630,9 @@ class StreamBank:
             raise ValueError("StreamBank: eps is NaN")
         if scale not in ("scipy", "torch"):
             raise ValueError(f"StreamBank: scale must be 'scipy' or 'torch' (got {scale!r})")
+        if self.movemean and scale != "torch":
+            raise ValueError("StreamBank: an algorithm='torchgate' bank has torch.stft's unscaled transform only: pass "
+                             "scale='torch'")
         if self._fb is None:
             raise ValueError("StreamBank: no filterbank set (set_filterbank)")
         # (0.0: the bank's own 1 / sum(window), the very factor push_spectrum applies; 1.0: the unscaled transform)
@@ -692,6 +810,11 @@ class StreamBank:
         (``frames_applied`` of ``received(slot)``; host arithmetic)."""
         return frames_applied(self._n[self._slots(slot)[0]], self.win_length, self.hop_length, self._lag)
 
+    def _not_torchgate(self, what, why):
+        """What an ``algorithm="torchgate"`` bank refuses, before any device work."""
+        if self.movemean:
+            raise ValueError(f"StreamBank: {what} is not available on an algorithm='torchgate' bank ({why})")
+
     @staticmethod
     def _block_map(blocks, who):
         """{slot: block} of a mapping or of (slot, block) pairs; a slot listed twice is an error."""
@@ -709,11 +832,13 @@ class StreamBank:
         ``(..., k, F)`` with the bins contiguous and returned as the transposed view (``torch.stft``'s layout).  complex64
         for a float32 block, complex128 for float64 / int16 / int32, whatever the other streams of the step are; ``mask``
         has ``Y``'s shape and its real type.  Same four launches, no host synchronisation for device tensors."""
+        self._not_torchgate("push_spectrum", "the spectrum would need torch.stft's phase and scale")
         return self._step(self._block_map(blocks, "step"), flush=False, spectrum=True, return_mask=bool(return_mask))
 
     def flush_spectrum(self, slots, blocks=None, return_mask=False):
         """``flush`` that also reports every remaining frame, up to ``T = (N + 2 (W // 2) - W) // H + 1`` of a stream of
         ``N`` samples: ``{slot: (tail, Y[, mask])}``."""
+        self._not_torchgate("flush_spectrum", "the spectrum would need torch.stft's phase and scale")
         slots = self._slots(slots)
         if len(set(slots)) != len(slots):
             raise ValueError("StreamBank: a slot appears twice in one flush")
@@ -782,6 +907,7 @@ class StreamBank:
 
     def state_bytes_of(self, slot):
         """Bytes of ``slot``'s state payload right now (host arithmetic from ``received(slot)``)."""
+        self._not_torchgate("state_bytes_of", "it has no snapshots")
         return state_payload_bytes(self._n[self._slots(slot)[0]], self.n_fft, self.win_length, self.hop_length, self.nt,
                                    self.lookahead_frames, self.channels, _KINDS[self._signature()["kind"]], self.exact)
 
@@ -789,6 +915,7 @@ class StreamBank:
         """``{slot: StreamState}`` of the listed slots, without disturbing them: one launch on the current stream, no host
         synchronisation; the payloads are views into one uint8 device buffer.  A slot that has received nothing is valid
         (restoring it is ``reset``, plus the slot's noise profile if it had one)."""
+        self._not_torchgate("snapshot", "a state header of kind 1 cannot tell the two non-stationary gates apart")
         slots = self._slots(slots)
         if len(set(slots)) != len(slots):
             raise ValueError("StreamBank: a slot appears twice in one snapshot")
@@ -813,6 +940,7 @@ class StreamBank:
         profile is the source's).  The states may come from this bank or any bank with the same signature, whatever its
         ``n_streams``, ``max_block``, device or slot, or from ``StreamState.from_bytes`` (uploaded here).  Every argument is
         checked before any device work; one launch on the current stream, no host synchronisation for device states."""
+        self._not_torchgate("restore", "a state header of kind 1 cannot tell the two non-stationary gates apart")
         items = []
         for s, state in (states.items() if hasattr(states, "items") else states):      # a mapping, or (slot, state) pairs
             s = self._slots(s)[0]
@@ -882,7 +1010,7 @@ class StreamBank:
 
 class StreamGate:
     """One stream: ``push(block) -> out``, ``flush() -> tail`` (a ``StreamBank`` of one slot; same arguments,
-    ``stationary=False``, ``noise_from_stream=True`` and ``precision="float64"`` included)."""
+    ``stationary=False``, ``noise_from_stream=True``, ``precision="float64"`` and ``algorithm="torchgate"`` included)."""
 
     def __init__(self, sr, y_noise=None, **kw):
         self.bank = StreamBank(sr, 1, y_noise=y_noise, **kw)
